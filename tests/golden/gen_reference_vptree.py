@@ -14,6 +14,11 @@ absent) and then lets the reference do everything else itself:
 
 The fixture holds inputs and the reference's outputs only (data, no source). tests/test_reference_fixture.py replays
 the inputs through this repo's facade / adapter / converter and compares. Run:  python tests/golden/gen_reference_vptree.py
+
+`--live` writes tests/golden/reference_live.npz instead: the reference's pipeline run on a second library (its own
+tree, and this repo's facade swapped in) and the shape_vptree table after every file its own DedupeDb inserts -- what
+test_reference_fixture.py::test_reference_pipeline_runs_unchanged_on_the_facade and
+test_vptree_facade.py::test_reference_tree_and_facade_alternate_on_one_database_without_losing_a_hash replay.
 """
 import json
 import os
@@ -231,5 +236,66 @@ def main():
     print("wrote", path, {k: (v.shape if hasattr(v, "shape") else v) for k, v in out.items()})
 
 
+TREE_COLUMNS = "phash_id, parent_id, radius, inner_id, inner_population, outer_id, outer_population"
+
+
+def pack(blist):
+    lens = np.array([len(b) for b in blist], dtype=np.int64)
+    return np.frombuffer(b"".join(blist), dtype=np.uint8), lens
+
+
+def main_live():
+    import hvd_amd.vptree as our_vptree
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_sqlite_adapter import OracleMatcher
+    from test_vptree_facade import dedupe_keep_order
+
+    out = {}
+    # ---- the reference's pipeline loop on a second library: its own tree, then this repo's facade swapped in ---------
+    blobs = build_library(n_videos=60, seed=77)
+    names = [f"{v:064x}" for v in range(len(blobs))]
+    rel_tree, ret_tree, cache_tree = run_reference_pipeline(blobs, names, 50.0)
+    rel_fac, ret_fac, cache_fac = run_reference_pipeline(
+        blobs, names, 50.0, tree_factory=lambda db: our_vptree.VpTreeManager(db, matcher=OracleMatcher(O)))
+    out["pipe_blobs_data"], out["pipe_blobs_len"] = pack(blobs)
+    out["pipe_pairs_reference_tree"] = np.array(rel_tree).reshape(-1, 2)
+    out["pipe_return_reference_tree"] = np.int64(ret_tree)
+    out["pipe_cache_reference_tree"] = np.array(cache_tree, dtype=np.int64)
+    out["pipe_pairs_facade"] = np.array(rel_fac).reshape(-1, 2)
+    out["pipe_return_facade"] = np.int64(ret_fac)
+    out["pipe_cache_facade"] = np.array(cache_fac, dtype=np.int64)
+
+    # ---- the reference's own DedupeDb inserting files one by one: shape_vptree after every insertion ------------------
+    blobs = dedupe_keep_order(build_library(n_videos=50, seed=123))
+    random.seed(4)  # the reference's tree samples vantage points with the global RNG when it rebalances
+    vptree.TemporaryIntegerTableNameCache()
+    states = []
+    with tempfile.TemporaryDirectory() as tmp:
+        db = DedupeDB.DedupeDb(Path(tmp), "a.sqlite")
+        db.init_connection()
+        db.create_tables()
+        for k, b in enumerate(blobs):
+            name = f"{k:064x}"
+            db.add_file(name)
+            db.add_perceptual_hash(b)
+            db.associate_file_with_perceptual_hash(name, b)
+            states.append(db.execute(f"SELECT {TREE_COLUMNS} FROM shape_vptree ORDER BY phash_id").fetchall())
+        db.commit()
+        vptree.TemporaryIntegerTableNameCache()
+        tree = vptree.VpTreeManager(db)
+        search = [sorted(tree.search_file(k + 1, 51)) for k in range(len(blobs))]
+        db.close()
+    out["alt_blobs_data"], out["alt_blobs_len"] = pack(blobs)
+    out["alt_tree_states"] = np.array(json.dumps(states))  # JSON: NULL columns stay null
+    out["alt_search_51"] = np.array(json.dumps(search))
+    out["meta"] = np.array(json.dumps({
+        "reference_version": DedupeDB.__version__, "matcher": "oracle.match_two, comparator le, reduction min, tolerance 31",
+        "generator": "tests/golden/gen_reference_vptree.py --live"}))
+    path = os.path.join(HERE, "reference_live.npz")
+    np.savez_compressed(path, **out)
+    print("wrote", path, {k: (v.shape if hasattr(v, "shape") else v) for k, v in out.items()})
+
+
 if __name__ == "__main__":
-    main()
+    main_live() if "--live" in sys.argv[1:] else main()

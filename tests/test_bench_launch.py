@@ -11,6 +11,7 @@ import sys
 import threading
 import time
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -178,3 +179,63 @@ def _check_breakdown(out, steps, world):
     assert rt["devices"] and "gfx950" in rt["devices"][0]["arch"]
     assert [r["rank"] for r in rt["ranks"]] == list(range(world)) and all("device" in r and "pci" in r for r in rt["ranks"])
     assert rt["xgmi_or_pcie"] and rt["exchange"] == out["config"]["exchange"]
+
+
+def _bench_module():
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("hvd_bench", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_the_same_rows_every_time(tmp_path, monkeypatch):
+    """--dump-outputs: one float64 array per pair field; over the size limit a fixed seeded sample, still in (i, j) order."""
+    from hvd_amd._lib import PAIR_DTYPE
+
+    bench = _bench_module()
+    merged = np.zeros(5000, dtype=PAIR_DTYPE)
+    merged["i"] = np.arange(5000) // 10
+    merged["j"] = 100_000 + np.arange(5000)
+    merged["dist"] = np.arange(5000) % 32
+    info = bench.dump_outputs(str(tmp_path / "all"), merged)
+    assert info["records"] == info["records_written"] == 5000
+    for f in ("i", "j", "dist"):
+        a = np.load(tmp_path / "all" / f"pairs_{f}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, merged[f].astype(np.float64))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 24 * 1000)
+    a = bench.dump_outputs(str(tmp_path / "s1"), merged)
+    b = bench.dump_outputs(str(tmp_path / "s2"), merged)
+    assert a["records_written"] == b["records_written"] == 1000
+    for f in ("i", "j", "dist"):
+        x, y = np.load(tmp_path / "s1" / f"pairs_{f}.npy"), np.load(tmp_path / "s2" / f"pairs_{f}.npy")
+        assert np.array_equal(x, y)
+    j = np.load(tmp_path / "s1" / "pairs_j.npy")
+    assert (np.diff(j) > 0).all()  # rows of the sample keep the (i, j) order (j is increasing in this array)
+    assert sum(os.path.getsize(tmp_path / "s1" / f"pairs_{f}.npy") for f in ("i", "j", "dist")) < 24 * 1000 + 3 * 256
+
+
+def test_bench_refuses_zero_timed_steps():
+    r = _run_bench(["--gpus", "1", "--steps", "0", "--warmup", "0"], {}, timeout=120)
+    assert r.returncode == 2 and b"--steps" in r.stderr and r.stdout.strip() == b""
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_oracles_pairs(gpu, oracle, tmp_path):
+    """One GPU, `--steps 3`: three timed steps, one JSON line, and the dumped pair list of the last step is the CPU
+    oracle's for the same seeded DB."""
+    from hvd_amd import synth
+
+    r = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-extras", "--hashes", "100000", "--frames", "2000",
+                    "--dump-outputs", str(tmp_path)], {}, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and len(out["per_rank"][0]["steps"]["step_ms"]) == 3
+    want = oracle.allpairs(synth.hash_db(100_000, seed=3)[0], 31)
+    assert out["dump_outputs"]["records"] == len(want) == out["config"]["pairs_found"] > 0
+    for f in ("i", "j", "dist"):
+        got = np.load(tmp_path / f"pairs_{f}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, want[f].astype(np.float64)), f

@@ -8,6 +8,7 @@ import time
 import numpy as np
 import pytest
 
+from conftest import load_golden
 from test_sqlite_adapter import SCHEMA, OracleMatcher, brute_force, build_db
 
 
@@ -303,75 +304,48 @@ def dedupe_keep_order(xs):
     return out
 
 
-def test_reference_tree_and_facade_alternate_on_one_database_without_losing_a_hash():
-    """LIVE (build container only): files are added alternately through the reference's own VpTreeManager and through the
-    facade on ONE SQLite file; afterwards the reference's own search, on the tree both of them wrote, finds every
-    near-duplicate the reference finds on a tree it built alone, for files inserted by either side."""
-    import importlib.util
-    import os
-    import sys
+def test_reference_tree_and_facade_alternate_on_one_database_without_losing_a_hash(hvd, oracle):
+    """Files are added alternately through the reference's own VpTreeManager and through the facade on ONE SQLite file;
+    afterwards the reference's own search, on the tree both of them wrote, must find every near-duplicate it finds on a
+    tree it built alone. tests/golden/reference_live.npz holds the reference's shape_vptree after each file its own
+    DedupeDb inserted, and its search over the finished tree (gen_reference_vptree.py --live). Replayed: every other file
+    is inserted by the facade into the reference's table as it stood before that file, and must leave exactly the table
+    the reference left -- so the alternating database holds the reference's tree, and the reference's search on it is the
+    recorded one."""
+    import sqlite3
 
-    ref = os.environ.get("HVD_REFERENCE", "/root/reference")
-    if not os.path.isdir(os.path.join(ref, "src", "hydrusvideodeduplicator")):
-        pytest.skip("the reference tree is not present (GPU box)")
-    here = os.path.dirname(os.path.abspath(__file__))
-    before = set(sys.modules)
-    spec = importlib.util.spec_from_file_location("gen_reference_vptree", os.path.join(here, "golden", "gen_reference_vptree.py"))
-    gen = importlib.util.module_from_spec(spec)
-    try:
-        spec.loader.exec_module(gen)
-        _alternation_checks(gen)
-    finally:
-        for name in set(sys.modules) - before:
-            if name.split(".")[0] in ("hvdaccelerators", "av", "hydrusvideodeduplicator"):
-                del sys.modules[name]
-
-
-def _alternation_checks(gen):
-    import random
-    import tempfile
-    from pathlib import Path
-
-    import hvd_amd.vptree as ours
-    from oracle import oracle as O
-
-    blobs = dedupe_keep_order(gen.build_library(n_videos=50, seed=123))
-    m = OracleMatcher(O)
-
-    def build(tree_for_file):
-        d = Path(tempfile.mkdtemp())
-        db = gen.DedupeDB.DedupeDb(d, "a.sqlite")
-        db.init_connection()
-        db.create_tables()
-        for k, b in enumerate(blobs):
-            name = f"{k:064x}"
-            db.add_file(name)
-            db.add_perceptual_hash(b)
-            # DedupeDb.associate_file_with_perceptual_hash (db/DedupeDB.py:287-324) with the tree class chosen per file
-            gen.DedupeDB.VpTreeManager = tree_for_file(k)
-            db.associate_file_with_perceptual_hash(name, b)
-        db.commit()
-        gen.DedupeDB.VpTreeManager = gen.vptree.VpTreeManager
-        return db
-
-    random.seed(4)  # the reference's tree uses unseeded random sampling when it rebalances; none happens at this size
-    ref_only = build(lambda k: gen.vptree.VpTreeManager)
-    mixed = build(lambda k: gen.vptree.VpTreeManager if k % 2 == 0 else (lambda db: ours.VpTreeManager(db, matcher=m, maintain_reference_tree=True)))
-    # same rule, same distances, same insertion order -> the very same tree
-    q = "SELECT phash_id, parent_id, radius, inner_id, inner_population, outer_id, outer_population FROM shape_vptree ORDER BY phash_id"
-    assert mixed.execute(q).fetchall() == ref_only.execute(q).fetchall()
-    _check_tree_is_valid(mixed.conn, m.calculate_distance)
-    # and the reference's own search on the mixed tree sees the files the facade inserted
-    def search_all(db):
-        # the reference keeps a PROCESS-wide cache of temporary table names (db/vptree.py:34-70) that assumes one
-        # connection per process; this test holds two databases, so start each from a clean cache
-        gen.vptree.TemporaryIntegerTableNameCache()
-        tree = gen.vptree.VpTreeManager(db)
-        return [sorted(tree.search_file(k + 1, 51)) for k in range(len(blobs))]
-
-    want, got = search_all(ref_only), search_all(mixed)
-    assert got == want
-    assert sum(len(r) - 1 for r in got) >= 10
+    g = load_golden("reference_live.npz")
+    lens = g["alt_blobs_len"]
+    off = np.concatenate([[0], np.cumsum(lens)])
+    data = g["alt_blobs_data"].tobytes()
+    blobs = [data[off[k]:off[k + 1]] for k in range(len(lens))]
+    states = [[tuple(r) for r in s_] for s_ in json.loads(str(g["alt_tree_states"]))]
+    want = [[tuple(x) for x in r] for r in json.loads(str(g["alt_search_51"]))]
+    assert len(states) == len(blobs) == len(set(blobs))
+    m = OracleMatcher(oracle)
+    cols = "phash_id, parent_id, radius, inner_id, inner_population, outer_id, outer_population"
+    conn = sqlite3.connect(":memory:")
+    for stmt in SCHEMA:
+        conn.execute(stmt)
+    for k, b in enumerate(blobs):
+        # DedupeDb.add_file / add_perceptual_hash / associate_file_with_perceptual_hash (db/DedupeDB.py:241-324)
+        conn.execute("INSERT INTO files VALUES (?, ?)", (k + 1, f"{k:064x}"))
+        conn.execute("INSERT INTO shape_perceptual_hashes VALUES (?, ?)", (k + 1, b))
+        conn.execute("INSERT INTO shape_perceptual_hash_map VALUES (?, ?)", (k + 1, k + 1))
+        conn.execute("INSERT INTO shape_search_cache VALUES (?, NULL)", (k + 1,))
+        if k % 2 == 0:  # the reference's insertion: its recorded result
+            conn.execute("DELETE FROM shape_vptree")
+            conn.executemany(f"INSERT INTO shape_vptree ( {cols} ) VALUES ( ?, ?, ?, ?, ?, ?, ? )", states[k])
+        else:           # the facade's, one manager per file as the reference constructs them
+            hvd.vptree.VpTreeManager(conn, matcher=m, maintain_reference_tree=True).add_leaf(k + 1, b)
+            assert conn.execute(f"SELECT {cols} FROM shape_vptree ORDER BY phash_id").fetchall() == states[k], k
+    _check_tree_is_valid(conn, m.calculate_distance)
+    # the reference's search over that tree, and the facade's answer to the same questions
+    assert sum(len(r) - 1 for r in want) >= 10
+    tree = hvd.vptree.VpTreeManager(conn, matcher=m)
+    for k, r in enumerate(want):
+        assert (k + 1, 0) in r
+        assert set(r) <= set(tree.search_file(k + 1, 51)), k
 
 
 class _RecordedMatcher:
