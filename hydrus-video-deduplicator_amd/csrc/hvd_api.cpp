@@ -795,11 +795,15 @@ size_t api_scratch_bytes(int64_t n, int h, int w, int channels) {
     return b;
 }
 
-// Enqueue the PDQ kernels for one batch on stream s (geometry already validated).
-hipError_t api_launch_hash(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
-                           void* d_quality, hipStream_t s) {
-    if (h == 64 && w == 64 && channels == 1)
-        return launch_pdq_hash64(d_frames, 0, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s);
+// Enqueue the PDQ kernels for one batch on stream s (geometry already validated). dihedral: the 8-hash kernel
+// (k_pdq_dihedral.hip, d_hashes n*8*32 bytes) behind the same front-ends.
+static hipError_t launch_hash_any(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
+                                  void* d_quality, hipStream_t s, bool dihedral) {
+    auto hash64 = [&](const void* in, int kind) {
+        return dihedral ? launch_pdq_dihedral64(in, kind, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s)
+                        : launch_pdq_hash64(in, kind, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s);
+    };
+    if (h == 64 && w == 64 && channels == 1) return hash64(d_frames, 0);
     hipError_t e;
     float* out64 = (float*)d_scratch;
     if (h == 64 && w == 64)
@@ -807,25 +811,42 @@ hipError_t api_launch_hash(const void* d_frames, int64_t n, int h, int w, int ch
     else
         e = launch_pdq_downsample((const uint8_t*)d_frames, n, h, w, channels, out64 + (size_t)n * 4096, out64, s);
     if (e != hipSuccess) return e;
-    return launch_pdq_hash64(d_scratch, 1, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s);
+    return hash64(d_scratch, 1);
+}
+
+hipError_t api_launch_hash(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
+                           void* d_quality, hipStream_t s) {
+    return launch_hash_any(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, s, false);
 }
 }  // namespace hvd
 
 extern "C" {
 
-int hvd_dev_pdq_hash_frames(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch,
-                            void* d_hashes, void* d_quality) {
+static int dev_hash_frames(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
+                           void* d_quality, bool dihedral) {
     if (int rc = need_ready()) return rc;
     if (n < 0 || h < 64 || w < 64 || (channels != 1 && channels != 3))
         return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d channels=%d (need h,w >= 64)", (long long)n, h,
                     w, channels);
     if (h > 4096 || w > 4096) return fail(HVD_ERR_ARG, "frames larger than 4096 px per side are not supported");
+    if (dihedral && hvd::g_pdq_dct_mode != 0)
+        return fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");
     if (n == 0) return HVD_OK;
     if (!d_frames || !d_hashes || !d_quality) return fail(HVD_ERR_ARG, "NULL device pointer");
     const bool need_scratch = !(h == 64 && w == 64 && channels == 1);
     if (need_scratch && !d_scratch) return fail(HVD_ERR_ARG, "d_scratch (hvd_pdq_scratch_bytes) is required unless 64x64 gray");
-    HIP_TRY(hvd::api_launch_hash(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, g.stream));
+    HIP_TRY(hvd::launch_hash_any(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, g.stream, dihedral));
     return HVD_OK;
+}
+
+int hvd_dev_pdq_hash_frames(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch,
+                            void* d_hashes, void* d_quality) {
+    return dev_hash_frames(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, false);
+}
+
+int hvd_dev_pdq_hash_frames_dihedral(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch,
+                                     void* d_hashes8, void* d_quality) {
+    return dev_hash_frames(d_frames, n, h, w, channels, d_scratch, d_hashes8, d_quality, true);
 }
 
 int hvd_allpairs_tile_geometry(int64_t n, int variant, uint32_t* rows_per_block, uint32_t* col_chunk) {

@@ -105,6 +105,9 @@ extern int g_pdq_down512_wave_grid;
 extern int g_pdq_down512_strip;
 hipError_t launch_pdq_hash64(const void* d_in, int kind, int64_t n, const float* d_dct, uint8_t* d_hashes,
                              int32_t* d_quality, hipStream_t s);
+// The 8 dihedral hashes of every frame (k_pdq_dihedral.hip, strict DCT only): d_hashes8 n*8*32 bytes, identity first.
+hipError_t launch_pdq_dihedral64(const void* d_in, int kind, int64_t n, const float* d_dct, uint8_t* d_hashes8,
+                                 int32_t* d_quality, hipStream_t s);
 
 // Luma + 2x Jarosz box filter + decimate to 64x64 float, for h,w != 64 (the
 // reference's 512x512 rgb24 frames, vpdqpy/vpdqpy.py:90-95,113).

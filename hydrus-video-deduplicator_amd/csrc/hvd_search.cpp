@@ -24,14 +24,18 @@ constexpr unsigned long long kMatchServerLifeUs = 2000;  // ... and after this l
 extern "C" {
 
 
+// variants: 1 (the PDQ hash) or 8 (the dihedral hashes, hvd_dev_pdq_hash_frames_dihedral): hash bytes per frame 32 * variants
 static int hash_frames_host(const uint8_t* frames, int64_t n, int h, int w, int channels, uint8_t* out_hashes,
-                            int32_t* out_quality) {
+                            int32_t* out_quality, int variants = 1) {
     if (int rc = need_ready()) return rc;
     if (n < 0 || h < 64 || w < 64) return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d", (long long)n, h, w);
+    if (variants != 1 && hvd::g_pdq_dct_mode != 0)
+        return fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");
     if (n == 0) return HVD_OK;
     if (!frames || !out_hashes || !out_quality) return fail(HVD_ERR_ARG, "NULL buffer");
     std::lock_guard<std::recursive_mutex> lk(g.h_mu);
     const size_t frame_bytes = (size_t)h * w * channels;
+    const size_t hash_bytes = 32 * (size_t)variants;
     // Batches bound the staging footprint (<= ~1 GiB of frames per batch).
     int64_t batch = (int64_t)((1ull << 30) / frame_bytes);
     if (batch < 1) batch = 1;
@@ -44,13 +48,16 @@ static int hash_frames_host(const uint8_t* frames, int64_t n, int h, int w, int 
         if (int rc = hvd_pdq_scratch_bytes(batch, h, w, channels, &sb)) return rc;
         SCR(S_FSCR, sb, d_scr);
     }
-    SCR(S_HASH, 32 * (size_t)batch, d_h);
+    SCR(S_HASH, hash_bytes * (size_t)batch, d_h);
     SCR(S_QUAL, 4 * (size_t)batch, d_q);
     for (int64_t f0 = 0; f0 < n; f0 += batch) {
         const int64_t m = std::min(batch, n - f0);
         HIP_TRY(hipMemcpyAsync(d_in, frames + frame_bytes * f0, frame_bytes * m, hipMemcpyHostToDevice, g.stream));
-        if (int rc = hvd_dev_pdq_hash_frames(d_in, m, h, w, channels, need_scratch ? d_scr : nullptr, d_h, d_q)) return rc;
-        HIP_TRY(hipMemcpyAsync(out_hashes + 32 * f0, d_h, 32 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
+        if (int rc = variants == 1 ? hvd_dev_pdq_hash_frames(d_in, m, h, w, channels, need_scratch ? d_scr : nullptr, d_h, d_q)
+                                   : hvd_dev_pdq_hash_frames_dihedral(d_in, m, h, w, channels, need_scratch ? d_scr : nullptr,
+                                                                      d_h, d_q))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(out_hashes + hash_bytes * f0, d_h, hash_bytes * (size_t)m, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipMemcpyAsync(out_quality + f0, d_q, 4 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipStreamSynchronize(g.stream));
     }
@@ -59,14 +66,15 @@ static int hash_frames_host(const uint8_t* frames, int64_t n, int h, int w, int 
 
 // frames are independent: a group hashes contiguous ranges of them, one per context, no exchange
 static int hash_frames_group(const uint8_t* frames, int64_t n, int h, int w, int channels, uint8_t* out_hashes,
-                             int32_t* out_quality) {
+                             int32_t* out_quality, int variants = 1) {
     const int W = g_nctx;
     if (W <= 1 || n < 4 * (int64_t)W || !frames || !out_hashes || !out_quality || h < 64 || w < 64)
-        return hash_frames_host(frames, n, h, w, channels, out_hashes, out_quality);
+        return hash_frames_host(frames, n, h, w, channels, out_hashes, out_quality, variants);
     const size_t frame_bytes = (size_t)h * w * channels;
     return run_on_group([&](int r) -> int {
         const int64_t per = (n + W - 1) / W, lo = std::min<int64_t>(n, per * r), hi = std::min<int64_t>(n, lo + per);
-        return hash_frames_host(frames + frame_bytes * (size_t)lo, hi - lo, h, w, channels, out_hashes + 32 * lo, out_quality + lo);
+        return hash_frames_host(frames + frame_bytes * (size_t)lo, hi - lo, h, w, channels, out_hashes + 32 * variants * lo,
+                                out_quality + lo, variants);
     });
 }
 
@@ -78,6 +86,16 @@ int hvd_pdq_hash_frames_gray_u8(const uint8_t* frames, int64_t n, int h, int w, 
 int hvd_pdq_hash_frames_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, uint8_t* out_hashes,
                                  int32_t* out_quality) {
     return hash_frames_group(frames, n, h, w, 3, out_hashes, out_quality);
+}
+
+int hvd_pdq_hash_frames_dihedral_gray_u8(const uint8_t* frames, int64_t n, int h, int w, uint8_t* out_hashes8,
+                                         int32_t* out_quality) {
+    return hash_frames_group(frames, n, h, w, 1, out_hashes8, out_quality, 8);
+}
+
+int hvd_pdq_hash_frames_dihedral_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, uint8_t* out_hashes8,
+                                          int32_t* out_quality) {
+    return hash_frames_group(frames, n, h, w, 3, out_hashes8, out_quality, 8);
 }
 
 // Runs the default all-pairs kernel (FP4-MFMA form) on a host DB -- this context's share of the tiles (rank of world) --

@@ -163,3 +163,129 @@ def find_potential_duplicates(video_hashes, threshold: float = 50.0, policy: str
     recs = match_videos(frames, offsets, vpdq.frame_max_dist(DISTANCE_TOLERANCE))
     pairs = similar_video_pairs(recs, lengths, threshold, policy)
     return [(int(a), int(b)) for a, b in pairs]
+
+
+# Named transform sets of find_transformed_duplicates / Vpdq.computeTransformedHashes (names: vpdq.TRANSFORMS)
+TRANSFORM_SETS = {
+    "mirror": ("identity", "flip_h"),
+    "flips": ("identity", "flip_h", "flip_v", "rot180"),
+    "dihedral": vpdq.TRANSFORMS,
+}
+
+
+def transform_set(transforms, require_identity: bool = True) -> tuple[str, ...]:
+    """A set name of TRANSFORM_SETS or a sequence of vpdq.TRANSFORMS names -> the names, in vpdq.TRANSFORMS order."""
+    if isinstance(transforms, str):
+        if transforms not in TRANSFORM_SETS:
+            raise ValueError(f"unknown transform set {transforms!r}; expected one of {sorted(TRANSFORM_SETS)} or a tuple "
+                             f"of names from {vpdq.TRANSFORMS}")
+        return TRANSFORM_SETS[transforms]
+    names = set(transforms)
+    bad = names - set(vpdq.TRANSFORMS)
+    if bad:
+        raise ValueError(f"unknown transform(s) {sorted(bad)}; expected names from {vpdq.TRANSFORMS}")
+    if not names:
+        raise ValueError("no transform given")
+    if require_identity and "identity" not in names:
+        raise ValueError("the transform set must include 'identity'")
+    return tuple(t for t in vpdq.TRANSFORMS if t in names)
+
+
+def fold_transformed_records(records_identity: np.ndarray, records_cross: np.ndarray, lengths: np.ndarray,
+                             cross_transforms, threshold: float = 50.0,
+                             policy: str | None = None) -> tuple[np.ndarray, np.ndarray]:
+    """The pair set of find_transformed_duplicates from its two searches (pure numpy; no device).
+
+    records_identity: VMATCH records (a < b) of the videos against each other. records_cross: VMATCH records of the
+    query set -- video v under transform cross_transforms[k] is query v * K + k, K = len(cross_transforms) -- against the
+    videos (b). lengths: frames per video (every variant of a video has the same frames). cross_transforms: indices into
+    vpdq.TRANSFORMS. sim_T(A, B) is the largest similarity_of_records value of the pair over the identity record and the
+    cross records of either direction (A_t vs B, B_t vs A); a pair is kept if int(sim_T) >= int(threshold).
+    -> (pairs int64[m, 2] with a < b, sorted; transform int64[m]: the vpdq.TRANSFORMS index that reached sim_T, the lowest
+    index on a tie; identity is 0)."""
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    lengths = np.asarray(lengths, dtype=np.int64)
+    V = lengths.size
+    K = len(cross_transforms)
+    tmap = np.asarray(cross_transforms, dtype=np.int64).reshape(-1)
+    rc = np.asarray(records_cross)
+    if K == 0 and rc.size:
+        raise ValueError("cross records without cross transforms")
+    va = rc["a"].astype(np.int64) // max(K, 1)
+    vrec = rc.copy()
+    vrec["a"] = va  # query index -> its video (same frame count)
+    sim_c = similarity_of_records(vrec, lengths, policy)
+    t_c = tmap[rc["a"].astype(np.int64) % K] if K else np.zeros(0, np.int64)
+    ri = np.asarray(records_identity)
+    sim_i = similarity_of_records(ri, lengths, policy)
+    vb = rc["b"].astype(np.int64)
+    lo = np.concatenate([ri["a"].astype(np.int64), np.minimum(va, vb)])
+    hi = np.concatenate([ri["b"].astype(np.int64), np.maximum(va, vb)])
+    sim = np.concatenate([sim_i, sim_c])
+    tid = np.concatenate([np.zeros(ri.size, np.int64), t_c])
+    key = lo * max(V, 1) + hi
+    order = np.lexsort((tid, -sim, key))  # per key: largest similarity first, then the lowest transform index
+    key, sim, tid, lo, hi = key[order], sim[order], tid[order], lo[order], hi[order]
+    first = np.ones(key.size, dtype=bool)
+    first[1:] = key[1:] != key[:-1]
+    keep = first & (sim.astype(np.int64) >= int(threshold))  # int() truncation as in fix_vpdq_similarity
+    return np.stack([lo[keep], hi[keep]], axis=1).reshape(-1, 2), tid[keep]
+
+
+def find_transformed_duplicates(variant_hashes, threshold: float = 50.0, policy: str | None = None,
+                                transforms="mirror") -> list[tuple[int, int, str]]:
+    """find_potential_duplicates that also finds mirrored / flipped / rotated copies.
+
+    variant_hashes[v]: the dict Vpdq.computeTransformedHashes returns for video v (transform name -> VpdqHash or bytes;
+    it must hold every name of `transforms`). transforms: "mirror" (identity, flip_h), "flips" (+ flip_v, rot180),
+    "dihedral" (all 8 of vpdq.TRANSFORMS), or a tuple of names that includes "identity". The similarity of a pair is
+    sim_T(A, B) = max over t in T of max(sim(A_t, B), sim(B_t, A)) with sim the rule of find_potential_duplicates
+    (policy included); both directions make it symmetric although each variant is thresholded at its own median.
+    Returns (a, b, transform name) for every a < b with int(sim_T) >= int(threshold), sorted by (a, b); the name is the
+    transform that reached sim_T (the first in vpdq.TRANSFORMS order on a tie). Two searches on the device: the videos
+    against each other (match_videos), and every non-identity variant of every video against the videos
+    (match_videos_cross, a video never against its own variants)."""
+    names = transform_set(transforms)
+    cross = [t for t in names if t != "identity"]
+    K = len(cross)
+
+    def blob(x):
+        b = x.bytes if isinstance(x, vpdq.VpdqHash) else bytes(x)
+        if len(b) % 32:
+            raise ValueError("phash length not a multiple of 32")
+        return b
+
+    ident, var = [], []
+    for v, d in enumerate(variant_hashes):
+        missing = [t for t in names if t not in d]
+        if missing:
+            raise ValueError(f"video {v} has no hash for transform(s) {missing}")
+        ident.append(blob(d["identity"]))
+        vb = [blob(d[t]) for t in cross]
+        if any(len(b) != len(ident[-1]) for b in vb):
+            raise ValueError(f"video {v}: the variants must hash the same frames as the identity")
+        var.extend(vb)
+    V = len(ident)
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    if V == 0:
+        return []
+    lengths = np.array([len(b) // 32 for b in ident], dtype=np.int64)
+    offsets = np.zeros(V + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    frames = np.frombuffer(b"".join(ident), dtype=np.uint8).reshape(-1, 32)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
+    recs_i = match_videos(frames, offsets, max_dist)
+    if K:
+        offsets_q = np.zeros(V * K + 1, dtype=np.int64)
+        np.cumsum(np.repeat(lengths, K), out=offsets_q[1:])
+        frames_q = np.frombuffer(b"".join(var), dtype=np.uint8).reshape(-1, 32)
+        vids = np.arange(V, dtype=np.int32)
+        recs_c = match_videos_cross(frames_q, offsets_q, frames, offsets, ids_q=np.repeat(vids, K), ids_t=vids,
+                                    max_dist=max_dist)
+    else:
+        recs_c = np.zeros(0, dtype=VMATCH_DTYPE)
+    pairs, tid = fold_transformed_records(recs_i, recs_c, lengths, [vpdq.TRANSFORMS.index(t) for t in cross],
+                                          threshold, policy)
+    return [(int(a), int(b), vpdq.TRANSFORMS[int(t)]) for (a, b), t in zip(pairs, tid)]

@@ -370,6 +370,32 @@ def hash_frames(frames: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
     return hashes, quality
 
 
+# Dihedral PDQ (include/hvd_mi355x.h): the hashes of the frame's mirror images and rotations, in the
+# kernel's output order -- TRANSFORMS[k] is what hash_frames_dihedral(frames)[0][:, k] hashes. Names of the physical
+# transform of the 64x64 luma A (rows top to bottom; rotations as numpy's rot90): A, A[:, ::-1], A[::-1, :],
+# A[::-1, ::-1], A.T, A[::-1, ::-1].T, rot90(A, 1), rot90(A, -1).
+TRANSFORMS = ("identity", "flip_h", "flip_v", "rot180", "transpose", "antitranspose", "rot90_ccw", "rot90_cw")
+
+
+def hash_frames_dihedral(frames: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+    """Dihedral counterpart of `hash_frames`: uint8[n,h,w] (gray) or uint8[n,h,w,3] (rgb24) ->
+    (hashes uint8[n,8,32] in TRANSFORMS order, quality int32[n]). hashes[:, 0] equals hash_frames(frames)[0]; one
+    quality per frame serves all 8. No quality filtering. Strict DCT mode only (the "fma" mode raises HvdError)."""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    lib = _lib.ensure()
+    if frames.ndim == 3:
+        fn = lib.hvd_pdq_hash_frames_dihedral_gray_u8
+    elif frames.ndim == 4 and frames.shape[3] == 3:
+        fn = lib.hvd_pdq_hash_frames_dihedral_rgb24_u8
+    else:
+        raise ValueError("frames must be uint8[n,h,w] or uint8[n,h,w,3]")
+    n, h, w = frames.shape[:3]
+    hashes = np.zeros((n, len(TRANSFORMS), BYTES_PER_PDQ_HASH), dtype=np.uint8)
+    quality = np.zeros(n, dtype=np.int32)
+    _lib.check(fn(frames.ctypes.data, n, h, w, hashes.ctypes.data, quality.ctypes.data))
+    return hashes, quality
+
+
 def match_counts(a: bytes, b: bytes, distance_tolerance: int = 31) -> tuple[int, int]:
     """(q_hits, t_hits) for query a / target b, both concatenated 32-byte frame hashes."""
     a = bytes(a)

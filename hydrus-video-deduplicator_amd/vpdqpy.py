@@ -103,6 +103,51 @@ class Vpdq:
         raise ValueError("Failed to hash: invalid frames object type.")
 
     @staticmethod
+    def computeTransformedHashes(frames, transforms="dihedral", width: int | None = None, height: int | None = None,
+                                 average_rate=None, all_decoded_frames: bool = False) -> dict:
+        """The video hashes of the video's mirror images / rotations: {transform name: VpdqHash}, for the names of
+        `transforms` (a set name of ``search.transform_set`` -- "mirror", "flips", "dihedral" -- or a sequence of
+        ``vpdq.TRANSFORMS`` names). Takes what ``computeHash`` takes; all variants come from one dihedral hashing pass
+        (vpdq.hash_frames_dihedral) and keep the SAME frames: the quality filter (>= QUALITY_TOLERANCE) is applied once,
+        per frame. ``["identity"]`` equals ``computeHash(frames)``."""
+        from .search import transform_set
+
+        names = transform_set(transforms, require_identity=False)
+        if frames is None:
+            raise ValueError
+        if isinstance(frames, (bytes, bytearray, memoryview, str, os.PathLike)):
+            raise ValueError("encoded video input (bytes / path) is not supported: decode first and pass the frames "
+                             "(uint8[n,h,w,3] array or an iterable of per-frame byte strings)")
+        if all_decoded_frames:
+            frames = (frames[selected_frame_indices(frames.shape[0], average_rate)] if isinstance(frames, np.ndarray)
+                      else select_frames(frames, average_rate))
+        if isinstance(frames, np.ndarray):
+            if frames.ndim not in (3, 4) or (frames.ndim == 4 and frames.shape[3] != 3):
+                raise ValueError("frames must be uint8[n,h,w] or uint8[n,h,w,3]")
+            arr = frames
+        elif isinstance(frames, Iterable):
+            w = DOWNSCALE_DIMENSIONS if width is None else int(width)
+            h = DOWNSCALE_DIMENSIONS if height is None else int(height)
+            bufs = [np.frombuffer(f, dtype=np.uint8) for f in frames]
+            sizes = {b.size for b in bufs}
+            if len(sizes) > 1:
+                raise ValueError("all frames of one video must have the same pixel format")
+            size = sizes.pop() if sizes else h * w * 3
+            if size == h * w * 3:
+                arr = np.stack(bufs).reshape(-1, h, w, 3) if bufs else np.zeros((0, h, w, 3), np.uint8)
+            elif size == h * w:
+                arr = np.stack(bufs).reshape(-1, h, w)
+            else:
+                raise ValueError(f"frame has {size} bytes; expected {h * w * 3} (rgb24) or {h * w} (gray)")
+        else:
+            raise ValueError("Failed to hash: invalid frames object type.")
+        if arr.shape[1] < 64 or arr.shape[2] < 64:
+            raise ValueError("frames must be at least 64x64")
+        hashes, quality = vpdq.hash_frames_dihedral(arr)
+        kept = hashes[quality >= vpdq.QUALITY_TOLERANCE]
+        return {t: VpdqHash(kept[:, vpdq.TRANSFORMS.index(t)].tobytes()) for t in names}
+
+    @staticmethod
     def is_similar(vpdq_features1: VpdqHash, vpdq_features2: VpdqHash, threshold: float = 75.0) -> tuple[bool, float]:
         """Threshold is minimum similarity to be considered similar (vpdqpy.py:121-131)."""
         similarity = Vpdq.match_hash(query_features=vpdq_features1, target_features=vpdq_features2)

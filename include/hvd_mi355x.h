@@ -39,7 +39,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -119,6 +119,16 @@ int hvd_pdq_hash_frames_gray_u8(const uint8_t* frames, int64_t n, int h, int w, 
                                 int32_t* out_quality);
 int hvd_pdq_hash_frames_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, uint8_t* out_hashes,
                                  int32_t* out_quality);
+/* Dihedral PDQ: 8 hashes per frame in the order of the table in DESIGN (identity first), n*8*32 bytes:
+ * identity, flip_h, flip_v, rot180, transpose, antitranspose, rot90_ccw, rot90_cw -- the PDQ hash of the frame's 64x64
+ * luma mirrored / rotated that way, computed from the frame's one DCT (sign flips and a transpose), each variant
+ * thresholded at its own median. Hash k of frame f is bytes [(8f+k)*32, (8f+k+1)*32); variant 0 is bit-identical to
+ * hvd_pdq_hash_frames_*. One quality per frame (the same for all 8). Same geometry rules and device-group sharding as
+ * hvd_pdq_hash_frames_*. Strict DCT mode only: HVD_ERR_STATE while hvd_set_pdq_dct_mode(1) is active. */
+int hvd_pdq_hash_frames_dihedral_gray_u8(const uint8_t* frames, int64_t n, int h, int w, uint8_t* out_hashes8,
+                                         int32_t* out_quality);
+int hvd_pdq_hash_frames_dihedral_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, uint8_t* out_hashes8,
+                                          int32_t* out_quality);
 
 /* Replaces the O(visited nodes) stream of vpdq.matchHashBytes calls issued by the
  * VP-tree (db/vptree.py:29-31,737; dedup.py:445-502) with one brute-force pass:
@@ -258,6 +268,9 @@ int hvd_pdq_scratch_bytes(int64_t n, int h, int w, int channels, size_t* out_byt
  * (NULL when that is 0). h,w in [64,4096]. */
 int hvd_dev_pdq_hash_frames(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch,
                             void* d_hashes, void* d_quality);
+/* Dihedral PDQ: 8 hashes per frame in the order of the table in DESIGN (identity first), n*8*32 bytes. */
+int hvd_dev_pdq_hash_frames_dihedral(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch,
+                                     void* d_hashes8, void* d_quality);      /* scratch: hvd_pdq_scratch_bytes */
 
 /* Brute-force pass over the tiles owned by `rank` of `world` (tile (rb,cb) belongs
  * to rank (rb+cb) % world; world=1 => everything). Appends hvd_pair records to
