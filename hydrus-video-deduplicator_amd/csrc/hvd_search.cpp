@@ -28,7 +28,11 @@ extern "C" {
 static int hash_frames_host(const uint8_t* frames, int64_t n, int h, int w, int channels, uint8_t* out_hashes,
                             int32_t* out_quality, int variants = 1) {
     if (int rc = need_ready()) return rc;
-    if (n < 0 || h < 64 || w < 64) return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d", (long long)n, h, w);
+    // the whole geometry is checked before anything is sized or allocated for it: an oversized frame is HVD_ERR_ARG,
+    // never a failed allocation (HVD_ERR_HIP) of its staging or scratch
+    if (n < 0 || h < 64 || w < 64 || h > 4096 || w > 4096 || (channels != 1 && channels != 3))
+        return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d channels=%d (need h,w in [64,4096])", (long long)n,
+                    h, w, channels);
     if (variants != 1 && hvd::g_pdq_dct_mode != 0)
         return fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");
     if (n == 0) return HVD_OK;
@@ -68,7 +72,7 @@ static int hash_frames_host(const uint8_t* frames, int64_t n, int h, int w, int 
 static int hash_frames_group(const uint8_t* frames, int64_t n, int h, int w, int channels, uint8_t* out_hashes,
                              int32_t* out_quality, int variants = 1) {
     const int W = g_nctx;
-    if (W <= 1 || n < 4 * (int64_t)W || !frames || !out_hashes || !out_quality || h < 64 || w < 64)
+    if (W <= 1 || n < 4 * (int64_t)W || !frames || !out_hashes || !out_quality || h < 64 || w < 64 || h > 4096 || w > 4096)
         return hash_frames_host(frames, n, h, w, channels, out_hashes, out_quality, variants);
     const size_t frame_bytes = (size_t)h * w * channels;
     return run_on_group([&](int r) -> int {

@@ -353,3 +353,140 @@ def test_avx512_scan_reports_exactly_what_the_scalar_loop_reports(oracle, tmp_pa
     assert outs[1][0][0] == b"0"  # the switch works
     assert outs[0][0][1] == outs[1][0][1]
     assert np.array_equal(outs[0][1], outs[1][1]) and outs[0][1].size > 1000
+
+
+# ---- the generic down-sampler at real video geometries: the reference pinned at every box-filter window ----
+
+def jarosz_window(side):
+    """Box-filter window for one axis: what both restatements and k_box_scan_T derive from that axis' length."""
+    return (side + 127) // 128
+
+
+def hard_frames(h, w, channels=3, seed=0):
+    """(uint8[n,h,w] or uint8[n,h,w,3], labels): content where a down-sampler goes wrong -- noise, saturated binary noise,
+    stripes of period 2 x the window on each axis, both constants, one-pixel impulses at the corners and at the first pixel
+    of the last partial 64-line block / 32-column tile (both ways round: the kernel transposes between passes), a dark frame
+    but for its last row and column, and two smooth synth fields. Shared by the GPU geometry tests."""
+    import hvd_amd
+
+    rng = np.random.default_rng(seed)
+    wr, wc = jarosz_window(w), jarosz_window(h)
+    yy, xx = np.arange(h)[:, None], np.arange(w)[None, :]
+    frames, labels = [], []
+
+    def add(label, img):
+        img = np.asarray(img, np.uint8)
+        frames.append(np.broadcast_to(img[..., None], (h, w, 3)) if channels == 3 and img.ndim == 2 else img)
+        labels.append(label)
+
+    shape = (h, w, 3) if channels == 3 else (h, w)
+    add("noise", rng.integers(0, 256, shape, dtype=np.uint8))
+    add("binary_noise", rng.integers(0, 2, shape, dtype=np.uint8) * 255)
+    add("stripes_x", np.broadcast_to(((xx // wr) % 2) * 255, (h, w)))
+    add("stripes_y", np.broadcast_to(((yy // wc) % 2) * 255, (h, w)))
+    add("const0", np.zeros((h, w)))
+    add("const255", np.full((h, w), 255))
+    for r, c in ((0, 0), (h - 1, w - 1), (h - 1, 0), (0, w - 1), (64 * ((h - 1) // 64), 32 * ((w - 1) // 32)),
+                 (32 * ((h - 1) // 32), 64 * ((w - 1) // 64))):
+        img = np.zeros((h, w), np.uint8)
+        img[r, c] = 255
+        add(f"impulse_{r}_{c}", img)
+    img = np.zeros((h, w), np.uint8)
+    img[-1, :] = 255
+    img[:, -1] = 255
+    add("last_row_and_col", img)
+    fields = (hvd_amd.synth.frames_rgb(2, seed=seed + 7, h=h, w=w) if channels == 3
+              else hvd_amd.synth.frames_gray(2, seed=seed + 7, h=h, w=w, const_fraction=0.0))
+    for k in range(2):
+        add(f"synth{k}", fields[k])
+    return np.ascontiguousarray(np.stack(frames)), labels
+
+
+def _window_sides(k):
+    """Both edges of window k's side range (sides below 64 are not frames; 65 keeps k = 1 off the 64x64 shortcut)."""
+    return (max(65, 128 * (k - 1) + 1), 128 * k)
+
+
+@pytest.mark.parametrize("k", range(1, 33))
+def test_restatements_agree_at_every_window(oracle, k):
+    """C oracle vs pdq_numpy, bit for bit (hash, quality, all 256 coefficients) through the Jarosz down-sampler at window
+    k on the long axis: 64 x side with side at the top of k's range, side x 64 at the bottom."""
+    lo, hi = _window_sides(k)
+    assert jarosz_window(lo) == jarosz_window(hi) == k
+    rng = np.random.default_rng(1000 + k)
+    for shape in ((64, hi), (lo, 64)):
+        fr = rng.integers(0, 256, (1,) + shape, dtype=np.uint8)
+        h, q, c = oracle.hash_frames(fr, want_coeffs=True)
+        hp, qp, cp = P.hash_gray(fr[0])
+        assert np.array_equal(cp.ravel().view(np.uint32), c[0].view(np.uint32)), shape
+        assert hp == h[0].tobytes() and qp == q[0], shape
+
+
+def test_restatements_agree_at_1080p(oracle):
+    import hvd_amd
+
+    fr = hvd_amd.synth.frames_rgb(1, seed=1080, h=1080, w=1920)
+    h, q, c = oracle.hash_frames(fr, want_coeffs=True)
+    hp, qp, cp = P.hash_rgb(fr[0])
+    assert np.array_equal(cp.ravel().view(np.uint32), c[0].view(np.uint32))
+    assert hp == h[0].tobytes() and qp == q[0]
+
+
+def box_filter_f64(a, win):
+    """The box filter by its definition, along axis 0, in float64: out[o] = mean of a[j] for j in
+    [o - win + half, o + half - 1] intersected with [0, n), half = (win + 2) // 2. Cumulative sums, no running state."""
+    n = a.shape[0]
+    half = (win + 2) // 2
+    s = np.concatenate([np.zeros((1,) + a.shape[1:]), np.cumsum(a, axis=0, dtype=np.float64)])
+    o = np.arange(n)
+    lo = np.clip(o - win + half, 0, n)
+    hi = np.clip(o + half, 0, n)  # exclusive
+    shape = (n,) + (1,) * (a.ndim - 1)
+    return (s[hi] - s[lo]) / (hi - lo).reshape(shape)
+
+
+def jarosz_decimate_f64(luma):
+    h, w = luma.shape
+    a = luma.astype(np.float64)
+    for _ in range(2):
+        a = box_filter_f64(a.T, jarosz_window(w)).T  # along rows
+        a = box_filter_f64(a, jarosz_window(h))     # along columns
+    ii = [int(((i + 0.5) * h) / 64) for i in range(64)]
+    jj = [int(((j + 0.5) * w) / 64) for j in range(64)]
+    return a[np.ix_(ii, jj)]
+
+
+def running_sum_bound(h, w, peak=255.0):
+    """Worst-case |float32 - exact| of jarosz_decimate on luma in [0, peak]. One pass over a line of n values does <= 2n
+    rounded adds/subtracts on a running sum of <= win values (each error <= u * win * peak, u = 2^-24), divides it by a
+    count >= win / 2 and rounds the quotient once: <= (4n + 1) u peak per output. A box filter is an average, so it never
+    grows the error it is given: the four passes add."""
+    u = 2.0 ** -24
+    return 2 * (4 * w + 1) * u * peak + 2 * (4 * h + 1) * u * peak
+
+
+@pytest.mark.parametrize("k", [1, 2, 17, 32])
+def test_jarosz_float32_matches_its_float64_definition(k):
+    """pdq_numpy.jarosz_decimate (the running-sum recurrence both restatements and the kernels share) against the filter's
+    definition at window k on both axes: within the running-sum bound on noise and on stripes of period 2 x window (where
+    a window or output lag off by one moves samples by ~255 / 8k, still 4x the bound at k = 32), exact on constant frames. Sides
+    inside k's range but not multiples of 64, so the 64 decimation samples fall at varying phases of the stripes."""
+    side = 128 * k - 37 if k > 1 else 91
+    assert jarosz_window(side) == k
+    rng = np.random.default_rng(k)
+    bound = running_sum_bound(side, side)
+    yy, xx = np.arange(side)[:, None], np.arange(side)[None, :]
+    stripes = ((((xx // k) % 2) ^ ((yy // k) % 2)) * 255).astype(np.float32)
+    for name, luma in (("noise", P.luma_gray(rng.integers(0, 256, (side, side), dtype=np.uint8))), ("stripes", stripes)):
+        got = P.jarosz_decimate(luma).astype(np.float64)
+        want = jarosz_decimate_f64(luma)
+        err = np.abs(got - want).max()
+        assert err <= bound, (name, err, bound)
+        # the check has teeth: the same definition with the output lag one sample late is outside the bound
+        if name == "stripes":
+            late = jarosz_decimate_f64(np.pad(luma, ((1, 0), (1, 0)))[:side, :side])
+            assert np.abs(late - want).max() > 2 * bound
+    for v in (0, 1, 128, 255):
+        luma = P.luma_gray(np.full((side, side), v, np.uint8))
+        got = P.jarosz_decimate(luma)
+        assert np.array_equal(got.astype(np.float64), jarosz_decimate_f64(luma)) and (got == v).all(), v
