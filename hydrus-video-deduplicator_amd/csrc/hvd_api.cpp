@@ -634,6 +634,11 @@ int hvd_debug_set(const char* key, int value) {
         hvd::g_mfma_force_sel = value;
         return HVD_OK;
     }
+    if (strcmp(key, "allpairs_index") == 0) {  // pigeonhole index path of the auto self pass: -1 the device decides, 0 never, 1 whenever eligible
+        if (value < -1 || value > 1) return fail(HVD_ERR_ARG, "allpairs_index: -1 (auto), 0 (never) or 1 (force when eligible)");
+        hvd::g_allpairs_index = value;
+        return HVD_OK;
+    }
     if (strcmp(key, "mfma_queue_packed") == 0) {  // 0: the pair-queue form settles its candidates from the FP4 images only
         hvd::g_mfma_queue_packed = value != 0;
         return HVD_OK;
@@ -677,6 +682,11 @@ int hvd_debug_set(const char* key, int value) {
         return HVD_OK;
     }
 #ifndef HVD_NO_BENCH_SYMBOLS
+    if (strcmp(key, "allpairs_index_fail_ctx") == 0) {  // tests only: context (value - 1) cannot reserve its index scratch; 0 = off
+        if (value < 0) return fail(HVD_ERR_ARG, "allpairs_index_fail_ctx: context + 1, or 0 (off)");
+        hvd::g_allpairs_index_fail = value;
+        return HVD_OK;
+    }
     if (strcmp(key, "vmatch_fail_rank") == 0) {  // tests only (include/hvd_mi355x_bench.h): rank (value - 1) fails before the key exchange; 0 = off
         for (int k = 0; k < g_nctx; ++k) g_ctx[k].v_fail_rank = value;
         return HVD_OK;
@@ -741,6 +751,22 @@ int hvd_debug_get(const char* key, int* out_value) {
             *out_value = (int)v[k];
             return HVD_OK;
         }
+    if (strcmp(key, "allpairs_index_used") == 0 || strcmp(key, "allpairs_index_kcand") == 0) {
+        // the last auto-variant pass of this context: 1 if it ran on the pigeonhole index; its exact candidates / 1000 (0 when
+        // the histograms were not built)
+        uint32_t* sel = nullptr;
+        HIP_TRY(hvd::mfma_select_buffer(t_ctx, &sel));
+        uint32_t v[16] = {};
+        HIP_TRY(hipMemcpyAsync(v, sel, sizeof(v), hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        if (key[15] == 'u') {
+            *out_value = (int)v[hvd::kSelIdxUsed];
+        } else {
+            const unsigned long long cand = (unsigned long long)v[hvd::kSelIdxCand] | (unsigned long long)v[hvd::kSelIdxCand + 1] << 32;
+            *out_value = (int)std::min<unsigned long long>(cand / 1000ull, 0x7FFFFFFFull);
+        }
+        return HVD_OK;
+    }
     if (strcmp(key, "vmatch_bit_order_used") == 0) {
         *out_value = g.v_bit_order_used;
         return HVD_OK;

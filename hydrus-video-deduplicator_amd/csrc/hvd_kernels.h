@@ -49,6 +49,55 @@ hipError_t launch_allpairs_mfma(const AllPairsArgs& a, const void* d_img, hipStr
 hipError_t launch_cross_mfma(const AllPairsArgs& a, const void* d_img_q, uint32_t nq, const void* d_img_t,
                              const int32_t* d_group_t, hipStream_t s);
 hipError_t mfma_select_buffer(int ctx_id, uint32_t** out);  // per context; [0] = form the auto variant ran last, [1] = probe survivors
+
+// Pigeonhole index path of the auto variant's self all-pairs pass (k_hamming_index.hip): 16 blocks of 16 bits; two hashes
+// within max_dist <= 31 agree to within r bits (r = 1 for max_dist 16..31, 0 below 16) in at least one block, so only pairs
+// that share a block key or whose keys differ in one bit are compared. Select words it owns (one buffer per context, cleared
+// with the probe's words in front of every pass):
+enum : int {
+    kSelIdxClose = 6,    // probe: sampled pairs x blocks with block distance <= r
+    kSelIdxUsed = 7,     // 1: the index path runs this pass (the matrix-core forms return at once)
+    kSelIdxCand = 8,     // words 8, 9: exact candidates of the pass (sum over blocks of the pairs within r in that block)
+    kSelIdxMaxWalk = 10,  // the longest work item: max over (b, u) of c_u x (c_u + the counts of its neighbours above u)
+    kSelIdxTicket = 11,  // the statistics kernel's last workgroup decides
+    kSelIdxGate = 12,    // the probe's estimate lets the histograms be built at all
+};
+// The cost rule (calibrated on MI355X): nanoseconds of the index pass against the matrix-core pass.
+struct IndexRule {
+    double pairs;         // n (n - 1) / 2 (every rank does 1/world of either pass)
+    double n;
+    uint32_t r;           // block radius
+    uint32_t force;       // 1: the index path whenever eligible (hvd_debug_set "allpairs_index" 1)
+    uint32_t world;
+    float fs_mfma_fetch;  // femtoseconds per comparison of form 9 / of the other matrix-core forms
+    float fs_mfma_other;
+    float ps_cand;        // picoseconds per candidate (join)
+    float ps_hash;        // picoseconds per hash (histograms, scan, scatter)
+    float ps_crit;        // picoseconds per pair of the longest work item: one wave walks it alone (critical path)
+    float fixed_ns;       // launches of the index pass
+};
+// (form: the matrix-core form the probe chose; any other value prices the costlier forms)
+__host__ __device__ inline bool index_wins(const IndexRule& q, double cand, double max_walk, uint32_t form) {
+    if (q.force) return true;
+    const double t_mfma = q.pairs / q.world * (form == 9u ? q.fs_mfma_fetch : q.fs_mfma_other) * 1e-6;
+    const double t_idx = q.fixed_ns + q.n * q.ps_hash * 1e-3 + cand / q.world * q.ps_cand * 1e-3 + max_walk * q.ps_crit * 1e-3;
+    return t_idx < t_mfma;
+}
+extern int g_allpairs_index;       // hvd_debug_set "allpairs_index": -1 auto, 0 never, 1 force when eligible
+extern int g_allpairs_index_fail;  // fault injection (tests): context (value - 1) fails to reserve its index scratch; 0 = off
+// Eligible: self pass (not query x target, not the video sink), max_dist <= 31, packed hashes at hand, not switched off, and
+// -- unless forced -- a DB large enough that the index could win even with no candidates at all. Depends only on what every
+// rank of a pass shares (arguments, n, world, the process-wide key), so all ranks agree.
+bool index_eligible(const AllPairsArgs& a, bool rect, uint32_t* r);
+IndexRule index_rule(const AllPairsArgs& a, uint32_t r);
+// Grows the context's index scratch (~36 B x 16 per hash). Called outside the launch lock: growing frees the old buffer,
+// which waits for the whole device.
+hipError_t index_reserve(int ctx_id, uint32_t n);
+// Histograms, exact statistics and decision (select[kSelIdxUsed]); then scan, scatter and join. Every kernel of the first call
+// returns at once unless the probe's gate is set, every kernel of the second unless the decision is.
+hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const IndexRule& q, hipStream_t s);
+hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t r, hipStream_t s);
+void index_release();
 // clock telemetry of a context's all-pairs passes: {shader cycles, constant-rate ticks, sampled workgroups, 0} since the reset
 hipError_t mfma_clock_reset(int ctx_id, hipStream_t s);
 hipError_t mfma_clock_read(int ctx_id, hipStream_t s, unsigned long long out[4]);

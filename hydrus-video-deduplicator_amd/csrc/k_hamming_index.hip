@@ -1,0 +1,445 @@
+// k_hamming_index.hip -- exact pigeonhole index for the auto variant's self all-pairs pass.
+//
+// Cut the 256 bits into 16 blocks of 16 bits (block b = bits 16b..16b+15 of the packed hash, i.e. half b & 1 of word b >> 1).
+// Two hashes within max_dist <= 31 differ in at most 1 bit in at least one block (16 x 2 = 32 > 31); within max_dist <= 15
+// they agree in at least one block. With r = 1 (resp. 0) only pairs whose key of some block is within r bits are candidates:
+// on uniform hashes ~1/241 of all pairs at 1 M hashes. Every pass rebuilds the index in the context's scratch:
+//   k_index_clear    zero the 16 histograms of 65 536 keys
+//   k_index_hist     one thread per hash: 16 increments
+//   k_index_stats    one thread per (block, key): exact candidates and the longest work item; the last workgroup decides
+//                    (select[kSelIdxUsed], hvd_kernels.h: index_wins) -- the matrix-core forms return at once when it is set
+//   k_index_scan     exclusive scan per block -> bucket offsets (and the scatter's cursors)
+//   k_index_scatter  one thread per hash: bucket-ordered per-block copies {hash, row}
+//   k_index_join     one wave per work item (block b, key u): B_u x B_u (positions i < j) and B_u x B_{u ^ (1 << t)} for
+//                    the one-bit neighbours above u; the full 256-bit distance, and a pair is emitted only by its CANONICAL
+//                    block -- the first block whose keys are within r -- so it comes out exactly once, without a dedup pass
+// Kernels of the first three steps return at once unless the probe's gate (select[kSelIdxGate]) is set, the last three unless
+// the decision is. Nothing waits on the host.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <mutex>
+
+#include "hvd_kernels.h"
+
+namespace {
+
+constexpr uint32_t kBlocks = 16, kKeys = 65536;
+constexpr uint32_t kWavePairs = 256;  // a wave's pair buffer in LDS; full -> one atomic reserves room for all of it
+
+__device__ __forceinline__ uint32_t key_of(const uint32_t w[8], uint32_t b) { return (w[b >> 1] >> (16u * (b & 1u))) & 0xFFFFu; }
+
+__device__ __forceinline__ void load_words(const uint4* __restrict__ db, uint32_t i, uint32_t w[8]) {
+    const uint4 h0 = db[(size_t)i * 2u], h1 = db[(size_t)i * 2u + 1u];
+    w[0] = h0.x; w[1] = h0.y; w[2] = h0.z; w[3] = h0.w;
+    w[4] = h1.x; w[5] = h1.y; w[6] = h1.z; w[7] = h1.w;
+}
+
+__global__ __launch_bounds__(256) void k_index_clear(uint4* __restrict__ cnt, const uint32_t* __restrict__ select) {
+    if (select[hvd::kSelIdxGate] == 0u) return;
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t < kBlocks * kKeys / 4u) cnt[t] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+__global__ __launch_bounds__(256) void k_index_hist(const uint4* __restrict__ db, uint32_t n, uint32_t* __restrict__ cnt,
+                                                    const uint32_t* __restrict__ select) {
+    if (select[hvd::kSelIdxGate] == 0u) return;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    uint32_t w[8];
+    load_words(db, i, w);
+#pragma unroll
+    for (uint32_t b = 0; b < kBlocks; ++b)
+        __hip_atomic_fetch_add(&cnt[b * kKeys + key_of(w, b)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Candidates of key u in its block: C(c_u, 2) + (r = 1) c_u x c_v over the one-bit neighbours v = u ^ (1 << t) above u --
+// the exact number of pairs whose keys of this block are within r, i.e. the pairs the join walks for this work item.
+__global__ __launch_bounds__(256) void k_index_stats(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ select,
+                                                     const hvd::IndexRule q) {
+    if (select[hvd::kSelIdxGate] == 0u) return;
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;  // < kBlocks * kKeys: the grid is exact
+    const uint32_t u = t & (kKeys - 1u);
+    const uint32_t* cb = cnt + (t & ~(kKeys - 1u));
+    const unsigned long long c = cb[u];
+    unsigned long long cand = c * (c - (c != 0ull)) / 2ull, ylen = c;
+    if (q.r != 0u && c != 0ull) {
+#pragma unroll
+        for (uint32_t s = 0; s < 16u; ++s)
+            if (((u >> s) & 1u) == 0u) ylen += cb[u ^ (1u << s)];
+        cand += c * (ylen - c);
+    }
+    // the work item's walk: its wave steps its c x's over a y list of ylen entries (saturated: any such item loses anyway)
+    uint32_t mx = (uint32_t)min(c * ylen, 0xFFFFFFFFull);
+    for (int off = 32; off > 0; off >>= 1) {
+        cand += __shfl_down(cand, off);
+        mx = max(mx, (uint32_t)__shfl_down((int)mx, off));
+    }
+    __shared__ unsigned long long part[4];
+    __shared__ uint32_t partm[4];
+    if ((threadIdx.x & 63u) == 0u) {
+        part[threadIdx.x >> 6] = cand;
+        partm[threadIdx.x >> 6] = mx;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0u) return;
+    const unsigned long long sum = part[0] + part[1] + part[2] + part[3];
+    const uint32_t m = max(max(partm[0], partm[1]), max(partm[2], partm[3]));
+    unsigned long long* cand_w = reinterpret_cast<unsigned long long*>(select + hvd::kSelIdxCand);
+    // (as the probe: the sums travel in returning atomics, and the ticket is taken after they have returned)
+    unsigned long long seen = 0;
+    if (sum) seen += atomicAdd(cand_w, sum);
+    if (m) seen += atomicMax(&select[hvd::kSelIdxMaxWalk], m);
+    asm volatile("" ::"v"(seen));
+    if (atomicAdd(&select[hvd::kSelIdxTicket], 1u) == gridDim.x - 1u) {
+        const unsigned long long total = atomicAdd(cand_w, 0ull);
+        const uint32_t big = atomicMax(&select[hvd::kSelIdxMaxWalk], 0u);
+        const uint32_t form = atomicAdd(&select[0], 0u);
+        select[hvd::kSelIdxUsed] = hvd::index_wins(q, (double)total, (double)big, form) ? 1u : 0u;
+    }
+}
+
+// One workgroup per block: 1024 threads x 64 keys. off[b][0..65536] = exclusive prefix (off[b][65536] = n); the counters
+// become the scatter's cursors.
+__global__ __launch_bounds__(1024) void k_index_scan(uint32_t* __restrict__ cnt, uint32_t* __restrict__ off,
+                                                     const uint32_t* __restrict__ select) {
+    if (select[hvd::kSelIdxUsed] == 0u) return;
+    const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint4* c4 = reinterpret_cast<uint4*>(cnt + (size_t)b * kKeys + tid * 64u);
+    uint32_t v[64];
+    uint32_t sum = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const uint4 x = c4[k];
+        v[4 * k] = x.x; v[4 * k + 1] = x.y; v[4 * k + 2] = x.z; v[4 * k + 3] = x.w;
+        sum += x.x + x.y + x.z + x.w;
+    }
+    // inclusive scan of the thread sums: within the wave, then over the 16 waves
+    uint32_t incl = sum;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(incl, d);
+        if (lane >= (uint32_t)d) incl += y;
+    }
+    __shared__ uint32_t wsum[16];
+    if (lane == 63u) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t base = 0;
+    for (uint32_t w = 0; w < wave; ++w) base += wsum[w];
+    uint32_t run = base + incl - sum;
+    uint32_t* ob = off + (size_t)b * (kKeys + 1u) + tid * 64u;
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+        const uint32_t x = v[k];
+        v[k] = run;
+        run += x;
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        c4[k] = make_uint4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+        ob[4 * k] = v[4 * k]; ob[4 * k + 1] = v[4 * k + 1]; ob[4 * k + 2] = v[4 * k + 2]; ob[4 * k + 3] = v[4 * k + 3];
+    }
+    if (tid == 1023u) off[(size_t)b * (kKeys + 1u) + kKeys] = run;
+}
+
+// hc[b][pos] = {hash words 0..3, 4..7}, rows[b][pos] = row, in key order (order inside a bucket: whatever the atomics give --
+// the join's rule does not depend on it)
+__global__ __launch_bounds__(256) void k_index_scatter(const uint4* __restrict__ db, uint32_t n, uint32_t* __restrict__ cnt,
+                                                       uint4* __restrict__ hc, uint32_t* __restrict__ rows,
+                                                       const uint32_t* __restrict__ select) {
+    if (select[hvd::kSelIdxUsed] == 0u) return;
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint4 h0 = db[(size_t)i * 2u], h1 = db[(size_t)i * 2u + 1u];
+    const uint32_t w[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+    uint32_t pos[kBlocks];
+#pragma unroll
+    for (uint32_t b = 0; b < kBlocks; ++b) pos[b] = atomicAdd(&cnt[b * kKeys + key_of(w, b)], 1u);  // (all 16 in flight)
+#pragma unroll
+    for (uint32_t b = 0; b < kBlocks; ++b) {
+        const size_t p = (size_t)b * n + pos[b];
+        hc[p * 2u] = h0;
+        hc[p * 2u + 1u] = h1;
+        rows[p] = i;
+    }
+}
+
+__device__ __forceinline__ uint32_t popc4(const uint4& x, const uint4& y) {
+    return __popc(x.x ^ y.x) + __popc(x.y ^ y.y) + __popc(x.z ^ y.z) + __popc(x.w ^ y.w);
+}
+
+struct JoinArgs {
+    const uint32_t* off;
+    const uint4* hc;
+    const uint32_t* rows;
+    uint32_t n;
+    const int32_t* group;
+    hvd_pair* out;
+    unsigned long long cap;
+    unsigned long long* count;
+    uint32_t max_dist, r, rank, world;
+};
+
+// A wave's buffered pairs -> global: one atomic reserves room for all of them; beyond `cap` nothing is written but the count
+// still grows (the caller reports HVD_ERR_OVERFLOW with the number needed).
+__device__ __forceinline__ void flush_wave(const JoinArgs& a, const hvd_pair* buf, uint32_t fill, uint32_t lane) {
+    unsigned long long base = 0;
+    if (lane == 0u) base = atomicAdd(a.count, (unsigned long long)fill);
+    base = __shfl(base, 0);
+    for (uint32_t k = lane; k < fill; k += 64u)
+        if (base + k < a.cap) a.out[base + k] = buf[k];
+}
+
+// Work item = (block b, key u), one wave each; item (b << 16 | u) belongs to rank item mod world. The y list of an item is
+// its own bucket (segment 0) followed by the buckets u ^ (1 << t) > u (r = 1): lanes take 64 consecutive entries of it per
+// round; the x side is the bucket itself, staged 64 at a time in LDS and read as a broadcast. The 128 bits that do NOT hold
+// block b are compared first (a candidate's key agrees, its other bits are unrelated: ~64 of 128 differ); only when a lane of
+// the wave is within max_dist there does the wave look at the rest.
+__global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint32_t* __restrict__ select) {
+    __shared__ uint4 xs_a[4][64], xs_b[4][64];
+    __shared__ hvd_pair pbuf[4][kWavePairs];
+    if (select[hvd::kSelIdxUsed] == 0u) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t item = (blockIdx.x * 4u + wave) * a.world + a.rank;
+    if (item >= kBlocks * kKeys) return;  // (wave-uniform; nothing below synchronises across waves)
+    const uint32_t b = item >> 16, u = item & (kKeys - 1u);
+    const uint32_t* offb = a.off + (size_t)b * (kKeys + 1u);
+    const uint32_t s0 = offb[u], nu = offb[u + 1u] - s0;
+    if (nu == 0u) return;
+    // segments: lane 0 the bucket itself, lane 1 + t the bucket u ^ (1 << t) if that key lies above u
+    uint32_t sstart = 0, ssize = 0;
+    if (lane == 0u) {
+        sstart = s0;
+        ssize = nu;
+    } else if (lane <= 16u && a.r != 0u && ((u >> (lane - 1u)) & 1u) == 0u) {
+        const uint32_t v = u ^ (1u << (lane - 1u));
+        sstart = offb[v];
+        ssize = offb[v + 1u] - sstart;
+    }
+    uint32_t incl = ssize;
+    for (int d = 1; d < 32; d <<= 1) {
+        const uint32_t y = __shfl_up(incl, d);
+        if (lane >= (uint32_t)d) incl += y;
+    }
+    const int delta = (int)sstart - (int)(incl - ssize);  // position = p + delta for an entry p of this segment
+    uint32_t ends[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) ends[s] = (uint32_t)__builtin_amdgcn_readlane((int)incl, s);
+    const uint32_t ny = (uint32_t)__builtin_amdgcn_readlane((int)incl, 16);
+    const size_t base = (size_t)b * a.n;
+    const uint4* __restrict__ hb = a.hc + base * 2u;
+    const uint32_t sa = b < 8u ? 1u : 0u;  // the 16-B half that does not hold block b: compared first
+    const uint32_t nxc = (nu + 63u) >> 6;
+    auto stage = [&](uint32_t xc) {
+        const uint32_t k = xc * 64u + lane;
+        if (k < nu) {
+            xs_a[wave][lane] = hb[(size_t)(s0 + k) * 2u + sa];
+            xs_b[wave][lane] = hb[(size_t)(s0 + k) * 2u + (sa ^ 1u)];
+        }
+        __builtin_amdgcn_wave_barrier();
+    };
+    if (nxc == 1u) stage(0u);
+    uint32_t fill = 0;  // wave-uniform
+    hvd_pair* buf = pbuf[wave];
+    for (uint32_t p0 = 0; p0 < ny; p0 += 64u) {
+        const uint32_t p = p0 + lane;
+        uint32_t seg = 0;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) seg += p >= ends[s] ? 1u : 0u;
+        const uint32_t ypos = (uint32_t)((int)p + __shfl(delta, (int)seg));
+        const bool has_y = p < ny;
+        // x index k pairs with this y iff k < ylim: inside the bucket only the x before it (positions i < j)
+        const uint32_t ylim = !has_y ? 0u : seg == 0u ? p : nu;
+        uint4 ya = make_uint4(0u, 0u, 0u, 0u), yb = ya;
+        if (has_y) {
+            ya = hb[(size_t)ypos * 2u + sa];
+            yb = hb[(size_t)ypos * 2u + (sa ^ 1u)];
+        }
+        for (uint32_t xc = 0; xc < nxc; ++xc) {
+            if (nxc > 1u) {
+                __builtin_amdgcn_wave_barrier();  // (every lane is done with the previous chunk)
+                stage(xc);
+            }
+            const uint32_t xn = min(64u, nu - xc * 64u), k0 = xc * 64u;
+            for (uint32_t k = 0; k < xn; ++k) {
+                const uint32_t d0 = popc4(xs_a[wave][k], ya);
+                const bool c = d0 <= a.max_dist && k0 + k < ylim;
+                if (__builtin_expect(__any(c), 0)) {
+                    bool emit = false;
+                    uint32_t d = 0, i = 0, j = 0;
+                    if (c) {
+                        const uint4 xa = xs_a[wave][k], xb = xs_b[wave][k];
+                        d = d0 + popc4(xb, yb);
+                        emit = d <= a.max_dist;
+                        if (emit) {
+                            const uint4 lo_x = sa ? xb : xa, hi_x = sa ? xa : xb, lo_y = sa ? yb : ya, hi_y = sa ? ya : yb;
+                            const uint32_t dw[8] = {lo_x.x ^ lo_y.x, lo_x.y ^ lo_y.y, lo_x.z ^ lo_y.z, lo_x.w ^ lo_y.w,
+                                                    hi_x.x ^ hi_y.x, hi_x.y ^ hi_y.y, hi_x.z ^ hi_y.z, hi_x.w ^ hi_y.w};
+                            for (uint32_t b2 = 0; b2 < b; ++b2)  // an earlier block within r owns this pair
+                                if ((uint32_t)__popc(key_of(dw, b2)) <= a.r) {
+                                    emit = false;
+                                    break;
+                                }
+                        }
+                        if (emit) {
+                            const uint32_t ri = a.rows[base + s0 + k0 + k], rj = a.rows[base + ypos];
+                            if (a.group != nullptr && a.group[ri] == a.group[rj]) emit = false;
+                            i = min(ri, rj);
+                            j = max(ri, rj);
+                        }
+                    }
+                    const unsigned long long em = __ballot(emit);
+                    const uint32_t m = (uint32_t)__popcll(em);
+                    if (m != 0u) {
+                        if (fill + m > kWavePairs) {
+                            flush_wave(a, buf, fill, lane);
+                            fill = 0;
+                        }
+                        if (emit) {
+                            const uint32_t slot = fill + __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
+                            hvd_pair rec;
+                            rec.i = i;
+                            rec.j = j;
+                            rec.dist = d;
+                            rec.pad = 0;
+                            buf[slot] = rec;
+                        }
+                        fill += m;
+                    }
+                }
+            }
+        }
+    }
+    if (fill != 0u) flush_wave(a, buf, fill, lane);
+}
+
+}  // namespace
+
+namespace hvd {
+
+int g_allpairs_index = -1;
+int g_allpairs_index_fail = 0;
+
+// per-context scratch: counters [16][65536], offsets [16][65537], hash copies [16][n] x 32 B, rows [16][n]
+struct IndexScratch {
+    void* p = nullptr;
+    size_t cap = 0;
+};
+constexpr int kMaxIdxCtx = 16;
+static IndexScratch g_idx[kMaxIdxCtx];
+static std::mutex g_idx_mu;
+
+static size_t off_words() { return ((size_t)kBlocks * (kKeys + 1u) + 3u) & ~(size_t)3u; }
+static size_t index_bytes(uint32_t n) {
+    return 4u * (size_t)kBlocks * kKeys + 4u * off_words() + (size_t)kBlocks * n * 32u + (size_t)kBlocks * n * 4u;
+}
+struct IndexPtrs {
+    uint32_t* cnt;
+    uint32_t* off;
+    uint4* hc;
+    uint32_t* rows;
+};
+static IndexPtrs index_ptrs(int ctx_id, uint32_t n) {
+    char* p = (char*)g_idx[ctx_id].p;
+    IndexPtrs q;
+    q.cnt = (uint32_t*)p;
+    q.off = (uint32_t*)(p + 4u * (size_t)kBlocks * kKeys);
+    q.hc = (uint4*)(p + 4u * (size_t)kBlocks * kKeys + 4u * off_words());
+    q.rows = (uint32_t*)((char*)q.hc + (size_t)kBlocks * n * 32u);
+    return q;
+}
+
+bool index_eligible(const AllPairsArgs& a, bool rect, uint32_t* r) {
+    if (g_allpairs_index == 0 || rect || a.sink.set != nullptr || a.d_db == nullptr || a.max_dist > 31u || a.n < 2u) return false;
+    if (a.ctx_id < 0 || a.ctx_id >= kMaxIdxCtx) return false;
+    *r = a.max_dist >= 16u ? 1u : 0u;
+    // (a small DB never pays for the index's fixed cost: no scratch, no launches; any matrix-core form may be the probe's)
+    return g_allpairs_index == 1 || index_wins(index_rule(a, *r), 0.0, 0.0, 0u);
+}
+
+IndexRule index_rule(const AllPairsArgs& a, uint32_t r) {
+    IndexRule q;
+    q.pairs = (double)a.n * (double)(a.n - 1u) / 2.0;
+    q.n = (double)a.n;
+    q.r = r;
+    q.force = g_allpairs_index == 1 ? 1u : 0u;
+    q.world = a.world;
+    // (DESIGN 4.1, 1 M uniform hashes on MI355X: form 9 18.1 ms = 36 fs per comparison, forms 18 / 12 +4 / +11 %; join 2.08 ms
+    // for 2.075e9 candidates; histograms + statistics + scan + scatter 2.2 ms = 2.2 ns per hash; the longest work item's wave
+    // takes ~30 ns per step of 64 pairs)
+    q.fs_mfma_fetch = 36.0f;
+    q.fs_mfma_other = 40.0f;
+    q.ps_cand = 1.0f;
+    q.ps_hash = 2200.0f;
+    q.ps_crit = 500.0f;
+    q.fixed_ns = 40000.0f;
+    return q;
+}
+
+hipError_t index_reserve(int ctx_id, uint32_t n) {
+    if (ctx_id < 0 || ctx_id >= kMaxIdxCtx) return hipErrorInvalidValue;
+    if (g_allpairs_index_fail == ctx_id + 1) return hipErrorOutOfMemory;
+    std::lock_guard<std::mutex> lk(g_idx_mu);
+    IndexScratch& s = g_idx[ctx_id];
+    const size_t need = index_bytes(n);
+    if (s.cap >= need) return hipSuccess;
+    size_t free_b = 0, total_b = 0;
+    hipError_t e = hipMemGetInfo(&free_b, &total_b);
+    if (e != hipSuccess) return e;
+    // (keep a quarter of what is free for everything else; the old buffer is given back first)
+    if ((double)need > 0.75 * (double)(free_b + s.cap)) return hipErrorOutOfMemory;
+    if (s.p) {
+        (void)hipFree(s.p);  // (waits for the device -- an earlier pass may still read it; the launch lock is not held here)
+        s.p = nullptr;
+        s.cap = 0;
+    }
+    e = hipMalloc(&s.p, need);
+    if (e != hipSuccess) {
+        s.p = nullptr;
+        (void)hipGetLastError();  // (the pass goes on without the index: leave no sticky error behind)
+        return e;
+    }
+    s.cap = need;
+    return hipSuccess;
+}
+
+hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const IndexRule& q, hipStream_t s) {
+    const IndexPtrs p = index_ptrs(a.ctx_id, a.n);
+    hipLaunchKernelGGL(k_index_clear, dim3(kBlocks * kKeys / 4u / 256u), dim3(256), 0, s, (uint4*)p.cnt, d_select);
+    hipLaunchKernelGGL(k_index_hist, dim3((a.n + 255u) / 256u), dim3(256), 0, s, (const uint4*)a.d_db, a.n, p.cnt, d_select);
+    hipLaunchKernelGGL(k_index_stats, dim3(kBlocks * kKeys / 256u), dim3(256), 0, s, p.cnt, d_select, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t r, hipStream_t s) {
+    const IndexPtrs p = index_ptrs(a.ctx_id, a.n);
+    hipLaunchKernelGGL(k_index_scan, dim3(kBlocks), dim3(1024), 0, s, p.cnt, p.off, d_select);
+    hipLaunchKernelGGL(k_index_scatter, dim3((a.n + 255u) / 256u), dim3(256), 0, s, (const uint4*)a.d_db, a.n, p.cnt, p.hc,
+                       p.rows, d_select);
+    JoinArgs j;
+    j.off = p.off;
+    j.hc = p.hc;
+    j.rows = p.rows;
+    j.n = a.n;
+    j.group = a.d_group;
+    j.out = a.d_pairs;
+    j.cap = a.cap;
+    j.count = a.d_count;
+    j.max_dist = a.max_dist;
+    j.r = r;
+    j.rank = a.rank;
+    j.world = a.world;
+    const uint32_t items = (kBlocks * kKeys + a.world - 1u - a.rank) / a.world;  // this rank's items: rank, rank + world, ...
+    hipLaunchKernelGGL(k_index_join, dim3((items + 3u) / 4u), dim3(256), 0, s, j, (const uint32_t*)d_select);
+    return hipGetLastError();
+}
+
+void index_release() {
+    std::lock_guard<std::mutex> lk(g_idx_mu);
+    for (IndexScratch& s : g_idx) {
+        if (s.p) (void)hipFree(s.p);
+        s = IndexScratch();
+    }
+}
+
+}  // namespace hvd

@@ -653,8 +653,8 @@ __global__ __launch_bounds__(256, ((TILES == 4 && NBR == 4 && S1 == 2) || QUEUE)
     __shared__ uint4 lds0[kSuper * 8], lds1[kSuper * 8];
 
     // data-dependent choice between the forms of this kernel (launch_auto): all are launched, the probe's verdict lets one
-    // of them run
-    if (select != nullptr && *select != select_id) return;
+    // of them run -- or none, when the pass runs on the pigeonhole index (k_hamming_index.hip)
+    if (select != nullptr && (select[0] != select_id || select[hvd::kSelIdxUsed] != 0u)) return;
     // Clock telemetry (round 6): one workgroup in eight brackets its lifetime with the shader-cycle counter (s_memtime) and the
     // constant-rate counter (s_memrealtime) and adds both deltas to the context's accumulators -- effective shader clock of
     // a pass = cycles / ticks x the tick rate, averaged over the sampled workgroups' lifetimes (hvd_debug_get "mfma_pass_khz").
@@ -895,8 +895,12 @@ struct ProbeRule {  // survivors among `pairs` sampled pairs -> form (probe_deci
     uint32_t pairs_per_step, id_rare, id_mid, id_often;
     float mid_max_per_tile;
     int force_sel;  // >= 0: the first-stage selection is not the probe's to choose (hvd_debug_set "mfma_force_sel": tests, A/B runs)
+    uint32_t idx_r;  // the pass may run on the pigeonhole index with block radius idx_r; kNoIndex: it may not
+    hvd::IndexRule idx;
 };
-__device__ void probe_decide(uint32_t* __restrict__ select, uint32_t lo, uint32_t hi, uint32_t mix, const ProbeRule& rule);
+constexpr uint32_t kNoIndex = 0xFFu;
+__device__ void probe_decide(uint32_t* __restrict__ select, uint32_t lo, uint32_t hi, uint32_t mix, uint32_t close,
+                             const ProbeRule& rule);
 
 __global__ __launch_bounds__(256) void k_prefilter_probe(const uint4* __restrict__ img_q, uint32_t nq,
                                                          const uint4* __restrict__ img_t, uint32_t nt, uint32_t max_dist,
@@ -922,55 +926,82 @@ __global__ __launch_bounds__(256) void k_prefilter_probe(const uint4* __restrict
     const uint32_t m = c0 >= ncols ? 0u : min(kProbeColsPerWg, ncols - c0);
     // survivors of a first stage over bits 0..127 / over bits 128..255 / over bits 0..63 + 192..255 (per 64-bit unit u0..u3:
     // the same 32 popcounts as before, three sums instead of two)
-    uint32_t cnt = 0, cnt_hi = 0, cnt_mix = 0;
-    for (uint32_t k = 0; k < m; ++k) {
-        const uint32_t u0 = sign_popc(q[0], cols[k][0], sign_popc(q[1], cols[k][1], 0u)), u1 = sign_popc(q[2], cols[k][2], sign_popc(q[3], cols[k][3], 0u));
-        const uint32_t u2 = sign_popc(q[4], cols[k][4], sign_popc(q[5], cols[k][5], 0u)), u3 = sign_popc(q[6], cols[k][6], sign_popc(q[7], cols[k][7], 0u));
-        cnt += u0 + u1 <= max_dist ? 1u : 0u;
-        cnt_hi += u2 + u3 <= max_dist ? 1u : 0u;
-        cnt_mix += u0 + u3 <= max_dist ? 1u : 0u;
+    uint32_t cnt = 0, cnt_hi = 0, cnt_mix = 0, close = 0;
+    if (rule.idx_r == kNoIndex) {
+        for (uint32_t k = 0; k < m; ++k) {
+            const uint32_t u0 = sign_popc(q[0], cols[k][0], sign_popc(q[1], cols[k][1], 0u)), u1 = sign_popc(q[2], cols[k][2], sign_popc(q[3], cols[k][3], 0u));
+            const uint32_t u2 = sign_popc(q[4], cols[k][4], sign_popc(q[5], cols[k][5], 0u)), u3 = sign_popc(q[6], cols[k][6], sign_popc(q[7], cols[k][7], 0u));
+            cnt += u0 + u1 <= max_dist ? 1u : 0u;
+            cnt_hi += u2 + u3 <= max_dist ? 1u : 0u;
+            cnt_mix += u0 + u3 <= max_dist ? 1u : 0u;
+        }
+    } else {
+        // the same, from the 16 block distances (block 2c / 2c + 1 = dwords x, y / z, w of chunk c), and how many of them are
+        // within the index's radius: sum over the sample of the blocks whose keys the index would pair
+        for (uint32_t k = 0; k < m; ++k) {
+            uint32_t u[4];
+#pragma unroll
+            for (int c2 = 0; c2 < 4; ++c2) {
+                u[c2] = 0u;
+#pragma unroll
+                for (int c = 2 * c2; c < 2 * c2 + 2; ++c) {
+                    const uint32_t b0 = __popc(q[c].x ^ cols[k][c].x) + __popc(q[c].y ^ cols[k][c].y);
+                    const uint32_t b1 = __popc(q[c].z ^ cols[k][c].z) + __popc(q[c].w ^ cols[k][c].w);
+                    close += (b0 <= rule.idx_r ? 1u : 0u) + (b1 <= rule.idx_r ? 1u : 0u);
+                    u[c2] += b0 + b1;
+                }
+            }
+            cnt += u[0] + u[1] <= max_dist ? 1u : 0u;
+            cnt_hi += u[2] + u[3] <= max_dist ? 1u : 0u;
+            cnt_mix += u[0] + u[3] <= max_dist ? 1u : 0u;
+        }
     }
-    if (r >= rows) cnt = cnt_hi = cnt_mix = 0;
+    if (r >= rows) cnt = cnt_hi = cnt_mix = close = 0;
     for (int off = 32; off > 0; off >>= 1) {
         cnt += __shfl_down(cnt, off);
         cnt_hi += __shfl_down(cnt_hi, off);
         cnt_mix += __shfl_down(cnt_mix, off);
+        close += __shfl_down(close, off);
     }
     // one pair of atomics per WORKGROUP (same-address device atomics take ~8 ns each: per wave they were 65 us of a probe over
     // frame hashes), and the workgroup that finishes last turns the two sums into the decision -- one launch less per pass (a
     // one-lane kernel costs ~5 us plus the gap in front of it). No fence anywhere: the sums travel in atomics, which are
     // performed at the memory side, and a workgroup takes its ticket (select[4], zeroed by k_set_hit_ctx with the rest) only
     // after its own additions have RETURNED.
-    __shared__ uint32_t part[3][4];
+    __shared__ uint32_t part[4][4];
     if ((threadIdx.x & 63u) == 0u) {
         part[0][threadIdx.x >> 6] = cnt;
         part[1][threadIdx.x >> 6] = cnt_hi;
         part[2][threadIdx.x >> 6] = cnt_mix;
+        part[3][threadIdx.x >> 6] = close;
     }
     __syncthreads();
     if (threadIdx.x == 0u) {
         const uint32_t c_lo = part[0][0] + part[0][1] + part[0][2] + part[0][3];
         const uint32_t c_hi = part[1][0] + part[1][1] + part[1][2] + part[1][3];
         const uint32_t c_mix = part[2][0] + part[2][1] + part[2][2] + part[2][3];
+        const uint32_t c_close = part[3][0] + part[3][1] + part[3][2] + part[3][3];
         uint32_t seen = 0;
         if (c_lo) seen += atomicAdd(&select[1], c_lo);
         if (c_hi) seen += atomicAdd(&select[2], c_hi);
         if (c_mix) seen += atomicAdd(&select[5], c_mix);
+        if (c_close) seen += atomicAdd(&select[hvd::kSelIdxClose], c_close);
         asm volatile("" ::"v"(seen));  // (the returning form, and its result waited for)
         if (atomicAdd(&select[4], 1u) == gridDim.x * gridDim.y - 1u)
-            probe_decide(select, atomicAdd(&select[1], 0u), atomicAdd(&select[2], 0u), atomicAdd(&select[5], 0u), rule);
+            probe_decide(select, atomicAdd(&select[1], 0u), atomicAdd(&select[2], 0u), atomicAdd(&select[5], 0u),
+                         atomicAdd(&select[hvd::kSelIdxClose], 0u), rule);
     }
 }
 
 // The hit handler's launch-uniform arguments live in device memory (written by this one-lane kernel in stream order
 // in front of the pass), so that the rare handler call passes one pointer instead of ~30 argument registers that the
 // fast path's register allocation would have to keep clear.
-// (select != nullptr: the auto variant's launch -- the probe's words are cleared in the same launch)
+// (select != nullptr: the auto variant's launch -- the probe's and the index's words are cleared in the same launch)
 __global__ void k_set_hit_ctx(HitCtx* __restrict__ dst, const HitCtx src, uint32_t* __restrict__ select) {
     *dst = src;
     if (select != nullptr) {
 #pragma unroll
-        for (int k = 0; k < 6; ++k) select[k] = 0u;
+        for (int k = 0; k < 16; ++k) select[k] = 0u;
     }
 }
 
@@ -984,7 +1015,8 @@ __global__ void k_clk_reset(unsigned long long* clk) {
 // entry per surviving lane and nothing on the matrix pipe: right for real frame hashes, whose first 128 bits agree within the
 // tolerance for ~2e-4 of unrelated pairs. The register form (id_often) pays one MFMA per surviving tile however many pairs
 // survive in it: right when most tiles hold several survivors (a library whose hashes barely differ in either half).
-__device__ void probe_decide(uint32_t* __restrict__ select, uint32_t lo, uint32_t hi, uint32_t mix, const ProbeRule& rule) {
+__device__ void probe_decide(uint32_t* __restrict__ select, uint32_t lo, uint32_t hi, uint32_t mix, uint32_t close,
+                             const ProbeRule& rule) {
     // first the selection: the 128 bits that let the fewest unrelated pairs through (ties and near-ties stay with bits 0..127,
     // so that uniform data always runs the same configuration; an alternative has to be 20 % better than what it replaces);
     // then the form, from that selection's rate
@@ -1007,6 +1039,12 @@ __device__ void probe_decide(uint32_t* __restrict__ select, uint32_t lo, uint32_
     if (rate * (double)rule.pairs_per_step > 0.01)
         form = (rule.id_mid != 0u && rate * 1024.0 <= (double)rule.mid_max_per_tile) ? rule.id_mid : rule.id_often;
     select[0] = form;
+    // Pigeonhole index: the sample's close blocks estimate the pass's candidates; the histograms are built (and the exact
+    // decision taken from them, k_index_stats) only if the index could win at half that estimate.
+    if (rule.idx_r != kNoIndex) {
+        const double est = rule.pairs ? (double)close / (double)rule.pairs * rule.idx.pairs : 0.0;
+        select[hvd::kSelIdxGate] = hvd::index_wins(rule.idx, 0.5 * est, 0.0, form) ? 1u : 0u;
+    }
 }
 
 }  // namespace
@@ -1158,7 +1196,8 @@ hipError_t mfma_select_buffer(int ctx_id, uint32_t** out) {
     std::lock_guard<std::mutex> lk(alloc_mu);
     if (!g_select[ctx_id]) {
         static_assert(sizeof(HitCtx) <= 192, "hit context does not fit its slot");
-        // 24 B of select words, the hit context at +64, the clock telemetry's four accumulators at +768 (kClkWord)
+        // 64 B of select words (probe 0..5, index 6..12: hvd_kernels.h), the hit context at +64, the clock telemetry's four
+        // accumulators at +768 (kClkWord)
         uint32_t* p = nullptr;
         hipError_t e = hipMalloc((void**)&p, 1024);
         // (hipMemset on device memory does not wait: without the synchronisation it can land on top of the first context
@@ -1198,13 +1237,18 @@ void mfma_release() {
         if (p) (void)hipFree(p);
         p = nullptr;
     }
+    index_release();
 }
 
 // Probe, decide on the device, launch both candidate forms: the one the probe did not choose returns at once.
 // No host synchronisation. The DB is replicated and the probe is deterministic, so every rank of a multi-GPU
 // pass picks the same form (the tile partition depends on it).
+// A self pass may run on the pigeonhole index instead (k_hamming_index.hip): the probe's estimate gates its histograms, their
+// statistics decide exactly (select[kSelIdxUsed]), and the forms launched behind it return at once when the index runs. The
+// histograms are identical on every rank, so is the decision. idx_r: the index's block radius, kNoIndex if the pass may not
+// use it (launch_allpairs_mfma: eligibility and scratch are settled before the launch lock is taken).
 static hipError_t launch_auto(const AllPairsArgs& a, const void* d_img, bool rect, const void* d_img_q, uint32_t nq,
-                              const int32_t* d_group_t, hipStream_t s) {
+                              const int32_t* d_group_t, uint32_t idx_r, hipStream_t s) {
     uint32_t* sel = nullptr;
     hipError_t e = mfma_select_buffer(a.ctx_id, &sel);
     if (e != hipSuccess) return e;
@@ -1216,16 +1260,28 @@ static hipError_t launch_auto(const AllPairsArgs& a, const void* d_img, bool rec
     const uint32_t rows = nrows < kProbeRows ? nrows : kProbeRows, cols = a.n < kProbeCols ? a.n : kProbeCols;
     // (the pair queue keeps (column << 1 | half) in 32 bits)
     const uint32_t mid = fp4_rows_padded(a.n) < (1u << 31) ? g_mfma_auto_mid : 0u;
-    const ProbeRule rule = {(uint64_t)rows * cols, 8192u, 9u, mid, 12u, 0.01f * (float)g_mfma_auto_mid_max_x100, g_mfma_force_sel};
+    const IndexRule irule = idx_r != kNoIndex ? index_rule(a, idx_r) : IndexRule{};
+    const ProbeRule rule = {(uint64_t)rows * cols, 8192u, 9u, mid, 12u, 0.01f * (float)g_mfma_auto_mid_max_x100, g_mfma_force_sel,
+                            idx_r, irule};
     hipLaunchKernelGGL(k_prefilter_probe, dim3((rows + 255u) / 256u, (cols + kProbeColsPerWg - 1u) / kProbeColsPerWg), dim3(256), 0, s,
                        (const uint4*)(rect ? d_img_q : d_img), nrows, (const uint4*)d_img, a.n, a.max_dist, sel, rule);
+    if (idx_r != kNoIndex) {
+        e = launch_index_decide(a, sel, irule, s);
+        if (e != hipSuccess) return e;
+    }
     if (a.sync_decide) {
-        uint32_t form = 0;
-        e = hipMemcpyAsync(&form, sel, 4, hipMemcpyDeviceToHost, s);
+        uint32_t words[8] = {};
+        e = hipMemcpyAsync(words, sel, sizeof(words), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return e;
+        const uint32_t form = words[0];
         if (form != 9u && form != 12u && form != mid) return hipErrorUnknown;  // (the probe writes one of its rule's three ids)
+        if (words[kSelIdxUsed] != 0u) return launch_index_join(a, sel, idx_r, s);
         return launch_variant((int)form, a, d_img, rect, d_img_q, nq, d_group_t, sel, s, false);
+    }
+    if (idx_r != kNoIndex) {
+        e = launch_index_join(a, sel, idx_r, s);
+        if (e != hipSuccess) return e;
     }
     e = launch_variant(9, a, d_img, rect, d_img_q, nq, d_group_t, sel, s, false);
     if (e != hipSuccess) return e;
@@ -1249,7 +1305,7 @@ hipError_t launch_cross_mfma(const AllPairsArgs& a, const void* d_img_q, uint32_
     std::lock_guard<std::mutex> lk(g_launch_mu);
     if (a.max_dist >= 128u) return hipErrorInvalidValue;  // sign trick needs a positive threshold
     const int v = effective_variant(a.variant, a.max_dist, a.n);
-    if (v == 13) return launch_auto(a, d_img_t, true, d_img_q, nq, d_group_t, s);
+    if (v == 13) return launch_auto(a, d_img_t, true, d_img_q, nq, d_group_t, kNoIndex, s);
     return launch_variant(v, a, d_img_t, true, d_img_q, nq, d_group_t, nullptr, s);
 }
 
@@ -1265,8 +1321,19 @@ hipError_t launch_allpairs_mfma(const AllPairsArgs& a_in, const void* d_img, hip
         return launch_allpairs(a, s);
     }
     const int v = effective_variant(a.variant, a.max_dist, a.n);
+    // Pigeonhole index: ranks split its work items differently from the matrix-core tiles, so every rank of a pass must take
+    // the same path. Eligibility rests on shared inputs only; a rank that cannot get its scratch fails the pass (the group's
+    // agreement step hands the failure to every rank) instead of quietly walking other tiles. A lone rank falls back.
+    uint32_t idx_r = kNoIndex;
+    if (v == 13 && index_eligible(a, false, &idx_r)) {
+        const hipError_t e = index_reserve(a.ctx_id, a.n);
+        if (e != hipSuccess) {
+            if (a.world > 1u) return e;
+            idx_r = kNoIndex;
+        }
+    }
     std::lock_guard<std::mutex> lk(g_launch_mu);
-    if (v == 13) return launch_auto(a, d_img, false, nullptr, 0u, nullptr, s);
+    if (v == 13) return launch_auto(a, d_img, false, nullptr, 0u, nullptr, idx_r, s);
     return launch_variant(v, a, d_img, false, nullptr, 0u, nullptr, nullptr, s);
 }
 

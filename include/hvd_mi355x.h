@@ -230,6 +230,9 @@ int hvd_get_pdq_dct_mode(void);
  *   "mfma_auto_mid" 0|18, "mfma_auto_mid_max_x100" n       (auto variant: may it pick the panel-mark queue form -- 18 -- and the
  *                                                           survivor density per 1024-pair tile, x 0.01, up to which it does -- 500)
  *   "mfma_queue_packed" 0|1                                (0: the pair queue settles from the FP4 images only)
+ *   "allpairs_index" -1|0|1                                (auto variant, self pass, max_dist <= 31: the exact pigeonhole index path --
+ *                                                           -1 the device decides from its histograms (default) | never | whenever
+ *                                                           eligible; not the query x target or video searches)
  *   "mfma_force_sel" -1|0|1|2                              (which 128 bits the first stage sees: the probe's choice | bits 0..127 |
  *                                                           128..255 | 0..63 + 192..255)
  *   "pdq_hash_grid" n, "pdq_hash_prefetch" 0|1             (64x64 hash kernel: forced grid; next frame fetched ahead, off)
@@ -247,6 +250,9 @@ int hvd_debug_set(const char* key, int value);
 /* "mfma_auto_form": the form (9, 18 or 12) the last auto-variant launch ran;
  * "mfma_probe_survivors" / "mfma_probe_survivors_hi" / "mfma_probe_survivors_mix": what its probe counted over bits 0..127 /
  * 128..255 / 0..63 + 192..255; "mfma_auto_half": the selection the first stage ran on (0 / 1 / 2 in that order).
+ * "mfma_auto_form" keeps meaning the matrix-core form the probe chose, also when the pass ran on the pigeonhole index.
+ * "allpairs_index_used": 1 if the last auto-variant pass ran on the pigeonhole index, else 0; "allpairs_index_kcand": its exact
+ * candidate count / 1000 (0 when the probe's estimate kept the histograms from being built).
  * Synchronises the library stream.
  * "vmatch_us_local" / "vmatch_us_exchange" / "vmatch_us_fold": host microseconds of the three phases of the last video-level
  * search on the calling thread's context (local: packed hashes, probe, all-pairs pass, key set; exchange: agreement words,
