@@ -841,8 +841,8 @@ static hipError_t launch_hash_any(const void* d_frames, int64_t n, int h, int w,
 }
 
 hipError_t api_launch_hash(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
-                           void* d_quality, hipStream_t s) {
-    return launch_hash_any(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, s, false);
+                           void* d_quality, hipStream_t s, bool dihedral) {
+    return launch_hash_any(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, s, dihedral);
 }
 }  // namespace hvd
 

@@ -4,7 +4,8 @@
 // uploaded (async H2D), hashed (PDQ kernels) and its 36 bytes per frame downloaded. Uploading
 // batch k+1 overlaps hashing batch k; push() blocks only when every slot is still in flight,
 // which bounds the staging memory like the reference's blocking frame queue
-// (vpdqpy.py:115-117).
+// (vpdqpy.py:115-117). A dihedral hasher (hvd_hasher_create_dihedral) runs the same ring through the dihedral kernel
+// and downloads 8 x 32 bytes of hashes per frame.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,7 +36,7 @@ int api_context();                                // the calling thread's curren
 void api_set_context(int idx);
 size_t api_scratch_bytes(int64_t n, int h, int w, int channels);
 hipError_t api_launch_hash(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
-                           void* d_quality, hipStream_t s);
+                           void* d_quality, hipStream_t s, bool dihedral);
 }  // namespace hvd
 
 namespace {
@@ -104,6 +105,7 @@ struct hvd_hasher {
     int ctx = 0;           // the context (device of the group) this hasher was created on: every call runs there
     int copy_threads = default_copy_threads();  // threads that share one frame's copy into the ring (hvd_hasher_set_threads)
     int w = 0, h = 0, channels = 0;
+    bool dihedral = false;         // hvd_hasher_create_dihedral: 8 hashes per frame (hash_bytes() = 256)
     int64_t batch = 0;             // frames a slot holds
     int64_t limit = 0;             // frames after which the CURRENT batch is submitted: ramps up to `batch` (first_limit)
     size_t frame_bytes = 0;
@@ -113,6 +115,7 @@ struct hvd_hasher {
     std::vector<int32_t> quality;
     bool acquired = false;         // hvd_hasher_acquire handed out the next frame's slot memory
     int64_t acquired_n = 0;        // ... and hvd_hasher_acquire_n this many frames of it
+    size_t hash_bytes() const { return dihedral ? 8 * 32 : 32; }
 };
 
 // A video starts on an empty pipeline (the reference makes one hasher per video and finish() drains it, vpdqpy/vpdqpy.py:113-119):
@@ -153,7 +156,7 @@ static int collect(hvd_hasher* hs, Slot& s) {
         NsScope ns(g_ns_wait);
         S_TRY(hipEventSynchronize(s.done));
     }
-    hs->hashes.insert(hs->hashes.end(), s.h_hashes, s.h_hashes + 32 * s.in_flight);
+    hs->hashes.insert(hs->hashes.end(), s.h_hashes, s.h_hashes + hs->hash_bytes() * s.in_flight);
     hs->quality.insert(hs->quality.end(), s.h_quality, s.h_quality + s.in_flight);
     s.in_flight = 0;
     return HVD_OK;
@@ -161,13 +164,18 @@ static int collect(hvd_hasher* hs, Slot& s) {
 
 static int submit(hvd_hasher* hs, Slot& s) {
     if (s.filled == 0) return HVD_OK;
+    // the dihedral kernel has K1's strict arithmetic only: a switch to fma while a video is in progress fails here, before
+    // anything of this batch is enqueued (it stays staged), instead of hashing the rest of the video another way
+    if (hs->dihedral && hvd::g_pdq_dct_mode != 0)
+        return hvd::api_fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");
     NsScope ns(g_ns_submit);
     const int64_t m = s.filled;
     S_TRY(hipMemcpyAsync(s.d_frames, s.h_frames, hs->frame_bytes * (size_t)m, hipMemcpyHostToDevice, s.stream));
 #ifndef HVD_ABL_STREAM_NOHASH
-    S_TRY(hvd::api_launch_hash(s.d_frames, m, hs->h, hs->w, hs->channels, s.d_scratch, s.d_hashes, s.d_quality, s.stream));
+    S_TRY(hvd::api_launch_hash(s.d_frames, m, hs->h, hs->w, hs->channels, s.d_scratch, s.d_hashes, s.d_quality, s.stream,
+                               hs->dihedral));
 #endif
-    S_TRY(hipMemcpyAsync(s.h_hashes, s.d_hashes, 32 * (size_t)m, hipMemcpyDeviceToHost, s.stream));
+    S_TRY(hipMemcpyAsync(s.h_hashes, s.d_hashes, hs->hash_bytes() * (size_t)m, hipMemcpyDeviceToHost, s.stream));
     S_TRY(hipMemcpyAsync(s.h_quality, s.d_quality, 4 * (size_t)m, hipMemcpyDeviceToHost, s.stream));
     S_TRY(hipEventRecord(s.done, s.stream));
     s.in_flight = m;
@@ -179,8 +187,9 @@ static int submit(hvd_hasher* hs, Slot& s) {
 // The reference creates one VideoHasher per video (vpdqpy/vpdqpy.py:113) and videos come strictly one after the
 // other (dedup.py:346-352). Pinning and unpinning 6 x 32 MiB of host memory per video costs more than hashing a
 // short video, so a destroyed hasher's slots (pinned staging, device buffers, streams, events) are PARKED and the
-// next hvd_hasher_create with the same geometry takes them over. At most kMaxParked sets are kept (a GUI worker
-// and the CLI never run more than one or two hashers at a time); hvd_shutdown() releases them.
+// next hvd_hasher_create with the same geometry and kind (plain / dihedral: hash buffers of 32 / 256 bytes per frame) takes
+// them over. At most kMaxParked sets are kept (a GUI worker and the CLI never run more than one or two hashers at a time);
+// hvd_shutdown() releases them.
 namespace {
 constexpr size_t kMaxParked = 2;
 std::mutex g_park_mu;
@@ -245,18 +254,23 @@ int hvd_hasher_destroy(hvd_hasher* hs) {
     return HVD_OK;
 }
 
-int hvd_hasher_create(int width, int height, int channels, int64_t batch_frames, hvd_hasher** out) {
+}  // extern "C"
+
+static int create_hasher(int width, int height, int channels, int64_t batch_frames, bool dihedral, hvd_hasher** out) {
     if (!out) return hvd::api_fail(HVD_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (!hvd::api_dct_device()) return hvd::api_fail(HVD_ERR_STATE, "hvd_init() has not been called (no CPU fallback exists)");
     if (width < 64 || height < 64 || width > 4096 || height > 4096 || (channels != 1 && channels != 3) || batch_frames < 1)
         return hvd::api_fail(HVD_ERR_ARG, "bad hasher geometry %dx%dx%d batch %lld", width, height, channels,
                              (long long)batch_frames);
+    if (dihedral && hvd::g_pdq_dct_mode != 0)
+        return hvd::api_fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");
     {
         std::lock_guard<std::mutex> lk(g_park_mu);
         for (size_t k = g_parked.size(); k-- > 0;) {
             hvd_hasher* p = g_parked[k];
-            if (p->ctx == hvd::api_context() && p->w == width && p->h == height && p->channels == channels && p->batch == batch_frames) {
+            if (p->ctx == hvd::api_context() && p->w == width && p->h == height && p->channels == channels && p->batch == batch_frames &&
+                p->dihedral == dihedral) {
                 g_parked.erase(g_parked.begin() + (long)k);
                 p->copy_threads = default_copy_threads();
                 *out = p;
@@ -270,6 +284,7 @@ int hvd_hasher_create(int width, int height, int channels, int64_t batch_frames,
     hs->w = width;
     hs->h = height;
     hs->channels = channels;
+    hs->dihedral = dihedral;
     hs->batch = batch_frames;
     hs->frame_bytes = (size_t)width * height * channels;
     hs->limit = first_limit(hs);
@@ -279,11 +294,11 @@ int hvd_hasher_create(int width, int height, int channels, int64_t batch_frames,
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.done, hipEventDisableTiming);
         if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_frames, hs->frame_bytes * (size_t)batch_frames, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_hashes, 32 * (size_t)batch_frames, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_hashes, hs->hash_bytes() * (size_t)batch_frames, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_quality, 4 * (size_t)batch_frames, hipHostMallocDefault);
         if (e == hipSuccess) e = hipMalloc(&s.d_frames, hs->frame_bytes * (size_t)batch_frames);
         if (e == hipSuccess && scratch) e = hipMalloc(&s.d_scratch, scratch);
-        if (e == hipSuccess) e = hipMalloc(&s.d_hashes, 32 * (size_t)batch_frames);
+        if (e == hipSuccess) e = hipMalloc(&s.d_hashes, hs->hash_bytes() * (size_t)batch_frames);
         if (e == hipSuccess) e = hipMalloc(&s.d_quality, 4 * (size_t)batch_frames);
         if (e != hipSuccess) {
             free_hasher(hs);
@@ -295,6 +310,16 @@ int hvd_hasher_create(int width, int height, int channels, int64_t batch_frames,
     return HVD_OK;
 }
 
+extern "C" {
+
+int hvd_hasher_create(int width, int height, int channels, int64_t batch_frames, hvd_hasher** out) {
+    return create_hasher(width, height, channels, batch_frames, false, out);
+}
+
+int hvd_hasher_create_dihedral(int width, int height, int channels, int64_t batch_frames, hvd_hasher** out) {
+    return create_hasher(width, height, channels, batch_frames, true, out);
+}
+
 /* Zero-copy feed: *out_frame is where the NEXT frame (width*height*channels bytes) belongs, inside the
  * pinned batch slot, so a decoder can reformat straight into it (the reference makes a Python bytes copy
  * per frame instead, vpdqpy/vpdqpy.py:118). Blocks only when that slot's previous batch is still being
@@ -303,6 +328,10 @@ int hvd_hasher_acquire(hvd_hasher* hs, uint8_t** out_frame) {
     if (!hs || !out_frame) return hvd::api_fail(HVD_ERR_ARG, "NULL hasher/out_frame");
     CtxScope scope(hs->ctx);
     if (int rc = hvd::api_bind_device()) return rc;
+    if (hs->slot[hs->cur].filled >= hs->limit) {  // its submit failed (e.g. HVD_ERR_STATE): submit it before staging past it
+        if (int rc = submit(hs, hs->slot[hs->cur])) return rc;
+        hs->cur = (hs->cur + 1) % kSlots;
+    }
     Slot& s = hs->slot[hs->cur];
     if (s.filled == 0 && s.in_flight) {  // slot being reused: its previous batch must have landed
         if (int rc = collect(hs, s)) return rc;
@@ -377,11 +406,16 @@ int hvd_hasher_set_threads(hvd_hasher* hs, int n) {
     return HVD_OK;
 }
 
+}  // extern "C"
+
 /* Flushes the partial batch, waits for everything, returns all hashes / qualities in push
  * order (no quality filtering: that is VideoHasher.finish's policy, vpdqpy.py:119). The hasher
  * is empty afterwards and can be reused for the next video. */
-int hvd_hasher_finish(hvd_hasher* hs, uint8_t* out_hashes, int32_t* out_quality, int64_t cap, int64_t* out_n) {
+static int finish_hasher(hvd_hasher* hs, bool dihedral, uint8_t* out_hashes, int32_t* out_quality, int64_t cap, int64_t* out_n) {
     if (!hs || !out_n) return hvd::api_fail(HVD_ERR_ARG, "NULL hasher/out_n");
+    if (hs->dihedral != dihedral)
+        return hvd::api_fail(HVD_ERR_STATE, dihedral ? "hvd_hasher_finish_dihedral() on a plain hasher: use hvd_hasher_finish()"
+                                                     : "hvd_hasher_finish() on a dihedral hasher: use hvd_hasher_finish_dihedral()");
     CtxScope scope(hs->ctx);
     if (int rc = hvd::api_bind_device()) return rc;
     hs->acquired = false;
@@ -405,7 +439,7 @@ int hvd_hasher_finish(hvd_hasher* hs, uint8_t* out_hashes, int32_t* out_quality,
     if (n > cap) return hvd::api_fail(HVD_ERR_OVERFLOW, "need room for %lld frames, cap %lld", (long long)n, (long long)cap);
     if (n) {
         if (!out_hashes || !out_quality) return hvd::api_fail(HVD_ERR_ARG, "NULL output");
-        memcpy(out_hashes, hs->hashes.data(), 32 * (size_t)n);
+        memcpy(out_hashes, hs->hashes.data(), hs->hash_bytes() * (size_t)n);
         memcpy(out_quality, hs->quality.data(), 4 * (size_t)n);
     }
     hs->hashes.clear();
@@ -413,6 +447,17 @@ int hvd_hasher_finish(hvd_hasher* hs, uint8_t* out_hashes, int32_t* out_quality,
     hs->cur = 0;
     hs->limit = first_limit(hs);  // the next video starts on an empty pipeline again
     return HVD_OK;
+}
+
+extern "C" {
+
+int hvd_hasher_finish(hvd_hasher* hs, uint8_t* out_hashes, int32_t* out_quality, int64_t cap, int64_t* out_n) {
+    return finish_hasher(hs, false, out_hashes, out_quality, cap, out_n);
+}
+
+/* n*8*32 bytes: a frame's 8 variants back to back, in the dihedral kernel's order (vpdq.TRANSFORMS). */
+int hvd_hasher_finish_dihedral(hvd_hasher* hs, uint8_t* out_hashes8, int32_t* out_quality, int64_t cap, int64_t* out_n) {
+    return finish_hasher(hs, true, out_hashes8, out_quality, cap, out_n);
 }
 
 int hvd_hasher_pending(hvd_hasher* hs, int64_t* out_frames) {

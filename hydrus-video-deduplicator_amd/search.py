@@ -192,8 +192,8 @@ def transform_set(transforms, require_identity: bool = True) -> tuple[str, ...]:
 
 
 def fold_transformed_records(records_identity: np.ndarray, records_cross: np.ndarray, lengths: np.ndarray,
-                             cross_transforms, threshold: float = 50.0,
-                             policy: str | None = None) -> tuple[np.ndarray, np.ndarray]:
+                             cross_transforms, threshold: float = 50.0, policy: str | None = None,
+                             return_similarity: bool = False) -> tuple[np.ndarray, ...]:
     """The pair set of find_transformed_duplicates from its two searches (pure numpy; no device).
 
     records_identity: VMATCH records (a < b) of the videos against each other. records_cross: VMATCH records of the
@@ -202,7 +202,7 @@ def fold_transformed_records(records_identity: np.ndarray, records_cross: np.nda
     vpdq.TRANSFORMS. sim_T(A, B) is the largest similarity_of_records value of the pair over the identity record and the
     cross records of either direction (A_t vs B, B_t vs A); a pair is kept if int(sim_T) >= int(threshold).
     -> (pairs int64[m, 2] with a < b, sorted; transform int64[m]: the vpdq.TRANSFORMS index that reached sim_T, the lowest
-    index on a tie; identity is 0)."""
+    index on a tie; identity is 0), and with return_similarity=True a third array: sim_T float64[m]."""
     if int(threshold) < 1:
         raise ValueError("threshold < 1 would select every pair of videos")
     lengths = np.asarray(lengths, dtype=np.int64)
@@ -230,7 +230,8 @@ def fold_transformed_records(records_identity: np.ndarray, records_cross: np.nda
     first = np.ones(key.size, dtype=bool)
     first[1:] = key[1:] != key[:-1]
     keep = first & (sim.astype(np.int64) >= int(threshold))  # int() truncation as in fix_vpdq_similarity
-    return np.stack([lo[keep], hi[keep]], axis=1).reshape(-1, 2), tid[keep]
+    pairs = np.stack([lo[keep], hi[keep]], axis=1).reshape(-1, 2)
+    return (pairs, tid[keep], sim[keep]) if return_similarity else (pairs, tid[keep])
 
 
 def find_transformed_duplicates(variant_hashes, threshold: float = 50.0, policy: str | None = None,
@@ -248,7 +249,6 @@ def find_transformed_duplicates(variant_hashes, threshold: float = 50.0, policy:
     (match_videos_cross, a video never against its own variants)."""
     names = transform_set(transforms)
     cross = [t for t in names if t != "identity"]
-    K = len(cross)
 
     def blob(x):
         b = x.bytes if isinstance(x, vpdq.VpdqHash) else bytes(x)
@@ -266,26 +266,36 @@ def find_transformed_duplicates(variant_hashes, threshold: float = 50.0, policy:
         if any(len(b) != len(ident[-1]) for b in vb):
             raise ValueError(f"video {v}: the variants must hash the same frames as the identity")
         var.extend(vb)
-    V = len(ident)
     if int(threshold) < 1:
         raise ValueError("threshold < 1 would select every pair of videos")
+    pairs, tid, _ = transformed_pairs(ident, var, cross, threshold, policy)
+    return [(int(a), int(b), vpdq.TRANSFORMS[int(t)]) for (a, b), t in zip(pairs, tid)]
+
+
+def transformed_pairs(ident: list, var: list, cross, threshold: float = 50.0, policy: str | None = None,
+                      matcher=None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The two searches of find_transformed_duplicates and their fold, on validated blobs: ident[v] the identity hash of
+    video v, var[v * K + k] its variant under cross[k] (K = len(cross) non-identity names), as long as ident[v].
+    matcher: object with match_videos / match_videos_cross (default: the GPU entry points of this module).
+    -> fold_transformed_records(..., return_similarity=True)."""
+    mv, mvc = (match_videos, match_videos_cross) if matcher is None else (matcher.match_videos, matcher.match_videos_cross)
+    K = len(cross)
+    V = len(ident)
     if V == 0:
-        return []
+        return np.zeros((0, 2), np.int64), np.zeros(0, np.int64), np.zeros(0, np.float64)
     lengths = np.array([len(b) // 32 for b in ident], dtype=np.int64)
     offsets = np.zeros(V + 1, dtype=np.int64)
     np.cumsum(lengths, out=offsets[1:])
     frames = np.frombuffer(b"".join(ident), dtype=np.uint8).reshape(-1, 32)
     max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
-    recs_i = match_videos(frames, offsets, max_dist)
+    recs_i = mv(frames, offsets, max_dist)
     if K:
         offsets_q = np.zeros(V * K + 1, dtype=np.int64)
         np.cumsum(np.repeat(lengths, K), out=offsets_q[1:])
         frames_q = np.frombuffer(b"".join(var), dtype=np.uint8).reshape(-1, 32)
         vids = np.arange(V, dtype=np.int32)
-        recs_c = match_videos_cross(frames_q, offsets_q, frames, offsets, ids_q=np.repeat(vids, K), ids_t=vids,
-                                    max_dist=max_dist)
+        recs_c = mvc(frames_q, offsets_q, frames, offsets, ids_q=np.repeat(vids, K), ids_t=vids, max_dist=max_dist)
     else:
         recs_c = np.zeros(0, dtype=VMATCH_DTYPE)
-    pairs, tid = fold_transformed_records(recs_i, recs_c, lengths, [vpdq.TRANSFORMS.index(t) for t in cross],
-                                          threshold, policy)
-    return [(int(a), int(b), vpdq.TRANSFORMS[int(t)]) for (a, b), t in zip(pairs, tid)]
+    return fold_transformed_records(recs_i, recs_c, lengths, [vpdq.TRANSFORMS.index(t) for t in cross], threshold, policy,
+                                    return_similarity=True)

@@ -17,16 +17,22 @@ against the whole library (VpTreeManager.search_file semantics, db/vptree.py:865
 reported once, and the cache is updated exactly as the reference does (dedup.py:488-491), so a
 later run of either implementation continues incrementally. Hydrus I/O (marking the pairs) stays
 with the caller.
+
+Mirror-aware search (`store_transformed_hashes`, `find_transformed_duplicates`): the hashes of a video's mirror images
+and rotations (`vpdq.VideoHasher(..., transforms=...)`) live in a side table of this project that the reference ignores,
+    hvd_transformed_phashes(phash_sha256, transform, phash)        -- keyed by the SHA-256 of the identity phash BLOB
+so they follow the perceptual hash, whatever file or phash_id carries it.
 """
 
 from __future__ import annotations
 
+import hashlib
 import sqlite3
 from dataclasses import dataclass
 
 import numpy as np
 
-from . import search
+from . import search, vpdq
 
 QUALITY_TOLERANCE = 31  # db/DedupeDB.py:550-553
 
@@ -237,3 +243,124 @@ def find_potential_duplicates(conn: sqlite3.Connection, threshold: float = 50.0,
                          [(search_threshold, int(h)) for h in lib.hash_ids[file_pending]])
         conn.commit()
     return pairs, directed // 2
+
+
+TRANSFORMED_TABLE = "hvd_transformed_phashes"
+
+
+def transformed_key(identity_phash) -> bytes:
+    """The side table's key of a perceptual hash: SHA-256 of its BLOB in the current (post-0.10) format."""
+    b = identity_phash.bytes if isinstance(identity_phash, vpdq.VpdqHash) else bytes(identity_phash)
+    return hashlib.sha256(b).digest()
+
+
+def _has_transformed_table(conn: sqlite3.Connection) -> bool:
+    return conn.execute("SELECT 1 FROM sqlite_master WHERE type = 'table' AND name = ?",
+                        (TRANSFORMED_TABLE,)).fetchone() is not None
+
+
+def store_transformed_hashes(conn: sqlite3.Connection, variants: dict) -> bytes:
+    """Keep a video's variant hashes (the dict `VideoHasher.finish_transformed` / `Vpdq.computeTransformedHashes`
+    returns: transform name -> VpdqHash or bytes; "identity" required, the hash stored as the file's perceptual hash)
+    for `find_transformed_duplicates`. Every variant hashes the same frames: a multiple of 32 bytes, as long as the
+    identity. Upserts one row per non-identity variant (the identity is the library's own row), creates the table on
+    first use, commits. -> the key (`transformed_key` of the identity)."""
+    if "identity" not in variants:
+        raise ValueError("variants must include 'identity' (the hash stored as the file's perceptual hash)")
+    blobs = {}
+    for name, h in variants.items():
+        if name not in vpdq.TRANSFORMS:
+            raise ValueError(f"unknown transform {name!r}; expected names from {vpdq.TRANSFORMS}")
+        b = h.bytes if isinstance(h, vpdq.VpdqHash) else bytes(h)
+        if len(b) % 32:
+            raise ValueError(f"{name}: phash length not a multiple of 32")
+        blobs[name] = b
+    ident = blobs.pop("identity")
+    for name, b in blobs.items():
+        if len(b) != len(ident):
+            raise ValueError(f"{name}: the variants must hash the same frames as the identity")
+    key = transformed_key(ident)
+    conn.execute(f"CREATE TABLE IF NOT EXISTS {TRANSFORMED_TABLE} ( phash_sha256 BLOB NOT NULL, transform TEXT NOT NULL, "
+                 "phash BLOB NOT NULL, PRIMARY KEY ( phash_sha256, transform ) )")
+    conn.executemany(f"REPLACE INTO {TRANSFORMED_TABLE} ( phash_sha256, transform, phash ) VALUES ( ?, ?, ? )",
+                     [(key, name, b) for name, b in blobs.items()])
+    conn.commit()
+    return key
+
+
+def load_transformed_hashes(conn: sqlite3.Connection, identity_phash) -> dict:
+    """{transform name: bytes} stored for a perceptual hash, "identity" (the argument) included."""
+    ident = identity_phash.bytes if isinstance(identity_phash, vpdq.VpdqHash) else bytes(identity_phash)
+    out = {"identity": ident}
+    if _has_transformed_table(conn):
+        out.update((t, bytes(b)) for t, b in conn.execute(
+            f"SELECT transform, phash FROM {TRANSFORMED_TABLE} WHERE phash_sha256 = ?", (transformed_key(ident),)))
+    return out
+
+
+def find_transformed_duplicates(conn: sqlite3.Connection, threshold: float = 50.0, transforms="mirror",
+                                policy: str | None = None, matcher=None, ingest_queue: bool = True):
+    """`search.find_transformed_duplicates` over the library in the database: the mirrored / flipped / rotated copies
+    among its files. -> (pairs, missing).
+
+    pairs: sorted list of (file_hash_a, file_hash_b, similarity, transform name) with hash_id_a < hash_id_b, similarity
+    sim_T of the two perceptual hashes and the transform that reached it (the search's rules: maximum over the
+    transforms of `transforms` and both directions, int(sim_T) >= int(threshold), the first name of vpdq.TRANSFORMS on a
+    tie); files sharing one non-empty perceptual hash give (..., 100.0, "identity"). missing: sorted phash_ids whose
+    variants for `transforms` are not all stored (`store_transformed_hashes`); they take no part. An empty perceptual
+    hash is never missing (its variants are empty too) and never similar to anything.
+
+    A full pass every time: `shape_search_cache` is neither read nor written, and no reference table is written except
+    by `ingest_phashed_file_queue` (ingest_queue=True, as in `find_potential_duplicates`). Device work: one
+    match_videos and one match_videos_cross call (matcher: object with both; default the GPU entry points)."""
+    names = search.transform_set(transforms)
+    cross = [t for t in names if t != "identity"]
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    if ingest_queue:
+        ingest_phashed_file_queue(conn)
+    lib = load_library(conn)
+    P = lib.phash_ids.size
+    lengths = lib.lengths
+    blobs = [lib.frames[lib.offsets[p]:lib.offsets[p + 1]].tobytes() for p in range(P)]
+    stored = {}
+    if cross and _has_transformed_table(conn):
+        marks = ", ".join("?" * len(cross))
+        for key, t, b in conn.execute(f"SELECT phash_sha256, transform, phash FROM {TRANSFORMED_TABLE} "
+                                      f"WHERE transform IN ( {marks} )", cross):
+            stored[(bytes(key), t)] = bytes(b)
+    included, missing, ident, var = [], [], [], []
+    for p in range(P):
+        if lengths[p] == 0:
+            vb = [b""] * len(cross)
+        else:
+            key = transformed_key(blobs[p])
+            vb = [stored.get((key, t)) for t in cross]
+            if any(b is None for b in vb):
+                missing.append(int(lib.phash_ids[p]))
+                continue
+            for t, b in zip(cross, vb):
+                if len(b) != len(blobs[p]):
+                    raise ValueError(f"phash_id {int(lib.phash_ids[p])}: stored {t} variant is not as long as the phash")
+        included.append(p)
+        ident.append(blobs[p])
+        var.extend(vb)
+    ph_pairs, tid, sim = search.transformed_pairs(ident, var, cross, threshold, policy, matcher=matcher)
+
+    files_of = [[] for _ in range(P)]
+    for f, p in enumerate(lib.phash_of_file):
+        files_of[int(p)].append(f)
+    found = {}
+    for (a, b), t, s_ in zip(ph_pairs, tid, sim):
+        pa, pb = included[int(a)], included[int(b)]
+        for fa in files_of[pa]:
+            for fb in files_of[pb]:
+                found[(min(fa, fb), max(fa, fb))] = (float(s_), vpdq.TRANSFORMS[int(t)])
+    for p in included:  # files sharing one non-empty perceptual hash are 100 % similar
+        fs = files_of[p]
+        if lengths[p] > 0:
+            for x in range(len(fs)):
+                for y in range(x + 1, len(fs)):
+                    found[(fs[x], fs[y])] = (100.0, "identity")
+    pairs = [(lib.file_hashes[a], lib.file_hashes[b], s_, t) for (a, b), (s_, t) in sorted(found.items())]
+    return pairs, sorted(missing)

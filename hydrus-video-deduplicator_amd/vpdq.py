@@ -182,12 +182,23 @@ class VideoHasher:
     staging memory like the reference's blocking frame queue (vpdqpy/vpdqpy.py:115-117). The
     reference's hasher runs a CPU thread pool instead; ``num_threads`` is accepted for signature
     compatibility; what it controls here is how many host threads share the copy of one frame into the ring
-    (0 = library default). One hasher per decoder thread."""
+    (0 = library default). One hasher per decoder thread.
+
+    ``transforms``: None (default) is the plain hasher. A set name of ``search.transform_set`` ("mirror", "flips",
+    "dihedral") or a sequence of ``TRANSFORMS`` names makes it a dihedral hasher (hvd_hasher_create_dihedral): the same
+    ring, every batch hashed by the dihedral kernel. ``finish_transformed()`` then returns ``{name: VpdqHash}`` for those
+    names and ``finish()`` the identity hash, which is what the plain hasher returns. Strict DCT mode only: in the "fma"
+    mode the constructor raises HvdError."""
 
     def __init__(self, average_fps: int, width: int, height: int, num_threads: int = 0,
-                 batch_bytes: int = 32 << 20):
+                 batch_bytes: int = 32 << 20, transforms=None):
         if width < 64 or height < 64:
             raise ValueError("frames must be at least 64x64")
+        self._transforms = None
+        if transforms is not None:
+            from .search import transform_set
+
+            self._transforms = transform_set(transforms, require_identity=False)
         self.average_fps = average_fps
         self.width = int(width)
         self.height = int(height)
@@ -202,12 +213,16 @@ class VideoHasher:
         self._run_pos = 0       # ... and how many of them commit_frame() has counted
         self._batch_run = None  # acquire_frames(): the run handed out
         self._lib = _lib.ensure()  # fail at construction, not at the first frame, if no GPU is usable
+        if self._transforms is not None and self._lib.hvd_get_pdq_dct_mode() != 0:
+            # the native hasher is created at the first frame (its pixel format decides the channels): fail here instead
+            raise _lib.HvdError(_lib.HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: set_dct_mode('strict') first")
 
     def _open(self, channels: int) -> None:
         frame_bytes = self._frame_bytes_rgb if channels == 3 else self._frame_bytes_gray
         batch = max(1, min(4096, self._batch_bytes // frame_bytes))
         h = C.c_void_p()
-        _lib.check(self._lib.hvd_hasher_create(self.width, self.height, channels, batch, C.byref(h)))
+        create = self._lib.hvd_hasher_create if self._transforms is None else self._lib.hvd_hasher_create_dihedral
+        _lib.check(create(self.width, self.height, channels, batch, C.byref(h)))
         self._handle = h
         self._channels = channels
         # num_threads: the reference hasher's worker threads (vpdqpy/vpdqpy.py:113; 0 = library default, negative =
@@ -319,26 +334,48 @@ class VideoHasher:
         _lib.check(self._lib.hvd_hasher_push(self._handle, ptr))
         del keep
 
-    def finish(self) -> VpdqHash:
+    def _drain(self) -> np.ndarray | None:
+        """Ends the hasher: the hashes of the frames kept by the quality filter (>= QUALITY_TOLERANCE, once per frame),
+        uint8[m,32] (plain) or uint8[m,8,32] (dihedral, TRANSFORMS order); None if no frame was fed."""
         self._finished = True
         if self._handle is None:
-            return VpdqHash(b"")
+            return None
         try:
             self._flush_run()
             self._batch_run = None
             pending = C.c_int64(0)
             _lib.check(self._lib.hvd_hasher_pending(self._handle, C.byref(pending)))
             n = pending.value
-            hashes = np.zeros((max(n, 1), BYTES_PER_PDQ_HASH), dtype=np.uint8)
+            if self._transforms is None:
+                shape, finish = (max(n, 1), BYTES_PER_PDQ_HASH), self._lib.hvd_hasher_finish
+            else:
+                shape, finish = (max(n, 1), len(TRANSFORMS), BYTES_PER_PDQ_HASH), self._lib.hvd_hasher_finish_dihedral
+            hashes = np.zeros(shape, dtype=np.uint8)
             quality = np.zeros(max(n, 1), dtype=np.int32)
             got = C.c_int64(0)
-            _lib.check(self._lib.hvd_hasher_finish(self._handle, hashes.ctypes.data, quality.ctypes.data, n,
-                                                   C.byref(got)))
+            _lib.check(finish(self._handle, hashes.ctypes.data, quality.ctypes.data, n, C.byref(got)))
             assert got.value == n
             hashes, quality = hashes[:n], quality[:n]
-            return VpdqHash(hashes[quality >= QUALITY_TOLERANCE].tobytes())
+            return hashes[quality >= QUALITY_TOLERANCE]
         finally:
             self.close()
+
+    def finish(self) -> VpdqHash:
+        """The video hash (vpdqpy.py:119); on a dihedral hasher its identity variant. Ends the hasher."""
+        kept = self._drain()
+        if kept is None:
+            return VpdqHash(b"")
+        return VpdqHash((kept if self._transforms is None else kept[:, 0]).tobytes())
+
+    def finish_transformed(self) -> dict:
+        """{transform name: VpdqHash} for the names given as ``transforms``, every variant over the same kept frames
+        (what ``Vpdq.computeTransformedHashes`` returns). Ends the hasher."""
+        if self._transforms is None:
+            raise RuntimeError("finish_transformed() on a plain hasher: create it with transforms=")
+        kept = self._drain()
+        if kept is None:
+            return {t: VpdqHash(b"") for t in self._transforms}
+        return {t: VpdqHash(kept[:, TRANSFORMS.index(t)].tobytes()) for t in self._transforms}
 
     def close(self) -> None:
         if self._handle is not None:

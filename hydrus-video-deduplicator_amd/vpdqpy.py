@@ -108,8 +108,10 @@ class Vpdq:
         """The video hashes of the video's mirror images / rotations: {transform name: VpdqHash}, for the names of
         `transforms` (a set name of ``search.transform_set`` -- "mirror", "flips", "dihedral" -- or a sequence of
         ``vpdq.TRANSFORMS`` names). Takes what ``computeHash`` takes; all variants come from one dihedral hashing pass
-        (vpdq.hash_frames_dihedral) and keep the SAME frames: the quality filter (>= QUALITY_TOLERANCE) is applied once,
-        per frame. ``["identity"]`` equals ``computeHash(frames)``."""
+        and keep the SAME frames: the quality filter (>= QUALITY_TOLERANCE) is applied once, per frame.
+        ``["identity"]`` equals ``computeHash(frames)``. An array goes through the batch entry
+        (vpdq.hash_frames_dihedral); an iterable is streamed through a dihedral ``vpdq.VideoHasher``, so host memory
+        stays bounded by its ring whatever the length of the video."""
         from .search import transform_set
 
         names = transform_set(transforms, require_identity=False)
@@ -128,17 +130,13 @@ class Vpdq:
         elif isinstance(frames, Iterable):
             w = DOWNSCALE_DIMENSIONS if width is None else int(width)
             h = DOWNSCALE_DIMENSIONS if height is None else int(height)
-            bufs = [np.frombuffer(f, dtype=np.uint8) for f in frames]
-            sizes = {b.size for b in bufs}
-            if len(sizes) > 1:
-                raise ValueError("all frames of one video must have the same pixel format")
-            size = sizes.pop() if sizes else h * w * 3
-            if size == h * w * 3:
-                arr = np.stack(bufs).reshape(-1, h, w, 3) if bufs else np.zeros((0, h, w, 3), np.uint8)
-            elif size == h * w:
-                arr = np.stack(bufs).reshape(-1, h, w)
-            else:
-                raise ValueError(f"frame has {size} bytes; expected {h * w * 3} (rgb24) or {h * w} (gray)")
+            hasher = vpdq.VideoHasher(1, w, h, transforms=names)
+            try:
+                for frame in frames:
+                    hasher.hash_frame(frame)
+                return hasher.finish_transformed()
+            finally:
+                hasher.close()
         else:
             raise ValueError("Failed to hash: invalid frames object type.")
         if arr.shape[1] < 64 or arr.shape[2] < 64:

@@ -39,7 +39,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -189,6 +189,15 @@ int hvd_hasher_pending(hvd_hasher* hs, int64_t* out_frames);
 /* All hashes (n*32 bytes) and qualities in push order; the hasher is reusable afterwards. */
 int hvd_hasher_finish(hvd_hasher* hs, uint8_t* out_hashes, int32_t* out_quality, int64_t cap, int64_t* out_n);
 int hvd_hasher_destroy(hvd_hasher* hs);
+/* Dihedral streaming hasher: the same ring, every batch hashed by the dihedral kernel (the 8 hashes of
+ * hvd_dev_pdq_hash_frames_dihedral per frame). push / acquire[_n] / commit[_n] / pending / set_threads / destroy work on
+ * it unchanged; its results come from hvd_hasher_finish_dihedral: n*8*32 bytes (a frame's 8 variants back to back, the
+ * order of hvd_dev_pdq_hash_frames_dihedral) and n qualities in push order. hvd_hasher_finish on a dihedral hasher and
+ * hvd_hasher_finish_dihedral on a plain one return HVD_ERR_STATE. Strict DCT mode only: create returns HVD_ERR_STATE
+ * in the fma mode, and a call that submits a batch (push, commit, finish) after a switch to fma returns HVD_ERR_STATE;
+ * the batch stays staged and is submitted by the next call. */
+int hvd_hasher_create_dihedral(int width, int height, int channels, int64_t batch_frames, hvd_hasher** out);
+int hvd_hasher_finish_dihedral(hvd_hasher* hs, uint8_t* out_hashes8, int32_t* out_quality, int64_t cap, int64_t* out_n);
 
 /* --------------------------------------------- device-resident API ------- */
 /* For pipelines that keep data in HBM (hash on the GPU, then search) and for the
