@@ -11,7 +11,8 @@ from .hashing import compute_phash, decode_phash_from_str, encode_phash_to_str, 
 from .search import (allpairs_hamming, calculate_distance, find_potential_duplicates, find_transformed_duplicates,  # noqa: F401
                      fix_vpdq_similarity, match_videos)
 from .vpdq import VideoHasher, VpdqHash, matchHash, matchHashBytes  # noqa: F401
-from .pipeline import DeviceLibrary, dedupe_frames_on_device, dedupe_videos, hash_videos  # noqa: F401
+from .pipeline import (DeviceLibrary, dedupe_frames_on_device, dedupe_transformed_frames_on_device, dedupe_videos,  # noqa: F401
+                       hash_videos)
 from .vpdqpy import Vpdq  # noqa: F401
 
 __version__ = "0.1.0"

@@ -89,6 +89,8 @@ SIGNATURES = {
     "hvd_dev_cross_hamming256_mfma": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _int, _int, _int, _vp, _i64, _vp]),
     "hvd_dev_video_of_frames": (_int, [_vp, _i64, _i64, _vp]),
     "hvd_dev_compact_kept": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "hvd_dev_compact_kept_dihedral": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             C.POINTER(_i64)]),
     "hvd_dev_vpdq_match_videos": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _i64, _vp]),
     "hvd_dev_vpdq_emit_again": (_int, [_vp, _i64, _vp]),
     "hvd_dev_vpdq_match_videos_cross": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _int, _int, _int, _vp, _i64,

@@ -123,6 +123,10 @@ size_t compact_scratch_bytes(unsigned long long n);
 hipError_t launch_compact_kept(const void* d_hashes, const int32_t* d_quality, unsigned long long n, const long long* d_offsets,
                                uint32_t V, int min_q, void* d_out_hashes, long long* d_out_offsets, int32_t* d_out_video,
                                void* d_scratch, unsigned long long* d_total, hipStream_t s);
+hipError_t launch_compact_kept_dihedral(const void* d_hashes8, const int32_t* d_quality, unsigned long long n,
+                                        const long long* d_offsets, uint32_t V, int min_q, uint32_t mask, void* d_out_hashes,
+                                        long long* d_out_offsets, int32_t* d_out_video, void* d_q_hashes, int32_t* d_q_video,
+                                        int32_t* d_q_excl, void* d_scratch, unsigned long long* d_total, hipStream_t s);
 hipError_t launch_video_of_frames(const long long* d_offsets, uint32_t V, unsigned long long n, int32_t* d_out_video,
                                   hipStream_t s);
 

@@ -868,6 +868,36 @@ int hvd_dev_compact_kept(const void* d_hashes, const void* d_quality, int64_t n,
     return HVD_OK;
 }
 
+int hvd_dev_compact_kept_dihedral(const void* d_hashes8, const void* d_quality, int64_t n, const void* d_offsets, int64_t V,
+                                  int min_quality, int transform_mask, void* d_out_hashes, void* d_out_offsets,
+                                  void* d_out_video, void* d_out_qhashes, void* d_out_qvideo, void* d_out_qexcl,
+                                  int64_t* out_kept) {
+    if (int rc = need_ready()) return rc;
+    if (!(transform_mask & 1) || transform_mask < 0 || transform_mask > 0xff)
+        return fail(HVD_ERR_ARG, "transform_mask=%d: bits 0..7 only, bit 0 (identity) set", transform_mask);
+    const int64_t K = __builtin_popcount((unsigned)transform_mask) - 1;
+    if (n < 0 || V < 0 || n >= (1ll << 32) - 1 || V >= (1ll << 31) || V * (K > 0 ? K : 1) >= (1ll << 31) || !d_offsets ||
+        !d_out_offsets || !out_kept)
+        return fail(HVD_ERR_ARG, "bad arguments");
+    if (n > 0 && (!d_hashes8 || !d_quality || !d_out_hashes || !d_out_video)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if (n > 0 && V == 0) return fail(HVD_ERR_ARG, "n=%lld frames in no video", (long long)n);
+    if (n > 0 && K > 0 && (!d_out_qhashes || !d_out_qvideo || !d_out_qexcl)) return fail(HVD_ERR_ARG, "NULL query output");
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    void* d_scr = nullptr;
+    unsigned long long* d_counters = nullptr;
+    SCR(S_COMPACT, hvd::compact_scratch_bytes((unsigned long long)n), d_scr);
+    SCR(S_COUNTERS, 64, d_counters);
+    HIP_TRY(hvd::launch_compact_kept_dihedral(d_hashes8, (const int32_t*)d_quality, (unsigned long long)n,
+                                              (const long long*)d_offsets, (uint32_t)V, min_quality, (uint32_t)transform_mask,
+                                              d_out_hashes, (long long*)d_out_offsets, (int32_t*)d_out_video, d_out_qhashes,
+                                              (int32_t*)d_out_qvideo, (int32_t*)d_out_qexcl, d_scr, d_counters + 2, g.stream));
+    unsigned long long kept = 0;
+    HIP_TRY(hipMemcpyAsync(&kept, d_counters + 2, 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    *out_kept = (int64_t)kept;
+    return HVD_OK;
+}
+
 int hvd_dev_vpdq_match_videos(const void* d_img, int64_t n, const void* d_video, int max_dist, int rank, int world,
                               void* d_out, int64_t cap, void* d_count) {
     if (int rc = need_ready()) return rc;

@@ -7,7 +7,8 @@
 //     may be found by two ranks);
 //   * VideoHasher.finish() for a whole library on the device: stream compaction of the frames with
 //     quality >= tolerance, per-video CSR offsets and the frame -> video map (vpdqpy/vpdqpy.py:119,
-//     db/DedupeDB.py:550-553, dedup.py:74-86), so that frames -> hashes -> search never leaves HBM.
+//     db/DedupeDB.py:550-553, dedup.py:74-86), so that frames -> hashes -> search never leaves HBM; its dihedral form
+//     also lays out the query set of the transformed search.
 // All of this is O(frames) byte shuffling next to the O(frames^2) compare; none of it is on the roofline.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -163,24 +164,18 @@ __device__ __forceinline__ uint32_t video_of_frame(const long long* __restrict__
     return lo;
 }
 
-// pos[f] = number of kept frames before raw frame f; kept frames are copied to their slot together with their
-// video index
-__global__ __launch_bounds__(256) void k_keep_scatter(const uint4* __restrict__ hashes, const int32_t* __restrict__ quality,
-                                                      unsigned long long n, int min_q,
-                                                      const uint32_t* __restrict__ block_prefix,
-                                                      const long long* __restrict__ offsets, uint32_t V,
-                                                      uint4* __restrict__ out_hashes, int32_t* __restrict__ out_video,
-                                                      uint32_t* __restrict__ pos) {
+// The keep flags of this lane's 4 frames and the number of kept frames before its first one (block_prefix: the scanned
+// block sums): an exclusive scan of the lanes' counts, by shuffles inside a wave, then over the 4 wave totals.
+__device__ __forceinline__ uint32_t keep_prefix(const int32_t* __restrict__ quality, unsigned long long n, int min_q,
+                                                const uint32_t* __restrict__ block_prefix, unsigned long long base,
+                                                bool (&keep)[4]) {
     __shared__ uint32_t wave_sum[4];
-    const unsigned long long base = (unsigned long long)blockIdx.x * kBlk + threadIdx.x * 4u;
-    bool keep[4];
     uint32_t c = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         keep[k] = base + k < n && quality[base + k] >= min_q;
         c += keep[k] ? 1u : 0u;
     }
-    // exclusive scan of c over the 256 lanes: wave scan by shuffles, then the 4 wave totals
     uint32_t incl = c;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (int off = 1; off < 64; off <<= 1) {
@@ -191,6 +186,20 @@ __global__ __launch_bounds__(256) void k_keep_scatter(const uint4* __restrict__ 
     __syncthreads();
     uint32_t before = block_prefix[blockIdx.x] + incl - c;
     for (uint32_t w = 0; w < wave; ++w) before += wave_sum[w];
+    return before;
+}
+
+// pos[f] = number of kept frames before raw frame f; kept frames are copied to their slot together with their
+// video index
+__global__ __launch_bounds__(256) void k_keep_scatter(const uint4* __restrict__ hashes, const int32_t* __restrict__ quality,
+                                                      unsigned long long n, int min_q,
+                                                      const uint32_t* __restrict__ block_prefix,
+                                                      const long long* __restrict__ offsets, uint32_t V,
+                                                      uint4* __restrict__ out_hashes, int32_t* __restrict__ out_video,
+                                                      uint32_t* __restrict__ pos) {
+    const unsigned long long base = (unsigned long long)blockIdx.x * kBlk + threadIdx.x * 4u;
+    bool keep[4];
+    uint32_t before = keep_prefix(quality, n, min_q, block_prefix, base, keep);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const unsigned long long f = base + k;
@@ -205,6 +214,24 @@ __global__ __launch_bounds__(256) void k_keep_scatter(const uint4* __restrict__ 
     }
 }
 
+// k_keep_scatter without the hash copy (the dihedral compaction moves the hashes in k_keep_variants, once the per-video
+// kept lengths are known)
+__global__ __launch_bounds__(256) void k_keep_positions(const int32_t* __restrict__ quality, unsigned long long n, int min_q,
+                                                        const uint32_t* __restrict__ block_prefix,
+                                                        const long long* __restrict__ offsets, uint32_t V,
+                                                        int32_t* __restrict__ out_video, uint32_t* __restrict__ pos) {
+    const unsigned long long base = (unsigned long long)blockIdx.x * kBlk + threadIdx.x * 4u;
+    bool keep[4];
+    uint32_t before = keep_prefix(quality, n, min_q, block_prefix, base, keep);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned long long f = base + k;
+        if (f >= n) break;
+        pos[f] = before;
+        if (keep[k]) out_video[before++] = (int32_t)video_of_frame(offsets, V, f);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_keep_offsets(const long long* __restrict__ offsets, uint32_t V, unsigned long long n,
                                                       const uint32_t* __restrict__ pos,
                                                       const unsigned long long* __restrict__ total,
@@ -213,6 +240,45 @@ __global__ __launch_bounds__(256) void k_keep_offsets(const long long* __restric
     if (u > V) return;
     const unsigned long long r = (unsigned long long)offsets[u];
     out_offsets[u] = r >= n ? (long long)total[0] : (long long)pos[r];
+}
+
+// Dihedral compaction, hash pass: every selected variant of every kept frame is read once and written to its place.
+// hashes8: n x 8 x 32 B (transform-minor). S selected variants, sel = their transform indices, 4 bits each, identity
+// (0) first. One lane per 16 B chunk: a frame takes 2S lanes of a group of 1 << lg_w (lanes past 2S idle), so the
+// selected bytes of a frame are read by neighbouring lanes. Variant 0 goes to the identity library at the frame's kept
+// index j; variant s > 0 (k = s - 1, K = S - 1) of a frame at position i of video v (kept offset o, kept length L) goes
+// to query slot K*o + k*L + i, query video v*K + k, exclusion id v -- the host layout of search.transformed_pairs.
+__global__ __launch_bounds__(256) void k_keep_variants(const uint4* __restrict__ hashes8, const int32_t* __restrict__ quality,
+                                                       unsigned long long n, int min_q, const uint32_t* __restrict__ pos,
+                                                       const int32_t* __restrict__ kept_video,
+                                                       const long long* __restrict__ kept_offsets, uint32_t sel, uint32_t S,
+                                                       uint32_t lg_w, unsigned long long q_cap,
+                                                       uint4* __restrict__ out_hashes, uint4* __restrict__ q_hashes,
+                                                       int32_t* __restrict__ q_video, int32_t* __restrict__ q_excl) {
+    const uint32_t c = threadIdx.x & ((1u << lg_w) - 1u);
+    if (c >= 2u * S) return;
+    const uint32_t s = c >> 1, half = c & 1u, t = (sel >> (4u * s)) & 7u, K = S - 1u;
+    const uint32_t per = 256u >> lg_w;  // frames per workgroup and step
+    for (unsigned long long f = (unsigned long long)blockIdx.x * per + (threadIdx.x >> lg_w); f < n;
+         f += (unsigned long long)gridDim.x * per) {
+        if (quality[f] < min_q) continue;
+        const uint4 val = hashes8[f * 16u + t * 2u + half];
+        const unsigned long long j = pos[f];
+        if (s == 0u) {
+            out_hashes[j * 2u + half] = val;
+            continue;
+        }
+        const uint32_t v = (uint32_t)kept_video[j];
+        const unsigned long long o = (unsigned long long)kept_offsets[v];
+        const unsigned long long len = (unsigned long long)kept_offsets[v + 1u] - o;
+        const unsigned long long slot = K * o + (s - 1u) * len + (j - o);
+        if (slot >= q_cap) continue;  // only raw offsets that are no CSR over the n frames get here
+        q_hashes[slot * 2u + half] = val;
+        if (half == 0u) {
+            q_video[slot] = (int32_t)(v * K + s - 1u);
+            q_excl[slot] = (int32_t)v;
+        }
+    }
 }
 
 // frame -> video map from CSR offsets (for libraries that arrive as hashes + offsets)
@@ -285,6 +351,41 @@ hipError_t launch_compact_kept(const void* d_hashes, const int32_t* d_quality, u
     }
     hipLaunchKernelGGL(k_keep_offsets, dim3((V + 1u + 255u) / 256u), dim3(256), 0, s, d_offsets, V, n, pos, d_total,
                        d_out_offsets);
+    return hipGetLastError();
+}
+
+// Dihedral form of launch_compact_kept. mask: bit t = transform t of the 8 hashes per frame (bit 0 set). The identity
+// library (out_hashes, out_offsets, out_video) is what launch_compact_kept makes of the plain hashes; q_*: the query
+// library of the K = popcount(mask) - 1 other variants (k_keep_variants).
+hipError_t launch_compact_kept_dihedral(const void* d_hashes8, const int32_t* d_quality, unsigned long long n,
+                                        const long long* d_offsets, uint32_t V, int min_q, uint32_t mask, void* d_out_hashes,
+                                        long long* d_out_offsets, int32_t* d_out_video, void* d_q_hashes, int32_t* d_q_video,
+                                        int32_t* d_q_excl, void* d_scratch, unsigned long long* d_total, hipStream_t s) {
+    const unsigned long long nb = (n + kBlk - 1) / kBlk;
+    uint32_t* sums = (uint32_t*)d_scratch;
+    uint32_t* pos = sums + (nb + 1);
+    if (n > 0) {
+        hipLaunchKernelGGL(k_keep_count, dim3((unsigned)nb), dim3(256), 0, s, d_quality, n, min_q, sums);
+        hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, sums, (uint32_t)nb, d_total);
+        hipLaunchKernelGGL(k_keep_positions, dim3((unsigned)nb), dim3(256), 0, s, d_quality, n, min_q, sums, d_offsets, V,
+                           d_out_video, pos);
+    } else {
+        hipError_t e = hipMemsetAsync(d_total, 0, 8, s);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_keep_offsets, dim3((V + 1u + 255u) / 256u), dim3(256), 0, s, d_offsets, V, n, pos, d_total,
+                       d_out_offsets);
+    if (n > 0) {
+        uint32_t sel = 0, S = 0;
+        for (uint32_t t = 0; t < 8u; ++t)
+            if (mask >> t & 1u) sel |= t << (4u * S++);
+        uint32_t lg_w = 1;
+        while ((1u << lg_w) < 2u * S) ++lg_w;
+        const unsigned long long groups = (n + (256u >> lg_w) - 1u) / (256u >> lg_w);
+        hipLaunchKernelGGL(k_keep_variants, dim3((unsigned)(groups < 16384ull ? groups : 16384ull)), dim3(256), 0, s,
+                           (const uint4*)d_hashes8, d_quality, n, min_q, pos, d_out_video, d_out_offsets, sel, S, lg_w,
+                           (unsigned long long)(S - 1u) * n, (uint4*)d_out_hashes, (uint4*)d_q_hashes, d_q_video, d_q_excl);
+    }
     return hipGetLastError();
 }
 

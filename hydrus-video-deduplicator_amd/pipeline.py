@@ -76,6 +76,38 @@ def hash_frames_on_device(d_frames_ptr: int, n: int, h: int, w: int, channels: i
     return d_h, d_q
 
 
+def hash_frames_dihedral_on_device(d_frames_ptr: int, n: int, h: int, w: int, channels: int):
+    """Dihedral form of `hash_frames_on_device`: -> (d_hashes8, d_quality) DeviceBuffers (n*8*32 B in vpdq.TRANSFORMS
+    order, int32[n]). Strict DCT mode only: the fma mode raises HvdError(HVD_ERR_STATE) before anything is launched."""
+    lib = _lib.ensure()
+    if lib.hvd_get_pdq_dct_mode() != 0:
+        raise _lib.HvdError(_lib.HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: set_dct_mode('strict') first")
+    d_h = DeviceBuffer(256 * max(n, 1))
+    d_q = DeviceBuffer(4 * max(n, 1))
+    sb = C.c_size_t(0)
+    _lib.check(lib.hvd_pdq_scratch_bytes(n, h, w, channels, C.byref(sb)))
+    d_s = DeviceBuffer(sb.value) if sb.value else None
+    _lib.check(lib.hvd_dev_pdq_hash_frames_dihedral(d_frames_ptr, n, h, w, channels, d_s.ptr if d_s else None, d_h.ptr,
+                                                    d_q.ptr))
+    if d_s is not None:
+        _lib.check(lib.hvd_dev_sync())  # the scratch must outlive the kernels
+        d_s.free()
+    return d_h, d_q
+
+
+def transform_mask(names) -> int:
+    """Transform names (search.transform_set) -> the mask of hvd_dev_compact_kept_dihedral (bit t = vpdq.TRANSFORMS[t])."""
+    return sum(1 << vpdq.TRANSFORMS.index(t) for t in names)
+
+
+def _check_raw_offsets(raw_offsets, n: int | None = None) -> np.ndarray:
+    raw_offsets = np.ascontiguousarray(raw_offsets, dtype=np.int64)
+    V = raw_offsets.size - 1
+    if (V < 0 or raw_offsets[0] != 0 or (n is not None and raw_offsets[-1] != n) or (np.diff(raw_offsets) < 0).any()):
+        raise ValueError("raw_offsets must be a CSR over the n frames")
+    return raw_offsets
+
+
 class DeviceLibrary:
     """A video library resident in HBM: kept frame hashes (CSR by video), their FP4 image and the
     frame -> video map -- the operand of the video-level search."""
@@ -108,6 +140,35 @@ class DeviceLibrary:
         finally:
             d_roff.free()
         return cls(d_out_h, d_out_off, d_out_vid, kept.value, V)
+
+    @classmethod
+    def from_raw_dihedral(cls, d_hashes8_ptr: int, d_quality_ptr: int, n: int, raw_offsets: np.ndarray, transforms,
+                          min_quality: int = vpdq.QUALITY_TOLERANCE) -> tuple["DeviceLibrary", "DeviceQueries | None"]:
+        """Quality filter + CSR of the dihedral hashes (hvd_dev_compact_kept_dihedral). transforms: names as
+        search.transform_set returns them (identity included). -> (identity library, the same as from_raw_hashes on the
+        plain hashes; query set of the other variants, None when there are none)."""
+        lib = _lib.ensure()
+        raw_offsets = _check_raw_offsets(raw_offsets, n)
+        V = raw_offsets.size - 1
+        cross = [t for t in transforms if t != "identity"]
+        K = len(cross)
+        d_roff = DeviceBuffer.from_array(raw_offsets)
+        d_out_h = DeviceBuffer(32 * max(n, 1))
+        d_out_off = DeviceBuffer(8 * (V + 1))
+        d_out_vid = DeviceBuffer(4 * max(n, 1))
+        d_qh, d_qv, d_qx = (DeviceBuffer(32 * K * max(n, 1)), DeviceBuffer(4 * K * max(n, 1)),
+                            DeviceBuffer(4 * K * max(n, 1))) if K else (None, None, None)
+        kept = C.c_int64(0)
+        try:
+            _lib.check(lib.hvd_dev_compact_kept_dihedral(
+                d_hashes8_ptr, d_quality_ptr, n, d_roff.ptr, V, int(min_quality), transform_mask(transforms), d_out_h.ptr,
+                d_out_off.ptr, d_out_vid.ptr, d_qh.ptr if K else None, d_qv.ptr if K else None, d_qx.ptr if K else None,
+                C.byref(kept)))
+        finally:
+            d_roff.free()
+        library = cls(d_out_h, d_out_off, d_out_vid, kept.value, V)
+        queries = DeviceQueries(d_qh, d_qv, d_qx, K * kept.value, K * V, tuple(cross)) if K else None
+        return library, queries
 
     @classmethod
     def from_host(cls, frames: np.ndarray, offsets: np.ndarray) -> "DeviceLibrary":
@@ -152,31 +213,68 @@ class DeviceLibrary:
         if max_dist < 0 or self.n_frames < 2:
             return np.zeros(0, dtype=VMATCH_DTYPE)
         cap = max(4096, self.n_videos) if cap is None else int(cap)
-        # the record buffer is kept from call to call (per context): two hipMalloc / hipFree round trips inside every search were
-        # ~1 % of a 50 000-video pass during which the GPU did nothing. Buffer, launch and read-back stay under the context's
-        # lock: two threads searching on one context would otherwise read each other's records, or free a buffer the other
-        # is still reading back.
-        with _record_lock():
-            d_out, d_cnt, _ = _record_buffers(cap)  # (the call is told `cap` as asked, whatever the kept buffer would hold)
-            _lib.check(lib.hvd_dev_vpdq_match_videos(self.image().ptr, self.n_frames, self.d_video.ptr, max_dist,
-                                                     rank, world, d_out.ptr, cap, d_cnt.ptr))
-            cnt = int(d_cnt.to_array(np.uint64, 1)[0])
-            if cnt > cap:  # more video pairs than room: ONLY the emit is repeated (no second O(n^2) pass, no second
-                # key exchange that every rank would have to enter in lock-step)
-                cap = cnt
-                d_out, d_cnt, _ = _record_buffers(cap)
-                _lib.check(lib.hvd_dev_vpdq_emit_again(d_out.ptr, cap, d_cnt.ptr))
-                cnt = int(d_cnt.to_array(np.uint64, 1)[0])
-                assert cnt <= cap
-            recs = d_out.to_array(VMATCH_DTYPE, cnt)
-        # ((a, b) is unique, so the sort need not be stable: numpy's default 64-bit sort is three times faster on 21 k records)
-        return recs[np.argsort((recs["a"].astype(np.uint64) << np.uint64(32)) | recs["b"])]
+        return _search_records(lambda d_out, cap_, d_cnt: lib.hvd_dev_vpdq_match_videos(
+            self.image().ptr, self.n_frames, self.d_video.ptr, max_dist, rank, world, d_out, cap_, d_cnt), cap)
+
+    def match_queries(self, queries: "DeviceQueries", max_dist: int | None = None, rank: int = 0, world: int = 1,
+                      cap: int | None = None) -> np.ndarray:
+        """hvd_dev_vpdq_match_videos_cross of a query set (from_raw_dihedral) against this library, a video never against
+        its own variants (the library's frame -> video map is the target's exclusion map). VMATCH_DTYPE records (a = query
+        video v*K + k, b = video) sorted by (a, b); the same record buffer, cap and emit-again retry as match_videos."""
+        lib = _lib.ensure()
+        max_dist = vpdq.frame_max_dist(search.DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
+        if max_dist < 0 or queries is None or queries.n_frames == 0 or self.n_frames == 0:
+            return np.zeros(0, dtype=VMATCH_DTYPE)
+        cap = max(4096, queries.n_videos) if cap is None else int(cap)
+        return _search_records(lambda d_out, cap_, d_cnt: lib.hvd_dev_vpdq_match_videos_cross(
+            queries.image().ptr, queries.n_frames, queries.d_video.ptr, queries.d_excl.ptr, self.image().ptr, self.n_frames,
+            self.d_video.ptr, self.d_video.ptr, max_dist, rank, world, d_out, cap_, d_cnt), cap)
 
     def free(self) -> None:
         for b in (self.d_hashes, self.d_offsets, self.d_video, self.d_img):
             if b is not None:
                 b.free()
         self.d_img = None
+
+
+class DeviceQueries(DeviceLibrary):
+    """The query operand of the transformed search (DeviceLibrary.from_raw_dihedral): the kept frames of every video v
+    under each of the K non-identity transforms, query video v*K + k for transforms[k], d_excl = v per frame."""
+
+    def __init__(self, d_hashes: DeviceBuffer, d_video: DeviceBuffer, d_excl: DeviceBuffer, n_frames: int, n_videos: int,
+                 transforms: tuple):
+        super().__init__(d_hashes, None, d_video, n_frames, n_videos)
+        self.d_excl, self.transforms = d_excl, transforms
+
+    def offsets(self) -> np.ndarray:
+        raise NotImplementedError("a query set has no CSR of its own: query video v*K + k has video v's kept frames")
+
+    def free(self) -> None:
+        super().free()
+        self.d_excl.free()
+
+
+def _search_records(launch, cap: int) -> np.ndarray:
+    """One device video search: launch(d_out, cap, d_count) -> status, then the records sorted by (a, b)."""
+    lib = _lib.ensure()
+    # the record buffer is kept from call to call (per context): two hipMalloc / hipFree round trips inside every search were
+    # ~1 % of a 50 000-video pass during which the GPU did nothing. Buffer, launch and read-back stay under the context's
+    # lock: two threads searching on one context would otherwise read each other's records, or free a buffer the other
+    # is still reading back (ADVICE r5).
+    with _record_lock():
+        d_out, d_cnt, _ = _record_buffers(cap)  # (the call is told `cap` as asked, whatever the kept buffer would hold)
+        _lib.check(launch(d_out.ptr, cap, d_cnt.ptr))
+        cnt = int(d_cnt.to_array(np.uint64, 1)[0])
+        if cnt > cap:  # more video pairs than room: ONLY the emit is repeated (no second O(n^2) pass, no second
+            # key exchange that every rank would have to enter in lock-step)
+            cap = cnt
+            d_out, d_cnt, _ = _record_buffers(cap)
+            _lib.check(lib.hvd_dev_vpdq_emit_again(d_out.ptr, cap, d_cnt.ptr))
+            cnt = int(d_cnt.to_array(np.uint64, 1)[0])
+            assert cnt <= cap
+        recs = d_out.to_array(VMATCH_DTYPE, cnt)
+    # ((a, b) is unique, so the sort need not be stable: numpy's default 64-bit sort is three times faster on 21 k records)
+    return recs[np.argsort((recs["a"].astype(np.uint64) << np.uint64(32)) | recs["b"])]
 
 
 _RECORD_BUFFERS: dict = {}  # context index -> (d_out, d_cnt, cap): grow-only, released by release_record_buffers()
@@ -223,29 +321,32 @@ def shard_frames(raw_offsets: np.ndarray, world: int) -> int:
                for r in range(world))
 
 
-def gather_hash_shards(d_h: DeviceBuffer, d_q: DeviceBuffer, raw_offsets: np.ndarray, rank: int, world: int, exchange):
+def gather_hash_shards(d_h: DeviceBuffer, d_q: DeviceBuffer, raw_offsets: np.ndarray, rank: int, world: int, exchange,
+                       hash_bytes: int = 32):
     """All-gather of the per-rank hash / quality shards (RCCL, equal-size padded blocks), then the padding is
-    squeezed out so that the frames are in library order. -> (d_hashes, d_quality) for the whole library."""
+    squeezed out so that the frames are in library order. hash_bytes: per frame (256 for the dihedral hashes).
+    -> (d_hashes, d_quality) for the whole library."""
     lib = _lib.ensure()
     V = raw_offsets.size - 1
     n_total = int(raw_offsets[-1])
     v_lo, v_hi = video_range_of_rank(V, rank, world)
     n_mine = int(raw_offsets[v_hi] - raw_offsets[v_lo])
     shard = max(1, shard_frames(raw_offsets, world))
-    d_all_h, d_all_q = DeviceBuffer(32 * shard * world), DeviceBuffer(4 * shard * world)
-    d_ph, d_pq = DeviceBuffer(32 * shard), DeviceBuffer(4 * shard)  # my shard, padded to the longest
+    d_all_h, d_all_q = DeviceBuffer(hash_bytes * shard * world), DeviceBuffer(4 * shard * world)
+    d_ph, d_pq = DeviceBuffer(hash_bytes * shard), DeviceBuffer(4 * shard)  # my shard, padded to the longest
     d_ph.zero()
     d_pq.zero()
-    _lib.check(lib.hvd_memcpy_d2d(d_ph.ptr, d_h.ptr, 32 * n_mine))
+    _lib.check(lib.hvd_memcpy_d2d(d_ph.ptr, d_h.ptr, hash_bytes * n_mine))
     _lib.check(lib.hvd_memcpy_d2d(d_pq.ptr, d_q.ptr, 4 * n_mine))
-    exchange.allgather_bytes_dev(d_ph.ptr, d_all_h.ptr, 32 * shard)
+    exchange.allgather_bytes_dev(d_ph.ptr, d_all_h.ptr, hash_bytes * shard)
     exchange.allgather_bytes_dev(d_pq.ptr, d_all_q.ptr, 4 * shard)
-    d_fh, d_fq = DeviceBuffer(32 * max(n_total, 1)), DeviceBuffer(4 * max(n_total, 1))
+    d_fh, d_fq = DeviceBuffer(hash_bytes * max(n_total, 1)), DeviceBuffer(4 * max(n_total, 1))
     for r in range(world):  # ranks own contiguous video ranges
         lo, hi = video_range_of_rank(V, r, world)
         a, b = int(raw_offsets[lo]), int(raw_offsets[hi])
         if b > a:
-            _lib.check(lib.hvd_memcpy_d2d(d_fh.ptr + 32 * a, d_all_h.ptr + 32 * shard * r, 32 * (b - a)))
+            _lib.check(lib.hvd_memcpy_d2d(d_fh.ptr + hash_bytes * a, d_all_h.ptr + hash_bytes * shard * r,
+                                          hash_bytes * (b - a)))
             _lib.check(lib.hvd_memcpy_d2d(d_fq.ptr + 4 * a, d_all_q.ptr + 4 * shard * r, 4 * (b - a)))
     _lib.check(lib.hvd_dev_sync())  # the staging buffers are freed below
     for buf in (d_all_h, d_all_q, d_ph, d_pq):
@@ -334,6 +435,97 @@ def dedupe_frames_in_process(frames_of_rank, raw_offsets: np.ndarray, h: int, w:
 
     results = multigpu.run_on_contexts(one)
     return results[0]
+
+
+def dedupe_transformed_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                        threshold: float = 50.0, policy: str | None = None, transforms="mirror",
+                                        rank: int = 0, world: int = 1, exchange=None, keep_library: bool = False,
+                                        timings: dict | None = None):
+    """`dedupe_frames_on_device` that also finds mirrored / flipped / rotated copies (search.find_transformed_duplicates
+    on frames in HBM). Dihedral hash -> (all-gather of the 256 B/frame shards) -> quality filter + CSR of the identity
+    library and of the query set of the other selected variants (hvd_dev_compact_kept_dihedral) -> FP4 images -> video
+    search of the identity library -> one cross search of the query set against it -> search.fold_transformed_records.
+    transforms: what search.transform_set takes ("mirror", "flips", "dihedral" or names including "identity").
+    -> (pairs int64[m,2], transform int64[m] (vpdq.TRANSFORMS index), similarity float64[m], identity records, cross
+    records, identity library or None). Every rank returns the same result. timings (optional dict): hash_ms, search_ms
+    and cross_ms (HIP events on the library stream), gather_ms and compact_ms (host clock, as in dedupe_frames_on_device)."""
+    import time
+    names = search.transform_set(transforms)
+    cross = [t for t in names if t != "identity"]
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    raw_offsets = _check_raw_offsets(raw_offsets)
+    V = raw_offsets.size - 1
+    n_total = int(raw_offsets[-1])
+    if world > 1 and exchange is None:
+        raise ValueError("world > 1 needs the RCCL exchange")
+    v_lo, v_hi = video_range_of_rank(V, rank, world)
+    n_mine = int(raw_offsets[v_hi] - raw_offsets[v_lo])
+    lib = _lib.ensure()
+
+    def timed(key, fn):
+        if timings is None:
+            return fn()
+        _lib.check(lib.hvd_timer_start())
+        out = fn()
+        ms = C.c_float(0)
+        _lib.check(lib.hvd_timer_stop(C.byref(ms)))
+        timings[key] = float(ms.value)
+        return out
+
+    d_h, d_q = timed("hash_ms", lambda: hash_frames_dihedral_on_device(d_frames_ptr, n_mine, h, w, channels))
+    t0 = time.perf_counter()
+    if world > 1:
+        d_fh, d_fq = gather_hash_shards(d_h, d_q, raw_offsets, rank, world, exchange, hash_bytes=256)
+        d_h.free()
+        d_q.free()
+        d_h, d_q = d_fh, d_fq
+    t1 = time.perf_counter()
+    library, queries = DeviceLibrary.from_raw_dihedral(d_h.ptr, d_q.ptr, n_total, raw_offsets, names)
+    t2 = time.perf_counter()
+    d_h.free()
+    d_q.free()
+    try:
+        # the identity records are read back before the cross search: emit-again state belongs to the last search only
+        recs_i = timed("search_ms", lambda: library.match_videos(rank=rank, world=world))
+        recs_c = timed("cross_ms", lambda: library.match_queries(queries, rank=rank, world=world)) if cross else \
+            np.zeros(0, dtype=VMATCH_DTYPE)
+    finally:
+        if queries is not None:
+            queries.free()
+    if timings is not None:
+        timings["gather_ms"] = (t1 - t0) * 1e3 if world > 1 else 0.0
+        timings["compact_ms"] = (t2 - t1) * 1e3
+        timings.setdefault("cross_ms", 0.0)
+    pairs, tid, sim = search.fold_transformed_records(recs_i, recs_c, library.lengths(),
+                                                      [vpdq.TRANSFORMS.index(t) for t in cross], threshold, policy,
+                                                      return_similarity=True)
+    if keep_library:
+        return pairs, tid, sim, recs_i, recs_c, library
+    library.free()
+    return pairs, tid, sim, recs_i, recs_c, None
+
+
+def dedupe_transformed_frames_in_process(frames_of_rank, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                         threshold: float = 50.0, policy: str | None = None, transforms="mirror",
+                                         timings: dict | None = None):
+    """`dedupe_frames_in_process` for `dedupe_transformed_frames_on_device`: one thread per context of the in-process
+    device group, rank = context index, frames_of_rank(rank, world) as there. -> rank 0's (pairs, transform, similarity,
+    identity records, cross records); every rank computes the same. timings: rank 0's stage times."""
+    from . import multigpu
+
+    names = search.transform_set(transforms)  # a bad set fails here, not on every rank's thread
+
+    def one(rank, world):
+        ex = multigpu.GroupExchange(rank, world) if world > 1 else None
+        tm = {} if timings is not None and rank == 0 else None
+        out = dedupe_transformed_frames_on_device(frames_of_rank(rank, world), raw_offsets, h, w, channels, threshold,
+                                                  policy, names, rank, world, ex, timings=tm)
+        if tm is not None:
+            timings.update(tm)
+        return out[:5]
+
+    return multigpu.run_on_contexts(one)[0]
 
 
 def video_range_of_rank(V: int, rank: int, world: int) -> tuple[int, int]:

@@ -39,7 +39,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -326,6 +326,19 @@ int hvd_dev_video_of_frames(const void* d_offsets, int64_t V, int64_t n, void* d
  * *out_kept. A video may end up with 0 frames (legal: dedup.py:82-86). */
 int hvd_dev_compact_kept(const void* d_hashes, const void* d_quality, int64_t n, const void* d_offsets, int64_t V,
                          int min_quality, void* d_out_hashes, void* d_out_offsets, void* d_out_video, int64_t* out_kept);
+
+/* hvd_dev_compact_kept for the dihedral hashes (hvd_dev_pdq_hash_frames_dihedral: d_hashes8 n*8*32 B) and a transform
+ * mask (bit t = transform t of the DESIGN table; bit 0, identity, required; bits >= 8 refused). Identity library:
+ * d_out_hashes / d_out_offsets / d_out_video / *out_kept, byte for byte what hvd_dev_compact_kept makes of the variant-0
+ * hashes. Query library of the K = popcount(mask) - 1 other variants, k in mask order: a kept frame at position i of
+ * video v (kept offset o, kept length L) under the k-th variant goes to slot K*o + k*L + i of d_out_qhashes (room for
+ * K*n*32 B), with query video v*K + k in d_out_qvideo and exclusion id v in d_out_qexcl (int32, room for K*n each) --
+ * the operands of hvd_dev_vpdq_match_videos_cross against the identity library (its d_out_video as d_excl_t). The query
+ * outputs may be NULL when K = 0. Only the selected variants are read. */
+int hvd_dev_compact_kept_dihedral(const void* d_hashes8, const void* d_quality, int64_t n, const void* d_offsets, int64_t V,
+                                  int min_quality, int transform_mask, void* d_out_hashes, void* d_out_offsets,
+                                  void* d_out_video, void* d_out_qhashes, void* d_out_qvideo, void* d_out_qexcl,
+                                  int64_t* out_kept);
 
 /* Every video pair a<b with >= 1 frame hit, with its vPDQ counters (semantics of vpdqpy/vpdqpy.py:49-56 for all
  * pairs at once; replaces the tree walk of dedup.py:468-475). d_img: FP4 image of the n frame hashes; d_video:
