@@ -12,17 +12,22 @@ hash DB resident in HBM, including the candidate-pair exchange: BASELINE.json co
   --mode strong BASELINE configs[2] itself at every N (total work fixed);
   --mode cfg4   BASELINE configs[3]: 10M hashes.
 The DB is replicated, tiles of the pair matrix are dealt round-robin to the ranks, the only
-collective is the RCCL all-gather of each rank's candidate pairs. Measured in the same run and
-reported in the same JSON line: the frame-hashing half of the metric (configs[1]: 10k pre-decoded
-64x64 frames), one pass of configs[3] (10M hashes) and the chained end-to-end configs[4]
-(50k videos x 64 frames: hash -> quality filter -> video search, everything resident in HBM);
-at N=1 also the 512x512 RGB24 front-end, a CLUSTERED hash DB (the regime of real frame hashes),
-a sustained run and the CPU baseline.
+collective is the RCCL all-gather of each rank's candidate pairs.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write
+--dump-outputs, print the line (with the per-step split, the runtime block and the roofline
+of the headline's own passes). Everything else runs with --full, in the same run and reported
+in the same JSON line: the host re-verification of the headline's pairs, the frame-hashing half
+of the metric (configs[1]: 10k pre-decoded 64x64 frames), one pass of configs[3] (10M hashes)
+and the chained end-to-end configs[4] (50k videos x 64 frames: hash -> quality filter -> video
+search, everything resident in HBM); at N > 1 the strong-scaling companion; at N=1 also the
+512x512 RGB24 front-end, the other kernel forms, a CLUSTERED hash DB (the regime of real frame
+hashes), a sustained run, the CPU baseline with its oracle gates and the reference-shaped loops.
 
 No PyTorch: the ranks meet over hvd_amd.rendezvous (TCP on loopback; the launcher only provides
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_PORT), the data exchange is RCCL inside the C-ABI.
 Rank 0 prints ONE JSON line. The CPU baseline (the oracle, a port -- the reference's real
-arithmetic is the absent hvdaccelerators wheel) is timed on rank 0 at N=1 only.
+arithmetic is the absent hvdaccelerators wheel) is timed on rank 0 at N=1 only, with --full.
 """
 import argparse
 import ctypes as C
@@ -240,13 +245,17 @@ def parse():
     ap.add_argument("--hashes", type=int, default=1_000_000, help="DB size at N=1 (weak/strong modes)")
     ap.add_argument("--frames", type=int, default=10_000)
     ap.add_argument("--variant", type=int, default=-1, help="all-pairs kernel variant (-1: product default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg and gate (frames hashed, configs[3] / configs[4], strong scaling, kernel forms, "
+                         "clustered DBs, RGB24, streaming feeds, sustained, CPU baseline + oracle gates, reference-shaped loops); "
+                         "default: the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its oracle gates")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--oracle-check-seconds", type=float, default=90.0,
                     help="budget (estimated CPU seconds) of EACH full-size oracle gate of the cpu_baseline leg (config4 row bands, "
                          "config5 every frame + every frame pair); a gate whose estimate exceeds it is skipped with the reason")
-    ap.add_argument("--sustain-seconds", type=float, default=12.0, help="length of the sustained leg at N=1 (0: skip)")
-    ap.add_argument("--no-extras", action="store_true", help="headline + frames_hashed only")
+    ap.add_argument("--sustain-seconds", type=float, default=12.0, help="length of the sustained leg at N=1 with --full (0: skip)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: headline + frames_hashed only")
     ap.add_argument("--cfg5-videos", type=int, default=50_000)
     ap.add_argument("--single-process", action="store_true",
                     help="N > 1 inside ONE process: the library's device group (hvd_init_devices, ncclCommInitAll), one "
@@ -742,8 +751,8 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
         clk_mhz, clk_samples = pass_clock_mhz(lib, L) if v >= 8 else (None, 0)
         merged = M.merge_pairs([recs])
         if verify:
-            # parity gate that runs with every measurement: every reported pair verifies on the host with its exact
-            # distance, and every planted pair within tolerance is reported
+            # parity gate that runs with every measurement of --full: every reported pair verifies on the host with its
+            # exact distance, and every planted pair within tolerance is reported
             dist_host = np.unpackbits(db_[merged["i"]] ^ db_[merged["j"]], axis=1).sum(1)
             assert np.array_equal(dist_host, merged["dist"]) and (merged["dist"] <= 31).all()
             if planted_ is not None and len(planted_):
@@ -759,8 +768,9 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
                                               **{k_: round(float(np.mean(v_)), 3) for k_, v_ in split.items() if k_ != "kernel_ms"},
                                               "pairs": my_pairs[0], "merged_pairs": int(merged.size), "digest": digest,
                                               "steps": split}).encode())
-        assert len({(json.loads(p)["merged_pairs"], json.loads(p)["digest"]) for p in per_rank}) == 1, \
-            "ranks disagree on the merged pair list"
+        if verify:
+            assert len({(json.loads(p)["merged_pairs"], json.loads(p)["digest"]) for p in per_rank}) == 1, \
+                "ranks disagree on the merged pair list"
         res = {"elapsed": elapsed, "kernel_ms": kms, "merged": merged, "per_rank": [json.loads(p) for p in per_rank],
                "bufs": (d_db, d_img, d_pairs, d_cnt), "db": db_}
         return res
@@ -791,15 +801,19 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
         d_f.free()
         return fr_, d_h, d_q, ks, wall
 
-    # the 64x64 hash leg once BEFORE the matrix-core workload (chip idle until now) and once after it (below: the reported
-    # `value`): after 0.5 s of FP4 MFMAs at the power limit the clocks are lower for a while, and 10k frames take 50 us
-    _, dh0, dq0, k1_idle, _ = time_k1(args.frames, 50)
-    dh0.free()
-    dq0.free()
-    k1_idle_ms = rdzv.allreduce_max([mean_sd(k1_idle)[0]])[0]
+    # what runs besides the headline: with --full the frames_hashed leg, and unless --no-extras every other leg and gate
+    full_legs = args.full and not args.no_extras
+
+    # --full: the 64x64 hash leg once BEFORE the matrix-core workload (chip idle until now) and once after it (below: the
+    # reported `value`): after 0.5 s of FP4 MFMAs at the power limit the clocks are lower for a while, and 10k frames take 50 us
+    if args.full:
+        _, dh0, dq0, k1_idle, _ = time_k1(args.frames, 50)
+        dh0.free()
+        dq0.free()
+        k1_idle_ms = rdzv.allreduce_max([mean_sd(k1_idle)[0]])[0]
 
     total_cmp = n * (n - 1) // 2
-    head = allpairs_workload(n, seed, args.steps, args.warmup)
+    head = allpairs_workload(n, seed, args.steps, args.warmup, verify=args.full)
     form = variant
     if variant == 13:  # which of its two forms did the probe choose for this DB? (read before any other leg launches)
         fv = C.c_int(0)
@@ -814,10 +828,10 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
     ms_per_step = elapsed / args.steps * 1e3
     value = total_cmp / (elapsed / args.steps)
 
-    # N > 1 in the default (weak) mode: BASELINE configs[2] itself -- fixed total work -- in the same run, so that one driver
-    # run per N yields both scaling curves
+    # --full, N > 1 in the default (weak) mode: BASELINE configs[2] itself -- fixed total work -- in the same run, so that one
+    # driver run per N yields both scaling curves
     strong = None
-    if world > 1 and args.mode == "weak" and not args.no_extras:
+    if full_legs and world > 1 and args.mode == "weak":
         k_s = max(1, min(args.steps, 10))
         rs = allpairs_workload(args.hashes, 3, steps=k_s, warmup=1)
         for b in rs["bufs"]:
@@ -829,9 +843,10 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
                   "pairs_found": int(len(rs["merged"])), "per_rank": rs["per_rank"]}
         del rs
 
-    fr, d_h, d_q, k1_list, k1_wall = time_k1(args.frames, 50)
-    k1_ms, k1_sd = mean_sd(k1_list)
-    k1_ms, k1_wall = rdzv.allreduce_max([k1_ms, k1_wall])
+    if args.full:
+        fr, d_h, d_q, k1_list, k1_wall = time_k1(args.frames, 50)
+        k1_ms, k1_sd = mean_sd(k1_list)
+        k1_ms, k1_wall = rdzv.allreduce_max([k1_ms, k1_wall])
 
     # ---------------- BASELINE configs[3] (10M hashes) and configs[4] (end to end), at every N --------------
     # At N > 1 these two legs run paths that a 1-GPU development box cannot exercise (RCCL all-gathers of hash shards and
@@ -841,11 +856,11 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
     # joined).
     extras = {}
     # the full-size oracle gates of the cpu_baseline leg (below) need what these legs produced: kept on the host / in HBM until then
-    want_oracle_gates = world == 1 and not args.no_cpu_baseline and not args.no_extras
+    want_oracle_gates = world == 1 and not args.no_cpu_baseline and full_legs
     keep_for_gates = {}
 
     def run_extras():
-        if not args.no_extras:
+        if full_legs:
             if args.mode != "cfg4":
                 for b in (d_db, d_img, d_pairs, d_cnt):
                     b.free()
@@ -868,7 +883,7 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
                             max(p_["kernel_ms"] for p_ in r4["per_rank"])),
                         "gate": "every planted pair within tolerance reported; every reported pair re-verified on the host"}
                 del r4
-        if not args.no_extras and (world == 1 or exchange is not None):  # the hash-shard exchange needs RCCL
+        if full_legs and (world == 1 or exchange is not None):  # the hash-shard exchange needs RCCL
             # configs[4]: 50k videos x 64 distinct synthetic 64x64 frames, generated in HBM (13.1 GB over all ranks)
             V, F = args.cfg5_videos, 64
             rng = np.random.default_rng(5)
@@ -971,7 +986,7 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
     extras_note = None
     if world == 1:
         run_extras()
-    else:
+    elif full_legs:
         import threading
 
         box = {}
@@ -996,7 +1011,7 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
             hard_exit = True
     cfg4, cfg5 = extras.get("cfg4"), extras.get("cfg5")
     cfg5_note = None
-    if cfg5 is None and not args.no_extras and not extras_note and world > 1 and exchange is None:
+    if cfg5 is None and full_legs and not extras_note and world > 1 and exchange is None:
         # (said out loud: a line without config5 must be readable as "skipped, and why", not as a failure)
         cfg5_note = ("config5 leg skipped: its hash-shard and key-list exchanges run inside the library over RCCL, and this run "
                      f"exchanges over {exchange_kind}")
@@ -1055,18 +1070,20 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
                     "note": hbm_equiv["note"] + "; binding unit: integer VALU (v_bcnt_u32_b32 issues at half rate, "
                                                 "profiles/r01_ubench_valu.txt)"}
 
-    fps = world * args.frames / (k1_ms * 1e-3)
-    frames_out = {
-        "workload": f"{args.frames} pre-decoded synthetic 64x64 gray frames per GPU -> PDQ hash + quality "
-                    "(BASELINE configs[1]; frames are independent, ranks hash disjoint batches, no collective)",
-        "value": sig(fps), "unit": "frames/s", "kernel_ms": round(k1_ms, 4), "kernel_ms_sd": round(k1_sd, 4), "dtype": "f32",
-        "warmup_launches": K1_WARM, "timed_launches": 50,
-        "value_idle_chip": sig(world * args.frames / (k1_idle_ms * 1e-3)), "kernel_ms_idle_chip": round(k1_idle_ms, 4),
-        "order_note": "`value` is measured right after the headline's matrix-core passes (clocks still power-limited), "
-                      "`value_idle_chip` before them",
-        "n_gpus": world, "wall_value": sig(world * args.frames * 50 / k1_wall),
-        "roofline": k1_roofline(fps / world, load_traffic(f"pdq_hash64_n{args.frames}")),
-    }
+    frames_out = None
+    if args.full:
+        fps = world * args.frames / (k1_ms * 1e-3)
+        frames_out = {
+            "workload": f"{args.frames} pre-decoded synthetic 64x64 gray frames per GPU -> PDQ hash + quality "
+                        "(BASELINE configs[1]; frames are independent, ranks hash disjoint batches, no collective)",
+            "value": sig(fps), "unit": "frames/s", "kernel_ms": round(k1_ms, 4), "kernel_ms_sd": round(k1_sd, 4), "dtype": "f32",
+            "warmup_launches": K1_WARM, "timed_launches": 50,
+            "value_idle_chip": sig(world * args.frames / (k1_idle_ms * 1e-3)), "kernel_ms_idle_chip": round(k1_idle_ms, 4),
+            "order_note": "`value` is measured right after the headline's matrix-core passes (clocks still power-limited), "
+                          "`value_idle_chip` before them",
+            "n_gpus": world, "wall_value": sig(world * args.frames * 50 / k1_wall),
+            "roofline": k1_roofline(fps / world, load_traffic(f"pdq_hash64_n{args.frames}")),
+        }
 
     out = {
         "metric": "hash-pair comparisons/sec", "value": sig(value, 5), "unit": "comparisons/s",
@@ -1086,8 +1103,8 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
         # which block is the scaling curve: the top-level `value` at every N
         "scale_metric": {
             "weak": f"`value`: all-pairs comparisons/s over n = {args.hashes}*sqrt(N) hashes (comparisons per GPU fixed at "
-                    f"{args.hashes * (args.hashes - 1) // 2:.4g}; BASELINE configs[2] at N=1); `config4.value` is the strong-"
-                    "scaling companion (BASELINE configs[3], 10M hashes, fixed total work) measured in the same run",
+                    f"{args.hashes * (args.hashes - 1) // 2:.4g}; BASELINE configs[2] at N=1); with --full, `config4.value` is the "
+                    "strong-scaling companion (BASELINE configs[3], 10M hashes, fixed total work) measured in the same run",
             "strong": "`value`: all-pairs comparisons/s over BASELINE configs[2] (fixed total work) at every N",
             "cfg4": "`value`: all-pairs comparisons/s over BASELINE configs[3] (10M hashes, fixed total work) at every N",
         }[args.mode],
@@ -1124,7 +1141,7 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
         out["dump_outputs"] = dumped
 
     cpu = None
-    if world == 1 and not args.no_extras:
+    if world == 1 and full_legs:
         extra = {}
         # chip-filling batch of the 64x64 hash kernel (10k frames occupy a fraction of the 256 CUs' wave slots)
         _, dh2, dq2, kl, _ = time_k1(400_000, 10)
@@ -1486,7 +1503,8 @@ def rank_main(args, rank, local_rank, world, real_stdout, inproc):
                     "package's per-pair entry: reference_shaped_loop)"}
         conn.close()
 
-    out["frames_hashed"] = frames_out
+    if frames_out:
+        out["frames_hashed"] = frames_out
     for pr in head["per_rank"]:  # clock / power of the timed region, per device
         rk = next((r_ for r_ in runtime.get("ranks", []) if r_.get("rank") == pr["rank"]), None)
         dev = next((d_ for d_ in runtime.get("devices", []) if rk and d_.get("pci") == rk.get("pci")), None)

@@ -8,7 +8,7 @@ set -u
 TAG=${1:-r06}
 REPO=$(pwd); OUT=$REPO/gpurun_out; mkdir -p $OUT/${TAG}_stats
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -o bench -- python $REPO/bench.py --gpus 1 --steps 20 --warmup 5 --no-extras > $OUT/${TAG}_bench_prof.json 2> $OUT/${TAG}_bench_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_stats -o bench -- python $REPO/bench.py --gpus 1 --steps 20 --warmup 5 --full --no-extras > $OUT/${TAG}_bench_prof.json 2> $OUT/${TAG}_bench_prof.err
 echo "bench under rocprof rc=$?"
 cp $(find $OUT/${TAG}_stats -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_bench_kernel_stats.csv
 cd $REPO && bash scripts/profile_pmc.sh ${TAG} > /dev/null 2>&1

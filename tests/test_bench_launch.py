@@ -136,11 +136,11 @@ def test_bench_self_launch_propagates_a_rank_failure(gpu):
 
 @pytest.mark.gpu
 def test_single_process_bench_runs_two_contexts_on_one_gpu():
-    """`python bench.py --gpus 2 --single-process --devices 0,0`: the two ranks are the two contexts of the library's
+    """`python bench.py --gpus 2 --single-process --devices 0,0 --full`: the two ranks are the two contexts of the library's
     in-process device group (the mode the drop-in surfaces use under HVD_DEVICES), one thread each; device 0 listed twice,
     so the candidates meet in host memory. One JSON line, exit code 0, the riding config-4 / config-5 legs included."""
     r = _run_bench(["--gpus", "2", "--single-process", "--devices", "0,0", "--steps", "2", "--warmup", "1", "--hashes", "200000",
-                    "--cfg5-videos", "2000", "--no-cpu-baseline"], {}, timeout=900)
+                    "--cfg5-videos", "2000", "--no-cpu-baseline", "--full"], {}, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -214,6 +214,27 @@ def test_dump_outputs_writes_float_arrays_and_samples_the_same_rows_every_time(t
     j = np.load(tmp_path / "s1" / "pairs_j.npy")
     assert (np.diff(j) > 0).all()  # rows of the sample keep the (i, j) order (j is increasing in this array)
     assert sum(os.path.getsize(tmp_path / "s1" / f"pairs_{f}.npy") for f in ("i", "j", "dist")) < 24 * 1000 + 3 * 256
+
+
+@pytest.mark.gpu
+def test_plain_bench_runs_the_headline_alone(gpu):
+    """Without --full the line carries the headline and what its own timed steps yield, and none of the other legs."""
+    r = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--hashes", "100000"], {}, timeout=300)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["metric"] == "hash-pair comparisons/sec" and out["unit"] == "comparisons/s" and out["higher_is_better"] is True
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["dtype"]
+    n = out["config"]["n_hashes"]
+    assert n == 100_000 and out["config"]["pairs_found"] > 0
+    assert abs(out["value"] / (n * (n - 1) / 2 / (out["ms_per_step"] * 1e-3)) - 1) < 0.02  # (ms_per_step is rounded to 1 us)
+    assert [p["rank"] for p in out["per_rank"]] == [0] and len(out["per_rank"][0]["steps"]["step_ms"]) == 2
+    assert out["roofline"]["kernel_ms"] > 0 and out["runtime"]["devices"]
+    for key in ("frames_hashed", "config4", "config5", "strong", "kernel_variants", "clustered_db", "videohasher_stream",
+                "sustained", "cpu_baseline", "full_size_oracle_check", "video_match", "reference_shaped_loop",
+                "vptree_facade_loop"):
+        assert key not in out, key
 
 
 def test_bench_refuses_zero_timed_steps():
