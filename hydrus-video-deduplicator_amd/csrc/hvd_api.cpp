@@ -602,21 +602,13 @@ int hvd_get_pdq_dct_mode(void) { return hvd::g_pdq_dct_mode; }
 int hvd_debug_set(const char* key, int value) {
     if (!key) return fail(HVD_ERR_ARG, "key is NULL");
     if (strcmp(key, "pdq_dct_from_lds") == 0) {
-        if (value < 0 || value > 3) return fail(HVD_ERR_ARG, "pdq_dct_from_lds: 0 SGPR operands, 1 LDS, 2 literals, 3 by batch size");
+        if (value != 0 && value != 2 && value != 3) return fail(HVD_ERR_ARG, "pdq_dct_from_lds: 0 SGPR operands, 2 literals, 3 by batch size");
         hvd::g_pdq_dct_from_lds = value;
         return HVD_OK;
     }
     if (strcmp(key, "pdq_hash_grid") == 0) {
         if (value < 0) return fail(HVD_ERR_ARG, "pdq_hash_grid must not be negative (0 = default)");
         hvd::g_pdq_hash_grid = value;
-        return HVD_OK;
-    }
-    if (strcmp(key, "pdq_hash_prefetch") == 0) {  // 64x64 gray hash kernel, static launches: next frame fetched one frame ahead
-        hvd::g_pdq_hash_prefetch = value != 0;
-        return HVD_OK;
-    }
-    if (strcmp(key, "pdq_luma_lut") == 0) {
-        hvd::g_pdq_luma_lut = value;
         return HVD_OK;
     }
     if (strcmp(key, "mfma_col_chunk_max") == 0) {

@@ -22,12 +22,6 @@
 #include "copy_pool.h"
 #include "hvd_kernels.h"
 
-// HVD_ABL_STREAM_NOHASH: timing-only ablation (WRONG RESULTS: batches are uploaded, nothing is hashed) -- is the upload rate of
-// the pipeline held back by the kernels that run beside it? Like every ablation it needs -DHVD_DEV_ABLATION as well.
-#if defined(HVD_ABL_STREAM_NOHASH) && !defined(HVD_DEV_ABLATION)
-#error "HVD_ABL_STREAM_NOHASH is a developer ablation build (wrong results): add -DHVD_DEV_ABLATION to confirm"
-#endif
-
 namespace hvd {
 int api_fail(int code, const char* fmt, ...);     // hvd_api.cpp
 const float* api_dct_device();                    // hvd_api.cpp; nullptr before hvd_init
@@ -171,10 +165,8 @@ static int submit(hvd_hasher* hs, Slot& s) {
     NsScope ns(g_ns_submit);
     const int64_t m = s.filled;
     S_TRY(hipMemcpyAsync(s.d_frames, s.h_frames, hs->frame_bytes * (size_t)m, hipMemcpyHostToDevice, s.stream));
-#ifndef HVD_ABL_STREAM_NOHASH
     S_TRY(hvd::api_launch_hash(s.d_frames, m, hs->h, hs->w, hs->channels, s.d_scratch, s.d_hashes, s.d_quality, s.stream,
                                hs->dihedral));
-#endif
     S_TRY(hipMemcpyAsync(s.h_hashes, s.d_hashes, hs->hash_bytes() * (size_t)m, hipMemcpyDeviceToHost, s.stream));
     S_TRY(hipMemcpyAsync(s.h_quality, s.d_quality, 4 * (size_t)m, hipMemcpyDeviceToHost, s.stream));
     S_TRY(hipEventRecord(s.done, s.stream));

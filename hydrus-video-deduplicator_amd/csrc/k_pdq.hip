@@ -22,12 +22,6 @@
 //   median   radix select of the 128th smallest of 256 keys with wave ballots
 //   bits     ballot(B > median): lane l, output r is hash bit l + 64 r
 #include <hip/hip_runtime.h>
-
-// HVD_ABL_NOSTATE / HVD_ABL_NOFETCH / HVD_ABL_NOD / HVD_ABL_NOLUMA / HVD_ABL_NOSTATELOAD builds are timing-only ABLATIONS of the down-sampler that produce
-// WRONG RESULTS. They may not come out of the product source with a single -D:
-#if (defined(HVD_ABL_NOSTATE) || defined(HVD_ABL_NOFETCH) || defined(HVD_ABL_NOD) || defined(HVD_ABL_NOLUMA) || defined(HVD_ABL_NOSTATELOAD)) && !defined(HVD_DEV_ABLATION)
-#error "HVD_ABL_* are developer ablation builds (wrong results): add -DHVD_DEV_ABLATION to confirm"
-#endif
 #include <stdint.h>
 #include <string.h>
 
@@ -113,12 +107,11 @@ __device__ __forceinline__ void wave_lds_handover() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// KIND 0: uint8 gray 64x64 frames. KIND 1: float 64x64 buffers (down-sampler output).
-// DLDS: where stage 1 takes D[i][k] from. 0: scalar loads (SGPR operands: v_mul_f32 s,v issues at half rate,
-// profiles/r01_ubench_valu.txt). 1: LDS broadcast reads (VGPR operands, full-rate v_mul, but an LDS read per 4
-// products). 2: 32-bit LITERALS in the instruction stream -- the matrix is a constant of the algorithm, so stage 1 is
-// unrolled completely (16 x 64 multiply-adds, ~20 KB of code) and every multiply carries its coefficient: no operand
-// fetch at all, full-rate issue.
+// KIND 0: uint8 gray 64x64 frames (luma from an LDS table). KIND 1: float 64x64 buffers (down-sampler output).
+// LIT: where stage 1 takes D[i][k] from. false: scalar loads (SGPR operands: v_mul_f32 s,v issues at half rate,
+// profiles/r01_ubench_valu.txt). true: 32-bit LITERALS in the instruction stream -- the matrix is a constant of the
+// algorithm, so stage 1 is unrolled completely (16 x 64 multiply-adds, ~20 KB of code) and every multiply carries its
+// coefficient: no operand fetch at all, full-rate issue.
 // Work distribution (round 3): a workgroup takes chunk blockIdx.x (`chunk` consecutive groups of 4 frames) statically and
 // every further chunk from a counter in device memory, so that no workgroup is left with a trip more than its neighbours
 // while their SIMDs idle (at 400 k frames the static stride cost 16 %). One atomic per trip, ISSUED at the top of the trip
@@ -126,17 +119,8 @@ __device__ __forceinline__ void wave_lds_handover() {
 // a launch starts -- which is why launches below 64 k frames keep the static stride (work == nullptr): measured, the draws cost
 // 10 k frames 52 -> 65 us, while 400 k frames gain 12 % (profiles/r03_k1_grid.txt). Every trip draws exactly once, so the draw that returns (trips - 1) is the last of the launch: its
 // workgroup zeroes the counter for the next launch that is handed this slot -- no exit counter.
-// PREF (gray bytes, static stride only -- the launches below 64 k frames): the wave's NEXT frame is fetched while it works
-// on this one, as four 16-byte loads per lane (16 VGPRs in flight for a whole frame's time), handed to the lanes through
-// the wave's own T area (4 096 of its 4 352 bytes; T is written only after the last byte has been read) -- instead of 64
-// byte loads per lane whose latency every frame started with (the fma kernel has worked this way since round 2).
-#ifdef HVD_K1_WAVES  // A/B builds: force the strict hash kernel to this many waves per SIMD (profiles/r04_k1_grid.txt)
-#define HVD_K1_OCC __attribute__((amdgpu_waves_per_eu(HVD_K1_WAVES, HVD_K1_WAVES)))
-#else
-#define HVD_K1_OCC
-#endif
-template <int KIND, int DLDS, int LUT, bool PREF = false>
-__global__ __launch_bounds__(256) HVD_K1_OCC void k_pdq_hash64(const void* __restrict__ in, long long n,
+template <int KIND, bool LIT>
+__global__ __launch_bounds__(256) void k_pdq_hash64(const void* __restrict__ in, long long n,
                                                     const float* __restrict__ dct, uint8_t* __restrict__ hashes,
                                                     int32_t* __restrict__ quality, unsigned int* __restrict__ work,
                                                     int chunk) {
@@ -147,19 +131,11 @@ __global__ __launch_bounds__(256) HVD_K1_OCC void k_pdq_hash64(const void* __res
 
     // Padded LDS copy of the DCT matrix for stage 2 (once per workgroup).
     for (int e = threadIdx.x; e < 16 * 64; e += 256) lds.D[e >> 6][e & 63] = dct[e];
-    lds.luma_lut[threadIdx.x] = luma_gray(threadIdx.x);
+    lds.luma_lut[threadIdx.x] = luma_gray(threadIdx.x);  // (read by KIND 0 only; filled for both)
     __syncthreads();
 
     const long long groups = (n + kWaves - 1) / kWaves;
     const long long nchunks = (groups + chunk - 1) / chunk;
-    uint4 nb0 = make_uint4(0, 0, 0, 0), nb1 = nb0, nb2 = nb0, nb3 = nb0;  // PREF: the next frame's bytes, in flight
-    if (PREF) {
-        const long long f0 = (long long)blockIdx.x * kWaves + wave;
-        if ((long long)blockIdx.x < groups && f0 < n) {
-            const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(in) + f0 * 4096);
-            nb0 = src[lane]; nb1 = src[64 + lane]; nb2 = src[128 + lane]; nb3 = src[192 + lane];
-        }
-    }
     for (long long ck = blockIdx.x; ck < nchunks;) {
         unsigned int drawn = 0;
         if (work != nullptr && threadIdx.x == 0) drawn = atomicAdd(&work[0], 1u);  // consumed behind this trip's last group
@@ -170,30 +146,10 @@ __global__ __launch_bounds__(256) HVD_K1_OCC void k_pdq_hash64(const void* __res
         if (valid) {
             // ---- stage 0: column `lane` of the frame -------------------------------
             float a[64];
-            if (KIND == 0 && PREF) {
-                uint4* dstb = reinterpret_cast<uint4*>(&lds.T[wave][0][0]);
-                dstb[lane] = nb0; dstb[64 + lane] = nb1; dstb[128 + lane] = nb2; dstb[192 + lane] = nb3;
-                const long long fn = (g + gridDim.x) * kWaves + wave;  // (static stride, one group per trip)
-                if (g + gridDim.x < groups && fn < n) {
-                    const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(in) + fn * 4096);
-                    nb0 = src[lane]; nb1 = src[64 + lane]; nb2 = src[128 + lane]; nb3 = src[192 + lane];
-                }
-                wave_lds_handover();
-                const uint8_t* srcb = reinterpret_cast<const uint8_t*>(&lds.T[wave][0][0]) + lane;
-#pragma unroll
-                for (int k = 0; k < 64; ++k) a[k] = lds.luma_lut[srcb[k * 64]];
-                wave_lds_handover();  // every byte has been read before stage 1 writes T over them
-            } else if (KIND == 0) {
+            if (KIND == 0) {
                 const uint8_t* src = reinterpret_cast<const uint8_t*>(in) + f * 4096 + lane;
 #pragma unroll
-                for (int k = 0; k < 64; ++k) {
-                    if (LUT == 0) {
-                        a[k] = luma_gray(src[k * 64]);
-                    } else {
-                        a[k] = lds.luma_lut[src[k * 64]];
-                        if (LUT == 2 && (k & 15) == 15) __builtin_amdgcn_sched_barrier(0);  // bound the loads in flight
-                    }
-                }
+                for (int k = 0; k < 64; ++k) a[k] = lds.luma_lut[src[k * 64]];
             } else {
                 const float* src = reinterpret_cast<const float*>(in) + f * 4096 + lane;
 #pragma unroll
@@ -227,7 +183,7 @@ __global__ __launch_bounds__(256) HVD_K1_OCC void k_pdq_hash64(const void* __res
             qual = qual > 100 ? 100 : qual;
 
             // ---- stage 1: T[i][lane] = sum_k D[i][k] * a[k], k ascending ------------
-            if (DLDS == 2) {
+            if (LIT) {
 #pragma unroll
                 for (int i0 = 0; i0 < 16; i0 += 4) {
                     float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
@@ -247,35 +203,16 @@ __global__ __launch_bounds__(256) HVD_K1_OCC void k_pdq_hash64(const void* __res
 #pragma unroll 1
             for (int i0 = 0; i0 < 16; i0 += 4) {
                 float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
-                if (DLDS == 1) {
+                const float* d0 = dct + (i0 + 0) * 64;  // wave-uniform -> s_load
+                const float* d1 = dct + (i0 + 1) * 64;
+                const float* d2 = dct + (i0 + 2) * 64;
+                const float* d3 = dct + (i0 + 3) * 64;
 #pragma unroll
-                    for (int k4 = 0; k4 < 16; ++k4) {  // same address in every lane: LDS broadcast
-                        const float4 e0 = *reinterpret_cast<const float4*>(&lds.D[i0 + 0][4 * k4]);
-                        const float4 e1 = *reinterpret_cast<const float4*>(&lds.D[i0 + 1][4 * k4]);
-                        const float4 e2 = *reinterpret_cast<const float4*>(&lds.D[i0 + 2][4 * k4]);
-                        const float4 e3 = *reinterpret_cast<const float4*>(&lds.D[i0 + 3][4 * k4]);
-                        const float x0 = a[4 * k4], x1 = a[4 * k4 + 1], x2 = a[4 * k4 + 2], x3 = a[4 * k4 + 3];
-                        s0 = __fadd_rn(s0, __fmul_rn(e0.x, x0)); s1 = __fadd_rn(s1, __fmul_rn(e1.x, x0));
-                        s2 = __fadd_rn(s2, __fmul_rn(e2.x, x0)); s3 = __fadd_rn(s3, __fmul_rn(e3.x, x0));
-                        s0 = __fadd_rn(s0, __fmul_rn(e0.y, x1)); s1 = __fadd_rn(s1, __fmul_rn(e1.y, x1));
-                        s2 = __fadd_rn(s2, __fmul_rn(e2.y, x1)); s3 = __fadd_rn(s3, __fmul_rn(e3.y, x1));
-                        s0 = __fadd_rn(s0, __fmul_rn(e0.z, x2)); s1 = __fadd_rn(s1, __fmul_rn(e1.z, x2));
-                        s2 = __fadd_rn(s2, __fmul_rn(e2.z, x2)); s3 = __fadd_rn(s3, __fmul_rn(e3.z, x2));
-                        s0 = __fadd_rn(s0, __fmul_rn(e0.w, x3)); s1 = __fadd_rn(s1, __fmul_rn(e1.w, x3));
-                        s2 = __fadd_rn(s2, __fmul_rn(e2.w, x3)); s3 = __fadd_rn(s3, __fmul_rn(e3.w, x3));
-                    }
-                } else {
-                    const float* d0 = dct + (i0 + 0) * 64;  // wave-uniform -> s_load
-                    const float* d1 = dct + (i0 + 1) * 64;
-                    const float* d2 = dct + (i0 + 2) * 64;
-                    const float* d3 = dct + (i0 + 3) * 64;
-#pragma unroll
-                    for (int k = 0; k < 64; ++k) {
-                        s0 = __fadd_rn(s0, __fmul_rn(d0[k], a[k]));
-                        s1 = __fadd_rn(s1, __fmul_rn(d1[k], a[k]));
-                        s2 = __fadd_rn(s2, __fmul_rn(d2[k], a[k]));
-                        s3 = __fadd_rn(s3, __fmul_rn(d3[k], a[k]));
-                    }
+                for (int k = 0; k < 64; ++k) {
+                    s0 = __fadd_rn(s0, __fmul_rn(d0[k], a[k]));
+                    s1 = __fadd_rn(s1, __fmul_rn(d1[k], a[k]));
+                    s2 = __fadd_rn(s2, __fmul_rn(d2[k], a[k]));
+                    s3 = __fadd_rn(s3, __fmul_rn(d3[k], a[k]));
                 }
                 lds.T[wave][i0 + 0][lane] = s0;
                 lds.T[wave][i0 + 1][lane] = s1;
@@ -1109,10 +1046,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
     // index of four different slots in one instruction -- at a stride of 64 dwords those are four addresses in the SAME banks
     // (a 4-way conflict on every one of pass D's reads: the 17 % conflict cycles of profiles/r04_pmc_down512w.txt); 68 moves each
     // slot on by four banks, which is what a 128-bit read per lane needs.
-#ifndef HVD_F1_SMPS
-#define HVD_F1_SMPS 68
-#endif
-    constexpr int SMPS = HVD_F1_SMPS;
+    constexpr int SMPS = 68;
     float (*smp)[SMPS] = reinterpret_cast<float (*)[SMPS]>(&buf[0]);
     static_assert(sizeof(buf) >= 4 * SMPS * sizeof(float) && SMPS >= kWR && SMPS % 4 == 0, "smp aliases buf");
     const uint32_t buf_lds = (uint32_t)(uintptr_t)(&buf[0]);  // LDS byte address of the buffer (M0 base of the addtid stores)
@@ -1193,20 +1127,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
                     // unconditional, all lanes (the upper half's copies are never read): see the tile row's first load
                     // next step = column tile tx + 1 of this tile row (its state was left by the tile row above), or -- from the
                     // tile row's last step -- column tile 0 of the next tile row (left by this one, 16 steps ago)
-#ifdef HVD_ABL_NOSTATE
-                    const bool have = false;
-#else
                     const bool have = tx <= kWNX ? (ty > 0 && tx + 1 <= kWNX) : (ty < kWNY);
-#endif
                     const uint32_t pi = (have ? (uint32_t)(tx <= kWNX ? tx + 1 : 0) * (5 * 32) : (uint32_t)kWScratchFloats) + (uint32_t)cl5;
-#ifdef HVD_ABL_NOSTATELOAD  // timing ablation only (wrong results): no state load at all -> no vmcnt wait at the top of a step
-                    (void)pi;
-                    nxB = 0.0f; nxl[0] = nxl[1] = nxl[2] = nxl[3] = 0.0f;
-#else
                     nxB = buf_ld(rs, pi);
                     nxl[0] = buf_ld(rs, pi + 32); nxl[1] = buf_ld(rs, pi + 64);
                     nxl[2] = buf_ld(rs, pi + 96); nxl[3] = buf_ld(rs, pi + 128);
-#endif
                 }
                 // ---------------- A: luma + rep-1 along the row (lane = row 64ty + lane) -----------------
                 // unit m of half `par` arrives in this step (lower half: steps 2m, 2m+1 <-> tiles 2m, 2m+1; upper half: steps
@@ -1245,9 +1170,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
                         fbytes = frame_bytes;
                         soff = (uint32_t)(32 * par) * row_bytes;
                     }
-#ifdef HVD_ABL_NOFETCH  // timing ablation only: every prefetch reads from a zero-byte resource
-                    fbytes = 0;
-#endif
                     unit_fetch<CH>(make_rsrc(frames + (size_t)fsel * frame_bytes, fbytes), soff, lane, pre[par]);
                 }
                 if (ty < kWNY) {
@@ -1275,12 +1197,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
 #pragma unroll
                         for (int j = 0; j < kWT / 4; ++j) {
                             float v[4];
-#ifdef HVD_ABL_NOLUMA  // timing ablation only (wrong results): one conversion per pixel instead of the 8-instruction luma
-                            if (CH == 3) {
-                                const uint32_t w0 = fifo_word(fifo, 3 * j), w1 = fifo_word(fifo, 3 * j + 1), w2 = fifo_word(fifo, 3 * j + 2);
-                                v[0] = (float)(w0 & 0xFFu); v[1] = (float)(w0 >> 24); v[2] = (float)((w1 >> 16) & 0xFFu); v[3] = (float)((w2 >> 8) & 0xFFu);
-                            } else
-#endif
                             if (CH == 3) {
                                 const uint32_t w0 = fifo_word(fifo, 3 * j), w1 = fifo_word(fifo, 3 * j + 1), w2 = fifo_word(fifo, 3 * j + 2);
                                 v[0] = luma_rgb_f((float)(w0 & 0xFFu), (float)((w0 >> 8) & 0xFFu), (float)((w0 >> 16) & 0xFFu));
@@ -1369,9 +1285,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
                         stS = sB;
 #pragma unroll
                         for (int k = 0; k < 4; ++k) stl[k] = bl[k];
-#ifndef HVD_ABL_NOSTATE
                         st_ok = half && valid;
-#endif
                         // lower half -> upper half of the next step (lane l -> lane l + 32)
                         inB = __shfl_up(sB, 32, 64);
 #pragma unroll
@@ -1444,11 +1358,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
                 // i = 8ty-1+r/8 iff r % 8 == 0.
                 {
                     const int js = lane + 1, gs = js >> 2;
-#ifdef HVD_ABL_NOD  // timing ablation only (wrong results): pass D does nothing
-                    const bool lo_pass = false, hi_pass = false;
-#else
                     const bool lo_pass = (gs == tx) && (tx <= kWNX), hi_pass = (gs == tx - 1);
-#endif
                     // the step's (up to) four outputs of a lane and where they go; 4096 = past the end of the frame's 64 x 64
                     // floats = nowhere (every step issues its four stores: uniform memory schedule)
                     uint32_t di[4] = {4096u, 4096u, 4096u, 4096u};
@@ -1494,10 +1404,9 @@ namespace hvd {
 
 int g_pdq_dct_mode = 0;           // 0: strict mul-then-add on the VALU (default); 1: fma chain on the matrix cores
 int g_pdq_hash_grid = 0;          // A/B switch (hvd_debug_set "pdq_hash_grid"): workgroups of k_pdq_hash64, 0 = default
-int g_pdq_luma_lut = 1;           // 0: compute luma, 1: LDS table, 2: LDS table, loads in groups of 16
-// stage-1 DCT operand source (hvd_debug_set "pdq_dct_from_lds"): 0 SGPRs, 1 LDS, 2 literals, 3 (default) by batch size --
-// literals from 64k frames on (+9 % at 400k frames: full-rate multiplies), SGPRs below (the unrolled 21 KB of code cost
-// 4 % at 10k frames, where every workgroup runs it once or twice; profiles/r02_k1_dct_operand.txt)
+// stage-1 DCT operand source (hvd_debug_set "pdq_dct_from_lds"): 0 SGPRs, 2 literals, 3 (default) by batch size -- literals
+// from 8 k frames on (+9 % at 400 k frames: full-rate multiplies), SGPRs below (profiles/r02_k1_dct_operand.txt); 1, LDS
+// operands, measured slower and is gone
 int g_pdq_dct_from_lds = 3;
 
 void pdq_dct_table_copy(float* out_16x64) {
@@ -1560,8 +1469,7 @@ hipError_t launch_pdq_hash64(const void* d_in, int kind, int64_t n, const float*
     if (n <= 0) return hipSuccess;
     const int64_t groups = (n + kWaves - 1) / kWaves;
     // literals from 8 k frames on (round 3: with the leaner quality term the literal form also wins at 10 k frames)
-    const int dlds = g_pdq_dct_from_lds == 3 ? (n >= 8192 ? 2 : 0) : g_pdq_dct_from_lds;
-    const int lut = g_pdq_luma_lut;
+    const bool lit = g_pdq_dct_from_lds == 3 ? n >= 8192 : g_pdq_dct_from_lds == 2;
     // long launches of the strict kernels distribute their work dynamically (see the kernel), several groups per draw
     const bool dynamic = g_pdq_dct_mode != 1 && n >= 65536;
     unsigned int* work = nullptr;
@@ -1591,29 +1499,18 @@ hipError_t launch_pdq_hash64(const void* d_in, int kind, int64_t n, const float*
             hipLaunchKernelGGL(k_pdq_hash64_fma<1>, grid, dim3(256), 0, s, d_in, (long long)n, d_dct, d_hashes, d_quality);
         return hipGetLastError();
     }
-#define HVD_K1(KIND, D, L) hipLaunchKernelGGL((k_pdq_hash64<KIND, D, L>), grid, dim3(256), 0, s, d_in, (long long)n, d_dct, d_hashes, d_quality, work, chunk)
-#define HVD_K1P(D) hipLaunchKernelGGL((k_pdq_hash64<0, D, 1, true>), grid, dim3(256), 0, s, d_in, (long long)n, d_dct, d_hashes, d_quality, work, chunk)
-    if (kind == 0 && !dynamic && g_pdq_hash_prefetch && lut == 1 && dlds != 1) {
-        if (dlds == 2) HVD_K1P(2);
-        else HVD_K1P(0);
-    } else if (kind == 0) {
-        if (dlds == 2) HVD_K1(0, 2, 1);
-        else if (dlds == 1) HVD_K1(0, 1, 1);
-        else if (lut == 0) HVD_K1(0, 0, 0);
-        else if (lut == 1) HVD_K1(0, 0, 1);
-        else HVD_K1(0, 0, 2);
+#define HVD_K1(KIND, LIT) hipLaunchKernelGGL((k_pdq_hash64<KIND, LIT>), grid, dim3(256), 0, s, d_in, (long long)n, d_dct, d_hashes, d_quality, work, chunk)
+    if (kind == 0) {
+        if (lit) HVD_K1(0, true);
+        else HVD_K1(0, false);
     } else {
-        if (dlds == 2) HVD_K1(1, 2, 0);
-        else if (dlds == 1) HVD_K1(1, 1, 0);
-        else HVD_K1(1, 0, 0);
+        if (lit) HVD_K1(1, true);
+        else HVD_K1(1, false);
     }
 #undef HVD_K1
-#undef HVD_K1P
     return hipGetLastError();
 }
 
-int g_pdq_hash_prefetch = 0;  // A/B switch (hvd_debug_set "pdq_hash_prefetch"): measured SLOWER (115 VGPRs = 4 waves per SIMD instead of 5:
-                              // 10 k frames 47.6 -> 50.2 us, profiles/r04_k1_grid.txt), so off; bit-identical either way
 static int jarosz_window(int dim) { return (dim + 2 * 64 - 1) / (2 * 64); }
 
 // Workspace (floats per frame) the down-sampler needs besides the 64x64 output.

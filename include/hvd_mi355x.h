@@ -230,7 +230,7 @@ int hvd_set_pdq_dct_mode(int mode);
 int hvd_get_pdq_dct_mode(void);
 
 /* Developer switches for A/B measurements; results never change, only which kernel form runs:
- *   "pdq_dct_from_lds" 0|1|2|3 (SGPR | LDS | literals | by batch size), "pdq_luma_lut" 0|1|2   (64x64 hash kernel)
+ *   "pdq_dct_from_lds" 0|2|3                               (64x64 hash kernel's DCT operands: SGPRs | literals | by batch size)
  *   "pdq_fused_down512" 0|1                                (0: generic 4-launch down-sampler)
  *   "pdq_down512_wave" 0|1|2                               (wave-per-frame kernel: never | batches >= 704 | always)
  *   "pdq_down512_wave_grid" n                              (waves in flight; 0 = what is resident at once)
@@ -244,7 +244,7 @@ int hvd_get_pdq_dct_mode(void);
  *                                                           eligible; not the query x target or video searches)
  *   "mfma_force_sel" -1|0|1|2                              (which 128 bits the first stage sees: the probe's choice | bits 0..127 |
  *                                                           128..255 | 0..63 + 192..255)
- *   "pdq_hash_grid" n, "pdq_hash_prefetch" 0|1             (64x64 hash kernel: forced grid; next frame fetched ahead, off)
+ *   "pdq_hash_grid" n                                      (64x64 hash kernel: forced grid; 0 = by batch size)
  *   "vmatch_exchange" 0|1|2                                (key exchange of the video search: iff world > 1 | always | never)
  *   "vmatch_slots_log2" 0|4..30                            (initial size of the video-reduction tables; tests the regrowth)
  *   "vmatch_variant" 0|8|9|12|13|18                        (all-pairs form of the video-level searches; 0 = the auto variant)

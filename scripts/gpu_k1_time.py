@@ -1,4 +1,4 @@
-"""Dev probe: 64x64 hash kernel timing, strict and fma, for the three DCT-operand sources."""
+"""Dev probe: 64x64 hash kernel timing for the two DCT-operand sources (0: SGPRs, 2: literals)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C, numpy as np, hvd_amd
@@ -11,7 +11,7 @@ for nf in (10000, 400000):
         L.check(lib.hvd_memcpy_h2d(C.c_void_p(d_f.ptr + r0 * 4096), fr.ctypes.data, 10000 * 4096))
     d_h, d_q = L.DeviceBuffer(32 * nf), L.DeviceBuffer(4 * nf)
     ref = None
-    for src in (0, 1, 2):
+    for src in (0, 2):
         L.check(lib.hvd_debug_set(b"pdq_dct_from_lds", src))
         ks = []
         for r in range(12):

@@ -273,6 +273,21 @@ def test_hvd_devices_environment_is_parsed_before_any_device_is_touched(hvd, mon
     assert lib.hvd_init(0) == _lib.HVD_ERR_NO_DEVICE
 
 
+def test_hash_kernel_debug_switches_offer_only_launched_forms(hvd):
+    """The 64x64 hash kernel has two stage-1 operand forms, SGPRs and literals: "pdq_dct_from_lds" forces one of them (0, 2)
+    or leaves the choice to the batch size (3, the default). The LDS-operand form (1), the computed luma and the next-frame
+    prefetch are gone, and so are their switches. hvd_debug_set needs no device."""
+    from hvd_amd import _lib
+
+    lib = _lib.load()
+    for key in (b"pdq_luma_lut", b"pdq_hash_prefetch"):
+        for value in (0, 1):
+            assert lib.hvd_debug_set(key, value) == _lib.HVD_ERR_ARG, (key, value)
+    assert lib.hvd_debug_set(b"pdq_dct_from_lds", 1) == _lib.HVD_ERR_ARG
+    for value in (0, 2, 3):  # 3 last: the default stays set
+        assert lib.hvd_debug_set(b"pdq_dct_from_lds", value) == _lib.HVD_OK, value
+
+
 def test_thread_rendezvous_is_a_rendezvous():
     """The control plane of `bench.py --single-process` / the in-process ranks: same interface as the TCP rendezvous."""
     import threading

@@ -130,19 +130,13 @@ def test_probe_and_image_kernels(shapes):
         assert waves_per_simd(k["vgpr"]) == 8 and k["lds"] == 0 and k["vgpr_spill"] == 0
 
 
-# k_pdq_hash64<KIND, DLDS, LUT, PREF>: KIND 0 = u8 gray in, 1 = float luma in (after the down-sampler); DLDS 2 = DCT matrix as
-# literals (>= 8192 frames), 0 = SGPRs; launch_pdq_hash64 picks <0,2,1> / <0,0,1> for gray and <1,2,0> / <1,0,0> for luma.
+# k_pdq_hash64<KIND, LIT>: KIND 0 = u8 gray in, 1 = float luma in (after the down-sampler); LIT true = DCT matrix as
+# literals (>= 8192 frames), false = SGPRs.
 PDQ = {
-    "k_pdq_hash64<0, 2, 1, false>": dict(waves=5),  # configs[1] (10 k frames) and everything larger
-    "k_pdq_hash64<0, 0, 1, false>": dict(waves=5),
-    "k_pdq_hash64<0, 0, 0, false>": dict(waves=5),
-    "k_pdq_hash64<0, 0, 2, false>": dict(waves=5),
-    "k_pdq_hash64<0, 1, 1, false>": dict(waves=4),
-    "k_pdq_hash64<1, 2, 0, false>": dict(waves=5),  # behind k_down512w (the reference's 512x512 frames)
-    "k_pdq_hash64<1, 1, 0, false>": dict(waves=4),
-    "k_pdq_hash64<1, 0, 0, false>": dict(waves=4),
-    "k_pdq_hash64<0, 2, 1, true>": dict(waves=4),   # prefetch experiment (off)
-    "k_pdq_hash64<0, 0, 1, true>": dict(waves=4),
+    "k_pdq_hash64<0, true>": dict(waves=5),   # configs[1] (10 k frames) and everything larger
+    "k_pdq_hash64<0, false>": dict(waves=5),
+    "k_pdq_hash64<1, true>": dict(waves=5),   # behind k_down512w (the reference's 512x512 frames)
+    "k_pdq_hash64<1, false>": dict(waves=4),
     "k_pdq_hash64_fma<0>": dict(waves=3),
     "k_pdq_hash64_fma<1>": dict(waves=3),
     "k_down512w<3>": dict(waves=3),                 # one wave per RGB frame: 12 waves per CU
@@ -191,13 +185,3 @@ def test_strict_hash_kernel_has_no_fused_multiply_add(shapes):
             assert all(re.match(r"v_fma_f32 v\d+, -v\d+, v\d+, (?:v\d+|1\.0)$|v_fmac_f32_e32 ", ln) for ln in bad), (name, bad[:8])
         if name.startswith("k_pdq_hash64_fma"):
             assert any("v_mfma_f32_16x16x4_f32" in ln or "v_mfma_f32_16x16x4f32" in ln for ln in lines), name
-
-
-def test_ablation_builds_need_a_second_define(tmp_path):
-    """Wrong-result ablation switches (HVD_ABL_*; the all-pairs kernel's were removed with the pruned forms in round 6) must
-    not compile out of the product source with one -D: without -DHVD_DEV_ABLATION the preprocessor
-    stops with #error."""
-    for src, define in (("k_pdq.hip", "-DHVD_ABL_NOFETCH"),):
-        r = subprocess.run([HIPCC] + _makefile_flags() + [define, "--cuda-host-only", "-E", os.path.join(CSRC, src), "-o",
-                                                          str(tmp_path / "x.ii")], capture_output=True, text=True)
-        assert r.returncode != 0 and "developer ablation builds" in r.stderr, (src, define, r.stderr[-300:])

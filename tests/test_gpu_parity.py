@@ -33,9 +33,10 @@ def test_k1_golden_gray64(gpu, hvd):
     assert np.array_equal(q, g["quality"])
 
 
-@pytest.mark.parametrize("n", [1, 3, 4, 5, 1023, 10000])
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 1023, 4099, 10000])
 def test_k1_gray64_vs_oracle(gpu, hvd, oracle, n):
-    """BASELINE config 2 at n=10000; ragged counts exercise the partial last workgroup."""
+    """BASELINE config 2 at n=10000; ragged counts exercise the partial last workgroup. Below 8192 frames the hash kernel
+    takes the DCT matrix from SGPRs (4099: several trips per workgroup, the last one ragged), from 8192 on as literals."""
     fr = hvd.synth.frames_gray(n, seed=2)
     h, q = hvd.vpdq.hash_frames(fr)
     ho, qo = oracle.hash_frames(fr, num_threads=8)
@@ -128,7 +129,8 @@ def test_k1_golden_rgb512_and_misc(gpu, hvd):
     assert np.array_equal(h, m["hashes_64"]) and np.array_equal(q, m["quality_64"])
 
 
-@pytest.mark.parametrize("shape", [(5, 512, 512, 3), (3, 64, 200, 3), (2, 257, 64, 3), (2, 130, 190)])
+# (8192, 64, 64, 3): the float-input hash kernel at the size from which it takes the DCT matrix as literals
+@pytest.mark.parametrize("shape", [(5, 512, 512, 3), (3, 64, 200, 3), (2, 257, 64, 3), (2, 130, 190), (8192, 64, 64, 3)])
 def test_k1_downsampler_vs_oracle(gpu, hvd, oracle, shape):
     n, h, w = shape[:3]
     fr = hvd.synth.frames_rgb(n, seed=21, h=h, w=w) if len(shape) == 4 else hvd.synth.frames_gray(n, 22, h, w)
