@@ -1,5 +1,5 @@
 // host_barrier.h -- rendezvous of the device group's worker threads for the exchange steps that have no RCCL underneath
-// (hvd_api.cpp: a group that lists one device twice, or whose communicators could not be created). HIP-free and header-only,
+// (hvd_comm.cpp: a group that lists one device twice, or whose communicators could not be created). HIP-free and header-only,
 // so that the same code is stressed under ThreadSanitizer on a CPU (tests/native/host_barrier_tsan.cpp), like copy_pool.h.
 //
 // A plain generation barrier plus a slot of words per rank. The barrier can be ABORTED: a rank that leaves a group call with an

@@ -1038,28 +1038,4 @@ int run_on_group(const std::function<int(int)>& fn) {
         }
     return HVD_OK;
 }
-
-// all-gather of two words per rank inside a sharded group call (RCCL or host memory); every context's thread calls it
-int exchange_words(const unsigned long long word[2], std::vector<unsigned long long>& all) {
-    const int W = g.world;
-    all.assign(2 * (size_t)W, 0ull);
-    if (g.host_exchange) {
-        HxGuard hx;
-        HX_BARRIER(W);
-        g_hx.words[(size_t)g.rank].assign(word, word + 2);
-        HX_BARRIER(W);
-        for (int r = 0; r < W; ++r) {
-            all[2 * (size_t)r] = g_hx.words[(size_t)r][0];
-            all[2 * (size_t)r + 1] = g_hx.words[(size_t)r][1];
-        }
-        hx.done = true;
-        return HVD_OK;
-    }
-    if (!g.comm_ready) return fail(HVD_ERR_STATE, "no communicator on context %d", g.id);
-    HIP_TRY(hipMemcpyAsync(g.x_cnt_in, word, 16, hipMemcpyHostToDevice, g.stream));
-    NCCL_TRY(ncclAllGather(g.x_cnt_in, g.x_cnt_all, 2, ncclUint64, g.comm, g.stream));
-    HIP_TRY(hipMemcpyAsync(all.data(), g.x_cnt_all, 16 * (size_t)W, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return HVD_OK;
-}
 }  // namespace

@@ -1,6 +1,7 @@
-// hvd_comm.cpp -- the RCCL exchange of the C-ABI (one communicator per context: unique id, init, all-gathers of candidate pairs and
-// of raw bytes, destroy / abort) and the grow-only device staging it shares with the scratch pool of a context. Split out of
-// hvd_api.cpp in round 6; shared state: hvd_internal.h.
+// hvd_comm.cpp -- the exchange steps of the C-ABI: one RCCL communicator per context (unique id, init, destroy / abort), the
+// all-gathers of candidate pairs and of raw bytes, and the agreement step of a sharded group call -- each over RCCL, or through
+// host memory where the group has no RCCL -- plus the grow-only device staging they share with the scratch pool of a context.
+// Shared state: hvd_internal.h.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -30,8 +31,8 @@ int hvd_comm_init(const uint8_t id_bytes[HVD_UNIQUE_ID_BYTES], int rank, int wor
     if (g.comm_ready) return fail(HVD_ERR_STATE, "communicator already initialised");
     ncclUniqueId id;
     memcpy(&id, id_bytes, sizeof id);
-    // the two small words of the video search's agreement step are allocated here, so that nothing can fail between a
-    // rank's decision to enter that collective and the collective itself
+    // the two small words of the agreement step (agree) are allocated here, so that nothing can fail between a rank's
+    // decision to enter that collective and the collective itself
     // (sized for THIS world: a failed hvd_comm_init used to leave buffers of its own world behind, and a retry with a
     // larger one all-gathered 16 * world bytes into them -- ADVICE r3)
     free_exchange_buffers();
@@ -90,10 +91,52 @@ int hvd_comm_abort(void) {
 
 int hvd_comm_allgather_bytes(const void* d_send, void* d_recv, size_t bytes_per_rank) {
     if (int rc = need_ready()) return rc;
-    if (g.host_exchange) {  // in-process group without RCCL: through host memory (every context's thread calls this)
+    return allgather_bytes(d_send, d_recv, bytes_per_rank);
+}
+
+}  // extern "C"
+
+namespace hvdi {
+// The agreement step of a sharded group call: every rank all-gathers (count, failed?), its own result code deciding both words.
+// If any rank failed, all of them leave here in lock-step -- this rank with its own code (its message is already recorded), the
+// others with "<what> abandoned" -- and say so in t_agreed_exit: nobody is left in a collective, so run_on_group aborts no
+// communicator. Over RCCL the words travel in x_cnt_in / x_cnt_all, allocated with the communicator: nothing can fail between a
+// rank's decision to enter the collective and the collective itself. counts[r] = rank r's count.
+int agree(unsigned long long count, int own_rc, const char* what, std::vector<unsigned long long>& counts) {
+    const int W = g.world;
+    const unsigned long long word[2] = {own_rc ? 0ull : count, own_rc ? 1ull : 0ull};
+    std::vector<unsigned long long> all(2 * (size_t)W);
+    if (g.host_exchange) {
+        HxGuard hx;
+        HX_BARRIER(W);  // (everybody is done with the previous round's slots)
+        g_hx.words[(size_t)g.rank].assign(word, word + 2);
+        HX_BARRIER(W);
+        for (int r = 0; r < W; ++r) std::copy_n(g_hx.words[(size_t)r].begin(), 2, all.begin() + 2 * r);
+        hx.done = true;
+    } else {
+        if (!g.comm_ready) return fail(HVD_ERR_STATE, "no communicator on context %d (aborted after another rank's failure?)", g.id);
+        HIP_TRY(hipMemcpyAsync(g.x_cnt_in, word, 16, hipMemcpyHostToDevice, g.stream));
+        NCCL_TRY(ncclAllGather(g.x_cnt_in, g.x_cnt_all, 2, ncclUint64, g.comm, g.stream));
+        HIP_TRY(hipMemcpyAsync(all.data(), g.x_cnt_all, 16 * (size_t)W, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+    }
+    counts.resize((size_t)W);
+    for (int r = 0; r < W; ++r) {
+        if (all[2 * (size_t)r + 1]) {
+            t_agreed_exit = true;  // every rank reads the same words and leaves here
+            return own_rc ? own_rc : fail(HVD_ERR_RCCL, "%s abandoned: rank %d failed", what, r);
+        }
+        counts[(size_t)r] = all[2 * (size_t)r];
+    }
+    return HVD_OK;
+}
+
+// bytes_per_rank device bytes of every rank -> d_recv, in rank order
+int allgather_bytes(const void* d_send, void* d_recv, size_t bytes_per_rank) {
+    if (g.host_exchange) {  // every rank's bytes through host memory, the concatenation back to every device
         const int W = g.world;
         std::vector<unsigned long long>& mine = g_hx.words[(size_t)g.rank];
-        HxGuard hx;
+        HxGuard hx;  // (a failure between the barriers must not strand the peers: ADVICE r4)
         HX_BARRIER(W);
         mine.resize((bytes_per_rank + 7) / 8);
         if (bytes_per_rank) HIP_TRY(hipMemcpyAsync(mine.data(), d_send, bytes_per_rank, hipMemcpyDeviceToHost, g.stream));
@@ -103,18 +146,16 @@ int hvd_comm_allgather_bytes(const void* d_send, void* d_recv, size_t bytes_per_
             HIP_TRY(hipMemcpyAsync((char*)d_recv + (size_t)r * bytes_per_rank, g_hx.words[(size_t)r].data(), bytes_per_rank,
                                    hipMemcpyHostToDevice, g.stream));
         HIP_TRY(hipStreamSynchronize(g.stream));
-        HX_BARRIER(W);
+        HX_BARRIER(W);  // (the slots are free again only when everybody has copied them)
         hx.done = true;
         return HVD_OK;
     }
-    if (!g.comm_ready) return fail(HVD_ERR_STATE, "hvd_comm_init() has not been called");
+    if (!g.comm_ready)
+        return fail(HVD_ERR_STATE, "no communicator on context %d (hvd_comm_init() not called, or aborted after another rank's failure)", g.id);
     NCCL_TRY(ncclAllGather(d_send, d_recv, bytes_per_rank, ncclUint8, g.comm, g.stream));
     return HVD_OK;
 }
 
-}  // extern "C"
-
-namespace hvdi {
 int grow(void** p, size_t* cap, size_t need) {
     if (need <= *cap) return HVD_OK;
     if (*p) HIP_TRY(hipFree(*p));

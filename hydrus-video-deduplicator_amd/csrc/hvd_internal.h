@@ -1,7 +1,8 @@
 // hvd_internal.h -- what the translation units of the host layer share (round 6: hvd_api.cpp was one 2 200-line unit):
 //   hvd_api.cpp     contexts and the device group (init, fan-out, abandon / re-arm), device-resident API, timers, developer keys
 //   hvd_search.cpp  host-buffer entry points and the video-level search (K3)
-//   hvd_comm.cpp    the RCCL exchange (communicator per context, all-gathers of pairs / bytes)
+//   hvd_comm.cpp    the exchange steps, over RCCL or host memory (communicator per context, agreement step, all-gathers of
+//                   pairs / bytes) and the grow-only device staging
 // Everything here is internal linkage in spirit (namespace hvdi); the C-ABI is include/hvd_mi355x.h alone.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -123,10 +124,12 @@ inline bool pair_less(const hvd_pair& x, const hvd_pair& y) { return x.i != y.i 
 
 // hvd_api.cpp: the group
 int run_on_group(const std::function<int(int)>& fn);  // fn(rank) on every context, one host thread each
-int exchange_words(const unsigned long long word[2], std::vector<unsigned long long>& all);  // all-gather of two words per rank inside a group call
 void abort_group_comms();
 
-// hvd_comm.cpp: grow-only device staging, scratch pool of a context
+// hvd_comm.cpp: the exchange steps inside a sharded group call (every context's thread calls them), grow-only device staging,
+// scratch pool of a context
+int agree(unsigned long long count, int own_rc, const char* what, std::vector<unsigned long long>& counts);
+int allgather_bytes(const void* d_send, void* d_recv, size_t bytes_per_rank);
 void free_exchange_buffers();
 int grow(void** p, size_t* cap, size_t need);
 int scratch(Ctx::Scr id, size_t need, void** out);

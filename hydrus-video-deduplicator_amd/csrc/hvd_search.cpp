@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <thread>
 #include <vector>
@@ -19,6 +20,29 @@ using namespace hvdi;
 namespace {
 constexpr unsigned long long kMatchServerIdleUs = 300;   // the server leaves after this long without a call ...
 constexpr unsigned long long kMatchServerLifeUs = 2000;  // ... and after this long in any case (another thread's hipFree / device-wide wait gets its turn)
+
+// fn(rank, result) on every context of the group (run_on_group: one host thread each); the call's result is rank 0's
+template <class R, class Fn>
+int run_keep_rank0(R& res, const Fn& fn) {
+    return run_on_group([&](int r) -> int {
+        R mine{};
+        if (int rc = fn(r, mine)) return rc;
+        if (r == 0) res = std::move(mine);
+        return HVD_OK;
+    });
+}
+
+// the records of a host-buffer entry point, sorted, to out[cap]; *out_count = their true number (total)
+template <class T>
+int copy_out(std::vector<T>& recs, int64_t total, bool (*less)(const T&, const T&), T* out, int64_t cap, int64_t* out_count,
+             const char* what) {
+    *out_count = total;
+    if (total > cap)
+        return fail(HVD_ERR_OVERFLOW, "%s buffer too small: need %lld records, cap %lld", what, (long long)total, (long long)cap);
+    std::sort(recs.begin(), recs.end(), less);
+    if (!recs.empty()) memcpy(out, recs.data(), sizeof(T) * recs.size());
+    return HVD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -104,14 +128,14 @@ int hvd_pdq_hash_frames_dihedral_rgb24_u8(const uint8_t* frames, int64_t n, int 
 
 // Runs the default all-pairs kernel (FP4-MFMA form) on a host DB -- this context's share of the tiles (rank of world) --
 // and fetches up to `cap` unordered records: its own when world == 1, every rank's after the group's exchange otherwise
-// (RCCL all-gather of counts then padded records between the devices, or host memory where the group has no RCCL).
+// (agreement step on the true counts, then the records: RCCL between the devices, or host memory where the group has no RCCL).
 // *out_count = the true number of records over all ranks. Device buffers come from the grow-only pool (caller holds h_mu).
 static int allpairs_host_raw(const uint8_t* db, int64_t n, const int32_t* group, int max_dist,
                              std::vector<hvd_pair>& recs, int64_t cap, int64_t* out_count, int rank = 0, int world = 1) {
     void* d_pairs = nullptr;
     unsigned long long cnt = 0;
-    // Everything up to the exchange runs inside `local`: at world > 1 its result code rides along with the count, so that a
-    // rank that fails on its own does not leave the others waiting in the exchange (as in the video search, vmatch_build).
+    // Everything up to the exchange runs inside `local`: at world > 1 its result code goes into the agreement step with the
+    // count, so that a rank that fails on its own does not leave the others waiting in the exchange (as in vmatch_build).
     auto local = [&]() -> int {
         void *d_db = nullptr, *d_img = nullptr, *d_grp = nullptr;
         unsigned long long* d_cnt = nullptr;
@@ -148,14 +172,10 @@ static int allpairs_host_raw(const uint8_t* db, int64_t n, const int32_t* group,
         return HVD_OK;
     }
     // the true counts first (a rank whose own buffer overflowed must not truncate the total), then the records
-    const unsigned long long word[2] = {local_rc ? 0ull : cnt, local_rc ? 1ull : 0ull};
-    std::vector<unsigned long long> all;
-    if (int rc = exchange_words(word, all)) return local_rc ? local_rc : rc;
+    std::vector<unsigned long long> counts;
+    if (int rc = agree(cnt, local_rc, "all-pairs search", counts)) return rc;
     unsigned long long total = 0;
-    for (int r = 0; r < world; ++r) {
-        if (all[2 * (size_t)r + 1]) return local_rc ? local_rc : fail(HVD_ERR_RCCL, "all-pairs search abandoned: rank %d failed", r);
-        total += all[2 * (size_t)r];
-    }
+    for (unsigned long long c : counts) total += c;
     *out_count = (int64_t)total;
     if (total > (unsigned long long)cap) {  // every rank sees the same total: all of them skip the record exchange
         recs.clear();
@@ -177,34 +197,23 @@ int hvd_allpairs_hamming256(const uint8_t* db, int64_t n, const int32_t* group, 
     *out_count = 0;
     if (n < 2) return HVD_OK;
     if (!db) return fail(HVD_ERR_ARG, "db is NULL");
-    std::vector<hvd_pair> recs;
+    struct Found {
+        std::vector<hvd_pair> recs;
+        int64_t total = 0;
+    } res;
     const int W = (g_nctx > 1 && max_dist < 128 && n >= 4096) ? g_nctx : 1;  // small DBs: one device (launch-bound anyway)
-    int64_t total = 0;
     if (W == 1) {
         std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-        if (int rc = allpairs_host_raw(db, n, group, max_dist, recs, cap, &total)) return rc;
+        if (int rc = allpairs_host_raw(db, n, group, max_dist, res.recs, cap, &res.total)) return rc;
     } else {
         // DB replicated on every device of the group, tile (rb, cb) -> context (rb + cb) % W, candidates exchanged
-        int rc = run_on_group([&](int r) -> int {
-            std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-            std::vector<hvd_pair> mine;
-            int64_t t = 0;
-            if (int rc_ = allpairs_host_raw(db, n, group, max_dist, mine, cap, &t, r, W)) return rc_;
-            if (r == 0) {
-                recs.swap(mine);
-                total = t;
-            }
-            return HVD_OK;
-        });
-        if (rc) return rc;
+        if (int rc = run_keep_rank0(res, [&](int r, Found& mine) -> int {
+                std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+                return allpairs_host_raw(db, n, group, max_dist, mine.recs, cap, &mine.total, r, W);
+            }))
+            return rc;
     }
-    *out_count = total;
-    if (*out_count > cap)
-        return fail(HVD_ERR_OVERFLOW, "pair buffer too small: need %lld records, cap %lld", (long long)*out_count,
-                    (long long)cap);
-    std::sort(recs.begin(), recs.end(), pair_less);
-    if (!recs.empty()) memcpy(out, recs.data(), sizeof(hvd_pair) * recs.size());
-    return HVD_OK;
+    return copy_out(res.recs, res.total, pair_less, out, cap, out_count, "pair");
 }
 
 // Frame-level hits -> per video pair (a = video of the row frame, b = video of the column frame):
@@ -377,6 +386,29 @@ int read_counters(unsigned long long* d_counters, unsigned long long out[4]) {
     return HVD_OK;
 }
 
+// A hash table of the video search: the scratch slots `tables` share one size -- 4 slots of 8 bytes per key, a power of two, at
+// least `floor` (hvd_debug_set "vmatch_slots_log2" forces the first size) -- and each is cleared to its byte; then insert(slots)
+// runs. When some insert ran out of probes (c[0] != 0) the tables are rebuilt 4x larger and the same pass runs again.
+struct Table {
+    Ctx::Scr id;
+    int fill;
+    void** p;
+};
+template <class Insert>
+int build_table(std::initializer_list<Table> tables, unsigned long long floor, unsigned long long keys, unsigned long long* d_counters,
+                unsigned long long c[4], unsigned long long* slots, const Insert& insert) {
+    *slots = g.v_force_slots_log2 ? 1ull << g.v_force_slots_log2 : pow2_at_least(std::max(floor, 4ull * keys));
+    for (;; *slots *= 4) {
+        for (const Table& t : tables)
+            if (int rc = scratch(t.id, 8 * *slots, t.p)) return rc;
+        for (const Table& t : tables) HIP_TRY(hipMemsetAsync(*t.p, t.fill, 8 * *slots, g.stream));
+        HIP_TRY(hipMemsetAsync(d_counters, 0, 32, g.stream));
+        if (int rc = insert(*slots)) return rc;
+        if (int rc = read_counters(d_counters, c)) return rc;
+        if (c[0] == 0) return HVD_OK;
+    }
+}
+
 // Which 128 bits should the first stage see? (k_hamming_mfma.hip: "data-dependent bit order".) From the co-occurrence counts of a
 // strided sample of the packed hashes: Pearson correlation of every pair of bits, then 128 times drop the bit whose summed
 // |correlation| with the bits still in the set is largest (a constant bit goes first). perm = the 128 kept bits in ascending
@@ -434,8 +466,8 @@ int vmatch_build(const VmArgs& v) {
     if (exchange && ((!g.comm_ready && !g.host_exchange) || g.world != v.world || g.rank != v.rank))
         return fail(HVD_ERR_STATE, "rank %d of %d needs hvd_comm_init() with the same rank/world first", v.rank, v.world);
     // world > 1: a rank that fails on its own (out of memory while a table regrows, a launch error) must not leave its
-    // peers blocked in the all-gathers below. Everything up to the exchange runs inside `local`, whose result code rides
-    // along with the key count in the first all-gather: every rank learns of a failure anywhere and all of them return.
+    // peers blocked in the all-gathers below. Everything up to the exchange runs inside `local`, whose result code goes into
+    // the first agreement step with the key count: every rank learns of a failure anywhere and all of them return.
     unsigned long long* d_counters = nullptr;
     unsigned long long slots = 0;
     unsigned long long* d_set = nullptr;
@@ -482,16 +514,11 @@ int vmatch_build(const VmArgs& v) {
             g.v_bit_order_used = 1;
         }
     }
-    const unsigned long long frames = (unsigned long long)v.nt + (v.rect ? v.nq : 0u);
-    slots = pow2_at_least(std::max<unsigned long long>(1ull << 16, 4ull * frames));
-    if (g.v_force_slots_log2) slots = 1ull << g.v_force_slots_log2;
 #ifndef HVD_NO_BENCH_SYMBOLS
     if (g.v_fail_rank == v.rank + 1) return fail(HVD_ERR_HIP, "injected failure on rank %d (hvd_debug_set vmatch_fail_rank)", v.rank);
 #endif
-    for (;;) {
-        SCR(S_SET, 8 * slots, d_set);
-        HIP_TRY(hipMemsetAsync(d_set, 0xFF, 8 * slots, g.stream));
-        HIP_TRY(hipMemsetAsync(d_counters, 0, 32, g.stream));
+    const unsigned long long frames = (unsigned long long)v.nt + (v.rect ? v.nq : 0u);
+    return build_table({{Ctx::S_SET, 0xFF, (void**)&d_set}}, 1ull << 16, frames, d_counters, c, &slots, [&](unsigned long long n) -> int {
         hvd::AllPairsArgs a;
         a.d_db = d_bits_t;
         a.d_db_q = d_bits_q;
@@ -507,15 +534,12 @@ int vmatch_build(const VmArgs& v) {
         a.variant = g.v_variant ? g.v_variant : HVD_DEFAULT_VARIANT;
         a.col_chunk = 0;
         a.ctx_id = t_ctx;
-        a.sink = hvd::VideoSink{d_set, slots - 1, d_counters, v.d_vid_q, v.d_vid_t};
+        a.sink = hvd::VideoSink{d_set, n - 1, d_counters, v.d_vid_q, v.d_vid_t};
         hipError_t e = v.rect ? hvd::launch_cross_mfma(a, img_q, v.nq, img_t, v.d_excl_t, g.stream)
                               : hvd::launch_allpairs_mfma(a, img_t, g.stream);
         if (e != hipSuccess) return fail(HVD_ERR_HIP, "video-level all-pairs launch: %s", hipGetErrorString(e));
-        if (int rc = read_counters(d_counters, c)) return rc;
-        if (c[0] == 0) break;
-        slots *= 4;  // some insert ran out of probes: larger table, same pass again
-    }
-    return HVD_OK;
+        return HVD_OK;
+    });
     };
     const auto t_begin = std::chrono::steady_clock::now();
     auto us_since = [](std::chrono::steady_clock::time_point t0) {
@@ -530,42 +554,14 @@ int vmatch_build(const VmArgs& v) {
     unsigned long long n_src = slots, n_keys = c[1];
     if (exchange) {
         // each rank saw only its tiles' hits: all-gather the key lists and de-duplicate (a key may be found twice)
-        unsigned long long *d_list = nullptr, *d_all = nullptr, *d_set2 = nullptr;
+        unsigned long long *d_list = nullptr, *d_all = nullptr, *d_set2 = nullptr, slots2 = 0;
         const int W = g.world;
-        // (the two small exchange words were allocated with the communicator: nothing can fail between here and the collective)
-        unsigned long long word[2] = {local_rc ? 0ull : n_keys, (unsigned long long)(unsigned)(local_rc ? 1 : 0)};
-        std::vector<unsigned long long> words(2 * (size_t)W);
-        auto agree = [&](const char* what, int own_rc) -> int {  // all-gather (count, status); a failure anywhere -> everyone leaves
-            if (g.host_exchange) {  // group without RCCL: the words meet in host memory
-                HxGuard hx;
-                HX_BARRIER(W);      // (everybody is done with the previous round's slots)
-                g_hx.words[(size_t)g.rank].assign(word, word + 2);
-                HX_BARRIER(W);
-                for (int r = 0; r < W; ++r) {
-                    words[2 * (size_t)r] = g_hx.words[(size_t)r][0];
-                    words[2 * (size_t)r + 1] = g_hx.words[(size_t)r][1];
-                }
-                hx.done = true;
-            } else {
-                if (!g.comm_ready) return fail(HVD_ERR_STATE, "no communicator on context %d (aborted after another rank's failure?)", g.id);
-                HIP_TRY(hipMemcpyAsync(g.x_cnt_in, word, 16, hipMemcpyHostToDevice, g.stream));
-                NCCL_TRY(ncclAllGather(g.x_cnt_in, g.x_cnt_all, 2, ncclUint64, g.comm, g.stream));
-                HIP_TRY(hipMemcpyAsync(words.data(), g.x_cnt_all, 16 * (size_t)W, hipMemcpyDeviceToHost, g.stream));
-                HIP_TRY(hipStreamSynchronize(g.stream));
-            }
-            for (int r = 0; r < W; ++r)
-                if (words[2 * (size_t)r + 1]) {
-                    t_agreed_exit = true;       // every rank reads the same words and leaves here, in lock-step
-                    if (own_rc) return own_rc;  // our own failure: its message is already recorded
-                    return fail(HVD_ERR_RCCL, "video search abandoned: rank %d failed %s", r, what);
-                }
-            return HVD_OK;
-        };
-        if (int rc = agree("before the key exchange", local_rc)) return rc;
+        std::vector<unsigned long long> counts;
+        if (int rc = agree(n_keys, local_rc, "video search", counts)) return rc;
         unsigned long long mx = 1, total = 0;
-        for (int r = 0; r < W; ++r) {
-            mx = std::max(mx, words[2 * (size_t)r]);
-            total += words[2 * (size_t)r];
+        for (unsigned long long k : counts) {
+            mx = std::max(mx, k);
+            total += k;
         }
         // the exchange buffers depend on the gathered counts: allocate, then agree once more before the big all-gather
         const int alloc_rc = [&]() -> int {
@@ -573,62 +569,33 @@ int vmatch_build(const VmArgs& v) {
             SCR(S_LISTALL, 8 * mx * (size_t)W, d_all);
             return HVD_OK;
         }();
-        word[0] = 0;
-        word[1] = alloc_rc ? 1ull : 0ull;
-        if (int rc = agree("while allocating the exchange buffers", alloc_rc)) return rc;
+        if (int rc = agree(0, alloc_rc, "video key exchange", counts)) return rc;
         HIP_TRY(hipMemsetAsync(d_list, 0xFF, 8 * mx, g.stream));
         HIP_TRY(hipMemsetAsync(d_counters + 2, 0, 8, g.stream));
         HIP_TRY(hvd::launch_set_to_list(d_set, slots, d_list, mx, d_counters + 2, g.stream));
-        if (g.host_exchange) {  // every rank's list through host memory, the concatenation back to every device
-            std::vector<unsigned long long>& mine = g_hx.words[(size_t)g.rank];
-            HxGuard hx;  // (a failure between the barriers must not strand the peers: ADVICE r4)
-            HX_BARRIER(W);
-            mine.resize((size_t)mx);
-            HIP_TRY(hipMemcpyAsync(mine.data(), d_list, 8 * (size_t)mx, hipMemcpyDeviceToHost, g.stream));
-            HIP_TRY(hipStreamSynchronize(g.stream));
-            HX_BARRIER(W);
-            for (int r = 0; r < W; ++r)
-                HIP_TRY(hipMemcpyAsync(d_all + (size_t)r * mx, g_hx.words[(size_t)r].data(), 8 * (size_t)mx, hipMemcpyHostToDevice, g.stream));
-            HIP_TRY(hipStreamSynchronize(g.stream));
-            HX_BARRIER(W);  // (the slots are free again only when everybody has copied them)
-            hx.done = true;
-        } else {
-            if (!g.comm_ready) return fail(HVD_ERR_STATE, "no communicator on context %d (aborted after another rank's failure?)", g.id);
-            NCCL_TRY(ncclAllGather(d_list, d_all, 8 * mx, ncclUint8, g.comm, g.stream));
-        }
-        unsigned long long slots2 = pow2_at_least(std::max<unsigned long long>(1ull << 16, 4ull * total));
-        if (g.v_force_slots_log2) slots2 = 1ull << g.v_force_slots_log2;
-        for (;;) {
-            SCR(S_SET2, 8 * slots2, d_set2);
-            HIP_TRY(hipMemsetAsync(d_set2, 0xFF, 8 * slots2, g.stream));
-            HIP_TRY(hipMemsetAsync(d_counters, 0, 32, g.stream));
-            HIP_TRY(hvd::launch_list_to_set(d_all, mx * (unsigned long long)W, d_set2, slots2 - 1, d_counters, g.stream));
-            if (int rc = read_counters(d_counters, c)) return rc;
-            if (c[0] == 0) break;
-            slots2 *= 4;
-        }
+        if (int rc = allgather_bytes(d_list, d_all, 8 * mx)) return rc;
+        if (int rc = build_table({{Ctx::S_SET2, 0xFF, (void**)&d_set2}}, 1ull << 16, total, d_counters, c, &slots2,
+                                 [&](unsigned long long n) -> int {
+                                     HIP_TRY(hvd::launch_list_to_set(d_all, mx * (unsigned long long)W, d_set2, n - 1, d_counters, g.stream));
+                                     return HVD_OK;
+                                 }))
+            return rc;
         d_src = d_set2;
         n_src = slots2;
         n_keys = c[1];
         g.v_us[1] = us_since(t_exchange);
     }
     const auto t_fold = std::chrono::steady_clock::now();
-    unsigned long long pslots = pow2_at_least(std::max<unsigned long long>(1024, 4ull * n_keys));
-    if (g.v_force_slots_log2) pslots = 1ull << g.v_force_slots_log2;
-    for (;;) {
-        unsigned long long* d_pkeys = nullptr;
-        void* d_pcnt = nullptr;
-        SCR(S_PKEYS, 8 * pslots, d_pkeys);
-        SCR(S_PCNT, 8 * pslots, d_pcnt);
-        HIP_TRY(hipMemsetAsync(d_pkeys, 0xFF, 8 * pslots, g.stream));
-        HIP_TRY(hipMemsetAsync(d_pcnt, 0, 8 * pslots, g.stream));
-        HIP_TRY(hipMemsetAsync(d_counters, 0, 32, g.stream));
-        HIP_TRY(hvd::launch_keys_to_pairs(d_src, n_src, v.d_vid_q, v.d_vid_t, v.rect, d_pkeys, d_pcnt, pslots - 1, d_counters,
-                                          g.stream));
-        if (int rc = read_counters(d_counters, c)) return rc;
-        if (c[0] == 0) break;
-        pslots *= 4;
-    }
+    unsigned long long* d_pkeys = nullptr;
+    void* d_pcnt = nullptr;
+    unsigned long long pslots = 0;
+    if (int rc = build_table({{Ctx::S_PKEYS, 0xFF, (void**)&d_pkeys}, {Ctx::S_PCNT, 0, &d_pcnt}}, 1024, n_keys, d_counters, c,
+                             &pslots, [&](unsigned long long n) -> int {
+                                 HIP_TRY(hvd::launch_keys_to_pairs(d_src, n_src, v.d_vid_q, v.d_vid_t, v.rect, d_pkeys, d_pcnt, n - 1,
+                                                                   d_counters, g.stream));
+                                 return HVD_OK;
+                             }))
+        return rc;
     g.v_pslots = pslots;
     g.v_us[2] = us_since(t_fold);
     return HVD_OK;
@@ -644,7 +611,7 @@ int vmatch_emit(hvd_vmatch* d_out, int64_t cap, unsigned long long* d_count) {
 
 bool vmatch_less(const hvd_vmatch& x, const hvd_vmatch& y) { return x.a != y.a ? x.a < y.a : x.b < y.b; }
 
-// build + emit into the pool's record buffer, grown until everything fits (only the emit is repeated)
+// build + emit into the pool's record buffer, grown until everything fits (only the emit is repeated); unordered
 int vmatch_to_host(const VmArgs& v, int64_t expect, std::vector<hvd_vmatch>& res) {
     if (int rc = vmatch_build(v)) return rc;
     unsigned long long* d_counters = nullptr;
@@ -668,7 +635,20 @@ int vmatch_to_host(const VmArgs& v, int64_t expect, std::vector<hvd_vmatch>& res
         }
         break;
     }
-    std::sort(res.begin(), res.end(), vmatch_less);
+    return HVD_OK;
+}
+
+// the device-resident searches after their argument checks: nothing to compare zeroes the count, otherwise build + emit;
+// the stream is drained either way
+int vmatch_on_device(bool empty, const VmArgs& v, void* d_out, int64_t cap, void* d_count) {
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    if (empty) {
+        HIP_TRY(hipMemsetAsync(d_count, 0, 8, g.stream));
+    } else {
+        if (int rc = vmatch_build(v)) return rc;
+        if (int rc = vmatch_emit((hvd_vmatch*)d_out, cap, (unsigned long long*)d_count)) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(g.stream));
     return HVD_OK;
 }
 
@@ -721,53 +701,40 @@ int hvd_vpdq_match_videos(const uint8_t* frames, const int64_t* offsets, int64_t
         // vmatch_build (RCCL all-gather between the devices, host memory where the group has no RCCL); every rank ends up
         // with the whole result, rank 0's is returned
         const int W = g_nctx;
-        int rc = run_on_group([&](int r) -> int {
-            std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+        if (int rc = run_keep_rank0(res, [&](int r, std::vector<hvd_vmatch>& mine) -> int {
+                std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+                void* d_img = nullptr;
+                int32_t* d_vid = nullptr;
+                const int up = upload_library(frames, offsets, V, nf, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_img, &d_vid);
+                VmArgs v{d_img, (uint32_t)nf, d_img, (uint32_t)nf, false, d_vid, d_vid, nullptr, nullptr, max_dist, r, W};
+                v.pre_rc = up;
+                return vmatch_to_host(v, V, mine);
+            }))
+            return rc;
+    } else {
+        std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+        if (max_dist >= 128) {
+            // popcount route (a tolerance the reference never uses): frame-level hits reduced on the host
+            std::vector<int32_t> vid((size_t)nf);
+            for (int64_t v = 0; v < V; ++v)
+                for (int64_t f = offsets[v]; f < offsets[v + 1]; ++f) vid[(size_t)f] = (int32_t)v;
+            std::vector<hvd_pair> recs;
+            int64_t fcap = std::max<int64_t>(1 << 16, nf), fcount = 0;
+            for (;;) {
+                if (int rc = allpairs_host_raw(frames, nf, vid.data(), max_dist, recs, fcap, &fcount)) return rc;
+                if (fcount <= fcap) break;
+                fcap = fcount;
+            }
+            aggregate_video_hits(recs, vid.data(), vid.data(), res);
+        } else {
             void* d_img = nullptr;
             int32_t* d_vid = nullptr;
-            const int up = upload_library(frames, offsets, V, nf, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_img, &d_vid);
-            VmArgs v{d_img, (uint32_t)nf, d_img, (uint32_t)nf, false, d_vid, d_vid, nullptr, nullptr, max_dist, r, W};
-            v.pre_rc = up;
-            std::vector<hvd_vmatch> mine;
-            if (int rc_ = vmatch_to_host(v, V, mine)) return rc_;
-            if (r == 0) res.swap(mine);
-            return HVD_OK;
-        });
-        if (rc) return rc;
-        *out_count = (int64_t)res.size();
-        if ((int64_t)res.size() > cap)
-            return fail(HVD_ERR_OVERFLOW, "video match buffer too small: need %lld, cap %lld", (long long)res.size(),
-                        (long long)cap);
-        if (!res.empty()) memcpy(out, res.data(), sizeof(hvd_vmatch) * res.size());
-        return HVD_OK;
-    }
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    if (max_dist >= 128) {
-        // popcount route (a tolerance the reference never uses): frame-level hits reduced on the host
-        std::vector<int32_t> vid((size_t)nf);
-        for (int64_t v = 0; v < V; ++v)
-            for (int64_t f = offsets[v]; f < offsets[v + 1]; ++f) vid[(size_t)f] = (int32_t)v;
-        std::vector<hvd_pair> recs;
-        int64_t fcap = std::max<int64_t>(1 << 16, nf), fcount = 0;
-        for (;;) {
-            if (int rc = allpairs_host_raw(frames, nf, vid.data(), max_dist, recs, fcap, &fcount)) return rc;
-            if (fcount <= fcap) break;
-            fcap = fcount;
+            if (int rc = upload_library(frames, offsets, V, nf, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_img, &d_vid)) return rc;
+            VmArgs v{d_img, (uint32_t)nf, d_img, (uint32_t)nf, false, d_vid, d_vid, nullptr, nullptr, max_dist, 0, 1};
+            if (int rc = vmatch_to_host(v, V, res)) return rc;
         }
-        aggregate_video_hits(recs, vid.data(), vid.data(), res);
-    } else {
-        void* d_img = nullptr;
-        int32_t* d_vid = nullptr;
-        if (int rc = upload_library(frames, offsets, V, nf, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_img, &d_vid)) return rc;
-        VmArgs v{d_img, (uint32_t)nf, d_img, (uint32_t)nf, false, d_vid, d_vid, nullptr, nullptr, max_dist, 0, 1};
-        if (int rc = vmatch_to_host(v, V, res)) return rc;
     }
-    *out_count = (int64_t)res.size();
-    if ((int64_t)res.size() > cap)
-        return fail(HVD_ERR_OVERFLOW, "video match buffer too small: need %lld, cap %lld", (long long)res.size(),
-                    (long long)cap);
-    if (!res.empty()) memcpy(out, res.data(), sizeof(hvd_vmatch) * res.size());
-    return HVD_OK;
+    return copy_out(res, (int64_t)res.size(), vmatch_less, out, cap, out_count, "video match");
 }
 
 int hvd_vpdq_match_videos_cross(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* ids_q,
@@ -818,22 +785,11 @@ int hvd_vpdq_match_videos_cross(const uint8_t* frames_q, const int64_t* offsets_
     std::vector<hvd_vmatch> res;
     if (g_nctx > 1 && nq + nt >= 4096) {
         const int W = g_nctx;
-        int rc = run_on_group([&](int r) -> int {
-            std::vector<hvd_vmatch> mine;
-            if (int rc_ = one(r, W, mine)) return rc_;
-            if (r == 0) res.swap(mine);
-            return HVD_OK;
-        });
-        if (rc) return rc;
+        if (int rc = run_keep_rank0(res, [&](int r, std::vector<hvd_vmatch>& mine) { return one(r, W, mine); })) return rc;
     } else if (int rc = one(0, 1, res)) {
         return rc;
     }
-    *out_count = (int64_t)res.size();
-    if ((int64_t)res.size() > cap)
-        return fail(HVD_ERR_OVERFLOW, "video match buffer too small: need %lld, cap %lld", (long long)res.size(),
-                    (long long)cap);
-    if (!res.empty()) memcpy(out, res.data(), sizeof(hvd_vmatch) * res.size());
-    return HVD_OK;
+    return copy_out(res, (int64_t)res.size(), vmatch_less, out, cap, out_count, "video match");
 }
 
 /* ---- device-resident forms: hashes / images / maps already in HBM (BASELINE config 5) ---- */
@@ -905,19 +861,10 @@ int hvd_dev_vpdq_match_videos(const void* d_img, int64_t n, const void* d_video,
     if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
     if (world < 1 || rank < 0 || rank >= world) return fail(HVD_ERR_ARG, "bad rank/world %d/%d", rank, world);
     if (cap < 0 || !d_count || (cap > 0 && !d_out)) return fail(HVD_ERR_ARG, "bad output buffer");
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    if (n < 2) {
-        HIP_TRY(hipMemsetAsync(d_count, 0, 8, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        return HVD_OK;
-    }
-    if (!d_img || !d_video) return fail(HVD_ERR_ARG, "d_img / d_video is NULL");
-    VmArgs v{d_img, (uint32_t)n, d_img, (uint32_t)n, false, (const int32_t*)d_video, (const int32_t*)d_video, nullptr, nullptr,
-             max_dist, rank, world};
-    if (int rc = vmatch_build(v)) return rc;
-    if (int rc = vmatch_emit((hvd_vmatch*)d_out, cap, (unsigned long long*)d_count)) return rc;
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return HVD_OK;
+    if (n >= 2 && (!d_img || !d_video)) return fail(HVD_ERR_ARG, "d_img / d_video is NULL");
+    return vmatch_on_device(n < 2, {d_img, (uint32_t)n, d_img, (uint32_t)n, false, (const int32_t*)d_video, (const int32_t*)d_video,
+                                    nullptr, nullptr, max_dist, rank, world},
+                            d_out, cap, d_count);
 }
 
 int hvd_dev_vpdq_emit_again(void* d_out, int64_t cap, void* d_count) {
@@ -939,19 +886,11 @@ int hvd_dev_vpdq_match_videos_cross(const void* d_img_q, int64_t nq, const void*
     if (world < 1 || rank < 0 || rank >= world) return fail(HVD_ERR_ARG, "bad rank/world %d/%d", rank, world);
     if (cap < 0 || !d_count || (cap > 0 && !d_out)) return fail(HVD_ERR_ARG, "bad output buffer");
     if ((d_excl_q == nullptr) != (d_excl_t == nullptr)) return fail(HVD_ERR_ARG, "pass both exclusion maps or neither");
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    if (nq == 0 || nt == 0) {
-        HIP_TRY(hipMemsetAsync(d_count, 0, 8, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-        return HVD_OK;
-    }
-    if (!d_img_q || !d_img_t || !d_video_q || !d_video_t) return fail(HVD_ERR_ARG, "NULL image / video map");
-    VmArgs v{d_img_q, (uint32_t)nq, d_img_t, (uint32_t)nt, true, (const int32_t*)d_video_q, (const int32_t*)d_video_t,
-             (const int32_t*)d_excl_q, (const int32_t*)d_excl_t, max_dist, rank, world};
-    if (int rc = vmatch_build(v)) return rc;
-    if (int rc = vmatch_emit((hvd_vmatch*)d_out, cap, (unsigned long long*)d_count)) return rc;
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return HVD_OK;
+    const bool empty = nq == 0 || nt == 0;
+    if (!empty && (!d_img_q || !d_img_t || !d_video_q || !d_video_t)) return fail(HVD_ERR_ARG, "NULL image / video map");
+    return vmatch_on_device(empty, {d_img_q, (uint32_t)nq, d_img_t, (uint32_t)nt, true, (const int32_t*)d_video_q, (const int32_t*)d_video_t,
+                                    (const int32_t*)d_excl_q, (const int32_t*)d_excl_t, max_dist, rank, world},
+                            d_out, cap, d_count);
 }
 
 #ifndef HVD_NO_BENCH_SYMBOLS

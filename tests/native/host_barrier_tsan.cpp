@@ -1,7 +1,7 @@
 // ThreadSanitizer stress of the device group's host-memory rendezvous (csrc/host_barrier.h), built and run by
 // tests/test_copy_pool.py::test_host_barrier_under_thread_sanitizer:
 //   g++ -std=c++17 -O1 -g -fsanitize=thread -pthread host_barrier_tsan.cpp -o host_barrier_tsan && ./host_barrier_tsan
-// The shape of hvd_api.cpp's exchange blocks (run_on_group -> exchange_words / all-gather through g_hx.words): W rank threads per
+// The shape of hvd_comm.cpp's exchange blocks (run_on_group -> agree / all-gathers through g_hx.words): W rank threads per
 // "group call"; every rank writes its slot between two barriers and reads everybody's after the second. Calls alternate
 // between clean ones (every rank's sum must be right), calls in which one rank leaves early through an HxGuard (its peers must
 // come out of their barrier with `false`, nobody may hang, nobody may read a slot that is being written) and calls aborted from

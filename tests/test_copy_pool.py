@@ -83,7 +83,7 @@ def test_copy_pool_under_thread_sanitizer(tmp_path):
 
 def test_host_barrier_under_thread_sanitizer(tmp_path):
     """The device group's host-memory rendezvous (csrc/host_barrier.h: abortable generation barrier + one slot of words per
-    rank -- what run_on_group, the agreement step and the host-memory all-gathers of hvd_api.cpp run on) factored into a HIP-free
+    rank -- what run_on_group, the agreement step and the host-memory all-gathers of hvd_comm.cpp run on) factored into a HIP-free
     header and stressed under ThreadSanitizer: clean calls, calls in which one rank leaves early through its
     guard, calls aborted from another thread; world sizes 2, 3 and 8; nobody hangs, no slot is read while it is written."""
     import os

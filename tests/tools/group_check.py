@@ -218,6 +218,16 @@ try:
 finally:
     L.check(lib.hvd_debug_set(b"vmatch_fail_rank", 0))
 assert np.array_equal(hvd_amd.match_videos(frames, offsets, 31), wantv)
+# ... and so does an agreed local failure of the all-pairs pass (the last context cannot reserve its index scratch)
+L.check(lib.hvd_debug_set(b"allpairs_index", 1))
+L.check(lib.hvd_debug_set(b"allpairs_index_fail_ctx", W))
+try:
+    exc = _raises(lambda: hvd_amd.allpairs_hamming(db, 31))
+    assert isinstance(exc, L.HvdError), repr(exc)
+finally:
+    L.check(lib.hvd_debug_set(b"allpairs_index_fail_ctx", 0))
+    L.check(lib.hvd_debug_set(b"allpairs_index", -1))
+assert np.array_equal(hvd_amd.allpairs_hamming(db, 31), want)
 
 L.shutdown()
 print("GROUP_OK", devs, "exchange", "host" if len(set(devs)) < W else "rccl")
