@@ -277,7 +277,9 @@ int hvd_debug_set(const char* key, int value);
 int hvd_debug_get(const char* key, int* out_value);
 
 /* Bytes of device scratch hvd_dev_pdq_hash_frames needs for this geometry (0 for
- * 64x64 gray): the 64x64 float luma of every frame plus the blur workspace. */
+ * 64x64 gray): the 64x64 float luma of every frame plus the blur workspace.
+ * Layout contract: after hvd_dev_pdq_hash_frames[_dihedral] the first 4096*n floats of the scratch hold the n
+ * frame-major, row-major 64x64 planes that were hashed (tests/test_gpu_pdq_planes.py compares them with the oracle's). */
 int hvd_pdq_scratch_bytes(int64_t n, int h, int w, int channels, size_t* out_bytes);
 /* channels: 1 (gray u8) or 3 (RGB24). d_scratch: hvd_pdq_scratch_bytes() bytes
  * (NULL when that is 0). h,w in [64,4096]. */

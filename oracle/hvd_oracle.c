@@ -261,18 +261,27 @@ static void bits_from_dct(const float* B, uint8_t hash[32]) {
 
 /* ------------------------------------------------- one frame, from luma -- */
 
+/* The 64x64 plane that pdqHash256FromFloatLuma hashes: the luma itself for a 64x64 frame, else the luma blurred and
+ * decimated. luma is clobbered; scratch has h*w floats. The one place the plane is computed: the hash path
+ * (hvd_cpu_pdq_from_luma) and the plane export (hvd_cpu_pdq_planes64) both go through it. */
+static int plane64_from_luma(float* luma, float* scratch, int h, int w, float* a64 /*64*64*/) {
+    if (h < 64 || w < 64) return HVD_ERR_ARG;
+    if (h == 64 && w == 64) {
+        memcpy(a64, luma, 64 * 64 * sizeof(float)); /* upstream: already-downsampled video frames skip the blur */
+    } else {
+        jarosz(luma, scratch, h, w, jarosz_window(w), jarosz_window(h), 2);
+        decimate64(luma, h, w, a64);
+    }
+    return HVD_OK;
+}
+
 /* pdqhashing.cpp pdqHash256FromFloatLuma. luma is clobbered; scratch has h*w floats.
  * coeffs (nullable) receives the 16x16 DCT output for cross-implementation checks. */
 int hvd_cpu_pdq_from_luma(float* luma, float* scratch, int h, int w, uint8_t hash[32], int32_t* quality,
                           float* coeffs) {
     float a64[64 * 64], T[16 * 64], B[16 * 16];
-    if (h < 64 || w < 64) return HVD_ERR_ARG;
-    if (h == 64 && w == 64) {
-        memcpy(a64, luma, sizeof a64); /* upstream: already-downsampled video frames skip the blur */
-    } else {
-        jarosz(luma, scratch, h, w, jarosz_window(w), jarosz_window(h), 2);
-        decimate64(luma, h, w, a64);
-    }
+    int rc = plane64_from_luma(luma, scratch, h, w, a64);
+    if (rc != HVD_OK) return rc;
     *quality = quality64(a64);
     dct64to16(a64, T, B);
     bits_from_dct(B, hash);
@@ -289,6 +298,7 @@ typedef struct {
     uint8_t* hashes;
     int32_t* quality;
     float* coeffs;
+    float* planes; /* non-NULL: export the 64x64 planes instead of hashing them */
     int rc;
 } frame_job;
 
@@ -304,8 +314,9 @@ static void* frame_worker(void* arg) {
             hvd_cpu_luma_rgb24(src, (int64_t)npix, luma);
         else
             hvd_cpu_luma_gray(src, (int64_t)npix, luma);
-        int rc = hvd_cpu_pdq_from_luma(luma, scratch, jb->h, jb->w, jb->hashes + 32 * f, jb->quality + f,
-                                       jb->coeffs ? jb->coeffs + 256 * f : NULL);
+        int rc = jb->planes ? plane64_from_luma(luma, scratch, jb->h, jb->w, jb->planes + 4096 * f)
+                            : hvd_cpu_pdq_from_luma(luma, scratch, jb->h, jb->w, jb->hashes + 32 * f, jb->quality + f,
+                                                    jb->coeffs ? jb->coeffs + 256 * f : NULL);
         if (rc != HVD_OK) jb->rc = rc;
     }
     free(luma);
@@ -313,9 +324,10 @@ static void* frame_worker(void* arg) {
     return NULL;
 }
 
+/* planes == NULL: hashes, quality (and coeffs) of every frame; planes != NULL: only the planes (n*4096 floats). */
 static int hash_frames(const uint8_t* frames, int64_t n, int h, int w, int channels, uint8_t* hashes,
-                       int32_t* quality, float* coeffs, int num_threads) {
-    if (n < 0 || h < 64 || w < 64 || (n > 0 && (!frames || !hashes || !quality))) return HVD_ERR_ARG;
+                       int32_t* quality, float* coeffs, float* planes, int num_threads) {
+    if (n < 0 || h < 64 || w < 64 || (n > 0 && (!frames || (!planes && (!hashes || !quality))))) return HVD_ERR_ARG;
     if (num_threads < 1) num_threads = 1;
     if (num_threads > 256) num_threads = 256;
     if ((int64_t)num_threads > n) num_threads = n > 0 ? (int)n : 1;
@@ -325,7 +337,7 @@ static int hash_frames(const uint8_t* frames, int64_t n, int h, int w, int chann
     int rc = HVD_OK;
     for (int t = 0; t < num_threads; ++t) {
         jobs[t] = (frame_job){frames, n * t / num_threads, n * (t + 1) / num_threads, h, w, channels,
-                              hashes, quality, coeffs, HVD_OK};
+                              hashes, quality, coeffs, planes, HVD_OK};
         if (num_threads == 1)
             frame_worker(&jobs[t]);
         else
@@ -341,12 +353,20 @@ static int hash_frames(const uint8_t* frames, int64_t n, int h, int w, int chann
 /* Counterpart of VideoHasher.hash_frame for a batch (vpdqpy/vpdqpy.py:118). */
 int hvd_cpu_pdq_hash_frames_gray_u8(const uint8_t* frames, int64_t n, int h, int w, uint8_t* out_hashes,
                                     int32_t* out_quality, float* out_coeffs, int num_threads) {
-    return hash_frames(frames, n, h, w, 1, out_hashes, out_quality, out_coeffs, num_threads);
+    return hash_frames(frames, n, h, w, 1, out_hashes, out_quality, out_coeffs, NULL, num_threads);
 }
 
 int hvd_cpu_pdq_hash_frames_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, uint8_t* out_hashes,
                                      int32_t* out_quality, float* out_coeffs, int num_threads) {
-    return hash_frames(frames, n, h, w, 3, out_hashes, out_quality, out_coeffs, num_threads);
+    return hash_frames(frames, n, h, w, 3, out_hashes, out_quality, out_coeffs, NULL, num_threads);
+}
+
+/* The 64x64 float plane of every frame that the two entries above go on to hash (quality, DCT, median): the luma for
+ * 64x64 frames, luma + Jarosz blur + decimation otherwise. channels: 1 (gray u8) or 3 (rgb24). out: n*4096 floats,
+ * frame-major, row-major inside a frame. The same workers and the same plane function as the hash entries. */
+int hvd_cpu_pdq_planes64(const uint8_t* frames, int64_t n, int h, int w, int channels, float* out, int num_threads) {
+    if ((channels != 1 && channels != 3) || (n > 0 && !out)) return HVD_ERR_ARG;
+    return hash_frames(frames, n, h, w, channels, NULL, NULL, NULL, out, num_threads);
 }
 
 /* ------------------------------------------------------------- Hamming -- */

@@ -45,6 +45,8 @@ def lib() -> C.CDLL:
             fn = getattr(L, name)
             fn.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
             fn.restype = C.c_int
+        L.hvd_cpu_pdq_planes64.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.hvd_cpu_pdq_planes64.restype = C.c_int
         L.hvd_cpu_set_dct_mode.argtypes = [C.c_int]
         L.hvd_cpu_set_dct_mode.restype = None
         L.hvd_cpu_hamming256.argtypes = [C.c_void_p, C.c_void_p]
@@ -97,6 +99,21 @@ def hash_frames(frames: np.ndarray, num_threads: int = 1, want_coeffs: bool = Fa
     if rc != 0:
         raise RuntimeError(f"oracle hash_frames rc={rc}")
     return (hashes, quality, coeffs) if want_coeffs else (hashes, quality)
+
+
+def planes64(frames: np.ndarray, num_threads: int = 1) -> np.ndarray:
+    """frames: uint8[n,h,w] (gray) or uint8[n,h,w,3] (rgb24) -> float32[n,64,64]: the plane hash_frames hashes (the luma
+    of a 64x64 frame; luma, Jarosz blur and decimation otherwise), from the same C function as the hash path."""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8)
+    if not (frames.ndim == 3 or (frames.ndim == 4 and frames.shape[3] == 3)):
+        raise ValueError("frames must be uint8[n,h,w] or uint8[n,h,w,3]")
+    n, h, w = frames.shape[:3]
+    out = np.zeros((n, 64, 64), dtype=np.float32)
+    rc = lib().hvd_cpu_pdq_planes64(frames.ctypes.data, n, h, w, 1 if frames.ndim == 3 else 3, out.ctypes.data,
+                                    num_threads)
+    if rc != 0:
+        raise RuntimeError(f"oracle planes64 rc={rc}")
+    return out
 
 
 def hamming256(a, b) -> int:

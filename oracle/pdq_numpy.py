@@ -53,12 +53,12 @@ def luma_gray(gray: np.ndarray) -> np.ndarray:
 
 
 def _box_axis0(a: np.ndarray, w: int) -> np.ndarray:
-    """Sequential running-sum box filter along axis 0 (box1DFloat), vectorised over axis 1."""
+    """Sequential running-sum box filter along axis 0 (box1DFloat), vectorised over the other axes."""
     n = a.shape[0]
     out = np.empty_like(a)
     half = (w + 2) // 2
     p1, p2, p3, p4 = half - 1, w - half + 1, n - w, half - 1
-    s = np.zeros(a.shape[1], dtype=np.float32)
+    s = np.zeros(a.shape[1:], dtype=np.float32)
     li = ri = oi = 0
     cur = 0
     for _ in range(p1):
@@ -88,6 +88,18 @@ def _box_axis0(a: np.ndarray, w: int) -> np.ndarray:
 
 
 def jarosz_decimate(luma: np.ndarray) -> np.ndarray:
+    """float32[h,w] -> float32[64,64]; a batch float32[n,h,w] -> float32[n,64,64] (the frames ride along as a third
+    axis of the same elementwise recurrence, so each frame's plane is bit for bit what it is alone)."""
+    if luma.ndim == 3:
+        n, h, w = luma.shape
+        win_rows, win_cols = (w + 127) // 128, (h + 127) // 128
+        a = np.ascontiguousarray(luma.astype(np.float32).transpose(1, 2, 0))  # [h, w, n]
+        for _ in range(2):
+            a = _box_axis0(np.ascontiguousarray(a.transpose(1, 0, 2)), win_rows).transpose(1, 0, 2)  # along rows
+            a = _box_axis0(np.ascontiguousarray(a), win_cols)  # along columns
+        ii = [int(((i + 0.5) * h) / 64) for i in range(64)]
+        jj = [int(((j + 0.5) * w) / 64) for j in range(64)]
+        return np.ascontiguousarray(a[np.ix_(ii, jj)].transpose(2, 0, 1)).astype(np.float32)
     h, w = luma.shape
     win_rows = (w + 127) // 128  # window along a row, from the column count
     win_cols = (h + 127) // 128

@@ -490,3 +490,194 @@ def test_jarosz_float32_matches_its_float64_definition(k):
         luma = P.luma_gray(np.full((side, side), v, np.uint8))
         got = P.jarosz_decimate(luma)
         assert np.array_equal(got.astype(np.float64), jarosz_decimate_f64(luma)) and (got == v).all(), v
+
+
+# ---- the exported 64x64 plane: what the GPU front-ends are compared with, bit for bit (tests/test_gpu_pdq_planes.py) ----
+
+PLANE_WINDOWS = (1, 2, 3, 4, 8, 17, 32)
+
+
+def _luma(frames):
+    return P.luma_rgb(frames) if frames.ndim == 4 else P.luma_gray(frames)
+
+
+def _plane_cases():
+    """(h, w, channels, seed): both edges of each window of PLANE_WINDOWS on the long axis, in both orientations, gray and
+    rgb (the orientation and the channel count alternate with the edge, so every combination of the four occurs)."""
+    cases = []
+    for k in PLANE_WINDOWS:
+        for e, side in enumerate(_window_sides(k)):
+            for o, (h, w) in enumerate(((64, side), (side, 64))):
+                cases.append((h, w, 1, 10 * k + 2 * e + o))
+                cases.append((h, w, 3, 500 + 10 * k + 2 * e + o))
+    return cases
+
+
+@pytest.mark.parametrize("k", PLANE_WINDOWS)
+def test_exported_plane_equals_the_numpy_restatement(oracle, k):
+    """oracle.planes64 (hvd_cpu_pdq_planes64) against pdq_numpy.jarosz_decimate(pdq_numpy.luma_*()), bit for bit, on
+    hard_frames at both edges of window k, both orientations, gray and rgb -- and hash_from_luma of that plane is the hash
+    and quality oracle.hash_frames reports: the export is the plane that is hashed."""
+    for h, w, ch, seed in (c for c in _plane_cases() if jarosz_window(max(c[0], c[1])) == k):
+        fr, labels = hard_frames(h, w, channels=ch, seed=seed)
+        got = oracle.planes64(fr)
+        want = P.jarosz_decimate(_luma(fr))
+        assert got.dtype == np.float32 and got.shape == (len(fr), 64, 64)
+        bad = np.flatnonzero((got.view(np.uint32) != want.view(np.uint32)).any(axis=(1, 2)))
+        assert bad.size == 0, f"{fr.shape}: frames {[labels[i] for i in bad]} differ"
+        ho, qo = oracle.hash_frames(fr)
+        for i in range(0, len(fr), 4):
+            hp, qp, _ = P.hash_from_luma(got[i])
+            assert hp == ho[i].tobytes() and qp == qo[i], (fr.shape, labels[i])
+
+
+def test_exported_plane_batch_restatement_equals_the_single_frame_one():
+    """pdq_numpy.jarosz_decimate on a batch is, frame by frame, what it is on each frame alone."""
+    fr, _ = hard_frames(150, 300, channels=1, seed=3)
+    luma = P.luma_gray(fr)
+    batch = P.jarosz_decimate(luma)
+    for i in range(len(fr)):
+        assert np.array_equal(batch[i].view(np.uint32), P.jarosz_decimate(luma[i]).view(np.uint32)), i
+
+
+def test_exported_plane_of_64x64_rgb_is_the_luma(oracle):
+    """64x64 rgb: no blur, the plane is the left-to-right float luma; 64x64 gray likewise; threads change nothing."""
+    import hvd_amd
+
+    fr = hvd_amd.synth.frames_rgb(40, seed=64, h=64, w=64)
+    fr[0] = np.random.default_rng(64).integers(0, 256, fr[0].shape, dtype=np.uint8)
+    got = oracle.planes64(fr)
+    assert np.array_equal(got.view(np.uint32), P.luma_rgb(fr).view(np.uint32))
+    assert np.array_equal(oracle.planes64(fr, num_threads=3).view(np.uint32), got.view(np.uint32))
+    ho, qo = oracle.hash_frames(fr)
+    for i in range(0, len(fr), 7):
+        hp, qp, _ = P.hash_from_luma(got[i])
+        assert hp == ho[i].tobytes() and qp == qo[i]
+    g = fr[..., 1]
+    assert np.array_equal(oracle.planes64(g).view(np.uint32), P.luma_gray(g).view(np.uint32))
+    assert oracle.planes64(fr[:0]).shape == (0, 64, 64)
+    with pytest.raises(RuntimeError):
+        oracle.planes64(np.zeros((1, 63, 64), np.uint8))
+
+
+def box_means_f64(a, win):
+    """The box filter of the published 4-phase schedule, along axis 0, as what each phase's output IS: the mean of the
+    inputs the running sum holds at that moment, summed directly in float64 (no running sum, no cumulative sum).
+    half = (win + 2) // 2. Phase 1 reads half - 1 inputs and emits nothing. Phase 2 (win - half + 1 outputs): output o
+    is the mean of inputs 0 .. o + half - 1. Phase 3 (n - win outputs): one input enters, one leaves, the mean of win
+    inputs ending at o + half - 1. Phase 4 (half - 1 outputs): inputs only leave, the mean of o - win + half .. n - 1.
+    So output o averages the inputs o - win + half .. o + half - 1 that exist, divided by how many exist."""
+    n = a.shape[0]
+    half = (win + 2) // 2
+    total = np.zeros(a.shape, np.float64)
+    count = np.zeros((n,) + (1,) * (a.ndim - 1), np.float64)
+    for d in range(half - win, half):  # input o + d contributes to output o
+        lo, hi = max(0, -d), min(n, n - d)  # outputs o with 0 <= o + d < n
+        total[lo:hi] += a[lo + d:hi + d]
+        count[lo:hi] += 1
+    return total / count
+
+
+def plane_f64(frames):
+    """Float64 restatement of the front-end for this test: luma with the algorithm's float coefficients held in double,
+    two repetitions of (box along rows with the window of the width, box along columns with the window of the height),
+    window = ceil(side / 128), then the samples at int((i + 0.5) * side / 64)."""
+    f = frames.astype(np.float64)
+    cr, cg, cb = (float(np.float32(c)) for c in (0.299, 0.587, 0.114))
+    luma = cr * f[..., 0] + cg * f[..., 1] + cb * f[..., 2] if frames.ndim == 4 else cr * f + cg * f + cb * f
+    n, h, w = luma.shape
+    if (h, w) == (64, 64):
+        return luma
+    a = luma.transpose(1, 2, 0)  # [h, w, n]
+    for _ in range(2):
+        a = box_means_f64(a.transpose(1, 0, 2), -(-w // 128)).transpose(1, 0, 2)
+        a = box_means_f64(a, -(-h // 128))
+    ii = [int((i + 0.5) * h / 64) for i in range(64)]
+    jj = [int((j + 0.5) * w / 64) for j in range(64)]
+    return a[np.ix_(ii, jj)].transpose(2, 0, 1)
+
+
+def plane_bound(h, w):
+    """Derived worst case of |float32 plane - exact plane|; see test_exported_plane_within_float32_bound_of_float64."""
+    u, peak = 2.0 ** -24, 256.0
+    if (h, w) == (64, 64):
+        return 5 * u * peak
+    return (5 + 2 * (4 * w + 1) + 2 * (4 * h + 1)) * u * peak
+
+
+F64_SIZES = [(64, 65), (65, 64), (64, 64), (91, 150), (128, 129), (200, 257), (300, 385), (480, 853), (512, 512),
+             (720, 1280), (64, 4096), (4096, 64)]
+
+
+@pytest.mark.parametrize("h,w", F64_SIZES, ids=[f"{h}x{w}" for h, w in F64_SIZES])
+def test_exported_plane_within_float32_bound_of_float64(oracle, h, w):
+    """oracle.planes64 against plane_f64 (exact window means, direct sums, float64) on hard_frames, gray and rgb.
+
+    The bound is derived, not fitted. u = 2^-24 is the relative error of one float32 rounding; every value of the
+    pipeline is a luma or a mean of lumas, at most 255 * (0.299f + 0.587f + 0.114f) < 255.0001, and `peak` = 256 leaves
+    room for the rounding errors themselves (each term below is first order in u; the 0.4 % between 255.0001 and 256
+    covers the second-order terms, since the errors stay below 1 % of the values they sit on).
+      luma: three products and two sums, each rounded once, each result <= peak: error <= 5 u peak.
+      one box pass over a line of n values with window win: the running sum is changed by at most n adds and n
+        subtracts before any output. After each one it holds at most win + 1 inputs (phase 3 adds before it subtracts),
+        so each rounding errs by <= u (win + 1) peak, and the roundings are the ONLY error of the sum relative to the
+        exact sum of the inputs it currently holds: what was added is subtracted again as the same float. The sum
+        therefore errs by <= 2 n u (win + 1) peak. It is divided by the count of inputs held, which is at least
+        half = (win + 2) // 2 >= (win + 1) / 2: <= 4 n u peak after the division, plus u peak for rounding the quotient,
+        plus the error the inputs came with (a mean never grows it): a pass adds (4 n + 1) u peak.
+      four passes, two along rows (n = w) and two along columns (n = h), then a selection:
+        bound = (5 + 2 (4 w + 1) + 2 (4 h + 1)) u peak    (64x64: 5 u peak, the luma alone).
+    The float64 side's own error (~(win + 4) 2^-53 peak per pass) is 10^-9 of that. The bound is a worst case that grows
+    with the line length -- 0.016 at 64x65, 0.13 at 512x512, 0.51 at 64x4096 --, so the sizes run from the smallest up,
+    where it is tight, and the check's teeth are measured by test_float64_bound_has_teeth: the same restatement with the
+    window one too wide, the edge phases divided by the full window, or the output one sample late lands at least ten
+    times above it on the same kind of frames."""
+    bound = plane_bound(h, w)
+    for ch in (1, 3):
+        fr, labels = hard_frames(h, w, channels=ch, seed=h + 3 * w + ch)
+        got = oracle.planes64(fr, num_threads=4).astype(np.float64)
+        want = plane_f64(fr)
+        err = np.abs(got - want).max(axis=(1, 2))
+        i = int(err.argmax())
+        assert err[i] <= bound, f"{fr.shape} frame {labels[i]}: error {err[i]:.3g} above the derived bound {bound:.3g}"
+        assert err.max() > 0 or (h, w) == (64, 64)  # (float32 and float64 do differ: the comparison is not vacuous)
+
+
+def _mutant_plane(fr, window_plus=0, edge_full=False, late=0):
+    """plane_f64 with one misreading of the algorithm built in (gray frames)."""
+    luma = fr.astype(np.float64) * sum(float(np.float32(c)) for c in (0.299, 0.587, 0.114))
+    n, h, w = luma.shape
+
+    def box(a, win):
+        win += window_plus
+        m = len(a)
+        half = (win + 2) // 2
+        total = np.zeros(a.shape)
+        count = np.zeros((m, 1, 1))
+        for d in range(half - win, half):
+            lo, hi = max(0, -d), min(m, m - d)
+            total[lo:hi] += a[lo + d:hi + d]
+            count[lo:hi] += 1
+        out = total / (win if edge_full else count)
+        return np.concatenate([out[:late], out[:m - late]]) if late else out
+
+    a = luma.transpose(1, 2, 0)
+    for _ in range(2):
+        a = box(a.transpose(1, 0, 2), -(-w // 128)).transpose(1, 0, 2)
+        a = box(a, -(-h // 128))
+    ii = [int((i + 0.5) * h / 64) for i in range(64)]
+    jj = [int((j + 0.5) * w / 64) for j in range(64)]
+    return a[np.ix_(ii, jj)].transpose(2, 0, 1)
+
+
+@pytest.mark.parametrize("h,w", [(91, 150), (300, 385), (512, 512)])
+def test_float64_bound_has_teeth(oracle, h, w):
+    """Each misreading of the algorithm that the float64 check exists to catch is at least 10x outside the derived bound on
+    the frames the check uses: window one too wide, edge phases divided by the full window, output one sample late."""
+    fr, _ = hard_frames(h, w, channels=1, seed=h + 3 * w + 1)
+    got = oracle.planes64(fr).astype(np.float64)
+    bound = plane_bound(h, w)
+    assert np.abs(got - _mutant_plane(fr)).max() <= bound  # the unmutated helper is plane_f64
+    for kw in ({"window_plus": 1}, {"edge_full": True}, {"late": 1}):
+        err = np.abs(got - _mutant_plane(fr, **kw)).max()
+        assert err > 10 * bound, (kw, err, bound)
