@@ -82,6 +82,11 @@ SIGNATURES = {
     "hvd_pdq_scratch_bytes": (_int, [_i64, _int, _int, _int, C.POINTER(_sz)]),
     "hvd_dev_pdq_hash_frames": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp, _vp]),
     "hvd_dev_pdq_hash_frames_dihedral": (_int, [_vp, _i64, _int, _int, _int, _vp, _vp, _vp]),
+    "hvd_pdq_hash_frames_autocrop_gray_u8": (_int, [_vp, _i64, _int, _int, _vp, _i64, _int, _int, _vp, _vp, _vp]),
+    "hvd_pdq_hash_frames_autocrop_rgb24_u8": (_int, [_vp, _i64, _int, _int, _vp, _i64, _int, _int, _vp, _vp, _vp]),
+    "hvd_dev_content_rects": (_int, [_vp, _i64, _int, _int, _int, _vp, _i64, _int, _int, _vp]),
+    "hvd_pdq_rects_scratch_bytes": (_int, [_i64, _int, _int, _int, C.POINTER(_sz)]),
+    "hvd_dev_pdq_hash_frames_rects": (_int, [_vp, _i64, _int, _int, _int, _vp, _i64, _vp, _vp, _vp, _vp]),
     "hvd_dev_allpairs_hamming256": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _i64, _vp, _int]),
     "hvd_fp4_image_bytes": (_int, [_i64, C.POINTER(_sz)]),
     "hvd_dev_expand_fp4": (_int, [_vp, _i64, _vp]),

@@ -867,6 +867,67 @@ int hvd_dev_pdq_hash_frames_dihedral(const void* d_frames, int64_t n, int h, int
     return dev_hash_frames(d_frames, n, h, w, channels, d_scratch, d_hashes8, d_quality, true);
 }
 
+/* ---- content-rectangle PDQ (k_autocrop.hip) ---- */
+
+static int rects_geometry(int64_t n, int h, int w, int channels, int64_t V) {
+    if (n < 0 || h < 64 || w < 64 || h > 4096 || w > 4096 || (channels != 1 && channels != 3))
+        return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d channels=%d (need h,w in [64,4096])", (long long)n, h, w,
+                    channels);
+    if (V < 0 || V >= (1ll << 31) || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad counts n=%lld V=%lld", (long long)n, (long long)V);
+    if (n > 0 && V == 0) return fail(HVD_ERR_ARG, "n=%lld frames in no video", (long long)n);
+    return HVD_OK;
+}
+
+int hvd_dev_content_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
+                          int black_level, int min_bright, void* d_rects) {
+    if (int rc = need_ready()) return rc;
+    if (int rc = rects_geometry(n, h, w, channels, V)) return rc;
+    if (black_level < 0 || black_level > 254) return fail(HVD_ERR_ARG, "black_level=%d: need 0..254", black_level);
+    if (min_bright < 1) return fail(HVD_ERR_ARG, "min_bright=%d: need >= 1", min_bright);
+    if (V == 0) return HVD_OK;
+    if (!d_offsets || !d_rects || (n > 0 && !d_frames)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if ((uintptr_t)d_rects & 15u) return fail(HVD_ERR_ARG, "d_rects must be 16-byte aligned (hvd_dev_malloc's are)");
+    HIP_TRY(hvd::launch_content_rects((const uint8_t*)d_frames, n, h, w, channels, (const long long*)d_offsets, (uint32_t)V,
+                                      black_level, min_bright, (int32_t*)d_rects, g.stream));
+    return HVD_OK;
+}
+
+int hvd_pdq_rects_scratch_bytes(int64_t n, int h, int w, int channels, size_t* out_bytes) {
+    if (!out_bytes || n < 0 || h < 64 || w < 64 || h > 4096 || w > 4096 || (channels != 1 && channels != 3))
+        return fail(HVD_ERR_ARG, "bad frame geometry");
+    if (int rc = hvd_pdq_scratch_bytes(n, h, w, channels, out_bytes)) return rc;
+    // frame -> rectangle table (int4 per frame) behind the workspace, at the next multiple of 16 bytes
+    if (!(h == 64 && w == 64)) *out_bytes = (*out_bytes + 15) / 16 * 16 + hvd::pdq_rects_geom_bytes(n);
+    return HVD_OK;
+}
+
+int hvd_dev_pdq_hash_frames_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets,
+                                  int64_t V, const void* d_rects, void* d_scratch, void* d_hashes, void* d_quality) {
+    if (int rc = need_ready()) return rc;
+    if (int rc = rects_geometry(n, h, w, channels, V)) return rc;
+    if (n == 0) return HVD_OK;
+    if (!d_frames || !d_offsets || !d_rects || !d_hashes || !d_quality) return fail(HVD_ERR_ARG, "NULL device pointer");
+    const bool need_scratch = !(h == 64 && w == 64 && channels == 1);
+    if (need_scratch && !d_scratch)
+        return fail(HVD_ERR_ARG, "d_scratch (hvd_pdq_rects_scratch_bytes) is required unless 64x64 gray");
+    if (((uintptr_t)d_rects | (uintptr_t)d_scratch) & 15u)
+        return fail(HVD_ERR_ARG, "d_rects and d_scratch must be 16-byte aligned (hvd_dev_malloc's are)");
+    // 64x64 frames: every rectangle is the full frame by the rule (an axis shorter than 64 keeps its full extent)
+    if (h == 64 && w == 64) {
+        HIP_TRY(hvd::launch_hash_any(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, g.stream, false));
+        return HVD_OK;
+    }
+    float* out64 = (float*)d_scratch;
+    const size_t cnt = (size_t)(n < 1024 ? n : 1024);
+    float* ws = out64 + (size_t)n * 4096;
+    const size_t geom_at = (sizeof(float) * (4096 * (size_t)n + cnt * hvd::pdq_downsample_ws_floats(h, w)) + 15) / 16 * 16;
+    void* geom = (char*)d_scratch + geom_at;  // (hvd_pdq_rects_scratch_bytes rounds the same way)
+    HIP_TRY(hvd::launch_pdq_downsample_rects((const uint8_t*)d_frames, n, h, w, channels, (const long long*)d_offsets,
+                                             (uint32_t)V, (const int32_t*)d_rects, geom, ws, out64, g.stream));
+    HIP_TRY(hvd::launch_pdq_hash64(d_scratch, 1, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, g.stream));
+    return HVD_OK;
+}
+
 int hvd_allpairs_tile_geometry(int64_t n, int variant, uint32_t* rows_per_block, uint32_t* col_chunk) {
     if (n < 0 || n >= (1ll << 32) || !rows_per_block || !col_chunk) return fail(HVD_ERR_ARG, "bad arguments");
     if (!hvd::allpairs_geometry((uint32_t)n, variant, rows_per_block, col_chunk) &&

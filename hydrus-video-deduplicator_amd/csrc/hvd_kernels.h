@@ -169,4 +169,15 @@ hipError_t launch_pdq_downsample(const uint8_t* d_frames, int64_t n, int h, int 
 // 64x64 rgb24 frames: luma only (no blur, as upstream's 64x64 shortcut).
 hipError_t launch_pdq_luma64_rgb(const uint8_t* d_frames, int64_t n, float* d_out64, hipStream_t s);
 
+// Content-rectangle PDQ (k_autocrop.hip). d_offsets: the int64[V+1] CSR of the n frames; d_rects: int32[V][4]
+// {top, left, height, width}, also the kernels' accumulator (nothing else is allocated).
+hipError_t launch_content_rects(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
+                                uint32_t V, int black_level, int min_bright, int32_t* d_rects, hipStream_t s);
+// The generic four-pass down-sampler inside every frame's video rectangle. d_geom: pdq_rects_geom_bytes(n) bytes (the
+// frame -> rectangle table); d_ws as for launch_pdq_downsample (sized for the full h x w).
+size_t pdq_rects_geom_bytes(int64_t n);
+hipError_t launch_pdq_downsample_rects(const uint8_t* d_frames, int64_t n, int h, int w, int channels,
+                                       const long long* d_offsets, uint32_t V, const int32_t* d_rects, void* d_geom,
+                                       float* d_ws, float* d_out64, hipStream_t s);
+
 }  // namespace hvd

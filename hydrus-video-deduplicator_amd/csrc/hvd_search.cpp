@@ -126,6 +126,97 @@ int hvd_pdq_hash_frames_dihedral_rgb24_u8(const uint8_t* frames, int64_t n, int 
     return hash_frames_group(frames, n, h, w, 3, out_hashes8, out_quality, 8);
 }
 
+// Content-rectangle hashing of host frames. Runs on the calling thread's current context, also under a device
+// group. Batches end on video boundaries, so a video's rectangle always sees all of its frames.
+static int hash_frames_autocrop_host(const uint8_t* frames, int64_t n, int h, int w, int channels, const int64_t* offsets,
+                                     int64_t V, int black_level, int min_bright, uint8_t* out_hashes, int32_t* out_quality,
+                                     int32_t* out_rects) {
+    if (int rc = need_ready()) return rc;
+    if (n < 0 || h < 64 || w < 64 || h > 4096 || w > 4096 || (channels != 1 && channels != 3))
+        return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d channels=%d (need h,w in [64,4096])", (long long)n,
+                    h, w, channels);
+    if (V < 0 || V >= (1ll << 31) || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad counts n=%lld V=%lld", (long long)n, (long long)V);
+    if (black_level < 0 || black_level > 254) return fail(HVD_ERR_ARG, "black_level=%d: need 0..254", black_level);
+    if (min_bright < 1) return fail(HVD_ERR_ARG, "min_bright=%d: need >= 1", min_bright);
+    if (V == 0 && n == 0) return HVD_OK;
+    if (!offsets) return fail(HVD_ERR_ARG, "NULL offsets");
+    if (offsets[0] != 0 || offsets[V] != n) return fail(HVD_ERR_ARG, "offsets must run from 0 to n=%lld", (long long)n);
+    for (int64_t v = 0; v < V; ++v)
+        if (offsets[v + 1] < offsets[v]) return fail(HVD_ERR_ARG, "offsets decrease at video %lld", (long long)v);
+    if (!out_rects || (n > 0 && (!frames || !out_hashes || !out_quality))) return fail(HVD_ERR_ARG, "NULL buffer");
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    const size_t frame_bytes = (size_t)h * w * channels;
+    // Batches bound the staging footprint (<= ~1 GiB of frames per batch, as hash_frames_host).
+    int64_t limit = (int64_t)((1ull << 30) / frame_bytes);
+    if (limit < 1) limit = 1;
+    int64_t batch = 0, batch_v = 0;  // the largest batch of whole videos: sizes the pool once
+    for (int64_t v0 = 0; v0 < V;) {
+        int64_t v1 = v0 + 1;
+        if (offsets[v1] - offsets[v0] > limit)
+            return fail(HVD_ERR_ARG, "video %lld has %lld frames, more than the %lld that fit the staging limit of 1 GiB at this "
+                        "geometry: a video's rectangle needs all of its frames in one batch", (long long)v0,
+                        (long long)(offsets[v1] - offsets[v0]), (long long)limit);
+        while (v1 < V && offsets[v1 + 1] - offsets[v0] <= limit) ++v1;
+        batch = std::max<int64_t>(batch, offsets[v1] - offsets[v0]);
+        batch_v = std::max<int64_t>(batch_v, v1 - v0);
+        v0 = v1;
+    }
+    const bool need_scratch = !(h == 64 && w == 64 && channels == 1);
+    void *d_in = nullptr, *d_scr = nullptr, *d_h = nullptr, *d_q = nullptr, *d_off = nullptr, *d_rects = nullptr;
+    if (batch > 0) {
+        SCR(S_FRAMES, frame_bytes * batch, d_in);
+        if (need_scratch) {
+            size_t sb = 0;
+            if (int rc = hvd_pdq_rects_scratch_bytes(batch, h, w, channels, &sb)) return rc;
+            SCR(S_FSCR, sb, d_scr);
+        }
+        SCR(S_HASH, 32 * (size_t)batch, d_h);
+        SCR(S_QUAL, 4 * (size_t)batch, d_q);
+    }
+    SCR(S_OFF, 8 * (size_t)(batch_v + 1), d_off);
+    SCR(S_RECTS, 16 * (size_t)batch_v, d_rects);
+    std::vector<int64_t> local;
+    for (int64_t v0 = 0; v0 < V;) {
+        int64_t v1 = v0 + 1;
+        while (v1 < V && offsets[v1 + 1] - offsets[v0] <= limit) ++v1;
+        const int64_t f0 = offsets[v0], m = offsets[v1] - f0, mv = v1 - v0;
+        local.assign(offsets + v0, offsets + v1 + 1);
+        for (auto& o : local) o -= f0;
+        int32_t* rects = out_rects + 4 * v0;
+        HIP_TRY(hipMemcpyAsync(d_off, local.data(), 8 * (size_t)(mv + 1), hipMemcpyHostToDevice, g.stream));
+        if (m > 0) HIP_TRY(hipMemcpyAsync(d_in, frames + frame_bytes * f0, frame_bytes * m, hipMemcpyHostToDevice, g.stream));
+        if (int rc = hvd_dev_content_rects(d_in, m, h, w, channels, d_off, mv, black_level, min_bright, d_rects)) return rc;
+        HIP_TRY(hipMemcpyAsync(rects, d_rects, 16 * (size_t)mv, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+        if (m > 0) {
+            // every rectangle full: today's path (fused 512x512 kernels included); both are the oracle's bits
+            bool full = true;
+            for (int64_t v = 0; v < mv && full; ++v)
+                full = rects[4 * v] == 0 && rects[4 * v + 1] == 0 && rects[4 * v + 2] == h && rects[4 * v + 3] == w;
+            if (int rc = full ? hvd_dev_pdq_hash_frames(d_in, m, h, w, channels, need_scratch ? d_scr : nullptr, d_h, d_q)
+                              : hvd_dev_pdq_hash_frames_rects(d_in, m, h, w, channels, d_off, mv, d_rects, d_scr, d_h, d_q))
+                return rc;
+            HIP_TRY(hipMemcpyAsync(out_hashes + 32 * f0, d_h, 32 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
+            HIP_TRY(hipMemcpyAsync(out_quality + f0, d_q, 4 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
+            HIP_TRY(hipStreamSynchronize(g.stream));
+        }
+        v0 = v1;
+    }
+    return HVD_OK;
+}
+
+int hvd_pdq_hash_frames_autocrop_gray_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
+                                         int black_level, int min_bright, uint8_t* out_hashes, int32_t* out_quality,
+                                         int32_t* out_rects) {
+    return hash_frames_autocrop_host(frames, n, h, w, 1, offsets, V, black_level, min_bright, out_hashes, out_quality, out_rects);
+}
+
+int hvd_pdq_hash_frames_autocrop_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
+                                          int black_level, int min_bright, uint8_t* out_hashes, int32_t* out_quality,
+                                          int32_t* out_rects) {
+    return hash_frames_autocrop_host(frames, n, h, w, 3, offsets, V, black_level, min_bright, out_hashes, out_quality, out_rects);
+}
+
 // Runs the default all-pairs kernel (FP4-MFMA form) on a host DB -- this context's share of the tiles (rank of world) --
 // and fetches up to `cap` unordered records: its own when world == 1, every rank's after the group's exchange otherwise
 // (agreement step on the true counts, then the records: RCCL between the devices, or host memory where the group has no RCCL).

@@ -26,10 +26,13 @@ from . import _lib, search, vpdq
 from ._lib import VMATCH_DTYPE, DeviceBuffer
 
 
-def hash_videos(videos) -> list[vpdq.VpdqHash]:
+def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
     """videos: sequence of uint8[n_i,h,w] / uint8[n_i,h,w,3] arrays with one common frame
     geometry. All frames go through the PDQ kernels in one batch; per video the frames with
-    quality >= 31 are kept in order (VideoHasher.finish semantics, vpdqpy/vpdqpy.py:119)."""
+    quality >= 31 are kept in order (VideoHasher.finish semantics, vpdqpy/vpdqpy.py:119).
+    autocrop: True or a dict of black_level / min_bright: every video is hashed inside its content rectangle
+    (vpdq.hash_frames_autocrop)."""
+    crop = vpdq.autocrop_params(autocrop)
     videos = [np.ascontiguousarray(v, dtype=np.uint8) for v in videos]
     if not videos:
         return []
@@ -41,7 +44,10 @@ def hash_videos(videos) -> list[vpdq.VpdqHash]:
     if lengths.sum() == 0:
         return [vpdq.VpdqHash(b"") for _ in videos]
     flat = np.concatenate([v for v in videos if v.shape[0]], axis=0)
-    hashes, quality = vpdq.hash_frames(flat)
+    if crop is not None:
+        hashes, quality, _ = vpdq.hash_frames_autocrop(flat, np.concatenate([[0], np.cumsum(lengths)]), crop[0], crop[1])
+    else:
+        hashes, quality = vpdq.hash_frames(flat)
     out, pos = [], 0
     for n in lengths:
         h, q = hashes[pos : pos + n], quality[pos : pos + n]
@@ -93,6 +99,43 @@ def hash_frames_dihedral_on_device(d_frames_ptr: int, n: int, h: int, w: int, ch
         _lib.check(lib.hvd_dev_sync())  # the scratch must outlive the kernels
         d_s.free()
     return d_h, d_q
+
+
+def hash_frames_autocrop_on_device(d_frames_ptr: int, n: int, h: int, w: int, channels: int, offsets: np.ndarray,
+                                   black_level: int = 16, min_bright: int = 1, timed=None):
+    """Content-rectangle form of `hash_frames_on_device`: the n frames in HBM are the videos of the CSR
+    `offsets` (int64[V+1], from 0 to n); hvd_dev_content_rects finds every video's rectangle, hvd_dev_pdq_hash_frames_rects
+    hashes every frame inside it. -> (d_hashes, d_quality, d_rects) DeviceBuffers (n*32 B, int32[n], int32[V,4]).
+    timed(key, fn): optional stage timer, called with "rects_ms" and "hash_ms"."""
+    lib = _lib.ensure()
+    offsets = _check_raw_offsets(offsets, n)
+    V = offsets.size - 1
+    run = timed if timed is not None else (lambda key, fn: fn())
+    bufs = {}
+    try:
+        bufs["off"] = d_off = DeviceBuffer.from_array(offsets)
+        bufs["r"] = d_r = DeviceBuffer(16 * max(V, 1))
+        run("rects_ms", lambda: _lib.check(lib.hvd_dev_content_rects(d_frames_ptr, n, h, w, channels, d_off.ptr, V,
+                                                                     int(black_level), int(min_bright), d_r.ptr)))
+        bufs["h"] = d_h = DeviceBuffer(32 * max(n, 1))
+        bufs["q"] = d_q = DeviceBuffer(4 * max(n, 1))
+        sb = C.c_size_t(0)
+        _lib.check(lib.hvd_pdq_rects_scratch_bytes(n, h, w, channels, C.byref(sb)))
+        bufs["s"] = d_s = DeviceBuffer(sb.value) if sb.value else None
+        run("hash_ms", lambda: _lib.check(lib.hvd_dev_pdq_hash_frames_rects(d_frames_ptr, n, h, w, channels, d_off.ptr, V,
+                                                                            d_r.ptr, d_s.ptr if d_s else None, d_h.ptr,
+                                                                            d_q.ptr)))
+        _lib.check(lib.hvd_dev_sync())  # the scratch and the offsets must outlive the kernels
+    except BaseException:
+        lib.hvd_dev_sync()  # nothing may still run on a buffer that is freed here
+        for b in bufs.values():
+            if b is not None:
+                b.free()
+        raise
+    for key in ("s", "off"):
+        if bufs[key] is not None:
+            bufs[key].free()
+    return d_h, d_q, d_r
 
 
 def transform_mask(names) -> int:
@@ -356,7 +399,7 @@ def gather_hash_shards(d_h: DeviceBuffer, d_q: DeviceBuffer, raw_offsets: np.nda
 
 def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
                             threshold: float = 50.0, policy: str | None = None, rank: int = 0, world: int = 1,
-                            exchange=None, keep_library: bool = False, timings: dict | None = None):
+                            exchange=None, keep_library: bool = False, timings: dict | None = None, autocrop=None):
     """BASELINE config 5 for one rank: the frames of videos [v_lo, v_hi) of this rank sit at d_frames_ptr
     (world == 1: all of them); raw_offsets is the CSR of the WHOLE library. Hash -> (all-gather of the hash
     shards) -> quality filter + CSR -> FP4 image -> sharded video search with the counters reduced on the GPU
@@ -367,8 +410,13 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
     all-gather of the hash shards over RCCL incl. the squeeze into library order, 0 at world 1), compact_ms (host clock:
     quality filter + CSR, synchronous) and the search's own phases from the library (host clock, hvd_debug_get
     vmatch_us_*): search_local_ms (packed hashes, probe, all-pairs pass, key set), search_exchange_ms (agreement words,
-    all-gather of the key lists, merged set; 0 at world 1), search_fold_ms (keys -> pair map)."""
+    all-gather of the key lists, merged set; 0 at world 1), search_fold_ms (keys -> pair map).
+    autocrop (True, or a dict of black_level / min_bright): the hash stage becomes hvd_dev_content_rects +
+    hvd_dev_pdq_hash_frames_rects over this rank's own videos (`hash_frames_autocrop_on_device`; a rank owns whole videos,
+    so every rectangle sees all its frames); timings then also receives rects_ms. Everything after the hash stage is
+    unchanged."""
     import time
+    crop = vpdq.autocrop_params(autocrop)
     raw_offsets = np.ascontiguousarray(raw_offsets, dtype=np.int64)
     V = raw_offsets.size - 1
     n_total = int(raw_offsets[-1])
@@ -386,7 +434,12 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
         timings[key] = float(ms.value)
         return out
 
-    d_h, d_q = timed("hash_ms", lambda: hash_frames_on_device(d_frames_ptr, n_mine, h, w, channels))
+    if crop is not None:
+        mine = raw_offsets[v_lo:v_hi + 1] - raw_offsets[v_lo]
+        d_h, d_q, d_r = hash_frames_autocrop_on_device(d_frames_ptr, n_mine, h, w, channels, mine, crop[0], crop[1], timed)
+        d_r.free()
+    else:
+        d_h, d_q = timed("hash_ms", lambda: hash_frames_on_device(d_frames_ptr, n_mine, h, w, channels))
     t0 = time.perf_counter()
     if world > 1:
         if exchange is None:
@@ -416,19 +469,21 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
 
 
 def dedupe_frames_in_process(frames_of_rank, raw_offsets: np.ndarray, h: int, w: int, channels: int,
-                             threshold: float = 50.0, policy: str | None = None, timings: dict | None = None):
+                             threshold: float = 50.0, policy: str | None = None, timings: dict | None = None, autocrop=None):
     """BASELINE config 5 on the library's in-process device group (hvd_init_devices / HVD_DEVICES), no launcher:
     one thread per context runs `dedupe_frames_on_device` as rank = context index. frames_of_rank(rank, world) ->
     device pointer of the frames of that rank's video range (`video_range_of_rank`), resident on that rank's device (it is
     called on the rank's thread, with the rank's context current). -> (pairs, records) -- every rank computes the same;
-    rank 0's are returned. timings: rank 0's stage times."""
+    rank 0's are returned. timings: rank 0's stage times. autocrop: as `dedupe_frames_on_device`."""
     from . import multigpu
+
+    vpdq.autocrop_params(autocrop)  # a bad value fails here, not on every rank's thread
 
     def one(rank, world):
         ex = multigpu.GroupExchange(rank, world) if world > 1 else None
         tm = {} if timings is not None and rank == 0 else None
         pairs, recs, _ = dedupe_frames_on_device(frames_of_rank(rank, world), raw_offsets, h, w, channels, threshold, policy,
-                                                 rank, world, ex, timings=tm)
+                                                 rank, world, ex, timings=tm, autocrop=autocrop)
         if tm is not None:
             timings.update(tm)
         return pairs, recs

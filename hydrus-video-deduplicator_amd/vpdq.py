@@ -407,6 +407,89 @@ def hash_frames(frames: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
     return hashes, quality
 
 
+# Content-rectangle PDQ (include/hvd_mi355x.h): black bars (letterbox / pillarbox) are left out of the hash.
+def autocrop_params(autocrop) -> tuple[int, int] | None:
+    """None when `autocrop` is off (None / False); else (black_level, min_bright) from True (the defaults 16, 1) or a dict
+    with those two keys. Argument errors are raised here, before any device work."""
+    if autocrop is None or autocrop is False:
+        return None
+    if autocrop is True:
+        autocrop = {}
+    if not isinstance(autocrop, dict) or set(autocrop) - {"black_level", "min_bright"}:
+        raise ValueError("autocrop must be True / False or a dict with the keys black_level and min_bright")
+    return _check_autocrop(autocrop.get("black_level", 16), autocrop.get("min_bright", 1))
+
+
+def _check_autocrop(black_level, min_bright) -> tuple[int, int]:
+    for name, v in (("black_level", black_level), ("min_bright", min_bright)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not 0 <= black_level <= 254:
+        raise ValueError(f"black_level must be in 0..254 (a pixel is bright iff max(R, G, B) > black_level), got {black_level}")
+    if not 1 <= min_bright < 2**31:
+        raise ValueError(f"min_bright must be >= 1, got {min_bright}")
+    return int(black_level), int(min_bright)
+
+
+def _autocrop_args(frames, offsets, black_level, min_bright):
+    level, bright = _check_autocrop(black_level, min_bright)
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or not (frames.ndim == 3 or (frames.ndim == 4 and frames.shape[3] == 3)):
+        raise ValueError("frames must be uint8[n,h,w] or uint8[n,h,w,3]")
+    frames = np.ascontiguousarray(frames)
+    n = frames.shape[0]
+    if offsets is None:
+        offsets = np.array([0, n], dtype=np.int64)
+    else:
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if offsets.ndim != 1 or len(offsets) < 1 or offsets[0] != 0 or offsets[-1] != n or np.any(np.diff(offsets) < 0):
+            raise ValueError(f"offsets must be int64[V+1]: offsets[0] = 0, non-decreasing, offsets[V] = n = {n}")
+    return frames, offsets, level, bright
+
+
+def content_rects(frames: np.ndarray, offsets=None, black_level: int = 16, min_bright: int = 1) -> np.ndarray:
+    """The content rectangle of every video, found on the device: int32[V,4] = (top, left, height, width). frames:
+    uint8[n,h,w] or uint8[n,h,w,3]; offsets: int64[V+1] CSR of the videos (None: one video). The rule is in
+    include/hvd_mi355x.h (hvd_dev_content_rects)."""
+    frames, offsets, level, bright = _autocrop_args(frames, offsets, black_level, min_bright)
+    lib = _lib.ensure()
+    n, h, w = frames.shape[:3]
+    V = len(offsets) - 1
+    rects = np.zeros((V, 4), dtype=np.int32)
+    if V == 0:
+        return rects
+    d_fr = _lib.DeviceBuffer.from_array(frames) if n else None
+    d_off = _lib.DeviceBuffer.from_array(offsets)
+    d_rc = _lib.DeviceBuffer(rects.nbytes)
+    try:
+        _lib.check(lib.hvd_dev_content_rects(d_fr.ptr if n else None, n, h, w, 1 if frames.ndim == 3 else 3, d_off.ptr, V,
+                                             level, bright, d_rc.ptr))
+        rects[:] = d_rc.to_array(np.int32, V * 4).reshape(V, 4)
+    finally:
+        for b in (d_fr, d_off, d_rc):
+            if b is not None:
+                b.free()
+    return rects
+
+
+def hash_frames_autocrop(frames: np.ndarray, offsets=None, black_level: int = 16,
+                         min_bright: int = 1) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """`hash_frames` inside every video's content rectangle: (hashes uint8[n,32], quality int32[n], rects int32[V,4]).
+    A frame's hash and quality are the plain PDQ hash and quality of frames[f, top:top+height, left:left+width] under its
+    video's rectangle. offsets: int64[V+1] CSR of the videos (None: one video). No quality filtering."""
+    frames, offsets, level, bright = _autocrop_args(frames, offsets, black_level, min_bright)
+    lib = _lib.ensure()
+    fn = lib.hvd_pdq_hash_frames_autocrop_gray_u8 if frames.ndim == 3 else lib.hvd_pdq_hash_frames_autocrop_rgb24_u8
+    n, h, w = frames.shape[:3]
+    V = len(offsets) - 1
+    hashes = np.zeros((n, BYTES_PER_PDQ_HASH), dtype=np.uint8)
+    quality = np.zeros(n, dtype=np.int32)
+    rects = np.zeros((V, 4), dtype=np.int32)
+    _lib.check(fn(frames.ctypes.data, n, h, w, offsets.ctypes.data, V, level, bright, hashes.ctypes.data, quality.ctypes.data,
+                  rects.ctypes.data))
+    return hashes, quality, rects
+
+
 # Dihedral PDQ (include/hvd_mi355x.h, DESIGN.md 4.6): the hashes of the frame's mirror images and rotations, in the
 # kernel's output order -- TRANSFORMS[k] is what hash_frames_dihedral(frames)[0][:, k] hashes. Names of the physical
 # transform of the 64x64 luma A (rows top to bottom; rotations as numpy's rot90): A, A[:, ::-1], A[::-1, :],

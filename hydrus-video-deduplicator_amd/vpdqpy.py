@@ -66,15 +66,23 @@ class Vpdq:
 
     @staticmethod
     def computeHash(frames, num_threads: int = 0, width: int | None = None, height: int | None = None,
-                    average_rate=None, all_decoded_frames: bool = False) -> VpdqHash:
+                    average_rate=None, all_decoded_frames: bool = False, autocrop=False) -> VpdqHash:
         """Perceptually hash a video given its decoded frames (vpdqpy.py:103-119 minus decode).
 
         frames: uint8[n,h,w,3] / uint8[n,h,w] array, or an iterable of per-frame byte strings
         (then width/height default to DOWNSCALE_DIMENSIONS, as the reference passes). By default `frames` are
         the frames to hash (what ``frame_extract_pyav`` yields); with ``all_decoded_frames=True`` they are EVERY
-        decoded frame and the reference's selection rule is applied first (``select_frames(frames, average_rate)``)."""
+        decoded frame and the reference's selection rule is applied first (``select_frames(frames, average_rate)``).
+
+        autocrop: True, or a dict with ``black_level`` / ``min_bright``, hashes an array of frames inside the video's content
+        rectangle (``vpdq.hash_frames_autocrop``: black bars are left out) and applies the usual quality filter. The rectangle
+        is known only after the last frame, so an iterable of frames cannot be hashed this way: pass the array form."""
         if frames is None:
             raise ValueError
+        crop = vpdq.autocrop_params(autocrop)
+        if crop is not None and not isinstance(frames, np.ndarray):
+            raise ValueError("autocrop needs the array form of the frames (uint8[n,h,w] or uint8[n,h,w,3]): the content "
+                             "rectangle is known only after the last frame, so an iterable cannot be streamed")
         if all_decoded_frames and not isinstance(frames, (bytes, bytearray, memoryview, str, os.PathLike)):
             frames = (frames[selected_frame_indices(frames.shape[0], average_rate)] if isinstance(frames, np.ndarray)
                       else select_frames(frames, average_rate))
@@ -88,6 +96,9 @@ class Vpdq:
             if frames.ndim not in (3, 4):
                 raise ValueError("frames must be uint8[n,h,w] or uint8[n,h,w,3]")
             h, w = frames.shape[1], frames.shape[2]
+            if crop is not None:
+                hashes, quality, _ = vpdq.hash_frames_autocrop(frames, None, crop[0], crop[1])
+                return VpdqHash(hashes[quality >= vpdq.QUALITY_TOLERANCE].tobytes())
             hasher = vpdq.VideoHasher(average_fps, w, h, num_threads)
             flat = np.ascontiguousarray(frames, dtype=np.uint8).reshape(frames.shape[0], -1)
             for f in flat:

@@ -129,6 +129,18 @@ int hvd_pdq_hash_frames_dihedral_gray_u8(const uint8_t* frames, int64_t n, int h
                                          int32_t* out_quality);
 int hvd_pdq_hash_frames_dihedral_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, uint8_t* out_hashes8,
                                           int32_t* out_quality);
+/* Content-rectangle PDQ on host buffers (the rule: hvd_dev_content_rects below): the n frames are the V videos of the CSR
+ * offsets (int64[V+1]: offsets[0] = 0, non-decreasing, offsets[V] = n; checked); every frame is hashed inside its video's
+ * rectangle. out_rects: int32[V][4] = {top, left, height, width}. A call whose rectangles are all the full frame runs the
+ * plain kernels of hvd_pdq_hash_frames_*. Frames are staged in batches of whole videos (<= 1 GiB), so that a video's
+ * rectangle always sees all its frames; a single video larger than that is HVD_ERR_ARG (it is not split). Under a device
+ * group the call runs on the calling thread's current context alone (same bytes as on one context). Both DCT modes. */
+int hvd_pdq_hash_frames_autocrop_gray_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
+                                         int black_level, int min_bright, uint8_t* out_hashes, int32_t* out_quality,
+                                         int32_t* out_rects);
+int hvd_pdq_hash_frames_autocrop_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
+                                          int black_level, int min_bright, uint8_t* out_hashes, int32_t* out_quality,
+                                          int32_t* out_rects);
 
 /* Replaces the O(visited nodes) stream of vpdq.matchHashBytes calls issued by the
  * VP-tree (db/vptree.py:29-31,737; dedup.py:445-502) with one brute-force pass:
@@ -288,6 +300,32 @@ int hvd_dev_pdq_hash_frames(const void* d_frames, int64_t n, int h, int w, int c
 /* Dihedral PDQ: 8 hashes per frame in the order of the table in DESIGN (identity first), n*8*32 bytes. */
 int hvd_dev_pdq_hash_frames_dihedral(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch,
                                      void* d_hashes8, void* d_quality);      /* scratch: hvd_pdq_scratch_bytes */
+
+/* ---- content-rectangle PDQ: re-uploads with black bars (letterbox, pillarbox) hash like the original ----
+ * The rule, integers only: a pixel is bright iff max(R, G, B) > black_level (0..254); a row (column) of a frame is content
+ * iff it holds >= min_bright (>= 1) bright pixels; a frame's rectangle is the bounding box of its content rows x the bounding
+ * box of its content columns (none if either is empty); a VIDEO's rectangle is the bounding box of the rectangles of all its
+ * frames. Per axis: no rectangle in any frame, or a box shorter than 64 -> the full extent. A video without frames gets the
+ * full frame. Record: int32[4] = {top, left, height, width}. The hash of a frame under its video's rectangle is the plain PDQ
+ * hash and quality of the contiguous height x width crop.
+ * d_offsets: int64[V+1] CSR of the n frames in device memory (offsets[0] = 0, non-decreasing, offsets[V] = n; the host-buffer
+ * entries check that, the device-resident ones cannot without a synchronisation: a frame is looked up by binary search and
+ * always lands in [0, V), so a broken CSR gives wrong rectangles, never an access out of bounds).
+ * d_rects: int32[V][4], 16-byte aligned (the kernels access a record as one 16-byte word; HVD_ERR_ARG otherwise); nothing
+ * else is allocated. d_frames needs no alignment. Enqueued on the library stream, no host synchronisation. */
+int hvd_dev_content_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
+                          int black_level, int min_bright, void* d_rects);
+/* Scratch of hvd_dev_pdq_hash_frames_rects: hvd_pdq_scratch_bytes, rounded up to 16, plus 16 bytes per frame (at 64x64:
+ * hvd_pdq_scratch_bytes as it is, 0 for gray). d_scratch and d_rects must be 16-byte aligned (HVD_ERR_ARG otherwise). The layout
+ * contract of hvd_pdq_scratch_bytes holds: afterwards the first 4096*n floats are the planes that were hashed. */
+int hvd_pdq_rects_scratch_bytes(int64_t n, int h, int w, int channels, size_t* out_bytes);
+/* Hashes every frame inside its video's rectangle d_rects[video] (from hvd_dev_content_rects, or the caller's own: any
+ * rectangle inside the frame with both sides >= 64; a record that is not is taken as the full frame). Enqueues without a
+ * host synchronisation, so it does not look at the rectangles: every geometry but 64x64 (where the rule leaves only the full
+ * frame, and the plain kernels run) takes the table-driven generic down-sampler, full rectangles included. A caller that
+ * knows all its rectangles are full calls hvd_dev_pdq_hash_frames instead (same bits, fused 512x512 kernels). Both DCT modes. */
+int hvd_dev_pdq_hash_frames_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets,
+                                  int64_t V, const void* d_rects, void* d_scratch, void* d_hashes, void* d_quality);
 
 /* Brute-force pass over the tiles owned by `rank` of `world` (tile (rb,cb) belongs
  * to rank (rb+cb) % world; world=1 => everything). Appends hvd_pair records to
