@@ -8,8 +8,8 @@ The directory name has hyphens; import it as ``hvd_amd`` (see /hvd_amd.py).
 from . import (_lib, hashing, multigpu, pipeline, rendezvous, search, sqlite_adapter, synth, vpdq,  # noqa: F401
                vpdqpy, vptree)
 from .hashing import compute_phash, decode_phash_from_str, encode_phash_to_str, get_phash_similarity  # noqa: F401
-from .search import (allpairs_hamming, calculate_distance, find_potential_duplicates, find_transformed_duplicates,  # noqa: F401
-                     fix_vpdq_similarity, match_videos)
+from .search import (allpairs_hamming, calculate_distance, find_excerpts, find_potential_duplicates,  # noqa: F401
+                     find_transformed_duplicates, fix_vpdq_similarity, match_videos)
 from .vpdq import VideoHasher, VpdqHash, matchHash, matchHashBytes  # noqa: F401
 from .pipeline import (DeviceLibrary, dedupe_frames_on_device, dedupe_transformed_frames_on_device, dedupe_videos,  # noqa: F401
                        hash_videos)

@@ -25,6 +25,12 @@ HVD_ERR_STATE = -6
 
 PAIR_DTYPE = np.dtype([("i", "<u4"), ("j", "<u4"), ("dist", "<u4"), ("pad", "<u4")])
 VMATCH_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("q_hits", "<u4"), ("t_hits", "<u4")])
+# one aligned video pair (hvd_valign, include/hvd_mi355x.h): offset = INT32_MIN marks a pair the device entry could not align
+VALIGN_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("q_hits", "<u4"), ("t_hits", "<u4"), ("offset", "<i4"),
+                         ("band_votes", "<u4"), ("q_aligned", "<u4"), ("t_aligned", "<u4"), ("q_first", "<i4"),
+                         ("q_last", "<i4"), ("t_first", "<i4"), ("t_last", "<i4")])
+ALIGN_LDS_BINS = 4096  # HVD_ALIGN_LDS_BINS
+ALIGN_MAX_BINS = 1 << 20
 
 # name -> (restype, argtypes); every symbol include/hvd_mi355x.h declares.
 _vp, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
@@ -53,6 +59,7 @@ SIGNATURES = {
     "hvd_vpdq_match_videos": (_int, [_vp, _vp, _i64, _int, _vp, _i64, C.POINTER(_i64)]),
     "hvd_vpdq_match_videos_cross": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _i64,
                                            C.POINTER(_i64)]),
+    "hvd_vpdq_align_videos": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp]),
     "hvd_hasher_create": (_int, [_int, _int, _int, _i64, C.POINTER(_vp)]),
     "hvd_hasher_push": (_int, [_vp, _vp]),
     "hvd_hasher_set_threads": (_int, [_vp, _int]),
@@ -96,6 +103,9 @@ SIGNATURES = {
     "hvd_dev_compact_kept": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _vp, _vp, _vp, C.POINTER(_i64)]),
     "hvd_dev_compact_kept_dihedral": (_int, [_vp, _vp, _i64, _vp, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp,
                                              C.POINTER(_i64)]),
+    "hvd_dev_kept_positions": (_int, [_vp, _i64, _vp, _i64, _int, _vp]),
+    "hvd_align_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
+    "hvd_dev_vpdq_align_videos": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _sz, _vp]),
     "hvd_dev_vpdq_match_videos": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _i64, _vp]),
     "hvd_dev_vpdq_emit_again": (_int, [_vp, _i64, _vp]),
     "hvd_dev_vpdq_match_videos_cross": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _int, _int, _int, _vp, _i64,

@@ -130,6 +130,17 @@ hipError_t launch_compact_kept_dihedral(const void* d_hashes8, const int32_t* d_
 hipError_t launch_video_of_frames(const long long* d_offsets, uint32_t V, unsigned long long n, int32_t* d_out_video,
                                   hipStream_t s);
 
+hipError_t launch_kept_positions(const int32_t* d_quality, unsigned long long n, const long long* d_offsets, uint32_t V, int min_q,
+                                 int32_t* d_out_pos, void* d_scratch, unsigned long long* d_total, hipStream_t s);
+
+// Time alignment of listed video pairs (k_valign.hip). Two launches: the pairs whose delta histogram fits LDS, then
+// the larger ones out of d_scratch (align_scratch_bytes(max_bins); may be nullptr / 0: such pairs then get the INT32_MIN record).
+size_t align_scratch_bytes(unsigned long long max_bins);
+hipError_t launch_valign(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
+                         const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
+                         const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, void* d_scratch,
+                         size_t scratch_bytes, hvd_valign* d_out, hipStream_t s);
+
 // Synthetic 64x64 gray video frames generated in HBM (k_synth.hip; workload generator, not on the hashing path).
 hipError_t launch_synth_frames64(uint8_t* d_out, long long v0, uint32_t frames_per_video, unsigned long long n_frames,
                                  uint64_t seed, const int32_t* d_copy_of, hipStream_t s);

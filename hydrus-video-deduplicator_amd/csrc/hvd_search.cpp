@@ -984,6 +984,127 @@ int hvd_dev_vpdq_match_videos_cross(const void* d_img_q, int64_t nq, const void*
                             d_out, cap, d_count);
 }
 
+/* ---- time alignment of listed video pairs (k_valign.hip) ---- */
+
+int hvd_dev_kept_positions(const void* d_quality, int64_t n, const void* d_offsets, int64_t V, int min_quality, void* d_out_pos) {
+    if (int rc = need_ready()) return rc;
+    if (n < 0 || V < 0 || n >= (1ll << 32) - 1 || V >= (1ll << 31) || !d_offsets) return fail(HVD_ERR_ARG, "bad arguments");
+    if (n > 0 && (!d_quality || !d_out_pos)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if (n > 0 && V == 0) return fail(HVD_ERR_ARG, "n=%lld frames in no video", (long long)n);
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    void* d_scr = nullptr;
+    unsigned long long* d_counters = nullptr;
+    SCR(S_COMPACT, hvd::compact_scratch_bytes((unsigned long long)n), d_scr);
+    SCR(S_COUNTERS, 64, d_counters);
+    HIP_TRY(hvd::launch_kept_positions((const int32_t*)d_quality, (unsigned long long)n, (const long long*)d_offsets, (uint32_t)V,
+                                       min_quality, (int32_t*)d_out_pos, d_scr, d_counters + 2, g.stream));
+    return HVD_OK;
+}
+
+int hvd_align_scratch_bytes(int64_t max_bins, size_t* out_bytes) {
+    if (!out_bytes || max_bins < 0 || max_bins > (1ll << 20)) return fail(HVD_ERR_ARG, "max_bins=%lld: need 0..2^20", (long long)max_bins);
+    *out_bytes = hvd::align_scratch_bytes((unsigned long long)max_bins);
+    return HVD_OK;
+}
+
+int hvd_dev_vpdq_align_videos(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                              const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                              const void* d_pairs, int64_t M, int max_dist, int slack, void* d_scratch, size_t scratch_bytes,
+                              void* d_out) {
+    if (int rc = need_ready()) return rc;
+    if (VQ < 0 || VT < 0 || VQ >= (1ll << 31) || VT >= (1ll << 31) || M < 0) return fail(HVD_ERR_ARG, "bad counts");
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    if (slack < 0 || slack > 16) return fail(HVD_ERR_ARG, "slack=%d out of range [0,16]", slack);
+    if (M == 0) return HVD_OK;
+    if (!d_offsets_q || !d_offsets_t || !d_pairs || !d_out) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if (((uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch) & 15u)
+        return fail(HVD_ERR_ARG, "hashes and scratch must be 16-byte aligned");
+    HIP_TRY(hvd::launch_valign(d_hashes_q, (const long long*)d_offsets_q, (uint32_t)VQ, (const int32_t*)d_pos_q, d_hashes_t,
+                               (const long long*)d_offsets_t, (uint32_t)VT, (const int32_t*)d_pos_t, (const uint32_t*)d_pairs,
+                               (unsigned long long)M, (uint32_t)max_dist, (uint32_t)slack, d_scratch, scratch_bytes,
+                               (hvd_valign*)d_out, g.stream));
+    return HVD_OK;
+}
+
+// positions of one library: non-negative, strictly increasing inside a video, below 2^20
+static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V, const char* side) {
+    if (!pos) return HVD_OK;
+    for (int64_t v = 0; v < V; ++v)
+        for (int64_t f = offsets[v]; f < offsets[v + 1]; ++f)
+            if (pos[f] < 0 || pos[f] >= (1 << 20) || (f > offsets[v] && pos[f] <= pos[f - 1]))
+                return fail(HVD_ERR_ARG, "%s positions: frame %lld of video %lld is %d (need >= 0, strictly increasing inside a "
+                            "video, below 2^20)", side, (long long)(f - offsets[v]), (long long)v, pos[f]);
+    return HVD_OK;
+}
+
+int hvd_vpdq_align_videos(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                          const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                          const uint32_t* pairs, int64_t M, int max_dist, int slack, hvd_valign* out) {
+    if (int rc = need_ready()) return rc;
+    if (M < 0 || (M > 0 && (!pairs || !out))) return fail(HVD_ERR_ARG, "bad pair list / output buffer");
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    if (slack < 0 || slack > 16) return fail(HVD_ERR_ARG, "slack=%d out of range [0,16]", slack);
+    int64_t nq = 0, nt = 0;
+    if (int rc = check_offsets(offsets_q, VQ, &nq)) return rc;
+    if (int rc = check_offsets(offsets_t, VT, &nt)) return rc;
+    if ((nq > 0 && !frames_q) || (nt > 0 && !frames_t)) return fail(HVD_ERR_ARG, "frames is NULL");
+    if (int rc = check_positions(positions_q, offsets_q, VQ, "query")) return rc;
+    if (int rc = check_positions(positions_t, offsets_t, VT, "target")) return rc;
+    auto span = [](const int32_t* pos, const int64_t* off, int64_t v) -> int64_t {
+        const int64_t n = off[v + 1] - off[v];
+        return n == 0 ? -1 : pos ? (int64_t)pos[off[v + 1] - 1] - pos[off[v]] : n - 1;
+    };
+    int64_t max_bins = 0;
+    for (int64_t p = 0; p < M; ++p) {
+        const uint32_t a = pairs[2 * p], b = pairs[2 * p + 1];
+        if ((int64_t)a >= VQ || (int64_t)b >= VT)
+            return fail(HVD_ERR_ARG, "pair %lld = (%u, %u) is outside the %lld x %lld videos", (long long)p, a, b, (long long)VQ, (long long)VT);
+        const int64_t sa = span(positions_q, offsets_q, a), sb = span(positions_t, offsets_t, b);
+        if (sa < 0 || sb < 0) continue;  // an empty video: the zero record
+        const int64_t bins = sa + sb + 1 + 2 * (int64_t)slack;
+        if (bins > (1ll << 20))
+            return fail(HVD_ERR_ARG, "pair %lld = (%u, %u) spans %lld offsets with slack %d: more than the 2^20 histogram bins",
+                        (long long)p, a, b, (long long)bins, slack);
+        max_bins = std::max(max_bins, bins);
+    }
+    if (M == 0) return HVD_OK;
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    const bool self = frames_t == frames_q && offsets_t == offsets_q && positions_t == positions_q && VT == VQ;
+    void *d_hq = nullptr, *d_ht = nullptr, *d_scr = nullptr, *d_pairs = nullptr, *d_out = nullptr;
+    long long *d_oq = nullptr, *d_ot = nullptr;
+    int32_t *d_pq = nullptr, *d_pt = nullptr;
+    auto upload = [&](const uint8_t* frames, const int64_t* offsets, int64_t V, int64_t n, const int32_t* pos, Ctx::Scr s_db,
+                      Ctx::Scr s_off, Ctx::Scr s_pos, void** d_h, long long** d_o, int32_t** d_p) -> int {
+        if (int rc = scratch(s_db, 32 * (size_t)n, d_h)) return rc;
+        if (int rc = scratch(s_off, 8 * (size_t)(V + 1), (void**)d_o)) return rc;
+        if (n > 0) HIP_TRY(hipMemcpyAsync(*d_h, frames, 32 * (size_t)n, hipMemcpyHostToDevice, g.stream));
+        HIP_TRY(hipMemcpyAsync(*d_o, offsets, 8 * (size_t)(V + 1), hipMemcpyHostToDevice, g.stream));
+        if (pos && n > 0) {
+            if (int rc = scratch(s_pos, 4 * (size_t)n, (void**)d_p)) return rc;
+            HIP_TRY(hipMemcpyAsync(*d_p, pos, 4 * (size_t)n, hipMemcpyHostToDevice, g.stream));
+        }
+        return HVD_OK;
+    };
+    if (int rc = upload(frames_q, offsets_q, VQ, nq, positions_q, Ctx::S_DB, Ctx::S_OFF, Ctx::S_POSQ, &d_hq, &d_oq, &d_pq)) return rc;
+    if (self) {
+        d_ht = d_hq;
+        d_ot = d_oq;
+        d_pt = d_pq;
+    } else if (int rc = upload(frames_t, offsets_t, VT, nt, positions_t, Ctx::S_DB2, Ctx::S_OFF2, Ctx::S_POST, &d_ht, &d_ot, &d_pt)) {
+        return rc;
+    }
+    SCR(S_APAIRS, 8 * (size_t)M, d_pairs);
+    SCR(S_AOUT, sizeof(hvd_valign) * (size_t)M, d_out);
+    const size_t sb = hvd::align_scratch_bytes((unsigned long long)max_bins);
+    if (sb) SCR(S_ASCR, sb, d_scr);
+    HIP_TRY(hipMemcpyAsync(d_pairs, pairs, 8 * (size_t)M, hipMemcpyHostToDevice, g.stream));
+    if (int rc = hvd_dev_vpdq_align_videos(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack, d_scr, sb, d_out))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(hvd_valign) * (size_t)M, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
+}
+
 #ifndef HVD_NO_BENCH_SYMBOLS
 int hvd_dev_synth_video_frames(void* d_frames, int64_t v0, int64_t n_videos, int frames_per_video, uint64_t seed,
                                const void* d_copy_of) {

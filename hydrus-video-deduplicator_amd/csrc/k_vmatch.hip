@@ -232,6 +232,23 @@ __global__ __launch_bounds__(256) void k_keep_positions(const int32_t* __restric
     }
 }
 
+// The raw index inside its video of every kept frame, in kept order (the keep rule and the prefix of k_keep_scatter): the
+// timeline of the alignment (k_valign.hip), which a dropped fade or black frame must not shift.
+__global__ __launch_bounds__(256) void k_kept_positions(const int32_t* __restrict__ quality, unsigned long long n, int min_q,
+                                                        const uint32_t* __restrict__ block_prefix,
+                                                        const long long* __restrict__ offsets, uint32_t V,
+                                                        int32_t* __restrict__ out_pos) {
+    const unsigned long long base = (unsigned long long)blockIdx.x * kBlk + threadIdx.x * 4u;
+    bool keep[4];
+    uint32_t before = keep_prefix(quality, n, min_q, block_prefix, base, keep);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned long long f = base + k;
+        if (f >= n) break;
+        if (keep[k]) out_pos[before++] = (int32_t)(f - (unsigned long long)offsets[video_of_frame(offsets, V, f)]);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_keep_offsets(const long long* __restrict__ offsets, uint32_t V, unsigned long long n,
                                                       const uint32_t* __restrict__ pos,
                                                       const unsigned long long* __restrict__ total,
@@ -386,6 +403,18 @@ hipError_t launch_compact_kept_dihedral(const void* d_hashes8, const int32_t* d_
                            (const uint4*)d_hashes8, d_quality, n, min_q, pos, d_out_video, d_out_offsets, sel, S, lg_w,
                            (unsigned long long)(S - 1u) * n, (uint4*)d_out_hashes, (uint4*)d_q_hashes, d_q_video, d_q_excl);
     }
+    return hipGetLastError();
+}
+
+// d_scratch: compact_scratch_bytes(n) (only the block sums are used). d_total: one uint64 (device), receives the kept count.
+hipError_t launch_kept_positions(const int32_t* d_quality, unsigned long long n, const long long* d_offsets, uint32_t V, int min_q,
+                                 int32_t* d_out_pos, void* d_scratch, unsigned long long* d_total, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const unsigned long long nb = (n + kBlk - 1) / kBlk;
+    uint32_t* sums = (uint32_t*)d_scratch;
+    hipLaunchKernelGGL(k_keep_count, dim3((unsigned)nb), dim3(256), 0, s, d_quality, n, min_q, sums);
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, sums, (uint32_t)nb, d_total);
+    hipLaunchKernelGGL(k_kept_positions, dim3((unsigned)nb), dim3(256), 0, s, d_quality, n, min_q, sums, d_offsets, V, d_out_pos);
     return hipGetLastError();
 }
 

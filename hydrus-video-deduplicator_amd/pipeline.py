@@ -23,7 +23,7 @@ import threading
 import numpy as np
 
 from . import _lib, search, vpdq
-from ._lib import VMATCH_DTYPE, DeviceBuffer
+from ._lib import VALIGN_DTYPE, VMATCH_DTYPE, DeviceBuffer
 
 
 def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
@@ -160,13 +160,17 @@ class DeviceLibrary:
         self.d_hashes, self.d_offsets, self.d_video = d_hashes, d_offsets, d_video
         self.n_frames, self.n_videos = int(n_frames), int(n_videos)
         self.d_img = None
+        self.d_positions = None  # int32 per kept frame: its raw index inside its video (from_raw_hashes(positions=True))
+        self._position_limit = 0
         self._lengths = None
 
     @classmethod
     def from_raw_hashes(cls, d_hashes_ptr: int, d_quality_ptr: int, n: int, raw_offsets: np.ndarray,
-                        min_quality: int = vpdq.QUALITY_TOLERANCE) -> "DeviceLibrary":
+                        min_quality: int = vpdq.QUALITY_TOLERANCE, positions: bool = False) -> "DeviceLibrary":
         """Quality filter + CSR on the device (hvd_dev_compact_kept). raw_offsets: int64[V+1] over the n
-        hashed frames (host array; V+1 numbers are the only thing uploaded)."""
+        hashed frames (host array; V+1 numbers are the only thing uploaded). positions=True: also the raw index inside
+        its video of every kept frame (hvd_dev_kept_positions; the quality array is the caller's and may be gone later), the
+        timeline `align` then works on; the default runs exactly the launches of the plain pipeline."""
         lib = _lib.ensure()
         raw_offsets = np.ascontiguousarray(raw_offsets, dtype=np.int64)
         V = raw_offsets.size - 1
@@ -180,9 +184,17 @@ class DeviceLibrary:
         try:
             _lib.check(lib.hvd_dev_compact_kept(d_hashes_ptr, d_quality_ptr, n, d_roff.ptr, V, int(min_quality),
                                                 d_out_h.ptr, d_out_off.ptr, d_out_vid.ptr, C.byref(kept)))
+            d_pos = None
+            if positions:
+                d_pos = DeviceBuffer(4 * max(n, 1))
+                _lib.check(lib.hvd_dev_kept_positions(d_quality_ptr, n, d_roff.ptr, V, int(min_quality), d_pos.ptr))
+                _lib.check(lib.hvd_dev_sync())  # the raw offsets are freed below
         finally:
             d_roff.free()
-        return cls(d_out_h, d_out_off, d_out_vid, kept.value, V)
+        library = cls(d_out_h, d_out_off, d_out_vid, kept.value, V)
+        library.d_positions = d_pos
+        library._position_limit = int(np.diff(raw_offsets).max()) if V else 0  # every position is below this
+        return library
 
     @classmethod
     def from_raw_dihedral(cls, d_hashes8_ptr: int, d_quality_ptr: int, n: int, raw_offsets: np.ndarray, transforms,
@@ -273,11 +285,59 @@ class DeviceLibrary:
             queries.image().ptr, queries.n_frames, queries.d_video.ptr, queries.d_excl.ptr, self.image().ptr, self.n_frames,
             self.d_video.ptr, self.d_video.ptr, max_dist, rank, world, d_out, cap_, d_cnt), cap)
 
+    def positions(self) -> np.ndarray | None:
+        return None if self.d_positions is None else self.d_positions.to_array(np.int32, self.n_frames)
+
+    def align(self, records, slack: int = search.ALIGN_SLACK, max_dist: int | None = None) -> np.ndarray:
+        """hvd_dev_vpdq_align_videos of the listed pairs of this library against itself (records: VMATCH records, or
+        int[M, 2]): one VALIGN_DTYPE record per pair, in their order. The hashes, the CSR and the positions stay where they
+        are; the pair list goes up, the records come back. Positions: those of from_raw_hashes(positions=True), else the
+        index inside the kept video."""
+        lib = _lib.ensure()
+        if isinstance(records, np.ndarray) and records.dtype.names:
+            records = np.stack([records["a"], records["b"]], axis=1)
+        pairs = np.ascontiguousarray(np.asarray(records, dtype=np.int64).reshape(-1, 2), dtype=np.uint32)
+        M = pairs.shape[0]
+        max_dist = vpdq.frame_max_dist(search.DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
+        out = np.zeros(M, dtype=VALIGN_DTYPE)
+        out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
+        if M == 0 or max_dist < 0:
+            return out
+        # the scratch serves the widest pair this library can hold: positions lie below the longest (raw) video's length
+        if self.d_positions is None:
+            lengths = self.lengths()
+            limit = int(lengths.max()) if lengths.size else 0
+        else:
+            limit = self._position_limit
+        max_bins = min(2 * max(limit, 1) - 1 + 2 * int(slack), _lib.ALIGN_MAX_BINS)
+        sb = C.c_size_t(0)
+        _lib.check(lib.hvd_align_scratch_bytes(max_bins, C.byref(sb)))
+        bufs = []
+        try:
+            d_pairs = DeviceBuffer.from_array(pairs)
+            bufs.append(d_pairs)
+            d_out = DeviceBuffer(VALIGN_DTYPE.itemsize * M)
+            bufs.append(d_out)
+            d_scr = DeviceBuffer(sb.value) if sb.value else None
+            bufs.append(d_scr)
+            d_pos = self.d_positions.ptr if self.d_positions is not None else None
+            _lib.check(lib.hvd_dev_vpdq_align_videos(self.d_hashes.ptr, self.d_offsets.ptr, self.n_videos, d_pos,
+                                                     self.d_hashes.ptr, self.d_offsets.ptr, self.n_videos, d_pos, d_pairs.ptr,
+                                                     M, max_dist, int(slack), d_scr.ptr if d_scr else None, sb.value,
+                                                     d_out.ptr))
+            return d_out.to_array(VALIGN_DTYPE, M)  # (the copy waits for the library stream)
+        finally:
+            lib.hvd_dev_sync()  # nothing may still run on a buffer that is freed here
+            for b in bufs:
+                if b is not None:
+                    b.free()
+
     def free(self) -> None:
-        for b in (self.d_hashes, self.d_offsets, self.d_video, self.d_img):
+        for b in (self.d_hashes, self.d_offsets, self.d_video, self.d_img, self.d_positions):
             if b is not None:
                 b.free()
         self.d_img = None
+        self.d_positions = None
 
 
 class DeviceQueries(DeviceLibrary):
@@ -466,6 +526,37 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
         return pairs, recs, library
     library.free()
     return pairs, recs, None
+
+
+def find_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                            threshold: float = 50.0, min_aligned: int = 4, slack: int = search.ALIGN_SLACK,
+                            positions: bool = True, keep_library: bool = False):
+    """search.find_excerpts on frames in HBM, one device: hash -> quality filter + CSR, with the kept frames' raw positions
+    (`DeviceLibrary.from_raw_hashes(positions=True)`) -> video search -> alignment of its records (`DeviceLibrary.align`) ->
+    the keep rule of search.excerpts_from_records. raw_offsets: CSR of the videos over the frames at d_frames_ptr.
+    positions=False aligns on the index inside the KEPT video instead: a frame the quality filter dropped then shifts
+    everything after it (kept for comparison; the default is what a caller wants).
+    -> (excerpts, search records, alignment records, library or None); Excerpt offsets / first / last are raw frame indices."""
+    raw_offsets = _check_raw_offsets(raw_offsets)
+    n = int(raw_offsets[-1])
+    d_h, d_q = hash_frames_on_device(d_frames_ptr, n, h, w, channels)
+    try:
+        library = DeviceLibrary.from_raw_hashes(d_h.ptr, d_q.ptr, n, raw_offsets, positions=bool(positions))
+    finally:
+        d_h.free()
+        d_q.free()
+    try:
+        recs = library.match_videos()
+        aligned = library.align(recs, slack=slack)
+        lengths = library.lengths()
+        out = search.excerpts_from_records(aligned, lengths, search.similarity_of_records(recs, lengths), threshold, min_aligned)
+    except BaseException:
+        library.free()
+        raise
+    if keep_library:
+        return out, recs, aligned, library
+    library.free()
+    return out, recs, aligned, None
 
 
 def dedupe_frames_in_process(frames_of_rank, raw_offsets: np.ndarray, h: int, w: int, channels: int,

@@ -12,11 +12,12 @@ db/vptree.py:431-441); this module computes it exactly.
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 
 import numpy as np
 
 from . import _lib, vpdq
-from ._lib import PAIR_DTYPE, VMATCH_DTYPE
+from ._lib import PAIR_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE
 
 DISTANCE_TOLERANCE = 31  # per-frame Hamming tolerance (vpdqpy/vpdqpy.py:53, db/vptree.py:31)
 DEFAULT_VARIANT = 13  # all-pairs kernel the product uses (FP4-MFMA, 128-bit first stage, form chosen by a probe); DESIGN.md 4.1
@@ -299,3 +300,128 @@ def transformed_pairs(ident: list, var: list, cross, threshold: float = 50.0, po
         recs_c = np.zeros(0, dtype=VMATCH_DTYPE)
     return fold_transformed_records(recs_i, recs_c, lengths, [vpdq.TRANSFORMS.index(t) for t in cross], threshold, policy,
                                     return_similarity=True)
+
+
+# ------------------------------------------------------------------ excerpts: time-aligned matching ------
+
+ALIGN_SLACK = 1  # frames a hit may lie off the best offset and still count as aligned (a dropped or doubled frame)
+
+
+def _library(frames, offsets, positions):
+    frames = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1, 32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offsets.size < 1 or offsets[-1] != frames.shape[0]:
+        raise ValueError("offsets[-1] must equal the number of frame hashes")
+    if positions is not None:
+        positions = np.ascontiguousarray(positions, dtype=np.int32)
+        if positions.shape != (frames.shape[0],):
+            raise ValueError("positions must hold one int32 per frame hash")
+    return frames, offsets, positions
+
+
+def align_videos(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.ndarray | None = None,
+                 max_dist: int | None = None, slack: int = ALIGN_SLACK, frames_t: np.ndarray | None = None,
+                 offsets_t: np.ndarray | None = None, positions_t: np.ndarray | None = None) -> np.ndarray:
+    """Time alignment of the listed video pairs (hvd_vpdq_align_videos): one VALIGN_DTYPE record per pair, in the order of
+    `pairs` (int[M, 2], or VMATCH records: their a, b). frames / offsets (/ positions: int32 per frame, non-negative, strictly
+    increasing inside a video, below 2^20; default: the index inside the video): the library of the a side, and of the b side
+    too unless frames_t / offsets_t (/ positions_t) give another one. A record holds the pair's vPDQ counters, the best
+    offset (p_b = p_a + offset), the frame hits within `slack` of it, and per side the number of frames with such a hit and
+    the first and last position among them; max_dist defaults to the search's frame tolerance."""
+    frames, offsets, positions = _library(frames, offsets, positions)
+    if (frames_t is None) != (offsets_t is None):
+        raise ValueError("pass frames_t and offsets_t together")
+    if frames_t is None:
+        if positions_t is not None:
+            raise ValueError("positions_t without a target library")
+        frames_t, offsets_t, positions_t = frames, offsets, positions
+    else:
+        frames_t, offsets_t, positions_t = _library(frames_t, offsets_t, positions_t)
+    if isinstance(pairs, np.ndarray) and pairs.dtype.names:
+        pairs = np.stack([pairs["a"], pairs["b"]], axis=1)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= 1 << 32):
+        raise ValueError("pair index out of range")
+    pairs = np.ascontiguousarray(pairs, dtype=np.uint32)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
+    M = pairs.shape[0]
+    out = np.zeros(M, dtype=VALIGN_DTYPE)
+    out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
+    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
+        return out
+    lib = _lib.ensure()
+    ptr = lambda x: x.ctypes.data if x is not None and x.size else None  # noqa: E731
+    _lib.check(lib.hvd_vpdq_align_videos(ptr(frames), offsets.ctypes.data, offsets.size - 1, ptr(positions), ptr(frames_t),
+                                         offsets_t.ctypes.data, offsets_t.size - 1, ptr(positions_t), ptr(pairs), M, max_dist,
+                                         int(slack), ptr(out)))
+    return out
+
+
+Excerpt = namedtuple("Excerpt", "short long offset first last coverage similarity")
+
+
+def excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: np.ndarray, threshold: float = 50.0,
+                          min_aligned: int = 4) -> list:
+    """The keep rule of find_excerpts on alignment records (pure numpy; no device). short = the video with fewer frames (a on
+    a tie); coverage = 100 * aligned frames of short / frames of short; kept iff int(coverage) >= int(threshold) and at least
+    min_aligned frames of short are aligned. -> sorted list of Excerpt; offset / first / last are in long's timeline
+    (p_long = p_short + offset)."""
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    lengths = np.asarray(lengths, dtype=np.int64)
+    out = []
+    for r, sim in zip(aligned, similarity):
+        a, b = int(r["a"]), int(r["b"])
+        a_short = lengths[a] <= lengths[b]
+        n_short = int(lengths[a] if a_short else lengths[b])
+        on = int(r["q_aligned"] if a_short else r["t_aligned"])
+        if n_short == 0 or on < int(min_aligned) or int(r["offset"]) == -(1 << 31):
+            continue
+        coverage = 100.0 * on / n_short
+        if int(coverage) < int(threshold):
+            continue
+        out.append(Excerpt(a, b, int(r["offset"]), int(r["t_first"]), int(r["t_last"]), coverage, float(sim)) if a_short else
+                   Excerpt(b, a, -int(r["offset"]), int(r["q_first"]), int(r["q_last"]), coverage, float(sim)))
+    return sorted(out)
+
+
+def excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK, positions=None,
+                  matcher=None) -> list:
+    """The search and the alignment of find_excerpts and their fold, on validated blobs (blobs[v]: the hash bytes of video v;
+    positions: None, or one int sequence per video). matcher: object with match_videos / align_videos (default: the GPU
+    entry points of this module). -> excerpts_from_records(...)."""
+    mv, al = (match_videos, align_videos) if matcher is None else (matcher.match_videos, matcher.align_videos)
+    lengths = np.array([len(b) // 32 for b in blobs], dtype=np.int64)
+    offsets = np.zeros(len(blobs) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    frames = np.frombuffer(b"".join(blobs), dtype=np.uint8).reshape(-1, 32)
+    pos = None
+    if positions is not None:
+        if len(positions) != len(blobs) or any(len(p) != n for p, n in zip(positions, lengths)):
+            raise ValueError("positions must hold one position per frame of every video")
+        pos = np.concatenate([np.asarray(p, dtype=np.int32).reshape(-1) for p in positions]) if len(blobs) else \
+            np.zeros(0, np.int32)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
+    recs = mv(frames, offsets, max_dist)
+    aligned = al(frames, offsets, np.stack([recs["a"], recs["b"]], axis=1), positions=pos, max_dist=max_dist, slack=slack)
+    return excerpts_from_records(aligned, lengths, similarity_of_records(recs, lengths), threshold, min_aligned)
+
+
+def find_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
+                  positions=None) -> list:
+    """Videos that are a clip cut out of a longer one (a scene, a trailer, a highlight), and full copies: every pair of the
+    video search (match_videos) is aligned in time (align_videos), and kept iff the frames of the SHORTER video that line up
+    on one offset of the longer one cover at least `threshold` percent of it. video_hashes: a sequence of VpdqHash / bytes;
+    positions: optionally one increasing int sequence per video, the place of each hashed frame on the video's timeline
+    (frames the quality filter dropped leave gaps; default: the index among the hashed frames). -> sorted list of
+    Excerpt(short, long, offset, first, last, coverage, similarity): short lines up with long at p_long = p_short + offset and
+    covers its positions first..last; similarity is find_potential_duplicates' value of the pair under the current match
+    policy (high for a full copy, about 100 * len(short) / len(long) for an excerpt under "min").
+    min_aligned = 4 is a POLICY DEFAULT of this project, not a rule of the reference (which has no excerpt search): fewer
+    than four frames in a row are as likely a shared title card as a clip. slack: how far a hit may lie off the offset and
+    still count (one dropped or doubled frame at the default 1)."""
+    blobs = [h.bytes if isinstance(h, vpdq.VpdqHash) else bytes(h) for h in video_hashes]
+    for b in blobs:
+        if len(b) % 32:
+            raise ValueError("phash length not a multiple of 32")
+    return excerpt_pairs(blobs, threshold, min_aligned, slack, positions)

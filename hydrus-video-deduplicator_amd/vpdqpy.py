@@ -62,6 +62,19 @@ class Vpdq:
         """Get the similarity of two videos by comparing their list of features (vpdqpy.py:49-56)."""
         return vpdq.matchHash(query_features, target_features, int(distance_tolerance))
 
+    @staticmethod
+    def align(phash_a, phash_b, slack: int = 1):
+        """Where two video hashes line up in time: the one ``search.align_videos`` record of the pair (a = 0, b = 1; best
+        offset p_b = p_a + offset, aligned frames per side and their first / last index). VpdqHash or bytes."""
+        from . import search
+
+        blobs = [h.bytes if isinstance(h, VpdqHash) else bytes(h) for h in (phash_a, phash_b)]
+        if any(len(b) % 32 for b in blobs):
+            raise ValueError("phash length not a multiple of 32")
+        na, nb = len(blobs[0]) // 32, len(blobs[1]) // 32
+        frames = np.frombuffer(blobs[0] + blobs[1], dtype=np.uint8).reshape(-1, 32)
+        return search.align_videos(frames, np.array([0, na, na + nb], dtype=np.int64), [(0, 1)], slack=slack)[0]
+
     select_frames = staticmethod(select_frames)
 
     @staticmethod

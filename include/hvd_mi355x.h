@@ -39,7 +39,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -51,6 +51,21 @@ typedef struct {
 typedef struct {
     uint32_t a, b, q_hits, t_hits;
 } hvd_vmatch;
+
+/* One aligned video pair (hvd_vpdq_align_videos / hvd_dev_vpdq_align_videos), twelve 32-bit words. q_hits / t_hits:
+ * the vPDQ counters of the pair (what hvd_vmatch holds). offset: the best offset d* of the target's timeline against the
+ * query's (p_b = p_a + d*). band_votes: frame hits within slack of d*. q_aligned / t_aligned: frames of a / b with such a hit;
+ * *_first / *_last: the smallest and largest position among them. A pair without a frame hit: every word after b is 0. A pair
+ * the device entry cannot align (index out of range, positions that are not strictly increasing from >= 0, more than 2^20
+ * histogram bins, no room in the scratch): offset = INT32_MIN, the other words after b 0. */
+typedef struct hvd_valign {
+    uint32_t a, b, q_hits, t_hits;
+    int32_t offset;
+    uint32_t band_votes, q_aligned, t_aligned;
+    int32_t q_first, q_last, t_first, t_last;
+} hvd_valign;
+/* Pairs of up to this many histogram bins (span of p_a + span of p_b + 1 + 2 slack) are aligned out of LDS alone. */
+#define HVD_ALIGN_LDS_BINS 4096
 
 /* ------------------------------------------------------------ lifecycle -- */
 
@@ -172,6 +187,21 @@ int hvd_vpdq_match_videos(const uint8_t* frames, const int64_t* offsets, int64_t
 int hvd_vpdq_match_videos_cross(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* ids_q,
                                 const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* ids_t,
                                 int max_dist, hvd_vmatch* out, int64_t cap, int64_t* out_count);
+
+/* Time alignment of listed video pairs: is video a an excerpt of video b (or b of a), and where. The rule,
+ * integers only. Position p(f) of a frame: positions[f] if given (int32 per frame of the library; non-negative, strictly
+ * increasing inside a video, below 2^20), else the frame's index inside its video. H = {(i, j) : hamming(A_i, B_j) <= max_dist}
+ * over the frames of a and b; delta(i, j) = p_b(j) - p_a(i); votes[d] = |{(i, j) in H : delta = d}|; S(d) = the sum of
+ * votes[d - slack .. d + slack]. Best offset d*: the largest S(d), ties by the larger votes[d], then the smaller |d|, then the
+ * smaller d. A frame i of a is aligned iff some (i, j) in H has |delta(i, j) - d*| <= slack; likewise the frames of b.
+ * pairs: uint32[M][2] = (a = video of the query library, b = video of the target library); the self form passes one library
+ * twice. out: M hvd_valign records in the order of the pair list. max_dist in [0, 127], slack in [0, 16].
+ * This host-buffer form checks the offsets (as hvd_vpdq_match_videos), the positions, the pair indices and the 2^20-bin limit of
+ * every pair (HVD_ERR_ARG), stages, runs the kernels and copies the records back. Under a device group it runs on the calling
+ * thread's current context alone. positions_q / positions_t may be NULL. */
+int hvd_vpdq_align_videos(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                          const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                          const uint32_t* pairs, int64_t M, int max_dist, int slack, hvd_valign* out);
 
 /* ------------------------------------------------ streaming frame hasher -- */
 /* The native side of vpdq.VideoHasher (vpdqpy/vpdqpy.py:113-119): frames are pushed one at a
@@ -379,6 +409,26 @@ int hvd_dev_compact_kept_dihedral(const void* d_hashes8, const void* d_quality, 
                                   int min_quality, int transform_mask, void* d_out_hashes, void* d_out_offsets,
                                   void* d_out_video, void* d_out_qhashes, void* d_out_qvideo, void* d_out_qexcl,
                                   int64_t* out_kept);
+
+/* The raw index inside its video of every kept frame, in kept order: d_out_pos int32[kept] (room for n), the positions operand
+ * of hvd_dev_vpdq_align_videos for a library made by hvd_dev_compact_kept from the same d_quality / d_offsets (raw CSR, int64[V+1])
+ * / min_quality. Without it a dropped frame shifts the timeline of every frame after it. Enqueued on the library stream, no
+ * host synchronisation; library-owned scratch. */
+int hvd_dev_kept_positions(const void* d_quality, int64_t n, const void* d_offsets, int64_t V, int min_quality, void* d_out_pos);
+
+/* Device-resident alignment (the rule: hvd_vpdq_align_videos above). d_hashes_*: packed hashes (n*32 B, 16-byte aligned);
+ * d_offsets_*: int64[V+1] CSR; d_pos_*: int32 per frame or NULL; d_pairs: uint32[M][2]; d_out: M hvd_valign records. Pairs
+ * whose histogram has more than HVD_ALIGN_LDS_BINS bins need d_scratch: hvd_align_scratch_bytes(max_bins) bytes serve every
+ * pair of up to max_bins bins (<= 2^20; 0 bytes up to HVD_ALIGN_LDS_BINS, d_scratch may then be NULL). Enqueued on the library
+ * stream: no host synchronisation, nothing allocated -- so nothing on the device is validated: a pair index outside [0, V), a
+ * pair beyond 2^20 bins or beyond the scratch, and positions that are visibly not increasing give the INT32_MIN record (see
+ * hvd_valign); frame ranges are clamped to [0, offsets[V]] and every bin index is checked, so broken operands give wrong
+ * records, never an access out of bounds. */
+int hvd_align_scratch_bytes(int64_t max_bins, size_t* out_bytes);
+int hvd_dev_vpdq_align_videos(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                              const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                              const void* d_pairs, int64_t M, int max_dist, int slack, void* d_scratch, size_t scratch_bytes,
+                              void* d_out);
 
 /* Every video pair a<b with >= 1 frame hit, with its vPDQ counters (semantics of vpdqpy/vpdqpy.py:49-56 for all
  * pairs at once; replaces the tree walk of dedup.py:468-475). d_img: FP4 image of the n frame hashes; d_video:
