@@ -166,6 +166,20 @@ def check(rc: int) -> None:
         raise HvdError(rc, last_error())
 
 
+def records_with_retry(call, dtype, cap: int) -> np.ndarray:
+    """The records of an entry point that writes up to `cap` of them into a host buffer: call(out_ptr, cap, byref(count))
+    -> status. HVD_ERR_OVERFLOW reports the count and never truncates: the call is repeated with the exact size."""
+    while True:
+        out = np.zeros(max(cap, 1), dtype=dtype)
+        cnt = C.c_int64(0)
+        rc = call(out.ctypes.data, cap, C.byref(cnt))
+        if rc == HVD_ERR_OVERFLOW:
+            cap = int(cnt.value)
+            continue
+        check(rc)
+        return out[: cnt.value].copy()
+
+
 def device_count() -> int:
     n = C.c_int(0)
     check(load().hvd_device_count(C.byref(n)))

@@ -149,16 +149,8 @@ class RcclExchange:
 
     def allgather_pairs_dev(self, d_pairs_ptr: int, count: int) -> np.ndarray:
         lib = _lib.ensure()
-        cap = 1 << 16
-        while True:
-            out = np.zeros(cap, dtype=PAIR_DTYPE)
-            total = C.c_int64(0)
-            rc = lib.hvd_comm_allgather_pairs(d_pairs_ptr, count, out.ctypes.data, cap, C.byref(total))
-            if rc == _lib.HVD_ERR_OVERFLOW:
-                cap = int(total.value)
-                continue
-            _lib.check(rc)
-            return out[: total.value].copy()
+        return _lib.records_with_retry(
+            lambda out, cap, total: lib.hvd_comm_allgather_pairs(d_pairs_ptr, count, out, cap, total), PAIR_DTYPE, 1 << 16)
 
     def allgather_bytes_dev(self, d_send_ptr: int, d_recv_ptr: int, bytes_per_rank: int) -> None:
         """RCCL all-gather of equally sized device buffers (hash shards produced on-device, config 5)."""

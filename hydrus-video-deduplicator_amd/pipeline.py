@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import ctypes as C
 import threading
+import time
 
 import numpy as np
 
@@ -66,20 +67,68 @@ def dedupe_videos(videos, threshold: float = 50.0, policy: str | None = None):
 # ------------------------------------------------------------------ device-resident form ------
 
 
+class _DeviceScope:
+    """The DeviceBuffers of one call. `temp` buffers (scratch, staging, uploaded operands) are freed on the way out, in the
+    order they were registered; `keep` buffers are the call's results and are freed only if it raises -- after one
+    hvd_dev_sync, since nothing may still run on a buffer that is freed. None is accepted and ignored (no scratch needed)."""
+
+    def __init__(self):
+        self._temp, self._kept = [], []
+
+    def temp(self, buf):
+        self._temp.append(buf)
+        return buf
+
+    def keep(self, buf):
+        self._kept.append(buf)
+        return buf
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        if exc_type is not None:
+            _lib.ensure().hvd_dev_sync()
+        for b in self._temp + (self._kept if exc_type is not None else []):
+            if b is not None:
+                b.free()
+
+
+def _stage_timer(timings):
+    """timed(key, fn) -> fn(); with a timings dict, timings[key] = HIP-event time of fn's work on the library stream."""
+    def timed(key, fn):
+        if timings is None:
+            return fn()
+        lib = _lib.ensure()
+        _lib.check(lib.hvd_timer_start())
+        out = fn()
+        ms = C.c_float(0)
+        _lib.check(lib.hvd_timer_stop(C.byref(ms)))
+        timings[key] = float(ms.value)
+        return out
+
+    return timed
+
+
+def _hash_frames(entry, hash_bytes: int, d_frames_ptr: int, n: int, h: int, w: int, channels: int):
+    """entry: hvd_dev_pdq_hash_frames or its dihedral form; hash_bytes: what it writes per frame."""
+    lib = _lib.ensure()
+    with _DeviceScope() as scope:
+        d_h = scope.keep(DeviceBuffer(hash_bytes * max(n, 1)))
+        d_q = scope.keep(DeviceBuffer(4 * max(n, 1)))
+        sb = C.c_size_t(0)
+        _lib.check(lib.hvd_pdq_scratch_bytes(n, h, w, channels, C.byref(sb)))
+        d_s = scope.temp(DeviceBuffer(sb.value) if sb.value else None)
+        _lib.check(entry(d_frames_ptr, n, h, w, channels, d_s.ptr if d_s else None, d_h.ptr, d_q.ptr))
+        if d_s is not None:
+            _lib.check(lib.hvd_dev_sync())  # the scratch must outlive the kernels
+    return d_h, d_q
+
+
 def hash_frames_on_device(d_frames_ptr: int, n: int, h: int, w: int, channels: int):
     """PDQ-hash n frames that already sit in HBM -> (d_hashes, d_quality) DeviceBuffers (n*32 B, int32[n]).
     Enqueued on the library stream; no host synchronisation."""
-    lib = _lib.ensure()
-    d_h = DeviceBuffer(32 * max(n, 1))
-    d_q = DeviceBuffer(4 * max(n, 1))
-    sb = C.c_size_t(0)
-    _lib.check(lib.hvd_pdq_scratch_bytes(n, h, w, channels, C.byref(sb)))
-    d_s = DeviceBuffer(sb.value) if sb.value else None
-    _lib.check(lib.hvd_dev_pdq_hash_frames(d_frames_ptr, n, h, w, channels, d_s.ptr if d_s else None, d_h.ptr, d_q.ptr))
-    if d_s is not None:
-        _lib.check(lib.hvd_dev_sync())  # the scratch must outlive the kernels
-        d_s.free()
-    return d_h, d_q
+    return _hash_frames(_lib.ensure().hvd_dev_pdq_hash_frames, 32, d_frames_ptr, n, h, w, channels)
 
 
 def hash_frames_dihedral_on_device(d_frames_ptr: int, n: int, h: int, w: int, channels: int):
@@ -88,17 +137,7 @@ def hash_frames_dihedral_on_device(d_frames_ptr: int, n: int, h: int, w: int, ch
     lib = _lib.ensure()
     if lib.hvd_get_pdq_dct_mode() != 0:
         raise _lib.HvdError(_lib.HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: set_dct_mode('strict') first")
-    d_h = DeviceBuffer(256 * max(n, 1))
-    d_q = DeviceBuffer(4 * max(n, 1))
-    sb = C.c_size_t(0)
-    _lib.check(lib.hvd_pdq_scratch_bytes(n, h, w, channels, C.byref(sb)))
-    d_s = DeviceBuffer(sb.value) if sb.value else None
-    _lib.check(lib.hvd_dev_pdq_hash_frames_dihedral(d_frames_ptr, n, h, w, channels, d_s.ptr if d_s else None, d_h.ptr,
-                                                    d_q.ptr))
-    if d_s is not None:
-        _lib.check(lib.hvd_dev_sync())  # the scratch must outlive the kernels
-        d_s.free()
-    return d_h, d_q
+    return _hash_frames(lib.hvd_dev_pdq_hash_frames_dihedral, 256, d_frames_ptr, n, h, w, channels)
 
 
 def hash_frames_autocrop_on_device(d_frames_ptr: int, n: int, h: int, w: int, channels: int, offsets: np.ndarray,
@@ -111,30 +150,21 @@ def hash_frames_autocrop_on_device(d_frames_ptr: int, n: int, h: int, w: int, ch
     offsets = _check_raw_offsets(offsets, n)
     V = offsets.size - 1
     run = timed if timed is not None else (lambda key, fn: fn())
-    bufs = {}
-    try:
-        bufs["off"] = d_off = DeviceBuffer.from_array(offsets)
-        bufs["r"] = d_r = DeviceBuffer(16 * max(V, 1))
+    with _DeviceScope() as scope:
+        d_off = scope.keep(DeviceBuffer.from_array(offsets))
+        d_r = scope.keep(DeviceBuffer(16 * max(V, 1)))
         run("rects_ms", lambda: _lib.check(lib.hvd_dev_content_rects(d_frames_ptr, n, h, w, channels, d_off.ptr, V,
                                                                      int(black_level), int(min_bright), d_r.ptr)))
-        bufs["h"] = d_h = DeviceBuffer(32 * max(n, 1))
-        bufs["q"] = d_q = DeviceBuffer(4 * max(n, 1))
+        d_h = scope.keep(DeviceBuffer(32 * max(n, 1)))
+        d_q = scope.keep(DeviceBuffer(4 * max(n, 1)))
         sb = C.c_size_t(0)
         _lib.check(lib.hvd_pdq_rects_scratch_bytes(n, h, w, channels, C.byref(sb)))
-        bufs["s"] = d_s = DeviceBuffer(sb.value) if sb.value else None
+        d_s = scope.temp(DeviceBuffer(sb.value) if sb.value else None)
         run("hash_ms", lambda: _lib.check(lib.hvd_dev_pdq_hash_frames_rects(d_frames_ptr, n, h, w, channels, d_off.ptr, V,
                                                                             d_r.ptr, d_s.ptr if d_s else None, d_h.ptr,
                                                                             d_q.ptr)))
         _lib.check(lib.hvd_dev_sync())  # the scratch and the offsets must outlive the kernels
-    except BaseException:
-        lib.hvd_dev_sync()  # nothing may still run on a buffer that is freed here
-        for b in bufs.values():
-            if b is not None:
-                b.free()
-        raise
-    for key in ("s", "off"):
-        if bufs[key] is not None:
-            bufs[key].free()
+        scope.temp(d_off)  # (done with: it goes after the scratch)
     return d_h, d_q, d_r
 
 
@@ -149,6 +179,18 @@ def _check_raw_offsets(raw_offsets, n: int | None = None) -> np.ndarray:
     if (V < 0 or raw_offsets[0] != 0 or (n is not None and raw_offsets[-1] != n) or (np.diff(raw_offsets) < 0).any()):
         raise ValueError("raw_offsets must be a CSR over the n frames")
     return raw_offsets
+
+
+def _compaction_buffers(scope: _DeviceScope, raw_offsets: np.ndarray, n: int):
+    """What both compactions take: the raw CSR, uploaded for the length of the scope, and their outputs for at most n kept
+    frames. -> (d_raw_offsets, d_hashes, d_offsets, d_video)."""
+    d_roff = scope.temp(DeviceBuffer.from_array(raw_offsets))
+    return (d_roff, scope.keep(DeviceBuffer(32 * max(n, 1))), scope.keep(DeviceBuffer(8 * raw_offsets.size)),
+            scope.keep(DeviceBuffer(4 * max(n, 1))))
+
+
+def _default_max_dist(max_dist: int | None) -> int:
+    return vpdq.frame_max_dist(search.DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
 
 
 class DeviceLibrary:
@@ -172,25 +214,18 @@ class DeviceLibrary:
         its video of every kept frame (hvd_dev_kept_positions; the quality array is the caller's and may be gone later), the
         timeline `align` then works on; the default runs exactly the launches of the plain pipeline."""
         lib = _lib.ensure()
-        raw_offsets = np.ascontiguousarray(raw_offsets, dtype=np.int64)
+        raw_offsets = _check_raw_offsets(raw_offsets, n)
         V = raw_offsets.size - 1
-        if V < 0 or raw_offsets[0] != 0 or raw_offsets[-1] != n or (np.diff(raw_offsets) < 0).any():
-            raise ValueError("raw_offsets must be a CSR over the n frames")
-        d_roff = DeviceBuffer.from_array(raw_offsets)
-        d_out_h = DeviceBuffer(32 * max(n, 1))
-        d_out_off = DeviceBuffer(8 * (V + 1))
-        d_out_vid = DeviceBuffer(4 * max(n, 1))
         kept = C.c_int64(0)
-        try:
+        with _DeviceScope() as scope:
+            d_roff, d_out_h, d_out_off, d_out_vid = _compaction_buffers(scope, raw_offsets, n)
             _lib.check(lib.hvd_dev_compact_kept(d_hashes_ptr, d_quality_ptr, n, d_roff.ptr, V, int(min_quality),
                                                 d_out_h.ptr, d_out_off.ptr, d_out_vid.ptr, C.byref(kept)))
             d_pos = None
             if positions:
-                d_pos = DeviceBuffer(4 * max(n, 1))
+                d_pos = scope.keep(DeviceBuffer(4 * max(n, 1)))
                 _lib.check(lib.hvd_dev_kept_positions(d_quality_ptr, n, d_roff.ptr, V, int(min_quality), d_pos.ptr))
-                _lib.check(lib.hvd_dev_sync())  # the raw offsets are freed below
-        finally:
-            d_roff.free()
+                _lib.check(lib.hvd_dev_sync())  # the raw offsets are freed on the way out
         library = cls(d_out_h, d_out_off, d_out_vid, kept.value, V)
         library.d_positions = d_pos
         library._position_limit = int(np.diff(raw_offsets).max()) if V else 0  # every position is below this
@@ -207,20 +242,14 @@ class DeviceLibrary:
         V = raw_offsets.size - 1
         cross = [t for t in transforms if t != "identity"]
         K = len(cross)
-        d_roff = DeviceBuffer.from_array(raw_offsets)
-        d_out_h = DeviceBuffer(32 * max(n, 1))
-        d_out_off = DeviceBuffer(8 * (V + 1))
-        d_out_vid = DeviceBuffer(4 * max(n, 1))
-        d_qh, d_qv, d_qx = (DeviceBuffer(32 * K * max(n, 1)), DeviceBuffer(4 * K * max(n, 1)),
-                            DeviceBuffer(4 * K * max(n, 1))) if K else (None, None, None)
         kept = C.c_int64(0)
-        try:
+        with _DeviceScope() as scope:
+            d_roff, d_out_h, d_out_off, d_out_vid = _compaction_buffers(scope, raw_offsets, n)
+            d_qh, d_qv, d_qx = (scope.keep(DeviceBuffer(size * K * max(n, 1))) if K else None for size in (32, 4, 4))
             _lib.check(lib.hvd_dev_compact_kept_dihedral(
                 d_hashes8_ptr, d_quality_ptr, n, d_roff.ptr, V, int(min_quality), transform_mask(transforms), d_out_h.ptr,
                 d_out_off.ptr, d_out_vid.ptr, d_qh.ptr if K else None, d_qv.ptr if K else None, d_qx.ptr if K else None,
                 C.byref(kept)))
-        finally:
-            d_roff.free()
         library = cls(d_out_h, d_out_off, d_out_vid, kept.value, V)
         queries = DeviceQueries(d_qh, d_qv, d_qx, K * kept.value, K * V, tuple(cross)) if K else None
         return library, queries
@@ -264,7 +293,7 @@ class DeviceLibrary:
     def match_videos(self, max_dist: int | None = None, rank: int = 0, world: int = 1, cap: int | None = None) -> np.ndarray:
         """hvd_dev_vpdq_match_videos: VMATCH_DTYPE records sorted by (a, b); only these cross PCIe."""
         lib = _lib.ensure()
-        max_dist = vpdq.frame_max_dist(search.DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
+        max_dist = _default_max_dist(max_dist)
         if max_dist < 0 or self.n_frames < 2:
             return np.zeros(0, dtype=VMATCH_DTYPE)
         cap = max(4096, self.n_videos) if cap is None else int(cap)
@@ -277,7 +306,7 @@ class DeviceLibrary:
         its own variants (the library's frame -> video map is the target's exclusion map). VMATCH_DTYPE records (a = query
         video v*K + k, b = video) sorted by (a, b); the same record buffer, cap and emit-again retry as match_videos."""
         lib = _lib.ensure()
-        max_dist = vpdq.frame_max_dist(search.DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
+        max_dist = _default_max_dist(max_dist)
         if max_dist < 0 or queries is None or queries.n_frames == 0 or self.n_frames == 0:
             return np.zeros(0, dtype=VMATCH_DTYPE)
         cap = max(4096, queries.n_videos) if cap is None else int(cap)
@@ -294,11 +323,9 @@ class DeviceLibrary:
         are; the pair list goes up, the records come back. Positions: those of from_raw_hashes(positions=True), else the
         index inside the kept video."""
         lib = _lib.ensure()
-        if isinstance(records, np.ndarray) and records.dtype.names:
-            records = np.stack([records["a"], records["b"]], axis=1)
-        pairs = np.ascontiguousarray(np.asarray(records, dtype=np.int64).reshape(-1, 2), dtype=np.uint32)
+        pairs = search.pair_array(records)
         M = pairs.shape[0]
-        max_dist = vpdq.frame_max_dist(search.DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
+        max_dist = _default_max_dist(max_dist)
         out = np.zeros(M, dtype=VALIGN_DTYPE)
         out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
         if M == 0 or max_dist < 0:
@@ -312,25 +339,18 @@ class DeviceLibrary:
         max_bins = min(2 * max(limit, 1) - 1 + 2 * int(slack), _lib.ALIGN_MAX_BINS)
         sb = C.c_size_t(0)
         _lib.check(lib.hvd_align_scratch_bytes(max_bins, C.byref(sb)))
-        bufs = []
-        try:
-            d_pairs = DeviceBuffer.from_array(pairs)
-            bufs.append(d_pairs)
-            d_out = DeviceBuffer(VALIGN_DTYPE.itemsize * M)
-            bufs.append(d_out)
-            d_scr = DeviceBuffer(sb.value) if sb.value else None
-            bufs.append(d_scr)
+        with _DeviceScope() as scope:
+            d_pairs = scope.temp(DeviceBuffer.from_array(pairs))
+            d_out = scope.temp(DeviceBuffer(VALIGN_DTYPE.itemsize * M))
+            d_scr = scope.temp(DeviceBuffer(sb.value) if sb.value else None)
             d_pos = self.d_positions.ptr if self.d_positions is not None else None
             _lib.check(lib.hvd_dev_vpdq_align_videos(self.d_hashes.ptr, self.d_offsets.ptr, self.n_videos, d_pos,
                                                      self.d_hashes.ptr, self.d_offsets.ptr, self.n_videos, d_pos, d_pairs.ptr,
                                                      M, max_dist, int(slack), d_scr.ptr if d_scr else None, sb.value,
                                                      d_out.ptr))
-            return d_out.to_array(VALIGN_DTYPE, M)  # (the copy waits for the library stream)
-        finally:
+            aligned = d_out.to_array(VALIGN_DTYPE, M)  # (the copy waits for the library stream)
             lib.hvd_dev_sync()  # nothing may still run on a buffer that is freed here
-            for b in bufs:
-                if b is not None:
-                    b.free()
+        return aligned
 
     def free(self) -> None:
         for b in (self.d_hashes, self.d_offsets, self.d_video, self.d_img, self.d_positions):
@@ -420,8 +440,8 @@ def release_record_buffers() -> None:
 def shard_frames(raw_offsets: np.ndarray, world: int) -> int:
     """Frames in the longest rank's share (shards are padded to it for the equal-size all-gather)."""
     V = raw_offsets.size - 1
-    return max(int(raw_offsets[video_range_of_rank(V, r, world)[1]] - raw_offsets[video_range_of_rank(V, r, world)[0]])
-               for r in range(world))
+    ranges = (video_range_of_rank(V, r, world) for r in range(world))
+    return max(int(raw_offsets[hi] - raw_offsets[lo]) for lo, hi in ranges)
 
 
 def gather_hash_shards(d_h: DeviceBuffer, d_q: DeviceBuffer, raw_offsets: np.ndarray, rank: int, world: int, exchange,
@@ -435,26 +455,56 @@ def gather_hash_shards(d_h: DeviceBuffer, d_q: DeviceBuffer, raw_offsets: np.nda
     v_lo, v_hi = video_range_of_rank(V, rank, world)
     n_mine = int(raw_offsets[v_hi] - raw_offsets[v_lo])
     shard = max(1, shard_frames(raw_offsets, world))
-    d_all_h, d_all_q = DeviceBuffer(hash_bytes * shard * world), DeviceBuffer(4 * shard * world)
-    d_ph, d_pq = DeviceBuffer(hash_bytes * shard), DeviceBuffer(4 * shard)  # my shard, padded to the longest
-    d_ph.zero()
-    d_pq.zero()
-    _lib.check(lib.hvd_memcpy_d2d(d_ph.ptr, d_h.ptr, hash_bytes * n_mine))
-    _lib.check(lib.hvd_memcpy_d2d(d_pq.ptr, d_q.ptr, 4 * n_mine))
-    exchange.allgather_bytes_dev(d_ph.ptr, d_all_h.ptr, hash_bytes * shard)
-    exchange.allgather_bytes_dev(d_pq.ptr, d_all_q.ptr, 4 * shard)
-    d_fh, d_fq = DeviceBuffer(hash_bytes * max(n_total, 1)), DeviceBuffer(4 * max(n_total, 1))
-    for r in range(world):  # ranks own contiguous video ranges
-        lo, hi = video_range_of_rank(V, r, world)
-        a, b = int(raw_offsets[lo]), int(raw_offsets[hi])
-        if b > a:
-            _lib.check(lib.hvd_memcpy_d2d(d_fh.ptr + hash_bytes * a, d_all_h.ptr + hash_bytes * shard * r,
-                                          hash_bytes * (b - a)))
-            _lib.check(lib.hvd_memcpy_d2d(d_fq.ptr + 4 * a, d_all_q.ptr + 4 * shard * r, 4 * (b - a)))
-    _lib.check(lib.hvd_dev_sync())  # the staging buffers are freed below
-    for buf in (d_all_h, d_all_q, d_ph, d_pq):
-        buf.free()
+    with _DeviceScope() as scope:
+        d_all_h, d_all_q = scope.temp(DeviceBuffer(hash_bytes * shard * world)), scope.temp(DeviceBuffer(4 * shard * world))
+        d_ph, d_pq = scope.temp(DeviceBuffer(hash_bytes * shard)), scope.temp(DeviceBuffer(4 * shard))  # my shard, padded
+        d_ph.zero()
+        d_pq.zero()
+        _lib.check(lib.hvd_memcpy_d2d(d_ph.ptr, d_h.ptr, hash_bytes * n_mine))
+        _lib.check(lib.hvd_memcpy_d2d(d_pq.ptr, d_q.ptr, 4 * n_mine))
+        exchange.allgather_bytes_dev(d_ph.ptr, d_all_h.ptr, hash_bytes * shard)
+        exchange.allgather_bytes_dev(d_pq.ptr, d_all_q.ptr, 4 * shard)
+        d_fh = scope.keep(DeviceBuffer(hash_bytes * max(n_total, 1)))
+        d_fq = scope.keep(DeviceBuffer(4 * max(n_total, 1)))
+        for r in range(world):  # ranks own contiguous video ranges
+            lo, hi = video_range_of_rank(V, r, world)
+            a, b = int(raw_offsets[lo]), int(raw_offsets[hi])
+            if b > a:
+                _lib.check(lib.hvd_memcpy_d2d(d_fh.ptr + hash_bytes * a, d_all_h.ptr + hash_bytes * shard * r,
+                                              hash_bytes * (b - a)))
+                _lib.check(lib.hvd_memcpy_d2d(d_fq.ptr + 4 * a, d_all_q.ptr + 4 * shard * r, 4 * (b - a)))
+        _lib.check(lib.hvd_dev_sync())  # the staging buffers are freed on the way out
     return d_fh, d_fq
+
+
+def _hashed_library(raw_offsets, rank: int, world: int, exchange, hash_stage, hash_bytes: int, compact, timings):
+    """The front half of the chained entries, for one rank: this rank's videos are hashed, the hash shards all-gathered
+    (world > 1), the whole library compacted, the raw hashes freed. The arguments are checked before any device work.
+    hash_stage(mine) -> (d_hashes, d_quality) of this rank's frames, mine = the CSR of its videos counted from 0;
+    hash_bytes: what it writes per frame; compact(d_hashes_ptr, d_quality_ptr, n, raw_offsets) -> returned as it is (a
+    DeviceLibrary.from_raw_* constructor). timings (dict or None): receives gather_ms and compact_ms (host clock)."""
+    raw_offsets = _check_raw_offsets(raw_offsets)
+    if world > 1 and exchange is None:
+        raise ValueError("world > 1 needs the RCCL exchange")
+    v_lo, v_hi = video_range_of_rank(raw_offsets.size - 1, rank, world)
+    d_h, d_q = hash_stage(raw_offsets[v_lo:v_hi + 1] - raw_offsets[v_lo])
+    try:
+        t0 = time.perf_counter()
+        if world > 1:
+            d_fh, d_fq = gather_hash_shards(d_h, d_q, raw_offsets, rank, world, exchange, hash_bytes)
+            d_h.free()
+            d_q.free()
+            d_h, d_q = d_fh, d_fq
+        t1 = time.perf_counter()
+        out = compact(d_h.ptr, d_q.ptr, int(raw_offsets[-1]), raw_offsets)
+        t2 = time.perf_counter()
+    finally:
+        d_h.free()
+        d_q.free()
+    if timings is not None:
+        timings["gather_ms"] = (t1 - t0) * 1e3 if world > 1 else 0.0
+        timings["compact_ms"] = (t2 - t1) * 1e3
+    return out
 
 
 def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
@@ -475,48 +525,21 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
     hvd_dev_pdq_hash_frames_rects over this rank's own videos (`hash_frames_autocrop_on_device`; a rank owns whole videos,
     so every rectangle sees all its frames); timings then also receives rects_ms. Everything after the hash stage is
     unchanged."""
-    import time
     crop = vpdq.autocrop_params(autocrop)
-    raw_offsets = np.ascontiguousarray(raw_offsets, dtype=np.int64)
-    V = raw_offsets.size - 1
-    n_total = int(raw_offsets[-1])
-    v_lo, v_hi = video_range_of_rank(V, rank, world)
-    n_mine = int(raw_offsets[v_hi] - raw_offsets[v_lo])
-    lib = _lib.ensure()
+    timed = _stage_timer(timings)
 
-    def timed(key, fn):
-        if timings is None:
-            return fn()
-        _lib.check(lib.hvd_timer_start())
-        out = fn()
-        ms = C.c_float(0)
-        _lib.check(lib.hvd_timer_stop(C.byref(ms)))
-        timings[key] = float(ms.value)
-        return out
-
-    if crop is not None:
-        mine = raw_offsets[v_lo:v_hi + 1] - raw_offsets[v_lo]
+    def hash_stage(mine):
+        n_mine = int(mine[-1])
+        if crop is None:
+            return timed("hash_ms", lambda: hash_frames_on_device(d_frames_ptr, n_mine, h, w, channels))
         d_h, d_q, d_r = hash_frames_autocrop_on_device(d_frames_ptr, n_mine, h, w, channels, mine, crop[0], crop[1], timed)
         d_r.free()
-    else:
-        d_h, d_q = timed("hash_ms", lambda: hash_frames_on_device(d_frames_ptr, n_mine, h, w, channels))
-    t0 = time.perf_counter()
-    if world > 1:
-        if exchange is None:
-            raise ValueError("world > 1 needs the RCCL exchange")
-        d_fh, d_fq = gather_hash_shards(d_h, d_q, raw_offsets, rank, world, exchange)
-        d_h.free()
-        d_q.free()
-        d_h, d_q = d_fh, d_fq
-    t1 = time.perf_counter()
-    library = DeviceLibrary.from_raw_hashes(d_h.ptr, d_q.ptr, n_total, raw_offsets)
-    t2 = time.perf_counter()
-    d_h.free()
-    d_q.free()
+        return d_h, d_q
+
+    library = _hashed_library(raw_offsets, rank, world, exchange, hash_stage, 32, DeviceLibrary.from_raw_hashes, timings)
     recs = timed("search_ms", lambda: library.match_videos(rank=rank, world=world))
     if timings is not None:
-        timings["gather_ms"] = (t1 - t0) * 1e3 if world > 1 else 0.0
-        timings["compact_ms"] = (t2 - t1) * 1e3
+        lib = _lib.ensure()
         us = C.c_int(0)
         for key in ("local", "exchange", "fold"):
             _lib.check(lib.hvd_debug_get(f"vmatch_us_{key}".encode(), C.byref(us)))
@@ -537,14 +560,9 @@ def find_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
     positions=False aligns on the index inside the KEPT video instead: a frame the quality filter dropped then shifts
     everything after it (kept for comparison; the default is what a caller wants).
     -> (excerpts, search records, alignment records, library or None); Excerpt offsets / first / last are raw frame indices."""
-    raw_offsets = _check_raw_offsets(raw_offsets)
-    n = int(raw_offsets[-1])
-    d_h, d_q = hash_frames_on_device(d_frames_ptr, n, h, w, channels)
-    try:
-        library = DeviceLibrary.from_raw_hashes(d_h.ptr, d_q.ptr, n, raw_offsets, positions=bool(positions))
-    finally:
-        d_h.free()
-        d_q.free()
+    library = _hashed_library(
+        raw_offsets, 0, 1, None, lambda mine: hash_frames_on_device(d_frames_ptr, int(mine[-1]), h, w, channels), 32,
+        lambda *raw: DeviceLibrary.from_raw_hashes(*raw, positions=bool(positions)), None)
     try:
         recs = library.match_videos()
         aligned = library.align(recs, slack=slack)
@@ -559,6 +577,23 @@ def find_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
     return out, recs, aligned, None
 
 
+def _rank0_of_every_context(entry, frames_of_rank, timings, n_results: int, *args, **kwargs):
+    """entry(frames_of_rank(rank, world), *args, rank, world, exchange, timings, **kwargs) on one thread per context of the
+    in-process device group, rank = context index. -> the first n_results values rank 0 returned (every rank computes the
+    same); timings receives rank 0's stage times."""
+    from . import multigpu
+
+    def one(rank, world):
+        ex = multigpu.GroupExchange(rank, world) if world > 1 else None
+        tm = {} if timings is not None and rank == 0 else None
+        out = entry(frames_of_rank(rank, world), *args, rank=rank, world=world, exchange=ex, timings=tm, **kwargs)
+        if tm is not None:
+            timings.update(tm)
+        return out[:n_results]
+
+    return multigpu.run_on_contexts(one)[0]
+
+
 def dedupe_frames_in_process(frames_of_rank, raw_offsets: np.ndarray, h: int, w: int, channels: int,
                              threshold: float = 50.0, policy: str | None = None, timings: dict | None = None, autocrop=None):
     """BASELINE config 5 on the library's in-process device group (hvd_init_devices / HVD_DEVICES), no launcher:
@@ -566,21 +601,9 @@ def dedupe_frames_in_process(frames_of_rank, raw_offsets: np.ndarray, h: int, w:
     device pointer of the frames of that rank's video range (`video_range_of_rank`), resident on that rank's device (it is
     called on the rank's thread, with the rank's context current). -> (pairs, records) -- every rank computes the same;
     rank 0's are returned. timings: rank 0's stage times. autocrop: as `dedupe_frames_on_device`."""
-    from . import multigpu
-
     vpdq.autocrop_params(autocrop)  # a bad value fails here, not on every rank's thread
-
-    def one(rank, world):
-        ex = multigpu.GroupExchange(rank, world) if world > 1 else None
-        tm = {} if timings is not None and rank == 0 else None
-        pairs, recs, _ = dedupe_frames_on_device(frames_of_rank(rank, world), raw_offsets, h, w, channels, threshold, policy,
-                                                 rank, world, ex, timings=tm, autocrop=autocrop)
-        if tm is not None:
-            timings.update(tm)
-        return pairs, recs
-
-    results = multigpu.run_on_contexts(one)
-    return results[0]
+    return _rank0_of_every_context(dedupe_frames_on_device, frames_of_rank, timings, 2, raw_offsets, h, w, channels,
+                                   threshold, policy, autocrop=autocrop)
 
 
 def dedupe_transformed_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
@@ -595,42 +618,15 @@ def dedupe_transformed_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarr
     -> (pairs int64[m,2], transform int64[m] (vpdq.TRANSFORMS index), similarity float64[m], identity records, cross
     records, identity library or None). Every rank returns the same result. timings (optional dict): hash_ms, search_ms
     and cross_ms (HIP events on the library stream), gather_ms and compact_ms (host clock, as in dedupe_frames_on_device)."""
-    import time
     names = search.transform_set(transforms)
     cross = [t for t in names if t != "identity"]
     if int(threshold) < 1:
         raise ValueError("threshold < 1 would select every pair of videos")
-    raw_offsets = _check_raw_offsets(raw_offsets)
-    V = raw_offsets.size - 1
-    n_total = int(raw_offsets[-1])
-    if world > 1 and exchange is None:
-        raise ValueError("world > 1 needs the RCCL exchange")
-    v_lo, v_hi = video_range_of_rank(V, rank, world)
-    n_mine = int(raw_offsets[v_hi] - raw_offsets[v_lo])
-    lib = _lib.ensure()
-
-    def timed(key, fn):
-        if timings is None:
-            return fn()
-        _lib.check(lib.hvd_timer_start())
-        out = fn()
-        ms = C.c_float(0)
-        _lib.check(lib.hvd_timer_stop(C.byref(ms)))
-        timings[key] = float(ms.value)
-        return out
-
-    d_h, d_q = timed("hash_ms", lambda: hash_frames_dihedral_on_device(d_frames_ptr, n_mine, h, w, channels))
-    t0 = time.perf_counter()
-    if world > 1:
-        d_fh, d_fq = gather_hash_shards(d_h, d_q, raw_offsets, rank, world, exchange, hash_bytes=256)
-        d_h.free()
-        d_q.free()
-        d_h, d_q = d_fh, d_fq
-    t1 = time.perf_counter()
-    library, queries = DeviceLibrary.from_raw_dihedral(d_h.ptr, d_q.ptr, n_total, raw_offsets, names)
-    t2 = time.perf_counter()
-    d_h.free()
-    d_q.free()
+    timed = _stage_timer(timings)
+    library, queries = _hashed_library(
+        raw_offsets, rank, world, exchange,
+        lambda mine: timed("hash_ms", lambda: hash_frames_dihedral_on_device(d_frames_ptr, int(mine[-1]), h, w, channels)), 256,
+        lambda *raw: DeviceLibrary.from_raw_dihedral(*raw, names), timings)
     try:
         # the identity records are read back before the cross search: emit-again state belongs to the last search only
         recs_i = timed("search_ms", lambda: library.match_videos(rank=rank, world=world))
@@ -640,8 +636,6 @@ def dedupe_transformed_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarr
         if queries is not None:
             queries.free()
     if timings is not None:
-        timings["gather_ms"] = (t1 - t0) * 1e3 if world > 1 else 0.0
-        timings["compact_ms"] = (t2 - t1) * 1e3
         timings.setdefault("cross_ms", 0.0)
     pairs, tid, sim = search.fold_transformed_records(recs_i, recs_c, library.lengths(),
                                                       [vpdq.TRANSFORMS.index(t) for t in cross], threshold, policy,
@@ -658,20 +652,9 @@ def dedupe_transformed_frames_in_process(frames_of_rank, raw_offsets: np.ndarray
     """`dedupe_frames_in_process` for `dedupe_transformed_frames_on_device`: one thread per context of the in-process
     device group, rank = context index, frames_of_rank(rank, world) as there. -> rank 0's (pairs, transform, similarity,
     identity records, cross records); every rank computes the same. timings: rank 0's stage times."""
-    from . import multigpu
-
     names = search.transform_set(transforms)  # a bad set fails here, not on every rank's thread
-
-    def one(rank, world):
-        ex = multigpu.GroupExchange(rank, world) if world > 1 else None
-        tm = {} if timings is not None and rank == 0 else None
-        out = dedupe_transformed_frames_on_device(frames_of_rank(rank, world), raw_offsets, h, w, channels, threshold,
-                                                  policy, names, rank, world, ex, timings=tm)
-        if tm is not None:
-            timings.update(tm)
-        return out[:5]
-
-    return multigpu.run_on_contexts(one)[0]
+    return _rank0_of_every_context(dedupe_transformed_frames_on_device, frames_of_rank, timings, 5, raw_offsets, h, w,
+                                   channels, threshold, policy, names)
 
 
 def video_range_of_rank(V: int, rank: int, world: int) -> tuple[int, int]:

@@ -11,7 +11,6 @@ db/vptree.py:431-441); this module computes it exactly.
 
 from __future__ import annotations
 
-import ctypes as C
 from collections import namedtuple
 
 import numpy as np
@@ -33,6 +32,23 @@ def calculate_distance(phash_a: bytes, phash_b: bytes) -> int:
     return fix_vpdq_similarity(vpdq.matchHashBytes(phash_a, phash_b, DISTANCE_TOLERANCE))
 
 
+def _library(frames, offsets, positions=None):
+    """A host library as the C-ABI takes it: hashes uint8[sum,32], CSR offsets int64[V+1] (/ positions int32[sum])."""
+    frames = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1, 32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offsets.size < 1 or offsets[-1] != frames.shape[0]:
+        raise ValueError("offsets[-1] must equal the number of frame hashes")
+    if positions is not None:
+        positions = np.ascontiguousarray(positions, dtype=np.int32)
+        if positions.shape != (frames.shape[0],):
+            raise ValueError("positions must hold one int32 per frame hash")
+    return frames, offsets, positions
+
+
+def _ptr(x):
+    return x.ctypes.data if x is not None and x.size else None
+
+
 def allpairs_hamming(db: np.ndarray, max_dist: int = DISTANCE_TOLERANCE, group: np.ndarray | None = None,
                      cap: int | None = None) -> np.ndarray:
     """All i<j with hamming(db[i], db[j]) <= max_dist (and group[i] != group[j] if given),
@@ -44,43 +60,25 @@ def allpairs_hamming(db: np.ndarray, max_dist: int = DISTANCE_TOLERANCE, group: 
         if group.shape != (n,):
             raise ValueError("group must have one int32 per hash")
     lib = _lib.ensure()
-    cap = max(1024, n // 4) if cap is None else int(cap)
-    while True:
-        out = np.zeros(max(cap, 1), dtype=PAIR_DTYPE)
-        cnt = C.c_int64(0)
-        rc = lib.hvd_allpairs_hamming256(db.ctypes.data if n else None, n,
-                                         group.ctypes.data if group is not None else None, int(max_dist),
-                                         out.ctypes.data, cap, C.byref(cnt))
-        if rc == _lib.HVD_ERR_OVERFLOW:  # reported, never truncated: retry with the exact size
-            cap = int(cnt.value)
-            continue
-        _lib.check(rc)
-        return out[: cnt.value].copy()
+    return _lib.records_with_retry(
+        lambda out, cap_, cnt: lib.hvd_allpairs_hamming256(db.ctypes.data if n else None, n,
+                                                           group.ctypes.data if group is not None else None, int(max_dist),
+                                                           out, cap_, cnt),
+        PAIR_DTYPE, max(1024, n // 4) if cap is None else int(cap))
 
 
 def match_videos(frames: np.ndarray, offsets: np.ndarray, max_dist: int = DISTANCE_TOLERANCE,
                  cap: int | None = None) -> np.ndarray:
     """Every video pair a<b with at least one frame hit, with its vPDQ counters, as a
     VMATCH_DTYPE array sorted by (a, b). frames: uint8[sum,32]; offsets: int64[V+1] (CSR)."""
-    frames = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1, 32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    frames, offsets, _ = _library(frames, offsets)
     V = offsets.size - 1
-    if V < 0 or (V >= 0 and offsets[-1] != frames.shape[0]):
-        raise ValueError("offsets[-1] must equal the number of frame hashes")
     if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
         return np.zeros(0, dtype=VMATCH_DTYPE)
     lib = _lib.ensure()
-    cap = max(1024, V) if cap is None else int(cap)
-    while True:
-        out = np.zeros(max(cap, 1), dtype=VMATCH_DTYPE)
-        cnt = C.c_int64(0)
-        rc = lib.hvd_vpdq_match_videos(frames.ctypes.data if frames.size else None, offsets.ctypes.data, V,
-                                       int(max_dist), out.ctypes.data, cap, C.byref(cnt))
-        if rc == _lib.HVD_ERR_OVERFLOW:
-            cap = int(cnt.value)
-            continue
-        _lib.check(rc)
-        return out[: cnt.value].copy()
+    return _lib.records_with_retry(
+        lambda out, cap_, cnt: lib.hvd_vpdq_match_videos(_ptr(frames), offsets.ctypes.data, V, int(max_dist), out, cap_, cnt),
+        VMATCH_DTYPE, max(1024, V) if cap is None else int(cap))
 
 
 def match_videos_cross(frames_q: np.ndarray, offsets_q: np.ndarray, frames_t: np.ndarray, offsets_t: np.ndarray,
@@ -89,13 +87,9 @@ def match_videos_cross(frames_q: np.ndarray, offsets_q: np.ndarray, frames_t: np
     """Query videos x target videos (batch form of VpTreeManager.search_file, db/vptree.py:865-902):
     VMATCH_DTYPE records (a = query index, b = target index) with >= 1 frame hit, sorted by (a, b).
     ids_q/ids_t (int32 per video): equal ids are never compared (a query that is in the target set)."""
-    frames_q = np.ascontiguousarray(frames_q, dtype=np.uint8).reshape(-1, 32)
-    frames_t = np.ascontiguousarray(frames_t, dtype=np.uint8).reshape(-1, 32)
-    offsets_q = np.ascontiguousarray(offsets_q, dtype=np.int64)
-    offsets_t = np.ascontiguousarray(offsets_t, dtype=np.int64)
+    frames_q, offsets_q, _ = _library(frames_q, offsets_q)
+    frames_t, offsets_t, _ = _library(frames_t, offsets_t)
     VQ, VT = offsets_q.size - 1, offsets_t.size - 1
-    if offsets_q[-1] != frames_q.shape[0] or offsets_t[-1] != frames_t.shape[0]:
-        raise ValueError("offsets[-1] must equal the number of frame hashes")
     if (ids_q is None) != (ids_t is None):
         raise ValueError("pass both id arrays or neither")
     if ids_q is not None:
@@ -106,31 +100,27 @@ def match_videos_cross(frames_q: np.ndarray, offsets_q: np.ndarray, frames_t: np
     if max_dist < 0:
         return np.zeros(0, dtype=VMATCH_DTYPE)
     lib = _lib.ensure()
-    cap = max(1024, VQ) if cap is None else int(cap)
-    while True:
-        out = np.zeros(max(cap, 1), dtype=VMATCH_DTYPE)
-        cnt = C.c_int64(0)
-        rc = lib.hvd_vpdq_match_videos_cross(
-            frames_q.ctypes.data if frames_q.size else None, offsets_q.ctypes.data, VQ,
-            ids_q.ctypes.data if ids_q is not None else None,
-            frames_t.ctypes.data if frames_t.size else None, offsets_t.ctypes.data, VT,
-            ids_t.ctypes.data if ids_t is not None else None, int(max_dist), out.ctypes.data, cap, C.byref(cnt))
-        if rc == _lib.HVD_ERR_OVERFLOW:
-            cap = int(cnt.value)
-            continue
-        _lib.check(rc)
-        return out[: cnt.value].copy()
+    return _lib.records_with_retry(
+        lambda out, cap_, cnt: lib.hvd_vpdq_match_videos_cross(
+            _ptr(frames_q), offsets_q.ctypes.data, VQ, ids_q.ctypes.data if ids_q is not None else None,
+            _ptr(frames_t), offsets_t.ctypes.data, VT, ids_t.ctypes.data if ids_t is not None else None, int(max_dist),
+            out, cap_, cnt),
+        VMATCH_DTYPE, max(1024, VQ) if cap is None else int(cap))
 
 
 def similarity_of_records(records: np.ndarray, lengths: np.ndarray, policy: str | None = None) -> np.ndarray:
     """Per-record similarity in [0,100] under the match policy, taking the better of the two
     search directions (the reference finds {A,B} from A's search or from B's)."""
+    return similarity_of_hits(records["q_hits"], records["t_hits"], lengths[records["a"]], lengths[records["b"]], policy)
+
+
+def similarity_of_hits(q_hits, t_hits, na, nb, policy: str | None = None) -> np.ndarray:
+    """similarity_of_records on its columns: the two hit counters and the frame counts na / nb of the two videos."""
     policy = vpdq.MATCH_POLICY if policy is None else policy
-    na = lengths[records["a"]].astype(np.float64)
-    nb = lengths[records["b"]].astype(np.float64)
+    na, nb = na.astype(np.float64), nb.astype(np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
-        qp = np.where(na > 0, records["q_hits"] * 100.0 / na, 0.0)
-        tp = np.where(nb > 0, records["t_hits"] * 100.0 / nb, 0.0)
+        qp = np.where(na > 0, q_hits * 100.0 / na, 0.0)
+        tp = np.where(nb > 0, t_hits * 100.0 / nb, 0.0)
     if policy == "min":
         return np.minimum(qp, tp)
     if policy in ("max", "query", "target"):
@@ -148,19 +138,30 @@ def similar_video_pairs(records: np.ndarray, lengths: np.ndarray, threshold: flo
     return np.stack([records["a"][keep], records["b"][keep]], axis=1).astype(np.int64)
 
 
+def hash_blob(phash, what: str = "phash") -> bytes:
+    """VpdqHash or bytes -> the hash bytes: 32 per frame."""
+    blob = phash.bytes if isinstance(phash, vpdq.VpdqHash) else bytes(phash)
+    if len(blob) % 32:
+        raise ValueError(f"{what} length not a multiple of 32")
+    return blob
+
+
+def pack_hashes(hashes) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """A sequence of VpdqHash / bytes as one library: (frames uint8[n,32] (a read-only view), CSR offsets int64[V+1],
+    lengths int64[V])."""
+    blobs = [hash_blob(h) for h in hashes]
+    lengths = np.array([len(b) // 32 for b in blobs], dtype=np.int64)
+    offsets = np.zeros(len(blobs) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=offsets[1:])
+    return np.frombuffer(b"".join(blobs), dtype=np.uint8).reshape(-1, 32), offsets, lengths
+
+
 def find_potential_duplicates(video_hashes, threshold: float = 50.0, policy: str | None = None) -> list[tuple[int, int]]:
     """Counterpart of HydrusVideoDeduplicator.find_potential_duplicates (dedup.py:445-502)
     for an in-memory library: video_hashes is a sequence of VpdqHash / bytes; returns the
     sorted list of index pairs (a < b) that the reference would mark as potential
     duplicates (threshold default 50, entrypoint.py:55-57)."""
-    blobs = [h.bytes if isinstance(h, vpdq.VpdqHash) else bytes(h) for h in video_hashes]
-    for b in blobs:
-        if len(b) % 32:
-            raise ValueError("phash length not a multiple of 32")
-    lengths = np.array([len(b) // 32 for b in blobs], dtype=np.int64)
-    offsets = np.zeros(len(blobs) + 1, dtype=np.int64)
-    np.cumsum(lengths, out=offsets[1:])
-    frames = np.frombuffer(b"".join(blobs), dtype=np.uint8).reshape(-1, 32)
+    frames, offsets, lengths = pack_hashes(video_hashes)
     recs = match_videos(frames, offsets, vpdq.frame_max_dist(DISTANCE_TOLERANCE))
     pairs = similar_video_pairs(recs, lengths, threshold, policy)
     return [(int(a), int(b)) for a, b in pairs]
@@ -251,19 +252,13 @@ def find_transformed_duplicates(variant_hashes, threshold: float = 50.0, policy:
     names = transform_set(transforms)
     cross = [t for t in names if t != "identity"]
 
-    def blob(x):
-        b = x.bytes if isinstance(x, vpdq.VpdqHash) else bytes(x)
-        if len(b) % 32:
-            raise ValueError("phash length not a multiple of 32")
-        return b
-
     ident, var = [], []
     for v, d in enumerate(variant_hashes):
         missing = [t for t in names if t not in d]
         if missing:
             raise ValueError(f"video {v} has no hash for transform(s) {missing}")
-        ident.append(blob(d["identity"]))
-        vb = [blob(d[t]) for t in cross]
+        ident.append(hash_blob(d["identity"]))
+        vb = [hash_blob(d[t]) for t in cross]
         if any(len(b) != len(ident[-1]) for b in vb):
             raise ValueError(f"video {v}: the variants must hash the same frames as the identity")
         var.extend(vb)
@@ -284,16 +279,11 @@ def transformed_pairs(ident: list, var: list, cross, threshold: float = 50.0, po
     V = len(ident)
     if V == 0:
         return np.zeros((0, 2), np.int64), np.zeros(0, np.int64), np.zeros(0, np.float64)
-    lengths = np.array([len(b) // 32 for b in ident], dtype=np.int64)
-    offsets = np.zeros(V + 1, dtype=np.int64)
-    np.cumsum(lengths, out=offsets[1:])
-    frames = np.frombuffer(b"".join(ident), dtype=np.uint8).reshape(-1, 32)
+    frames, offsets, lengths = pack_hashes(ident)
     max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
     recs_i = mv(frames, offsets, max_dist)
     if K:
-        offsets_q = np.zeros(V * K + 1, dtype=np.int64)
-        np.cumsum(np.repeat(lengths, K), out=offsets_q[1:])
-        frames_q = np.frombuffer(b"".join(var), dtype=np.uint8).reshape(-1, 32)
+        frames_q, offsets_q, _ = pack_hashes(var)  # (var[v * K + k] is as long as ident[v])
         vids = np.arange(V, dtype=np.int32)
         recs_c = mvc(frames_q, offsets_q, frames, offsets, ids_q=np.repeat(vids, K), ids_t=vids, max_dist=max_dist)
     else:
@@ -307,16 +297,14 @@ def transformed_pairs(ident: list, var: list, cross, threshold: float = 50.0, po
 ALIGN_SLACK = 1  # frames a hit may lie off the best offset and still count as aligned (a dropped or doubled frame)
 
 
-def _library(frames, offsets, positions):
-    frames = np.ascontiguousarray(frames, dtype=np.uint8).reshape(-1, 32)
-    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-    if offsets.size < 1 or offsets[-1] != frames.shape[0]:
-        raise ValueError("offsets[-1] must equal the number of frame hashes")
-    if positions is not None:
-        positions = np.ascontiguousarray(positions, dtype=np.int32)
-        if positions.shape != (frames.shape[0],):
-            raise ValueError("positions must hold one int32 per frame hash")
-    return frames, offsets, positions
+def pair_array(pairs) -> np.ndarray:
+    """VMATCH records (their a, b) or int[M, 2] -> uint32[M, 2], as the alignment entries take their pair list."""
+    if isinstance(pairs, np.ndarray) and pairs.dtype.names:
+        pairs = np.stack([pairs["a"], pairs["b"]], axis=1)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= 1 << 32):
+        raise ValueError("pair index out of range")
+    return np.ascontiguousarray(pairs, dtype=np.uint32)
 
 
 def align_videos(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.ndarray | None = None,
@@ -337,12 +325,7 @@ def align_videos(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.n
         frames_t, offsets_t, positions_t = frames, offsets, positions
     else:
         frames_t, offsets_t, positions_t = _library(frames_t, offsets_t, positions_t)
-    if isinstance(pairs, np.ndarray) and pairs.dtype.names:
-        pairs = np.stack([pairs["a"], pairs["b"]], axis=1)
-    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    if pairs.size and (pairs.min() < 0 or pairs.max() >= 1 << 32):
-        raise ValueError("pair index out of range")
-    pairs = np.ascontiguousarray(pairs, dtype=np.uint32)
+    pairs = pair_array(pairs)
     max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
     M = pairs.shape[0]
     out = np.zeros(M, dtype=VALIGN_DTYPE)
@@ -350,10 +333,9 @@ def align_videos(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.n
     if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
         return out
     lib = _lib.ensure()
-    ptr = lambda x: x.ctypes.data if x is not None and x.size else None  # noqa: E731
-    _lib.check(lib.hvd_vpdq_align_videos(ptr(frames), offsets.ctypes.data, offsets.size - 1, ptr(positions), ptr(frames_t),
-                                         offsets_t.ctypes.data, offsets_t.size - 1, ptr(positions_t), ptr(pairs), M, max_dist,
-                                         int(slack), ptr(out)))
+    _lib.check(lib.hvd_vpdq_align_videos(_ptr(frames), offsets.ctypes.data, offsets.size - 1, _ptr(positions), _ptr(frames_t),
+                                         offsets_t.ctypes.data, offsets_t.size - 1, _ptr(positions_t), _ptr(pairs), M,
+                                         max_dist, int(slack), _ptr(out)))
     return out
 
 
@@ -391,10 +373,7 @@ def excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, sl
     positions: None, or one int sequence per video). matcher: object with match_videos / align_videos (default: the GPU
     entry points of this module). -> excerpts_from_records(...)."""
     mv, al = (match_videos, align_videos) if matcher is None else (matcher.match_videos, matcher.align_videos)
-    lengths = np.array([len(b) // 32 for b in blobs], dtype=np.int64)
-    offsets = np.zeros(len(blobs) + 1, dtype=np.int64)
-    np.cumsum(lengths, out=offsets[1:])
-    frames = np.frombuffer(b"".join(blobs), dtype=np.uint8).reshape(-1, 32)
+    frames, offsets, lengths = pack_hashes(blobs)
     pos = None
     if positions is not None:
         if len(positions) != len(blobs) or any(len(p) != n for p, n in zip(positions, lengths)):
@@ -420,8 +399,4 @@ def find_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, s
     min_aligned = 4 is a POLICY DEFAULT of this project, not a rule of the reference (which has no excerpt search): fewer
     than four frames in a row are as likely a shared title card as a clip. slack: how far a hit may lie off the offset and
     still count (one dropped or doubled frame at the default 1)."""
-    blobs = [h.bytes if isinstance(h, vpdq.VpdqHash) else bytes(h) for h in video_hashes]
-    for b in blobs:
-        if len(b) % 32:
-            raise ValueError("phash length not a multiple of 32")
-    return excerpt_pairs(blobs, threshold, min_aligned, slack, positions)
+    return excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, positions)

@@ -100,9 +100,7 @@ def ingest_phashed_file_queue(conn: sqlite3.Connection, tree=None) -> int:
     searched), and the queue row is deleted. `tree`: a VpTreeManager facade to notify (add_leaf). -> files ingested."""
     rows = conn.execute("SELECT file_hash, phash FROM phashed_file_queue").fetchall()
     for file_hash, phash in rows:
-        blob = convert_old_vpdq_to_new(phash) if is_old_format(phash) else bytes(phash)
-        if len(blob) % 32:
-            raise ValueError("queued phash length is not a multiple of 32")
+        blob = search.hash_blob(convert_old_vpdq_to_new(phash) if is_old_format(phash) else phash, "queued phash")
         conn.execute("INSERT OR IGNORE INTO files ( file_hash ) VALUES ( ? )", (file_hash,))
         row = conn.execute("SELECT phash_id FROM shape_perceptual_hashes WHERE phash = ?", (blob,)).fetchone()
         if row is None:
@@ -146,13 +144,9 @@ def load_library(conn: sqlite3.Connection) -> Library:
     phash_ids = np.array([r[0] for r in phash_rows], dtype=np.int64)
     index_of = {int(pid): k for k, pid in enumerate(phash_ids)}
     # a pre-0.10 database is read through the reference's own conversion (upgrade_old_phashes rewrites it in place)
-    blobs = [convert_old_vpdq_to_new(r[1]) if is_old_format(r[1]) else bytes(r[1]) for r in phash_rows]
-    for b in blobs:
-        if len(b) % 32:
-            raise ValueError("phash BLOB length is not a multiple of 32")
-    offsets = np.zeros(len(blobs) + 1, dtype=np.int64)
-    np.cumsum([len(b) // 32 for b in blobs], out=offsets[1:])
-    frames = np.frombuffer(b"".join(blobs), dtype=np.uint8).reshape(-1, 32).copy()
+    frames, offsets, _ = search.pack_hashes(convert_old_vpdq_to_new(r[1]) if is_old_format(r[1]) else r[1]
+                                            for r in phash_rows)
+    frames = frames.copy()  # (writable, and not a view of the joined blobs)
     return Library(
         hash_ids=np.array([r[0] for r in rows], dtype=np.int64),
         file_hashes=[r[1] for r in rows],
@@ -208,12 +202,7 @@ def find_potential_duplicates(conn: sqlite3.Connection, threshold: float = 50.0,
                                           ids_q=q_sel.astype(np.int32), ids_t=np.arange(P, dtype=np.int32),
                                           max_dist=search.vpdq.frame_max_dist(search.DISTANCE_TOLERANCE))
         a_idx, b_idx = q_sel[recs["a"].astype(np.int64)], recs["b"].astype(np.int64)
-    na, nb = lengths[a_idx].astype(np.float64), lengths[b_idx].astype(np.float64)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        qp = np.where(na > 0, recs["q_hits"] * 100.0 / na, 0.0)
-        tp = np.where(nb > 0, recs["t_hits"] * 100.0 / nb, 0.0)
-    pol = search.vpdq.MATCH_POLICY if policy is None else policy
-    sim = np.minimum(qp, tp) if pol == "min" else np.maximum(qp, tp)
+    sim = search.similarity_of_hits(recs["q_hits"], recs["t_hits"], lengths[a_idx], lengths[b_idx], policy)
     keep = sim.astype(np.int64) >= int(threshold)  # <=> fix_vpdq_similarity(sim) <= search_threshold
 
     phash_pairs = {}
@@ -271,10 +260,7 @@ def store_transformed_hashes(conn: sqlite3.Connection, variants: dict) -> bytes:
     for name, h in variants.items():
         if name not in vpdq.TRANSFORMS:
             raise ValueError(f"unknown transform {name!r}; expected names from {vpdq.TRANSFORMS}")
-        b = h.bytes if isinstance(h, vpdq.VpdqHash) else bytes(h)
-        if len(b) % 32:
-            raise ValueError(f"{name}: phash length not a multiple of 32")
-        blobs[name] = b
+        blobs[name] = search.hash_blob(h, f"{name}: phash")
     ident = blobs.pop("identity")
     for name, b in blobs.items():
         if len(b) != len(ident):

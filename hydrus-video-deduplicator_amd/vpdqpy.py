@@ -68,12 +68,8 @@ class Vpdq:
         offset p_b = p_a + offset, aligned frames per side and their first / last index). VpdqHash or bytes."""
         from . import search
 
-        blobs = [h.bytes if isinstance(h, VpdqHash) else bytes(h) for h in (phash_a, phash_b)]
-        if any(len(b) % 32 for b in blobs):
-            raise ValueError("phash length not a multiple of 32")
-        na, nb = len(blobs[0]) // 32, len(blobs[1]) // 32
-        frames = np.frombuffer(blobs[0] + blobs[1], dtype=np.uint8).reshape(-1, 32)
-        return search.align_videos(frames, np.array([0, na, na + nb], dtype=np.int64), [(0, 1)], slack=slack)[0]
+        frames, offsets, _ = search.pack_hashes((phash_a, phash_b))
+        return search.align_videos(frames, offsets, [(0, 1)], slack=slack)[0]
 
     select_frames = staticmethod(select_frames)
 

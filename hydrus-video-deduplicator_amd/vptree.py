@@ -260,8 +260,7 @@ class VpTreeManager:
 
     # ---- library + cached GPU pass ------------------------------------------------------------------------------
     def _append(self, phash_id: int, blob: bytes) -> None:
-        if len(blob) % vpdq.BYTES_PER_PDQ_HASH:
-            raise ValueError("phash BLOB length is not a multiple of 32")
+        blob = search.hash_blob(blob, "phash BLOB")
         self._index[phash_id] = len(self._phash_ids)
         self._phash_ids.append(phash_id)
         self._blobs.append(blob)
@@ -274,11 +273,7 @@ class VpTreeManager:
             self._append(int(phash_id), bytes(blob))
 
     def _csr(self, lo: int, hi: int):
-        lens = np.fromiter((len(b) // 32 for b in self._blobs[lo:hi]), dtype=np.int64, count=hi - lo)
-        off = np.zeros(lens.size + 1, dtype=np.int64)
-        np.cumsum(lens, out=off[1:])
-        data = b"".join(self._blobs[lo:hi])
-        return np.frombuffer(data, dtype=np.uint8).reshape(-1, 32), off, lens
+        return search.pack_hashes(self._blobs[lo:hi])
 
     def _fold(self, a, b, q_hits, t_hits, lens, keep_old: bool) -> None:
         """Video-level records (positions a, b; the kernel's two counters) -> directed neighbour lists, all in numpy."""
@@ -464,12 +459,7 @@ class VpTreeManager:
             hits.extend(self._similar_positions(p, max_hamming_distance))
         foreign = [b for b in foreign if len(b)]
         if foreign and self._blobs:  # one rectangular pass: the foreign hashes as queries against the whole library
-            if any(len(b) % vpdq.BYTES_PER_PDQ_HASH for b in foreign):
-                raise ValueError("phash BLOB length is not a multiple of 32")
-            lens = np.array([len(b) // 32 for b in foreign], dtype=np.int64)
-            oq = np.zeros(lens.size + 1, dtype=np.int64)
-            np.cumsum(lens, out=oq[1:])
-            fq = np.frombuffer(b"".join(foreign), dtype=np.uint8).reshape(-1, 32)
+            fq, oq, lens = search.pack_hashes(foreign)
             ft, ot, lt = self._csr(0, len(self._blobs))
             recs = self._matcher.match_videos_cross(fq, oq, ft, ot, max_dist=vpdq.frame_max_dist(search.DISTANCE_TOLERANCE))
             if len(recs):

@@ -129,6 +129,18 @@ def test_sqlite_adapter_with_oracle_matcher(hvd, oracle):
     check_scenario(hvd, oracle, OracleMatcher(oracle))
 
 
+def test_unknown_policy_is_rejected_as_in_search(hvd, oracle):
+    from hvd_amd import sqlite_adapter as A
+
+    conn, _ = build_db(hvd)
+    with pytest.raises(ValueError, match="unknown match policy"):
+        A.find_potential_duplicates(conn, 50.0, policy="median", matcher=OracleMatcher(oracle))
+    # the accepted names still give what search.similarity_of_records gives them
+    for policy in ("min", "max", "query", "target"):
+        pairs, _ = A.find_potential_duplicates(conn, 50.0, policy=policy, matcher=OracleMatcher(oracle), update_cache=False)
+        assert pairs
+
+
 @pytest.mark.gpu
 def test_sqlite_adapter_on_gpu(gpu, hvd, oracle):
     check_scenario(hvd, oracle, None)

@@ -138,6 +138,10 @@ def test_entry_rejects_bad_arguments_before_any_device_call(hvd, monkeypatch, kw
     raw = args.pop("raw_offsets")
     with pytest.raises(ValueError, match=match):
         hvd.pipeline.dedupe_transformed_frames_on_device(0, raw, 64, 64, 1, **args)
+    if match in ("raw_offsets", "exchange"):  # the plain entry makes the same two checks, as early
+        args.pop("transforms")
+        with pytest.raises(ValueError, match=match):
+            hvd.pipeline.dedupe_frames_on_device(0, raw, 64, 64, 1, **args)
 
 
 def test_public_entry_is_exported(hvd):
