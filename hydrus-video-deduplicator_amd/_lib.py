@@ -72,6 +72,8 @@ SIGNATURES = {
     "hvd_hasher_destroy": (_int, [_vp]),
     "hvd_hasher_create_dihedral": (_int, [_int, _int, _int, _i64, C.POINTER(_vp)]),
     "hvd_hasher_finish_dihedral": (_int, [_vp, _vp, _vp, _i64, C.POINTER(_i64)]),
+    "hvd_hasher_create_autocrop": (_int, [_int, _int, _int, _i64, _int, _int, _i64, C.POINTER(_vp)]),
+    "hvd_hasher_finish_autocrop": (_int, [_vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "hvd_dev_malloc": (_int, [C.POINTER(_vp), _sz]),
     "hvd_dev_free": (_int, [_vp]),
     "hvd_host_malloc": (_int, [C.POINTER(_vp), _sz]),

@@ -693,6 +693,10 @@ int hvd_debug_set(const char* key, int value) {
         hvd::g_pdq_fused_down512 = value != 0;
         return HVD_OK;
     }
+    if (strcmp(key, "pdq_fused_rect") == 0) {  // content-rectangle down-sampler, frames up to 512 x 512: 1 fused kernel (default), 0 the generic passes
+        hvd::g_pdq_fused_rect = value != 0;
+        return HVD_OK;
+    }
     if (strcmp(key, "match_server") == 0) {  // hvd_match_two, small operands: 1 resident match server (default), 0 one launch per call
         g_match_server = value != 0;
         return HVD_OK;
@@ -836,6 +840,29 @@ hipError_t api_launch_hash(const void* d_frames, int64_t n, int h, int w, int ch
                            void* d_quality, hipStream_t s, bool dihedral) {
     return launch_hash_any(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, s, dihedral);
 }
+
+size_t api_rects_scratch_bytes(int64_t n, int h, int w, int channels) {
+    size_t b = 0;
+    (void)hvd_pdq_rects_scratch_bytes(n, h, w, channels, &b);
+    return b;
+}
+
+// The launch chain of hvd_dev_pdq_hash_frames_rects on stream s (arguments already validated, n > 0): frame -> rectangle
+// table, down-sampler inside the rectangles, K1. Scratch layout: hvd_pdq_rects_scratch_bytes.
+hipError_t api_launch_hash_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
+                                 const void* d_rects, void* d_scratch, void* d_hashes, void* d_quality, hipStream_t s) {
+    // 64x64 frames: every rectangle is the full frame by the rule (an axis shorter than 64 keeps its full extent)
+    if (h == 64 && w == 64) return launch_hash_any(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, s, false);
+    float* out64 = (float*)d_scratch;
+    const size_t cnt = (size_t)(n < 1024 ? n : 1024);
+    float* ws = out64 + (size_t)n * 4096;
+    const size_t geom_at = (sizeof(float) * (4096 * (size_t)n + cnt * pdq_downsample_ws_floats(h, w)) + 15) / 16 * 16;
+    void* geom = (char*)d_scratch + geom_at;  // (hvd_pdq_rects_scratch_bytes rounds the same way)
+    hipError_t e = launch_pdq_downsample_rects((const uint8_t*)d_frames, n, h, w, channels, (const long long*)d_offsets,
+                                               (uint32_t)V, (const int32_t*)d_rects, geom, ws, out64, s);
+    if (e != hipSuccess) return e;
+    return launch_pdq_hash64(d_scratch, 1, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s);
+}
 }  // namespace hvd
 
 extern "C" {
@@ -912,19 +939,7 @@ int hvd_dev_pdq_hash_frames_rects(const void* d_frames, int64_t n, int h, int w,
         return fail(HVD_ERR_ARG, "d_scratch (hvd_pdq_rects_scratch_bytes) is required unless 64x64 gray");
     if (((uintptr_t)d_rects | (uintptr_t)d_scratch) & 15u)
         return fail(HVD_ERR_ARG, "d_rects and d_scratch must be 16-byte aligned (hvd_dev_malloc's are)");
-    // 64x64 frames: every rectangle is the full frame by the rule (an axis shorter than 64 keeps its full extent)
-    if (h == 64 && w == 64) {
-        HIP_TRY(hvd::launch_hash_any(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, g.stream, false));
-        return HVD_OK;
-    }
-    float* out64 = (float*)d_scratch;
-    const size_t cnt = (size_t)(n < 1024 ? n : 1024);
-    float* ws = out64 + (size_t)n * 4096;
-    const size_t geom_at = (sizeof(float) * (4096 * (size_t)n + cnt * hvd::pdq_downsample_ws_floats(h, w)) + 15) / 16 * 16;
-    void* geom = (char*)d_scratch + geom_at;  // (hvd_pdq_rects_scratch_bytes rounds the same way)
-    HIP_TRY(hvd::launch_pdq_downsample_rects((const uint8_t*)d_frames, n, h, w, channels, (const long long*)d_offsets,
-                                             (uint32_t)V, (const int32_t*)d_rects, geom, ws, out64, g.stream));
-    HIP_TRY(hvd::launch_pdq_hash64(d_scratch, 1, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, g.stream));
+    HIP_TRY(hvd::api_launch_hash_rects(d_frames, n, h, w, channels, d_offsets, V, d_rects, d_scratch, d_hashes, d_quality, g.stream));
     return HVD_OK;
 }
 

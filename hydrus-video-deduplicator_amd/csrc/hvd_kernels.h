@@ -184,8 +184,19 @@ hipError_t launch_pdq_luma64_rgb(const uint8_t* d_frames, int64_t n, float* d_ou
 // {top, left, height, width}, also the kernels' accumulator (nothing else is allocated).
 hipError_t launch_content_rects(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
                                 uint32_t V, int black_level, int min_bright, int32_t* d_rects, hipStream_t s);
+// ... and its three steps one by one (rectangle accumulators are folded batch by batch by the streaming hasher).
+hipError_t launch_rect_init(int32_t* d_rects, uint32_t V, hipStream_t s);
+hipError_t launch_rect_fold(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
+                            uint32_t V, int black_level, int min_bright, int32_t* d_rects, hipStream_t s);
+hipError_t launch_rect_finish(int32_t* d_rects, uint32_t V, int h, int w, hipStream_t s);
 // The generic four-pass down-sampler inside every frame's video rectangle. d_geom: pdq_rects_geom_bytes(n) bytes (the
 // frame -> rectangle table); d_ws as for launch_pdq_downsample (sized for the full h x w).
+// Frames with h <= 512 and w <= 512 take the fused k_down_rect (one launch, same planes bit for bit) unless
+// g_pdq_fused_rect is off (hvd_debug_set "pdq_fused_rect").
+extern bool g_pdq_fused_rect;
+constexpr int kDownRectMax = 512;  // largest frame side k_down_rect takes (k_autocrop_fused.hip)
+void launch_down_rect(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const void* d_geom, float* d_out64,
+                      hipStream_t s);
 size_t pdq_rects_geom_bytes(int64_t n);
 hipError_t launch_pdq_downsample_rects(const uint8_t* d_frames, int64_t n, int h, int w, int channels,
                                        const long long* d_offsets, uint32_t V, const int32_t* d_rects, void* d_geom,

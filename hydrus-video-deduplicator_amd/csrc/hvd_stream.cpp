@@ -6,6 +6,11 @@
 // which bounds the staging memory like the reference's blocking frame queue
 // (vpdqpy.py:115-117). A dihedral hasher (hvd_hasher_create_dihedral) runs the same ring through the dihedral kernel
 // and downloads 8 x 32 bytes of hashes per frame.
+// An autocrop hasher (hvd_hasher_create_autocrop) hashes inside the video's content rectangle, which is known only
+// after the last frame: a batch is uploaded straight into a store of device blocks that keeps the whole video in HBM, and
+// behind the upload, on the same stream, k_content_rect folds the batch into the hasher's one rectangle record (an order-free
+// atomicMin / atomicMax merge: the slots' streams need no ordering among themselves). finish() closes the rectangle and
+// sends every retained frame through the same slot ring once more, this time to be hashed under the rectangle.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +36,9 @@ void api_set_context(int idx);
 size_t api_scratch_bytes(int64_t n, int h, int w, int channels);
 hipError_t api_launch_hash(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
                            void* d_quality, hipStream_t s, bool dihedral);
+size_t api_rects_scratch_bytes(int64_t n, int h, int w, int channels);
+hipError_t api_launch_hash_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
+                                 const void* d_rects, void* d_scratch, void* d_hashes, void* d_quality, hipStream_t s);
 }  // namespace hvd
 
 namespace {
@@ -46,13 +54,21 @@ struct Slot {
     uint8_t* h_frames = nullptr;   // pinned
     uint8_t* h_hashes = nullptr;   // pinned
     int32_t* h_quality = nullptr;  // pinned
-    void* d_frames = nullptr;
+    void* d_frames = nullptr;      // (an autocrop hasher has none: its batches go into the retained store)
     void* d_scratch = nullptr;
     void* d_hashes = nullptr;
     void* d_quality = nullptr;
     int64_t filled = 0;    // frames staged in h_frames
     int64_t in_flight = 0; // frames submitted and not yet collected
+    bool results = true;   // ... whose hashes and qualities collect() takes (an autocrop upload has none)
 };
+
+// A block of the retained store of an autocrop hasher: frames [0, used) of cap, back to back. A batch never spans blocks.
+struct Block {
+    uint8_t* d = nullptr;
+    int64_t cap = 0, used = 0;
+};
+constexpr int64_t kDefaultRetained = (int64_t)8 << 30;  // bytes of frames one video may keep in HBM (hvd_hasher_create_autocrop)
 
 }  // namespace
 
@@ -109,6 +125,16 @@ struct hvd_hasher {
     std::vector<int32_t> quality;
     bool acquired = false;         // hvd_hasher_acquire handed out the next frame's slot memory
     int64_t acquired_n = 0;        // ... and hvd_hasher_acquire_n this many frames of it
+    // autocrop (hvd_hasher_create_autocrop)
+    bool autocrop = false;
+    int black_level = 0, min_bright = 0;
+    int64_t max_frames = 0;        // frames one video may retain (max_retained_bytes / frame_bytes)
+    int64_t taken = 0;             // frames committed since the last finish
+    bool rect_closed = false;      // k_rect_finish has turned the accumulators into the rectangle (it must run once)
+    std::vector<Block> store;      // the video's frames in HBM, in push order
+    void* d_meta = nullptr;        // int32[4] rectangle record (accumulators, then {top, left, height, width}) + int64[2] CSR of one video
+    int32_t* d_rect() const { return (int32_t*)d_meta; }
+    const long long* d_offsets() const { return (const long long*)((char*)d_meta + 16); }
     size_t hash_bytes() const { return dihedral ? 8 * 32 : 32; }
 };
 
@@ -150,14 +176,58 @@ static int collect(hvd_hasher* hs, Slot& s) {
         NsScope ns(g_ns_wait);
         S_TRY(hipEventSynchronize(s.done));
     }
-    hs->hashes.insert(hs->hashes.end(), s.h_hashes, s.h_hashes + hs->hash_bytes() * s.in_flight);
-    hs->quality.insert(hs->quality.end(), s.h_quality, s.h_quality + s.in_flight);
+    if (s.results) {
+        hs->hashes.insert(hs->hashes.end(), s.h_hashes, s.h_hashes + hs->hash_bytes() * s.in_flight);
+        hs->quality.insert(hs->quality.end(), s.h_quality, s.h_quality + s.in_flight);
+    }
     s.in_flight = 0;
+    return HVD_OK;
+}
+
+// Room for `frames` more frames, back to back, in the last block of the store -- or a new block, of up to one slot set's worth
+// of frames (kSlots batches) and never more than the video may still retain. Called when a batch BEGINS, so an allocation
+// failure surfaces before the batch's first frame is taken.
+static int store_reserve(hvd_hasher* hs, int64_t frames) {
+    if (!hs->store.empty() && hs->store.back().used + frames <= hs->store.back().cap) return HVD_OK;
+    int64_t held = 0;
+    for (const Block& b : hs->store) held += b.used;
+    if (!hs->store.empty() && hs->store.back().used == 0) {  // (a parked block too small for this batch)
+        (void)hipFree(hs->store.back().d);
+        hs->store.pop_back();
+    }
+    Block b;
+    b.cap = std::max<int64_t>(frames, std::min<int64_t>(kSlots * hs->batch, hs->max_frames - held));
+    hipError_t e = hipMalloc((void**)&b.d, hs->frame_bytes * (size_t)b.cap);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return hvd::api_fail(HVD_ERR_HIP, "retained frame store: %s (%lld frames held)", hipGetErrorString(e), (long long)held);
+    }
+    hs->store.push_back(b);
+    return HVD_OK;
+}
+
+// An autocrop batch: upload into the store, fold into the rectangle record behind it. Nothing is hashed yet.
+static int submit_retain(hvd_hasher* hs, Slot& s) {
+    NsScope ns(g_ns_submit);
+    const int64_t m = s.filled;
+    if (int rc = store_reserve(hs, m)) return rc;  // (reserved when the batch began: no allocation here)
+    Block& b = hs->store.back();
+    uint8_t* dst = b.d + hs->frame_bytes * (size_t)b.used;
+    S_TRY(hipMemcpyAsync(dst, s.h_frames, hs->frame_bytes * (size_t)m, hipMemcpyHostToDevice, s.stream));
+    S_TRY(hvd::launch_rect_fold(dst, m, hs->h, hs->w, hs->channels, hs->d_offsets(), 1, hs->black_level, hs->min_bright,
+                                hs->d_rect(), s.stream));
+    S_TRY(hipEventRecord(s.done, s.stream));
+    b.used += m;
+    s.in_flight = m;
+    s.results = false;
+    s.filled = 0;
+    hs->limit = next_limit(hs);
     return HVD_OK;
 }
 
 static int submit(hvd_hasher* hs, Slot& s) {
     if (s.filled == 0) return HVD_OK;
+    if (hs->autocrop) return submit_retain(hs, s);
     // the dihedral kernel has K1's strict arithmetic only: a switch to fma while a video is in progress fails here, before
     // anything of this batch is enqueued (it stays staged), instead of hashing the rest of the video another way
     if (hs->dihedral && hvd::g_pdq_dct_mode != 0)
@@ -200,7 +270,25 @@ void free_hasher(hvd_hasher* hs) {
         if (s.done) (void)hipEventDestroy(s.done);
         if (s.stream) (void)hipStreamDestroy(s.stream);
     }
+    for (Block& b : hs->store) (void)hipFree(b.d);
+    if (hs->d_meta) (void)hipFree(hs->d_meta);
     delete hs;
+}
+
+// An autocrop hasher before its (next) video: nothing retained, the rectangle record at its initial value. The first block is
+// kept for the next video (at most one slot set's worth of frames, what a plain hasher's slots hold in d_frames), the others
+// are freed. Every slot is idle when this runs.
+int reset_video(hvd_hasher* hs) {
+    hs->taken = 0;
+    hs->rect_closed = false;
+    while (hs->store.size() > 1) {
+        (void)hipFree(hs->store.back().d);
+        hs->store.pop_back();
+    }
+    if (!hs->store.empty()) hs->store[0].used = 0;
+    S_TRY(hvd::launch_rect_init(hs->d_rect(), 1, hs->slot[0].stream));
+    S_TRY(hipStreamSynchronize(hs->slot[0].stream));
+    return HVD_OK;
 }
 }  // namespace
 
@@ -224,10 +312,11 @@ int hvd_hasher_destroy(hvd_hasher* hs) {
     bool complete = true;
     for (Slot& s : hs->slot) {
         if (s.stream) (void)hipStreamSynchronize(s.stream);
-        complete = complete && s.stream && s.done && s.h_frames && s.h_hashes && s.h_quality && s.d_frames && s.d_hashes &&
-                   s.d_quality;
+        complete = complete && s.stream && s.done && s.h_frames && s.h_hashes && s.h_quality && (s.d_frames || hs->autocrop) &&
+                   s.d_hashes && s.d_quality;
         s.filled = s.in_flight = 0;
     }
+    if (complete && hs->autocrop && hvd::api_dct_device()) complete = hs->d_meta && reset_video(hs) == HVD_OK;
     if (complete && hvd::api_dct_device()) {  // park it for the next video (never after hvd_shutdown)
         hs->hashes.clear();
         hs->quality.clear();
@@ -248,7 +337,13 @@ int hvd_hasher_destroy(hvd_hasher* hs) {
 
 }  // extern "C"
 
-static int create_hasher(int width, int height, int channels, int64_t batch_frames, bool dihedral, hvd_hasher** out) {
+struct AutocropArgs {
+    int black_level, min_bright;
+    int64_t max_retained_bytes;
+};
+
+static int create_hasher(int width, int height, int channels, int64_t batch_frames, bool dihedral, hvd_hasher** out,
+                         const AutocropArgs* ac = nullptr) {
     if (!out) return hvd::api_fail(HVD_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (!hvd::api_dct_device()) return hvd::api_fail(HVD_ERR_STATE, "hvd_init() has not been called (no CPU fallback exists)");
@@ -257,14 +352,23 @@ static int create_hasher(int width, int height, int channels, int64_t batch_fram
                              (long long)batch_frames);
     if (dihedral && hvd::g_pdq_dct_mode != 0)
         return hvd::api_fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");
+    if (ac && (ac->black_level < 0 || ac->black_level > 254)) return hvd::api_fail(HVD_ERR_ARG, "black_level=%d: need 0..254", ac->black_level);
+    if (ac && ac->min_bright < 1) return hvd::api_fail(HVD_ERR_ARG, "min_bright=%d: need >= 1", ac->min_bright);
+    const int64_t max_frames =
+        !ac ? 0 : (ac->max_retained_bytes > 0 ? ac->max_retained_bytes : kDefaultRetained) / ((int64_t)width * height * channels);
     {
         std::lock_guard<std::mutex> lk(g_park_mu);
         for (size_t k = g_parked.size(); k-- > 0;) {
             hvd_hasher* p = g_parked[k];
             if (p->ctx == hvd::api_context() && p->w == width && p->h == height && p->channels == channels && p->batch == batch_frames &&
-                p->dihedral == dihedral) {
+                p->dihedral == dihedral && p->autocrop == (ac != nullptr)) {
                 g_parked.erase(g_parked.begin() + (long)k);
                 p->copy_threads = default_copy_threads();
+                if (ac) {
+                    p->black_level = ac->black_level;
+                    p->min_bright = ac->min_bright;
+                    p->max_frames = max_frames;
+                }
                 *out = p;
                 return HVD_OK;
             }
@@ -277,10 +381,17 @@ static int create_hasher(int width, int height, int channels, int64_t batch_fram
     hs->h = height;
     hs->channels = channels;
     hs->dihedral = dihedral;
+    hs->autocrop = ac != nullptr;
+    if (ac) {
+        hs->black_level = ac->black_level;
+        hs->min_bright = ac->min_bright;
+        hs->max_frames = max_frames;
+    }
     hs->batch = batch_frames;
     hs->frame_bytes = (size_t)width * height * channels;
     hs->limit = first_limit(hs);
-    const size_t scratch = hvd::api_scratch_bytes(batch_frames, height, width, channels);
+    const size_t scratch = ac ? hvd::api_rects_scratch_bytes(batch_frames, height, width, channels)
+                              : hvd::api_scratch_bytes(batch_frames, height, width, channels);
     for (Slot& s : hs->slot) {
         hipError_t e = hipSuccess;
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
@@ -288,7 +399,7 @@ static int create_hasher(int width, int height, int channels, int64_t batch_fram
         if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_frames, hs->frame_bytes * (size_t)batch_frames, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_hashes, hs->hash_bytes() * (size_t)batch_frames, hipHostMallocDefault);
         if (e == hipSuccess) e = hipHostMalloc((void**)&s.h_quality, 4 * (size_t)batch_frames, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc(&s.d_frames, hs->frame_bytes * (size_t)batch_frames);
+        if (e == hipSuccess && !ac) e = hipMalloc(&s.d_frames, hs->frame_bytes * (size_t)batch_frames);
         if (e == hipSuccess && scratch) e = hipMalloc(&s.d_scratch, scratch);
         if (e == hipSuccess) e = hipMalloc(&s.d_hashes, hs->hash_bytes() * (size_t)batch_frames);
         if (e == hipSuccess) e = hipMalloc(&s.d_quality, 4 * (size_t)batch_frames);
@@ -298,11 +409,26 @@ static int create_hasher(int width, int height, int channels, int64_t batch_fram
             return hvd::api_fail(HVD_ERR_HIP, "hasher allocation: %s", hipGetErrorString(e));
         }
     }
+    if (ac) {
+        const long long csr[2] = {0, 0x7FFFFFFF};  // one video that holds every frame of any batch
+        hipError_t e = hipMalloc(&hs->d_meta, 32);
+        if (e == hipSuccess) e = hipMemcpy((char*)hs->d_meta + 16, csr, 16, hipMemcpyHostToDevice);
+        if (e != hipSuccess || reset_video(hs) != HVD_OK) {
+            free_hasher(hs);
+            return hvd::api_fail(HVD_ERR_HIP, "hasher allocation: %s", hipGetErrorString(e));
+        }
+    }
     *out = hs;
     return HVD_OK;
 }
 
 extern "C" {
+
+int hvd_hasher_create_autocrop(int width, int height, int channels, int64_t batch_frames, int black_level, int min_bright,
+                               int64_t max_retained_bytes, hvd_hasher** out) {
+    const AutocropArgs ac{black_level, min_bright, max_retained_bytes};
+    return create_hasher(width, height, channels, batch_frames, false, out, &ac);
+}
 
 int hvd_hasher_create(int width, int height, int channels, int64_t batch_frames, hvd_hasher** out) {
     return create_hasher(width, height, channels, batch_frames, false, out);
@@ -328,6 +454,13 @@ int hvd_hasher_acquire(hvd_hasher* hs, uint8_t** out_frame) {
     if (s.filled == 0 && s.in_flight) {  // slot being reused: its previous batch must have landed
         if (int rc = collect(hs, s)) return rc;
     }
+    if (hs->autocrop) {  // before the frame is taken: the cap, and room in the store for the batch that begins here
+        if (hs->taken >= hs->max_frames)
+            return hvd::api_fail(HVD_ERR_OVERFLOW, "the video would retain more than %lld frames (max_retained_bytes)",
+                                 (long long)hs->max_frames);
+        if (s.filled == 0)
+            if (int rc = store_reserve(hs, std::min<int64_t>(hs->limit, hs->max_frames - hs->taken))) return rc;
+    }
     *out_frame = s.h_frames + hs->frame_bytes * (size_t)s.filled;
     hs->acquired = true;
     hs->acquired_n = 1;
@@ -340,6 +473,7 @@ int hvd_hasher_commit(hvd_hasher* hs) {
     if (!hs->acquired) return hvd::api_fail(HVD_ERR_STATE, "hvd_hasher_commit() without hvd_hasher_acquire()");
     if (int rc = hvd::api_bind_device()) return rc;
     hs->acquired = false;
+    ++hs->taken;
     Slot& s = hs->slot[hs->cur];
     if (++s.filled >= hs->limit) {
         if (int rc = submit(hs, s)) return rc;
@@ -358,6 +492,7 @@ int hvd_hasher_acquire_n(hvd_hasher* hs, int64_t want, uint8_t** out_frames, int
     if (int rc = hvd_hasher_acquire(hs, out_frames)) return rc;
     const Slot& s = hs->slot[hs->cur];
     *out_n = hs->acquired_n = std::min<int64_t>(want, hs->limit - s.filled);
+    if (hs->autocrop) *out_n = hs->acquired_n = std::min<int64_t>(*out_n, hs->max_frames - hs->taken);
     return HVD_OK;
 }
 
@@ -369,6 +504,7 @@ int hvd_hasher_commit_n(hvd_hasher* hs, int64_t n) {
     if (n < 0 || n > hs->acquired_n) return hvd::api_fail(HVD_ERR_ARG, "commit of %lld frames, %lld acquired", (long long)n, (long long)hs->acquired_n);
     if (int rc = hvd::api_bind_device()) return rc;
     hs->acquired = false;
+    hs->taken += n;
     s.filled += n;
     if (s.filled >= hs->limit) {
         if (int rc = submit(hs, s)) return rc;
@@ -400,11 +536,53 @@ int hvd_hasher_set_threads(hvd_hasher* hs, int n) {
 
 }  // extern "C"
 
+// finish() of an autocrop hasher, every upload and fold done: close the rectangle, read its 16 bytes back, then hash the
+// retained frames block by block in runs of up to a batch, one run per slot on the slot's stream (its scratch, its result
+// buffers), so that kSlots runs are in flight; collect() gathers them in ring order = push order. A full-frame rectangle takes
+// the plain kernels (the same bits: a full rectangle is the frame), as the host batch entry does.
+static int hash_retained(hvd_hasher* hs, int32_t out_rect[4]) {
+    hs->hashes.clear();  // (a finish() that failed on a small `cap` may be repeated)
+    hs->quality.clear();
+    hipStream_t s0 = hs->slot[0].stream;
+    if (!hs->rect_closed) S_TRY(hvd::launch_rect_finish(hs->d_rect(), 1, hs->h, hs->w, s0));
+    hs->rect_closed = true;
+    S_TRY(hipMemcpyAsync(out_rect, hs->d_rect(), 16, hipMemcpyDeviceToHost, s0));
+    S_TRY(hipStreamSynchronize(s0));
+    const bool full = out_rect[0] == 0 && out_rect[1] == 0 && out_rect[2] == hs->h && out_rect[3] == hs->w;
+    int k = 0;
+    for (const Block& b : hs->store) {
+        for (int64_t f0 = 0; f0 < b.used; f0 += hs->batch, k = (k + 1) % kSlots) {
+            Slot& s = hs->slot[k];
+            if (int rc = collect(hs, s)) return rc;
+            NsScope ns(g_ns_submit);
+            const int64_t m = std::min<int64_t>(hs->batch, b.used - f0);
+            const uint8_t* src = b.d + hs->frame_bytes * (size_t)f0;
+            if (full)
+                S_TRY(hvd::api_launch_hash(src, m, hs->h, hs->w, hs->channels, s.d_scratch, s.d_hashes, s.d_quality, s.stream, false));
+            else
+                S_TRY(hvd::api_launch_hash_rects(src, m, hs->h, hs->w, hs->channels, hs->d_offsets(), 1, hs->d_rect(), s.d_scratch,
+                                                 s.d_hashes, s.d_quality, s.stream));
+            S_TRY(hipMemcpyAsync(s.h_hashes, s.d_hashes, 32 * (size_t)m, hipMemcpyDeviceToHost, s.stream));
+            S_TRY(hipMemcpyAsync(s.h_quality, s.d_quality, 4 * (size_t)m, hipMemcpyDeviceToHost, s.stream));
+            S_TRY(hipEventRecord(s.done, s.stream));
+            s.in_flight = m;
+            s.results = true;
+        }
+    }
+    for (int j = 0; j < kSlots; ++j, k = (k + 1) % kSlots)  // the oldest run still in flight sits in the slot that comes next
+        if (int rc = collect(hs, hs->slot[k])) return rc;
+    return HVD_OK;
+}
+
 /* Flushes the partial batch, waits for everything, returns all hashes / qualities in push
  * order (no quality filtering: that is VideoHasher.finish's policy, vpdqpy.py:119). The hasher
  * is empty afterwards and can be reused for the next video. */
-static int finish_hasher(hvd_hasher* hs, bool dihedral, uint8_t* out_hashes, int32_t* out_quality, int64_t cap, int64_t* out_n) {
+static int finish_hasher(hvd_hasher* hs, bool dihedral, uint8_t* out_hashes, int32_t* out_quality, int64_t cap, int64_t* out_n,
+                         int32_t* out_rect = nullptr) {
     if (!hs || !out_n) return hvd::api_fail(HVD_ERR_ARG, "NULL hasher/out_n");
+    if (hs->autocrop != (out_rect != nullptr))
+        return hvd::api_fail(HVD_ERR_STATE, hs->autocrop ? "an autocrop hasher finishes with hvd_hasher_finish_autocrop()"
+                                                         : "hvd_hasher_finish_autocrop() on a hasher without autocrop");
     if (hs->dihedral != dihedral)
         return hvd::api_fail(HVD_ERR_STATE, dihedral ? "hvd_hasher_finish_dihedral() on a plain hasher: use hvd_hasher_finish()"
                                                      : "hvd_hasher_finish() on a dihedral hasher: use hvd_hasher_finish_dihedral()");
@@ -426,6 +604,8 @@ static int finish_hasher(hvd_hasher* hs, bool dihedral, uint8_t* out_hashes, int
         for (int k = 0; k < kSlots; ++k)
             if (int rc = collect(hs, hs->slot[(hs->cur + k) % kSlots])) return rc;
     }
+    if (hs->autocrop)
+        if (int rc = hash_retained(hs, out_rect)) return rc;
     const int64_t n = (int64_t)hs->quality.size();
     *out_n = n;
     if (n > cap) return hvd::api_fail(HVD_ERR_OVERFLOW, "need room for %lld frames, cap %lld", (long long)n, (long long)cap);
@@ -438,6 +618,7 @@ static int finish_hasher(hvd_hasher* hs, bool dihedral, uint8_t* out_hashes, int
     hs->quality.clear();
     hs->cur = 0;
     hs->limit = first_limit(hs);  // the next video starts on an empty pipeline again
+    if (hs->autocrop) return reset_video(hs);
     return HVD_OK;
 }
 
@@ -452,8 +633,19 @@ int hvd_hasher_finish_dihedral(hvd_hasher* hs, uint8_t* out_hashes8, int32_t* ou
     return finish_hasher(hs, true, out_hashes8, out_quality, cap, out_n);
 }
 
+/* An autocrop hasher's results: hashes and qualities under the video's content rectangle, which goes to out_rect. */
+int hvd_hasher_finish_autocrop(hvd_hasher* hs, uint8_t* out_hashes, int32_t* out_quality, int64_t cap, int64_t* out_n,
+                               int32_t out_rect[4]) {
+    if (!out_rect) return hvd::api_fail(HVD_ERR_ARG, "NULL out_rect");
+    return finish_hasher(hs, false, out_hashes, out_quality, cap, out_n, out_rect);
+}
+
 int hvd_hasher_pending(hvd_hasher* hs, int64_t* out_frames) {
     if (!hs || !out_frames) return hvd::api_fail(HVD_ERR_ARG, "NULL");
+    if (hs->autocrop) {
+        *out_frames = hs->taken;
+        return HVD_OK;
+    }
     int64_t n = (int64_t)hs->quality.size();
     for (Slot& s : hs->slot) n += s.filled + s.in_flight;
     *out_frames = n;

@@ -12,6 +12,7 @@
 //   k_frame_geom       frame -> its video's rectangle (binary search in the CSR), checked against the frame
 //   k_box_scan_rect    k_pdq.hip's k_box_scan_T with {origin, lines, len, win, pitch} taken from that table
 //   k_luma64_rect      the plane of a 64 x 64 rectangle: the crop's luma, unfiltered
+// Frames up to 512 x 512 take the same four passes fused into one launch instead: k_down_rect, k_autocrop_fused.hip.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -301,27 +302,45 @@ __global__ __launch_bounds__(256) void k_luma64_rect(const uint8_t* __restrict__
 
 }  // namespace
 
+bool g_pdq_fused_rect = true;  // A/B switch (hvd_debug_set "pdq_fused_rect"): 0 forces the four generic passes
+
 hipError_t launch_content_rects(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
                                 uint32_t V, int black_level, int min_bright, int32_t* d_rects, hipStream_t s) {
     if (V == 0) return hipSuccess;
-    const dim3 gv((V + 255) / 256);
-    hipLaunchKernelGGL(k_rect_init, gv, dim3(256), 0, s, d_rects, (int)V);
+    hipError_t e = launch_rect_init(d_rects, V, s);
+    if (e == hipSuccess) e = launch_rect_fold(d_frames, n, h, w, channels, d_offsets, V, black_level, min_bright, d_rects, s);
+    if (e == hipSuccess) e = launch_rect_finish(d_rects, V, h, w, s);
+    return e;
+}
+
+// The three steps of launch_content_rects one by one, for a caller that folds a video's frames batch by batch (the streaming
+// hasher): init once, fold every batch (the atomicMin / atomicMax merge is order-free), finish once.
+hipError_t launch_rect_init(int32_t* d_rects, uint32_t V, hipStream_t s) {
+    hipLaunchKernelGGL(k_rect_init, dim3((V + 255) / 256), dim3(256), 0, s, d_rects, (int)V);
+    return hipGetLastError();
+}
+
+hipError_t launch_rect_fold(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
+                            uint32_t V, int black_level, int min_bright, int32_t* d_rects, hipStream_t s) {
     // 64 x 64 frames: no box can be smaller than the frame and at least 64 long, so every rectangle is the full frame
-    if (n > 0 && !(h == 64 && w == 64)) {
-        const size_t lds = sizeof(int) * (size_t)(h + w);
-        const bool wide = (w % kUnit) == 0 && ((uintptr_t)d_frames & 15u) == 0;
-        const dim3 gf((unsigned)n);
+    if (n <= 0 || (h == 64 && w == 64)) return hipSuccess;
+    const size_t lds = sizeof(int) * (size_t)(h + w);
+    const bool wide = (w % kUnit) == 0 && ((uintptr_t)d_frames & 15u) == 0;
+    const dim3 gf((unsigned)n);
 #define HVD_CR(CH, WIDE) hipLaunchKernelGGL((k_content_rect<CH, WIDE>), gf, dim3(256), lds, s, d_frames, h, w, d_offsets, (int)V, black_level, min_bright, d_rects)
-        if (channels == 3) {
-            if (wide) HVD_CR(3, true);
-            else HVD_CR(3, false);
-        } else {
-            if (wide) HVD_CR(1, true);
-            else HVD_CR(1, false);
-        }
-#undef HVD_CR
+    if (channels == 3) {
+        if (wide) HVD_CR(3, true);
+        else HVD_CR(3, false);
+    } else {
+        if (wide) HVD_CR(1, true);
+        else HVD_CR(1, false);
     }
-    hipLaunchKernelGGL(k_rect_finish, gv, dim3(256), 0, s, d_rects, (int)V, h, w);
+#undef HVD_CR
+    return hipGetLastError();
+}
+
+hipError_t launch_rect_finish(int32_t* d_rects, uint32_t V, int h, int w, hipStream_t s) {
+    hipLaunchKernelGGL(k_rect_finish, dim3((V + 255) / 256), dim3(256), 0, s, d_rects, (int)V, h, w);
     return hipGetLastError();
 }
 
@@ -336,6 +355,14 @@ hipError_t launch_pdq_downsample_rects(const uint8_t* d_frames, int64_t n, int h
     hipLaunchKernelGGL(k_frame_geom, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_offsets, (int)V, d_rects,
                        (long long)n, h, w, geom);
     const size_t hw = (size_t)h * w;
+    if (h <= kDownRectMax && w <= kDownRectMax && g_pdq_fused_rect) {
+        launch_down_rect(d_frames, n, h, w, channels, geom, d_out64, s);
+        if (channels == 3)
+            hipLaunchKernelGGL(k_luma64_rect<3>, dim3((unsigned)n), dim3(256), 0, s, d_frames, d_out64, geom, w, (long long)hw * 3);
+        else
+            hipLaunchKernelGGL(k_luma64_rect<1>, dim3((unsigned)n), dim3(256), 0, s, d_frames, d_out64, geom, w, (long long)hw);
+        return hipGetLastError();
+    }
     // slabs of 1024 frames, workspace laid out as the generic path lays it out for the full h x w (crops are never larger)
     const int64_t slab = 1024;
     for (int64_t f0 = 0; f0 < n; f0 += slab) {

@@ -188,12 +188,29 @@ class VideoHasher:
     "dihedral") or a sequence of ``TRANSFORMS`` names makes it a dihedral hasher (hvd_hasher_create_dihedral): the same
     ring, every batch hashed by the dihedral kernel. ``finish_transformed()`` then returns ``{name: VpdqHash}`` for those
     names and ``finish()`` the identity hash, which is what the plain hasher returns. Strict DCT mode only: in the "fma"
-    mode the constructor raises HvdError."""
+    mode the constructor raises HvdError.
+
+    ``autocrop``: None (default) hashes whole frames. True, or a dict with ``black_level`` / ``min_bright`` (what
+    ``autocrop_params`` takes), makes it an autocrop hasher (hvd_hasher_create_autocrop): the video's frames
+    stay in device memory while they stream in, their content rectangle is folded batch by batch behind the uploads, and
+    ``finish()`` hashes every frame inside that rectangle -- the result of ``hash_frames_autocrop`` on the same frames as
+    one video, byte for byte. After ``finish()``, ``rect`` is ``(top, left, height, width)``. ``max_retained_bytes``: how
+    many bytes of frames one video may keep on the device (None: the library default, 8 GiB); the frame that would pass
+    it raises HvdError(HVD_ERR_OVERFLOW) and ``finish()`` still returns the result of the frames taken before. Not
+    together with ``transforms``."""
 
     def __init__(self, average_fps: int, width: int, height: int, num_threads: int = 0,
-                 batch_bytes: int = 32 << 20, transforms=None):
+                 batch_bytes: int = 32 << 20, transforms=None, autocrop=None, max_retained_bytes: int | None = None):
         if width < 64 or height < 64:
             raise ValueError("frames must be at least 64x64")
+        self._autocrop = autocrop_params(autocrop)
+        if self._autocrop is not None and transforms is not None:
+            raise ValueError("autocrop and transforms cannot be combined (content-rectangle dihedral hashing does not exist)")
+        if max_retained_bytes is not None and (isinstance(max_retained_bytes, bool) or not isinstance(max_retained_bytes, (int, np.integer))
+                                               or max_retained_bytes < 1):
+            raise ValueError("max_retained_bytes must be a positive integer or None")
+        self._max_retained = 0 if max_retained_bytes is None else int(max_retained_bytes)
+        self.rect = None
         self._transforms = None
         if transforms is not None:
             from .search import transform_set
@@ -221,8 +238,12 @@ class VideoHasher:
         frame_bytes = self._frame_bytes_rgb if channels == 3 else self._frame_bytes_gray
         batch = max(1, min(4096, self._batch_bytes // frame_bytes))
         h = C.c_void_p()
-        create = self._lib.hvd_hasher_create if self._transforms is None else self._lib.hvd_hasher_create_dihedral
-        _lib.check(create(self.width, self.height, channels, batch, C.byref(h)))
+        if self._autocrop is not None:
+            _lib.check(self._lib.hvd_hasher_create_autocrop(self.width, self.height, channels, batch, self._autocrop[0],
+                                                            self._autocrop[1], self._max_retained, C.byref(h)))
+        else:
+            create = self._lib.hvd_hasher_create if self._transforms is None else self._lib.hvd_hasher_create_dihedral
+            _lib.check(create(self.width, self.height, channels, batch, C.byref(h)))
         self._handle = h
         self._channels = channels
         # num_threads: the reference hasher's worker threads (vpdqpy/vpdqpy.py:113; 0 = library default, negative =
@@ -339,6 +360,8 @@ class VideoHasher:
         uint8[m,32] (plain) or uint8[m,8,32] (dihedral, TRANSFORMS order); None if no frame was fed."""
         self._finished = True
         if self._handle is None:
+            if self._autocrop is not None:
+                self.rect = (0, 0, self.height, self.width)
             return None
         try:
             self._flush_run()
@@ -353,7 +376,13 @@ class VideoHasher:
             hashes = np.zeros(shape, dtype=np.uint8)
             quality = np.zeros(max(n, 1), dtype=np.int32)
             got = C.c_int64(0)
-            _lib.check(finish(self._handle, hashes.ctypes.data, quality.ctypes.data, n, C.byref(got)))
+            if self._autocrop is not None:
+                rect = (C.c_int32 * 4)()
+                _lib.check(self._lib.hvd_hasher_finish_autocrop(self._handle, hashes.ctypes.data, quality.ctypes.data, n,
+                                                                C.byref(got), rect))
+                self.rect = tuple(int(v) for v in rect)
+            else:
+                _lib.check(finish(self._handle, hashes.ctypes.data, quality.ctypes.data, n, C.byref(got)))
             assert got.value == n
             hashes, quality = hashes[:n], quality[:n]
             return hashes[quality >= QUALITY_TOLERANCE]

@@ -39,7 +39,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -240,6 +240,26 @@ int hvd_hasher_destroy(hvd_hasher* hs);
  * the batch stays staged and is submitted by the next call. */
 int hvd_hasher_create_dihedral(int width, int height, int channels, int64_t batch_frames, hvd_hasher** out);
 int hvd_hasher_finish_dihedral(hvd_hasher* hs, uint8_t* out_hashes8, int32_t* out_quality, int64_t cap, int64_t* out_n);
+/* Autocrop streaming hasher (content-rectangle PDQ, see hvd_dev_content_rects): for any sequence of frames, out_hashes,
+ * out_quality and out_rect ({top, left, height, width}) of hvd_hasher_finish_autocrop are what
+ * hvd_pdq_hash_frames_autocrop_gray_u8 / _rgb24_u8 return for the same frames as one video (V = 1) with the same
+ * black_level (0..254) / min_bright (>= 1; else HVD_ERR_ARG) -- byte for byte, in push order, in the DCT mode active at
+ * finish. The rectangle is known only after the last frame, so the video's frames stay in device memory until finish: a
+ * batch is uploaded straight into a store of device blocks, the rectangle is folded batch by batch behind the uploads,
+ * and finish hashes every retained frame under it. push / acquire[_n] / commit[_n] / pending / set_threads / destroy
+ * work on it unchanged. max_retained_bytes (<= 0: the library default, 8 GiB) bounds the frames one video keeps: the
+ * push / acquire[_n] of the frame that would pass it returns HVD_ERR_OVERFLOW before the frame is taken (acquire_n hands
+ * out at most what is left), the frames already taken stay and finish returns their result. A block that cannot be
+ * allocated is HVD_ERR_HIP with the same guarantee (room for a batch is reserved when the batch begins). No frames:
+ * out_n = 0 and the full-frame rectangle. hvd_hasher_finish / _finish_dihedral on an autocrop hasher and
+ * hvd_hasher_finish_autocrop on the other kinds return HVD_ERR_STATE. What is kept after finish / destroy: the slot set
+ * (parked per geometry and kind, as for the other kinds; no slot-sized device frame buffers here) and the store's first
+ * block, at most 6 batches of frames -- what a plain hasher's slots hold in device frame buffers; every other block is
+ * freed at finish, and hvd_shutdown frees everything. */
+int hvd_hasher_create_autocrop(int width, int height, int channels, int64_t batch_frames, int black_level, int min_bright,
+                               int64_t max_retained_bytes, hvd_hasher** out);
+int hvd_hasher_finish_autocrop(hvd_hasher* hs, uint8_t* out_hashes, int32_t* out_quality, int64_t cap, int64_t* out_n,
+                               int32_t out_rect[4]);
 
 /* --------------------------------------------- device-resident API ------- */
 /* For pipelines that keep data in HBM (hash on the GPU, then search) and for the
@@ -294,6 +314,7 @@ int hvd_get_pdq_dct_mode(void);
  *                                                           from 65 536 frames on (default) | always; results never change)
  *   "match_server" 0|1                                     (hvd_match_two, small operands: one launch per call | a workgroup that stays
  *                                                           resident between calls and polls pinned host memory -- the default)
+ *   "pdq_fused_rect" 0|1                                   (content-rectangle down-sampler, frames up to 512 x 512: four generic passes | fused kernel; same bits)
  *   "copy_nt" 0|1                                          (hvd_hasher_push: plain memcpy | non-temporal stores where the CPU has them)
  *   "mfma_clock_reset" 1                                   (telemetry: clear this context's clock accumulators, in stream order)
  * Unknown keys and out-of-range values return HVD_ERR_ARG. */
