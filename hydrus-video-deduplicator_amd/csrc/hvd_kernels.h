@@ -60,7 +60,7 @@ enum : int {
     kSelIdxCand = 8,     // words 8, 9: exact candidates of the pass (sum over blocks of the pairs within r in that block)
     kSelIdxMaxWalk = 10,  // the longest work item: max over (b, u) of c_u x (c_u + the counts of its neighbours above u)
     kSelIdxTicket = 11,  // the statistics kernel's last workgroup decides
-    kSelIdxGate = 12,    // the probe's estimate lets the histograms be built at all
+    kSelIdxGate = 12,    // the probe's estimate lets the keys be sorted and counted at all
 };
 // The cost rule (calibrated on MI355X): nanoseconds of the index pass against the matrix-core pass.
 struct IndexRule {
@@ -72,9 +72,9 @@ struct IndexRule {
     float fs_mfma_fetch;  // femtoseconds per comparison of form 9 / of the other matrix-core forms
     float fs_mfma_other;
     float ps_cand;        // picoseconds per candidate (join)
-    float ps_hash;        // picoseconds per hash (histograms, scan, scatter)
+    float ps_hash;        // picoseconds per hash (counting sort, statistics, place)
     float ps_crit;        // picoseconds per pair of the longest work item: one wave walks it alone (critical path)
-    float fixed_ns;       // launches of the index pass
+    float fixed_ns;       // launches of the index pass and its kernels whose length does not depend on n
 };
 // (form: the matrix-core form the probe chose; any other value prices the costlier forms)
 __host__ __device__ inline bool index_wins(const IndexRule& q, double cand, double max_walk, uint32_t form) {
@@ -90,10 +90,11 @@ extern int g_allpairs_index_fail;  // fault injection (tests): context (value - 
 // rank of a pass shares (arguments, n, world, the process-wide key), so all ranks agree.
 bool index_eligible(const AllPairsArgs& a, bool rect, uint32_t* r);
 IndexRule index_rule(const AllPairsArgs& a, uint32_t r);
-// Grows the context's index scratch (~36 B x 16 per hash). Called outside the launch lock: growing frees the old buffer,
+// Grows the context's index scratch (~44 B x 16 per hash: copies, rows, partition records). Called outside the launch lock: growing frees the old buffer,
 // which waits for the whole device.
 hipError_t index_reserve(int ctx_id, uint32_t n);
-// Histograms, exact statistics and decision (select[kSelIdxUsed]); then scan, scatter and join. Every kernel of the first call
+// Counting sort of the keys (partition, per-key counts, offsets), exact statistics and decision (select[kSelIdxUsed]); then
+// place and join. Every kernel of the first call
 // returns at once unless the probe's gate is set, every kernel of the second unless the decision is.
 hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const IndexRule& q, hipStream_t s);
 hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t r, hipStream_t s);

@@ -3,18 +3,25 @@
 // Cut the 256 bits into 16 blocks of 16 bits (block b = bits 16b..16b+15 of the packed hash, i.e. half b & 1 of word b >> 1).
 // Two hashes within max_dist <= 31 differ in at most 1 bit in at least one block (16 x 2 = 32 > 31); within max_dist <= 15
 // they agree in at least one block. With r = 1 (resp. 0) only pairs whose key of some block is within r bits are candidates:
-// on uniform hashes ~1/241 of all pairs at 1 M hashes. Every pass rebuilds the index in the context's scratch:
-//   k_index_clear    zero the 16 histograms of 65 536 keys
-//   k_index_hist     one thread per hash: 16 increments
-//   k_index_stats    one thread per (block, key): exact candidates and the longest work item; the last workgroup decides
-//                    (select[kSelIdxUsed], hvd_kernels.h: index_wins) -- the matrix-core forms return at once when it is set
-//   k_index_scan     exclusive scan per block -> bucket offsets (and the scatter's cursors)
-//   k_index_scatter  one thread per hash: bucket-ordered per-block copies {hash, row}
-//   k_index_join     one wave per work item (block b, key u): B_u x B_u (positions i < j) and B_u x B_{u ^ (1 << t)} for
-//                    the one-bit neighbours above u; the full 256-bit distance, and a pair is emitted only by its CANONICAL
-//                    block -- the first block whose keys are within r -- so it comes out exactly once, without a dedup pass
-// Kernels of the first three steps return at once unless the probe's gate (select[kSelIdxGate]) is set, the last three unless
-// the decision is. Nothing waits on the host.
+// on uniform hashes ~1/241 of all pairs at 1 M hashes. Every pass rebuilds the index in the context's scratch by a two-level
+// counting sort (high byte of the key, then low byte) whose counters live in LDS -- no global atomic per hash, and every
+// output region is written from one place:
+//   k_index_tile_count  one workgroup per tile of kTile hashes: high-byte digits of all 16 blocks counted in LDS -> tcnt[part][tile]
+//   k_index_scan_rows   one wave per partition (block, high byte): exclusive scan over the tiles, the partition's size
+//   k_index_scan_parts  one workgroup: every partition's base inside its block, and the list of chunks (a partition larger
+//                       than csz entries is cut into several, so that no workgroup sets the length of the passes below)
+//   k_index_partition   the tiles again: rank from a returning LDS atomic, record {row, key} -> its partition (short runs)
+//   k_index_count       one workgroup per chunk: low-byte digits counted in 256 LDS bins
+//   k_index_offsets     one workgroup per partition: the chunks' counts -> per-key counts, off[b][h * 256 ..], chunk cursors
+//   k_index_stats       one thread per (block, key): exact candidates and the longest work item; the last workgroup decides
+//                       (select[kSelIdxUsed], hvd_kernels.h: index_wins) -- the matrix-core forms return at once when it is set
+//   k_index_place       the chunks again: final position from a returning LDS atomic on the bin's cursor; rows, and the hash
+//                       gathered from the packed DB -> hc
+//   k_index_join        one wave per work item (block b, key u): B_u x B_u (positions i < j) and B_u x B_{u ^ (1 << t)} for
+//                       the one-bit neighbours above u; the full 256-bit distance, and a pair is emitted only by its CANONICAL
+//                       block -- the first block whose keys are within r -- so it comes out exactly once, without a dedup pass
+// Kernels up to the statistics return at once unless the probe's gate (select[kSelIdxGate]) is set, the last two unless the
+// decision is. Nothing waits on the host.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -35,22 +42,189 @@ __device__ __forceinline__ void load_words(const uint4* __restrict__ db, uint32_
     w[4] = h1.x; w[5] = h1.y; w[6] = h1.z; w[7] = h1.w;
 }
 
-__global__ __launch_bounds__(256) void k_index_clear(uint4* __restrict__ cnt, const uint32_t* __restrict__ select) {
-    if (select[hvd::kSelIdxGate] == 0u) return;
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t < kBlocks * kKeys / 4u) cnt[t] = make_uint4(0u, 0u, 0u, 0u);
+constexpr uint32_t kParts = kBlocks * 256u;       // partitions: (block, high byte of the key)
+constexpr uint32_t kTile = 4096u;                   // hashes per tile: a tile's run in a partition is ~16 records = 128 B
+constexpr uint32_t kTileThreads = 1024u;            // 16 waves per workgroup, kTile / kTileThreads hashes per thread
+constexpr uint32_t kMinChunk = 4096u;               // a chunk: at most max(kMinChunk, 2 x the mean partition) entries ...
+constexpr uint32_t kMaxChunks = kParts + 2048u;     // ... so a pass never has more chunks than this (index_chunk)
+
+__device__ __forceinline__ uint32_t lds_add(uint32_t* p) {
+    return __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(v, d);
+        if (lane >= (uint32_t)d) v += y;
+    }
+    return v;
 }
 
-__global__ __launch_bounds__(256) void k_index_hist(const uint4* __restrict__ db, uint32_t n, uint32_t* __restrict__ cnt,
-                                                    const uint32_t* __restrict__ select) {
+// tcnt[part][tile] = the tile's hashes whose key of block (part >> 8) has the high byte (part & 255)
+__global__ __launch_bounds__(kTileThreads) void k_index_tile_count(const uint4* __restrict__ db, uint32_t n, uint32_t ntiles,
+                                                                   uint32_t* __restrict__ tcnt, const uint32_t* __restrict__ select) {
+    __shared__ uint32_t bins[kParts];
     if (select[hvd::kSelIdxGate] == 0u) return;
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    uint32_t w[8];
-    load_words(db, i, w);
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t k = tid; k < kParts; k += kTileThreads) bins[k] = 0u;
+    __syncthreads();
 #pragma unroll
-    for (uint32_t b = 0; b < kBlocks; ++b)
-        __hip_atomic_fetch_add(&cnt[b * kKeys + key_of(w, b)], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (uint32_t j = 0; j < kTile / kTileThreads; ++j) {
+        const uint32_t i = blockIdx.x * kTile + j * kTileThreads + tid;
+        if (i < n) {
+            uint32_t w[8];
+            load_words(db, i, w);
+#pragma unroll
+            for (uint32_t b = 0; b < kBlocks; ++b) (void)lds_add(&bins[b * 256u + (key_of(w, b) >> 8)]);
+        }
+    }
+    __syncthreads();
+    for (uint32_t k = tid; k < kParts; k += kTileThreads) tcnt[(size_t)k * ntiles + blockIdx.x] = bins[k];
+}
+
+// One wave per partition: tcnt[part][.] becomes its exclusive scan over the tiles, ptotal[part] the partition's size.
+__global__ __launch_bounds__(256) void k_index_scan_rows(uint32_t* __restrict__ tcnt, uint32_t ntiles, uint32_t* __restrict__ ptotal,
+                                                         const uint32_t* __restrict__ select) {
+    if (select[hvd::kSelIdxGate] == 0u) return;
+    const uint32_t lane = threadIdx.x & 63u, p = blockIdx.x * 4u + (threadIdx.x >> 6);  // < kParts: the grid is exact
+    uint32_t* row = tcnt + (size_t)p * ntiles;
+    uint32_t run = 0;
+    for (uint32_t t0 = 0; t0 < ntiles; t0 += 64u) {
+        const uint32_t t = t0 + lane;
+        const uint32_t v = t < ntiles ? row[t] : 0u;
+        const uint32_t incl = wave_incl_scan(v, lane);
+        if (t < ntiles) row[t] = run + incl - v;
+        run += __shfl(incl, 63);
+    }
+    if (lane == 0u) ptotal[p] = run;
+}
+
+// One workgroup, thread t = partitions 4t .. 4t + 3 (wave w = block w): pbase[part] = the partition's first position inside
+// its block; pfirst[part] = its first chunk (pfirst[kParts] = chunks of the pass), chunk_p[chunk] = the chunk's partition.
+__global__ __launch_bounds__(1024) void k_index_scan_parts(const uint32_t* __restrict__ ptotal, uint32_t csz, uint32_t* __restrict__ pbase,
+                                                           uint32_t* __restrict__ pfirst, uint32_t* __restrict__ chunk_p,
+                                                           const uint32_t* __restrict__ select) {
+    __shared__ uint32_t wsum[16];
+    if (select[hvd::kSelIdxGate] == 0u) return;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint4 tv = reinterpret_cast<const uint4*>(ptotal)[tid];
+    const uint32_t tot[4] = {tv.x, tv.y, tv.z, tv.w};
+    uint32_t nch[4], size = 0, chunks = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        nch[k] = (tot[k] + csz - 1u) / csz;
+        size += tot[k];
+        chunks += nch[k];
+    }
+    uint32_t base = wave_incl_scan(size, lane) - size;  // (inside the block: a wave holds exactly one)
+    const uint32_t cincl = wave_incl_scan(chunks, lane);
+    if (lane == 63u) wsum[wave] = cincl;
+    __syncthreads();
+    uint32_t first = cincl - chunks;
+    for (uint32_t w = 0; w < wave; ++w) first += wsum[w];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        pbase[tid * 4u + k] = base;
+        pfirst[tid * 4u + k] = first;
+        for (uint32_t c = 0; c < nch[k]; ++c)
+            if (first + c < kMaxChunks) chunk_p[first + c] = tid * 4u + k;
+        base += tot[k];
+        first += nch[k];
+    }
+    if (tid == 1023u) pfirst[kParts] = min(first, kMaxChunks);
+}
+
+// rec[b][pbase + tile base + rank] = {row, key of block b}: the rank inside the tile's run comes from a returning LDS atomic.
+// Block by block, so that the runs a workgroup is filling at any time are few (256 x ~128 B) and soon complete.
+__global__ __launch_bounds__(kTileThreads) void k_index_partition(const uint4* __restrict__ db, uint32_t n, uint32_t ntiles,
+                                                                  const uint32_t* __restrict__ tcnt, const uint32_t* __restrict__ pbase,
+                                                                  uint2* __restrict__ rec, const uint32_t* __restrict__ select) {
+    __shared__ uint32_t cur[kParts];
+    if (select[hvd::kSelIdxGate] == 0u) return;
+    const uint32_t tid = threadIdx.x;
+    for (uint32_t k = tid; k < kParts; k += kTileThreads) cur[k] = pbase[k] + tcnt[(size_t)k * ntiles + blockIdx.x];
+    constexpr uint32_t kPer = kTile / kTileThreads;
+    uint32_t w[kPer][8];
+#pragma unroll
+    for (uint32_t j = 0; j < kPer; ++j) {
+        const uint32_t i = blockIdx.x * kTile + j * kTileThreads + tid;
+        if (i < n) load_words(db, i, w[j]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t b = 0; b < kBlocks; ++b) {
+#pragma unroll
+        for (uint32_t j = 0; j < kPer; ++j) {
+            const uint32_t i = blockIdx.x * kTile + j * kTileThreads + tid;
+            if (i < n) {
+                const uint32_t key = key_of(w[j], b);
+                const uint32_t pos = lds_add(&cur[b * 256u + (key >> 8)]);
+                if (pos < n) rec[(size_t)b * n + pos] = make_uint2(i, key);
+            }
+        }
+    }
+}
+
+// A chunk's place: partition, block, and its entries [lo, hi) of the partition's records.
+struct Chunk {
+    uint32_t p, b, lo, hi;
+    size_t at;  // the partition's first record inside rec / its first position inside hc and rows (block included)
+};
+__device__ __forceinline__ bool chunk_of(uint32_t c, uint32_t n, uint32_t csz, const uint32_t* __restrict__ ptotal,
+                                         const uint32_t* __restrict__ pbase, const uint32_t* __restrict__ pfirst,
+                                         const uint32_t* __restrict__ chunk_p, Chunk* q) {
+    if (c >= pfirst[kParts]) return false;
+    q->p = chunk_p[c];
+    q->b = q->p >> 8;
+    q->lo = (c - pfirst[q->p]) * csz;
+    q->hi = min(ptotal[q->p], q->lo + csz);
+    q->at = (size_t)q->b * n + pbase[q->p];
+    return true;
+}
+
+// ccount[chunk][low byte] = the chunk's entries with that low byte (the elements are streamed, only the 256 counters are in LDS)
+__global__ __launch_bounds__(256) void k_index_count(const uint2* __restrict__ rec, uint32_t n, uint32_t csz,
+                                                     const uint32_t* __restrict__ ptotal, const uint32_t* __restrict__ pbase,
+                                                     const uint32_t* __restrict__ pfirst, const uint32_t* __restrict__ chunk_p,
+                                                     uint32_t* __restrict__ ccount, const uint32_t* __restrict__ select) {
+    __shared__ uint32_t bins[256];
+    if (select[hvd::kSelIdxGate] == 0u) return;
+    Chunk q;
+    if (!chunk_of(blockIdx.x, n, csz, ptotal, pbase, pfirst, chunk_p, &q)) return;  // (uniform over the workgroup)
+    const uint32_t tid = threadIdx.x;
+    bins[tid] = 0u;
+    __syncthreads();
+    const uint2* __restrict__ r = rec + q.at;
+#pragma unroll 4
+    for (uint32_t e = q.lo + tid; e < q.hi; e += 256u) (void)lds_add(&bins[r[e].y & 255u]);
+    __syncthreads();
+    ccount[(size_t)blockIdx.x * 256u + tid] = bins[tid];
+}
+
+// One workgroup per partition (b, h), thread t = key h * 256 + t: cnt[b][key] (the statistics read it), off[b][key], and
+// ccount[chunk][t] becomes the chunk's cursor: the position inside block b of its first entry with that low byte.
+__global__ __launch_bounds__(256) void k_index_offsets(uint32_t n, const uint32_t* __restrict__ pbase, const uint32_t* __restrict__ pfirst,
+                                                       uint32_t* __restrict__ ccount, uint32_t* __restrict__ cnt, uint32_t* __restrict__ off,
+                                                       const uint32_t* __restrict__ select) {
+    __shared__ uint32_t wsum[4];
+    if (select[hvd::kSelIdxGate] == 0u) return;
+    const uint32_t p = blockIdx.x, b = p >> 8, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t c0 = pfirst[p], c1 = min(pfirst[p + 1u], kMaxChunks);
+    uint32_t total = 0;
+    for (uint32_t c = c0; c < c1; ++c) total += ccount[(size_t)c * 256u + tid];
+    const uint32_t incl = wave_incl_scan(total, lane);
+    if (lane == 63u) wsum[wave] = incl;
+    __syncthreads();
+    uint32_t pos = pbase[p] + incl - total;
+    for (uint32_t w = 0; w < wave; ++w) pos += wsum[w];
+    const uint32_t key = (p & 255u) * 256u + tid;
+    cnt[b * kKeys + key] = total;
+    off[(size_t)b * (kKeys + 1u) + key] = pos;
+    if (key == kKeys - 1u) off[(size_t)b * (kKeys + 1u) + kKeys] = n;
+    for (uint32_t c = c0; c < c1; ++c) {
+        const uint32_t v = ccount[(size_t)c * 256u + tid];
+        ccount[(size_t)c * 256u + tid] = pos;
+        pos += v;
+    }
 }
 
 // Candidates of key u in its block: C(c_u, 2) + (r = 1) c_u x c_v over the one-bit neighbours v = u ^ (1 << t) above u --
@@ -99,67 +273,49 @@ __global__ __launch_bounds__(256) void k_index_stats(const uint32_t* __restrict_
     }
 }
 
-// One workgroup per block: 1024 threads x 64 keys. off[b][0..65536] = exclusive prefix (off[b][65536] = n); the counters
-// become the scatter's cursors.
-__global__ __launch_bounds__(1024) void k_index_scan(uint32_t* __restrict__ cnt, uint32_t* __restrict__ off,
+// hc[b][pos] = {hash words 0..3, 4..7} (gathered from the packed DB), rows[b][pos] = row, in key order: pos from a returning
+// LDS atomic on the bin's cursor (order inside a bucket: whatever the atomics give -- the join's rule does not depend on it).
+// The chunks of a partition fill its region of hc and rows completely, and nobody else writes there.
+__global__ __launch_bounds__(256) void k_index_place(const uint4* __restrict__ db, const uint2* __restrict__ rec, uint32_t n, uint32_t csz,
+                                                     const uint32_t* __restrict__ ptotal, const uint32_t* __restrict__ pbase,
+                                                     const uint32_t* __restrict__ pfirst, const uint32_t* __restrict__ chunk_p,
+                                                     const uint32_t* __restrict__ ccount, uint4* __restrict__ hc, uint32_t* __restrict__ rows,
                                                      const uint32_t* __restrict__ select) {
+    __shared__ uint32_t cur[256];
     if (select[hvd::kSelIdxUsed] == 0u) return;
-    const uint32_t b = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    uint4* c4 = reinterpret_cast<uint4*>(cnt + (size_t)b * kKeys + tid * 64u);
-    uint32_t v[64];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const uint4 x = c4[k];
-        v[4 * k] = x.x; v[4 * k + 1] = x.y; v[4 * k + 2] = x.z; v[4 * k + 3] = x.w;
-        sum += x.x + x.y + x.z + x.w;
-    }
-    // inclusive scan of the thread sums: within the wave, then over the 16 waves
-    uint32_t incl = sum;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(incl, d);
-        if (lane >= (uint32_t)d) incl += y;
-    }
-    __shared__ uint32_t wsum[16];
-    if (lane == 63u) wsum[wave] = incl;
+    Chunk q;
+    if (!chunk_of(blockIdx.x, n, csz, ptotal, pbase, pfirst, chunk_p, &q)) return;  // (uniform over the workgroup)
+    const uint32_t tid = threadIdx.x;
+    cur[tid] = ccount[(size_t)blockIdx.x * 256u + tid];
     __syncthreads();
-    uint32_t base = 0;
-    for (uint32_t w = 0; w < wave; ++w) base += wsum[w];
-    uint32_t run = base + incl - sum;
-    uint32_t* ob = off + (size_t)b * (kKeys + 1u) + tid * 64u;
+    const uint2* __restrict__ r = rec + q.at;
+    const size_t base = (size_t)q.b * n;
+    constexpr uint32_t kU = 4u;  // entries per thread in flight: their gathers overlap
+    for (uint32_t e0 = q.lo; e0 < q.hi; e0 += 256u * kU) {
+        uint32_t row[kU], low[kU], pos[kU];
+        uint4 h0[kU], h1[kU];
 #pragma unroll
-    for (int k = 0; k < 64; ++k) {
-        const uint32_t x = v[k];
-        v[k] = run;
-        run += x;
-    }
+        for (uint32_t u = 0; u < kU; ++u) {
+            const uint32_t e = e0 + u * 256u + tid;
+            const uint2 rc = e < q.hi ? r[e] : make_uint2(n, 0u);
+            row[u] = rc.x;  // (n: no entry)
+            low[u] = rc.y & 255u;
+        }
 #pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        c4[k] = make_uint4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
-        ob[4 * k] = v[4 * k]; ob[4 * k + 1] = v[4 * k + 1]; ob[4 * k + 2] = v[4 * k + 2]; ob[4 * k + 3] = v[4 * k + 3];
-    }
-    if (tid == 1023u) off[(size_t)b * (kKeys + 1u) + kKeys] = run;
-}
-
-// hc[b][pos] = {hash words 0..3, 4..7}, rows[b][pos] = row, in key order (order inside a bucket: whatever the atomics give --
-// the join's rule does not depend on it)
-__global__ __launch_bounds__(256) void k_index_scatter(const uint4* __restrict__ db, uint32_t n, uint32_t* __restrict__ cnt,
-                                                       uint4* __restrict__ hc, uint32_t* __restrict__ rows,
-                                                       const uint32_t* __restrict__ select) {
-    if (select[hvd::kSelIdxUsed] == 0u) return;
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const uint4 h0 = db[(size_t)i * 2u], h1 = db[(size_t)i * 2u + 1u];
-    const uint32_t w[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-    uint32_t pos[kBlocks];
+        for (uint32_t u = 0; u < kU; ++u) {
+            const uint32_t g = min(row[u], n - 1u);
+            h0[u] = db[(size_t)g * 2u];
+            h1[u] = db[(size_t)g * 2u + 1u];
+        }
 #pragma unroll
-    for (uint32_t b = 0; b < kBlocks; ++b) pos[b] = atomicAdd(&cnt[b * kKeys + key_of(w, b)], 1u);  // (all 16 in flight)
+        for (uint32_t u = 0; u < kU; ++u) pos[u] = row[u] < n ? lds_add(&cur[low[u]]) : n;
 #pragma unroll
-    for (uint32_t b = 0; b < kBlocks; ++b) {
-        const size_t p = (size_t)b * n + pos[b];
-        hc[p * 2u] = h0;
-        hc[p * 2u + 1u] = h1;
-        rows[p] = i;
+        for (uint32_t u = 0; u < kU; ++u)
+            if (pos[u] < n) {
+                hc[(base + pos[u]) * 2u] = h0[u];
+                hc[(base + pos[u]) * 2u + 1u] = h1[u];
+                rows[base + pos[u]] = row[u];
+            }
     }
 }
 
@@ -320,7 +476,9 @@ namespace hvd {
 int g_allpairs_index = -1;
 int g_allpairs_index_fail = 0;
 
-// per-context scratch: counters [16][65536], offsets [16][65537], hash copies [16][n] x 32 B, rows [16][n]
+// per-context scratch: per-key counts [16][65536], offsets [16][65537], hash copies [16][n] x 32 B, rows [16][n]; for the
+// build: partition records [16][n] x 8 B, tile counts [4096][tiles], and per partition / chunk: sizes, bases, first chunks,
+// the chunk list and the chunks' low-byte counts (cursors)
 struct IndexScratch {
     void* p = nullptr;
     size_t cap = 0;
@@ -330,14 +488,22 @@ static IndexScratch g_idx[kMaxIdxCtx];
 static std::mutex g_idx_mu;
 
 static size_t off_words() { return ((size_t)kBlocks * (kKeys + 1u) + 3u) & ~(size_t)3u; }
+static uint32_t index_tiles(uint32_t n) { return (n + kTile - 1u) / kTile; }
+// Entries per chunk: at least twice the mean partition (n / 256), so the 16 n entries of a pass make at most 4096 + 2048 chunks.
+static uint32_t index_chunk(uint32_t n) { return max(kMinChunk, 2u * ((n + 255u) / 256u)); }
+static size_t tcnt_words(uint32_t n) { return ((size_t)kParts * index_tiles(n) + 3u) & ~(size_t)3u; }
+constexpr size_t kPartWords = 3u * kParts + 4u + kMaxChunks;  // ptotal, pbase, pfirst (+ 1, padded), chunk_p
 static size_t index_bytes(uint32_t n) {
-    return 4u * (size_t)kBlocks * kKeys + 4u * off_words() + (size_t)kBlocks * n * 32u + (size_t)kBlocks * n * 4u;
+    return 4u * (size_t)kBlocks * kKeys + 4u * off_words() + (size_t)kBlocks * n * 32u + (size_t)kBlocks * n * 4u +
+           (size_t)kBlocks * n * 8u + 4u * tcnt_words(n) + 4u * kPartWords + 4u * (size_t)kMaxChunks * 256u;
 }
 struct IndexPtrs {
     uint32_t* cnt;
     uint32_t* off;
     uint4* hc;
     uint32_t* rows;
+    uint2* rec;
+    uint32_t *tcnt, *ptotal, *pbase, *pfirst, *chunk_p, *ccount;
 };
 static IndexPtrs index_ptrs(int ctx_id, uint32_t n) {
     char* p = (char*)g_idx[ctx_id].p;
@@ -346,6 +512,13 @@ static IndexPtrs index_ptrs(int ctx_id, uint32_t n) {
     q.off = (uint32_t*)(p + 4u * (size_t)kBlocks * kKeys);
     q.hc = (uint4*)(p + 4u * (size_t)kBlocks * kKeys + 4u * off_words());
     q.rows = (uint32_t*)((char*)q.hc + (size_t)kBlocks * n * 32u);
+    q.rec = (uint2*)(q.rows + (size_t)kBlocks * n);  // (16 n words behind a 16-byte boundary: aligned)
+    q.tcnt = (uint32_t*)(q.rec + (size_t)kBlocks * n);
+    q.ptotal = q.tcnt + tcnt_words(n);
+    q.pbase = q.ptotal + kParts;
+    q.pfirst = q.pbase + kParts;
+    q.chunk_p = q.pfirst + kParts + 4u;
+    q.ccount = q.chunk_p + kMaxChunks;
     return q;
 }
 
@@ -364,15 +537,16 @@ IndexRule index_rule(const AllPairsArgs& a, uint32_t r) {
     q.r = r;
     q.force = g_allpairs_index == 1 ? 1u : 0u;
     q.world = a.world;
-    // (DESIGN 4.1, 1 M uniform hashes on MI355X: form 9 18.1 ms = 36 fs per comparison, forms 18 / 12 +4 / +11 %; join 2.08 ms
-    // for 2.075e9 candidates; histograms + statistics + scan + scatter 2.2 ms = 2.2 ns per hash; the longest work item's wave
-    // takes ~30 ns per step of 64 pairs)
+    // (DESIGN 4.1, 1 M uniform hashes on MI355X: form 9 18.1 ms = 36 fs per comparison, forms 18 / 12 +4 / +11 %; join 2.0 ms
+    // for 2.075e9 candidates; the counting sort, the statistics and the place pass 0.93 ms, of which ~0.03 ms do not depend
+    // on n (the scans over 4096 partitions, the grid of 6144 chunks): 0.9 ns per hash, and those 30 us next to the 40 us of
+    // launches; the longest work item's wave takes ~30 ns per step of 64 pairs)
     q.fs_mfma_fetch = 36.0f;
     q.fs_mfma_other = 40.0f;
     q.ps_cand = 1.0f;
-    q.ps_hash = 2200.0f;
+    q.ps_hash = 900.0f;
     q.ps_crit = 500.0f;
-    q.fixed_ns = 40000.0f;
+    q.fixed_ns = 70000.0f;
     return q;
 }
 
@@ -405,17 +579,23 @@ hipError_t index_reserve(int ctx_id, uint32_t n) {
 
 hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const IndexRule& q, hipStream_t s) {
     const IndexPtrs p = index_ptrs(a.ctx_id, a.n);
-    hipLaunchKernelGGL(k_index_clear, dim3(kBlocks * kKeys / 4u / 256u), dim3(256), 0, s, (uint4*)p.cnt, d_select);
-    hipLaunchKernelGGL(k_index_hist, dim3((a.n + 255u) / 256u), dim3(256), 0, s, (const uint4*)a.d_db, a.n, p.cnt, d_select);
+    const uint32_t tiles = index_tiles(a.n), csz = index_chunk(a.n);
+    const uint4* db = (const uint4*)a.d_db;
+    hipLaunchKernelGGL(k_index_tile_count, dim3(tiles), dim3(kTileThreads), 0, s, db, a.n, tiles, p.tcnt, d_select);
+    hipLaunchKernelGGL(k_index_scan_rows, dim3(kParts / 4u), dim3(256), 0, s, p.tcnt, tiles, p.ptotal, d_select);
+    hipLaunchKernelGGL(k_index_scan_parts, dim3(1), dim3(1024), 0, s, p.ptotal, csz, p.pbase, p.pfirst, p.chunk_p, d_select);
+    hipLaunchKernelGGL(k_index_partition, dim3(tiles), dim3(kTileThreads), 0, s, db, a.n, tiles, p.tcnt, p.pbase, p.rec, d_select);
+    hipLaunchKernelGGL(k_index_count, dim3(kMaxChunks), dim3(256), 0, s, p.rec, a.n, csz, p.ptotal, p.pbase, p.pfirst, p.chunk_p,
+                       p.ccount, d_select);
+    hipLaunchKernelGGL(k_index_offsets, dim3(kParts), dim3(256), 0, s, a.n, p.pbase, p.pfirst, p.ccount, p.cnt, p.off, d_select);
     hipLaunchKernelGGL(k_index_stats, dim3(kBlocks * kKeys / 256u), dim3(256), 0, s, p.cnt, d_select, q);
     return hipGetLastError();
 }
 
 hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t r, hipStream_t s) {
     const IndexPtrs p = index_ptrs(a.ctx_id, a.n);
-    hipLaunchKernelGGL(k_index_scan, dim3(kBlocks), dim3(1024), 0, s, p.cnt, p.off, d_select);
-    hipLaunchKernelGGL(k_index_scatter, dim3((a.n + 255u) / 256u), dim3(256), 0, s, (const uint4*)a.d_db, a.n, p.cnt, p.hc,
-                       p.rows, d_select);
+    hipLaunchKernelGGL(k_index_place, dim3(kMaxChunks), dim3(256), 0, s, (const uint4*)a.d_db, p.rec, a.n, index_chunk(a.n), p.ptotal,
+                       p.pbase, p.pfirst, p.chunk_p, p.ccount, p.hc, p.rows, d_select);
     JoinArgs j;
     j.off = p.off;
     j.hc = p.hc;
