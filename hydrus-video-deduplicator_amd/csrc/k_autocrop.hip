@@ -10,14 +10,17 @@
 //   k_content_rect     one workgroup per frame: bright counts per row and per column, frame box -> atomicMin / atomicMax
 //   k_rect_finish      fallbacks, {top, bottom, left, right} -> {top, left, height, width}
 //   k_frame_geom       frame -> its video's rectangle (binary search in the CSR), checked against the frame
-//   k_box_scan_rect    k_pdq.hip's k_box_scan_T with {origin, lines, len, win, pitch} taken from that table
+//   k_box_scan_rect    the generic line pass (hvd_pdq_dev.h: box_scan_lines, k_pdq.hip's k_box_scan_T) with {origin, lines,
+//                      len, win, pitch} taken from that table
 //   k_luma64_rect      the plane of a 64 x 64 rectangle: the crop's luma, unfiltered
 // Frames up to 512 x 512 take the same four passes fused into one launch instead: k_down_rect, k_autocrop_fused.hip.
+// Luma and the line pass are hvd_pdq_dev.h's, the one home of the bit-exactness contract.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 
 #include "hvd_kernels.h"
+#include "hvd_pdq_dev.h"
 
 namespace hvd {
 
@@ -50,8 +53,6 @@ __global__ __launch_bounds__(256) void k_rect_finish(int32_t* __restrict__ rects
 }
 
 constexpr int kUnit = 16;  // pixels a lane takes from a row: 16 B of gray, 48 B of RGB24 = whole 16-byte loads
-
-__device__ __forceinline__ uint32_t byte_of(uint32_t word, int i) { return (word >> (8 * i)) & 0xFFu; }
 
 // Bright pixels per row and per column of one frame, one workgroup of 256 lanes per frame. The lanes form R = 256 / P rows of
 // P = pow2 >= ceil(w / 16) lanes; lane (r, u) reads pixels [16u, 16u + 16) of rows r, r + R, ... and keeps the 16 column counts
@@ -168,17 +169,6 @@ __global__ __launch_bounds__(256) void k_frame_geom(const long long* __restrict_
     geom[f] = r;
 }
 
-constexpr int kTW = 32;         // columns per staged tile
-constexpr int kRing = 2 * kTW;  // LDS ring (window <= 32 looks back at most one tile)
-
-__device__ __forceinline__ float luma_of_gray(uint32_t g) {
-    const float v = (float)g;
-    float y = __fmul_rn(0.299f, v);
-    y = __fadd_rn(y, __fmul_rn(0.587f, v));
-    y = __fadd_rn(y, __fmul_rn(0.114f, v));
-    return y;
-}
-
 // The generic down-sampler's pass (k_pdq.hip: k_box_scan_T -- upstream's sequential running-sum box filter along the lines
 // of a row-major [lines][len] image, one lane per line, output transposed, passes 3 and 4 keep the 64 sampled positions
 // only), with the geometry of every frame taken from geom[frame] = {top, left, hh, ww} instead of the launch arguments:
@@ -186,95 +176,21 @@ __device__ __forceinline__ float luma_of_gray(uint32_t g) {
 //   PASS 2  [ww][hh]                                   lines ww, len hh   -> [hh][ww]
 //   PASS 3  [hh][ww]                                   lines hh, len ww   -> [64][hh]
 //   PASS 4  [64][hh]                                   lines 64, len hh   -> [64][64]
-// Window (len + 127) / 128. Same recurrence and operation order as k_box_scan_T, so the planes are those of the contiguous
-// crop, bit for bit. The grid covers the full frame's lines; a workgroup beyond its frame's lines returns at once.
+// Window jarosz_window(len). The recurrence is k_box_scan_T's own (one definition: box_scan_lines), so the planes are those
+// of the contiguous crop, bit for bit. The grid covers the full frame's lines; a workgroup beyond its frame's lines returns at once.
 // A 64 x 64 rectangle is no work here: the plain hash of a 64 x 64 frame is taken from its luma as it is (upstream's shortcut:
 // no filter, and a window-1 running sum is not the identity in float), k_luma64_rect writes that plane.
 template <int SRC, int PASS>  // SRC 0: float, 1: gray u8, 3: rgb24 (PASS 1 only)
 __global__ __launch_bounds__(64) void k_box_scan_rect(const void* __restrict__ in, float* __restrict__ out,
                                                       const int4* __restrict__ geom, int w, long long in_frame_stride,
                                                       long long out_frame_stride) {
-    __shared__ float ring[64][kRing + 1];
     const int4 rc = geom[blockIdx.y];
     const int lines = (PASS == 1 || PASS == 3) ? rc.z : PASS == 2 ? rc.w : 64;
     const int len = (PASS == 1 || PASS == 3) ? rc.w : rc.z;
     const int nsel = PASS >= 3 ? 64 : 0;
-    const int line0 = blockIdx.x * 64;
-    if (line0 >= lines || (rc.z == 64 && rc.w == 64)) return;
-    const int win = (len + 127) / 128;
-    const int lane = threadIdx.x;
-    const long long frame = blockIdx.y;
-    const int my_line = line0 + lane;
-    const int half = (win + 2) / 2;
-    const int steps = len + half - 1;
-    const int out_lines = lines;  // transposed output: [kept positions][lines]
-    float* dst = out + frame * out_frame_stride;
-
-    float sum = 0.0f;
-    int cur = 0;
-    int next_j = 0;
-    int next_sel = nsel ? (int)(((0 + 0.5) * len) / 64) : 0;
-
-    for (int s = 0; s < steps; ++s) {
-        if (s < len && (s % kTW) == 0) {
-            // stage columns [s, s+kTW) of the 64 lines into ring slot (s/kTW)&1
-            __syncthreads();
-            const int c = lane & (kTW - 1);
-            const int col = s + c;
-#pragma unroll 4
-            for (int rr = lane / kTW; rr < 64; rr += 64 / kTW) {
-                const int ln = line0 + rr;
-                float v = 0.0f;
-                if (ln < lines && col < len) {
-                    if (SRC == 0) {
-                        v = reinterpret_cast<const float*>(in)[frame * in_frame_stride + (long long)ln * len + col];
-                    } else {
-                        const long long e = (long long)(rc.x + ln) * w + (rc.y + col);
-                        if (SRC == 1) {
-                            v = luma_of_gray(reinterpret_cast<const uint8_t*>(in)[frame * in_frame_stride + e]);
-                        } else {
-                            const uint8_t* p = reinterpret_cast<const uint8_t*>(in) + frame * in_frame_stride + 3 * e;
-                            const float r = (float)p[0], g = (float)p[1], b = (float)p[2];
-                            v = __fmul_rn(0.299f, r);
-                            v = __fadd_rn(v, __fmul_rn(0.587f, g));
-                            v = __fadd_rn(v, __fmul_rn(0.114f, b));
-                        }
-                    }
-                }
-                ring[rr][col & (kRing - 1)] = v;
-            }
-            __syncthreads();
-        }
-        if (s < len) {
-            sum = __fadd_rn(sum, ring[lane][s & (kRing - 1)]);
-            if (s < win) ++cur;
-        }
-        if (s >= win) {
-            sum = __fsub_rn(sum, ring[lane][(s - win) & (kRing - 1)]);
-            if (s >= len) --cur;
-        }
-        if (s >= half - 1) {
-            const int oi = s - (half - 1);
-            bool keep = true;
-            int slot = oi;
-            if (nsel) {
-                keep = (next_j < nsel) && (oi == next_sel);
-                slot = next_j;
-            }
-            if (keep) {
-                float o;
-                if ((cur & (cur - 1)) == 0)
-                    o = __fmul_rn(sum, 1.0f / (float)cur);  // exact: power-of-two divisor
-                else
-                    o = __fdiv_rn(sum, (float)cur);
-                if (my_line < lines) dst[(long long)slot * out_lines + my_line] = o;
-                if (nsel) {
-                    ++next_j;
-                    next_sel = (int)(((next_j + 0.5) * len) / 64);
-                }
-            }
-        }
-    }
+    if ((int)(blockIdx.x * 64) >= lines || (rc.z == 64 && rc.w == 64)) return;
+    // (passes 2 - 4 read the contiguous [lines][len] image the pass before wrote: pitch and origin are pass 1's)
+    box_scan_lines<SRC>(in, out, in_frame_stride, out_frame_stride, w, rc.x, rc.y, lines, len, jarosz_window(len), nsel);
 }
 
 // The plane of a frame whose rectangle is 64 x 64: the luma of the crop, unfiltered. One workgroup per frame.
@@ -287,16 +203,7 @@ __global__ __launch_bounds__(256) void k_luma64_rect(const uint8_t* __restrict__
     float* dst = out64 + (size_t)blockIdx.x * 4096;
     for (int p = threadIdx.x; p < 4096; p += 256) {
         const long long e = (long long)(rc.x + (p >> 6)) * w + (rc.y + (p & 63));
-        float y;
-        if (CH == 1) {
-            y = luma_of_gray(src[e]);
-        } else {
-            const float r = (float)src[3 * e], g = (float)src[3 * e + 1], b = (float)src[3 * e + 2];
-            y = __fmul_rn(0.299f, r);
-            y = __fadd_rn(y, __fmul_rn(0.587f, g));
-            y = __fadd_rn(y, __fmul_rn(0.114f, b));
-        }
-        dst[p] = y;
+        dst[p] = CH == 1 ? luma_gray(src[e]) : luma_rgb((float)src[3 * e], (float)src[3 * e + 1], (float)src[3 * e + 2]);
     }
 }
 
@@ -350,7 +257,7 @@ hipError_t launch_pdq_downsample_rects(const uint8_t* d_frames, int64_t n, int h
                                        const long long* d_offsets, uint32_t V, const int32_t* d_rects, void* d_geom,
                                        float* d_ws, float* d_out64, hipStream_t s) {
     if (n <= 0) return hipSuccess;
-    if ((h + 127) / 128 > kTW || (w + 127) / 128 > kTW || V == 0) return hipErrorInvalidValue;
+    if (jarosz_window(h) > kTW || jarosz_window(w) > kTW || V == 0) return hipErrorInvalidValue;
     int4* geom = (int4*)d_geom;
     hipLaunchKernelGGL(k_frame_geom, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, d_offsets, (int)V, d_rects,
                        (long long)n, h, w, geom);

@@ -1,25 +1,16 @@
 // k_autocrop_fused.hip -- content-rectangle PDQ: the four down-sampler passes of k_autocrop.hip's k_box_scan_rect
 // in one launch, for frames up to 512 x 512. Same recurrence, same operation order: the 64 x 64 planes are those of the generic
-// passes and of the oracle on the contiguous crop, bit for bit.
+// passes and of the oracle on the contiguous crop, bit for bit. Luma is hvd_pdq_dev.h's, the home of that contract.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
 #include "hvd_kernels.h"
+#include "hvd_pdq_dev.h"
 
 namespace hvd {
 
 namespace {
-
-__device__ __forceinline__ uint32_t byte_of(uint32_t word, int i) { return (word >> (8 * i)) & 0xFFu; }
-
-__device__ __forceinline__ float luma_of_gray(uint32_t g) {  // as k_autocrop.hip's
-    const float v = (float)g;
-    float y = __fmul_rn(0.299f, v);
-    y = __fadd_rn(y, __fmul_rn(0.587f, v));
-    y = __fadd_rn(y, __fmul_rn(0.114f, v));
-    return y;
-}
 
 // k_down_rect: the four passes above in ONE launch, for frames with h <= 512 and w <= 512 ("fused rectangle
 // down-sampler"). k_pdq.hip's k_down512 with the rectangle's origin, its sides and the two windows (1..4, one per axis) as
@@ -278,15 +269,10 @@ __device__ __forceinline__ void rect_strip_luma(const RectRaw<CH>& raw, uint32_t
     for (int c = 0; c < kRS; ++c) {
         if (CH == 3) {
             const int b0 = 3 * c, b1 = 3 * c + 1, b2 = 3 * c + 2;
-            const float r = (float)byte_of(wd[b0 >> 2], b0 & 3);
-            const float g = (float)byte_of(wd[b1 >> 2], b1 & 3);
-            const float b = (float)byte_of(wd[b2 >> 2], b2 & 3);
-            float y = __fmul_rn(0.299f, r);
-            y = __fadd_rn(y, __fmul_rn(0.587f, g));
-            y = __fadd_rn(y, __fmul_rn(0.114f, b));
-            v[c] = y;
+            v[c] = luma_rgb((float)byte_of(wd[b0 >> 2], b0 & 3), (float)byte_of(wd[b1 >> 2], b1 & 3),
+                            (float)byte_of(wd[b2 >> 2], b2 & 3));
         } else {
-            v[c] = luma_of_gray(byte_of(wd[c >> 2], c & 3));
+            v[c] = luma_gray(byte_of(wd[c >> 2], c & 3));
         }
     }
 }

@@ -5,10 +5,10 @@
 // -> quality metric -> 16x16 DCT -> median -> 256 bits, laid out as
 // db/DedupeDB.py:535-559 describes (bit k=i*16+j at byte k>>3, bit k&7).
 //
-// Bit-exactness contract (oracle/hvd_oracle.c): every float op is a separately
-// rounded binary32 op in the oracle's order. All arithmetic that must match uses
-// __fmul_rn/__fadd_rn/__fsub_rn/__fdiv_rn, which hipcc never contracts into FMA,
-// and the DCT matrix is computed on the host in double and uploaded.
+// Bit-exactness contract (oracle/hvd_oracle.c): every float op is a separately rounded binary32 op in the oracle's
+// order. hvd_pdq_dev.h is the home of that contract: luma, the quality metric, stages 0 and 2 of the strict DCT, the
+// median select and the box-filter line pass are defined there once, for this file and for k_pdq_dihedral.hip,
+// k_autocrop.hip and k_autocrop_fused.hip. The DCT matrix is computed on the host in double and uploaded.
 // The f32 MFMA is an fmaf chain (one rounding per product+add) and therefore NOT
 // bit-identical to the reference's mul-then-add on x86-64; the DCT runs on the VALU.
 //
@@ -29,70 +29,9 @@
 #include <mutex>
 
 #include "hvd_kernels.h"
+#include "hvd_pdq_dev.h"
 
 namespace {
-
-constexpr int kWaves = 4;       // frames in flight per workgroup
-constexpr int kLd = 68;         // padded LDS row stride (floats): 272 B, 16-B aligned, bank-skewed
-
-struct alignas(16) PdqLds {
-    float T[kWaves][16][kLd];
-    float D[16][kLd];
-    float luma_lut[256];  // luma_gray(g) for every byte value
-};
-
-__device__ __forceinline__ float luma_gray(uint32_t g) {
-    const float v = (float)g;
-    float y = __fmul_rn(0.299f, v);
-    y = __fadd_rn(y, __fmul_rn(0.587f, v));
-    y = __fadd_rn(y, __fmul_rn(0.114f, v));
-    return y;
-}
-
-// |(int)(((u - v) * 100) / 255)| (pdqhashing.cpp quality metric) as a non-negative integer-valued
-// float, WITHOUT the IEEE division (10+ VALU ops). The multiplier is the float just BELOW 1/255
-// (RN(1/255) = 0x1.010102p-8 lies above the true value), so q = |x| * c stays below the true
-// quotient even after its own rounding: trunc(q) is floor(|x|/255) or one less. The remainder
-// r = |x| - 255*m is exact in one fma (|x| and 255*m are multiples of ulp(|x|) and close) and
-// r >= 255 says when to add one. Equality with (int)(x / 255.0f) is checked for EVERY float
-// |x| <= 26000 by tests/tools/check_div255.c (2.4e9 values, 0 mismatches); |x| <= 25500.01 here
-// because luma and its box-filter averages never exceed 255.0001. The fma is this kernel's own
-// exact-arithmetic device, not a contraction of reference arithmetic.
-// The term is m + (r >= 255): the caller accumulates the m's as floats (exact: integers far below
-// 2^24) and the corrections as an integer count (v_cmp + add-with-carry).
-__device__ __forceinline__ void grad_term(float u, float v, float& acc_m, int& acc_c) {
-    const float ax = fabsf(__fmul_rn(__fsub_rn(u, v), 100.0f));
-    const float m = truncf(__fmul_rn(ax, 0x1.0101p-8f));
-    const float r = __fmaf_rn(-255.0f, m, ax);
-    acc_m += m;
-    acc_c += (r >= 255.0f) ? 1 : 0;
-}
-
-// The same term for GRAY BYTE input in one multiply: there the operands are luma_gray(g) of a byte g, so (u, v) takes
-// only 256 x 256 values, and for every one of them trunc(|u - v| * RN(100/255)) equals the reference's
-// |(int)(((u - v) * 100) / 255)| -- checked exhaustively (tests/test_oracle.py::test_quality_term_gray_shortcut_is_exact
-// on the host, test_k1_quality_all_byte_pairs on the GPU). 4 VALU ops per term instead of 8; the quality metric was a
-// quarter of this kernel's instructions (profiles/r01_pmc_k1.txt). Float frames (the down-sampler's output) keep the
-// general form above.
-__device__ __forceinline__ void grad_term_gray(float u, float v, int& acc) {
-    // (int)x IS the truncation (v_cvt_i32_f32 rounds toward zero); an explicit truncf in front of it cost one more VALU
-    // instruction per term, 127 per frame (round 3)
-    acc += (int)__fmul_rn(fabsf(__fsub_rn(u, v)), 0x1.919192p-2f /* RN(100/255) = 0x3EC8C8C9 */);
-}
-
-// Lane l reads lane l+1 of the whole 64-lane wave (lane 63 reads 0 and is ignored by callers): the DPP
-// wave_shl:1 control of the GFX9 family, which folds into the consuming VALU instruction instead
-// of a trip through the LDS crossbar (ds_bpermute).
-__device__ __forceinline__ float wave_next_lane(float v) {
-    const int x = __float_as_int(v);
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x130 /* wave_shl:1 */, 0xF, 0xF, true));
-}
-
-__device__ __forceinline__ float wave_sum_f32(float v) {  // exact: integer-valued, far below 2^24
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // The DCT matrix as compile-time constants (scripts/gen_dct_table.py). This table is authoritative: hvd_init does not
 // consult the host's libm (tests/ compare the table with hvd_dct_matrix_libm() and with the oracle).
@@ -100,12 +39,6 @@ constexpr uint32_t kDctBits[16][64] = {
 #include "dct_table.inc"
 };
 __device__ __forceinline__ constexpr float dct_lit(int i, int k) { return __builtin_bit_cast(float, kDctBits[i][k]); }
-
-__device__ __forceinline__ void wave_lds_handover() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // KIND 0: uint8 gray 64x64 frames (luma from an LDS table). KIND 1: float 64x64 buffers (down-sampler output).
 // LIT: where stage 1 takes D[i][k] from. false: scalar loads (SGPR operands: v_mul_f32 s,v issues at half rate,
@@ -144,43 +77,9 @@ __global__ __launch_bounds__(256) void k_pdq_hash64(const void* __restrict__ in,
         const bool valid = f < n;  // wave-uniform
 
         if (valid) {
-            // ---- stage 0: column `lane` of the frame -------------------------------
             float a[64];
-            if (KIND == 0) {
-                const uint8_t* src = reinterpret_cast<const uint8_t*>(in) + f * 4096 + lane;
-#pragma unroll
-                for (int k = 0; k < 64; ++k) a[k] = lds.luma_lut[src[k * 64]];
-            } else {
-                const float* src = reinterpret_cast<const float*>(in) + f * 4096 + lane;
-#pragma unroll
-                for (int k = 0; k < 64; ++k) a[k] = src[k * 64];
-            }
-
-            // ---- quality -----------------------------------------------------------
-            int gsum;
-            if (KIND == 0) {
-                int qs = 0, qh = 0;
-#pragma unroll
-                for (int k = 0; k < 63; ++k) grad_term_gray(a[k], a[k + 1], qs);
-#pragma unroll
-                for (int k = 0; k < 64; ++k) grad_term_gray(a[k], wave_next_lane(a[k]), qh);
-                if (lane < 63) qs += qh;  // column 63 has no right neighbour
-                gsum = (int)wave_sum_f32((float)qs);
-            } else {
-                float gs = 0.0f, gh = 0.0f;
-                int cs_ = 0, ch_ = 0;
-#pragma unroll
-                for (int k = 0; k < 63; ++k) grad_term(a[k], a[k + 1], gs, cs_);
-#pragma unroll
-                for (int k = 0; k < 64; ++k) grad_term(a[k], wave_next_lane(a[k]), gh, ch_);
-                if (lane < 63) {  // column 63 has no right neighbour
-                    gs += gh;
-                    cs_ += ch_;
-                }
-                gsum = (int)wave_sum_f32(gs + (float)cs_);
-            }
-            int qual = gsum / 90;
-            qual = qual > 100 ? 100 : qual;
+            pdq_load_column<KIND>(lds, in, f, lane, a);   // stage 0
+            const int qual = pdq_quality<KIND>(a, lane);
 
             // ---- stage 1: T[i][lane] = sum_k D[i][k] * a[k], k ascending ------------
             if (LIT) {
@@ -227,57 +126,9 @@ __global__ __launch_bounds__(256) void k_pdq_hash64(const void* __restrict__ in,
         wave_lds_handover();
 
         if (valid) {
-            // ---- stage 2: B[i][j] = sum_k T[i][k] * D[j][k], k ascending ------------
-            const int j = lane & 15, i0 = lane >> 4;
-            float b[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int k4 = 0; k4 < 16; ++k4) {
-                const float4 dv = *reinterpret_cast<const float4*>(&lds.D[j][4 * k4]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float4 tv = *reinterpret_cast<const float4*>(&lds.T[wave][i0 + 4 * r][4 * k4]);
-                    b[r] = __fadd_rn(b[r], __fmul_rn(tv.x, dv.x));
-                    b[r] = __fadd_rn(b[r], __fmul_rn(tv.y, dv.y));
-                    b[r] = __fadd_rn(b[r], __fmul_rn(tv.z, dv.z));
-                    b[r] = __fadd_rn(b[r], __fmul_rn(tv.w, dv.w));
-                }
-            }
-
-            // ---- median: 128th smallest of the 256 coefficients (Torben's result) ---
-            uint32_t key[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const uint32_t u = __float_as_uint(b[r]);
-                key[r] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // order-preserving
-            }
-            uint32_t prefix = 0, mask = 0;
-            int kth = 128, remaining = 256;
-#pragma unroll 1
-            for (int bit = 31; bit >= 0; --bit) {
-                const uint32_t bsel = 1u << bit;
-                const uint32_t m2 = mask | bsel;
-                int cnt0 = 0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) cnt0 += __popcll(__ballot((key[r] & m2) == prefix));
-                if (kth > cnt0) {
-                    kth -= cnt0;
-                    remaining -= cnt0;
-                    prefix |= bsel;
-                } else {
-                    remaining = cnt0;
-                }
-                mask = m2;
-                if (remaining == 1) break;  // a single key carries this prefix: it is the median
-            }
-            if (mask != 0xFFFFFFFFu) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const unsigned long long bm = __ballot((key[r] & mask) == prefix);
-                    if (bm) prefix = __builtin_amdgcn_readlane(key[r], (int)__builtin_ctzll(bm));
-                }
-            }
-            const uint32_t mu = (prefix & 0x80000000u) ? (prefix ^ 0x80000000u) : ~prefix;
-            const float med = __uint_as_float(mu);
+            float b[4];
+            pdq_dct_stage2(lds, wave, lane, b);
+            const float med = wave_median256(b);
 
             // ---- bits: lane l, output r is coefficient (i0+4r, j) = bit l + 64 r ----
             unsigned long long m[4];
@@ -317,7 +168,7 @@ __global__ __launch_bounds__(256) void k_pdq_hash64(const void* __restrict__ in,
 //            B operand = luma(row 4ks + (lane>>4), column 16nb + (lane&15))
 //   stage 2  B(16x16) = T * D^T: A operand = T[i = lane&15][k] (through LDS), B operand = the same
 //            D fragments; output B[i = 4(lane>>4) + r][j = lane&15]
-// Quality, median and bit extraction are shared with the strict kernel (the quality needs the
+// Quality, median and bit extraction are the strict kernel's (hvd_pdq_dev.h; the quality needs the
 // column-per-lane view, so the frame bytes are read in both layouts; they are L1-hot).
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -363,9 +214,7 @@ __global__ __launch_bounds__(256, 3) void k_pdq_hash64_fma(const void* __restric
                     const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(in) + fn * 4096);
                     nb0 = src[lane]; nb1 = src[64 + lane]; nb2 = src[128 + lane]; nb3 = src[192 + lane];
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_handover();
             }
             // ---- quality: column `lane` of the frame, as in the strict kernel ---------------------
             {
@@ -379,30 +228,7 @@ __global__ __launch_bounds__(256, 3) void k_pdq_hash64_fma(const void* __restric
 #pragma unroll
                     for (int k = 0; k < 64; ++k) a[k] = src[k * 64];
                 }
-                int gsum;
-                if (KIND == 0) {  // gray bytes: the one-multiply form (grad_term_gray)
-                    int qs = 0, qh = 0;
-#pragma unroll
-                    for (int k = 0; k < 63; ++k) grad_term_gray(a[k], a[k + 1], qs);
-#pragma unroll
-                    for (int k = 0; k < 64; ++k) grad_term_gray(a[k], wave_next_lane(a[k]), qh);
-                    if (lane < 63) qs += qh;
-                    gsum = (int)wave_sum_f32((float)qs);
-                } else {
-                    float gs = 0.0f, gh = 0.0f;
-                    int cs_ = 0, ch_ = 0;
-#pragma unroll
-                    for (int k = 0; k < 63; ++k) grad_term(a[k], a[k + 1], gs, cs_);
-#pragma unroll
-                    for (int k = 0; k < 64; ++k) grad_term(a[k], wave_next_lane(a[k]), gh, ch_);
-                    if (lane < 63) {
-                        gs += gh;
-                        cs_ += ch_;
-                    }
-                    gsum = (int)wave_sum_f32(gs + (float)cs_);
-                }
-                int qual = gsum / 90;
-                qual = qual > 100 ? 100 : qual;
+                const int qual = pdq_quality<KIND>(a, lane);
                 if (lane == 0) quality[f] = qual;
             }
 
@@ -438,41 +264,7 @@ __global__ __launch_bounds__(256, 3) void k_pdq_hash64_fma(const void* __restric
 #pragma unroll
             for (int r = 0; r < 4; ++r) b[r] = acc[r];  // B[i = 4 g4 + r][j = c16]
 
-            // ---- median (same radix select as the strict kernel) ---------------------------------------
-            uint32_t key[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const uint32_t u = __float_as_uint(b[r]);
-                key[r] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-            }
-            uint32_t prefix = 0, mask = 0;
-            int kth = 128, remaining = 256;
-#pragma unroll 1
-            for (int bit = 31; bit >= 0; --bit) {
-                const uint32_t bsel = 1u << bit;
-                const uint32_t m2 = mask | bsel;
-                int cnt0 = 0;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) cnt0 += __popcll(__ballot((key[r] & m2) == prefix));
-                if (kth > cnt0) {
-                    kth -= cnt0;
-                    remaining -= cnt0;
-                    prefix |= bsel;
-                } else {
-                    remaining = cnt0;
-                }
-                mask = m2;
-                if (remaining == 1) break;
-            }
-            if (mask != 0xFFFFFFFFu) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const unsigned long long bm = __ballot((key[r] & mask) == prefix);
-                    if (bm) prefix = __builtin_amdgcn_readlane(key[r], (int)__builtin_ctzll(bm));
-                }
-            }
-            const uint32_t mu = (prefix & 0x80000000u) ? (prefix ^ 0x80000000u) : ~prefix;
-            const float med = __uint_as_float(mu);
+            const float med = wave_median256(b);
 
             // ---- bits: lane (g4, c16), output r is coefficient (4 g4 + r, c16) = hash bit 64 g4 + 16 r + c16:
             //      64-bit word w of the hash takes 16 bits from each of the four ballots
@@ -494,14 +286,9 @@ __global__ __launch_bounds__(256, 3) void k_pdq_hash64_fma(const void* __restric
 __global__ __launch_bounds__(256) void k_luma64_rgb(const uint8_t* __restrict__ rgb, long long npix,
                                                     float* __restrict__ out) {
     for (long long p = (long long)blockIdx.x * 256 + threadIdx.x; p < npix; p += (long long)gridDim.x * 256) {
-        const float r = (float)rgb[3 * p], g = (float)rgb[3 * p + 1], b = (float)rgb[3 * p + 2];
-        float y = __fmul_rn(0.299f, r);
-        y = __fadd_rn(y, __fmul_rn(0.587f, g));
-        y = __fadd_rn(y, __fmul_rn(0.114f, b));
-        out[p] = y;
+        out[p] = luma_rgb((float)rgb[3 * p], (float)rgb[3 * p + 1], (float)rgb[3 * p + 2]);
     }
 }
-
 
 // ---------------------------------------------------------------------------
 // Down-sampler for frames that are not already 64x64 (the reference feeds 512x512
@@ -514,89 +301,14 @@ __global__ __launch_bounds__(256) void k_luma64_rgb(const uint8_t* __restrict__ 
 // so that (a) the input is staged through an LDS ring with coalesced loads, (b) the
 // stores are coalesced across lanes, and (c) four launches of the same kernel give
 // rows, cols, rows, cols. Passes 3 and 4 only emit the 64 sample positions the
-// decimation keeps (the recurrence still runs over every element).
-constexpr int kTW = 32;           // columns per staged tile
-constexpr int kRing = 2 * kTW;    // LDS ring (window <= 32 looks back at most one tile)
-
+// decimation keeps (the recurrence still runs over every element). The pass itself is hvd_pdq_dev.h's box_scan_lines,
+// shared with k_autocrop.hip's k_box_scan_rect.
 template <int SRC>  // 0: float, 1: gray u8, 3: rgb24 (luma fused into the load)
 __global__ __launch_bounds__(64) void k_box_scan_T(const void* __restrict__ in, float* __restrict__ out, int lines,
                                                    int len, int win, int nsel, long long in_frame_stride,
                                                    long long out_frame_stride) {
-    __shared__ float ring[64][kRing + 1];
-    const int lane = threadIdx.x;
-    const int line0 = blockIdx.x * 64;
-    const long long frame = blockIdx.y;
-    const int my_line = line0 + lane;
-    const int half = (win + 2) / 2;
-    const int steps = len + half - 1;
-    const int out_lines = lines;  // transposed output: [kept positions][lines]
-    float* dst = out + frame * out_frame_stride;
-
-    float sum = 0.0f;
-    int cur = 0;
-    int next_j = 0;
-    int next_sel = nsel ? (int)(((0 + 0.5) * len) / 64) : 0;
-
-    for (int s = 0; s < steps; ++s) {
-        if (s < len && (s % kTW) == 0) {
-            // stage columns [s, s+kTW) of the 64 lines into ring slot (s/kTW)&1
-            __syncthreads();
-            const int c = lane & (kTW - 1);
-            const int col = s + c;
-#pragma unroll 4
-            for (int rr = lane / kTW; rr < 64; rr += 64 / kTW) {
-                const int ln = line0 + rr;
-                float v = 0.0f;
-                if (ln < lines && col < len) {
-                    const long long e = (long long)ln * len + col;
-                    if (SRC == 0) {
-                        v = reinterpret_cast<const float*>(in)[frame * in_frame_stride + e];
-                    } else if (SRC == 1) {
-                        v = luma_gray(reinterpret_cast<const uint8_t*>(in)[frame * in_frame_stride + e]);
-                    } else {
-                        const uint8_t* p = reinterpret_cast<const uint8_t*>(in) + frame * in_frame_stride + 3 * e;
-                        const float r = (float)p[0], g = (float)p[1], b = (float)p[2];
-                        v = __fmul_rn(0.299f, r);
-                        v = __fadd_rn(v, __fmul_rn(0.587f, g));
-                        v = __fadd_rn(v, __fmul_rn(0.114f, b));
-                    }
-                }
-                ring[rr][col & (kRing - 1)] = v;
-            }
-            __syncthreads();
-        }
-        if (s < len) {
-            sum = __fadd_rn(sum, ring[lane][s & (kRing - 1)]);
-            if (s < win) ++cur;
-        }
-        if (s >= win) {
-            sum = __fsub_rn(sum, ring[lane][(s - win) & (kRing - 1)]);
-            if (s >= len) --cur;
-        }
-        if (s >= half - 1) {
-            const int oi = s - (half - 1);
-            bool keep = true;
-            int slot = oi;
-            if (nsel) {
-                keep = (next_j < nsel) && (oi == next_sel);
-                slot = next_j;
-            }
-            if (keep) {
-                float o;
-                if ((cur & (cur - 1)) == 0)
-                    o = __fmul_rn(sum, 1.0f / (float)cur);  // exact: power-of-two divisor
-                else
-                    o = __fdiv_rn(sum, (float)cur);
-                if (my_line < lines) dst[(long long)slot * out_lines + my_line] = o;
-                if (nsel) {
-                    ++next_j;
-                    next_sel = (int)(((next_j + 0.5) * len) / 64);
-                }
-            }
-        }
-    }
+    box_scan_lines<SRC>(in, out, in_frame_stride, out_frame_stride, len, 0, 0, lines, len, win, nsel);
 }
-
 
 // ---------------------------------------------------------------------------
 // Fused down-sampler for the reference's frame geometry, 512x512 (window 4 on both axes):
@@ -648,10 +360,7 @@ __device__ __forceinline__ void strip_luma(const StripRaw<CH, S>& raw, float (&v
             const float r = (float)((w[b0 >> 2] >> (8 * (b0 & 3))) & 0xFFu);
             const float g = (float)((w[b1 >> 2] >> (8 * (b1 & 3))) & 0xFFu);
             const float b = (float)((w[b2 >> 2] >> (8 * (b2 & 3))) & 0xFFu);
-            float yv = __fmul_rn(0.299f, r);
-            yv = __fadd_rn(yv, __fmul_rn(0.587f, g));
-            yv = __fadd_rn(yv, __fmul_rn(0.114f, b));
-            v[c] = yv;
+            v[c] = luma_rgb(r, g, b);
         }
     } else {
         uint32_t w[S / 4];
@@ -902,12 +611,6 @@ constexpr int kWC = 16;                                 // elements per register
 constexpr int kWStateFloats = (kWNX + 1) * 5 * 32;      // pass-B state: [column tile][5][column]
 constexpr int kWScratchFloats = kWStateFloats;
 
-__device__ __forceinline__ void wave_mem_sync() {  // stores of this wave become visible to its other lanes
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // One chunk of upstream's running sum (window 4): step r adds x[r] and drops the input four steps
 // back, which is x[r-4] inside the chunk and lag[r] (the previous chunk's last four inputs) before.
 // o[r] is the sum after step r = 4x the filter output two positions behind the input.
@@ -993,9 +696,6 @@ template <int N>
 __device__ __forceinline__ uint32_t fifo_word(const uint4 (&f)[N], const int k) {  // k is a compile-time constant after unrolling
     const uint4 q = f[k >> 2];
     return (k & 3) == 0 ? q.x : (k & 3) == 1 ? q.y : (k & 3) == 2 ? q.z : q.w;
-}
-__device__ __forceinline__ float luma_rgb_f(const float r, const float g, const float b) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(0.299f, r), __fmul_rn(0.587f, g)), __fmul_rn(0.114f, b));
 }
 
 // ds_write_addtid_b32: LDS address = M0 + offset + 4 * lane, no address VGPR. It is the one LDS store that runs at
@@ -1144,7 +844,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
                         for (int q = 0; q < SQ; ++q)
                             fifo[q] = *reinterpret_cast<const uint4*>(park + cl5 * TileLoad<CH>::RS + q * 16);
                     }
-                    wave_mem_sync();  // ... before the arriving unit is parked there
+                    wave_lds_handover();  // ... before the arriving unit is parked there
                     if (stage_now) unit_stage<CH>(stage, park, lane, pre[par]);
                 }
                 {   // THE FETCH SLOT: every step issues the six loads of one unit into pre[par] (uniform memory schedule, above) --
@@ -1179,13 +879,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
                     }
                     if (tx <= kWNX) {
                         if (stage_now) {
-                            wave_mem_sync();
+                            wave_lds_handover();
                             if (half == hr) {
 #pragma unroll
                                 for (int q = 0; q < SQ; ++q)
                                     fifo[q] = *reinterpret_cast<const uint4*>(stage + cl5 * TileLoad<CH>::RS + q * 16);
                             }
-                            wave_mem_sync();  // the staged bytes are in registers before A overwrites them
+                            wave_lds_handover();  // the staged bytes are in registers before A overwrites them
                         }
                         if (tx <= 1 && txl == 0) {  // a new line starts from the all-zero state
                             sA = 0.0f;
@@ -1199,10 +899,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
                             float v[4];
                             if (CH == 3) {
                                 const uint32_t w0 = fifo_word(fifo, 3 * j), w1 = fifo_word(fifo, 3 * j + 1), w2 = fifo_word(fifo, 3 * j + 2);
-                                v[0] = luma_rgb_f((float)(w0 & 0xFFu), (float)((w0 >> 8) & 0xFFu), (float)((w0 >> 16) & 0xFFu));
-                                v[1] = luma_rgb_f((float)(w0 >> 24), (float)(w1 & 0xFFu), (float)((w1 >> 8) & 0xFFu));
-                                v[2] = luma_rgb_f((float)((w1 >> 16) & 0xFFu), (float)(w1 >> 24), (float)(w2 & 0xFFu));
-                                v[3] = luma_rgb_f((float)((w2 >> 8) & 0xFFu), (float)((w2 >> 16) & 0xFFu), (float)(w2 >> 24));
+                                v[0] = luma_rgb((float)(w0 & 0xFFu), (float)((w0 >> 8) & 0xFFu), (float)((w0 >> 16) & 0xFFu));
+                                v[1] = luma_rgb((float)(w0 >> 24), (float)(w1 & 0xFFu), (float)((w1 >> 8) & 0xFFu));
+                                v[2] = luma_rgb((float)((w1 >> 16) & 0xFFu), (float)(w1 >> 24), (float)(w2 & 0xFFu));
+                                v[3] = luma_rgb((float)((w2 >> 8) & 0xFFu), (float)((w2 >> 16) & 0xFFu), (float)(w2 >> 24));
                             } else {
                                 const uint32_t w0 = fifo_word(fifo, j);
 #pragma unroll
@@ -1234,7 +934,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
                     }
                     if (tx >= kWNX && txl == kWNX) lds_store1_addtid<0>(buf_lds, tailA);  // element (row = lane, column 0)
                 }
-                wave_mem_sync();
+                wave_lds_handover();
 
                 // ---------------- B: rep-1 down the buffer columns, in place (lane = half, column) --------
                 {
@@ -1254,7 +954,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
                                 x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
                             }
                         }
-                        wave_mem_sync();  // every lane holds its inputs: the buffer may change layout under them
+                        wave_lds_handover();  // every lane holds its inputs: the buffer may change layout under them
 #pragma unroll
                         for (int g = 0; g < 8; ++g) {
                             float o[4];
@@ -1301,7 +1001,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
                         buf_st(rs, si + 96, stl[2]); buf_st(rs, si + 128, stl[3]);
                     }
                 }
-                wave_mem_sync();
+                wave_lds_handover();
 
                 // ---------------- C: rep-2 along the row over the buffer columns (lane = buffer row) -------
                 // buffer column c <-> input index X = 32t-2+c; output X-2 is decimation sample j = 4t-1+c/8 iff c
@@ -1339,14 +1039,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
-                    wave_mem_sync();  // every lane has read its buffer row; the samples may now overwrite it
+                    wave_lds_handover();  // every lane has read its buffer row; the samples may now overwrite it
                     if (store) {  // smp[k][lane]: lane-contiguous, 256 bytes per slot
                         lds_store4_addtid<0, SMPS * 4>(buf_lds, sv[0], sv[1], sv[2], sv[3]);
                     } else if (tail) {
                         lds_store1_addtid<0>(buf_lds, sv[0]);
                     }
                 }
-                wave_mem_sync();  // buf is rewritten by the next step; smp is read below
+                wave_lds_handover();  // buf is rewritten by the next step; smp is read below
 
                 // ---------------- D: rep-2 down the sample columns (lane j owns sample column j = slot j+1) ----
                 // Slot group g = slot/4 is produced by the lower half (rows 0..31) in step g and by the upper half
@@ -1391,7 +1091,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(CH == 3 ? 3 
 #pragma unroll
                     for (int i = 0; i < 4; ++i) buf_st(rd, di[i], dv[i]);
                 }
-                wave_mem_sync();  // smp is rewritten by the next step
+                wave_lds_handover();  // smp is rewritten by the next step
             }
             }
         }
@@ -1510,8 +1210,6 @@ hipError_t launch_pdq_hash64(const void* d_in, int kind, int64_t n, const float*
 #undef HVD_K1
     return hipGetLastError();
 }
-
-static int jarosz_window(int dim) { return (dim + 2 * 64 - 1) / (2 * 64); }
 
 // Workspace (floats per frame) the down-sampler needs besides the 64x64 output.
 size_t pdq_downsample_ws_floats(int h, int w) { return 2 * (size_t)h * w + (size_t)64 * h; }

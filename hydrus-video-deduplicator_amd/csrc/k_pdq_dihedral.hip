@@ -11,9 +11,9 @@
 // 4 bit transposes per frame.
 //
 // k_pdq_dihedral64: one wave64 per frame, 4 frames per workgroup, static grid stride -- k_pdq_hash64's
-// strict layout (k_pdq.hip) up to the median, with the same bit-exactness contract: stage 1 and 2
-// are __fmul_rn/__fadd_rn, k ascending, in K1's order, with the context's DCT matrix, so variant 0
-// is bit-identical to K1's hash and the coefficients are the oracle's.
+// strict layout (k_pdq.hip) up to the median, built from the same definitions (hvd_pdq_dev.h, the home of the
+// bit-exactness contract): stage 1 and 2 are __fmul_rn/__fadd_rn, k ascending, in K1's order, with the context's
+// DCT matrix, so variant 0 is bit-identical to K1's hash and the coefficients are the oracle's.
 //   stage 0  lane j loads column j of the 64x64 frame
 //   quality  as K1
 //   stage 1  T = D*A: lane j owns column j, D[i][k] wave-uniform -> scalar loads
@@ -26,95 +26,9 @@
 #include <stdint.h>
 
 #include "hvd_kernels.h"
+#include "hvd_pdq_dev.h"
 
 namespace {
-
-constexpr int kWaves = 4;  // frames in flight per workgroup
-constexpr int kLd = 68;    // padded LDS row stride (floats), as k_pdq.hip
-
-struct alignas(16) DihedralLds {
-    float T[kWaves][16][kLd];
-    float D[16][kLd];
-    float luma_lut[256];
-};
-
-// ---- helpers copied from k_pdq.hip (kept there unchanged; see that file for their derivations) ----
-__device__ __forceinline__ float luma_gray(uint32_t g) {
-    const float v = (float)g;
-    float y = __fmul_rn(0.299f, v);
-    y = __fadd_rn(y, __fmul_rn(0.587f, v));
-    y = __fadd_rn(y, __fmul_rn(0.114f, v));
-    return y;
-}
-
-// |(int)(((u - v) * 100) / 255)| for float luma: trunc(|x| * (float below 1/255)) plus a remainder correction
-__device__ __forceinline__ void grad_term(float u, float v, float& acc_m, int& acc_c) {
-    const float ax = fabsf(__fmul_rn(__fsub_rn(u, v), 100.0f));
-    const float m = truncf(__fmul_rn(ax, 0x1.0101p-8f));
-    const float r = __fmaf_rn(-255.0f, m, ax);
-    acc_m += m;
-    acc_c += (r >= 255.0f) ? 1 : 0;
-}
-
-// the same term for luma of gray bytes: one multiply by RN(100/255), exact for all 256 x 256 byte pairs
-__device__ __forceinline__ void grad_term_gray(float u, float v, int& acc) {
-    acc += (int)__fmul_rn(fabsf(__fsub_rn(u, v)), 0x1.919192p-2f);
-}
-
-__device__ __forceinline__ float wave_next_lane(float v) {  // lane l reads lane l+1 (DPP wave_shl:1)
-    const int x = __float_as_int(v);
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, x, 0x130, 0xF, 0xF, true));
-}
-
-__device__ __forceinline__ float wave_sum_f32(float v) {  // exact: integer-valued, far below 2^24
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ void wave_lds_handover() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// 128th smallest of the wave's 256 values (4 per lane): K1's radix select over order-preserving keys
-__device__ __forceinline__ float wave_median256(const float (&b)[4]) {
-    uint32_t key[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const uint32_t u = __float_as_uint(b[r]);
-        key[r] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    uint32_t prefix = 0, mask = 0;
-    int kth = 128, remaining = 256;
-#pragma unroll 1
-    for (int bit = 31; bit >= 0; --bit) {
-        const uint32_t bsel = 1u << bit;
-        const uint32_t m2 = mask | bsel;
-        int cnt0 = 0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) cnt0 += __popcll(__ballot((key[r] & m2) == prefix));
-        if (kth > cnt0) {
-            kth -= cnt0;
-            remaining -= cnt0;
-            prefix |= bsel;
-        } else {
-            remaining = cnt0;
-        }
-        mask = m2;
-        if (remaining == 1) break;  // a single key carries this prefix: it is the median
-    }
-    if (mask != 0xFFFFFFFFu) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const unsigned long long bm = __ballot((key[r] & mask) == prefix);
-            if (bm) prefix = __builtin_amdgcn_readlane(key[r], (int)__builtin_ctzll(bm));
-        }
-    }
-    const uint32_t mu = (prefix & 0x80000000u) ? (prefix ^ 0x80000000u) : ~prefix;
-    return __uint_as_float(mu);
-}
 
 // Hash words of B' > median (word r = bits 64r..64r+63 = lane l, value r) for the sign pattern `neg` of this lane.
 __device__ __forceinline__ void signed_bits(const float (&b)[4], bool neg, unsigned long long (&m)[4]) {
@@ -149,7 +63,7 @@ template <int KIND>
 __global__ __launch_bounds__(256) void k_pdq_dihedral64(const void* __restrict__ in, long long n,
                                                         const float* __restrict__ dct, uint8_t* __restrict__ hashes,
                                                         int32_t* __restrict__ quality) {
-    __shared__ DihedralLds lds;
+    __shared__ PdqLds lds;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
@@ -163,43 +77,9 @@ __global__ __launch_bounds__(256) void k_pdq_dihedral64(const void* __restrict__
         const bool valid = f < n;  // wave-uniform
 
         if (valid) {
-            // ---- stage 0: column `lane` of the frame ----
             float a[64];
-            if (KIND == 0) {
-                const uint8_t* src = reinterpret_cast<const uint8_t*>(in) + f * 4096 + lane;
-#pragma unroll
-                for (int k = 0; k < 64; ++k) a[k] = lds.luma_lut[src[k * 64]];
-            } else {
-                const float* src = reinterpret_cast<const float*>(in) + f * 4096 + lane;
-#pragma unroll
-                for (int k = 0; k < 64; ++k) a[k] = src[k * 64];
-            }
-
-            // ---- quality (one value for all 8 variants) ----
-            int gsum;
-            if (KIND == 0) {
-                int qs = 0, qh = 0;
-#pragma unroll
-                for (int k = 0; k < 63; ++k) grad_term_gray(a[k], a[k + 1], qs);
-#pragma unroll
-                for (int k = 0; k < 64; ++k) grad_term_gray(a[k], wave_next_lane(a[k]), qh);
-                if (lane < 63) qs += qh;  // column 63 has no right neighbour
-                gsum = (int)wave_sum_f32((float)qs);
-            } else {
-                float gs = 0.0f, gh = 0.0f;
-                int cs_ = 0, ch_ = 0;
-#pragma unroll
-                for (int k = 0; k < 63; ++k) grad_term(a[k], a[k + 1], gs, cs_);
-#pragma unroll
-                for (int k = 0; k < 64; ++k) grad_term(a[k], wave_next_lane(a[k]), gh, ch_);
-                if (lane < 63) {
-                    gs += gh;
-                    cs_ += ch_;
-                }
-                gsum = (int)wave_sum_f32(gs + (float)cs_);
-            }
-            int qual = gsum / 90;
-            qual = qual > 100 ? 100 : qual;
+            pdq_load_column<KIND>(lds, in, f, lane, a);             // stage 0
+            const int qual = pdq_quality<KIND>(a, lane);  // one value for all 8 variants
 
             // ---- stage 1: T[i][lane] = sum_k D[i][k] * a[k], k ascending ----
 #pragma unroll 1
@@ -225,21 +105,9 @@ __global__ __launch_bounds__(256) void k_pdq_dihedral64(const void* __restrict__
         wave_lds_handover();  // T[wave] is private to this wave
 
         if (valid) {
-            // ---- stage 2: B[i][j] = sum_k T[i][k] * D[j][k], k ascending ----
-            const int j = lane & 15, i0 = lane >> 4;
-            float b[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-            for (int k4 = 0; k4 < 16; ++k4) {
-                const float4 dv = *reinterpret_cast<const float4*>(&lds.D[j][4 * k4]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float4 tv = *reinterpret_cast<const float4*>(&lds.T[wave][i0 + 4 * r][4 * k4]);
-                    b[r] = __fadd_rn(b[r], __fmul_rn(tv.x, dv.x));
-                    b[r] = __fadd_rn(b[r], __fmul_rn(tv.y, dv.y));
-                    b[r] = __fadd_rn(b[r], __fmul_rn(tv.z, dv.z));
-                    b[r] = __fadd_rn(b[r], __fmul_rn(tv.w, dv.w));
-                }
-            }
+            float b[4];
+            pdq_dct_stage2(lds, wave, lane, b);
+            const int j = lane & 15, i0 = lane >> 4;  // b[r] = B[i0 + 4r][j]
 
             // ---- 4 sign patterns -> 4 medians -> 8 hashes ----
             const bool nx = (j & 1) == 0;   // sx(j) = -1
