@@ -30,6 +30,15 @@ VALIGN_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("q_hits", "<u4"), ("t_hits
                          ("band_votes", "<u4"), ("q_aligned", "<u4"), ("t_aligned", "<u4"), ("q_first", "<i4"),
                          ("q_last", "<i4"), ("t_first", "<i4"), ("t_last", "<i4")])
 ALIGN_LDS_BINS = 4096  # HVD_ALIGN_LDS_BINS
+ALIGN_MAX_SEGMENTS = 8  # HVD_ALIGN_MAX_SEGMENTS
+# one segment of a pair (hvd_vsegment): the words of VALIGN_DTYPE from offset on, on the frame hits no earlier segment owns
+VSEGMENT_DTYPE = np.dtype([("offset", "<i4"), ("band_votes", "<u4"), ("q_aligned", "<u4"), ("t_aligned", "<u4"),
+                           ("q_first", "<i4"), ("q_last", "<i4"), ("t_first", "<i4"), ("t_last", "<i4")])
+# one video pair aligned on up to ALIGN_MAX_SEGMENTS offsets (hvd_vsegments): seg[0].offset = INT32_MIN with n_segments = 0
+# marks a pair the device entry could not align
+VSEGMENTS_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("q_hits", "<u4"), ("t_hits", "<u4"), ("n_segments", "<u4"),
+                            ("q_covered", "<u4"), ("t_covered", "<u4"), ("reserved", "<u4"),
+                            ("seg", VSEGMENT_DTYPE, (ALIGN_MAX_SEGMENTS,))])
 ALIGN_MAX_BINS = 1 << 20
 
 # name -> (restype, argtypes); every symbol include/hvd_mi355x.h declares.
@@ -60,6 +69,7 @@ SIGNATURES = {
     "hvd_vpdq_match_videos_cross": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _i64,
                                            C.POINTER(_i64)]),
     "hvd_vpdq_align_videos": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp]),
+    "hvd_vpdq_align_segments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _int, _int, _vp]),
     "hvd_hasher_create": (_int, [_int, _int, _int, _i64, C.POINTER(_vp)]),
     "hvd_hasher_push": (_int, [_vp, _vp]),
     "hvd_hasher_set_threads": (_int, [_vp, _int]),
@@ -108,6 +118,9 @@ SIGNATURES = {
     "hvd_dev_kept_positions": (_int, [_vp, _i64, _vp, _i64, _int, _vp]),
     "hvd_align_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
     "hvd_dev_vpdq_align_videos": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _sz, _vp]),
+    "hvd_segments_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
+    "hvd_dev_vpdq_align_segments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _sz,
+                                           _vp]),
     "hvd_dev_vpdq_match_videos": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _i64, _vp]),
     "hvd_dev_vpdq_emit_again": (_int, [_vp, _i64, _vp]),
     "hvd_dev_vpdq_match_videos_cross": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _int, _int, _int, _vp, _i64,

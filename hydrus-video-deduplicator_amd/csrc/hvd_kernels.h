@@ -142,6 +142,15 @@ hipError_t launch_valign(const void* d_hashes_q, const long long* d_offsets_q, u
                          const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, void* d_scratch,
                          size_t scratch_bytes, hvd_valign* d_out, hipStream_t s);
 
+// Multi-segment time alignment (k_valign_segments.hip): launch_valign's operands and two launches, up to max_segments
+// greedy rounds per pair; a slot of d_scratch (segments_scratch_bytes(max_bins)) also holds the pair's taken sets.
+size_t segments_scratch_bytes(unsigned long long max_bins);
+hipError_t launch_valign_segments(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
+                                  const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
+                                  const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack,
+                                  uint32_t max_segments, uint32_t min_band_votes, void* d_scratch, size_t scratch_bytes,
+                                  hvd_vsegments* d_out, hipStream_t s);
+
 // Synthetic 64x64 gray video frames generated in HBM (k_synth.hip; workload generator, not on the hashing path).
 hipError_t launch_synth_frames64(uint8_t* d_out, long long v0, uint32_t frames_per_video, unsigned long long n_frames,
                                  uint64_t seed, const int32_t* d_copy_of, hipStream_t s);

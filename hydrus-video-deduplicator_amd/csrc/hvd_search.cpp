@@ -984,7 +984,7 @@ int hvd_dev_vpdq_match_videos_cross(const void* d_img_q, int64_t nq, const void*
                             d_out, cap, d_count);
 }
 
-/* ---- time alignment of listed video pairs (k_valign.hip) ---- */
+/* ---- time alignment of listed video pairs (k_valign.hip, k_valign_segments.hip) ---- */
 
 int hvd_dev_kept_positions(const void* d_quality, int64_t n, const void* d_offsets, int64_t V, int min_quality, void* d_out_pos) {
     if (int rc = need_ready()) return rc;
@@ -1026,6 +1026,35 @@ int hvd_dev_vpdq_align_videos(const void* d_hashes_q, const void* d_offsets_q, i
     return HVD_OK;
 }
 
+int hvd_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) {
+    if (!out_bytes || max_bins < 0 || max_bins > (1ll << 20)) return fail(HVD_ERR_ARG, "max_bins=%lld: need 0..2^20", (long long)max_bins);
+    *out_bytes = hvd::segments_scratch_bytes((unsigned long long)max_bins);
+    return HVD_OK;
+}
+
+int hvd_dev_vpdq_align_segments(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                                const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                                const void* d_pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
+                                void* d_scratch, size_t scratch_bytes, void* d_out) {
+    if (int rc = need_ready()) return rc;
+    if (VQ < 0 || VT < 0 || VQ >= (1ll << 31) || VT >= (1ll << 31) || M < 0) return fail(HVD_ERR_ARG, "bad counts");
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    if (slack < 0 || slack > 16) return fail(HVD_ERR_ARG, "slack=%d out of range [0,16]", slack);
+    if (max_segments < 1 || max_segments > HVD_ALIGN_MAX_SEGMENTS)
+        return fail(HVD_ERR_ARG, "max_segments=%d out of range [1,%d]", max_segments, HVD_ALIGN_MAX_SEGMENTS);
+    if (min_band_votes < 1) return fail(HVD_ERR_ARG, "min_band_votes=%d: need >= 1", min_band_votes);
+    if (M == 0) return HVD_OK;
+    if (!d_offsets_q || !d_offsets_t || !d_pairs || !d_out) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if (((uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch | (uintptr_t)d_out) & 15u)
+        return fail(HVD_ERR_ARG, "hashes, scratch and records must be 16-byte aligned");
+    HIP_TRY(hvd::launch_valign_segments(d_hashes_q, (const long long*)d_offsets_q, (uint32_t)VQ, (const int32_t*)d_pos_q, d_hashes_t,
+                                        (const long long*)d_offsets_t, (uint32_t)VT, (const int32_t*)d_pos_t,
+                                        (const uint32_t*)d_pairs, (unsigned long long)M, (uint32_t)max_dist, (uint32_t)slack,
+                                        (uint32_t)max_segments, (uint32_t)min_band_votes, d_scratch, scratch_bytes,
+                                        (hvd_vsegments*)d_out, g.stream));
+    return HVD_OK;
+}
+
 // positions of one library: non-negative, strictly increasing inside a video, below 2^20
 static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V, const char* side) {
     if (!pos) return HVD_OK;
@@ -1037,9 +1066,12 @@ static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V
     return HVD_OK;
 }
 
-int hvd_vpdq_align_videos(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
-                          const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
-                          const uint32_t* pairs, int64_t M, int max_dist, int slack, hvd_valign* out) {
+// The host-buffer form of both alignments: validate, stage, run, copy the records back. max_segments 0: hvd_valign records
+// (hvd_dev_vpdq_align_videos); else hvd_vsegments records (hvd_dev_vpdq_align_segments).
+static int align_from_host(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                           const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                           const uint32_t* pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
+                           void* out) {
     if (int rc = need_ready()) return rc;
     if (M < 0 || (M > 0 && (!pairs || !out))) return fail(HVD_ERR_ARG, "bad pair list / output buffer");
     if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
@@ -1094,15 +1126,38 @@ int hvd_vpdq_align_videos(const uint8_t* frames_q, const int64_t* offsets_q, int
         return rc;
     }
     SCR(S_APAIRS, 8 * (size_t)M, d_pairs);
-    SCR(S_AOUT, sizeof(hvd_valign) * (size_t)M, d_out);
-    const size_t sb = hvd::align_scratch_bytes((unsigned long long)max_bins);
+    const size_t out_bytes = (max_segments ? sizeof(hvd_vsegments) : sizeof(hvd_valign)) * (size_t)M;
+    SCR(S_AOUT, out_bytes, d_out);
+    const size_t sb = max_segments ? hvd::segments_scratch_bytes((unsigned long long)max_bins)
+                                   : hvd::align_scratch_bytes((unsigned long long)max_bins);
     if (sb) SCR(S_ASCR, sb, d_scr);
     HIP_TRY(hipMemcpyAsync(d_pairs, pairs, 8 * (size_t)M, hipMemcpyHostToDevice, g.stream));
-    if (int rc = hvd_dev_vpdq_align_videos(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack, d_scr, sb, d_out))
+    if (int rc = max_segments ? hvd_dev_vpdq_align_segments(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack,
+                                                            max_segments, min_band_votes, d_scr, sb, d_out)
+                              : hvd_dev_vpdq_align_videos(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack,
+                                                          d_scr, sb, d_out))
         return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out, sizeof(hvd_valign) * (size_t)M, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     return HVD_OK;
+}
+
+int hvd_vpdq_align_videos(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                          const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                          const uint32_t* pairs, int64_t M, int max_dist, int slack, hvd_valign* out) {
+    return align_from_host(frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, 0,
+                           1, out);
+}
+
+int hvd_vpdq_align_segments(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                            const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                            const uint32_t* pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
+                            hvd_vsegments* out) {
+    if (max_segments < 1 || max_segments > HVD_ALIGN_MAX_SEGMENTS)
+        return fail(HVD_ERR_ARG, "max_segments=%d out of range [1,%d]", max_segments, HVD_ALIGN_MAX_SEGMENTS);
+    if (min_band_votes < 1) return fail(HVD_ERR_ARG, "min_band_votes=%d: need >= 1", min_band_votes);
+    return align_from_host(frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack,
+                           max_segments, min_band_votes, out);
 }
 
 #ifndef HVD_NO_BENCH_SYMBOLS

@@ -24,7 +24,7 @@ import time
 import numpy as np
 
 from . import _lib, search, vpdq
-from ._lib import VALIGN_DTYPE, VMATCH_DTYPE, DeviceBuffer
+from ._lib import VALIGN_DTYPE, VMATCH_DTYPE, VSEGMENTS_DTYPE, DeviceBuffer
 
 
 def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
@@ -323,10 +323,24 @@ class DeviceLibrary:
         are; the pair list goes up, the records come back. Positions: those of from_raw_hashes(positions=True), else the
         index inside the kept video."""
         lib = _lib.ensure()
+        return self._align(records, slack, max_dist, VALIGN_DTYPE, lib.hvd_align_scratch_bytes, lib.hvd_dev_vpdq_align_videos, ())
+
+    def align_segments(self, records, slack: int = search.ALIGN_SLACK, max_dist: int | None = None,
+                       max_segments: int = _lib.ALIGN_MAX_SEGMENTS, min_band_votes: int = 1) -> np.ndarray:
+        """hvd_dev_vpdq_align_segments of the listed pairs of this library against itself: one VSEGMENTS_DTYPE record per
+        pair, in their order (search.align_segments on what is in HBM; operands and positions as `align`)."""
+        lib = _lib.ensure()
+        return self._align(records, slack, max_dist, VSEGMENTS_DTYPE, lib.hvd_segments_scratch_bytes,
+                           lib.hvd_dev_vpdq_align_segments, (int(max_segments), int(min_band_votes)))
+
+    def _align(self, records, slack, max_dist, dtype, scratch_bytes, entry, extra: tuple) -> np.ndarray:
+        """One device-resident alignment call over this library against itself: `entry` with the operands both alignments
+        share, `extra` between slack and the scratch, records of `dtype` back."""
+        lib = _lib.ensure()
         pairs = search.pair_array(records)
         M = pairs.shape[0]
         max_dist = _default_max_dist(max_dist)
-        out = np.zeros(M, dtype=VALIGN_DTYPE)
+        out = np.zeros(M, dtype=dtype)
         out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
         if M == 0 or max_dist < 0:
             return out
@@ -338,17 +352,16 @@ class DeviceLibrary:
             limit = self._position_limit
         max_bins = min(2 * max(limit, 1) - 1 + 2 * int(slack), _lib.ALIGN_MAX_BINS)
         sb = C.c_size_t(0)
-        _lib.check(lib.hvd_align_scratch_bytes(max_bins, C.byref(sb)))
+        _lib.check(scratch_bytes(max_bins, C.byref(sb)))
         with _DeviceScope() as scope:
             d_pairs = scope.temp(DeviceBuffer.from_array(pairs))
-            d_out = scope.temp(DeviceBuffer(VALIGN_DTYPE.itemsize * M))
+            d_out = scope.temp(DeviceBuffer(dtype.itemsize * M))
             d_scr = scope.temp(DeviceBuffer(sb.value) if sb.value else None)
             d_pos = self.d_positions.ptr if self.d_positions is not None else None
-            _lib.check(lib.hvd_dev_vpdq_align_videos(self.d_hashes.ptr, self.d_offsets.ptr, self.n_videos, d_pos,
-                                                     self.d_hashes.ptr, self.d_offsets.ptr, self.n_videos, d_pos, d_pairs.ptr,
-                                                     M, max_dist, int(slack), d_scr.ptr if d_scr else None, sb.value,
-                                                     d_out.ptr))
-            aligned = d_out.to_array(VALIGN_DTYPE, M)  # (the copy waits for the library stream)
+            _lib.check(entry(self.d_hashes.ptr, self.d_offsets.ptr, self.n_videos, d_pos, self.d_hashes.ptr, self.d_offsets.ptr,
+                             self.n_videos, d_pos, d_pairs.ptr, M, max_dist, int(slack), *extra,
+                             d_scr.ptr if d_scr else None, sb.value, d_out.ptr))
+            aligned = d_out.to_array(dtype, M)  # (the copy waits for the library stream)
             lib.hvd_dev_sync()  # nothing may still run on a buffer that is freed here
         return aligned
 
@@ -551,6 +564,27 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
     return pairs, recs, None
 
 
+def _aligned_search_on_device(d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library, align, fold):
+    """The chain of the excerpt searches on frames in HBM, one device: hash -> quality filter + CSR, with the kept frames' raw
+    positions (`DeviceLibrary.from_raw_hashes(positions=True)`) -> video search -> align(library, records) -> fold(aligned,
+    lengths, similarity). -> (fold's result, search records, alignment records, library or None)."""
+    library = _hashed_library(
+        raw_offsets, 0, 1, None, lambda mine: hash_frames_on_device(d_frames_ptr, int(mine[-1]), h, w, channels), 32,
+        lambda *raw: DeviceLibrary.from_raw_hashes(*raw, positions=bool(positions)), None)
+    try:
+        recs = library.match_videos()
+        aligned = align(library, recs)
+        lengths = library.lengths()
+        out = fold(aligned, lengths, search.similarity_of_records(recs, lengths))
+    except BaseException:
+        library.free()
+        raise
+    if keep_library:
+        return out, recs, aligned, library
+    library.free()
+    return out, recs, aligned, None
+
+
 def find_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
                             threshold: float = 50.0, min_aligned: int = 4, slack: int = search.ALIGN_SLACK,
                             positions: bool = True, keep_library: bool = False):
@@ -560,21 +594,23 @@ def find_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
     positions=False aligns on the index inside the KEPT video instead: a frame the quality filter dropped then shifts
     everything after it (kept for comparison; the default is what a caller wants).
     -> (excerpts, search records, alignment records, library or None); Excerpt offsets / first / last are raw frame indices."""
-    library = _hashed_library(
-        raw_offsets, 0, 1, None, lambda mine: hash_frames_on_device(d_frames_ptr, int(mine[-1]), h, w, channels), 32,
-        lambda *raw: DeviceLibrary.from_raw_hashes(*raw, positions=bool(positions)), None)
-    try:
-        recs = library.match_videos()
-        aligned = library.align(recs, slack=slack)
-        lengths = library.lengths()
-        out = search.excerpts_from_records(aligned, lengths, search.similarity_of_records(recs, lengths), threshold, min_aligned)
-    except BaseException:
-        library.free()
-        raise
-    if keep_library:
-        return out, recs, aligned, library
-    library.free()
-    return out, recs, aligned, None
+    return _aligned_search_on_device(
+        d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library, lambda library, recs: library.align(recs, slack=slack),
+        lambda aligned, lengths, sim: search.excerpts_from_records(aligned, lengths, sim, threshold, min_aligned))
+
+
+def find_segmented_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                      threshold: float = 50.0, min_aligned: int = 4, slack: int = search.ALIGN_SLACK,
+                                      positions: bool = True, max_segments: int = _lib.ALIGN_MAX_SEGMENTS,
+                                      keep_library: bool = False):
+    """search.find_segmented_excerpts on frames in HBM, one device: the chain of `find_excerpts_on_device` with the
+    multi-segment alignment (`DeviceLibrary.align_segments`, min_band_votes = min_aligned) and the keep rule of
+    search.segmented_excerpts_from_records; nothing but records crosses PCIe.
+    -> (segmented excerpts, search records, VSEGMENTS records, library or None); positions are raw frame indices."""
+    return _aligned_search_on_device(
+        d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library,
+        lambda library, recs: library.align_segments(recs, slack=slack, max_segments=max_segments, min_band_votes=int(min_aligned)),
+        lambda aligned, lengths, sim: search.segmented_excerpts_from_records(aligned, lengths, sim, threshold, min_aligned))
 
 
 def _rank0_of_every_context(entry, frames_of_rank, timings, n_results: int, *args, **kwargs):

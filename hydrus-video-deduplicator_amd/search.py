@@ -16,7 +16,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib, vpdq
-from ._lib import PAIR_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE
+from ._lib import ALIGN_MAX_SEGMENTS, PAIR_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VSEGMENTS_DTYPE
 
 DISTANCE_TOLERANCE = 31  # per-frame Hamming tolerance (vpdqpy/vpdqpy.py:53, db/vptree.py:31)
 DEFAULT_VARIANT = 13  # all-pairs kernel the product uses (FP4-MFMA, 128-bit first stage, form chosen by a probe); DESIGN.md 4.1
@@ -307,15 +307,9 @@ def pair_array(pairs) -> np.ndarray:
     return np.ascontiguousarray(pairs, dtype=np.uint32)
 
 
-def align_videos(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.ndarray | None = None,
-                 max_dist: int | None = None, slack: int = ALIGN_SLACK, frames_t: np.ndarray | None = None,
-                 offsets_t: np.ndarray | None = None, positions_t: np.ndarray | None = None) -> np.ndarray:
-    """Time alignment of the listed video pairs (hvd_vpdq_align_videos): one VALIGN_DTYPE record per pair, in the order of
-    `pairs` (int[M, 2], or VMATCH records: their a, b). frames / offsets (/ positions: int32 per frame, non-negative, strictly
-    increasing inside a video, below 2^20; default: the index inside the video): the library of the a side, and of the b side
-    too unless frames_t / offsets_t (/ positions_t) give another one. A record holds the pair's vPDQ counters, the best
-    offset (p_b = p_a + offset), the frame hits within `slack` of it, and per side the number of frames with such a hit and
-    the first and last position among them; max_dist defaults to the search's frame tolerance."""
+def _align_operands(frames, offsets, pairs, positions, max_dist, frames_t, offsets_t, positions_t):
+    """The operands both alignment entries take: the a side's library, the b side's (the same unless frames_t / offsets_t
+    give another one), the pair list as uint32[M, 2] and the frame tolerance."""
     frames, offsets, positions = _library(frames, offsets, positions)
     if (frames_t is None) != (offsets_t is None):
         raise ValueError("pass frames_t and offsets_t together")
@@ -325,8 +319,21 @@ def align_videos(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.n
         frames_t, offsets_t, positions_t = frames, offsets, positions
     else:
         frames_t, offsets_t, positions_t = _library(frames_t, offsets_t, positions_t)
-    pairs = pair_array(pairs)
     max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
+    return frames, offsets, positions, frames_t, offsets_t, positions_t, pair_array(pairs), max_dist
+
+
+def align_videos(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.ndarray | None = None,
+                 max_dist: int | None = None, slack: int = ALIGN_SLACK, frames_t: np.ndarray | None = None,
+                 offsets_t: np.ndarray | None = None, positions_t: np.ndarray | None = None) -> np.ndarray:
+    """Time alignment of the listed video pairs (hvd_vpdq_align_videos): one VALIGN_DTYPE record per pair, in the order of
+    `pairs` (int[M, 2], or VMATCH records: their a, b). frames / offsets (/ positions: int32 per frame, non-negative, strictly
+    increasing inside a video, below 2^20; default: the index inside the video): the library of the a side, and of the b side
+    too unless frames_t / offsets_t (/ positions_t) give another one. A record holds the pair's vPDQ counters, the best
+    offset (p_b = p_a + offset), the frame hits within `slack` of it, and per side the number of frames with such a hit and
+    the first and last position among them; max_dist defaults to the search's frame tolerance."""
+    frames, offsets, positions, frames_t, offsets_t, positions_t, pairs, max_dist = _align_operands(
+        frames, offsets, pairs, positions, max_dist, frames_t, offsets_t, positions_t)
     M = pairs.shape[0]
     out = np.zeros(M, dtype=VALIGN_DTYPE)
     out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
@@ -367,6 +374,16 @@ def excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: 
     return sorted(out)
 
 
+def _positions_of(positions, blobs: list, lengths) -> np.ndarray | None:
+    """One int sequence per video -> int32 per frame of the packed library (None stays None)."""
+    if positions is None:
+        return None
+    if len(positions) != len(blobs) or any(len(p) != n for p, n in zip(positions, lengths)):
+        raise ValueError("positions must hold one position per frame of every video")
+    return np.concatenate([np.asarray(p, dtype=np.int32).reshape(-1) for p in positions]) if len(blobs) else \
+        np.zeros(0, np.int32)
+
+
 def excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK, positions=None,
                   matcher=None) -> list:
     """The search and the alignment of find_excerpts and their fold, on validated blobs (blobs[v]: the hash bytes of video v;
@@ -374,12 +391,7 @@ def excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, sl
     entry points of this module). -> excerpts_from_records(...)."""
     mv, al = (match_videos, align_videos) if matcher is None else (matcher.match_videos, matcher.align_videos)
     frames, offsets, lengths = pack_hashes(blobs)
-    pos = None
-    if positions is not None:
-        if len(positions) != len(blobs) or any(len(p) != n for p, n in zip(positions, lengths)):
-            raise ValueError("positions must hold one position per frame of every video")
-        pos = np.concatenate([np.asarray(p, dtype=np.int32).reshape(-1) for p in positions]) if len(blobs) else \
-            np.zeros(0, np.int32)
+    pos = _positions_of(positions, blobs, lengths)
     max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
     recs = mv(frames, offsets, max_dist)
     aligned = al(frames, offsets, np.stack([recs["a"], recs["b"]], axis=1), positions=pos, max_dist=max_dist, slack=slack)
@@ -400,3 +412,103 @@ def find_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, s
     than four frames in a row are as likely a shared title card as a clip. slack: how far a hit may lie off the offset and
     still count (one dropped or doubled frame at the default 1)."""
     return excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, positions)
+
+
+# ------------------------------------------------ highlight reels and re-cuts: multi-segment alignment (DESIGN 4.9) ------
+
+def align_segments(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.ndarray | None = None,
+                   max_dist: int | None = None, slack: int = ALIGN_SLACK, frames_t: np.ndarray | None = None,
+                   offsets_t: np.ndarray | None = None, positions_t: np.ndarray | None = None,
+                   max_segments: int = ALIGN_MAX_SEGMENTS, min_band_votes: int = 1) -> np.ndarray:
+    """Multi-segment time alignment of the listed video pairs (hvd_vpdq_align_segments): one VSEGMENTS_DTYPE record per pair,
+    in the order of `pairs`. The operands are align_videos'. Up to `max_segments` (1..8) offsets are peeled off a pair,
+    greedily: each round is align_videos' rule on the frame hits whose frames no earlier segment owns, and ends the pair if
+    its best band holds fewer than `min_band_votes` hits. A record holds the pair's vPDQ counters, n_segments, the frames of
+    a and of b that the segments cover, and the segments in the order they were found (the words of a VALIGN_DTYPE record from
+    offset on; seg[0] IS the align_videos record of the pair)."""
+    frames, offsets, positions, frames_t, offsets_t, positions_t, pairs, max_dist = _align_operands(
+        frames, offsets, pairs, positions, max_dist, frames_t, offsets_t, positions_t)
+    M = pairs.shape[0]
+    out = np.zeros(M, dtype=VSEGMENTS_DTYPE)
+    out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
+    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
+        return out
+    lib = _lib.ensure()
+    _lib.check(lib.hvd_vpdq_align_segments(_ptr(frames), offsets.ctypes.data, offsets.size - 1, _ptr(positions), _ptr(frames_t),
+                                           offsets_t.ctypes.data, offsets_t.size - 1, _ptr(positions_t), _ptr(pairs), M,
+                                           max_dist, int(slack), int(max_segments), int(min_band_votes), _ptr(out)))
+    return out
+
+
+Segment = namedtuple("Segment", "offset short_first short_last first last aligned")
+SegmentedExcerpt = namedtuple("SegmentedExcerpt", "short long coverage similarity segments")
+
+
+def segmented_excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: np.ndarray,
+                                    threshold: float = 50.0, min_aligned: int = 4) -> list:
+    """The keep rule of find_segmented_excerpts on VSEGMENTS_DTYPE records (pure numpy; no device). short = the video with
+    fewer frames (a on a tie). A segment counts iff at least min_aligned frames of short are aligned in it; coverage =
+    100 * the aligned frames of short over the segments that count / frames of short; kept iff int(coverage) >=
+    int(threshold) and at least one segment counts. -> sorted list of SegmentedExcerpt(short, long, coverage, similarity,
+    segments); segments: the ones that count, ordered by short_first, each Segment(offset, short_first, short_last, first,
+    last, aligned) in long's timeline as Excerpt is (p_long = p_short + offset; first / last: positions in long)."""
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    lengths = np.asarray(lengths, dtype=np.int64)
+    out = []
+    for r, sim in zip(aligned, similarity):
+        a, b = int(r["a"]), int(r["b"])
+        a_short = lengths[a] <= lengths[b]
+        n_short = int(lengths[a] if a_short else lengths[b])
+        if n_short == 0:
+            continue
+        segs = []
+        for s in r["seg"][:int(r["n_segments"])]:
+            on = int(s["q_aligned"] if a_short else s["t_aligned"])
+            if on < int(min_aligned):
+                continue
+            segs.append(Segment(int(s["offset"]), int(s["q_first"]), int(s["q_last"]), int(s["t_first"]), int(s["t_last"]), on)
+                        if a_short else
+                        Segment(-int(s["offset"]), int(s["t_first"]), int(s["t_last"]), int(s["q_first"]), int(s["q_last"]), on))
+        if not segs:
+            continue
+        coverage = 100.0 * sum(s.aligned for s in segs) / n_short
+        if int(coverage) < int(threshold):
+            continue
+        segs = tuple(sorted(segs, key=lambda s: s.short_first))
+        out.append(SegmentedExcerpt(a, b, coverage, float(sim), segs) if a_short else
+                   SegmentedExcerpt(b, a, coverage, float(sim), segs))
+    return sorted(out)
+
+
+def segmented_excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
+                            positions=None, max_segments: int = ALIGN_MAX_SEGMENTS, min_band_votes: int | None = None,
+                            matcher=None) -> list:
+    """The search and the segment alignment of find_segmented_excerpts and their fold, on validated blobs (as
+    excerpt_pairs). matcher: object with match_videos / align_segments (default: the GPU entry points of this module).
+    min_band_votes: None = min_aligned (see find_segmented_excerpts). -> segmented_excerpts_from_records(...)."""
+    mv, al = (match_videos, align_segments) if matcher is None else (matcher.match_videos, matcher.align_segments)
+    frames, offsets, lengths = pack_hashes(blobs)
+    pos = _positions_of(positions, blobs, lengths)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
+    recs = mv(frames, offsets, max_dist)
+    aligned = al(frames, offsets, np.stack([recs["a"], recs["b"]], axis=1), positions=pos, max_dist=max_dist, slack=slack,
+                 max_segments=max_segments, min_band_votes=int(min_aligned if min_band_votes is None else min_band_votes))
+    return segmented_excerpts_from_records(aligned, lengths, similarity_of_records(recs, lengths), threshold, min_aligned)
+
+
+def find_segmented_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
+                            positions=None, max_segments: int = ALIGN_MAX_SEGMENTS) -> list:
+    """Videos that are SEVERAL pieces of a longer one -- a highlight reel, a trailer cut from several scenes, a compilation,
+    a re-cut with scenes removed and the rest reordered -- besides what find_excerpts finds (one piece, full copies). Every
+    pair of the video search is aligned on up to `max_segments` offsets (align_segments); a segment counts iff at least
+    `min_aligned` frames of the SHORTER video line up in it, and the pair is kept iff the segments that count cover at least
+    `threshold` percent of the shorter video. The arguments are find_excerpts'. -> sorted list of SegmentedExcerpt(short,
+    long, coverage, similarity, segments), segments = tuple of Segment(offset, short_first, short_last, first, last,
+    aligned) ordered by short_first: short's positions short_first..short_last sit at first..last of long
+    (p_long = p_short + offset). With max_segments = 1 the pairs, coverages and offsets are exactly find_excerpts'.
+    The alignment is asked to stop at min_band_votes = min_aligned. That prunes rounds and changes no result: a frame is
+    aligned only through a hit in the band, so a segment's aligned frames never outnumber its band_votes, and band_votes
+    never increases from one segment to the next -- a segment below the floor cannot count, nor can any after it. The same
+    frames in shuffled order stay unreported: no offset collects min_aligned of them."""
+    return segmented_excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, positions, max_segments)

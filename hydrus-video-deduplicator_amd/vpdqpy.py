@@ -71,6 +71,17 @@ class Vpdq:
         frames, offsets, _ = search.pack_hashes((phash_a, phash_b))
         return search.align_videos(frames, offsets, [(0, 1)], slack=slack)[0]
 
+    @staticmethod
+    def align_segments(phash_a, phash_b, slack: int = 1, max_segments: int = 8, min_band_votes: int = 1):
+        """Where the pieces of two video hashes line up in time -- a reel or re-cut against its source: the one
+        ``search.align_segments`` record of the pair (a = 0, b = 1; up to max_segments offsets, seg[0] is ``align``'s).
+        VpdqHash or bytes."""
+        from . import search
+
+        frames, offsets, _ = search.pack_hashes((phash_a, phash_b))
+        return search.align_segments(frames, offsets, [(0, 1)], slack=slack, max_segments=max_segments,
+                                     min_band_votes=min_band_votes)[0]
+
     select_frames = staticmethod(select_frames)
 
     @staticmethod

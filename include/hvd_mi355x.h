@@ -39,7 +39,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -66,6 +66,24 @@ typedef struct hvd_valign {
 } hvd_valign;
 /* Pairs of up to this many histogram bins (span of p_a + span of p_b + 1 + 2 slack) are aligned out of LDS alone. */
 #define HVD_ALIGN_LDS_BINS 4096
+
+/* One video pair aligned on up to HVD_ALIGN_MAX_SEGMENTS offsets (hvd_vpdq_align_segments / hvd_dev_vpdq_align_segments;
+ * DESIGN 4.9): a highlight reel, a trailer cut from several scenes, a re-cut. A segment is eight 32-bit words, the words of
+ * hvd_valign from offset on, computed on the frame hits that no earlier segment owns; a record is 72 words: a, b, q_hits, t_hits
+ * (the vPDQ counters of the pair, as in hvd_valign), n_segments, q_covered / t_covered = the sums of q_aligned / t_aligned over
+ * the segments, a reserved word (0), then the segments in the order they were found; unused slots are 0. A pair without a frame
+ * hit: every word after b is 0. A pair the device entry cannot align (the conditions of hvd_valign): n_segments = 0,
+ * seg[0].offset = INT32_MIN, the other words after b 0. */
+#define HVD_ALIGN_MAX_SEGMENTS 8
+typedef struct hvd_vsegment {
+    int32_t offset;
+    uint32_t band_votes, q_aligned, t_aligned;
+    int32_t q_first, q_last, t_first, t_last;
+} hvd_vsegment;
+typedef struct hvd_vsegments {
+    uint32_t a, b, q_hits, t_hits, n_segments, q_covered, t_covered, reserved;
+    hvd_vsegment seg[HVD_ALIGN_MAX_SEGMENTS];
+} hvd_vsegments;
 
 /* ------------------------------------------------------------ lifecycle -- */
 
@@ -202,6 +220,28 @@ int hvd_vpdq_match_videos_cross(const uint8_t* frames_q, const int64_t* offsets_
 int hvd_vpdq_align_videos(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
                           const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                           const uint32_t* pairs, int64_t M, int max_dist, int slack, hvd_valign* out);
+
+/* Multi-segment time alignment of listed video pairs: a short video that is SEVERAL pieces of a longer one. The
+ * notation and the operands of hvd_vpdq_align_videos apply (H, delta, votes, S, slack, the tie order). The rule, integers only,
+ * one answer per pair, with K = max_segments in [1, HVD_ALIGN_MAX_SEGMENTS] and min_band_votes >= 1:
+ *   taken_a = taken_b = {}
+ *   for r = 1..K:
+ *     H_r = {(i, j) in H : i not in taken_a and j not in taken_b};  if H_r is empty: stop
+ *     votes, S, d*_r: the rule and tie order of hvd_vpdq_align_videos, on H_r;  if S(d*_r) < min_band_votes: stop
+ *     aligned_a = {i : some (i, j) in H_r has |delta - d*_r| <= slack};  aligned_b likewise
+ *     segment r = (offset d*_r, band_votes S(d*_r), q_aligned, t_aligned, q_first, q_last, t_first, t_last)
+ *     taken_a |= aligned_a;  taken_b |= aligned_b
+ * Three consequences: (a) segment 1 is, word for word, the hvd_valign record of the pair (offset .. t_last; q_hits / t_hits are
+ * the same too); (b) band_votes never increases from one segment to the next, because H_{r+1} is a subset of H_r; (c) the
+ * aligned sets of the segments are disjoint, so q_covered = the sum of q_aligned and t_covered = the sum of t_aligned. Once
+ * every frame of a or of b is taken, H_r is empty: a full copy is one segment.
+ * out: M hvd_vsegments records in the order of the pair list. This host-buffer form validates what hvd_vpdq_align_videos
+ * validates and max_segments / min_band_votes (HVD_ERR_ARG), stages, runs the kernels and copies the records back; under a
+ * device group it runs on the calling thread's current context alone. */
+int hvd_vpdq_align_segments(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                            const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                            const uint32_t* pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
+                            hvd_vsegments* out);
 
 /* ------------------------------------------------ streaming frame hasher -- */
 /* The native side of vpdq.VideoHasher (vpdqpy/vpdqpy.py:113-119): frames are pushed one at a
@@ -450,6 +490,19 @@ int hvd_dev_vpdq_align_videos(const void* d_hashes_q, const void* d_offsets_q, i
                               const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                               const void* d_pairs, int64_t M, int max_dist, int slack, void* d_scratch, size_t scratch_bytes,
                               void* d_out);
+
+/* Device-resident multi-segment alignment (the rule: hvd_vpdq_align_segments above). The operands of
+ * hvd_dev_vpdq_align_videos, plus max_segments in [1, HVD_ALIGN_MAX_SEGMENTS] and min_band_votes >= 1 (HVD_ERR_ARG otherwise);
+ * d_out: M hvd_vsegments records, 16-byte aligned. The scratch of a pair beyond HVD_ALIGN_LDS_BINS bins also holds the taken
+ * sets: hvd_segments_scratch_bytes(max_bins) bytes serve every pair of up to max_bins bins (<= 2^20). Enqueued on the library
+ * stream: no host synchronisation, nothing allocated, nothing on the device validated -- what gives the INT32_MIN record of
+ * hvd_dev_vpdq_align_videos gives the one of hvd_vsegments here, and broken operands give wrong records, never an access out
+ * of bounds. A pair stops without another pass over its frames once q_covered or t_covered reaches the video's length. */
+int hvd_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes);
+int hvd_dev_vpdq_align_segments(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                                const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                                const void* d_pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
+                                void* d_scratch, size_t scratch_bytes, void* d_out);
 
 /* Every video pair a<b with >= 1 frame hit, with its vPDQ counters (semantics of vpdqpy/vpdqpy.py:49-56 for all
  * pairs at once; replaces the tree walk of dedup.py:468-475). d_img: FP4 image of the n frame hashes; d_video:
