@@ -242,25 +242,34 @@ def test_counters_equal_the_video_search(gpu, hvd):
 def test_kept_positions_against_numpy(gpu):
     lib = gpu.ensure()
     rng = np.random.default_rng(17)
-    lengths = np.concatenate([[0, 1, 1030, 0, 5], rng.integers(0, 70, 200), [2100]])
-    offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
-    n = int(offsets[-1])
-    quality = rng.integers(0, 101, n).astype(np.int32)
-    for v in (2, 4, 9, 10):  # videos that lose all their frames
-        quality[offsets[v]:offsets[v + 1]] = rng.integers(0, 31, int(lengths[v]))
-    for min_q in (31, 0, 101):
-        keep = quality >= min_q
-        want = (np.arange(n) - np.repeat(offsets[:-1], lengths))[keep].astype(np.int32)
-        d_q, d_off = gpu.DeviceBuffer.from_array(quality), gpu.DeviceBuffer.from_array(offsets)
-        d_pos = _sentinel_buffer(gpu, 4 * int(keep.sum()))
-        try:
-            gpu.check(lib.hvd_dev_kept_positions(d_q.ptr, n, d_off.ptr, len(lengths), min_q, d_pos.ptr))
-            gpu.check(lib.hvd_dev_sync())
-            assert np.array_equal(d_pos.to_array(np.int32, want.size), want)
-            assert _tail_intact(gpu, d_pos, 4 * want.size)
-        finally:
-            for b in (d_q, d_off, d_pos):
-                b.free()
+    small = np.concatenate([[0, 1, 1030, 0, 5], rng.integers(0, 70, 200), [2100]])
+    # 1024 * 1024 + 1025 frames: more than one chunk of 1024 block sums, so the scan carries. Ragged lengths with empty
+    # videos; video 9001 straddles frame 1024 * 1024.
+    n_big = 1024 * 1024 + 1025
+    head = np.concatenate([[0, 3, 0, 2000, 1], np.random.default_rng(1717).integers(0, 230, 8996)])
+    head[-1] += 1024 * 1024 - 700 - int(head.sum())
+    assert head[-1] >= 0 and head.sum() == 1024 * 1024 - 700
+    big = np.concatenate([head, [1500, 0, 0, 40], [n_big - 1024 * 1024 - 800 - 40]])
+    assert big.sum() == n_big and big[:9001].sum() < 1024 * 1024 < big[:9002].sum() and (big == 0).sum() > 20
+    for lengths, dropped in ((small, (2, 4, 9, 10)), (big, (3, 4, 10, 4000, 9004))):
+        offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        n = int(offsets[-1])
+        quality = rng.integers(0, 101, n).astype(np.int32)
+        for v in dropped:  # videos that lose all their frames
+            quality[offsets[v]:offsets[v + 1]] = rng.integers(0, 31, int(lengths[v]))
+        for min_q in (31, 0, 101):
+            keep = quality >= min_q
+            want = (np.arange(n) - np.repeat(offsets[:-1], lengths))[keep].astype(np.int32)
+            d_q, d_off = gpu.DeviceBuffer.from_array(quality), gpu.DeviceBuffer.from_array(offsets)
+            d_pos = _sentinel_buffer(gpu, 4 * int(keep.sum()))
+            try:
+                gpu.check(lib.hvd_dev_kept_positions(d_q.ptr, n, d_off.ptr, len(lengths), min_q, d_pos.ptr))
+                gpu.check(lib.hvd_dev_sync())
+                assert np.array_equal(d_pos.to_array(np.int32, want.size), want)
+                assert _tail_intact(gpu, d_pos, 4 * want.size)
+            finally:
+                for b in (d_q, d_off, d_pos):
+                    b.free()
 
 
 def test_chained_excerpt_search_needs_the_positions(gpu, hvd):

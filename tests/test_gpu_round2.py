@@ -237,7 +237,8 @@ def test_k3_cross_device_reduction_vs_oracle(gpu, hvd, oracle):
 
 # ------------------------------------------------------------------ quality compaction --------
 
-@pytest.mark.parametrize("n,V", [(0, 0), (0, 3), (1, 1), (1023, 7), (1024, 1), (5000, 300), (70000, 1500)])
+@pytest.mark.parametrize("n,V", [(0, 0), (0, 3), (1, 1), (1023, 7), (1024, 1), (5000, 300), (70000, 1500),
+                                 (1024 * 1024 + 1025, 9000)])  # (more than 1024 block sums: the scan carries)
 def test_compact_kept_vs_numpy(gpu, hvd, n, V):
     """VideoHasher.finish for a whole library on the device: kept hashes in order, CSR, frame->video map;
     empty videos (at the start, in the middle, at the end) and all-dropped videos included."""
