@@ -1001,9 +1001,43 @@ int hvd_dev_kept_positions(const void* d_quality, int64_t n, const void* d_offse
     return HVD_OK;
 }
 
-int hvd_align_scratch_bytes(int64_t max_bins, size_t* out_bytes) {
+static int scratch_bytes_entry(int64_t max_bins, size_t* out_bytes, size_t (*bytes)(unsigned long long)) {
     if (!out_bytes || max_bins < 0 || max_bins > (1ll << 20)) return fail(HVD_ERR_ARG, "max_bins=%lld: need 0..2^20", (long long)max_bins);
-    *out_bytes = hvd::align_scratch_bytes((unsigned long long)max_bins);
+    *out_bytes = bytes((unsigned long long)max_bins);
+    return HVD_OK;
+}
+
+int hvd_align_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(max_bins, out_bytes, hvd::align_scratch_bytes); }
+
+int hvd_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) {
+    return scratch_bytes_entry(max_bins, out_bytes, hvd::segments_scratch_bytes);
+}
+
+static int check_tolerances(int max_dist, int slack) {
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    if (slack < 0 || slack > 16) return fail(HVD_ERR_ARG, "slack=%d out of range [0,16]", slack);
+    return HVD_OK;
+}
+
+static int check_segment_limits(int max_segments, int min_band_votes) {
+    if (max_segments < 1 || max_segments > HVD_ALIGN_MAX_SEGMENTS)
+        return fail(HVD_ERR_ARG, "max_segments=%d out of range [1,%d]", max_segments, HVD_ALIGN_MAX_SEGMENTS);
+    if (min_band_votes < 1) return fail(HVD_ERR_ARG, "min_band_votes=%d: need >= 1", min_band_votes);
+    return HVD_OK;
+}
+
+// What both device entries check, in the order the errors are reported: this before the limits of the segments entry ...
+static int check_align_counts(int64_t VQ, int64_t VT, int64_t M, int max_dist, int slack) {
+    if (int rc = need_ready()) return rc;
+    if (VQ < 0 || VT < 0 || VQ >= (1ll << 31) || VT >= (1ll << 31) || M < 0) return fail(HVD_ERR_ARG, "bad counts");
+    return check_tolerances(max_dist, slack);
+}
+
+// ... and, for M > 0, the pointers. aligned16: the pointers that are read or written 16 bytes at a time, or-ed; what: their names.
+static int check_align_pointers(const void* d_offsets_q, const void* d_offsets_t, const void* d_pairs, const void* d_out,
+                                uintptr_t aligned16, const char* what) {
+    if (!d_offsets_q || !d_offsets_t || !d_pairs || !d_out) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if (aligned16 & 15u) return fail(HVD_ERR_ARG, "%s must be 16-byte aligned", what);
     return HVD_OK;
 }
 
@@ -1011,14 +1045,11 @@ int hvd_dev_vpdq_align_videos(const void* d_hashes_q, const void* d_offsets_q, i
                               const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                               const void* d_pairs, int64_t M, int max_dist, int slack, void* d_scratch, size_t scratch_bytes,
                               void* d_out) {
-    if (int rc = need_ready()) return rc;
-    if (VQ < 0 || VT < 0 || VQ >= (1ll << 31) || VT >= (1ll << 31) || M < 0) return fail(HVD_ERR_ARG, "bad counts");
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    if (slack < 0 || slack > 16) return fail(HVD_ERR_ARG, "slack=%d out of range [0,16]", slack);
+    if (int rc = check_align_counts(VQ, VT, M, max_dist, slack)) return rc;
     if (M == 0) return HVD_OK;
-    if (!d_offsets_q || !d_offsets_t || !d_pairs || !d_out) return fail(HVD_ERR_ARG, "NULL device pointer");
-    if (((uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch) & 15u)
-        return fail(HVD_ERR_ARG, "hashes and scratch must be 16-byte aligned");
+    if (int rc = check_align_pointers(d_offsets_q, d_offsets_t, d_pairs, d_out,
+                                      (uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch, "hashes and scratch"))
+        return rc;
     HIP_TRY(hvd::launch_valign(d_hashes_q, (const long long*)d_offsets_q, (uint32_t)VQ, (const int32_t*)d_pos_q, d_hashes_t,
                                (const long long*)d_offsets_t, (uint32_t)VT, (const int32_t*)d_pos_t, (const uint32_t*)d_pairs,
                                (unsigned long long)M, (uint32_t)max_dist, (uint32_t)slack, d_scratch, scratch_bytes,
@@ -1026,27 +1057,17 @@ int hvd_dev_vpdq_align_videos(const void* d_hashes_q, const void* d_offsets_q, i
     return HVD_OK;
 }
 
-int hvd_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) {
-    if (!out_bytes || max_bins < 0 || max_bins > (1ll << 20)) return fail(HVD_ERR_ARG, "max_bins=%lld: need 0..2^20", (long long)max_bins);
-    *out_bytes = hvd::segments_scratch_bytes((unsigned long long)max_bins);
-    return HVD_OK;
-}
-
 int hvd_dev_vpdq_align_segments(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
                                 const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                                 const void* d_pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
                                 void* d_scratch, size_t scratch_bytes, void* d_out) {
-    if (int rc = need_ready()) return rc;
-    if (VQ < 0 || VT < 0 || VQ >= (1ll << 31) || VT >= (1ll << 31) || M < 0) return fail(HVD_ERR_ARG, "bad counts");
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    if (slack < 0 || slack > 16) return fail(HVD_ERR_ARG, "slack=%d out of range [0,16]", slack);
-    if (max_segments < 1 || max_segments > HVD_ALIGN_MAX_SEGMENTS)
-        return fail(HVD_ERR_ARG, "max_segments=%d out of range [1,%d]", max_segments, HVD_ALIGN_MAX_SEGMENTS);
-    if (min_band_votes < 1) return fail(HVD_ERR_ARG, "min_band_votes=%d: need >= 1", min_band_votes);
+    if (int rc = check_align_counts(VQ, VT, M, max_dist, slack)) return rc;
+    if (int rc = check_segment_limits(max_segments, min_band_votes)) return rc;
     if (M == 0) return HVD_OK;
-    if (!d_offsets_q || !d_offsets_t || !d_pairs || !d_out) return fail(HVD_ERR_ARG, "NULL device pointer");
-    if (((uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch | (uintptr_t)d_out) & 15u)
-        return fail(HVD_ERR_ARG, "hashes, scratch and records must be 16-byte aligned");
+    if (int rc = check_align_pointers(d_offsets_q, d_offsets_t, d_pairs, d_out,
+                                      (uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch | (uintptr_t)d_out,
+                                      "hashes, scratch and records"))
+        return rc;
     HIP_TRY(hvd::launch_valign_segments(d_hashes_q, (const long long*)d_offsets_q, (uint32_t)VQ, (const int32_t*)d_pos_q, d_hashes_t,
                                         (const long long*)d_offsets_t, (uint32_t)VT, (const int32_t*)d_pos_t,
                                         (const uint32_t*)d_pairs, (unsigned long long)M, (uint32_t)max_dist, (uint32_t)slack,
@@ -1074,8 +1095,7 @@ static int align_from_host(const uint8_t* frames_q, const int64_t* offsets_q, in
                            void* out) {
     if (int rc = need_ready()) return rc;
     if (M < 0 || (M > 0 && (!pairs || !out))) return fail(HVD_ERR_ARG, "bad pair list / output buffer");
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    if (slack < 0 || slack > 16) return fail(HVD_ERR_ARG, "slack=%d out of range [0,16]", slack);
+    if (int rc = check_tolerances(max_dist, slack)) return rc;
     int64_t nq = 0, nt = 0;
     if (int rc = check_offsets(offsets_q, VQ, &nq)) return rc;
     if (int rc = check_offsets(offsets_t, VT, &nt)) return rc;
@@ -1153,9 +1173,7 @@ int hvd_vpdq_align_segments(const uint8_t* frames_q, const int64_t* offsets_q, i
                             const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                             const uint32_t* pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
                             hvd_vsegments* out) {
-    if (max_segments < 1 || max_segments > HVD_ALIGN_MAX_SEGMENTS)
-        return fail(HVD_ERR_ARG, "max_segments=%d out of range [1,%d]", max_segments, HVD_ALIGN_MAX_SEGMENTS);
-    if (min_band_votes < 1) return fail(HVD_ERR_ARG, "min_band_votes=%d: need >= 1", min_band_votes);
+    if (int rc = check_segment_limits(max_segments, min_band_votes)) return rc;
     return align_from_host(frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack,
                            max_segments, min_band_votes, out);
 }

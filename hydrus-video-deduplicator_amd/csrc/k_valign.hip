@@ -1,135 +1,16 @@
 // k_valign.hip -- time alignment of listed video pairs: where inside the longer video does the shorter one
-// sit, and how many of its frames line up there. The rule, integers only (include/hvd_mi355x.h has the full text):
-//   H = {(i, j) : hamming(A_i, B_j) <= max_dist},  delta(i, j) = p_b(j) - p_a(i),  votes[d] = |{(i, j) in H : delta = d}|,
-//   S(d) = votes[d - slack] + ... + votes[d + slack];  d* = the d of the largest S, ties by larger votes[d], smaller |d|,
-//   smaller d;  a frame is aligned iff one of its hits lies within slack of d*.
-// One workgroup per pair (grid-stride). The na x nb Hamming matrix is recomputed in two passes, never stored: 8 xor + 8
-// popcount per comparison on the packed hashes, the integer form of k_hamming.hip. Video a is staged through LDS in chunks of
-// kStage frames (rows padded to 9 words: lanes that read different rows hit different banks), so a video of any length is
-// served out of LDS; every lane keeps one frame of video b in registers, and with fewer than 256 frames in b the staged frames
-// are dealt out over 256 / nb lanes per frame, so that a 64 x 64 pair keeps all 256 lanes busy.
+// sit, and how many of its frames line up there. The rule, the staging of the Hamming matrix, the LDS / scratch split and the
+// bounds checks are hvd_valign_dev.h's; this file is the single-offset loop over them. One workgroup per pair (grid-stride):
 //   pass 1: hits vote into a histogram over delta (LDS atomics) and set one bit per frame (q_hits / t_hits);
-//   arg-max of the windowed sums under the tie order: lanes stride over the bins, wave shuffles, then the four waves;
+//   arg-max of the windowed sums under the tie order;
 //   pass 2: the bits of the frames that have a hit on the band; counts, first and last aligned frame from the bit words.
-// The histogram lives in LDS up to HVD_ALIGN_LDS_BINS bins (k_valign<false>); pairs with more bins are left to a second launch
-// (k_valign<true>) whose workgroups own one slot each of the caller's scratch -- up to 2^20 bins. Every bin index and every
-// frame range is checked against its bound before it is used: a broken CSR, pair list or position array gives wrong or
-// INT32_MIN records, never an access out of bounds.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "hvd_kernels.h"
+#include "hvd_valign_dev.h"
 
 namespace {
-
-constexpr uint32_t kLdsBins = HVD_ALIGN_LDS_BINS;
-constexpr uint32_t kMaxBins = 1u << 20;
-constexpr uint32_t kStage = 256;                     // frames of video a per LDS chunk
-constexpr uint32_t kFlagWords = kLdsBins / 32u + 4u;  // na + nb <= bins + 1 bits, in two word-aligned runs
-
-// one video of a pair: its hashes and positions (nullptr: the index inside the video), both from its first frame on
-struct Side {
-    const uint4* hashes;  // 2 per frame
-    const int32_t* pos;
-    uint32_t n;
-};
-
-__device__ __forceinline__ int32_t pos_of(const Side& s, uint32_t f) { return s.pos ? s.pos[f] : (int32_t)f; }
-
-struct Best {
-    uint32_t S, v;
-    int32_t d;
-};
-
-__device__ __forceinline__ uint32_t iabs(int32_t d) { return d < 0 ? 0u - (uint32_t)d : (uint32_t)d; }
-
-// the tie order: larger S, larger votes[d], smaller |d|, smaller d
-__device__ __forceinline__ bool better(const Best& x, const Best& y) {
-    if (x.S != y.S) return x.S > y.S;
-    if (x.v != y.v) return x.v > y.v;
-    if (iabs(x.d) != iabs(y.d)) return iabs(x.d) < iabs(y.d);
-    return x.d < y.d;
-}
-
-// number, lowest and highest set bit of a run of flag words, over the workgroup; red: 12 words of LDS
-__device__ __forceinline__ void count_bits(const uint32_t* flags, uint32_t n_bits, uint32_t* red, uint32_t* cnt, uint32_t* first,
-                                           uint32_t* last) {
-    uint32_t c = 0, lo = 0xffffffffu, hi = 0;
-    for (uint32_t k = threadIdx.x; k < (n_bits + 31u) / 32u; k += 256u) {
-        const uint32_t w = flags[k];
-        if (w) {
-            c += __popc(w);
-            lo = min(lo, k * 32u + (uint32_t)__ffs((int)w) - 1u);
-            hi = max(hi, k * 32u + 31u - (uint32_t)__clz((int)w));
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        c += __shfl_down(c, off);
-        lo = min(lo, (uint32_t)__shfl_down(lo, off));
-        hi = max(hi, (uint32_t)__shfl_down(hi, off));
-    }
-    __syncthreads();  // red may still be read from the call before
-    if ((threadIdx.x & 63u) == 0u) {
-        red[(threadIdx.x >> 6) * 3u] = c;
-        red[(threadIdx.x >> 6) * 3u + 1u] = lo;
-        red[(threadIdx.x >> 6) * 3u + 2u] = hi;
-    }
-    __syncthreads();
-    *cnt = red[0] + red[3] + red[6] + red[9];
-    *first = min(min(red[1], red[4]), min(red[7], red[10]));
-    *last = max(max(red[2], red[5]), max(red[8], red[11]));
-}
-
-// One pass over the Hamming matrix. PASS 1: votes and hit bits. PASS 2: the bits of the frames with a hit within slack of dstar.
-// Video a is staged, chunk by chunk; a lane keeps one frame of video b. flagA / flagB: where the flag words start behind hist.
-template <int PASS>
-__device__ __forceinline__ void scan_pair(const Side& A, const Side& B, uint32_t max_dist, uint32_t* stage, int32_t* spos,
-                                          uint32_t* hist, uint32_t flagA, uint32_t flagB, int32_t dmin, uint32_t core,
-                                          uint32_t slack, int32_t dstar) {
-    const uint32_t tid = threadIdx.x;
-    const uint32_t nsplit = B.n >= 256u ? 1u : 256u / B.n;
-    const uint32_t j_small = tid % B.n, part_small = tid / B.n;
-#pragma unroll 1
-    for (uint32_t i0 = 0; i0 < A.n; i0 += kStage) {
-        const uint32_t ci = min(kStage, A.n - i0);
-        __syncthreads();  // the chunk before is done with
-        for (uint32_t k = tid; k < ci * 2u; k += 256u) {
-            const uint4 v = A.hashes[(size_t)i0 * 2u + k];
-            uint32_t* d = stage + (k >> 1) * 9u + (k & 1u) * 4u;
-            d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        }
-        for (uint32_t k = tid; k < ci; k += 256u) spos[k] = pos_of(A, i0 + k);
-        __syncthreads();
-#pragma unroll 1
-        for (uint32_t base = 0; base < B.n; base += 256u) {
-            const uint32_t j = nsplit == 1u ? base + tid : j_small;
-            const uint32_t part = nsplit == 1u ? 0u : part_small;
-            if (j >= B.n || part >= nsplit) continue;
-            const uint4 q0 = B.hashes[(size_t)j * 2u], q1 = B.hashes[(size_t)j * 2u + 1u];
-            const int32_t pb = pos_of(B, j);
-            bool any = false;
-#pragma unroll 1
-            for (uint32_t i = part; i < ci; i += nsplit) {
-                const uint32_t* c = stage + i * 9u;
-                uint32_t d = __popc(q0.x ^ c[0]) + __popc(q0.y ^ c[1]) + __popc(q0.z ^ c[2]) + __popc(q0.w ^ c[3]);
-                d += __popc(q1.x ^ c[4]) + __popc(q1.y ^ c[5]) + __popc(q1.z ^ c[6]) + __popc(q1.w ^ c[7]);
-                if (d > max_dist) continue;
-                const int32_t delta = pb - spos[i];
-                const uint32_t f = i0 + i;
-                if (PASS == 1) {
-                    const uint32_t bin = (uint32_t)(delta - dmin);
-                    if (bin < core) atomicAdd(&hist[bin + slack], 1u);  // (only broken positions fail the check)
-                } else if (iabs(delta - dstar) > slack) {
-                    continue;
-                }
-                any = true;
-                atomicOr(&hist[flagA + (f >> 5)], 1u << (f & 31u));
-            }
-            if (any) atomicOr(&hist[flagB + (j >> 5)], 1u << (j & 31u));
-        }
-    }
-    __syncthreads();
-}
 
 // BIG false: every pair whose histogram fits LDS, and the INT32_MIN record of a pair index out of range. BIG true: the pairs
 // that do not fit LDS, each workgroup with its own slot of slot_words words at scratch (histogram, then the flag words); a
@@ -153,31 +34,12 @@ __global__ __launch_bounds__(256) void k_valign(const uint4* __restrict__ hashes
 #pragma unroll 1
     for (uint32_t p = blockIdx.x; p < M; p += gridDim.x) {
         const uint2 ab = pairs[p];
-        // ---- geometry of the pair (the same on every lane) ----
-        bool bad = ab.x >= VQ || ab.y >= VT, empty = false;
-        Side A = {nullptr, nullptr, 0}, B = {nullptr, nullptr, 0};
-        long long bins = 0;
-        int32_t dmin = 0;
-        if (!bad) {
-            const long long nq_all = offsets_q[VQ], nt_all = offsets_t[VT];
-            const long long a0 = min(max(offsets_q[ab.x], 0ll), nq_all), a1 = min(max(offsets_q[ab.x + 1u], a0), nq_all);
-            const long long b0 = min(max(offsets_t[ab.y], 0ll), nt_all), b1 = min(max(offsets_t[ab.y + 1u], b0), nt_all);
-            empty = a1 == a0 || b1 == b0;
-            bad = a1 - a0 > (long long)kMaxBins || b1 - b0 > (long long)kMaxBins;
-            if (!bad && !empty) {
-                A = {hashes_q + a0 * 2, pos_q ? pos_q + a0 : nullptr, (uint32_t)(a1 - a0)};
-                B = {hashes_t + b0 * 2, pos_t ? pos_t + b0 : nullptr, (uint32_t)(b1 - b0)};
-                const long long pa0 = pos_of(A, 0), pa1 = pos_of(A, A.n - 1u), pb0 = pos_of(B, 0), pb1 = pos_of(B, B.n - 1u);
-                // strictly increasing positions make a video's span at least its length - 1; the flag words rely on it
-                bad = pa0 < 0 || pb0 < 0 || pa1 - pa0 + 1 < (long long)A.n || pb1 - pb0 + 1 < (long long)B.n;
-                bins = (pa1 - pa0) + (pb1 - pb0) + 1 + 2 * (long long)slack;
-                bad = bad || bins > (long long)kMaxBins;
-                dmin = (int32_t)(pb0 - pa1);
-            }
-        }
-        const bool big = !bad && !empty && bins > (long long)kLdsBins;
-        if (big != BIG) continue;  // the other launch's pair (bad and empty pairs belong to the LDS launch)
-        const uint32_t nbins = (uint32_t)bins, wa = (A.n + 31u) / 32u, wb = (B.n + 31u) / 32u;
+        const Geometry geo = pair_geometry({hashes_q, offsets_q, pos_q, hashes_t, offsets_t, pos_t, VQ, VT}, ab, slack);
+        if (geo.big() != BIG) continue;  // the other launch's pair (bad and empty pairs belong to the LDS launch)
+        Side A = geo.A, B = geo.B;
+        const int32_t dmin = geo.dmin;
+        bool bad = geo.bad;
+        const uint32_t nbins = (uint32_t)geo.bins, wa = (A.n + 31u) / 32u, wb = (B.n + 31u) / 32u;
         uint32_t* const flags = hist + nbins;
         if (BIG && nbins + wa + wb > slot_words) bad = true;  // no room in the slot
         // the record is written as its words become known (lane 0): nothing of it has to stay in registers over the passes
@@ -189,7 +51,7 @@ __global__ __launch_bounds__(256) void k_valign(const uint4* __restrict__ hashes
             if (bad) zero.offset = INT32_MIN;
             *rec = zero;
         }
-        if (bad || empty) continue;
+        if (bad || geo.empty) continue;
         // ---- pass 1 ----
         __syncthreads();  // the pair before is done with LDS
         // The four pointers of the pair go through LDS and come back as vector registers: the scalar file holds every kernel
@@ -206,39 +68,21 @@ __global__ __launch_bounds__(256) void k_valign(const uint4* __restrict__ hashes
         for (uint32_t k = tid; k < nbins; k += 256u) hist[k] = 0u;
         for (uint32_t k = tid; k < wa + wb; k += 256u) flags[k] = 0u;
         const uint32_t core = nbins - 2u * slack;
-        scan_pair<1>(A, B, max_dist, stage, spos, hist, nbins, nbins + wa, dmin, core, slack, 0);
+        scan_pair<1, false>(A, B, max_dist, stage, spos, hist, nbins, nbins + wa, 0u, 0u, dmin, core, slack, 0, true);
         uint32_t cnt, first, last;
         count_bits(flags + wa, B.n, red, &cnt, &first, &last);
         if (tid == 0) rec->t_hits = cnt;
         count_bits(flags, A.n, red, &cnt, &first, &last);
         if (tid == 0) rec->q_hits = cnt;
         if (cnt == 0u) continue;  // H is empty
-        // ---- best offset: windowed sums, arg-max under the tie order ----
-        Best best = {0u, 0u, 0};
-#pragma unroll 1
-        for (uint32_t k = tid; k < nbins; k += 256u) {
-            const uint32_t u0 = k >= slack ? k - slack : 0u, u1 = min(nbins - 1u, k + slack);
-            Best c = {0u, hist[k], dmin - (int32_t)slack + (int32_t)k};
-#pragma unroll 1
-            for (uint32_t u = u0; u <= u1; ++u) c.S += hist[u];
-            if (better(c, best)) best = c;
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            Best o = {(uint32_t)__shfl_down(best.S, off), (uint32_t)__shfl_down(best.v, off), __shfl_down(best.d, off)};
-            if (better(o, best)) best = o;
-        }
-        if ((tid & 63u) == 0u) wbest[tid >> 6] = best;
-        __syncthreads();
-        best = wbest[0];
-        for (int w = 1; w < 4; ++w)
-            if (better(wbest[w], best)) best = wbest[w];
+        const Best best = best_offset<false>(hist, nbins, slack, dmin, wbest);
         if (tid == 0) {
             rec->offset = best.d;
             rec->band_votes = best.S;
         }
         // ---- pass 2 ----
         for (uint32_t k = tid; k < wa + wb; k += 256u) flags[k] = 0u;
-        scan_pair<2>(A, B, max_dist, stage, spos, hist, nbins, nbins + wa, dmin, core, slack, best.d);
+        scan_pair<2, false>(A, B, max_dist, stage, spos, hist, nbins, nbins + wa, 0u, 0u, dmin, core, slack, best.d, true);
         count_bits(flags, A.n, red, &cnt, &first, &last);
         if (tid == 0) {
             rec->q_aligned = cnt;
@@ -258,33 +102,17 @@ __global__ __launch_bounds__(256) void k_valign(const uint4* __restrict__ hashes
 
 namespace hvd {
 
-// workgroups of the scratch launch: one slot each
-constexpr unsigned kAlignSlots = 64;
-
-size_t align_scratch_bytes(unsigned long long max_bins) {
-    if (max_bins <= kLdsBins) return 0;
-    if (max_bins > kMaxBins) max_bins = kMaxBins;
-    // histogram + the two runs of flag words (na + nb <= bins + 1 bits)
-    return (size_t)kAlignSlots * 4u * (size_t)(max_bins + (max_bins + 1u) / 32u + 3u);
-}
+size_t align_scratch_bytes(unsigned long long max_bins) { return slot_scratch_bytes(max_bins, 1u); }  // the flag words
 
 hipError_t launch_valign(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
                          const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
                          const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, void* d_scratch,
                          size_t scratch_bytes, hvd_valign* d_out, hipStream_t s) {
-    if (M == 0) return hipSuccess;
-    const unsigned grid = (unsigned)(M < 8192ull ? M : 8192ull);
-    hipLaunchKernelGGL(k_valign<false>, dim3(grid), dim3(256), 0, s, (const uint4*)d_hashes_q, d_offsets_q, VQ, d_pos_q,
-                       (const uint4*)d_hashes_t, d_offsets_t, VT, d_pos_t, (const uint2*)d_pairs, (uint32_t)M, max_dist, slack, (uint32_t*)nullptr,
-                       0u, d_out);
-    // the pairs beyond the LDS histogram: found again from the same geometry, by as many workgroups as there are slots
-    unsigned long long slot_words = d_scratch ? scratch_bytes / 4u / kAlignSlots : 0ull;
-    if (slot_words > 2u * kMaxBins) slot_words = 2u * kMaxBins;  // (more than any pair needs)
-    const unsigned big_grid = (unsigned)(M < kAlignSlots ? M : kAlignSlots);
-    hipLaunchKernelGGL(k_valign<true>, dim3(big_grid), dim3(256), 0, s, (const uint4*)d_hashes_q, d_offsets_q, VQ, d_pos_q,
-                       (const uint4*)d_hashes_t, d_offsets_t, VT, d_pos_t, (const uint2*)d_pairs, (uint32_t)M, max_dist, slack, (uint32_t*)d_scratch,
-                       (uint32_t)slot_words, d_out);
-    return hipGetLastError();
+    return launch_lds_then_scratch(M, d_scratch, scratch_bytes, [&](auto big, unsigned grid, uint32_t* scratch, uint32_t slot_words) {
+        hipLaunchKernelGGL(k_valign<decltype(big)::value>, dim3(grid), dim3(256), 0, s, (const uint4*)d_hashes_q, d_offsets_q, VQ,
+                           d_pos_q, (const uint4*)d_hashes_t, d_offsets_t, VT, d_pos_t, (const uint2*)d_pairs, (uint32_t)M, max_dist,
+                           slack, scratch, slot_words, d_out);
+    });
 }
 
 }  // namespace hvd

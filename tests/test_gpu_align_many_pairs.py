@@ -18,7 +18,7 @@ from test_gpu_segments import dev_segments
 pytestmark = pytest.mark.gpu
 
 LDS_GRID = 8192      # workgroups of the LDS launches at most (launch_valign, launch_valign_segments)
-SCRATCH_SLOTS = 64   # workgroups of the scratch launches: kAlignSlots, kSegmentSlots
+SCRATCH_SLOTS = 64   # workgroups of the scratch launches: kSlots (csrc/hvd_valign_dev.h)
 
 KINDS = "abcdefghij"
 TRIPLES = ("fcf", "fdb", "jfj", "hfg", "ege", "iac")  # the chosen triples of the three-row columns
