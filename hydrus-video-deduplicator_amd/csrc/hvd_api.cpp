@@ -735,14 +735,17 @@ int hvd_debug_get(const char* key, int* out_value) {
     if (int rc = need_ready()) return rc;
     // what the probe of the last auto-variant launch saw and chose: form id, survivors over bits 0..127 / 128..255,
     // 1 if the first stage ran on bits 128..255
-    // (word 4 is the probe's ticket; word 5 the survivors over bits 0..63 + 192..255, round 5)
-    const char* keys[6] = {"mfma_auto_form", "mfma_probe_survivors", "mfma_probe_survivors_hi", "mfma_auto_half", "", "mfma_probe_survivors_mix"};
-    for (int k = 0; k < 6; ++k)
+    // (word 4 is the probe's ticket; word 5 the survivors over bits 0..63 + 192..255, round 5; word 6 = kSelIdxClose the
+    // sampled block pairs within the index radius, summed only when the pass may run on the pigeonhole index)
+    static_assert(hvd::kSelIdxClose == 6, "mfma_probe_close reads select word 6");
+    const char* keys[7] = {"mfma_auto_form", "mfma_probe_survivors", "mfma_probe_survivors_hi", "mfma_auto_half", "", "mfma_probe_survivors_mix",
+                           "mfma_probe_close"};
+    for (int k = 0; k < 7; ++k)
         if (keys[k][0] && strcmp(key, keys[k]) == 0) {
             uint32_t* sel = nullptr;
             HIP_TRY(hvd::mfma_select_buffer(t_ctx, &sel));
-            uint32_t v[6] = {0, 0, 0, 0, 0, 0};
-            HIP_TRY(hipMemcpyAsync(v, sel, 24, hipMemcpyDeviceToHost, g.stream));
+            uint32_t v[7] = {0, 0, 0, 0, 0, 0, 0};
+            HIP_TRY(hipMemcpyAsync(v, sel, sizeof(v), hipMemcpyDeviceToHost, g.stream));
             HIP_TRY(hipStreamSynchronize(g.stream));
             *out_value = (int)v[k];
             return HVD_OK;

@@ -363,6 +363,8 @@ int hvd_debug_set(const char* key, int value);
  * "mfma_probe_survivors" / "mfma_probe_survivors_hi" / "mfma_probe_survivors_mix": what its probe counted over bits 0..127 /
  * 128..255 / 0..63 + 192..255; "mfma_auto_half": the selection the first stage ran on (0 / 1 / 2 in that order).
  * "mfma_auto_form" keeps meaning the matrix-core form the probe chose, also when the pass ran on the pigeonhole index.
+ * "mfma_probe_close": over the same sample, the 16-bit block pairs (16 per hash pair) within the pigeonhole index's block radius
+ * (1 for max_dist 16..31, 0 below); 0 when the pass was not index-eligible (the probe sums it only then). Read-only.
  * "allpairs_index_used": 1 if the last auto-variant pass ran on the pigeonhole index, else 0; "allpairs_index_kcand": its exact
  * candidate count / 1000 (0 when the probe's estimate kept the histograms from being built).
  * Synchronises the library stream.

@@ -3,9 +3,14 @@ settled pair by pair on the VALU instead of tile by tile on the matrix pipe) -- 
 in frame-pair, video and cross mode, with and without packed hashes, and on the data that overflows its queues -- all
 through the C-ABI, against the CPU oracle."""
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import probe_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -77,7 +82,8 @@ def test_k2_probe_picks_the_pair_queue_on_frame_hashes(gpu, hvd, oracle, frame_l
 
 def test_k2_probe_counts_what_a_host_restatement_of_its_sample_counts(gpu, hvd, frame_library):
     """k_prefilter_probe: up to 4096 sample rows x 4096 sample columns (strided, columns half a stride off the rows), survivors
-    of a 128-bit first stage over bits 0..127 and over bits 128..255 -- the two numbers the form choice rests on."""
+    of a 128-bit first stage over bits 0..127 and over bits 128..255 -- the two numbers the form choice rests on -- and (round
+    5) over bits 0..63 + 192..255, all three through the host model as well (tests/tools/probe_ref.py)."""
     frames, offsets, video, _ = frame_library
     for db in (frames, frames[:3001], np.random.default_rng(5).integers(0, 256, (5000, 32), dtype=np.uint8)):
         n = len(db)
@@ -95,6 +101,9 @@ def test_k2_probe_counts_what_a_host_restatement_of_its_sample_counts(gpu, hvd, 
                 want[h] += int((d <= 31).sum())
         assert lo is None or int((lo <= 31).sum()) == want[0]
         assert [_auto(gpu, b"mfma_probe_survivors"), _auto(gpu, b"mfma_probe_survivors_hi")] == want, n
+        model = probe_ref.counts(db, db, 31)
+        assert list(model[:2]) == want
+        assert _auto(gpu, b"mfma_probe_survivors_mix") == model[2], n
 
 
 def test_k2_pair_queue_settles_from_the_images_when_there_are_no_packed_hashes(gpu, hvd, oracle, frame_library):
