@@ -90,7 +90,7 @@ extern int g_allpairs_index_fail;  // fault injection (tests): context (value - 
 // rank of a pass shares (arguments, n, world, the process-wide key), so all ranks agree.
 bool index_eligible(const AllPairsArgs& a, bool rect, uint32_t* r);
 IndexRule index_rule(const AllPairsArgs& a, uint32_t r);
-// Grows the context's index scratch (~44 B x 16 per hash: copies, rows, partition records). Called outside the launch lock: growing frees the old buffer,
+// Grows the context's index scratch (~28 B x 16 per hash: half-hash copies, rows, partition records). Called outside the launch lock: growing frees the old buffer,
 // which waits for the whole device.
 hipError_t index_reserve(int ctx_id, uint32_t n);
 // Counting sort of the keys (partition, per-key counts, offsets), exact statistics and decision (select[kSelIdxUsed]); then

@@ -13,26 +13,33 @@
 //   k_index_partition   the tiles again: rank from a returning LDS atomic, record {row, key} -> its partition (short runs)
 //   k_index_count       one workgroup per chunk: low-byte digits counted in 256 LDS bins
 //   k_index_offsets     one workgroup per partition: the chunks' counts -> per-key counts, off[b][h * 256 ..], chunk cursors
-//   k_index_stats       one thread per (block, key): exact candidates and the longest work item; the last workgroup decides
+//   k_index_stats       a few hundred workgroups stride over the (block, key)s: exact candidates and the longest work item,
+//                       reduced privately, two atomics and a ticket per workgroup; the last workgroup decides
 //                       (select[kSelIdxUsed], hvd_kernels.h: index_wins) -- the matrix-core forms return at once when it is set
-//   k_index_place       the chunks again: final position from a returning LDS atomic on the bin's cursor; rows, and the hash
-//                       gathered from the packed DB -> hc
+//   k_index_place       the chunks again: final position from a returning LDS atomic on the bin's cursor; rows, and the 16-byte
+//                       half of the hash that does NOT hold block b (words 4..7 for b < 8, words 0..3 otherwise), gathered
+//                       from the packed DB -> hc
 //   k_index_join        one wave per work item (block b, key u): B_u x B_u (positions i < j) and B_u x B_{u ^ (1 << t)} for
-//                       the one-bit neighbours above u; the full 256-bit distance, and a pair is emitted only by its CANONICAL
-//                       block -- the first block whose keys are within r -- so it comes out exactly once, without a dedup pass
+//                       the one-bit neighbours above u. First stage on the indexed half: y in registers, x through scalar
+//                       loads (the bucket is contiguous at a wave-uniform address), one survivor test per batch of x. Survivors
+//                       fetch the other halves from the packed DB through rows; the full 256-bit distance, and a pair is
+//                       emitted only by its CANONICAL block -- the first block whose keys are within r -- so it comes out
+//                       exactly once, without a dedup pass
 // Kernels up to the statistics return at once unless the probe's gate (select[kSelIdxGate]) is set, the last two unless the
 // decision is. Nothing waits on the host.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "hvd_kernels.h"
 
 namespace {
 
 constexpr uint32_t kBlocks = 16, kKeys = 65536;
-constexpr uint32_t kWavePairs = 256;  // a wave's pair buffer in LDS; full -> one atomic reserves room for all of it
+constexpr uint32_t kWavePairs = 64;  // a wave's pair buffer in LDS (a step emits at most 64); full -> one atomic reserves room for all of it
+constexpr uint32_t kXB = 4;          // x entries per scalar batch of the join: one survivor test per batch
 
 __device__ __forceinline__ uint32_t key_of(const uint32_t w[8], uint32_t b) { return (w[b >> 1] >> (16u * (b & 1u))) & 0xFFFFu; }
 
@@ -227,24 +234,31 @@ __global__ __launch_bounds__(256) void k_index_offsets(uint32_t n, const uint32_
     }
 }
 
+constexpr uint32_t kStatsGrid = 256u;  // workgroups of the statistics: each ends in two atomics and a ticket
+
 // Candidates of key u in its block: C(c_u, 2) + (r = 1) c_u x c_v over the one-bit neighbours v = u ^ (1 << t) above u --
 // the exact number of pairs whose keys of this block are within r, i.e. the pairs the join walks for this work item.
 __global__ __launch_bounds__(256) void k_index_stats(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ select,
                                                      const hvd::IndexRule q) {
     if (select[hvd::kSelIdxGate] == 0u) return;
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;  // < kBlocks * kKeys: the grid is exact
-    const uint32_t u = t & (kKeys - 1u);
-    const uint32_t* cb = cnt + (t & ~(kKeys - 1u));
-    const unsigned long long c = cb[u];
-    unsigned long long cand = c * (c - (c != 0ull)) / 2ull, ylen = c;
-    if (q.r != 0u && c != 0ull) {
+    // the workgroups stride over the kBlocks * kKeys (block, key)s (a multiple of the grid's threads) and reduce privately
+    unsigned long long cand = 0;
+    uint32_t mx = 0;
+    for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < kBlocks * kKeys; t += gridDim.x * 256u) {
+        const uint32_t u = t & (kKeys - 1u);
+        const uint32_t* cb = cnt + (t & ~(kKeys - 1u));
+        const unsigned long long c = cb[u];
+        unsigned long long ylen = c;
+        cand += c * (c - (c != 0ull)) / 2ull;
+        if (q.r != 0u && c != 0ull) {
 #pragma unroll
-        for (uint32_t s = 0; s < 16u; ++s)
-            if (((u >> s) & 1u) == 0u) ylen += cb[u ^ (1u << s)];
-        cand += c * (ylen - c);
+            for (uint32_t s = 0; s < 16u; ++s)
+                if (((u >> s) & 1u) == 0u) ylen += cb[u ^ (1u << s)];
+            cand += c * (ylen - c);
+        }
+        // the work item's walk: its wave steps its c x's over a y list of ylen entries (saturated: any such item loses anyway)
+        mx = max(mx, (uint32_t)min(c * ylen, 0xFFFFFFFFull));
     }
-    // the work item's walk: its wave steps its c x's over a y list of ylen entries (saturated: any such item loses anyway)
-    uint32_t mx = (uint32_t)min(c * ylen, 0xFFFFFFFFull);
     for (int off = 32; off > 0; off >>= 1) {
         cand += __shfl_down(cand, off);
         mx = max(mx, (uint32_t)__shfl_down((int)mx, off));
@@ -273,7 +287,8 @@ __global__ __launch_bounds__(256) void k_index_stats(const uint32_t* __restrict_
     }
 }
 
-// hc[b][pos] = {hash words 0..3, 4..7} (gathered from the packed DB), rows[b][pos] = row, in key order: pos from a returning
+// hc[b][pos] = the 16-byte half of the hash that does not hold block b (gathered from the packed DB: words 4..7 for b < 8,
+// words 0..3 otherwise -- the half the join compares first), rows[b][pos] = row, in key order: pos from a returning
 // LDS atomic on the bin's cursor (order inside a bucket: whatever the atomics give -- the join's rule does not depend on it).
 // The chunks of a partition fill its region of hc and rows completely, and nobody else writes there.
 __global__ __launch_bounds__(256) void k_index_place(const uint4* __restrict__ db, const uint2* __restrict__ rec, uint32_t n, uint32_t csz,
@@ -290,10 +305,11 @@ __global__ __launch_bounds__(256) void k_index_place(const uint4* __restrict__ d
     __syncthreads();
     const uint2* __restrict__ r = rec + q.at;
     const size_t base = (size_t)q.b * n;
+    const uint32_t sa = q.b < 8u ? 1u : 0u;
     constexpr uint32_t kU = 4u;  // entries per thread in flight: their gathers overlap
     for (uint32_t e0 = q.lo; e0 < q.hi; e0 += 256u * kU) {
         uint32_t row[kU], low[kU], pos[kU];
-        uint4 h0[kU], h1[kU];
+        uint4 h[kU];
 #pragma unroll
         for (uint32_t u = 0; u < kU; ++u) {
             const uint32_t e = e0 + u * 256u + tid;
@@ -304,16 +320,14 @@ __global__ __launch_bounds__(256) void k_index_place(const uint4* __restrict__ d
 #pragma unroll
         for (uint32_t u = 0; u < kU; ++u) {
             const uint32_t g = min(row[u], n - 1u);
-            h0[u] = db[(size_t)g * 2u];
-            h1[u] = db[(size_t)g * 2u + 1u];
+            h[u] = db[(size_t)g * 2u + sa];
         }
 #pragma unroll
         for (uint32_t u = 0; u < kU; ++u) pos[u] = row[u] < n ? lds_add(&cur[low[u]]) : n;
 #pragma unroll
         for (uint32_t u = 0; u < kU; ++u)
             if (pos[u] < n) {
-                hc[(base + pos[u]) * 2u] = h0[u];
-                hc[(base + pos[u]) * 2u + 1u] = h1[u];
+                hc[base + pos[u]] = h[u];
                 rows[base + pos[u]] = row[u];
             }
     }
@@ -323,10 +337,26 @@ __device__ __forceinline__ uint32_t popc4(const uint4& x, const uint4& y) {
     return __popc(x.x ^ y.x) + __popc(x.y ^ y.y) + __popc(x.z ^ y.z) + __popc(x.w ^ y.w);
 }
 
+// The index as the join reads its x side: constant address space, so that a wave-uniform address is read by scalar loads
+// (the index is read-only for the whole kernel) and the words reach the xor as scalar operands.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef const __attribute__((address_space(4))) u32x4 kx4;
+
+// acc + popcount(v) in one instruction (the compiler, left alone, counts three of the four words from zero and adds up after)
+__device__ __forceinline__ uint32_t bcnt_acc(uint32_t v, uint32_t acc) {
+    uint32_t r;
+    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(v), "v"(acc));
+    return r;
+}
+__device__ __forceinline__ uint32_t popc4s(const u32x4 x, const uint4& y) {
+    return bcnt_acc(x.w ^ y.w, bcnt_acc(x.z ^ y.z, bcnt_acc(x.y ^ y.y, __popc(x.x ^ y.x))));
+}
+
 struct JoinArgs {
     const uint32_t* off;
     const uint4* hc;
     const uint32_t* rows;
+    const uint4* db;
     uint32_t n;
     const int32_t* group;
     hvd_pair* out;
@@ -345,13 +375,39 @@ __device__ __forceinline__ void flush_wave(const JoinArgs& a, const hvd_pair* bu
         if (base + k < a.cap) a.out[base + k] = buf[k];
 }
 
+// One batch of kXB x entries against the wave's 64 y: does any lane come within max_dist of any of them on the indexed half?
+// All kXB entries are read at once, whatever the bucket holds: one past its end can only raise a false alarm, which the walk
+// one by one (over the bucket's entries only) puts right. OWN: the round overlaps the item's own bucket, where x index k
+// pairs with a y only if k < ylim (<= the bucket's size).
+template <bool OWN>
+__device__ __forceinline__ bool batch_hit(kx4* xp, const uint4& ya, uint32_t max_dist, uint32_t k0, uint32_t ylim) {
+    u32x4 x[kXB];
+#pragma unroll
+    for (uint32_t j = 0; j < kXB; ++j) x[j] = xp[j];
+    uint32_t d[kXB];
+#pragma unroll
+    for (uint32_t j = 0; j < kXB; ++j) d[j] = popc4s(x[j], ya);
+    if (OWN) {
+        bool c = false;
+#pragma unroll
+        for (uint32_t j = 0; j < kXB; ++j) c |= d[j] <= max_dist && k0 + j < ylim;
+        return __any(c);
+    }
+    uint32_t m = d[0];
+#pragma unroll
+    for (uint32_t j = 1; j < kXB; ++j) m = min(m, d[j]);
+    return __any(m <= max_dist);
+}
+
 // Work item = (block b, key u), one wave each; item (b << 16 | u) belongs to rank item mod world. The y list of an item is
 // its own bucket (segment 0) followed by the buckets u ^ (1 << t) > u (r = 1): lanes take 64 consecutive entries of it per
-// round; the x side is the bucket itself, staged 64 at a time in LDS and read as a broadcast. The 128 bits that do NOT hold
-// block b are compared first (a candidate's key agrees, its other bits are unrelated: ~64 of 128 differ); only when a lane of
-// the wave is within max_dist there does the wave look at the rest.
+// round and hold their y -- the 128 bits that do NOT hold block b, which is all the index stores -- in registers; the next
+// round's y is loaded before the current round's x loop. The x side is the bucket itself, contiguous at a wave-uniform
+// address: kXB entries per scalar batch, xor'ed as scalar operands, one survivor test per batch. A candidate's key agrees and
+// its other bits are unrelated (~64 of 128 differ), so a batch with a lane within max_dist is rare: only then are its x
+// looked at one by one, and the lanes that pass fetch the other 128 bits of both hashes from the packed DB through rows.
+// Positions inside the own bucket are the first nu entries of the y list: only the rounds with p0 < nu pay for the i < j rule.
 __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint32_t* __restrict__ select) {
-    __shared__ uint4 xs_a[4][64], xs_b[4][64];
     __shared__ hvd_pair pbuf[4][kWavePairs];
     if (select[hvd::kSelIdxUsed] == 0u) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
@@ -359,19 +415,16 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
     const uint32_t item = (blockIdx.x * 4u + wave) * a.world + a.rank;
     if (item >= kBlocks * kKeys) return;  // (wave-uniform; nothing below synchronises across waves)
     const uint32_t b = item >> 16, u = item & (kKeys - 1u);
-    const uint32_t* offb = a.off + (size_t)b * (kKeys + 1u);
+    const uint32_t* __restrict__ offb = a.off + (size_t)b * (kKeys + 1u);
+    // the bucket's and the 16 neighbours' offset pairs, all issued before the first of them is needed
+    // segments: lane 0 the bucket itself, lane 1 + t the bucket u ^ (1 << t) if that key lies above u
+    const bool nb = lane >= 1u && lane <= 16u && a.r != 0u && ((u >> ((lane - 1u) & 15u)) & 1u) == 0u;
+    const uint32_t v = nb ? u ^ (1u << ((lane - 1u) & 15u)) : u;
+    const uint32_t vstart = offb[v], vend = offb[v + 1u];
     const uint32_t s0 = offb[u], nu = offb[u + 1u] - s0;
     if (nu == 0u) return;
-    // segments: lane 0 the bucket itself, lane 1 + t the bucket u ^ (1 << t) if that key lies above u
-    uint32_t sstart = 0, ssize = 0;
-    if (lane == 0u) {
-        sstart = s0;
-        ssize = nu;
-    } else if (lane <= 16u && a.r != 0u && ((u >> (lane - 1u)) & 1u) == 0u) {
-        const uint32_t v = u ^ (1u << (lane - 1u));
-        sstart = offb[v];
-        ssize = offb[v + 1u] - sstart;
-    }
+    const uint32_t sstart = lane == 0u || nb ? vstart : 0u;
+    const uint32_t ssize = lane == 0u || nb ? vend - vstart : 0u;
     uint32_t incl = ssize;
     for (int d = 1; d < 32; d <<= 1) {
         const uint32_t y = __shfl_up(incl, d);
@@ -383,88 +436,96 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
     for (int s = 0; s < 16; ++s) ends[s] = (uint32_t)__builtin_amdgcn_readlane((int)incl, s);
     const uint32_t ny = (uint32_t)__builtin_amdgcn_readlane((int)incl, 16);
     const size_t base = (size_t)b * a.n;
-    const uint4* __restrict__ hb = a.hc + base * 2u;
-    const uint32_t sa = b < 8u ? 1u : 0u;  // the 16-B half that does not hold block b: compared first
-    const uint32_t nxc = (nu + 63u) >> 6;
-    auto stage = [&](uint32_t xc) {
-        const uint32_t k = xc * 64u + lane;
-        if (k < nu) {
-            xs_a[wave][lane] = hb[(size_t)(s0 + k) * 2u + sa];
-            xs_b[wave][lane] = hb[(size_t)(s0 + k) * 2u + (sa ^ 1u)];
-        }
-        __builtin_amdgcn_wave_barrier();
-    };
-    if (nxc == 1u) stage(0u);
-    uint32_t fill = 0;  // wave-uniform
+    const uint4* __restrict__ hb = a.hc + base;
+    // (a batch reads kXB entries whatever the bucket holds: at most kXB - 1 entries past the block's last position, and behind
+    // the last block's hc lie the rows, 64 B per hash, in the same allocation)
+    kx4* xb = (kx4*)(a.hc + base + s0);
+    const uint32_t sa = b < 8u ? 1u : 0u;  // the 16-B half that does not hold block b: the one in hc
+    uint32_t fill = 0;                    // wave-uniform
     hvd_pair* buf = pbuf[wave];
+
+    // x entry k of the bucket against the wave's y, one by one: the batch had a lane within max_dist
+    auto examine = [&](uint32_t k, const uint4& ya, uint32_t ypos, uint32_t ylim) {
+        const u32x4 xv = xb[k];
+        const uint4 xa = make_uint4(xv.x, xv.y, xv.z, xv.w);
+        const uint32_t d0 = popc4(xa, ya);
+        const bool c = d0 <= a.max_dist && k < ylim;
+        if (!__any(c)) return;
+        bool emit = false;
+        uint32_t d = 0, i = 0, j = 0;
+        if (c) {
+            const uint32_t ri = a.rows[base + s0 + k], rj = a.rows[base + ypos];
+            const uint4 xo = a.db[(size_t)ri * 2u + (sa ^ 1u)], yo = a.db[(size_t)rj * 2u + (sa ^ 1u)];
+            d = d0 + popc4(xo, yo);
+            emit = d <= a.max_dist;
+            if (emit) {
+                const uint4 lo_x = sa ? xo : xa, hi_x = sa ? xa : xo, lo_y = sa ? yo : ya, hi_y = sa ? ya : yo;
+                const uint32_t dw[8] = {lo_x.x ^ lo_y.x, lo_x.y ^ lo_y.y, lo_x.z ^ lo_y.z, lo_x.w ^ lo_y.w,
+                                        hi_x.x ^ hi_y.x, hi_x.y ^ hi_y.y, hi_x.z ^ hi_y.z, hi_x.w ^ hi_y.w};
+                uint32_t within = 0;  // bit b2: the keys of block b2 are within r
+#pragma unroll
+                for (uint32_t b2 = 0; b2 < kBlocks; ++b2) within |= (uint32_t)__popc(key_of(dw, b2)) <= a.r ? 1u << b2 : 0u;
+                if ((within & ((1u << b) - 1u)) != 0u) emit = false;  // an earlier block within r owns this pair
+            }
+            if (emit && a.group != nullptr && a.group[ri] == a.group[rj]) emit = false;
+            i = min(ri, rj);
+            j = max(ri, rj);
+        }
+        const unsigned long long em = __ballot(emit);
+        const uint32_t m = (uint32_t)__popcll(em);
+        if (m == 0u) return;
+        if (fill + m > kWavePairs) {
+            flush_wave(a, buf, fill, lane);
+            fill = 0;
+        }
+        if (emit) {
+            const uint32_t slot = fill + __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
+            hvd_pair rec;
+            rec.i = i;
+            rec.j = j;
+            rec.dist = d;
+            rec.pad = 0;
+            buf[slot] = rec;
+        }
+        fill += m;
+    };
+    // the whole bucket against one round's y
+    auto walk = [&](auto own, const uint4& ya, uint32_t ypos, uint32_t ylim) {
+        constexpr bool kOwn = decltype(own)::value;
+        for (uint32_t k0 = 0; k0 < nu; k0 += kXB) {
+            const uint32_t nvalid = min(kXB, nu - k0);
+            const bool hit = batch_hit<kOwn>(xb + k0, ya, a.max_dist, k0, ylim);
+            if (__builtin_expect(hit, 0))
+                for (uint32_t j = 0; j < nvalid; ++j) examine(k0 + j, ya, ypos, ylim);
+        }
+    };
+    // entry p of the y list: its segment and its position inside block b
+    auto locate = [&](uint32_t p, uint32_t* seg) {
+        uint32_t sg = 0;
+#pragma unroll
+        for (int s = 0; s < 16; ++s) sg += p >= ends[s] ? 1u : 0u;
+        *seg = sg;
+        return (uint32_t)((int)p + __shfl(delta, (int)sg));
+    };
+    uint32_t seg, ypos = locate(lane, &seg);
+    uint4 ya = make_uint4(0u, 0u, 0u, 0u);
+    if (lane < ny) ya = hb[ypos];
     for (uint32_t p0 = 0; p0 < ny; p0 += 64u) {
         const uint32_t p = p0 + lane;
-        uint32_t seg = 0;
-#pragma unroll
-        for (int s = 0; s < 16; ++s) seg += p >= ends[s] ? 1u : 0u;
-        const uint32_t ypos = (uint32_t)((int)p + __shfl(delta, (int)seg));
-        const bool has_y = p < ny;
+        uint32_t seg_n;
+        const uint32_t ypos_n = locate(p + 64u, &seg_n);
+        asm volatile("" ::"v"(ya.x), "v"(ya.y), "v"(ya.z), "v"(ya.w));  // (this round's y has arrived before the next one's load is issued)
+        uint4 ya_n = make_uint4(0u, 0u, 0u, 0u);
+        if (p + 64u < ny) ya_n = hb[ypos_n];  // the next round's y: in flight under this round's x loop
         // x index k pairs with this y iff k < ylim: inside the bucket only the x before it (positions i < j)
-        const uint32_t ylim = !has_y ? 0u : seg == 0u ? p : nu;
-        uint4 ya = make_uint4(0u, 0u, 0u, 0u), yb = ya;
-        if (has_y) {
-            ya = hb[(size_t)ypos * 2u + sa];
-            yb = hb[(size_t)ypos * 2u + (sa ^ 1u)];
-        }
-        for (uint32_t xc = 0; xc < nxc; ++xc) {
-            if (nxc > 1u) {
-                __builtin_amdgcn_wave_barrier();  // (every lane is done with the previous chunk)
-                stage(xc);
-            }
-            const uint32_t xn = min(64u, nu - xc * 64u), k0 = xc * 64u;
-            for (uint32_t k = 0; k < xn; ++k) {
-                const uint32_t d0 = popc4(xs_a[wave][k], ya);
-                const bool c = d0 <= a.max_dist && k0 + k < ylim;
-                if (__builtin_expect(__any(c), 0)) {
-                    bool emit = false;
-                    uint32_t d = 0, i = 0, j = 0;
-                    if (c) {
-                        const uint4 xa = xs_a[wave][k], xb = xs_b[wave][k];
-                        d = d0 + popc4(xb, yb);
-                        emit = d <= a.max_dist;
-                        if (emit) {
-                            const uint4 lo_x = sa ? xb : xa, hi_x = sa ? xa : xb, lo_y = sa ? yb : ya, hi_y = sa ? ya : yb;
-                            const uint32_t dw[8] = {lo_x.x ^ lo_y.x, lo_x.y ^ lo_y.y, lo_x.z ^ lo_y.z, lo_x.w ^ lo_y.w,
-                                                    hi_x.x ^ hi_y.x, hi_x.y ^ hi_y.y, hi_x.z ^ hi_y.z, hi_x.w ^ hi_y.w};
-                            for (uint32_t b2 = 0; b2 < b; ++b2)  // an earlier block within r owns this pair
-                                if ((uint32_t)__popc(key_of(dw, b2)) <= a.r) {
-                                    emit = false;
-                                    break;
-                                }
-                        }
-                        if (emit) {
-                            const uint32_t ri = a.rows[base + s0 + k0 + k], rj = a.rows[base + ypos];
-                            if (a.group != nullptr && a.group[ri] == a.group[rj]) emit = false;
-                            i = min(ri, rj);
-                            j = max(ri, rj);
-                        }
-                    }
-                    const unsigned long long em = __ballot(emit);
-                    const uint32_t m = (uint32_t)__popcll(em);
-                    if (m != 0u) {
-                        if (fill + m > kWavePairs) {
-                            flush_wave(a, buf, fill, lane);
-                            fill = 0;
-                        }
-                        if (emit) {
-                            const uint32_t slot = fill + __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
-                            hvd_pair rec;
-                            rec.i = i;
-                            rec.j = j;
-                            rec.dist = d;
-                            rec.pad = 0;
-                            buf[slot] = rec;
-                        }
-                        fill += m;
-                    }
-                }
-            }
-        }
+        const uint32_t ylim = p >= ny ? 0u : seg == 0u ? p : nu;
+        if (p0 < nu)
+            walk(std::true_type(), ya, ypos, ylim);
+        else
+            walk(std::false_type(), ya, ypos, ylim);
+        seg = seg_n;
+        ypos = ypos_n;
+        ya = ya_n;
     }
     if (fill != 0u) flush_wave(a, buf, fill, lane);
 }
@@ -476,7 +537,7 @@ namespace hvd {
 int g_allpairs_index = -1;
 int g_allpairs_index_fail = 0;
 
-// per-context scratch: per-key counts [16][65536], offsets [16][65537], hash copies [16][n] x 32 B, rows [16][n]; for the
+// per-context scratch: per-key counts [16][65536], offsets [16][65537], half-hash copies [16][n] x 16 B, rows [16][n]; for the
 // build: partition records [16][n] x 8 B, tile counts [4096][tiles], and per partition / chunk: sizes, bases, first chunks,
 // the chunk list and the chunks' low-byte counts (cursors)
 struct IndexScratch {
@@ -494,7 +555,7 @@ static uint32_t index_chunk(uint32_t n) { return max(kMinChunk, 2u * ((n + 255u)
 static size_t tcnt_words(uint32_t n) { return ((size_t)kParts * index_tiles(n) + 3u) & ~(size_t)3u; }
 constexpr size_t kPartWords = 3u * kParts + 4u + kMaxChunks;  // ptotal, pbase, pfirst (+ 1, padded), chunk_p
 static size_t index_bytes(uint32_t n) {
-    return 4u * (size_t)kBlocks * kKeys + 4u * off_words() + (size_t)kBlocks * n * 32u + (size_t)kBlocks * n * 4u +
+    return 4u * (size_t)kBlocks * kKeys + 4u * off_words() + (size_t)kBlocks * n * 16u + (size_t)kBlocks * n * 4u +
            (size_t)kBlocks * n * 8u + 4u * tcnt_words(n) + 4u * kPartWords + 4u * (size_t)kMaxChunks * 256u;
 }
 struct IndexPtrs {
@@ -511,7 +572,7 @@ static IndexPtrs index_ptrs(int ctx_id, uint32_t n) {
     q.cnt = (uint32_t*)p;
     q.off = (uint32_t*)(p + 4u * (size_t)kBlocks * kKeys);
     q.hc = (uint4*)(p + 4u * (size_t)kBlocks * kKeys + 4u * off_words());
-    q.rows = (uint32_t*)((char*)q.hc + (size_t)kBlocks * n * 32u);
+    q.rows = (uint32_t*)((char*)q.hc + (size_t)kBlocks * n * 16u);
     q.rec = (uint2*)(q.rows + (size_t)kBlocks * n);  // (16 n words behind a 16-byte boundary: aligned)
     q.tcnt = (uint32_t*)(q.rec + (size_t)kBlocks * n);
     q.ptotal = q.tcnt + tcnt_words(n);
@@ -540,7 +601,9 @@ IndexRule index_rule(const AllPairsArgs& a, uint32_t r) {
     // (DESIGN 4.1, 1 M uniform hashes on MI355X: form 9 18.1 ms = 36 fs per comparison, forms 18 / 12 +4 / +11 %; join 2.0 ms
     // for 2.075e9 candidates; the counting sort, the statistics and the place pass 0.93 ms, of which ~0.03 ms do not depend
     // on n (the scans over 4096 partitions, the grid of 6144 chunks): 0.9 ns per hash, and those 30 us next to the 40 us of
-    // launches; the longest work item's wave takes ~30 ns per step of 64 pairs)
+    // launches; the longest work item's wave takes ~30 ns per step of 64 pairs. These are the figures of the full-width
+    // index with the LDS-staged join: the half-width index and the scalar-x join have not been profiled yet, so ps_cand and
+    // ps_hash are the old, costlier ones -- the rule can only be too cautious about the index until they are re-derived)
     q.fs_mfma_fetch = 36.0f;
     q.fs_mfma_other = 40.0f;
     q.ps_cand = 1.0f;
@@ -588,7 +651,7 @@ hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const 
     hipLaunchKernelGGL(k_index_count, dim3(kMaxChunks), dim3(256), 0, s, p.rec, a.n, csz, p.ptotal, p.pbase, p.pfirst, p.chunk_p,
                        p.ccount, d_select);
     hipLaunchKernelGGL(k_index_offsets, dim3(kParts), dim3(256), 0, s, a.n, p.pbase, p.pfirst, p.ccount, p.cnt, p.off, d_select);
-    hipLaunchKernelGGL(k_index_stats, dim3(kBlocks * kKeys / 256u), dim3(256), 0, s, p.cnt, d_select, q);
+    hipLaunchKernelGGL(k_index_stats, dim3(kStatsGrid), dim3(256), 0, s, p.cnt, d_select, q);
     return hipGetLastError();
 }
 
@@ -600,6 +663,7 @@ hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t
     j.off = p.off;
     j.hc = p.hc;
     j.rows = p.rows;
+    j.db = (const uint4*)a.d_db;
     j.n = a.n;
     j.group = a.d_group;
     j.out = a.d_pairs;
