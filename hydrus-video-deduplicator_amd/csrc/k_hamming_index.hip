@@ -10,21 +10,24 @@
 //   k_index_scan_rows   one wave per partition (block, high byte): exclusive scan over the tiles, the partition's size
 //   k_index_scan_parts  one workgroup: every partition's base inside its block, and the list of chunks (a partition larger
 //                       than csz entries is cut into several, so that no workgroup sets the length of the passes below)
-//   k_index_partition   the tiles again: rank from a returning LDS atomic, record {row, key} -> its partition (short runs)
+//   k_index_partition   the tiles again: rank from a returning LDS atomic, record {row, key | sibling key << 16} -> its
+//                       partition (short runs): the record carries the whole 32-bit word that holds block b
 //   k_index_count       one workgroup per chunk: low-byte digits counted in 256 LDS bins
 //   k_index_offsets     one workgroup per partition: the chunks' counts -> per-key counts, off[b][h * 256 ..], chunk cursors
 //   k_index_stats       a few hundred workgroups stride over the (block, key)s: exact candidates and the longest work item,
 //                       reduced privately, two atomics and a ticket per workgroup; the last workgroup decides
 //                       (select[kSelIdxUsed], hvd_kernels.h: index_wins) -- the matrix-core forms return at once when it is set
-//   k_index_place       the chunks again: final position from a returning LDS atomic on the bin's cursor; rows, and the 16-byte
-//                       half of the hash that does NOT hold block b (words 4..7 for b < 8, words 0..3 otherwise), gathered
-//                       from the packed DB -> hc
+//   k_index_place       the chunks again: final position from a returning LDS atomic on the bin's cursor; the record's word
+//                       -> hw, its row -> rows (the packed DB is not touched)
 //   k_index_join        one wave per work item (block b, key u): B_u x B_u (positions i < j) and B_u x B_{u ^ (1 << t)} for
-//                       the one-bit neighbours above u. First stage on the indexed half: y in registers, x through scalar
-//                       loads (the bucket is contiguous at a wave-uniform address), one survivor test per batch of x. Survivors
-//                       fetch the other halves from the packed DB through rows; the full 256-bit distance, and a pair is
-//                       emitted only by its CANONICAL block -- the first block whose keys are within r -- so it comes out
-//                       exactly once, without a dedup pass
+//                       the one-bit neighbours above u. First stage on the word that holds block b: a pair within max_dist
+//                       has a word within tw = max_dist / 8 bits (8 (tw + 1) > max_dist), and one of that word's two blocks
+//                       within tw / 2 = r. y in registers, x through scalar loads (the bucket is contiguous at a wave-uniform
+//                       address), xor + popcount + one shift of the outcome into a per-lane mask per candidate.
+//                       Survivors queue up in LDS and are drained 64 at a time: both whole hashes from the packed DB through
+//                       rows, the full 256-bit distance, and a pair is emitted only by its CANONICAL block -- the first
+//                       block that QUALIFIES (keys within r and word within tw: what lets a candidate reach the full check)
+//                       -- so it comes out exactly once, without a dedup pass
 // Kernels up to the statistics return at once unless the probe's gate (select[kSelIdxGate]) is set, the last two unless the
 // decision is. Nothing waits on the host.
 #include <hip/hip_runtime.h>
@@ -38,8 +41,9 @@
 namespace {
 
 constexpr uint32_t kBlocks = 16, kKeys = 65536;
-constexpr uint32_t kWavePairs = 64;  // a wave's pair buffer in LDS (a step emits at most 64); full -> one atomic reserves room for all of it
-constexpr uint32_t kXB = 4;          // x entries per scalar batch of the join: one survivor test per batch
+constexpr uint32_t kWavePairs = 64;  // a wave's pair buffer in LDS (a drain emits at most 64); full -> one atomic reserves room for all of it
+constexpr uint32_t kXB = 16;         // x entries per scalar batch of the join: one 64-byte scalar load, one survivor mask per lane
+constexpr uint32_t kQueue = 128;     // a wave's survivor queue in LDS (a ring): a push adds at most 64, 64 pending are drained at once
 
 __device__ __forceinline__ uint32_t key_of(const uint32_t w[8], uint32_t b) { return (w[b >> 1] >> (16u * (b & 1u))) & 0xFFFFu; }
 
@@ -140,7 +144,8 @@ __global__ __launch_bounds__(1024) void k_index_scan_parts(const uint32_t* __res
     if (tid == 1023u) pfirst[kParts] = min(first, kMaxChunks);
 }
 
-// rec[b][pbase + tile base + rank] = {row, key of block b}: the rank inside the tile's run comes from a returning LDS atomic.
+// rec[b][pbase + tile base + rank] = {row, key of block b | key of its sibling block b ^ 1 << 16} -- the word that holds block b,
+// its own key in the low half whichever half that is: the rank inside the tile's run comes from a returning LDS atomic.
 // Block by block, so that the runs a workgroup is filling at any time are few (256 x ~128 B) and soon complete.
 __global__ __launch_bounds__(kTileThreads) void k_index_partition(const uint4* __restrict__ db, uint32_t n, uint32_t ntiles,
                                                                   const uint32_t* __restrict__ tcnt, const uint32_t* __restrict__ pbase,
@@ -165,7 +170,7 @@ __global__ __launch_bounds__(kTileThreads) void k_index_partition(const uint4* _
             if (i < n) {
                 const uint32_t key = key_of(w[j], b);
                 const uint32_t pos = lds_add(&cur[b * 256u + (key >> 8)]);
-                if (pos < n) rec[(size_t)b * n + pos] = make_uint2(i, key);
+                if (pos < n) rec[(size_t)b * n + pos] = make_uint2(i, key | key_of(w[j], b ^ 1u) << 16);
             }
         }
     }
@@ -174,7 +179,7 @@ __global__ __launch_bounds__(kTileThreads) void k_index_partition(const uint4* _
 // A chunk's place: partition, block, and its entries [lo, hi) of the partition's records.
 struct Chunk {
     uint32_t p, b, lo, hi;
-    size_t at;  // the partition's first record inside rec / its first position inside hc and rows (block included)
+    size_t at;  // the partition's first record inside rec / its first position inside hw and rows (block included)
 };
 __device__ __forceinline__ bool chunk_of(uint32_t c, uint32_t n, uint32_t csz, const uint32_t* __restrict__ ptotal,
                                          const uint32_t* __restrict__ pbase, const uint32_t* __restrict__ pfirst,
@@ -287,14 +292,14 @@ __global__ __launch_bounds__(256) void k_index_stats(const uint32_t* __restrict_
     }
 }
 
-// hc[b][pos] = the 16-byte half of the hash that does not hold block b (gathered from the packed DB: words 4..7 for b < 8,
-// words 0..3 otherwise -- the half the join compares first), rows[b][pos] = row, in key order: pos from a returning
-// LDS atomic on the bin's cursor (order inside a bucket: whatever the atomics give -- the join's rule does not depend on it).
-// The chunks of a partition fill its region of hc and rows completely, and nobody else writes there.
-__global__ __launch_bounds__(256) void k_index_place(const uint4* __restrict__ db, const uint2* __restrict__ rec, uint32_t n, uint32_t csz,
+// hw[b][pos] = the record's word (key of block b | sibling key << 16: what the join compares first), rows[b][pos] = row, in
+// key order: pos from a returning LDS atomic on the bin's cursor (order inside a bucket: whatever the atomics give -- the
+// join's rule does not depend on it). Records in, words and rows out: the packed DB is not read.
+// The chunks of a partition fill its region of hw and rows completely, and nobody else writes there.
+__global__ __launch_bounds__(256) void k_index_place(const uint2* __restrict__ rec, uint32_t n, uint32_t csz,
                                                      const uint32_t* __restrict__ ptotal, const uint32_t* __restrict__ pbase,
                                                      const uint32_t* __restrict__ pfirst, const uint32_t* __restrict__ chunk_p,
-                                                     const uint32_t* __restrict__ ccount, uint4* __restrict__ hc, uint32_t* __restrict__ rows,
+                                                     const uint32_t* __restrict__ ccount, uint32_t* __restrict__ hw, uint32_t* __restrict__ rows,
                                                      const uint32_t* __restrict__ select) {
     __shared__ uint32_t cur[256];
     if (select[hvd::kSelIdxUsed] == 0u) return;
@@ -305,56 +310,45 @@ __global__ __launch_bounds__(256) void k_index_place(const uint4* __restrict__ d
     __syncthreads();
     const uint2* __restrict__ r = rec + q.at;
     const size_t base = (size_t)q.b * n;
-    const uint32_t sa = q.b < 8u ? 1u : 0u;
-    constexpr uint32_t kU = 4u;  // entries per thread in flight: their gathers overlap
+    constexpr uint32_t kU = 4u;  // entries per thread in flight: their loads overlap
     for (uint32_t e0 = q.lo; e0 < q.hi; e0 += 256u * kU) {
-        uint32_t row[kU], low[kU], pos[kU];
-        uint4 h[kU];
+        uint2 rc[kU];
+        uint32_t pos[kU];
 #pragma unroll
         for (uint32_t u = 0; u < kU; ++u) {
             const uint32_t e = e0 + u * 256u + tid;
-            const uint2 rc = e < q.hi ? r[e] : make_uint2(n, 0u);
-            row[u] = rc.x;  // (n: no entry)
-            low[u] = rc.y & 255u;
+            rc[u] = e < q.hi ? r[e] : make_uint2(n, 0u);  // (row n: no entry)
         }
 #pragma unroll
-        for (uint32_t u = 0; u < kU; ++u) {
-            const uint32_t g = min(row[u], n - 1u);
-            h[u] = db[(size_t)g * 2u + sa];
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < kU; ++u) pos[u] = row[u] < n ? lds_add(&cur[low[u]]) : n;
+        for (uint32_t u = 0; u < kU; ++u) pos[u] = rc[u].x < n ? lds_add(&cur[rc[u].y & 255u]) : n;
 #pragma unroll
         for (uint32_t u = 0; u < kU; ++u)
             if (pos[u] < n) {
-                hc[base + pos[u]] = h[u];
-                rows[base + pos[u]] = row[u];
+                hw[base + pos[u]] = rc[u].y;
+                rows[base + pos[u]] = rc[u].x;
             }
     }
 }
 
-__device__ __forceinline__ uint32_t popc4(const uint4& x, const uint4& y) {
-    return __popc(x.x ^ y.x) + __popc(x.y ^ y.y) + __popc(x.z ^ y.z) + __popc(x.w ^ y.w);
-}
-
 // The index as the join reads its x side: constant address space, so that a wave-uniform address is read by scalar loads
-// (the index is read-only for the whole kernel) and the words reach the xor as scalar operands.
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(4))) u32x4 kx4;
+// (the index is read-only for the whole kernel) and the words reach the xor as scalar operands. A bucket begins at any
+// word, so a batch of kXB words is aligned to 4 bytes only.
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+typedef u32x16 u32x16w __attribute__((aligned(4)));
+typedef const __attribute__((address_space(4))) uint32_t kxw;
+typedef const __attribute__((address_space(4))) u32x16w kx16;
 
-// acc + popcount(v) in one instruction (the compiler, left alone, counts three of the four words from zero and adds up after)
-__device__ __forceinline__ uint32_t bcnt_acc(uint32_t v, uint32_t acc) {
-    uint32_t r;
-    asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(v), "v"(acc));
-    return r;
-}
-__device__ __forceinline__ uint32_t popc4s(const u32x4 x, const uint4& y) {
-    return bcnt_acc(x.w ^ y.w, bcnt_acc(x.z ^ y.z, bcnt_acc(x.y ^ y.y, __popc(x.x ^ y.x))));
+// One candidate of the first stage: fails = fails << 1 | (popcount(x ^ y) > tw). The popcount accumulates onto
+// kfail = 2^31 - 1 - tw, so bit 31 of the sum is "more than tw bits differ", and one v_alignbit of {fails, sum} by 31 shifts
+// that bit in: xor, popcount, align -- three VALU instructions, no compare and no condition code between them
+__device__ __forceinline__ uint32_t word_step(uint32_t fails, uint32_t x, uint32_t y, uint32_t kfail) {
+    const uint32_t d = (uint32_t)__popc(x ^ y) + kfail;
+    return __builtin_amdgcn_alignbit(fails, d, 31u);
 }
 
 struct JoinArgs {
     const uint32_t* off;
-    const uint4* hc;
+    const uint32_t* hw;
     const uint32_t* rows;
     const uint4* db;
     uint32_t n;
@@ -362,7 +356,7 @@ struct JoinArgs {
     hvd_pair* out;
     unsigned long long cap;
     unsigned long long* count;
-    uint32_t max_dist, r, rank, world;
+    uint32_t max_dist, r, tw, rank, world;
 };
 
 // A wave's buffered pairs -> global: one atomic reserves room for all of them; beyond `cap` nothing is written but the count
@@ -375,40 +369,21 @@ __device__ __forceinline__ void flush_wave(const JoinArgs& a, const hvd_pair* bu
         if (base + k < a.cap) a.out[base + k] = buf[k];
 }
 
-// One batch of kXB x entries against the wave's 64 y: does any lane come within max_dist of any of them on the indexed half?
-// All kXB entries are read at once, whatever the bucket holds: one past its end can only raise a false alarm, which the walk
-// one by one (over the bucket's entries only) puts right. OWN: the round overlaps the item's own bucket, where x index k
-// pairs with a y only if k < ylim (<= the bucket's size).
-template <bool OWN>
-__device__ __forceinline__ bool batch_hit(kx4* xp, const uint4& ya, uint32_t max_dist, uint32_t k0, uint32_t ylim) {
-    u32x4 x[kXB];
-#pragma unroll
-    for (uint32_t j = 0; j < kXB; ++j) x[j] = xp[j];
-    uint32_t d[kXB];
-#pragma unroll
-    for (uint32_t j = 0; j < kXB; ++j) d[j] = popc4s(x[j], ya);
-    if (OWN) {
-        bool c = false;
-#pragma unroll
-        for (uint32_t j = 0; j < kXB; ++j) c |= d[j] <= max_dist && k0 + j < ylim;
-        return __any(c);
-    }
-    uint32_t m = d[0];
-#pragma unroll
-    for (uint32_t j = 1; j < kXB; ++j) m = min(m, d[j]);
-    return __any(m <= max_dist);
-}
-
 // Work item = (block b, key u), one wave each; item (b << 16 | u) belongs to rank item mod world. The y list of an item is
 // its own bucket (segment 0) followed by the buckets u ^ (1 << t) > u (r = 1): lanes take 64 consecutive entries of it per
-// round and hold their y -- the 128 bits that do NOT hold block b, which is all the index stores -- in registers; the next
-// round's y is loaded before the current round's x loop. The x side is the bucket itself, contiguous at a wave-uniform
-// address: kXB entries per scalar batch, xor'ed as scalar operands, one survivor test per batch. A candidate's key agrees and
-// its other bits are unrelated (~64 of 128 differ), so a batch with a lane within max_dist is rare: only then are its x
-// looked at one by one, and the lanes that pass fetch the other 128 bits of both hashes from the packed DB through rows.
-// Positions inside the own bucket are the first nu entries of the y list: only the rounds with p0 < nu pay for the i < j rule.
+// round and hold their y -- one word: the key of block b and, above it, the key of its sibling block -- in a register; the
+// next round's y is loaded before the current round's x loop. The x side is the bucket itself, contiguous at a wave-uniform
+// address: kXB words per scalar batch, xor'ed as scalar operands. Per candidate: xor, popcount onto a constant that carries
+// "more than tw = max_dist / 8 bits" into bit 31, and that bit shifted into the lane's mask. All kXB words are read whatever the bucket holds; the mask keeps only the x
+// that exist and, inside the own bucket, only those before the lane's y (x index k pairs with a y iff k < ylim). A
+// candidate's key is within r and its sibling key is unrelated (~8 of 16 bits differ), so about one in a hundred survives
+// (same bucket) or one in five hundred (neighbour): the survivors' {x position, y position} inside block b go into the wave's
+// queue in LDS, and whenever 64 are pending (and once at the end of the item) each lane takes one: both rows, both whole
+// hashes from the packed DB, the exact distance, the ownership rule, the group filter, the pair buffer.
+// Positions inside the own bucket are the first nu entries of the y list.
 __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint32_t* __restrict__ select) {
     __shared__ hvd_pair pbuf[4][kWavePairs];
+    __shared__ uint2 qbuf[4][kQueue];
     if (select[hvd::kSelIdxUsed] == 0u) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -436,41 +411,44 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
     for (int s = 0; s < 16; ++s) ends[s] = (uint32_t)__builtin_amdgcn_readlane((int)incl, s);
     const uint32_t ny = (uint32_t)__builtin_amdgcn_readlane((int)incl, 16);
     const size_t base = (size_t)b * a.n;
-    const uint4* __restrict__ hb = a.hc + base;
-    // (a batch reads kXB entries whatever the bucket holds: at most kXB - 1 entries past the block's last position, and behind
-    // the last block's hc lie the rows, 64 B per hash, in the same allocation)
-    kx4* xb = (kx4*)(a.hc + base + s0);
-    const uint32_t sa = b < 8u ? 1u : 0u;  // the 16-B half that does not hold block b: the one in hc
-    uint32_t fill = 0;                    // wave-uniform
+    const uint32_t* __restrict__ hb = a.hw + base;
+    const uint32_t* __restrict__ rowb = a.rows + base;
+    // (a batch reads kXB words whatever the bucket holds: at most kXB - 1 words past the block's last position, and behind
+    // the last block's hw lie the rows, 16 n >= 32 words, in the same allocation)
+    kxw* xb = (kxw*)(a.hw + base + s0);
+    const uint32_t kfail = 0x7FFFFFFFu - a.tw;  // popcount + kfail reaches bit 31 iff popcount > tw
+    uint32_t fill = 0;       // wave-uniform: pairs in the buffer
+    uint32_t qh = 0, qt = 0;  // wave-uniform: the queue holds entries qh .. qt - 1 (mod kQueue), fewer than 64 between pushes
     hvd_pair* buf = pbuf[wave];
+    uint2* queue = qbuf[wave];
 
-    // x entry k of the bucket against the wave's y, one by one: the batch had a lane within max_dist
-    auto examine = [&](uint32_t k, const uint4& ya, uint32_t ypos, uint32_t ylim) {
-        const u32x4 xv = xb[k];
-        const uint4 xa = make_uint4(xv.x, xv.y, xv.z, xv.w);
-        const uint32_t d0 = popc4(xa, ya);
-        const bool c = d0 <= a.max_dist && k < ylim;
-        if (!__any(c)) return;
+    // the first cnt (<= 64) queued survivors, one per lane: the full check
+    auto drain = [&](uint32_t cnt) {
+        __builtin_amdgcn_wave_barrier();  // (the pushes are in LDS before the entries are read)
         bool emit = false;
         uint32_t d = 0, i = 0, j = 0;
-        if (c) {
-            const uint32_t ri = a.rows[base + s0 + k], rj = a.rows[base + ypos];
-            const uint4 xo = a.db[(size_t)ri * 2u + (sa ^ 1u)], yo = a.db[(size_t)rj * 2u + (sa ^ 1u)];
-            d = d0 + popc4(xo, yo);
-            emit = d <= a.max_dist;
-            if (emit) {
-                const uint4 lo_x = sa ? xo : xa, hi_x = sa ? xa : xo, lo_y = sa ? yo : ya, hi_y = sa ? ya : yo;
-                const uint32_t dw[8] = {lo_x.x ^ lo_y.x, lo_x.y ^ lo_y.y, lo_x.z ^ lo_y.z, lo_x.w ^ lo_y.w,
-                                        hi_x.x ^ hi_y.x, hi_x.y ^ hi_y.y, hi_x.z ^ hi_y.z, hi_x.w ^ hi_y.w};
-                uint32_t within = 0;  // bit b2: the keys of block b2 are within r
+        if (lane < cnt) {
+            const uint2 e = queue[(qh + lane) & (kQueue - 1u)];
+            const uint32_t ri = rowb[e.x], rj = rowb[e.y];
+            uint32_t wx[8], wy[8], dw[8];
+            load_words(a.db, ri, wx);
+            load_words(a.db, rj, wy);
 #pragma unroll
-                for (uint32_t b2 = 0; b2 < kBlocks; ++b2) within |= (uint32_t)__popc(key_of(dw, b2)) <= a.r ? 1u << b2 : 0u;
-                if ((within & ((1u << b) - 1u)) != 0u) emit = false;  // an earlier block within r owns this pair
+            for (uint32_t k = 0; k < 8u; ++k) {
+                dw[k] = wx[k] ^ wy[k];
+                d += (uint32_t)__popc(dw[k]);
             }
+            emit = d <= a.max_dist;
+            uint32_t qual = 0;  // bit b2: block b2 qualifies -- its keys are within r and its word within tw
+#pragma unroll
+            for (uint32_t b2 = 0; b2 < kBlocks; ++b2)
+                qual |= (uint32_t)__popc(key_of(dw, b2)) <= a.r && (int32_t)((uint32_t)__popc(dw[b2 >> 1]) + kfail) >= 0 ? 1u << b2 : 0u;
+            if ((qual & ((1u << b) - 1u)) != 0u) emit = false;  // an earlier qualifying block owns this pair
             if (emit && a.group != nullptr && a.group[ri] == a.group[rj]) emit = false;
             i = min(ri, rj);
             j = max(ri, rj);
         }
+        qh += cnt;
         const unsigned long long em = __ballot(emit);
         const uint32_t m = (uint32_t)__popcll(em);
         if (m == 0u) return;
@@ -489,14 +467,24 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
         }
         fill += m;
     };
-    // the whole bucket against one round's y
-    auto walk = [&](auto own, const uint4& ya, uint32_t ypos, uint32_t ylim) {
-        constexpr bool kOwn = decltype(own)::value;
-        for (uint32_t k0 = 0; k0 < nu; k0 += kXB) {
-            const uint32_t nvalid = min(kXB, nu - k0);
-            const bool hit = batch_hit<kOwn>(xb + k0, ya, a.max_dist, k0, ylim);
-            if (__builtin_expect(hit, 0))
-                for (uint32_t j = 0; j < nvalid; ++j) examine(k0 + j, ya, ypos, ylim);
+    // one batch of kXB x words (x index k0 ..) against the wave's 64 y: bit kXB - 1 - j of the mask = x k0 + j survives
+    auto batch = [&](const u32x16& x, uint32_t k0, uint32_t yw, uint32_t ypos, uint32_t ylim) {
+        uint32_t fails = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < kXB; ++j) fails = word_step(fails, x[j], yw, kfail);
+        const uint32_t c = ylim > k0 ? min(kXB, ylim - k0) : 0u;  // the lane's y pairs with the first c x of the batch
+        uint32_t mask = ~fails & (0xFFFF0000u >> c) & 0xFFFFu;
+        // one survivor per lane and turn: at most 64 join the fewer than 64 pending, so the push always fits
+        while (__any(mask != 0u)) {
+            const bool has = mask != 0u;
+            const unsigned long long bal = __ballot(has);
+            if (has) {
+                const uint32_t slot = qt + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+                queue[slot & (kQueue - 1u)] = make_uint2(s0 + k0 + (kXB - 1u) - (uint32_t)__builtin_ctz(mask), ypos);
+                mask &= mask - 1u;
+            }
+            qt += (uint32_t)__popcll(bal);
+            if (qt - qh >= 64u) drain(64u);
         }
     };
     // entry p of the y list: its segment and its position inside block b
@@ -508,25 +496,28 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
         return (uint32_t)((int)p + __shfl(delta, (int)sg));
     };
     uint32_t seg, ypos = locate(lane, &seg);
-    uint4 ya = make_uint4(0u, 0u, 0u, 0u);
-    if (lane < ny) ya = hb[ypos];
-    for (uint32_t p0 = 0; p0 < ny; p0 += 64u) {
+    uint32_t yw = 0u;
+    if (lane < ny) yw = hb[ypos];
+    uint32_t p0 = 0;
+    do {  // (ny >= nu > 0: at least one round)
         const uint32_t p = p0 + lane;
         uint32_t seg_n;
         const uint32_t ypos_n = locate(p + 64u, &seg_n);
-        asm volatile("" ::"v"(ya.x), "v"(ya.y), "v"(ya.z), "v"(ya.w));  // (this round's y has arrived before the next one's load is issued)
-        uint4 ya_n = make_uint4(0u, 0u, 0u, 0u);
-        if (p + 64u < ny) ya_n = hb[ypos_n];  // the next round's y: in flight under this round's x loop
+        asm volatile("" ::"v"(yw));  // (this round's y has arrived before the next one's load is issued)
+        uint32_t yw_n = 0u;
+        if (p + 64u < ny) yw_n = hb[ypos_n];  // the next round's y: in flight under this round's x loop
         // x index k pairs with this y iff k < ylim: inside the bucket only the x before it (positions i < j)
         const uint32_t ylim = p >= ny ? 0u : seg == 0u ? p : nu;
-        if (p0 < nu)
-            walk(std::true_type(), ya, ypos, ylim);
-        else
-            walk(std::false_type(), ya, ypos, ylim);
+        for (uint32_t k0 = 0; k0 < nu; k0 += kXB) {
+            const u32x16 x = *(kx16*)(xb + k0);
+            batch(x, k0, yw, ypos, ylim);
+        }
         seg = seg_n;
         ypos = ypos_n;
-        ya = ya_n;
-    }
+        yw = yw_n;
+        p0 += 64u;
+    } while (p0 < ny);
+    if (qt != qh) drain(qt - qh);
     if (fill != 0u) flush_wave(a, buf, fill, lane);
 }
 
@@ -537,9 +528,10 @@ namespace hvd {
 int g_allpairs_index = -1;
 int g_allpairs_index_fail = 0;
 
-// per-context scratch: per-key counts [16][65536], offsets [16][65537], half-hash copies [16][n] x 16 B, rows [16][n]; for the
-// build: partition records [16][n] x 8 B, tile counts [4096][tiles], and per partition / chunk: sizes, bases, first chunks,
-// the chunk list and the chunks' low-byte counts (cursors)
+// per-context scratch: per-key counts [16][65536], offsets [16][65537], words [16][n] x 4 B, rows [16][n] x 4 B -- in this
+// order: the join's scalar batch reads up to 15 words past a bucket's end, which behind the last block's words are rows --;
+// for the build: partition records [16][n] x 8 B, tile counts [4096][tiles], and per partition / chunk: sizes, bases, first
+// chunks, the chunk list and the chunks' low-byte counts (cursors). 16 B per hash and block: 0.27 GB at 1 M, 2.6 GB at 10 M
 struct IndexScratch {
     void* p = nullptr;
     size_t cap = 0;
@@ -555,13 +547,13 @@ static uint32_t index_chunk(uint32_t n) { return max(kMinChunk, 2u * ((n + 255u)
 static size_t tcnt_words(uint32_t n) { return ((size_t)kParts * index_tiles(n) + 3u) & ~(size_t)3u; }
 constexpr size_t kPartWords = 3u * kParts + 4u + kMaxChunks;  // ptotal, pbase, pfirst (+ 1, padded), chunk_p
 static size_t index_bytes(uint32_t n) {
-    return 4u * (size_t)kBlocks * kKeys + 4u * off_words() + (size_t)kBlocks * n * 16u + (size_t)kBlocks * n * 4u +
+    return 4u * (size_t)kBlocks * kKeys + 4u * off_words() + (size_t)kBlocks * n * 4u + (size_t)kBlocks * n * 4u +
            (size_t)kBlocks * n * 8u + 4u * tcnt_words(n) + 4u * kPartWords + 4u * (size_t)kMaxChunks * 256u;
 }
 struct IndexPtrs {
     uint32_t* cnt;
     uint32_t* off;
-    uint4* hc;
+    uint32_t* hw;
     uint32_t* rows;
     uint2* rec;
     uint32_t *tcnt, *ptotal, *pbase, *pfirst, *chunk_p, *ccount;
@@ -571,9 +563,9 @@ static IndexPtrs index_ptrs(int ctx_id, uint32_t n) {
     IndexPtrs q;
     q.cnt = (uint32_t*)p;
     q.off = (uint32_t*)(p + 4u * (size_t)kBlocks * kKeys);
-    q.hc = (uint4*)(p + 4u * (size_t)kBlocks * kKeys + 4u * off_words());
-    q.rows = (uint32_t*)((char*)q.hc + (size_t)kBlocks * n * 16u);
-    q.rec = (uint2*)(q.rows + (size_t)kBlocks * n);  // (16 n words behind a 16-byte boundary: aligned)
+    q.hw = (uint32_t*)(p + 4u * (size_t)kBlocks * kKeys + 4u * off_words());
+    q.rows = q.hw + (size_t)kBlocks * n;
+    q.rec = (uint2*)(q.rows + (size_t)kBlocks * n);  // (32 n words behind a 16-byte boundary: aligned)
     q.tcnt = (uint32_t*)(q.rec + (size_t)kBlocks * n);
     q.ptotal = q.tcnt + tcnt_words(n);
     q.pbase = q.ptotal + kParts;
@@ -602,8 +594,9 @@ IndexRule index_rule(const AllPairsArgs& a, uint32_t r) {
     // for 2.075e9 candidates; the counting sort, the statistics and the place pass 0.93 ms, of which ~0.03 ms do not depend
     // on n (the scans over 4096 partitions, the grid of 6144 chunks): 0.9 ns per hash, and those 30 us next to the 40 us of
     // launches; the longest work item's wave takes ~30 ns per step of 64 pairs. These are the figures of the full-width
-    // index with the LDS-staged join: the half-width index and the scalar-x join have not been profiled yet, so ps_cand and
-    // ps_hash are the old, costlier ones -- the rule can only be too cautious about the index until they are re-derived)
+    // index with the LDS-staged join: the word index (place without a gather) and the word join have not been profiled yet,
+    // so ps_cand and ps_hash are the old, costlier ones -- the rule can only be too cautious about the index until they are
+    // re-derived: ps_cand = join time / candidates, ps_hash = (every kernel between probe and join - 30 us) / n)
     q.fs_mfma_fetch = 36.0f;
     q.fs_mfma_other = 40.0f;
     q.ps_cand = 1.0f;
@@ -657,11 +650,11 @@ hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const 
 
 hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t r, hipStream_t s) {
     const IndexPtrs p = index_ptrs(a.ctx_id, a.n);
-    hipLaunchKernelGGL(k_index_place, dim3(kMaxChunks), dim3(256), 0, s, (const uint4*)a.d_db, p.rec, a.n, index_chunk(a.n), p.ptotal,
-                       p.pbase, p.pfirst, p.chunk_p, p.ccount, p.hc, p.rows, d_select);
+    hipLaunchKernelGGL(k_index_place, dim3(kMaxChunks), dim3(256), 0, s, p.rec, a.n, index_chunk(a.n), p.ptotal, p.pbase, p.pfirst,
+                       p.chunk_p, p.ccount, p.hw, p.rows, d_select);
     JoinArgs j;
     j.off = p.off;
-    j.hc = p.hc;
+    j.hw = p.hw;
     j.rows = p.rows;
     j.db = (const uint4*)a.d_db;
     j.n = a.n;
@@ -671,6 +664,7 @@ hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t
     j.count = a.d_count;
     j.max_dist = a.max_dist;
     j.r = r;
+    j.tw = a.max_dist / 8u;  // a pair within max_dist has a word within tw bits, and one of its two blocks within tw / 2 = r
     j.rank = a.rank;
     j.world = a.world;
     const uint32_t items = (kBlocks * kKeys + a.world - 1u - a.rank) / a.world;  // this rank's items: rank, rank + world, ...
