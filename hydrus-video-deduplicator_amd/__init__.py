@@ -9,7 +9,8 @@ from . import (_lib, hashing, multigpu, pipeline, rendezvous, search, sqlite_ada
                vpdqpy, vptree)
 from .hashing import compute_phash, decode_phash_from_str, encode_phash_to_str, get_phash_similarity  # noqa: F401
 from .search import (allpairs_hamming, calculate_distance, find_excerpts, find_potential_duplicates,  # noqa: F401
-                     find_segmented_excerpts, find_transformed_duplicates, fix_vpdq_similarity, match_videos)
+                     find_rate_excerpts, find_segmented_excerpts, find_transformed_duplicates, fix_vpdq_similarity,
+                     match_videos)
 from .vpdq import VideoHasher, VpdqHash, matchHash, matchHashBytes  # noqa: F401
 from .pipeline import (DeviceLibrary, dedupe_frames_on_device, dedupe_transformed_frames_on_device, dedupe_videos,  # noqa: F401
                        hash_videos)

@@ -151,6 +151,46 @@ hipError_t launch_valign_segments(const void* d_hashes_q, const long long* d_off
                                   uint32_t max_segments, uint32_t min_band_votes, void* d_scratch, size_t scratch_bytes,
                                   hvd_vsegments* d_out, hipStream_t s);
 
+// Rate-aware time alignment (k_valign_rates.hip): launch_valign's operands and two launches, one offset per pair at
+// the best of the listed rates. The list travels as two kernel arguments: entry r = (num, den) in bits 4r .. 4r + 3 of nums and
+// of dens, and it ends at the first entry whose two nibbles are 0. rate_list_length: its length R, or 0 for a broken list (a
+// value outside 1..8, a pair with a common factor, a rate listed twice, something behind the end, no entry) -- the one definition
+// of a sound list, for the host entries and for the kernel (which then gives every pair the INT32_MIN record).
+constexpr uint32_t rate_list_length(uint32_t nums, uint32_t dens) {
+    uint32_t R = 0;
+    while (R < (uint32_t)HVD_ALIGN_MAX_RATES && (((nums | dens) >> (4u * R)) & 15u)) ++R;
+    if (R < (uint32_t)HVD_ALIGN_MAX_RATES && ((nums | dens) >> (4u * R))) return 0u;
+    for (uint32_t r = 0; r < R; ++r) {
+        const uint32_t num = (nums >> (4u * r)) & 15u, den = (dens >> (4u * r)) & 15u;
+        if (num - 1u >= 8u || den - 1u >= 8u) return 0u;
+        for (uint32_t f = 2; f <= 7u; ++f)
+            if (num % f == 0u && den % f == 0u) return 0u;
+        for (uint32_t q = 0; q < r; ++q)
+            if (((nums >> (4u * q)) & 15u) == num && ((dens >> (4u * q)) & 15u) == den) return 0u;
+    }
+    return R;
+}
+// (num, den) x n_rates as the caller lists them -> the two words; false (and 0, 0: a broken list) unless the list is sound
+inline bool pack_rate_list(const int32_t* rates, int n_rates, uint32_t* nums, uint32_t* dens) {
+    *nums = *dens = 0u;
+    if (!rates || n_rates < 1 || n_rates > HVD_ALIGN_MAX_RATES) return false;
+    uint32_t nn = 0, dd = 0;
+    for (int r = 0; r < n_rates; ++r) {
+        if (rates[2 * r] < 1 || rates[2 * r] > 8 || rates[2 * r + 1] < 1 || rates[2 * r + 1] > 8) return false;
+        nn |= (uint32_t)rates[2 * r] << (4 * r);
+        dd |= (uint32_t)rates[2 * r + 1] << (4 * r);
+    }
+    if (rate_list_length(nn, dd) != (uint32_t)n_rates) return false;
+    *nums = nn;
+    *dens = dd;
+    return true;
+}
+size_t rates_scratch_bytes(unsigned long long max_bins);  // max_bins: the largest bins_r of any pair and listed rate
+hipError_t launch_valign_rates(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
+                               const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
+                               const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, uint32_t nums,
+                               uint32_t dens, void* d_scratch, size_t scratch_bytes, hvd_vrate* d_out, hipStream_t s);
+
 // Synthetic 64x64 gray video frames generated in HBM (k_synth.hip; workload generator, not on the hashing path).
 hipError_t launch_synth_frames64(uint8_t* d_out, long long v0, uint32_t frames_per_video, unsigned long long n_frames,
                                  uint64_t seed, const int32_t* d_copy_of, hipStream_t s);

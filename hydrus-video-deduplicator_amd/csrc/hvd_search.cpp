@@ -1013,6 +1013,8 @@ int hvd_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) {
     return scratch_bytes_entry(max_bins, out_bytes, hvd::segments_scratch_bytes);
 }
 
+int hvd_rates_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(max_bins, out_bytes, hvd::rates_scratch_bytes); }
+
 static int check_tolerances(int max_dist, int slack) {
     if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
     if (slack < 0 || slack > 16) return fail(HVD_ERR_ARG, "slack=%d out of range [0,16]", slack);
@@ -1076,6 +1078,26 @@ int hvd_dev_vpdq_align_segments(const void* d_hashes_q, const void* d_offsets_q,
     return HVD_OK;
 }
 
+int hvd_dev_vpdq_align_rates(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                             const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                             const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                             void* d_scratch, size_t scratch_bytes, void* d_out) {
+    if (int rc = check_align_counts(VQ, VT, M, max_dist, slack)) return rc;
+    if (!rates || n_rates < 0) return fail(HVD_ERR_ARG, "rates is NULL or n_rates=%d < 0", n_rates);
+    if (M == 0) return HVD_OK;
+    if (int rc = check_align_pointers(d_offsets_q, d_offsets_t, d_pairs, d_out,
+                                      (uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch | (uintptr_t)d_out,
+                                      "hashes, scratch and records"))
+        return rc;
+    uint32_t nums = 0, dens = 0;
+    hvd::pack_rate_list(rates, n_rates, &nums, &dens);  // a broken list travels as (0, 0): the kernel's INT32_MIN records
+    HIP_TRY(hvd::launch_valign_rates(d_hashes_q, (const long long*)d_offsets_q, (uint32_t)VQ, (const int32_t*)d_pos_q, d_hashes_t,
+                                     (const long long*)d_offsets_t, (uint32_t)VT, (const int32_t*)d_pos_t, (const uint32_t*)d_pairs,
+                                     (unsigned long long)M, (uint32_t)max_dist, (uint32_t)slack, nums, dens, d_scratch,
+                                     scratch_bytes, (hvd_vrate*)d_out, g.stream));
+    return HVD_OK;
+}
+
 // positions of one library: non-negative, strictly increasing inside a video, below 2^20
 static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V, const char* side) {
     if (!pos) return HVD_OK;
@@ -1087,13 +1109,16 @@ static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V
     return HVD_OK;
 }
 
-// The host-buffer form of both alignments: validate, stage, run, copy the records back. max_segments 0: hvd_valign records
+// The host-buffer form of the alignments: validate, stage, run, copy the records back. rates given: hvd_vrate records
+// (hvd_dev_vpdq_align_rates), the list sound (the caller has checked it), and the arguments are judged before the library's
+// state is, so that a bad call is HVD_ERR_ARG with or without a device; else max_segments 0: hvd_valign records
 // (hvd_dev_vpdq_align_videos); else hvd_vsegments records (hvd_dev_vpdq_align_segments).
 static int align_from_host(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
                            const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                            const uint32_t* pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
-                           void* out) {
-    if (int rc = need_ready()) return rc;
+                           void* out, const int32_t* rates = nullptr, int n_rates = 0) {
+    if (!rates)
+        if (int rc = need_ready()) return rc;
     if (M < 0 || (M > 0 && (!pairs || !out))) return fail(HVD_ERR_ARG, "bad pair list / output buffer");
     if (int rc = check_tolerances(max_dist, slack)) return rc;
     int64_t nq = 0, nt = 0;
@@ -1113,12 +1138,17 @@ static int align_from_host(const uint8_t* frames_q, const int64_t* offsets_q, in
             return fail(HVD_ERR_ARG, "pair %lld = (%u, %u) is outside the %lld x %lld videos", (long long)p, a, b, (long long)VQ, (long long)VT);
         const int64_t sa = span(positions_q, offsets_q, a), sb = span(positions_t, offsets_t, b);
         if (sa < 0 || sb < 0) continue;  // an empty video: the zero record
-        const int64_t bins = sa + sb + 1 + 2 * (int64_t)slack;
+        int64_t bins = sa + sb + 1 + 2 * (int64_t)slack;
+        for (int r = 0; r < n_rates; ++r)  // the largest bins_r of the list
+            bins = std::max(bins, rates[2 * r] * sa + rates[2 * r + 1] * sb + 1 +
+                                      2 * (int64_t)slack * std::max(rates[2 * r], rates[2 * r + 1]));
         if (bins > (1ll << 20))
             return fail(HVD_ERR_ARG, "pair %lld = (%u, %u) spans %lld offsets with slack %d: more than the 2^20 histogram bins",
                         (long long)p, a, b, (long long)bins, slack);
         max_bins = std::max(max_bins, bins);
     }
+    if (rates)
+        if (int rc = need_ready()) return rc;
     if (M == 0) return HVD_OK;
     std::lock_guard<std::recursive_mutex> lk(g.h_mu);
     const bool self = frames_t == frames_q && offsets_t == offsets_q && positions_t == positions_q && VT == VQ;
@@ -1146,13 +1176,16 @@ static int align_from_host(const uint8_t* frames_q, const int64_t* offsets_q, in
         return rc;
     }
     SCR(S_APAIRS, 8 * (size_t)M, d_pairs);
-    const size_t out_bytes = (max_segments ? sizeof(hvd_vsegments) : sizeof(hvd_valign)) * (size_t)M;
+    const size_t out_bytes = (rates ? sizeof(hvd_vrate) : max_segments ? sizeof(hvd_vsegments) : sizeof(hvd_valign)) * (size_t)M;
     SCR(S_AOUT, out_bytes, d_out);
-    const size_t sb = max_segments ? hvd::segments_scratch_bytes((unsigned long long)max_bins)
-                                   : hvd::align_scratch_bytes((unsigned long long)max_bins);
+    const size_t sb = rates          ? hvd::rates_scratch_bytes((unsigned long long)max_bins)
+                      : max_segments ? hvd::segments_scratch_bytes((unsigned long long)max_bins)
+                                     : hvd::align_scratch_bytes((unsigned long long)max_bins);
     if (sb) SCR(S_ASCR, sb, d_scr);
     HIP_TRY(hipMemcpyAsync(d_pairs, pairs, 8 * (size_t)M, hipMemcpyHostToDevice, g.stream));
-    if (int rc = max_segments ? hvd_dev_vpdq_align_segments(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack,
+    if (int rc = rates        ? hvd_dev_vpdq_align_rates(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack, rates,
+                                                         n_rates, d_scr, sb, d_out)
+                 : max_segments ? hvd_dev_vpdq_align_segments(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack,
                                                             max_segments, min_band_votes, d_scr, sb, d_out)
                               : hvd_dev_vpdq_align_videos(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack,
                                                           d_scr, sb, d_out))
@@ -1176,6 +1209,18 @@ int hvd_vpdq_align_segments(const uint8_t* frames_q, const int64_t* offsets_q, i
     if (int rc = check_segment_limits(max_segments, min_band_votes)) return rc;
     return align_from_host(frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack,
                            max_segments, min_band_votes, out);
+}
+
+int hvd_vpdq_align_rates(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                         const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                         const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                         hvd_vrate* out) {
+    uint32_t nums = 0, dens = 0;
+    if (!hvd::pack_rate_list(rates, n_rates, &nums, &dens))
+        return fail(HVD_ERR_ARG, "rates: need 1..%d pairs (num, den) with 1 <= num, den <= 8, no common factor, none listed twice",
+                    HVD_ALIGN_MAX_RATES);
+    return align_from_host(frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, 0,
+                           1, out, rates, n_rates);
 }
 
 #ifndef HVD_NO_BENCH_SYMBOLS

@@ -1,6 +1,7 @@
-// hvd_valign_dev.h -- what the two time-alignment kernels share, one definition of each piece: k_valign.hip (one offset per pair,
-// DESIGN.md 4.8) and k_valign_segments.hip (up to eight) include it and add their records and their loops. Device
-// code first; the last section is host code: the slot count, the scratch sizing and the helper that enqueues the two launches.
+// hvd_valign_dev.h -- what the time-alignment kernels share, one definition of each piece: k_valign.hip (one offset per pair,
+// DESIGN.md 4.8), k_valign_segments.hip (up to eight) and k_valign_rates.hip (one offset at the best of up to eight
+// listed rates) include it and add their records and their loops. Device code first; the last section is host
+// code: the slot count, the scratch sizing and the helper that enqueues the two launches.
 //
 // The rule, integers only (include/hvd_mi355x.h has the full text):
 //   H = {(i, j) : hamming(A_i, B_j) <= max_dist},  delta(i, j) = p_b(j) - p_a(i),  votes[d] = |{(i, j) in H : delta = d}|,
@@ -15,6 +16,8 @@
 // k_valign_segments the taken words. Histogram and bit words live in LDS up to HVD_ALIGN_LDS_BINS bins (the <false> kernels);
 // pairs with more bins are left to a second launch (the <true> kernels) whose workgroups own one slot each of the caller's
 // scratch -- up to 2^20 bins.
+// RATE (k_valign_rates; defaulted template parameters and trailing arguments, so the other two kernels compile to the code they
+// had): the lines are p_b = (num / den) p_a + c, delta = den p_b - num p_a, and slack is the caller's slack_r = slack max(num, den).
 // The promise: every bin index, frame range and slot size is checked against its bound before it is used. A broken CSR, pair
 // list or position array gives wrong or INT32_MIN records, never an access out of bounds.
 // Every device function is __forceinline__: a kernel that calls them compiles to the code it had with the statements written out.
@@ -68,9 +71,20 @@ struct Geometry {
     __device__ __forceinline__ bool big() const { return !bad && !empty && bins > (long long)kLdsBins; }  // the scratch launch's
 };
 
+// what every rate's geometry is made of: bins_r = num span_a + den span_b + 1 + 2 slack_r, dmin_r = den p_b0 - num p_a1
+struct Spans {
+    uint32_t a, b;  // p_a1 - p_a0, p_b1 - p_b0
+    int32_t pa1, pb0;
+};
+
 // The same on every lane. Frame ranges are clamped to [0, offsets[V]]; A and B stay empty unless the pair is neither bad nor empty.
-__device__ __forceinline__ Geometry pair_geometry(const Libraries& L, uint2 ab, uint32_t slack) {
+// RATE: entry r of the list is (nums >> 4r & 15, dens >> 4r & 15), n_rates of them (0: a broken list, every pair is bad);
+// bins is then the largest bins_r of the list, dmin is not set, and *spans is (for a pair neither bad nor empty).
+template <bool RATE = false>
+__device__ __forceinline__ Geometry pair_geometry(const Libraries& L, uint2 ab, uint32_t slack, uint32_t nums = 0u,
+                                                  uint32_t dens = 0u, uint32_t n_rates = 0u, Spans* spans = nullptr) {
     Geometry g = {{nullptr, nullptr, 0}, {nullptr, nullptr, 0}, 0, 0, ab.x >= L.VQ || ab.y >= L.VT, false};
+    if (RATE && n_rates == 0u) g.bad = true;
     if (g.bad) return g;
     const long long* const oq = L.offsets_q;
     const long long* const ot = L.offsets_t;
@@ -85,6 +99,17 @@ __device__ __forceinline__ Geometry pair_geometry(const Libraries& L, uint2 ab, 
     const long long pa0 = pos_of(g.A, 0), pa1 = pos_of(g.A, g.A.n - 1u), pb0 = pos_of(g.B, 0), pb1 = pos_of(g.B, g.B.n - 1u);
     // strictly increasing positions make a video's span at least its length - 1; the bit words rely on it
     g.bad = pa0 < 0 || pb0 < 0 || pa1 - pa0 + 1 < (long long)g.A.n || pb1 - pb0 + 1 < (long long)g.B.n;
+    if constexpr (RATE) {
+        if (g.bad) return g;  // (the spans below may be anything)
+#pragma unroll 1
+        for (uint32_t r = 0; r < n_rates; ++r) {
+            const long long num = (nums >> (4u * r)) & 15u, den = (dens >> (4u * r)) & 15u;
+            g.bins = max(g.bins, num * (pa1 - pa0) + den * (pb1 - pb0) + 1 + 2 * (long long)slack * max(num, den));
+        }
+        g.bad = g.bins > (long long)kMaxBins;
+        *spans = {(uint32_t)(pa1 - pa0), (uint32_t)(pb1 - pb0), (int32_t)pa1, (int32_t)pb0};
+        return g;
+    }
     g.bins = (pa1 - pa0) + (pb1 - pb0) + 1 + 2 * (long long)slack;
     g.bad = g.bad || g.bins > (long long)kMaxBins;
     g.dmin = (int32_t)(pb0 - pa1);
@@ -126,11 +151,14 @@ __device__ __forceinline__ void count_bits(const uint32_t* flags, uint32_t n_bit
 // Video a is staged, chunk by chunk; a lane keeps one frame of video b. flagA / flagB / takenA / takenB: where the runs of bit
 // words start behind hist. TAKEN (k_valign_segments): the pass skips the frames in the taken sets -- a taken frame of b skips its
 // lane's row; the taken bit of a frame of a is read AFTER the distance test: hits are rare, and a comparison that misses pays
-// nothing for the sets. Without TAKEN there are no taken words, and hit_bits is true.
-template <int PASS, bool TAKEN>
+// nothing for the sets. Without TAKEN there are no taken words, and hit_bits is true unless RATE. RATE: delta = den p_b - num p_a
+// (the staged positions are num p_a, a lane's is den p_b; 32-bit wrap-around, which the bin check is indifferent to), and dmin,
+// core, slack and dstar are the rate's, in its scaled units.
+template <int PASS, bool TAKEN, bool RATE = false>
 __device__ __forceinline__ void scan_pair(const Side& A, const Side& B, uint32_t max_dist, uint32_t* stage, int32_t* spos,
                                           uint32_t* hist, uint32_t flagA, uint32_t flagB, uint32_t takenA, uint32_t takenB,
-                                          int32_t dmin, uint32_t core, uint32_t slack, int32_t dstar, bool hit_bits) {
+                                          int32_t dmin, uint32_t core, uint32_t slack, int32_t dstar, bool hit_bits,
+                                          uint32_t num = 1u, uint32_t den = 1u) {
     const uint32_t tid = threadIdx.x;
     const uint32_t nsplit = B.n >= 256u ? 1u : 256u / B.n;
     const uint32_t j_small = tid % B.n, part_small = tid / B.n;
@@ -143,7 +171,7 @@ __device__ __forceinline__ void scan_pair(const Side& A, const Side& B, uint32_t
             uint32_t* d = stage + (k >> 1) * 9u + (k & 1u) * 4u;
             d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
         }
-        for (uint32_t k = tid; k < ci; k += 256u) spos[k] = pos_of(A, i0 + k);
+        for (uint32_t k = tid; k < ci; k += 256u) spos[k] = RATE ? (int32_t)(num * (uint32_t)pos_of(A, i0 + k)) : pos_of(A, i0 + k);
         __syncthreads();
 #pragma unroll 1
         for (uint32_t base = 0; base < B.n; base += 256u) {
@@ -152,7 +180,7 @@ __device__ __forceinline__ void scan_pair(const Side& A, const Side& B, uint32_t
             if (j >= B.n || part >= nsplit) continue;
             if (TAKEN && ((hist[takenB + (j >> 5)] >> (j & 31u)) & 1u)) continue;  // a segment before owns this frame of b
             const uint4 q0 = B.hashes[(size_t)j * 2u], q1 = B.hashes[(size_t)j * 2u + 1u];
-            const int32_t pb = pos_of(B, j);
+            const int32_t pb = RATE ? (int32_t)(den * (uint32_t)pos_of(B, j)) : pos_of(B, j);
             bool any = false;
 #pragma unroll 1
             for (uint32_t i = part; i < ci; i += nsplit) {
@@ -166,7 +194,7 @@ __device__ __forceinline__ void scan_pair(const Side& A, const Side& B, uint32_t
                 if (PASS == 1) {
                     const uint32_t bin = (uint32_t)(delta - dmin);
                     if (bin < core) atomicAdd(&hist[bin + slack], 1u);  // (only broken positions fail the check)
-                    if (TAKEN && !hit_bits) continue;
+                    if ((TAKEN || RATE) && !hit_bits) continue;
                 } else if (iabs(delta - dstar) > slack) {
                     continue;
                 }

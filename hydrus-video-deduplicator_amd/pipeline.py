@@ -24,7 +24,7 @@ import time
 import numpy as np
 
 from . import _lib, search, vpdq
-from ._lib import VALIGN_DTYPE, VMATCH_DTYPE, VSEGMENTS_DTYPE, DeviceBuffer
+from ._lib import VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VSEGMENTS_DTYPE, DeviceBuffer
 
 
 def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
@@ -333,9 +333,22 @@ class DeviceLibrary:
         return self._align(records, slack, max_dist, VSEGMENTS_DTYPE, lib.hvd_segments_scratch_bytes,
                            lib.hvd_dev_vpdq_align_segments, (int(max_segments), int(min_band_votes)))
 
-    def _align(self, records, slack, max_dist, dtype, scratch_bytes, entry, extra: tuple) -> np.ndarray:
+    def align_rates(self, records, rates=search.DEFAULT_RATES, slack: int = search.ALIGN_SLACK,
+                    max_dist: int | None = None) -> np.ndarray:
+        """hvd_dev_vpdq_align_rates of the listed pairs of this library against itself: one VRATE_DTYPE record per pair, in
+        their order (search.align_rates on what is in HBM; operands and positions as `align`). A broken rate list gives
+        INT32_MIN records, as the device entry does."""
+        lib = _lib.ensure()
+        rates = search.rate_array(rates)
+        # a pair's histogram is sized by its largest bins_r = num span_a + den span_b + 1 + 2 slack max(num, den)
+        widest = [lambda span, r=r: (int(r[0]) + int(r[1])) * span + 1 + 2 * int(slack) * int(max(r)) for r in rates]
+        return self._align(records, slack, max_dist, VRATE_DTYPE, lib.hvd_rates_scratch_bytes, lib.hvd_dev_vpdq_align_rates,
+                           (rates.ctypes.data, rates.shape[0]), widest)
+
+    def _align(self, records, slack, max_dist, dtype, scratch_bytes, entry, extra: tuple, widest=()) -> np.ndarray:
         """One device-resident alignment call over this library against itself: `entry` with the operands both alignments
-        share, `extra` between slack and the scratch, records of `dtype` back."""
+        share, `extra` between slack and the scratch, records of `dtype` back. widest: functions span -> bins, for an entry
+        whose histogram may be wider than span_a + span_b + 1 + 2 slack."""
         lib = _lib.ensure()
         pairs = search.pair_array(records)
         M = pairs.shape[0]
@@ -350,7 +363,8 @@ class DeviceLibrary:
             limit = int(lengths.max()) if lengths.size else 0
         else:
             limit = self._position_limit
-        max_bins = min(2 * max(limit, 1) - 1 + 2 * int(slack), _lib.ALIGN_MAX_BINS)
+        max_bins = 2 * max(limit, 1) - 1 + 2 * int(slack)
+        max_bins = min(max([max_bins] + [bins(max(limit, 1) - 1) for bins in widest]), _lib.ALIGN_MAX_BINS)
         sb = C.c_size_t(0)
         _lib.check(scratch_bytes(max_bins, C.byref(sb)))
         with _DeviceScope() as scope:
@@ -611,6 +625,18 @@ def find_segmented_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray
         d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library,
         lambda library, recs: library.align_segments(recs, slack=slack, max_segments=max_segments, min_band_votes=int(min_aligned)),
         lambda aligned, lengths, sim: search.segmented_excerpts_from_records(aligned, lengths, sim, threshold, min_aligned))
+
+
+def find_rate_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                 threshold: float = 50.0, min_aligned: int = 4, slack: int = search.ALIGN_SLACK,
+                                 rates=search.DEFAULT_RATES, positions: bool = True, keep_library: bool = False):
+    """search.find_rate_excerpts on frames in HBM, one device: the chain of `find_excerpts_on_device` with the rate-aware
+    alignment (`DeviceLibrary.align_rates`) and the keep rule of search.rate_excerpts_from_records; nothing but records
+    crosses PCIe. -> (rate excerpts, search records, VRATE records, library or None); positions are raw frame indices."""
+    return _aligned_search_on_device(
+        d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library,
+        lambda library, recs: library.align_rates(recs, rates=rates, slack=slack),
+        lambda aligned, lengths, sim: search.rate_excerpts_from_records(aligned, lengths, sim, threshold, min_aligned))
 
 
 def _rank0_of_every_context(entry, frames_of_rank, timings, n_results: int, *args, **kwargs):

@@ -12,11 +12,12 @@ db/vptree.py:431-441); this module computes it exactly.
 from __future__ import annotations
 
 from collections import namedtuple
+from fractions import Fraction
 
 import numpy as np
 
 from . import _lib, vpdq
-from ._lib import ALIGN_MAX_SEGMENTS, PAIR_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VSEGMENTS_DTYPE
+from ._lib import ALIGN_MAX_RATES, ALIGN_MAX_SEGMENTS, PAIR_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VSEGMENTS_DTYPE
 
 DISTANCE_TOLERANCE = 31  # per-frame Hamming tolerance (vpdqpy/vpdqpy.py:53, db/vptree.py:31)
 DEFAULT_VARIANT = 13  # all-pairs kernel the product uses (FP4-MFMA, 128-bit first stage, form chosen by a probe); DESIGN.md 4.1
@@ -512,3 +513,107 @@ def find_segmented_excerpts(video_hashes, threshold: float = 50.0, min_aligned: 
     never increases from one segment to the next -- a segment below the floor cannot count, nor can any after it. The same
     frames in shuffled order stay unreported: no offset collects min_aligned of them."""
     return segmented_excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, positions, max_segments)
+
+
+# ------------------------------------------------ sped-up and slowed-down excerpts: rate-aware alignment (DESIGN 4.10) ---
+
+# (num, den): p_b = (num / den) p_a + c. The common re-upload speeds and their inverses (either video of a pair may be the
+# faster one), 1x first so that it wins a tie. HVD_ALIGN_MAX_RATES is 8: (1, 2), the inverse of (2, 1), is left to callers who
+# list it in place of another.
+DEFAULT_RATES = ((1, 1), (5, 4), (4, 5), (4, 3), (3, 4), (3, 2), (2, 3), (2, 1))
+assert len(DEFAULT_RATES) <= ALIGN_MAX_RATES
+
+
+def rate_array(rates) -> np.ndarray:
+    """A rate list -> int32[R, 2] of (num, den), as the alignment entries take it (the entry judges it)."""
+    rates = np.asarray([tuple(r) for r in rates], dtype=np.int64).reshape(-1, 2)
+    if rates.size and (rates.min() < -(1 << 31) or rates.max() >= 1 << 31):
+        raise ValueError("rate out of range")
+    return np.ascontiguousarray(rates, dtype=np.int32)
+
+
+def align_rates(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.ndarray | None = None, rates=DEFAULT_RATES,
+                slack: int = ALIGN_SLACK, max_dist: int | None = None, frames_t: np.ndarray | None = None,
+                offsets_t: np.ndarray | None = None, positions_t: np.ndarray | None = None) -> np.ndarray:
+    """Rate-aware time alignment of the listed video pairs (hvd_vpdq_align_rates): one VRATE_DTYPE record per pair, in the order
+    of `pairs`. The operands are align_videos'. rates: 1..8 pairs (num, den), 1 <= num, den <= 8 in lowest terms, none twice;
+    (num, den) models p_b = (num / den) p_a + c. Every listed rate gets align_videos' vote on den p_b - num p_a with the slack
+    widened to slack * max(num, den); the rate whose best band holds the most frame hits wins (the earlier one on a tie). A
+    record holds the words of a VALIGN_DTYPE record at that rate -- offset in its scaled units, c = offset / rate_den -- then
+    rate_num, rate_den and rate_index. With rates = ((1, 1),) these ARE align_videos' records. The default list has 1x, the
+    common speeds and their inverses except (1, 2): the limit is eight, list it in place of another if b may be the half-speed
+    one."""
+    frames, offsets, positions, frames_t, offsets_t, positions_t, pairs, max_dist = _align_operands(
+        frames, offsets, pairs, positions, max_dist, frames_t, offsets_t, positions_t)
+    rates = rate_array(rates)
+    M = pairs.shape[0]
+    out = np.zeros(M, dtype=VRATE_DTYPE)
+    out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
+    lib = _lib.ensure()
+    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
+        max_dist, M = 0, 0  # (the entry still judges the list and the libraries)
+    _lib.check(lib.hvd_vpdq_align_rates(_ptr(frames), offsets.ctypes.data, offsets.size - 1, _ptr(positions), _ptr(frames_t),
+                                        offsets_t.ctypes.data, offsets_t.size - 1, _ptr(positions_t), _ptr(pairs), M,
+                                        max_dist, int(slack), rates.ctypes.data, rates.shape[0], _ptr(out)))
+    return out
+
+
+RateExcerpt = namedtuple("RateExcerpt", "short long rate offset first last coverage similarity")
+
+
+def rate_excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: np.ndarray, threshold: float = 50.0,
+                               min_aligned: int = 4) -> list:
+    """The keep rule of find_rate_excerpts on VRATE_DTYPE records (pure numpy; no device): excerpts_from_records' rule -- short
+    = the video with fewer frames (a on a tie); coverage = 100 * aligned frames of short / frames of short; kept iff
+    int(coverage) >= int(threshold) and at least min_aligned frames of short are aligned. -> sorted list of RateExcerpt;
+    rate and offset are Fractions in long's timeline, p_long = rate * p_short + offset: a record (num, den, d) reads
+    p_b = (num / den) p_a + d / den when a is short, and p_a = (den / num) p_b - d / num when b is. first / last: positions in
+    long."""
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    lengths = np.asarray(lengths, dtype=np.int64)
+    out = []
+    for r, sim in zip(aligned, similarity):
+        a, b = int(r["a"]), int(r["b"])
+        a_short = lengths[a] <= lengths[b]
+        n_short = int(lengths[a] if a_short else lengths[b])
+        on = int(r["q_aligned"] if a_short else r["t_aligned"])
+        if n_short == 0 or on < int(min_aligned) or int(r["offset"]) == -(1 << 31):
+            continue
+        coverage = 100.0 * on / n_short
+        if int(coverage) < int(threshold):
+            continue
+        num, den, d = int(r["rate_num"]), int(r["rate_den"]), int(r["offset"])
+        out.append(RateExcerpt(a, b, Fraction(num, den), Fraction(d, den), int(r["t_first"]), int(r["t_last"]), coverage, float(sim))
+                   if a_short else
+                   RateExcerpt(b, a, Fraction(den, num), Fraction(-d, num), int(r["q_first"]), int(r["q_last"]), coverage, float(sim)))
+    return sorted(out)
+
+
+def rate_excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK, rates=DEFAULT_RATES,
+                       positions=None, matcher=None) -> list:
+    """The search and the rate alignment of find_rate_excerpts and their fold, on validated blobs (as excerpt_pairs).
+    matcher: object with match_videos / align_rates (default: the GPU entry points of this module).
+    -> rate_excerpts_from_records(...)."""
+    mv, al = (match_videos, align_rates) if matcher is None else (matcher.match_videos, matcher.align_rates)
+    frames, offsets, lengths = pack_hashes(blobs)
+    pos = _positions_of(positions, blobs, lengths)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
+    recs = mv(frames, offsets, max_dist)
+    aligned = al(frames, offsets, np.stack([recs["a"], recs["b"]], axis=1), positions=pos, rates=rates, slack=slack,
+                 max_dist=max_dist)
+    return rate_excerpts_from_records(aligned, lengths, similarity_of_records(recs, lengths), threshold, min_aligned)
+
+
+def find_rate_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
+                       rates=DEFAULT_RATES, positions=None) -> list:
+    """Copies and excerpts that were sped up or slowed down -- a 1.25x or 1.5x re-upload, a clip slowed to 0.75x, a frame-rate
+    conversion hashed by frame index -- besides what find_excerpts finds. One offset fits such a pair only for a few frames
+    at a time; here every pair of the video search is aligned at each listed rate (align_rates) and kept by find_excerpts'
+    rule on the frames of the SHORTER video that line up at the best one. The arguments are find_excerpts'; rates: see
+    align_rates. -> sorted list of RateExcerpt(short, long, rate, offset, first, last, coverage, similarity): rate and offset
+    are Fractions with p_long = rate * p_short + offset, rate = long-video time per short-video time (above 1: short is the
+    sped-up one); short covers long's positions first..last. With rates = ((1, 1),) the pairs, coverages and offsets are
+    exactly find_excerpts'. `rate` is the best-fitting LISTED rate: on smooth content, where neighbouring frames match each
+    other, a neighbouring rate of the list may be reported; detection rests on the coverage."""
+    return rate_excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, rates, positions)

@@ -82,6 +82,17 @@ class Vpdq:
         return search.align_segments(frames, offsets, [(0, 1)], slack=slack, max_segments=max_segments,
                                      min_band_votes=min_band_votes)[0]
 
+    @staticmethod
+    def align_rates(phash_a, phash_b, rates=None, slack: int = 1):
+        """Where two video hashes line up in time when one of them was sped up or slowed down: the one
+        ``search.align_rates`` record of the pair (a = 0, b = 1; the best-fitting rate of `rates`, default
+        ``search.DEFAULT_RATES``, p_b = (rate_num / rate_den) p_a + offset / rate_den). VpdqHash or bytes."""
+        from . import search
+
+        frames, offsets, _ = search.pack_hashes((phash_a, phash_b))
+        return search.align_rates(frames, offsets, [(0, 1)], rates=search.DEFAULT_RATES if rates is None else rates,
+                                  slack=slack)[0]
+
     select_frames = staticmethod(select_frames)
 
     @staticmethod

@@ -39,7 +39,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -84,6 +84,21 @@ typedef struct hvd_vsegments {
     uint32_t a, b, q_hits, t_hits, n_segments, q_covered, t_covered, reserved;
     hvd_vsegment seg[HVD_ALIGN_MAX_SEGMENTS];
 } hvd_vsegments;
+
+/* One video pair aligned at the best of up to HVD_ALIGN_MAX_RATES listed rates (hvd_vpdq_align_rates / hvd_dev_vpdq_align_rates;
+ * DESIGN 4.10): a sped-up or slowed-down copy or excerpt. Sixteen 32-bit words: the twelve of hvd_valign, in its order, then the
+ * winning rate p_b = (rate_num / rate_den) p_a + offset / rate_den, its index in the caller's list and a reserved word (0).
+ * offset is d* in the rate's scaled units (den p_b - num p_a), band_votes the frame hits within slack_r of it. A pair without a
+ * frame hit, or with an empty video: every word after b is 0. A pair the device entry cannot align (the conditions of
+ * hvd_valign; more than 2^20 bins at ANY listed rate; a broken rate list): offset = INT32_MIN, the other words after b 0. */
+#define HVD_ALIGN_MAX_RATES 8
+typedef struct hvd_vrate {
+    uint32_t a, b, q_hits, t_hits;
+    int32_t offset;
+    uint32_t band_votes, q_aligned, t_aligned;
+    int32_t q_first, q_last, t_first, t_last;
+    uint32_t rate_num, rate_den, rate_index, reserved;
+} hvd_vrate;
 
 /* ------------------------------------------------------------ lifecycle -- */
 
@@ -242,6 +257,39 @@ int hvd_vpdq_align_segments(const uint8_t* frames_q, const int64_t* offsets_q, i
                             const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                             const uint32_t* pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
                             hvd_vsegments* out);
+
+/* Rate-aware time alignment of listed video pairs: a copy or an excerpt that was sped up or slowed down. The
+ * notation and the operands of hvd_vpdq_align_videos apply (positions p, the hit set H, max_dist, slack, the tie order). One
+ * input is new: rates, int32[n_rates][2] = (num_r, den_r) with 1 <= n_rates <= HVD_ALIGN_MAX_RATES, 1 <= num, den <= 8,
+ * gcd(num, den) = 1, pairwise distinct. Rate (num, den) models p_b = (num / den) p_a + c: video b runs through the content
+ * num / den times as slowly as a (a is the sped-up one when num > den). The rule, integers only, one answer per pair:
+ *   for each rate r, in list order:
+ *     delta_r(i, j) = den p_b(j) - num p_a(i)  for (i, j) in H
+ *     slack_r = slack max(num, den)   (the rounding of a resampled timeline alone spreads delta_r over +-den / 2; at (1, 1)
+ *                                      slack_r = slack)
+ *     votes_r[d] = |{(i, j) in H : delta_r = d}|;  S_r(d) = the sum of votes_r[d - slack_r .. d + slack_r];
+ *     d*_r: the largest S_r(d), ties by the larger votes_r[d], then the smaller |d|, then the smaller d
+ *   the winning rate w: the largest S_r(d*_r), ties to the earlier rate of the list
+ *   a frame i of a is aligned iff some (i, j) in H has |delta_w(i, j) - d*_w| <= slack_w; likewise the frames of b
+ * The record (hvd_vrate): a, b, q_hits, t_hits as in hvd_valign; offset = d*_w in the scaled units, so c = offset / rate_den;
+ * band_votes = S_w(d*_w); q_aligned .. t_last as in hvd_valign, on the aligned frames above; rate_num, rate_den, rate_index = w
+ * (0-based); a reserved zero word. Special cases: no hit, or an empty video -> all zero apart from a and b. offset = INT32_MIN
+ * and every other word after b zero: under the conditions of hvd_valign, and when ANY listed rate needs more than 2^20 bins,
+ * bins_r = num span_a + den span_b + 1 + 2 slack_r (span: last position - first position of the video). The device entry gives
+ * the INT32_MIN record to every pair when the rate list is broken; this host entry rejects a broken list, and everything else
+ * named here, with HVD_ERR_ARG -- and does so before it touches the device.
+ * Four consequences: (a) with rates = [(1, 1)], words 0-11 are the pair's hvd_valign record, word for word, and words 12-15 are
+ * 1, 1, 0, 0; (b) with (1, 1) anywhere in the list, band_votes >= the pair's hvd_valign.band_votes; (c) q_hits and t_hits do not
+ * depend on the list; (d) reordering the list changes the record (apart from rate_index) only when two rates tie on S.
+ * S is compared raw across rates although a window of slack_r units is not equally wide in time at every rate: on smooth content
+ * (neighbouring frames within max_dist of each other) a neighbouring listed rate may win. rate_num / rate_den is the
+ * best-fitting LISTED rate; what detection rests on is the coverage (q_aligned / t_aligned).
+ * out: M hvd_vrate records in the order of the pair list. Under a device group it runs on the calling thread's current context
+ * alone. */
+int hvd_vpdq_align_rates(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                         const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                         const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                         hvd_vrate* out);
 
 /* ------------------------------------------------ streaming frame hasher -- */
 /* The native side of vpdq.VideoHasher (vpdqpy/vpdqpy.py:113-119): frames are pushed one at a
@@ -505,6 +553,20 @@ int hvd_dev_vpdq_align_segments(const void* d_hashes_q, const void* d_offsets_q,
                                 const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                                 const void* d_pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
                                 void* d_scratch, size_t scratch_bytes, void* d_out);
+
+/* Device-resident rate-aware alignment (the rule: hvd_vpdq_align_rates above). The operands of hvd_dev_vpdq_align_videos, plus
+ * rates / n_rates: the list, in HOST memory (it is packed into two kernel arguments); d_out: M hvd_vrate records, 16-byte aligned.
+ * A pair's histogram is sized by its largest bins_r over the list: beyond HVD_ALIGN_LDS_BINS the pair needs d_scratch, and
+ * hvd_rates_scratch_bytes(max_bins) bytes serve every pair whose largest bins_r is up to max_bins (<= 2^20). Two launches are
+ * enqueued on the library stream: no host synchronisation, nothing allocated, nothing on the device validated. What gives the
+ * INT32_MIN record of hvd_dev_vpdq_align_videos gives it here, and so do a rate that needs more than 2^20 bins and a broken
+ * rate list (every pair then); broken operands give wrong records, never an access out of bounds. HVD_ERR_ARG: rates NULL or
+ * n_rates < 0, and what hvd_dev_vpdq_align_videos rejects. R listed rates cost R + 1 passes over the pair's Hamming matrix. */
+int hvd_rates_scratch_bytes(int64_t max_bins, size_t* out_bytes);
+int hvd_dev_vpdq_align_rates(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                             const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                             const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                             void* d_scratch, size_t scratch_bytes, void* d_out);
 
 /* Every video pair a<b with >= 1 frame hit, with its vPDQ counters (semantics of vpdqpy/vpdqpy.py:49-56 for all
  * pairs at once; replaces the tree walk of dedup.py:468-475). d_img: FP4 image of the n frame hashes; d_video:
