@@ -44,6 +44,9 @@ ALIGN_MAX_RATES = 8  # HVD_ALIGN_MAX_RATES
 # one video pair aligned at the best of the listed rates (hvd_vrate): the words of VALIGN_DTYPE, offset in the scaled units of the
 # winning rate (den p_b - num p_a), then that rate, its index in the list and a reserved word
 VRATE_DTYPE = np.dtype(VALIGN_DTYPE.descr + [("rate_num", "<u4"), ("rate_den", "<u4"), ("rate_index", "<u4"), ("reserved", "<u4")])
+# one duplicate group (hvd_group): a connected component of size >= 2 of a pair list; root = its smallest member = its label
+GROUP_DTYPE = np.dtype([("root", "<u4"), ("size", "<u4"), ("edges", "<u4"), ("keeper", "<u4")])
+EDGES_ALL, EDGES_VMATCH = 0, 1  # HVD_EDGES_ALL, HVD_EDGES_VMATCH
 
 # name -> (restype, argtypes); every symbol include/hvd_mi355x.h declares.
 _vp, _i64, _int, _sz = C.c_void_p, C.c_int64, C.c_int, C.c_size_t
@@ -75,6 +78,7 @@ SIGNATURES = {
     "hvd_vpdq_align_videos": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp]),
     "hvd_vpdq_align_segments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _int, _int, _vp]),
     "hvd_vpdq_align_rates": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _vp]),
+    "hvd_group_edges": (_int, [_vp, _i64, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     "hvd_hasher_create": (_int, [_int, _int, _int, _i64, C.POINTER(_vp)]),
     "hvd_hasher_push": (_int, [_vp, _vp]),
     "hvd_hasher_set_threads": (_int, [_vp, _int]),
@@ -129,6 +133,8 @@ SIGNATURES = {
     "hvd_rates_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
     "hvd_dev_vpdq_align_rates": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _vp, _sz,
                                         _vp]),
+    "hvd_group_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
+    "hvd_dev_group_edges": (_int, [_vp, _i64, _vp, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hvd_dev_vpdq_match_videos": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _i64, _vp]),
     "hvd_dev_vpdq_emit_again": (_int, [_vp, _i64, _vp]),
     "hvd_dev_vpdq_match_videos_cross": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _int, _int, _int, _vp, _i64,

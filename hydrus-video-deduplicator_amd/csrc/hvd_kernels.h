@@ -191,6 +191,15 @@ hipError_t launch_valign_rates(const void* d_hashes_q, const long long* d_offset
                                const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, uint32_t nums,
                                uint32_t dens, void* d_scratch, size_t scratch_bytes, hvd_vrate* d_out, hipStream_t s);
 
+// Duplicate groups with a keeper: connected components of a list of 16-byte records (k_group.hip). d_scratch:
+// group_scratch_bytes(V), 8-byte aligned; d_record_count: nullptr, or the uint64 an all-pairs pass counted its records in (the
+// kernels then take min(*d_record_count, n_records)); d_count: one uint64, receives the number of groups.
+size_t group_scratch_bytes(unsigned long long V);
+hipError_t launch_group_edges(const void* d_records, unsigned long long n_records, const unsigned long long* d_record_count,
+                              int kind, const long long* d_lengths, uint32_t T, bool is_min, uint32_t V, const uint32_t* d_score,
+                              void* d_scratch, int32_t* d_label, hvd_group* d_groups, unsigned long long cap,
+                              unsigned long long* d_count, hipStream_t s);
+
 // Synthetic 64x64 gray video frames generated in HBM (k_synth.hip; workload generator, not on the hashing path).
 hipError_t launch_synth_frames64(uint8_t* d_out, long long v0, uint32_t frames_per_video, unsigned long long n_frames,
                                  uint64_t seed, const int32_t* d_copy_of, hipStream_t s);

@@ -1223,6 +1223,88 @@ int hvd_vpdq_align_rates(const uint8_t* frames_q, const int64_t* offsets_q, int6
                            1, out, rates, n_rates);
 }
 
+/* ---- duplicate groups with a keeper: connected components of a pair list (k_group.hip) ---- */
+
+static int check_group_shape(int64_t n_records, int kind, const void* lengths, int threshold, int64_t V) {
+    if (V < 1 || V >= (1ll << 31)) return fail(HVD_ERR_ARG, "V=%lld out of range [1,2^31)", (long long)V);
+    if (n_records < 0 || n_records >= (1ll << 32)) return fail(HVD_ERR_ARG, "%lld records: need 0..2^32-1", (long long)n_records);
+    if (kind != HVD_EDGES_ALL && kind != HVD_EDGES_VMATCH) return fail(HVD_ERR_ARG, "kind=%d: need HVD_EDGES_ALL or HVD_EDGES_VMATCH", kind);
+    if (kind == HVD_EDGES_VMATCH) {
+        if (!lengths) return fail(HVD_ERR_ARG, "HVD_EDGES_VMATCH needs the lengths");
+        if (threshold < 1 || threshold > 100) return fail(HVD_ERR_ARG, "threshold=%d out of range [1,100]", threshold);
+    }
+    return HVD_OK;
+}
+
+int hvd_group_scratch_bytes(int64_t V, size_t* out_bytes) {
+    if (!out_bytes || V < 1 || V >= (1ll << 31)) return fail(HVD_ERR_ARG, "V=%lld out of range [1,2^31)", (long long)V);
+    *out_bytes = hvd::group_scratch_bytes((unsigned long long)V);
+    return HVD_OK;
+}
+
+int hvd_dev_group_edges(const void* d_records, int64_t n_records, const void* d_record_count, int kind, const void* d_lengths,
+                        int threshold, int policy_is_min, int64_t V, const void* d_score, void* d_scratch, void* d_out_label,
+                        void* d_out_groups, int64_t cap, void* d_out_count) {
+    if (int rc = need_ready()) return rc;
+    if (int rc = check_group_shape(n_records, kind, d_lengths, threshold, V)) return rc;
+    if (!d_scratch || !d_out_label || !d_out_count || (n_records > 0 && !d_records) || cap < 0 || (cap > 0 && !d_out_groups))
+        return fail(HVD_ERR_ARG, "NULL device pointer / bad cap");
+    if ((((uintptr_t)d_records | (uintptr_t)d_out_groups) & 15u) || (((uintptr_t)d_scratch | (uintptr_t)d_out_count | (uintptr_t)d_record_count) & 7u))
+        return fail(HVD_ERR_ARG, "records and groups must be 16-byte aligned, scratch and counts 8-byte aligned");
+    HIP_TRY(hvd::launch_group_edges(d_records, (unsigned long long)n_records, (const unsigned long long*)d_record_count, kind,
+                                    (const long long*)d_lengths, (uint32_t)threshold, policy_is_min != 0, (uint32_t)V,
+                                    (const uint32_t*)d_score, d_scratch, (int32_t*)d_out_label, (hvd_group*)d_out_groups,
+                                    (unsigned long long)cap, (unsigned long long*)d_out_count, g.stream));
+    return HVD_OK;
+}
+
+int hvd_group_edges(const void* records, int64_t E, int kind, const int64_t* lengths, int threshold, int policy_is_min, int64_t V,
+                    const uint32_t* score, int32_t* out_label, hvd_group* out_groups, int64_t cap, int64_t* out_count) {
+    // the arguments are judged before the library's state is: a bad call is HVD_ERR_ARG with or without a device
+    if (int rc = check_group_shape(E, kind, lengths, threshold, V)) return rc;
+    if (!out_label || !out_count || (E > 0 && !records) || cap < 0 || (cap > 0 && !out_groups))
+        return fail(HVD_ERR_ARG, "NULL pointer / bad cap");
+    const uint32_t* w = (const uint32_t*)records;
+    for (int64_t e = 0; e < E; ++e)
+        if ((int64_t)w[4 * e] >= V || (int64_t)w[4 * e + 1] >= V || w[4 * e] == w[4 * e + 1])
+            return fail(HVD_ERR_ARG, "record %lld = (%u, %u) is no edge between two of the %lld nodes", (long long)e, w[4 * e],
+                        w[4 * e + 1], (long long)V);
+    if (int rc = need_ready()) return rc;
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    void *d_rec = nullptr, *d_len = nullptr, *d_score = nullptr, *d_scr = nullptr, *d_label = nullptr;
+    uint8_t* d_out = nullptr;  // the count, then the group records
+    SCR(S_GSCR, hvd::group_scratch_bytes((unsigned long long)V), d_scr);
+    SCR(S_GLABEL, 4 * (size_t)V, d_label);
+    SCR(S_GOUT, 16 + 16 * (size_t)cap, d_out);
+    if (E > 0) {
+        SCR(S_GREC, 16 * (size_t)E, d_rec);
+        HIP_TRY(hipMemcpyAsync(d_rec, records, 16 * (size_t)E, hipMemcpyHostToDevice, g.stream));
+    }
+    if (kind == HVD_EDGES_VMATCH) {
+        SCR(S_GLEN, 8 * (size_t)V, d_len);
+        HIP_TRY(hipMemcpyAsync(d_len, lengths, 8 * (size_t)V, hipMemcpyHostToDevice, g.stream));
+    }
+    if (score) {
+        SCR(S_GSCORE, 4 * (size_t)V, d_score);
+        HIP_TRY(hipMemcpyAsync(d_score, score, 4 * (size_t)V, hipMemcpyHostToDevice, g.stream));
+    }
+    if (int rc = hvd_dev_group_edges(d_rec, E, nullptr, kind, d_len, threshold, policy_is_min, V, d_score, d_scr, d_label,
+                                     cap > 0 ? d_out + 16 : nullptr, cap, d_out))
+        return rc;
+    unsigned long long count = 0;
+    HIP_TRY(hipMemcpyAsync(&count, d_out, 8, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(out_label, d_label, 4 * (size_t)V, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    const unsigned long long n_out = std::min(count, (unsigned long long)cap);
+    if (n_out > 0) {
+        HIP_TRY(hipMemcpyAsync(out_groups, d_out + 16, 16 * (size_t)n_out, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+    }
+    *out_count = (int64_t)count;
+    if (count > (unsigned long long)cap) return fail(HVD_ERR_OVERFLOW, "%llu groups, room for %lld", count, (long long)cap);
+    return HVD_OK;
+}
+
 #ifndef HVD_NO_BENCH_SYMBOLS
 int hvd_dev_synth_video_frames(void* d_frames, int64_t v0, int64_t n_videos, int frames_per_video, uint64_t seed,
                                const void* d_copy_of) {

@@ -24,7 +24,7 @@ import time
 import numpy as np
 
 from . import _lib, search, vpdq
-from ._lib import VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VSEGMENTS_DTYPE, DeviceBuffer
+from ._lib import GROUP_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VSEGMENTS_DTYPE, DeviceBuffer
 
 
 def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
@@ -576,6 +576,89 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
         return pairs, recs, library
     library.free()
     return pairs, recs, None
+
+
+def group_records_on_device(d_records_ptr: int, n_records: int, d_record_count_ptr, V: int, d_score_ptr=None,
+                            accept=None) -> tuple[np.ndarray, np.ndarray] | None:
+    """hvd_dev_group_edges (HVD_EDGES_ALL) over records that lie in HBM -> (labels, groups) as search.group_edges returns them;
+    only those cross PCIe. d_record_count_ptr: None, or the uint64 an all-pairs entry counted its records in: the grouping is
+    then enqueued behind that pass with no read-back in between and takes min(count, n_records) records. accept(): called after
+    the launches and before anything is downloaded; returning False drops the result (-> None)."""
+    lib = _lib.ensure()
+    sb = C.c_size_t(0)
+    _lib.check(lib.hvd_group_scratch_bytes(V, C.byref(sb)))
+    cap = max(1, min(V // 2, n_records))  # a group has two members and one record at least
+    with _DeviceScope() as scope:
+        d_scr, d_label = scope.temp(DeviceBuffer(sb.value)), scope.temp(DeviceBuffer(4 * V))
+        d_groups, d_cnt = scope.temp(DeviceBuffer(16 * cap)), scope.temp(DeviceBuffer(8))
+        _lib.check(lib.hvd_dev_group_edges(d_records_ptr, n_records, d_record_count_ptr, _lib.EDGES_ALL, None, 0, 0, V, d_score_ptr,
+                                           d_scr.ptr, d_label.ptr, d_groups.ptr, cap, d_cnt.ptr))
+        out = None
+        if accept is None or accept():
+            count = int(d_cnt.to_array(np.uint64, 1)[0])  # (the copy waits for the library stream)
+            assert count <= cap
+            out = d_label.to_array(np.int32, V), d_groups.to_array(GROUP_DTYPE, count)
+        _lib.check(lib.hvd_dev_sync())  # nothing may still run on a buffer that is freed here
+    return out
+
+
+def cluster_hashes_on_device(d_db_ptr: int, n: int, max_dist: int = search.DISTANCE_TOLERANCE, pair_cap: int | None = None,
+                             score=None, variant: int = search.DEFAULT_VARIANT) -> tuple[np.ndarray, np.ndarray]:
+    """Groups of near-duplicate hashes with the pair list never leaving HBM: n packed hashes at d_db_ptr -> FP4 image ->
+    hvd_dev_allpairs_hamming256_mfma (every i < j within max_dist, appended to a pair buffer of pair_cap records) ->
+    hvd_dev_group_edges over that buffer and its device-side count, enqueued without a read-back -> (labels, groups) as
+    search.group_edges(search.allpairs_hamming(db, max_dist), n) returns them. The one number read before the download is the
+    pair count: when it exceeded the buffer, the pass is repeated with a buffer of exactly that size (the spirit of
+    _lib.records_with_retry). score: uint32 per hash for the keeper, default all 0 (the smallest index)."""
+    lib = _lib.ensure()
+    n = int(n)
+    if n == 0:
+        return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=GROUP_DTYPE)
+    score = search._score_array(score, n)
+    cap = max(4096, 8 * n) if pair_cap is None else max(1, int(pair_cap))
+    sz = C.c_size_t(0)
+    _lib.check(lib.hvd_fp4_image_bytes(n, C.byref(sz)))
+    with _DeviceScope() as scope:
+        d_img = scope.temp(DeviceBuffer(sz.value))
+        d_score = scope.temp(DeviceBuffer.from_array(score) if score is not None else None)
+        d_cnt = scope.temp(DeviceBuffer(8))
+        _lib.check(lib.hvd_dev_expand_fp4(d_db_ptr, n, d_img.ptr))
+        found = 0
+
+        def pairs_fit():
+            nonlocal found
+            found = int(d_cnt.to_array(np.uint64, 1)[0])  # (the copy waits for the library stream)
+            return found <= cap
+
+        while True:
+            d_pairs = scope.temp(DeviceBuffer(16 * cap))
+            d_cnt.zero()
+            _lib.check(lib.hvd_dev_allpairs_hamming256_mfma(d_db_ptr, d_img.ptr, n, None, int(max_dist), 0, 1, d_pairs.ptr, cap,
+                                                            d_cnt.ptr, int(variant)))
+            out = group_records_on_device(d_pairs.ptr, cap, d_cnt.ptr, n, d_score.ptr if d_score else None, pairs_fit)
+            if out is not None:
+                return out
+            d_pairs.free()  # (group_records_on_device has waited for the stream)
+            cap = found
+
+
+def find_duplicate_groups_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                    threshold: float = 50.0, policy: str | None = None, score=None, keep_library: bool = False):
+    """search.find_duplicate_groups on frames in HBM, one device: the chain of `dedupe_frames_on_device` (hash -> quality filter
+    + CSR -> video search), then search.group_records over its records with the library's kept lengths: the pair predicate and
+    the grouping run on the device. score: uint32 per video for the keeper; default the number of kept frames.
+    -> (duplicate groups, labels, group records, library or None)."""
+    _, recs, library = dedupe_frames_on_device(d_frames_ptr, raw_offsets, h, w, channels, threshold, policy, keep_library=True)
+    try:
+        lengths = library.lengths()
+        labels, groups = search.group_records(recs, lengths, threshold, policy, lengths if score is None else score)
+    except BaseException:
+        library.free()
+        raise
+    if not keep_library:
+        library.free()
+        library = None
+    return search.groups_from_labels(labels, groups), labels, groups, library
 
 
 def _aligned_search_on_device(d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library, align, fold):

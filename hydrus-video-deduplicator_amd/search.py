@@ -11,13 +11,14 @@ db/vptree.py:431-441); this module computes it exactly.
 
 from __future__ import annotations
 
+import ctypes as C
 from collections import namedtuple
 from fractions import Fraction
 
 import numpy as np
 
 from . import _lib, vpdq
-from ._lib import ALIGN_MAX_RATES, ALIGN_MAX_SEGMENTS, PAIR_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VSEGMENTS_DTYPE
+from ._lib import ALIGN_MAX_RATES, ALIGN_MAX_SEGMENTS, GROUP_DTYPE, PAIR_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VSEGMENTS_DTYPE
 
 DISTANCE_TOLERANCE = 31  # per-frame Hamming tolerance (vpdqpy/vpdqpy.py:53, db/vptree.py:31)
 DEFAULT_VARIANT = 13  # all-pairs kernel the product uses (FP4-MFMA, 128-bit first stage, form chosen by a probe); DESIGN.md 4.1
@@ -617,3 +618,123 @@ def find_rate_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int =
     exactly find_excerpts'. `rate` is the best-fitting LISTED rate: on smooth content, where neighbouring frames match each
     other, a neighbouring rate of the list may be reported; detection rests on the coverage."""
     return rate_excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, rates, positions)
+
+
+# ------------------------------------------------------------------ duplicate groups with a keeper (DESIGN 4.11) ------
+
+DuplicateGroup = namedtuple("DuplicateGroup", "members keeper edges complete")
+
+
+def edge_records(edges) -> np.ndarray:
+    """What the grouping entries read: 16-byte records with the two nodes in words 0 and 1. Records of a search (PAIR_DTYPE,
+    VMATCH_DTYPE or any other 16-byte record dtype) pass as they are; int[M, 2] rows -- the (a, b) columns of the transformed
+    and excerpt searches, find_potential_duplicates' list -- become PAIR_DTYPE records."""
+    if isinstance(edges, np.ndarray) and edges.dtype.names:
+        if edges.dtype.itemsize != 16:
+            raise ValueError("edge records must be 16 bytes with the two nodes in words 0 and 1")
+        return np.ascontiguousarray(edges).reshape(-1)
+    pairs = pair_array(edges)
+    recs = np.zeros(pairs.shape[0], dtype=PAIR_DTYPE)
+    recs["i"], recs["j"] = pairs[:, 0], pairs[:, 1]
+    return recs
+
+
+def _score_array(score, V: int) -> np.ndarray | None:
+    if score is None:
+        return None
+    score = np.asarray(score)
+    if score.shape != (V,):
+        raise ValueError("score must hold one value per node")
+    if V and (score.min() < 0 or score.max() >= 1 << 32):
+        raise ValueError("scores must fit 32 unsigned bits")
+    return np.ascontiguousarray(score, dtype=np.uint32)
+
+
+def _group(records: np.ndarray, kind: int, lengths, T: int, is_min: bool, V: int, score) -> tuple[np.ndarray, np.ndarray]:
+    """hvd_group_edges -> (labels int32[V], GROUP_DTYPE records sorted by root)."""
+    score = _score_array(score, V)
+    if V == 0:
+        if records.size:
+            raise ValueError("records without a node")
+        return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=GROUP_DTYPE)
+    E = records.shape[0]
+    cap = min(V // 2, E)  # a group has two members and one record at least
+    labels = np.empty(V, dtype=np.int32)
+    groups = np.zeros(max(cap, 1), dtype=GROUP_DTYPE)
+    cnt = C.c_int64(0)
+    lib = _lib.ensure()
+    _lib.check(lib.hvd_group_edges(_ptr(records), E, kind, _ptr(lengths), T, int(is_min), V, _ptr(score), labels.ctypes.data,
+                                   groups.ctypes.data, cap, C.byref(cnt)))
+    return labels, groups[: cnt.value].copy()
+
+
+def group_edges(edges, V: int, score=None) -> tuple[np.ndarray, np.ndarray]:
+    """Connected components of a pair list on the GPU (hvd_group_edges, HVD_EDGES_ALL): `edges` are the records of a search or
+    int[M, 2] rows (see `edge_records`) over nodes 0..V-1, either orientation, repeats allowed. -> (labels, groups): labels
+    int32[V], labels[v] = the smallest index in v's component; groups: one GROUP_DTYPE record (root, size, edges, keeper) per
+    component of two or more nodes, sorted by root. keeper: the member with the largest score (uint32 per node; default all 0),
+    ties to the smaller index."""
+    return _group(edge_records(edges), _lib.EDGES_ALL, None, 0, False, int(V), score)
+
+
+def group_records(records: np.ndarray, lengths: np.ndarray, threshold: float = 50.0, policy: str | None = None,
+                  score=None) -> tuple[np.ndarray, np.ndarray]:
+    """The groups of a video search: `group_edges` over the VMATCH records that pass the pair predicate of
+    `similar_video_pairs` (hvd_group_edges, HVD_EDGES_VMATCH: the same rows, chosen in integers on the device). lengths: frames
+    per video, one node each. -> (labels, groups)."""
+    policy = vpdq.MATCH_POLICY if policy is None else policy
+    if policy not in ("min", "max", "query", "target"):
+        raise ValueError(f"unknown match policy {policy!r}")
+    T = int(threshold)
+    if T < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    records = np.ascontiguousarray(records, dtype=VMATCH_DTYPE).reshape(-1)
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    V = lengths.shape[0]
+    if T > 100:  # no similarity is above 100: every video on its own
+        return np.arange(V, dtype=np.int32), np.zeros(0, dtype=GROUP_DTYPE)
+    return _group(records, _lib.EDGES_VMATCH, lengths, T, policy == "min", V, score)
+
+
+def groups_from_labels(labels: np.ndarray, groups: np.ndarray) -> list:
+    """(labels, groups) of the grouping entries -> [DuplicateGroup(members, keeper, edges, complete)], sorted by first member.
+    members: ascending tuple (a stable argsort of the labels, on the host); complete: every member pairs with every other,
+    edges == size (size - 1) / 2 -- a chain A~B~C without A~C is one group that is not complete."""
+    labels = np.asarray(labels)
+    order = np.argsort(labels, kind="stable")
+    by_label = labels[order]
+    out = []
+    for g in groups[np.argsort(groups["root"], kind="stable")]:
+        size = int(g["size"])
+        lo = int(np.searchsorted(by_label, int(g["root"]), side="left"))
+        members = tuple(int(m) for m in order[lo:lo + size])
+        out.append(DuplicateGroup(members, int(g["keeper"]), int(g["edges"]), int(g["edges"]) == size * (size - 1) // 2))
+    return out
+
+
+def find_duplicate_groups(video_hashes, threshold: float = 50.0, policy: str | None = None, score=None) -> list:
+    """find_potential_duplicates as groups with a keeper: the connected components of its pairs, as DuplicateGroup(members,
+    keeper, edges, complete) sorted by first member. score (uint32 per video): the keeper of a group is its member with the
+    largest score, ties to the smaller index; default: the number of kept frames, so the longest copy is kept -- pass
+    resolution, file size or bitrate to keep by those."""
+    frames, offsets, lengths = pack_hashes(video_hashes)
+    recs = match_videos(frames, offsets, vpdq.frame_max_dist(DISTANCE_TOLERANCE))
+    labels, groups = group_records(recs, lengths, threshold, policy, lengths if score is None else score)
+    return groups_from_labels(labels, groups)
+
+
+def cluster_hashes(db: np.ndarray, max_dist: int = DISTANCE_TOLERANCE, score=None) -> tuple[np.ndarray, np.ndarray]:
+    """The groups of `allpairs_hamming(db, max_dist)` without its pair list: the hashes go up, the all-pairs pass leaves its
+    pairs in HBM, the grouping runs over them there (pipeline.cluster_hashes_on_device), labels and group records come back.
+    -> (labels, groups) as `group_edges`."""
+    from . import pipeline
+
+    db = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1, 32)
+    n = db.shape[0]
+    if n == 0:
+        return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=GROUP_DTYPE)
+    d_db = _lib.DeviceBuffer.from_array(db)
+    try:
+        return pipeline.cluster_hashes_on_device(d_db.ptr, n, max_dist, score=score)
+    finally:
+        d_db.free()

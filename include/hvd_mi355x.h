@@ -18,6 +18,7 @@
  *   hvd_pair    : one frame-level hit (i<j, Hamming distance).
  *   hvd_vmatch  : one video-level hit (a<b) with the vPDQ counters: q_hits = frames
  *                 of a that have >=1 frame of b within max_dist, t_hits the converse.
+ *   hvd_group   : one group of duplicates (a connected component of a pair list) with its keeper.
  */
 #ifndef HVD_MI355X_H
 #define HVD_MI355X_H
@@ -39,7 +40,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -99,6 +100,17 @@ typedef struct hvd_vrate {
     int32_t q_first, q_last, t_first, t_last;
     uint32_t rate_num, rate_den, rate_index, reserved;
 } hvd_vrate;
+
+/* One duplicate group (hvd_group_edges / hvd_dev_group_edges): a connected component of size >= 2 of the graph
+ * whose edges are the records of a search. root: the smallest member, which is also the label of every member; size: members;
+ * edges: input records that are edges inside the group (a repeated record counts each time); keeper: the member with the largest
+ * score, ties to the smaller index -- Hydrus' "king". The group is complete (every member pairs with every other) iff
+ * edges == size (size - 1) / 2, given that the list holds each pair once, as the searches emit them. */
+typedef struct hvd_group {
+    uint32_t root, size, edges, keeper;
+} hvd_group;
+#define HVD_EDGES_ALL 0    /* every record is an edge (hvd_pair, or any 16-byte record with the two nodes in words 0 and 1) */
+#define HVD_EDGES_VMATCH 1 /* hvd_vmatch records; a record is an edge iff the reference's pair predicate holds */
 
 /* ------------------------------------------------------------ lifecycle -- */
 
@@ -290,6 +302,29 @@ int hvd_vpdq_align_rates(const uint8_t* frames_q, const int64_t* offsets_q, int6
                          const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                          const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                          hvd_vrate* out);
+
+/* Duplicate groups with a keeper: the connected components of a pair list. The rule, integers only, one answer per
+ * input. V nodes, 1 <= V < 2^31. E records of 16 bytes, E < 2^32, words 0 and 1 the two node indices u, v (hvd_pair and
+ * hvd_vmatch have this shape). kind:
+ *   HVD_EDGES_ALL     every record is an edge; either orientation and repeated records are allowed.
+ *   HVD_EDGES_VMATCH  the record is an hvd_vmatch and is an edge iff the reference's pair predicate holds (dedup.py:445-502).
+ *                     With na = lengths[u], nb = lengths[v] (int64 per node) and T = threshold in [1, 100]:
+ *                       qa = na > 0 and 100 q_hits >= T na;   tb = nb > 0 and 100 t_hits >= T nb
+ *                     policy_is_min != 0 (policy "min"): edge iff qa and tb; else ("max", "query", "target"): iff qa or tb. All of
+ *                     it in 64-bit integers. The reference divides in floating point and truncates: floor(100 q / n) >= T
+ *                     <=> 100 q >= T n, so these are exactly its pairs.
+ * A record with u >= V, v >= V or u == v is no edge: the device entry ignores it, this host entry rejects it (HVD_ERR_ARG).
+ * score: uint32 per node, or NULL: every score 0.
+ * out_label: int32[V]; label[v] = the smallest index in v's component (label[v] == v for a node on its own).
+ * out_groups: one hvd_group per component of size >= 2, sorted by root ascending; min(count, cap) are written. *out_count: the
+ * true number of groups; HVD_ERR_OVERFLOW if it exceeds cap (the labels and the first cap groups are valid then). There are at
+ * most min(V / 2, E) groups.
+ * Nothing in the result depends on the order of the records or on scheduling.
+ * This host-buffer form validates everything -- V and E in range, kind, T, lengths with kind 1, every record -- before it asks
+ * for a device (HVD_ERR_ARG with or without one), then uploads, runs the kernels and downloads. Under a device group it runs on
+ * the calling thread's current context alone. */
+int hvd_group_edges(const void* records, int64_t E, int kind, const int64_t* lengths, int threshold, int policy_is_min, int64_t V,
+                    const uint32_t* score, int32_t* out_label, hvd_group* out_groups, int64_t cap, int64_t* out_count);
 
 /* ------------------------------------------------ streaming frame hasher -- */
 /* The native side of vpdq.VideoHasher (vpdqpy/vpdqpy.py:113-119): frames are pushed one at a
@@ -567,6 +602,19 @@ int hvd_dev_vpdq_align_rates(const void* d_hashes_q, const void* d_offsets_q, in
                              const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                              const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                              void* d_scratch, size_t scratch_bytes, void* d_out);
+
+/* Device-resident grouping (the rule: hvd_group_edges above). d_records: n_records records of 16 bytes, 16-byte aligned;
+ * d_record_count: NULL, or the uint64 the all-pairs entries bump -- the kernels then take min(*d_record_count, n_records)
+ * records, so the call chains behind hvd_dev_allpairs_hamming256[_mfma] (d_pairs, cap, d_count) with no read-back. d_lengths:
+ * int64[V] (HVD_EDGES_VMATCH only); d_score: uint32[V] or NULL; d_scratch: hvd_group_scratch_bytes(V) bytes (20 per node and 4
+ * per 1024 nodes), 8-byte aligned; d_out_label: int32[V]; d_out_groups: cap records, 16-byte aligned (may be NULL when cap is
+ * 0); d_out_count: one uint64, the true number of groups. Enqueued on the library stream: no host synchronisation, nothing
+ * allocated. Records that are no edge (an index >= V, u == v) are ignored; every index is checked before use, so a broken list
+ * gives other groups, never an access out of bounds. */
+int hvd_group_scratch_bytes(int64_t V, size_t* out_bytes);
+int hvd_dev_group_edges(const void* d_records, int64_t n_records, const void* d_record_count, int kind, const void* d_lengths,
+                        int threshold, int policy_is_min, int64_t V, const void* d_score, void* d_scratch, void* d_out_label,
+                        void* d_out_groups, int64_t cap, void* d_out_count);
 
 /* Every video pair a<b with >= 1 frame hit, with its vPDQ counters (semantics of vpdqpy/vpdqpy.py:49-56 for all
  * pairs at once; replaces the tree walk of dedup.py:468-475). d_img: FP4 image of the n frame hashes; d_video:
