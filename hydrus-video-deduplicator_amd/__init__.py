@@ -8,13 +8,13 @@ The directory name has hyphens; import it as ``hvd_amd`` (see /hvd_amd.py).
 from . import (_lib, hashing, multigpu, pipeline, rendezvous, search, sqlite_adapter, synth, vpdq,  # noqa: F401
                vpdqpy, vptree)
 from .hashing import compute_phash, decode_phash_from_str, encode_phash_to_str, get_phash_similarity  # noqa: F401
-from .search import (allpairs_hamming, calculate_distance, find_duplicate_groups, find_excerpts,  # noqa: F401
+from .search import (allpairs_hamming, calculate_distance, find_cropped_duplicates, find_duplicate_groups, find_excerpts,  # noqa: F401
                      find_potential_duplicates,
                      find_rate_excerpts, find_segmented_excerpts, find_transformed_duplicates, fix_vpdq_similarity,
                      match_videos)
 from .vpdq import VideoHasher, VpdqHash, matchHash, matchHashBytes  # noqa: F401
-from .pipeline import (DeviceLibrary, dedupe_frames_on_device, dedupe_transformed_frames_on_device, dedupe_videos,  # noqa: F401
-                       hash_videos)
+from .pipeline import (DeviceLibrary, dedupe_cropped_frames_on_device, dedupe_frames_on_device,  # noqa: F401
+                       dedupe_transformed_frames_on_device, dedupe_videos, hash_videos)
 from .vpdqpy import Vpdq  # noqa: F401
 
 __version__ = "0.1.0"

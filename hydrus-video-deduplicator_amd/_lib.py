@@ -70,6 +70,8 @@ SIGNATURES = {
     "hvd_pdq_hash_frames_rgb24_u8": (_int, [_vp, _i64, _int, _int, _vp, _vp]),
     "hvd_pdq_hash_frames_dihedral_gray_u8": (_int, [_vp, _i64, _int, _int, _vp, _vp]),
     "hvd_pdq_hash_frames_dihedral_rgb24_u8": (_int, [_vp, _i64, _int, _int, _vp, _vp]),
+    "hvd_pdq_hash_frames_crops_gray_u8": (_int, [_vp, _i64, _int, _int, _vp, _int, _vp, _vp, _vp]),
+    "hvd_pdq_hash_frames_crops_rgb24_u8": (_int, [_vp, _i64, _int, _int, _vp, _int, _vp, _vp, _vp]),
     "hvd_allpairs_hamming256": (_int, [_vp, _i64, _vp, _int, _vp, _i64, C.POINTER(_i64)]),
     "hvd_match_two": (_int, [_vp, _i64, _vp, _i64, _int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "hvd_vpdq_match_videos": (_int, [_vp, _vp, _i64, _int, _vp, _i64, C.POINTER(_i64)]),
@@ -115,6 +117,8 @@ SIGNATURES = {
     "hvd_dev_content_rects": (_int, [_vp, _i64, _int, _int, _int, _vp, _i64, _int, _int, _vp]),
     "hvd_pdq_rects_scratch_bytes": (_int, [_i64, _int, _int, _int, C.POINTER(_sz)]),
     "hvd_dev_pdq_hash_frames_rects": (_int, [_vp, _i64, _int, _int, _int, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "hvd_pdq_crops_scratch_bytes": (_int, [_i64, _int, _int, _int, C.POINTER(_sz)]),
+    "hvd_dev_pdq_hash_frames_crops": (_int, [_vp, _i64, _int, _int, _int, _vp, _int, _vp, _vp, _vp, _vp]),
     "hvd_dev_allpairs_hamming256": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _i64, _vp, _int]),
     "hvd_fp4_image_bytes": (_int, [_i64, C.POINTER(_sz)]),
     "hvd_dev_expand_fp4": (_int, [_vp, _i64, _vp]),

@@ -946,6 +946,41 @@ int hvd_dev_pdq_hash_frames_rects(const void* d_frames, int64_t n, int h, int w,
     return HVD_OK;
 }
 
+/* ---- crop-ladder PDQ (k_crops.hip) ---- */
+
+// what needs no device: the frame geometry and the caller's list
+static int crops_arguments(int64_t n, int h, int w, const int32_t* crops, int K) {
+    if (n < 0 || n >= (1ll << 31) || h < 64 || w < 64 || h > 4096 || w > 4096)
+        return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d (need h,w in [64,4096])", (long long)n, h, w);
+    if (K < 1 || K > HVD_MAX_CROPS) return fail(HVD_ERR_ARG, "K=%d crops: need 1..%d", K, HVD_MAX_CROPS);
+    if (!crops) return fail(HVD_ERR_ARG, "NULL crop list");
+    if (!hvd::crops_valid(crops, K, h, w))
+        return fail(HVD_ERR_ARG, "a crop does not lie inside the %d x %d frame or has a side below 64", h, w);
+    return HVD_OK;
+}
+
+int hvd_pdq_crops_scratch_bytes(int64_t n, int h, int w, int K, size_t* out_bytes) {
+    if (!out_bytes || n < 0 || n >= (1ll << 31) || h < 64 || w < 64 || h > 4096 || w > 4096 || K < 1 || K > HVD_MAX_CROPS)
+        return fail(HVD_ERR_ARG, "bad frame geometry or crop count");
+    *out_bytes = hvd::pdq_crops_scratch_bytes(n, h, w, K);
+    return HVD_OK;
+}
+
+int hvd_dev_pdq_hash_frames_crops(const void* d_frames, int64_t n, int h, int w, int channels, const int32_t* crops, int K,
+                                  void* d_scratch, void* d_hashes8, void* d_quality, void* d_crop_quality) {
+    if (int rc = crops_arguments(n, h, w, crops, K)) return rc;
+    if (channels != 1 && channels != 3) return fail(HVD_ERR_ARG, "channels=%d: need 1 or 3", channels);
+    if (int rc = need_ready()) return rc;
+    if (n == 0) return HVD_OK;
+    if (!d_frames || !d_scratch || !d_hashes8 || !d_quality) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if ((uintptr_t)d_scratch & 15u) return fail(HVD_ERR_ARG, "d_scratch must be 16-byte aligned (hvd_dev_malloc's are)");
+    if (((uintptr_t)d_hashes8 | (uintptr_t)d_quality | (uintptr_t)d_crop_quality) & 3u)
+        return fail(HVD_ERR_ARG, "d_hashes8, d_quality and d_crop_quality must be 4-byte aligned");
+    HIP_TRY(hvd::launch_pdq_hash_crops((const uint8_t*)d_frames, n, h, w, channels, crops, K, g.d_dct, d_scratch,
+                                       (uint8_t*)d_hashes8, (int32_t*)d_quality, (int32_t*)d_crop_quality, g.stream));
+    return HVD_OK;
+}
+
 int hvd_allpairs_tile_geometry(int64_t n, int variant, uint32_t* rows_per_block, uint32_t* col_chunk) {
     if (n < 0 || n >= (1ll << 32) || !rows_per_block || !col_chunk) return fail(HVD_ERR_ARG, "bad arguments");
     if (!hvd::allpairs_geometry((uint32_t)n, variant, rows_per_block, col_chunk) &&

@@ -234,6 +234,7 @@ hipError_t launch_pdq_dihedral64(const void* d_in, int kind, int64_t n, const fl
 // reference's 512x512 rgb24 frames, vpdqpy/vpdqpy.py:90-95,113).
 // d_ws: min(n,1024) * pdq_downsample_ws_floats(h,w) floats of workspace.
 size_t pdq_downsample_ws_floats(int h, int w);
+size_t pdq_down512_ws_floats(int64_t n);  // of those, what a 512 x 512 call needs while g_pdq_fused_down512 is on
 hipError_t launch_pdq_downsample(const uint8_t* d_frames, int64_t n, int h, int w, int channels, float* d_ws,
                                  float* d_out64, hipStream_t s);
 // 64x64 rgb24 frames: luma only (no blur, as upstream's 64x64 shortcut).
@@ -260,5 +261,13 @@ size_t pdq_rects_geom_bytes(int64_t n);
 hipError_t launch_pdq_downsample_rects(const uint8_t* d_frames, int64_t n, int h, int w, int channels,
                                        const long long* d_offsets, uint32_t V, const int32_t* d_rects, void* d_geom,
                                        float* d_ws, float* d_out64, hipStream_t s);
+
+// Crop-ladder PDQ (k_crops.hip). crops: HOST int32[K][4] {top, left, height, width}; crops_valid: 1 <= K <=
+// HVD_MAX_CROPS and every crop inside the h x w frame with both sides >= 64 -- the one definition of a sound list.
+bool crops_valid(const int32_t* crops, int K, int h, int w);
+size_t pdq_crops_scratch_bytes(int64_t n, int h, int w, int K);
+hipError_t launch_pdq_hash_crops(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const int32_t* crops, int K,
+                                 const float* d_dct, void* d_scratch, uint8_t* d_hashes8, int32_t* d_quality,
+                                 int32_t* d_crop_quality, hipStream_t s);
 
 }  // namespace hvd

@@ -126,6 +126,51 @@ int hvd_pdq_hash_frames_dihedral_rgb24_u8(const uint8_t* frames, int64_t n, int 
     return hash_frames_group(frames, n, h, w, 3, out_hashes8, out_quality, 8);
 }
 
+// Crop-ladder hashing of host frames. Runs on the calling thread's current context, also under a device group;
+// batches as hash_frames_host. The list is checked by the device entry before it asks for a device, so a bad list is
+// HVD_ERR_ARG here too, whatever the state.
+static int hash_frames_crops_host(const uint8_t* frames, int64_t n, int h, int w, int channels, const int32_t* crops, int K,
+                                  uint8_t* out_hashes8, int32_t* out_quality, int32_t* out_crop_quality) {
+    if (int rc = hvd_dev_pdq_hash_frames_crops(nullptr, 0, h, w, channels, crops, K, nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (n < 0 || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad frame count n=%lld", (long long)n);
+    if (n == 0) return HVD_OK;
+    if (!frames || !out_hashes8 || !out_quality) return fail(HVD_ERR_ARG, "NULL buffer");
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    const size_t frame_bytes = (size_t)h * w * channels;
+    int64_t batch = (int64_t)((1ull << 30) / frame_bytes);
+    if (batch < 1) batch = 1;
+    if (batch > n) batch = n;
+    void *d_in = nullptr, *d_scr = nullptr, *d_h = nullptr, *d_q = nullptr;
+    size_t sb = 0;
+    if (int rc = hvd_pdq_crops_scratch_bytes(batch, h, w, K, &sb)) return rc;
+    SCR(S_FRAMES, frame_bytes * batch, d_in);
+    SCR(S_FSCR, sb, d_scr);
+    SCR(S_HASH, 256 * (size_t)batch, d_h);
+    SCR(S_QUAL, 36 * (size_t)batch, d_q);  // int32[batch] of the full frame, then int32[batch][8] per slot
+    void* d_cq = (char*)d_q + 4 * (size_t)batch;
+    for (int64_t f0 = 0; f0 < n; f0 += batch) {
+        const int64_t m = std::min(batch, n - f0);
+        HIP_TRY(hipMemcpyAsync(d_in, frames + frame_bytes * f0, frame_bytes * m, hipMemcpyHostToDevice, g.stream));
+        if (int rc = hvd_dev_pdq_hash_frames_crops(d_in, m, h, w, channels, crops, K, d_scr, d_h, d_q, d_cq)) return rc;
+        HIP_TRY(hipMemcpyAsync(out_hashes8 + 256 * f0, d_h, 256 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipMemcpyAsync(out_quality + f0, d_q, 4 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
+        if (out_crop_quality)
+            HIP_TRY(hipMemcpyAsync(out_crop_quality + 8 * f0, d_cq, 32 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+    }
+    return HVD_OK;
+}
+
+int hvd_pdq_hash_frames_crops_gray_u8(const uint8_t* frames, int64_t n, int h, int w, const int32_t* crops, int K,
+                                      uint8_t* out_hashes8, int32_t* out_quality, int32_t* out_crop_quality) {
+    return hash_frames_crops_host(frames, n, h, w, 1, crops, K, out_hashes8, out_quality, out_crop_quality);
+}
+
+int hvd_pdq_hash_frames_crops_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, const int32_t* crops, int K,
+                                       uint8_t* out_hashes8, int32_t* out_quality, int32_t* out_crop_quality) {
+    return hash_frames_crops_host(frames, n, h, w, 3, crops, K, out_hashes8, out_quality, out_crop_quality);
+}
+
 // Content-rectangle hashing of host frames. Runs on the calling thread's current context, also under a device
 // group. Batches end on video boundaries, so a video's rectangle always sees all of its frames.
 static int hash_frames_autocrop_host(const uint8_t* frames, int64_t n, int h, int w, int channels, const int64_t* offsets,

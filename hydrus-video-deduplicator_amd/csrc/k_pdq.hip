@@ -1213,6 +1213,8 @@ hipError_t launch_pdq_hash64(const void* d_in, int kind, int64_t n, const float*
 
 // Workspace (floats per frame) the down-sampler needs besides the 64x64 output.
 size_t pdq_downsample_ws_floats(int h, int w) { return 2 * (size_t)h * w + (size_t)64 * h; }
+// ... and what the fused 512 x 512 forms need of it for n frames: k_down512w's state per wave, never more waves than frames
+size_t pdq_down512_ws_floats(int64_t n) { return (size_t)kWScratchFloats * (size_t)(n > 0 ? n : 0); }
 
 bool g_pdq_fused_down512 = true;  // A/B switch (hvd_debug_set "pdq_fused_down512")
 int g_pdq_down512_wave = 1;       // k_down512w (one wave per frame): 0 never, 1 for batches >= 704 frames, 2 always

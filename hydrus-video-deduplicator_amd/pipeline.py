@@ -168,6 +168,29 @@ def hash_frames_autocrop_on_device(d_frames_ptr: int, n: int, h: int, w: int, ch
     return d_h, d_q, d_r
 
 
+def hash_frames_crops_on_device(d_frames_ptr: int, n: int, h: int, w: int, channels: int, crops="aspect",
+                                crop_quality: bool = True):
+    """Crop-ladder form of `hash_frames_on_device`: -> (d_hashes8, d_quality, d_crop_quality, names)
+    DeviceBuffers (n*8*32 B in the dihedral layout: slot 0 the full frame, slots 1..K the crops of
+    vpdq.crop_ladder(h, w, crops) in list order, the rest zero; int32[n], the full frame's quality; int32[n*8] per slot) and
+    the crops' names. crop_quality=False: the per-slot qualities are not written and d_crop_quality is None. Enqueued on the
+    library stream; the scratch is freed after one hvd_dev_sync."""
+    lib = _lib.ensure()
+    names, rects = vpdq.crop_ladder(h, w, crops)
+    K = len(names)
+    with _DeviceScope() as scope:
+        d_h = scope.keep(DeviceBuffer(256 * max(n, 1)))
+        d_q = scope.keep(DeviceBuffer(4 * max(n, 1)))
+        d_cq = scope.keep(DeviceBuffer(32 * max(n, 1))) if crop_quality else None
+        sb = C.c_size_t(0)
+        _lib.check(lib.hvd_pdq_crops_scratch_bytes(n, h, w, K, C.byref(sb)))
+        d_s = scope.temp(DeviceBuffer(max(sb.value, 1)))
+        _lib.check(lib.hvd_dev_pdq_hash_frames_crops(d_frames_ptr, n, h, w, channels, rects.ctypes.data, K, d_s.ptr, d_h.ptr,
+                                                     d_q.ptr, d_cq.ptr if d_cq else None))
+        _lib.check(lib.hvd_dev_sync())  # the scratch must outlive the kernels
+    return d_h, d_q, d_cq, names
+
+
 def transform_mask(names) -> int:
     """Transform names (search.transform_set) -> the mask of hvd_dev_compact_kept_dihedral (bit t = vpdq.TRANSFORMS[t])."""
     return sum(1 << vpdq.TRANSFORMS.index(t) for t in names)
@@ -237,17 +260,33 @@ class DeviceLibrary:
         """Quality filter + CSR of the dihedral hashes (hvd_dev_compact_kept_dihedral). transforms: names as
         search.transform_set returns them (identity included). -> (identity library, the same as from_raw_hashes on the
         plain hashes; query set of the other variants, None when there are none)."""
+        return cls._from_raw_slots(d_hashes8_ptr, d_quality_ptr, n, raw_offsets, transform_mask(transforms),
+                                   tuple(t for t in transforms if t != "identity"), min_quality)
+
+    @classmethod
+    def from_raw_crops(cls, d_hashes8_ptr: int, d_quality_ptr: int, n: int, raw_offsets: np.ndarray, names,
+                       min_quality: int = vpdq.QUALITY_TOLERANCE) -> tuple["DeviceLibrary", "DeviceQueries | None"]:
+        """from_raw_dihedral for the crop-ladder hashes (hvd_dev_pdq_hash_frames_crops writes the dihedral layout: slot 0
+        the full frame, slot k + 1 crop names[k]): the same compaction with the slot mask (1 << (K + 1)) - 1. -> (identity
+        library; query set whose `transforms` are the crops' names, query video v * K + k for names[k])."""
+        names = tuple(names)
+        return cls._from_raw_slots(d_hashes8_ptr, d_quality_ptr, n, raw_offsets, (1 << (len(names) + 1)) - 1, names, min_quality)
+
+    @classmethod
+    def _from_raw_slots(cls, d_hashes8_ptr: int, d_quality_ptr: int, n: int, raw_offsets: np.ndarray, mask: int, cross: tuple,
+                        min_quality: int):
+        """hvd_dev_compact_kept_dihedral with a slot mask (bit t = slot t of the 8 hashes per frame, bit 0 set): the identity
+        library from slot 0, the query set from the other set bits in ascending order, named by `cross`."""
         lib = _lib.ensure()
         raw_offsets = _check_raw_offsets(raw_offsets, n)
         V = raw_offsets.size - 1
-        cross = [t for t in transforms if t != "identity"]
         K = len(cross)
         kept = C.c_int64(0)
         with _DeviceScope() as scope:
             d_roff, d_out_h, d_out_off, d_out_vid = _compaction_buffers(scope, raw_offsets, n)
             d_qh, d_qv, d_qx = (scope.keep(DeviceBuffer(size * K * max(n, 1))) if K else None for size in (32, 4, 4))
             _lib.check(lib.hvd_dev_compact_kept_dihedral(
-                d_hashes8_ptr, d_quality_ptr, n, d_roff.ptr, V, int(min_quality), transform_mask(transforms), d_out_h.ptr,
+                d_hashes8_ptr, d_quality_ptr, n, d_roff.ptr, V, int(min_quality), int(mask), d_out_h.ptr,
                 d_out_off.ptr, d_out_vid.ptr, d_qh.ptr if K else None, d_qv.ptr if K else None, d_qx.ptr if K else None,
                 C.byref(kept)))
         library = cls(d_out_h, d_out_off, d_out_vid, kept.value, V)
@@ -789,6 +828,48 @@ def dedupe_transformed_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarr
         return pairs, tid, sim, recs_i, recs_c, library
     library.free()
     return pairs, tid, sim, recs_i, recs_c, None
+
+
+def dedupe_cropped_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                    threshold: float = 50.0, policy: str | None = None, crops="aspect",
+                                    keep_library: bool = False, timings: dict | None = None):
+    """`dedupe_frames_on_device` that also finds aspect-ratio re-crops of the listed centre crops
+    (search.find_cropped_duplicates on frames in HBM; one device). Crop-ladder hash (the full frame and the K crops of every
+    frame in one call) -> quality filter + CSR of the identity library and of the query set of the crop
+    variants (hvd_dev_compact_kept_dihedral with the slot mask) -> FP4 images -> video search of the identity library ->
+    one cross search of the query set against it -> search.fold_cropped_records. crops: what vpdq.crop_ladder takes.
+    -> (duplicates: [search.CroppedDuplicate(a, b, crop, similarity, wide)], identity records, cross records, identity
+    library or None). timings (optional dict): hash_ms, search_ms and cross_ms (HIP events on the library stream),
+    gather_ms and compact_ms (host clock, as in dedupe_frames_on_device)."""
+    names, _ = vpdq.crop_ladder(h, w, crops)  # a bad list fails here, before any device work
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    timed = _stage_timer(timings)
+
+    def hash_stage(mine):
+        d_h, d_q, _, _ = timed("hash_ms", lambda: hash_frames_crops_on_device(d_frames_ptr, int(mine[-1]), h, w, channels, crops,
+                                                                                crop_quality=False))
+        return d_h, d_q
+
+    library, queries = _hashed_library(raw_offsets, 0, 1, None, hash_stage, 256,
+                                       lambda *raw: DeviceLibrary.from_raw_crops(*raw, names), timings)
+    try:
+        try:
+            # the identity records are read back before the cross search: emit-again state belongs to the last search only
+            recs_i = timed("search_ms", lambda: library.match_videos())
+            recs_c = timed("cross_ms", lambda: library.match_queries(queries))
+        finally:
+            if queries is not None:
+                queries.free()
+        folded = search.fold_cropped_records(recs_i, recs_c, library.lengths(), len(names), threshold, policy)
+    except BaseException:
+        library.free()
+        raise
+    dups = search.cropped_duplicates(*folded, names)
+    if keep_library:
+        return dups, recs_i, recs_c, library
+    library.free()
+    return dups, recs_i, recs_c, None
 
 
 def dedupe_transformed_frames_in_process(frames_of_rank, raw_offsets: np.ndarray, h: int, w: int, channels: int,

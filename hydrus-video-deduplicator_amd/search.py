@@ -270,18 +270,15 @@ def find_transformed_duplicates(variant_hashes, threshold: float = 50.0, policy:
     return [(int(a), int(b), vpdq.TRANSFORMS[int(t)]) for (a, b), t in zip(pairs, tid)]
 
 
-def transformed_pairs(ident: list, var: list, cross, threshold: float = 50.0, policy: str | None = None,
-                      matcher=None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
-    """The two searches of find_transformed_duplicates and their fold, on validated blobs: ident[v] the identity hash of
-    video v, var[v * K + k] its variant under cross[k] (K = len(cross) non-identity names), as long as ident[v].
-    matcher: object with match_videos / match_videos_cross (default: the GPU entry points of this module).
-    -> fold_transformed_records(..., return_similarity=True)."""
+def _variant_searches(ident: list, var: list, K: int, matcher=None):
+    """The two searches over a library and its variants: ident[v] the identity hash of video v, var[v * K + k] its k-th
+    variant, as long as ident[v]. The videos against each other, and every variant against the videos, a video never
+    against its own variants. -> (identity records, cross records (a = v * K + k, b = video), lengths)."""
     mv, mvc = (match_videos, match_videos_cross) if matcher is None else (matcher.match_videos, matcher.match_videos_cross)
-    K = len(cross)
     V = len(ident)
-    if V == 0:
-        return np.zeros((0, 2), np.int64), np.zeros(0, np.int64), np.zeros(0, np.float64)
     frames, offsets, lengths = pack_hashes(ident)
+    if V == 0:
+        return np.zeros(0, dtype=VMATCH_DTYPE), np.zeros(0, dtype=VMATCH_DTYPE), lengths
     max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
     recs_i = mv(frames, offsets, max_dist)
     if K:
@@ -290,8 +287,105 @@ def transformed_pairs(ident: list, var: list, cross, threshold: float = 50.0, po
         recs_c = mvc(frames_q, offsets_q, frames, offsets, ids_q=np.repeat(vids, K), ids_t=vids, max_dist=max_dist)
     else:
         recs_c = np.zeros(0, dtype=VMATCH_DTYPE)
+    return recs_i, recs_c, lengths
+
+
+def transformed_pairs(ident: list, var: list, cross, threshold: float = 50.0, policy: str | None = None,
+                      matcher=None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """The two searches of find_transformed_duplicates and their fold, on validated blobs: ident[v] the identity hash of
+    video v, var[v * K + k] its variant under cross[k] (K = len(cross) non-identity names), as long as ident[v].
+    matcher: object with match_videos / match_videos_cross (default: the GPU entry points of this module).
+    -> fold_transformed_records(..., return_similarity=True)."""
+    K = len(cross)
+    if len(ident) == 0:
+        return np.zeros((0, 2), np.int64), np.zeros(0, np.int64), np.zeros(0, np.float64)
+    recs_i, recs_c, lengths = _variant_searches(ident, var, K, matcher)
     return fold_transformed_records(recs_i, recs_c, lengths, [vpdq.TRANSFORMS.index(t) for t in cross], threshold, policy,
                                     return_similarity=True)
+
+
+# ------------------------------------------------------------------ crop-ladder duplicates (DESIGN 4.12) ------
+
+CroppedDuplicate = namedtuple("CroppedDuplicate", "a b crop similarity wide")
+
+
+def fold_cropped_records(records_identity: np.ndarray, records_cross: np.ndarray, lengths: np.ndarray, K: int,
+                         threshold: float = 50.0, policy: str | None = None) -> tuple[np.ndarray, ...]:
+    """The pair set of find_cropped_duplicates from its two searches (pure numpy; no device), the sibling of
+    fold_transformed_records.
+
+    records_identity: VMATCH records (a < b) of the videos against each other. records_cross: VMATCH records of the query
+    set -- video v under crop k of the K listed is query v * K + k -- against the videos (b). lengths: frames per video
+    (every variant of a video has the identity's frames). sim_T(A, B) is the largest similarity_of_records value of the
+    pair over the identity record and the cross records of both directions (A_k vs B, B_k vs A); a pair is kept if
+    int(sim_T) >= int(threshold). -> (pairs int64[m, 2] with a < b, sorted; crop int64[m]: 0 for the identity record, else
+    k + 1 of the crop that reached sim_T, the lowest on a tie; similarity float64[m]; wide int64[m]: the video whose
+    cropped variant matched -- the one that shows more of the scene --, the lower one on a tie, -1 for the identity)."""
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    lengths = np.asarray(lengths, dtype=np.int64)
+    V = lengths.size
+    K = int(K)
+    rc = np.asarray(records_cross)
+    if K == 0 and rc.size:
+        raise ValueError("cross records without crops")
+    va = rc["a"].astype(np.int64) // max(K, 1)
+    vrec = rc.copy()
+    vrec["a"] = va  # query index -> its video (same frame count)
+    sim_c = similarity_of_records(vrec, lengths, policy)
+    c_c = rc["a"].astype(np.int64) % max(K, 1) + 1
+    ri = np.asarray(records_identity)
+    sim_i = similarity_of_records(ri, lengths, policy)
+    vb = rc["b"].astype(np.int64)
+    lo = np.concatenate([ri["a"].astype(np.int64), np.minimum(va, vb)])
+    hi = np.concatenate([ri["b"].astype(np.int64), np.maximum(va, vb)])
+    sim = np.concatenate([sim_i, sim_c])
+    cid = np.concatenate([np.zeros(ri.size, np.int64), c_c])
+    wide = np.concatenate([np.full(ri.size, -1, np.int64), va])
+    key = lo * max(V, 1) + hi
+    order = np.lexsort((wide, cid, -sim, key))  # per key: largest similarity, then the lowest list index, then the lower wide
+    key, sim, cid, wide, lo, hi = key[order], sim[order], cid[order], wide[order], lo[order], hi[order]
+    first = np.ones(key.size, dtype=bool)
+    first[1:] = key[1:] != key[:-1]
+    keep = first & (sim.astype(np.int64) >= int(threshold))  # int() truncation as in fix_vpdq_similarity
+    pairs = np.stack([lo[keep], hi[keep]], axis=1).reshape(-1, 2)
+    return pairs, cid[keep], sim[keep], wide[keep]
+
+
+def cropped_duplicates(pairs, cid, sim, wide, names) -> list:
+    """fold_cropped_records' arrays -> [CroppedDuplicate(a, b, crop name or "identity", similarity, wide or None)]."""
+    labels = ("identity",) + tuple(names)
+    return [CroppedDuplicate(int(a), int(b), labels[int(c)], float(s), None if int(c) == 0 else int(wd))
+            for (a, b), c, s, wd in zip(pairs, cid, sim, wide)]
+
+
+def find_cropped_duplicates(variant_hashes, threshold: float = 50.0, policy: str | None = None, crops="aspect",
+                            matcher=None) -> list:
+    """find_potential_duplicates that also finds aspect-ratio re-crops and pan-and-scan copies of the LISTED centre crops.
+
+    variant_hashes[v]: the dict Vpdq.computeCroppedHashes returns for video v ("identity" and every name of
+    vpdq.crop_names(crops) -> VpdqHash or bytes, all with the identity's frames). Two searches, those of transformed_pairs:
+    the videos against each other, and every crop variant of every video against the videos, never a video against its own
+    variants. sim_T(A, B) is the maximum over the identity record and the cross records of both directions.
+    -> [CroppedDuplicate(a, b, crop, similarity, wide)] for every a < b with int(sim_T) >= int(threshold), sorted by (a, b).
+    crop: the rung that reached sim_T, or "identity"; on a tie the lowest list index wins (identity first), then the lower
+    wide. wide: the video whose cropped variant matched, i.e. the one that shows more of the scene; None for identity.
+    matcher: object with match_videos / match_videos_cross (default: the GPU entry points of this module)."""
+    names = vpdq.crop_names(crops, unique=True)
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    ident, var = [], []
+    for v, d in enumerate(variant_hashes):
+        missing = [t for t in ("identity",) + names if t not in d]
+        if missing:
+            raise ValueError(f"video {v} has no hash for crop(s) {missing}")
+        ident.append(hash_blob(d["identity"]))
+        vb = [hash_blob(d[t]) for t in names]
+        if any(len(b) != len(ident[-1]) for b in vb):
+            raise ValueError(f"video {v}: the variants must hash the same frames as the identity")
+        var.extend(vb)
+    recs_i, recs_c, lengths = _variant_searches(ident, var, len(names), matcher)
+    return cropped_duplicates(*fold_cropped_records(recs_i, recs_c, lengths, len(names), threshold, policy), names)
 
 
 # ------------------------------------------------------------------ excerpts: time-aligned matching (DESIGN 4.8) ------

@@ -545,6 +545,107 @@ def hash_frames_dihedral(frames: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
     return hashes, quality
 
 
+# Crop-ladder PDQ (include/hvd_mi355x.h): every frame hashed under the full frame and under a short list of
+# rectangles, so that an aspect-ratio re-crop ("crop to fill") matches its source under the rectangle it kept. A rung
+# (axis, num, den) keeps the centre (side * num) // den pixels of that axis and all of the other one; CROP_NAMES names the
+# listed rungs the way TRANSFORMS names the dihedral variants: 16:9 -> 4:3, 1:1, 9:16 on the width, the same on the height.
+CROP_RUNGS = {"w3/4": ("w", 3, 4), "w9/16": ("w", 9, 16), "w81/256": ("w", 81, 256),
+              "h3/4": ("h", 3, 4), "h9/16": ("h", 9, 16), "h81/256": ("h", 81, 256)}
+CROP_NAMES = tuple(CROP_RUNGS)
+CROP_SETS = {"landscape": CROP_NAMES[:3], "portrait": CROP_NAMES[3:], "aspect": CROP_NAMES}
+MAX_CROPS = 7  # HVD_MAX_CROPS
+
+
+def _crop_items(crops) -> list:
+    """`crops` as crop_ladder takes it -> [(name, rung or pixel rectangle)], in list order."""
+    if isinstance(crops, str):
+        if crops not in CROP_SETS:
+            raise ValueError(f"unknown crop set {crops!r}; expected one of {sorted(CROP_SETS)}, or a tuple of rungs "
+                             f"(names from {CROP_NAMES}, (axis, num, den)) or pixel rectangles (top, left, height, width)")
+        crops = CROP_SETS[crops]
+    items = []
+    for c in crops:
+        if isinstance(c, str):
+            if c not in CROP_RUNGS:
+                raise ValueError(f"unknown crop rung {c!r}; expected names from {CROP_NAMES}")
+            items.append((c, CROP_RUNGS[c]))
+            continue
+        c = tuple(c)
+        if len(c) == 3 and c[0] in ("w", "h"):
+            axis, num, den = c[0], int(c[1]), int(c[2])
+            if not 1 <= num <= den:
+                raise ValueError(f"crop rung {c!r}: need 1 <= num <= den")
+            items.append((f"{axis}{num}/{den}", (axis, num, den)))
+        elif len(c) == 4 and not isinstance(c[0], str):
+            rect = tuple(int(x) for x in c)
+            items.append(("r{},{},{},{}".format(*rect), rect))
+        else:
+            raise ValueError(f"crop {c!r} is neither a rung (axis, num, den) nor a rectangle (top, left, height, width)")
+    if not 1 <= len(items) <= MAX_CROPS:
+        raise ValueError(f"a crop list holds 1..{MAX_CROPS} crops, got {len(items)}")
+    return items
+
+
+def crop_names(crops="aspect", unique: bool = False) -> tuple:
+    """The names of a crop list, in list order (what crop_ladder(h, w, crops)[0] is at any geometry). unique=True: ValueError
+    if a crop is listed twice -- legal for the hashing entries, but a result keyed by name would hold one of the two."""
+    names = tuple(name for name, _ in _crop_items(crops))
+    if unique and len(set(names)) != len(names):
+        raise ValueError(f"a crop is listed twice in {names}: variants are keyed by name")
+    return names
+
+
+def crop_ladder(h: int, w: int, crops="aspect") -> tuple[tuple, np.ndarray]:
+    """(names, int32[K,4] = (top, left, height, width)) of a crop list in an h x w frame. crops: "landscape" (w3/4, w9/16,
+    w81/256: a 16:9 frame cut to 4:3, 1:1, 9:16), "portrait" (the same on the height), "aspect" (all six), or a tuple of
+    rung names, rungs (axis, num, den) and explicit pixel rectangles, taken as given (1..7 of them). A rung ("w", num, den)
+    keeps ww = (w * num) // den columns at left = (w - ww) // 2 and all rows; ("h", num, den) the same on the other axis.
+    ValueError for a rung whose kept side would be below 64 and for a rectangle that is not inside the frame with both
+    sides >= 64. Only these centre crops are found; an off-centre crop needs its explicit rectangle."""
+    h, w = int(h), int(w)
+    rects = []
+    for name, c in _crop_items(crops):
+        if len(c) == 3:
+            axis, num, den = c
+            if axis == "w":
+                ww = (w * num) // den
+                rect = (0, (w - ww) // 2, h, ww)
+            else:
+                hh = (h * num) // den
+                rect = ((h - hh) // 2, 0, hh, w)
+            if min(rect[2], rect[3]) < 64:
+                raise ValueError(f"crop rung {name} keeps {rect[2]} x {rect[3]} of a {h} x {w} frame: both sides must be >= 64")
+        else:
+            rect = c
+            top, left, hh, ww = rect
+            if top < 0 or left < 0 or hh < 64 or ww < 64 or top + hh > h or left + ww > w:
+                raise ValueError(f"crop rectangle {rect} must lie inside the {h} x {w} frame with both sides >= 64")
+        rects.append(rect)
+    return tuple(n for n, _ in _crop_items(crops)), np.array(rects, dtype=np.int32).reshape(-1, 4)
+
+
+def hash_frames_crops(frames: np.ndarray, crops="aspect") -> tuple[np.ndarray, np.ndarray, np.ndarray, tuple]:
+    """Crop-ladder counterpart of `hash_frames`: uint8[n,h,w] (gray) or uint8[n,h,w,3] (rgb24) -> (hashes uint8[n,K+1,32],
+    quality int32[n], crop_quality int32[n,K+1], names). Slot 0 is the full frame (hashes[:, 0] and quality equal
+    hash_frames(frames)), slot k + 1 the plain PDQ hash and quality of frames[f, top:top+height, left:left+width] under
+    crop k of `crop_ladder(h, w, crops)`; names[k] names it. No quality filtering. Both DCT modes."""
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8 or not (frames.ndim == 3 or (frames.ndim == 4 and frames.shape[3] == 3)):
+        raise ValueError("frames must be uint8[n,h,w] or uint8[n,h,w,3]")
+    frames = np.ascontiguousarray(frames)
+    n, h, w = frames.shape[:3]
+    names, rects = crop_ladder(h, w, crops)
+    K = len(names)
+    lib = _lib.ensure()
+    fn = lib.hvd_pdq_hash_frames_crops_gray_u8 if frames.ndim == 3 else lib.hvd_pdq_hash_frames_crops_rgb24_u8
+    hashes = np.zeros((n, 8, BYTES_PER_PDQ_HASH), dtype=np.uint8)
+    quality = np.zeros(n, dtype=np.int32)
+    crop_quality = np.zeros((n, 8), dtype=np.int32)
+    _lib.check(fn(frames.ctypes.data, n, h, w, rects.ctypes.data, K, hashes.ctypes.data, quality.ctypes.data,
+                  crop_quality.ctypes.data))
+    return np.ascontiguousarray(hashes[:, :K + 1]), quality, np.ascontiguousarray(crop_quality[:, :K + 1]), names
+
+
 def match_counts(a: bytes, b: bytes, distance_tolerance: int = 31) -> tuple[int, int]:
     """(q_hits, t_hits) for query a / target b, both concatenated 32-byte frame hashes."""
     a = bytes(a)

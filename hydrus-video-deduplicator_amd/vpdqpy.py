@@ -188,6 +188,21 @@ class Vpdq:
         return {t: VpdqHash(kept[:, vpdq.TRANSFORMS.index(t)].tobytes()) for t in names}
 
     @staticmethod
+    def computeCroppedHashes(frames, crops="aspect") -> dict:
+        """The video hashes of the video under the full frame and under every crop of `crops` (what ``vpdq.crop_ladder``
+        takes): {"identity": VpdqHash, "w3/4": VpdqHash, ...}, from one crop-ladder hashing call
+        (``vpdq.hash_frames_crops``). All variants keep the SAME frames: the quality filter (>= QUALITY_TOLERANCE) is
+        applied once, on the full frame's quality, as ``computeTransformedHashes`` does. ``["identity"]`` equals
+        ``computeHash(frames)``. frames: uint8[n,h,w] / uint8[n,h,w,3] array (the streaming form is not offered). The result
+        is keyed by name, so a crop listed twice is a ValueError here (``vpdq.hash_frames_crops`` takes it)."""
+        vpdq.crop_names(crops, unique=True)
+        if not isinstance(frames, np.ndarray):
+            raise ValueError("computeCroppedHashes needs the array form of the frames (uint8[n,h,w] or uint8[n,h,w,3])")
+        hashes, quality, _, names = vpdq.hash_frames_crops(frames, crops)
+        kept = hashes[quality >= vpdq.QUALITY_TOLERANCE]
+        return {name: VpdqHash(kept[:, k].tobytes()) for k, name in enumerate(("identity",) + tuple(names))}
+
+    @staticmethod
     def is_similar(vpdq_features1: VpdqHash, vpdq_features2: VpdqHash, threshold: float = 75.0) -> tuple[bool, float]:
         """Threshold is minimum similarity to be considered similar (vpdqpy.py:121-131)."""
         similarity = Vpdq.match_hash(query_features=vpdq_features1, target_features=vpdq_features2)

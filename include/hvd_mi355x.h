@@ -40,7 +40,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -201,6 +201,15 @@ int hvd_pdq_hash_frames_autocrop_gray_u8(const uint8_t* frames, int64_t n, int h
 int hvd_pdq_hash_frames_autocrop_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
                                           int black_level, int min_bright, uint8_t* out_hashes, int32_t* out_quality,
                                           int32_t* out_rects);
+/* Crop-ladder PDQ on host buffers (the rule: hvd_dev_pdq_hash_frames_crops below): every frame under the full frame and under
+ * the K crops of the caller's list. out_hashes8: n*8*32 bytes in the dihedral layout (slot 0 the full frame, slots 1..K the
+ * crops in list order, the rest zero); out_quality: int32[n], the full frame's; out_crop_quality: int32[n*8] per slot, or
+ * NULL. Frames are staged in batches as hvd_pdq_hash_frames_dihedral_* stages them. Under a device group the call runs on
+ * the calling thread's current context alone (same bytes as on one context). Both DCT modes. */
+int hvd_pdq_hash_frames_crops_gray_u8(const uint8_t* frames, int64_t n, int h, int w, const int32_t* crops, int K,
+                                      uint8_t* out_hashes8, int32_t* out_quality, int32_t* out_crop_quality);
+int hvd_pdq_hash_frames_crops_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, const int32_t* crops, int K,
+                                       uint8_t* out_hashes8, int32_t* out_quality, int32_t* out_crop_quality);
 
 /* Replaces the O(visited nodes) stream of vpdq.matchHashBytes calls issued by the
  * VP-tree (db/vptree.py:29-31,737; dedup.py:445-502) with one brute-force pass:
@@ -502,6 +511,25 @@ int hvd_pdq_rects_scratch_bytes(int64_t n, int h, int w, int channels, size_t* o
  * knows all its rectangles are full calls hvd_dev_pdq_hash_frames instead (same bits, fused 512x512 kernels). Both DCT modes. */
 int hvd_dev_pdq_hash_frames_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets,
                                   int64_t V, const void* d_rects, void* d_scratch, void* d_hashes, void* d_quality);
+
+/* ---- crop-ladder PDQ: aspect-ratio re-crops and pan-and-scan copies hash like the original under the same rectangle
+ * A crop is int32[4] = {top, left, height, width} in pixels of the call's h x w frame; it is valid iff it lies inside the frame
+ * and both sides are >= 64. The full frame is a valid crop, duplicates are allowed, a call takes 1 <= K <= HVD_MAX_CROPS crops
+ * in HOST memory (they travel as kernel arguments). Anything else is HVD_ERR_ARG, decided before a device is asked for: a
+ * caller's list is an argument, not data (hvd_dev_pdq_hash_frames_rects, whose rectangles are data, substitutes the full frame).
+ * The hash and quality of a frame under a crop are the plain PDQ hash and quality of the contiguous height x width crop (a
+ * 64 x 64 crop: of its unfiltered luma). Output, the dihedral layout, so that hvd_dev_compact_kept_dihedral with the mask
+ * (1 << (K + 1)) - 1 serves as it is: d_hashes8 n*8*32 bytes, hash of frame f in slot k at bytes [(8f+k)*32, (8f+k+1)*32), slot
+ * 0 the full frame (bit-identical to hvd_dev_pdq_hash_frames), slots 1..K the crops in list order, slots above K zero;
+ * d_quality int32[n], the full frame's; d_crop_quality int32[n*8] per slot (0 above K), or NULL. Frames up to 512 x 512 go
+ * through one kernel that loops over the rectangles of a frame (at exactly 512 x 512 the full frame is hashed by the plain
+ * front-end instead, so such a frame is read twice); larger ones take the generic passes once per rectangle. d_scratch:
+ * hvd_pdq_crops_scratch_bytes(n, h, w, K) bytes, 16-byte aligned; bounded, the frames are taken in slabs. d_hashes8, d_quality
+ * and d_crop_quality: 4-byte aligned. Enqueued on the library stream, no host synchronisation. n == 0 is legal. Both DCT modes. */
+#define HVD_MAX_CROPS 7
+int hvd_pdq_crops_scratch_bytes(int64_t n, int h, int w, int K, size_t* out_bytes);
+int hvd_dev_pdq_hash_frames_crops(const void* d_frames, int64_t n, int h, int w, int channels, const int32_t* crops, int K,
+                                  void* d_scratch, void* d_hashes8, void* d_quality, void* d_crop_quality);
 
 /* Brute-force pass over the tiles owned by `rank` of `world` (tile (rb,cb) belongs
  * to rank (rb+cb) % world; world=1 => everything). Appends hvd_pair records to
