@@ -406,9 +406,7 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
         if (lane >= (uint32_t)d) incl += y;
     }
     const int delta = (int)sstart - (int)(incl - ssize);  // position = p + delta for an entry p of this segment
-    uint32_t ends[16];
-#pragma unroll
-    for (int s = 0; s < 16; ++s) ends[s] = (uint32_t)__builtin_amdgcn_readlane((int)incl, s);
+    // (segment s ends at the incl of lane s, the last one, 16, at ny; the lanes above hold ny too)
     const uint32_t ny = (uint32_t)__builtin_amdgcn_readlane((int)incl, 16);
     const size_t base = (size_t)b * a.n;
     const uint32_t* __restrict__ hb = a.hw + base;
@@ -426,11 +424,12 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
     auto drain = [&](uint32_t cnt) {
         __builtin_amdgcn_wave_barrier();  // (the pushes are in LDS before the entries are read)
         bool emit = false;
-        uint32_t d = 0, i = 0, j = 0;
+        uint32_t d = 0, ri = 0, rj = 0, dw[8];
         if (lane < cnt) {
             const uint2 e = queue[(qh + lane) & (kQueue - 1u)];
-            const uint32_t ri = rowb[e.x], rj = rowb[e.y];
-            uint32_t wx[8], wy[8], dw[8];
+            ri = rowb[e.x];
+            rj = rowb[e.y];
+            uint32_t wx[8], wy[8];
             load_words(a.db, ri, wx);
             load_words(a.db, rj, wy);
 #pragma unroll
@@ -439,16 +438,19 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
                 d += (uint32_t)__popc(dw[k]);
             }
             emit = d <= a.max_dist;
+        }
+        qh += cnt;
+        // ownership and the group filter only when some lane of the wave is within max_dist (wave-uniform): about one
+        // survivor in seven thousand is on uniform hashes, so almost every drain ends here, after the eight popcounts
+        if (!__any(emit)) return;
+        if (emit) {
             uint32_t qual = 0;  // bit b2: block b2 qualifies -- its keys are within r and its word within tw
 #pragma unroll
             for (uint32_t b2 = 0; b2 < kBlocks; ++b2)
                 qual |= (uint32_t)__popc(key_of(dw, b2)) <= a.r && (int32_t)((uint32_t)__popc(dw[b2 >> 1]) + kfail) >= 0 ? 1u << b2 : 0u;
             if ((qual & ((1u << b) - 1u)) != 0u) emit = false;  // an earlier qualifying block owns this pair
             if (emit && a.group != nullptr && a.group[ri] == a.group[rj]) emit = false;
-            i = min(ri, rj);
-            j = max(ri, rj);
         }
-        qh += cnt;
         const unsigned long long em = __ballot(emit);
         const uint32_t m = (uint32_t)__popcll(em);
         if (m == 0u) return;
@@ -459,8 +461,8 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
         if (emit) {
             const uint32_t slot = fill + __builtin_amdgcn_mbcnt_hi((uint32_t)(em >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)em, 0u));
             hvd_pair rec;
-            rec.i = i;
-            rec.j = j;
+            rec.i = min(ri, rj);
+            rec.j = max(ri, rj);
             rec.dist = d;
             rec.pad = 0;
             buf[slot] = rec;
@@ -487,32 +489,42 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
             if (qt - qh >= 64u) drain(64u);
         }
     };
-    // entry p of the y list: its segment and its position inside block b
-    auto locate = [&](uint32_t p, uint32_t* seg) {
-        uint32_t sg = 0;
-#pragma unroll
-        for (int s = 0; s < 16; ++s) sg += p >= ends[s] ? 1u : 0u;
-        *seg = sg;
-        return (uint32_t)((int)p + __shfl(delta, (int)sg));
+    // The position inside block b of the entries q0 + lane of the y list, for the rounds in their order. A round touches a
+    // short run of consecutive segments, and that run only moves forward: cs (wave-uniform) is the first segment that does
+    // not end below the round's first entry, ce its end, read from the lane that holds it. A lane's segment is cs plus
+    // the segments from cs on that end at or below its entry: one compare and one add per segment that ends inside the
+    // round, whatever its size (an empty one too), and one scalar compare for a round inside a long segment.
+    uint32_t cs = 0, ce = nu;
+    auto locate = [&](uint32_t q0) {
+        const uint32_t p = q0 + lane;
+        asm volatile("" : "+s"(cs));  // (the cursor stays in a scalar register from round to round)
+        const uint32_t c0 = cs;
+        uint32_t past = 0;
+        while (ce < min(q0 + 64u, ny)) {  // (an end below ny belongs to a segment below 16; entries from ny on are not used)
+            past += p >= ce ? 1u : 0u;
+            ++cs;
+            ce = (uint32_t)__builtin_amdgcn_readlane((int)incl, (int)cs);
+        }
+        return (uint32_t)((int)p + __shfl(delta, (int)(c0 + past)));
     };
-    uint32_t seg, ypos = locate(lane, &seg);
+    uint32_t ypos = locate(0u);
     uint32_t yw = 0u;
     if (lane < ny) yw = hb[ypos];
     uint32_t p0 = 0;
     do {  // (ny >= nu > 0: at least one round)
         const uint32_t p = p0 + lane;
-        uint32_t seg_n;
-        const uint32_t ypos_n = locate(p + 64u, &seg_n);
-        asm volatile("" ::"v"(yw));  // (this round's y has arrived before the next one's load is issued)
-        uint32_t yw_n = 0u;
-        if (p + 64u < ny) yw_n = hb[ypos_n];  // the next round's y: in flight under this round's x loop
-        // x index k pairs with this y iff k < ylim: inside the bucket only the x before it (positions i < j)
-        const uint32_t ylim = p >= ny ? 0u : seg == 0u ? p : nu;
+        uint32_t ypos_n = 0u, yw_n = 0u;
+        if (p0 + 64u < ny) {  // (wave-uniform: the last round looks for nothing)
+            ypos_n = locate(p0 + 64u);
+            asm volatile("" ::"v"(yw));  // (this round's y has arrived before the next one's load is issued)
+            if (p + 64u < ny) yw_n = hb[ypos_n];  // the next round's y: in flight under this round's x loop
+        }
+        // x index k pairs with this y iff k < ylim: inside the bucket (the first nu entries) only the x before it (positions i < j)
+        const uint32_t ylim = p >= ny ? 0u : min(p, nu);
         for (uint32_t k0 = 0; k0 < nu; k0 += kXB) {
             const u32x16 x = *(kx16*)(xb + k0);
             batch(x, k0, yw, ypos, ylim);
         }
-        seg = seg_n;
         ypos = ypos_n;
         yw = yw_n;
         p0 += 64u;
@@ -590,18 +602,20 @@ IndexRule index_rule(const AllPairsArgs& a, uint32_t r) {
     q.r = r;
     q.force = g_allpairs_index == 1 ? 1u : 0u;
     q.world = a.world;
-    // (DESIGN 4.1, 1 M uniform hashes on MI355X: form 9 18.1 ms = 36 fs per comparison, forms 18 / 12 +4 / +11 %; join 2.0 ms
-    // for 2.075e9 candidates; the counting sort, the statistics and the place pass 0.93 ms, of which ~0.03 ms do not depend
-    // on n (the scans over 4096 partitions, the grid of 6144 chunks): 0.9 ns per hash, and those 30 us next to the 40 us of
-    // launches; the longest work item's wave takes ~30 ns per step of 64 pairs. These are the figures of the full-width
-    // index with the LDS-staged join: the word index (place without a gather) and the word join have not been profiled yet,
-    // so ps_cand and ps_hash are the old, costlier ones -- the rule can only be too cautious about the index until they are
-    // re-derived: ps_cand = join time / candidates, ps_hash = (every kernel between probe and join - 30 us) / n)
+    // (DESIGN 4.1, 1 M uniform hashes on MI355X: form 9 18.1 ms = 36 fs per comparison, forms 18 / 12 +4 / +11 %. From the
+    // kernel trace of the word index (profiles/r15_index_kernel_stats_after.csv): join 0.880 ms for 2.075e9 candidates =
+    // 0.42 ps each; the counting sort, the statistics and the place pass -- every kernel between probe and join -- 0.356 ms,
+    // of which ~0.03 ms do not depend on n (the scans over 4096 partitions, the grid of 6144 chunks): 0.33 ns per hash, and
+    // those 30 us next to the 40 us of launches. To re-derive after a change of these kernels: ps_cand = join time /
+    // candidates, ps_hash = (every kernel between probe and join - 30 us) / n, ps_crit from the crowded DB of
+    // scripts/gpu_index_join_time.py (profiles/r15_index_join_time.jsonl): 200 000 hashes, 5 000 of them in one bucket, a
+    // longest walk of 25.15e6 pairs, 8.83 ms per call of which ~0.2 ms are what the other terms price and ~0.4 ms copies:
+    // 0.33 ns per pair, 21 ns per step of 64 -- rounded up, which errs towards the matrix cores)
     q.fs_mfma_fetch = 36.0f;
     q.fs_mfma_other = 40.0f;
-    q.ps_cand = 1.0f;
-    q.ps_hash = 900.0f;
-    q.ps_crit = 500.0f;
+    q.ps_cand = 0.43f;
+    q.ps_hash = 330.0f;
+    q.ps_crit = 350.0f;
     q.fixed_ns = 70000.0f;
     return q;
 }
