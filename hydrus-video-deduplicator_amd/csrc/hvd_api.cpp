@@ -26,6 +26,7 @@
 #include <thread>
 #include <vector>
 
+#include "hvd_hash_host.h"
 #include "hvd_internal.h"
 #include "../../include/hvd_mi355x_bench.h"
 
@@ -47,6 +48,7 @@ bool g_group_rccl = false;
 bool g_group_was_rccl = false;
 thread_local bool t_agreed_exit = false;
 int g_match_server = 1;
+int64_t g_hash_staging_bytes = 0;
 thread_local int t_ctx = 0;
 std::mutex g_mu;
 HostExchange g_hx;
@@ -679,6 +681,11 @@ int hvd_debug_set(const char* key, int value) {
         hvd::g_allpairs_index_fail = value;
         return HVD_OK;
     }
+    if (strcmp(key, "hash_staging_bytes") == 0) {  // tests only: frames staged per batch by the host-buffer hashing entries; 0 = 1 GiB
+        if (value != 0 && value < 4096) return fail(HVD_ERR_ARG, "hash_staging_bytes: 0 (the default, 1 GiB) or >= 4096");
+        g_hash_staging_bytes = value;
+        return HVD_OK;
+    }
     if (strcmp(key, "vmatch_fail_rank") == 0) {  // tests only (include/hvd_mi355x_bench.h): rank (value - 1) fails before the key exchange; 0 = off
         for (int k = 0; k < g_nctx; ++k) g_ctx[k].v_fail_rank = value;
         return HVD_OK;
@@ -798,73 +805,40 @@ int hvd_debug_get(const char* key, int* out_value) {
 }
 
 int hvd_pdq_scratch_bytes(int64_t n, int h, int w, int channels, size_t* out_bytes) {
-    if (!out_bytes || n < 0 || h < 64 || w < 64 || (channels != 1 && channels != 3))
+    // (no upper bound on the sides, unlike every hashing entry: kept as it has always been)
+    if (!out_bytes || n < 0 || h < hvd::kMinSide || w < hvd::kMinSide || !hvd::channels_ok(channels))
         return fail(HVD_ERR_ARG, "bad frame geometry");
-    if (h == 64 && w == 64 && channels == 1) {
-        *out_bytes = 0;
-    } else if (h == 64 && w == 64) {
-        *out_bytes = sizeof(float) * 4096 * (size_t)n;
-    } else {
-        const size_t cnt = (size_t)(n < 1024 ? n : 1024);
-        *out_bytes = sizeof(float) * (4096 * (size_t)n + cnt * hvd::pdq_downsample_ws_floats(h, w));
-    }
+    *out_bytes = hvd::HashScratch(n, h, w, channels, false).total;
     return HVD_OK;
 }
 
-}  // extern "C" (the helpers below have C++ linkage; hvd_stream.cpp uses them)
+}  // extern "C" (the helpers below have C++ linkage: hvd_hash_host.h)
 
 namespace hvd {
-size_t api_scratch_bytes(int64_t n, int h, int w, int channels) {
-    size_t b = 0;
-    (void)hvd_pdq_scratch_bytes(n, h, w, channels, &b);
-    return b;
-}
-
-// Enqueue the PDQ kernels for one batch on stream s (geometry already validated). dihedral: the 8-hash kernel
-// (k_pdq_dihedral.hip, d_hashes n*8*32 bytes) behind the same front-ends.
-static hipError_t launch_hash_any(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
-                                  void* d_quality, hipStream_t s, bool dihedral) {
-    auto hash64 = [&](const void* in, int kind) {
-        return dihedral ? launch_pdq_dihedral64(in, kind, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s)
-                        : launch_pdq_hash64(in, kind, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s);
-    };
-    if (h == 64 && w == 64 && channels == 1) return hash64(d_frames, 0);
-    hipError_t e;
-    float* out64 = (float*)d_scratch;
-    if (h == 64 && w == 64)
-        e = launch_pdq_luma64_rgb((const uint8_t*)d_frames, n, out64, s);
-    else
-        e = launch_pdq_downsample((const uint8_t*)d_frames, n, h, w, channels, out64 + (size_t)n * 4096, out64, s);
-    if (e != hipSuccess) return e;
-    return hash64(d_scratch, 1);
-}
-
 hipError_t api_launch_hash(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
                            void* d_quality, hipStream_t s, bool dihedral) {
-    return launch_hash_any(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, s, dihedral);
+    const auto hash64 = dihedral ? launch_pdq_dihedral64 : launch_pdq_hash64;  // (kind 0: u8 gray frames, 1: float planes)
+    if (!needs_scratch(h, w, channels)) return hash64(d_frames, 0, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s);
+    const HashScratch lay(n, h, w, channels, false);
+    float* out64 = (float*)((char*)d_scratch + lay.planes);
+    hipError_t e = h == 64 && w == 64 ? launch_pdq_luma64_rgb((const uint8_t*)d_frames, n, out64, s)
+                                      : launch_pdq_downsample((const uint8_t*)d_frames, n, h, w, channels,
+                                                              (float*)((char*)d_scratch + lay.ws), out64, s);
+    if (e != hipSuccess) return e;
+    return hash64(out64, 1, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s);
 }
 
-size_t api_rects_scratch_bytes(int64_t n, int h, int w, int channels) {
-    size_t b = 0;
-    (void)hvd_pdq_rects_scratch_bytes(n, h, w, channels, &b);
-    return b;
-}
-
-// The launch chain of hvd_dev_pdq_hash_frames_rects on stream s (arguments already validated, n > 0): frame -> rectangle
-// table, down-sampler inside the rectangles, K1. Scratch layout: hvd_pdq_rects_scratch_bytes.
 hipError_t api_launch_hash_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
                                  const void* d_rects, void* d_scratch, void* d_hashes, void* d_quality, hipStream_t s) {
     // 64x64 frames: every rectangle is the full frame by the rule (an axis shorter than 64 keeps its full extent)
-    if (h == 64 && w == 64) return launch_hash_any(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, s, false);
-    float* out64 = (float*)d_scratch;
-    const size_t cnt = (size_t)(n < 1024 ? n : 1024);
-    float* ws = out64 + (size_t)n * 4096;
-    const size_t geom_at = (sizeof(float) * (4096 * (size_t)n + cnt * pdq_downsample_ws_floats(h, w)) + 15) / 16 * 16;
-    void* geom = (char*)d_scratch + geom_at;  // (hvd_pdq_rects_scratch_bytes rounds the same way)
+    if (h == 64 && w == 64) return api_launch_hash(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, s, false);
+    const HashScratch lay(n, h, w, channels, true);
+    char* base = (char*)d_scratch;
     hipError_t e = launch_pdq_downsample_rects((const uint8_t*)d_frames, n, h, w, channels, (const long long*)d_offsets,
-                                               (uint32_t)V, (const int32_t*)d_rects, geom, ws, out64, s);
+                                               (uint32_t)V, (const int32_t*)d_rects, base + lay.table, (float*)(base + lay.ws),
+                                               (float*)(base + lay.planes), s);
     if (e != hipSuccess) return e;
-    return launch_pdq_hash64(d_scratch, 1, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s);
+    return launch_pdq_hash64(base + lay.planes, 1, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s);
 }
 }  // namespace hvd
 
@@ -873,17 +847,14 @@ extern "C" {
 static int dev_hash_frames(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
                            void* d_quality, bool dihedral) {
     if (int rc = need_ready()) return rc;
-    if (n < 0 || h < 64 || w < 64 || (channels != 1 && channels != 3))
-        return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d channels=%d (need h,w >= 64)", (long long)n, h,
-                    w, channels);
-    if (h > 4096 || w > 4096) return fail(HVD_ERR_ARG, "frames larger than 4096 px per side are not supported");
-    if (dihedral && hvd::g_pdq_dct_mode != 0)
-        return fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");
+    if (n < 0) return fail(HVD_ERR_ARG, "bad frame count n=%lld", (long long)n);
+    if (int rc = hvd::check_geometry(h, w, channels)) return rc;
+    if (int rc = hvd::check_dihedral_dct(dihedral)) return rc;
     if (n == 0) return HVD_OK;
     if (!d_frames || !d_hashes || !d_quality) return fail(HVD_ERR_ARG, "NULL device pointer");
-    const bool need_scratch = !(h == 64 && w == 64 && channels == 1);
-    if (need_scratch && !d_scratch) return fail(HVD_ERR_ARG, "d_scratch (hvd_pdq_scratch_bytes) is required unless 64x64 gray");
-    HIP_TRY(hvd::launch_hash_any(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, g.stream, dihedral));
+    if (hvd::needs_scratch(h, w, channels) && !d_scratch)
+        return fail(HVD_ERR_ARG, "d_scratch (hvd_pdq_scratch_bytes) is required unless 64x64 gray");
+    HIP_TRY(hvd::api_launch_hash(d_frames, n, h, w, channels, d_scratch, d_hashes, d_quality, g.stream, dihedral));
     return HVD_OK;
 }
 
@@ -900,10 +871,8 @@ int hvd_dev_pdq_hash_frames_dihedral(const void* d_frames, int64_t n, int h, int
 /* ---- content-rectangle PDQ (k_autocrop.hip) ---- */
 
 static int rects_geometry(int64_t n, int h, int w, int channels, int64_t V) {
-    if (n < 0 || h < 64 || w < 64 || h > 4096 || w > 4096 || (channels != 1 && channels != 3))
-        return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d channels=%d (need h,w in [64,4096])", (long long)n, h, w,
-                    channels);
-    if (V < 0 || V >= (1ll << 31) || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad counts n=%lld V=%lld", (long long)n, (long long)V);
+    if (int rc = hvd::check_geometry(h, w, channels)) return rc;
+    if (n < 0 || V < 0 || V >= (1ll << 31) || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad counts n=%lld V=%lld", (long long)n, (long long)V);
     if (n > 0 && V == 0) return fail(HVD_ERR_ARG, "n=%lld frames in no video", (long long)n);
     return HVD_OK;
 }
@@ -912,8 +881,7 @@ int hvd_dev_content_rects(const void* d_frames, int64_t n, int h, int w, int cha
                           int black_level, int min_bright, void* d_rects) {
     if (int rc = need_ready()) return rc;
     if (int rc = rects_geometry(n, h, w, channels, V)) return rc;
-    if (black_level < 0 || black_level > 254) return fail(HVD_ERR_ARG, "black_level=%d: need 0..254", black_level);
-    if (min_bright < 1) return fail(HVD_ERR_ARG, "min_bright=%d: need >= 1", min_bright);
+    if (int rc = hvd::check_autocrop_levels(black_level, min_bright)) return rc;
     if (V == 0) return HVD_OK;
     if (!d_offsets || !d_rects || (n > 0 && !d_frames)) return fail(HVD_ERR_ARG, "NULL device pointer");
     if ((uintptr_t)d_rects & 15u) return fail(HVD_ERR_ARG, "d_rects must be 16-byte aligned (hvd_dev_malloc's are)");
@@ -923,11 +891,9 @@ int hvd_dev_content_rects(const void* d_frames, int64_t n, int h, int w, int cha
 }
 
 int hvd_pdq_rects_scratch_bytes(int64_t n, int h, int w, int channels, size_t* out_bytes) {
-    if (!out_bytes || n < 0 || h < 64 || w < 64 || h > 4096 || w > 4096 || (channels != 1 && channels != 3))
-        return fail(HVD_ERR_ARG, "bad frame geometry");
-    if (int rc = hvd_pdq_scratch_bytes(n, h, w, channels, out_bytes)) return rc;
-    // frame -> rectangle table (int4 per frame) behind the workspace, at the next multiple of 16 bytes
-    if (!(h == 64 && w == 64)) *out_bytes = (*out_bytes + 15) / 16 * 16 + hvd::pdq_rects_geom_bytes(n);
+    if (!out_bytes || n < 0) return fail(HVD_ERR_ARG, "bad frame geometry");
+    if (int rc = hvd::check_geometry(h, w, channels)) return rc;
+    *out_bytes = hvd::HashScratch(n, h, w, channels, true).total;
     return HVD_OK;
 }
 
@@ -937,8 +903,7 @@ int hvd_dev_pdq_hash_frames_rects(const void* d_frames, int64_t n, int h, int w,
     if (int rc = rects_geometry(n, h, w, channels, V)) return rc;
     if (n == 0) return HVD_OK;
     if (!d_frames || !d_offsets || !d_rects || !d_hashes || !d_quality) return fail(HVD_ERR_ARG, "NULL device pointer");
-    const bool need_scratch = !(h == 64 && w == 64 && channels == 1);
-    if (need_scratch && !d_scratch)
+    if (hvd::needs_scratch(h, w, channels) && !d_scratch)
         return fail(HVD_ERR_ARG, "d_scratch (hvd_pdq_rects_scratch_bytes) is required unless 64x64 gray");
     if (((uintptr_t)d_rects | (uintptr_t)d_scratch) & 15u)
         return fail(HVD_ERR_ARG, "d_rects and d_scratch must be 16-byte aligned (hvd_dev_malloc's are)");
@@ -949,9 +914,9 @@ int hvd_dev_pdq_hash_frames_rects(const void* d_frames, int64_t n, int h, int w,
 /* ---- crop-ladder PDQ (k_crops.hip) ---- */
 
 // what needs no device: the frame geometry and the caller's list
-static int crops_arguments(int64_t n, int h, int w, const int32_t* crops, int K) {
-    if (n < 0 || n >= (1ll << 31) || h < 64 || w < 64 || h > 4096 || w > 4096)
-        return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d (need h,w in [64,4096])", (long long)n, h, w);
+static int crops_arguments(int64_t n, int h, int w, int channels, const int32_t* crops, int K) {
+    if (n < 0 || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad frame count n=%lld", (long long)n);
+    if (int rc = hvd::check_geometry(h, w, channels)) return rc;
     if (K < 1 || K > HVD_MAX_CROPS) return fail(HVD_ERR_ARG, "K=%d crops: need 1..%d", K, HVD_MAX_CROPS);
     if (!crops) return fail(HVD_ERR_ARG, "NULL crop list");
     if (!hvd::crops_valid(crops, K, h, w))
@@ -960,7 +925,7 @@ static int crops_arguments(int64_t n, int h, int w, const int32_t* crops, int K)
 }
 
 int hvd_pdq_crops_scratch_bytes(int64_t n, int h, int w, int K, size_t* out_bytes) {
-    if (!out_bytes || n < 0 || n >= (1ll << 31) || h < 64 || w < 64 || h > 4096 || w > 4096 || K < 1 || K > HVD_MAX_CROPS)
+    if (!out_bytes || n < 0 || n >= (1ll << 31) || !hvd::sides_ok(h, w) || K < 1 || K > HVD_MAX_CROPS)
         return fail(HVD_ERR_ARG, "bad frame geometry or crop count");
     *out_bytes = hvd::pdq_crops_scratch_bytes(n, h, w, K);
     return HVD_OK;
@@ -968,8 +933,7 @@ int hvd_pdq_crops_scratch_bytes(int64_t n, int h, int w, int K, size_t* out_byte
 
 int hvd_dev_pdq_hash_frames_crops(const void* d_frames, int64_t n, int h, int w, int channels, const int32_t* crops, int K,
                                   void* d_scratch, void* d_hashes8, void* d_quality, void* d_crop_quality) {
-    if (int rc = crops_arguments(n, h, w, crops, K)) return rc;
-    if (channels != 1 && channels != 3) return fail(HVD_ERR_ARG, "channels=%d: need 1 or 3", channels);
+    if (int rc = crops_arguments(n, h, w, channels, crops, K)) return rc;
     if (int rc = need_ready()) return rc;
     if (n == 0) return HVD_OK;
     if (!d_frames || !d_scratch || !d_hashes8 || !d_quality) return fail(HVD_ERR_ARG, "NULL device pointer");

@@ -71,7 +71,7 @@ struct Ctx {
         S_DB, S_IMG, S_GRP, S_PAIRS, S_DB2, S_IMG2, S_GRP2, S_VIDQ, S_VIDT, S_OFF, S_SET, S_SET2, S_PKEYS, S_PCNT, S_LIST,
         S_LISTALL, S_VOUT, S_FRAMES, S_FSCR, S_HASH, S_QUAL, S_COMPACT, S_COUNTERS, S_BITS, S_BITS2, S_BROWS, S_BCOOC, S_BITS_O, S_BITS2_O,
         S_IMG_O, S_IMG2_O, S_RECTS, S_OFF2, S_POSQ, S_POST, S_APAIRS, S_AOUT, S_ASCR, S_GREC, S_GLEN, S_GSCORE, S_GSCR, S_GLABEL,
-        S_GOUT, S_N
+        S_GOUT, S_CQUAL, S_N
     };
     void* scr[S_N] = {};
     size_t scr_cap[S_N] = {};
@@ -91,6 +91,7 @@ extern bool g_group_rccl;          // the group's contexts hold communicators of
 extern bool g_group_was_rccl;      // ... did when the group was formed (hvd_group_rearm re-creates aborted communicators)
 extern thread_local bool t_agreed_exit;  // this context left its last group call through an agreement step, in lock-step with its peers
 extern int g_match_server;         // hvd_debug_set "match_server"
+extern int64_t g_hash_staging_bytes;  // hvd_debug_set "hash_staging_bytes": frames staged per batch of a host-buffer hashing entry; 0 = 1 GiB
 extern thread_local int t_ctx;     // the calling thread's current context
 #define g (hvdi::g_ctx[hvdi::t_ctx])
 extern std::mutex g_mu;

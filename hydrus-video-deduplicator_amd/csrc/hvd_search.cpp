@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "hvd_hash_host.h"
 #include "hvd_internal.h"
 #include "../../include/hvd_mi355x_bench.h"
 
@@ -47,6 +48,45 @@ int copy_out(std::vector<T>& recs, int64_t total, bool (*less)(const T&, const T
 
 extern "C" {
 
+// Frames one batch of a host-buffer hashing entry stages on the device: <= ~1 GiB of them (hvd_debug_set "hash_staging_bytes"
+// lowers the limit so that tests reach the multi-batch paths at small shapes), at least one.
+static int64_t staging_frames(size_t frame_bytes) {
+    const size_t limit = g_hash_staging_bytes ? (size_t)g_hash_staging_bytes : (size_t)1 << 30;
+    return std::max<int64_t>(1, (int64_t)(limit / frame_bytes));
+}
+
+// One per-frame output of a host-buffer hashing entry: `bytes` per frame, from a pool slot of its own to `host` (NULL: not wanted)
+struct FrameOut {
+    void* host;
+    Ctx::Scr slot;
+    size_t bytes;
+};
+
+// The batch loop of the host-buffer hashing entries (arguments validated, n > 0): stage at most staging_frames() frames, size
+// the pool for that batch once, then per batch upload, enqueue(d_in, m, d_scratch, d_out[]) -- the device entry; d_out[k] is
+// outs[k]'s buffer --, download every output and synchronise. scratch_bytes(batch) = 0: the entry needs no scratch (NULL).
+static int hash_in_batches(const uint8_t* frames, int64_t n, size_t frame_bytes, const std::function<size_t(int64_t)>& scratch_bytes,
+                           std::initializer_list<FrameOut> outs,
+                           const std::function<int(const void*, int64_t, void*, void* const*)>& enqueue) {
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    const int64_t batch = std::min(n, staging_frames(frame_bytes));
+    void *d_in = nullptr, *d_scr = nullptr, *d_out[4] = {};
+    SCR(S_FRAMES, frame_bytes * batch, d_in);
+    if (const size_t sb = scratch_bytes(batch)) SCR(S_FSCR, sb, d_scr);
+    const FrameOut* out = outs.begin();
+    for (size_t k = 0; k < outs.size(); ++k)
+        if (int rc = scratch(out[k].slot, out[k].bytes * (size_t)batch, &d_out[k])) return rc;
+    for (int64_t f0 = 0; f0 < n; f0 += batch) {
+        const int64_t m = std::min(batch, n - f0);
+        HIP_TRY(hipMemcpyAsync(d_in, frames + frame_bytes * f0, frame_bytes * m, hipMemcpyHostToDevice, g.stream));
+        if (int rc = enqueue(d_in, m, d_scr, d_out)) return rc;
+        for (size_t k = 0; k < outs.size(); ++k)
+            if (out[k].host)
+                HIP_TRY(hipMemcpyAsync((char*)out[k].host + out[k].bytes * f0, d_out[k], out[k].bytes * (size_t)m, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+    }
+    return HVD_OK;
+}
 
 // variants: 1 (the PDQ hash) or 8 (the dihedral hashes, hvd_dev_pdq_hash_frames_dihedral): hash bytes per frame 32 * variants
 static int hash_frames_host(const uint8_t* frames, int64_t n, int h, int w, int channels, uint8_t* out_hashes,
@@ -54,49 +94,25 @@ static int hash_frames_host(const uint8_t* frames, int64_t n, int h, int w, int 
     if (int rc = need_ready()) return rc;
     // the whole geometry is checked before anything is sized or allocated for it: an oversized frame is HVD_ERR_ARG,
     // never a failed allocation (HVD_ERR_HIP) of its staging or scratch
-    if (n < 0 || h < 64 || w < 64 || h > 4096 || w > 4096 || (channels != 1 && channels != 3))
-        return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d channels=%d (need h,w in [64,4096])", (long long)n,
-                    h, w, channels);
-    if (variants != 1 && hvd::g_pdq_dct_mode != 0)
-        return fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");
+    if (n < 0) return fail(HVD_ERR_ARG, "bad frame count n=%lld", (long long)n);
+    if (int rc = hvd::check_geometry(h, w, channels)) return rc;
+    if (int rc = hvd::check_dihedral_dct(variants != 1)) return rc;
     if (n == 0) return HVD_OK;
     if (!frames || !out_hashes || !out_quality) return fail(HVD_ERR_ARG, "NULL buffer");
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    const size_t frame_bytes = (size_t)h * w * channels;
-    const size_t hash_bytes = 32 * (size_t)variants;
-    // Batches bound the staging footprint (<= ~1 GiB of frames per batch).
-    int64_t batch = (int64_t)((1ull << 30) / frame_bytes);
-    if (batch < 1) batch = 1;
-    if (batch > n) batch = n;
-    const bool need_scratch = !(h == 64 && w == 64 && channels == 1);
-    void *d_in = nullptr, *d_scr = nullptr, *d_h = nullptr, *d_q = nullptr;
-    SCR(S_FRAMES, frame_bytes * batch, d_in);
-    if (need_scratch) {
-        size_t sb = 0;
-        if (int rc = hvd_pdq_scratch_bytes(batch, h, w, channels, &sb)) return rc;
-        SCR(S_FSCR, sb, d_scr);
-    }
-    SCR(S_HASH, hash_bytes * (size_t)batch, d_h);
-    SCR(S_QUAL, 4 * (size_t)batch, d_q);
-    for (int64_t f0 = 0; f0 < n; f0 += batch) {
-        const int64_t m = std::min(batch, n - f0);
-        HIP_TRY(hipMemcpyAsync(d_in, frames + frame_bytes * f0, frame_bytes * m, hipMemcpyHostToDevice, g.stream));
-        if (int rc = variants == 1 ? hvd_dev_pdq_hash_frames(d_in, m, h, w, channels, need_scratch ? d_scr : nullptr, d_h, d_q)
-                                   : hvd_dev_pdq_hash_frames_dihedral(d_in, m, h, w, channels, need_scratch ? d_scr : nullptr,
-                                                                      d_h, d_q))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(out_hashes + hash_bytes * f0, d_h, hash_bytes * (size_t)m, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipMemcpyAsync(out_quality + f0, d_q, 4 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-    }
-    return HVD_OK;
+    return hash_in_batches(
+        frames, n, (size_t)h * w * channels, [&](int64_t batch) { return hvd::HashScratch(batch, h, w, channels, false).total; },
+        {{out_hashes, Ctx::S_HASH, 32 * (size_t)variants}, {out_quality, Ctx::S_QUAL, 4}},
+        [&](const void* d_in, int64_t m, void* d_scr, void* const* d_out) {
+            return (variants == 1 ? hvd_dev_pdq_hash_frames : hvd_dev_pdq_hash_frames_dihedral)(d_in, m, h, w, channels, d_scr,
+                                                                                                 d_out[0], d_out[1]);
+        });
 }
 
 // frames are independent: a group hashes contiguous ranges of them, one per context, no exchange
 static int hash_frames_group(const uint8_t* frames, int64_t n, int h, int w, int channels, uint8_t* out_hashes,
                              int32_t* out_quality, int variants = 1) {
     const int W = g_nctx;
-    if (W <= 1 || n < 4 * (int64_t)W || !frames || !out_hashes || !out_quality || h < 64 || w < 64 || h > 4096 || w > 4096)
+    if (W <= 1 || n < 4 * (int64_t)W || !frames || !out_hashes || !out_quality || !hvd::geometry_ok(h, w, channels))
         return hash_frames_host(frames, n, h, w, channels, out_hashes, out_quality, variants);
     const size_t frame_bytes = (size_t)h * w * channels;
     return run_on_group([&](int r) -> int {
@@ -135,30 +151,12 @@ static int hash_frames_crops_host(const uint8_t* frames, int64_t n, int h, int w
     if (n < 0 || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad frame count n=%lld", (long long)n);
     if (n == 0) return HVD_OK;
     if (!frames || !out_hashes8 || !out_quality) return fail(HVD_ERR_ARG, "NULL buffer");
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    const size_t frame_bytes = (size_t)h * w * channels;
-    int64_t batch = (int64_t)((1ull << 30) / frame_bytes);
-    if (batch < 1) batch = 1;
-    if (batch > n) batch = n;
-    void *d_in = nullptr, *d_scr = nullptr, *d_h = nullptr, *d_q = nullptr;
-    size_t sb = 0;
-    if (int rc = hvd_pdq_crops_scratch_bytes(batch, h, w, K, &sb)) return rc;
-    SCR(S_FRAMES, frame_bytes * batch, d_in);
-    SCR(S_FSCR, sb, d_scr);
-    SCR(S_HASH, 256 * (size_t)batch, d_h);
-    SCR(S_QUAL, 36 * (size_t)batch, d_q);  // int32[batch] of the full frame, then int32[batch][8] per slot
-    void* d_cq = (char*)d_q + 4 * (size_t)batch;
-    for (int64_t f0 = 0; f0 < n; f0 += batch) {
-        const int64_t m = std::min(batch, n - f0);
-        HIP_TRY(hipMemcpyAsync(d_in, frames + frame_bytes * f0, frame_bytes * m, hipMemcpyHostToDevice, g.stream));
-        if (int rc = hvd_dev_pdq_hash_frames_crops(d_in, m, h, w, channels, crops, K, d_scr, d_h, d_q, d_cq)) return rc;
-        HIP_TRY(hipMemcpyAsync(out_hashes8 + 256 * f0, d_h, 256 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipMemcpyAsync(out_quality + f0, d_q, 4 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
-        if (out_crop_quality)
-            HIP_TRY(hipMemcpyAsync(out_crop_quality + 8 * f0, d_cq, 32 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-    }
-    return HVD_OK;
+    return hash_in_batches(
+        frames, n, (size_t)h * w * channels, [&](int64_t batch) { return hvd::pdq_crops_scratch_bytes(batch, h, w, K); },
+        {{out_hashes8, Ctx::S_HASH, 256}, {out_quality, Ctx::S_QUAL, 4}, {out_crop_quality, Ctx::S_CQUAL, 32}},
+        [&](const void* d_in, int64_t m, void* d_scr, void* const* d_out) {
+            return hvd_dev_pdq_hash_frames_crops(d_in, m, h, w, channels, crops, K, d_scr, d_out[0], d_out[1], d_out[2]);
+        });
 }
 
 int hvd_pdq_hash_frames_crops_gray_u8(const uint8_t* frames, int64_t n, int h, int w, const int32_t* crops, int K,
@@ -171,18 +169,23 @@ int hvd_pdq_hash_frames_crops_rgb24_u8(const uint8_t* frames, int64_t n, int h, 
     return hash_frames_crops_host(frames, n, h, w, 3, crops, K, out_hashes8, out_quality, out_crop_quality);
 }
 
+// The batches of the autocrop entry end on video boundaries: from video v0, the end v1 > v0 of the largest run of whole videos
+// of at most `limit` frames (a video of its own is always taken: the caller has checked that each fits).
+static int64_t videos_that_fit(const int64_t* offsets, int64_t V, int64_t v0, int64_t limit) {
+    int64_t v1 = v0 + 1;
+    while (v1 < V && offsets[v1 + 1] - offsets[v0] <= limit) ++v1;
+    return v1;
+}
+
 // Content-rectangle hashing of host frames. Runs on the calling thread's current context, also under a device
 // group. Batches end on video boundaries, so a video's rectangle always sees all of its frames.
 static int hash_frames_autocrop_host(const uint8_t* frames, int64_t n, int h, int w, int channels, const int64_t* offsets,
                                      int64_t V, int black_level, int min_bright, uint8_t* out_hashes, int32_t* out_quality,
                                      int32_t* out_rects) {
     if (int rc = need_ready()) return rc;
-    if (n < 0 || h < 64 || w < 64 || h > 4096 || w > 4096 || (channels != 1 && channels != 3))
-        return fail(HVD_ERR_ARG, "bad frame geometry n=%lld h=%d w=%d channels=%d (need h,w in [64,4096])", (long long)n,
-                    h, w, channels);
-    if (V < 0 || V >= (1ll << 31) || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad counts n=%lld V=%lld", (long long)n, (long long)V);
-    if (black_level < 0 || black_level > 254) return fail(HVD_ERR_ARG, "black_level=%d: need 0..254", black_level);
-    if (min_bright < 1) return fail(HVD_ERR_ARG, "min_bright=%d: need >= 1", min_bright);
+    if (int rc = hvd::check_geometry(h, w, channels)) return rc;
+    if (n < 0 || V < 0 || V >= (1ll << 31) || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad counts n=%lld V=%lld", (long long)n, (long long)V);
+    if (int rc = hvd::check_autocrop_levels(black_level, min_bright)) return rc;
     if (V == 0 && n == 0) return HVD_OK;
     if (!offsets) return fail(HVD_ERR_ARG, "NULL offsets");
     if (offsets[0] != 0 || offsets[V] != n) return fail(HVD_ERR_ARG, "offsets must run from 0 to n=%lld", (long long)n);
@@ -191,39 +194,30 @@ static int hash_frames_autocrop_host(const uint8_t* frames, int64_t n, int h, in
     if (!out_rects || (n > 0 && (!frames || !out_hashes || !out_quality))) return fail(HVD_ERR_ARG, "NULL buffer");
     std::lock_guard<std::recursive_mutex> lk(g.h_mu);
     const size_t frame_bytes = (size_t)h * w * channels;
-    // Batches bound the staging footprint (<= ~1 GiB of frames per batch, as hash_frames_host).
-    int64_t limit = (int64_t)((1ull << 30) / frame_bytes);
-    if (limit < 1) limit = 1;
+    const int64_t limit = staging_frames(frame_bytes);
+    for (int64_t v = 0; v < V; ++v)
+        if (offsets[v + 1] - offsets[v] > limit)
+            return fail(HVD_ERR_ARG, "video %lld has %lld frames, more than the %lld that fit the staging limit of %lld bytes at this "
+                        "geometry: a video's rectangle needs all of its frames in one batch", (long long)v,
+                        (long long)(offsets[v + 1] - offsets[v]), (long long)limit, (long long)(limit * frame_bytes));
     int64_t batch = 0, batch_v = 0;  // the largest batch of whole videos: sizes the pool once
-    for (int64_t v0 = 0; v0 < V;) {
-        int64_t v1 = v0 + 1;
-        if (offsets[v1] - offsets[v0] > limit)
-            return fail(HVD_ERR_ARG, "video %lld has %lld frames, more than the %lld that fit the staging limit of 1 GiB at this "
-                        "geometry: a video's rectangle needs all of its frames in one batch", (long long)v0,
-                        (long long)(offsets[v1] - offsets[v0]), (long long)limit);
-        while (v1 < V && offsets[v1 + 1] - offsets[v0] <= limit) ++v1;
+    for (int64_t v0 = 0, v1; v0 < V; v0 = v1) {
+        v1 = videos_that_fit(offsets, V, v0, limit);
         batch = std::max<int64_t>(batch, offsets[v1] - offsets[v0]);
         batch_v = std::max<int64_t>(batch_v, v1 - v0);
-        v0 = v1;
     }
-    const bool need_scratch = !(h == 64 && w == 64 && channels == 1);
     void *d_in = nullptr, *d_scr = nullptr, *d_h = nullptr, *d_q = nullptr, *d_off = nullptr, *d_rects = nullptr;
     if (batch > 0) {
         SCR(S_FRAMES, frame_bytes * batch, d_in);
-        if (need_scratch) {
-            size_t sb = 0;
-            if (int rc = hvd_pdq_rects_scratch_bytes(batch, h, w, channels, &sb)) return rc;
-            SCR(S_FSCR, sb, d_scr);
-        }
+        if (const size_t sb = hvd::HashScratch(batch, h, w, channels, true).total) SCR(S_FSCR, sb, d_scr);
         SCR(S_HASH, 32 * (size_t)batch, d_h);
         SCR(S_QUAL, 4 * (size_t)batch, d_q);
     }
     SCR(S_OFF, 8 * (size_t)(batch_v + 1), d_off);
     SCR(S_RECTS, 16 * (size_t)batch_v, d_rects);
     std::vector<int64_t> local;
-    for (int64_t v0 = 0; v0 < V;) {
-        int64_t v1 = v0 + 1;
-        while (v1 < V && offsets[v1 + 1] - offsets[v0] <= limit) ++v1;
+    for (int64_t v0 = 0, v1; v0 < V; v0 = v1) {
+        v1 = videos_that_fit(offsets, V, v0, limit);
         const int64_t f0 = offsets[v0], m = offsets[v1] - f0, mv = v1 - v0;
         local.assign(offsets + v0, offsets + v1 + 1);
         for (auto& o : local) o -= f0;
@@ -233,19 +227,16 @@ static int hash_frames_autocrop_host(const uint8_t* frames, int64_t n, int h, in
         if (int rc = hvd_dev_content_rects(d_in, m, h, w, channels, d_off, mv, black_level, min_bright, d_rects)) return rc;
         HIP_TRY(hipMemcpyAsync(rects, d_rects, 16 * (size_t)mv, hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipStreamSynchronize(g.stream));
-        if (m > 0) {
-            // every rectangle full: today's path (fused 512x512 kernels included); both are the oracle's bits
-            bool full = true;
-            for (int64_t v = 0; v < mv && full; ++v)
-                full = rects[4 * v] == 0 && rects[4 * v + 1] == 0 && rects[4 * v + 2] == h && rects[4 * v + 3] == w;
-            if (int rc = full ? hvd_dev_pdq_hash_frames(d_in, m, h, w, channels, need_scratch ? d_scr : nullptr, d_h, d_q)
-                              : hvd_dev_pdq_hash_frames_rects(d_in, m, h, w, channels, d_off, mv, d_rects, d_scr, d_h, d_q))
-                return rc;
-            HIP_TRY(hipMemcpyAsync(out_hashes + 32 * f0, d_h, 32 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
-            HIP_TRY(hipMemcpyAsync(out_quality + f0, d_q, 4 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
-            HIP_TRY(hipStreamSynchronize(g.stream));
-        }
-        v0 = v1;
+        if (m == 0) continue;
+        // every rectangle full: today's path (fused 512x512 kernels included); both are the oracle's bits
+        bool full = true;
+        for (int64_t v = 0; v < mv && full; ++v) full = hvd::rect_is_full_frame(rects + 4 * v, h, w);
+        if (int rc = full ? hvd_dev_pdq_hash_frames(d_in, m, h, w, channels, d_scr, d_h, d_q)
+                          : hvd_dev_pdq_hash_frames_rects(d_in, m, h, w, channels, d_off, mv, d_rects, d_scr, d_h, d_q))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(out_hashes + 32 * f0, d_h, 32 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipMemcpyAsync(out_quality + f0, d_q, 4 * (size_t)m, hipMemcpyDeviceToHost, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
     }
     return HVD_OK;
 }

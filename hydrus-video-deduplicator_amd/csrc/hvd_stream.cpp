@@ -25,21 +25,7 @@
 #include <sched.h>
 
 #include "copy_pool.h"
-#include "hvd_kernels.h"
-
-namespace hvd {
-int api_fail(int code, const char* fmt, ...);     // hvd_api.cpp
-const float* api_dct_device();                    // hvd_api.cpp; nullptr before hvd_init
-int api_bind_device();                            // hvd_api.cpp: hipSetDevice(bound device) for the calling thread
-int api_context();                                // the calling thread's current context of the device group
-void api_set_context(int idx);
-size_t api_scratch_bytes(int64_t n, int h, int w, int channels);
-hipError_t api_launch_hash(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
-                           void* d_quality, hipStream_t s, bool dihedral);
-size_t api_rects_scratch_bytes(int64_t n, int h, int w, int channels);
-hipError_t api_launch_hash_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
-                                 const void* d_rects, void* d_scratch, void* d_hashes, void* d_quality, hipStream_t s);
-}  // namespace hvd
+#include "hvd_hash_host.h"
 
 namespace {
 
@@ -225,22 +211,29 @@ static int submit_retain(hvd_hasher* hs, Slot& s) {
     return HVD_OK;
 }
 
-static int submit(hvd_hasher* hs, Slot& s) {
-    if (s.filled == 0) return HVD_OK;
-    if (hs->autocrop) return submit_retain(hs, s);
-    // the dihedral kernel has K1's strict arithmetic only: a switch to fma while a video is in progress fails here, before
-    // anything of this batch is enqueued (it stays staged), instead of hashing the rest of the video another way
-    if (hs->dihedral && hvd::g_pdq_dct_mode != 0)
-        return hvd::api_fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");
-    NsScope ns(g_ns_submit);
-    const int64_t m = s.filled;
-    S_TRY(hipMemcpyAsync(s.d_frames, s.h_frames, hs->frame_bytes * (size_t)m, hipMemcpyHostToDevice, s.stream));
-    S_TRY(hvd::api_launch_hash(s.d_frames, m, hs->h, hs->w, hs->channels, s.d_scratch, s.d_hashes, s.d_quality, s.stream,
-                               hs->dihedral));
+// Hash the m frames at src (device memory) on slot s, on its stream and into its buffers -- with the hasher's kernel (plain or
+// dihedral), or under_rect: inside the video's rectangle --, download the results, record the event, mark the slot in flight.
+static int enqueue_hash(hvd_hasher* hs, Slot& s, const void* src, int64_t m, bool under_rect) {
+    S_TRY(under_rect ? hvd::api_launch_hash_rects(src, m, hs->h, hs->w, hs->channels, hs->d_offsets(), 1, hs->d_rect(), s.d_scratch,
+                                                  s.d_hashes, s.d_quality, s.stream)
+                     : hvd::api_launch_hash(src, m, hs->h, hs->w, hs->channels, s.d_scratch, s.d_hashes, s.d_quality, s.stream, hs->dihedral));
     S_TRY(hipMemcpyAsync(s.h_hashes, s.d_hashes, hs->hash_bytes() * (size_t)m, hipMemcpyDeviceToHost, s.stream));
     S_TRY(hipMemcpyAsync(s.h_quality, s.d_quality, 4 * (size_t)m, hipMemcpyDeviceToHost, s.stream));
     S_TRY(hipEventRecord(s.done, s.stream));
     s.in_flight = m;
+    s.results = true;
+    return HVD_OK;
+}
+
+static int submit(hvd_hasher* hs, Slot& s) {
+    if (s.filled == 0) return HVD_OK;
+    if (hs->autocrop) return submit_retain(hs, s);
+    // a switch to fma while a dihedral video is in progress fails here, before anything of this batch is enqueued (it stays
+    // staged), instead of hashing the rest of the video another way
+    if (int rc = hvd::check_dihedral_dct(hs->dihedral)) return rc;
+    NsScope ns(g_ns_submit);
+    S_TRY(hipMemcpyAsync(s.d_frames, s.h_frames, hs->frame_bytes * (size_t)s.filled, hipMemcpyHostToDevice, s.stream));
+    if (int rc = enqueue_hash(hs, s, s.d_frames, s.filled, false)) return rc;
     s.filled = 0;
     hs->limit = next_limit(hs);
     return HVD_OK;
@@ -347,15 +340,18 @@ static int create_hasher(int width, int height, int channels, int64_t batch_fram
     if (!out) return hvd::api_fail(HVD_ERR_ARG, "out is NULL");
     *out = nullptr;
     if (!hvd::api_dct_device()) return hvd::api_fail(HVD_ERR_STATE, "hvd_init() has not been called (no CPU fallback exists)");
-    if (width < 64 || height < 64 || width > 4096 || height > 4096 || (channels != 1 && channels != 3) || batch_frames < 1)
-        return hvd::api_fail(HVD_ERR_ARG, "bad hasher geometry %dx%dx%d batch %lld", width, height, channels,
-                             (long long)batch_frames);
-    if (dihedral && hvd::g_pdq_dct_mode != 0)
-        return hvd::api_fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");
-    if (ac && (ac->black_level < 0 || ac->black_level > 254)) return hvd::api_fail(HVD_ERR_ARG, "black_level=%d: need 0..254", ac->black_level);
-    if (ac && ac->min_bright < 1) return hvd::api_fail(HVD_ERR_ARG, "min_bright=%d: need >= 1", ac->min_bright);
+    if (int rc = hvd::check_geometry(height, width, channels)) return rc;
+    if (batch_frames < 1) return hvd::api_fail(HVD_ERR_ARG, "bad hasher batch of %lld frames", (long long)batch_frames);
+    if (int rc = hvd::check_dihedral_dct(dihedral)) return rc;
+    if (int rc = ac ? hvd::check_autocrop_levels(ac->black_level, ac->min_bright) : HVD_OK) return rc;
     const int64_t max_frames =
         !ac ? 0 : (ac->max_retained_bytes > 0 ? ac->max_retained_bytes : kDefaultRetained) / ((int64_t)width * height * channels);
+    const auto set_autocrop = [&](hvd_hasher* p) {
+        if (!ac) return;
+        p->black_level = ac->black_level;
+        p->min_bright = ac->min_bright;
+        p->max_frames = max_frames;
+    };
     {
         std::lock_guard<std::mutex> lk(g_park_mu);
         for (size_t k = g_parked.size(); k-- > 0;) {
@@ -364,11 +360,7 @@ static int create_hasher(int width, int height, int channels, int64_t batch_fram
                 p->dihedral == dihedral && p->autocrop == (ac != nullptr)) {
                 g_parked.erase(g_parked.begin() + (long)k);
                 p->copy_threads = default_copy_threads();
-                if (ac) {
-                    p->black_level = ac->black_level;
-                    p->min_bright = ac->min_bright;
-                    p->max_frames = max_frames;
-                }
+                set_autocrop(p);
                 *out = p;
                 return HVD_OK;
             }
@@ -382,16 +374,11 @@ static int create_hasher(int width, int height, int channels, int64_t batch_fram
     hs->channels = channels;
     hs->dihedral = dihedral;
     hs->autocrop = ac != nullptr;
-    if (ac) {
-        hs->black_level = ac->black_level;
-        hs->min_bright = ac->min_bright;
-        hs->max_frames = max_frames;
-    }
+    set_autocrop(hs);
     hs->batch = batch_frames;
     hs->frame_bytes = (size_t)width * height * channels;
     hs->limit = first_limit(hs);
-    const size_t scratch = ac ? hvd::api_rects_scratch_bytes(batch_frames, height, width, channels)
-                              : hvd::api_scratch_bytes(batch_frames, height, width, channels);
+    const size_t scratch = hvd::HashScratch(batch_frames, height, width, channels, ac != nullptr).total;
     for (Slot& s : hs->slot) {
         hipError_t e = hipSuccess;
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
@@ -548,7 +535,7 @@ static int hash_retained(hvd_hasher* hs, int32_t out_rect[4]) {
     hs->rect_closed = true;
     S_TRY(hipMemcpyAsync(out_rect, hs->d_rect(), 16, hipMemcpyDeviceToHost, s0));
     S_TRY(hipStreamSynchronize(s0));
-    const bool full = out_rect[0] == 0 && out_rect[1] == 0 && out_rect[2] == hs->h && out_rect[3] == hs->w;
+    const bool full = hvd::rect_is_full_frame(out_rect, hs->h, hs->w);
     int k = 0;
     for (const Block& b : hs->store) {
         for (int64_t f0 = 0; f0 < b.used; f0 += hs->batch, k = (k + 1) % kSlots) {
@@ -556,17 +543,7 @@ static int hash_retained(hvd_hasher* hs, int32_t out_rect[4]) {
             if (int rc = collect(hs, s)) return rc;
             NsScope ns(g_ns_submit);
             const int64_t m = std::min<int64_t>(hs->batch, b.used - f0);
-            const uint8_t* src = b.d + hs->frame_bytes * (size_t)f0;
-            if (full)
-                S_TRY(hvd::api_launch_hash(src, m, hs->h, hs->w, hs->channels, s.d_scratch, s.d_hashes, s.d_quality, s.stream, false));
-            else
-                S_TRY(hvd::api_launch_hash_rects(src, m, hs->h, hs->w, hs->channels, hs->d_offsets(), 1, hs->d_rect(), s.d_scratch,
-                                                 s.d_hashes, s.d_quality, s.stream));
-            S_TRY(hipMemcpyAsync(s.h_hashes, s.d_hashes, 32 * (size_t)m, hipMemcpyDeviceToHost, s.stream));
-            S_TRY(hipMemcpyAsync(s.h_quality, s.d_quality, 4 * (size_t)m, hipMemcpyDeviceToHost, s.stream));
-            S_TRY(hipEventRecord(s.done, s.stream));
-            s.in_flight = m;
-            s.results = true;
+            if (int rc = enqueue_hash(hs, s, b.d + hs->frame_bytes * (size_t)f0, m, !full)) return rc;
         }
     }
     for (int j = 0; j < kSlots; ++j, k = (k + 1) % kSlots)  // the oldest run still in flight sits in the slot that comes next

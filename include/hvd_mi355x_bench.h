@@ -29,7 +29,11 @@ int hvd_debug_parallel_copy(void* dst, const void* src, size_t n, int threads);
  * Fault injection, tests only: hvd_debug_set("vmatch_fail_rank", r + 1) makes rank r of the next video-level search fail
  * before the key exchange, so that the agreement step (every rank leaves the collective with the same error instead of
  * hanging) can be tested; 0 = off. Like the two entry points above it is absent from -DHVD_NO_BENCH_SYMBOLS builds (the
- * key is then unknown: HVD_ERR_ARG), and it is deliberately NOT in the key list of hvd_mi355x.h. */
+ * key is then unknown: HVD_ERR_ARG), and it is deliberately NOT in the key list of hvd_mi355x.h.
+ * Tests only, same build rule: hvd_debug_set("hash_staging_bytes", v) lowers the frames a host-buffer hashing entry
+ * (hvd_pdq_hash_frames_*) stages per batch from 1 GiB to v >= 4096 bytes (at least one frame), so that the multi-batch
+ * paths run at shapes that take milliseconds; 0 = the default. Results do not depend on it, except that the autocrop
+ * entries refuse (HVD_ERR_ARG) a video with more frames than one batch holds. */
 
 #ifdef __cplusplus
 }
