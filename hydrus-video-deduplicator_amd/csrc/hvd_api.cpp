@@ -681,6 +681,11 @@ int hvd_debug_set(const char* key, int value) {
         hvd::g_allpairs_index_fail = value;
         return HVD_OK;
     }
+    if (strcmp(key, "index_join_wgs") == 0) {  // tests only: workgroups of the index join; 0 = sized by the device's residency
+        if (value < 0 || value > (1 << 20)) return fail(HVD_ERR_ARG, "index_join_wgs: 0 (sized by the device) or 1 .. 2^20 workgroups");
+        hvd::g_index_join_wgs = value;
+        return HVD_OK;
+    }
     if (strcmp(key, "hash_staging_bytes") == 0) {  // tests only: frames staged per batch by the host-buffer hashing entries; 0 = 1 GiB
         if (value != 0 && value < 4096) return fail(HVD_ERR_ARG, "hash_staging_bytes: 0 (the default, 1 GiB) or >= 4096");
         g_hash_staging_bytes = value;
@@ -773,6 +778,14 @@ int hvd_debug_get(const char* key, int* out_value) {
         }
         return HVD_OK;
     }
+#ifndef HVD_NO_BENCH_SYMBOLS
+    if (strcmp(key, "index_join_wgs") == 0) {  // tests only: the workgroups the index join's next launch on this device takes
+        uint32_t wgs = 0;
+        HIP_TRY(hvd::index_join_workgroups(&wgs));
+        *out_value = (int)wgs;
+        return HVD_OK;
+    }
+#endif
     if (strcmp(key, "vmatch_bit_order_used") == 0) {
         *out_value = g.v_bit_order_used;
         return HVD_OK;

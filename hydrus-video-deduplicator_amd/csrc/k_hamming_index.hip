@@ -19,7 +19,7 @@
 //                       (select[kSelIdxUsed], hvd_kernels.h: index_wins) -- the matrix-core forms return at once when it is set
 //   k_index_place       the chunks again: final position from a returning LDS atomic on the bin's cursor; the record's word
 //                       -> hw, its row -> rows (the packed DB is not touched)
-//   k_index_join        one wave per work item (block b, key u): B_u x B_u (positions i < j) and B_u x B_{u ^ (1 << t)} for
+//   k_index_join        work item (block b, key u): B_u x B_u (positions i < j) and B_u x B_{u ^ (1 << t)} for
 //                       the one-bit neighbours above u. First stage on the word that holds block b: a pair within max_dist
 //                       has a word within tw = max_dist / 8 bits (8 (tw + 1) > max_dist), and one of that word's two blocks
 //                       within tw / 2 = r. y in registers, x through scalar loads (the bucket is contiguous at a wave-uniform
@@ -27,7 +27,8 @@
 //                       Survivors queue up in LDS and are drained 64 at a time: both whole hashes from the packed DB through
 //                       rows, the full 256-bit distance, and a pair is emitted only by its CANONICAL block -- the first
 //                       block that QUALIFIES (keys within r and word within tw: what lets a candidate reach the full check)
-//                       -- so it comes out exactly once, without a dedup pass
+//                       -- so it comes out exactly once, without a dedup pass. A fixed grid: every wave walks runs
+//                       of kRun consecutive keys at a grid stride and carries its queue and pair buffer from item to item
 // Kernels up to the statistics return at once unless the probe's gate (select[kSelIdxGate]) is set, the last two unless the
 // decision is. Nothing waits on the host.
 #include <hip/hip_runtime.h>
@@ -44,6 +45,8 @@ constexpr uint32_t kBlocks = 16, kKeys = 65536;
 constexpr uint32_t kWavePairs = 64;  // a wave's pair buffer in LDS (a drain emits at most 64); full -> one atomic reserves room for all of it
 constexpr uint32_t kXB = 16;         // x entries per scalar batch of the join: one 64-byte scalar load, one survivor mask per lane
 constexpr uint32_t kQueue = 128;     // a wave's survivor queue in LDS (a ring): a push adds at most 64, 64 pending are drained at once
+constexpr uint32_t kRun = 4;         // consecutive keys of one block that a wave of the join walks before it strides on
+constexpr uint32_t kRuns = 16u * 65536u / kRun;
 
 __device__ __forceinline__ uint32_t key_of(const uint32_t w[8], uint32_t b) { return (w[b >> 1] >> (16u * (b & 1u))) & 0xFFFFu; }
 
@@ -369,7 +372,17 @@ __device__ __forceinline__ void flush_wave(const JoinArgs& a, const hvd_pair* bu
         if (base + k < a.cap) a.out[base + k] = buf[k];
 }
 
-// Work item = (block b, key u), one wave each; item (b << 16 | u) belongs to rank item mod world. The y list of an item is
+// Work item = (block b, key u); item (b << 16 | u) belongs to rank item mod world. The grid is sized by the device, not by
+// the work (index_join_workgroups): wave w of G walks the runs w, w + G, ... of kRun consecutive keys of one block (run = item / kRun, static: no
+// workgroup waits for another and no counter is shared), inside a run only the items of its rank (the first one from one
+// modulo per run, then steps of world). The offsets of the next item of the sequence are loaded before the current one is
+// walked, so no item begins behind a fresh launch and three dependent loads. The survivor queue, the pair buffer and their
+// scalar counters live for the whole wave: a drain happens when 64 survivors are pending and once at the wave's end, a
+// flush when the pair buffer cannot take a drain's pairs and once at the end. A queue entry CARRIES ITS BLOCK (qblk, a byte
+// beside the two positions), so survivors of block b may be drained while the wave walks another block: the rows and the
+// ownership verdict come from the entry's block, never from the item being walked. Everything else is per item and is set
+// up afresh by walk(): the segment table (incl, delta, ny), the cursor (cs, ce), the y registers and ylim.
+// The y list of an item is
 // its own bucket (segment 0) followed by the buckets u ^ (1 << t) > u (r = 1): lanes take 64 consecutive entries of it per
 // round and hold their y -- one word: the key of block b and, above it, the key of its sibling block -- in a register; the
 // next round's y is loaded before the current round's x loop. The x side is the bucket itself, contiguous at a wave-uniform
@@ -377,56 +390,55 @@ __device__ __forceinline__ void flush_wave(const JoinArgs& a, const hvd_pair* bu
 // "more than tw = max_dist / 8 bits" into bit 31, and that bit shifted into the lane's mask. All kXB words are read whatever the bucket holds; the mask keeps only the x
 // that exist and, inside the own bucket, only those before the lane's y (x index k pairs with a y iff k < ylim). A
 // candidate's key is within r and its sibling key is unrelated (~8 of 16 bits differ), so about one in a hundred survives
-// (same bucket) or one in five hundred (neighbour): the survivors' {x position, y position} inside block b go into the wave's
-// queue in LDS, and whenever 64 are pending (and once at the end of the item) each lane takes one: both rows, both whole
+// (same bucket) or one in five hundred (neighbour): the survivors' {x position, y position} inside their block go into the
+// wave's queue in LDS, and whenever 64 are pending each lane takes one: both rows, both whole
 // hashes from the packed DB, the exact distance, the ownership rule, the group filter, the pair buffer.
 // Positions inside the own bucket are the first nu entries of the y list.
 __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint32_t* __restrict__ select) {
     __shared__ hvd_pair pbuf[4][kWavePairs];
     __shared__ uint2 qbuf[4][kQueue];
+    __shared__ uint8_t qblk[4][kQueue];
     if (select[hvd::kSelIdxUsed] == 0u) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t item = (blockIdx.x * 4u + wave) * a.world + a.rank;
-    if (item >= kBlocks * kKeys) return;  // (wave-uniform; nothing below synchronises across waves)
-    const uint32_t b = item >> 16, u = item & (kKeys - 1u);
-    const uint32_t* __restrict__ offb = a.off + (size_t)b * (kKeys + 1u);
-    // the bucket's and the 16 neighbours' offset pairs, all issued before the first of them is needed
-    // segments: lane 0 the bucket itself, lane 1 + t the bucket u ^ (1 << t) if that key lies above u
-    const bool nb = lane >= 1u && lane <= 16u && a.r != 0u && ((u >> ((lane - 1u) & 15u)) & 1u) == 0u;
-    const uint32_t v = nb ? u ^ (1u << ((lane - 1u) & 15u)) : u;
-    const uint32_t vstart = offb[v], vend = offb[v + 1u];
-    const uint32_t s0 = offb[u], nu = offb[u + 1u] - s0;
-    if (nu == 0u) return;
-    const uint32_t sstart = lane == 0u || nb ? vstart : 0u;
-    const uint32_t ssize = lane == 0u || nb ? vend - vstart : 0u;
-    uint32_t incl = ssize;
-    for (int d = 1; d < 32; d <<= 1) {
-        const uint32_t y = __shfl_up(incl, d);
-        if (lane >= (uint32_t)d) incl += y;
-    }
-    const int delta = (int)sstart - (int)(incl - ssize);  // position = p + delta for an entry p of this segment
-    // (segment s ends at the incl of lane s, the last one, 16, at ny; the lanes above hold ny too)
-    const uint32_t ny = (uint32_t)__builtin_amdgcn_readlane((int)incl, 16);
-    const size_t base = (size_t)b * a.n;
-    const uint32_t* __restrict__ hb = a.hw + base;
-    const uint32_t* __restrict__ rowb = a.rows + base;
-    // (a batch reads kXB words whatever the bucket holds: at most kXB - 1 words past the block's last position, and behind
-    // the last block's hw lie the rows, 16 n >= 32 words, in the same allocation)
-    kxw* xb = (kxw*)(a.hw + base + s0);
+    const uint32_t wid = blockIdx.x * 4u + wave, nwaves = gridDim.x * 4u;  // (wave-uniform; nothing below synchronises across waves)
+    constexpr uint32_t kEnd = 0xFFFFFFFFu;  // no item
+    // the first item of this rank in the runs run, run + nwaves, ... (a run shorter than world may hold none)
+    auto first_in = [&](uint32_t run) {
+        for (; run < kRuns; run += nwaves) {
+            const uint32_t i0 = run * kRun, m = i0 % a.world;
+            const uint32_t f = i0 + (a.rank >= m ? a.rank - m : a.rank + a.world - m);
+            if (f < i0 + kRun) return f;
+        }
+        return kEnd;
+    };
+    // an item's offset pairs: lane 0 the bucket itself, lane 1 + t the bucket u ^ (1 << t) if that key lies above u (the
+    // other lanes read the bucket's own pair and do not use it)
+    auto offsets = [&](uint32_t item, uint32_t* vs, uint32_t* ve) {
+        const uint32_t u = item & (kKeys - 1u), t = (lane - 1u) & 15u;
+        const bool nb = lane >= 1u && lane <= 16u && a.r != 0u && ((u >> t) & 1u) == 0u;
+        const uint32_t* __restrict__ o = a.off + (size_t)(item >> 16) * (kKeys + 1u) + (nb ? u ^ (1u << t) : u);
+        *vs = o[0];
+        *ve = o[1];
+    };
+    uint32_t item = first_in(wid);
+    if (item == kEnd) return;
     const uint32_t kfail = 0x7FFFFFFFu - a.tw;  // popcount + kfail reaches bit 31 iff popcount > tw
     uint32_t fill = 0;       // wave-uniform: pairs in the buffer
     uint32_t qh = 0, qt = 0;  // wave-uniform: the queue holds entries qh .. qt - 1 (mod kQueue), fewer than 64 between pushes
     hvd_pair* buf = pbuf[wave];
     uint2* queue = qbuf[wave];
+    uint8_t* qb = qblk[wave];
 
     // the first cnt (<= 64) queued survivors, one per lane: the full check
     auto drain = [&](uint32_t cnt) {
         __builtin_amdgcn_wave_barrier();  // (the pushes are in LDS before the entries are read)
         bool emit = false;
-        uint32_t d = 0, ri = 0, rj = 0, dw[8];
+        uint32_t d = 0, ri = 0, rj = 0, eb = 0, dw[8];
         if (lane < cnt) {
             const uint2 e = queue[(qh + lane) & (kQueue - 1u)];
+            eb = qb[(qh + lane) & (kQueue - 1u)];  // the entry's block: its positions are inside that block
+            const uint32_t* __restrict__ rowb = a.rows + (size_t)eb * a.n;
             ri = rowb[e.x];
             rj = rowb[e.y];
             uint32_t wx[8], wy[8];
@@ -448,7 +460,7 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
 #pragma unroll
             for (uint32_t b2 = 0; b2 < kBlocks; ++b2)
                 qual |= (uint32_t)__popc(key_of(dw, b2)) <= a.r && (int32_t)((uint32_t)__popc(dw[b2 >> 1]) + kfail) >= 0 ? 1u << b2 : 0u;
-            if ((qual & ((1u << b) - 1u)) != 0u) emit = false;  // an earlier qualifying block owns this pair
+            if ((qual & ((1u << eb) - 1u)) != 0u) emit = false;  // an earlier qualifying block owns this pair
             if (emit && a.group != nullptr && a.group[ri] == a.group[rj]) emit = false;
         }
         const unsigned long long em = __ballot(emit);
@@ -469,66 +481,105 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
         }
         fill += m;
     };
-    // one batch of kXB x words (x index k0 ..) against the wave's 64 y: bit kXB - 1 - j of the mask = x k0 + j survives
-    auto batch = [&](const u32x16& x, uint32_t k0, uint32_t yw, uint32_t ypos, uint32_t ylim) {
-        uint32_t fails = 0;
+    // One item, its offset pairs in vstart / vend: every value below is the item's own.
+    auto walk = [&](uint32_t item, uint32_t vstart, uint32_t vend) {
+        const uint32_t b = item >> 16, u = item & (kKeys - 1u);
+        const uint32_t s0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)vstart);
+        const uint32_t nu = (uint32_t)__builtin_amdgcn_readfirstlane((int)vend) - s0;
+        if (nu == 0u) return;
+        const bool seg = lane == 0u || (lane <= 16u && a.r != 0u && ((u >> ((lane - 1u) & 15u)) & 1u) == 0u);
+        const uint32_t sstart = seg ? vstart : 0u;
+        const uint32_t ssize = seg ? vend - vstart : 0u;
+        uint32_t incl = ssize;
+        for (int d = 1; d < 32; d <<= 1) {
+            const uint32_t y = __shfl_up(incl, d);
+            if (lane >= (uint32_t)d) incl += y;
+        }
+        const int delta = (int)sstart - (int)(incl - ssize);  // position = p + delta for an entry p of this segment
+        // (segment s ends at the incl of lane s, the last one, 16, at ny; the lanes above hold ny too)
+        const uint32_t ny = (uint32_t)__builtin_amdgcn_readlane((int)incl, 16);
+        const size_t base = (size_t)b * a.n;
+        const uint32_t* __restrict__ hb = a.hw + base;
+        // (a batch reads kXB words whatever the bucket holds: at most kXB - 1 words past the block's last position, and behind
+        // the last block's hw lie the rows, 16 n >= 32 words, in the same allocation)
+        kxw* xb = (kxw*)(a.hw + base + s0);
+        // one batch of kXB x words (x index k0 ..) against the wave's 64 y: bit kXB - 1 - j of the mask = x k0 + j survives
+        auto batch = [&](const u32x16& x, uint32_t k0, uint32_t yw, uint32_t ypos, uint32_t ylim) {
+            uint32_t fails = 0;
 #pragma unroll
-        for (uint32_t j = 0; j < kXB; ++j) fails = word_step(fails, x[j], yw, kfail);
-        const uint32_t c = ylim > k0 ? min(kXB, ylim - k0) : 0u;  // the lane's y pairs with the first c x of the batch
-        uint32_t mask = ~fails & (0xFFFF0000u >> c) & 0xFFFFu;
-        // one survivor per lane and turn: at most 64 join the fewer than 64 pending, so the push always fits
-        while (__any(mask != 0u)) {
-            const bool has = mask != 0u;
-            const unsigned long long bal = __ballot(has);
-            if (has) {
-                const uint32_t slot = qt + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-                queue[slot & (kQueue - 1u)] = make_uint2(s0 + k0 + (kXB - 1u) - (uint32_t)__builtin_ctz(mask), ypos);
-                mask &= mask - 1u;
+            for (uint32_t j = 0; j < kXB; ++j) fails = word_step(fails, x[j], yw, kfail);
+            const uint32_t c = ylim > k0 ? min(kXB, ylim - k0) : 0u;  // the lane's y pairs with the first c x of the batch
+            uint32_t mask = ~fails & (0xFFFF0000u >> c) & 0xFFFFu;
+            // one survivor per lane and turn: at most 64 join the fewer than 64 pending, so the push always fits
+            while (__any(mask != 0u)) {
+                const bool has = mask != 0u;
+                const unsigned long long bal = __ballot(has);
+                if (has) {
+                    const uint32_t slot = (qt + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))) &
+                                          (kQueue - 1u);
+                    queue[slot] = make_uint2(s0 + k0 + (kXB - 1u) - (uint32_t)__builtin_ctz(mask), ypos);
+                    qb[slot] = (uint8_t)b;
+                    mask &= mask - 1u;
+                }
+                qt += (uint32_t)__popcll(bal);
+                if (qt - qh >= 64u) drain(64u);
             }
-            qt += (uint32_t)__popcll(bal);
-            if (qt - qh >= 64u) drain(64u);
-        }
+        };
+        // The position inside block b of the entries q0 + lane of the y list, for the rounds in their order. A round touches a
+        // short run of consecutive segments, and that run only moves forward: cs (wave-uniform) is the first segment that does
+        // not end below the round's first entry, ce its end, read from the lane that holds it. A lane's segment is cs plus
+        // the segments from cs on that end at or below its entry: one compare and one add per segment that ends inside the
+        // round, whatever its size (an empty one too), and one scalar compare for a round inside a long segment.
+        uint32_t cs = 0, ce = nu;
+        auto locate = [&](uint32_t q0) {
+            const uint32_t p = q0 + lane;
+            asm volatile("" : "+s"(cs));  // (the cursor stays in a scalar register from round to round)
+            const uint32_t c0 = cs;
+            uint32_t past = 0;
+            while (ce < min(q0 + 64u, ny)) {  // (an end below ny belongs to a segment below 16; entries from ny on are not used)
+                past += p >= ce ? 1u : 0u;
+                ++cs;
+                ce = (uint32_t)__builtin_amdgcn_readlane((int)incl, (int)cs);
+            }
+            return (uint32_t)((int)p + __shfl(delta, (int)(c0 + past)));
+        };
+        uint32_t ypos = locate(0u);
+        uint32_t yw = 0u;
+        if (lane < ny) yw = hb[ypos];
+        uint32_t p0 = 0;
+        do {  // (ny >= nu > 0: at least one round)
+            const uint32_t p = p0 + lane;
+            uint32_t ypos_n = 0u, yw_n = 0u;
+            if (p0 + 64u < ny) {  // (wave-uniform: the last round looks for nothing)
+                ypos_n = locate(p0 + 64u);
+                asm volatile("" ::"v"(yw));  // (this round's y has arrived before the next one's load is issued)
+                if (p + 64u < ny) yw_n = hb[ypos_n];  // the next round's y: in flight under this round's x loop
+            }
+            // x index k pairs with this y iff k < ylim: inside the bucket (the first nu entries) only the x before it (positions i < j)
+            const uint32_t ylim = p >= ny ? 0u : min(p, nu);
+            for (uint32_t k0 = 0; k0 < nu; k0 += kXB) {
+                const u32x16 x = *(kx16*)(xb + k0);
+                batch(x, k0, yw, ypos, ylim);
+            }
+            ypos = ypos_n;
+            yw = yw_n;
+            p0 += 64u;
+        } while (p0 < ny);
     };
-    // The position inside block b of the entries q0 + lane of the y list, for the rounds in their order. A round touches a
-    // short run of consecutive segments, and that run only moves forward: cs (wave-uniform) is the first segment that does
-    // not end below the round's first entry, ce its end, read from the lane that holds it. A lane's segment is cs plus
-    // the segments from cs on that end at or below its entry: one compare and one add per segment that ends inside the
-    // round, whatever its size (an empty one too), and one scalar compare for a round inside a long segment.
-    uint32_t cs = 0, ce = nu;
-    auto locate = [&](uint32_t q0) {
-        const uint32_t p = q0 + lane;
-        asm volatile("" : "+s"(cs));  // (the cursor stays in a scalar register from round to round)
-        const uint32_t c0 = cs;
-        uint32_t past = 0;
-        while (ce < min(q0 + 64u, ny)) {  // (an end below ny belongs to a segment below 16; entries from ny on are not used)
-            past += p >= ce ? 1u : 0u;
-            ++cs;
-            ce = (uint32_t)__builtin_amdgcn_readlane((int)incl, (int)cs);
-        }
-        return (uint32_t)((int)p + __shfl(delta, (int)(c0 + past)));
-    };
-    uint32_t ypos = locate(0u);
-    uint32_t yw = 0u;
-    if (lane < ny) yw = hb[ypos];
-    uint32_t p0 = 0;
-    do {  // (ny >= nu > 0: at least one round)
-        const uint32_t p = p0 + lane;
-        uint32_t ypos_n = 0u, yw_n = 0u;
-        if (p0 + 64u < ny) {  // (wave-uniform: the last round looks for nothing)
-            ypos_n = locate(p0 + 64u);
-            asm volatile("" ::"v"(yw));  // (this round's y has arrived before the next one's load is issued)
-            if (p + 64u < ny) yw_n = hb[ypos_n];  // the next round's y: in flight under this round's x loop
-        }
-        // x index k pairs with this y iff k < ylim: inside the bucket (the first nu entries) only the x before it (positions i < j)
-        const uint32_t ylim = p >= ny ? 0u : min(p, nu);
-        for (uint32_t k0 = 0; k0 < nu; k0 += kXB) {
-            const u32x16 x = *(kx16*)(xb + k0);
-            batch(x, k0, yw, ypos, ylim);
-        }
-        ypos = ypos_n;
-        yw = yw_n;
-        p0 += 64u;
-    } while (p0 < ny);
+    uint32_t vstart, vend;
+    offsets(item, &vstart, &vend);
+    for (;;) {
+        // the next item of the sequence: the next one of this rank inside the run, or the first of the wave's next run
+        uint32_t next = item + a.world;
+        if ((next ^ item) >= kRun) next = first_in(item / kRun + nwaves);
+        uint32_t vstart_n = 0u, vend_n = 0u;
+        if (next != kEnd) offsets(next, &vstart_n, &vend_n);  // in flight under this item's walk
+        walk(item, vstart, vend);
+        if (next == kEnd) break;
+        item = next;
+        vstart = vstart_n;
+        vend = vend_n;
+    }
     if (qt != qh) drain(qt - qh);
     if (fill != 0u) flush_wave(a, buf, fill, lane);
 }
@@ -539,6 +590,7 @@ namespace hvd {
 
 int g_allpairs_index = -1;
 int g_allpairs_index_fail = 0;
+int g_index_join_wgs = 0;
 
 // per-context scratch: per-key counts [16][65536], offsets [16][65537], words [16][n] x 4 B, rows [16][n] x 4 B -- in this
 // order: the join's scalar batch reads up to 15 words past a bucket's end, which behind the last block's words are rows --;
@@ -603,17 +655,18 @@ IndexRule index_rule(const AllPairsArgs& a, uint32_t r) {
     q.force = g_allpairs_index == 1 ? 1u : 0u;
     q.world = a.world;
     // (DESIGN 4.1, 1 M uniform hashes on MI355X: form 9 18.1 ms = 36 fs per comparison, forms 18 / 12 +4 / +11 %. From the
-    // kernel trace of the word index (profiles/r15_index_kernel_stats_after.csv): join 0.880 ms for 2.075e9 candidates =
-    // 0.42 ps each; the counting sort, the statistics and the place pass -- every kernel between probe and join -- 0.356 ms,
+    // kernel trace of the looping join (profiles/r16_index_kernel_stats_after.csv): join 0.808 ms for 2.075e9 candidates =
+    // 0.39 ps each; the counting sort, the statistics and the place pass -- every kernel between probe and join -- 0.356 ms,
     // of which ~0.03 ms do not depend on n (the scans over 4096 partitions, the grid of 6144 chunks): 0.33 ns per hash, and
     // those 30 us next to the 40 us of launches. To re-derive after a change of these kernels: ps_cand = join time /
     // candidates, ps_hash = (every kernel between probe and join - 30 us) / n, ps_crit from the crowded DB of
-    // scripts/gpu_index_join_time.py (profiles/r15_index_join_time.jsonl): 200 000 hashes, 5 000 of them in one bucket, a
-    // longest walk of 25.15e6 pairs, 8.83 ms per call of which ~0.2 ms are what the other terms price and ~0.4 ms copies:
-    // 0.33 ns per pair, 21 ns per step of 64 -- rounded up, which errs towards the matrix cores)
+    // scripts/gpu_index_join_time.py (profiles/r16_index_join_time.jsonl): 200 000 hashes, 5 000 of them in one bucket, a
+    // longest walk of 25.15e6 pairs, 8.95 .. 9.00 ms per call of which ~0.2 ms are what the other terms price and ~0.4 ms
+    // copies: 0.33 ns per pair, 21 ns per step of 64 -- rounded up, which errs towards the matrix cores. The wave that
+    // walks the crowded bucket also walks the other 15 items of its sequence, ~60 us at 1 M: the terms ADD, which prices that)
     q.fs_mfma_fetch = 36.0f;
     q.fs_mfma_other = 40.0f;
-    q.ps_cand = 0.43f;
+    q.ps_cand = 0.40f;
     q.ps_hash = 330.0f;
     q.ps_crit = 350.0f;
     q.fixed_ns = 70000.0f;
@@ -662,6 +715,26 @@ hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const 
     return hipGetLastError();
 }
 
+// Workgroups of the join: 64 per compute unit (the compute units from the device's attributes), eight times what the device
+// holds at once -- 8 workgroups of 4 waves per compute unit, 8 waves per SIMD --, and never more waves than there are runs.
+// Measured on 1 M uniform hashes (profiles/r16_index_join_grid.txt): with exactly the resident number the
+// waves of a SIMD do not advance alike -- the oldest is served first --, they end one after the other and the slots stand
+// empty behind them (3.96 of 8 occupied, the join slower than one wave per item); with several workgroups per slot the
+// hardware's dispatcher fills every slot that frees, and a wave still walks 16 items. The grid only sets how the runs are
+// dealt out: any number of workgroups walks every item once ("index_join_wgs" n: exactly n).
+hipError_t index_join_workgroups(uint32_t* wgs) {
+    if (g_index_join_wgs > 0) {
+        *wgs = (uint32_t)g_index_join_wgs;
+        return hipSuccess;
+    }
+    int dev = 0, cus = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return e;
+    if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) return e;
+    if (cus <= 0) return hipErrorInvalidDevice;
+    *wgs = min((uint32_t)cus * 64u, kRuns / 4u);
+    return hipSuccess;
+}
+
 hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t r, hipStream_t s) {
     const IndexPtrs p = index_ptrs(a.ctx_id, a.n);
     hipLaunchKernelGGL(k_index_place, dim3(kMaxChunks), dim3(256), 0, s, p.rec, a.n, index_chunk(a.n), p.ptotal, p.pbase, p.pfirst,
@@ -681,8 +754,9 @@ hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t
     j.tw = a.max_dist / 8u;  // a pair within max_dist has a word within tw bits, and one of its two blocks within tw / 2 = r
     j.rank = a.rank;
     j.world = a.world;
-    const uint32_t items = (kBlocks * kKeys + a.world - 1u - a.rank) / a.world;  // this rank's items: rank, rank + world, ...
-    hipLaunchKernelGGL(k_index_join, dim3((items + 3u) / 4u), dim3(256), 0, s, j, (const uint32_t*)d_select);
+    uint32_t wgs = 0;
+    if (hipError_t e = index_join_workgroups(&wgs)) return e;
+    hipLaunchKernelGGL(k_index_join, dim3(wgs), dim3(256), 0, s, j, (const uint32_t*)d_select);
     return hipGetLastError();
 }
 

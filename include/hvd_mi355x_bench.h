@@ -26,6 +26,10 @@ int hvd_debug_parallel_copy(void* dst, const void* src, size_t n, int threads);
 /* Fault injection, tests only: hvd_debug_set("allpairs_index_fail_ctx", c + 1) makes context c's reservation of the
  * pigeonhole index's scratch fail, as if its device were out of memory: a pass of world > 1 then fails on every rank, a
  * lone pass falls back to the matrix cores; 0 = off. Same build rule as the key below.
+ * Tests only, same build rule: hvd_debug_set("index_join_wgs", n) launches the pigeonhole index's join with exactly n
+ * workgroups (1 .. 2^20) instead of as many as the device holds at once (0, the default), so that one wave walks many work
+ * items, or crosses a block, on a DB small enough to check against the oracle; hvd_debug_get of the same key returns the
+ * workgroups the next launch takes. Results do not depend on it.
  * Fault injection, tests only: hvd_debug_set("vmatch_fail_rank", r + 1) makes rank r of the next video-level search fail
  * before the key exchange, so that the agreement step (every rank leaves the collective with the same error instead of
  * hanging) can be tested; 0 = off. Like the two entry points above it is absent from -DHVD_NO_BENCH_SYMBOLS builds (the
