@@ -781,7 +781,7 @@ int hvd_debug_get(const char* key, int* out_value) {
 #ifndef HVD_NO_BENCH_SYMBOLS
     if (strcmp(key, "index_join_wgs") == 0) {  // tests only: the workgroups the index join's next launch on this device takes
         uint32_t wgs = 0;
-        HIP_TRY(hvd::index_join_workgroups(&wgs));
+        HIP_TRY(hvd::index_join_workgroups(0u, &wgs));  // (the grid of a pass over at most 2^20 hashes)
         *out_value = (int)wgs;
         return HVD_OK;
     }

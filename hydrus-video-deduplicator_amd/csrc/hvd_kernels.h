@@ -85,7 +85,7 @@ __host__ __device__ inline bool index_wins(const IndexRule& q, double cand, doub
 }
 extern int g_allpairs_index;       // hvd_debug_set "allpairs_index": -1 auto, 0 never, 1 force when eligible
 extern int g_allpairs_index_fail;  // fault injection (tests): context (value - 1) fails to reserve its index scratch; 0 = off
-extern int g_index_join_wgs;       // tests: workgroups of the join; 0 = as many as the device holds at once (launch_index_join)
+extern int g_index_join_wgs;       // tests: workgroups of the join; 0 = sized by the device and, above 2^20 hashes, by n (index_join_workgroups)
 // Eligible: self pass (not query x target, not the video sink), max_dist <= 31, packed hashes at hand, not switched off, and
 // -- unless forced -- a DB large enough that the index could win even with no candidates at all. Depends only on what every
 // rank of a pass shares (arguments, n, world, the process-wide key), so all ranks agree.
@@ -99,7 +99,8 @@ hipError_t index_reserve(int ctx_id, uint32_t n);
 // returns at once unless the probe's gate is set, every kernel of the second unless the decision is.
 hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const IndexRule& q, hipStream_t s);
 hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t r, hipStream_t s);
-hipError_t index_join_workgroups(uint32_t* wgs);  // the join's grid on the current device (or what "index_join_wgs" sets)
+// the join's grid for n hashes on the current device (or what "index_join_wgs" sets): the same for every n <= 2^20
+hipError_t index_join_workgroups(uint32_t n, uint32_t* wgs);
 void index_release();
 // clock telemetry of a context's all-pairs passes: {shader cycles, constant-rate ticks, sampled workgroups, 0} since the reset
 hipError_t mfma_clock_reset(int ctx_id, hipStream_t s);

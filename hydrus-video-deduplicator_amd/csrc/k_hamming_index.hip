@@ -362,9 +362,19 @@ struct JoinArgs {
     uint32_t max_dist, r, tw, rank, world;
 };
 
+// The join's arguments as read where they are needed: what only a flush or the group filter uses (out, cap, count, group) is
+// loaded there, once in thousands of items, and holds no scalar register for the whole kernel (JoinArgs is the kernel's
+// first argument: offset 0 of the kernel's argument segment).
+__device__ __forceinline__ const JoinArgs* rare_args() {
+    const JoinArgs* p = (const JoinArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
 // A wave's buffered pairs -> global: one atomic reserves room for all of them; beyond `cap` nothing is written but the count
 // still grows (the caller reports HVD_ERR_OVERFLOW with the number needed).
-__device__ __forceinline__ void flush_wave(const JoinArgs& a, const hvd_pair* buf, uint32_t fill, uint32_t lane) {
+__device__ __forceinline__ void flush_wave(const hvd_pair* buf, uint32_t fill, uint32_t lane) {
+    const JoinArgs& a = *rare_args();
     unsigned long long base = 0;
     if (lane == 0u) base = atomicAdd(a.count, (unsigned long long)fill);
     base = __shfl(base, 0);
@@ -387,8 +397,11 @@ __device__ __forceinline__ void flush_wave(const JoinArgs& a, const hvd_pair* bu
 // round and hold their y -- one word: the key of block b and, above it, the key of its sibling block -- in a register; the
 // next round's y is loaded before the current round's x loop. The x side is the bucket itself, contiguous at a wave-uniform
 // address: kXB words per scalar batch, xor'ed as scalar operands. Per candidate: xor, popcount onto a constant that carries
-// "more than tw = max_dist / 8 bits" into bit 31, and that bit shifted into the lane's mask. All kXB words are read whatever the bucket holds; the mask keeps only the x
-// that exist and, inside the own bucket, only those before the lane's y (x index k pairs with a y iff k < ylim). A
+// "more than tw = max_dist / 8 bits" into bit 31, and that bit shifted into the lane's mask. All kXB words are read whatever the bucket holds,
+// but only the quarters of a batch that hold an x are stepped; the mask keeps only the x
+// that exist and, inside the own bucket, only those before the lane's y (x index k pairs with a y iff k < ylim). The kernel
+// is bound by the instructions its waves issue, not by what they wait for (fetching an item's y, x and rows
+// further ahead measured slower, every instruction taken out measured faster), so the loops are written for few of them. A
 // candidate's key is within r and its sibling key is unrelated (~8 of 16 bits differ), so about one in a hundred survives
 // (same bucket) or one in five hundred (neighbour): the survivors' {x position, y position} inside their block go into the
 // wave's queue in LDS, and whenever 64 are pending each lane takes one: both rows, both whole
@@ -456,18 +469,21 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
         // survivor in seven thousand is on uniform hashes, so almost every drain ends here, after the eight popcounts
         if (!__any(emit)) return;
         if (emit) {
-            uint32_t qual = 0;  // bit b2: block b2 qualifies -- its keys are within r and its word within tw
+            // bit b2: block b2 qualifies -- its keys are within r and its word within tw (shifted in from the top block down:
+            // a constant 1 << b2 per block would hold a vector register each for the whole kernel)
+            uint32_t qual = 0;
 #pragma unroll
-            for (uint32_t b2 = 0; b2 < kBlocks; ++b2)
-                qual |= (uint32_t)__popc(key_of(dw, b2)) <= a.r && (int32_t)((uint32_t)__popc(dw[b2 >> 1]) + kfail) >= 0 ? 1u << b2 : 0u;
+            for (uint32_t b2 = kBlocks; b2-- > 0u;)
+                qual = qual << 1 | ((uint32_t)__popc(key_of(dw, b2)) <= a.r && (int32_t)((uint32_t)__popc(dw[b2 >> 1]) + kfail) >= 0 ? 1u : 0u);
             if ((qual & ((1u << eb) - 1u)) != 0u) emit = false;  // an earlier qualifying block owns this pair
-            if (emit && a.group != nullptr && a.group[ri] == a.group[rj]) emit = false;
+            const int32_t* __restrict__ group = rare_args()->group;
+            if (emit && group != nullptr && group[ri] == group[rj]) emit = false;
         }
         const unsigned long long em = __ballot(emit);
         const uint32_t m = (uint32_t)__popcll(em);
         if (m == 0u) return;
         if (fill + m > kWavePairs) {
-            flush_wave(a, buf, fill, lane);
+            flush_wave(buf, fill, lane);
             fill = 0;
         }
         if (emit) {
@@ -490,13 +506,16 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
         const bool seg = lane == 0u || (lane <= 16u && a.r != 0u && ((u >> ((lane - 1u) & 15u)) & 1u) == 0u);
         const uint32_t sstart = seg ? vstart : 0u;
         const uint32_t ssize = seg ? vend - vstart : 0u;
+        // inclusive scan over the lanes 0 .. 16 in the data path (no LDS, no index registers): four shifts inside the row of
+        // 16 lanes, then lane 15 onto the row above
         uint32_t incl = ssize;
-        for (int d = 1; d < 32; d <<= 1) {
-            const uint32_t y = __shfl_up(incl, d);
-            if (lane >= (uint32_t)d) incl += y;
-        }
+        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x111, 0xF, 0xF, true);  // row_shr:1
+        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x112, 0xF, 0xF, true);  // row_shr:2
+        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x114, 0xF, 0xF, true);  // row_shr:4
+        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x118, 0xF, 0xF, true);  // row_shr:8
+        incl += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)incl, 0x142, 0xA, 0xF, true);  // row_bcast:15 onto rows 1 and 3
         const int delta = (int)sstart - (int)(incl - ssize);  // position = p + delta for an entry p of this segment
-        // (segment s ends at the incl of lane s, the last one, 16, at ny; the lanes above hold ny too)
+        // (segment s ends at the incl of lane s, the last one, 16, at ny; the lanes 17 .. 31 hold ny too, the rest is not read)
         const uint32_t ny = (uint32_t)__builtin_amdgcn_readlane((int)incl, 16);
         const size_t base = (size_t)b * a.n;
         const uint32_t* __restrict__ hb = a.hw + base;
@@ -505,13 +524,31 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
         kxw* xb = (kxw*)(a.hw + base + s0);
         // one batch of kXB x words (x index k0 ..) against the wave's 64 y: bit kXB - 1 - j of the mask = x k0 + j survives
         auto batch = [&](const u32x16& x, uint32_t k0, uint32_t yw, uint32_t ypos, uint32_t ylim) {
+            // only the quarters of the batch that hold an x are stepped (wave-uniform: the bucket's last batch is short, and the
+            // mean bucket of 15 at 1 M hashes fills 70 % of whole batches, 93 % of quarters)
             uint32_t fails = 0;
+            const uint32_t nq = min(kXB / 4u, (nu - k0 + 3u) / 4u);
 #pragma unroll
-            for (uint32_t j = 0; j < kXB; ++j) fails = word_step(fails, x[j], yw, kfail);
+            for (uint32_t j = 0; j < 4u; ++j) fails = word_step(fails, x[j], yw, kfail);
+            if (nq > 1u) {
+#pragma unroll
+                for (uint32_t j = 4u; j < 8u; ++j) fails = word_step(fails, x[j], yw, kfail);
+                if (nq > 2u) {
+#pragma unroll
+                    for (uint32_t j = 8u; j < 12u; ++j) fails = word_step(fails, x[j], yw, kfail);
+                    if (nq > 3u) {
+#pragma unroll
+                        for (uint32_t j = 12u; j < 16u; ++j) fails = word_step(fails, x[j], yw, kfail);
+                    }
+                }
+            }
+            fails <<= kXB - 4u * nq;  // (the outcome of x k0 + j at bit kXB - 1 - j, as after all kXB steps)
             const uint32_t c = ylim > k0 ? min(kXB, ylim - k0) : 0u;  // the lane's y pairs with the first c x of the batch
             uint32_t mask = ~fails & (0xFFFF0000u >> c) & 0xFFFFu;
-            // one survivor per lane and turn: at most 64 join the fewer than 64 pending, so the push always fits
-            while (__any(mask != 0u)) {
+            // one survivor per lane and turn: at most 64 join the fewer than 64 pending, so the push always fits (a batch
+            // without a survivor leaves at once: one compare and one branch)
+            if (!__any(mask != 0u)) return;
+            do {
                 const bool has = mask != 0u;
                 const unsigned long long bal = __ballot(has);
                 if (has) {
@@ -523,7 +560,7 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
                 }
                 qt += (uint32_t)__popcll(bal);
                 if (qt - qh >= 64u) drain(64u);
-            }
+            } while (__any(mask != 0u));
         };
         // The position inside block b of the entries q0 + lane of the y list, for the rounds in their order. A round touches a
         // short run of consecutive segments, and that run only moves forward: cs (wave-uniform) is the first segment that does
@@ -550,9 +587,9 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
         do {  // (ny >= nu > 0: at least one round)
             const uint32_t p = p0 + lane;
             uint32_t ypos_n = 0u, yw_n = 0u;
+            asm volatile("" ::"v"(yw));  // (this round's y has arrived, on every path, before the next one's load is issued)
             if (p0 + 64u < ny) {  // (wave-uniform: the last round looks for nothing)
                 ypos_n = locate(p0 + 64u);
-                asm volatile("" ::"v"(yw));  // (this round's y has arrived before the next one's load is issued)
                 if (p + 64u < ny) yw_n = hb[ypos_n];  // the next round's y: in flight under this round's x loop
             }
             // x index k pairs with this y iff k < ylim: inside the bucket (the first nu entries) only the x before it (positions i < j)
@@ -581,7 +618,7 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
         vend = vend_n;
     }
     if (qt != qh) drain(qt - qh);
-    if (fill != 0u) flush_wave(a, buf, fill, lane);
+    if (fill != 0u) flush_wave(buf, fill, lane);
 }
 
 }  // namespace
@@ -655,20 +692,21 @@ IndexRule index_rule(const AllPairsArgs& a, uint32_t r) {
     q.force = g_allpairs_index == 1 ? 1u : 0u;
     q.world = a.world;
     // (DESIGN 4.1, 1 M uniform hashes on MI355X: form 9 18.1 ms = 36 fs per comparison, forms 18 / 12 +4 / +11 %. From the
-    // kernel trace of the looping join (profiles/r16_index_kernel_stats_after.csv): join 0.808 ms for 2.075e9 candidates =
-    // 0.39 ps each; the counting sort, the statistics and the place pass -- every kernel between probe and join -- 0.356 ms,
-    // of which ~0.03 ms do not depend on n (the scans over 4096 partitions, the grid of 6144 chunks): 0.33 ns per hash, and
-    // those 30 us next to the 40 us of launches. To re-derive after a change of these kernels: ps_cand = join time /
-    // candidates, ps_hash = (every kernel between probe and join - 30 us) / n, ps_crit from the crowded DB of
-    // scripts/gpu_index_join_time.py (profiles/r16_index_join_time.jsonl): 200 000 hashes, 5 000 of them in one bucket, a
-    // longest walk of 25.15e6 pairs, 8.95 .. 9.00 ms per call of which ~0.2 ms are what the other terms price and ~0.4 ms
-    // copies: 0.33 ns per pair, 21 ns per step of 64 -- rounded up, which errs towards the matrix cores. The wave that
-    // walks the crowded bucket also walks the other 15 items of its sequence, ~60 us at 1 M: the terms ADD, which prices that)
+    // kernel trace of the join with fewer instructions per item (profiles/r17_index_kernel_stats_after.csv): join 0.638 ms
+    // for 2.075e9 candidates = 0.31 ps each; the counting sort, the statistics and the place pass -- every kernel between
+    // probe and join -- 0.352 ms, of which ~0.03 ms do not depend on n (the scans over 4096 partitions, the grid of 6144
+    // chunks): 0.32 ns per hash, kept at 0.33, and those 30 us next to the 40 us of launches. To re-derive after a change
+    // of these kernels: ps_cand = join time / candidates, ps_hash = (every kernel between probe and join - 30 us) / n,
+    // ps_crit from the crowded DB of scripts/gpu_index_join_time.py (profiles/r17_index_join_time.jsonl): 200 000 hashes,
+    // 5 000 of them in one bucket, a longest walk of 25.15e6 pairs, 8.07 .. 8.13 ms per call of which ~0.2 ms are what
+    // the other terms price and ~0.4 ms copies: 0.30 ns per pair, 19 ns per step of 64 -- rounded up, which errs towards
+    // the matrix cores. The wave that walks the crowded bucket also walks the other 15 items of its sequence, ~50 us at
+    // 1 M: the terms ADD, which prices that)
     q.fs_mfma_fetch = 36.0f;
     q.fs_mfma_other = 40.0f;
-    q.ps_cand = 0.40f;
+    q.ps_cand = 0.31f;
     q.ps_hash = 330.0f;
-    q.ps_crit = 350.0f;
+    q.ps_crit = 320.0f;
     q.fixed_ns = 70000.0f;
     return q;
 }
@@ -721,8 +759,11 @@ hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const 
 // waves of a SIMD do not advance alike -- the oldest is served first --, they end one after the other and the slots stand
 // empty behind them (3.96 of 8 occupied, the join slower than one wave per item); with several workgroups per slot the
 // hardware's dispatcher fills every slot that frees, and a wave still walks 16 items. The grid only sets how the runs are
-// dealt out: any number of workgroups walks every item once ("index_join_wgs" n: exactly n).
-hipError_t index_join_workgroups(uint32_t* wgs) {
+// dealt out: any number of workgroups walks every item once ("index_join_wgs" n: exactly n). Up to 2^20 hashes that is the
+// grid. Above, an item grows with n and a wave of the fixed grid lives for milliseconds (at 10 M: eight generations of ~6 ms
+// waves, and the last one of each holds its slot while the others stand empty), so the grid grows with n -- the fixed number
+// times n / 2^20, rounded up -- until every wave walks one run.
+hipError_t index_join_workgroups(uint32_t n, uint32_t* wgs) {
     if (g_index_join_wgs > 0) {
         *wgs = (uint32_t)g_index_join_wgs;
         return hipSuccess;
@@ -731,7 +772,8 @@ hipError_t index_join_workgroups(uint32_t* wgs) {
     if (hipError_t e = hipGetDevice(&dev)) return e;
     if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) return e;
     if (cus <= 0) return hipErrorInvalidDevice;
-    *wgs = min((uint32_t)cus * 64u, kRuns / 4u);
+    const unsigned long long scale = n > (1u << 20) ? ((unsigned long long)n + (1u << 20) - 1u) >> 20 : 1u;
+    *wgs = (uint32_t)min((unsigned long long)cus * 64u * scale, (unsigned long long)(kRuns / 4u));
     return hipSuccess;
 }
 
@@ -755,7 +797,7 @@ hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t
     j.rank = a.rank;
     j.world = a.world;
     uint32_t wgs = 0;
-    if (hipError_t e = index_join_workgroups(&wgs)) return e;
+    if (hipError_t e = index_join_workgroups(a.n, &wgs)) return e;
     hipLaunchKernelGGL(k_index_join, dim3(wgs), dim3(256), 0, s, j, (const uint32_t*)d_select);
     return hipGetLastError();
 }
