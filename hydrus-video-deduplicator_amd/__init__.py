@@ -11,7 +11,7 @@ from .hashing import compute_phash, decode_phash_from_str, encode_phash_to_str, 
 from .search import (allpairs_hamming, calculate_distance, find_cropped_duplicates, find_duplicate_groups, find_excerpts,  # noqa: F401
                      find_potential_duplicates,
                      find_rate_excerpts, find_segmented_excerpts, find_transformed_duplicates, fix_vpdq_similarity,
-                     match_videos)
+                     match_videos, without_common_frames)
 from .vpdq import VideoHasher, VpdqHash, matchHash, matchHashBytes  # noqa: F401
 from .pipeline import (DeviceLibrary, dedupe_cropped_frames_on_device, dedupe_frames_on_device,  # noqa: F401
                        dedupe_transformed_frames_on_device, dedupe_videos, hash_videos)

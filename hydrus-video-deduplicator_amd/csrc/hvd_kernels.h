@@ -137,6 +137,16 @@ hipError_t launch_video_of_frames(const long long* d_offsets, uint32_t V, unsign
 hipError_t launch_kept_positions(const int32_t* d_quality, unsigned long long n, const long long* d_offsets, uint32_t V, int min_q,
                                  int32_t* d_out_pos, void* d_scratch, unsigned long long* d_total, hipStream_t s);
 
+// Common-frame filter (k_spread.hip). launch_keys_to_spread: d_src / n_src as launch_keys_to_pairs takes them, d_spread
+// int32[n], zeroed by the launcher on s. launch_common_rule: d_keep int32[n], 1 or 0. launch_gather_kept_i32: d_scratch of
+// compact_scratch_bytes(n), d_total one uint64 (device) that receives the kept count.
+hipError_t launch_keys_to_spread(const unsigned long long* d_src, unsigned long long n_src, unsigned long long n,
+                                 int32_t* d_spread, hipStream_t s);
+hipError_t launch_common_rule(const int32_t* d_spread, const long long* d_offsets, uint32_t V, unsigned long long n,
+                              int max_videos, int max_share, int32_t* d_keep, hipStream_t s);
+hipError_t launch_gather_kept_i32(const int32_t* d_in, const int32_t* d_keep, unsigned long long n, int32_t* d_out,
+                                  void* d_scratch, unsigned long long* d_total, hipStream_t s);
+
 // Time alignment of listed video pairs (k_valign.hip). Two launches: the pairs whose delta histogram fits LDS, then
 // the larger ones out of d_scratch (align_scratch_bytes(max_bins); may be nullptr / 0: such pairs then get the INT32_MIN record).
 size_t align_scratch_bytes(unsigned long long max_bins);

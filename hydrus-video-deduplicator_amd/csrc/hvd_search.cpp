@@ -585,10 +585,18 @@ int choose_bit_order(const void* d_bits, uint32_t n, bool always, uint8_t perm[2
     return HVD_OK;
 }
 
-// All-pairs pass in video mode -> set of (frame, video) keys -> [key exchange between ranks] -> pair map with
-// the vPDQ counters, left in the pool for vmatch_emit. Overflowing tables are rebuilt larger and only the
-// step that overflowed is repeated; the inputs never move.
-int vmatch_build(const VmArgs& v) {
+// The key set of a video search, where vmatch_keys leaves it: a table (n_src slots, kEmptyKey = free) in the pool -- the local
+// set, or the merged one after an exchange -- with n_keys keys.
+struct VmKeys {
+    const unsigned long long* d_src = nullptr;
+    unsigned long long n_src = 0, n_keys = 0;
+    unsigned long long* d_counters = nullptr;
+};
+
+// Key stage: all-pairs pass in video mode -> set of (frame, video) keys -> [key exchange between ranks]. Overflowing tables
+// are rebuilt larger and only the step that overflowed is repeated; the inputs never move. The pair map of the last
+// search (S_PKEYS, S_PCNT, g.v_pslots) is not touched.
+int vmatch_keys(const VmArgs& v, VmKeys* keys) {
     const bool exchange = g.v_exchange_mode == 1 || (g.v_exchange_mode == 0 && v.world > 1);
     if (exchange && ((!g.comm_ready && !g.host_exchange) || g.world != v.world || g.rank != v.rank))
         return fail(HVD_ERR_STATE, "rank %d of %d needs hvd_comm_init() with the same rank/world first", v.rank, v.world);
@@ -712,19 +720,27 @@ int vmatch_build(const VmArgs& v) {
         n_keys = c[1];
         g.v_us[1] = us_since(t_exchange);
     }
+    *keys = VmKeys{d_src, n_src, n_keys, d_counters};
+    return HVD_OK;
+}
+
+// Key stage, then the fold stage: key set -> pair map with the vPDQ counters, left in the pool for vmatch_emit.
+int vmatch_build(const VmArgs& v) {
+    VmKeys k;
+    if (int rc = vmatch_keys(v, &k)) return rc;
     const auto t_fold = std::chrono::steady_clock::now();
     unsigned long long* d_pkeys = nullptr;
     void* d_pcnt = nullptr;
-    unsigned long long pslots = 0;
-    if (int rc = build_table({{Ctx::S_PKEYS, 0xFF, (void**)&d_pkeys}, {Ctx::S_PCNT, 0, &d_pcnt}}, 1024, n_keys, d_counters, c,
+    unsigned long long pslots = 0, c[4] = {0, 0, 0, 0};
+    if (int rc = build_table({{Ctx::S_PKEYS, 0xFF, (void**)&d_pkeys}, {Ctx::S_PCNT, 0, &d_pcnt}}, 1024, k.n_keys, k.d_counters, c,
                              &pslots, [&](unsigned long long n) -> int {
-                                 HIP_TRY(hvd::launch_keys_to_pairs(d_src, n_src, v.d_vid_q, v.d_vid_t, v.rect, d_pkeys, d_pcnt, n - 1,
-                                                                   d_counters, g.stream));
+                                 HIP_TRY(hvd::launch_keys_to_pairs(k.d_src, k.n_src, v.d_vid_q, v.d_vid_t, v.rect, d_pkeys, d_pcnt,
+                                                                   n - 1, k.d_counters, g.stream));
                                  return HVD_OK;
                              }))
         return rc;
     g.v_pslots = pslots;
-    g.v_us[2] = us_since(t_fold);
+    g.v_us[2] = (int)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_fold).count();
     return HVD_OK;
 }
 
@@ -862,6 +878,29 @@ int hvd_vpdq_match_videos(const uint8_t* frames, const int64_t* offsets, int64_t
         }
     }
     return copy_out(res, (int64_t)res.size(), vmatch_less, out, cap, out_count, "video match");
+}
+
+int hvd_vpdq_frame_spread(const uint8_t* frames, const int64_t* offsets, int64_t V, int max_dist, int32_t* out_spread) {
+    if (int rc = need_ready()) return rc;
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    int64_t nf = 0;
+    if (int rc = check_offsets(offsets, V, &nf)) return rc;
+    if (nf == 0) return HVD_OK;
+    if (!out_spread) return fail(HVD_ERR_ARG, "out_spread is NULL");
+    if (nf < 2) {
+        out_spread[0] = 0;
+        return HVD_OK;
+    }
+    if (!frames) return fail(HVD_ERR_ARG, "frames is NULL");
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    void *d_img = nullptr, *d_spread = nullptr;
+    int32_t* d_vid = nullptr;
+    if (int rc = upload_library(frames, offsets, V, nf, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_img, &d_vid)) return rc;
+    SCR(S_SPREAD, 4 * (size_t)nf, d_spread);
+    if (int rc = hvd_dev_vpdq_frame_spread(d_img, nf, d_vid, max_dist, d_spread)) return rc;
+    HIP_TRY(hipMemcpyAsync(out_spread, d_spread, 4 * (size_t)nf, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
 }
 
 int hvd_vpdq_match_videos_cross(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* ids_q,
@@ -1004,6 +1043,28 @@ int hvd_dev_vpdq_emit_again(void* d_out, int64_t cap, void* d_count) {
     return HVD_OK;
 }
 
+int hvd_dev_vpdq_frame_spread(const void* d_img, int64_t n, const void* d_video, int max_dist, void* d_out_spread) {
+    if (int rc = need_ready()) return rc;
+    if (n < 0 || n >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "n=%lld out of range", (long long)n);
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    if (n > 0 && !d_out_spread) return fail(HVD_ERR_ARG, "d_out_spread is NULL");
+    if (n >= 2 && (!d_img || !d_video)) return fail(HVD_ERR_ARG, "d_img / d_video is NULL");
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    if (n < 2) {
+        if (n > 0) HIP_TRY(hipMemsetAsync(d_out_spread, 0, 4 * (size_t)n, g.stream));
+    } else {
+        // the key stage of the symmetric search on this context alone; no pair map is built, the last search's stays
+        VmKeys k;
+        if (int rc = vmatch_keys({d_img, (uint32_t)n, d_img, (uint32_t)n, false, (const int32_t*)d_video, (const int32_t*)d_video,
+                                  nullptr, nullptr, max_dist, 0, 1},
+                                 &k))
+            return rc;
+        HIP_TRY(hvd::launch_keys_to_spread(k.d_src, k.n_src, (unsigned long long)n, (int32_t*)d_out_spread, g.stream));
+    }
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
+}
+
 int hvd_dev_vpdq_match_videos_cross(const void* d_img_q, int64_t nq, const void* d_video_q, const void* d_excl_q,
                                     const void* d_img_t, int64_t nt, const void* d_video_t, const void* d_excl_t,
                                     int max_dist, int rank, int world, void* d_out, int64_t cap, void* d_count) {
@@ -1034,6 +1095,35 @@ int hvd_dev_kept_positions(const void* d_quality, int64_t n, const void* d_offse
     SCR(S_COUNTERS, 64, d_counters);
     HIP_TRY(hvd::launch_kept_positions((const int32_t*)d_quality, (unsigned long long)n, (const long long*)d_offsets, (uint32_t)V,
                                        min_quality, (int32_t*)d_out_pos, d_scr, d_counters + 2, g.stream));
+    return HVD_OK;
+}
+
+/* ---- common-frame filter: rule and position gather (k_spread.hip) ---- */
+
+int hvd_dev_common_frames(const void* d_spread, const void* d_offsets, int64_t V, int64_t n, int max_videos, int max_share,
+                          void* d_out_keep) {
+    if (int rc = need_ready()) return rc;
+    if (max_videos < 0) return fail(HVD_ERR_ARG, "max_videos=%d must not be negative", max_videos);
+    if (max_share < 0 || max_share > 100) return fail(HVD_ERR_ARG, "max_share=%d out of range [0,100] (per cent)", max_share);
+    if (n < 0 || V < 0 || n >= (1ll << 32) - 1 || V >= (1ll << 31) || !d_offsets) return fail(HVD_ERR_ARG, "bad arguments");
+    if (n > 0 && (!d_spread || !d_out_keep)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if (n > 0 && V == 0) return fail(HVD_ERR_ARG, "n=%lld frames in no video", (long long)n);
+    HIP_TRY(hvd::launch_common_rule((const int32_t*)d_spread, (const long long*)d_offsets, (uint32_t)V, (unsigned long long)n,
+                                    max_videos, max_share, (int32_t*)d_out_keep, g.stream));
+    return HVD_OK;
+}
+
+int hvd_dev_gather_kept_i32(const void* d_in, const void* d_keep, int64_t n, void* d_out) {
+    if (int rc = need_ready()) return rc;
+    if (n < 0 || n >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "n=%lld out of range", (long long)n);
+    if (n > 0 && (!d_in || !d_keep || !d_out)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    void* d_scr = nullptr;
+    unsigned long long* d_counters = nullptr;
+    SCR(S_COMPACT, hvd::compact_scratch_bytes((unsigned long long)n), d_scr);
+    SCR(S_COUNTERS, 64, d_counters);
+    HIP_TRY(hvd::launch_gather_kept_i32((const int32_t*)d_in, (const int32_t*)d_keep, (unsigned long long)n, (int32_t*)d_out, d_scr,
+                                        d_counters + 2, g.stream));
     return HVD_OK;
 }
 

@@ -418,6 +418,51 @@ class DeviceLibrary:
             lib.hvd_dev_sync()  # nothing may still run on a buffer that is freed here
         return aligned
 
+    def spread(self, max_dist: int | None = None) -> DeviceBuffer:
+        """hvd_dev_vpdq_frame_spread: int32 per kept frame, the number of OTHER videos of this library the frame occurs in
+        (DESIGN 4.13), as a DeviceBuffer that is the caller's to free. The compare and the key set of `match_videos`
+        without its fold; the records of the last search stay valid for hvd_dev_vpdq_emit_again."""
+        lib = _lib.ensure()
+        max_dist = _default_max_dist(max_dist)
+        with _DeviceScope() as scope:
+            d_spread = scope.keep(DeviceBuffer(4 * max(self.n_frames, 1)))
+            if max_dist < 0 or self.n_frames < 2:
+                d_spread.zero()
+            else:
+                _lib.check(lib.hvd_dev_vpdq_frame_spread(self.image().ptr, self.n_frames, self.d_video.ptr, max_dist, d_spread.ptr))
+        return d_spread
+
+    def without_common_frames(self, max_videos: int, max_share: int = 50,
+                              max_dist: int | None = None) -> tuple["DeviceLibrary", np.ndarray]:
+        """This library without the frames that many videos share (search.without_common_frames on what is in HBM): spread ->
+        rule (hvd_dev_common_frames) -> compaction (hvd_dev_compact_kept on the keep flags, bound 1). -> (a NEW library,
+        dropped int64[V]); this one is untouched and still the caller's to free. The result always has positions: this
+        library's, gathered (hvd_dev_gather_kept_i32), else the index inside this library's video
+        (hvd_dev_kept_positions) -- so `align*` work on the timeline they had before. Nothing but CSR offsets crosses PCIe."""
+        max_videos, max_share = search.check_common_rule(max_videos, max_share)
+        lib = _lib.ensure()
+        n, V = self.n_frames, self.n_videos
+        kept = C.c_int64(0)
+        with _DeviceScope() as scope:
+            d_spread = scope.temp(self.spread(max_dist))
+            d_keep = scope.temp(DeviceBuffer(4 * max(n, 1)))
+            _lib.check(lib.hvd_dev_common_frames(d_spread.ptr, self.d_offsets.ptr, V, n, max_videos, max_share, d_keep.ptr))
+            d_h, d_vid, d_pos = (scope.keep(DeviceBuffer(size * max(n, 1))) for size in (32, 4, 4))
+            d_off = scope.keep(DeviceBuffer(8 * (V + 1)))
+            _lib.check(lib.hvd_dev_compact_kept(self.d_hashes.ptr, d_keep.ptr, n, self.d_offsets.ptr, V, 1, d_h.ptr, d_off.ptr,
+                                                d_vid.ptr, C.byref(kept)))
+            if self.d_positions is not None:
+                _lib.check(lib.hvd_dev_gather_kept_i32(self.d_positions.ptr, d_keep.ptr, n, d_pos.ptr))
+            else:
+                _lib.check(lib.hvd_dev_kept_positions(d_keep.ptr, n, self.d_offsets.ptr, V, 1, d_pos.ptr))
+            _lib.check(lib.hvd_dev_sync())  # the keep flags are freed on the way out
+        library = DeviceLibrary(d_h, d_off, d_vid, kept.value, V)
+        library.d_positions = d_pos
+        lengths = self.lengths()
+        library._position_limit = self._position_limit if self.d_positions is not None else \
+            (int(lengths.max()) if lengths.size else 0)
+        return library, (lengths - library.lengths()).astype(np.int64)
+
     def free(self) -> None:
         for b in (self.d_hashes, self.d_offsets, self.d_video, self.d_img, self.d_positions):
             if b is not None:
@@ -615,6 +660,34 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
         return pairs, recs, library
     library.free()
     return pairs, recs, None
+
+
+def dedupe_frames_without_common_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                           max_videos: int, max_share: int = 50, threshold: float = 50.0,
+                                           policy: str | None = None, min_quality: int = vpdq.QUALITY_TOLERANCE):
+    """`dedupe_frames_on_device` with the common-frame filter between the quality filter and the search, on
+    the calling thread's context: hash -> quality filter + CSR -> spread -> rule -> compaction -> the video search on what
+    is left -> pair predicate. max_videos / max_share: DeviceLibrary.without_common_frames. -> (pairs int64[m,2], records,
+    dropped int64[V], timings); the records' counters and the predicate's lengths are those of the filtered library.
+    timings: hash_ms, common_ms (spread, rule, compaction) and search_ms, HIP-event times on the library stream;
+    compact_ms (host clock: quality filter + CSR, synchronous)."""
+    search.check_common_rule(max_videos, max_share)
+    timings: dict = {}
+    timed = _stage_timer(timings)
+    library = _hashed_library(
+        raw_offsets, 0, 1, None, lambda mine: timed("hash_ms", lambda: hash_frames_on_device(d_frames_ptr, int(mine[-1]), h, w, channels)),
+        32, lambda d_h, d_q, n, raw: DeviceLibrary.from_raw_hashes(d_h, d_q, n, raw, min_quality), timings)
+    del timings["gather_ms"]
+    try:
+        filtered, dropped = timed("common_ms", lambda: library.without_common_frames(max_videos, max_share))
+    finally:
+        library.free()
+    try:
+        recs = timed("search_ms", filtered.match_videos)
+        pairs = search.similar_video_pairs(recs, filtered.lengths(), threshold, policy)
+    finally:
+        filtered.free()
+    return pairs, recs, dropped, timings
 
 
 def group_records_on_device(d_records_ptr: int, n_records: int, d_record_count_ptr, V: int, d_score_ptr=None,

@@ -832,3 +832,78 @@ def cluster_hashes(db: np.ndarray, max_dist: int = DISTANCE_TOLERANCE, score=Non
         return pipeline.cluster_hashes_on_device(d_db.ptr, n, max_dist, score=score)
     finally:
         d_db.free()
+
+
+# ------------------------------------------------ intros and title cards: the common-frame filter ------
+
+def frame_spread(frames: np.ndarray, offsets: np.ndarray, max_dist: int | None = None) -> np.ndarray:
+    """In how many OTHER videos does every frame occur? int32 per frame hash: the number of videos v != the frame's own that
+    hold at least one frame within max_dist of it (hvd_vpdq_frame_spread: the compare and the key set of match_videos without
+    its fold). frames: uint8[sum,32]; offsets: int64[V+1] (CSR); max_dist: default the tolerance of the video search."""
+    frames, offsets, _ = _library(frames, offsets)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
+    spread = np.zeros(frames.shape[0], dtype=np.int32)
+    if max_dist < 0 or frames.shape[0] < 2:  # comparator "lt" at tolerance 0: nothing can match
+        return spread
+    _lib.check(_lib.ensure().hvd_vpdq_frame_spread(_ptr(frames), offsets.ctypes.data, offsets.size - 1, max_dist,
+                                                   spread.ctypes.data))
+    return spread
+
+
+def check_common_rule(max_videos, max_share) -> tuple[int, int]:
+    """The two parameters of the common-frame rule as ints, or ValueError. max_videos has no default on purpose: nobody has
+    measured a value that suits real libraries."""
+    if int(max_videos) != max_videos or int(max_share) != max_share:
+        raise ValueError("max_videos and max_share are integers")
+    if max_videos < 0:
+        raise ValueError("max_videos must not be negative")
+    if not 0 <= max_share <= 100:
+        raise ValueError("max_share is a percentage in [0, 100]")
+    return int(max_videos), int(max_share)
+
+
+def common_frame_mask(spread: np.ndarray, offsets: np.ndarray, max_videos: int, max_share: int = 50) -> np.ndarray:
+    """The rule of the common-frame filter in numpy (the device form is hvd_dev_common_frames): bool per frame, True = dropped.
+    A frame is common iff spread > max_videos; a video is a carrier iff it has c > 0 common frames and 100 c <= max_share len;
+    a frame is dropped iff it is common and its video is a carrier -- a video copied as a whole many times, or one that is
+    nothing but the intro, keeps every frame."""
+    max_videos, max_share = check_common_rule(max_videos, max_share)
+    spread = np.asarray(spread).reshape(-1)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != spread.size or (np.diff(offsets) < 0).any():
+        raise ValueError("offsets must be a CSR over the frames of spread")
+    common = spread.astype(np.int64) > max_videos
+    lengths = np.diff(offsets)
+    before = np.concatenate([[0], np.cumsum(common, dtype=np.int64)])
+    ncommon = before[offsets[1:]] - before[offsets[:-1]]
+    carrier = (ncommon > 0) & (100 * ncommon <= max_share * lengths)
+    return common & np.repeat(carrier, lengths)
+
+
+CommonFrames = namedtuple("CommonFrames", "hashes positions dropped spread")
+
+
+def without_common_frames(video_hashes, max_videos: int, max_share: int = 50, max_dist: int | None = None,
+                          positions=None) -> CommonFrames:
+    """The library without the frames that many videos share (a studio logo, a channel intro, an end card, a "subscribe"
+    slate), as if the quality filter had removed them: every search of this module then runs on the result as it is.
+    video_hashes: a sequence of VpdqHash / bytes. A frame is dropped iff it occurs in more than max_videos other videos
+    (`frame_spread`) and the common frames are at most max_share per cent of its video (`common_frame_mask`).
+    -> CommonFrames(hashes: one `bytes` per input video, possibly empty; positions: one int32 array per video, the index of
+    every kept frame in its input video -- or the input `positions` (one int sequence per video) of the kept frames --, for
+    the positions= argument of find_excerpts / find_segmented_excerpts / find_rate_excerpts, so timelines do not shift;
+    dropped: int64[V]; spread: int32 per input frame)."""
+    check_common_rule(max_videos, max_share)
+    blobs = [hash_blob(h) for h in video_hashes]
+    frames, offsets, lengths = pack_hashes(blobs)
+    pos = _positions_of(positions, blobs, lengths)
+    if pos is None:
+        pos = (np.arange(frames.shape[0], dtype=np.int64) - np.repeat(offsets[:-1], lengths)).astype(np.int32)
+    spread = frame_spread(frames, offsets, max_dist)
+    drop = common_frame_mask(spread, offsets, max_videos, max_share)
+    keep = ~drop
+    hashes = [frames[lo:hi][keep[lo:hi]].tobytes() for lo, hi in zip(offsets[:-1], offsets[1:])]
+    kept_pos = [pos[lo:hi][keep[lo:hi]] for lo, hi in zip(offsets[:-1], offsets[1:])]
+    before = np.concatenate([[0], np.cumsum(drop, dtype=np.int64)])
+    dropped = before[offsets[1:]] - before[offsets[:-1]]
+    return CommonFrames(hashes, kept_pos, dropped, spread)

@@ -232,6 +232,14 @@ int hvd_match_two(const uint8_t* a, int64_t na, const uint8_t* b, int64_t nb, in
 int hvd_vpdq_match_videos(const uint8_t* frames, const int64_t* offsets, int64_t V, int max_dist, hvd_vmatch* out,
                           int64_t cap, int64_t* out_count);
 
+/* In how many OTHER videos does every frame occur? out_spread[f] (int32 per frame hash) = the number of videos
+ * v != video(f) that hold at least one frame within max_dist of frame f: two matching frames of one video count once, frames of
+ * f's own video never. A studio logo, a channel intro or an end card has a large spread; the common-frame filter
+ * (hvd_dev_common_frames) deletes such frames before a search. frames / offsets / V as hvd_vpdq_match_videos; max_dist in
+ * [0, 127]. Upload, FP4 image, frame -> video map, then hvd_dev_vpdq_frame_spread; under a device group it runs on the calling
+ * thread's current context alone. */
+int hvd_vpdq_frame_spread(const uint8_t* frames, const int64_t* offsets, int64_t V, int max_dist, int32_t* out_spread);
+
 /* Query-set x target-set form of the same search: the steady-state workload after the first
  * run (new videos against the existing library; semantics of VpTreeManager.search_file,
  * db/vptree.py:865-902, for a batch of files). out: every (a = query video, b = target video)
@@ -659,6 +667,25 @@ int hvd_dev_vpdq_match_videos(const void* d_img, int64_t n, const void* d_video,
  * others into another collective. The pair map of that call stays valid until the next video search on this
  * process (the host-buffer entry points hvd_vpdq_match_videos[_cross] included). */
 int hvd_dev_vpdq_emit_again(void* d_out, int64_t cap, void* d_count);
+/* Device-resident form of hvd_vpdq_frame_spread: d_img / n / d_video as hvd_dev_vpdq_match_videos, d_out_spread int32[n]. The
+ * compare and the key set of that search without its fold: every key (frame f, video v) adds one to spread[f], no pair map
+ * is built, and the pair map of the last search stays valid for hvd_dev_vpdq_emit_again. Runs on the calling thread's context
+ * alone (no rank / world), uses library-owned scratch, is serialised with the video searches and synchronises the library
+ * stream before returning. max_dist in [0, 127]; n < 2 zeroes the output. */
+int hvd_dev_vpdq_frame_spread(const void* d_img, int64_t n, const void* d_video, int max_dist, void* d_out_spread);
+/* The rule of the common-frame filter, integers only. d_spread int32[n], d_offsets int64[V+1] (a CSR over the n frames) ->
+ * d_out_keep int32[n], 1 or 0. A frame is common iff spread > max_videos; a video is a carrier iff it has c > 0 common frames
+ * and 100 c <= max_share len (64-bit); a frame is dropped (keep 0) iff it is common and its video is a carrier -- so a video
+ * that is mass-copied as a whole, or is nothing but the intro, keeps every frame. max_videos >= 0, max_share in [0, 100]
+ * (HVD_ERR_ARG otherwise, nothing launched). d_out_keep is the d_quality operand of hvd_dev_compact_kept /
+ * hvd_dev_kept_positions with min_quality 1. One launch, enqueued on the library stream, no host synchronisation, nothing
+ * allocated; ranges are clamped to [0, n], so broken offsets give other flags, never an access out of bounds. */
+int hvd_dev_common_frames(const void* d_spread, const void* d_offsets, int64_t V, int64_t n, int max_videos, int max_share,
+                          void* d_out_keep);
+/* d_out[j] = d_in[f] for the j-th frame f with d_keep[f] >= 1 (int32 each; d_out: room for n): carries the positions of a
+ * library through the compaction hvd_dev_compact_kept does on its hashes. Enqueued on the library stream, no host
+ * synchronisation; library-owned scratch. */
+int hvd_dev_gather_kept_i32(const void* d_in, const void* d_keep, int64_t n, void* d_out);
 /* Query library x target library form (VpTreeManager.search_file for a batch, db/vptree.py:865-902).
  * d_excl_q / d_excl_t (both or neither): int32 per frame, frames with equal values are not compared. */
 int hvd_dev_vpdq_match_videos_cross(const void* d_img_q, int64_t nq, const void* d_video_q, const void* d_excl_q,
