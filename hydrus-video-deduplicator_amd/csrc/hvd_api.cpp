@@ -619,7 +619,7 @@ int hvd_debug_set(const char* key, int value) {
         return HVD_OK;
     }
     if (strcmp(key, "mfma_auto_mid") == 0) {  // form the auto variant runs on data with common false survivors
-        if (value != 0 && value != 18) return fail(HVD_ERR_ARG, "mfma_auto_mid: 18 (panel-mark queue form) or 0 (none: fetch or register form only)");
+        if (!hvd::mfma_auto_mid_ok(value)) return fail(HVD_ERR_ARG, "mfma_auto_mid: 18 (panel-mark queue form) or 0 (none: fetch or register form only)");
         hvd::g_mfma_auto_mid = (uint32_t)value;
         return HVD_OK;
     }
@@ -663,7 +663,7 @@ int hvd_debug_set(const char* key, int value) {
         return HVD_OK;
     }
     if (strcmp(key, "vmatch_variant") == 0) {  // tests / scripts/gpu_fuzz_k3.py: the video-level searches through one explicit form
-        if (value != 0 && value != 8 && value != 9 && value != 12 && value != 13 && value != 18)
+        if (value != 0 && !hvd::mfma_variant_known(value))
             return fail(HVD_ERR_ARG, "vmatch_variant: 0 (default) or an MFMA form: 8, 9, 12, 13 (auto), 18");
         // every context of the group: forms differ in their tile height, so ranks on different forms would walk different
         // (rb + cb) % world partitions -- tiles skipped or compared twice
@@ -745,21 +745,25 @@ int hvd_debug_get(const char* key, int* out_value) {
             }
     }
     if (int rc = need_ready()) return rc;
-    // what the probe of the last auto-variant launch saw and chose: form id, survivors over bits 0..127 / 128..255,
-    // 1 if the first stage ran on bits 128..255
-    // (word 4 is the probe's ticket; word 5 the survivors over bits 0..63 + 192..255, round 5; word 6 = kSelIdxClose the
-    // sampled block pairs within the index radius, summed only when the pass may run on the pigeonhole index)
-    static_assert(hvd::kSelIdxClose == 6, "mfma_probe_close reads select word 6");
-    const char* keys[7] = {"mfma_auto_form", "mfma_probe_survivors", "mfma_probe_survivors_hi", "mfma_auto_half", "", "mfma_probe_survivors_mix",
-                           "mfma_probe_close"};
-    for (int k = 0; k < 7; ++k)
-        if (keys[k][0] && strcmp(key, keys[k]) == 0) {
+    // what the probe of the last auto-variant launch saw and chose (select words, hvd_kernels.h; kSelIdxClose: the sampled block
+    // pairs within the index radius, summed only when the pass may run on the pigeonhole index)
+    static const struct {
+        const char* key;
+        int word;
+    } probe_keys[] = {{"mfma_auto_form", hvd::kSelForm},
+                      {"mfma_probe_survivors", hvd::kSelSurvivorsLo},
+                      {"mfma_probe_survivors_hi", hvd::kSelSurvivorsHi},
+                      {"mfma_auto_half", hvd::kSelSelection},
+                      {"mfma_probe_survivors_mix", hvd::kSelSurvivorsMix},
+                      {"mfma_probe_close", hvd::kSelIdxClose}};
+    for (const auto& pk : probe_keys)
+        if (strcmp(key, pk.key) == 0) {
             uint32_t* sel = nullptr;
             HIP_TRY(hvd::mfma_select_buffer(t_ctx, &sel));
-            uint32_t v[7] = {0, 0, 0, 0, 0, 0, 0};
+            uint32_t v[hvd::kSelectWords] = {};
             HIP_TRY(hipMemcpyAsync(v, sel, sizeof(v), hipMemcpyDeviceToHost, g.stream));
             HIP_TRY(hipStreamSynchronize(g.stream));
-            *out_value = (int)v[k];
+            *out_value = (int)v[pk.word];
             return HVD_OK;
         }
     if (strcmp(key, "allpairs_index_used") == 0 || strcmp(key, "allpairs_index_kcand") == 0) {
@@ -767,7 +771,7 @@ int hvd_debug_get(const char* key, int* out_value) {
         // the histograms were not built)
         uint32_t* sel = nullptr;
         HIP_TRY(hvd::mfma_select_buffer(t_ctx, &sel));
-        uint32_t v[16] = {};
+        uint32_t v[hvd::kSelectWords] = {};
         HIP_TRY(hipMemcpyAsync(v, sel, sizeof(v), hipMemcpyDeviceToHost, g.stream));
         HIP_TRY(hipStreamSynchronize(g.stream));
         if (key[15] == 'u') {
@@ -979,17 +983,20 @@ int hvd_dev_expand_fp4(const void* d_db, int64_t n, void* d_img) {
     return HVD_OK;
 }
 
-int hvd_dev_allpairs_hamming256_mfma(const void* d_db, const void* d_img, int64_t n, const void* d_group, int max_dist, int rank,
-                                     int world, void* d_pairs, int64_t cap, void* d_count, int variant) {
-    if (int rc = need_ready()) return rc;
+// What the three all-pairs entries share, in the order the errors are reported: n, max_dist in [0, max_dist_hi], rank / world,
+// the output buffer.
+static int check_allpairs_args(int64_t n, int max_dist, int max_dist_hi, int rank, int world, const void* d_pairs, int64_t cap,
+                               const void* d_count) {
     if (n < 0 || n >= (1ll << 32)) return fail(HVD_ERR_ARG, "n=%lld out of range [0,2^32)", (long long)n);
-    if (max_dist < 0 || max_dist > 256) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,256]", max_dist);
+    if (max_dist < 0 || max_dist > max_dist_hi) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,%d]", max_dist, max_dist_hi);
     if (world < 1 || rank < 0 || rank >= world) return fail(HVD_ERR_ARG, "bad rank/world %d/%d", rank, world);
     if (cap < 0 || !d_count || (cap > 0 && !d_pairs)) return fail(HVD_ERR_ARG, "bad output buffer");
-    if (n < 2) return HVD_OK;
-    if (!d_img || !d_db) return fail(HVD_ERR_ARG, "d_db / d_img is NULL");
-    if (variant != 8 && variant != 9 && variant != 12 && variant != 13 && variant != 18)
-        return fail(HVD_ERR_ARG, "unknown FP4-MFMA variant %d (8, 9, 12, 18, or 13 = chosen by the probe)", variant);
+    return HVD_OK;
+}
+
+// the C arguments -> the launch layer's; n, d_group: of the hashes behind d_db (the rectangle's targets, with its queries' groups)
+static hvd::AllPairsArgs allpairs_args(const void* d_db, int64_t n, const void* d_group, int max_dist, int rank, int world,
+                                       void* d_pairs, int64_t cap, void* d_count, int variant) {
     hvd::AllPairsArgs a;
     a.d_db = d_db;
     a.n = (uint32_t)n;
@@ -1003,6 +1010,18 @@ int hvd_dev_allpairs_hamming256_mfma(const void* d_db, const void* d_img, int64_
     a.variant = variant;
     a.col_chunk = 0;
     a.ctx_id = t_ctx;
+    return a;
+}
+
+int hvd_dev_allpairs_hamming256_mfma(const void* d_db, const void* d_img, int64_t n, const void* d_group, int max_dist, int rank,
+                                     int world, void* d_pairs, int64_t cap, void* d_count, int variant) {
+    if (int rc = need_ready()) return rc;
+    if (int rc = check_allpairs_args(n, max_dist, 256, rank, world, d_pairs, cap, d_count)) return rc;
+    if (n < 2) return HVD_OK;
+    if (!d_img || !d_db) return fail(HVD_ERR_ARG, "d_db / d_img is NULL");
+    if (!hvd::mfma_variant_known(variant))
+        return fail(HVD_ERR_ARG, "unknown FP4-MFMA variant %d (8, 9, 12, 18, or 13 = chosen by the probe)", variant);
+    const hvd::AllPairsArgs a = allpairs_args(d_db, n, d_group, max_dist, rank, world, d_pairs, cap, d_count, variant);
     hipError_t e = hvd::launch_allpairs_mfma(a, d_img, g.stream);
     if (e != hipSuccess) return fail(HVD_ERR_HIP, "launch_allpairs_mfma(variant=%d): %s", variant, hipGetErrorString(e));
     return HVD_OK;
@@ -1011,26 +1030,11 @@ int hvd_dev_allpairs_hamming256_mfma(const void* d_db, const void* d_img, int64_
 int hvd_dev_allpairs_hamming256(const void* d_db, int64_t n, const void* d_group, int max_dist, int rank, int world,
                                 void* d_pairs, int64_t cap, void* d_count, int variant) {
     if (int rc = need_ready()) return rc;
-    if (n < 0 || n >= (1ll << 32)) return fail(HVD_ERR_ARG, "n=%lld out of range [0,2^32)", (long long)n);
-    if (max_dist < 0 || max_dist > 256) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,256]", max_dist);
-    if (world < 1 || rank < 0 || rank >= world) return fail(HVD_ERR_ARG, "bad rank/world %d/%d", rank, world);
-    if (cap < 0 || !d_count || (cap > 0 && !d_pairs)) return fail(HVD_ERR_ARG, "bad output buffer");
+    if (int rc = check_allpairs_args(n, max_dist, 256, rank, world, d_pairs, cap, d_count)) return rc;
     if (n < 2) return HVD_OK;
     if (!d_db) return fail(HVD_ERR_ARG, "d_db is NULL");
     if (variant != 0 && variant != 1) return fail(HVD_ERR_ARG, "unknown popcount variant %d (0 | 1)", variant);
-    hvd::AllPairsArgs a;
-    a.d_db = d_db;
-    a.n = (uint32_t)n;
-    a.d_group = (const int32_t*)d_group;
-    a.max_dist = (uint32_t)max_dist;
-    a.rank = (uint32_t)rank;
-    a.world = (uint32_t)world;
-    a.d_pairs = (hvd_pair*)d_pairs;
-    a.cap = (unsigned long long)cap;
-    a.d_count = (unsigned long long*)d_count;
-    a.variant = variant;
-    a.col_chunk = 0;
-    a.ctx_id = t_ctx;
+    const hvd::AllPairsArgs a = allpairs_args(d_db, n, d_group, max_dist, rank, world, d_pairs, cap, d_count, variant);
     hipError_t e = hvd::launch_allpairs(a, g.stream);
     if (e != hipSuccess) return fail(HVD_ERR_HIP, "launch_allpairs(variant=%d): %s", variant, hipGetErrorString(e));
     return HVD_OK;
@@ -1040,37 +1044,19 @@ int hvd_dev_cross_hamming256_mfma(const void* d_img_q, int64_t nq, const void* d
                                   const void* d_group_q, const void* d_group_t, int max_dist, int rank, int world,
                                   void* d_pairs, int64_t cap, void* d_count) {
     if (int rc = need_ready()) return rc;
-    if (nq < 0 || nt < 0 || nq >= (1ll << 32) || nt >= (1ll << 32)) return fail(HVD_ERR_ARG, "set size out of range");
-    if (max_dist < 0 || max_dist >= 128)
-        return fail(HVD_ERR_ARG, "cross search supports max_dist in [0,127] (the reference uses 31), got %d", max_dist);
-    if (world < 1 || rank < 0 || rank >= world) return fail(HVD_ERR_ARG, "bad rank/world %d/%d", rank, world);
-    if (cap < 0 || !d_count || (cap > 0 && !d_pairs)) return fail(HVD_ERR_ARG, "bad output buffer");
+    if (nq < 0 || nq >= (1ll << 32)) return fail(HVD_ERR_ARG, "nq=%lld out of range [0,2^32)", (long long)nq);
+    // (the sign trick needs a positive threshold, and there is no popcount form of the rectangle; the reference uses 31)
+    if (int rc = check_allpairs_args(nt, max_dist, 127, rank, world, d_pairs, cap, d_count)) return rc;
     if ((d_group_q == nullptr) != (d_group_t == nullptr)) return fail(HVD_ERR_ARG, "pass both group maps or neither");
     if (nq == 0 || nt == 0) return HVD_OK;
     if (!d_img_q || !d_img_t) return fail(HVD_ERR_ARG, "NULL image");
     // packed hashes for the pair-queue form, derived from the images into the pool (this entry is handed images only)
     std::lock_guard<std::recursive_mutex> lk(g.h_mu);
     void *d_bits_t = nullptr, *d_bits_q = nullptr;
-    if (int rc = grow(&g.scr[Ctx::S_BITS], &g.scr_cap[Ctx::S_BITS], 32 * (size_t)nt)) return rc;
-    if (int rc = grow(&g.scr[Ctx::S_BITS2], &g.scr_cap[Ctx::S_BITS2], 32 * (size_t)nq)) return rc;
-    d_bits_t = g.scr[Ctx::S_BITS];
-    d_bits_q = g.scr[Ctx::S_BITS2];
-    HIP_TRY(hvd::launch_pack_fp4(d_img_t, (uint32_t)nt, d_bits_t, g.stream));
-    HIP_TRY(hvd::launch_pack_fp4(d_img_q, (uint32_t)nq, d_bits_q, g.stream));
-    hvd::AllPairsArgs a;
-    a.d_db = d_bits_t;
+    if (int rc = packed_hashes(Ctx::S_BITS, d_img_t, (uint32_t)nt, &d_bits_t)) return rc;
+    if (int rc = packed_hashes(Ctx::S_BITS2, d_img_q, (uint32_t)nq, &d_bits_q)) return rc;
+    hvd::AllPairsArgs a = allpairs_args(d_bits_t, nt, d_group_q, max_dist, rank, world, d_pairs, cap, d_count, HVD_DEFAULT_VARIANT);
     a.d_db_q = d_bits_q;
-    a.n = (uint32_t)nt;
-    a.d_group = (const int32_t*)d_group_q;
-    a.max_dist = (uint32_t)max_dist;
-    a.rank = (uint32_t)rank;
-    a.world = (uint32_t)world;
-    a.d_pairs = (hvd_pair*)d_pairs;
-    a.cap = (unsigned long long)cap;
-    a.d_count = (unsigned long long*)d_count;
-    a.variant = HVD_DEFAULT_VARIANT;
-    a.col_chunk = 0;
-    a.ctx_id = t_ctx;
     hipError_t e = hvd::launch_cross_mfma(a, d_img_q, (uint32_t)nq, d_img_t, (const int32_t*)d_group_t, g.stream);
     if (e != hipSuccess) return fail(HVD_ERR_HIP, "launch_cross_mfma: %s", hipGetErrorString(e));
     return HVD_OK;

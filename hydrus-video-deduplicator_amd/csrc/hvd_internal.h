@@ -140,4 +140,9 @@ int scratch(Ctx::Scr id, size_t need, void** out);
         if (int rc_ = hvdi::scratch(hvdi::Ctx::id, (bytes), (void**)&(ptr))) return rc_;     \
     } while (0)
 
+
+// hvd_search.cpp: the packed 32-byte hashes of the n rows of an FP4 image, into pool slot `slot`, on the context's stream (the
+// pair-queue form settles its candidates on them; callers hold h_mu)
+int packed_hashes(Ctx::Scr slot, const void* d_img, uint32_t n, void** d_bits);
+
 }  // namespace hvdi

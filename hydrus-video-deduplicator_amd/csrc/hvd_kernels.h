@@ -6,6 +6,7 @@
 
 #include "../../include/hvd_mi355x.h"
 #include "hvd_devhash.h"
+#include "hvd_mfma_forms.h"
 
 namespace hvd {
 
@@ -33,10 +34,9 @@ struct AllPairsArgs {
 hipError_t launch_allpairs(const AllPairsArgs& a, hipStream_t s);
 bool allpairs_geometry(uint32_t n, int variant, uint32_t* rows_per_block, uint32_t* col_chunk);
 
-// FP4-MFMA forms (k_hamming_mfma.hip), variants 8, 9, 12, 13 (auto), 18. d_img: fp4_rows_padded(n)*128 bytes.
-uint32_t fp4_rows_padded(uint32_t n);
-extern uint32_t g_mfma_col_chunk_max;
-extern uint32_t g_mfma_auto_mid, g_mfma_auto_mid_max_x100, g_mfma_queue_packed;
+// FP4-MFMA forms (k_hamming_mfma.hip): the variants of hvd_mfma_forms.h's table, and its auto variant. d_img:
+// fp4_rows_padded(n)*128 bytes. The knobs (hvd_debug_set keys of the same names; defined in one block in k_hamming_mfma.hip):
+extern uint32_t g_mfma_col_chunk_max, g_mfma_auto_mid, g_mfma_auto_mid_max_x100, g_mfma_queue_packed;
 extern int g_mfma_force_sel;
 hipError_t launch_expand_fp4(const void* d_db, uint32_t n, void* d_img, hipStream_t s);
 hipError_t launch_pack_fp4(const void* d_img, uint32_t n, void* d_db, hipStream_t s);  // image -> packed 32-byte hashes
@@ -48,12 +48,33 @@ hipError_t launch_allpairs_mfma(const AllPairsArgs& a, const void* d_img, hipStr
 // for queries and d_group_t for targets; pass both or neither).
 hipError_t launch_cross_mfma(const AllPairsArgs& a, const void* d_img_q, uint32_t nq, const void* d_img_t,
                              const int32_t* d_group_t, hipStream_t s);
-hipError_t mfma_select_buffer(int ctx_id, uint32_t** out);  // per context; [0] = form the auto variant ran last, [1] = probe survivors
+hipError_t mfma_select_buffer(int ctx_id, uint32_t** out);  // per context: the select words, hit context and clock words below
+
+// The select buffer, one per CONTEXT of the library (a context = one stream on one device; a group may hold two contexts on one
+// device, whose passes run concurrently on their own streams): kSelectWords select words, cleared in front of every pass of
+// the auto variant; the pass's hit context (HitCtx, k_hamming_mfma.hip); the clock telemetry's four 64-bit accumulators.
+enum : int {
+    kSelectWords = 16,
+    kSelCtxWord = 16,    // 32-bit word offset of the hit context (byte 64)
+    kSelClkWord = 192,   // ... of the clock accumulators (byte 768)
+    kSelectBytes = 1024,  // allocated
+};
+constexpr size_t kHitCtxMaxBytes = 4u * (kSelClkWord - kSelCtxWord);  // (k_hamming_mfma.hip asserts that HitCtx fits)
+static_assert(kSelectWords <= kSelCtxWord && kSelCtxWord < kSelClkWord && 4 * kSelClkWord + 4 * 8 <= kSelectBytes, "select buffer layout");
+// The probe's select words (k_prefilter_probe, probe_decide):
+enum : int {
+    kSelForm = 0,          // the form to run (the auto variant's launches of every other form return at once)
+    kSelSurvivorsLo = 1,   // first-stage survivors the probe counted over bits 0..127
+    kSelSurvivorsHi = 2,   // ... over bits 128..255
+    kSelSelection = 3,     // the selection the first stage runs on: 0 = bits 0..127, 1 = bits 128..255, 2 = bits 0..63 + 192..255
+    kSelProbeTicket = 4,   // the probe's last workgroup decides
+    kSelSurvivorsMix = 5,  // ... over bits 0..63 + 192..255
+};
 
 // Pigeonhole index path of the auto variant's self all-pairs pass (k_hamming_index.hip): 16 blocks of 16 bits; two hashes
 // within max_dist <= 31 agree to within r bits (r = 1 for max_dist 16..31, 0 below 16) in at least one block, so only pairs
-// that share a block key or whose keys differ in one bit are compared. Select words it owns (one buffer per context, cleared
-// with the probe's words in front of every pass):
+// that share a block key or whose keys differ in one bit are compared. Select words it owns (cleared with the probe's words in
+// front of every pass):
 enum : int {
     kSelIdxClose = 6,    // probe: sampled pairs x blocks with block distance <= r
     kSelIdxUsed = 7,     // 1: the index path runs this pass (the matrix-core forms return at once)
@@ -79,7 +100,7 @@ struct IndexRule {
 // (form: the matrix-core form the probe chose; any other value prices the costlier forms)
 __host__ __device__ inline bool index_wins(const IndexRule& q, double cand, double max_walk, uint32_t form) {
     if (q.force) return true;
-    const double t_mfma = q.pairs / q.world * (form == 9u ? q.fs_mfma_fetch : q.fs_mfma_other) * 1e-6;
+    const double t_mfma = q.pairs / q.world * (form == (uint32_t)kFormFetch ? q.fs_mfma_fetch : q.fs_mfma_other) * 1e-6;
     const double t_idx = q.fixed_ns + q.n * q.ps_hash * 1e-3 + cand / q.world * q.ps_cand * 1e-3 + max_walk * q.ps_crit * 1e-3;
     return t_idx < t_mfma;
 }

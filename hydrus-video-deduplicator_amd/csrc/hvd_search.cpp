@@ -486,6 +486,12 @@ int hvd_match_two(const uint8_t* a, int64_t na, const uint8_t* b, int64_t nb, in
 
 }  // extern "C"
 
+int hvdi::packed_hashes(Ctx::Scr slot, const void* d_img, uint32_t n, void** d_bits) {
+    if (int rc = scratch(slot, 32 * (size_t)n, d_bits)) return rc;
+    HIP_TRY(hvd::launch_pack_fp4(d_img, n, *d_bits, g.stream));
+    return HVD_OK;
+}
+
 namespace {
 
 unsigned long long pow2_at_least(unsigned long long x) {
@@ -613,12 +619,9 @@ int vmatch_keys(const VmArgs& v, VmKeys* keys) {
     // the pair-queue form of the all-pairs kernel settles its candidates on PACKED hashes; this entry is handed images only
     void *d_bits_t = nullptr, *d_bits_q = nullptr;
     const void *img_t = v.d_img_t, *img_q = v.d_img_q;
-    SCR(S_BITS, 32 * (size_t)v.nt, d_bits_t);
-    HIP_TRY(hvd::launch_pack_fp4(v.d_img_t, v.nt, d_bits_t, g.stream));
-    if (v.rect) {
-        SCR(S_BITS2, 32 * (size_t)v.nq, d_bits_q);
-        HIP_TRY(hvd::launch_pack_fp4(v.d_img_q, v.nq, d_bits_q, g.stream));
-    }
+    if (int rc = packed_hashes(Ctx::S_BITS, v.d_img_t, v.nt, &d_bits_t)) return rc;
+    if (v.rect)
+        if (int rc = packed_hashes(Ctx::S_BITS2, v.d_img_q, v.nq, &d_bits_q)) return rc;
     // Round 5: the search runs on hashes rewritten in a bit order chosen from the library itself (choose_bit_order): the first
     // stage then sees the 128 least entangled bits. Library scratch only -- the caller's image is left as it is -- and the
     // same order for rows and columns, so every distance, and with it every record, is what it was.

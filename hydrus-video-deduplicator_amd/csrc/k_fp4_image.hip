@@ -131,8 +131,6 @@ __global__ __launch_bounds__(256) void k_reorder_bits(const uint32_t* __restrict
 
 namespace hvd {
 
-uint32_t fp4_rows_padded(uint32_t n) { return ((n ? n : 1u) + 1023u) / 1024u * 1024u; }
-
 hipError_t launch_expand_fp4(const void* d_db, uint32_t n, void* d_img, hipStream_t s) {
     const uint32_t n_pad = fp4_rows_padded(n);
     const uint64_t threads = (uint64_t)n_pad * 8u;

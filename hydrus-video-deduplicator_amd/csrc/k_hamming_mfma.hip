@@ -30,6 +30,7 @@
 #include <string.h>
 
 #include <mutex>
+#include <utility>
 
 #include "hvd_devhash.h"
 #include "hvd_fp4.h"
@@ -134,6 +135,7 @@ __device__ __forceinline__ void append_pair_wg(hvd_pair* out, unsigned long long
 }
 
 constexpr int kSuper = 128;  // candidates per LDS super-panel (256: -4 % with the prefilter, +2 % without)
+static_assert(kSuper == (int)hvd::kSuperPanel, "the column-chunk rule (hvd_mfma_forms.h) rounds to whole super-panels");
 
 __device__ __forceinline__ v4i as_v4i(const uint4& v) { return v4i{(int)v.x, (int)v.y, (int)v.z, (int)v.w}; }
 
@@ -164,6 +166,7 @@ struct HitCtx {
     uint32_t max_dist;
     unsigned long long* clk;  // clock telemetry: {shader cycles, constant-rate ticks, sampled workgroups} accumulated over passes
 };
+static_assert(sizeof(HitCtx) <= hvd::kHitCtxMaxBytes, "the hit context runs into the select buffer's clock words (hvd_kernels.h)");
 
 // Hits of one 32x32 tile whose accumulators hold the full 256-bit dot products: acc[r] belongs to
 // row = row0 + (r&3) + 8*(r>>2) + 4*(lane>>5), column j (C/D layout of the 32x32 MFMA).
@@ -349,7 +352,7 @@ __device__ __forceinline__ uint32_t sign_popc(const uint4& x, const uint4& y, ui
     return acc + __popc(x.x ^ y.x) + __popc(x.y ^ y.y) + __popc(x.z ^ y.z) + __popc(x.w ^ y.w);
 }
 
-// Which 128 bits the first stage sees (`sel`, the probe's choice, select[3]): 0 = bits 0..127, 1 = bits 128..255,
+// Which 128 bits the first stage sees (`sel`, the probe's choice, kSelSelection): 0 = bits 0..127, 1 = bits 128..255,
 // 2 = bits 0..63 and 192..255 (round 5: on config 5's frame hashes this mix lets 3x fewer unrelated pairs through than
 // either half, and a settled entry is what the pair-queue forms pay for). In 8-byte units of a packed hash (u0..u3) the
 // first stage sees {u0,u1} / {u2,u3} / {u0,u3}; the settlement's filter looks at the OTHER 128 bits, which are one
@@ -654,7 +657,7 @@ __global__ __launch_bounds__(256, ((TILES == 4 && NBR == 4 && S1 == 2) || QUEUE)
 
     // data-dependent choice between the forms of this kernel (launch_auto): all are launched, the probe's verdict lets one
     // of them run -- or none, when the pass runs on the pigeonhole index (k_hamming_index.hip)
-    if (select != nullptr && (select[0] != select_id || select[hvd::kSelIdxUsed] != 0u)) return;
+    if (select != nullptr && (select[hvd::kSelForm] != select_id || select[hvd::kSelIdxUsed] != 0u)) return;
     // Clock telemetry (round 6): one workgroup in eight brackets its lifetime with the shader-cycle counter (s_memtime) and the
     // constant-rate counter (s_memrealtime) and adds both deltas to the context's accumulators -- effective shader clock of
     // a pass = cycles / ticks x the tick rate, averaged over the sampled workgroups' lifetimes (hvd_debug_get "mfma_pass_khz").
@@ -666,12 +669,12 @@ __global__ __launch_bounds__(256, ((TILES == 4 && NBR == 4 && S1 == 2) || QUEUE)
         g_clk_t0[1] = sample ? (unsigned long long)__builtin_amdgcn_s_memrealtime() : 0ull;
     }
 
-    // Which 128 bits the first stage sees is the probe's choice too (select[3]): the image keeps bits 0..127 in chunks
+    // Which 128 bits the first stage sees is the probe's choice too (kSelSelection): the image keeps bits 0..127 in chunks
     // 0..3 and bits 128..255 in chunks 4..7, so "the other half first" is chunk ^ 4 in every fragment address -- a
     // launch-uniform XOR into the slot swizzle. The full-distance paths sum over all eight chunks and do not care.
     // Round 5: a third selection, bits 0..63 + 192..255 (other_unit_of, above): k-step s reads chunks 2s, 2s+1 XOR selx_s with
     // selx_0 = selx_2, selx_1 = selx_3 in {0, 4}, so that the four steps still cover every chunk once.
-    const uint32_t sel = select != nullptr ? (select[3] & 3u) : sel_arg;
+    const uint32_t sel = select != nullptr ? (select[hvd::kSelSelection] & 3u) : sel_arg;
     const uint32_t selx0 = sel == 1u ? 4u : 0u, selx1 = sel != 0u ? 4u : 0u;
 
     // Tile (rb, cb) belongs to rank (rb + cb) mod world. Round 5: only a rank's OWN tiles are launched (grid.y = ceil(n_cb /
@@ -883,7 +886,7 @@ __global__ __launch_bounds__(256, ((TILES == 4 && NBR == 4 && S1 == 2) || QUEUE)
 // Probe for the data-dependent choice of the kernel form: over a strided sample of the two images (up to 4096 rows
 // x 4096 columns), how often do the first 128 bits of two hashes agree to within the tolerance? In the FP4 image a
 // differing bit is a differing sign nibble, so the partial distance is popcount(x ^ y) over chunks 0..3.
-// One lane per sample row, 64 sample columns per workgroup broadcast from LDS. select[1] += survivors.
+// One lane per sample row, 64 sample columns per workgroup broadcast from LDS. select[kSelSurvivorsLo] += survivors.
 constexpr uint32_t kProbeRows = 4096, kProbeCols = 4096;
 
 // (round 4: 64 sample columns per workgroup instead of 256 -- 1024 workgroups instead of 256, four waves per SIMD instead of a
@@ -966,7 +969,7 @@ __global__ __launch_bounds__(256) void k_prefilter_probe(const uint4* __restrict
     // one pair of atomics per WORKGROUP (same-address device atomics take ~8 ns each: per wave they were 65 us of a probe over
     // frame hashes), and the workgroup that finishes last turns the two sums into the decision -- one launch less per pass (a
     // one-lane kernel costs ~5 us plus the gap in front of it). No fence anywhere: the sums travel in atomics, which are
-    // performed at the memory side, and a workgroup takes its ticket (select[4], zeroed by k_set_hit_ctx with the rest) only
+    // performed at the memory side, and a workgroup takes its ticket (kSelProbeTicket, zeroed by k_set_hit_ctx with the rest) only
     // after its own additions have RETURNED.
     __shared__ uint32_t part[4][4];
     if ((threadIdx.x & 63u) == 0u) {
@@ -982,14 +985,14 @@ __global__ __launch_bounds__(256) void k_prefilter_probe(const uint4* __restrict
         const uint32_t c_mix = part[2][0] + part[2][1] + part[2][2] + part[2][3];
         const uint32_t c_close = part[3][0] + part[3][1] + part[3][2] + part[3][3];
         uint32_t seen = 0;
-        if (c_lo) seen += atomicAdd(&select[1], c_lo);
-        if (c_hi) seen += atomicAdd(&select[2], c_hi);
-        if (c_mix) seen += atomicAdd(&select[5], c_mix);
+        if (c_lo) seen += atomicAdd(&select[hvd::kSelSurvivorsLo], c_lo);
+        if (c_hi) seen += atomicAdd(&select[hvd::kSelSurvivorsHi], c_hi);
+        if (c_mix) seen += atomicAdd(&select[hvd::kSelSurvivorsMix], c_mix);
         if (c_close) seen += atomicAdd(&select[hvd::kSelIdxClose], c_close);
         asm volatile("" ::"v"(seen));  // (the returning form, and its result waited for)
-        if (atomicAdd(&select[4], 1u) == gridDim.x * gridDim.y - 1u)
-            probe_decide(select, atomicAdd(&select[1], 0u), atomicAdd(&select[2], 0u), atomicAdd(&select[5], 0u),
-                         atomicAdd(&select[hvd::kSelIdxClose], 0u), rule);
+        if (atomicAdd(&select[hvd::kSelProbeTicket], 1u) == gridDim.x * gridDim.y - 1u)
+            probe_decide(select, atomicAdd(&select[hvd::kSelSurvivorsLo], 0u), atomicAdd(&select[hvd::kSelSurvivorsHi], 0u),
+                         atomicAdd(&select[hvd::kSelSurvivorsMix], 0u), atomicAdd(&select[hvd::kSelIdxClose], 0u), rule);
     }
 }
 
@@ -1001,7 +1004,7 @@ __global__ void k_set_hit_ctx(HitCtx* __restrict__ dst, const HitCtx src, uint32
     *dst = src;
     if (select != nullptr) {
 #pragma unroll
-        for (int k = 0; k < 16; ++k) select[k] = 0u;
+        for (int k = 0; k < hvd::kSelectWords; ++k) select[k] = 0u;
     }
 }
 
@@ -1033,12 +1036,12 @@ __device__ void probe_decide(uint32_t* __restrict__ select, uint32_t lo, uint32_
         sel = (uint32_t)rule.force_sel;
         best = sel == 0u ? lo : sel == 1u ? hi : mix;
     }
-    select[3] = sel;
+    select[hvd::kSelSelection] = sel;
     const double rate = rule.pairs ? (double)best / (double)rule.pairs : 0.0;
     uint32_t form = rule.id_rare;
     if (rate * (double)rule.pairs_per_step > 0.01)
         form = (rule.id_mid != 0u && rate * 1024.0 <= (double)rule.mid_max_per_tile) ? rule.id_mid : rule.id_often;
-    select[0] = form;
+    select[hvd::kSelForm] = form;
     // Pigeonhole index: the sample's close blocks estimate the pass's candidates; the histograms are built (and the exact
     // decision taken from them, k_index_stats) only if the index could win at half that estimate.
     if (rule.idx_r != kNoIndex) {
@@ -1051,158 +1054,125 @@ __device__ void probe_decide(uint32_t* __restrict__ select, uint32_t lo, uint32_
 
 namespace hvd {
 
-static uint32_t round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
-
-constexpr int kClkWord = 192;  // 32-bit word offset of the clock telemetry's accumulators in a context's select buffer (byte 768)
-
-
-// auto variant (13): the form for data with common false survivors (18 = panel-mark queue; 0 = none, i.e. round 3's two-way
-// choice) and the survivor density (per 1024-pair tile, as the probe estimates it) up to which it is preferred over the register form
-uint32_t g_mfma_queue_packed = 1;  // 0: the pair queue settles from the FP4 images even when packed hashes are at hand (tests)
-uint32_t g_mfma_auto_mid = 18;
-int g_mfma_force_sel = -1;  // hvd_debug_set "mfma_force_sel": -1 the probe chooses (explicit forms: bits 0..127); 0 | 1 | 2 forced
-uint32_t g_mfma_auto_mid_max_x100 = 500;  // (scripts/gpu_k2_rate_sweep.py: the panel-mark queue takes 0.61-0.67 of the register form's time
-                                          // at 1-2.7 survivors per tile, 0.79 at 4, 0.88 at 5.3, 1.23 at 8; round 4's first queue form, 15,
-                                          // won up to ~1 and the boundary was 1.3)
-
-
-uint32_t g_mfma_col_chunk_max = 8192;  // tuning knob (hvd_debug_set "mfma_col_chunk_max"); 2048..32768 within 3 %
-
-static uint32_t pick_col_chunk_m(uint32_t n_pad, uint32_t rows_per_wg) {
-    uint64_t n_rb = (n_pad + rows_per_wg - 1) / rows_per_wg;
-    uint64_t want_cb = (8192 + n_rb - 1) / n_rb;
-    if (want_cb < 1) want_cb = 1;
-    uint64_t chunk = (n_pad + want_cb - 1) / want_cb;
-    if (chunk < 256) chunk = 256;
-    if (chunk > g_mfma_col_chunk_max) chunk = g_mfma_col_chunk_max;
-    chunk = (chunk + kSuper - 1) / kSuper * kSuper;
-    if ((n_pad + chunk - 1) / chunk > 65535u) chunk = round_up((n_pad + 65534u) / 65535u, kSuper);
-    return (uint32_t)chunk;
-}
-
-struct MfmaForm {
-    int tiles, nbr, s1, waves = 4;
-};
-// variants: 8 = 256 bits at once (the reference form); 9 = 128-bit first stage, survivors fetch their other half (uniform
-// data); 12 = 128-bit first stage, second stage out of registers (4 tiles; dense data); 18 = 128-bit first stage, survivors
-// through the panel-mark queue (frame hashes); 13 = 9, 18 or 12, chosen per launch by the probe.
-static bool mfma_form(int variant, MfmaForm* f) {
-    switch (variant) {
-        case 8: *f = {8, 4, 4}; return true;
-        case 9: case 13: case 18: *f = {8, 2, 2}; return true;
-        case 12: *f = {4, 4, 2}; return true;
-        default: return false;
-    }
-}
+// The knobs of the matrix-core pass (hvd_debug_set keys of the same names).
+// column chunk of the self pass at most this; 2048..32768 within 3 %
+uint32_t g_mfma_col_chunk_max = 8192;
+// auto variant: the form for data with common false survivors (mfma_auto_mid_ok: the panel-mark queue; 0 = none, the two-way choice)
+uint32_t g_mfma_auto_mid = kFormAutoMidDefault;
+// ... preferred over the register form up to this survivor density (x 0.01 per 1024-pair tile, as the probe estimates it).
+// scripts/gpu_k2_rate_sweep.py: the panel-mark queue takes 0.61-0.67 of the register form's time at 1-2.7 survivors per tile,
+// 0.79 at 4, 0.88 at 5.3, 1.23 at 8; round 4's first queue form won up to ~1 and the boundary was 1.3
+uint32_t g_mfma_auto_mid_max_x100 = 500;
+// 0: the pair queue settles from the FP4 images even when packed hashes are at hand (tests)
+uint32_t g_mfma_queue_packed = 1;
+// which 128 bits the first stage sees: -1 the probe chooses (explicit forms: bits 0..127); 0 | 1 | 2 forced
+int g_mfma_force_sel = -1;
 
 bool allpairs_mfma_geometry(uint32_t n, int variant, uint32_t* rows_per_block, uint32_t* col_chunk) {
-    MfmaForm f;
-    if (!mfma_form(variant, &f)) return false;
-    *rows_per_block = 32u * (uint32_t)f.tiles * (uint32_t)f.waves;
-    *col_chunk = pick_col_chunk_m(fp4_rows_padded(n), *rows_per_block);
+    const MfmaForm* f = mfma_form(variant);
+    if (!f) return false;
+    const MfmaGeometry geo = mfma_geometry(*f, n, fp4_rows_padded64(n), false, g_mfma_col_chunk_max);
+    *rows_per_block = geo.rows_per_wg;
+    *col_chunk = geo.col_chunk;
     return true;
 }
 
-static HitCtx hit_ctx(const AllPairsArgs& a, bool rect, uint32_t nq, const int32_t* d_group_t, int s1, const void* d_img_q,
-                      const void* d_img_t) {
+// One pass of the matrix-core kernels, rows x columns. The columns are the a.n hashes of the image d_img_t. The rows of a
+// rectangle are the nq hashes of d_img_q (groups: a.d_group for the rows, d_group_t for the columns); a self pass has its
+// columns for rows: d_img_q == d_img_t, nq == a.n, no d_group_t.
+struct MfmaPass {
+    const AllPairsArgs& a;
+    const void* d_img_t;
+    const void* d_img_q;
+    uint32_t nq;
+    const int32_t* d_group_t;
+    bool rect;
+    hipStream_t s;
+    uint32_t rows() const { return nq; }
+    const uint4* row_image() const { return (const uint4*)d_img_q; }
+    const uint4* col_image() const { return (const uint4*)d_img_t; }
+};
+
+// sel: the context's select buffer (mfma_select_buffer)
+static HitCtx hit_ctx(const MfmaPass& p, int s1, uint32_t* sel) {
+    const AllPairsArgs& a = p.a;
     HitCtx c;
     c.group = a.d_group;
-    c.group_t = d_group_t;
+    c.group_t = p.d_group_t;
     c.out = a.d_pairs;
     c.cap = a.cap;
     c.count = a.d_count;
     c.vs = a.sink;
     c.n = a.n;
-    c.nq = nq;
+    c.nq = p.rect ? p.nq : 0u;
     c.thr_full = 256.0f - 2.0f * (float)a.max_dist;
-    c.rect = rect ? 1u : 0u;
+    c.rect = p.rect ? 1u : 0u;
     c.acc_start = (float)(64 * s1) - 2.0f * (float)a.max_dist - 1.0f;
-    c.img_q = (const uint4*)d_img_q;
-    c.img_t = (const uint4*)d_img_t;
+    c.img_q = p.row_image();
+    c.img_t = p.col_image();
     c.db_t = (const uint4*)a.d_db;
-    c.db_q = (const uint4*)(rect ? a.d_db_q : a.d_db);
+    c.db_q = (const uint4*)(p.rect ? a.d_db_q : a.d_db);
     if (c.db_q == nullptr || c.db_t == nullptr || !g_mfma_queue_packed) c.db_q = c.db_t = nullptr;
     c.max_dist = a.max_dist;
-    uint32_t* sel = nullptr;
-    c.clk = mfma_select_buffer(a.ctx_id, &sel) == hipSuccess ? reinterpret_cast<unsigned long long*>(sel + kClkWord) : nullptr;
+    c.clk = reinterpret_cast<unsigned long long*>(sel + kSelClkWord);
     return c;
 }
 
-// One launch of one form. rect: rows = the nq hashes of d_img_q, columns = the a.n hashes of d_img.
-template <int T, int NBR, int S1, bool QUEUE = false>
-static hipError_t launch_form(const AllPairsArgs& a, const void* d_img, bool rect, const void* d_img_q, uint32_t nq,
-                              const int32_t* d_group_t, const uint32_t* d_select, uint32_t select_id, hipStream_t s,
-                              bool write_ctx = true) {
+// One launch of the form kMfmaForms[I]. write_ctx: the launch writes the pass's hit context first (an explicit form; the auto
+// variant has written one context for its three launches: they share S1, the only form-dependent field). d_select: nullptr,
+// or the auto variant's select words -- the kernel returns at once unless they name this form.
+template <size_t I>
+static hipError_t launch_form(std::integral_constant<size_t, I>, const MfmaPass& p, const uint32_t* d_select, bool write_ctx) {
+    constexpr MfmaForm F = kMfmaForms[I];
+    const AllPairsArgs& a = p.a;
     const uint32_t n_pad = fp4_rows_padded(a.n);
-    constexpr uint32_t ROWS = 32u * T * 4u;
-    const uint32_t nrows = rect ? nq : a.n;
-    const uint64_t n_rb = (nrows + ROWS - 1) / ROWS;
-    uint64_t chunk;
-    if (!rect) {
-        chunk = pick_col_chunk_m(n_pad, ROWS);
-    } else {  // column chunk sized for the rectangle: enough tiles to fill the chip even when nq is small
-        const uint64_t want_cb = (4096 + n_rb - 1) / n_rb;
-        chunk = (n_pad + want_cb - 1) / want_cb;
-        if (chunk < 256) chunk = 256;
-        if (chunk > 4096) chunk = 4096;
-        chunk = (chunk + kSuper - 1) / kSuper * kSuper;
-        if ((n_pad + chunk - 1) / chunk > 65535u) chunk = round_up((n_pad + 65534u) / 65535u, kSuper);
-    }
-    const uint64_t n_cb = (n_pad + chunk - 1) / chunk;
-    dim3 grid((unsigned)n_rb, (unsigned)(a.world > 1u ? (n_cb + a.world - 1) / a.world : n_cb));  // (own tiles only: see the kernel)
+    const MfmaGeometry geo = mfma_geometry(F, p.rows(), n_pad, p.rect, g_mfma_col_chunk_max);
+    const uint64_t n_cb = geo.col_blocks;
+    dim3 grid((unsigned)geo.row_blocks, (unsigned)(a.world > 1u ? (n_cb + a.world - 1) / a.world : n_cb));  // (own tiles only: see the kernel)
     uint32_t* buf = nullptr;
     hipError_t e = mfma_select_buffer(a.ctx_id, &buf);
     if (e != hipSuccess) return e;
-    HitCtx* ctx = reinterpret_cast<HitCtx*>(buf + 16);
-    // (the auto variant writes one context for its three launches: they share S1, the only form-dependent field)
-    if (write_ctx)
-        hipLaunchKernelGGL(k_set_hit_ctx, dim3(1), dim3(1), 0, s, ctx, hit_ctx(a, rect, nq, d_group_t, S1, rect ? d_img_q : d_img, d_img),
-                           (uint32_t*)nullptr);
-    if (rect)
-        hipLaunchKernelGGL((k_allpairs_mfma<T, NBR, S1, true, QUEUE>), grid, dim3(256), 0, s, (const uint4*)d_img, a.n, n_pad,
-                           a.max_dist, (uint32_t)chunk, a.rank, a.world, (const uint4*)d_img_q, ctx, d_select,
-                           select_id, (uint32_t)(g_mfma_force_sel > 0 ? g_mfma_force_sel : 0));
+    HitCtx* ctx = reinterpret_cast<HitCtx*>(buf + kSelCtxWord);
+    if (write_ctx) hipLaunchKernelGGL(k_set_hit_ctx, dim3(1), dim3(1), 0, p.s, ctx, hit_ctx(p, F.s1, buf), (uint32_t*)nullptr);
+    const uint32_t sel_arg = (uint32_t)(g_mfma_force_sel > 0 ? g_mfma_force_sel : 0);
+    if (p.rect)
+        hipLaunchKernelGGL((k_allpairs_mfma<F.tiles, F.nbr, F.s1, true, F.queue>), grid, dim3(256), 0, p.s, p.col_image(), a.n, n_pad,
+                           a.max_dist, geo.col_chunk, a.rank, a.world, p.row_image(), ctx, d_select, (uint32_t)F.id, sel_arg);
     else
-        hipLaunchKernelGGL((k_allpairs_mfma<T, NBR, S1, false, QUEUE>), grid, dim3(256), 0, s, (const uint4*)d_img, a.n, n_pad,
-                           a.max_dist, (uint32_t)chunk, a.rank, a.world, (const uint4*)nullptr, ctx, d_select,
-                           select_id, (uint32_t)(g_mfma_force_sel > 0 ? g_mfma_force_sel : 0));
+        hipLaunchKernelGGL((k_allpairs_mfma<F.tiles, F.nbr, F.s1, false, F.queue>), grid, dim3(256), 0, p.s, p.col_image(), a.n, n_pad,
+                           a.max_dist, geo.col_chunk, a.rank, a.world, (const uint4*)nullptr, ctx, d_select, (uint32_t)F.id, sel_arg);
     return hipGetLastError();
 }
 
-static hipError_t launch_variant(int variant, const AllPairsArgs& a, const void* d_img, bool rect, const void* d_img_q,
-                                 uint32_t nq, const int32_t* d_group_t, const uint32_t* d_select, hipStream_t s,
-                                 bool write_ctx = true) {
-    switch (variant) {
-        case 8: return launch_form<8, 4, 4>(a, d_img, rect, d_img_q, nq, d_group_t, d_select, 8u, s, write_ctx);
-        case 9: return launch_form<8, 2, 2>(a, d_img, rect, d_img_q, nq, d_group_t, d_select, 9u, s, write_ctx);
-        case 12: return launch_form<4, 4, 2>(a, d_img, rect, d_img_q, nq, d_group_t, d_select, 12u, s, write_ctx);
-        case 18: return launch_form<8, 2, 2, true>(a, d_img, rect, d_img_q, nq, d_group_t, d_select, 18u, s, write_ctx);
-        default: return hipErrorInvalidValue;
-    }
+// variant -> its row of the table -> launch_form (instantiated in the table's order)
+template <size_t... I>
+static hipError_t launch_variant(std::index_sequence<I...>, int variant, const MfmaPass& p, const uint32_t* d_select, bool write_ctx) {
+    hipError_t e = hipErrorInvalidValue;
+    // (a left fold: the forms are instantiated first to last)
+    (void)(... || (kMfmaForms[I].id == variant && ((e = launch_form(std::integral_constant<size_t, I>{}, p, d_select, write_ctx)), true)));
+    return e;
+}
+static hipError_t launch_variant(int variant, const MfmaPass& p, const uint32_t* d_select, bool write_ctx) {
+    return launch_variant(std::make_index_sequence<(size_t)kMfmaFormCount>{}, variant, p, d_select, write_ctx);
 }
 
-// select[0] = form to run, select[1] / select[2] / select[5] = first-stage survivors the probe counted over bits 0..127 /
-// 128..255 / 0..63 + 192..255, select[3] = the selection the first stage runs on (0 / 1 / 2), select[4] = the probe's ticket. One buffer per CONTEXT of the library (a context = one stream on one
-// device; a group may hold two contexts on one device, whose passes run concurrently on their own streams).
 constexpr int kMaxSelect = 16;
 static uint32_t* g_select[kMaxSelect] = {};
 // The hit context and the select words are device state written in stream order right before the kernels that
 // read them: two host threads enqueueing passes at once must not interleave "write context, launch" sequences.
 static std::mutex g_launch_mu;
 
+// (the buffer's layout and its select words: hvd_kernels.h)
 hipError_t mfma_select_buffer(int ctx_id, uint32_t** out) {
     if (ctx_id < 0 || ctx_id >= kMaxSelect) return hipErrorInvalidValue;
     static std::mutex alloc_mu;
     std::lock_guard<std::mutex> lk(alloc_mu);
     if (!g_select[ctx_id]) {
-        static_assert(sizeof(HitCtx) <= 192, "hit context does not fit its slot");
-        // 64 B of select words (probe 0..5, index 6..12: hvd_kernels.h), the hit context at +64, the clock telemetry's four
-        // accumulators at +768 (kClkWord)
         uint32_t* p = nullptr;
-        hipError_t e = hipMalloc((void**)&p, 1024);
+        hipError_t e = hipMalloc((void**)&p, kSelectBytes);
         // (hipMemset on device memory does not wait: without the synchronisation it can land on top of the first context
         // that the non-blocking library stream writes)
-        if (e == hipSuccess) e = hipMemset(p, 0, 1024);
+        if (e == hipSuccess) e = hipMemset(p, 0, kSelectBytes);
         if (e == hipSuccess) e = hipDeviceSynchronize();
         if (e != hipSuccess) {
             if (p) (void)hipFree(p);
@@ -1220,7 +1190,7 @@ hipError_t mfma_clock_reset(int ctx_id, hipStream_t s) {
     uint32_t* sel = nullptr;
     hipError_t e = mfma_select_buffer(ctx_id, &sel);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_clk_reset, dim3(1), dim3(1), 0, s, reinterpret_cast<unsigned long long*>(sel + kClkWord));
+    hipLaunchKernelGGL(k_clk_reset, dim3(1), dim3(1), 0, s, reinterpret_cast<unsigned long long*>(sel + kSelClkWord));
     return hipGetLastError();
 }
 
@@ -1228,7 +1198,7 @@ hipError_t mfma_clock_read(int ctx_id, hipStream_t s, unsigned long long out[4])
     uint32_t* sel = nullptr;
     hipError_t e = mfma_select_buffer(ctx_id, &sel);
     if (e != hipSuccess) return e;
-    e = hipMemcpyAsync(out, sel + kClkWord, 32, hipMemcpyDeviceToHost, s);
+    e = hipMemcpyAsync(out, sel + kSelClkWord, 32, hipMemcpyDeviceToHost, s);
     return e == hipSuccess ? hipStreamSynchronize(s) : e;
 }
 
@@ -1247,55 +1217,55 @@ void mfma_release() {
 // statistics decide exactly (select[kSelIdxUsed]), and the forms launched behind it return at once when the index runs. The
 // histograms are identical on every rank, so is the decision. idx_r: the index's block radius, kNoIndex if the pass may not
 // use it (launch_allpairs_mfma: eligibility and scratch are settled before the launch lock is taken).
-static hipError_t launch_auto(const AllPairsArgs& a, const void* d_img, bool rect, const void* d_img_q, uint32_t nq,
-                              const int32_t* d_group_t, uint32_t idx_r, hipStream_t s) {
+static hipError_t launch_auto(const MfmaPass& p, uint32_t idx_r) {
+    const AllPairsArgs& a = p.a;
+    const hipStream_t s = p.s;
     uint32_t* sel = nullptr;
     hipError_t e = mfma_select_buffer(a.ctx_id, &sel);
     if (e != hipSuccess) return e;
     // one launch writes the hit context of all three forms (they share S1 = 2) and clears the probe's words; the probe's last
     // workgroup decides. Per pass: context, probe, three forms -- five launches where there were nine.
-    hipLaunchKernelGGL(k_set_hit_ctx, dim3(1), dim3(1), 0, s, reinterpret_cast<HitCtx*>(sel + 16),
-                       hit_ctx(a, rect, nq, d_group_t, 2, rect ? d_img_q : d_img, d_img), sel);
-    const uint32_t nrows = rect ? nq : a.n;
-    const uint32_t rows = nrows < kProbeRows ? nrows : kProbeRows, cols = a.n < kProbeCols ? a.n : kProbeCols;
+    hipLaunchKernelGGL(k_set_hit_ctx, dim3(1), dim3(1), 0, s, reinterpret_cast<HitCtx*>(sel + kSelCtxWord),
+                       hit_ctx(p, mfma_form(kFormAuto)->s1, sel), sel);
+    const uint32_t rows = p.rows() < kProbeRows ? p.rows() : kProbeRows, cols = a.n < kProbeCols ? a.n : kProbeCols;
     // (the pair queue keeps (column << 1 | half) in 32 bits)
     const uint32_t mid = fp4_rows_padded(a.n) < (1u << 31) ? g_mfma_auto_mid : 0u;
     const IndexRule irule = idx_r != kNoIndex ? index_rule(a, idx_r) : IndexRule{};
-    const ProbeRule rule = {(uint64_t)rows * cols, 8192u, 9u, mid, 12u, 0.01f * (float)g_mfma_auto_mid_max_x100, g_mfma_force_sel,
-                            idx_r, irule};
+    const ProbeRule rule = {(uint64_t)rows * cols, 8192u, kFormFetch, mid, kFormRegister, 0.01f * (float)g_mfma_auto_mid_max_x100,
+                            g_mfma_force_sel, idx_r, irule};
     hipLaunchKernelGGL(k_prefilter_probe, dim3((rows + 255u) / 256u, (cols + kProbeColsPerWg - 1u) / kProbeColsPerWg), dim3(256), 0, s,
-                       (const uint4*)(rect ? d_img_q : d_img), nrows, (const uint4*)d_img, a.n, a.max_dist, sel, rule);
+                       p.row_image(), p.rows(), p.col_image(), a.n, a.max_dist, sel, rule);
     if (idx_r != kNoIndex) {
         e = launch_index_decide(a, sel, irule, s);
         if (e != hipSuccess) return e;
     }
     if (a.sync_decide) {
         uint32_t words[8] = {};
+        static_assert(kSelForm < 8 && kSelIdxUsed < 8, "the words the host decides by");
         e = hipMemcpyAsync(words, sel, sizeof(words), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) return e;
-        const uint32_t form = words[0];
-        if (form != 9u && form != 12u && form != mid) return hipErrorUnknown;  // (the probe writes one of its rule's three ids)
+        const uint32_t form = words[kSelForm];
+        if (form != rule.id_rare && form != rule.id_often && form != mid) return hipErrorUnknown;  // (the probe writes one of its rule's three ids)
         if (words[kSelIdxUsed] != 0u) return launch_index_join(a, sel, idx_r, s);
-        return launch_variant((int)form, a, d_img, rect, d_img_q, nq, d_group_t, sel, s, false);
+        return launch_variant((int)form, p, sel, false);
     }
     if (idx_r != kNoIndex) {
         e = launch_index_join(a, sel, idx_r, s);
         if (e != hipSuccess) return e;
     }
-    e = launch_variant(9, a, d_img, rect, d_img_q, nq, d_group_t, sel, s, false);
+    e = launch_variant(kFormFetch, p, sel, false);
     if (e != hipSuccess) return e;
     if (mid) {
-        e = launch_variant((int)mid, a, d_img, rect, d_img_q, nq, d_group_t, sel, s, false);
+        e = launch_variant((int)mid, p, sel, false);
         if (e != hipSuccess) return e;
     }
-    return launch_variant(12, a, d_img, rect, d_img_q, nq, d_group_t, sel, s, false);
+    return launch_variant(kFormRegister, p, sel, false);
 }
 
 static int effective_variant(int variant, uint32_t max_dist, uint32_t n) {
-    if (variant == 18 && fp4_rows_padded(n) >= (1u << 31)) variant = 12;  // the pair queue keeps (column << 1 | half) in 32 bits
-    // the 128-bit first stage needs 128 - 2*max_dist > 0
-    if (max_dist >= 64u && (variant == 9 || variant == 12 || variant == 13 || variant == 18)) return 8;
+    if (variant == kFormQueue && fp4_rows_padded(n) >= (1u << 31)) variant = kFormRegister;  // the pair queue keeps (column << 1 | half) in 32 bits
+    if (max_dist >= 64u && mfma_two_stage(variant)) return kFormFull;  // the 128-bit first stage needs 128 - 2*max_dist > 0
     return variant;
 }
 
@@ -1305,8 +1275,8 @@ hipError_t launch_cross_mfma(const AllPairsArgs& a, const void* d_img_q, uint32_
     std::lock_guard<std::mutex> lk(g_launch_mu);
     if (a.max_dist >= 128u) return hipErrorInvalidValue;  // sign trick needs a positive threshold
     const int v = effective_variant(a.variant, a.max_dist, a.n);
-    if (v == 13) return launch_auto(a, d_img_t, true, d_img_q, nq, d_group_t, kNoIndex, s);
-    return launch_variant(v, a, d_img_t, true, d_img_q, nq, d_group_t, nullptr, s);
+    const MfmaPass p = {a, d_img_t, d_img_q, nq, d_group_t, true, s};
+    return v == kFormAuto ? launch_auto(p, kNoIndex) : launch_variant(v, p, nullptr, true);
 }
 
 hipError_t launch_allpairs_mfma(const AllPairsArgs& a_in, const void* d_img, hipStream_t s) {
@@ -1325,7 +1295,7 @@ hipError_t launch_allpairs_mfma(const AllPairsArgs& a_in, const void* d_img, hip
     // the same path. Eligibility rests on shared inputs only; a rank that cannot get its scratch fails the pass (the group's
     // agreement step hands the failure to every rank) instead of quietly walking other tiles. A lone rank falls back.
     uint32_t idx_r = kNoIndex;
-    if (v == 13 && index_eligible(a, false, &idx_r)) {
+    if (v == kFormAuto && index_eligible(a, false, &idx_r)) {
         const hipError_t e = index_reserve(a.ctx_id, a.n);
         if (e != hipSuccess) {
             if (a.world > 1u) return e;
@@ -1333,8 +1303,8 @@ hipError_t launch_allpairs_mfma(const AllPairsArgs& a_in, const void* d_img, hip
         }
     }
     std::lock_guard<std::mutex> lk(g_launch_mu);
-    if (v == 13) return launch_auto(a, d_img, false, nullptr, 0u, nullptr, idx_r, s);
-    return launch_variant(v, a, d_img, false, nullptr, 0u, nullptr, nullptr, s);
+    const MfmaPass p = {a, d_img, d_img, a.n, nullptr, false, s};
+    return v == kFormAuto ? launch_auto(p, idx_r) : launch_variant(v, p, nullptr, true);
 }
 
 }  // namespace hvd

@@ -72,7 +72,7 @@ def shapes(tmp_path_factory):
     return {"mfma": _compile("k_hamming_mfma.hip", tmp), "pdq": _compile("k_pdq.hip", tmp), "img": _compile("k_fp4_image.hip", tmp)}
 
 
-# form -> template arguments <TILES, NBR, S1, RECT, QUEUE> (k_hamming_mfma.hip: launch table), what the form must keep:
+# form -> template arguments <TILES, NBR, S1, RECT, QUEUE> (csrc/hvd_mfma_forms.h: kMfmaForms; this copy is hand-written on purpose), what the form must keep:
 # waves = resident waves per SIMD, spill = VGPR spills allowed (0 everywhere), lds = bytes.
 # Round 6: the table holds only the forms that have a job (the eleven measured-and-lost ones are in HISTORY.md).
 FORMS = {

@@ -66,7 +66,7 @@ def flip_mask(rng, k, region):
 
 
 def mfma_col_chunk(nq, nt, rows_per_block):
-    """The rectangle's column chunk (launch_form in k_hamming_mfma.hip): enough tiles to fill the chip even for few rows."""
+    """The rectangle's column chunk (mfma_col_chunk in csrc/hvd_mfma_forms.h, below its 65535-chunk clamp): enough tiles to fill the chip even for few rows."""
     n_pad = (nt + 1023) // 1024 * 1024
     n_rb = (nq + rows_per_block - 1) // rows_per_block
     want_cb = (4096 + n_rb - 1) // n_rb
@@ -78,7 +78,7 @@ def mfma_col_chunk(nq, nt, rows_per_block):
 
 SUPER = 128  # hashes per LDS super-panel (kSuper)
 # (nq, nt) -> {rows per block: (column chunk, its super-panels, super-panels of the last chunk)}: the shapes at which the
-# rectangle's workgroups walk three or more super-panels, with the values launch_form computes for them
+# rectangle's workgroups walk three or more super-panels, with the values mfma_geometry (csrc/hvd_mfma_forms.h) computes for them
 # (test_cross_reference_cpu.py pins them against mfma_col_chunk)
 LONG_SHAPES = {
     (8, 1_300_000): {1024: (384, 3, 2), 512: (384, 3, 2)},
