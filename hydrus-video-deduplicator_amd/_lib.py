@@ -82,6 +82,7 @@ SIGNATURES = {
     "hvd_vpdq_align_segments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _int, _int, _vp]),
     "hvd_vpdq_align_rates": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _vp]),
     "hvd_group_edges": (_int, [_vp, _i64, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
+    "hvd_keeper_groups": (_int, [_vp, _i64, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "hvd_hasher_create": (_int, [_int, _int, _int, _i64, C.POINTER(_vp)]),
     "hvd_hasher_push": (_int, [_vp, _vp]),
     "hvd_hasher_set_threads": (_int, [_vp, _int]),
@@ -140,6 +141,8 @@ SIGNATURES = {
                                         _vp]),
     "hvd_group_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
     "hvd_dev_group_edges": (_int, [_vp, _i64, _vp, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "hvd_keeper_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
+    "hvd_dev_keeper_groups": (_int, [_vp, _i64, _vp, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _vp, _i64, _vp, C.POINTER(_i64)]),
     "hvd_dev_vpdq_match_videos": (_int, [_vp, _i64, _vp, _int, _int, _int, _vp, _i64, _vp]),
     "hvd_dev_vpdq_emit_again": (_int, [_vp, _i64, _vp]),
     "hvd_dev_vpdq_frame_spread": (_int, [_vp, _i64, _vp, _int, _vp]),

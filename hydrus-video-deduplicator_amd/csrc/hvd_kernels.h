@@ -234,6 +234,16 @@ hipError_t launch_group_edges(const void* d_records, unsigned long long n_record
                               void* d_scratch, int32_t* d_label, hvd_group* d_groups, unsigned long long cap,
                               unsigned long long* d_count, hipStream_t s);
 
+// Keeper-first duplicate groups over the same records (k_keeper.hip). d_scratch: keeper_scratch_bytes(V), 8-byte
+// aligned. The rounds are enqueued in batches of 32 with the undecided count read back in between, so the call synchronises
+// the stream; *settled: no node was left undecided within V rounds (else nothing else was launched); *rounds (may be nullptr):
+// the rounds that ran.
+size_t keeper_scratch_bytes(unsigned long long V);
+hipError_t launch_keeper_groups(const void* d_records, unsigned long long n_records, const unsigned long long* d_record_count,
+                                int kind, const long long* d_lengths, uint32_t T, bool is_min, uint32_t V, const uint32_t* d_score,
+                                void* d_scratch, int32_t* d_keeper, hvd_group* d_groups, unsigned long long cap,
+                                unsigned long long* d_count, hipStream_t s, long long* rounds, bool* settled);
+
 // Synthetic 64x64 gray video frames generated in HBM (k_synth.hip; workload generator, not on the hashing path).
 hipError_t launch_synth_frames64(uint8_t* d_out, long long v0, uint32_t frames_per_video, unsigned long long n_frames,
                                  uint64_t seed, const int32_t* d_copy_of, hipStream_t s);

@@ -1387,11 +1387,43 @@ int hvd_dev_group_edges(const void* d_records, int64_t n_records, const void* d_
     return HVD_OK;
 }
 
-int hvd_group_edges(const void* records, int64_t E, int kind, const int64_t* lengths, int threshold, int policy_is_min, int64_t V,
-                    const uint32_t* score, int32_t* out_label, hvd_group* out_groups, int64_t cap, int64_t* out_count) {
+/* ---- keeper-first duplicate groups: every member matches its keeper directly (k_keeper.hip) ---- */
+
+int hvd_keeper_scratch_bytes(int64_t V, size_t* out_bytes) {
+    if (!out_bytes || V < 1 || V >= (1ll << 31)) return fail(HVD_ERR_ARG, "V=%lld out of range [1,2^31)", (long long)V);
+    *out_bytes = hvd::keeper_scratch_bytes((unsigned long long)V);
+    return HVD_OK;
+}
+
+int hvd_dev_keeper_groups(const void* d_records, int64_t n_records, const void* d_record_count, int kind, const void* d_lengths,
+                          int threshold, int policy_is_min, int64_t V, const void* d_score, void* d_scratch, void* d_out_keeper,
+                          void* d_out_groups, int64_t cap, void* d_out_count, int64_t* out_rounds) {
+    if (int rc = need_ready()) return rc;
+    if (int rc = check_group_shape(n_records, kind, d_lengths, threshold, V)) return rc;
+    if (!d_scratch || !d_out_keeper || !d_out_count || (n_records > 0 && !d_records) || cap < 0 || (cap > 0 && !d_out_groups))
+        return fail(HVD_ERR_ARG, "NULL device pointer / bad cap");
+    if ((((uintptr_t)d_records | (uintptr_t)d_out_groups) & 15u) || (((uintptr_t)d_scratch | (uintptr_t)d_out_count | (uintptr_t)d_record_count) & 7u))
+        return fail(HVD_ERR_ARG, "records and groups must be 16-byte aligned, scratch and counts 8-byte aligned");
+    bool settled = false;
+    long long rounds = 0;
+    HIP_TRY(hvd::launch_keeper_groups(d_records, (unsigned long long)n_records, (const unsigned long long*)d_record_count, kind,
+                                      (const long long*)d_lengths, (uint32_t)threshold, policy_is_min != 0, (uint32_t)V,
+                                      (const uint32_t*)d_score, d_scratch, (int32_t*)d_out_keeper, (hvd_group*)d_out_groups,
+                                      (unsigned long long)cap, (unsigned long long*)d_out_count, g.stream,
+                                      out_rounds ? &rounds : nullptr, &settled));
+    if (!settled) return fail(HVD_ERR_STATE, "nodes left undecided after %lld rounds: every round decides one at least", (long long)V);
+    if (out_rounds) *out_rounds = (int64_t)rounds;
+    return HVD_OK;
+}
+
+// The host-array form of both groupings: everything is judged, the operands go up, the device entry runs, the node array and
+// the group records come down. keeper_first: hvd_dev_keeper_groups (out_node = keeper_of), else hvd_dev_group_edges (labels).
+static int groups_from_host(bool keeper_first, const void* records, int64_t E, int kind, const int64_t* lengths, int threshold,
+                            int policy_is_min, int64_t V, const uint32_t* score, int32_t* out_node, hvd_group* out_groups,
+                            int64_t cap, int64_t* out_count, int64_t* out_rounds) {
     // the arguments are judged before the library's state is: a bad call is HVD_ERR_ARG with or without a device
     if (int rc = check_group_shape(E, kind, lengths, threshold, V)) return rc;
-    if (!out_label || !out_count || (E > 0 && !records) || cap < 0 || (cap > 0 && !out_groups))
+    if (!out_node || !out_count || (E > 0 && !records) || cap < 0 || (cap > 0 && !out_groups))
         return fail(HVD_ERR_ARG, "NULL pointer / bad cap");
     const uint32_t* w = (const uint32_t*)records;
     for (int64_t e = 0; e < E; ++e)
@@ -1400,10 +1432,10 @@ int hvd_group_edges(const void* records, int64_t E, int kind, const int64_t* len
                         w[4 * e + 1], (long long)V);
     if (int rc = need_ready()) return rc;
     std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    void *d_rec = nullptr, *d_len = nullptr, *d_score = nullptr, *d_scr = nullptr, *d_label = nullptr;
+    void *d_rec = nullptr, *d_len = nullptr, *d_score = nullptr, *d_scr = nullptr, *d_node = nullptr;
     uint8_t* d_out = nullptr;  // the count, then the group records
-    SCR(S_GSCR, hvd::group_scratch_bytes((unsigned long long)V), d_scr);
-    SCR(S_GLABEL, 4 * (size_t)V, d_label);
+    SCR(S_GSCR, keeper_first ? hvd::keeper_scratch_bytes((unsigned long long)V) : hvd::group_scratch_bytes((unsigned long long)V), d_scr);
+    SCR(S_GLABEL, 4 * (size_t)V, d_node);
     SCR(S_GOUT, 16 + 16 * (size_t)cap, d_out);
     if (E > 0) {
         SCR(S_GREC, 16 * (size_t)E, d_rec);
@@ -1417,12 +1449,15 @@ int hvd_group_edges(const void* records, int64_t E, int kind, const int64_t* len
         SCR(S_GSCORE, 4 * (size_t)V, d_score);
         HIP_TRY(hipMemcpyAsync(d_score, score, 4 * (size_t)V, hipMemcpyHostToDevice, g.stream));
     }
-    if (int rc = hvd_dev_group_edges(d_rec, E, nullptr, kind, d_len, threshold, policy_is_min, V, d_score, d_scr, d_label,
-                                     cap > 0 ? d_out + 16 : nullptr, cap, d_out))
+    void* d_groups = cap > 0 ? d_out + 16 : nullptr;
+    if (int rc = keeper_first ? hvd_dev_keeper_groups(d_rec, E, nullptr, kind, d_len, threshold, policy_is_min, V, d_score, d_scr,
+                                                      d_node, d_groups, cap, d_out, out_rounds)
+                              : hvd_dev_group_edges(d_rec, E, nullptr, kind, d_len, threshold, policy_is_min, V, d_score, d_scr, d_node,
+                                                    d_groups, cap, d_out))
         return rc;
     unsigned long long count = 0;
     HIP_TRY(hipMemcpyAsync(&count, d_out, 8, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipMemcpyAsync(out_label, d_label, 4 * (size_t)V, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(out_node, d_node, 4 * (size_t)V, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     const unsigned long long n_out = std::min(count, (unsigned long long)cap);
     if (n_out > 0) {
@@ -1432,6 +1467,19 @@ int hvd_group_edges(const void* records, int64_t E, int kind, const int64_t* len
     *out_count = (int64_t)count;
     if (count > (unsigned long long)cap) return fail(HVD_ERR_OVERFLOW, "%llu groups, room for %lld", count, (long long)cap);
     return HVD_OK;
+}
+
+int hvd_group_edges(const void* records, int64_t E, int kind, const int64_t* lengths, int threshold, int policy_is_min, int64_t V,
+                    const uint32_t* score, int32_t* out_label, hvd_group* out_groups, int64_t cap, int64_t* out_count) {
+    return groups_from_host(false, records, E, kind, lengths, threshold, policy_is_min, V, score, out_label, out_groups, cap,
+                            out_count, nullptr);
+}
+
+int hvd_keeper_groups(const void* records, int64_t E, int kind, const int64_t* lengths, int threshold, int policy_is_min, int64_t V,
+                      const uint32_t* score, int32_t* out_keeper, hvd_group* out_groups, int64_t cap, int64_t* out_count,
+                      int64_t* out_rounds) {
+    return groups_from_host(true, records, E, kind, lengths, threshold, policy_is_min, V, score, out_keeper, out_groups, cap,
+                            out_count, out_rounds);
 }
 
 #ifndef HVD_NO_BENCH_SYMBOLS

@@ -773,6 +773,46 @@ def find_duplicate_groups_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, 
     return search.groups_from_labels(labels, groups), labels, groups, library
 
 
+def keeper_groups_on_device(d_records_ptr: int, n_records: int, d_record_count_ptr, V: int, d_score_ptr=None,
+                            kind: int = _lib.EDGES_ALL, d_lengths_ptr=None, T: int = 0, is_min: bool = False):
+    """hvd_dev_keeper_groups over records that lie in HBM -> (keeper_of, groups, rounds): the first two as
+    search.keeper_groups returns them, only those cross PCIe; rounds: how many rounds the keepers took. d_record_count_ptr as for
+    `group_records_on_device`; the entry itself waits for the stream between its batches of rounds."""
+    lib = _lib.ensure()
+    sb = C.c_size_t(0)
+    _lib.check(lib.hvd_keeper_scratch_bytes(V, C.byref(sb)))
+    cap = max(1, min(V // 2, n_records))  # a group has two nodes and one record at least
+    rounds = C.c_int64(0)
+    with _DeviceScope() as scope:
+        d_scr, d_keeper = scope.temp(DeviceBuffer(sb.value)), scope.temp(DeviceBuffer(4 * V))
+        d_groups, d_cnt = scope.temp(DeviceBuffer(16 * cap)), scope.temp(DeviceBuffer(8))
+        _lib.check(lib.hvd_dev_keeper_groups(d_records_ptr, n_records, d_record_count_ptr, kind, d_lengths_ptr, T, int(is_min), V,
+                                             d_score_ptr, d_scr.ptr, d_keeper.ptr, d_groups.ptr, cap, d_cnt.ptr, C.byref(rounds)))
+        count = int(d_cnt.to_array(np.uint64, 1)[0])  # (the copy waits for the library stream)
+        assert count <= cap
+        out = d_keeper.to_array(np.int32, V), d_groups.to_array(GROUP_DTYPE, count), rounds.value
+        _lib.check(lib.hvd_dev_sync())  # nothing may still run on a buffer that is freed here
+    return out
+
+
+def find_keeper_groups_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                 threshold: float = 50.0, policy: str | None = None, score=None, keep_library: bool = False):
+    """search.find_keeper_groups on frames in HBM, one device: the chain of `dedupe_frames_on_device`, then
+    search.keeper_group_records over its records with the library's kept lengths. score: uint32 per video, the larger is kept;
+    default the number of kept frames. -> (keeper groups, keeper_of, group records, library or None)."""
+    _, recs, library = dedupe_frames_on_device(d_frames_ptr, raw_offsets, h, w, channels, threshold, policy, keep_library=True)
+    try:
+        lengths = library.lengths()
+        keeper_of, groups = search.keeper_group_records(recs, lengths, threshold, policy, lengths if score is None else score)
+    except BaseException:
+        library.free()
+        raise
+    if not keep_library:
+        library.free()
+        library = None
+    return search.keeper_groups_from(keeper_of, groups), keeper_of, groups, library
+
+
 def _aligned_search_on_device(d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library, align, fold):
     """The chain of the excerpt searches on frames in HBM, one device: hash -> quality filter + CSR, with the kept frames' raw
     positions (`DeviceLibrary.from_raw_hashes(positions=True)`) -> video search -> align(library, records) -> fold(aligned,

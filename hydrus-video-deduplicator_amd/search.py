@@ -817,6 +817,83 @@ def find_duplicate_groups(video_hashes, threshold: float = 50.0, policy: str | N
     return groups_from_labels(labels, groups)
 
 
+# ------------------------------------------------ keeper-first groups: every member matches its keeper ------
+
+KeeperGroup = namedtuple("KeeperGroup", "keeper members edges complete")
+
+
+def _keeper(records: np.ndarray, kind: int, lengths, T: int, is_min: bool, V: int, score) -> tuple[np.ndarray, np.ndarray]:
+    """hvd_keeper_groups -> (keeper_of int32[V], GROUP_DTYPE records sorted by keeper)."""
+    score = _score_array(score, V)
+    if V == 0:
+        if records.size:
+            raise ValueError("records without a node")
+        return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=GROUP_DTYPE)
+    E = records.shape[0]
+    cap = min(V // 2, E)  # a group has two nodes and one record at least
+    keeper_of = np.empty(V, dtype=np.int32)
+    groups = np.zeros(max(cap, 1), dtype=GROUP_DTYPE)
+    cnt = C.c_int64(0)
+    lib = _lib.ensure()
+    _lib.check(lib.hvd_keeper_groups(_ptr(records), E, kind, _ptr(lengths), T, int(is_min), V, _ptr(score), keeper_of.ctypes.data,
+                                     groups.ctypes.data, cap, C.byref(cnt), None))
+    return keeper_of, groups[: cnt.value].copy()
+
+
+def keeper_groups(edges, V: int, score=None) -> tuple[np.ndarray, np.ndarray]:
+    """Keeper-first groups of a pair list on the GPU (hvd_keeper_groups, HVD_EDGES_ALL): `edges` as for `group_edges`. Walk the
+    nodes by descending (score, then smaller index): a node nobody has claimed is a keeper and claims its unclaimed neighbours.
+    -> (keeper_of, groups): keeper_of int32[V], keeper_of[v] = the keeper v is a direct match of (v itself for a keeper);
+    groups: one GROUP_DTYPE record (root = keeper, size, edges, keeper) per keeper with a member, sorted by keeper. Unlike the
+    components of `group_edges`, every member pairs with its keeper and no two keepers pair."""
+    return _keeper(edge_records(edges), _lib.EDGES_ALL, None, 0, False, int(V), score)
+
+
+def keeper_group_records(records: np.ndarray, lengths: np.ndarray, threshold: float = 50.0, policy: str | None = None,
+                         score=None) -> tuple[np.ndarray, np.ndarray]:
+    """`keeper_groups` over the VMATCH records that pass the pair predicate of `similar_video_pairs` (hvd_keeper_groups,
+    HVD_EDGES_VMATCH), as `group_records` is to `group_edges`. -> (keeper_of, groups)."""
+    policy = vpdq.MATCH_POLICY if policy is None else policy
+    if policy not in ("min", "max", "query", "target"):
+        raise ValueError(f"unknown match policy {policy!r}")
+    T = int(threshold)
+    if T < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    records = np.ascontiguousarray(records, dtype=VMATCH_DTYPE).reshape(-1)
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    V = lengths.shape[0]
+    if T > 100:  # no similarity is above 100: every video its own keeper
+        return np.arange(V, dtype=np.int32), np.zeros(0, dtype=GROUP_DTYPE)
+    return _keeper(records, _lib.EDGES_VMATCH, lengths, T, policy == "min", V, score)
+
+
+def keeper_groups_from(keeper_of: np.ndarray, groups: np.ndarray) -> list:
+    """(keeper_of, groups) of the keeper entries -> [KeeperGroup(keeper, members, edges, complete)], sorted by keeper. members:
+    the nodes to remove, ascending, without the keeper -- each a direct match of it; complete: every node of the group pairs
+    with every other, edges == size (size - 1) / 2 with size = 1 + len(members)."""
+    keeper_of = np.asarray(keeper_of)
+    order = np.argsort(keeper_of, kind="stable")
+    by_keeper = keeper_of[order]
+    out = []
+    for g in groups[np.argsort(groups["keeper"], kind="stable")]:
+        size, keeper = int(g["size"]), int(g["keeper"])
+        lo = int(np.searchsorted(by_keeper, keeper, side="left"))
+        members = tuple(int(m) for m in order[lo:lo + size] if m != keeper)
+        out.append(KeeperGroup(keeper, members, int(g["edges"]), int(g["edges"]) == size * (size - 1) // 2))
+    return out
+
+
+def find_keeper_groups(video_hashes, threshold: float = 50.0, policy: str | None = None, score=None) -> list:
+    """find_potential_duplicates as groups that can be acted on: [KeeperGroup(keeper, members, edges, complete)] sorted by
+    keeper, where every member is itself one of the keeper's pairs, and no pair is left among the videos that remain once every
+    member is removed. score (uint32 per video): the larger is kept, ties to the smaller index; default: the number of kept
+    frames, as in `find_duplicate_groups`."""
+    frames, offsets, lengths = pack_hashes(video_hashes)
+    recs = match_videos(frames, offsets, vpdq.frame_max_dist(DISTANCE_TOLERANCE))
+    keeper_of, groups = keeper_group_records(recs, lengths, threshold, policy, lengths if score is None else score)
+    return keeper_groups_from(keeper_of, groups)
+
+
 def cluster_hashes(db: np.ndarray, max_dist: int = DISTANCE_TOLERANCE, score=None) -> tuple[np.ndarray, np.ndarray]:
     """The groups of `allpairs_hamming(db, max_dist)` without its pair list: the hashes go up, the all-pairs pass leaves its
     pairs in HBM, the grouping runs over them there (pipeline.cluster_hashes_on_device), labels and group records come back.

@@ -105,7 +105,10 @@ typedef struct hvd_vrate {
  * whose edges are the records of a search. root: the smallest member, which is also the label of every member; size: members;
  * edges: input records that are edges inside the group (a repeated record counts each time); keeper: the member with the largest
  * score, ties to the smaller index -- Hydrus' "king". The group is complete (every member pairs with every other) iff
- * edges == size (size - 1) / 2, given that the list holds each pair once, as the searches emit them. */
+ * edges == size (size - 1) / 2, given that the list holds each pair once, as the searches emit them.
+ * The keeper-first grouping (hvd_keeper_groups / hvd_dev_keeper_groups) writes the same record with root = keeper =
+ * the keeper's index, which is then the label of every member (keeper_of), size = 1 + its members, and edges counted inside the
+ * group the same way. */
 typedef struct hvd_group {
     uint32_t root, size, edges, keeper;
 } hvd_group;
@@ -342,6 +345,33 @@ int hvd_vpdq_align_rates(const uint8_t* frames_q, const int64_t* offsets_q, int6
  * the calling thread's current context alone. */
 int hvd_group_edges(const void* records, int64_t E, int kind, const int64_t* lengths, int threshold, int policy_is_min, int64_t V,
                     const uint32_t* score, int32_t* out_label, hvd_group* out_groups, int64_t cap, int64_t* out_count);
+
+/* Keeper-first duplicate groups: every member of a group is a direct match of the group's keeper. The components
+ * of hvd_group_edges are single linkage: a chain A~B~C without A~C is one group, whose keeper may be A, no duplicate of C. This
+ * grouping is for a caller that acts on its groups. The rule, integers only, one answer per input; V, the records, kind,
+ * lengths, threshold, policy_is_min and score mean what they mean for hvd_group_edges, and the same records are edges:
+ *   priority   key(v) = score[v] << 32 | (2^32 - 1 - v); larger is better: the larger score, then the smaller index.
+ *   adjacent   u and v, iff some record is an edge between them; orientation and repeats do not matter.
+ *   keeper     v, iff no adjacent node of higher priority is a keeper (well founded from the highest priority down: the
+ *              lexicographically first maximal independent set). A node without edges is a keeper.
+ *   member     every other node; it has an adjacent keeper by definition. keeper_of[v] = its adjacent keeper of highest
+ *              priority; keeper_of[v] = v for a keeper.
+ *   group      one per keeper with at least one member: size = 1 + its members; edges = the records that are edges with both
+ *              ends in the group, each repeat counted; complete iff edges == size (size - 1) / 2.
+ * Equivalently: walk the nodes in descending priority; a node nobody has claimed becomes a keeper and claims every unclaimed
+ * neighbour. What follows:
+ *   (a) every member has a record that is an edge to its keeper;
+ *   (b) no two keepers are adjacent: once the members are deleted, no pair of the input remains among the kept nodes;
+ *   (c) nothing in the result depends on the order of the records or on scheduling -- nor does *out_rounds.
+ * out_keeper: int32[V], keeper_of. out_groups: one hvd_group per group with root = keeper = the keeper's index, sorted by keeper
+ * ascending; min(count, cap) are written. *out_count: the true number of groups; HVD_ERR_OVERFLOW if it exceeds cap (keeper_of
+ * and the first cap groups are valid then). There are at most min(V / 2, E) groups. out_rounds: NULL, or receives the number of
+ * rounds the device took (hvd_dev_keeper_groups), at least 1.
+ * This host-buffer form validates everything hvd_group_edges validates, every record included, before it asks for a device
+ * (HVD_ERR_ARG with or without one, nothing written), then uploads, runs the kernels and downloads. */
+int hvd_keeper_groups(const void* records, int64_t E, int kind, const int64_t* lengths, int threshold, int policy_is_min, int64_t V,
+                      const uint32_t* score, int32_t* out_keeper, hvd_group* out_groups, int64_t cap, int64_t* out_count,
+                      int64_t* out_rounds);
 
 /* ------------------------------------------------ streaming frame hasher -- */
 /* The native side of vpdq.VideoHasher (vpdqpy/vpdqpy.py:113-119): frames are pushed one at a
@@ -651,6 +681,20 @@ int hvd_group_scratch_bytes(int64_t V, size_t* out_bytes);
 int hvd_dev_group_edges(const void* d_records, int64_t n_records, const void* d_record_count, int kind, const void* d_lengths,
                         int threshold, int policy_is_min, int64_t V, const void* d_score, void* d_scratch, void* d_out_label,
                         void* d_out_groups, int64_t cap, void* d_out_count);
+
+/* Device-resident keeper-first grouping (the rule: hvd_keeper_groups above). The operands are those of hvd_dev_group_edges,
+ * d_record_count included; d_scratch: hvd_keeper_scratch_bytes(V) bytes (28 per node, 4 per 1024 nodes and 16), 8-byte aligned;
+ * d_out_keeper: int32[V]; d_out_groups: cap records, 16-byte aligned (may be NULL when cap is 0); d_out_count: one uint64, the
+ * true number of groups; out_rounds: a HOST int64, or NULL. The keepers are decided in rounds of two launches; a round decides
+ * at least the best undecided node of every component, so V rounds suffice, and a few do unless priority runs monotone along
+ * long chains. Unlike hvd_dev_group_edges this entry DOES synchronise: it enqueues the rounds in batches of 32
+ * on the library stream and between batches reads the number of undecided nodes back, one 4-byte copy, until that is zero;
+ * the closing launches are then enqueued behind, as hvd_dev_group_edges' are. More than V rounds: HVD_ERR_STATE. Nothing is
+ * allocated. Records that are no edge are ignored; every index is checked before use. */
+int hvd_keeper_scratch_bytes(int64_t V, size_t* out_bytes);
+int hvd_dev_keeper_groups(const void* d_records, int64_t n_records, const void* d_record_count, int kind, const void* d_lengths,
+                          int threshold, int policy_is_min, int64_t V, const void* d_score, void* d_scratch, void* d_out_keeper,
+                          void* d_out_groups, int64_t cap, void* d_out_count, int64_t* out_rounds);
 
 /* Every video pair a<b with >= 1 frame hit, with its vPDQ counters (semantics of vpdqpy/vpdqpy.py:49-56 for all
  * pairs at once; replaces the tree walk of dedup.py:468-475). d_img: FP4 image of the n frame hashes; d_video:
