@@ -928,6 +928,42 @@ int hvd_dev_pdq_hash_frames_rects(const void* d_frames, int64_t n, int h, int w,
     return HVD_OK;
 }
 
+/* ---- bar-colour content rectangle (k_barcolor.hip) ---- */
+
+int hvd_bar_colors_scratch_bytes(int64_t V, size_t* out_bytes) {
+    if (!out_bytes || V < 0 || V >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad video count V=%lld", (long long)V);
+    *out_bytes = hvd::bar_colors_scratch_bytes((uint32_t)V);
+    return HVD_OK;
+}
+
+int hvd_dev_bar_colors(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
+                       int bar_level, void* d_scratch, void* d_colors) {
+    if (int rc = need_ready()) return rc;
+    if (int rc = rects_geometry(n, h, w, channels, V)) return rc;
+    if (int rc = hvd::check_bar_level(bar_level)) return rc;
+    if (V == 0) return HVD_OK;
+    if (!d_offsets || !d_scratch || !d_colors || (n > 0 && !d_frames)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if (((uintptr_t)d_scratch | (uintptr_t)d_colors) & 3u) return fail(HVD_ERR_ARG, "d_scratch and d_colors must be 4-byte aligned");
+    HIP_TRY(hvd::launch_bar_colors((const uint8_t*)d_frames, n, h, w, channels, (const long long*)d_offsets, (uint32_t)V,
+                                   bar_level, (int32_t*)d_scratch, (int32_t*)d_colors, g.stream));
+    return HVD_OK;
+}
+
+int hvd_dev_content_rects_color(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
+                                const void* d_colors, int bar_level, int min_bright, void* d_rects) {
+    if (int rc = need_ready()) return rc;
+    if (int rc = rects_geometry(n, h, w, channels, V)) return rc;
+    if (int rc = hvd::check_bar_level(bar_level)) return rc;
+    if (min_bright < 1) return fail(HVD_ERR_ARG, "min_bright=%d: need >= 1", min_bright);
+    if (V == 0) return HVD_OK;
+    if (!d_offsets || !d_rects || !d_colors || (n > 0 && !d_frames)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if ((uintptr_t)d_rects & 15u) return fail(HVD_ERR_ARG, "d_rects must be 16-byte aligned (hvd_dev_malloc's are)");
+    if ((uintptr_t)d_colors & 3u) return fail(HVD_ERR_ARG, "d_colors must be 4-byte aligned");
+    HIP_TRY(hvd::launch_content_rects_color((const uint8_t*)d_frames, n, h, w, channels, (const long long*)d_offsets, (uint32_t)V,
+                                            (const int32_t*)d_colors, bar_level, min_bright, (int32_t*)d_rects, g.stream));
+    return HVD_OK;
+}
+
 /* ---- crop-ladder PDQ (k_crops.hip) ---- */
 
 // what needs no device: the frame geometry and the caller's list

@@ -40,6 +40,9 @@ inline int check_autocrop_levels(int black_level, int min_bright) {
     if (black_level < 0 || black_level > 254) return api_fail(HVD_ERR_ARG, "black_level=%d: need 0..254", black_level);
     return min_bright >= 1 ? HVD_OK : api_fail(HVD_ERR_ARG, "min_bright=%d: need >= 1", min_bright);
 }
+inline int check_bar_level(int bar_level) {
+    return bar_level >= 0 && bar_level <= 254 ? HVD_OK : api_fail(HVD_ERR_ARG, "bar_level=%d: need 0..254", bar_level);
+}
 inline int check_dihedral_dct(bool dihedral) {  // the dihedral kernel has K1's strict arithmetic only
     if (!dihedral || g_pdq_dct_mode == 0) return HVD_OK;
     return api_fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");

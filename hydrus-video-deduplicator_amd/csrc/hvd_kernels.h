@@ -306,6 +306,17 @@ hipError_t launch_pdq_downsample_rects(const uint8_t* d_frames, int64_t n, int h
                                        const long long* d_offsets, uint32_t V, const int32_t* d_rects, void* d_geom,
                                        float* d_ws, float* d_out64, hipStream_t s);
 
+// Bar-colour content rectangle (k_barcolor.hip). d_colors: int32[V] = c0 | c1 << 8 | c2 << 16, the bar colour
+// of every video. launch_bar_colors finds it from the four corner pixels of every frame; d_acc: bar_colors_scratch_bytes(V)
+// bytes of accumulators. launch_content_rects_color is launch_content_rects with "content iff max_k |p_k - c_k| > bar_level"
+// as the pixel rule (rect init and finish are k_autocrop.hip's).
+size_t bar_colors_scratch_bytes(uint32_t V);
+hipError_t launch_bar_colors(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
+                             uint32_t V, int bar_level, int32_t* d_acc, int32_t* d_colors, hipStream_t s);
+hipError_t launch_content_rects_color(const uint8_t* d_frames, int64_t n, int h, int w, int channels,
+                                      const long long* d_offsets, uint32_t V, const int32_t* d_colors, int bar_level,
+                                      int min_bright, int32_t* d_rects, hipStream_t s);
+
 // Crop-ladder PDQ (k_crops.hip). crops: HOST int32[K][4] {top, left, height, width}; crops_valid: 1 <= K <=
 // HVD_MAX_CROPS and every crop inside the h x w frame with both sides >= 64 -- the one definition of a sound list.
 bool crops_valid(const int32_t* crops, int K, int h, int w);

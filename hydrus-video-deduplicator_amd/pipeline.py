@@ -32,8 +32,9 @@ def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
     geometry. All frames go through the PDQ kernels in one batch; per video the frames with
     quality >= 31 are kept in order (VideoHasher.finish semantics, vpdqpy/vpdqpy.py:119).
     autocrop: True or a dict of black_level / min_bright: every video is hashed inside its content rectangle
-    (vpdq.hash_frames_autocrop)."""
-    crop = vpdq.autocrop_params(autocrop)
+    (vpdq.hash_frames_autocrop). A dict of bar_color / bar_level / min_bright (vpdq.autocrop_rule) leaves out
+    bars of the video's colour instead; an array bar_color has one row per video of `videos`."""
+    crop = vpdq.autocrop_rule(autocrop)
     videos = [np.ascontiguousarray(v, dtype=np.uint8) for v in videos]
     if not videos:
         return []
@@ -46,7 +47,8 @@ def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
         return [vpdq.VpdqHash(b"") for _ in videos]
     flat = np.concatenate([v for v in videos if v.shape[0]], axis=0)
     if crop is not None:
-        hashes, quality, _ = vpdq.hash_frames_autocrop(flat, np.concatenate([[0], np.cumsum(lengths)]), crop[0], crop[1])
+        level = dict(black_level=crop[0]) if crop[2] is None else dict(bar_color=crop[2], bar_level=crop[0])
+        hashes, quality, _ = vpdq.hash_frames_autocrop(flat, np.concatenate([[0], np.cumsum(lengths)]), min_bright=crop[1], **level)
     else:
         hashes, quality = vpdq.hash_frames(flat)
     out, pos = [], 0
@@ -141,20 +143,42 @@ def hash_frames_dihedral_on_device(d_frames_ptr: int, n: int, h: int, w: int, ch
 
 
 def hash_frames_autocrop_on_device(d_frames_ptr: int, n: int, h: int, w: int, channels: int, offsets: np.ndarray,
-                                   black_level: int = 16, min_bright: int = 1, timed=None):
+                                   black_level: int = 16, min_bright: int = 1, timed=None, bar_color=None, bar_level=None):
     """Content-rectangle form of `hash_frames_on_device`: the n frames in HBM are the videos of the CSR
     `offsets` (int64[V+1], from 0 to n); hvd_dev_content_rects finds every video's rectangle, hvd_dev_pdq_hash_frames_rects
     hashes every frame inside it. -> (d_hashes, d_quality, d_rects) DeviceBuffers (n*32 B, int32[n], int32[V,4]).
-    timed(key, fn): optional stage timer, called with "rects_ms" and "hash_ms"."""
+    timed(key, fn): optional stage timer, called with "rects_ms" and "hash_ms".
+    bar_color ("auto", an int, a 3-tuple or an array [V, channels]) with bar_level (default 16): the rectangles leave out
+    bars of the video's colour (hvd_dev_bar_colors where "auto", then hvd_dev_content_rects_color; both inside
+    "rects_ms"); black_level then stays at its default."""
     lib = _lib.ensure()
     offsets = _check_raw_offsets(offsets, n)
     V = offsets.size - 1
     run = timed if timed is not None else (lambda key, fn: fn())
+    if bar_color is None and bar_level is not None:
+        raise ValueError("bar_level needs bar_color (the black rule's level is black_level)")
+    if bar_color is not None:
+        level, bright = vpdq._bar_rule_args(black_level, min_bright, bar_color, bar_level)
+        packed = vpdq._pack_bar_color(bar_color, V, channels)
     with _DeviceScope() as scope:
         d_off = scope.keep(DeviceBuffer.from_array(offsets))
         d_r = scope.keep(DeviceBuffer(16 * max(V, 1)))
-        run("rects_ms", lambda: _lib.check(lib.hvd_dev_content_rects(d_frames_ptr, n, h, w, channels, d_off.ptr, V,
-                                                                     int(black_level), int(min_bright), d_r.ptr)))
+        if bar_color is None:
+            run("rects_ms", lambda: _lib.check(lib.hvd_dev_content_rects(d_frames_ptr, n, h, w, channels, d_off.ptr, V,
+                                                                         int(black_level), int(min_bright), d_r.ptr)))
+        else:
+            sb = C.c_size_t(0)
+            _lib.check(lib.hvd_bar_colors_scratch_bytes(V, C.byref(sb)))
+            d_c = scope.temp(DeviceBuffer(4 * max(V, 1)) if packed is None else DeviceBuffer.from_array(packed))
+            d_a = scope.temp(DeviceBuffer(max(sb.value, 1))) if packed is None else None
+
+            def colour_rects():
+                if packed is None:
+                    _lib.check(lib.hvd_dev_bar_colors(d_frames_ptr, n, h, w, channels, d_off.ptr, V, level, d_a.ptr, d_c.ptr))
+                _lib.check(lib.hvd_dev_content_rects_color(d_frames_ptr, n, h, w, channels, d_off.ptr, V, d_c.ptr, level, bright,
+                                                           d_r.ptr))
+
+            run("rects_ms", colour_rects)
         d_h = scope.keep(DeviceBuffer(32 * max(n, 1)))
         d_q = scope.keep(DeviceBuffer(4 * max(n, 1)))
         sb = C.c_size_t(0)
@@ -635,15 +659,22 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
     autocrop (True, or a dict of black_level / min_bright): the hash stage becomes hvd_dev_content_rects +
     hvd_dev_pdq_hash_frames_rects over this rank's own videos (`hash_frames_autocrop_on_device`; a rank owns whole videos,
     so every rectangle sees all its frames); timings then also receives rects_ms. Everything after the hash stage is
-    unchanged."""
-    crop = vpdq.autocrop_params(autocrop)
+    unchanged. A dict of bar_color / bar_level / min_bright (vpdq.autocrop_rule) finds the rectangles by the
+    bar-colour rule instead; that form is for world == 1 (an array bar_color has one row per video of the library)."""
+    crop = vpdq.autocrop_rule(autocrop)
+    if crop is not None and crop[2] is not None and world != 1:
+        raise ValueError("the bar-colour rule is not sharded over a device group: world must be 1")
     timed = _stage_timer(timings)
 
     def hash_stage(mine):
         n_mine = int(mine[-1])
         if crop is None:
             return timed("hash_ms", lambda: hash_frames_on_device(d_frames_ptr, n_mine, h, w, channels))
-        d_h, d_q, d_r = hash_frames_autocrop_on_device(d_frames_ptr, n_mine, h, w, channels, mine, crop[0], crop[1], timed)
+        if crop[2] is None:
+            d_h, d_q, d_r = hash_frames_autocrop_on_device(d_frames_ptr, n_mine, h, w, channels, mine, crop[0], crop[1], timed)
+        else:
+            d_h, d_q, d_r = hash_frames_autocrop_on_device(d_frames_ptr, n_mine, h, w, channels, mine, min_bright=crop[1],
+                                                           timed=timed, bar_color=crop[2], bar_level=crop[0])
         d_r.free()
         return d_h, d_q
 

@@ -197,12 +197,16 @@ class VideoHasher:
     one video, byte for byte. After ``finish()``, ``rect`` is ``(top, left, height, width)``. ``max_retained_bytes``: how
     many bytes of frames one video may keep on the device (None: the library default, 8 GiB); the frame that would pass
     it raises HvdError(HVD_ERR_OVERFLOW) and ``finish()`` still returns the result of the frames taken before. Not
-    together with ``transforms``."""
+    together with ``transforms``. The black rule only: a dict with ``bar_color`` / ``bar_level`` raises a
+    ValueError that names the array form (``hash_frames_autocrop(frames, bar_color=...)``)."""
 
     def __init__(self, average_fps: int, width: int, height: int, num_threads: int = 0,
                  batch_bytes: int = 32 << 20, transforms=None, autocrop=None, max_retained_bytes: int | None = None):
         if width < 64 or height < 64:
             raise ValueError("frames must be at least 64x64")
+        if isinstance(autocrop, dict) and {"bar_color", "bar_level"} & set(autocrop):
+            raise ValueError("the streaming hasher has no bar-colour rule (the automatic colour is known only after the last "
+                             "frame): hash the array form of the frames, vpdq.hash_frames_autocrop(frames, bar_color=...)")
         self._autocrop = autocrop_params(autocrop)
         if self._autocrop is not None and transforms is not None:
             raise ValueError("autocrop and transforms cannot be combined (content-rectangle dihedral hashing does not exist)")
@@ -476,10 +480,139 @@ def _autocrop_args(frames, offsets, black_level, min_bright):
     return frames, offsets, level, bright
 
 
-def content_rects(frames: np.ndarray, offsets=None, black_level: int = 16, min_bright: int = 1) -> np.ndarray:
+# Bar-colour content rectangle (include/hvd_mi355x.h: hvd_dev_bar_colors): bars that are not black. A pixel is
+# content iff it differs from its video's bar colour by more than bar_level on some channel.
+_RULE_KEYS = {"black_level", "min_bright", "bar_color", "bar_level"}
+
+
+def autocrop_rule(autocrop) -> tuple[int, int, object] | None:
+    """`autocrop_params` for the call sites that also know the bar-colour rule: None when `autocrop` is off, else
+    (level, min_bright, bar_color). bar_color None is the black rule and level its black_level -- what `autocrop_params`
+    returns, for every input it accepts. A dict with ``bar_color`` ("auto", an int, a 3-tuple or an array [V, channels])
+    may carry ``bar_level`` (default 16) and ``min_bright``; ``black_level`` together with ``bar_color`` is a ValueError,
+    and so is ``bar_level`` without it. The colour's shape is checked where the frames are known."""
+    if not isinstance(autocrop, dict) or not ({"bar_color", "bar_level"} & set(autocrop)):
+        params = autocrop_params(autocrop)
+        return None if params is None else (*params, None)
+    if set(autocrop) - _RULE_KEYS:
+        raise ValueError("autocrop must be True / False or a dict with the keys black_level and min_bright, or bar_color, "
+                         "bar_level and min_bright")
+    if "black_level" in autocrop and autocrop.get("bar_color") is not None:
+        raise ValueError("black_level and bar_color cannot be combined: the level of the bar-colour rule is bar_level")
+    if autocrop.get("bar_color") is None:
+        raise ValueError("bar_level needs bar_color (the black rule's level is black_level)")
+    level, bright = _check_bar_levels(autocrop.get("bar_level"), autocrop.get("min_bright", 1))
+    return level, bright, autocrop["bar_color"]
+
+
+def _check_bar_levels(bar_level, min_bright) -> tuple[int, int]:
+    bar_level = 16 if bar_level is None else bar_level
+    if isinstance(bar_level, bool) or not isinstance(bar_level, (int, np.integer)) or not 0 <= bar_level <= 254:
+        raise ValueError(f"bar_level must be an integer in 0..254 (a pixel is content iff it differs from the bar colour by "
+                         f"more than bar_level on some channel), got {bar_level!r}")
+    return int(bar_level), _check_autocrop(0, min_bright)[1]
+
+
+def _pack_bar_color(bar_color, V: int, channels: int) -> np.ndarray | None:
+    """None for "auto"; else int32[V] = c0 | c1 << 8 | c2 << 16 from an int (every channel), a sequence of `channels` ints (one
+    colour for all videos) or an array [V, channels] (gray: also [V])."""
+    if isinstance(bar_color, str):
+        if bar_color != "auto":
+            raise ValueError(f"bar_color must be 'auto', an int, a 3-tuple or an array [V, channels], got {bar_color!r}")
+        return None
+    c = np.asarray(bar_color)
+    if c.dtype == np.bool_ or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f"bar_color must hold integers in 0..255, got {bar_color!r}")
+    if c.size and (c.min() < 0 or c.max() > 255):
+        raise ValueError(f"bar_color must hold integers in 0..255, got {bar_color!r}")
+    if c.ndim == 0:
+        c = np.full((V, channels), int(c))
+    elif c.shape == (channels,) and not (channels == 1 and V == 1):
+        c = np.broadcast_to(c, (V, channels))
+    elif channels == 1 and c.shape == (V,):
+        c = c.reshape(V, 1)
+    elif c.shape != (V, channels):
+        raise ValueError(f"bar_color must be an int, {channels} ints or an array [V, channels] = [{V}, {channels}], got shape {c.shape}")
+    c = c.astype(np.int32).reshape(V, channels)
+    return np.ascontiguousarray(sum(c[:, k] << (8 * k) for k in range(channels)), dtype=np.int32).reshape(V)
+
+
+def _unpack_bar_colors(packed: np.ndarray, channels: int) -> np.ndarray:
+    return np.stack([(packed >> (8 * k)) & 0xFF for k in range(channels)], axis=1).astype(np.uint8)
+
+
+def _bar_rule_args(black_level, min_bright, bar_color, bar_level):
+    """(level, min_bright) of a call with bar_color: its level is bar_level, and black_level stays at its default."""
+    if black_level != 16:
+        raise ValueError("black_level and bar_color cannot be combined: the level of the bar-colour rule is bar_level")
+    return _check_bar_levels(bar_level, min_bright)
+
+
+def _device_colors_and_rects(lib, frames, offsets, packed, level, bright, want_rects):
+    """hvd_dev_bar_colors (packed None) and, want_rects, hvd_dev_content_rects_color on the frames uploaded once.
+    -> (colors int32[V], rects int32[V,4] or None)."""
+    n, h, w = frames.shape[:3]
+    V, ch = len(offsets) - 1, 1 if frames.ndim == 3 else 3
+    sb = C.c_size_t(0)
+    _lib.check(lib.hvd_bar_colors_scratch_bytes(V, C.byref(sb)))
+    bufs = []
+    try:
+        d_fr = _lib.DeviceBuffer.from_array(frames) if n else None
+        bufs.append(d_fr)
+        d_off = _lib.DeviceBuffer.from_array(offsets)
+        bufs.append(d_off)
+        d_col = _lib.DeviceBuffer(4 * V) if packed is None else _lib.DeviceBuffer.from_array(packed)
+        bufs.append(d_col)
+        fr_ptr = d_fr.ptr if n else None
+        if packed is None:
+            d_acc = _lib.DeviceBuffer(sb.value)
+            bufs.append(d_acc)
+            _lib.check(lib.hvd_dev_bar_colors(fr_ptr, n, h, w, ch, d_off.ptr, V, level, d_acc.ptr, d_col.ptr))
+        rects = None
+        if want_rects:
+            d_rc = _lib.DeviceBuffer(16 * V)
+            bufs.append(d_rc)
+            _lib.check(lib.hvd_dev_content_rects_color(fr_ptr, n, h, w, ch, d_off.ptr, V, d_col.ptr, level, bright, d_rc.ptr))
+            rects = d_rc.to_array(np.int32, V * 4).reshape(V, 4)
+        colors = d_col.to_array(np.int32, V)
+    finally:
+        for b in bufs:
+            if b is not None:
+                b.free()
+    return colors, rects
+
+
+def bar_colors(frames: np.ndarray, offsets=None, bar_level: int = 16) -> np.ndarray:
+    """The automatic bar colour of every video, found on the device from the four corner pixels of all its frames:
+    uint8[V, channels] in the byte order of the pixel; (0, ...) where the corners differ by more than bar_level (no uniform
+    bars: the black rule) and for a video without frames. The rule is in include/hvd_mi355x.h (hvd_dev_bar_colors)."""
+    level, _ = _check_bar_levels(bar_level, 1)
+    frames, offsets, _, _ = _autocrop_args(frames, offsets, 16, 1)
+    channels = 1 if frames.ndim == 3 else 3
+    V = len(offsets) - 1
+    if V == 0:
+        return np.zeros((0, channels), dtype=np.uint8)
+    colors, _ = _device_colors_and_rects(_lib.ensure(), frames, offsets, None, level, 1, False)
+    return _unpack_bar_colors(colors, channels)
+
+
+def content_rects(frames: np.ndarray, offsets=None, black_level: int = 16, min_bright: int = 1, bar_color=None,
+                  bar_level=None) -> np.ndarray:
     """The content rectangle of every video, found on the device: int32[V,4] = (top, left, height, width). frames:
     uint8[n,h,w] or uint8[n,h,w,3]; offsets: int64[V+1] CSR of the videos (None: one video). The rule is in
-    include/hvd_mi355x.h (hvd_dev_content_rects)."""
+    include/hvd_mi355x.h (hvd_dev_content_rects).
+    bar_color: None is that rule (black bars). "auto", an int, a 3-tuple or an array [V, channels] is the bar-colour rule
+    (hvd_dev_bar_colors) with the level `bar_level` (default 16): bars of the video's colour are left out."""
+    if bar_color is None and bar_level is not None:
+        raise ValueError("bar_level needs bar_color (the black rule's level is black_level)")
+    if bar_color is not None:
+        level, bright = _bar_rule_args(black_level, min_bright, bar_color, bar_level)
+        frames, offsets, _, _ = _autocrop_args(frames, offsets, 16, 1)
+        V = len(offsets) - 1
+        packed = _pack_bar_color(bar_color, V, 1 if frames.ndim == 3 else 3)
+        if V == 0:
+            return np.zeros((0, 4), dtype=np.int32)
+        return _device_colors_and_rects(_lib.ensure(), frames, offsets, packed, level, bright, True)[1]
     frames, offsets, level, bright = _autocrop_args(frames, offsets, black_level, min_bright)
     lib = _lib.ensure()
     n, h, w = frames.shape[:3]
@@ -501,19 +634,34 @@ def content_rects(frames: np.ndarray, offsets=None, black_level: int = 16, min_b
     return rects
 
 
-def hash_frames_autocrop(frames: np.ndarray, offsets=None, black_level: int = 16,
-                         min_bright: int = 1) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+def hash_frames_autocrop(frames: np.ndarray, offsets=None, black_level: int = 16, min_bright: int = 1, bar_color=None,
+                         bar_level=None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """`hash_frames` inside every video's content rectangle: (hashes uint8[n,32], quality int32[n], rects int32[V,4]).
     A frame's hash and quality are the plain PDQ hash and quality of frames[f, top:top+height, left:left+width] under its
-    video's rectangle. offsets: int64[V+1] CSR of the videos (None: one video). No quality filtering."""
-    frames, offsets, level, bright = _autocrop_args(frames, offsets, black_level, min_bright)
+    video's rectangle. offsets: int64[V+1] CSR of the videos (None: one video). No quality filtering.
+    bar_color / bar_level: as `content_rects` -- the rectangle then leaves out bars of the video's colour (`bar_colors`
+    returns what "auto" finds)."""
+    if bar_color is None and bar_level is not None:
+        raise ValueError("bar_level needs bar_color (the black rule's level is black_level)")
+    if bar_color is not None:
+        level, bright = _bar_rule_args(black_level, min_bright, bar_color, bar_level)
+        frames, offsets, _, _ = _autocrop_args(frames, offsets, 16, 1)
+        packed = _pack_bar_color(bar_color, len(offsets) - 1, 1 if frames.ndim == 3 else 3)
+    else:
+        frames, offsets, level, bright = _autocrop_args(frames, offsets, black_level, min_bright)
     lib = _lib.ensure()
-    fn = lib.hvd_pdq_hash_frames_autocrop_gray_u8 if frames.ndim == 3 else lib.hvd_pdq_hash_frames_autocrop_rgb24_u8
     n, h, w = frames.shape[:3]
     V = len(offsets) - 1
     hashes = np.zeros((n, BYTES_PER_PDQ_HASH), dtype=np.uint8)
     quality = np.zeros(n, dtype=np.int32)
     rects = np.zeros((V, 4), dtype=np.int32)
+    if bar_color is not None:
+        used = np.zeros(V, dtype=np.int32)
+        fn = lib.hvd_pdq_hash_frames_barcolor_gray_u8 if frames.ndim == 3 else lib.hvd_pdq_hash_frames_barcolor_rgb24_u8
+        _lib.check(fn(frames.ctypes.data, n, h, w, offsets.ctypes.data, V, None if packed is None else packed.ctypes.data, level,
+                      bright, hashes.ctypes.data, quality.ctypes.data, rects.ctypes.data, used.ctypes.data))
+        return hashes, quality, rects
+    fn = lib.hvd_pdq_hash_frames_autocrop_gray_u8 if frames.ndim == 3 else lib.hvd_pdq_hash_frames_autocrop_rgb24_u8
     _lib.check(fn(frames.ctypes.data, n, h, w, offsets.ctypes.data, V, level, bright, hashes.ctypes.data, quality.ctypes.data,
                   rects.ctypes.data))
     return hashes, quality, rects

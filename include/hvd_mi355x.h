@@ -204,6 +204,17 @@ int hvd_pdq_hash_frames_autocrop_gray_u8(const uint8_t* frames, int64_t n, int h
 int hvd_pdq_hash_frames_autocrop_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
                                           int black_level, int min_bright, uint8_t* out_hashes, int32_t* out_quality,
                                           int32_t* out_rects);
+/* Bar-colour content-rectangle PDQ on host buffers (the rule: hvd_dev_bar_colors below): hvd_pdq_hash_frames_autocrop_* with
+ * "a pixel is content iff max_k |p_k - c_k| > bar_level" in place of "bright", c the bar colour of the frame's video. colors:
+ * int32[V], c0 | c1 << 8 | c2 << 16 per video (gray: c0 alone; anything else is HVD_ERR_ARG), or NULL: every video's colour
+ * is found from the corners of its frames. out_colors: int32[V], the colours that were used; out_rects as above. Staged and
+ * batched as hvd_pdq_hash_frames_autocrop_* (whole videos per batch, same limits, same errors). Both DCT modes. */
+int hvd_pdq_hash_frames_barcolor_gray_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
+                                         const int32_t* colors, int bar_level, int min_bright, uint8_t* out_hashes,
+                                         int32_t* out_quality, int32_t* out_rects, int32_t* out_colors);
+int hvd_pdq_hash_frames_barcolor_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
+                                          const int32_t* colors, int bar_level, int min_bright, uint8_t* out_hashes,
+                                          int32_t* out_quality, int32_t* out_rects, int32_t* out_colors);
 /* Crop-ladder PDQ on host buffers (the rule: hvd_dev_pdq_hash_frames_crops below): every frame under the full frame and under
  * the K crops of the caller's list. out_hashes8: n*8*32 bytes in the dihedral layout (slot 0 the full frame, slots 1..K the
  * crops in list order, the rest zero); out_quality: int32[n], the full frame's; out_crop_quality: int32[n*8] per slot, or
@@ -549,6 +560,28 @@ int hvd_pdq_rects_scratch_bytes(int64_t n, int h, int w, int channels, size_t* o
  * knows all its rectangles are full calls hvd_dev_pdq_hash_frames instead (same bits, fused 512x512 kernels). Both DCT modes. */
 int hvd_dev_pdq_hash_frames_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets,
                                   int64_t V, const void* d_rects, void* d_scratch, void* d_hashes, void* d_quality);
+
+/* ---- bar-colour content rectangle: re-uploads behind white, grey or coloured bars hash like the original ----
+ * The rule, integers only. Parameters: bar_level L (0..254), min_bright (>= 1), and one bar colour per video, c = (c0, c1, c2),
+ * each 0..255, in the byte order of the pixel (gray frames use c0 only). Colour record: int32 per video = c0 | c1 << 8 | c2 << 16.
+ *  1. A pixel p is content iff max_k |p_k - c_k| > L. Everything else is the content-rectangle rule above word for word, with
+ *     "bright" read as "content": content rows and columns with min_bright, the frame box, the video box as the union of the
+ *     frame boxes, the per-axis fallback below 64, the full frame for a video without frames. With c = 0 it IS that rule with
+ *     black_level = L.
+ *  2. Explicit colour: the caller writes d_colors.
+ *  3. Automatic colour (hvd_dev_bar_colors), per video, from the four corner pixels (0,0), (0,w-1), (h-1,0), (h-1,w-1) of all
+ *     its frames: per channel lo_k / hi_k are the min / max over those pixels; if hi_k - lo_k <= L on every channel,
+ *     c_k = (lo_k + hi_k) >> 1; otherwise c = (0, 0, 0), the black rule; a video without frames gets c = 0.
+ * The hash of a frame under the rectangle is the plain PDQ hash of the contiguous crop (hvd_dev_pdq_hash_frames_rects).
+ * d_offsets: as for hvd_dev_content_rects (a broken CSR gives wrong results, never an access out of bounds). d_scratch:
+ * hvd_bar_colors_scratch_bytes(V) bytes, 4-byte aligned; d_colors: int32[V], 4-byte aligned; d_rects: int32[V][4], 16-byte
+ * aligned (HVD_ERR_ARG otherwise). Nothing is allocated. 64x64 frames: every rectangle is the full frame and no frame is read
+ * for it. All enqueued on the library stream, no host synchronisation. */
+int hvd_bar_colors_scratch_bytes(int64_t V, size_t* out_bytes);
+int hvd_dev_bar_colors(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
+                       int bar_level, void* d_scratch, void* d_colors);
+int hvd_dev_content_rects_color(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
+                                const void* d_colors, int bar_level, int min_bright, void* d_rects);
 
 /* ---- crop-ladder PDQ: aspect-ratio re-crops and pan-and-scan copies hash like the original under the same rectangle
  * A crop is int32[4] = {top, left, height, width} in pixels of the call's h x w frame; it is valid iff it lies inside the frame
