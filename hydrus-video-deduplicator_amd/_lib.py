@@ -121,6 +121,10 @@ SIGNATURES = {
     "hvd_bar_colors_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
     "hvd_dev_bar_colors": (_int, [_vp, _i64, _int, _int, _int, _vp, _i64, _int, _vp, _vp]),
     "hvd_dev_content_rects_color": (_int, [_vp, _i64, _int, _int, _int, _vp, _i64, _vp, _int, _int, _vp]),
+    "hvd_pdq_hash_frames_detail_gray_u8": (_int, [_vp, _i64, _int, _int, _vp, _i64, _int, _int, _vp, _vp, _vp]),
+    "hvd_pdq_hash_frames_detail_rgb24_u8": (_int, [_vp, _i64, _int, _int, _vp, _i64, _int, _int, _vp, _vp, _vp]),
+    "hvd_dev_content_rects_detail": (_int, [_vp, _i64, _int, _int, _int, _vp, _i64, _int, _int, _vp]),
+    "hvd_hasher_create_autocrop_detail": (_int, [_int, _int, _int, _i64, _int, _int, _i64, C.POINTER(_vp)]),
     "hvd_dev_content_rects": (_int, [_vp, _i64, _int, _int, _int, _vp, _i64, _int, _int, _vp]),
     "hvd_pdq_rects_scratch_bytes": (_int, [_i64, _int, _int, _int, C.POINTER(_sz)]),
     "hvd_dev_pdq_hash_frames_rects": (_int, [_vp, _i64, _int, _int, _int, _vp, _i64, _vp, _vp, _vp, _vp]),

@@ -964,6 +964,21 @@ int hvd_dev_content_rects_color(const void* d_frames, int64_t n, int h, int w, i
     return HVD_OK;
 }
 
+/* ---- detail content rectangle (k_detail.hip) ---- */
+
+int hvd_dev_content_rects_detail(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
+                                 int detail_level, int min_detail, void* d_rects) {
+    if (int rc = need_ready()) return rc;
+    if (int rc = rects_geometry(n, h, w, channels, V)) return rc;
+    if (int rc = hvd::check_detail_levels(detail_level, min_detail)) return rc;
+    if (V == 0) return HVD_OK;
+    if (!d_offsets || !d_rects || (n > 0 && !d_frames)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if ((uintptr_t)d_rects & 15u) return fail(HVD_ERR_ARG, "d_rects must be 16-byte aligned (hvd_dev_malloc's are)");
+    HIP_TRY(hvd::launch_content_rects_detail((const uint8_t*)d_frames, n, h, w, channels, (const long long*)d_offsets, (uint32_t)V,
+                                             detail_level, min_detail, (int32_t*)d_rects, g.stream));
+    return HVD_OK;
+}
+
 /* ---- crop-ladder PDQ (k_crops.hip) ---- */
 
 // what needs no device: the frame geometry and the caller's list

@@ -43,6 +43,10 @@ inline int check_autocrop_levels(int black_level, int min_bright) {
 inline int check_bar_level(int bar_level) {
     return bar_level >= 0 && bar_level <= 254 ? HVD_OK : api_fail(HVD_ERR_ARG, "bar_level=%d: need 0..254", bar_level);
 }
+inline int check_detail_levels(int detail_level, int min_detail) {
+    if (detail_level < 0 || detail_level > 254) return api_fail(HVD_ERR_ARG, "detail_level=%d: need 0..254", detail_level);
+    return min_detail >= 1 ? HVD_OK : api_fail(HVD_ERR_ARG, "min_detail=%d: need >= 1", min_detail);
+}
 inline int check_dihedral_dct(bool dihedral) {  // the dihedral kernel has K1's strict arithmetic only
     if (!dihedral || g_pdq_dct_mode == 0) return HVD_OK;
     return api_fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");

@@ -317,6 +317,15 @@ hipError_t launch_content_rects_color(const uint8_t* d_frames, int64_t n, int h,
                                       const long long* d_offsets, uint32_t V, const int32_t* d_colors, int bar_level,
                                       int min_bright, int32_t* d_rects, hipStream_t s);
 
+// Detail content rectangle (k_detail.hip): launch_content_rects with "row y is content iff it holds >= min_detail
+// horizontal neighbour differences above detail_level, column x iff it holds >= min_detail vertical ones" as the rule (rect
+// init and finish are k_autocrop.hip's). launch_rect_fold_detail is its middle step, the streaming hasher's per-batch fold.
+hipError_t launch_rect_fold_detail(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
+                                   uint32_t V, int detail_level, int min_detail, int32_t* d_rects, hipStream_t s);
+hipError_t launch_content_rects_detail(const uint8_t* d_frames, int64_t n, int h, int w, int channels,
+                                       const long long* d_offsets, uint32_t V, int detail_level, int min_detail,
+                                       int32_t* d_rects, hipStream_t s);
+
 // Crop-ladder PDQ (k_crops.hip). crops: HOST int32[K][4] {top, left, height, width}; crops_valid: 1 <= K <=
 // HVD_MAX_CROPS and every crop inside the h x w frame with both sides >= 64 -- the one definition of a sound list.
 bool crops_valid(const int32_t* crops, int K, int h, int w);

@@ -181,20 +181,21 @@ static int64_t videos_that_fit(const int64_t* offsets, int64_t V, int64_t v0, in
 // group. Batches end on video boundaries, so a video's rectangle always sees all of its frames.
 // bar: the bar-colour form -- black_level is then the rule's bar_level, every batch's colours are the caller's
 // (bar->colors) or found from the batch's corners, and the colours used go to bar->out_colors.
+// detail: the detail form -- black_level / min_bright are then the rule's detail_level / min_detail.
 struct BarColors {
     const int32_t* colors;  // int32[V] packed, or nullptr: automatic
     int32_t* out_colors;    // int32[V]
 };
 static int hash_frames_autocrop_host(const uint8_t* frames, int64_t n, int h, int w, int channels, const int64_t* offsets,
                                      int64_t V, int black_level, int min_bright, uint8_t* out_hashes, int32_t* out_quality,
-                                     int32_t* out_rects, const BarColors* bar = nullptr) {
+                                     int32_t* out_rects, const BarColors* bar = nullptr, bool detail = false) {
     if (int rc = need_ready()) return rc;
     if (int rc = hvd::check_geometry(h, w, channels)) return rc;
     if (n < 0 || V < 0 || V >= (1ll << 31) || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad counts n=%lld V=%lld", (long long)n, (long long)V);
     if (bar) {
         if (int rc = hvd::check_bar_level(black_level)) return rc;
         if (min_bright < 1) return fail(HVD_ERR_ARG, "min_bright=%d: need >= 1", min_bright);
-    } else if (int rc = hvd::check_autocrop_levels(black_level, min_bright)) {
+    } else if (int rc = detail ? hvd::check_detail_levels(black_level, min_bright) : hvd::check_autocrop_levels(black_level, min_bright)) {
         return rc;
     }
     if (V == 0 && n == 0) return HVD_OK;
@@ -244,7 +245,9 @@ static int hash_frames_autocrop_host(const uint8_t* frames, int64_t n, int h, in
         int32_t* rects = out_rects + 4 * v0;
         HIP_TRY(hipMemcpyAsync(d_off, local.data(), 8 * (size_t)(mv + 1), hipMemcpyHostToDevice, g.stream));
         if (m > 0) HIP_TRY(hipMemcpyAsync(d_in, frames + frame_bytes * f0, frame_bytes * m, hipMemcpyHostToDevice, g.stream));
-        if (!bar) {
+        if (detail) {
+            if (int rc = hvd_dev_content_rects_detail(d_in, m, h, w, channels, d_off, mv, black_level, min_bright, d_rects)) return rc;
+        } else if (!bar) {
             if (int rc = hvd_dev_content_rects(d_in, m, h, w, channels, d_off, mv, black_level, min_bright, d_rects)) return rc;
         } else {
             if (bar->colors) {
@@ -296,6 +299,20 @@ int hvd_pdq_hash_frames_barcolor_rgb24_u8(const uint8_t* frames, int64_t n, int 
                                           int32_t* out_quality, int32_t* out_rects, int32_t* out_colors) {
     const BarColors bar{colors, out_colors};
     return hash_frames_autocrop_host(frames, n, h, w, 3, offsets, V, bar_level, min_bright, out_hashes, out_quality, out_rects, &bar);
+}
+
+int hvd_pdq_hash_frames_detail_gray_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
+                                       int detail_level, int min_detail, uint8_t* out_hashes, int32_t* out_quality,
+                                       int32_t* out_rects) {
+    return hash_frames_autocrop_host(frames, n, h, w, 1, offsets, V, detail_level, min_detail, out_hashes, out_quality, out_rects,
+                                     nullptr, true);
+}
+
+int hvd_pdq_hash_frames_detail_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
+                                        int detail_level, int min_detail, uint8_t* out_hashes, int32_t* out_quality,
+                                        int32_t* out_rects) {
+    return hash_frames_autocrop_host(frames, n, h, w, 3, offsets, V, detail_level, min_detail, out_hashes, out_quality, out_rects,
+                                     nullptr, true);
 }
 
 // Runs the default all-pairs kernel (FP4-MFMA form) on a host DB -- this context's share of the tiles (rank of world) --

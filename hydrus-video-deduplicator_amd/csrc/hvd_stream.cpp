@@ -114,6 +114,7 @@ struct hvd_hasher {
     // autocrop (hvd_hasher_create_autocrop)
     bool autocrop = false;
     int black_level = 0, min_bright = 0;
+    bool detail = false;           // hvd_hasher_create_autocrop_detail: the fold is the detail rule, the two above its level and count
     int64_t max_frames = 0;        // frames one video may retain (max_retained_bytes / frame_bytes)
     int64_t taken = 0;             // frames committed since the last finish
     bool rect_closed = false;      // k_rect_finish has turned the accumulators into the rectangle (it must run once)
@@ -200,8 +201,8 @@ static int submit_retain(hvd_hasher* hs, Slot& s) {
     Block& b = hs->store.back();
     uint8_t* dst = b.d + hs->frame_bytes * (size_t)b.used;
     S_TRY(hipMemcpyAsync(dst, s.h_frames, hs->frame_bytes * (size_t)m, hipMemcpyHostToDevice, s.stream));
-    S_TRY(hvd::launch_rect_fold(dst, m, hs->h, hs->w, hs->channels, hs->d_offsets(), 1, hs->black_level, hs->min_bright,
-                                hs->d_rect(), s.stream));
+    S_TRY((hs->detail ? hvd::launch_rect_fold_detail : hvd::launch_rect_fold)(dst, m, hs->h, hs->w, hs->channels, hs->d_offsets(), 1,
+                                                                              hs->black_level, hs->min_bright, hs->d_rect(), s.stream));
     S_TRY(hipEventRecord(s.done, s.stream));
     b.used += m;
     s.in_flight = m;
@@ -333,6 +334,7 @@ int hvd_hasher_destroy(hvd_hasher* hs) {
 struct AutocropArgs {
     int black_level, min_bright;
     int64_t max_retained_bytes;
+    bool detail;  // black_level / min_bright are detail_level / min_detail
 };
 
 static int create_hasher(int width, int height, int channels, int64_t batch_frames, bool dihedral, hvd_hasher** out,
@@ -343,13 +345,17 @@ static int create_hasher(int width, int height, int channels, int64_t batch_fram
     if (int rc = hvd::check_geometry(height, width, channels)) return rc;
     if (batch_frames < 1) return hvd::api_fail(HVD_ERR_ARG, "bad hasher batch of %lld frames", (long long)batch_frames);
     if (int rc = hvd::check_dihedral_dct(dihedral)) return rc;
-    if (int rc = ac ? hvd::check_autocrop_levels(ac->black_level, ac->min_bright) : HVD_OK) return rc;
+    if (int rc = !ac ? HVD_OK
+                 : ac->detail ? hvd::check_detail_levels(ac->black_level, ac->min_bright)
+                              : hvd::check_autocrop_levels(ac->black_level, ac->min_bright))
+        return rc;
     const int64_t max_frames =
         !ac ? 0 : (ac->max_retained_bytes > 0 ? ac->max_retained_bytes : kDefaultRetained) / ((int64_t)width * height * channels);
     const auto set_autocrop = [&](hvd_hasher* p) {
         if (!ac) return;
         p->black_level = ac->black_level;
         p->min_bright = ac->min_bright;
+        p->detail = ac->detail;
         p->max_frames = max_frames;
     };
     {
@@ -413,7 +419,13 @@ extern "C" {
 
 int hvd_hasher_create_autocrop(int width, int height, int channels, int64_t batch_frames, int black_level, int min_bright,
                                int64_t max_retained_bytes, hvd_hasher** out) {
-    const AutocropArgs ac{black_level, min_bright, max_retained_bytes};
+    const AutocropArgs ac{black_level, min_bright, max_retained_bytes, false};
+    return create_hasher(width, height, channels, batch_frames, false, out, &ac);
+}
+
+int hvd_hasher_create_autocrop_detail(int width, int height, int channels, int64_t batch_frames, int detail_level, int min_detail,
+                                      int64_t max_retained_bytes, hvd_hasher** out) {
+    const AutocropArgs ac{detail_level, min_detail, max_retained_bytes, true};
     return create_hasher(width, height, channels, batch_frames, false, out, &ac);
 }
 

@@ -33,7 +33,8 @@ def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
     quality >= 31 are kept in order (VideoHasher.finish semantics, vpdqpy/vpdqpy.py:119).
     autocrop: True or a dict of black_level / min_bright: every video is hashed inside its content rectangle
     (vpdq.hash_frames_autocrop). A dict of bar_color / bar_level / min_bright (vpdq.autocrop_rule) leaves out
-    bars of the video's colour instead; an array bar_color has one row per video of `videos`."""
+    bars of the video's colour instead; an array bar_color has one row per video of `videos`. A dict of
+    detail (True) / detail_level / min_detail leaves out smooth bars of any colour -- blurred, gradient -- (DESIGN 4.16)."""
     crop = vpdq.autocrop_rule(autocrop)
     videos = [np.ascontiguousarray(v, dtype=np.uint8) for v in videos]
     if not videos:
@@ -47,8 +48,7 @@ def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
         return [vpdq.VpdqHash(b"") for _ in videos]
     flat = np.concatenate([v for v in videos if v.shape[0]], axis=0)
     if crop is not None:
-        level = dict(black_level=crop[0]) if crop[2] is None else dict(bar_color=crop[2], bar_level=crop[0])
-        hashes, quality, _ = vpdq.hash_frames_autocrop(flat, np.concatenate([[0], np.cumsum(lengths)]), min_bright=crop[1], **level)
+        hashes, quality, _ = vpdq.hash_frames_autocrop(flat, np.concatenate([[0], np.cumsum(lengths)]), **vpdq.rule_kwargs(crop))
     else:
         hashes, quality = vpdq.hash_frames(flat)
     out, pos = [], 0
@@ -143,14 +143,18 @@ def hash_frames_dihedral_on_device(d_frames_ptr: int, n: int, h: int, w: int, ch
 
 
 def hash_frames_autocrop_on_device(d_frames_ptr: int, n: int, h: int, w: int, channels: int, offsets: np.ndarray,
-                                   black_level: int = 16, min_bright: int = 1, timed=None, bar_color=None, bar_level=None):
+                                   black_level: int = 16, min_bright: int = 1, timed=None, bar_color=None, bar_level=None,
+                                   detail=False, detail_level=None, min_detail=None):
     """Content-rectangle form of `hash_frames_on_device`: the n frames in HBM are the videos of the CSR
     `offsets` (int64[V+1], from 0 to n); hvd_dev_content_rects finds every video's rectangle, hvd_dev_pdq_hash_frames_rects
     hashes every frame inside it. -> (d_hashes, d_quality, d_rects) DeviceBuffers (n*32 B, int32[n], int32[V,4]).
     timed(key, fn): optional stage timer, called with "rects_ms" and "hash_ms".
     bar_color ("auto", an int, a 3-tuple or an array [V, channels]) with bar_level (default 16): the rectangles leave out
     bars of the video's colour (hvd_dev_bar_colors where "auto", then hvd_dev_content_rects_color; both inside
-    "rects_ms"); black_level then stays at its default."""
+    "rects_ms"); black_level then stays at its default.
+    detail=True with detail_level / min_detail (defaults 8 and 8, unverified): the rectangles leave out smooth bars of any
+    colour (hvd_dev_content_rects_detail in "rects_ms"); the other rules' keywords then stay at their defaults."""
+    levels = vpdq._detail_rule_args(detail, detail_level, min_detail, vpdq._other_rules(black_level, min_bright, bar_color, bar_level))
     lib = _lib.ensure()
     offsets = _check_raw_offsets(offsets, n)
     V = offsets.size - 1
@@ -163,7 +167,10 @@ def hash_frames_autocrop_on_device(d_frames_ptr: int, n: int, h: int, w: int, ch
     with _DeviceScope() as scope:
         d_off = scope.keep(DeviceBuffer.from_array(offsets))
         d_r = scope.keep(DeviceBuffer(16 * max(V, 1)))
-        if bar_color is None:
+        if levels is not None:
+            run("rects_ms", lambda: _lib.check(lib.hvd_dev_content_rects_detail(d_frames_ptr, n, h, w, channels, d_off.ptr, V,
+                                                                                levels[0], levels[1], d_r.ptr)))
+        elif bar_color is None:
             run("rects_ms", lambda: _lib.check(lib.hvd_dev_content_rects(d_frames_ptr, n, h, w, channels, d_off.ptr, V,
                                                                          int(black_level), int(min_bright), d_r.ptr)))
         else:
@@ -660,8 +667,11 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
     hvd_dev_pdq_hash_frames_rects over this rank's own videos (`hash_frames_autocrop_on_device`; a rank owns whole videos,
     so every rectangle sees all its frames); timings then also receives rects_ms. Everything after the hash stage is
     unchanged. A dict of bar_color / bar_level / min_bright (vpdq.autocrop_rule) finds the rectangles by the
-    bar-colour rule instead; that form is for world == 1 (an array bar_color has one row per video of the library)."""
+    bar-colour rule instead; that form is for world == 1 (an array bar_color has one row per video of the library). A dict
+    of detail (True) / detail_level / min_detail finds them by the detail rule, for world == 1 as well."""
     crop = vpdq.autocrop_rule(autocrop)
+    if crop is not None and crop[2] is vpdq.DETAIL and world != 1:
+        raise ValueError("the detail rule is not sharded over a device group: world must be 1")
     if crop is not None and crop[2] is not None and world != 1:
         raise ValueError("the bar-colour rule is not sharded over a device group: world must be 1")
     timed = _stage_timer(timings)
@@ -673,8 +683,8 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
         if crop[2] is None:
             d_h, d_q, d_r = hash_frames_autocrop_on_device(d_frames_ptr, n_mine, h, w, channels, mine, crop[0], crop[1], timed)
         else:
-            d_h, d_q, d_r = hash_frames_autocrop_on_device(d_frames_ptr, n_mine, h, w, channels, mine, min_bright=crop[1],
-                                                           timed=timed, bar_color=crop[2], bar_level=crop[0])
+            d_h, d_q, d_r = hash_frames_autocrop_on_device(d_frames_ptr, n_mine, h, w, channels, mine, timed=timed,
+                                                           **vpdq.rule_kwargs(crop))
         d_r.free()
         return d_h, d_q
 
@@ -929,7 +939,13 @@ def dedupe_frames_in_process(frames_of_rank, raw_offsets: np.ndarray, h: int, w:
     device pointer of the frames of that rank's video range (`video_range_of_rank`), resident on that rank's device (it is
     called on the rank's thread, with the rank's context current). -> (pairs, records) -- every rank computes the same;
     rank 0's are returned. timings: rank 0's stage times. autocrop: as `dedupe_frames_on_device`."""
-    vpdq.autocrop_params(autocrop)  # a bad value fails here, not on every rank's thread
+    # a bad value fails here, not on every rank's thread; a group takes the black rule only
+    black = autocrop
+    if isinstance(autocrop, dict) and vpdq._DETAIL_KEYS & set(autocrop):
+        if vpdq.autocrop_rule(autocrop)[2] is vpdq.DETAIL:
+            raise ValueError("the detail rule is not sharded over a device group: world must be 1 (dedupe_frames_on_device)")
+        black = {k: v for k, v in autocrop.items() if k != "detail"}  # "detail": False states the default
+    vpdq.autocrop_params(black)
     return _rank0_of_every_context(dedupe_frames_on_device, frames_of_rank, timings, 2, raw_offsets, h, w, channels,
                                    threshold, policy, autocrop=autocrop)
 

@@ -197,8 +197,11 @@ class VideoHasher:
     one video, byte for byte. After ``finish()``, ``rect`` is ``(top, left, height, width)``. ``max_retained_bytes``: how
     many bytes of frames one video may keep on the device (None: the library default, 8 GiB); the frame that would pass
     it raises HvdError(HVD_ERR_OVERFLOW) and ``finish()`` still returns the result of the frames taken before. Not
-    together with ``transforms``. The black rule only: a dict with ``bar_color`` / ``bar_level`` raises a
-    ValueError that names the array form (``hash_frames_autocrop(frames, bar_color=...)``)."""
+    together with ``transforms``. A dict with ``bar_color`` / ``bar_level`` raises a ValueError that names the
+    array form (``hash_frames_autocrop(frames, bar_color=...)``): that colour is known only after the last frame.
+    ``{"detail": True}``, with optional ``detail_level`` (default 8, unverified) / ``min_detail`` (default 8, unverified),
+    is the detail rule (hvd_hasher_create_autocrop_detail): smooth bars of any colour -- blurred, gradient --
+    are left out. It is order-free per frame, so it streams; ``finish()`` equals ``hash_frames_autocrop(frames, detail=True)``."""
 
     def __init__(self, average_fps: int, width: int, height: int, num_threads: int = 0,
                  batch_bytes: int = 32 << 20, transforms=None, autocrop=None, max_retained_bytes: int | None = None):
@@ -207,7 +210,9 @@ class VideoHasher:
         if isinstance(autocrop, dict) and {"bar_color", "bar_level"} & set(autocrop):
             raise ValueError("the streaming hasher has no bar-colour rule (the automatic colour is known only after the last "
                              "frame): hash the array form of the frames, vpdq.hash_frames_autocrop(frames, bar_color=...)")
-        self._autocrop = autocrop_params(autocrop)
+        rule = autocrop_rule(autocrop)
+        self._detail = rule is not None and rule[2] is DETAIL
+        self._autocrop = None if rule is None else rule[:2]
         if self._autocrop is not None and transforms is not None:
             raise ValueError("autocrop and transforms cannot be combined (content-rectangle dihedral hashing does not exist)")
         if max_retained_bytes is not None and (isinstance(max_retained_bytes, bool) or not isinstance(max_retained_bytes, (int, np.integer))
@@ -243,8 +248,9 @@ class VideoHasher:
         batch = max(1, min(4096, self._batch_bytes // frame_bytes))
         h = C.c_void_p()
         if self._autocrop is not None:
-            _lib.check(self._lib.hvd_hasher_create_autocrop(self.width, self.height, channels, batch, self._autocrop[0],
-                                                            self._autocrop[1], self._max_retained, C.byref(h)))
+            create = self._lib.hvd_hasher_create_autocrop_detail if self._detail else self._lib.hvd_hasher_create_autocrop
+            _lib.check(create(self.width, self.height, channels, batch, self._autocrop[0], self._autocrop[1], self._max_retained,
+                              C.byref(h)))
         else:
             create = self._lib.hvd_hasher_create if self._transforms is None else self._lib.hvd_hasher_create_dihedral
             _lib.check(create(self.width, self.height, channels, batch, C.byref(h)))
@@ -484,13 +490,83 @@ def _autocrop_args(frames, offsets, black_level, min_bright):
 # content iff it differs from its video's bar colour by more than bar_level on some channel.
 _RULE_KEYS = {"black_level", "min_bright", "bar_color", "bar_level"}
 
+# Detail content rectangle (include/hvd_mi355x.h: hvd_dev_content_rects_detail): bars that are smooth. A row is
+# content iff it holds >= min_detail horizontal neighbour differences above detail_level, a column likewise with vertical ones.
+_DETAIL_KEYS = {"detail", "detail_level", "min_detail"}
+
+
+class _DetailRule:
+    """What `autocrop_rule` returns in the colour's place for the detail rule."""
+
+    def __repr__(self):
+        return "DETAIL"
+
+
+DETAIL = _DetailRule()
+
+
+def _check_detail_levels(detail_level, min_detail) -> tuple[int, int]:
+    """(detail_level, min_detail) with the defaults 8 and 8 (both unverified on real video) for None."""
+    detail_level = 8 if detail_level is None else detail_level
+    min_detail = 8 if min_detail is None else min_detail
+    for name, v in (("detail_level", detail_level), ("min_detail", min_detail)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not 0 <= detail_level <= 254:
+        raise ValueError(f"detail_level must be in 0..254 (two neighbours differ iff some channel differs by more than "
+                         f"detail_level), got {detail_level}")
+    if not 1 <= min_detail < 2**31:
+        raise ValueError(f"min_detail must be >= 1, got {min_detail}")
+    return int(detail_level), int(min_detail)
+
+
+def _detail_rule_args(detail, detail_level, min_detail, others: dict):
+    """The detail keywords of a call. -> None (the other rules) or (detail_level, min_detail). others: name -> (value, default)
+    of the other rules' keywords, none of which goes with the detail rule."""
+    if detail is not True and detail is not False:
+        raise ValueError(f"detail must be True or False, got {detail!r}")
+    if not detail:
+        for name, v in (("detail_level", detail_level), ("min_detail", min_detail)):
+            if v is not None:
+                raise ValueError(f"{name} needs detail=True (the detail rule, DESIGN 4.16)")
+        return None
+    for name, (v, default) in others.items():
+        same_int = default is not None and not isinstance(v, bool) and isinstance(v, (int, np.integer)) and v == default
+        if v is not default and not same_int:
+            raise ValueError(f"detail and {name} cannot be combined: the detail rule's parameters are detail_level and min_detail")
+    return _check_detail_levels(detail_level, min_detail)
+
+
+def rule_kwargs(rule) -> dict:
+    """The keywords of `hash_frames_autocrop` / `content_rects` that state what `autocrop_rule` returned (not None)."""
+    if rule[2] is None:
+        return dict(black_level=rule[0], min_bright=rule[1])
+    if rule[2] is DETAIL:
+        return dict(detail=True, detail_level=rule[0], min_detail=rule[1])
+    return dict(bar_color=rule[2], bar_level=rule[0], min_bright=rule[1])
+
 
 def autocrop_rule(autocrop) -> tuple[int, int, object] | None:
     """`autocrop_params` for the call sites that also know the bar-colour rule: None when `autocrop` is off, else
     (level, min_bright, bar_color). bar_color None is the black rule and level its black_level -- what `autocrop_params`
     returns, for every input it accepts. A dict with ``bar_color`` ("auto", an int, a 3-tuple or an array [V, channels])
     may carry ``bar_level`` (default 16) and ``min_bright``; ``black_level`` together with ``bar_color`` is a ValueError,
-    and so is ``bar_level`` without it. The colour's shape is checked where the frames are known."""
+    and so is ``bar_level`` without it. The colour's shape is checked where the frames are known.
+    A dict with ``detail`` True is the detail rule: (detail_level, min_detail, DETAIL), from the optional keys
+    ``detail_level`` (default 8, unverified) and ``min_detail`` (default 8, unverified). Any key of the other rules beside
+    it is a ValueError that names both, and so are ``detail_level`` / ``min_detail`` without ``detail``."""
+    if isinstance(autocrop, dict) and _DETAIL_KEYS & set(autocrop):
+        if set(autocrop) - _RULE_KEYS - _DETAIL_KEYS:
+            raise ValueError("autocrop must be True / False or a dict with the keys black_level and min_bright, or bar_color, "
+                             "bar_level and min_bright, or detail, detail_level and min_detail")
+        detail = autocrop.get("detail", False)
+        if detail is True and _RULE_KEYS & set(autocrop):
+            name = sorted(_RULE_KEYS & set(autocrop))[0]
+            raise ValueError(f"detail and {name} cannot be combined: the detail rule's parameters are detail_level and min_detail")
+        levels = _detail_rule_args(detail, autocrop.get("detail_level"), autocrop.get("min_detail"), {})
+        if levels is not None:
+            return (*levels, DETAIL)
+        autocrop = {k: v for k, v in autocrop.items() if k != "detail"}  # "detail": False states the default
     if not isinstance(autocrop, dict) or not ({"bar_color", "bar_level"} & set(autocrop)):
         params = autocrop_params(autocrop)
         return None if params is None else (*params, None)
@@ -596,13 +672,26 @@ def bar_colors(frames: np.ndarray, offsets=None, bar_level: int = 16) -> np.ndar
     return _unpack_bar_colors(colors, channels)
 
 
+def _other_rules(black_level, min_bright, bar_color, bar_level) -> dict:
+    return {"black_level": (black_level, 16), "min_bright": (min_bright, 1), "bar_color": (bar_color, None),
+            "bar_level": (bar_level, None)}
+
+
 def content_rects(frames: np.ndarray, offsets=None, black_level: int = 16, min_bright: int = 1, bar_color=None,
-                  bar_level=None) -> np.ndarray:
+                  bar_level=None, detail=False, detail_level=None, min_detail=None) -> np.ndarray:
     """The content rectangle of every video, found on the device: int32[V,4] = (top, left, height, width). frames:
     uint8[n,h,w] or uint8[n,h,w,3]; offsets: int64[V+1] CSR of the videos (None: one video). The rule is in
     include/hvd_mi355x.h (hvd_dev_content_rects).
     bar_color: None is that rule (black bars). "auto", an int, a 3-tuple or an array [V, channels] is the bar-colour rule
-    (hvd_dev_bar_colors) with the level `bar_level` (default 16): bars of the video's colour are left out."""
+    (hvd_dev_bar_colors) with the level `bar_level` (default 16): bars of the video's colour are left out.
+    detail=True is the detail rule (hvd_dev_content_rects_detail) with `detail_level` (default 8, unverified)
+    and `min_detail` (default 8, unverified): smooth bars of any colour are left out; none of the other rules' keywords
+    goes with it."""
+    levels = _detail_rule_args(detail, detail_level, min_detail, _other_rules(black_level, min_bright, bar_color, bar_level))
+    entry = "hvd_dev_content_rects"
+    if levels is not None:
+        black_level, min_bright = levels
+        entry = "hvd_dev_content_rects_detail"
     if bar_color is None and bar_level is not None:
         raise ValueError("bar_level needs bar_color (the black rule's level is black_level)")
     if bar_color is not None:
@@ -613,7 +702,9 @@ def content_rects(frames: np.ndarray, offsets=None, black_level: int = 16, min_b
         if V == 0:
             return np.zeros((0, 4), dtype=np.int32)
         return _device_colors_and_rects(_lib.ensure(), frames, offsets, packed, level, bright, True)[1]
-    frames, offsets, level, bright = _autocrop_args(frames, offsets, black_level, min_bright)
+    frames, offsets, level, bright = _autocrop_args(frames, offsets, 16 if levels else black_level, 1 if levels else min_bright)
+    if levels is not None:
+        level, bright = levels
     lib = _lib.ensure()
     n, h, w = frames.shape[:3]
     V = len(offsets) - 1
@@ -624,8 +715,8 @@ def content_rects(frames: np.ndarray, offsets=None, black_level: int = 16, min_b
     d_off = _lib.DeviceBuffer.from_array(offsets)
     d_rc = _lib.DeviceBuffer(rects.nbytes)
     try:
-        _lib.check(lib.hvd_dev_content_rects(d_fr.ptr if n else None, n, h, w, 1 if frames.ndim == 3 else 3, d_off.ptr, V,
-                                             level, bright, d_rc.ptr))
+        _lib.check(getattr(lib, entry)(d_fr.ptr if n else None, n, h, w, 1 if frames.ndim == 3 else 3, d_off.ptr, V,
+                                       level, bright, d_rc.ptr))
         rects[:] = d_rc.to_array(np.int32, V * 4).reshape(V, 4)
     finally:
         for b in (d_fr, d_off, d_rc):
@@ -635,15 +726,21 @@ def content_rects(frames: np.ndarray, offsets=None, black_level: int = 16, min_b
 
 
 def hash_frames_autocrop(frames: np.ndarray, offsets=None, black_level: int = 16, min_bright: int = 1, bar_color=None,
-                         bar_level=None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+                         bar_level=None, detail=False, detail_level=None,
+                         min_detail=None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """`hash_frames` inside every video's content rectangle: (hashes uint8[n,32], quality int32[n], rects int32[V,4]).
     A frame's hash and quality are the plain PDQ hash and quality of frames[f, top:top+height, left:left+width] under its
     video's rectangle. offsets: int64[V+1] CSR of the videos (None: one video). No quality filtering.
     bar_color / bar_level: as `content_rects` -- the rectangle then leaves out bars of the video's colour (`bar_colors`
-    returns what "auto" finds)."""
+    returns what "auto" finds).
+    detail / detail_level / min_detail: as `content_rects` -- the rectangle then leaves out smooth bars of any colour."""
+    levels = _detail_rule_args(detail, detail_level, min_detail, _other_rules(black_level, min_bright, bar_color, bar_level))
     if bar_color is None and bar_level is not None:
         raise ValueError("bar_level needs bar_color (the black rule's level is black_level)")
-    if bar_color is not None:
+    if levels is not None:
+        frames, offsets, _, _ = _autocrop_args(frames, offsets, 16, 1)
+        level, bright = levels
+    elif bar_color is not None:
         level, bright = _bar_rule_args(black_level, min_bright, bar_color, bar_level)
         frames, offsets, _, _ = _autocrop_args(frames, offsets, 16, 1)
         packed = _pack_bar_color(bar_color, len(offsets) - 1, 1 if frames.ndim == 3 else 3)
@@ -661,7 +758,8 @@ def hash_frames_autocrop(frames: np.ndarray, offsets=None, black_level: int = 16
         _lib.check(fn(frames.ctypes.data, n, h, w, offsets.ctypes.data, V, None if packed is None else packed.ctypes.data, level,
                       bright, hashes.ctypes.data, quality.ctypes.data, rects.ctypes.data, used.ctypes.data))
         return hashes, quality, rects
-    fn = lib.hvd_pdq_hash_frames_autocrop_gray_u8 if frames.ndim == 3 else lib.hvd_pdq_hash_frames_autocrop_rgb24_u8
+    kind = "detail" if levels is not None else "autocrop"
+    fn = getattr(lib, f"hvd_pdq_hash_frames_{kind}_gray_u8" if frames.ndim == 3 else f"hvd_pdq_hash_frames_{kind}_rgb24_u8")
     _lib.check(fn(frames.ctypes.data, n, h, w, offsets.ctypes.data, V, level, bright, hashes.ctypes.data, quality.ctypes.data,
                   rects.ctypes.data))
     return hashes, quality, rects

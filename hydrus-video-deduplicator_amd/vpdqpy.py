@@ -108,7 +108,8 @@ class Vpdq:
         autocrop: True, or a dict with ``black_level`` / ``min_bright``, hashes an array of frames inside the video's content
         rectangle (``vpdq.hash_frames_autocrop``: black bars are left out) and applies the usual quality filter. A dict with
         ``bar_color`` ("auto", an int, a 3-tuple) / ``bar_level`` / ``min_bright`` leaves out bars of that colour instead
-        (``vpdq.autocrop_rule``). The rectangle
+        (``vpdq.autocrop_rule``); ``{"detail": True}`` with optional ``detail_level`` / ``min_detail`` leaves out
+        smooth bars of any colour -- blurred, gradient -- (DESIGN 4.16). The rectangle
         is known only after the last frame, so an iterable of frames cannot be hashed this way: pass the array form."""
         if frames is None:
             raise ValueError
@@ -130,8 +131,7 @@ class Vpdq:
                 raise ValueError("frames must be uint8[n,h,w] or uint8[n,h,w,3]")
             h, w = frames.shape[1], frames.shape[2]
             if crop is not None:
-                level = dict(black_level=crop[0]) if crop[2] is None else dict(bar_color=crop[2], bar_level=crop[0])
-                hashes, quality, _ = vpdq.hash_frames_autocrop(frames, None, min_bright=crop[1], **level)
+                hashes, quality, _ = vpdq.hash_frames_autocrop(frames, None, **vpdq.rule_kwargs(crop))
                 return VpdqHash(hashes[quality >= vpdq.QUALITY_TOLERANCE].tobytes())
             hasher = vpdq.VideoHasher(average_fps, w, h, num_threads)
             flat = np.ascontiguousarray(frames, dtype=np.uint8).reshape(frames.shape[0], -1)

@@ -40,7 +40,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -215,6 +215,16 @@ int hvd_pdq_hash_frames_barcolor_gray_u8(const uint8_t* frames, int64_t n, int h
 int hvd_pdq_hash_frames_barcolor_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
                                           const int32_t* colors, int bar_level, int min_bright, uint8_t* out_hashes,
                                           int32_t* out_quality, int32_t* out_rects, int32_t* out_colors);
+/* Detail content-rectangle PDQ on host buffers (the rule: hvd_dev_content_rects_detail below): hvd_pdq_hash_frames_autocrop_*
+ * with the detail rule as its rectangle step -- bars that are smooth (blurred, gradient, any colour) are left out. detail_level
+ * 0..254, min_detail >= 1 (HVD_ERR_ARG otherwise). Staged and batched as hvd_pdq_hash_frames_autocrop_* (whole videos per batch,
+ * same limits, same errors, the plain kernels when every rectangle of a batch is full). Both DCT modes. */
+int hvd_pdq_hash_frames_detail_gray_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
+                                       int detail_level, int min_detail, uint8_t* out_hashes, int32_t* out_quality,
+                                       int32_t* out_rects);
+int hvd_pdq_hash_frames_detail_rgb24_u8(const uint8_t* frames, int64_t n, int h, int w, const int64_t* offsets, int64_t V,
+                                        int detail_level, int min_detail, uint8_t* out_hashes, int32_t* out_quality,
+                                        int32_t* out_rects);
 /* Crop-ladder PDQ on host buffers (the rule: hvd_dev_pdq_hash_frames_crops below): every frame under the full frame and under
  * the K crops of the caller's list. out_hashes8: n*8*32 bytes in the dihedral layout (slot 0 the full frame, slots 1..K the
  * crops in list order, the rest zero); out_quality: int32[n], the full frame's; out_crop_quality: int32[n*8] per slot, or
@@ -441,6 +451,12 @@ int hvd_hasher_create_autocrop(int width, int height, int channels, int64_t batc
                                int64_t max_retained_bytes, hvd_hasher** out);
 int hvd_hasher_finish_autocrop(hvd_hasher* hs, uint8_t* out_hashes, int32_t* out_quality, int64_t cap, int64_t* out_n,
                                int32_t out_rect[4]);
+/* The autocrop streaming hasher under the detail rule (hvd_dev_content_rects_detail): the per-batch fold is the detail kernel,
+ * everything else -- retain, finish with hvd_hasher_finish_autocrop, reset, limits, errors -- is hvd_hasher_create_autocrop's.
+ * For any sequence of frames the result equals hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8 on the same frames as one video
+ * with the same detail_level (0..254) / min_detail (>= 1; else HVD_ERR_ARG). The rule is order-free per frame, so it streams. */
+int hvd_hasher_create_autocrop_detail(int width, int height, int channels, int64_t batch_frames, int detail_level, int min_detail,
+                                      int64_t max_retained_bytes, hvd_hasher** out);
 
 /* --------------------------------------------- device-resident API ------- */
 /* For pipelines that keep data in HBM (hash on the GPU, then search) and for the
@@ -582,6 +598,20 @@ int hvd_dev_bar_colors(const void* d_frames, int64_t n, int h, int w, int channe
                        int bar_level, void* d_scratch, void* d_colors);
 int hvd_dev_content_rects_color(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
                                 const void* d_colors, int bar_level, int min_bright, void* d_rects);
+
+/* ---- detail content rectangle: re-uploads behind blurred, gradient or any other smooth bars hash like the original ----
+ * The rule, integers only. Parameters: detail_level L (0..254), min_detail m (>= 1). For a frame p[y][x][k], h rows, w columns:
+ *  1. dh(y, x) = max_k |p[y][x][k] - p[y][x+1][k]| > L, x in [0, w-2]. ROW y is content iff #{x : dh(y, x)} >= m.
+ *  2. dv(y, x) = max_k |p[y][x][k] - p[y+1][x][k]| > L, y in [0, h-2]. COLUMN x is content iff #{y : dv(y, x)} >= m.
+ *  3. Everything else is the content-rectangle rule of hvd_dev_content_rects word for word: the frame box from content rows x
+ *     content columns, the video box as the union of the frame boxes, the per-axis fallback below 64, the full frame for a
+ *     video without frames. Rows count horizontal differences only and columns vertical ones only, so the step between a bar
+ *     and the picture never makes a bar row or a bar column content.
+ * No colour and no corner enters the rule: it covers black, coloured, gradient and blurred bars alike, and misses bars that
+ * carry text, a logo or noise above L. Arguments, alignment, the 64x64 shortcut and the broken-CSR guarantee are
+ * hvd_dev_content_rects'. Enqueued on the library stream, no host synchronisation, nothing allocated. */
+int hvd_dev_content_rects_detail(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
+                                 int detail_level, int min_detail, void* d_rects);
 
 /* ---- crop-ladder PDQ: aspect-ratio re-crops and pan-and-scan copies hash like the original under the same rectangle
  * A crop is int32[4] = {top, left, height, width} in pixels of the call's h x w frame; it is valid iff it lies inside the frame
