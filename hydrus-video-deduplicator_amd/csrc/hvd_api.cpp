@@ -831,6 +831,13 @@ int hvd_pdq_scratch_bytes(int64_t n, int h, int w, int channels, size_t* out_byt
 
 }  // extern "C" (the helpers below have C++ linkage: hvd_hash_host.h)
 
+static int rects_geometry(int64_t n, int h, int w, int channels, int64_t V) {
+    if (int rc = hvd::check_geometry(h, w, channels)) return rc;
+    if (n < 0 || V < 0 || V >= (1ll << 31) || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad counts n=%lld V=%lld", (long long)n, (long long)V);
+    if (n > 0 && V == 0) return fail(HVD_ERR_ARG, "n=%lld frames in no video", (long long)n);
+    return HVD_OK;
+}
+
 namespace hvd {
 hipError_t api_launch_hash(const void* d_frames, int64_t n, int h, int w, int channels, void* d_scratch, void* d_hashes,
                            void* d_quality, hipStream_t s, bool dihedral) {
@@ -856,6 +863,21 @@ hipError_t api_launch_hash_rects(const void* d_frames, int64_t n, int h, int w, 
                                                (float*)(base + lay.planes), s);
     if (e != hipSuccess) return e;
     return launch_pdq_hash64(base + lay.planes, 1, n, g.d_dct, (uint8_t*)d_hashes, (int32_t*)d_quality, s);
+}
+
+int api_content_rects(const RectRule& rule, const void* d_colors, const void* d_frames, int64_t n, int h, int w, int channels,
+                      const void* d_offsets, int64_t V, void* d_rects) {
+    const bool color = rule.kind == RectKind::Color;
+    if (int rc = need_ready()) return rc;
+    if (int rc = rects_geometry(n, h, w, channels, V)) return rc;
+    if (int rc = check_rect_rule(rule)) return rc;
+    if (V == 0) return HVD_OK;
+    if (!d_offsets || !d_rects || (color && !d_colors) || (n > 0 && !d_frames)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if ((uintptr_t)d_rects & 15u) return fail(HVD_ERR_ARG, "d_rects must be 16-byte aligned (hvd_dev_malloc's are)");
+    if (color && ((uintptr_t)d_colors & 3u)) return fail(HVD_ERR_ARG, "d_colors must be 4-byte aligned");
+    HIP_TRY(launch_content_rects(rule, (const int32_t*)d_colors, (const uint8_t*)d_frames, n, h, w, channels,
+                                 (const long long*)d_offsets, (uint32_t)V, (int32_t*)d_rects, g.stream));
+    return HVD_OK;
 }
 }  // namespace hvd
 
@@ -887,24 +909,9 @@ int hvd_dev_pdq_hash_frames_dihedral(const void* d_frames, int64_t n, int h, int
 
 /* ---- content-rectangle PDQ (k_autocrop.hip) ---- */
 
-static int rects_geometry(int64_t n, int h, int w, int channels, int64_t V) {
-    if (int rc = hvd::check_geometry(h, w, channels)) return rc;
-    if (n < 0 || V < 0 || V >= (1ll << 31) || n >= (1ll << 31)) return fail(HVD_ERR_ARG, "bad counts n=%lld V=%lld", (long long)n, (long long)V);
-    if (n > 0 && V == 0) return fail(HVD_ERR_ARG, "n=%lld frames in no video", (long long)n);
-    return HVD_OK;
-}
-
 int hvd_dev_content_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
                           int black_level, int min_bright, void* d_rects) {
-    if (int rc = need_ready()) return rc;
-    if (int rc = rects_geometry(n, h, w, channels, V)) return rc;
-    if (int rc = hvd::check_autocrop_levels(black_level, min_bright)) return rc;
-    if (V == 0) return HVD_OK;
-    if (!d_offsets || !d_rects || (n > 0 && !d_frames)) return fail(HVD_ERR_ARG, "NULL device pointer");
-    if ((uintptr_t)d_rects & 15u) return fail(HVD_ERR_ARG, "d_rects must be 16-byte aligned (hvd_dev_malloc's are)");
-    HIP_TRY(hvd::launch_content_rects((const uint8_t*)d_frames, n, h, w, channels, (const long long*)d_offsets, (uint32_t)V,
-                                      black_level, min_bright, (int32_t*)d_rects, g.stream));
-    return HVD_OK;
+    return hvd::api_content_rects({hvd::RectKind::Black, black_level, min_bright}, nullptr, d_frames, n, h, w, channels, d_offsets, V, d_rects);
 }
 
 int hvd_pdq_rects_scratch_bytes(int64_t n, int h, int w, int channels, size_t* out_bytes) {
@@ -951,32 +958,14 @@ int hvd_dev_bar_colors(const void* d_frames, int64_t n, int h, int w, int channe
 
 int hvd_dev_content_rects_color(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
                                 const void* d_colors, int bar_level, int min_bright, void* d_rects) {
-    if (int rc = need_ready()) return rc;
-    if (int rc = rects_geometry(n, h, w, channels, V)) return rc;
-    if (int rc = hvd::check_bar_level(bar_level)) return rc;
-    if (min_bright < 1) return fail(HVD_ERR_ARG, "min_bright=%d: need >= 1", min_bright);
-    if (V == 0) return HVD_OK;
-    if (!d_offsets || !d_rects || !d_colors || (n > 0 && !d_frames)) return fail(HVD_ERR_ARG, "NULL device pointer");
-    if ((uintptr_t)d_rects & 15u) return fail(HVD_ERR_ARG, "d_rects must be 16-byte aligned (hvd_dev_malloc's are)");
-    if ((uintptr_t)d_colors & 3u) return fail(HVD_ERR_ARG, "d_colors must be 4-byte aligned");
-    HIP_TRY(hvd::launch_content_rects_color((const uint8_t*)d_frames, n, h, w, channels, (const long long*)d_offsets, (uint32_t)V,
-                                            (const int32_t*)d_colors, bar_level, min_bright, (int32_t*)d_rects, g.stream));
-    return HVD_OK;
+    return hvd::api_content_rects({hvd::RectKind::Color, bar_level, min_bright}, d_colors, d_frames, n, h, w, channels, d_offsets, V, d_rects);
 }
 
 /* ---- detail content rectangle (k_detail.hip) ---- */
 
 int hvd_dev_content_rects_detail(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
                                  int detail_level, int min_detail, void* d_rects) {
-    if (int rc = need_ready()) return rc;
-    if (int rc = rects_geometry(n, h, w, channels, V)) return rc;
-    if (int rc = hvd::check_detail_levels(detail_level, min_detail)) return rc;
-    if (V == 0) return HVD_OK;
-    if (!d_offsets || !d_rects || (n > 0 && !d_frames)) return fail(HVD_ERR_ARG, "NULL device pointer");
-    if ((uintptr_t)d_rects & 15u) return fail(HVD_ERR_ARG, "d_rects must be 16-byte aligned (hvd_dev_malloc's are)");
-    HIP_TRY(hvd::launch_content_rects_detail((const uint8_t*)d_frames, n, h, w, channels, (const long long*)d_offsets, (uint32_t)V,
-                                             detail_level, min_detail, (int32_t*)d_rects, g.stream));
-    return HVD_OK;
+    return hvd::api_content_rects({hvd::RectKind::Detail, detail_level, min_detail}, nullptr, d_frames, n, h, w, channels, d_offsets, V, d_rects);
 }
 
 /* ---- crop-ladder PDQ (k_crops.hip) ---- */

@@ -21,6 +21,10 @@ hipError_t api_launch_hash(const void* d_frames, int64_t n, int h, int w, int ch
 // d_scratch: HashScratch(n, h, w, channels, true), 16-byte aligned.
 hipError_t api_launch_hash_rects(const void* d_frames, int64_t n, int h, int w, int channels, const void* d_offsets, int64_t V,
                                  const void* d_rects, void* d_scratch, void* d_hashes, void* d_quality, hipStream_t s);
+// hvd_dev_content_rects, _color and _detail: every check of theirs, then launch_content_rects on the library stream. d_colors:
+// the Color kind's int32[V], nullptr for the others.
+int api_content_rects(const RectRule& rule, const void* d_colors, const void* d_frames, int64_t n, int h, int w, int channels,
+                      const void* d_offsets, int64_t V, void* d_rects);
 
 /* ---- the frame geometry of a hashing call ---- */
 constexpr int kMinSide = 64, kMaxSide = 4096;
@@ -36,17 +40,15 @@ inline int check_geometry(int h, int w, int channels) {
     if (geometry_ok(h, w, channels)) return HVD_OK;
     return api_fail(HVD_ERR_ARG, "bad frame geometry h=%d w=%d channels=%d (need h,w in [64,4096], channels 1 or 3)", h, w, channels);
 }
-inline int check_autocrop_levels(int black_level, int min_bright) {
-    if (black_level < 0 || black_level > 254) return api_fail(HVD_ERR_ARG, "black_level=%d: need 0..254", black_level);
-    return min_bright >= 1 ? HVD_OK : api_fail(HVD_ERR_ARG, "min_bright=%d: need >= 1", min_bright);
+// a content-rectangle rule (hvd_kernels.h: RectRule), under the names its kind's entries give the level and the count
+inline int check_rect_rule(const RectRule& rule, bool with_count = true) {
+    static const char* const names[3][2] = {{"black_level", "min_bright"}, {"bar_level", "min_bright"}, {"detail_level", "min_detail"}};
+    const char* const* name = names[(int)rule.kind];
+    if (rule.level < 0 || rule.level > 254) return api_fail(HVD_ERR_ARG, "%s=%d: need 0..254", name[0], rule.level);
+    return !with_count || rule.count >= 1 ? HVD_OK : api_fail(HVD_ERR_ARG, "%s=%d: need >= 1", name[1], rule.count);
 }
-inline int check_bar_level(int bar_level) {
-    return bar_level >= 0 && bar_level <= 254 ? HVD_OK : api_fail(HVD_ERR_ARG, "bar_level=%d: need 0..254", bar_level);
-}
-inline int check_detail_levels(int detail_level, int min_detail) {
-    if (detail_level < 0 || detail_level > 254) return api_fail(HVD_ERR_ARG, "detail_level=%d: need 0..254", detail_level);
-    return min_detail >= 1 ? HVD_OK : api_fail(HVD_ERR_ARG, "min_detail=%d: need >= 1", min_detail);
-}
+// hvd_dev_bar_colors: the colour rule's level alone
+inline int check_bar_level(int bar_level) { return check_rect_rule({RectKind::Color, bar_level, 0}, false); }
 inline int check_dihedral_dct(bool dihedral) {  // the dihedral kernel has K1's strict arithmetic only
     if (!dihedral || g_pdq_dct_mode == 0) return HVD_OK;
     return api_fail(HVD_ERR_STATE, "dihedral hashing has no fma DCT mode: call hvd_set_pdq_dct_mode(0) first");

@@ -286,13 +286,30 @@ hipError_t launch_pdq_luma64_rgb(const uint8_t* d_frames, int64_t n, float* d_ou
 
 // Content-rectangle PDQ (k_autocrop.hip). d_offsets: the int64[V+1] CSR of the n frames; d_rects: int32[V][4]
 // {top, left, height, width}, also the kernels' accumulator (nothing else is allocated).
-hipError_t launch_content_rects(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
-                                uint32_t V, int black_level, int min_bright, int32_t* d_rects, hipStream_t s);
+// The rule that finds the rectangle: a row (column) is content iff it holds >= count of what the kind counts --
+//   Black   pixels with max(R, G, B) > level                                          (level = black_level, count = min_bright)
+//   Color   pixels with max_k |p_k - c_k| > level, c the video's colour in d_colors   (bar_level, min_bright)
+//   Detail  horizontal (vertical) neighbour pairs with max_k |p_k - p'_k| > level     (detail_level, min_detail)
+// d_colors: int32[V] = c0 | c1 << 8 | c2 << 16 for Color, unused (nullptr) otherwise.
+enum class RectKind { Black, Color, Detail };
+struct RectRule {
+    RectKind kind;
+    int level, count;
+};
+hipError_t launch_content_rects(const RectRule& rule, const int32_t* d_colors, const uint8_t* d_frames, int64_t n, int h, int w,
+                                int channels, const long long* d_offsets, uint32_t V, int32_t* d_rects, hipStream_t s);
 // ... and its three steps one by one (rectangle accumulators are folded batch by batch by the streaming hasher).
 hipError_t launch_rect_init(int32_t* d_rects, uint32_t V, hipStream_t s);
-hipError_t launch_rect_fold(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
-                            uint32_t V, int black_level, int min_bright, int32_t* d_rects, hipStream_t s);
+hipError_t launch_rect_fold(const RectRule& rule, const int32_t* d_colors, const uint8_t* d_frames, int64_t n, int h, int w,
+                            int channels, const long long* d_offsets, uint32_t V, int32_t* d_rects, hipStream_t s);
 hipError_t launch_rect_finish(int32_t* d_rects, uint32_t V, int h, int w, hipStream_t s);
+// what launch_rect_fold chooses from: the fold of one kind, in that kind's file (k_autocrop.hip, k_barcolor.hip, k_detail.hip)
+hipError_t rect_fold_black(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets, uint32_t V,
+                           int black_level, int min_bright, int32_t* d_rects, hipStream_t s);
+hipError_t rect_fold_color(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets, uint32_t V,
+                           const int32_t* d_colors, int bar_level, int min_bright, int32_t* d_rects, hipStream_t s);
+hipError_t rect_fold_detail(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets, uint32_t V,
+                            int detail_level, int min_detail, int32_t* d_rects, hipStream_t s);
 // The generic four-pass down-sampler inside every frame's video rectangle. d_geom: pdq_rects_geom_bytes(n) bytes (the
 // frame -> rectangle table); d_ws as for launch_pdq_downsample (sized for the full h x w).
 // Frames with h <= 512 and w <= 512 take the fused k_down_rect (one launch, same planes bit for bit) unless
@@ -308,23 +325,10 @@ hipError_t launch_pdq_downsample_rects(const uint8_t* d_frames, int64_t n, int h
 
 // Bar-colour content rectangle (k_barcolor.hip). d_colors: int32[V] = c0 | c1 << 8 | c2 << 16, the bar colour
 // of every video. launch_bar_colors finds it from the four corner pixels of every frame; d_acc: bar_colors_scratch_bytes(V)
-// bytes of accumulators. launch_content_rects_color is launch_content_rects with "content iff max_k |p_k - c_k| > bar_level"
-// as the pixel rule (rect init and finish are k_autocrop.hip's).
+// bytes of accumulators. The rectangles then come from launch_content_rects with a RectKind::Color rule.
 size_t bar_colors_scratch_bytes(uint32_t V);
 hipError_t launch_bar_colors(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
                              uint32_t V, int bar_level, int32_t* d_acc, int32_t* d_colors, hipStream_t s);
-hipError_t launch_content_rects_color(const uint8_t* d_frames, int64_t n, int h, int w, int channels,
-                                      const long long* d_offsets, uint32_t V, const int32_t* d_colors, int bar_level,
-                                      int min_bright, int32_t* d_rects, hipStream_t s);
-
-// Detail content rectangle (k_detail.hip): launch_content_rects with "row y is content iff it holds >= min_detail
-// horizontal neighbour differences above detail_level, column x iff it holds >= min_detail vertical ones" as the rule (rect
-// init and finish are k_autocrop.hip's). launch_rect_fold_detail is its middle step, the streaming hasher's per-batch fold.
-hipError_t launch_rect_fold_detail(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
-                                   uint32_t V, int detail_level, int min_detail, int32_t* d_rects, hipStream_t s);
-hipError_t launch_content_rects_detail(const uint8_t* d_frames, int64_t n, int h, int w, int channels,
-                                       const long long* d_offsets, uint32_t V, int detail_level, int min_detail,
-                                       int32_t* d_rects, hipStream_t s);
 
 // Crop-ladder PDQ (k_crops.hip). crops: HOST int32[K][4] {top, left, height, width}; crops_valid: 1 <= K <=
 // HVD_MAX_CROPS and every crop inside the h x w frame with both sides >= 64 -- the one definition of a sound list.

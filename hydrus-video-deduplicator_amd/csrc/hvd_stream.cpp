@@ -113,8 +113,7 @@ struct hvd_hasher {
     int64_t acquired_n = 0;        // ... and hvd_hasher_acquire_n this many frames of it
     // autocrop (hvd_hasher_create_autocrop)
     bool autocrop = false;
-    int black_level = 0, min_bright = 0;
-    bool detail = false;           // hvd_hasher_create_autocrop_detail: the fold is the detail rule, the two above its level and count
+    hvd::RectRule rule{};          // the rule of the fold: Black (hvd_hasher_create_autocrop) or Detail (.._autocrop_detail)
     int64_t max_frames = 0;        // frames one video may retain (max_retained_bytes / frame_bytes)
     int64_t taken = 0;             // frames committed since the last finish
     bool rect_closed = false;      // k_rect_finish has turned the accumulators into the rectangle (it must run once)
@@ -201,8 +200,7 @@ static int submit_retain(hvd_hasher* hs, Slot& s) {
     Block& b = hs->store.back();
     uint8_t* dst = b.d + hs->frame_bytes * (size_t)b.used;
     S_TRY(hipMemcpyAsync(dst, s.h_frames, hs->frame_bytes * (size_t)m, hipMemcpyHostToDevice, s.stream));
-    S_TRY((hs->detail ? hvd::launch_rect_fold_detail : hvd::launch_rect_fold)(dst, m, hs->h, hs->w, hs->channels, hs->d_offsets(), 1,
-                                                                              hs->black_level, hs->min_bright, hs->d_rect(), s.stream));
+    S_TRY(hvd::launch_rect_fold(hs->rule, nullptr, dst, m, hs->h, hs->w, hs->channels, hs->d_offsets(), 1, hs->d_rect(), s.stream));
     S_TRY(hipEventRecord(s.done, s.stream));
     b.used += m;
     s.in_flight = m;
@@ -332,9 +330,8 @@ int hvd_hasher_destroy(hvd_hasher* hs) {
 }  // extern "C"
 
 struct AutocropArgs {
-    int black_level, min_bright;
+    hvd::RectRule rule;
     int64_t max_retained_bytes;
-    bool detail;  // black_level / min_bright are detail_level / min_detail
 };
 
 static int create_hasher(int width, int height, int channels, int64_t batch_frames, bool dihedral, hvd_hasher** out,
@@ -345,17 +342,12 @@ static int create_hasher(int width, int height, int channels, int64_t batch_fram
     if (int rc = hvd::check_geometry(height, width, channels)) return rc;
     if (batch_frames < 1) return hvd::api_fail(HVD_ERR_ARG, "bad hasher batch of %lld frames", (long long)batch_frames);
     if (int rc = hvd::check_dihedral_dct(dihedral)) return rc;
-    if (int rc = !ac ? HVD_OK
-                 : ac->detail ? hvd::check_detail_levels(ac->black_level, ac->min_bright)
-                              : hvd::check_autocrop_levels(ac->black_level, ac->min_bright))
-        return rc;
+    if (int rc = ac ? hvd::check_rect_rule(ac->rule) : HVD_OK) return rc;
     const int64_t max_frames =
         !ac ? 0 : (ac->max_retained_bytes > 0 ? ac->max_retained_bytes : kDefaultRetained) / ((int64_t)width * height * channels);
     const auto set_autocrop = [&](hvd_hasher* p) {
         if (!ac) return;
-        p->black_level = ac->black_level;
-        p->min_bright = ac->min_bright;
-        p->detail = ac->detail;
+        p->rule = ac->rule;
         p->max_frames = max_frames;
     };
     {
@@ -419,13 +411,13 @@ extern "C" {
 
 int hvd_hasher_create_autocrop(int width, int height, int channels, int64_t batch_frames, int black_level, int min_bright,
                                int64_t max_retained_bytes, hvd_hasher** out) {
-    const AutocropArgs ac{black_level, min_bright, max_retained_bytes, false};
+    const AutocropArgs ac{{hvd::RectKind::Black, black_level, min_bright}, max_retained_bytes};
     return create_hasher(width, height, channels, batch_frames, false, out, &ac);
 }
 
 int hvd_hasher_create_autocrop_detail(int width, int height, int channels, int64_t batch_frames, int detail_level, int min_detail,
                                       int64_t max_retained_bytes, hvd_hasher** out) {
-    const AutocropArgs ac{detail_level, min_detail, max_retained_bytes, true};
+    const AutocropArgs ac{{hvd::RectKind::Detail, detail_level, min_detail}, max_retained_bytes};
     return create_hasher(width, height, channels, batch_frames, false, out, &ac);
 }
 

@@ -15,27 +15,19 @@
 //   k_luma64_rect      the plane of a 64 x 64 rectangle: the crop's luma, unfiltered
 // Frames up to 512 x 512 take the same four passes fused into one launch instead: k_down_rect, k_autocrop_fused.hip.
 // Luma and the line pass are hvd_pdq_dev.h's, the one home of the bit-exactness contract.
+// init -> fold -> finish is written here for every rule (launch_content_rects, launch_rect_fold: the one switch over
+// RectRule::kind); what the three rules' folds share is hvd_content_rect_dev.h.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 
+#include "hvd_content_rect_dev.h"
 #include "hvd_kernels.h"
 #include "hvd_pdq_dev.h"
 
 namespace hvd {
 
 namespace {
-
-// the video that holds frame f: the last v with offsets[v] <= f (videos without frames are skipped); always in [0, V)
-__device__ __forceinline__ int video_of_frame(const long long* __restrict__ offsets, int V, long long f) {
-    int lo = 0, hi = V;  // offsets[lo] <= f < offsets[hi] by the CSR's contract
-    while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (offsets[mid] <= f) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(256) void k_rect_init(int32_t* __restrict__ rects, int V) {
     const int v = blockIdx.x * 256 + threadIdx.x;
@@ -52,108 +44,24 @@ __global__ __launch_bounds__(256) void k_rect_finish(int32_t* __restrict__ rects
     reinterpret_cast<int4*>(rects)[v] = make_int4(top, left, hh, ww);
 }
 
-constexpr int kUnit = 16;  // pixels a lane takes from a row: 16 B of gray, 48 B of RGB24 = whole 16-byte loads
+// max(R, G, B) > level
+struct BrightPred {
+    uint32_t level;
+    __device__ __forceinline__ bool gray(uint32_t p) const { return p > level; }
+    __device__ __forceinline__ bool rgb(uint32_t a, uint32_t b, uint32_t c) const { return max(max(a, b), c) > level; }
+};
 
-// Bright pixels per row and per column of one frame, one workgroup of 256 lanes per frame. The lanes form R = 256 / P rows of
-// P = pow2 >= ceil(w / 16) lanes; lane (r, u) reads pixels [16u, 16u + 16) of rows r, r + R, ... and keeps the 16 column counts
-// of its unit in registers for the whole frame. A row's count is a segmented wave reduction (P <= 64: the row lies inside one
-// wave) folded into LDS; the column counts are folded into LDS once per frame.
-// WIDE: w % 16 == 0 and the frame base is 16-byte aligned, so every unit is CH aligned 16-byte loads (the geometries users
-// have: 64, 512, 640, 1920, ...); otherwise byte loads (any width, any alignment).
-// LDS: int rowcnt[h], colcnt[w] (dynamic), 4 words of box.
+// Bright pixels per row and per column of one frame, one workgroup of 256 lanes per frame: content_rect_fold
+// (hvd_content_rect_dev.h) under the bright predicate. The frame's video is looked up by the one lane that merges the box.
 template <int CH, bool WIDE>
 __global__ __launch_bounds__(256) void k_content_rect(const uint8_t* __restrict__ frames, int h, int w,
                                                       const long long* __restrict__ offsets, int V, int black_level,
                                                       int min_bright, int32_t* __restrict__ boxes) {
     extern __shared__ int lds[];
-    int* rowcnt = lds;
-    int* colcnt = lds + h;
     __shared__ int box[4];
-    const int tid = threadIdx.x;
     const long long frame = blockIdx.x;
-    const uint8_t* src = frames + (size_t)frame * h * w * CH;
-    const uint32_t level = (uint32_t)black_level;
-
-    for (int i = tid; i < h + w; i += 256) lds[i] = 0;
-    if (tid == 0) { box[0] = INT_MAX; box[1] = -1; box[2] = INT_MAX; box[3] = -1; }
-    __syncthreads();
-
-    const int units = (w + kUnit - 1) / kUnit;
-    int P = 1;
-    while (P < units) P <<= 1;  // <= 256 (w <= 4096)
-    const int R = 256 / P;
-    const int u = tid & (P - 1), r0 = tid / P;
-    const int x0 = u * kUnit;
-    const bool live = u < units;
-
-    int cnt[kUnit];
-#pragma unroll
-    for (int p = 0; p < kUnit; ++p) cnt[p] = 0;
-
-    for (int yb = 0; yb < h; yb += R) {
-        const int y = yb + r0;
-        int rc = 0;
-        if (live && y < h) {
-            const uint8_t* row = src + ((size_t)y * w + x0) * CH;
-            if (WIDE) {
-                uint32_t q[4 * CH];
-#pragma unroll
-                for (int c = 0; c < CH; ++c) {
-                    const uint4 t = reinterpret_cast<const uint4*>(row)[c];
-                    q[4 * c] = t.x; q[4 * c + 1] = t.y; q[4 * c + 2] = t.z; q[4 * c + 3] = t.w;
-                }
-#pragma unroll
-                for (int p = 0; p < kUnit; ++p) {
-                    bool b;
-                    if (CH == 1) {
-                        b = byte_of(q[p >> 2], p & 3) > level;
-                    } else {
-                        const int e = 3 * p;
-                        b = max(max(byte_of(q[e >> 2], e & 3), byte_of(q[(e + 1) >> 2], (e + 1) & 3)),
-                                byte_of(q[(e + 2) >> 2], (e + 2) & 3)) > level;
-                    }
-                    cnt[p] += b ? 1 : 0;
-                    rc += b ? 1 : 0;
-                }
-            } else {
-#pragma unroll
-                for (int p = 0; p < kUnit; ++p) {
-                    bool b = false;
-                    if (x0 + p < w) {
-                        if (CH == 1) b = (uint32_t)row[p] > level;
-                        else b = max(max((uint32_t)row[3 * p], (uint32_t)row[3 * p + 1]), (uint32_t)row[3 * p + 2]) > level;
-                    }
-                    cnt[p] += b ? 1 : 0;
-                    rc += b ? 1 : 0;
-                }
-            }
-        }
-        // the row's count: lanes of one row are P consecutive lanes (a segment of the wave, or whole waves)
-        for (int m = (P < 64 ? P : 64) >> 1; m > 0; m >>= 1) rc += __shfl_xor(rc, m);
-        if ((tid & ((P < 64 ? P : 64) - 1)) == 0 && y < h && rc) atomicAdd(&rowcnt[y], rc);
-    }
-    if (live) {
-#pragma unroll
-        for (int p = 0; p < kUnit; ++p)
-            if (cnt[p] && x0 + p < w) atomicAdd(&colcnt[x0 + p], cnt[p]);
-    }
-    __syncthreads();
-
-    int top = INT_MAX, bot = -1, left = INT_MAX, right = -1;
-    for (int y = tid; y < h; y += 256)
-        if (rowcnt[y] >= min_bright) { top = min(top, y); bot = max(bot, y); }
-    for (int x = tid; x < w; x += 256)
-        if (colcnt[x] >= min_bright) { left = min(left, x); right = max(right, x); }
-    if (bot >= 0) { atomicMin(&box[0], top); atomicMax(&box[1], bot); }
-    if (right >= 0) { atomicMin(&box[2], left); atomicMax(&box[3], right); }
-    __syncthreads();
-    if (tid == 0 && box[1] >= 0 && box[3] >= 0) {
-        int32_t* vb = boxes + 4 * (size_t)video_of_frame(offsets, V, frame);
-        atomicMin(&vb[0], box[0]);
-        atomicMax(&vb[1], box[1]);
-        atomicMin(&vb[2], box[2]);
-        atomicMax(&vb[3], box[3]);
-    }
+    content_rect_fold<CH, WIDE>(frames + (size_t)frame * h * w * CH, h, w, BrightPred{(uint32_t)black_level}, min_bright, lds, box,
+                                boxes, [&] { return video_of_frame(offsets, V, frame); });
 }
 
 // frame -> {top, left, height, width} of its video. A record that does not lie inside the frame or is shorter than 64 on an
@@ -211,11 +119,12 @@ __global__ __launch_bounds__(256) void k_luma64_rect(const uint8_t* __restrict__
 
 bool g_pdq_fused_rect = true;  // A/B switch (hvd_debug_set "pdq_fused_rect"): 0 forces the four generic passes
 
-hipError_t launch_content_rects(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
-                                uint32_t V, int black_level, int min_bright, int32_t* d_rects, hipStream_t s) {
+// init -> the rule's fold -> finish
+hipError_t launch_content_rects(const RectRule& rule, const int32_t* d_colors, const uint8_t* d_frames, int64_t n, int h, int w,
+                                int channels, const long long* d_offsets, uint32_t V, int32_t* d_rects, hipStream_t s) {
     if (V == 0) return hipSuccess;
     hipError_t e = launch_rect_init(d_rects, V, s);
-    if (e == hipSuccess) e = launch_rect_fold(d_frames, n, h, w, channels, d_offsets, V, black_level, min_bright, d_rects, s);
+    if (e == hipSuccess) e = launch_rect_fold(rule, d_colors, d_frames, n, h, w, channels, d_offsets, V, d_rects, s);
     if (e == hipSuccess) e = launch_rect_finish(d_rects, V, h, w, s);
     return e;
 }
@@ -227,23 +136,22 @@ hipError_t launch_rect_init(int32_t* d_rects, uint32_t V, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_rect_fold(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
-                            uint32_t V, int black_level, int min_bright, int32_t* d_rects, hipStream_t s) {
-    // 64 x 64 frames: no box can be smaller than the frame and at least 64 long, so every rectangle is the full frame
-    if (n <= 0 || (h == 64 && w == 64)) return hipSuccess;
-    const size_t lds = sizeof(int) * (size_t)(h + w);
-    const bool wide = (w % kUnit) == 0 && ((uintptr_t)d_frames & 15u) == 0;
-    const dim3 gf((unsigned)n);
-#define HVD_CR(CH, WIDE) hipLaunchKernelGGL((k_content_rect<CH, WIDE>), gf, dim3(256), lds, s, d_frames, h, w, d_offsets, (int)V, black_level, min_bright, d_rects)
-    if (channels == 3) {
-        if (wide) HVD_CR(3, true);
-        else HVD_CR(3, false);
-    } else {
-        if (wide) HVD_CR(1, true);
-        else HVD_CR(1, false);
+hipError_t launch_rect_fold(const RectRule& rule, const int32_t* d_colors, const uint8_t* d_frames, int64_t n, int h, int w,
+                            int channels, const long long* d_offsets, uint32_t V, int32_t* d_rects, hipStream_t s) {
+    switch (rule.kind) {
+        case RectKind::Black: return rect_fold_black(d_frames, n, h, w, channels, d_offsets, V, rule.level, rule.count, d_rects, s);
+        case RectKind::Color: return rect_fold_color(d_frames, n, h, w, channels, d_offsets, V, d_colors, rule.level, rule.count, d_rects, s);
+        case RectKind::Detail: return rect_fold_detail(d_frames, n, h, w, channels, d_offsets, V, rule.level, rule.count, d_rects, s);
     }
-#undef HVD_CR
-    return hipGetLastError();
+    return hipErrorInvalidValue;
+}
+
+hipError_t rect_fold_black(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets, uint32_t V,
+                           int black_level, int min_bright, int32_t* d_rects, hipStream_t s) {
+    return rect_fold_dispatch(d_frames, n, h, w, channels, [&](auto ch, auto wide, dim3 grid, size_t lds) {
+        hipLaunchKernelGGL((k_content_rect<decltype(ch)::value, decltype(wide)::value>), grid, dim3(256), lds, s, d_frames, h, w,
+                           d_offsets, (int)V, black_level, min_bright, d_rects);
+    });
 }
 
 hipError_t launch_rect_finish(int32_t* d_rects, uint32_t V, int h, int w, hipStream_t s) {

@@ -12,29 +12,18 @@
 //   k_corner_finish         the rule above -> the packed colour
 //   k_content_rect_color    k_content_rect's pass (k_autocrop.hip) under the colour predicate
 // The rectangle accumulators are initialised and closed by k_autocrop.hip's k_rect_init / k_rect_finish, and everything
-// behind the rectangle is shared as it is. The pass is written out here and not shared with k_content_rect: moving that
-// kernel's body into a header changed its instruction stream.
+// behind the rectangle is shared as it is. The pass itself is hvd_content_rect_dev.h's content_rect_fold, the one body of
+// k_content_rect and k_content_rect_color.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 
+#include "hvd_content_rect_dev.h"
 #include "hvd_kernels.h"
-#include "hvd_pdq_dev.h"
 
 namespace hvd {
 
 namespace {
-
-// the video that holds frame f: the last v with offsets[v] <= f (videos without frames are skipped); always in [0, V)
-__device__ __forceinline__ int video_of_frame(const long long* __restrict__ offsets, int V, long long f) {
-    int lo = 0, hi = V;  // offsets[lo] <= f < offsets[hi] by the CSR's contract
-    while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (offsets[mid] <= f) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
 
 constexpr int kAcc = 8;  // int32 words of corner accumulator per video: lo[3], hi[3], 2 unused (one 32-byte record)
 
@@ -85,8 +74,6 @@ __global__ __launch_bounds__(256) void k_corner_finish(const int32_t* __restrict
     colors[v] = uniform ? c : 0;
 }
 
-constexpr int kUnit = 16;  // pixels a lane takes from a row: 16 B of gray, 48 B of RGB24 = whole 16-byte loads
-
 // |p_k - c_k| > L on any channel, as one subtract and one unsigned compare per channel: with lo'_k = max(0, c_k - L) and
 // span_k = min(255, c_k + L) - lo'_k, a byte p lies in [lo'_k, lo'_k + span_k] iff (uint32)(p - lo'_k) <= span_k (below lo'_k
 // the difference wraps to >= 2^32 - 255), and inside [0, 255] that interval is exactly |p - c_k| <= L.
@@ -107,128 +94,20 @@ struct ColorPred {
     }
 };
 
-// Content pixels per row and per column of one frame, one workgroup of 256 lanes per frame: k_content_rect's decomposition
-// (k_autocrop.hip). The lanes form R = 256 / P rows of P = pow2 >= ceil(w / 16) lanes; lane (r, u) reads pixels
-// [16u, 16u + 16) of rows r, r + R, ... and keeps the 16 column counts of its unit in registers for the whole frame. A row's
-// count is a segmented wave reduction (P <= 64: the row lies inside one wave) folded into LDS; the column counts are folded
-// into LDS once per frame. The workgroup looks up its video and that video's colour once; lo' and span are wave-uniform.
-// WIDE: w % 16 == 0 and the frame base is 16-byte aligned, so every unit is CH aligned 16-byte loads; otherwise byte loads.
-// LDS: int rowcnt[h], colcnt[w] (dynamic), 4 words of box.
+// Content pixels per row and per column of one frame, one workgroup of 256 lanes per frame: content_rect_fold
+// (hvd_content_rect_dev.h) under the colour predicate. The workgroup looks up its video and that video's colour once, before
+// the fold; lo' and span are wave-uniform.
 template <int CH, bool WIDE>
 __global__ __launch_bounds__(256) void k_content_rect_color(const uint8_t* __restrict__ frames, int h, int w,
                                                             const long long* __restrict__ offsets, int V,
                                                             const int32_t* __restrict__ colors, int bar_level,
                                                             int min_bright, int32_t* __restrict__ boxes) {
     extern __shared__ int lds[];
-    int* rowcnt = lds;
-    int* colcnt = lds + h;
     __shared__ int box[4];
-    const int tid = threadIdx.x;
     const long long frame = blockIdx.x;
-    const uint8_t* src = frames + (size_t)frame * h * w * CH;
     const int video = video_of_frame(offsets, V, frame);
     const ColorPred pred(colors[video], bar_level);
-
-    for (int i = tid; i < h + w; i += 256) lds[i] = 0;
-    if (tid == 0) { box[0] = INT_MAX; box[1] = -1; box[2] = INT_MAX; box[3] = -1; }
-    __syncthreads();
-
-    const int units = (w + kUnit - 1) / kUnit;
-    int P = 1;
-    while (P < units) P <<= 1;  // <= 256 (w <= 4096)
-    const int R = 256 / P;
-    const int u = tid & (P - 1), r0 = tid / P;
-    const int x0 = u * kUnit;
-    const bool live = u < units;
-
-    int cnt[kUnit];
-#pragma unroll
-    for (int p = 0; p < kUnit; ++p) cnt[p] = 0;
-
-    for (int yb = 0; yb < h; yb += R) {
-        const int y = yb + r0;
-        int rc = 0;
-        if (live && y < h) {
-            const uint8_t* row = src + ((size_t)y * w + x0) * CH;
-            if (WIDE) {
-                uint32_t q[4 * CH];
-#pragma unroll
-                for (int c = 0; c < CH; ++c) {
-                    const uint4 t = reinterpret_cast<const uint4*>(row)[c];
-                    q[4 * c] = t.x; q[4 * c + 1] = t.y; q[4 * c + 2] = t.z; q[4 * c + 3] = t.w;
-                }
-#pragma unroll
-                for (int p = 0; p < kUnit; ++p) {
-                    bool b;
-                    if (CH == 1) {
-                        b = pred.gray(byte_of(q[p >> 2], p & 3));
-                    } else {
-                        const int e = 3 * p;
-                        b = pred.rgb(byte_of(q[e >> 2], e & 3), byte_of(q[(e + 1) >> 2], (e + 1) & 3),
-                                     byte_of(q[(e + 2) >> 2], (e + 2) & 3));
-                    }
-                    cnt[p] += b ? 1 : 0;
-                    rc += b ? 1 : 0;
-                }
-            } else {
-#pragma unroll
-                for (int p = 0; p < kUnit; ++p) {
-                    bool b = false;
-                    if (x0 + p < w) {
-                        if (CH == 1) b = pred.gray((uint32_t)row[p]);
-                        else b = pred.rgb((uint32_t)row[3 * p], (uint32_t)row[3 * p + 1], (uint32_t)row[3 * p + 2]);
-                    }
-                    cnt[p] += b ? 1 : 0;
-                    rc += b ? 1 : 0;
-                }
-            }
-        }
-        // the row's count: lanes of one row are P consecutive lanes (a segment of the wave, or whole waves)
-        for (int m = (P < 64 ? P : 64) >> 1; m > 0; m >>= 1) rc += __shfl_xor(rc, m);
-        if ((tid & ((P < 64 ? P : 64) - 1)) == 0 && y < h && rc) atomicAdd(&rowcnt[y], rc);
-    }
-    if (live) {
-#pragma unroll
-        for (int p = 0; p < kUnit; ++p)
-            if (cnt[p] && x0 + p < w) atomicAdd(&colcnt[x0 + p], cnt[p]);
-    }
-    __syncthreads();
-
-    int top = INT_MAX, bot = -1, left = INT_MAX, right = -1;
-    for (int y = tid; y < h; y += 256)
-        if (rowcnt[y] >= min_bright) { top = min(top, y); bot = max(bot, y); }
-    for (int x = tid; x < w; x += 256)
-        if (colcnt[x] >= min_bright) { left = min(left, x); right = max(right, x); }
-    if (bot >= 0) { atomicMin(&box[0], top); atomicMax(&box[1], bot); }
-    if (right >= 0) { atomicMin(&box[2], left); atomicMax(&box[3], right); }
-    __syncthreads();
-    if (tid == 0 && box[1] >= 0 && box[3] >= 0) {
-        int32_t* vb = boxes + 4 * (size_t)video;
-        atomicMin(&vb[0], box[0]);
-        atomicMax(&vb[1], box[1]);
-        atomicMin(&vb[2], box[2]);
-        atomicMax(&vb[3], box[3]);
-    }
-}
-
-// the middle step of launch_content_rects_color, between k_autocrop.hip's rect init and finish
-hipError_t rect_fold_color(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets, uint32_t V,
-                           const int32_t* d_colors, int bar_level, int min_bright, int32_t* d_rects, hipStream_t s) {
-    // 64 x 64 frames: no box can be smaller than the frame and at least 64 long, so every rectangle is the full frame
-    if (n <= 0 || (h == 64 && w == 64)) return hipSuccess;
-    const size_t lds = sizeof(int) * (size_t)(h + w);
-    const bool wide = (w % kUnit) == 0 && ((uintptr_t)d_frames & 15u) == 0;
-    const dim3 gf((unsigned)n);
-#define HVD_CRC(CH, WIDE) hipLaunchKernelGGL((k_content_rect_color<CH, WIDE>), gf, dim3(256), lds, s, d_frames, h, w, d_offsets, (int)V, d_colors, bar_level, min_bright, d_rects)
-    if (channels == 3) {
-        if (wide) HVD_CRC(3, true);
-        else HVD_CRC(3, false);
-    } else {
-        if (wide) HVD_CRC(1, true);
-        else HVD_CRC(1, false);
-    }
-#undef HVD_CRC
-    return hipGetLastError();
+    content_rect_fold<CH, WIDE>(frames + (size_t)frame * h * w * CH, h, w, pred, min_bright, lds, box, boxes, [&] { return video; });
 }
 
 }  // namespace
@@ -250,15 +129,13 @@ hipError_t launch_bar_colors(const uint8_t* d_frames, int64_t n, int h, int w, i
     return hipGetLastError();
 }
 
-hipError_t launch_content_rects_color(const uint8_t* d_frames, int64_t n, int h, int w, int channels,
-                                      const long long* d_offsets, uint32_t V, const int32_t* d_colors, int bar_level,
-                                      int min_bright, int32_t* d_rects, hipStream_t s) {
-    if (V == 0) return hipSuccess;
-    hipError_t e = launch_rect_init(d_rects, V, s);
-    if (e == hipSuccess)
-        e = rect_fold_color(d_frames, n, h, w, channels, d_offsets, V, d_colors, bar_level, min_bright, d_rects, s);
-    if (e == hipSuccess) e = launch_rect_finish(d_rects, V, h, w, s);
-    return e;
+// the colour rule's fold (launch_rect_fold, k_autocrop.hip)
+hipError_t rect_fold_color(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets, uint32_t V,
+                           const int32_t* d_colors, int bar_level, int min_bright, int32_t* d_rects, hipStream_t s) {
+    return rect_fold_dispatch(d_frames, n, h, w, channels, [&](auto ch, auto wide, dim3 grid, size_t lds) {
+        hipLaunchKernelGGL((k_content_rect_color<decltype(ch)::value, decltype(wide)::value>), grid, dim3(256), lds, s, d_frames, h,
+                           w, d_offsets, (int)V, d_colors, bar_level, min_bright, d_rects);
+    });
 }
 
 }  // namespace hvd

@@ -9,30 +9,18 @@
 //
 //   k_content_rect_detail   one workgroup per frame: dh counts per row, dv counts per column, frame box -> atomicMin / atomicMax
 // The rectangle accumulators are initialised and closed by k_autocrop.hip's k_rect_init / k_rect_finish, and everything
-// behind the rectangle is shared as it is. k_autocrop.hip and k_barcolor.hip are not touched.
+// behind the rectangle is shared as it is. The lane layout, the count folds and the closing step are
+// hvd_content_rect_dev.h's, shared with the other two rules' fold; the band walk and the pixel pairs are this file's.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
 
+#include "hvd_content_rect_dev.h"
 #include "hvd_kernels.h"
-#include "hvd_pdq_dev.h"
 
 namespace hvd {
 
 namespace {
-
-// the video that holds frame f: the last v with offsets[v] <= f (videos without frames are skipped); always in [0, V)
-__device__ __forceinline__ int video_of_frame(const long long* __restrict__ offsets, int V, long long f) {
-    int lo = 0, hi = V;  // offsets[lo] <= f < offsets[hi] by the CSR's contract
-    while (hi - lo > 1) {
-        const int mid = lo + (hi - lo) / 2;
-        if (offsets[mid] <= f) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
-constexpr int kUnit = 16;  // pixels a lane takes from a row: 16 B of gray, 48 B of RGB24 = whole 16-byte loads
 
 // |a - b| of two bytes held in 32-bit registers: one v_sad_u32
 __device__ __forceinline__ uint32_t absdiff(uint32_t a, uint32_t b) { return __usad(a, b, 0u); }
@@ -101,24 +89,18 @@ __global__ __launch_bounds__(256) void k_content_rect_detail(const uint8_t* __re
     const long long frame = blockIdx.x;
     const uint8_t* src = frames + (size_t)frame * h * w * CH;
     const uint32_t level = (uint32_t)detail_level;
+    rect_counts_clear(lds, box, h, w, tid);
 
-    for (int i = tid; i < h + w; i += 256) lds[i] = 0;
-    if (tid == 0) { box[0] = INT_MAX; box[1] = -1; box[2] = INT_MAX; box[3] = -1; }
-    __syncthreads();
-
-    const int units = (w + kUnit - 1) / kUnit;
-    int P = 1;
-    while (P < units) P <<= 1;  // <= 256 (w <= 4096)
-    const int lg = __ffs(P) - 1;      // P = 1 << lg: shifts, no division
+    const RectLanes L(w, tid);
+    const int lg = __ffs(L.P) - 1;    // P = 1 << lg: shifts, no division
     const int R = 256 >> lg;
     const int B = (h + R - 1) >> (8 - lg);
-    const int u = tid & (P - 1), r0 = tid >> lg;
-    const int x0 = u * kUnit;
-    const bool live = u < units;
+    const int r0 = tid >> lg;
+    const int x0 = L.x0;
+    const bool live = L.live;
     const int npix = w - x0;                   // pixels of a row from the unit's first on (live: > 0)
     const bool more = x0 + kUnit < w;          // pixel x0 + 16 exists
     const bool edge = more && (tid & 63) == 63;  // ... in another wave
-    const int seg = P < 64 ? P : 64;
 
     int cnt[kUnit];
 #pragma unroll
@@ -156,65 +138,22 @@ __global__ __launch_bounds__(256) void k_content_rect_detail(const uint8_t* __re
             bool bv = differs<CH>(cur, p, nxt, p, level);
             cnt[p] += bv ? 1 : 0;
         }
-        // the row's count: lanes of one row are P consecutive lanes (a segment of the wave, or whole waves)
-        for (int m = seg >> 1; m > 0; m >>= 1) rc += __shfl_xor(rc, m);
-        if ((tid & (seg - 1)) == 0 && y < h && rc) atomicAdd(&rowcnt[y], rc);
+        rect_fold_row(rowcnt, L, tid, y, h, rc);
         cur = nxt;
     }
-    if (live) {
-#pragma unroll
-        for (int p = 0; p < kUnit; ++p)
-            if (cnt[p] && x0 + p < w) atomicAdd(&colcnt[x0 + p], cnt[p]);
-    }
-    __syncthreads();
-
-    int top = INT_MAX, bot = -1, left = INT_MAX, right = -1;
-    for (int y = tid; y < h; y += 256)
-        if (rowcnt[y] >= min_detail) { top = min(top, y); bot = max(bot, y); }
-    for (int x = tid; x < w; x += 256)
-        if (colcnt[x] >= min_detail) { left = min(left, x); right = max(right, x); }
-    if (bot >= 0) { atomicMin(&box[0], top); atomicMax(&box[1], bot); }
-    if (right >= 0) { atomicMin(&box[2], left); atomicMax(&box[3], right); }
-    __syncthreads();
-    if (tid == 0 && box[1] >= 0 && box[3] >= 0) {
-        int32_t* vb = boxes + 4 * (size_t)video_of_frame(offsets, V, frame);
-        atomicMin(&vb[0], box[0]);
-        atomicMax(&vb[1], box[1]);
-        atomicMin(&vb[2], box[2]);
-        atomicMax(&vb[3], box[3]);
-    }
+    rect_fold_columns(colcnt, L, w, cnt);
+    rect_close(rowcnt, colcnt, box, h, w, tid, min_detail, boxes, [&] { return video_of_frame(offsets, V, frame); });
 }
 
 }  // namespace
 
-// the middle step of launch_content_rects_detail, between k_autocrop.hip's rect init and finish; the streaming hasher's fold
-hipError_t launch_rect_fold_detail(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets,
-                                   uint32_t V, int detail_level, int min_detail, int32_t* d_rects, hipStream_t s) {
-    // 64 x 64 frames: no box can be smaller than the frame and at least 64 long, so every rectangle is the full frame
-    if (n <= 0 || (h == 64 && w == 64)) return hipSuccess;
-    const size_t lds = sizeof(int) * (size_t)(h + w);
-    const bool wide = (w % kUnit) == 0 && ((uintptr_t)d_frames & 15u) == 0;
-    const dim3 gf((unsigned)n);
-#define HVD_CRD(CH, WIDE) hipLaunchKernelGGL((k_content_rect_detail<CH, WIDE>), gf, dim3(256), lds, s, d_frames, h, w, d_offsets, (int)V, detail_level, min_detail, d_rects)
-    if (channels == 3) {
-        if (wide) HVD_CRD(3, true);
-        else HVD_CRD(3, false);
-    } else {
-        if (wide) HVD_CRD(1, true);
-        else HVD_CRD(1, false);
-    }
-#undef HVD_CRD
-    return hipGetLastError();
-}
-
-hipError_t launch_content_rects_detail(const uint8_t* d_frames, int64_t n, int h, int w, int channels,
-                                       const long long* d_offsets, uint32_t V, int detail_level, int min_detail,
-                                       int32_t* d_rects, hipStream_t s) {
-    if (V == 0) return hipSuccess;
-    hipError_t e = launch_rect_init(d_rects, V, s);
-    if (e == hipSuccess) e = launch_rect_fold_detail(d_frames, n, h, w, channels, d_offsets, V, detail_level, min_detail, d_rects, s);
-    if (e == hipSuccess) e = launch_rect_finish(d_rects, V, h, w, s);
-    return e;
+// the detail rule's fold (launch_rect_fold, k_autocrop.hip)
+hipError_t rect_fold_detail(const uint8_t* d_frames, int64_t n, int h, int w, int channels, const long long* d_offsets, uint32_t V,
+                            int detail_level, int min_detail, int32_t* d_rects, hipStream_t s) {
+    return rect_fold_dispatch(d_frames, n, h, w, channels, [&](auto ch, auto wide, dim3 grid, size_t lds) {
+        hipLaunchKernelGGL((k_content_rect_detail<decltype(ch)::value, decltype(wide)::value>), grid, dim3(256), lds, s, d_frames, h,
+                           w, d_offsets, (int)V, detail_level, min_detail, d_rects);
+    });
 }
 
 }  // namespace hvd

@@ -48,7 +48,7 @@ def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
         return [vpdq.VpdqHash(b"") for _ in videos]
     flat = np.concatenate([v for v in videos if v.shape[0]], axis=0)
     if crop is not None:
-        hashes, quality, _ = vpdq.hash_frames_autocrop(flat, np.concatenate([[0], np.cumsum(lengths)]), **vpdq.rule_kwargs(crop))
+        hashes, quality, _ = vpdq.hash_frames_autocrop(flat, np.concatenate([[0], np.cumsum(lengths)]), **crop.kwargs())
     else:
         hashes, quality = vpdq.hash_frames(flat)
     out, pos = [], 0
@@ -154,38 +154,17 @@ def hash_frames_autocrop_on_device(d_frames_ptr: int, n: int, h: int, w: int, ch
     "rects_ms"); black_level then stays at its default.
     detail=True with detail_level / min_detail (defaults 8 and 8, unverified): the rectangles leave out smooth bars of any
     colour (hvd_dev_content_rects_detail in "rects_ms"); the other rules' keywords then stay at their defaults."""
-    levels = vpdq._detail_rule_args(detail, detail_level, min_detail, vpdq._other_rules(black_level, min_bright, bar_color, bar_level))
+    rule = vpdq.rect_rule(black_level, min_bright, bar_color, bar_level, detail, detail_level, min_detail)
     lib = _lib.ensure()
     offsets = _check_raw_offsets(offsets, n)
     V = offsets.size - 1
     run = timed if timed is not None else (lambda key, fn: fn())
-    if bar_color is None and bar_level is not None:
-        raise ValueError("bar_level needs bar_color (the black rule's level is black_level)")
-    if bar_color is not None:
-        level, bright = vpdq._bar_rule_args(black_level, min_bright, bar_color, bar_level)
-        packed = vpdq._pack_bar_color(bar_color, V, channels)
+    packed = vpdq._pack_bar_color(rule.colour, V, channels) if rule.kind == "color" else None
     with _DeviceScope() as scope:
         d_off = scope.keep(DeviceBuffer.from_array(offsets))
         d_r = scope.keep(DeviceBuffer(16 * max(V, 1)))
-        if levels is not None:
-            run("rects_ms", lambda: _lib.check(lib.hvd_dev_content_rects_detail(d_frames_ptr, n, h, w, channels, d_off.ptr, V,
-                                                                                levels[0], levels[1], d_r.ptr)))
-        elif bar_color is None:
-            run("rects_ms", lambda: _lib.check(lib.hvd_dev_content_rects(d_frames_ptr, n, h, w, channels, d_off.ptr, V,
-                                                                         int(black_level), int(min_bright), d_r.ptr)))
-        else:
-            sb = C.c_size_t(0)
-            _lib.check(lib.hvd_bar_colors_scratch_bytes(V, C.byref(sb)))
-            d_c = scope.temp(DeviceBuffer(4 * max(V, 1)) if packed is None else DeviceBuffer.from_array(packed))
-            d_a = scope.temp(DeviceBuffer(max(sb.value, 1))) if packed is None else None
-
-            def colour_rects():
-                if packed is None:
-                    _lib.check(lib.hvd_dev_bar_colors(d_frames_ptr, n, h, w, channels, d_off.ptr, V, level, d_a.ptr, d_c.ptr))
-                _lib.check(lib.hvd_dev_content_rects_color(d_frames_ptr, n, h, w, channels, d_off.ptr, V, d_c.ptr, level, bright,
-                                                           d_r.ptr))
-
-            run("rects_ms", colour_rects)
+        vpdq.enqueue_rects(lib, rule, packed, d_frames_ptr, n, h, w, channels, d_off.ptr, V, d_r.ptr, scope.temp,
+                           lambda fn: run("rects_ms", fn))
         d_h = scope.keep(DeviceBuffer(32 * max(n, 1)))
         d_q = scope.keep(DeviceBuffer(4 * max(n, 1)))
         sb = C.c_size_t(0)
@@ -670,9 +649,9 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
     bar-colour rule instead; that form is for world == 1 (an array bar_color has one row per video of the library). A dict
     of detail (True) / detail_level / min_detail finds them by the detail rule, for world == 1 as well."""
     crop = vpdq.autocrop_rule(autocrop)
-    if crop is not None and crop[2] is vpdq.DETAIL and world != 1:
+    if crop is not None and crop.kind == "detail" and world != 1:
         raise ValueError("the detail rule is not sharded over a device group: world must be 1")
-    if crop is not None and crop[2] is not None and world != 1:
+    if crop is not None and crop.kind == "color" and world != 1:
         raise ValueError("the bar-colour rule is not sharded over a device group: world must be 1")
     timed = _stage_timer(timings)
 
@@ -680,11 +659,7 @@ def dedupe_frames_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
         n_mine = int(mine[-1])
         if crop is None:
             return timed("hash_ms", lambda: hash_frames_on_device(d_frames_ptr, n_mine, h, w, channels))
-        if crop[2] is None:
-            d_h, d_q, d_r = hash_frames_autocrop_on_device(d_frames_ptr, n_mine, h, w, channels, mine, crop[0], crop[1], timed)
-        else:
-            d_h, d_q, d_r = hash_frames_autocrop_on_device(d_frames_ptr, n_mine, h, w, channels, mine, timed=timed,
-                                                           **vpdq.rule_kwargs(crop))
+        d_h, d_q, d_r = hash_frames_autocrop_on_device(d_frames_ptr, n_mine, h, w, channels, mine, timed=timed, **crop.kwargs())
         d_r.free()
         return d_h, d_q
 
@@ -940,12 +915,11 @@ def dedupe_frames_in_process(frames_of_rank, raw_offsets: np.ndarray, h: int, w:
     called on the rank's thread, with the rank's context current). -> (pairs, records) -- every rank computes the same;
     rank 0's are returned. timings: rank 0's stage times. autocrop: as `dedupe_frames_on_device`."""
     # a bad value fails here, not on every rank's thread; a group takes the black rule only
-    black = autocrop
-    if isinstance(autocrop, dict) and vpdq._DETAIL_KEYS & set(autocrop):
-        if vpdq.autocrop_rule(autocrop)[2] is vpdq.DETAIL:
-            raise ValueError("the detail rule is not sharded over a device group: world must be 1 (dedupe_frames_on_device)")
-        black = {k: v for k, v in autocrop.items() if k != "detail"}  # "detail": False states the default
-    vpdq.autocrop_params(black)
+    rule = vpdq.autocrop_rule(autocrop)
+    if rule is not None and rule.kind == "detail":
+        raise ValueError("the detail rule is not sharded over a device group: world must be 1 (dedupe_frames_on_device)")
+    if rule is not None and rule.kind == "color":
+        vpdq.autocrop_params(rule.kwargs())  # raises: the black rule's keys only
     return _rank0_of_every_context(dedupe_frames_on_device, frames_of_rank, timings, 2, raw_offsets, h, w, channels,
                                    threshold, policy, autocrop=autocrop)
 

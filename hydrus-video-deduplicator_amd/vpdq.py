@@ -31,6 +31,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
+from typing import NamedTuple
 
 import numpy as np
 
@@ -207,12 +209,10 @@ class VideoHasher:
                  batch_bytes: int = 32 << 20, transforms=None, autocrop=None, max_retained_bytes: int | None = None):
         if width < 64 or height < 64:
             raise ValueError("frames must be at least 64x64")
-        if isinstance(autocrop, dict) and {"bar_color", "bar_level"} & set(autocrop):
+        if isinstance(autocrop, dict) and _KIND_KEYS["color"] & set(autocrop):
             raise ValueError("the streaming hasher has no bar-colour rule (the automatic colour is known only after the last "
                              "frame): hash the array form of the frames, vpdq.hash_frames_autocrop(frames, bar_color=...)")
-        rule = autocrop_rule(autocrop)
-        self._detail = rule is not None and rule[2] is DETAIL
-        self._autocrop = None if rule is None else rule[:2]
+        self._autocrop = autocrop_rule(autocrop)  # a RectRule of the black or the detail kind, or None
         if self._autocrop is not None and transforms is not None:
             raise ValueError("autocrop and transforms cannot be combined (content-rectangle dihedral hashing does not exist)")
         if max_retained_bytes is not None and (isinstance(max_retained_bytes, bool) or not isinstance(max_retained_bytes, (int, np.integer))
@@ -248,9 +248,9 @@ class VideoHasher:
         batch = max(1, min(4096, self._batch_bytes // frame_bytes))
         h = C.c_void_p()
         if self._autocrop is not None:
-            create = self._lib.hvd_hasher_create_autocrop_detail if self._detail else self._lib.hvd_hasher_create_autocrop
-            _lib.check(create(self.width, self.height, channels, batch, self._autocrop[0], self._autocrop[1], self._max_retained,
-                              C.byref(h)))
+            create = getattr(self._lib, "hvd_hasher_create_autocrop" + _RECT_KINDS[self._autocrop.kind].dev)
+            _lib.check(create(self.width, self.height, channels, batch, self._autocrop.level, self._autocrop.count,
+                              self._max_retained, C.byref(h)))
         else:
             create = self._lib.hvd_hasher_create if self._transforms is None else self._lib.hvd_hasher_create_dihedral
             _lib.check(create(self.width, self.height, channels, batch, C.byref(h)))
@@ -446,32 +446,164 @@ def hash_frames(frames: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
     return hashes, quality
 
 
-# Content-rectangle PDQ (include/hvd_mi355x.h): black bars (letterbox / pillarbox) are left out of the hash.
-def autocrop_params(autocrop) -> tuple[int, int] | None:
-    """None when `autocrop` is off (None / False); else (black_level, min_bright) from True (the defaults 16, 1) or a dict
-    with those two keys. Argument errors are raised here, before any device work."""
+# Content-rectangle PDQ (include/hvd_mi355x.h): bars are left out of the hash. The rule that tells bar from
+# picture is one value, a RectRule, from the keywords of a call down to the native entry:
+#   black      black bars (letterbox / pillarbox): a pixel is bright iff max(R, G, B) > black_level
+#   color     bars that are not black: a pixel is content iff it differs from its video's bar colour by more than
+#                          bar_level on some channel (include/hvd_mi355x.h: hvd_dev_bar_colors)
+#   detail    bars that are smooth: a row is content iff it holds >= min_detail horizontal neighbour differences
+#                          above detail_level, a column likewise with vertical ones (hvd_dev_content_rects_detail)
+class _DetailRule:
+    """What a RectRule of the detail kind holds in the colour's place."""
+
+    def __repr__(self):
+        return "DETAIL"
+
+
+DETAIL = _DetailRule()
+
+
+# A kind of rule: the keywords of its level and count with their defaults and ranges, the words of the level's range message
+# (level_one_message: the level's type and range share one message, raised before the count is looked at), and its native
+# entries -- hvd_pdq_hash_frames_<stem>_<format>, hvd_dev_content_rects<dev>, hvd_hasher_create_autocrop<dev>.
+_RectKind = namedtuple("_RectKind", "level count level_default count_default level_range count_range why level_one_message stem dev")
+_RECT_KINDS = {  # (the detail defaults are unverified on real video)
+    "black": _RectKind("black_level", "min_bright", 16, 1, (0, 254), (1, 2**31 - 1),
+                       "a pixel is bright iff max(R, G, B) > black_level", False, "autocrop", ""),
+    "color": _RectKind("bar_level", "min_bright", 16, 1, (0, 254), (1, 2**31 - 1),
+                       "a pixel is content iff it differs from the bar colour by more than bar_level on some channel", True,
+                       "barcolor", "_color"),
+    "detail": _RectKind("detail_level", "min_detail", 8, 8, (0, 254), (1, 2**31 - 1),
+                        "two neighbours differ iff some channel differs by more than detail_level", False, "detail", "_detail"),
+}
+_KIND_KEYS = {"black": {"black_level", "min_bright"}, "color": {"bar_color", "bar_level"},
+              "detail": {"detail", "detail_level", "min_detail"}}
+
+
+class RectRule(NamedTuple):
+    """The rule that finds a video's content rectangle: (level, count, colour). colour None is the black rule, DETAIL the
+    detail rule, anything else ("auto", an int, a 3-tuple or an array [V, channels]) the bar colour of the colour rule.
+    Equal to the plain 3-tuple of its fields."""
+    level: int
+    count: int
+    colour: object = None
+
+    @property
+    def kind(self) -> str:
+        """ "black", "color" or "detail": a key of the table of kinds."""
+        if self.colour is None:
+            return "black"
+        return "detail" if self.colour is DETAIL else "color"
+
+    def kwargs(self) -> dict:
+        """The keywords of `hash_frames_autocrop` / `content_rects` that state this rule."""
+        k = _RECT_KINDS[self.kind]
+        stated = {k.level: self.level, k.count: self.count}
+        if self.kind == "detail":
+            stated["detail"] = True
+        elif self.kind == "color":
+            stated["bar_color"] = self.colour
+        return stated
+
+
+def rule_kwargs(rule) -> dict:
+    """`RectRule.kwargs` of what `autocrop_rule` returned (not None), or of the plain tuple (level, count, colour)."""
+    return RectRule(*rule).kwargs()
+
+
+def _is_int(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, np.integer))
+
+
+def _check_levels(kind: str, level, count) -> tuple[int, int]:
+    """(level, count) of a rule of `kind` as ints, or the ValueError that names the keyword."""
+    k = _RECT_KINDS[kind]
+    lo, hi = k.level_range
+    if k.level_one_message and (not _is_int(level) or not lo <= level <= hi):
+        raise ValueError(f"{k.level} must be an integer in {lo}..{hi} ({k.why}), got {level!r}")
+    for name, v in ((k.level, level), (k.count, count)):
+        if not _is_int(v):
+            raise ValueError(f"{name} must be an integer, got {v!r}")
+    if not lo <= level <= hi:
+        raise ValueError(f"{k.level} must be in {lo}..{hi} ({k.why}), got {level}")
+    if not k.count_range[0] <= count <= k.count_range[1]:
+        raise ValueError(f"{k.count} must be >= {k.count_range[0]}, got {count}")
+    return int(level), int(count)
+
+
+_RULE_DEFAULTS = dict(black_level=16, min_bright=1, bar_color=None, bar_level=None, detail=False, detail_level=None,
+                      min_detail=None)
+
+
+def rect_rule(black_level=16, min_bright=1, bar_color=None, bar_level=None, detail=False, detail_level=None, min_detail=None,
+              stated=None) -> RectRule:
+    """The one parser of the rule's keywords, as `content_rects`, `hash_frames_autocrop` and
+    `pipeline.hash_frames_autocrop_on_device` take them. bar_color not None is the colour rule with `bar_level` (default 16)
+    and `min_bright`; detail=True the detail rule with `detail_level` (default 8, unverified) and `min_detail` (default 8,
+    unverified); else the black rule with `black_level` and `min_bright`. A keyword of another rule beside the chosen one is a
+    ValueError that names both. stated: the keywords the caller stated, in the order the messages name them (None: those
+    that do not hold their default, in the order above; `autocrop_rule` passes the keys of its dict)."""
+    kw = dict(black_level=black_level, min_bright=min_bright, bar_color=bar_color, bar_level=bar_level, detail=detail,
+              detail_level=detail_level, min_detail=min_detail)
+    if stated is None:
+        stated = [name for name, v in kw.items() if v is not _RULE_DEFAULTS[name] and not (_is_int(v) and v == _RULE_DEFAULTS[name])]
+    if detail is not True and detail is not False:
+        raise ValueError(f"detail must be True or False, got {detail!r}")
+    if detail:
+        for name in stated:
+            if name not in _KIND_KEYS["detail"]:
+                raise ValueError(f"detail and {name} cannot be combined: the detail rule's parameters are detail_level and min_detail")
+        k = _RECT_KINDS["detail"]
+        return RectRule(*_check_levels("detail", k.level_default if detail_level is None else detail_level,
+                                       k.count_default if min_detail is None else min_detail), DETAIL)
+    for name, v in (("detail_level", detail_level), ("min_detail", min_detail)):
+        if v is not None:
+            raise ValueError(f"{name} needs detail=True (the detail rule, DESIGN 4.16)")
+    if bar_color is None:
+        if _KIND_KEYS["color"] & set(stated):
+            raise ValueError("bar_level needs bar_color (the black rule's level is black_level)")
+        return RectRule(*_check_levels("black", black_level, min_bright), None)
+    if "black_level" in stated:
+        raise ValueError("black_level and bar_color cannot be combined: the level of the bar-colour rule is bar_level")
+    return RectRule(*_check_levels("color", _RECT_KINDS["color"].level_default if bar_level is None else bar_level, min_bright),
+                    bar_color)
+
+
+def autocrop_rule(autocrop) -> RectRule | None:
+    """The `autocrop` argument of the video-level calls -> None when it is off (None / False), else its RectRule: `rect_rule`
+    behind the check of the dict's shape. True is the black rule at its defaults (16, 1); a dict may hold ``black_level`` /
+    ``min_bright`` (the black rule), ``bar_color`` ("auto", an int, a 3-tuple or an array [V, channels]) with ``bar_level``
+    (default 16) / ``min_bright`` (the colour rule; ``black_level`` beside ``bar_color`` is a ValueError, and so is
+    ``bar_level`` without it; the colour's shape is checked where the frames are known), or ``detail`` True with
+    ``detail_level`` (default 8, unverified) / ``min_detail`` (default 8, unverified) (the detail rule; any key
+    of the other rules beside it is a ValueError that names both, and so are ``detail_level`` / ``min_detail`` without
+    ``detail``; ``"detail": False`` states the default). Argument errors are raised here, before any device work."""
     if autocrop is None or autocrop is False:
         return None
     if autocrop is True:
         autocrop = {}
-    if not isinstance(autocrop, dict) or set(autocrop) - {"black_level", "min_bright"}:
+    keys = set(autocrop) if isinstance(autocrop, dict) else None
+    if keys is None or keys - set(_RULE_DEFAULTS):
+        shape = "autocrop must be True / False or a dict with the keys black_level and min_bright"
+        if keys is not None and keys & (_KIND_KEYS["color"] | _KIND_KEYS["detail"]):
+            shape += ", or bar_color, bar_level and min_bright"
+        if keys is not None and keys & _KIND_KEYS["detail"]:
+            shape += ", or detail, detail_level and min_detail"
+        raise ValueError(shape)
+    return rect_rule(**autocrop, stated=sorted(keys))
+
+
+def autocrop_params(autocrop) -> tuple[int, int] | None:
+    """`autocrop_rule` for a call site that takes the black rule only: None when `autocrop` is off (None / False); else
+    (black_level, min_bright) from True (the defaults 16, 1) or a dict with those two keys."""
+    if isinstance(autocrop, dict) and set(autocrop) - _KIND_KEYS["black"]:
         raise ValueError("autocrop must be True / False or a dict with the keys black_level and min_bright")
-    return _check_autocrop(autocrop.get("black_level", 16), autocrop.get("min_bright", 1))
+    rule = autocrop_rule(autocrop)
+    return None if rule is None else (rule.level, rule.count)
 
 
-def _check_autocrop(black_level, min_bright) -> tuple[int, int]:
-    for name, v in (("black_level", black_level), ("min_bright", min_bright)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"{name} must be an integer, got {v!r}")
-    if not 0 <= black_level <= 254:
-        raise ValueError(f"black_level must be in 0..254 (a pixel is bright iff max(R, G, B) > black_level), got {black_level}")
-    if not 1 <= min_bright < 2**31:
-        raise ValueError(f"min_bright must be >= 1, got {min_bright}")
-    return int(black_level), int(min_bright)
-
-
-def _autocrop_args(frames, offsets, black_level, min_bright):
-    level, bright = _check_autocrop(black_level, min_bright)
+def _frames_args(frames, offsets):
+    """frames as a contiguous uint8[n,h,w] / uint8[n,h,w,3] and the int64[V+1] CSR of its videos (None: one video)."""
     frames = np.asarray(frames)
     if frames.dtype != np.uint8 or not (frames.ndim == 3 or (frames.ndim == 4 and frames.shape[3] == 3)):
         raise ValueError("frames must be uint8[n,h,w] or uint8[n,h,w,3]")
@@ -483,110 +615,7 @@ def _autocrop_args(frames, offsets, black_level, min_bright):
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         if offsets.ndim != 1 or len(offsets) < 1 or offsets[0] != 0 or offsets[-1] != n or np.any(np.diff(offsets) < 0):
             raise ValueError(f"offsets must be int64[V+1]: offsets[0] = 0, non-decreasing, offsets[V] = n = {n}")
-    return frames, offsets, level, bright
-
-
-# Bar-colour content rectangle (include/hvd_mi355x.h: hvd_dev_bar_colors): bars that are not black. A pixel is
-# content iff it differs from its video's bar colour by more than bar_level on some channel.
-_RULE_KEYS = {"black_level", "min_bright", "bar_color", "bar_level"}
-
-# Detail content rectangle (include/hvd_mi355x.h: hvd_dev_content_rects_detail): bars that are smooth. A row is
-# content iff it holds >= min_detail horizontal neighbour differences above detail_level, a column likewise with vertical ones.
-_DETAIL_KEYS = {"detail", "detail_level", "min_detail"}
-
-
-class _DetailRule:
-    """What `autocrop_rule` returns in the colour's place for the detail rule."""
-
-    def __repr__(self):
-        return "DETAIL"
-
-
-DETAIL = _DetailRule()
-
-
-def _check_detail_levels(detail_level, min_detail) -> tuple[int, int]:
-    """(detail_level, min_detail) with the defaults 8 and 8 (both unverified on real video) for None."""
-    detail_level = 8 if detail_level is None else detail_level
-    min_detail = 8 if min_detail is None else min_detail
-    for name, v in (("detail_level", detail_level), ("min_detail", min_detail)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f"{name} must be an integer, got {v!r}")
-    if not 0 <= detail_level <= 254:
-        raise ValueError(f"detail_level must be in 0..254 (two neighbours differ iff some channel differs by more than "
-                         f"detail_level), got {detail_level}")
-    if not 1 <= min_detail < 2**31:
-        raise ValueError(f"min_detail must be >= 1, got {min_detail}")
-    return int(detail_level), int(min_detail)
-
-
-def _detail_rule_args(detail, detail_level, min_detail, others: dict):
-    """The detail keywords of a call. -> None (the other rules) or (detail_level, min_detail). others: name -> (value, default)
-    of the other rules' keywords, none of which goes with the detail rule."""
-    if detail is not True and detail is not False:
-        raise ValueError(f"detail must be True or False, got {detail!r}")
-    if not detail:
-        for name, v in (("detail_level", detail_level), ("min_detail", min_detail)):
-            if v is not None:
-                raise ValueError(f"{name} needs detail=True (the detail rule, DESIGN 4.16)")
-        return None
-    for name, (v, default) in others.items():
-        same_int = default is not None and not isinstance(v, bool) and isinstance(v, (int, np.integer)) and v == default
-        if v is not default and not same_int:
-            raise ValueError(f"detail and {name} cannot be combined: the detail rule's parameters are detail_level and min_detail")
-    return _check_detail_levels(detail_level, min_detail)
-
-
-def rule_kwargs(rule) -> dict:
-    """The keywords of `hash_frames_autocrop` / `content_rects` that state what `autocrop_rule` returned (not None)."""
-    if rule[2] is None:
-        return dict(black_level=rule[0], min_bright=rule[1])
-    if rule[2] is DETAIL:
-        return dict(detail=True, detail_level=rule[0], min_detail=rule[1])
-    return dict(bar_color=rule[2], bar_level=rule[0], min_bright=rule[1])
-
-
-def autocrop_rule(autocrop) -> tuple[int, int, object] | None:
-    """`autocrop_params` for the call sites that also know the bar-colour rule: None when `autocrop` is off, else
-    (level, min_bright, bar_color). bar_color None is the black rule and level its black_level -- what `autocrop_params`
-    returns, for every input it accepts. A dict with ``bar_color`` ("auto", an int, a 3-tuple or an array [V, channels])
-    may carry ``bar_level`` (default 16) and ``min_bright``; ``black_level`` together with ``bar_color`` is a ValueError,
-    and so is ``bar_level`` without it. The colour's shape is checked where the frames are known.
-    A dict with ``detail`` True is the detail rule: (detail_level, min_detail, DETAIL), from the optional keys
-    ``detail_level`` (default 8, unverified) and ``min_detail`` (default 8, unverified). Any key of the other rules beside
-    it is a ValueError that names both, and so are ``detail_level`` / ``min_detail`` without ``detail``."""
-    if isinstance(autocrop, dict) and _DETAIL_KEYS & set(autocrop):
-        if set(autocrop) - _RULE_KEYS - _DETAIL_KEYS:
-            raise ValueError("autocrop must be True / False or a dict with the keys black_level and min_bright, or bar_color, "
-                             "bar_level and min_bright, or detail, detail_level and min_detail")
-        detail = autocrop.get("detail", False)
-        if detail is True and _RULE_KEYS & set(autocrop):
-            name = sorted(_RULE_KEYS & set(autocrop))[0]
-            raise ValueError(f"detail and {name} cannot be combined: the detail rule's parameters are detail_level and min_detail")
-        levels = _detail_rule_args(detail, autocrop.get("detail_level"), autocrop.get("min_detail"), {})
-        if levels is not None:
-            return (*levels, DETAIL)
-        autocrop = {k: v for k, v in autocrop.items() if k != "detail"}  # "detail": False states the default
-    if not isinstance(autocrop, dict) or not ({"bar_color", "bar_level"} & set(autocrop)):
-        params = autocrop_params(autocrop)
-        return None if params is None else (*params, None)
-    if set(autocrop) - _RULE_KEYS:
-        raise ValueError("autocrop must be True / False or a dict with the keys black_level and min_bright, or bar_color, "
-                         "bar_level and min_bright")
-    if "black_level" in autocrop and autocrop.get("bar_color") is not None:
-        raise ValueError("black_level and bar_color cannot be combined: the level of the bar-colour rule is bar_level")
-    if autocrop.get("bar_color") is None:
-        raise ValueError("bar_level needs bar_color (the black rule's level is black_level)")
-    level, bright = _check_bar_levels(autocrop.get("bar_level"), autocrop.get("min_bright", 1))
-    return level, bright, autocrop["bar_color"]
-
-
-def _check_bar_levels(bar_level, min_bright) -> tuple[int, int]:
-    bar_level = 16 if bar_level is None else bar_level
-    if isinstance(bar_level, bool) or not isinstance(bar_level, (int, np.integer)) or not 0 <= bar_level <= 254:
-        raise ValueError(f"bar_level must be an integer in 0..254 (a pixel is content iff it differs from the bar colour by "
-                         f"more than bar_level on some channel), got {bar_level!r}")
-    return int(bar_level), _check_autocrop(0, min_bright)[1]
+    return frames, offsets
 
 
 def _pack_bar_color(bar_color, V: int, channels: int) -> np.ndarray | None:
@@ -617,64 +646,67 @@ def _unpack_bar_colors(packed: np.ndarray, channels: int) -> np.ndarray:
     return np.stack([(packed >> (8 * k)) & 0xFF for k in range(channels)], axis=1).astype(np.uint8)
 
 
-def _bar_rule_args(black_level, min_bright, bar_color, bar_level):
-    """(level, min_bright) of a call with bar_color: its level is bar_level, and black_level stays at its default."""
-    if black_level != 16:
-        raise ValueError("black_level and bar_color cannot be combined: the level of the bar-colour rule is bar_level")
-    return _check_bar_levels(bar_level, min_bright)
+def enqueue_rects(lib, rule: RectRule, packed, d_frames, n: int, h: int, w: int, channels: int, d_offsets, V: int, d_rects, temp,
+                  run=lambda fn: fn()):
+    """The rectangle step of `rule` on n frames that sit in HBM: its kind's hvd_dev_content_rects entry, enqueued on the
+    library stream. d_frames, d_offsets, d_rects: device pointers. The colour kind takes the colours from `packed`
+    (`_pack_bar_color`) or, where that is None ("auto"), finds them first (hvd_dev_bar_colors); d_rects None stops there
+    (`bar_colors`). temp(DeviceBuffer) -> that buffer, which the caller frees once the work is done; run(fn): what the
+    native calls run inside (a stage timer). -> the DeviceBuffer of the colours int32[V] (colour kind), else None."""
+    entry = getattr(lib, "hvd_dev_content_rects" + _RECT_KINDS[rule.kind].dev)
+    if rule.kind != "color":
+        run(lambda: _lib.check(entry(d_frames, n, h, w, channels, d_offsets, V, rule.level, rule.count, d_rects)))
+        return None
+    d_col = temp(_lib.DeviceBuffer(4 * max(V, 1)) if packed is None else _lib.DeviceBuffer.from_array(packed))
+    d_acc = None
+    if packed is None:
+        sb = C.c_size_t(0)
+        _lib.check(lib.hvd_bar_colors_scratch_bytes(V, C.byref(sb)))
+        d_acc = temp(_lib.DeviceBuffer(max(sb.value, 1)))
+
+    def colour_rects():
+        if d_acc is not None:
+            _lib.check(lib.hvd_dev_bar_colors(d_frames, n, h, w, channels, d_offsets, V, rule.level, d_acc.ptr, d_col.ptr))
+        if d_rects is not None:
+            _lib.check(entry(d_frames, n, h, w, channels, d_offsets, V, d_col.ptr, rule.level, rule.count, d_rects))
+
+    run(colour_rects)
+    return d_col
 
 
-def _device_colors_and_rects(lib, frames, offsets, packed, level, bright, want_rects):
-    """hvd_dev_bar_colors (packed None) and, want_rects, hvd_dev_content_rects_color on the frames uploaded once.
-    -> (colors int32[V], rects int32[V,4] or None)."""
+def _rects_of_host_frames(rule: RectRule, packed, frames, offsets, want_rects: bool):
+    """`enqueue_rects` on host frames, uploaded for the call. -> rects int32[V,4] (want_rects), or the colours int32[V]."""
+    lib = _lib.ensure()
     n, h, w = frames.shape[:3]
-    V, ch = len(offsets) - 1, 1 if frames.ndim == 3 else 3
-    sb = C.c_size_t(0)
-    _lib.check(lib.hvd_bar_colors_scratch_bytes(V, C.byref(sb)))
+    V = len(offsets) - 1
     bufs = []
+
+    def temp(buf):
+        bufs.append(buf)
+        return buf
+
     try:
-        d_fr = _lib.DeviceBuffer.from_array(frames) if n else None
-        bufs.append(d_fr)
-        d_off = _lib.DeviceBuffer.from_array(offsets)
-        bufs.append(d_off)
-        d_col = _lib.DeviceBuffer(4 * V) if packed is None else _lib.DeviceBuffer.from_array(packed)
-        bufs.append(d_col)
-        fr_ptr = d_fr.ptr if n else None
-        if packed is None:
-            d_acc = _lib.DeviceBuffer(sb.value)
-            bufs.append(d_acc)
-            _lib.check(lib.hvd_dev_bar_colors(fr_ptr, n, h, w, ch, d_off.ptr, V, level, d_acc.ptr, d_col.ptr))
-        rects = None
-        if want_rects:
-            d_rc = _lib.DeviceBuffer(16 * V)
-            bufs.append(d_rc)
-            _lib.check(lib.hvd_dev_content_rects_color(fr_ptr, n, h, w, ch, d_off.ptr, V, d_col.ptr, level, bright, d_rc.ptr))
-            rects = d_rc.to_array(np.int32, V * 4).reshape(V, 4)
-        colors = d_col.to_array(np.int32, V)
+        d_fr = temp(_lib.DeviceBuffer.from_array(frames)) if n else None
+        d_off = temp(_lib.DeviceBuffer.from_array(offsets))
+        d_rc = temp(_lib.DeviceBuffer(16 * V)) if want_rects else None
+        d_col = enqueue_rects(lib, rule, packed, d_fr.ptr if n else None, n, h, w, 1 if frames.ndim == 3 else 3, d_off.ptr, V,
+                              d_rc.ptr if want_rects else None, temp)
+        return d_rc.to_array(np.int32, V * 4).reshape(V, 4) if want_rects else d_col.to_array(np.int32, V)
     finally:
         for b in bufs:
-            if b is not None:
-                b.free()
-    return colors, rects
+            b.free()
 
 
 def bar_colors(frames: np.ndarray, offsets=None, bar_level: int = 16) -> np.ndarray:
     """The automatic bar colour of every video, found on the device from the four corner pixels of all its frames:
     uint8[V, channels] in the byte order of the pixel; (0, ...) where the corners differ by more than bar_level (no uniform
     bars: the black rule) and for a video without frames. The rule is in include/hvd_mi355x.h (hvd_dev_bar_colors)."""
-    level, _ = _check_bar_levels(bar_level, 1)
-    frames, offsets, _, _ = _autocrop_args(frames, offsets, 16, 1)
+    level, _ = _check_levels("color", _RECT_KINDS["color"].level_default if bar_level is None else bar_level, 1)
+    frames, offsets = _frames_args(frames, offsets)
     channels = 1 if frames.ndim == 3 else 3
-    V = len(offsets) - 1
-    if V == 0:
+    if len(offsets) == 1:
         return np.zeros((0, channels), dtype=np.uint8)
-    colors, _ = _device_colors_and_rects(_lib.ensure(), frames, offsets, None, level, 1, False)
-    return _unpack_bar_colors(colors, channels)
-
-
-def _other_rules(black_level, min_bright, bar_color, bar_level) -> dict:
-    return {"black_level": (black_level, 16), "min_bright": (min_bright, 1), "bar_color": (bar_color, None),
-            "bar_level": (bar_level, None)}
+    return _unpack_bar_colors(_rects_of_host_frames(RectRule(level, 1, "auto"), None, frames, offsets, False), channels)
 
 
 def content_rects(frames: np.ndarray, offsets=None, black_level: int = 16, min_bright: int = 1, bar_color=None,
@@ -687,42 +719,13 @@ def content_rects(frames: np.ndarray, offsets=None, black_level: int = 16, min_b
     detail=True is the detail rule (hvd_dev_content_rects_detail) with `detail_level` (default 8, unverified)
     and `min_detail` (default 8, unverified): smooth bars of any colour are left out; none of the other rules' keywords
     goes with it."""
-    levels = _detail_rule_args(detail, detail_level, min_detail, _other_rules(black_level, min_bright, bar_color, bar_level))
-    entry = "hvd_dev_content_rects"
-    if levels is not None:
-        black_level, min_bright = levels
-        entry = "hvd_dev_content_rects_detail"
-    if bar_color is None and bar_level is not None:
-        raise ValueError("bar_level needs bar_color (the black rule's level is black_level)")
-    if bar_color is not None:
-        level, bright = _bar_rule_args(black_level, min_bright, bar_color, bar_level)
-        frames, offsets, _, _ = _autocrop_args(frames, offsets, 16, 1)
-        V = len(offsets) - 1
-        packed = _pack_bar_color(bar_color, V, 1 if frames.ndim == 3 else 3)
-        if V == 0:
-            return np.zeros((0, 4), dtype=np.int32)
-        return _device_colors_and_rects(_lib.ensure(), frames, offsets, packed, level, bright, True)[1]
-    frames, offsets, level, bright = _autocrop_args(frames, offsets, 16 if levels else black_level, 1 if levels else min_bright)
-    if levels is not None:
-        level, bright = levels
-    lib = _lib.ensure()
-    n, h, w = frames.shape[:3]
+    rule = rect_rule(black_level, min_bright, bar_color, bar_level, detail, detail_level, min_detail)
+    frames, offsets = _frames_args(frames, offsets)
     V = len(offsets) - 1
-    rects = np.zeros((V, 4), dtype=np.int32)
+    packed = _pack_bar_color(rule.colour, V, 1 if frames.ndim == 3 else 3) if rule.kind == "color" else None
     if V == 0:
-        return rects
-    d_fr = _lib.DeviceBuffer.from_array(frames) if n else None
-    d_off = _lib.DeviceBuffer.from_array(offsets)
-    d_rc = _lib.DeviceBuffer(rects.nbytes)
-    try:
-        _lib.check(getattr(lib, entry)(d_fr.ptr if n else None, n, h, w, 1 if frames.ndim == 3 else 3, d_off.ptr, V,
-                                       level, bright, d_rc.ptr))
-        rects[:] = d_rc.to_array(np.int32, V * 4).reshape(V, 4)
-    finally:
-        for b in (d_fr, d_off, d_rc):
-            if b is not None:
-                b.free()
-    return rects
+        return np.zeros((0, 4), dtype=np.int32)
+    return _rects_of_host_frames(rule, packed, frames, offsets, True)
 
 
 def hash_frames_autocrop(frames: np.ndarray, offsets=None, black_level: int = 16, min_bright: int = 1, bar_color=None,
@@ -734,34 +737,22 @@ def hash_frames_autocrop(frames: np.ndarray, offsets=None, black_level: int = 16
     bar_color / bar_level: as `content_rects` -- the rectangle then leaves out bars of the video's colour (`bar_colors`
     returns what "auto" finds).
     detail / detail_level / min_detail: as `content_rects` -- the rectangle then leaves out smooth bars of any colour."""
-    levels = _detail_rule_args(detail, detail_level, min_detail, _other_rules(black_level, min_bright, bar_color, bar_level))
-    if bar_color is None and bar_level is not None:
-        raise ValueError("bar_level needs bar_color (the black rule's level is black_level)")
-    if levels is not None:
-        frames, offsets, _, _ = _autocrop_args(frames, offsets, 16, 1)
-        level, bright = levels
-    elif bar_color is not None:
-        level, bright = _bar_rule_args(black_level, min_bright, bar_color, bar_level)
-        frames, offsets, _, _ = _autocrop_args(frames, offsets, 16, 1)
-        packed = _pack_bar_color(bar_color, len(offsets) - 1, 1 if frames.ndim == 3 else 3)
-    else:
-        frames, offsets, level, bright = _autocrop_args(frames, offsets, black_level, min_bright)
-    lib = _lib.ensure()
+    rule = rect_rule(black_level, min_bright, bar_color, bar_level, detail, detail_level, min_detail)
+    frames, offsets = _frames_args(frames, offsets)
     n, h, w = frames.shape[:3]
     V = len(offsets) - 1
+    colours_in = colours_out = ()  # the colour kind's entries take the caller's colours and return the ones used
+    if rule.kind == "color":
+        packed = _pack_bar_color(rule.colour, V, 1 if frames.ndim == 3 else 3)
+        used = np.zeros(V, dtype=np.int32)
+        colours_in, colours_out = (None if packed is None else packed.ctypes.data,), (used.ctypes.data,)
+    lib = _lib.ensure()
     hashes = np.zeros((n, BYTES_PER_PDQ_HASH), dtype=np.uint8)
     quality = np.zeros(n, dtype=np.int32)
     rects = np.zeros((V, 4), dtype=np.int32)
-    if bar_color is not None:
-        used = np.zeros(V, dtype=np.int32)
-        fn = lib.hvd_pdq_hash_frames_barcolor_gray_u8 if frames.ndim == 3 else lib.hvd_pdq_hash_frames_barcolor_rgb24_u8
-        _lib.check(fn(frames.ctypes.data, n, h, w, offsets.ctypes.data, V, None if packed is None else packed.ctypes.data, level,
-                      bright, hashes.ctypes.data, quality.ctypes.data, rects.ctypes.data, used.ctypes.data))
-        return hashes, quality, rects
-    kind = "detail" if levels is not None else "autocrop"
-    fn = getattr(lib, f"hvd_pdq_hash_frames_{kind}_gray_u8" if frames.ndim == 3 else f"hvd_pdq_hash_frames_{kind}_rgb24_u8")
-    _lib.check(fn(frames.ctypes.data, n, h, w, offsets.ctypes.data, V, level, bright, hashes.ctypes.data, quality.ctypes.data,
-                  rects.ctypes.data))
+    fn = getattr(lib, f"hvd_pdq_hash_frames_{_RECT_KINDS[rule.kind].stem}_{'gray_u8' if frames.ndim == 3 else 'rgb24_u8'}")
+    _lib.check(fn(frames.ctypes.data, n, h, w, offsets.ctypes.data, V, *colours_in, rule.level, rule.count, hashes.ctypes.data,
+                  quality.ctypes.data, rects.ctypes.data, *colours_out))
     return hashes, quality, rects
 
 

@@ -131,7 +131,7 @@ class Vpdq:
                 raise ValueError("frames must be uint8[n,h,w] or uint8[n,h,w,3]")
             h, w = frames.shape[1], frames.shape[2]
             if crop is not None:
-                hashes, quality, _ = vpdq.hash_frames_autocrop(frames, None, **vpdq.rule_kwargs(crop))
+                hashes, quality, _ = vpdq.hash_frames_autocrop(frames, None, **crop.kwargs())
                 return VpdqHash(hashes[quality >= vpdq.QUALITY_TOLERANCE].tobytes())
             hasher = vpdq.VideoHasher(average_fps, w, h, num_threads)
             flat = np.ascontiguousarray(frames, dtype=np.uint8).reshape(frames.shape[0], -1)
