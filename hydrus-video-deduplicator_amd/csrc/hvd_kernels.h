@@ -163,6 +163,11 @@ hipError_t launch_kept_positions(const int32_t* d_quality, unsigned long long n,
 // compact_scratch_bytes(n), d_total one uint64 (device) that receives the kept count.
 hipError_t launch_keys_to_spread(const unsigned long long* d_src, unsigned long long n_src, unsigned long long n,
                                  int32_t* d_spread, hipStream_t s);
+// launch_keys_to_spread_cross: the rectangular key set, side 0 -> d_spread_q int32[nq], side 1 -> d_spread_t
+// int32[nt]; either may be nullptr. Zeroed by the launcher on s unless `accumulate`: the counts are then added to what is there.
+hipError_t launch_keys_to_spread_cross(const unsigned long long* d_src, unsigned long long n_src, unsigned long long nq,
+                                       unsigned long long nt, bool accumulate, int32_t* d_spread_q, int32_t* d_spread_t,
+                                       hipStream_t s);
 hipError_t launch_common_rule(const int32_t* d_spread, const long long* d_offsets, uint32_t V, unsigned long long n,
                               int max_videos, int max_share, int32_t* d_keep, hipStream_t s);
 hipError_t launch_gather_kept_i32(const int32_t* d_in, const int32_t* d_keep, unsigned long long n, int32_t* d_out,

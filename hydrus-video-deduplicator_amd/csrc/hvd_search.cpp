@@ -1008,6 +1008,34 @@ int hvd_vpdq_match_videos_cross(const uint8_t* frames_q, const int64_t* offsets_
     return copy_out(res, (int64_t)res.size(), vmatch_less, out, cap, out_count, "video match");
 }
 
+int hvd_vpdq_frame_spread_cross(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const uint8_t* frames_t,
+                                const int64_t* offsets_t, int64_t VT, int max_dist, int32_t* out_spread_q, int32_t* out_spread_t) {
+    if (int rc = need_ready()) return rc;
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    int64_t nq = 0, nt = 0;
+    if (int rc = check_offsets(offsets_q, VQ, &nq)) return rc;
+    if (int rc = check_offsets(offsets_t, VT, &nt)) return rc;
+    if ((nq > 0 && !out_spread_q) || (nt > 0 && !out_spread_t)) return fail(HVD_ERR_ARG, "out_spread is NULL");
+    if (nq == 0 || nt == 0) {
+        if (nq > 0) memset(out_spread_q, 0, 4 * (size_t)nq);
+        if (nt > 0) memset(out_spread_t, 0, 4 * (size_t)nt);
+        return HVD_OK;
+    }
+    if (!frames_q || !frames_t) return fail(HVD_ERR_ARG, "frames is NULL");
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    void *d_iq = nullptr, *d_it = nullptr, *d_sq = nullptr, *d_st = nullptr;
+    int32_t *d_vq = nullptr, *d_vt = nullptr;
+    if (int rc = upload_library(frames_q, offsets_q, VQ, nq, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_iq, &d_vq)) return rc;
+    if (int rc = upload_library(frames_t, offsets_t, VT, nt, Ctx::S_DB2, Ctx::S_IMG2, Ctx::S_VIDT, &d_it, &d_vt)) return rc;
+    SCR(S_SPREAD, 4 * (size_t)(nq + nt), d_sq);
+    d_st = (int32_t*)d_sq + nq;
+    if (int rc = hvd_dev_vpdq_frame_spread_cross(d_iq, nq, d_vq, d_it, nt, d_vt, max_dist, 0, d_sq, d_st)) return rc;
+    HIP_TRY(hipMemcpyAsync(out_spread_q, d_sq, 4 * (size_t)nq, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(out_spread_t, d_st, 4 * (size_t)nt, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
+}
+
 /* ---- device-resident forms: hashes / images / maps already in HBM (BASELINE config 5) ---- */
 
 int hvd_dev_video_of_frames(const void* d_offsets, int64_t V, int64_t n, void* d_out_video) {
@@ -1111,6 +1139,29 @@ int hvd_dev_vpdq_frame_spread(const void* d_img, int64_t n, const void* d_video,
             return rc;
         HIP_TRY(hvd::launch_keys_to_spread(k.d_src, k.n_src, (unsigned long long)n, (int32_t*)d_out_spread, g.stream));
     }
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
+}
+
+int hvd_dev_vpdq_frame_spread_cross(const void* d_img_q, int64_t nq, const void* d_video_q, const void* d_img_t, int64_t nt,
+                                    const void* d_video_t, int max_dist, int accumulate, void* d_spread_q, void* d_spread_t) {
+    if (int rc = need_ready()) return rc;
+    if (!d_spread_q && !d_spread_t) return fail(HVD_ERR_ARG, "d_spread_q and d_spread_t are both NULL");
+    if (nq < 0 || nt < 0 || nq >= (1ll << 32) - 1 || nt >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "set size out of range");
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    const bool empty = nq == 0 || nt == 0;
+    if (!empty && (!d_img_q || !d_img_t || !d_video_q || !d_video_t)) return fail(HVD_ERR_ARG, "NULL image / video map");
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    // the key stage of the rectangular search on this context alone; no pair map is built, the last search's stays
+    VmKeys k;
+    if (!empty)
+        if (int rc = vmatch_keys({d_img_q, (uint32_t)nq, d_img_t, (uint32_t)nt, true, (const int32_t*)d_video_q,
+                                  (const int32_t*)d_video_t, nullptr, nullptr, max_dist, 0, 1},
+                                 &k))
+            return rc;
+    // (nothing to compare: k is empty, the launcher zeroes the outputs unless it accumulates and launches nothing else)
+    HIP_TRY(hvd::launch_keys_to_spread_cross(k.d_src, k.n_src, (unsigned long long)nq, (unsigned long long)nt, accumulate != 0,
+                                             (int32_t*)d_spread_q, (int32_t*)d_spread_t, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     return HVD_OK;
 }

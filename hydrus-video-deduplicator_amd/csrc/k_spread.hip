@@ -2,6 +2,8 @@
 // intro, an end card) are found from the key set of the video search and deleted before it.
 //   * k_keys_to_spread   key set (frame f, video v) of hvd_devhash.h -> spread[f] = the number of keys frame f owns = the
 //                        number of OTHER videos f occurs in (keys are distinct, frames of f's own video are never compared);
+//   * k_keys_to_spread_cross  the key set of the rectangular search (new batch Q x library T), both sides: the
+//                        number of T's videos a frame of Q occurs in, and the number of Q's videos a frame of T occurs in;
 //   * k_common_rule      per video: count its frames with spread > max_videos, decide whether the video is an intro carrier
 //                        (it has common frames and they are at most max_share per cent of it), write keep[f];
 //   * k_gather_kept_i32  stream compaction of an int32 array by the keep flags (the positions of a library ride along with
@@ -29,6 +31,23 @@ __global__ __launch_bounds__(256) void k_keys_to_spread(const unsigned long long
         if (k == kEmptyKey || hvd::vkey_side(k) != 0u) continue;
         const uint32_t f = hvd::vkey_frame(k);
         if (f < n) atomicAdd(&spread[f], 1);
+    }
+}
+
+// The rectangular form's key set, both sides read: a side-0 key (query frame f, target video) adds one to
+// spread_q[f], a side-1 key (target frame g, query video) one to spread_t[g]. Either output may be null: that side is skipped.
+// The counts are ADDED to what the arrays hold (the launcher zeroes them, or not). src / n_src as k_keys_to_spread.
+__global__ __launch_bounds__(256) void k_keys_to_spread_cross(const unsigned long long* __restrict__ src, unsigned long long n_src,
+                                                              unsigned long long nq, unsigned long long nt,
+                                                              int32_t* __restrict__ spread_q, int32_t* __restrict__ spread_t) {
+    for (unsigned long long idx = (unsigned long long)blockIdx.x * 256u + threadIdx.x; idx < n_src;
+         idx += (unsigned long long)gridDim.x * 256u) {
+        const unsigned long long k = src[idx];
+        if (k == kEmptyKey) continue;
+        const bool target = hvd::vkey_side(k) != 0u;
+        int32_t* const out = target ? spread_t : spread_q;
+        const uint32_t f = hvd::vkey_frame(k);
+        if (out != nullptr && f < (target ? nt : nq)) atomicAdd(&out[f], 1);
     }
 }
 
@@ -93,6 +112,24 @@ hipError_t launch_keys_to_spread(const unsigned long long* d_src, unsigned long 
     unsigned long long blocks = (n_src + 255ull) / 256ull;
     if (blocks > 16384ull) blocks = 16384ull;  // grid-stride
     hipLaunchKernelGGL(k_keys_to_spread, dim3((unsigned)blocks), dim3(256), 0, s, d_src, n_src, n, d_spread);
+    return hipGetLastError();
+}
+
+// d_spread_q: int32[nq], d_spread_t: int32[nt]; either may be null. Zeroed here on the same stream unless `accumulate`.
+hipError_t launch_keys_to_spread_cross(const unsigned long long* d_src, unsigned long long n_src, unsigned long long nq,
+                                       unsigned long long nt, bool accumulate, int32_t* d_spread_q, int32_t* d_spread_t,
+                                       hipStream_t s) {
+    if (!accumulate) {
+        if (d_spread_q != nullptr && nq > 0)
+            if (hipError_t e = hipMemsetAsync(d_spread_q, 0, 4 * (size_t)nq, s)) return e;
+        if (d_spread_t != nullptr && nt > 0)
+            if (hipError_t e = hipMemsetAsync(d_spread_t, 0, 4 * (size_t)nt, s)) return e;
+    }
+    if (n_src == 0 || nq == 0 || nt == 0 || (d_spread_q == nullptr && d_spread_t == nullptr)) return hipSuccess;
+    unsigned long long blocks = (n_src + 255ull) / 256ull;
+    if (blocks > 16384ull) blocks = 16384ull;  // grid-stride
+    hipLaunchKernelGGL(k_keys_to_spread_cross, dim3((unsigned)blocks), dim3(256), 0, s, d_src, n_src, nq, nt, d_spread_q,
+                       d_spread_t);
     return hipGetLastError();
 }
 

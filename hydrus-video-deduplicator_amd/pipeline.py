@@ -20,6 +20,7 @@ from __future__ import annotations
 import ctypes as C
 import threading
 import time
+from collections import namedtuple
 
 import numpy as np
 
@@ -226,6 +227,11 @@ def _default_max_dist(max_dist: int | None) -> int:
     return vpdq.frame_max_dist(search.DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
 
 
+# What DeviceLibrary.ingest returns: the union library with its spread attached, the records with at least one
+# new video (union numbering), the frames the common-frame rule dropped per video of the union.
+Ingest = namedtuple("Ingest", "library records dropped")
+
+
 class DeviceLibrary:
     """A video library resident in HBM: kept frame hashes (CSR by video), their FP4 image and the
     frame -> video map -- the operand of the video-level search."""
@@ -238,6 +244,8 @@ class DeviceLibrary:
         self.d_positions = None  # int32 per kept frame: its raw index inside its video (from_raw_hashes(positions=True))
         self._position_limit = 0
         self._lengths = None
+        self.d_spread = None  # int32 per kept frame: the spread `attach_spread` (or `ingest`) left, at spread_max_dist
+        self.spread_max_dist = None
 
     @classmethod
     def from_raw_hashes(cls, d_hashes_ptr: int, d_quality_ptr: int, n: int, raw_offsets: np.ndarray,
@@ -473,12 +481,164 @@ class DeviceLibrary:
             (int(lengths.max()) if lengths.size else 0)
         return library, (lengths - library.lengths()).astype(np.int64)
 
+    # ---- new files against this library ----
+
+    def attach_spread(self, max_dist: int | None = None) -> DeviceBuffer:
+        """`spread(max_dist)`, kept: d_spread / spread_max_dist carry it from call to call (`ingest` starts from it) and
+        `free` frees it. -> the buffer, which stays this library's."""
+        max_dist = _default_max_dist(max_dist)
+        d_spread = self.spread(max_dist)
+        if self.d_spread is not None:
+            self.d_spread.free()
+        self.d_spread, self.spread_max_dist = d_spread, max_dist
+        return d_spread
+
+    def spread_cross(self, other: "DeviceLibrary", max_dist: int | None = None) -> tuple[DeviceBuffer, DeviceBuffer]:
+        """hvd_dev_vpdq_frame_spread_cross of `other` (the new batch, query side) against this library (target side):
+        -> (sq, st), DeviceBuffers that are the caller's to free. sq: int32 per frame of `other`, the number of this library's
+        videos it occurs in; st: int32 per frame of this library, the number of `other`'s videos it occurs in. The records of
+        the last search stay valid for hvd_dev_vpdq_emit_again."""
+        lib = _lib.ensure()
+        max_dist = _default_max_dist(max_dist)
+        with _DeviceScope() as scope:
+            d_sq = scope.keep(DeviceBuffer(4 * max(other.n_frames, 1)))
+            d_st = scope.keep(DeviceBuffer(4 * max(self.n_frames, 1)))
+            if max_dist < 0 or other.n_frames == 0 or self.n_frames == 0:
+                d_sq.zero()
+                d_st.zero()
+            else:
+                _lib.check(lib.hvd_dev_vpdq_frame_spread_cross(other.image().ptr, other.n_frames, other.d_video.ptr,
+                                                               self.image().ptr, self.n_frames, self.d_video.ptr, max_dist, 0,
+                                                               d_sq.ptr, d_st.ptr))
+        return d_sq, d_st
+
+    def match_library(self, other: "DeviceLibrary", max_dist: int | None = None, cap: int | None = None) -> np.ndarray:
+        """hvd_dev_vpdq_match_videos_cross of another resident library (query side) against this one (target side), no
+        exclusion maps: VMATCH_DTYPE records (a = other's video, b = this library's video) sorted by (a, b); the same record
+        buffer, cap and emit-again retry as match_queries."""
+        lib = _lib.ensure()
+        max_dist = _default_max_dist(max_dist)
+        if max_dist < 0 or other.n_frames == 0 or self.n_frames == 0:
+            return np.zeros(0, dtype=VMATCH_DTYPE)
+        cap = max(4096, other.n_videos) if cap is None else int(cap)
+        return _search_records(lambda d_out, cap_, d_cnt: lib.hvd_dev_vpdq_match_videos_cross(
+            other.image().ptr, other.n_frames, other.d_video.ptr, None, self.image().ptr, self.n_frames, self.d_video.ptr, None,
+            max_dist, 0, 1, d_out, cap_, d_cnt), cap)
+
+    def _check_extension(self, other: "DeviceLibrary") -> None:
+        """ValueError unless `extended(other)` can be built; touches nothing on the device."""
+        if (self.d_positions is None) != (other.d_positions is None):
+            raise ValueError("positions on one side only: both libraries carry them or neither does")
+        if self.n_frames + other.n_frames >= (1 << 32) - 1 or self.n_videos + other.n_videos >= (1 << 31):
+            raise ValueError("the union is over the library limits: frames below 2^32 - 1, videos below 2^31")
+
+    def extended(self, other: "DeviceLibrary") -> "DeviceLibrary":
+        """The union U = this library || other as a NEW library: this library's videos keep their numbers, other's video v
+        becomes n_videos + v, frames likewise. Both sources are untouched and stay the caller's. Device-to-device copies of
+        the hashes (and positions: carried if both have them, absent if neither), a host-built CSR (V + 1 numbers go up),
+        hvd_dev_video_of_frames for the map."""
+        self._check_extension(other)
+        lib = _lib.ensure()
+        nT, nQ, VT = self.n_frames, other.n_frames, self.n_videos
+        n, V = nT + nQ, VT + other.n_videos
+        offsets = np.concatenate([self.offsets(), other.offsets()[1:] + nT]).astype(np.int64)
+        with _DeviceScope() as scope:
+            d_h = scope.keep(DeviceBuffer(32 * max(n, 1)))
+            d_off = scope.keep(DeviceBuffer.from_array(offsets))
+            d_vid = scope.keep(DeviceBuffer(4 * max(n, 1)))
+            d_pos = scope.keep(DeviceBuffer(4 * max(n, 1))) if self.d_positions is not None else None
+            for d_dst, src_t, src_q, size in ((d_h, self.d_hashes, other.d_hashes, 32), (d_pos, self.d_positions, other.d_positions, 4)):
+                if d_dst is None:
+                    continue
+                if nT:
+                    _lib.check(lib.hvd_memcpy_d2d(d_dst.ptr, src_t.ptr, size * nT))
+                if nQ:
+                    _lib.check(lib.hvd_memcpy_d2d(d_dst.ptr + size * nT, src_q.ptr, size * nQ))
+            _lib.check(lib.hvd_dev_video_of_frames(d_off.ptr, V, n, d_vid.ptr))
+            _lib.check(lib.hvd_dev_sync())  # the sources are the caller's to free from here on
+        library = DeviceLibrary(d_h, d_off, d_vid, n, V)
+        library.d_positions = d_pos
+        library._position_limit = max(self._position_limit, other._position_limit)
+        return library
+
+    def _spread_at(self, max_dist: int, scope: _DeviceScope) -> DeviceBuffer:
+        """The attached spread if it was taken at max_dist, else a fresh one that the scope frees."""
+        if self.d_spread is not None and self.spread_max_dist == max_dist:
+            return self.d_spread
+        return scope.temp(self.spread(max_dist))
+
+    def _kept_by(self, d_keep_ptr: int) -> "DeviceLibrary":
+        """hvd_dev_compact_kept of this library on keep flags (bound 1): hashes, CSR and map of what is left; no positions."""
+        lib = _lib.ensure()
+        n, V = self.n_frames, self.n_videos
+        kept = C.c_int64(0)
+        with _DeviceScope() as scope:
+            d_h, d_vid = (scope.keep(DeviceBuffer(size * max(n, 1))) for size in (32, 4))
+            d_off = scope.keep(DeviceBuffer(8 * (V + 1)))
+            _lib.check(lib.hvd_dev_compact_kept(self.d_hashes.ptr, d_keep_ptr, n, self.d_offsets.ptr, V, 1, d_h.ptr, d_off.ptr,
+                                                d_vid.ptr, C.byref(kept)))
+        return DeviceLibrary(d_h, d_off, d_vid, kept.value, V)
+
+    def ingest(self, new: "DeviceLibrary", max_videos: int | None = None, max_share: int = 50,
+               max_dist: int | None = None) -> Ingest:
+        """A batch of new videos against this library, with the common-frame filter of DESIGN 4.13 over the union and without
+        its O(n^2) passes over what was already there (DESIGN 4.17). U = this library || new (`extended`);
+        spread_U = (spread_T + st) || (spread_Q + sq): this library's spread comes from `attach_spread` if it was taken at
+        max_dist (else it is computed), new's likewise, and ONE hvd_dev_vpdq_frame_spread_cross call adds st and sq on top. With
+        max_videos set, the rule (hvd_dev_common_frames) runs on U and each side is compacted by its slice of the keep flags.
+        -> Ingest(library = U with spread_U attached: the next ingest starts from it; records = those of the video search on
+        the filtered U that hold at least one new video (b >= this library's n_videos), in U's numbering, a < b, sorted by
+        (a, b): new x old by `match_library`, new x new by `match_videos`; old x old pairs are neither re-judged nor returned;
+        dropped int64[V_U]). max_videos=None: no frame is dropped. This library and `new` are untouched and stay the
+        caller's; the result's library is the caller's to free."""
+        if max_videos is not None:
+            max_videos, max_share = search.check_common_rule(max_videos, max_share)
+        else:
+            search.check_common_rule(0, max_share)  # (unused without the rule, but never accepted broken)
+        self._check_extension(new)
+        lib = _lib.ensure()
+        max_dist = _default_max_dist(max_dist)
+        nT, nQ, VT, VQ = self.n_frames, new.n_frames, self.n_videos, new.n_videos
+        n, V = nT + nQ, VT + VQ
+        with _DeviceScope() as scope:
+            union = scope.keep(self.extended(new))
+            d_spread_t, d_spread_q = self._spread_at(max_dist, scope), new._spread_at(max_dist, scope)
+            d_su = DeviceBuffer(4 * max(n, 1))
+            union.d_spread, union.spread_max_dist = d_su, max_dist  # (freed with the union)
+            if nT:
+                _lib.check(lib.hvd_memcpy_d2d(d_su.ptr, d_spread_t.ptr, 4 * nT))
+            if nQ:
+                _lib.check(lib.hvd_memcpy_d2d(d_su.ptr + 4 * nT, d_spread_q.ptr, 4 * nQ))
+            if max_dist >= 0 and nT and nQ:
+                _lib.check(lib.hvd_dev_vpdq_frame_spread_cross(new.image().ptr, nQ, new.d_video.ptr, self.image().ptr, nT,
+                                                               self.d_video.ptr, max_dist, 1, d_su.ptr + 4 * nT, d_su.ptr))
+            else:
+                _lib.check(lib.hvd_dev_sync())  # the copies read buffers the scope frees
+            old, fresh = self, new
+            dropped = np.zeros(V, dtype=np.int64)
+            if max_videos is not None:
+                d_keep = scope.temp(DeviceBuffer(4 * max(n, 1)))
+                _lib.check(lib.hvd_dev_common_frames(d_su.ptr, union.d_offsets.ptr, V, n, max_videos, max_share, d_keep.ptr))
+                old = scope.temp(self._kept_by(d_keep.ptr))
+                fresh = scope.temp(new._kept_by(d_keep.ptr + 4 * nT))
+                dropped = np.concatenate([self.lengths() - old.lengths(), new.lengths() - fresh.lengths()]).astype(np.int64)
+            cross = old.match_library(fresh, max_dist)
+            among = fresh.match_videos(max_dist)
+            records = np.zeros(cross.size + among.size, dtype=VMATCH_DTYPE)
+            head, tail = records[:cross.size], records[cross.size:]
+            head["a"], head["b"], head["q_hits"], head["t_hits"] = cross["b"], cross["a"] + VT, cross["t_hits"], cross["q_hits"]
+            tail["a"], tail["b"], tail["q_hits"], tail["t_hits"] = among["a"] + VT, among["b"] + VT, among["q_hits"], among["t_hits"]
+            records = records[np.lexsort((records["b"], records["a"]))]
+        return Ingest(union, records, dropped)
+
     def free(self) -> None:
-        for b in (self.d_hashes, self.d_offsets, self.d_video, self.d_img, self.d_positions):
+        for b in (self.d_hashes, self.d_offsets, self.d_video, self.d_img, self.d_positions, self.d_spread):
             if b is not None:
                 b.free()
         self.d_img = None
         self.d_positions = None
+        self.d_spread = None
+        self.spread_max_dist = None
 
 
 class DeviceQueries(DeviceLibrary):

@@ -927,6 +927,25 @@ def frame_spread(frames: np.ndarray, offsets: np.ndarray, max_dist: int | None =
     return spread
 
 
+def frame_spread_cross(frames_q: np.ndarray, offsets_q: np.ndarray, frames_t: np.ndarray, offsets_t: np.ndarray,
+                       max_dist: int | None = None) -> tuple[np.ndarray, np.ndarray]:
+    """New files against the library: -> (spread_q, spread_t), both int32. spread_q[f], per frame of the new
+    batch Q: the number of videos of the library T that hold at least one frame within max_dist of it; spread_t[g], per frame
+    of T: the number of videos of Q likewise (hvd_vpdq_frame_spread_cross: the compare and the key set of match_videos_cross
+    without its fold). Q's frames are never compared with Q's, nor T's with T's: with `frame_spread` of each side alone they
+    add up to the spread of the union. Arguments as `match_videos_cross`; max_dist: default the video search's tolerance."""
+    frames_q, offsets_q, _ = _library(frames_q, offsets_q)
+    frames_t, offsets_t, _ = _library(frames_t, offsets_t)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
+    spread_q, spread_t = np.zeros(frames_q.shape[0], dtype=np.int32), np.zeros(frames_t.shape[0], dtype=np.int32)
+    if max_dist < 0 or frames_q.shape[0] == 0 or frames_t.shape[0] == 0:
+        return spread_q, spread_t
+    _lib.check(_lib.ensure().hvd_vpdq_frame_spread_cross(_ptr(frames_q), offsets_q.ctypes.data, offsets_q.size - 1, _ptr(frames_t),
+                                                         offsets_t.ctypes.data, offsets_t.size - 1, max_dist,
+                                                         spread_q.ctypes.data, spread_t.ctypes.data))
+    return spread_q, spread_t
+
+
 def check_common_rule(max_videos, max_share) -> tuple[int, int]:
     """The two parameters of the common-frame rule as ints, or ValueError. max_videos has no default on purpose: nobody has
     measured a value that suits real libraries."""
@@ -984,3 +1003,39 @@ def without_common_frames(video_hashes, max_videos: int, max_share: int = 50, ma
     before = np.concatenate([[0], np.cumsum(drop, dtype=np.int64)])
     dropped = before[offsets[1:]] - before[offsets[:-1]]
     return CommonFrames(hashes, kept_pos, dropped, spread)
+
+
+# ------------------------------------------------ new files against the library: filtered ingest ------
+
+NewDuplicates = namedtuple("NewDuplicates", "pairs dropped spread")
+
+
+def find_new_duplicates(library_hashes, new_hashes, threshold: float = 50.0, policy: str | None = None,
+                        max_videos: int | None = None, max_share: int = 50, max_dist: int | None = None) -> NewDuplicates:
+    """The steady state after the first run: a batch of new videos against the library already searched, with the common-frame
+    filter over both (pipeline.DeviceLibrary.ingest on two uploaded libraries). library_hashes / new_hashes: sequences of
+    VpdqHash / bytes; the union numbers the library's videos first, then the new ones. -> NewDuplicates(pairs: the sorted
+    (a, b), a < b, b a new video, that `find_potential_duplicates` reports on the filtered union -- pairs of two old videos
+    are neither re-judged nor returned; dropped: int64 per video of the union; spread: int32 per frame of the union, as
+    `frame_spread` of the union gives it). max_videos=None: no frame is dropped; max_videos / max_share as
+    `without_common_frames`."""
+    from . import pipeline
+
+    check_common_rule(0 if max_videos is None else max_videos, max_share)
+    frames_t, offsets_t, lengths_t = pack_hashes(library_hashes)
+    frames_q, offsets_q, lengths_q = pack_hashes(new_hashes)
+    old = pipeline.DeviceLibrary.from_host(frames_t, offsets_t)
+    try:
+        new = pipeline.DeviceLibrary.from_host(frames_q, offsets_q)
+        try:
+            union, records, dropped = old.ingest(new, max_videos, max_share, max_dist)
+            try:
+                spread = union.d_spread.to_array(np.int32, union.n_frames)
+            finally:
+                union.free()
+        finally:
+            new.free()
+    finally:
+        old.free()
+    pairs = similar_video_pairs(records, np.concatenate([lengths_t, lengths_q]) - dropped, threshold, policy)
+    return NewDuplicates([(int(a), int(b)) for a, b in pairs], dropped, spread)

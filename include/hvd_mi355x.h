@@ -40,7 +40,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -273,6 +273,17 @@ int hvd_vpdq_frame_spread(const uint8_t* frames, const int64_t* offsets, int64_t
 int hvd_vpdq_match_videos_cross(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* ids_q,
                                 const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* ids_t,
                                 int max_dist, hvd_vmatch* out, int64_t cap, int64_t* out_count);
+
+/* New files against the library: the rectangular spread. Q is a new batch (frames_q / offsets_q / VQ), T the
+ * library (frames_t / offsets_t / VT), both as hvd_vpdq_match_videos takes them; their video sets are disjoint.
+ * out_spread_q[f] (int32 per frame of Q) = the number of videos of T that hold at least one frame within max_dist of f;
+ * out_spread_t[g] (int32 per frame of T) = the number of videos of Q that hold at least one frame within max_dist of g. Two
+ * matching frames of one video count once; frames of Q are never compared with frames of Q, nor T's with T's. With the
+ * symmetric spreads of Q and of T alone (hvd_vpdq_frame_spread) they add up to the spread of the union T || Q. max_dist in
+ * [0, 127]. Both sides are uploaded to the slots hvd_vpdq_match_videos_cross uses, then hvd_dev_vpdq_frame_spread_cross; under
+ * a device group it runs on the calling thread's current context alone. */
+int hvd_vpdq_frame_spread_cross(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const uint8_t* frames_t,
+                                const int64_t* offsets_t, int64_t VT, int max_dist, int32_t* out_spread_q, int32_t* out_spread_t);
 
 /* Time alignment of listed video pairs: is video a an excerpt of video b (or b of a), and where. The rule,
  * integers only. Position p(f) of a frame: positions[f] if given (int32 per frame of the library; non-negative, strictly
@@ -793,6 +804,17 @@ int hvd_dev_common_frames(const void* d_spread, const void* d_offsets, int64_t V
  * library through the compaction hvd_dev_compact_kept does on its hashes. Enqueued on the library stream, no host
  * synchronisation; library-owned scratch. */
 int hvd_dev_gather_kept_i32(const void* d_in, const void* d_keep, int64_t n, void* d_out);
+/* Device-resident form of hvd_vpdq_frame_spread_cross: operands as hvd_dev_vpdq_match_videos_cross without exclusion maps,
+ * d_spread_q int32[nq], d_spread_t int32[nt]. The compare and the key set of that search without its fold (rank 0 of 1): a
+ * side-0 key (query frame f, target video) adds one to d_spread_q[f], a side-1 key (target frame g, query video) one to
+ * d_spread_t[g]. Either output may be NULL (that side is skipped), not both. accumulate == 0: the outputs are zeroed first;
+ * otherwise the counts are added to what the arrays hold (spread_T + st in one pass). nq == 0 or nt == 0: the
+ * outputs are zeroed unless accumulate, nothing else is launched. No pair map is built: hvd_dev_vpdq_emit_again still returns
+ * the last search. Runs on the calling thread's context alone, is serialised with the video searches and synchronises the
+ * library stream before returning. HVD_ERR_ARG (nothing launched): both outputs NULL, sizes out of range, max_dist outside
+ * [0, 127], an image or video map NULL while both sides are non-empty. */
+int hvd_dev_vpdq_frame_spread_cross(const void* d_img_q, int64_t nq, const void* d_video_q, const void* d_img_t, int64_t nt,
+                                    const void* d_video_t, int max_dist, int accumulate, void* d_spread_q, void* d_spread_t);
 /* Query library x target library form (VpTreeManager.search_file for a batch, db/vptree.py:865-902).
  * d_excl_q / d_excl_t (both or neither): int32 per frame, frames with equal values are not compared. */
 int hvd_dev_vpdq_match_videos_cross(const void* d_img_q, int64_t nq, const void* d_video_q, const void* d_excl_q,
