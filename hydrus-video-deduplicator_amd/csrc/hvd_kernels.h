@@ -120,6 +120,9 @@ hipError_t index_reserve(int ctx_id, uint32_t n);
 // returns at once unless the probe's gate is set, every kernel of the second unless the decision is.
 hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const IndexRule& q, hipStream_t s);
 hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t r, hipStream_t s);
+// the partitions that fit LDS, ordered whole (k_index_order.hip): launched by launch_index_decide behind the partition pass
+hipError_t launch_index_order(const uint2* rec, uint32_t n, const uint32_t* ptotal, const uint32_t* pbase, uint32_t* cnt, uint32_t* off,
+                              uint32_t* hw, uint32_t* rows, const uint32_t* d_select, hipStream_t s);
 // the join's grid for n hashes on the current device (or what "index_join_wgs" sets): the same for every n <= 2^20
 hipError_t index_join_workgroups(uint32_t n, uint32_t* wgs);
 void index_release();

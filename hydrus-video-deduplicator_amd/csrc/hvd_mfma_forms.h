@@ -59,7 +59,7 @@ inline uint32_t fp4_rows_padded(uint32_t n) { return (uint32_t)fp4_rows_padded64
 
 // Column chunk of a pass over n_pad columns whose rows make row_blocks workgroup rows: about target_tiles tiles in all, a
 // chunk of 256 .. cap columns in whole super-panels -- and never more than 65535 chunks (grid.y).
-// The self pass: (8192, "mfma_col_chunk_max"); the rectangle: (4096, 4096), enough tiles to fill the chip even when nq is small.
+// The self pass: (8192, "mfma_col_chunk_max" -- or kSelfCapBehindIndex, below); the rectangle: (4096, 4096), enough tiles to fill the chip even when nq is small.
 constexpr uint32_t mfma_col_chunk(uint64_t n_pad, uint64_t row_blocks, uint32_t target_tiles, uint32_t cap) {
     if (row_blocks < 1) row_blocks = 1;
     const uint64_t want_cb = (target_tiles + row_blocks - 1) / row_blocks;  // (>= 1)
@@ -71,6 +71,14 @@ constexpr uint32_t mfma_col_chunk(uint64_t n_pad, uint64_t row_blocks, uint32_t 
     return (uint32_t)chunk;
 }
 constexpr uint32_t kSelfTargetTiles = 8192, kRectTargetTiles = 4096, kRectColChunkMax = 4096;
+// The self cap of the auto variant's three launches BEHIND AN INDEX LAUNCH (k_hamming_mfma.hip: launch_auto). Such a pass almost
+// always runs on the index, and its matrix-core launches are grids of workgroups that return at once: at 1 M hashes 977 x 16,
+// 977 x 16 and 1954 x 16 of them instead of 977 x 123 twice and 1954 x 123 (19 us per pass instead of 108; at 10 M hashes
+// 1.3 ms instead of 10.0). Up to ~262 000 hashes the target-tiles rule yields chunks of at most 8192 and nothing differs from the knob's
+// default. The cap is what a pass that DOES fall back may pay for long tiles and a coarser cut of the triangle
+// (profiles/r21_index_fallback_time.jsonl: 1 M hashes, 5 % of them in one bucket, against the knob's 8192): no cap (chunks
+// of 111 232) +6.0 %, 65536 +2.4 %, 32768 +0.0 % -- the coarsest within 3 % plus the spread of the parent's own rounds.
+constexpr uint32_t kSelfCapBehindIndex = 65536;
 
 // Geometry of one pass: rows = the nq queries of a rectangle, the n hashes themselves of a self pass; columns = the n hashes.
 struct MfmaGeometry {

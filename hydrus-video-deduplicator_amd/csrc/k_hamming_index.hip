@@ -12,6 +12,10 @@
 //                       than csz entries is cut into several, so that no workgroup sets the length of the passes below)
 //   k_index_partition   the tiles again: rank from a returning LDS atomic, record {row, key | sibling key << 16} -> its
 //                       partition (short runs): the record carries the whole 32-bit word that holds block b
+//   k_index_order       (k_index_order.hip) one workgroup per partition of at most kOrderMax records: low-byte digits counted,
+//                       scanned and ranked in LDS, the partition laid out there in final order and written out as two
+//                       contiguous streams -- cnt, off, hw and rows of that partition in one kernel. The three chunk
+//                       kernels below skip what it took and serve the larger partitions:
 //   k_index_count       one workgroup per chunk: low-byte digits counted in 256 LDS bins
 //   k_index_offsets     one workgroup per partition: the chunks' counts -> per-key counts, off[b][h * 256 ..], chunk cursors
 //   k_index_stats       a few hundred workgroups stride over the (block, key)s: exact candidates and the longest work item,
@@ -37,11 +41,13 @@
 #include <mutex>
 #include <type_traits>
 
+#include "hvd_index_dev.h"
 #include "hvd_kernels.h"
 
 namespace {
 
-constexpr uint32_t kBlocks = 16, kKeys = 65536;
+using namespace hvd::index_dev;  // kBlocks, kKeys, kParts, orders_whole, lds_add, wave_incl_scan: shared with k_index_order.hip
+
 constexpr uint32_t kWavePairs = 64;  // a wave's pair buffer in LDS (a drain emits at most 64); full -> one atomic reserves room for all of it
 constexpr uint32_t kXB = 16;         // x entries per scalar batch of the join: one 64-byte scalar load, one survivor mask per lane
 constexpr uint32_t kQueue = 128;     // a wave's survivor queue in LDS (a ring): a push adds at most 64, 64 pending are drained at once
@@ -56,22 +62,10 @@ __device__ __forceinline__ void load_words(const uint4* __restrict__ db, uint32_
     w[4] = h1.x; w[5] = h1.y; w[6] = h1.z; w[7] = h1.w;
 }
 
-constexpr uint32_t kParts = kBlocks * 256u;       // partitions: (block, high byte of the key)
 constexpr uint32_t kTile = 4096u;                   // hashes per tile: a tile's run in a partition is ~16 records = 128 B
 constexpr uint32_t kTileThreads = 1024u;            // 16 waves per workgroup, kTile / kTileThreads hashes per thread
 constexpr uint32_t kMinChunk = 4096u;               // a chunk: at most max(kMinChunk, 2 x the mean partition) entries ...
 constexpr uint32_t kMaxChunks = kParts + 2048u;     // ... so a pass never has more chunks than this (index_chunk)
-
-__device__ __forceinline__ uint32_t lds_add(uint32_t* p) {
-    return __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, uint32_t lane) {
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(v, d);
-        if (lane >= (uint32_t)d) v += y;
-    }
-    return v;
-}
 
 // tcnt[part][tile] = the tile's hashes whose key of block (part >> 8) has the high byte (part & 255)
 __global__ __launch_bounds__(kTileThreads) void k_index_tile_count(const uint4* __restrict__ db, uint32_t n, uint32_t ntiles,
@@ -179,7 +173,8 @@ __global__ __launch_bounds__(kTileThreads) void k_index_partition(const uint4* _
     }
 }
 
-// A chunk's place: partition, block, and its entries [lo, hi) of the partition's records.
+// A chunk's place: partition, block, and its entries [lo, hi) of the partition's records. The chunk kernels serve the
+// partitions that k_index_order (k_index_order.hip) left: those of more than kOrderMax records.
 struct Chunk {
     uint32_t p, b, lo, hi;
     size_t at;  // the partition's first record inside rec / its first position inside hw and rows (block included)
@@ -189,9 +184,11 @@ __device__ __forceinline__ bool chunk_of(uint32_t c, uint32_t n, uint32_t csz, c
                                          const uint32_t* __restrict__ chunk_p, Chunk* q) {
     if (c >= pfirst[kParts]) return false;
     q->p = chunk_p[c];
+    const uint32_t total = ptotal[q->p];
+    if (orders_whole(total)) return false;  // k_index_order has ordered this partition
     q->b = q->p >> 8;
     q->lo = (c - pfirst[q->p]) * csz;
-    q->hi = min(ptotal[q->p], q->lo + csz);
+    q->hi = min(total, q->lo + csz);
     q->at = (size_t)q->b * n + pbase[q->p];
     return true;
 }
@@ -217,11 +214,13 @@ __global__ __launch_bounds__(256) void k_index_count(const uint2* __restrict__ r
 
 // One workgroup per partition (b, h), thread t = key h * 256 + t: cnt[b][key] (the statistics read it), off[b][key], and
 // ccount[chunk][t] becomes the chunk's cursor: the position inside block b of its first entry with that low byte.
-__global__ __launch_bounds__(256) void k_index_offsets(uint32_t n, const uint32_t* __restrict__ pbase, const uint32_t* __restrict__ pfirst,
-                                                       uint32_t* __restrict__ ccount, uint32_t* __restrict__ cnt, uint32_t* __restrict__ off,
+__global__ __launch_bounds__(256) void k_index_offsets(uint32_t n, const uint32_t* __restrict__ ptotal, const uint32_t* __restrict__ pbase,
+                                                       const uint32_t* __restrict__ pfirst, uint32_t* __restrict__ ccount,
+                                                       uint32_t* __restrict__ cnt, uint32_t* __restrict__ off,
                                                        const uint32_t* __restrict__ select) {
     __shared__ uint32_t wsum[4];
     if (select[hvd::kSelIdxGate] == 0u) return;
+    if (orders_whole(ptotal[blockIdx.x])) return;  // k_index_order has written this partition's counts and offsets
     const uint32_t p = blockIdx.x, b = p >> 8, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t c0 = pfirst[p], c1 = min(pfirst[p + 1u], kMaxChunks);
     uint32_t total = 0;
@@ -696,18 +695,24 @@ IndexRule index_rule(const AllPairsArgs& a, uint32_t r) {
     // for 2.075e9 candidates = 0.31 ps each; the counting sort, the statistics and the place pass -- every kernel between
     // probe and join -- 0.352 ms, of which ~0.03 ms do not depend on n (the scans over 4096 partitions, the grid of 6144
     // chunks): 0.32 ns per hash, kept at 0.33, and those 30 us next to the 40 us of launches. To re-derive after a change
-    // of these kernels: ps_cand = join time / candidates, ps_hash = (every kernel between probe and join - 30 us) / n,
-    // ps_crit from the crowded DB of scripts/gpu_index_join_time.py (profiles/r17_index_join_time.jsonl): 200 000 hashes,
+    // of these kernels: ps_cand = join time / candidates, ps_hash = (every kernel between probe and join - what of them
+    // does not depend on n) / n, ps_crit from the crowded DB of scripts/gpu_index_join_time.py (profiles/r17_index_join_time.jsonl): 200 000 hashes,
     // 5 000 of them in one bucket, a longest walk of 25.15e6 pairs, 8.07 .. 8.13 ms per call of which ~0.2 ms are what
     // the other terms price and ~0.4 ms copies: 0.30 ns per pair, 19 ns per step of 64 -- rounded up, which errs towards
     // the matrix cores. The wave that walks the crowded bucket also walks the other 15 items of its sequence, ~50 us at
-    // 1 M: the terms ADD, which prices that)
+    // 1 M: the terms ADD, which prices that.
+    // With the partitions that fit LDS ordered whole (k_index_order.hip; profiles/r21_index_kernel_stats_after.csv): every
+    // kernel between probe and join 0.245 ms, of which 0.025 ms do not depend on n (the two scans and the three chunk
+    // kernels, whose workgroups all return): 0.22 ns per hash. That is the price up to ~1.4 M uniform hashes, which is where
+    // the rule decides anything: beyond, the partitions outgrow kOrderMax and a hash costs the 0.33 ns of the chunk kernels
+    // again, 1 ms more at 10 M than this term says, in a pass that wins by a factor of forty. fixed_ns: those 25 us, 43 us
+    // of launches (one more) and the three fall-back launches on their coarse grid, 19 us: 87 us, rounded up)
     q.fs_mfma_fetch = 36.0f;
     q.fs_mfma_other = 40.0f;
     q.ps_cand = 0.31f;
-    q.ps_hash = 330.0f;
+    q.ps_hash = 220.0f;
     q.ps_crit = 320.0f;
-    q.fixed_ns = 70000.0f;
+    q.fixed_ns = 90000.0f;
     return q;
 }
 
@@ -746,9 +751,10 @@ hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const 
     hipLaunchKernelGGL(k_index_scan_rows, dim3(kParts / 4u), dim3(256), 0, s, p.tcnt, tiles, p.ptotal, d_select);
     hipLaunchKernelGGL(k_index_scan_parts, dim3(1), dim3(1024), 0, s, p.ptotal, csz, p.pbase, p.pfirst, p.chunk_p, d_select);
     hipLaunchKernelGGL(k_index_partition, dim3(tiles), dim3(kTileThreads), 0, s, db, a.n, tiles, p.tcnt, p.pbase, p.rec, d_select);
+    if (hipError_t e = launch_index_order(p.rec, a.n, p.ptotal, p.pbase, p.cnt, p.off, p.hw, p.rows, d_select, s)) return e;
     hipLaunchKernelGGL(k_index_count, dim3(kMaxChunks), dim3(256), 0, s, p.rec, a.n, csz, p.ptotal, p.pbase, p.pfirst, p.chunk_p,
                        p.ccount, d_select);
-    hipLaunchKernelGGL(k_index_offsets, dim3(kParts), dim3(256), 0, s, a.n, p.pbase, p.pfirst, p.ccount, p.cnt, p.off, d_select);
+    hipLaunchKernelGGL(k_index_offsets, dim3(kParts), dim3(256), 0, s, a.n, p.ptotal, p.pbase, p.pfirst, p.ccount, p.cnt, p.off, d_select);
     hipLaunchKernelGGL(k_index_stats, dim3(kStatsGrid), dim3(256), 0, s, p.cnt, d_select, q);
     return hipGetLastError();
 }

@@ -1120,13 +1120,15 @@ static HitCtx hit_ctx(const MfmaPass& p, int s1, uint32_t* sel) {
 
 // One launch of the form kMfmaForms[I]. write_ctx: the launch writes the pass's hit context first (an explicit form; the auto
 // variant has written one context for its three launches: they share S1, the only form-dependent field). d_select: nullptr,
-// or the auto variant's select words -- the kernel returns at once unless they name this form.
+// or the auto variant's select words -- the kernel returns at once unless they name this form. self_cap: the self pass's
+// column-chunk cap (the "mfma_col_chunk_max" knob, or kSelfCapBehindIndex for a fall-back behind an index launch: launch_auto).
 template <size_t I>
-static hipError_t launch_form(std::integral_constant<size_t, I>, const MfmaPass& p, const uint32_t* d_select, bool write_ctx) {
+static hipError_t launch_form(std::integral_constant<size_t, I>, const MfmaPass& p, const uint32_t* d_select, bool write_ctx,
+                              uint32_t self_cap) {
     constexpr MfmaForm F = kMfmaForms[I];
     const AllPairsArgs& a = p.a;
     const uint32_t n_pad = fp4_rows_padded(a.n);
-    const MfmaGeometry geo = mfma_geometry(F, p.rows(), n_pad, p.rect, g_mfma_col_chunk_max);
+    const MfmaGeometry geo = mfma_geometry(F, p.rows(), n_pad, p.rect, self_cap);
     const uint64_t n_cb = geo.col_blocks;
     dim3 grid((unsigned)geo.row_blocks, (unsigned)(a.world > 1u ? (n_cb + a.world - 1) / a.world : n_cb));  // (own tiles only: see the kernel)
     uint32_t* buf = nullptr;
@@ -1146,14 +1148,15 @@ static hipError_t launch_form(std::integral_constant<size_t, I>, const MfmaPass&
 
 // variant -> its row of the table -> launch_form (instantiated in the table's order)
 template <size_t... I>
-static hipError_t launch_variant(std::index_sequence<I...>, int variant, const MfmaPass& p, const uint32_t* d_select, bool write_ctx) {
+static hipError_t launch_variant(std::index_sequence<I...>, int variant, const MfmaPass& p, const uint32_t* d_select, bool write_ctx,
+                                 uint32_t self_cap) {
     hipError_t e = hipErrorInvalidValue;
     // (a left fold: the forms are instantiated first to last)
-    (void)(... || (kMfmaForms[I].id == variant && ((e = launch_form(std::integral_constant<size_t, I>{}, p, d_select, write_ctx)), true)));
+    (void)(... || (kMfmaForms[I].id == variant && ((e = launch_form(std::integral_constant<size_t, I>{}, p, d_select, write_ctx, self_cap)), true)));
     return e;
 }
-static hipError_t launch_variant(int variant, const MfmaPass& p, const uint32_t* d_select, bool write_ctx) {
-    return launch_variant(std::make_index_sequence<(size_t)kMfmaFormCount>{}, variant, p, d_select, write_ctx);
+static hipError_t launch_variant(int variant, const MfmaPass& p, const uint32_t* d_select, bool write_ctx, uint32_t self_cap) {
+    return launch_variant(std::make_index_sequence<(size_t)kMfmaFormCount>{}, variant, p, d_select, write_ctx, self_cap);
 }
 
 constexpr int kMaxSelect = 16;
@@ -1248,19 +1251,25 @@ static hipError_t launch_auto(const MfmaPass& p, uint32_t idx_r) {
         const uint32_t form = words[kSelForm];
         if (form != rule.id_rare && form != rule.id_often && form != mid) return hipErrorUnknown;  // (the probe writes one of its rule's three ids)
         if (words[kSelIdxUsed] != 0u) return launch_index_join(a, sel, idx_r, s);
-        return launch_variant((int)form, p, sel, false);
+        return launch_variant((int)form, p, sel, false, g_mfma_col_chunk_max);
     }
+    // Behind an index launch the three forms are the fall-back of a pass that almost always runs on the index, and every
+    // workgroup of theirs then reads two select words and returns: they are launched on the coarse grid of
+    // kSelfCapBehindIndex (hvd_mfma_forms.h) -- 62 500 workgroups instead of 480 000 at 1 M hashes. Every rank derives the
+    // same chunk from n, and the kernel deals the tiles out by rank from the chunk it is given.
+    uint32_t self_cap = g_mfma_col_chunk_max;
     if (idx_r != kNoIndex) {
         e = launch_index_join(a, sel, idx_r, s);
         if (e != hipSuccess) return e;
+        self_cap = kSelfCapBehindIndex;
     }
-    e = launch_variant(kFormFetch, p, sel, false);
+    e = launch_variant(kFormFetch, p, sel, false, self_cap);
     if (e != hipSuccess) return e;
     if (mid) {
-        e = launch_variant((int)mid, p, sel, false);
+        e = launch_variant((int)mid, p, sel, false, self_cap);
         if (e != hipSuccess) return e;
     }
-    return launch_variant(kFormRegister, p, sel, false);
+    return launch_variant(kFormRegister, p, sel, false, self_cap);
 }
 
 static int effective_variant(int variant, uint32_t max_dist, uint32_t n) {
@@ -1276,7 +1285,7 @@ hipError_t launch_cross_mfma(const AllPairsArgs& a, const void* d_img_q, uint32_
     if (a.max_dist >= 128u) return hipErrorInvalidValue;  // sign trick needs a positive threshold
     const int v = effective_variant(a.variant, a.max_dist, a.n);
     const MfmaPass p = {a, d_img_t, d_img_q, nq, d_group_t, true, s};
-    return v == kFormAuto ? launch_auto(p, kNoIndex) : launch_variant(v, p, nullptr, true);
+    return v == kFormAuto ? launch_auto(p, kNoIndex) : launch_variant(v, p, nullptr, true, g_mfma_col_chunk_max);
 }
 
 hipError_t launch_allpairs_mfma(const AllPairsArgs& a_in, const void* d_img, hipStream_t s) {
@@ -1304,7 +1313,7 @@ hipError_t launch_allpairs_mfma(const AllPairsArgs& a_in, const void* d_img, hip
     }
     std::lock_guard<std::mutex> lk(g_launch_mu);
     const MfmaPass p = {a, d_img, d_img, a.n, nullptr, false, s};
-    return v == kFormAuto ? launch_auto(p, idx_r) : launch_variant(v, p, nullptr, true);
+    return v == kFormAuto ? launch_auto(p, idx_r) : launch_variant(v, p, nullptr, true, g_mfma_col_chunk_max);
 }
 
 }  // namespace hvd

@@ -19,7 +19,10 @@ from ._lib import PAIR_DTYPE
 
 
 def tile_geometry(n: int, variant: int = 9) -> tuple[int, int]:
-    """(rows_per_block, col_chunk) of the all-pairs launch for n hashes (host-only)."""
+    """(rows_per_block, col_chunk) of the all-pairs launch for n hashes (host-only): the explicit forms, and the auto variant
+    wherever a pass is not eligible for the pigeonhole index. The auto variant's fall-back launches behind an index launch
+    cut the columns more coarsely above ~262 000 hashes (csrc/hvd_mfma_forms.h: kSelfCapBehindIndex); tile (rb, cb) still
+    belongs to rank (rb + cb) % world."""
     lib = _lib.load()
     r, c = C.c_uint32(0), C.c_uint32(0)
     _lib.check(lib.hvd_allpairs_tile_geometry(n, variant, C.byref(r), C.byref(c)))
