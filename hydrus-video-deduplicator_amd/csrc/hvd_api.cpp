@@ -633,6 +633,11 @@ int hvd_debug_set(const char* key, int value) {
         hvd::g_allpairs_index = value;
         return HVD_OK;
     }
+    if (strcmp(key, "index_stage") == 0) {  // high-byte pass of the index build: 1 a tile's runs laid out in LDS (k_index_scatter, default), 0 k_index_partition
+        if (value < 0 || value > 1) return fail(HVD_ERR_ARG, "index_stage: 1 (runs staged in LDS) or 0 (direct stores)");
+        hvd::g_index_stage = value;
+        return HVD_OK;
+    }
     if (strcmp(key, "mfma_queue_packed") == 0) {  // 0: the pair-queue form settles its candidates from the FP4 images only
         hvd::g_mfma_queue_packed = value != 0;
         return HVD_OK;
@@ -766,9 +771,11 @@ int hvd_debug_get(const char* key, int* out_value) {
             *out_value = (int)v[pk.word];
             return HVD_OK;
         }
-    if (strcmp(key, "allpairs_index_used") == 0 || strcmp(key, "allpairs_index_kcand") == 0) {
+    if (strcmp(key, "allpairs_index_used") == 0 || strcmp(key, "allpairs_index_kcand") == 0 || strcmp(key, "allpairs_index_cand_lo") == 0 ||
+        strcmp(key, "allpairs_index_max_walk") == 0) {
         // the last auto-variant pass of this context: 1 if it ran on the pigeonhole index; its exact candidates / 1000 (0 when
-        // the histograms were not built)
+        // the histograms were not built), their low 31 bits, and the longest work item (saturated at 2^32 - 1 on the device,
+        // reported as at most 2^31 - 1)
         uint32_t* sel = nullptr;
         HIP_TRY(hvd::mfma_select_buffer(t_ctx, &sel));
         uint32_t v[hvd::kSelectWords] = {};
@@ -776,6 +783,10 @@ int hvd_debug_get(const char* key, int* out_value) {
         HIP_TRY(hipStreamSynchronize(g.stream));
         if (key[15] == 'u') {
             *out_value = (int)v[hvd::kSelIdxUsed];
+        } else if (key[15] == 'c') {
+            *out_value = (int)(v[hvd::kSelIdxCand] & 0x7FFFFFFFu);
+        } else if (key[15] == 'm') {
+            *out_value = (int)std::min<uint32_t>(v[hvd::kSelIdxMaxWalk], 0x7FFFFFFFu);
         } else {
             const unsigned long long cand = (unsigned long long)v[hvd::kSelIdxCand] | (unsigned long long)v[hvd::kSelIdxCand + 1] << 32;
             *out_value = (int)std::min<unsigned long long>(cand / 1000ull, 0x7FFFFFFFull);

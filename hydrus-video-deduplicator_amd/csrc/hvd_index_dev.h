@@ -1,5 +1,6 @@
 // hvd_index_dev.h -- what the kernel files of the pigeonhole index build share (k_hamming_index.hip: the chunked counting
-// sort and the join; k_index_order.hip: the partitions that fit LDS): the geometry of the keys, the two LDS / wave helpers,
+// sort and the join; k_index_scatter.hip: the high-byte pass staged in LDS; k_index_order.hip: the partitions that fit
+// LDS): the geometry of the keys, the two LDS / wave helpers,
 // and the ONE size test that says which of the two files orders a partition. Device code: HIP only.
 #pragma once
 #include <hip/hip_runtime.h>

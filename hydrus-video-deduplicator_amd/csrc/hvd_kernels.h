@@ -93,7 +93,7 @@ struct IndexRule {
     float fs_mfma_fetch;  // femtoseconds per comparison of form 9 / of the other matrix-core forms
     float fs_mfma_other;
     float ps_cand;        // picoseconds per candidate (join)
-    float ps_hash;        // picoseconds per hash (counting sort, statistics, place)
+    float ps_hash;        // picoseconds per hash (counting sort: what of it grows with n)
     float ps_crit;        // picoseconds per pair of the longest work item: one wave walks it alone (critical path)
     float fixed_ns;       // launches of the index pass and its kernels whose length does not depend on n
 };
@@ -106,6 +106,7 @@ __host__ __device__ inline bool index_wins(const IndexRule& q, double cand, doub
 }
 extern int g_allpairs_index;       // hvd_debug_set "allpairs_index": -1 auto, 0 never, 1 force when eligible
 extern int g_allpairs_index_fail;  // fault injection (tests): context (value - 1) fails to reserve its index scratch; 0 = off
+extern int g_index_stage;          // hvd_debug_set "index_stage": 1 the high-byte pass lays a tile's runs out in LDS (k_index_scatter), 0 k_index_partition
 extern int g_index_join_wgs;       // tests: workgroups of the join; 0 = sized by the device and, above 2^20 hashes, by n (index_join_workgroups)
 // Eligible: self pass (not query x target, not the video sink), max_dist <= 31, packed hashes at hand, not switched off, and
 // -- unless forced -- a DB large enough that the index could win even with no candidates at all. Depends only on what every
@@ -123,6 +124,10 @@ hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t
 // the partitions that fit LDS, ordered whole (k_index_order.hip): launched by launch_index_decide behind the partition pass
 hipError_t launch_index_order(const uint2* rec, uint32_t n, const uint32_t* ptotal, const uint32_t* pbase, uint32_t* cnt, uint32_t* off,
                               uint32_t* hw, uint32_t* rows, const uint32_t* d_select, hipStream_t s);
+// the high-byte pass with a tile's runs laid out in LDS (k_index_scatter.hip): launched by launch_index_decide where
+// k_index_partition was, same grid and arguments, unless "index_stage" is 0
+hipError_t launch_index_scatter(const uint4* db, uint32_t n, uint32_t ntiles, const uint32_t* tcnt, const uint32_t* pbase, uint2* rec,
+                                const uint32_t* d_select, hipStream_t s);
 // the join's grid for n hashes on the current device (or what "index_join_wgs" sets): the same for every n <= 2^20
 hipError_t index_join_workgroups(uint32_t n, uint32_t* wgs);
 void index_release();

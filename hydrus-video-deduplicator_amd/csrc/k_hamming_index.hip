@@ -10,16 +10,22 @@
 //   k_index_scan_rows   one wave per partition (block, high byte): exclusive scan over the tiles, the partition's size
 //   k_index_scan_parts  one workgroup: every partition's base inside its block, and the list of chunks (a partition larger
 //                       than csz entries is cut into several, so that no workgroup sets the length of the passes below)
-//   k_index_partition   the tiles again: rank from a returning LDS atomic, record {row, key | sibling key << 16} -> its
-//                       partition (short runs): the record carries the whole 32-bit word that holds block b
+//   k_index_scatter     (k_index_scatter.hip) the tiles again: record {row, key | sibling key << 16} -> its partition -- the
+//                       record carries the whole 32-bit word that holds block b. Block by block the tile's 4096 records
+//                       are ranked by a returning LDS atomic, laid out by high byte in LDS and copied out in that order,
+//                       so that neighbouring lanes write neighbouring records of a run
+//   k_index_partition   the same pass with every record stored straight from its lane to its run (a wave's store touches
+//                       ~64 cache lines): launched instead of k_index_scatter under hvd_debug_set "index_stage" 0, the
+//                       independent path of tests/test_gpu_index_scatter.py
 //   k_index_order       (k_index_order.hip) one workgroup per partition of at most kOrderMax records: low-byte digits counted,
 //                       scanned and ranked in LDS, the partition laid out there in final order and written out as two
 //                       contiguous streams -- cnt, off, hw and rows of that partition in one kernel. The three chunk
 //                       kernels below skip what it took and serve the larger partitions:
 //   k_index_count       one workgroup per chunk: low-byte digits counted in 256 LDS bins
 //   k_index_offsets     one workgroup per partition: the chunks' counts -> per-key counts, off[b][h * 256 ..], chunk cursors
-//   k_index_stats       a few hundred workgroups stride over the (block, key)s: exact candidates and the longest work item,
-//                       reduced privately, two atomics and a ticket per workgroup; the last workgroup decides
+//   k_index_stats       a few hundred workgroups of 16 waves stride over the (block, key)s: exact candidates and the longest
+//                       work item; a key's count and its 16 neighbours' are loaded at once, for two keys per thread (no
+//                       load waits for another), reduced privately, two atomics and a ticket per workgroup; the last workgroup decides
 //                       (select[kSelIdxUsed], hvd_kernels.h: index_wins) -- the matrix-core forms return at once when it is set
 //   k_index_place       the chunks again: final position from a returning LDS atomic on the bin's cursor; the record's word
 //                       -> hw, its row -> rows (the packed DB is not touched)
@@ -241,45 +247,73 @@ __global__ __launch_bounds__(256) void k_index_offsets(uint32_t n, const uint32_
     }
 }
 
-constexpr uint32_t kStatsGrid = 256u;  // workgroups of the statistics: each ends in two atomics and a ticket
+constexpr uint32_t kStatsGrid = 256u;      // workgroups of the statistics: each ends in two atomics and a ticket
+constexpr uint32_t kStatsThreads = 1024u;  // 16 waves: at 256 workgroups four waves per SIMD, each with kStatsPer entries in flight
+constexpr uint32_t kStatsPer = 2u;         // entries of a thread whose loads are issued together (2 x 17 loads)
 
 // Candidates of key u in its block: C(c_u, 2) + (r = 1) c_u x c_v over the one-bit neighbours v = u ^ (1 << t) above u --
 // the exact number of pairs whose keys of this block are within r, i.e. the pairs the join walks for this work item.
-__global__ __launch_bounds__(256) void k_index_stats(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ select,
-                                                     const hvd::IndexRule q) {
+// The kernel waits for its loads and for nothing else (the counts come from the other dies' k_index_order: at best the
+// Infinity Cache), so no load depends on another: an entry's own count and its 16 neighbours' counts are loaded
+// unconditionally -- a neighbour below u is masked out afterwards -- and kStatsPer entries of a thread are loaded before
+// the first is used.
+__global__ __launch_bounds__(kStatsThreads) void k_index_stats(const uint32_t* __restrict__ cnt, uint32_t* __restrict__ select,
+                                                               const hvd::IndexRule q) {
     if (select[hvd::kSelIdxGate] == 0u) return;
-    // the workgroups stride over the kBlocks * kKeys (block, key)s (a multiple of the grid's threads) and reduce privately
+    // the workgroups stride over the kBlocks * kKeys (block, key)s and reduce privately
     unsigned long long cand = 0;
     uint32_t mx = 0;
-    for (uint32_t t = blockIdx.x * 256u + threadIdx.x; t < kBlocks * kKeys; t += gridDim.x * 256u) {
-        const uint32_t u = t & (kKeys - 1u);
-        const uint32_t* cb = cnt + (t & ~(kKeys - 1u));
-        const unsigned long long c = cb[u];
-        unsigned long long ylen = c;
-        cand += c * (c - (c != 0ull)) / 2ull;
-        if (q.r != 0u && c != 0ull) {
+    const uint32_t stride = gridDim.x * kStatsThreads;
+    for (uint32_t t0 = blockIdx.x * kStatsThreads + threadIdx.x; t0 < kBlocks * kKeys; t0 += kStatsPer * stride) {
+        uint32_t c[kStatsPer], nb[kStatsPer][16];
 #pragma unroll
-            for (uint32_t s = 0; s < 16u; ++s)
-                if (((u >> s) & 1u) == 0u) ylen += cb[u ^ (1u << s)];
-            cand += c * (ylen - c);
+        for (uint32_t k = 0; k < kStatsPer; ++k) {
+            const uint32_t t = min(t0 + k * stride, kBlocks * kKeys - 1u);  // (an entry past the end: loaded, not used)
+            const uint32_t u = t & (kKeys - 1u);
+            const uint32_t* __restrict__ cb = cnt + (t & ~(kKeys - 1u));
+            c[k] = cb[u];
+            if (q.r != 0u) {  // (uniform over the grid)
+#pragma unroll
+                for (uint32_t s = 0; s < 16u; ++s) nb[k][s] = cb[u ^ (1u << s)];
+            }
         }
-        // the work item's walk: its wave steps its c x's over a y list of ylen entries (saturated: any such item loses anyway)
-        mx = max(mx, (uint32_t)min(c * ylen, 0xFFFFFFFFull));
+#pragma unroll
+        for (uint32_t k = 0; k < kStatsPer; ++k) {
+            const uint32_t t = t0 + k * stride, u = t & (kKeys - 1u);
+            if (t >= kBlocks * kKeys) break;
+            const unsigned long long cu = c[k];
+            unsigned long long ylen = cu;
+            cand += cu * (cu - (cu != 0ull)) / 2ull;
+            if (q.r != 0u) {
+#pragma unroll
+                for (uint32_t s = 0; s < 16u; ++s) ylen += ((u >> s) & 1u) == 0u ? nb[k][s] : 0u;
+                cand += cu * (ylen - cu);
+            }
+            // the work item's walk: its wave steps its c x's over a y list of ylen entries (saturated: any such item loses
+            // anyway; an empty bucket has no walk)
+            mx = max(mx, (uint32_t)min(cu * ylen, 0xFFFFFFFFull));
+        }
     }
     for (int off = 32; off > 0; off >>= 1) {
         cand += __shfl_down(cand, off);
         mx = max(mx, (uint32_t)__shfl_down((int)mx, off));
     }
-    __shared__ unsigned long long part[4];
-    __shared__ uint32_t partm[4];
+    constexpr uint32_t kWaves = kStatsThreads / 64u;
+    __shared__ unsigned long long part[kWaves];
+    __shared__ uint32_t partm[kWaves];
     if ((threadIdx.x & 63u) == 0u) {
         part[threadIdx.x >> 6] = cand;
         partm[threadIdx.x >> 6] = mx;
     }
     __syncthreads();
     if (threadIdx.x != 0u) return;
-    const unsigned long long sum = part[0] + part[1] + part[2] + part[3];
-    const uint32_t m = max(max(partm[0], partm[1]), max(partm[2], partm[3]));
+    unsigned long long sum = 0;
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kWaves; ++w) {
+        sum += part[w];
+        m = max(m, partm[w]);
+    }
     unsigned long long* cand_w = reinterpret_cast<unsigned long long*>(select + hvd::kSelIdxCand);
     // (as the probe: the sums travel in returning atomics, and the ticket is taken after they have returned)
     unsigned long long seen = 0;
@@ -627,6 +661,7 @@ namespace hvd {
 int g_allpairs_index = -1;
 int g_allpairs_index_fail = 0;
 int g_index_join_wgs = 0;
+int g_index_stage = 1;
 
 // per-context scratch: per-key counts [16][65536], offsets [16][65537], words [16][n] x 4 B, rows [16][n] x 4 B -- in this
 // order: the join's scalar batch reads up to 15 words past a bucket's end, which behind the last block's words are rows --;
@@ -706,13 +741,18 @@ IndexRule index_rule(const AllPairsArgs& a, uint32_t r) {
     // kernels, whose workgroups all return): 0.22 ns per hash. That is the price up to ~1.4 M uniform hashes, which is where
     // the rule decides anything: beyond, the partitions outgrow kOrderMax and a hash costs the 0.33 ns of the chunk kernels
     // again, 1 ms more at 10 M than this term says, in a pass that wins by a factor of forty. fixed_ns: those 25 us, 43 us
-    // of launches (one more) and the three fall-back launches on their coarse grid, 19 us: 87 us, rounded up)
+    // of launches (one more) and the three fall-back launches on their coarse grid, 19 us: 87 us, rounded up.
+    // With the high-byte pass staged in LDS (k_index_scatter.hip) and the statistics free of dependent loads
+    // (profiles/r22_index_kernel_stats_after.csv): every kernel between probe and join 0.157 ms. Of these the two scans and
+    // the three chunk kernels, 25 us, do not depend on n, and neither do the statistics, 17 us, which load all 16 x 65 536
+    // counts whatever n is: the tile count, the scatter and the order pass, 0.116 ms, are 0.12 ns per hash. fixed_ns: those
+    // 42 us, 43 us of launches (as many as before) and 21 us of fall-back launches: 106 us, rounded up)
     q.fs_mfma_fetch = 36.0f;
     q.fs_mfma_other = 40.0f;
     q.ps_cand = 0.31f;
-    q.ps_hash = 220.0f;
+    q.ps_hash = 120.0f;
     q.ps_crit = 320.0f;
-    q.fixed_ns = 90000.0f;
+    q.fixed_ns = 110000.0f;
     return q;
 }
 
@@ -750,12 +790,16 @@ hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const 
     hipLaunchKernelGGL(k_index_tile_count, dim3(tiles), dim3(kTileThreads), 0, s, db, a.n, tiles, p.tcnt, d_select);
     hipLaunchKernelGGL(k_index_scan_rows, dim3(kParts / 4u), dim3(256), 0, s, p.tcnt, tiles, p.ptotal, d_select);
     hipLaunchKernelGGL(k_index_scan_parts, dim3(1), dim3(1024), 0, s, p.ptotal, csz, p.pbase, p.pfirst, p.chunk_p, d_select);
-    hipLaunchKernelGGL(k_index_partition, dim3(tiles), dim3(kTileThreads), 0, s, db, a.n, tiles, p.tcnt, p.pbase, p.rec, d_select);
+    if (g_index_stage != 0) {
+        if (hipError_t e = launch_index_scatter(db, a.n, tiles, p.tcnt, p.pbase, p.rec, d_select, s)) return e;
+    } else {
+        hipLaunchKernelGGL(k_index_partition, dim3(tiles), dim3(kTileThreads), 0, s, db, a.n, tiles, p.tcnt, p.pbase, p.rec, d_select);
+    }
     if (hipError_t e = launch_index_order(p.rec, a.n, p.ptotal, p.pbase, p.cnt, p.off, p.hw, p.rows, d_select, s)) return e;
     hipLaunchKernelGGL(k_index_count, dim3(kMaxChunks), dim3(256), 0, s, p.rec, a.n, csz, p.ptotal, p.pbase, p.pfirst, p.chunk_p,
                        p.ccount, d_select);
     hipLaunchKernelGGL(k_index_offsets, dim3(kParts), dim3(256), 0, s, a.n, p.ptotal, p.pbase, p.pfirst, p.ccount, p.cnt, p.off, d_select);
-    hipLaunchKernelGGL(k_index_stats, dim3(kStatsGrid), dim3(256), 0, s, p.cnt, d_select, q);
+    hipLaunchKernelGGL(k_index_stats, dim3(kStatsGrid), dim3(kStatsThreads), 0, s, p.cnt, d_select, q);
     return hipGetLastError();
 }
 

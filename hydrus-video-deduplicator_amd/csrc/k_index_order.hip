@@ -1,7 +1,7 @@
 // k_index_order.hip -- the low-byte pass of the pigeonhole index build for the partitions that fit LDS (the build and its
 // other kernels: k_hamming_index.hip).
 //
-// k_index_partition has laid every (block, high byte) partition out as one contiguous run of records. A partition of at most
+// The high-byte pass (k_index_scatter.hip) has laid every (block, high byte) partition out as one contiguous run of records. A partition of at most
 // kOrderMax records (hvd_index_dev.h: every one of a uniform DB of 2^20 hashes, and of some way beyond) is ordered by ONE workgroup in ONE
 // kernel: the low bytes counted in 256 LDS counters, scanned, every record ranked by a returning LDS atomic and laid out in
 // final order in LDS, then copied out as two contiguous streams -- where the chunk kernels (k_index_count, k_index_offsets,

@@ -512,6 +512,8 @@ int hvd_get_pdq_dct_mode(void);
  *   "allpairs_index" -1|0|1                                (auto variant, self pass, max_dist <= 31: the exact pigeonhole index path --
  *                                                           -1 the device decides from its histograms (default) | never | whenever
  *                                                           eligible; not the query x target or video searches)
+ *   "index_stage" 0|1                                      (index build, high-byte pass: direct stores -- k_index_partition -- | a tile's
+ *                                                           runs laid out in LDS and copied out in order -- k_index_scatter, default)
  *   "mfma_force_sel" -1|0|1|2                              (which 128 bits the first stage sees: the probe's choice | bits 0..127 |
  *                                                           128..255 | 0..63 + 192..255)
  *   "pdq_hash_grid" n                                      (64x64 hash kernel: forced grid; 0 = by batch size)
@@ -535,6 +537,8 @@ int hvd_debug_set(const char* key, int value);
  * (1 for max_dist 16..31, 0 below); 0 when the pass was not index-eligible (the probe sums it only then). Read-only.
  * "allpairs_index_used": 1 if the last auto-variant pass ran on the pigeonhole index, else 0; "allpairs_index_kcand": its exact
  * candidate count / 1000 (0 when the probe's estimate kept the histograms from being built).
+ * "allpairs_index_cand_lo": the low 31 bits of that exact count; "allpairs_index_max_walk": its longest work item, max over
+ * (block, key u) of c_u x (c_u + the counts of the one-bit neighbours above u when the radius is 1), as min(value, 2^31 - 1).
  * Synchronises the library stream.
  * "vmatch_us_local" / "vmatch_us_exchange" / "vmatch_us_fold": host microseconds of the three phases of the last video-level
  * search on the calling thread's context (local: packed hashes, probe, all-pairs pass, key set; exchange: agreement words,
