@@ -222,7 +222,8 @@ __device__ __forceinline__ bool better(const Best& x, const Best& y) {
 }
 
 // Windowed sums and their arg-max under the tie order, the same on every lane: lanes stride over the bins (the window summed
-// directly, <= 33 reads), wave shuffles, then the four waves through wbest (4 Best of LDS). AGAIN: the caller may come back
+// directly: 2 slack + 1 reads clamped to the histogram, <= 33 for k_valign and k_valign_segments, <= 257 at k_valign_rates'
+// slack_r = 16 * 8), wave shuffles, then the four waves through wbest (4 Best of LDS). AGAIN: the caller may come back
 // with no barrier since the call before, whose wbest some wave may still be reading (the rounds of k_valign_segments).
 template <bool AGAIN>
 __device__ __forceinline__ Best best_offset(const uint32_t* hist, uint32_t nbins, uint32_t slack, int32_t dmin, Best* wbest) {

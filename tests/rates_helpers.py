@@ -142,3 +142,135 @@ def join(videos):
     off = np.concatenate([[0], np.cumsum([len(v) for v in videos])]).astype(np.int64)
     fr = np.concatenate(videos) if len(videos) else np.zeros((0, 32), np.uint8)
     return np.ascontiguousarray(fr, dtype=np.uint8), off
+
+
+# ---- the grid of tests/test_rates_grid_cpu.py and tests/test_gpu_rates_grid.py: rates up to 8, every tolerance and slack ----
+
+# every legal value that needs the top bit of a nibble, on either side, and (1, 1) for the header's consequence (b)
+WIDE_RATES = ((1, 1), (8, 7), (7, 8), (8, 1), (1, 8), (7, 2), (5, 8), (8, 3))
+GRID = tuple((max_dist, slack) for max_dist in (0, 30, 31, 32, 127) for slack in (0, 1, 3, 16))
+WIDE_CLIP = 36  # frames of a planted clip: 8 * 35 + c stays inside a 300-frame source
+
+
+def rotated(rates, k):
+    """The list with its first k entries moved behind the others."""
+    return tuple(rates[k:]) + tuple(rates[:k])
+
+
+def rate_tops(A, B, pa=None, pb=None, max_dist=31, slack=1, rates=WIDE_RATES) -> list:
+    """S_r(d*_r) of every listed rate, each on its own (0 for a pair without a hit)."""
+    return [rates_pair(A, B, pa, pb, max_dist, slack, (r,))[3] for r in rates]
+
+
+# case 4: single rates with an 8, WIDE_RATES with (8, 1) and with (1, 8) in the eighth entry, an 8 in the first and the eighth
+TOP_BIT_LISTS = (((8, 1),), ((1, 8),), ((8, 7),), ((7, 8),), rotated(WIDE_RATES, 4), rotated(WIDE_RATES, 5),
+                 ((1, 8), (1, 1), (8, 7), (7, 8), (7, 2), (5, 8), (8, 3), (8, 1)))
+REORDER_POINTS = ((31, 1), (127, 1), (31, 3))  # (max_dist, slack) at which at least nine pairs of wide_library(300) do not tie
+
+
+def non_tying(frames, offsets, pairs, max_dist, slack, rates=WIDE_RATES) -> list:
+    """Indices of the pairs with a hit whose largest S_r(d*_r) is reached by one listed rate alone (index positions)."""
+    out = []
+    for p, (a, b) in enumerate(pairs):
+        tops = rate_tops(frames[offsets[a]:offsets[a + 1]], frames[offsets[b]:offsets[b + 1]], None, None, max_dist, slack, rates)
+        if max(tops) > 0 and tops.count(max(tops)) == 1:
+            out.append(p)
+    return out
+
+
+def wide_library(n_source, seed):
+    """(videos, pairs). Video 0: a source of n_source independent random hashes; 1..8: one WIDE_CLIP-frame clip per rate of
+    WIDE_RATES, source index round(t num / den + c), up to 20 bits flipped per frame; 9, 10: 7 and 12 frames of one hash; 11:
+    9 random frames; 12: no frame. Pairs: every clip against the source in both orientations, the static pair in both
+    orientations, the 8/7 clip against the 1x clip (which it runs through at 8/7) and back, the random frames and the empty
+    video against the source."""
+    rng = np.random.default_rng(seed)
+    source = _rand(rng, n_source)
+    h = _rand(rng, 1)
+    vids = [source]
+    for k, (num, den) in enumerate(WIDE_RATES):
+        vids.append(AH.noisy(rng, resampled(source, WIDE_CLIP, num, den, 3.3 + 1.7 * k), 20))
+    vids += [np.repeat(h, 7, axis=0), np.repeat(h, 12, axis=0), _rand(rng, 9), np.zeros((0, 32), np.uint8)]
+    pairs = [(v, 0) for v in range(1, 9)] + [(0, v) for v in range(1, 9)] + [(9, 10), (10, 9), (2, 1), (1, 2), (11, 0), (12, 0)]
+    return vids, pairs
+
+
+_wide = {}
+
+
+def wide_case(n_source):
+    """(frames, offsets, pairs, {(max_dist, slack): the restatement's records under WIDE_RATES}) of wide_library(n_source),
+    over GRID. Computed once per process and shared: the arrays are read-only."""
+    if n_source not in _wide:
+        vids, pairs = wide_library(n_source, 80 + n_source)
+        frames, offsets = join(vids)
+        want = {}
+        for max_dist, slack in GRID:
+            want[(max_dist, slack)] = align_rates(frames, offsets, pairs, None, WIDE_RATES, slack, max_dist)
+            want[(max_dist, slack)].setflags(write=False)
+        frames.setflags(write=False)
+        offsets.setflags(write=False)
+        _wide[n_source] = (frames, offsets, tuple(pairs), want)
+    return _wide[n_source]
+
+
+def wide_bins(n_source, slack, pair) -> int:
+    """The largest bins_r of a pair of wide_library(n_source) under WIDE_RATES (index positions: span = length - 1)."""
+    _, offsets, _, _ = wide_case(n_source)
+    sa, sb = (int(offsets[v + 1] - offsets[v]) - 1 for v in pair)
+    return max(num * sa + den * sb + 1 + 2 * slack * max(num, den) for num, den in WIDE_RATES)
+
+
+def edge_library(seed=83, n_source=300):
+    """(videos, pairs): the source and one clip per rate of WIDE_RATES as in wide_library, but frame t of a clip differs from
+    its source frame in exactly 31 bits when t is even and in exactly 32 when t is odd. Pairs: every clip against the source
+    in both orientations."""
+    rng = np.random.default_rng(seed)
+    source = _rand(rng, n_source)
+    vids = [source]
+    for k, (num, den) in enumerate(WIDE_RATES):
+        clip = resampled(source, WIDE_CLIP, num, den, 4.4 + 1.3 * k)
+        vids.append(np.stack([AH.flip_bits(rng, f, 31 + (t & 1)) for t, f in enumerate(clip)]))
+    return vids, [(v, 0) for v in range(1, 9)] + [(0, v) for v in range(1, 9)]
+
+
+def tiny_library(seed=84):
+    """(videos, pairs): 1, 1, 2, 3, 7 and 12 frames of one hash, then the same lengths of independent random hashes; the pairs
+    1 x 1, 2 x 3 and 7 x 12 of each kind, the longer ones in both orientations. pairs[3] is the static 7 x 12 pair."""
+    rng = np.random.default_rng(seed)
+    h = _rand(rng, 1)
+    lengths = (1, 1, 2, 3, 7, 12)
+    vids = [np.repeat(h, n, axis=0) for n in lengths] + [_rand(rng, n) for n in lengths]
+    pairs = [(0, 1), (2, 3), (3, 2), (4, 5), (5, 4), (6, 7), (8, 9), (9, 8), (10, 11), (11, 10)]
+    return vids, pairs
+
+
+def bin_limit_library(seed=85):
+    """(videos, positions, span_a, spans_b): three videos of two frames at positions [0, span]. Under [(1, 1), (8, 1)] at slack 1
+    the pair (0, 1) has 8 * 100000 + 248559 + 1 + 16 = 2^20 bins at (8, 1), the pair (0, 2) one more; under [(1, 1), (1, 8)] the
+    pairs (1, 0) and (2, 0) have the same. Frame i of videos 1 and 2 is within 20 bits of frame 1 - i of video 0 and far from
+    frame i: two hits, (0, 1) and (1, 0), the last and the first core bin of the histogram at either rate. Their deltas lie far
+    apart, so both rates hold bands of one vote and (1, 1), listed first, keeps the tie. (With positions [0, span] and 2 x 2
+    frames no pair of exactly 2^20 bins can give (1, 1) two votes in a band and (8, 1) one: two deltas of (1, 1) within 2 of each
+    other need span_a <= 2, which (8, 1) gathers as well, or span_b <= 2 or |span_b - span_a| <= 2, which
+    8 span_a + span_b = 2^20 - 17 rules out.)"""
+    rng = np.random.default_rng(seed)
+    A = _rand(rng, 2)
+    span_a, spans_b = 100000, (248559, 248560)
+    vids = [A, AH.noisy(rng, A[::-1], 20), AH.noisy(rng, A[::-1], 20)]
+    positions = np.array([0, span_a, 0, spans_b[0], 0, spans_b[1]], dtype=np.int32)
+    return vids, positions, span_a, spans_b
+
+
+MAX_POSITION = (1 << 20) - 1  # the largest position the host entry accepts (check_positions of hvd_search.cpp)
+
+
+def far_positions_library(seed=86):
+    """(videos, positions): video 0, 60 random frames at positions 0..59; video 1, 8 frames that end at MAX_POSITION, frame t
+    a noisy copy of frame 8 t + 3 of video 0. As a against video 0 as b that is rate (8, 1) with
+    offset = p_b - 8 p_a = 3 - 8 (MAX_POSITION - 7), about -2^23; as b against a it is (1, 8) and the offset is the opposite."""
+    rng = np.random.default_rng(seed)
+    Q = _rand(rng, 60)
+    P = AH.noisy(rng, Q[8 * np.arange(8) + 3], 20)
+    positions = np.concatenate([np.arange(60), MAX_POSITION - 7 + np.arange(8)]).astype(np.int32)
+    return [Q, P], positions
