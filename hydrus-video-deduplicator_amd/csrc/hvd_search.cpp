@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "hvd_bit_order.h"
 #include "hvd_hash_host.h"
 #include "hvd_internal.h"
 #include "../../include/hvd_mi355x_bench.h"
@@ -589,51 +590,31 @@ int build_table(std::initializer_list<Table> tables, unsigned long long floor, u
     }
 }
 
-// Which 128 bits should the first stage see? (k_hamming_mfma.hip: "data-dependent bit order".) From the co-occurrence counts of a
-// strided sample of the packed hashes: Pearson correlation of every pair of bits, then 128 times drop the bit whose summed
-// |correlation| with the bits still in the set is largest (a constant bit goes first). perm = the 128 kept bits in ascending
-// order, then the dropped ones: bit k of a rewritten hash is bit perm[k] of the original. Deterministic in the data, so every rank
-// of a sharded search -- the library is replicated -- arrives at the same order. *changed = false: too few hashes, keep the order.
+// The co-occurrence counts of a library's sample (hvd_bit_order.h: bit_order_sample) into d_cooc, 256 * 256 u32, on the
+// context's stream; the transposed sample goes through pool slot S_BROWS (callers hold h_mu).
+int count_bit_cooc(const void* d_bits, const hvd::BitSample& s, void* d_cooc) {
+    void* d_rows = nullptr;
+    SCR(S_BROWS, 8 * 256 * (size_t)s.words, d_rows);
+    HIP_TRY(hvd::launch_bit_cooc(d_bits, s.stride, s.words, d_rows, d_cooc, g.stream));
+    return HVD_OK;
+}
+
+// Which 128 bits should the first stage see? (k_fp4_image.hip: "data-dependent bit order".) The co-occurrence counts of a
+// strided sample of the packed hashes, then the rule of hvd_bit_order.h: bit k of a rewritten hash is bit perm[k] of the
+// original. Deterministic in the data, so every rank of a sharded search -- the library is replicated -- arrives at the same
+// order. *changed = false: too few hashes, keep the order.
 int choose_bit_order(const void* d_bits, uint32_t n, bool always, uint8_t perm[256], bool* changed) {
     *changed = false;
     for (int k = 0; k < 256; ++k) perm[k] = (uint8_t)k;
-    const uint32_t sample = std::min<uint32_t>(n, 16384u) & ~63u;
-    if (sample < (always ? 64u : 4096u)) return HVD_OK;
-    const uint32_t words = sample / 64u, stride = n / sample;
-    void *d_rows = nullptr, *d_cooc = nullptr;
-    SCR(S_BROWS, 8 * 256 * (size_t)words, d_rows);
+    const hvd::BitSample s = hvd::bit_order_sample(n, always);
+    if (!s.sample) return HVD_OK;
+    void* d_cooc = nullptr;
     SCR(S_BCOOC, 4 * 256 * 256, d_cooc);
-    HIP_TRY(hvd::launch_bit_cooc(d_bits, stride, words, d_rows, d_cooc, g.stream));
+    if (int rc = count_bit_cooc(d_bits, s, d_cooc)) return rc;
     std::vector<uint32_t> cooc(256 * 256);
     HIP_TRY(hipMemcpyAsync(cooc.data(), d_cooc, 4 * cooc.size(), hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
-    const double N = (double)sample;
-    std::vector<double> pr(256), sd(256), a(256 * 256, 0.0), load(256, 0.0);
-    for (int i = 0; i < 256; ++i) {
-        pr[i] = cooc[(size_t)i * 257] / N;
-        sd[i] = std::sqrt(std::max(0.0, pr[i] * (1.0 - pr[i])));
-    }
-    for (int i = 0; i < 256; ++i)
-        for (int j = 0; j < 256; ++j) {
-            if (i == j) continue;
-            const double r = (sd[i] < 1e-6 || sd[j] < 1e-6) ? 1.0 : (cooc[(size_t)i * 256 + j] / N - pr[i] * pr[j]) / (sd[i] * sd[j]);
-            a[(size_t)i * 256 + j] = std::fabs(r);
-            load[i] += std::fabs(r);
-        }
-    bool in[256];
-    for (int i = 0; i < 256; ++i) in[i] = true;
-    for (int step = 0; step < 128; ++step) {
-        int worst = -1;
-        for (int i = 0; i < 256; ++i)
-            if (in[i] && (worst < 0 || load[i] >= load[worst])) worst = i;  // (ties: the higher bit goes)
-        in[worst] = false;
-        for (int j = 0; j < 256; ++j) load[j] -= a[(size_t)worst * 256 + j];
-    }
-    int k = 0;
-    for (int i = 0; i < 256; ++i)
-        if (in[i]) perm[k++] = (uint8_t)i;
-    for (int i = 0; i < 256; ++i)
-        if (!in[i]) perm[k++] = (uint8_t)i;
+    hvd::bit_order_from_cooc(cooc.data(), s.sample, perm);
     for (int i = 0; i < 256; ++i) *changed = *changed || perm[i] != i;
     return HVD_OK;
 }
@@ -1591,6 +1572,46 @@ int hvd_dev_synth_video_frames(void* d_frames, int64_t v0, int64_t n_videos, int
     HIP_TRY(hvd::launch_synth_frames64((uint8_t*)d_frames, v0, (uint32_t)frames_per_video,
                                        (unsigned long long)n_videos * (unsigned long long)frames_per_video, seed,
                                        (const int32_t*)d_copy_of, g.stream));
+    return HVD_OK;
+}
+
+// The pieces of the video search's bit order, one at a time (include/hvd_mi355x_bench.h): the sample rule and the counting
+// kernels as choose_bit_order runs them, its rule, the rewrite as vmatch_keys launches it, and packed_hashes' kernel.
+int hvd_dev_bit_cooc(const void* d_bits, int64_t n, int force, void* d_cooc, uint32_t* sample, uint32_t* stride) {
+    if (int rc = need_ready()) return rc;
+    if (n < 0 || n >= (1ll << 32) || !d_cooc || !sample || !stride || (n > 0 && !d_bits)) return fail(HVD_ERR_ARG, "bad arguments");
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    const hvd::BitSample s = hvd::bit_order_sample((uint32_t)n, force != 0);
+    *sample = s.sample;
+    *stride = s.stride;
+    if (!s.sample) return HVD_OK;
+    if (int rc = count_bit_cooc(d_bits, s, d_cooc)) return rc;
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
+}
+
+int hvd_bit_order_from_cooc(const uint32_t* cooc, uint32_t sample, uint8_t* perm) {
+    if (!cooc || !perm || sample == 0) return fail(HVD_ERR_ARG, "bad arguments");
+    hvd::bit_order_from_cooc(cooc, sample, perm);
+    return HVD_OK;
+}
+
+int hvd_dev_reorder_bits(const void* d_bits, int64_t n, const uint8_t* perm, void* d_bits_out, void* d_img) {
+    if (int rc = need_ready()) return rc;
+    if (n < 0 || n >= (1ll << 32) || !perm || !d_img || (n > 0 && (!d_bits || !d_bits_out))) return fail(HVD_ERR_ARG, "bad arguments");
+    bool seen[256] = {};
+    for (int k = 0; k < 256; ++k) {
+        if (seen[perm[k]]) return fail(HVD_ERR_ARG, "perm is not a permutation of 0..255: %d appears twice", (int)perm[k]);
+        seen[perm[k]] = true;
+    }
+    HIP_TRY(hvd::launch_reorder_bits(d_bits, (uint32_t)n, perm, d_bits_out, d_img, g.stream));
+    return HVD_OK;
+}
+
+int hvd_dev_pack_fp4(const void* d_img, int64_t n, void* d_bits) {
+    if (int rc = need_ready()) return rc;
+    if (n < 0 || n >= (1ll << 32) || (n > 0 && (!d_img || !d_bits))) return fail(HVD_ERR_ARG, "bad arguments");
+    HIP_TRY(hvd::launch_pack_fp4(d_img, (uint32_t)n, d_bits, g.stream));
     return HVD_OK;
 }
 

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void k_pack_fp4(const uint4* __restrict__ img,
 // everybody. The 128-bit first stage does: it sees the first 128 bits, and on real frame hashes some bits move together (on the
 // config-5 frames: DCT rows and columns 7..9), so unrelated frames agree on them far more often than on independent bits. The
 // video search therefore measures, on a sample of the library, how much every bit correlates with the others, keeps the 128
-// least entangled bits for the first stage (hvd_api.cpp: 128 times, drop the bit with the largest sum of |correlation| with the
+// least entangled bits for the first stage (hvd_bit_order.h: 128 times, drop the bit with the largest sum of |correlation| with the
 // bits still in the set) and rewrites packed hashes and FP4 image in that order: 7e-6 of the unrelated pairs pass instead of
 // 7.5e-5 (bits 0..63 + 192..255) or 2.3e-4 (bits 0..127). Results are bit-identical by construction.
 //   k_bit_rows: the sample, transposed -- rows[b][w] = bit b of sample hashes 64w .. 64w+63 (one ballot per bit and wave)

@@ -39,6 +39,28 @@ int hvd_debug_parallel_copy(void* dst, const void* src, size_t n, int threads);
  * paths run at shapes that take milliseconds; 0 = the default. Results do not depend on it, except that the autocrop
  * entries refuse (HVD_ERR_ARG) a video with more frames than one batch holds. */
 
+/* Test hooks: the pieces of the video search's data-dependent bit order ("vmatch_bit_order"), one at a time, so that
+ * tests/test_bit_order_cpu.py and tests/test_gpu_bit_order.py can compare each with numpy. Every one of them calls what the
+ * search itself calls; none changes what a search does.
+ *
+ * hvd_dev_bit_cooc: the search's sample of the n packed 32-byte hashes at d_bits -- *sample = min(n, 16384) rounded down to
+ * a multiple of 64, every *stride = n / *sample -th hash from hash 0 on -- and the co-occurrence counts of its bits in
+ * d_cooc (256 * 256 uint32: [i][j] = sampled hashes with bits i and j both set). Fewer than 4096 hashes (force != 0: fewer
+ * than 64) are too few to choose an order from: *sample = *stride = 0 and d_cooc is not written. Synchronises. */
+int hvd_dev_bit_cooc(const void* d_bits, int64_t n, int force, void* d_cooc, uint32_t* sample, uint32_t* stride);
+
+/* Host only (no device needed): the order the search chooses from such counts: perm[0..127] = the 128 kept bits,
+ * ascending, perm[128..255] = the dropped ones, ascending; bit k of a rewritten hash is bit perm[k] of the original. */
+int hvd_bit_order_from_cooc(const uint32_t* cooc, uint32_t sample, uint8_t* perm);
+
+/* The rewrite: n packed hashes -> n packed hashes at d_bits_out and their FP4 image (hvd_fp4_image_bytes(n)) at d_img, both
+ * in the order perm. HVD_ERR_ARG, and nothing launched, unless perm is a permutation of 0..255. Does not synchronise. */
+int hvd_dev_reorder_bits(const void* d_bits, int64_t n, const uint8_t* perm, void* d_bits_out, void* d_img);
+
+/* The packed hashes of the first n rows of an FP4 image (the inverse of hvd_dev_expand_fp4), as the searches that are
+ * handed images only derive them. Does not synchronise. */
+int hvd_dev_pack_fp4(const void* d_img, int64_t n, void* d_bits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,9 @@ def test_bench_symbols_are_not_in_the_product_header():
     assert sorted(os.listdir(os.path.join(ROOT, "include"))) == ["hvd_mi355x.h", "hvd_mi355x_bench.h"]
     product = declared_symbols(("hvd_mi355x.h",))
     assert "hvd_dev_synth_video_frames" not in product and "hvd_debug_parallel_copy" not in product
-    assert declared_symbols(("hvd_mi355x_bench.h",)) == ["hvd_debug_parallel_copy", "hvd_dev_synth_video_frames"]
+    assert not {"hvd_dev_bit_cooc", "hvd_bit_order_from_cooc", "hvd_dev_reorder_bits", "hvd_dev_pack_fp4"} & set(product)
+    assert declared_symbols(("hvd_mi355x_bench.h",)) == ["hvd_bit_order_from_cooc", "hvd_debug_parallel_copy", "hvd_dev_bit_cooc",
+                                                         "hvd_dev_pack_fp4", "hvd_dev_reorder_bits", "hvd_dev_synth_video_frames"]
 
 
 def test_header_symbols_all_exported_and_bound(hvd):

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+from bit_order_helpers import fp4_image
 from conftest import load_golden
 
 pytestmark = pytest.mark.gpu
@@ -293,6 +294,7 @@ def test_fp4_image_layout(gpu, hvd):
             raw = img[row, chunk ^ ((row >> 1) & 7)]
             nib = np.stack([raw & 15, raw >> 4], axis=1).reshape(-1)  # low nibble first
             assert np.array_equal(nib, np.where(bits[row, chunk] == 1, 0xA, 0x2))
+    assert np.array_equal(img, fp4_image(db, 1024))  # the same model for every row at once (shared with test_gpu_bit_order.py)
 
 
 @pytest.mark.parametrize("world", [2, 3, 8])
