@@ -10,7 +10,8 @@ from . import (_lib, hashing, multigpu, pipeline, rendezvous, search, sqlite_ada
 from .hashing import compute_phash, decode_phash_from_str, encode_phash_to_str, get_phash_similarity  # noqa: F401
 from .search import (allpairs_hamming, calculate_distance, find_cropped_duplicates, find_duplicate_groups, find_excerpts,  # noqa: F401
                      find_keeper_groups, find_new_duplicates, find_potential_duplicates,
-                     find_rate_excerpts, find_segmented_excerpts, find_transformed_duplicates, fix_vpdq_similarity,
+                     find_rate_excerpts, find_rate_segmented_excerpts, find_segmented_excerpts, find_transformed_duplicates,
+                     fix_vpdq_similarity,
                      match_videos, without_common_frames)
 from .vpdq import VideoHasher, VpdqHash, matchHash, matchHashBytes  # noqa: F401
 from .pipeline import (DeviceLibrary, dedupe_cropped_frames_on_device, dedupe_frames_on_device,  # noqa: F401

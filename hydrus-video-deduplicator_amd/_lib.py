@@ -44,6 +44,15 @@ ALIGN_MAX_RATES = 8  # HVD_ALIGN_MAX_RATES
 # one video pair aligned at the best of the listed rates (hvd_vrate): the words of VALIGN_DTYPE, offset in the scaled units of the
 # winning rate (den p_b - num p_a), then that rate, its index in the list and a reserved word
 VRATE_DTYPE = np.dtype(VALIGN_DTYPE.descr + [("rate_num", "<u4"), ("rate_den", "<u4"), ("rate_index", "<u4"), ("reserved", "<u4")])
+# one segment of a pair at its rate (hvd_vrsegment): the words of VSEGMENT_DTYPE, offset and band_votes in the scaled units of the
+# segment's rate, then that rate, its index in the list and a reserved word
+VRSEGMENT_DTYPE = np.dtype(VSEGMENT_DTYPE.descr + [("rate_num", "<u4"), ("rate_den", "<u4"), ("rate_index", "<u4"),
+                                                   ("reserved", "<u4")])
+# one video pair aligned on up to ALIGN_MAX_SEGMENTS lines, each at the best of the listed rates (hvd_vrsegments): the head of
+# VSEGMENTS_DTYPE; seg[0].offset = INT32_MIN with n_segments = 0 marks a pair the device entry could not align
+VRSEGMENTS_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("q_hits", "<u4"), ("t_hits", "<u4"), ("n_segments", "<u4"),
+                             ("q_covered", "<u4"), ("t_covered", "<u4"), ("reserved", "<u4"),
+                             ("seg", VRSEGMENT_DTYPE, (ALIGN_MAX_SEGMENTS,))])
 # one duplicate group (hvd_group): a connected component of size >= 2 of a pair list; root = its smallest member = its label
 GROUP_DTYPE = np.dtype([("root", "<u4"), ("size", "<u4"), ("edges", "<u4"), ("keeper", "<u4")])
 EDGES_ALL, EDGES_VMATCH = 0, 1  # HVD_EDGES_ALL, HVD_EDGES_VMATCH
@@ -82,6 +91,8 @@ SIGNATURES = {
     "hvd_vpdq_align_videos": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp]),
     "hvd_vpdq_align_segments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _int, _int, _vp]),
     "hvd_vpdq_align_rates": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _vp]),
+    "hvd_vpdq_align_rate_segments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _int, _int,
+                                            _vp]),
     "hvd_group_edges": (_int, [_vp, _i64, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     "hvd_keeper_groups": (_int, [_vp, _i64, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "hvd_hasher_create": (_int, [_int, _int, _int, _i64, C.POINTER(_vp)]),
@@ -149,6 +160,9 @@ SIGNATURES = {
     "hvd_rates_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
     "hvd_dev_vpdq_align_rates": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _vp, _sz,
                                         _vp]),
+    "hvd_rate_segments_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
+    "hvd_dev_vpdq_align_rate_segments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _int,
+                                                _int, _vp, _sz, _vp]),
     "hvd_group_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
     "hvd_dev_group_edges": (_int, [_vp, _i64, _vp, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hvd_keeper_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),

@@ -238,6 +238,16 @@ hipError_t launch_valign_rates(const void* d_hashes_q, const long long* d_offset
                                const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, uint32_t nums,
                                uint32_t dens, void* d_scratch, size_t scratch_bytes, hvd_vrate* d_out, hipStream_t s);
 
+// Rate-aware multi-segment time alignment (k_valign_rate_segments.hip): launch_valign_rates' operands and two
+// launches, up to max_segments greedy rounds per pair, each at the best of the listed rates; a slot of d_scratch
+// (rate_segments_scratch_bytes(max_bins), max_bins as for rates_scratch_bytes) also holds the pair's taken sets.
+size_t rate_segments_scratch_bytes(unsigned long long max_bins);
+hipError_t launch_valign_rate_segments(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
+                                       const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
+                                       const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, uint32_t nums,
+                                       uint32_t dens, uint32_t max_segments, uint32_t min_band_votes, void* d_scratch,
+                                       size_t scratch_bytes, hvd_vrsegments* d_out, hipStream_t s);
+
 // Duplicate groups with a keeper: connected components of a list of 16-byte records (k_group.hip). d_scratch:
 // group_scratch_bytes(V), 8-byte aligned; d_record_count: nullptr, or the uint64 an all-pairs pass counted its records in (the
 // kernels then take min(*d_record_count, n_records)); d_count: one uint64, receives the number of groups.

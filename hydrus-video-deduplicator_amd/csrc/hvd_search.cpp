@@ -1163,7 +1163,7 @@ int hvd_dev_vpdq_match_videos_cross(const void* d_img_q, int64_t nq, const void*
                             d_out, cap, d_count);
 }
 
-/* ---- time alignment of listed video pairs (k_valign.hip, k_valign_segments.hip) ---- */
+/* ---- time alignment of listed video pairs (k_valign*.hip) ---- */
 
 int hvd_dev_kept_positions(const void* d_quality, int64_t n, const void* d_offsets, int64_t V, int min_quality, void* d_out_pos) {
     if (int rc = need_ready()) return rc;
@@ -1222,6 +1222,10 @@ int hvd_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) {
 }
 
 int hvd_rates_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(max_bins, out_bytes, hvd::rates_scratch_bytes); }
+
+int hvd_rate_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) {
+    return scratch_bytes_entry(max_bins, out_bytes, hvd::rate_segments_scratch_bytes);
+}
 
 static int check_tolerances(int max_dist, int slack) {
     if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
@@ -1306,6 +1310,28 @@ int hvd_dev_vpdq_align_rates(const void* d_hashes_q, const void* d_offsets_q, in
     return HVD_OK;
 }
 
+int hvd_dev_vpdq_align_rate_segments(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                                     const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                                     const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                                     int max_segments, int min_band_votes, void* d_scratch, size_t scratch_bytes, void* d_out) {
+    if (int rc = check_align_counts(VQ, VT, M, max_dist, slack)) return rc;
+    if (!rates || n_rates < 0) return fail(HVD_ERR_ARG, "rates is NULL or n_rates=%d < 0", n_rates);
+    if (int rc = check_segment_limits(max_segments, min_band_votes)) return rc;
+    if (M == 0) return HVD_OK;
+    if (int rc = check_align_pointers(d_offsets_q, d_offsets_t, d_pairs, d_out,
+                                      (uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch | (uintptr_t)d_out,
+                                      "hashes, scratch and records"))
+        return rc;
+    uint32_t nums = 0, dens = 0;
+    hvd::pack_rate_list(rates, n_rates, &nums, &dens);  // a broken list travels as (0, 0): the kernel's INT32_MIN records
+    HIP_TRY(hvd::launch_valign_rate_segments(d_hashes_q, (const long long*)d_offsets_q, (uint32_t)VQ, (const int32_t*)d_pos_q,
+                                             d_hashes_t, (const long long*)d_offsets_t, (uint32_t)VT, (const int32_t*)d_pos_t,
+                                             (const uint32_t*)d_pairs, (unsigned long long)M, (uint32_t)max_dist, (uint32_t)slack, nums,
+                                             dens, (uint32_t)max_segments, (uint32_t)min_band_votes, d_scratch, scratch_bytes,
+                                             (hvd_vrsegments*)d_out, g.stream));
+    return HVD_OK;
+}
+
 // positions of one library: non-negative, strictly increasing inside a video, below 2^20
 static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V, const char* side) {
     if (!pos) return HVD_OK;
@@ -1318,8 +1344,9 @@ static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V
 }
 
 // The host-buffer form of the alignments: validate, stage, run, copy the records back. rates given: hvd_vrate records
-// (hvd_dev_vpdq_align_rates), the list sound (the caller has checked it), and the arguments are judged before the library's
-// state is, so that a bad call is HVD_ERR_ARG with or without a device; else max_segments 0: hvd_valign records
+// (hvd_dev_vpdq_align_rates) with max_segments 0, else hvd_vrsegments records (hvd_dev_vpdq_align_rate_segments), the list sound
+// (the caller has checked it), and the arguments are judged before the library's state is, so that a bad call is HVD_ERR_ARG
+// with or without a device; without rates, max_segments 0: hvd_valign records
 // (hvd_dev_vpdq_align_videos); else hvd_vsegments records (hvd_dev_vpdq_align_segments).
 static int align_from_host(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
                            const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
@@ -1384,14 +1411,21 @@ static int align_from_host(const uint8_t* frames_q, const int64_t* offsets_q, in
         return rc;
     }
     SCR(S_APAIRS, 8 * (size_t)M, d_pairs);
-    const size_t out_bytes = (rates ? sizeof(hvd_vrate) : max_segments ? sizeof(hvd_vsegments) : sizeof(hvd_valign)) * (size_t)M;
+    const size_t out_bytes = (rates && max_segments ? sizeof(hvd_vrsegments)
+                              : rates               ? sizeof(hvd_vrate)
+                              : max_segments        ? sizeof(hvd_vsegments)
+                                                    : sizeof(hvd_valign)) * (size_t)M;
     SCR(S_AOUT, out_bytes, d_out);
-    const size_t sb = rates          ? hvd::rates_scratch_bytes((unsigned long long)max_bins)
-                      : max_segments ? hvd::segments_scratch_bytes((unsigned long long)max_bins)
-                                     : hvd::align_scratch_bytes((unsigned long long)max_bins);
+    const size_t sb = rates && max_segments ? hvd::rate_segments_scratch_bytes((unsigned long long)max_bins)
+                      : rates               ? hvd::rates_scratch_bytes((unsigned long long)max_bins)
+                      : max_segments        ? hvd::segments_scratch_bytes((unsigned long long)max_bins)
+                                            : hvd::align_scratch_bytes((unsigned long long)max_bins);
     if (sb) SCR(S_ASCR, sb, d_scr);
     HIP_TRY(hipMemcpyAsync(d_pairs, pairs, 8 * (size_t)M, hipMemcpyHostToDevice, g.stream));
-    if (int rc = rates        ? hvd_dev_vpdq_align_rates(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack, rates,
+    if (int rc = rates && max_segments
+                     ? hvd_dev_vpdq_align_rate_segments(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack, rates,
+                                                        n_rates, max_segments, min_band_votes, d_scr, sb, d_out)
+                 : rates      ? hvd_dev_vpdq_align_rates(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack, rates,
                                                          n_rates, d_scr, sb, d_out)
                  : max_segments ? hvd_dev_vpdq_align_segments(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack,
                                                             max_segments, min_band_votes, d_scr, sb, d_out)
@@ -1429,6 +1463,19 @@ int hvd_vpdq_align_rates(const uint8_t* frames_q, const int64_t* offsets_q, int6
                     HVD_ALIGN_MAX_RATES);
     return align_from_host(frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, 0,
                            1, out, rates, n_rates);
+}
+
+int hvd_vpdq_align_rate_segments(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                                 const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                                 const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                                 int max_segments, int min_band_votes, hvd_vrsegments* out) {
+    uint32_t nums = 0, dens = 0;
+    if (!hvd::pack_rate_list(rates, n_rates, &nums, &dens))
+        return fail(HVD_ERR_ARG, "rates: need 1..%d pairs (num, den) with 1 <= num, den <= 8, no common factor, none listed twice",
+                    HVD_ALIGN_MAX_RATES);
+    if (int rc = check_segment_limits(max_segments, min_band_votes)) return rc;
+    return align_from_host(frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack,
+                           max_segments, min_band_votes, out, rates, n_rates);
 }
 
 /* ---- duplicate groups with a keeper: connected components of a pair list (k_group.hip) ---- */

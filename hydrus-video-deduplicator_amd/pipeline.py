@@ -25,7 +25,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib, search, vpdq
-from ._lib import GROUP_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VSEGMENTS_DTYPE, DeviceBuffer
+from ._lib import GROUP_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VRSEGMENTS_DTYPE, VSEGMENTS_DTYPE, DeviceBuffer
 
 
 def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
@@ -401,6 +401,19 @@ class DeviceLibrary:
         widest = [lambda span, r=r: (int(r[0]) + int(r[1])) * span + 1 + 2 * int(slack) * int(max(r)) for r in rates]
         return self._align(records, slack, max_dist, VRATE_DTYPE, lib.hvd_rates_scratch_bytes, lib.hvd_dev_vpdq_align_rates,
                            (rates.ctypes.data, rates.shape[0]), widest)
+
+    def align_rate_segments(self, records, rates=search.DEFAULT_RATES, slack: int = search.ALIGN_SLACK,
+                            max_dist: int | None = None, max_segments: int = _lib.ALIGN_MAX_SEGMENTS,
+                            min_band_votes: int = 1) -> np.ndarray:
+        """hvd_dev_vpdq_align_rate_segments of the listed pairs of this library against itself: one VRSEGMENTS_DTYPE record
+        per pair, in their order (search.align_rate_segments on what is in HBM; operands and positions as `align`). A broken
+        rate list gives INT32_MIN records, as the device entry does."""
+        lib = _lib.ensure()
+        rates = search.rate_array(rates)
+        widest = [lambda span, r=r: (int(r[0]) + int(r[1])) * span + 1 + 2 * int(slack) * int(max(r)) for r in rates]  # (align_rates')
+        return self._align(records, slack, max_dist, VRSEGMENTS_DTYPE, lib.hvd_rate_segments_scratch_bytes,
+                           lib.hvd_dev_vpdq_align_rate_segments,
+                           (rates.ctypes.data, rates.shape[0], int(max_segments), int(min_band_votes)), widest)
 
     def _align(self, records, slack, max_dist, dtype, scratch_bytes, entry, extra: tuple, widest=()) -> np.ndarray:
         """One device-resident alignment call over this library against itself: `entry` with the operands both alignments
@@ -1048,6 +1061,21 @@ def find_rate_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: 
         d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library,
         lambda library, recs: library.align_rates(recs, rates=rates, slack=slack),
         lambda aligned, lengths, sim: search.rate_excerpts_from_records(aligned, lengths, sim, threshold, min_aligned))
+
+
+def find_rate_segmented_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                           threshold: float = 50.0, min_aligned: int = 4, slack: int = search.ALIGN_SLACK,
+                                           rates=search.DEFAULT_RATES, positions: bool = True,
+                                           max_segments: int = _lib.ALIGN_MAX_SEGMENTS, keep_library: bool = False):
+    """search.find_rate_segmented_excerpts on frames in HBM, one device: the chain of `find_excerpts_on_device` with the
+    rate-aware multi-segment alignment (`DeviceLibrary.align_rate_segments`, min_band_votes = min_aligned) and the keep rule of
+    search.rate_segmented_excerpts_from_records; nothing but records crosses PCIe.
+    -> (rate-segmented excerpts, search records, VRSEGMENTS records, library or None); positions are raw frame indices."""
+    return _aligned_search_on_device(
+        d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library,
+        lambda library, recs: library.align_rate_segments(recs, rates=rates, slack=slack, max_segments=max_segments,
+                                                          min_band_votes=int(min_aligned)),
+        lambda aligned, lengths, sim: search.rate_segmented_excerpts_from_records(aligned, lengths, sim, threshold, min_aligned))
 
 
 def _rank0_of_every_context(entry, frames_of_rank, timings, n_results: int, *args, **kwargs):

@@ -18,7 +18,8 @@ from fractions import Fraction
 import numpy as np
 
 from . import _lib, vpdq
-from ._lib import ALIGN_MAX_RATES, ALIGN_MAX_SEGMENTS, GROUP_DTYPE, PAIR_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VSEGMENTS_DTYPE
+from ._lib import (ALIGN_MAX_RATES, ALIGN_MAX_SEGMENTS, GROUP_DTYPE, PAIR_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VRSEGMENTS_DTYPE,
+                   VSEGMENTS_DTYPE)
 
 DISTANCE_TOLERANCE = 31  # per-frame Hamming tolerance (vpdqpy/vpdqpy.py:53, db/vptree.py:31)
 DEFAULT_VARIANT = 13  # all-pairs kernel the product uses (FP4-MFMA, 128-bit first stage, form chosen by a probe); DESIGN.md 4.1
@@ -712,6 +713,124 @@ def find_rate_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int =
     exactly find_excerpts'. `rate` is the best-fitting LISTED rate: on smooth content, where neighbouring frames match each
     other, a neighbouring rate of the list may be reported; detection rests on the coverage."""
     return rate_excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, rates, positions)
+
+
+# ------------------------------------------------ sped-up reels and re-cuts: rate x segments in one call (DESIGN 4.18) ---
+
+def align_rate_segments(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.ndarray | None = None, rates=DEFAULT_RATES,
+                        slack: int = ALIGN_SLACK, max_dist: int | None = None, frames_t: np.ndarray | None = None,
+                        offsets_t: np.ndarray | None = None, positions_t: np.ndarray | None = None,
+                        max_segments: int = ALIGN_MAX_SEGMENTS, min_band_votes: int = 1) -> np.ndarray:
+    """Rate-aware multi-segment time alignment of the listed video pairs (hvd_vpdq_align_rate_segments): one VRSEGMENTS_DTYPE
+    record per pair, in the order of `pairs`. The operands are align_rates', the limits align_segments'. Up to `max_segments`
+    (1..8) lines are peeled off a pair, greedily: each round is align_rates' rule on the frame hits whose frames no earlier
+    segment owns -- every listed rate votes, the rate whose best band holds the most hits wins, the earlier one on a tie --
+    and ends the pair if that band holds fewer than `min_band_votes` hits. A record holds the head of a VSEGMENTS_DTYPE record
+    and the segments in the order they were found: the words of a VSEGMENT_DTYPE segment, offset in the scaled units of the
+    segment's rate (c = offset / rate_den), then rate_num, rate_den, rate_index. With rates = ((1, 1),) these are
+    align_segments' records with 1, 1, 0, 0 behind every used segment; with max_segments = 1 seg[0] is align_rates' record.
+    The default list lacks (1, 2): a 2x reel is segmented cleanly when it is the `a` side of its pair (rate (2, 1)); as the `b`
+    side the neighbouring rates of the list fragment it into short segments that still cover nearly all of it -- list (1, 2)
+    in place of another rate if b may be the sped-up one."""
+    frames, offsets, positions, frames_t, offsets_t, positions_t, pairs, max_dist = _align_operands(
+        frames, offsets, pairs, positions, max_dist, frames_t, offsets_t, positions_t)
+    rates = rate_array(rates)
+    M = pairs.shape[0]
+    out = np.zeros(M, dtype=VRSEGMENTS_DTYPE)
+    out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
+    lib = _lib.ensure()
+    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
+        max_dist, M = 0, 0  # (the entry still judges the list, the limits and the libraries)
+    _lib.check(lib.hvd_vpdq_align_rate_segments(_ptr(frames), offsets.ctypes.data, offsets.size - 1, _ptr(positions),
+                                                _ptr(frames_t), offsets_t.ctypes.data, offsets_t.size - 1, _ptr(positions_t),
+                                                _ptr(pairs), M, max_dist, int(slack), rates.ctypes.data, rates.shape[0],
+                                                int(max_segments), int(min_band_votes), _ptr(out)))
+    return out
+
+
+RateSegment = namedtuple("RateSegment", "rate offset short_first short_last first last aligned")
+RateSegmentedExcerpt = namedtuple("RateSegmentedExcerpt", "short long coverage similarity segments")
+
+
+def rate_segmented_excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: np.ndarray,
+                                         threshold: float = 50.0, min_aligned: int = 4) -> list:
+    """The keep rule of find_rate_segmented_excerpts on VRSEGMENTS_DTYPE records (pure numpy; no device): the rule of
+    segmented_excerpts_from_records -- short = the video with fewer frames (a on a tie); a segment counts iff at least
+    min_aligned frames of short are aligned in it; coverage = 100 * those frames over the segments that count / frames of
+    short; kept iff int(coverage) >= int(threshold) and at least one segment counts -- with the orientation arithmetic of
+    rate_excerpts_from_records: a segment (num, den, d) reads p_b = (num / den) p_a + d / den when a is short and
+    p_a = (den / num) p_b - d / num when b is. -> sorted list of RateSegmentedExcerpt(short, long, coverage, similarity,
+    segments); segments: the ones that count, ordered by short_first, each RateSegment(rate, offset, short_first, short_last,
+    first, last, aligned) with rate and offset Fractions in long's timeline, p_long = rate * p_short + offset."""
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    lengths = np.asarray(lengths, dtype=np.int64)
+    out = []
+    for r, sim in zip(aligned, similarity):
+        a, b = int(r["a"]), int(r["b"])
+        a_short = lengths[a] <= lengths[b]
+        n_short = int(lengths[a] if a_short else lengths[b])
+        if n_short == 0 or int(r["seg"][0]["offset"]) == -(1 << 31):
+            continue
+        segs = []
+        for s in r["seg"][:int(r["n_segments"])]:
+            on = int(s["q_aligned"] if a_short else s["t_aligned"])
+            if on < int(min_aligned):
+                continue
+            num, den, d = int(s["rate_num"]), int(s["rate_den"]), int(s["offset"])
+            segs.append(RateSegment(Fraction(num, den), Fraction(d, den), int(s["q_first"]), int(s["q_last"]), int(s["t_first"]),
+                                    int(s["t_last"]), on)
+                        if a_short else
+                        RateSegment(Fraction(den, num), Fraction(-d, num), int(s["t_first"]), int(s["t_last"]), int(s["q_first"]),
+                                    int(s["q_last"]), on))
+        if not segs:
+            continue
+        coverage = 100.0 * sum(s.aligned for s in segs) / n_short
+        if int(coverage) < int(threshold):
+            continue
+        segs = tuple(sorted(segs, key=lambda s: s.short_first))
+        out.append(RateSegmentedExcerpt(a, b, coverage, float(sim), segs) if a_short else
+                   RateSegmentedExcerpt(b, a, coverage, float(sim), segs))
+    return sorted(out)
+
+
+def rate_segmented_excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
+                                 rates=DEFAULT_RATES, positions=None, max_segments: int = ALIGN_MAX_SEGMENTS, matcher=None) -> list:
+    """The search and the alignment of find_rate_segmented_excerpts and their fold, on validated blobs (as excerpt_pairs).
+    matcher: object with match_videos / align_rate_segments (default: the GPU entry points of this module). The alignment is
+    asked to stop at min_band_votes = min_aligned (see find_rate_segmented_excerpts).
+    -> rate_segmented_excerpts_from_records(...)."""
+    mv, al = (match_videos, align_rate_segments) if matcher is None else (matcher.match_videos, matcher.align_rate_segments)
+    frames, offsets, lengths = pack_hashes(blobs)
+    pos = _positions_of(positions, blobs, lengths)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
+    recs = mv(frames, offsets, max_dist)
+    aligned = al(frames, offsets, np.stack([recs["a"], recs["b"]], axis=1), positions=pos, rates=rates, slack=slack,
+                 max_dist=max_dist, max_segments=max_segments, min_band_votes=int(min_aligned))
+    return rate_segmented_excerpts_from_records(aligned, lengths, similarity_of_records(recs, lengths), threshold, min_aligned)
+
+
+def find_rate_segmented_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
+                                 rates=DEFAULT_RATES, positions=None, max_segments: int = ALIGN_MAX_SEGMENTS) -> list:
+    """Videos that are SEVERAL pieces of a longer one, each piece sped up or slowed down -- a highlight reel or a trailer at
+    1.25x to 2x, a compilation whose clips run at different speeds -- besides what find_segmented_excerpts (slope one) and
+    find_rate_excerpts (one line) find. Every pair of the video search is aligned on up to `max_segments` lines, each at the
+    best of the listed rates on the frames no earlier line owns (align_rate_segments); a segment counts iff at least
+    `min_aligned` frames of the SHORTER video line up in it, and the pair is kept iff the segments that count cover at least
+    `threshold` percent of the shorter video. The arguments are find_excerpts'; rates: see align_rates. -> sorted list of
+    RateSegmentedExcerpt(short, long, coverage, similarity, segments), segments = tuple of RateSegment(rate, offset,
+    short_first, short_last, first, last, aligned) ordered by short_first: short's positions short_first..short_last sit at
+    first..last of long, p_long = rate * p_short + offset (Fractions; rate above 1: short is the sped-up one). With rates =
+    ((1, 1),) the result is find_segmented_excerpts' with rate = 1; with max_segments = 1 the pairs, rates, offsets and
+    coverages are find_rate_excerpts'.
+    The alignment is asked to stop at min_band_votes = min_aligned. That prunes rounds and changes no result: a segment's
+    aligned frames never outnumber its band_votes, and band_votes never increases from one segment to the next -- a segment
+    below the floor cannot count, nor can any after it. S is compared raw across rates, so a band at a neighbouring listed rate
+    may claim part of a piece first: `rate` is the best-fitting LISTED rate per segment, detection rests on the coverage. The
+    default list lacks (1, 2): a 2x reel is reported with its pieces whole when it is the first video of its pair, and in
+    fragments (the coverage nearly the same) when it is the second; list (1, 2) in place of another rate to change that."""
+    return rate_segmented_excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, rates, positions,
+                                        max_segments)
 
 
 # ------------------------------------------------------------------ duplicate groups with a keeper (DESIGN 4.11) ------

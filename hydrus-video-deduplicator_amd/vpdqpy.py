@@ -93,6 +93,17 @@ class Vpdq:
         return search.align_rates(frames, offsets, [(0, 1)], rates=search.DEFAULT_RATES if rates is None else rates,
                                   slack=slack)[0]
 
+    @staticmethod
+    def align_rate_segments(phash_a, phash_b, rates=None, slack: int = 1, max_segments: int = 8):
+        """Where the pieces of two video hashes line up in time when the pieces were also sped up or slowed down -- a sped-up
+        reel against its source: the one ``search.align_rate_segments`` record of the pair (a = 0, b = 1; up to max_segments
+        lines, each at the best-fitting rate of `rates`, default ``search.DEFAULT_RATES``). VpdqHash or bytes."""
+        from . import search
+
+        frames, offsets, _ = search.pack_hashes((phash_a, phash_b))
+        return search.align_rate_segments(frames, offsets, [(0, 1)], rates=search.DEFAULT_RATES if rates is None else rates,
+                                          slack=slack, max_segments=max_segments)[0]
+
     select_frames = staticmethod(select_frames)
 
     @staticmethod

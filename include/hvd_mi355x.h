@@ -40,7 +40,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross, then + hvd_rate_segments_scratch_bytes, hvd_dev_vpdq_align_rate_segments, hvd_vpdq_align_rate_segments; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -100,6 +100,25 @@ typedef struct hvd_vrate {
     int32_t q_first, q_last, t_first, t_last;
     uint32_t rate_num, rate_den, rate_index, reserved;
 } hvd_vrate;
+
+/* One video pair aligned on up to HVD_ALIGN_MAX_SEGMENTS lines, each at the best of up to HVD_ALIGN_MAX_RATES listed rates
+ * (hvd_vpdq_align_rate_segments / hvd_dev_vpdq_align_rate_segments): a reel cut from several scenes whose pieces
+ * were also sped up or slowed down. A segment (hvd_vrsegment) is twelve 32-bit words: the eight of hvd_vsegment, in its order,
+ * then rate_num, rate_den, rate_index and a reserved word (0) as in hvd_vrate; offset and band_votes are in the rate's scaled
+ * units, as in hvd_vrate. A record (hvd_vrsegments) is 104 words = 416 bytes, 16-byte aligned: the eight-word head of
+ * hvd_vsegments, then the segments in the order they were found; unused slots are 0. A pair without a frame hit, or with an
+ * empty video: every word after b is 0. A pair the device entry cannot align (the conditions of hvd_vrate): n_segments = 0,
+ * seg[0].offset = INT32_MIN, the other words after b 0. */
+typedef struct hvd_vrsegment {
+    int32_t offset;
+    uint32_t band_votes, q_aligned, t_aligned;
+    int32_t q_first, q_last, t_first, t_last;
+    uint32_t rate_num, rate_den, rate_index, reserved;
+} hvd_vrsegment;
+typedef struct hvd_vrsegments {
+    uint32_t a, b, q_hits, t_hits, n_segments, q_covered, t_covered, reserved;
+    hvd_vrsegment seg[HVD_ALIGN_MAX_SEGMENTS];
+} hvd_vrsegments;
 
 /* One duplicate group (hvd_group_edges / hvd_dev_group_edges): a connected component of size >= 2 of the graph
  * whose edges are the records of a search. root: the smallest member, which is also the label of every member; size: members;
@@ -354,6 +373,37 @@ int hvd_vpdq_align_rates(const uint8_t* frames_q, const int64_t* offsets_q, int6
                          const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                          const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                          hvd_vrate* out);
+
+/* Rate-aware multi-segment time alignment of listed video pairs: a short video that is SEVERAL pieces of a longer one, each
+ * sped up or slowed down by a listed rate. The notation and the operands are those of hvd_vpdq_align_videos (H,
+ * votes, S, the tie order), hvd_vpdq_align_segments (K = max_segments in [1, HVD_ALIGN_MAX_SEGMENTS], min_band_votes >= 1) and
+ * hvd_vpdq_align_rates (the list, delta_r, slack_r). The rule, integers only, one answer per pair:
+ *   taken_a = taken_b = {}
+ *   for s = 1..K:
+ *     H_s = {(i, j) in H : i not in taken_a and j not in taken_b};  if H_s is empty: stop
+ *     for each rate r = (num, den), in list order:
+ *       delta_r(i, j) = den p_b(j) - num p_a(i)  for (i, j) in H_s;  slack_r = slack max(num, den)
+ *       votes_r, S_r, d*_r: the rule and tie order of hvd_vpdq_align_videos on H_s, delta_r, slack_r
+ *     w = the rate of the largest S_r(d*_r), ties to the earlier rate of the list;  if S_w(d*_w) < min_band_votes: stop
+ *     aligned_a = {i : some (i, j) in H_s has |delta_w - d*_w| <= slack_w};  aligned_b likewise
+ *     segment s = (offset d*_w, band_votes S_w(d*_w), q_aligned, t_aligned, q_first, q_last, t_first, t_last,
+ *                  rate_num, rate_den, rate_index = w (0-based), 0)
+ *     taken_a |= aligned_a;  taken_b |= aligned_b;  if every frame of a, or every frame of b, is taken: stop
+ * Rate-list validity, the 2^20-bin limit at ANY listed rate and the INT32_MIN conditions are hvd_vpdq_align_rates'; max_segments
+ * and min_band_votes are hvd_vpdq_align_segments'. Four consequences: (a) with rates = [(1, 1)], the head and words 0-7 of every
+ * segment are the pair's hvd_vsegments record, word for word, and words 8-11 of a used segment are 1, 1, 0, 0; (b) with
+ * max_segments = 1 and min_band_votes = 1, the head's a .. t_hits and seg[0] are the pair's hvd_vrate record (its words 0-3 and
+ * 4-15); (c) q_hits and t_hits depend on neither the list nor K; (d) band_votes never increases from one segment to the next (H_s
+ * shrinks, so no S_r(d) grows), and a segment's q_aligned and t_aligned never exceed its band_votes (every aligned frame has a
+ * hit in the band). S is compared raw across rates, as in hvd_vpdq_align_rates: a band at a neighbouring listed rate may claim
+ * frames before the true one is looked at.
+ * out: M hvd_vrsegments records in the order of the pair list. This host-buffer form rejects a broken list, max_segments /
+ * min_band_votes out of range and everything hvd_vpdq_align_rates rejects with HVD_ERR_ARG, before it touches the device; under
+ * a device group it runs on the calling thread's current context alone. */
+int hvd_vpdq_align_rate_segments(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                                 const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                                 const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                                 int max_segments, int min_band_votes, hvd_vrsegments* out);
 
 /* Duplicate groups with a keeper: the connected components of a pair list. The rule, integers only, one answer per
  * input. V nodes, 1 <= V < 2^31. E records of 16 bytes, E < 2^32, words 0 and 1 the two node indices u, v (hvd_pair and
@@ -746,6 +796,21 @@ int hvd_dev_vpdq_align_rates(const void* d_hashes_q, const void* d_offsets_q, in
                              const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                              const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                              void* d_scratch, size_t scratch_bytes, void* d_out);
+
+/* Device-resident rate-aware multi-segment alignment (the rule: hvd_vpdq_align_rate_segments above). The operands of
+ * hvd_dev_vpdq_align_rates, plus max_segments in [1, HVD_ALIGN_MAX_SEGMENTS] and min_band_votes >= 1 (HVD_ERR_ARG otherwise)
+ * between the rate list and the scratch; d_out: M hvd_vrsegments records, 16-byte aligned. A pair's histogram is sized by its
+ * largest bins_r over the list, and its scratch slot also holds the taken sets: hvd_rate_segments_scratch_bytes(max_bins) bytes
+ * serve every pair whose largest bins_r is up to max_bins (<= 2^20). Two launches are enqueued on the library stream: no host
+ * synchronisation, nothing allocated, nothing on the device validated. What gives the INT32_MIN record of
+ * hvd_dev_vpdq_align_rates gives the one of hvd_vrsegments here (a broken list: every pair); broken operands give wrong records,
+ * never an access out of bounds. K rounds of R rates cost at most K (R + 1) passes over the pair's Hamming matrix; after round 1
+ * a rate whose last best band cannot beat the round's winner is passed over, so a full copy costs R + 1. */
+int hvd_rate_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes);
+int hvd_dev_vpdq_align_rate_segments(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                                     const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                                     const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                                     int max_segments, int min_band_votes, void* d_scratch, size_t scratch_bytes, void* d_out);
 
 /* Device-resident grouping (the rule: hvd_group_edges above). d_records: n_records records of 16 bytes, 16-byte aligned;
  * d_record_count: NULL, or the uint64 the all-pairs entries bump -- the kernels then take min(*d_record_count, n_records)
