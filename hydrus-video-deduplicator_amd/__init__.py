@@ -12,7 +12,7 @@ from .search import (allpairs_hamming, calculate_distance, find_cropped_duplicat
                      find_keeper_groups, find_new_duplicates, find_potential_duplicates,
                      find_rate_excerpts, find_rate_segmented_excerpts, find_segmented_excerpts, find_transformed_duplicates,
                      fix_vpdq_similarity,
-                     match_videos, without_common_frames)
+                     match_videos, without_common_frames, without_repeated_frames)
 from .vpdq import VideoHasher, VpdqHash, matchHash, matchHashBytes  # noqa: F401
 from .pipeline import (DeviceLibrary, dedupe_cropped_frames_on_device, dedupe_frames_on_device,  # noqa: F401
                        dedupe_transformed_frames_on_device, dedupe_videos, hash_videos)

@@ -86,6 +86,7 @@ SIGNATURES = {
     "hvd_vpdq_match_videos": (_int, [_vp, _vp, _i64, _int, _vp, _i64, C.POINTER(_i64)]),
     "hvd_vpdq_frame_spread": (_int, [_vp, _vp, _i64, _int, _vp]),
     "hvd_vpdq_frame_spread_cross": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _int, _vp, _vp]),
+    "hvd_vpdq_frame_runs": (_int, [_vp, _vp, _i64, _int, _int, _vp, _vp]),
     "hvd_vpdq_match_videos_cross": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _i64,
                                            C.POINTER(_i64)]),
     "hvd_vpdq_align_videos": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp]),
@@ -173,6 +174,7 @@ SIGNATURES = {
     "hvd_dev_common_frames": (_int, [_vp, _vp, _i64, _i64, _int, _int, _vp]),
     "hvd_dev_gather_kept_i32": (_int, [_vp, _vp, _i64, _vp]),
     "hvd_dev_vpdq_frame_spread_cross": (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _int, _int, _vp, _vp]),
+    "hvd_dev_frame_runs": (_int, [_vp, _vp, _i64, _i64, _int, _int, _vp, _vp]),
     "hvd_dev_vpdq_match_videos_cross": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _int, _int, _int, _vp, _i64,
                                                _vp]),
     # include/hvd_mi355x_bench.h (tests / bench only, not part of the drop-in boundary)

@@ -181,6 +181,13 @@ hipError_t launch_common_rule(const int32_t* d_spread, const long long* d_offset
 hipError_t launch_gather_kept_i32(const int32_t* d_in, const int32_t* d_keep, unsigned long long n, int32_t* d_out,
                                   void* d_scratch, unsigned long long* d_total, hipStream_t s);
 
+// Static-scene filter (k_runs.hip): d_hashes 32 B per frame, d_offsets a CSR over the n frames -> d_keep int32[n],
+// 1 or 0, and d_run int32[n] (may be nullptr), the frames a kept frame stands for. One launch of at most kFrameRunsMaxBlocks
+// workgroups (4 waves per SIMD on 256 compute units), each striding over groups of four videos.
+constexpr unsigned kFrameRunsMaxBlocks = 1024;
+hipError_t launch_frame_runs(const void* d_hashes, const long long* d_offsets, uint32_t V, unsigned long long n, int max_dist,
+                             int max_run, int32_t* d_keep, int32_t* d_run, hipStream_t s);
+
 // Time alignment of listed video pairs (k_valign.hip). Two launches: the pairs whose delta histogram fits LDS, then
 // the larger ones out of d_scratch (align_scratch_bytes(max_bins); may be nullptr / 0: such pairs then get the INT32_MIN record).
 size_t align_scratch_bytes(unsigned long long max_bins);

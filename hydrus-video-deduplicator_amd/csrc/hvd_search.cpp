@@ -1209,6 +1209,53 @@ int hvd_dev_gather_kept_i32(const void* d_in, const void* d_keep, int64_t n, voi
     return HVD_OK;
 }
 
+/* ---- static-scene filter: one keyframe per run of near-identical frames (k_runs.hip) ---- */
+
+static int check_run_rule(int max_dist, int max_run) {
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    if (max_run < 0 || max_run > (1 << 20)) return fail(HVD_ERR_ARG, "max_run=%d out of range [0,2^20] (0 = no limit)", max_run);
+    return HVD_OK;
+}
+
+int hvd_dev_frame_runs(const void* d_hashes, const void* d_offsets, int64_t V, int64_t n, int max_dist, int max_run,
+                       void* d_out_keep, void* d_out_run) {
+    if (int rc = check_run_rule(max_dist, max_run)) return rc;
+    if (n < 0 || V < 0 || n >= (1ll << 32) - 1 || V >= (1ll << 31) || !d_offsets) return fail(HVD_ERR_ARG, "bad arguments");
+    if (n > 0 && (!d_hashes || !d_out_keep)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if (n > 0 && V == 0) return fail(HVD_ERR_ARG, "n=%lld frames in no video", (long long)n);
+    if (int rc = need_ready()) return rc;
+    HIP_TRY(hvd::launch_frame_runs(d_hashes, (const long long*)d_offsets, (uint32_t)V, (unsigned long long)n, max_dist, max_run,
+                                   (int32_t*)d_out_keep, (int32_t*)d_out_run, g.stream));
+    return HVD_OK;
+}
+
+int hvd_vpdq_frame_runs(const uint8_t* frames, const int64_t* offsets, int64_t V, int max_dist, int max_run, int32_t* out_keep,
+                        int32_t* out_run) {
+    // every refusal comes before the question whether a device is there
+    if (int rc = check_run_rule(max_dist, max_run)) return rc;
+    int64_t nf = 0;
+    if (int rc = check_offsets(offsets, V, &nf)) return rc;
+    if (nf > 0 && !frames) return fail(HVD_ERR_ARG, "frames is NULL");
+    if (nf > 0 && !out_keep) return fail(HVD_ERR_ARG, "out_keep is NULL");
+    if (int rc = need_ready()) return rc;
+    if (nf == 0) return HVD_OK;
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    void* d_db = nullptr;
+    long long* d_off = nullptr;
+    int32_t* d_keep = nullptr;
+    SCR(S_DB, 32 * (size_t)nf, d_db);
+    SCR(S_OFF, 8 * (size_t)(V + 1), d_off);
+    SCR(S_SPREAD, 8 * (size_t)nf, d_keep);  // keep flags, then the run words
+    int32_t* d_run = out_run ? d_keep + nf : nullptr;
+    HIP_TRY(hipMemcpyAsync(d_db, frames, 32 * (size_t)nf, hipMemcpyHostToDevice, g.stream));
+    HIP_TRY(hipMemcpyAsync(d_off, offsets, 8 * (size_t)(V + 1), hipMemcpyHostToDevice, g.stream));
+    if (int rc = hvd_dev_frame_runs(d_db, d_off, V, nf, max_dist, max_run, d_keep, d_run)) return rc;
+    HIP_TRY(hipMemcpyAsync(out_keep, d_keep, 4 * (size_t)nf, hipMemcpyDeviceToHost, g.stream));
+    if (out_run) HIP_TRY(hipMemcpyAsync(out_run, d_run, 4 * (size_t)nf, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
+}
+
 static int scratch_bytes_entry(int64_t max_bins, size_t* out_bytes, size_t (*bytes)(unsigned long long)) {
     if (!out_bytes || max_bins < 0 || max_bins > (1ll << 20)) return fail(HVD_ERR_ARG, "max_bins=%lld: need 0..2^20", (long long)max_bins);
     *out_bytes = bytes((unsigned long long)max_bins);

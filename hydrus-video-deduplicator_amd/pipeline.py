@@ -494,6 +494,41 @@ class DeviceLibrary:
             (int(lengths.max()) if lengths.size else 0)
         return library, (lengths - library.lengths()).astype(np.int64)
 
+    def without_repeated_frames(self, max_dist: int, max_run: int = 0) -> tuple["DeviceLibrary", np.ndarray, DeviceBuffer]:
+        """This library with every run of near-identical consecutive frames collapsed to its first frame
+        (search.without_repeated_frames on what is in HBM): the rule (hvd_dev_frame_runs) -> compaction
+        (hvd_dev_compact_kept on the keep flags, bound 1). -> (a NEW library, dropped int64[V], runs: a DeviceBuffer of one
+        int32 per kept frame, the frames it stands for, the caller's to free); this one is untouched and still the caller's to
+        free. The result always has positions, as `without_common_frames` makes them: this library's, gathered
+        (hvd_dev_gather_kept_i32), else the index inside this library's video (hvd_dev_kept_positions); a kept frame carries
+        the position of the first frame of its run. Nothing but CSR offsets crosses PCIe."""
+        max_dist, max_run = search.check_run_rule(max_dist, max_run)
+        lib = _lib.ensure()
+        n, V = self.n_frames, self.n_videos
+        kept = C.c_int64(0)
+        with _DeviceScope() as scope:
+            d_keep, d_run = (scope.temp(DeviceBuffer(4 * max(n, 1))) for _ in range(2))
+            if max_dist < 0:  # nothing can match: every frame is its own run, which is the rule at max_run 1
+                max_dist, max_run = 0, 1
+            _lib.check(lib.hvd_dev_frame_runs(self.d_hashes.ptr, self.d_offsets.ptr, V, n, max_dist, max_run, d_keep.ptr,
+                                              d_run.ptr))
+            d_h, d_vid, d_pos, d_runs = (scope.keep(DeviceBuffer(size * max(n, 1))) for size in (32, 4, 4, 4))
+            d_off = scope.keep(DeviceBuffer(8 * (V + 1)))
+            _lib.check(lib.hvd_dev_compact_kept(self.d_hashes.ptr, d_keep.ptr, n, self.d_offsets.ptr, V, 1, d_h.ptr, d_off.ptr,
+                                                d_vid.ptr, C.byref(kept)))
+            if self.d_positions is not None:
+                _lib.check(lib.hvd_dev_gather_kept_i32(self.d_positions.ptr, d_keep.ptr, n, d_pos.ptr))
+            else:
+                _lib.check(lib.hvd_dev_kept_positions(d_keep.ptr, n, self.d_offsets.ptr, V, 1, d_pos.ptr))
+            _lib.check(lib.hvd_dev_gather_kept_i32(d_run.ptr, d_keep.ptr, n, d_runs.ptr))
+            _lib.check(lib.hvd_dev_sync())  # the keep flags and the run words are freed on the way out
+        library = DeviceLibrary(d_h, d_off, d_vid, kept.value, V)
+        library.d_positions = d_pos
+        lengths = self.lengths()
+        library._position_limit = self._position_limit if self.d_positions is not None else \
+            (int(lengths.max()) if lengths.size else 0)
+        return library, (lengths - library.lengths()).astype(np.int64), d_runs
+
     # ---- new files against this library (DESIGN 4.17) ----
 
     def attach_spread(self, max_dist: int | None = None) -> DeviceBuffer:
@@ -876,6 +911,35 @@ def dedupe_frames_without_common_on_device(d_frames_ptr: int, raw_offsets: np.nd
         pairs = search.similar_video_pairs(recs, filtered.lengths(), threshold, policy)
     finally:
         filtered.free()
+    return pairs, recs, dropped, timings
+
+
+def dedupe_frames_without_repeats_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                            max_dist: int, max_run: int = 0, threshold: float = 50.0,
+                                            policy: str | None = None, min_quality: int = vpdq.QUALITY_TOLERANCE):
+    """`dedupe_frames_on_device` with the static-scene filter between the quality filter and the search, on the
+    calling thread's context: hash -> quality filter + CSR -> runs of near-identical frames -> compaction -> the video search
+    on what is left -> pair predicate. max_dist / max_run: DeviceLibrary.without_repeated_frames. -> (pairs int64[m,2],
+    records, dropped int64[V], timings); the records' counters and the predicate's lengths are those of the collapsed library.
+    timings: hash_ms, runs_ms (rule, compaction, gathers) and search_ms, HIP-event times on the library stream; compact_ms
+    (host clock: quality filter + CSR, synchronous)."""
+    search.check_run_rule(max_dist, max_run)
+    timings: dict = {}
+    timed = _stage_timer(timings)
+    library = _hashed_library(
+        raw_offsets, 0, 1, None, lambda mine: timed("hash_ms", lambda: hash_frames_on_device(d_frames_ptr, int(mine[-1]), h, w, channels)),
+        32, lambda d_h, d_q, n, raw: DeviceLibrary.from_raw_hashes(d_h, d_q, n, raw, min_quality), timings)
+    del timings["gather_ms"]
+    try:
+        collapsed, dropped, d_runs = timed("runs_ms", lambda: library.without_repeated_frames(max_dist, max_run))
+        d_runs.free()
+    finally:
+        library.free()
+    try:
+        recs = timed("search_ms", collapsed.match_videos)
+        pairs = search.similar_video_pairs(recs, collapsed.lengths(), threshold, policy)
+    finally:
+        collapsed.free()
     return pairs, recs, dropped, timings
 
 

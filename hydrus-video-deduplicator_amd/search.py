@@ -1124,6 +1124,73 @@ def without_common_frames(video_hashes, max_videos: int, max_share: int = 50, ma
     return CommonFrames(hashes, kept_pos, dropped, spread)
 
 
+# ------------------------------------------------ static scenes: one keyframe per run of frames ------
+
+MAX_RUN_LIMIT = 1 << 20
+
+
+def check_run_rule(max_dist, max_run=0) -> tuple[int, int]:
+    """The two parameters of the static-scene rule as ints, or ValueError. max_dist: at most 127; a negative value (the
+    comparator "lt" at tolerance 0) drops nothing. max_run in [0, 2^20], 0 = no limit. max_dist has no default on purpose:
+    nobody has measured a value that suits real libraries; 0 is the lossless choice (a dropped frame equals its anchor)."""
+    if int(max_dist) != max_dist or int(max_run) != max_run:
+        raise ValueError("max_dist and max_run are integers")
+    if max_dist > 127:
+        raise ValueError("max_dist must be at most 127")
+    if not 0 <= max_run <= MAX_RUN_LIMIT:
+        raise ValueError("max_run must be in [0, 2^20] (0 = no limit)")
+    return int(max_dist), int(max_run)
+
+
+def frame_runs(frames: np.ndarray, offsets: np.ndarray, max_dist: int, max_run: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """One keyframe per run of near-identical consecutive frames (hvd_vpdq_frame_runs; the rule: include/hvd_mi355x.h at
+    hvd_dev_frame_runs). Per video, in order: the first frame is the anchor and is kept; a later frame within max_dist bits of
+    the anchor is dropped while the anchor's run holds fewer than max_run frames (0 = no limit); any other frame is kept and
+    becomes the anchor. frames: uint8[sum,32]; offsets: int64[V+1] (CSR). -> (keep bool per frame; run int32 per frame: the
+    frames a kept frame stands for, 0 at a dropped one). max_dist 0 is the lossless choice: a dropped frame equals its anchor,
+    so every search finds the same (frame, video) facts; max_dist < 0 or max_run == 1 drops nothing."""
+    max_dist, max_run = check_run_rule(max_dist, max_run)
+    frames, offsets, _ = _library(frames, offsets)
+    if offsets[0] != 0 or (np.diff(offsets) < 0).any():
+        raise ValueError("offsets must be a CSR over the frame hashes")
+    n = frames.shape[0]
+    if max_dist < 0 or n == 0:
+        return np.ones(n, dtype=bool), np.ones(n, dtype=np.int32)
+    keep, run = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    _lib.check(_lib.ensure().hvd_vpdq_frame_runs(_ptr(frames), offsets.ctypes.data, offsets.size - 1, max_dist, max_run,
+                                                 keep.ctypes.data, run.ctypes.data))
+    return keep != 0, run
+
+
+RepeatedFrames = namedtuple("RepeatedFrames", "hashes positions dropped runs")
+
+
+def without_repeated_frames(video_hashes, max_dist: int, max_run: int = 0, positions=None) -> RepeatedFrames:
+    """The library with every run of near-identical consecutive frames (a held shot, a slide, a title card, a freeze frame,
+    frames repeated by a frame-rate conversion) collapsed to its first frame, as if the quality filter had removed the rest:
+    every search of this module then runs on the result as it is. video_hashes: a sequence of VpdqHash / bytes; max_dist /
+    max_run: `frame_runs` (max_dist has no default; 0 is the lossless choice).
+    -> RepeatedFrames(hashes: one `bytes` per input video; positions: one int32 array per video, the index of every kept frame
+    in its input video -- or the input `positions` (one int sequence per video) of the kept frames --, for the positions=
+    argument of find_excerpts / find_segmented_excerpts / find_rate_excerpts, so timelines do not shift: a kept frame carries
+    the position of the FIRST frame of its run; dropped: int64[V]; runs: one int32 array per video, for every kept frame the
+    number of frames it stands for)."""
+    check_run_rule(max_dist, max_run)
+    blobs = [hash_blob(h) for h in video_hashes]
+    frames, offsets, lengths = pack_hashes(blobs)
+    pos = _positions_of(positions, blobs, lengths)
+    if pos is None:
+        pos = (np.arange(frames.shape[0], dtype=np.int64) - np.repeat(offsets[:-1], lengths)).astype(np.int32)
+    keep, run = frame_runs(frames, offsets, max_dist, max_run)
+    drop = ~keep
+    hashes = [frames[lo:hi][keep[lo:hi]].tobytes() for lo, hi in zip(offsets[:-1], offsets[1:])]
+    kept_pos = [pos[lo:hi][keep[lo:hi]] for lo, hi in zip(offsets[:-1], offsets[1:])]
+    runs = [run[lo:hi][keep[lo:hi]] for lo, hi in zip(offsets[:-1], offsets[1:])]
+    before = np.concatenate([[0], np.cumsum(drop, dtype=np.int64)])
+    dropped = before[offsets[1:]] - before[offsets[:-1]]
+    return RepeatedFrames(hashes, kept_pos, dropped, runs)
+
+
 # ------------------------------------------------ new files against the library: filtered ingest (DESIGN 4.17) ------
 
 NewDuplicates = namedtuple("NewDuplicates", "pairs dropped spread")

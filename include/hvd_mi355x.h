@@ -40,7 +40,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross, then + hvd_rate_segments_scratch_bytes, hvd_dev_vpdq_align_rate_segments, hvd_vpdq_align_rate_segments; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross, then + hvd_rate_segments_scratch_bytes, hvd_dev_vpdq_align_rate_segments, hvd_vpdq_align_rate_segments, then + hvd_dev_frame_runs, hvd_vpdq_frame_runs; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -282,6 +282,16 @@ int hvd_vpdq_match_videos(const uint8_t* frames, const int64_t* offsets, int64_t
  * [0, 127]. Upload, FP4 image, frame -> video map, then hvd_dev_vpdq_frame_spread; under a device group it runs on the calling
  * thread's current context alone. */
 int hvd_vpdq_frame_spread(const uint8_t* frames, const int64_t* offsets, int64_t V, int max_dist, int32_t* out_spread);
+
+/* One keyframe per run of near-identical consecutive frames: the host-buffer form of hvd_dev_frame_runs, whose
+ * comment holds the rule and what follows from it. frames / offsets / V as hvd_vpdq_match_videos; out_keep int32 per frame, 1 or
+ * 0; out_run int32 per frame (may be NULL), the frames a kept frame stands for, 0 at a dropped one. max_dist in [0, 127] (0: a
+ * dropped frame equals its anchor -- the lossless choice), max_run in [0, 2^20] (0 = no limit). A parameter out of range, a CSR
+ * that does not start at 0 or decreases, a NULL buffer: HVD_ERR_ARG, returned BEFORE the library asks whether a device is
+ * there. Then: upload of hashes and offsets, hvd_dev_frame_runs, copy back, one synchronisation; library-owned scratch; under
+ * a device group it runs on the calling thread's current context alone. */
+int hvd_vpdq_frame_runs(const uint8_t* frames, const int64_t* offsets, int64_t V, int max_dist, int max_run, int32_t* out_keep,
+                        int32_t* out_run);
 
 /* Query-set x target-set form of the same search: the steady-state workload after the first
  * run (new videos against the existing library; semantics of VpTreeManager.search_file,
@@ -873,6 +883,34 @@ int hvd_dev_common_frames(const void* d_spread, const void* d_offsets, int64_t V
  * library through the compaction hvd_dev_compact_kept does on its hashes. Enqueued on the library stream, no host
  * synchronisation; library-owned scratch. */
 int hvd_dev_gather_kept_i32(const void* d_in, const void* d_keep, int64_t n, void* d_out);
+/* The static-scene filter: one keyframe per run of near-identical consecutive frames -- a held shot, a slide, a
+ * title card, a freeze frame, the repeated frames of a 24 -> 60 fps conversion. The rule, integers only, one answer per library.
+ * d_hashes 32 B per frame, d_offsets int64[V+1] (a CSR over the n frames). For every video, over its frames in CSR order:
+ *     anchor = the first frame; keep it; run[anchor] = 1
+ *     for each later frame f, in order:
+ *         if hamming(h_f, h_anchor) <= max_dist and (max_run == 0 or run[anchor] < max_run):
+ *             drop f; run[anchor] += 1; run[f] = 0
+ *         else:
+ *             anchor = f; keep it; run[f] = 1
+ * -> d_out_keep int32[n], 1 or 0, and d_out_run int32[n] (may be NULL): the number of frames a kept frame stands for, 0 at a
+ * dropped frame. A frame is compared with its ANCHOR, not with its predecessor, so slow drift cannot chain a whole video into
+ * one run. What follows from the rule:
+ *   (a) the first frame of every non-empty video is kept;
+ *   (b) every dropped frame is within max_dist of the nearest kept frame before it in its video, and fewer than max_run frames
+ *       behind it when max_run > 0;
+ *   (c) for two consecutive kept frames k1 < k2 of one video, hamming(k1, k2) > max_dist or run[k1] == max_run;
+ *   (d) run sums to each video's length;
+ *   (e) with max_run == 0 the rule is idempotent: applied to its own output it drops nothing;
+ *   (f) with max_run == 1 nothing is dropped;
+ *   (g) with max_dist == 0 a dropped frame EQUALS its anchor, so the set of (frame, video) hit facts of any search is unchanged
+ *       and only the counts shrink: 0 is the lossless choice.
+ * max_dist in [0, 127], max_run in [0, 2^20] (0 = no limit), V and n not negative: HVD_ERR_ARG otherwise, nothing launched.
+ * d_out_keep is the d_quality operand of hvd_dev_compact_kept / hvd_dev_kept_positions with min_quality 1; the kept frame
+ * carries the position of the FIRST frame of its run. One launch, enqueued on the library stream, no host synchronisation,
+ * nothing allocated; ranges are clamped to [0, n], so offsets that are no CSR over n give other flags, never an access outside
+ * the buffers. A video is one wave's, however long it is. */
+int hvd_dev_frame_runs(const void* d_hashes, const void* d_offsets, int64_t V, int64_t n, int max_dist, int max_run,
+                       void* d_out_keep, void* d_out_run);
 /* Device-resident form of hvd_vpdq_frame_spread_cross: operands as hvd_dev_vpdq_match_videos_cross without exclusion maps,
  * d_spread_q int32[nq], d_spread_t int32[nt]. The compare and the key set of that search without its fold (rank 0 of 1): a
  * side-0 key (query frame f, target video) adds one to d_spread_q[f], a side-1 key (target frame g, query video) one to
