@@ -205,6 +205,7 @@ void shutdown_context(int idx) {
             (void)hipStreamDestroy(g.m_srv_stream);
         }
         if (g.m_pin) (void)hipHostFree(g.m_pin);
+        if (g.d2h_pin) (void)hipHostFree(g.d2h_pin);
         g.~Ctx();
         new (&g) Ctx();
     }
@@ -538,6 +539,23 @@ int hvd_memcpy_h2d(void* d_dst, const void* src, size_t bytes) {
 
 int hvd_memcpy_d2h(void* dst, const void* d_src, size_t bytes) {
     if (int rc = need_ready()) return rc;
+    // A copy into pageable memory is staged by the runtime through a copy kernel and a buffer of its own; a small one (a pair
+    // count, a few thousand records: what every search reads back after every pass) costs less through the context's page-locked
+    // buffer and a memcpy. Same ordering: the call returns when dst is complete.
+    if (bytes != 0 && bytes <= kSmallD2hMax) {
+        std::lock_guard<std::mutex> lk(g.d2h_mu);
+        if (!g.d2h_pin && !g.d2h_pin_failed && hipHostMalloc(&g.d2h_pin, kSmallD2hMax, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();  // (no sticky error: the direct path below serves the copy)
+            g.d2h_pin = nullptr;
+            g.d2h_pin_failed = true;
+        }
+        if (g.d2h_pin) {
+            HIP_TRY(hipMemcpyAsync(g.d2h_pin, d_src, bytes, hipMemcpyDeviceToHost, g.stream));
+            HIP_TRY(hipStreamSynchronize(g.stream));
+            memcpy(dst, g.d2h_pin, bytes);
+            return HVD_OK;
+        }
+    }
     HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     return HVD_OK;
@@ -642,6 +660,10 @@ int hvd_debug_set(const char* key, int value) {
         hvd::g_mfma_queue_packed = value != 0;
         return HVD_OK;
     }
+    if (strcmp(key, "mfma_probe_packed") == 0) {  // 0: the probe of an index-eligible pass reads the FP4 image like every other probe
+        hvd::g_mfma_probe_packed = value != 0;
+        return HVD_OK;
+    }
     if (strcmp(key, "mfma_auto_mid_max_x100") == 0) {  // ... up to this many survivors per 1024-pair tile (x 0.01)
         if (value < 0) return fail(HVD_ERR_ARG, "mfma_auto_mid_max_x100 must not be negative");
         hvd::g_mfma_auto_mid_max_x100 = (uint32_t)value;
@@ -739,6 +761,10 @@ int hvd_debug_get(const char* key, int* out_value) {
     }
     if (strcmp(key, "copy_nt") == 0) {  // (host only: no device needed)
         *out_value = hvd::stream_copy_nt_level();
+        return HVD_OK;
+    }
+    if (strcmp(key, "memcpy_d2h_small_max") == 0) {  // (host only) hvd_memcpy_d2h: the largest copy that takes the page-locked bounce buffer
+        *out_value = (int)kSmallD2hMax;
         return HVD_OK;
     }
     {

@@ -32,6 +32,11 @@ int fail(int code, const char* fmt, ...);
         if (r_ != ncclSuccess) return hvdi::fail(HVD_ERR_RCCL, "%s: %s", #expr, ncclGetErrorString(r_)); \
     } while (0)
 
+// hvd_memcpy_d2h: copies of at most this many bytes go through the context's page-locked bounce buffer
+// (scripts/gpu_d2h_time.py, profiles/r23_d2h_time.jsonl: 25.5 -> 13.7 us at 8 B, 26.1 -> 13.9 us at 16 KB; at 64 KB and 256 KB,
+// where the runtime's own path is already the quicker one, still 0.3 - 0.6 us ahead in both rounds: the largest size measured)
+constexpr size_t kSmallD2hMax = 256u * 1024u;
+
 struct Ctx {
     bool ready = false;
     int device = -1;
@@ -65,6 +70,12 @@ struct Ctx {
     hipStream_t m_srv_stream = nullptr;  // the match server's own stream (k_match_server stays resident between calls)
     int32_t m_launch = 0;                // id of the last server launch; hdr[7] == m_launch: that server has left
     std::mutex m_mu;
+    // page-locked bounce buffer of hvd_memcpy_d2h's small copies (kSmallD2hMax bytes, allocated at the first such copy, freed
+    // with the context; d2h_mu: two host threads on one context take turns with it). d2h_pin_failed: it could not be had, and
+    // every copy takes the direct path.
+    void* d2h_pin = nullptr;
+    bool d2h_pin_failed = false;
+    std::mutex d2h_mu;
     // grow-only device scratch of the host-buffer entry points and of the video-level reduction: nothing is
     // allocated or freed per call once the sizes have been seen (h_mu serialises the users)
     enum Scr {

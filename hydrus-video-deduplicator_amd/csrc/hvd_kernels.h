@@ -36,7 +36,7 @@ bool allpairs_geometry(uint32_t n, int variant, uint32_t* rows_per_block, uint32
 
 // FP4-MFMA forms (k_hamming_mfma.hip): the variants of hvd_mfma_forms.h's table, and its auto variant. d_img:
 // fp4_rows_padded(n)*128 bytes. The knobs (hvd_debug_set keys of the same names; defined in one block in k_hamming_mfma.hip):
-extern uint32_t g_mfma_col_chunk_max, g_mfma_auto_mid, g_mfma_auto_mid_max_x100, g_mfma_queue_packed;
+extern uint32_t g_mfma_col_chunk_max, g_mfma_auto_mid, g_mfma_auto_mid_max_x100, g_mfma_queue_packed, g_mfma_probe_packed;
 extern int g_mfma_force_sel;
 hipError_t launch_expand_fp4(const void* d_db, uint32_t n, void* d_img, hipStream_t s);
 hipError_t launch_pack_fp4(const void* d_img, uint32_t n, void* d_db, hipStream_t s);  // image -> packed 32-byte hashes

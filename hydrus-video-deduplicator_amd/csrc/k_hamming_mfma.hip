@@ -904,6 +904,8 @@ struct ProbeRule {  // survivors among `pairs` sampled pairs -> form (probe_deci
 constexpr uint32_t kNoIndex = 0xFFu;
 __device__ void probe_decide(uint32_t* __restrict__ select, uint32_t lo, uint32_t hi, uint32_t mix, uint32_t close,
                              const ProbeRule& rule);
+__device__ __forceinline__ void probe_finish(uint32_t cnt, uint32_t cnt_hi, uint32_t cnt_mix, uint32_t close,
+                                             uint32_t* __restrict__ select, const ProbeRule& rule);
 
 __global__ __launch_bounds__(256) void k_prefilter_probe(const uint4* __restrict__ img_q, uint32_t nq,
                                                          const uint4* __restrict__ img_t, uint32_t nt, uint32_t max_dist,
@@ -960,6 +962,13 @@ __global__ __launch_bounds__(256) void k_prefilter_probe(const uint4* __restrict
         }
     }
     if (r >= rows) cnt = cnt_hi = cnt_mix = close = 0;
+    probe_finish(cnt, cnt_hi, cnt_mix, close, select, rule);
+}
+
+// The probes' common ending: the lanes' four sums become the workgroup's, the workgroup's are added to the select words, and
+// the last workgroup decides.
+__device__ __forceinline__ void probe_finish(uint32_t cnt, uint32_t cnt_hi, uint32_t cnt_mix, uint32_t close,
+                                             uint32_t* __restrict__ select, const ProbeRule& rule) {
     for (int off = 32; off > 0; off >>= 1) {
         cnt += __shfl_down(cnt, off);
         cnt_hi += __shfl_down(cnt_hi, off);
@@ -994,6 +1003,76 @@ __global__ __launch_bounds__(256) void k_prefilter_probe(const uint4* __restrict
             probe_decide(select, atomicAdd(&select[hvd::kSelSurvivorsLo], 0u), atomicAdd(&select[hvd::kSelSurvivorsHi], 0u),
                          atomicAdd(&select[hvd::kSelSurvivorsMix], 0u), atomicAdd(&select[hvd::kSelIdxClose], 0u), rule);
     }
+}
+
+// The probe of an index-eligible self pass, on the packed hashes the pass was given (index_eligible: d_db is there; the index
+// build and the join's full check read the same array). The sample, the grid and the four sums are k_prefilter_probe's block-
+// distance branch, integer for integer: chunk c of the image is the 32 sign nibbles of packed word c, low half = block 2c,
+// high half = block 2c + 1 (key_of, k_hamming_index.hip), so a chunk's popcount over its nibbles is the word's popcount and a
+// block's distance is a 16-bit half's. 8 words per hash instead of 32: a quarter of the xors and popcounts, 32 B per hash read
+// instead of 128, 2 KiB of columns in LDS instead of 8.
+// `close` counts halves of popcount <= R (R = 0 | 1, index_radius) two at a time: with d = x ^ y, t = d (R = 0) or d & (d - 1)
+// with the subtraction per 16-bit half (R = 1) is zero exactly in the halves within R; min(t, 1) per half is 1 in the others,
+// and the per-half sums over a lane's <= 64 columns x 8 words stay below 2^16.
+typedef uint16_t probe_u16x2 __attribute__((ext_vector_type(2)));
+
+template <uint32_t R>
+__device__ __forceinline__ probe_u16x2 halves_beyond(uint32_t d) {
+    static_assert(R <= 1u, "the pigeonhole index's block radius");
+    probe_u16x2 t = __builtin_bit_cast(probe_u16x2, d);
+    const probe_u16x2 one = {1, 1};
+    if (R == 1u) t &= t - one;
+    // (hipcc turns a vector min(t, 1) into a compare, a select and a pack per half: eleven instructions per word instead of one)
+    probe_u16x2 nz;
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(nz) : "v"(t), "v"(one));
+    return nz;
+}
+
+template <uint32_t R>
+__device__ __forceinline__ void probe_packed_count(const uint32_t (&q)[8], const uint4 (*cols)[2], uint32_t m, uint32_t max_dist,
+                                                   uint32_t& cnt, uint32_t& cnt_hi, uint32_t& cnt_mix, uint32_t& close) {
+    probe_u16x2 far = {0, 0};
+    for (uint32_t k = 0; k < m; ++k) {
+        const uint4 c0 = cols[k][0], c1 = cols[k][1];
+        const uint32_t d[8] = {q[0] ^ c0.x, q[1] ^ c0.y, q[2] ^ c0.z, q[3] ^ c0.w, q[4] ^ c1.x, q[5] ^ c1.y, q[6] ^ c1.z, q[7] ^ c1.w};
+        uint32_t u[4];
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) {
+            u[c2] = __popc(d[2 * c2]) + __popc(d[2 * c2 + 1]);
+            far += halves_beyond<R>(d[2 * c2]) + halves_beyond<R>(d[2 * c2 + 1]);
+        }
+        cnt += u[0] + u[1] <= max_dist ? 1u : 0u;
+        cnt_hi += u[2] + u[3] <= max_dist ? 1u : 0u;
+        cnt_mix += u[0] + u[3] <= max_dist ? 1u : 0u;
+    }
+    close = 16u * m - ((uint32_t)far.x + (uint32_t)far.y);
+}
+
+__global__ __launch_bounds__(256) void k_prefilter_probe_packed(const uint4* __restrict__ db, uint32_t n, uint32_t max_dist,
+                                                                uint32_t* __restrict__ select, const ProbeRule rule) {
+    __shared__ uint4 cols[kProbeColsPerWg][2];
+    const uint32_t rows = min(n, kProbeRows), ncols = min(n, kProbeCols);
+    const uint32_t rstride = n / rows, cstride = n / ncols;
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t ri = min(r, rows - 1u) * rstride;
+    const uint4 q0 = db[(size_t)ri * 2u], q1 = db[(size_t)ri * 2u + 1u];
+    const uint32_t q[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+    if (threadIdx.x < 2u * kProbeColsPerWg) {  // two threads fetch one column's two halves (the same columns as the image probe's)
+        const uint32_t cl = threadIdx.x >> 1, h = threadIdx.x & 1u;
+        const uint32_t c = blockIdx.y * kProbeColsPerWg + cl;
+        const uint32_t ci = min(min(c, ncols - 1u) * cstride + cstride / 2u, n - 1u);
+        cols[cl][h] = db[(size_t)ci * 2u + h];
+    }
+    __syncthreads();
+    const uint32_t c0 = blockIdx.y * kProbeColsPerWg;
+    const uint32_t m = c0 >= ncols ? 0u : min(kProbeColsPerWg, ncols - c0);
+    uint32_t cnt = 0, cnt_hi = 0, cnt_mix = 0, close = 0;
+    if (rule.idx_r == 0u)
+        probe_packed_count<0u>(q, cols, m, max_dist, cnt, cnt_hi, cnt_mix, close);
+    else
+        probe_packed_count<1u>(q, cols, m, max_dist, cnt, cnt_hi, cnt_mix, close);
+    if (r >= rows) cnt = cnt_hi = cnt_mix = close = 0;
+    probe_finish(cnt, cnt_hi, cnt_mix, close, select, rule);
 }
 
 // The hit handler's launch-uniform arguments live in device memory (written by this one-lane kernel in stream order
@@ -1065,6 +1144,8 @@ uint32_t g_mfma_auto_mid = kFormAutoMidDefault;
 uint32_t g_mfma_auto_mid_max_x100 = 500;
 // 0: the pair queue settles from the FP4 images even when packed hashes are at hand (tests)
 uint32_t g_mfma_queue_packed = 1;
+// 0: the probe of an index-eligible pass counts over the FP4 image like every other (k_prefilter_probe; tests, A/B runs)
+uint32_t g_mfma_probe_packed = 1;
 // which 128 bits the first stage sees: -1 the probe chooses (explicit forms: bits 0..127); 0 | 1 | 2 forced
 int g_mfma_force_sel = -1;
 
@@ -1236,8 +1317,13 @@ static hipError_t launch_auto(const MfmaPass& p, uint32_t idx_r) {
     const IndexRule irule = idx_r != kNoIndex ? index_rule(a, idx_r) : IndexRule{};
     const ProbeRule rule = {(uint64_t)rows * cols, 8192u, kFormFetch, mid, kFormRegister, 0.01f * (float)g_mfma_auto_mid_max_x100,
                             g_mfma_force_sel, idx_r, irule};
-    hipLaunchKernelGGL(k_prefilter_probe, dim3((rows + 255u) / 256u, (cols + kProbeColsPerWg - 1u) / kProbeColsPerWg), dim3(256), 0, s,
-                       p.row_image(), p.rows(), p.col_image(), a.n, a.max_dist, sel, rule);
+    const dim3 probe_grid((rows + 255u) / 256u, (cols + kProbeColsPerWg - 1u) / kProbeColsPerWg);
+    // (an index-eligible pass is a self pass with its packed hashes at hand: index_eligible)
+    if (idx_r != kNoIndex && g_mfma_probe_packed)
+        hipLaunchKernelGGL(k_prefilter_probe_packed, probe_grid, dim3(256), 0, s, (const uint4*)a.d_db, a.n, a.max_dist, sel, rule);
+    else
+        hipLaunchKernelGGL(k_prefilter_probe, probe_grid, dim3(256), 0, s, p.row_image(), p.rows(), p.col_image(), a.n, a.max_dist, sel,
+                           rule);
     if (idx_r != kNoIndex) {
         e = launch_index_decide(a, sel, irule, s);
         if (e != hipSuccess) return e;

@@ -569,6 +569,9 @@ int hvd_get_pdq_dct_mode(void);
  *   "mfma_auto_mid" 0|18, "mfma_auto_mid_max_x100" n       (auto variant: may it pick the panel-mark queue form -- 18 -- and the
  *                                                           survivor density per 1024-pair tile, x 0.01, up to which it does -- 500)
  *   "mfma_queue_packed" 0|1                                (0: the pair queue settles from the FP4 images only)
+ *   "mfma_probe_packed" 0|1                                (auto variant, index-eligible self pass: the probe counts over the packed
+ *                                                           hashes -- 1, default -- | over the FP4 image like every other probe; the
+ *                                                           words it leaves, "mfma_probe_close" among them, are the same integers)
  *   "allpairs_index" -1|0|1                                (auto variant, self pass, max_dist <= 31: the exact pigeonhole index path --
  *                                                           -1 the device decides from its histograms (default) | never | whenever
  *                                                           eligible; not the query x target or video searches)
@@ -595,6 +598,10 @@ int hvd_debug_set(const char* key, int value);
  * "mfma_auto_form" keeps meaning the matrix-core form the probe chose, also when the pass ran on the pigeonhole index.
  * "mfma_probe_close": over the same sample, the 16-bit block pairs (16 per hash pair) within the pigeonhole index's block radius
  * (1 for max_dist 16..31, 0 below); 0 when the pass was not index-eligible (the probe sums it only then). Read-only.
+ * (hvd_debug_set "mfma_probe_packed" 1, the default: on such a pass these words are counted over the packed hashes instead of
+ * the FP4 image; 0: over the image as on every other pass. The same integers either way, and process-wide, so all ranks agree.)
+ * "memcpy_d2h_small_max": the largest hvd_memcpy_d2h copy, in bytes, that goes through the context's page-locked bounce buffer
+ * (larger ones are copied straight into the destination); a constant of the build, needs no device.
  * "allpairs_index_used": 1 if the last auto-variant pass ran on the pigeonhole index, else 0; "allpairs_index_kcand": its exact
  * candidate count / 1000 (0 when the probe's estimate kept the histograms from being built).
  * "allpairs_index_cand_lo": the low 31 bits of that exact count; "allpairs_index_max_walk": its longest work item, max over
