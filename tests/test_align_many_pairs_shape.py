@@ -1,6 +1,7 @@
-"""Source-shape guard (CPU test) for tests/test_gpu_align_many_pairs.py and tests/test_gpu_rates_many_pairs.py: their pair lists
+"""Source-shape guard (CPU test) for tests/test_gpu_align_many_pairs.py, tests/test_gpu_rates_many_pairs.py and
+tests/test_gpu_rate_segments_many_pairs.py: their pair lists
 are sized by two numbers that live only in the kernels' sources -- the grid cap of the LDS launches and the slots of the scratch
-launches, both in the launch helper of csrc/hvd_valign_dev.h that the three kernel files share. If one of them is raised, the
+launches, both in the launch helper of csrc/hvd_valign_dev.h that the four kernel files share. If one of them is raised, the
 many-pairs tests no longer make a workgroup serve a second pair; this test then says so, rather than the coverage going. The
 lists of the rate kernel are built here as well, with every claim their construction makes checked against the numpy
 restatement: that needs no device."""
@@ -11,12 +12,13 @@ import numpy as np
 import pytest
 
 import test_gpu_align_many_pairs as MP
+import test_gpu_rate_segments_many_pairs as RSMP
 import test_gpu_rates_many_pairs as RMP
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hydrus-video-deduplicator_amd", "csrc")
 
 
-@pytest.mark.parametrize("src", ["k_valign.hip", "k_valign_segments.hip", "k_valign_rates.hip"])
+@pytest.mark.parametrize("src", ["k_valign.hip", "k_valign_segments.hip", "k_valign_rates.hip", "k_valign_rate_segments.hip"])
 def test_grid_cap_and_slots_are_what_the_many_pairs_tests_assume(src):
     text = open(os.path.join(CSRC, src)).read()
     # both launches are grid-stride loops over the pair list
@@ -44,6 +46,14 @@ def test_the_rate_lists_reach_a_third_lds_row_and_a_fourth_scratch_row():
     assert RMP.kind_columns().size == 2 * MP.LDS_GRID + 77 > 2 * MP.LDS_GRID
     assert len(RMP.SLOT_PATTERNS[0]) * MP.SCRATCH_SLOTS + len(RMP.SLOT_FOURTH) == 3 * MP.SCRATCH_SLOTS + 5
     assert MP.SCRATCH_SLOTS % len(RMP.SLOT_PATTERNS) == 0 and len(RMP.TRIPLES) <= 77
+
+
+def test_the_rate_segments_lists_reach_a_third_lds_row_and_a_fourth_scratch_row():
+    assert (RSMP.LDS_GRID, RSMP.SCRATCH_SLOTS) == (MP.LDS_GRID, MP.SCRATCH_SLOTS)
+    assert RSMP.kind_columns().size == 2 * MP.LDS_GRID + 77 > 2 * MP.LDS_GRID
+    assert len(RSMP.SLOT_PATTERNS[0]) * MP.SCRATCH_SLOTS + len(RSMP.SLOT_FOURTH) == 3 * MP.SCRATCH_SLOTS + 5
+    assert MP.SCRATCH_SLOTS % len(RSMP.SLOT_PATTERNS) == 0 and len(RSMP.TRIPLES) <= 77
+    assert 77 + len(RSMP.KINDS) ** 2 <= MP.LDS_GRID  # the columns that enumerate the transitions have their two rows
 
 
 def test_the_rate_lists_hold_what_their_construction_claims():
