@@ -722,6 +722,14 @@ int hvd_debug_set(const char* key, int value) {
         for (int k = 0; k < g_nctx; ++k) g_ctx[k].v_fail_rank = value;
         return HVD_OK;
     }
+    if (strcmp(key, "match_seq") == 0) {  // tests only (include/hvd_mi355x_bench.h): the call counter of hvd_match_two's small routes, as 32 bits
+        std::lock_guard<std::mutex> lk(g.m_mu);
+        g.m_seq = (uint32_t)value;
+        // the answer word still holds the number of the last call: a counter set BACK must not meet it again (no call's
+        // number equals the counter it follows, in 32 bits or in the server's 21)
+        if (g.m_pin) __atomic_store_n(reinterpret_cast<volatile int32_t*>(g.m_pin + hvd::match_two_small_limit()) + 2, value, __ATOMIC_RELEASE);
+        return HVD_OK;
+    }
 #endif
     if (strcmp(key, "vmatch_exchange") == 0) {
         if (value < 0 || value > 2) return fail(HVD_ERR_ARG, "vmatch_exchange: 0 iff world > 1, 1 always, 2 never (partial results)");
@@ -824,6 +832,13 @@ int hvd_debug_get(const char* key, int* out_value) {
         uint32_t wgs = 0;
         HIP_TRY(hvd::index_join_workgroups(0u, &wgs));  // (the grid of a pass over at most 2^20 hashes)
         *out_value = (int)wgs;
+        return HVD_OK;
+    }
+    if (strcmp(key, "match_seq") == 0 || strcmp(key, "match_server_launches") == 0) {
+        // tests only: the number of the last small-route call of hvd_match_two (its 32 bits as an int), and the id of the last
+        // match server launched (it rises by one per launch: which route served a run of calls, and whether a server had left)
+        std::lock_guard<std::mutex> lk(g.m_mu);
+        *out_value = key[8] == 'r' ? (int)g.m_launch : (int)g.m_seq;
         return HVD_OK;
     }
 #endif

@@ -66,7 +66,7 @@ struct Ctx {
     size_t m_a_cap = 0, m_b_cap = 0, m_f_cap = 0;
     // pinned, device-visible staging of the small-operand path of hvd_match_two: operands, then the two counters
     uint8_t* m_pin = nullptr;
-    int32_t m_seq = 0;
+    uint32_t m_seq = 0;                  // call counter of the small-operand path; wraps past 2^32 - 1 to 1 (0 is skipped)
     hipStream_t m_srv_stream = nullptr;  // the match server's own stream (k_match_server stays resident between calls)
     int32_t m_launch = 0;                // id of the last server launch; hdr[7] == m_launch: that server has left
     std::mutex m_mu;

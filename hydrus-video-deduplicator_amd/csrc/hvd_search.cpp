@@ -455,7 +455,8 @@ int hvd_match_two(const uint8_t* a, int64_t na, const uint8_t* b, int64_t nb, in
         volatile int32_t* ph = reinterpret_cast<volatile int32_t*>(g.m_pin + small);
         memcpy(g.m_pin, a, 32 * (size_t)na);
         memcpy(pb, b, 32 * (size_t)nb);
-        const int32_t seq = ++g.m_seq == 0 ? ++g.m_seq : g.m_seq;
+        if (++g.m_seq == 0u) g.m_seq = 1u;  // (unsigned: the step past 0x7FFFFFFF and the wrap are defined; 0 is never a call's number)
+        const int32_t seq = (int32_t)g.m_seq;
         if (g_match_server) {
             // Round 5: post the request to the resident match server (k_match_server) and poll for the answer -- no launch and
             // no synchronisation per call while calls come back to back (the VP-tree's pattern); the server is (re)started

@@ -37,7 +37,14 @@ int hvd_debug_parallel_copy(void* dst, const void* src, size_t n, int threads);
  * Tests only, same build rule: hvd_debug_set("hash_staging_bytes", v) lowers the frames a host-buffer hashing entry
  * (hvd_pdq_hash_frames_*) stages per batch from 1 GiB to v >= 4096 bytes (at least one frame), so that the multi-batch
  * paths run at shapes that take milliseconds; 0 = the default. Results do not depend on it, except that the autocrop
- * entries refuse (HVD_ERR_ARG) a video with more frames than one batch holds. */
+ * entries refuse (HVD_ERR_ARG) a video with more frames than one batch holds.
+ * Tests only, same build rule: hvd_debug_set("match_seq", v) sets the call counter of hvd_match_two's two small-operand
+ * routes to v, taken as 32 bits; the next such call carries the number after it (v + 1, or 1 after 0xFFFFFFFF: 0 is
+ * skipped), so that the wrap of the 21 bits the match server's request word carries, the step past 0x7FFFFFFF and the wrap
+ * of the counter itself are reached in a few calls instead of millions. The answer word is set to v as well: it cannot be
+ * taken for the next call's. hvd_debug_get of the same key reads the counter (its 32 bits as an int). Answers do not
+ * depend on it. hvd_debug_get("match_server_launches") returns the id of the last match server launched: it rises by one
+ * per launch, and stays when the per-call kernel or the device-buffer kernel serves a call. */
 
 /* Test hooks: the pieces of the video search's data-dependent bit order ("vmatch_bit_order"), one at a time, so that
  * tests/test_bit_order_cpu.py and tests/test_gpu_bit_order.py can compare each with numpy. Every one of them calls what the
