@@ -6,6 +6,8 @@ rates, the clears and the three ways out are the kernel's, statement by statemen
 Without a fault the model must give the records of the restatement (rate_segments_helpers), whatever the pair before left
 behind; with one of the switches F1..F6 it is the kernel with that one re-arming step missing or that one comparison off by
 one, and the many-pairs lists have to show it. The model also says which (round, rate) evaluations the skip passed over.
+GRID_FAULTS G1..G6 are slips of one line of the rounds each -- a slack not scaled, a nibble read through three bits, a tie
+the wrong way, a window not clamped, a tolerance off by one -- for tests/test_rate_segments_grid_cpu.py, whose inputs show them.
 Nothing here touches the device."""
 import hashlib
 
@@ -27,12 +29,22 @@ FAULTS = {
     "F5": "the skip for good compares ub_r <= min_band_votes",
     "F6": "the histogram is cleared up to the nbins of the evaluation before, not its own",
 }
+# the slips of one line each that tests/test_rate_segments_grid_cpu.py switches on (kept apart from FAULTS: the many-pairs lists
+# are not built to show them)
+GRID_FAULTS = {
+    "G1": "pass 2 is handed slack in place of slack * max(num, den)",
+    "G2": "pass 1 uses slack * num",
+    "G3": "the rounds unpack the nibbles of the list with & 7",
+    "G4": "ties go to the later rate (S >= win_S)",
+    "G5": "best_offset's window is not clamped at nbins - 1",
+    "G6": "the hit test is d >= max_dist",
+}
 
 
 class Pair:
     """What the kernel makes of one list entry: pair_geometry<true> on the DEVICE positions, and the hit set."""
 
-    def __init__(self, frames, offsets, positions, a, b, rates, slack, max_dist=31):
+    def __init__(self, frames, offsets, positions, a, b, rates, slack, max_dist=31, faults=frozenset()):
         V = len(offsets) - 1
         self.a, self.b = int(a), int(b)
         self.bad, self.empty, self.bins = a >= V or b >= V, False, 0
@@ -52,7 +64,8 @@ class Pair:
         self.bad = self.bins > MAX_BINS
         self.wa, self.wb = (self.na + 31) // 32, (self.nb + 31) // 32
         self.need = self.bins + 2 * (self.wa + self.wb)
-        self.i, self.j = np.nonzero(AH.hamming_matrix(frames[sa], frames[sb]) <= max_dist)
+        dist = AH.hamming_matrix(frames[sa], frames[sb])
+        self.i, self.j = np.nonzero(dist < max_dist if "G6" in faults else dist <= max_dist)
 
     @property
     def big(self):
@@ -91,12 +104,17 @@ def _count_bits(words, at, n):
     return (int(nz.size), int(nz[0]), int(nz[-1])) if nz.size else (0, U32, 0)
 
 
-def _best_offset(h, slack, dmin):
-    """best_offset of hvd_valign_dev.h on the words h: (S, d) under the tie order, (0, 0) over an empty histogram."""
+def _best_offset(h, slack, dmin, behind=None):
+    """best_offset of hvd_valign_dev.h on the words h: (S, d) under the tie order, (0, 0) over an empty histogram. behind (G5):
+    the words that follow h, which a window without its upper clamp reads (zeros past their end)."""
     n = h.size
-    c = np.concatenate([[0], np.cumsum(h)])
     k = np.arange(n)
-    S = (c[np.minimum(n - 1, k + slack) + 1] - c[np.maximum(k - slack, 0)]) & U32
+    if behind is None:
+        c = np.concatenate([[0], np.cumsum(h)])
+        S = (c[np.minimum(n - 1, k + slack) + 1] - c[np.maximum(k - slack, 0)]) & U32
+    else:
+        c = np.concatenate([[0], np.cumsum(np.concatenate([h, behind[:slack], np.zeros(max(slack - behind.size, 0), np.int64)]))])
+        S = (c[k + slack + 1] - c[np.maximum(k - slack, 0)]) & U32
     top = int(S.max())
     if top == 0:
         return 0, 0
@@ -139,8 +157,8 @@ def serve(wg, P, rates, slack, max_segments, min_band_votes, faults=frozenset())
                     continue
             else:
                 u = None
-            num, den = rates[r]
-            slack_r = slack * max(num, den)
+            num, den = (rates[r][0] & 7, rates[r][1] & 7) if "G3" in faults else rates[r]
+            slack_r = slack * num if "G2" in faults else slack * max(num, den)
             core = num * P.span_a + den * P.span_b + 1
             nbins = core + 2 * slack_r
             dmin = den * int(pb[0]) - num * int(pa[-1])
@@ -159,12 +177,12 @@ def serve(wg, P, rates, slack, max_segments, min_band_votes, faults=frozenset())
                 if q_hits == 0:
                     no_hit = True
                     break
-            S, d = _best_offset(words[:nbins], slack_r, dmin)
+            S, d = _best_offset(words[:nbins], slack_r, dmin, words[nbins:] if "G5" in faults else None)
             trace["evaluated"] += 1
             if u is not None and win_r != R and u > win_S and S < u:
                 trace["again_less"] += 1
             wg.ub[r] = S
-            if win_r == R or S > win_S:  # ties go to the earlier rate
+            if win_r == R or S > win_S or ("G4" in faults and S == win_S):  # ties go to the earlier rate
                 first_r = r if win_r == R else first_r
                 win_S, win_d, win_r, win_u = S, d, r, u
         if no_hit or win_r == R or win_S < min_band_votes:
@@ -173,12 +191,12 @@ def serve(wg, P, rates, slack, max_segments, min_band_votes, faults=frozenset())
             trace["unled"] += 1
         if s != 0 and win_S == min_band_votes and win_u == min_band_votes and win_r != segs[0][10]:
             trace["floor_tie"] += 1
-        num, den = rates[win_r]
+        num, den = (rates[win_r][0] & 7, rates[win_r][1] & 7) if "G3" in faults else rates[win_r]
         if "F2" not in faults:
             words[flagA:flagA + wa + wb] = 0
         live = ~_bits(words, takenA, na)[P.i] & ~_bits(words, takenB, nb)[P.j]
         i, j = P.i[live], P.j[live]
-        on = np.abs(den * pb[j] - num * pa[i] - win_d) <= slack * max(num, den)
+        on = np.abs(den * pb[j] - num * pa[i] - win_d) <= (slack if "G1" in faults else slack * max(num, den))
         _set_bits(words, flagA, i[on])
         _set_bits(words, flagB, j[on])
         qc, qf, ql = _count_bits(words, flagA, na)
