@@ -177,6 +177,13 @@ SIGNATURES = {
     "hvd_dev_frame_runs": (_int, [_vp, _vp, _i64, _i64, _int, _int, _vp, _vp]),
     "hvd_dev_vpdq_match_videos_cross": (_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _int, _int, _int, _vp, _i64,
                                                _vp]),
+    "hvd_dev_video_weights": (_int, [_vp, _vp, _i64, _i64, _int, _vp]),
+    "hvd_dev_vpdq_match_videos_weighted": (_int, [_vp, _i64, _vp, _vp, _int, _int, _vp, _i64, _vp]),
+    "hvd_dev_vpdq_match_videos_cross_weighted": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _int, _int, _vp, _i64,
+                                                        _vp]),
+    "hvd_vpdq_match_videos_weighted": (_int, [_vp, _vp, _i64, _vp, _int, _int, _vp, _i64, C.POINTER(_i64), _vp]),
+    "hvd_vpdq_match_videos_cross_weighted": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _int, _int, _vp, _i64,
+                                                    C.POINTER(_i64), _vp, _vp]),
     # include/hvd_mi355x_bench.h (tests / bench only, not part of the drop-in boundary)
     "hvd_dev_synth_video_frames": (_int, [_vp, _i64, _i64, _int, C.c_uint64, _vp]),
     "hvd_debug_parallel_copy": (_int, [_vp, _vp, C.c_size_t, _int]),

@@ -56,6 +56,35 @@ __device__ __forceinline__ unsigned long long table_insert(unsigned long long* _
     return ~0ull;
 }
 
+// The video pair a key counts for, and the counter it counts in: key (frame f, video v) -> pair (a, b) and is_q (q_hits
+// when set, t_hits otherwise). The one definition for the folds of k_vmatch.hip and k_vmatch_weighted.hip. Symmetric form
+// (rect == 0): the frame's own video against the video it matched, smaller index first. Rectangular form: a side-0 key is a
+// query frame that matched target video v, a side-1 key a target frame that matched query video v.
+struct VideoPairOfKey {
+    uint32_t a, b;
+    bool is_q;
+};
+__device__ __forceinline__ VideoPairOfKey vkey_pair(unsigned long long k, const int32_t* __restrict__ vid_q,
+                                                    const int32_t* __restrict__ vid_t, int rect) {
+    const uint32_t f = vkey_frame(k), v = vkey_video(k);
+    VideoPairOfKey p;
+    if (!rect) {
+        const uint32_t own = (uint32_t)vid_q[f];
+        p.is_q = own < v;
+        p.a = p.is_q ? own : v;
+        p.b = p.is_q ? v : own;
+    } else if (vkey_side(k) == 0u) {
+        p.a = (uint32_t)vid_q[f];
+        p.b = v;
+        p.is_q = true;
+    } else {
+        p.a = v;
+        p.b = (uint32_t)vid_t[f];
+        p.is_q = false;
+    }
+    return p;
+}
+
 #endif  // __HIPCC__
 
 // What the all-pairs kernel needs to reduce to video level instead of appending frame pairs.

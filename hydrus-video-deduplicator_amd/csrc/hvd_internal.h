@@ -82,7 +82,7 @@ struct Ctx {
         S_DB, S_IMG, S_GRP, S_PAIRS, S_DB2, S_IMG2, S_GRP2, S_VIDQ, S_VIDT, S_OFF, S_SET, S_SET2, S_PKEYS, S_PCNT, S_LIST,
         S_LISTALL, S_VOUT, S_FRAMES, S_FSCR, S_HASH, S_QUAL, S_COMPACT, S_COUNTERS, S_BITS, S_BITS2, S_BROWS, S_BCOOC, S_BITS_O, S_BITS2_O,
         S_IMG_O, S_IMG2_O, S_RECTS, S_OFF2, S_POSQ, S_POST, S_APAIRS, S_AOUT, S_ASCR, S_GREC, S_GLEN, S_GSCORE, S_GSCR, S_GLABEL,
-        S_GOUT, S_CQUAL, S_SPREAD, S_COLORS, S_CACC, S_N
+        S_GOUT, S_CQUAL, S_SPREAD, S_COLORS, S_CACC, S_WQ, S_WT, S_N
     };
     void* scr[S_N] = {};
     size_t scr_cap[S_N] = {};

@@ -188,6 +188,19 @@ constexpr unsigned kFrameRunsMaxBlocks = 1024;
 hipError_t launch_frame_runs(const void* d_hashes, const long long* d_offsets, uint32_t V, unsigned long long n, int max_dist,
                              int max_run, int32_t* d_keep, int32_t* d_run, hipStream_t s);
 
+// Duration-weighted video search (k_vmatch_weighted.hip). launch_keys_to_pairs_weighted: launch_keys_to_pairs
+// with an int32 weight per frame of each side (d_weight_t == d_weight_q in the symmetric form); every key adds
+// max_weight ? min(weight, max_weight) : weight to its counter instead of 1. launch_video_weights: d_totals int64[V], the sum
+// of the capped weights per video of a CSR over the n frames (ranges clamped to [0, n]); one launch of at most
+// kVideoWeightsMaxBlocks workgroups, each striding over groups of four videos.
+constexpr unsigned kVideoWeightsMaxBlocks = 1024;
+hipError_t launch_keys_to_pairs_weighted(const unsigned long long* d_src, unsigned long long n_src, const int32_t* d_vid_q,
+                                         const int32_t* d_vid_t, bool rect, const int32_t* d_weight_q, const int32_t* d_weight_t,
+                                         uint32_t max_weight, unsigned long long* d_pkeys, void* d_pcnt, unsigned long long pmask,
+                                         unsigned long long* d_counters, hipStream_t s);
+hipError_t launch_video_weights(const int32_t* d_weight, const long long* d_offsets, uint32_t V, unsigned long long n,
+                                uint32_t max_weight, long long* d_totals, hipStream_t s);
+
 // Time alignment of listed video pairs (k_valign.hip). Two launches: the pairs whose delta histogram fits LDS, then
 // the larger ones out of d_scratch (align_scratch_bytes(max_bins); may be nullptr / 0: such pairs then get the INT32_MIN record).
 size_t align_scratch_bytes(unsigned long long max_bins);

@@ -560,6 +560,10 @@ struct VmArgs {
     int max_dist;                        // [0,127]
     int rank, world;
     int pre_rc = 0;                      // a failure of this rank BEFORE the search (upload): reported through the agreement step
+    // the weighted fold (k_vmatch_weighted.hip): int32 per frame of each side (== each other in the symmetric
+    // form), both or neither; null: the plain fold. max_weight caps a weight, 0 = no cap.
+    const int32_t *d_weight_q = nullptr, *d_weight_t = nullptr;
+    uint32_t max_weight = 0;
 };
 
 int read_counters(unsigned long long* d_counters, unsigned long long out[4]) {
@@ -766,8 +770,14 @@ int vmatch_build(const VmArgs& v) {
     unsigned long long pslots = 0, c[4] = {0, 0, 0, 0};
     if (int rc = build_table({{Ctx::S_PKEYS, 0xFF, (void**)&d_pkeys}, {Ctx::S_PCNT, 0, &d_pcnt}}, 1024, k.n_keys, k.d_counters, c,
                              &pslots, [&](unsigned long long n) -> int {
-                                 HIP_TRY(hvd::launch_keys_to_pairs(k.d_src, k.n_src, v.d_vid_q, v.d_vid_t, v.rect, d_pkeys, d_pcnt,
-                                                                   n - 1, k.d_counters, g.stream));
+                                 // (both tables were cleared for this pass: a weighted pass that runs again adds to zeroes)
+                                 if (v.d_weight_q)
+                                     HIP_TRY(hvd::launch_keys_to_pairs_weighted(k.d_src, k.n_src, v.d_vid_q, v.d_vid_t, v.rect,
+                                                                                v.d_weight_q, v.d_weight_t, v.max_weight, d_pkeys,
+                                                                                d_pcnt, n - 1, k.d_counters, g.stream));
+                                 else
+                                     HIP_TRY(hvd::launch_keys_to_pairs(k.d_src, k.n_src, v.d_vid_q, v.d_vid_t, v.rect, d_pkeys, d_pcnt,
+                                                                       n - 1, k.d_counters, g.stream));
                                  return HVD_OK;
                              }))
         return rc;
@@ -1162,6 +1172,152 @@ int hvd_dev_vpdq_match_videos_cross(const void* d_img_q, int64_t nq, const void*
     return vmatch_on_device(empty, {d_img_q, (uint32_t)nq, d_img_t, (uint32_t)nt, true, (const int32_t*)d_video_q, (const int32_t*)d_video_t,
                                     (const int32_t*)d_excl_q, (const int32_t*)d_excl_t, max_dist, rank, world},
                             d_out, cap, d_count);
+}
+
+/* ---- duration-weighted video search (k_vmatch_weighted.hip) ---- */
+
+int hvd_dev_video_weights(const void* d_weight, const void* d_offsets, int64_t V, int64_t n, int max_weight, void* d_out_totals) {
+    if (max_weight < 0) return fail(HVD_ERR_ARG, "max_weight=%d must not be negative (0 = no cap)", max_weight);
+    if (n < 0 || V < 0 || n >= (1ll << 32) - 1 || V >= (1ll << 31) || !d_offsets) return fail(HVD_ERR_ARG, "bad arguments");
+    if ((n > 0 && !d_weight) || (V > 0 && !d_out_totals)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    if (n > 0 && V == 0) return fail(HVD_ERR_ARG, "n=%lld frames in no video", (long long)n);
+    if (int rc = need_ready()) return rc;
+    HIP_TRY(hvd::launch_video_weights((const int32_t*)d_weight, (const long long*)d_offsets, (uint32_t)V, (unsigned long long)n,
+                                      (uint32_t)max_weight, (long long*)d_out_totals, g.stream));
+    return HVD_OK;
+}
+
+int hvd_dev_vpdq_match_videos_weighted(const void* d_img, int64_t n, const void* d_video, const void* d_weight, int max_weight,
+                                       int max_dist, void* d_out, int64_t cap, void* d_count) {
+    if (int rc = need_ready()) return rc;
+    if (n < 0 || n >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "n=%lld out of range", (long long)n);
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    if (max_weight < 0) return fail(HVD_ERR_ARG, "max_weight=%d must not be negative (0 = no cap)", max_weight);
+    if (cap < 0 || !d_count || (cap > 0 && !d_out)) return fail(HVD_ERR_ARG, "bad output buffer");
+    if (n >= 2 && (!d_img || !d_video || !d_weight)) return fail(HVD_ERR_ARG, "d_img / d_video / d_weight is NULL");
+    VmArgs v{d_img, (uint32_t)n, d_img, (uint32_t)n, false, (const int32_t*)d_video, (const int32_t*)d_video, nullptr, nullptr,
+             max_dist, 0, 1};
+    v.d_weight_q = v.d_weight_t = (const int32_t*)d_weight;
+    v.max_weight = (uint32_t)max_weight;
+    return vmatch_on_device(n < 2, v, d_out, cap, d_count);
+}
+
+int hvd_dev_vpdq_match_videos_cross_weighted(const void* d_img_q, int64_t nq, const void* d_video_q, const void* d_excl_q,
+                                             const void* d_weight_q, const void* d_img_t, int64_t nt, const void* d_video_t,
+                                             const void* d_excl_t, const void* d_weight_t, int max_weight, int max_dist,
+                                             void* d_out, int64_t cap, void* d_count) {
+    if (int rc = need_ready()) return rc;
+    if (nq < 0 || nt < 0 || nq >= (1ll << 32) - 1 || nt >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "set size out of range");
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    if (max_weight < 0) return fail(HVD_ERR_ARG, "max_weight=%d must not be negative (0 = no cap)", max_weight);
+    if (cap < 0 || !d_count || (cap > 0 && !d_out)) return fail(HVD_ERR_ARG, "bad output buffer");
+    if ((d_excl_q == nullptr) != (d_excl_t == nullptr)) return fail(HVD_ERR_ARG, "pass both exclusion maps or neither");
+    const bool empty = nq == 0 || nt == 0;
+    if (!empty && (!d_img_q || !d_img_t || !d_video_q || !d_video_t || !d_weight_q || !d_weight_t))
+        return fail(HVD_ERR_ARG, "NULL image / video map / weights");
+    VmArgs v{d_img_q, (uint32_t)nq, d_img_t, (uint32_t)nt, true, (const int32_t*)d_video_q, (const int32_t*)d_video_t,
+             (const int32_t*)d_excl_q, (const int32_t*)d_excl_t, max_dist, 0, 1};
+    v.d_weight_q = (const int32_t*)d_weight_q;
+    v.d_weight_t = (const int32_t*)d_weight_t;
+    v.max_weight = (uint32_t)max_weight;
+    return vmatch_on_device(empty, v, d_out, cap, d_count);
+}
+
+// The weights of a host library, before the library asks whether a device is there: one per frame, each at least 1, and per
+// video a capped total that the uint32 counters of a record can hold. out_totals: int64[V] or NULL.
+static int check_weights(const int32_t* weights, const int64_t* offsets, int64_t V, int64_t nf, int max_weight, int64_t* out_totals) {
+    if (nf > 0 && !weights) return fail(HVD_ERR_ARG, "weights is NULL");
+    for (int64_t v = 0; v < V; ++v) {
+        uint64_t total = 0;
+        for (int64_t f = offsets[v]; f < offsets[v + 1]; ++f) {
+            if (weights[f] < 1) return fail(HVD_ERR_ARG, "weight %d of frame %lld (video %lld): weights are at least 1", weights[f], (long long)f, (long long)v);
+            total += (uint64_t)(max_weight > 0 && weights[f] > max_weight ? max_weight : weights[f]);
+        }
+        if (total > 0xFFFFFFFFull)
+            return fail(HVD_ERR_ARG, "video %lld: capped weight total %llu exceeds 2^32 - 1 (the counters are uint32)", (long long)v, (unsigned long long)total);
+        if (out_totals) out_totals[v] = (int64_t)total;
+    }
+    return HVD_OK;
+}
+
+static int upload_weights(Ctx::Scr slot, const int32_t* weights, int64_t nf, int32_t** d_w) {
+    if (int rc = scratch(slot, 4 * (size_t)nf, (void**)d_w)) return rc;
+    HIP_TRY(hipMemcpyAsync(*d_w, weights, 4 * (size_t)nf, hipMemcpyHostToDevice, g.stream));
+    return HVD_OK;
+}
+
+int hvd_vpdq_match_videos_weighted(const uint8_t* frames, const int64_t* offsets, int64_t V, const int32_t* weights, int max_weight,
+                                   int max_dist, hvd_vmatch* out, int64_t cap, int64_t* out_count, int64_t* out_totals) {
+    // every refusal comes before the question whether a device is there
+    if (!out_count || cap < 0 || (cap > 0 && !out)) return fail(HVD_ERR_ARG, "bad arguments");
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    if (max_weight < 0) return fail(HVD_ERR_ARG, "max_weight=%d must not be negative (0 = no cap)", max_weight);
+    int64_t nf = 0;
+    if (int rc = check_offsets(offsets, V, &nf)) return rc;
+    if (nf > 0 && !frames) return fail(HVD_ERR_ARG, "frames is NULL");
+    if (int rc = check_weights(weights, offsets, V, nf, max_weight, out_totals)) return rc;
+    if (int rc = need_ready()) return rc;
+    *out_count = 0;
+    if (nf < 2) return HVD_OK;
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    void* d_img = nullptr;
+    int32_t *d_vid = nullptr, *d_w = nullptr;
+    if (int rc = upload_library(frames, offsets, V, nf, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_img, &d_vid)) return rc;
+    if (int rc = upload_weights(Ctx::S_WQ, weights, nf, &d_w)) return rc;
+    VmArgs v{d_img, (uint32_t)nf, d_img, (uint32_t)nf, false, d_vid, d_vid, nullptr, nullptr, max_dist, 0, 1};
+    v.d_weight_q = v.d_weight_t = d_w;
+    v.max_weight = (uint32_t)max_weight;
+    std::vector<hvd_vmatch> res;
+    if (int rc = vmatch_to_host(v, V, res)) return rc;
+    return copy_out(res, (int64_t)res.size(), vmatch_less, out, cap, out_count, "weighted video match");
+}
+
+int hvd_vpdq_match_videos_cross_weighted(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* ids_q,
+                                         const int32_t* weights_q, const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT,
+                                         const int32_t* ids_t, const int32_t* weights_t, int max_weight, int max_dist,
+                                         hvd_vmatch* out, int64_t cap, int64_t* out_count, int64_t* out_totals_q,
+                                         int64_t* out_totals_t) {
+    if (!out_count || cap < 0 || (cap > 0 && !out)) return fail(HVD_ERR_ARG, "bad output buffer");
+    if ((ids_q == nullptr) != (ids_t == nullptr)) return fail(HVD_ERR_ARG, "pass both id arrays or neither");
+    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
+    if (max_weight < 0) return fail(HVD_ERR_ARG, "max_weight=%d must not be negative (0 = no cap)", max_weight);
+    int64_t nq = 0, nt = 0;
+    if (int rc = check_offsets(offsets_q, VQ, &nq)) return rc;
+    if (int rc = check_offsets(offsets_t, VT, &nt)) return rc;
+    if ((nq > 0 && !frames_q) || (nt > 0 && !frames_t)) return fail(HVD_ERR_ARG, "frames is NULL");
+    if (int rc = check_weights(weights_q, offsets_q, VQ, nq, max_weight, out_totals_q)) return rc;
+    if (int rc = check_weights(weights_t, offsets_t, VT, nt, max_weight, out_totals_t)) return rc;
+    if (int rc = need_ready()) return rc;
+    *out_count = 0;
+    if (nq == 0 || nt == 0) return HVD_OK;
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    void *d_iq = nullptr, *d_it = nullptr;
+    int32_t *d_vq = nullptr, *d_vt = nullptr, *d_gq = nullptr, *d_gt = nullptr, *d_wq = nullptr, *d_wt = nullptr;
+    std::vector<int32_t> gq, gt;
+    if (int rc = upload_library(frames_q, offsets_q, VQ, nq, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_iq, &d_vq)) return rc;
+    if (int rc = upload_library(frames_t, offsets_t, VT, nt, Ctx::S_DB2, Ctx::S_IMG2, Ctx::S_VIDT, &d_it, &d_vt)) return rc;
+    if (int rc = upload_weights(Ctx::S_WQ, weights_q, nq, &d_wq)) return rc;
+    if (int rc = upload_weights(Ctx::S_WT, weights_t, nt, &d_wt)) return rc;
+    if (ids_q) {  // frames of videos with equal ids are not compared, as in hvd_vpdq_match_videos_cross
+        gq.resize((size_t)nq);
+        gt.resize((size_t)nt);
+        for (int64_t v = 0; v < VQ; ++v)
+            for (int64_t f = offsets_q[v]; f < offsets_q[v + 1]; ++f) gq[(size_t)f] = ids_q[v];
+        for (int64_t v = 0; v < VT; ++v)
+            for (int64_t f = offsets_t[v]; f < offsets_t[v + 1]; ++f) gt[(size_t)f] = ids_t[v];
+        SCR(S_GRP, 4 * (size_t)nq, d_gq);
+        SCR(S_GRP2, 4 * (size_t)nt, d_gt);
+        HIP_TRY(hipMemcpyAsync(d_gq, gq.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, g.stream));
+        HIP_TRY(hipMemcpyAsync(d_gt, gt.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, g.stream));
+        HIP_TRY(hipStreamSynchronize(g.stream));
+    }
+    VmArgs v{d_iq, (uint32_t)nq, d_it, (uint32_t)nt, true, d_vq, d_vt, d_gq, d_gt, max_dist, 0, 1};
+    v.d_weight_q = d_wq;
+    v.d_weight_t = d_wt;
+    v.max_weight = (uint32_t)max_weight;
+    std::vector<hvd_vmatch> res;
+    if (int rc = vmatch_to_host(v, VQ, res)) return rc;
+    return copy_out(res, (int64_t)res.size(), vmatch_less, out, cap, out_count, "weighted video match");
 }
 
 /* ---- time alignment of listed video pairs (k_valign*.hip) ---- */

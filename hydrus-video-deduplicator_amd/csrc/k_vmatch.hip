@@ -33,30 +33,14 @@ __global__ __launch_bounds__(256) void k_keys_to_pairs(const unsigned long long*
          idx += (unsigned long long)gridDim.x * 256u) {
         const unsigned long long k = src[idx];
         if (k == kEmptyKey) continue;
-        const uint32_t f = hvd::vkey_frame(k), v = hvd::vkey_video(k);
-        uint32_t a, b;
-        bool is_q;
-        if (!rect) {  // one frame space: the frame's own video against the video it matched
-            const uint32_t own = (uint32_t)vid_q[f];
-            is_q = own < v;
-            a = is_q ? own : v;
-            b = is_q ? v : own;
-        } else if (hvd::vkey_side(k) == 0u) {  // query frame matched target video v
-            a = (uint32_t)vid_q[f];
-            b = v;
-            is_q = true;
-        } else {  // target frame matched query video v
-            a = v;
-            b = (uint32_t)vid_t[f];
-            is_q = false;
-        }
+        const hvd::VideoPairOfKey p = hvd::vkey_pair(k, vid_q, vid_t, rect);
         bool is_new;
-        const unsigned long long slot = hvd::table_insert(pkeys, pmask, ((unsigned long long)a << 32) | b, &is_new);
+        const unsigned long long slot = hvd::table_insert(pkeys, pmask, ((unsigned long long)p.a << 32) | p.b, &is_new);
         if (slot == ~0ull) {
             atomicAdd(&counters[0], 1ull);
             continue;
         }
-        atomicAdd(is_q ? &pcnt[slot].x : &pcnt[slot].y, 1u);
+        atomicAdd(p.is_q ? &pcnt[slot].x : &pcnt[slot].y, 1u);
     }
 }
 

@@ -246,6 +246,7 @@ class DeviceLibrary:
         self._lengths = None
         self.d_spread = None  # int32 per kept frame: the spread `attach_spread` (or `ingest`) left, at spread_max_dist
         self.spread_max_dist = None
+        self.d_weights = None  # int32 per kept frame: the frames it stands for in the weighted search (`attach_weights`)
 
     @classmethod
     def from_raw_hashes(cls, d_hashes_ptr: int, d_quality_ptr: int, n: int, raw_offsets: np.ndarray,
@@ -347,13 +348,68 @@ class DeviceLibrary:
     def hashes(self) -> np.ndarray:
         return self.d_hashes.to_array(np.uint8, 32 * self.n_frames).reshape(-1, 32)
 
-    def match_videos(self, max_dist: int | None = None, rank: int = 0, world: int = 1, cap: int | None = None) -> np.ndarray:
-        """hvd_dev_vpdq_match_videos: VMATCH_DTYPE records sorted by (a, b); only these cross PCIe."""
+    def attach_weights(self, d_weights: DeviceBuffer) -> DeviceBuffer:
+        """Give every kept frame a weight for `match_videos(weighted=True)`: d_weights holds one int32 per frame,
+        each at least 1 -- the runs buffer of `without_repeated_frames` as it is. The buffer becomes this library's: `free`
+        frees it, and weights attached earlier are freed here. Nothing is checked on the device; `weight_totals` refuses a
+        video whose total the uint32 counters cannot hold. -> the buffer."""
+        if d_weights.nbytes < 4 * self.n_frames:
+            raise ValueError("weights must hold one int32 per kept frame")
+        if self.d_weights is not None and self.d_weights is not d_weights:
+            self.d_weights.free()
+        self.d_weights = d_weights
+        return d_weights
+
+    def _check_unweighted(self, what: str) -> None:
+        if self.d_weights is not None:
+            raise ValueError(f"{what} would drop the attached weights: it is not defined on a weighted library")
+
+    def weight_totals(self, max_weight: int = 0) -> np.ndarray:
+        """hvd_dev_video_weights: int64[V], per video the sum of min(weight, max_weight) over its frames (max_weight 0: of the
+        weights) -- what stands for `lengths()` after a weighted search. V numbers cross PCIe. ValueError: a total above
+        2^32 - 1, which the uint32 counters of that video's records cannot hold."""
+        if self.d_weights is None:
+            raise ValueError("no weights attached: call attach_weights first")
+        if int(max_weight) != max_weight or max_weight < 0:
+            raise ValueError("max_weight is an integer, at least 0 (0 = no cap)")
+        lib = _lib.ensure()
+        V = self.n_videos
+        if V == 0:
+            return np.zeros(0, dtype=np.int64)
+        with _DeviceScope() as scope:
+            d_totals = scope.temp(DeviceBuffer(8 * V))
+            _lib.check(lib.hvd_dev_video_weights(self.d_weights.ptr, self.d_offsets.ptr, V, self.n_frames, int(max_weight),
+                                                 d_totals.ptr))
+            totals = d_totals.to_array(np.int64, V)
+        over = np.flatnonzero(totals > search.WEIGHT_TOTAL_LIMIT)
+        if over.size:
+            raise ValueError(f"video {int(over[0])}: capped weight total {int(totals[over[0]])} exceeds 2^32 - 1")
+        return totals
+
+    def match_videos(self, max_dist: int | None = None, rank: int = 0, world: int = 1, cap: int | None = None,
+                     weighted: bool = False, max_weight: int = 0) -> np.ndarray:
+        """hvd_dev_vpdq_match_videos: VMATCH_DTYPE records sorted by (a, b); only these cross PCIe. weighted=True:
+        hvd_dev_vpdq_match_videos_weighted with the attached weights -- a matched frame adds
+        min(weight, max_weight) (max_weight 0: its weight) to q_hits / t_hits instead of 1, `weight_totals(max_weight)` are
+        the denominators; on this context alone (world must be 1)."""
         lib = _lib.ensure()
         max_dist = _default_max_dist(max_dist)
+        if weighted:
+            if world != 1 or rank != 0:
+                raise ValueError("the weighted search is not sharded over a device group: world must be 1")
+            if self.d_weights is None:
+                raise ValueError("no weights attached: call attach_weights first")
+            if int(max_weight) != max_weight or max_weight < 0:
+                raise ValueError("max_weight is an integer, at least 0 (0 = no cap)")
+        elif max_weight:
+            raise ValueError("max_weight caps weights: pass weighted=True as well")
         if max_dist < 0 or self.n_frames < 2:
             return np.zeros(0, dtype=VMATCH_DTYPE)
         cap = max(4096, self.n_videos) if cap is None else int(cap)
+        if weighted:
+            return _search_records(lambda d_out, cap_, d_cnt: lib.hvd_dev_vpdq_match_videos_weighted(
+                self.image().ptr, self.n_frames, self.d_video.ptr, self.d_weights.ptr, int(max_weight), max_dist, d_out, cap_,
+                d_cnt), cap)
         return _search_records(lambda d_out, cap_, d_cnt: lib.hvd_dev_vpdq_match_videos(
             self.image().ptr, self.n_frames, self.d_video.ptr, max_dist, rank, world, d_out, cap_, d_cnt), cap)
 
@@ -469,7 +525,8 @@ class DeviceLibrary:
         rule (hvd_dev_common_frames) -> compaction (hvd_dev_compact_kept on the keep flags, bound 1). -> (a NEW library,
         dropped int64[V]); this one is untouched and still the caller's to free. The result always has positions: this
         library's, gathered (hvd_dev_gather_kept_i32), else the index inside this library's video
-        (hvd_dev_kept_positions) -- so `align*` work on the timeline they had before. Nothing but CSR offsets crosses PCIe."""
+        (hvd_dev_kept_positions) -- so `align*` work on the timeline they had before. Attached weights are gathered likewise.
+        Nothing but CSR offsets crosses PCIe."""
         max_videos, max_share = search.check_common_rule(max_videos, max_share)
         lib = _lib.ensure()
         n, V = self.n_frames, self.n_videos
@@ -486,9 +543,14 @@ class DeviceLibrary:
                 _lib.check(lib.hvd_dev_gather_kept_i32(self.d_positions.ptr, d_keep.ptr, n, d_pos.ptr))
             else:
                 _lib.check(lib.hvd_dev_kept_positions(d_keep.ptr, n, self.d_offsets.ptr, V, 1, d_pos.ptr))
+            d_w = None
+            if self.d_weights is not None:  # a kept frame keeps its weight
+                d_w = scope.keep(DeviceBuffer(4 * max(n, 1)))
+                _lib.check(lib.hvd_dev_gather_kept_i32(self.d_weights.ptr, d_keep.ptr, n, d_w.ptr))
             _lib.check(lib.hvd_dev_sync())  # the keep flags are freed on the way out
         library = DeviceLibrary(d_h, d_off, d_vid, kept.value, V)
         library.d_positions = d_pos
+        library.d_weights = d_w
         lengths = self.lengths()
         library._position_limit = self._position_limit if self.d_positions is not None else \
             (int(lengths.max()) if lengths.size else 0)
@@ -501,7 +563,9 @@ class DeviceLibrary:
         int32 per kept frame, the frames it stands for, the caller's to free); this one is untouched and still the caller's to
         free. The result always has positions, as `without_common_frames` makes them: this library's, gathered
         (hvd_dev_gather_kept_i32), else the index inside this library's video (hvd_dev_kept_positions); a kept frame carries
-        the position of the first frame of its run. Nothing but CSR offsets crosses PCIe."""
+        the position of the first frame of its run. Nothing but CSR offsets crosses PCIe. ValueError on a library with
+        attached weights: the runs of a second collapse would have to be sums of weights, which nothing computes."""
+        self._check_unweighted("without_repeated_frames")
         max_dist, max_run = search.check_run_rule(max_dist, max_run)
         lib = _lib.ensure()
         n, V = self.n_frames, self.n_videos
@@ -575,6 +639,8 @@ class DeviceLibrary:
 
     def _check_extension(self, other: "DeviceLibrary") -> None:
         """ValueError unless `extended(other)` can be built; touches nothing on the device."""
+        self._check_unweighted("extended / ingest")
+        other._check_unweighted("extended / ingest")
         if (self.d_positions is None) != (other.d_positions is None):
             raise ValueError("positions on one side only: both libraries carry them or neither does")
         if self.n_frames + other.n_frames >= (1 << 32) - 1 or self.n_videos + other.n_videos >= (1 << 31):
@@ -680,9 +746,10 @@ class DeviceLibrary:
         return Ingest(union, records, dropped)
 
     def free(self) -> None:
-        for b in (self.d_hashes, self.d_offsets, self.d_video, self.d_img, self.d_positions, self.d_spread):
+        for b in (self.d_hashes, self.d_offsets, self.d_video, self.d_img, self.d_positions, self.d_spread, self.d_weights):
             if b is not None:
                 b.free()
+        self.d_weights = None
         self.d_img = None
         self.d_positions = None
         self.d_spread = None
@@ -916,14 +983,21 @@ def dedupe_frames_without_common_on_device(d_frames_ptr: int, raw_offsets: np.nd
 
 def dedupe_frames_without_repeats_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
                                             max_dist: int, max_run: int = 0, threshold: float = 50.0,
-                                            policy: str | None = None, min_quality: int = vpdq.QUALITY_TOLERANCE):
+                                            policy: str | None = None, min_quality: int = vpdq.QUALITY_TOLERANCE,
+                                            weighted: bool = False, max_weight: int = 0):
     """`dedupe_frames_on_device` with the static-scene filter between the quality filter and the search, on the
     calling thread's context: hash -> quality filter + CSR -> runs of near-identical frames -> compaction -> the video search
     on what is left -> pair predicate. max_dist / max_run: DeviceLibrary.without_repeated_frames. -> (pairs int64[m,2],
     records, dropped int64[V], timings); the records' counters and the predicate's lengths are those of the collapsed library.
     timings: hash_ms, runs_ms (rule, compaction, gathers) and search_ms, HIP-event times on the library stream; compact_ms
-    (host clock: quality filter + CSR, synchronous)."""
+    (host clock: quality filter + CSR, synchronous).
+    weighted=True: the runs become the collapsed library's weights, the search is the weighted one, and the
+    predicate's lengths are `weight_totals(max_weight)` -- a kept frame counts for min(run, max_weight) frames (max_weight 0:
+    for its run; at max_dist 0 the records are then those of the library before the collapse). The totals' time is part of
+    search_ms."""
     search.check_run_rule(max_dist, max_run)
+    if int(max_weight) != max_weight or max_weight < 0 or (max_weight and not weighted):
+        raise ValueError("max_weight is an integer, at least 0 (0 = no cap), and needs weighted=True")
     timings: dict = {}
     timed = _stage_timer(timings)
     library = _hashed_library(
@@ -932,12 +1006,19 @@ def dedupe_frames_without_repeats_on_device(d_frames_ptr: int, raw_offsets: np.n
     del timings["gather_ms"]
     try:
         collapsed, dropped, d_runs = timed("runs_ms", lambda: library.without_repeated_frames(max_dist, max_run))
-        d_runs.free()
+        if weighted:
+            collapsed.attach_weights(d_runs)
+        else:
+            d_runs.free()
     finally:
         library.free()
     try:
-        recs = timed("search_ms", collapsed.match_videos)
-        pairs = search.similar_video_pairs(recs, collapsed.lengths(), threshold, policy)
+        if weighted:
+            recs, lengths = timed("search_ms", lambda: (collapsed.match_videos(weighted=True, max_weight=max_weight),
+                                                         collapsed.weight_totals(max_weight)))
+        else:
+            recs, lengths = timed("search_ms", collapsed.match_videos), collapsed.lengths()
+        pairs = search.similar_video_pairs(recs, lengths, threshold, policy)
     finally:
         collapsed.free()
     return pairs, recs, dropped, timings

@@ -70,15 +70,75 @@ def allpairs_hamming(db: np.ndarray, max_dist: int = DISTANCE_TOLERANCE, group: 
         PAIR_DTYPE, max(1024, n // 4) if cap is None else int(cap))
 
 
+WEIGHT_TOTAL_LIMIT = (1 << 32) - 1  # the counters of a VMATCH record are uint32: no video's capped weights may add up to more
+
+
+def check_weights(weights, lengths, max_weight: int = 0) -> np.ndarray:
+    """The frame weights of the weighted search as the C-ABI takes them, or ValueError naming the video at fault.
+    weights: one int sequence per video (the shape of RepeatedFrames.runs), or one flat array with a weight per frame;
+    lengths: frames per video. Every weight is an integer in [1, 2^31 - 1]; max_weight >= 0 (0 = no cap); no video's capped
+    total exceeds 2^32 - 1. -> the weights, flat, int32."""
+    if int(max_weight) != max_weight or max_weight < 0:
+        raise ValueError("max_weight is an integer, at least 0 (0 = no cap)")
+    lengths = np.asarray(lengths, dtype=np.int64)
+    if isinstance(weights, np.ndarray) and weights.dtype != object and weights.ndim == 1:
+        flat = weights
+        if flat.shape[0] != int(lengths.sum()):
+            raise ValueError("weights must hold one value per frame hash")
+    else:
+        weights = list(weights)
+        if len(weights) != lengths.shape[0]:
+            raise ValueError(f"weights for {len(weights)} videos, library of {lengths.shape[0]}")
+        for v, (w, k) in enumerate(zip(weights, lengths)):
+            if np.asarray(w).shape != (int(k),):
+                raise ValueError(f"video {v}: {np.asarray(w).size} weights for {int(k)} frames")
+        flat = np.concatenate([np.asarray(w).reshape(-1) for w in weights]) if weights else np.zeros(0, np.int64)
+    if flat.size and not np.issubdtype(flat.dtype, np.integer):
+        if not (np.issubdtype(flat.dtype, np.floating) and np.array_equal(flat, np.floor(flat))):
+            raise ValueError("weights are integers")
+    flat = flat.astype(np.int64)
+    video = np.repeat(np.arange(lengths.shape[0]), lengths)
+    bad = np.flatnonzero((flat < 1) | (flat > np.iinfo(np.int32).max))
+    if bad.size:
+        raise ValueError(f"video {int(video[bad[0]])}: weight {int(flat[bad[0]])} is outside [1, 2^31 - 1]")
+    offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    totals = video_weights(flat, offsets, max_weight)
+    over = np.flatnonzero(totals > WEIGHT_TOTAL_LIMIT)
+    if over.size:
+        raise ValueError(f"video {int(over[0])}: capped weight total {int(totals[over[0]])} exceeds 2^32 - 1")
+    return np.ascontiguousarray(flat, dtype=np.int32)
+
+
+def video_weights(weights, offsets, max_weight: int = 0) -> np.ndarray:
+    """The denominators of the weighted search: int64[V], per video of the CSR `offsets` the sum of min(w, max_weight) over its
+    frames' weights (max_weight 0: of w). weights: flat, one per frame. Pure numpy; hvd_dev_video_weights is its device form."""
+    w = np.asarray(weights, dtype=np.int64).reshape(-1)
+    offsets = np.asarray(offsets, dtype=np.int64)
+    if max_weight:
+        w = np.minimum(w, int(max_weight))
+    before = np.concatenate([[0], np.cumsum(w, dtype=np.int64)])
+    return (before[offsets[1:]] - before[offsets[:-1]]).astype(np.int64)
+
+
 def match_videos(frames: np.ndarray, offsets: np.ndarray, max_dist: int = DISTANCE_TOLERANCE,
-                 cap: int | None = None) -> np.ndarray:
+                 cap: int | None = None, weights=None, max_weight: int = 0) -> np.ndarray:
     """Every video pair a<b with at least one frame hit, with its vPDQ counters, as a
-    VMATCH_DTYPE array sorted by (a, b). frames: uint8[sum,32]; offsets: int64[V+1] (CSR)."""
+    VMATCH_DTYPE array sorted by (a, b). frames: uint8[sum,32]; offsets: int64[V+1] (CSR).
+    weights (flat, one per frame, or one sequence per video; `check_weights`): the duration-weighted search of DESIGN 4.20
+    (hvd_vpdq_match_videos_weighted) -- a matched frame adds min(weight, max_weight) (max_weight 0: its weight) to q_hits /
+    t_hits instead of 1, and `video_weights` gives the denominators. None: the plain search."""
     frames, offsets, _ = _library(frames, offsets)
     V = offsets.size - 1
+    if weights is not None:
+        weights = check_weights(weights, np.diff(offsets), max_weight)
     if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
         return np.zeros(0, dtype=VMATCH_DTYPE)
     lib = _lib.ensure()
+    if weights is not None:
+        return _lib.records_with_retry(
+            lambda out, cap_, cnt: lib.hvd_vpdq_match_videos_weighted(_ptr(frames), offsets.ctypes.data, V, _ptr(weights),
+                                                                      int(max_weight), int(max_dist), out, cap_, cnt, None),
+            VMATCH_DTYPE, max(1024, V) if cap is None else int(cap))
     return _lib.records_with_retry(
         lambda out, cap_, cnt: lib.hvd_vpdq_match_videos(_ptr(frames), offsets.ctypes.data, V, int(max_dist), out, cap_, cnt),
         VMATCH_DTYPE, max(1024, V) if cap is None else int(cap))
@@ -86,15 +146,23 @@ def match_videos(frames: np.ndarray, offsets: np.ndarray, max_dist: int = DISTAN
 
 def match_videos_cross(frames_q: np.ndarray, offsets_q: np.ndarray, frames_t: np.ndarray, offsets_t: np.ndarray,
                        ids_q: np.ndarray | None = None, ids_t: np.ndarray | None = None,
-                       max_dist: int = DISTANCE_TOLERANCE, cap: int | None = None) -> np.ndarray:
+                       max_dist: int = DISTANCE_TOLERANCE, cap: int | None = None, weights_q=None, weights_t=None,
+                       max_weight: int = 0) -> np.ndarray:
     """Query videos x target videos (batch form of VpTreeManager.search_file, db/vptree.py:865-902):
     VMATCH_DTYPE records (a = query index, b = target index) with >= 1 frame hit, sorted by (a, b).
-    ids_q/ids_t (int32 per video): equal ids are never compared (a query that is in the target set)."""
+    ids_q/ids_t (int32 per video): equal ids are never compared (a query that is in the target set).
+    weights_q / weights_t (both or neither; as `match_videos` takes weights): the duration-weighted form
+    (hvd_vpdq_match_videos_cross_weighted) -- q_hits sums the query side's weights, t_hits the target side's."""
     frames_q, offsets_q, _ = _library(frames_q, offsets_q)
     frames_t, offsets_t, _ = _library(frames_t, offsets_t)
     VQ, VT = offsets_q.size - 1, offsets_t.size - 1
     if (ids_q is None) != (ids_t is None):
         raise ValueError("pass both id arrays or neither")
+    if (weights_q is None) != (weights_t is None):
+        raise ValueError("pass both weight arrays or neither")
+    if weights_q is not None:
+        weights_q = check_weights(weights_q, np.diff(offsets_q), max_weight)
+        weights_t = check_weights(weights_t, np.diff(offsets_t), max_weight)
     if ids_q is not None:
         ids_q = np.ascontiguousarray(ids_q, dtype=np.int32)
         ids_t = np.ascontiguousarray(ids_t, dtype=np.int32)
@@ -103,6 +171,13 @@ def match_videos_cross(frames_q: np.ndarray, offsets_q: np.ndarray, frames_t: np
     if max_dist < 0:
         return np.zeros(0, dtype=VMATCH_DTYPE)
     lib = _lib.ensure()
+    if weights_q is not None:
+        return _lib.records_with_retry(
+            lambda out, cap_, cnt: lib.hvd_vpdq_match_videos_cross_weighted(
+                _ptr(frames_q), offsets_q.ctypes.data, VQ, ids_q.ctypes.data if ids_q is not None else None, _ptr(weights_q),
+                _ptr(frames_t), offsets_t.ctypes.data, VT, ids_t.ctypes.data if ids_t is not None else None, _ptr(weights_t),
+                int(max_weight), int(max_dist), out, cap_, cnt, None, None),
+            VMATCH_DTYPE, max(1024, VQ) if cap is None else int(cap))
     return _lib.records_with_retry(
         lambda out, cap_, cnt: lib.hvd_vpdq_match_videos_cross(
             _ptr(frames_q), offsets_q.ctypes.data, VQ, ids_q.ctypes.data if ids_q is not None else None,
@@ -159,13 +234,29 @@ def pack_hashes(hashes) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     return np.frombuffer(b"".join(blobs), dtype=np.uint8).reshape(-1, 32), offsets, lengths
 
 
-def find_potential_duplicates(video_hashes, threshold: float = 50.0, policy: str | None = None) -> list[tuple[int, int]]:
+def _library_search(video_hashes, weights, max_weight):
+    """The video search behind the find_* entries -> (records, denominators int64[V]): the plain search and the frame counts,
+    or with weights (one int sequence per video) the weighted search and the capped weight totals."""
+    frames, offsets, lengths = pack_hashes(video_hashes)
+    T = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
+    if weights is None:
+        if max_weight:
+            raise ValueError("max_weight caps weights: pass weights as well")
+        return match_videos(frames, offsets, T), lengths
+    flat = check_weights(weights, lengths, max_weight)
+    return match_videos(frames, offsets, T, weights=flat, max_weight=max_weight), video_weights(flat, offsets, max_weight)
+
+
+def find_potential_duplicates(video_hashes, threshold: float = 50.0, policy: str | None = None, weights=None,
+                              max_weight: int = 0) -> list[tuple[int, int]]:
     """Counterpart of HydrusVideoDeduplicator.find_potential_duplicates (dedup.py:445-502)
     for an in-memory library: video_hashes is a sequence of VpdqHash / bytes; returns the
     sorted list of index pairs (a < b) that the reference would mark as potential
-    duplicates (threshold default 50, entrypoint.py:55-57)."""
-    frames, offsets, lengths = pack_hashes(video_hashes)
-    recs = match_videos(frames, offsets, vpdq.frame_max_dist(DISTANCE_TOLERANCE))
+    duplicates (threshold default 50, entrypoint.py:55-57).
+    weights (one int sequence per video, e.g. RepeatedFrames.runs) / max_weight: the duration-weighted search of DESIGN 4.20
+    -- a frame counts for min(weight, max_weight) frames (max_weight 0: for its weight), in the hits and in the lengths. On
+    `without_repeated_frames(hashes, 0)` with weights = its runs the result is that of the library before the collapse."""
+    recs, lengths = _library_search(video_hashes, weights, max_weight)
     pairs = similar_video_pairs(recs, lengths, threshold, policy)
     return [(int(a), int(b)) for a, b in pairs]
 
@@ -925,13 +1016,14 @@ def groups_from_labels(labels: np.ndarray, groups: np.ndarray) -> list:
     return out
 
 
-def find_duplicate_groups(video_hashes, threshold: float = 50.0, policy: str | None = None, score=None) -> list:
+def find_duplicate_groups(video_hashes, threshold: float = 50.0, policy: str | None = None, score=None, weights=None,
+                          max_weight: int = 0) -> list:
     """find_potential_duplicates as groups with a keeper: the connected components of its pairs, as DuplicateGroup(members,
     keeper, edges, complete) sorted by first member. score (uint32 per video): the keeper of a group is its member with the
     largest score, ties to the smaller index; default: the number of kept frames, so the longest copy is kept -- pass
-    resolution, file size or bitrate to keep by those."""
-    frames, offsets, lengths = pack_hashes(video_hashes)
-    recs = match_videos(frames, offsets, vpdq.frame_max_dist(DISTANCE_TOLERANCE))
+    resolution, file size or bitrate to keep by those. weights / max_weight: as `find_potential_duplicates`; the capped weight
+    totals then stand for the frame counts, in the predicate and as the default score."""
+    recs, lengths = _library_search(video_hashes, weights, max_weight)
     labels, groups = group_records(recs, lengths, threshold, policy, lengths if score is None else score)
     return groups_from_labels(labels, groups)
 
@@ -1002,13 +1094,13 @@ def keeper_groups_from(keeper_of: np.ndarray, groups: np.ndarray) -> list:
     return out
 
 
-def find_keeper_groups(video_hashes, threshold: float = 50.0, policy: str | None = None, score=None) -> list:
+def find_keeper_groups(video_hashes, threshold: float = 50.0, policy: str | None = None, score=None, weights=None,
+                       max_weight: int = 0) -> list:
     """find_potential_duplicates as groups that can be acted on: [KeeperGroup(keeper, members, edges, complete)] sorted by
     keeper, where every member is itself one of the keeper's pairs, and no pair is left among the videos that remain once every
     member is removed. score (uint32 per video): the larger is kept, ties to the smaller index; default: the number of kept
-    frames, as in `find_duplicate_groups`."""
-    frames, offsets, lengths = pack_hashes(video_hashes)
-    recs = match_videos(frames, offsets, vpdq.frame_max_dist(DISTANCE_TOLERANCE))
+    frames, as in `find_duplicate_groups`. weights / max_weight: as there."""
+    recs, lengths = _library_search(video_hashes, weights, max_weight)
     keeper_of, groups = keeper_group_records(recs, lengths, threshold, policy, lengths if score is None else score)
     return keeper_groups_from(keeper_of, groups)
 

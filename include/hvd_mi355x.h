@@ -40,7 +40,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross, then + hvd_rate_segments_scratch_bytes, hvd_dev_vpdq_align_rate_segments, hvd_vpdq_align_rate_segments, then + hvd_dev_frame_runs, hvd_vpdq_frame_runs; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross, then + hvd_rate_segments_scratch_bytes, hvd_dev_vpdq_align_rate_segments, hvd_vpdq_align_rate_segments, then + hvd_dev_frame_runs, hvd_vpdq_frame_runs, then + hvd_dev_video_weights, hvd_dev_vpdq_match_videos_weighted, hvd_dev_vpdq_match_videos_cross_weighted, hvd_vpdq_match_videos_weighted, hvd_vpdq_match_videos_cross_weighted; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -302,6 +302,28 @@ int hvd_vpdq_frame_runs(const uint8_t* frames, const int64_t* offsets, int64_t V
 int hvd_vpdq_match_videos_cross(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* ids_q,
                                 const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* ids_t,
                                 int max_dist, hvd_vmatch* out, int64_t cap, int64_t* out_count);
+
+/* Duration-weighted video search: hvd_vpdq_match_videos where every frame carries an integer weight -- the `run`
+ * of hvd_vpdq_frame_runs, the frames a kept frame stands for -- and a matched frame adds its weight to q_hits / t_hits where the
+ * plain search adds 1. weights: int32 per frame hash, each at least 1. max_weight caps a weight at min(w, max_weight); 0 = no
+ * cap, 1 = the plain search. out_totals (int64[V], may be NULL) receives the capped weight total of every video: the
+ * denominators that take the place of the frame counts. Two identities: with max_weight 1 the records are those of
+ * hvd_vpdq_match_videos on the same library; and on a library collapsed by the static-scene filter at max_dist 0 (a dropped
+ * frame equals its anchor) with weights = run and no cap, the records are those of hvd_vpdq_match_videos on the library BEFORE
+ * the collapse, and the totals are its frame counts. Records sorted by (a, b); cap / HVD_ERR_OVERFLOW as hvd_vpdq_match_videos;
+ * max_dist in [0, 127]. HVD_ERR_ARG, returned BEFORE the library asks whether a device is there: a CSR that does not start at
+ * 0 or decreases, a NULL frames or weights array, a weight below 1, max_weight < 0, a video whose capped total exceeds
+ * 2^32 - 1 (the counters are uint32). Under a device group it runs on the calling thread's current context alone. */
+int hvd_vpdq_match_videos_weighted(const uint8_t* frames, const int64_t* offsets, int64_t V, const int32_t* weights, int max_weight,
+                                   int max_dist, hvd_vmatch* out, int64_t cap, int64_t* out_count, int64_t* out_totals);
+/* Query-set x target-set form, as hvd_vpdq_match_videos_cross: q_hits sums weights_q over the matched query frames, t_hits
+ * weights_t over the matched target frames; out_totals_q int64[VQ] / out_totals_t int64[VT] (each may be NULL). The same
+ * refusals, on either side, before a device is asked for; on the calling thread's current context alone. */
+int hvd_vpdq_match_videos_cross_weighted(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* ids_q,
+                                         const int32_t* weights_q, const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT,
+                                         const int32_t* ids_t, const int32_t* weights_t, int max_weight, int max_dist,
+                                         hvd_vmatch* out, int64_t cap, int64_t* out_count, int64_t* out_totals_q,
+                                         int64_t* out_totals_t);
 
 /* New files against the library: the rectangular spread. Q is a new batch (frames_q / offsets_q / VQ), T the
  * library (frames_t / offsets_t / VT), both as hvd_vpdq_match_videos takes them; their video sets are disjoint.
@@ -918,6 +940,22 @@ int hvd_dev_gather_kept_i32(const void* d_in, const void* d_keep, int64_t n, voi
  * the buffers. A video is one wave's, however long it is. */
 int hvd_dev_frame_runs(const void* d_hashes, const void* d_offsets, int64_t V, int64_t n, int max_dist, int max_run,
                        void* d_out_keep, void* d_out_run);
+/* Device-resident forms of the duration-weighted search. d_weight: int32 per frame, as hvd_dev_frame_runs and
+ * hvd_dev_gather_kept_i32 leave the run words of a collapsed library. Nothing is validated on the device: a weight below 1 or
+ * a total past 2^32 - 1 gives wrong counters (mod 2^32), never an access outside the buffers.
+ * hvd_dev_video_weights: d_out_totals int64[V] = per video of the CSR d_offsets (int64[V+1] over the n frames, ranges clamped
+ * to [0, n]) the sum of max_weight ? min(w, max_weight) : w. One launch on the library stream, no host synchronisation,
+ * nothing allocated; a video is one wave's, however long it is (as in hvd_dev_frame_runs).
+ * hvd_dev_vpdq_match_videos_weighted / _cross_weighted: hvd_dev_vpdq_match_videos[_cross] on the calling thread's context
+ * alone (rank 0 of 1) with the weighted fold; serialised with the other video searches; library-owned scratch; the pair map
+ * stays for hvd_dev_vpdq_emit_again, which then emits the weighted counters again. */
+int hvd_dev_video_weights(const void* d_weight, const void* d_offsets, int64_t V, int64_t n, int max_weight, void* d_out_totals);
+int hvd_dev_vpdq_match_videos_weighted(const void* d_img, int64_t n, const void* d_video, const void* d_weight, int max_weight,
+                                       int max_dist, void* d_out, int64_t cap, void* d_count);
+int hvd_dev_vpdq_match_videos_cross_weighted(const void* d_img_q, int64_t nq, const void* d_video_q, const void* d_excl_q,
+                                             const void* d_weight_q, const void* d_img_t, int64_t nt, const void* d_video_t,
+                                             const void* d_excl_t, const void* d_weight_t, int max_weight, int max_dist,
+                                             void* d_out, int64_t cap, void* d_count);
 /* Device-resident form of hvd_vpdq_frame_spread_cross: operands as hvd_dev_vpdq_match_videos_cross without exclusion maps,
  * d_spread_q int32[nq], d_spread_t int32[nt]. The compare and the key set of that search without its fold (rank 0 of 1): a
  * side-0 key (query frame f, target video) adds one to d_spread_q[f], a side-1 key (target frame g, query video) one to
