@@ -32,8 +32,9 @@
 //   k_index_join        work item (block b, key u): B_u x B_u (positions i < j) and B_u x B_{u ^ (1 << t)} for
 //                       the one-bit neighbours above u. First stage on the word that holds block b: a pair within max_dist
 //                       has a word within tw = max_dist / 8 bits (8 (tw + 1) > max_dist), and one of that word's two blocks
-//                       within tw / 2 = r. y in registers, x through scalar loads (the bucket is contiguous at a wave-uniform
-//                       address), xor + popcount + one shift of the outcome into a per-lane mask per candidate.
+//                       within tw / 2 = r. Up to kYS y per lane in registers, x through scalar loads (the bucket is contiguous
+//                       at a wave-uniform address) that every y of the group meets, xor + popcount + one shift of the
+//                       outcome into a per-lane mask per candidate.
 //                       Survivors queue up in LDS and are drained 64 at a time: both whole hashes from the packed DB through
 //                       rows, the full 256-bit distance, and a pair is emitted only by its CANONICAL block -- the first
 //                       block that QUALIFIES (keys within r and word within tw: what lets a candidate reach the full check)
@@ -56,7 +57,9 @@ using namespace hvd::index_dev;  // kBlocks, kKeys, kParts, orders_whole, lds_ad
 
 constexpr uint32_t kWavePairs = 64;  // a wave's pair buffer in LDS (a drain emits at most 64); full -> one atomic reserves room for all of it
 constexpr uint32_t kXB = 16;         // x entries per scalar batch of the join: one 64-byte scalar load, one survivor mask per lane
-constexpr uint32_t kQueue = 128;     // a wave's survivor queue in LDS (a ring): a push adds at most 64, 64 pending are drained at once
+constexpr uint32_t kYS = 4;          // y entries a lane of the join holds at once: a group is 64 kYS entries of an item's y list
+static_assert(kYS == 4u && kXB == 16u, "the join packs the masks of two slots, kXB bits each, into a register, and selects among four");
+constexpr uint32_t kQueue = 128;    // a wave's survivor queue in LDS (a ring): a push adds at most 64, 64 pending are drained at once
 constexpr uint32_t kRun = 4;         // consecutive keys of one block that a wave of the join walks before it strides on
 constexpr uint32_t kRuns = 16u * 65536u / kRun;
 
@@ -424,12 +427,14 @@ __device__ __forceinline__ void flush_wave(const hvd_pair* buf, uint32_t fill, u
 // flush when the pair buffer cannot take a drain's pairs and once at the end. A queue entry CARRIES ITS BLOCK (qblk, a byte
 // beside the two positions), so survivors of block b may be drained while the wave walks another block: the rows and the
 // ownership verdict come from the entry's block, never from the item being walked. Everything else is per item and is set
-// up afresh by walk(): the segment table (incl, delta, ny), the cursor (cs, ce), the y registers and ylim.
+// up afresh by walk(): the segment table (incl, delta, ny), the cursor (nzm, ce, dl), the y registers and ylim.
 // The y list of an item is
-// its own bucket (segment 0) followed by the buckets u ^ (1 << t) > u (r = 1): lanes take 64 consecutive entries of it per
-// round and hold their y -- one word: the key of block b and, above it, the key of its sibling block -- in a register; the
-// next round's y is loaded before the current round's x loop. The x side is the bucket itself, contiguous at a wave-uniform
-// address: kXB words per scalar batch, xor'ed as scalar operands. Per candidate: xor, popcount onto a constant that carries
+// its own bucket (segment 0) followed by the buckets u ^ (1 << t) > u (r = 1): a group is 64 kYS consecutive entries of it,
+// and a lane holds up to kYS y -- slot s = entry 64 s + lane of the group; one word each: the key of block b and, above
+// it, the key of its sibling block -- in registers. The loops are group outside, x batch inside, slot innermost: all y
+// loads of a group and its first x batch are in flight together, and every x batch is read once per group -- at 1 M
+// hashes nearly every y list (~138 entries) is one group -- and meets all slots that hold an entry. The x side is the
+// bucket itself, contiguous at a wave-uniform address: kXB words per scalar batch, xor'ed as scalar operands. Per candidate: xor, popcount onto a constant that carries
 // "more than tw = max_dist / 8 bits" into bit 31, and that bit shifted into the lane's mask. All kXB words are read whatever the bucket holds,
 // but only the quarters of a batch that hold an x are stepped; the mask keeps only the x
 // that exist and, inside the own bucket, only those before the lane's y (x index k pairs with a y iff k < ylim). The kernel
@@ -437,13 +442,14 @@ __device__ __forceinline__ void flush_wave(const hvd_pair* buf, uint32_t fill, u
 // further ahead measured slower, every instruction taken out measured faster), so the loops are written for few of them. A
 // candidate's key is within r and its sibling key is unrelated (~8 of 16 bits differ), so about one in a hundred survives
 // (same bucket) or one in five hundred (neighbour): the survivors' {x position, y position} inside their block go into the
-// wave's queue in LDS, and whenever 64 are pending each lane takes one: both rows, both whole
+// wave's queue in LDS -- once per batch for all slots together --, and whenever 64 are pending each lane takes one: both rows, both whole
 // hashes from the packed DB, the exact distance, the ownership rule, the group filter, the pair buffer.
 // Positions inside the own bucket are the first nu entries of the y list.
 __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint32_t* __restrict__ select) {
     __shared__ hvd_pair pbuf[4][kWavePairs];
     __shared__ uint2 qbuf[4][kQueue];
     __shared__ uint8_t qblk[4][kQueue];
+    __shared__ uint32_t yposb[4][kYS * 64u];
     if (select[hvd::kSelIdxUsed] == 0u) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -475,6 +481,7 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
     hvd_pair* buf = pbuf[wave];
     uint2* queue = qbuf[wave];
     uint8_t* qb = qblk[wave];
+    uint32_t* ypl = yposb[wave];
 
     // the first cnt (<= 64) queued survivors, one per lane: the full check
     auto drain = [&](uint32_t cnt) {
@@ -555,86 +562,144 @@ __global__ __launch_bounds__(256) void k_index_join(const JoinArgs a, const uint
         // (a batch reads kXB words whatever the bucket holds: at most kXB - 1 words past the block's last position, and behind
         // the last block's hw lie the rows, 16 n >= 32 words, in the same allocation)
         kxw* xb = (kxw*)(a.hw + base + s0);
-        // one batch of kXB x words (x index k0 ..) against the wave's 64 y: bit kXB - 1 - j of the mask = x k0 + j survives
-        auto batch = [&](const u32x16& x, uint32_t k0, uint32_t yw, uint32_t ypos, uint32_t ylim) {
-            // only the quarters of the batch that hold an x are stepped (wave-uniform: the bucket's last batch is short, and the
-            // mean bucket of 15 at 1 M hashes fills 70 % of whole batches, 93 % of quarters)
-            uint32_t fails = 0;
+        // The y side of a group: a lane holds up to kYS y -- slot s is entry g0 + 64 s + lane of the y list --, their words,
+        // their positions inside block b and ylim: x index k pairs with the y iff k < ylim, inside the bucket (the first nu
+        // entries) only the x before it (positions i < j), past the list none.
+        // The positions are needed only when a survivor is pushed, by a slot that differs from lane to lane: they wait in
+        // LDS (ypl[64 s + lane]: a lane reads what it wrote itself) and hold no register under the steps.
+        uint32_t yw[kYS], ylim[kYS];
+        // One batch of kXB x words (x index k0 ..) against the first NS slots (wave-uniform: the slots that hold an entry):
+        // bit 4 nq - 1 - j of a slot's mask = x k0 + j survives; two slots' masks to a register, the even slot below. Only
+        // the quarters of the batch that hold an x are stepped (wave-uniform: the bucket's last batch is short, and the mean
+        // bucket of 15 at 1 M hashes fills 70 % of whole batches, 93 % of quarters): nq, the shift and every quarter branch
+        // once per batch, whatever NS is.
+        auto steps = [&](auto ns_tag, const u32x16& x, uint32_t k0, uint32_t* m01, uint32_t* m23) {
+            constexpr uint32_t NS = decltype(ns_tag)::value;
+            uint32_t fails[NS];
+#pragma unroll
+            for (uint32_t s = 0; s < NS; ++s) fails[s] = 0u;
             const uint32_t nq = min(kXB / 4u, (nu - k0 + 3u) / 4u);
 #pragma unroll
-            for (uint32_t j = 0; j < 4u; ++j) fails = word_step(fails, x[j], yw, kfail);
+            for (uint32_t s = 0; s < NS; ++s)
+#pragma unroll
+                for (uint32_t j = 0; j < 4u; ++j) fails[s] = word_step(fails[s], x[j], yw[s], kfail);
             if (nq > 1u) {
 #pragma unroll
-                for (uint32_t j = 4u; j < 8u; ++j) fails = word_step(fails, x[j], yw, kfail);
+                for (uint32_t s = 0; s < NS; ++s)
+#pragma unroll
+                    for (uint32_t j = 4u; j < 8u; ++j) fails[s] = word_step(fails[s], x[j], yw[s], kfail);
                 if (nq > 2u) {
 #pragma unroll
-                    for (uint32_t j = 8u; j < 12u; ++j) fails = word_step(fails, x[j], yw, kfail);
+                    for (uint32_t s = 0; s < NS; ++s)
+#pragma unroll
+                        for (uint32_t j = 8u; j < 12u; ++j) fails[s] = word_step(fails[s], x[j], yw[s], kfail);
                     if (nq > 3u) {
 #pragma unroll
-                        for (uint32_t j = 12u; j < 16u; ++j) fails = word_step(fails, x[j], yw, kfail);
+                        for (uint32_t s = 0; s < NS; ++s)
+#pragma unroll
+                            for (uint32_t j = 12u; j < 16u; ++j) fails[s] = word_step(fails[s], x[j], yw[s], kfail);
                     }
                 }
             }
-            fails <<= kXB - 4u * nq;  // (the outcome of x k0 + j at bit kXB - 1 - j, as after all kXB steps)
-            const uint32_t c = ylim > k0 ? min(kXB, ylim - k0) : 0u;  // the lane's y pairs with the first c x of the batch
-            uint32_t mask = ~fails & (0xFFFF0000u >> c) & 0xFFFFu;
-            // one survivor per lane and turn: at most 64 join the fewer than 64 pending, so the push always fits (a batch
-            // without a survivor leaves at once: one compare and one branch)
-            if (!__any(mask != 0u)) return;
+            // after 4 nq steps the outcome of x k0 + j is at bit 4 nq - 1 - j, and there it stays (the push knows nq): the
+            // y pairs with the first c x of the batch, the top c of those 4 nq bits (c <= 4 nq, since ylim <= nu)
+            const uint32_t sh = kXB - 4u * nq, top = 0xFFFF0000u >> sh, all = 0xFFFFu >> sh;
+            uint32_t mask[kYS];
+#pragma unroll
+            for (uint32_t s = 0; s < kYS; ++s) {
+                mask[s] = 0u;
+                if (s < NS) {
+                    const int c = min(max((int)ylim[s] - (int)k0, 0), (int)kXB);
+                    mask[s] = ~fails[s] & (top >> c) & all;
+                }
+            }
+            *m01 = mask[0] | mask[1] << 16;
+            *m23 = mask[2] | mask[3] << 16;
+        };
+        // The survivors of one batch, all slots together: one per lane and turn, so at most 64 join the fewer than 64
+        // pending and the push always fits (a batch without a survivor in any slot leaves at once: one compare and one
+        // branch). A lane takes its lowest mask bit: bit t of m01 (else of m23) is slot t / 16 (+ 2), x k0 + 4 nq - 1 - t % 16.
+        auto push = [&](uint32_t k0, uint32_t m01, uint32_t m23) {
+            if (!__any((m01 | m23) != 0u)) return;
+            const uint32_t xtop = s0 + k0 + min(kXB, (nu - k0 + 3u) & ~3u) - 1u;  // the position of the x at bit 0 of a mask
             do {
-                const bool has = mask != 0u;
+                const bool has = (m01 | m23) != 0u;
                 const unsigned long long bal = __ballot(has);
                 if (has) {
                     const uint32_t slot = (qt + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))) &
                                           (kQueue - 1u);
-                    queue[slot] = make_uint2(s0 + k0 + (kXB - 1u) - (uint32_t)__builtin_ctz(mask), ypos);
+                    const bool lo = m01 != 0u;
+                    const uint32_t t = (uint32_t)__builtin_ctz(lo ? m01 : m23);
+                    const bool up = t >= kXB;
+                    const uint32_t yp = ypl[64u * ((lo ? 0u : 2u) + (up ? 1u : 0u)) + lane];
+                    queue[slot] = make_uint2(xtop - (t & (kXB - 1u)), yp);
                     qb[slot] = (uint8_t)b;
-                    mask &= mask - 1u;
+                    if (lo) m01 &= m01 - 1u;
+                    else m23 &= m23 - 1u;
                 }
                 qt += (uint32_t)__popcll(bal);
                 if (qt - qh >= 64u) drain(64u);
-            } while (__any(mask != 0u));
+            } while (__any((m01 | m23) != 0u));
         };
-        // The position inside block b of the entries q0 + lane of the y list, for the rounds in their order. A round touches a
-        // short run of consecutive segments, and that run only moves forward: cs (wave-uniform) is the first segment that does
-        // not end below the round's first entry, ce its end, read from the lane that holds it. A lane's segment is cs plus
-        // the segments from cs on that end at or below its entry: one compare and one add per segment that ends inside the
-        // round, whatever its size (an empty one too), and one scalar compare for a round inside a long segment.
-        uint32_t cs = 0, ce = nu;
+        // The position inside block b of the entries q0 + lane of the y list, for the slots in their order: p + the delta of
+        // the entry's segment. The cursor -- all of it wave-uniform -- only moves forward over the segments that hold an
+        // entry (nzm: those still ahead): ce is the end of the current one, dl its delta. Every lane takes the current delta;
+        // for each segment that begins inside the slot, at lane ce - q0, the lanes from there on take that one's instead:
+        // its end and delta read from the lane that holds them, one add and one select by a lane mask made by a scalar shift.
+        // No compare per lane, nothing for an empty segment, and one add for a slot inside a long segment.
+        uint32_t nzm = (uint32_t)__ballot(ssize != 0u) & 0x1FFFEu;  // (segment 0 is the bucket: nu > 0, and it is the current one)
+        uint32_t ce = nu;
+        int dl = (int)s0;
         auto locate = [&](uint32_t q0) {
             const uint32_t p = q0 + lane;
-            asm volatile("" : "+s"(cs));  // (the cursor stays in a scalar register from round to round)
-            const uint32_t c0 = cs;
-            uint32_t past = 0;
-            while (ce < min(q0 + 64u, ny)) {  // (an end below ny belongs to a segment below 16; entries from ny on are not used)
-                past += p >= ce ? 1u : 0u;
-                ++cs;
-                ce = (uint32_t)__builtin_amdgcn_readlane((int)incl, (int)cs);
+            uint32_t yp = (uint32_t)((int)p + dl);
+            const uint32_t lim = min(q0 + 64u, ny);
+            while (ce < lim) {  // (an end below ny: a further segment holds an entry; q0 <= ce, the slot's first entry is the current segment's or ce itself)
+                const unsigned long long from = ~0ull << (ce - q0);
+                const int cs = __builtin_ctz(nzm);
+                nzm &= nzm - 1u;
+                ce = (uint32_t)__builtin_amdgcn_readlane((int)incl, cs);
+                dl = __builtin_amdgcn_readlane(delta, cs);
+                // (the select takes the scalar mask as it is: written in C++ it would need a compare per lane to make one)
+                const uint32_t moved = (uint32_t)((int)p + dl);
+                asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(yp) : "v"(moved), "s"(from));
             }
-            return (uint32_t)((int)p + __shfl(delta, (int)(c0 + past)));
+            return yp;
         };
-        uint32_t ypos = locate(0u);
-        uint32_t yw = 0u;
-        if (lane < ny) yw = hb[ypos];
-        uint32_t p0 = 0;
-        do {  // (ny >= nu > 0: at least one round)
-            const uint32_t p = p0 + lane;
-            uint32_t ypos_n = 0u, yw_n = 0u;
-            asm volatile("" ::"v"(yw));  // (this round's y has arrived, on every path, before the next one's load is issued)
-            if (p0 + 64u < ny) {  // (wave-uniform: the last round looks for nothing)
-                ypos_n = locate(p0 + 64u);
-                if (p + 64u < ny) yw_n = hb[ypos_n];  // the next round's y: in flight under this round's x loop
+        uint32_t g0 = 0;
+        do {  // (ny >= nu > 0: at least one group, and its slot 0 holds an entry)
+            // the slots that hold an entry (wave-uniform), located in their order -- the cursor only moves forward --, and
+            // all their y loads and the first x batch in flight together
+            const uint32_t ns = min(kYS, (ny - g0 + 63u) / 64u);
+#pragma unroll
+            for (uint32_t s = 0; s < kYS; ++s) {
+                yw[s] = 0u;
+                ylim[s] = 0u;
+                if (s < ns) {
+                    const uint32_t p = g0 + 64u * s + lane;
+                    const uint32_t yp = locate(g0 + 64u * s);
+                    if (p < ny) yw[s] = hb[yp];
+                    ylim[s] = p >= ny ? 0u : min(p, nu);
+                    ypl[64u * s + lane] = yp;
+                }
             }
-            // x index k pairs with this y iff k < ylim: inside the bucket (the first nu entries) only the x before it (positions i < j)
-            const uint32_t ylim = p >= ny ? 0u : min(p, nu);
-            for (uint32_t k0 = 0; k0 < nu; k0 += kXB) {
-                const u32x16 x = *(kx16*)(xb + k0);
-                batch(x, k0, yw, ypos, ylim);
+            u32x16 x = *(kx16*)xb;
+            for (uint32_t k0 = 0;;) {  // every x batch is loaded once per group and meets all its slots
+                uint32_t m01, m23;
+                if (ns > 2u) {
+                    if (ns > 3u) steps(std::integral_constant<uint32_t, 4u>(), x, k0, &m01, &m23);
+                    else steps(std::integral_constant<uint32_t, 3u>(), x, k0, &m01, &m23);
+                } else {
+                    if (ns > 1u) steps(std::integral_constant<uint32_t, 2u>(), x, k0, &m01, &m23);
+                    else steps(std::integral_constant<uint32_t, 1u>(), x, k0, &m01, &m23);
+                }
+                push(k0, m01, m23);
+                k0 += kXB;
+                if (k0 >= nu) break;
+                x = *(kx16*)(xb + k0);
             }
-            ypos = ypos_n;
-            yw = yw_n;
-            p0 += 64u;
-        } while (p0 < ny);
+            g0 += 64u * kYS;
+        } while (g0 < ny);
     };
     uint32_t vstart, vend;
     offsets(item, &vstart, &vend);
@@ -746,12 +811,15 @@ IndexRule index_rule(const AllPairsArgs& a, uint32_t r) {
     // (profiles/r22_index_kernel_stats_after.csv): every kernel between probe and join 0.157 ms. Of these the two scans and
     // the three chunk kernels, 25 us, do not depend on n, and neither do the statistics, 17 us, which load all 16 x 65 536
     // counts whatever n is: the tile count, the scatter and the order pass, 0.116 ms, are 0.12 ns per hash. fixed_ns: those
-    // 42 us, 43 us of launches (as many as before) and 21 us of fall-back launches: 106 us, rounded up)
+    // 42 us, 43 us of launches (as many as before) and 21 us of fall-back launches: 106 us, rounded up.
+    // With a lane's y in groups of kYS slots and every x batch read once per group (profiles/r24_kernel_stats_after.csv,
+    // profiles/r24_index_join_time.jsonl): join 0.601 ms for 2.075e9 candidates = 0.29 ps each; the crowded DB 5.83 .. 5.85
+    // ms per call, less the same ~0.6 ms, over 25.15e6 pairs = 0.21 ns per pair, rounded up)
     q.fs_mfma_fetch = 36.0f;
     q.fs_mfma_other = 40.0f;
-    q.ps_cand = 0.31f;
+    q.ps_cand = 0.29f;
     q.ps_hash = 120.0f;
-    q.ps_crit = 320.0f;
+    q.ps_crit = 220.0f;
     q.fixed_ns = 110000.0f;
     return q;
 }
