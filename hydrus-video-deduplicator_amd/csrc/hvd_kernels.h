@@ -181,7 +181,7 @@ hipError_t launch_common_rule(const int32_t* d_spread, const long long* d_offset
 hipError_t launch_gather_kept_i32(const int32_t* d_in, const int32_t* d_keep, unsigned long long n, int32_t* d_out,
                                   void* d_scratch, unsigned long long* d_total, hipStream_t s);
 
-// Static-scene filter (k_runs.hip; DESIGN 4.19): d_hashes 32 B per frame, d_offsets a CSR over the n frames -> d_keep int32[n],
+// Static-scene filter (k_runs.hip; DESIGN 4.21): d_hashes 32 B per frame, d_offsets a CSR over the n frames -> d_keep int32[n],
 // 1 or 0, and d_run int32[n] (may be nullptr), the frames a kept frame stands for. One launch of at most kFrameRunsMaxBlocks
 // workgroups (4 waves per SIMD on 256 compute units), each striding over groups of four videos.
 constexpr unsigned kFrameRunsMaxBlocks = 1024;
@@ -201,25 +201,49 @@ hipError_t launch_keys_to_pairs_weighted(const unsigned long long* d_src, unsign
 hipError_t launch_video_weights(const int32_t* d_weight, const long long* d_offsets, uint32_t V, unsigned long long n,
                                 uint32_t max_weight, long long* d_totals, hipStream_t s);
 
-// Time alignment of listed video pairs (k_valign.hip). Two launches: the pairs whose delta histogram fits LDS, then
-// the larger ones out of d_scratch (align_scratch_bytes(max_bins); may be nullptr / 0: such pairs then get the INT32_MIN record).
-size_t align_scratch_bytes(unsigned long long max_bins);
-hipError_t launch_valign(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
-                         const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
-                         const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, void* d_scratch,
-                         size_t scratch_bytes, hvd_valign* d_out, hipStream_t s);
+// Time alignment of listed video pairs: one offset per pair (k_valign.hip, 4.8), up to eight (k_valign_segments.hip,
+// 4.9), one line at the best of the listed rates (k_valign_rates.hip, 4.10), rate x segments (k_valign_rate_segments.hip, 4.18).
+// AlignMode says which of the four a call is and carries what only some of them take; everything that differs between them on
+// the host is read off it.
+struct AlignMode {
+    uint32_t nums, dens;               // rated: the packed list (pack_rate_list below); 0, 0: a broken list
+    int max_segments, min_band_votes;  // segmented: as the caller gave them (check_segment_limits judges them)
+    bool rated, segmented;
+    bool args_first;  // the host entry judges its arguments before the library's state (the rate entries), not after
+    static AlignMode of(bool rated, bool segmented, int max_segments = 0, int min_band_votes = 1) {
+        return {0u, 0u, max_segments, min_band_votes, rated, segmented, rated};
+    }
+    unsigned kind() const { return (rated ? 2u : 0u) + (segmented ? 1u : 0u); }
+    size_t record_bytes() const {
+        constexpr size_t bytes[4] = {sizeof(hvd_valign), sizeof(hvd_vsegments), sizeof(hvd_vrate), sizeof(hvd_vrsegments)};
+        return bytes[kind()];
+    }
+    unsigned runs() const { return segmented ? 2u : 1u; }  // pairs of runs of bit words: the flag words, and the taken words
+    bool records16() const { return rated || segmented; }  // the kernel zeroes its records 16 bytes at a time
+};
 
-// Multi-segment time alignment (k_valign_segments.hip): launch_valign's operands and two launches, up to max_segments
-// greedy rounds per pair; a slot of d_scratch (segments_scratch_bytes(max_bins)) also holds the pair's taken sets.
-size_t segments_scratch_bytes(unsigned long long max_bins);
-hipError_t launch_valign_segments(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
-                                  const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
-                                  const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack,
-                                  uint32_t max_segments, uint32_t min_band_votes, void* d_scratch, size_t scratch_bytes,
-                                  hvd_vsegments* d_out, hipStream_t s);
+// The operands every alignment takes, as the C entries name them: on the device for launch_alignment, host buffers (scratch
+// unused) for the host entries. hashes: 32 bytes per frame; offsets: int64 CSR; pos: int32 per frame or nullptr; pairs: uint32[M][2].
+struct AlignOperands {
+    const void *hashes_q, *offsets_q;
+    int64_t VQ;
+    const void *pos_q, *hashes_t, *offsets_t;
+    int64_t VT;
+    const void *pos_t, *pairs;
+    int64_t M;
+    int max_dist, slack;
+    void* scratch;
+    size_t scratch_bytes;
+    void* out;
+};
 
-// Rate-aware time alignment (k_valign_rates.hip): launch_valign's operands and two launches, one offset per pair at
-// the best of the listed rates. The list travels as two kernel arguments: entry r = (num, den) in bits 4r .. 4r + 3 of nums and
+// Two launches: the pairs whose (largest) delta histogram fits LDS, then the larger ones out of op.scratch
+// (alignment_scratch_bytes(mode, max_bins), max_bins: the largest bins, or bins_r of any listed rate, of any pair; may be
+// nullptr / 0: such pairs then get the INT32_MIN record). A slot of a segmented mode's scratch also holds the pair's taken sets.
+size_t alignment_scratch_bytes(const AlignMode& mode, unsigned long long max_bins);
+hipError_t launch_alignment(const AlignMode& mode, const AlignOperands& op, hipStream_t s);
+
+// The rate list of the rate-aware alignments travels as two kernel arguments: entry r = (num, den) in bits 4r .. 4r + 3 of nums and
 // of dens, and it ends at the first entry whose two nibbles are 0. rate_list_length: its length R, or 0 for a broken list (a
 // value outside 1..8, a pair with a common factor, a rate listed twice, something behind the end, no entry) -- the one definition
 // of a sound list, for the host entries and for the kernel (which then gives every pair the INT32_MIN record).
@@ -252,21 +276,6 @@ inline bool pack_rate_list(const int32_t* rates, int n_rates, uint32_t* nums, ui
     *dens = dd;
     return true;
 }
-size_t rates_scratch_bytes(unsigned long long max_bins);  // max_bins: the largest bins_r of any pair and listed rate
-hipError_t launch_valign_rates(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
-                               const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
-                               const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, uint32_t nums,
-                               uint32_t dens, void* d_scratch, size_t scratch_bytes, hvd_vrate* d_out, hipStream_t s);
-
-// Rate-aware multi-segment time alignment (k_valign_rate_segments.hip): launch_valign_rates' operands and two
-// launches, up to max_segments greedy rounds per pair, each at the best of the listed rates; a slot of d_scratch
-// (rate_segments_scratch_bytes(max_bins), max_bins as for rates_scratch_bytes) also holds the pair's taken sets.
-size_t rate_segments_scratch_bytes(unsigned long long max_bins);
-hipError_t launch_valign_rate_segments(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
-                                       const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
-                                       const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, uint32_t nums,
-                                       uint32_t dens, uint32_t max_segments, uint32_t min_band_votes, void* d_scratch,
-                                       size_t scratch_bytes, hvd_vrsegments* d_out, hipStream_t s);
 
 // Duplicate groups with a keeper: connected components of a list of 16-byte records (k_group.hip). d_scratch:
 // group_scratch_bytes(V), 8-byte aligned; d_record_count: nullptr, or the uint64 an all-pairs pass counted its records in (the

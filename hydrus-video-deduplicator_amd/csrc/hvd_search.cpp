@@ -1366,7 +1366,7 @@ int hvd_dev_gather_kept_i32(const void* d_in, const void* d_keep, int64_t n, voi
     return HVD_OK;
 }
 
-/* ---- static-scene filter: one keyframe per run of near-identical frames (k_runs.hip; DESIGN 4.19) ---- */
+/* ---- static-scene filter: one keyframe per run of near-identical frames (k_runs.hip; DESIGN 4.21) ---- */
 
 static int check_run_rule(int max_dist, int max_run) {
     if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
@@ -1413,23 +1413,21 @@ int hvd_vpdq_frame_runs(const uint8_t* frames, const int64_t* offsets, int64_t V
     return HVD_OK;
 }
 
-static int scratch_bytes_entry(int64_t max_bins, size_t* out_bytes, size_t (*bytes)(unsigned long long)) {
+/* ---- time alignment of listed pairs (k_valign*.hip): hvd::AlignMode says which of the four a call is ---- */
+
+using hvd::AlignMode;
+using hvd::AlignOperands;
+
+static int scratch_bytes_entry(const AlignMode& mode, int64_t max_bins, size_t* out_bytes) {
     if (!out_bytes || max_bins < 0 || max_bins > (1ll << 20)) return fail(HVD_ERR_ARG, "max_bins=%lld: need 0..2^20", (long long)max_bins);
-    *out_bytes = bytes((unsigned long long)max_bins);
+    *out_bytes = hvd::alignment_scratch_bytes(mode, (unsigned long long)max_bins);
     return HVD_OK;
 }
 
-int hvd_align_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(max_bins, out_bytes, hvd::align_scratch_bytes); }
-
-int hvd_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) {
-    return scratch_bytes_entry(max_bins, out_bytes, hvd::segments_scratch_bytes);
-}
-
-int hvd_rates_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(max_bins, out_bytes, hvd::rates_scratch_bytes); }
-
-int hvd_rate_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) {
-    return scratch_bytes_entry(max_bins, out_bytes, hvd::rate_segments_scratch_bytes);
-}
+int hvd_align_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of(false, false), max_bins, out_bytes); }
+int hvd_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of(false, true), max_bins, out_bytes); }
+int hvd_rates_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of(true, false), max_bins, out_bytes); }
+int hvd_rate_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of(true, true), max_bins, out_bytes); }
 
 static int check_tolerances(int max_dist, int slack) {
     if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
@@ -1444,18 +1442,23 @@ static int check_segment_limits(int max_segments, int min_band_votes) {
     return HVD_OK;
 }
 
-// What both device entries check, in the order the errors are reported: this before the limits of the segments entry ...
-static int check_align_counts(int64_t VQ, int64_t VT, int64_t M, int max_dist, int slack) {
+// The four device entries: the checks in the order their errors are reported, then the mode's launches. rates / n_rates: the
+// list as the caller gave it (rated modes); a broken one travels as (0, 0), the kernel's INT32_MIN records.
+static int align_on_device(AlignMode mode, const int32_t* rates, int n_rates, const AlignOperands& op) {
     if (int rc = need_ready()) return rc;
-    if (VQ < 0 || VT < 0 || VQ >= (1ll << 31) || VT >= (1ll << 31) || M < 0) return fail(HVD_ERR_ARG, "bad counts");
-    return check_tolerances(max_dist, slack);
-}
-
-// ... and, for M > 0, the pointers. aligned16: the pointers that are read or written 16 bytes at a time, or-ed; what: their names.
-static int check_align_pointers(const void* d_offsets_q, const void* d_offsets_t, const void* d_pairs, const void* d_out,
-                                uintptr_t aligned16, const char* what) {
-    if (!d_offsets_q || !d_offsets_t || !d_pairs || !d_out) return fail(HVD_ERR_ARG, "NULL device pointer");
-    if (aligned16 & 15u) return fail(HVD_ERR_ARG, "%s must be 16-byte aligned", what);
+    if (op.VQ < 0 || op.VT < 0 || op.VQ >= (1ll << 31) || op.VT >= (1ll << 31) || op.M < 0) return fail(HVD_ERR_ARG, "bad counts");
+    if (int rc = check_tolerances(op.max_dist, op.slack)) return rc;
+    if (mode.rated && (!rates || n_rates < 0)) return fail(HVD_ERR_ARG, "rates is NULL or n_rates=%d < 0", n_rates);
+    if (mode.segmented)
+        if (int rc = check_segment_limits(mode.max_segments, mode.min_band_votes)) return rc;
+    if (op.M == 0) return HVD_OK;
+    if (!op.offsets_q || !op.offsets_t || !op.pairs || !op.out) return fail(HVD_ERR_ARG, "NULL device pointer");
+    // what is read or written 16 bytes at a time: the hashes, the bit words, and the records where the kernel zeroes them so
+    const uintptr_t aligned16 = (uintptr_t)op.hashes_q | (uintptr_t)op.hashes_t | (uintptr_t)op.scratch | (mode.records16() ? (uintptr_t)op.out : 0u);
+    if (aligned16 & 15u)
+        return fail(HVD_ERR_ARG, "%s must be 16-byte aligned", mode.records16() ? "hashes, scratch and records" : "hashes and scratch");
+    if (mode.rated) hvd::pack_rate_list(rates, n_rates, &mode.nums, &mode.dens);
+    HIP_TRY(hvd::launch_alignment(mode, op, g.stream));
     return HVD_OK;
 }
 
@@ -1463,77 +1466,36 @@ int hvd_dev_vpdq_align_videos(const void* d_hashes_q, const void* d_offsets_q, i
                               const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                               const void* d_pairs, int64_t M, int max_dist, int slack, void* d_scratch, size_t scratch_bytes,
                               void* d_out) {
-    if (int rc = check_align_counts(VQ, VT, M, max_dist, slack)) return rc;
-    if (M == 0) return HVD_OK;
-    if (int rc = check_align_pointers(d_offsets_q, d_offsets_t, d_pairs, d_out,
-                                      (uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch, "hashes and scratch"))
-        return rc;
-    HIP_TRY(hvd::launch_valign(d_hashes_q, (const long long*)d_offsets_q, (uint32_t)VQ, (const int32_t*)d_pos_q, d_hashes_t,
-                               (const long long*)d_offsets_t, (uint32_t)VT, (const int32_t*)d_pos_t, (const uint32_t*)d_pairs,
-                               (unsigned long long)M, (uint32_t)max_dist, (uint32_t)slack, d_scratch, scratch_bytes,
-                               (hvd_valign*)d_out, g.stream));
-    return HVD_OK;
+    return align_on_device(AlignMode::of(false, false), nullptr, 0,
+                           {d_hashes_q, d_offsets_q, VQ, d_pos_q, d_hashes_t, d_offsets_t, VT, d_pos_t, d_pairs, M, max_dist, slack,
+                            d_scratch, scratch_bytes, d_out});
 }
 
 int hvd_dev_vpdq_align_segments(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
                                 const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                                 const void* d_pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
                                 void* d_scratch, size_t scratch_bytes, void* d_out) {
-    if (int rc = check_align_counts(VQ, VT, M, max_dist, slack)) return rc;
-    if (int rc = check_segment_limits(max_segments, min_band_votes)) return rc;
-    if (M == 0) return HVD_OK;
-    if (int rc = check_align_pointers(d_offsets_q, d_offsets_t, d_pairs, d_out,
-                                      (uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch | (uintptr_t)d_out,
-                                      "hashes, scratch and records"))
-        return rc;
-    HIP_TRY(hvd::launch_valign_segments(d_hashes_q, (const long long*)d_offsets_q, (uint32_t)VQ, (const int32_t*)d_pos_q, d_hashes_t,
-                                        (const long long*)d_offsets_t, (uint32_t)VT, (const int32_t*)d_pos_t,
-                                        (const uint32_t*)d_pairs, (unsigned long long)M, (uint32_t)max_dist, (uint32_t)slack,
-                                        (uint32_t)max_segments, (uint32_t)min_band_votes, d_scratch, scratch_bytes,
-                                        (hvd_vsegments*)d_out, g.stream));
-    return HVD_OK;
+    return align_on_device(AlignMode::of(false, true, max_segments, min_band_votes), nullptr, 0,
+                           {d_hashes_q, d_offsets_q, VQ, d_pos_q, d_hashes_t, d_offsets_t, VT, d_pos_t, d_pairs, M, max_dist, slack,
+                            d_scratch, scratch_bytes, d_out});
 }
 
 int hvd_dev_vpdq_align_rates(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
                              const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                              const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                              void* d_scratch, size_t scratch_bytes, void* d_out) {
-    if (int rc = check_align_counts(VQ, VT, M, max_dist, slack)) return rc;
-    if (!rates || n_rates < 0) return fail(HVD_ERR_ARG, "rates is NULL or n_rates=%d < 0", n_rates);
-    if (M == 0) return HVD_OK;
-    if (int rc = check_align_pointers(d_offsets_q, d_offsets_t, d_pairs, d_out,
-                                      (uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch | (uintptr_t)d_out,
-                                      "hashes, scratch and records"))
-        return rc;
-    uint32_t nums = 0, dens = 0;
-    hvd::pack_rate_list(rates, n_rates, &nums, &dens);  // a broken list travels as (0, 0): the kernel's INT32_MIN records
-    HIP_TRY(hvd::launch_valign_rates(d_hashes_q, (const long long*)d_offsets_q, (uint32_t)VQ, (const int32_t*)d_pos_q, d_hashes_t,
-                                     (const long long*)d_offsets_t, (uint32_t)VT, (const int32_t*)d_pos_t, (const uint32_t*)d_pairs,
-                                     (unsigned long long)M, (uint32_t)max_dist, (uint32_t)slack, nums, dens, d_scratch,
-                                     scratch_bytes, (hvd_vrate*)d_out, g.stream));
-    return HVD_OK;
+    return align_on_device(AlignMode::of(true, false), rates, n_rates,
+                           {d_hashes_q, d_offsets_q, VQ, d_pos_q, d_hashes_t, d_offsets_t, VT, d_pos_t, d_pairs, M, max_dist, slack,
+                            d_scratch, scratch_bytes, d_out});
 }
 
 int hvd_dev_vpdq_align_rate_segments(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
                                      const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                                      const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                                      int max_segments, int min_band_votes, void* d_scratch, size_t scratch_bytes, void* d_out) {
-    if (int rc = check_align_counts(VQ, VT, M, max_dist, slack)) return rc;
-    if (!rates || n_rates < 0) return fail(HVD_ERR_ARG, "rates is NULL or n_rates=%d < 0", n_rates);
-    if (int rc = check_segment_limits(max_segments, min_band_votes)) return rc;
-    if (M == 0) return HVD_OK;
-    if (int rc = check_align_pointers(d_offsets_q, d_offsets_t, d_pairs, d_out,
-                                      (uintptr_t)d_hashes_q | (uintptr_t)d_hashes_t | (uintptr_t)d_scratch | (uintptr_t)d_out,
-                                      "hashes, scratch and records"))
-        return rc;
-    uint32_t nums = 0, dens = 0;
-    hvd::pack_rate_list(rates, n_rates, &nums, &dens);  // a broken list travels as (0, 0): the kernel's INT32_MIN records
-    HIP_TRY(hvd::launch_valign_rate_segments(d_hashes_q, (const long long*)d_offsets_q, (uint32_t)VQ, (const int32_t*)d_pos_q,
-                                             d_hashes_t, (const long long*)d_offsets_t, (uint32_t)VT, (const int32_t*)d_pos_t,
-                                             (const uint32_t*)d_pairs, (unsigned long long)M, (uint32_t)max_dist, (uint32_t)slack, nums,
-                                             dens, (uint32_t)max_segments, (uint32_t)min_band_votes, d_scratch, scratch_bytes,
-                                             (hvd_vrsegments*)d_out, g.stream));
-    return HVD_OK;
+    return align_on_device(AlignMode::of(true, true, max_segments, min_band_votes), rates, n_rates,
+                           {d_hashes_q, d_offsets_q, VQ, d_pos_q, d_hashes_t, d_offsets_t, VT, d_pos_t, d_pairs, M, max_dist, slack,
+                            d_scratch, scratch_bytes, d_out});
 }
 
 // positions of one library: non-negative, strictly increasing inside a video, below 2^20
@@ -1547,23 +1509,27 @@ static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V
     return HVD_OK;
 }
 
-// The host-buffer form of the alignments: validate, stage, run, copy the records back. rates given: hvd_vrate records
-// (hvd_dev_vpdq_align_rates) with max_segments 0, else hvd_vrsegments records (hvd_dev_vpdq_align_rate_segments), the list sound
-// (the caller has checked it), and the arguments are judged before the library's state is, so that a bad call is HVD_ERR_ARG
-// with or without a device; without rates, max_segments 0: hvd_valign records
-// (hvd_dev_vpdq_align_videos); else hvd_vsegments records (hvd_dev_vpdq_align_segments).
-static int align_from_host(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
-                           const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
-                           const uint32_t* pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
-                           void* out, const int32_t* rates = nullptr, int n_rates = 0) {
-    if (!rates)
+// The host-buffer form of the alignments: validate, stage, run, copy the records back. h: the operands as host buffers (no
+// scratch). The list and the limits are judged first; a rated mode then judges the other arguments before the library's state,
+// so that a bad call is HVD_ERR_ARG with or without a device, the slope-one modes after it (mode.args_first).
+static int align_from_host(AlignMode mode, const int32_t* rates, int n_rates, const AlignOperands& h) {
+    if (mode.rated && !hvd::pack_rate_list(rates, n_rates, &mode.nums, &mode.dens))
+        return fail(HVD_ERR_ARG, "rates: need 1..%d pairs (num, den) with 1 <= num, den <= 8, no common factor, none listed twice",
+                    HVD_ALIGN_MAX_RATES);
+    if (mode.segmented)
+        if (int rc = check_segment_limits(mode.max_segments, mode.min_band_votes)) return rc;
+    if (!mode.args_first)
         if (int rc = need_ready()) return rc;
-    if (M < 0 || (M > 0 && (!pairs || !out))) return fail(HVD_ERR_ARG, "bad pair list / output buffer");
-    if (int rc = check_tolerances(max_dist, slack)) return rc;
+    const auto *offsets_q = (const int64_t*)h.offsets_q, *offsets_t = (const int64_t*)h.offsets_t;
+    const auto *positions_q = (const int32_t*)h.pos_q, *positions_t = (const int32_t*)h.pos_t;
+    const auto* pairs = (const uint32_t*)h.pairs;
+    const int64_t VQ = h.VQ, VT = h.VT, M = h.M;
+    if (M < 0 || (M > 0 && (!pairs || !h.out))) return fail(HVD_ERR_ARG, "bad pair list / output buffer");
+    if (int rc = check_tolerances(h.max_dist, h.slack)) return rc;
     int64_t nq = 0, nt = 0;
     if (int rc = check_offsets(offsets_q, VQ, &nq)) return rc;
     if (int rc = check_offsets(offsets_t, VT, &nt)) return rc;
-    if ((nq > 0 && !frames_q) || (nt > 0 && !frames_t)) return fail(HVD_ERR_ARG, "frames is NULL");
+    if ((nq > 0 && !h.hashes_q) || (nt > 0 && !h.hashes_t)) return fail(HVD_ERR_ARG, "frames is NULL");
     if (int rc = check_positions(positions_q, offsets_q, VQ, "query")) return rc;
     if (int rc = check_positions(positions_t, offsets_t, VT, "target")) return rc;
     auto span = [](const int32_t* pos, const int64_t* off, int64_t v) -> int64_t {
@@ -1577,24 +1543,24 @@ static int align_from_host(const uint8_t* frames_q, const int64_t* offsets_q, in
             return fail(HVD_ERR_ARG, "pair %lld = (%u, %u) is outside the %lld x %lld videos", (long long)p, a, b, (long long)VQ, (long long)VT);
         const int64_t sa = span(positions_q, offsets_q, a), sb = span(positions_t, offsets_t, b);
         if (sa < 0 || sb < 0) continue;  // an empty video: the zero record
-        int64_t bins = sa + sb + 1 + 2 * (int64_t)slack;
+        int64_t bins = sa + sb + 1 + 2 * (int64_t)h.slack;
         for (int r = 0; r < n_rates; ++r)  // the largest bins_r of the list
             bins = std::max(bins, rates[2 * r] * sa + rates[2 * r + 1] * sb + 1 +
-                                      2 * (int64_t)slack * std::max(rates[2 * r], rates[2 * r + 1]));
+                                      2 * (int64_t)h.slack * std::max(rates[2 * r], rates[2 * r + 1]));
         if (bins > (1ll << 20))
             return fail(HVD_ERR_ARG, "pair %lld = (%u, %u) spans %lld offsets with slack %d: more than the 2^20 histogram bins",
-                        (long long)p, a, b, (long long)bins, slack);
+                        (long long)p, a, b, (long long)bins, h.slack);
         max_bins = std::max(max_bins, bins);
     }
-    if (rates)
+    if (mode.args_first)
         if (int rc = need_ready()) return rc;
     if (M == 0) return HVD_OK;
     std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    const bool self = frames_t == frames_q && offsets_t == offsets_q && positions_t == positions_q && VT == VQ;
+    const bool self = h.hashes_t == h.hashes_q && offsets_t == offsets_q && positions_t == positions_q && VT == VQ;
     void *d_hq = nullptr, *d_ht = nullptr, *d_scr = nullptr, *d_pairs = nullptr, *d_out = nullptr;
     long long *d_oq = nullptr, *d_ot = nullptr;
     int32_t *d_pq = nullptr, *d_pt = nullptr;
-    auto upload = [&](const uint8_t* frames, const int64_t* offsets, int64_t V, int64_t n, const int32_t* pos, Ctx::Scr s_db,
+    auto upload = [&](const void* frames, const int64_t* offsets, int64_t V, int64_t n, const int32_t* pos, Ctx::Scr s_db,
                       Ctx::Scr s_off, Ctx::Scr s_pos, void** d_h, long long** d_o, int32_t** d_p) -> int {
         if (int rc = scratch(s_db, 32 * (size_t)n, d_h)) return rc;
         if (int rc = scratch(s_off, 8 * (size_t)(V + 1), (void**)d_o)) return rc;
@@ -1606,37 +1572,23 @@ static int align_from_host(const uint8_t* frames_q, const int64_t* offsets_q, in
         }
         return HVD_OK;
     };
-    if (int rc = upload(frames_q, offsets_q, VQ, nq, positions_q, Ctx::S_DB, Ctx::S_OFF, Ctx::S_POSQ, &d_hq, &d_oq, &d_pq)) return rc;
+    if (int rc = upload(h.hashes_q, offsets_q, VQ, nq, positions_q, Ctx::S_DB, Ctx::S_OFF, Ctx::S_POSQ, &d_hq, &d_oq, &d_pq)) return rc;
     if (self) {
         d_ht = d_hq;
         d_ot = d_oq;
         d_pt = d_pq;
-    } else if (int rc = upload(frames_t, offsets_t, VT, nt, positions_t, Ctx::S_DB2, Ctx::S_OFF2, Ctx::S_POST, &d_ht, &d_ot, &d_pt)) {
+    } else if (int rc = upload(h.hashes_t, offsets_t, VT, nt, positions_t, Ctx::S_DB2, Ctx::S_OFF2, Ctx::S_POST, &d_ht, &d_ot, &d_pt)) {
         return rc;
     }
     SCR(S_APAIRS, 8 * (size_t)M, d_pairs);
-    const size_t out_bytes = (rates && max_segments ? sizeof(hvd_vrsegments)
-                              : rates               ? sizeof(hvd_vrate)
-                              : max_segments        ? sizeof(hvd_vsegments)
-                                                    : sizeof(hvd_valign)) * (size_t)M;
+    const size_t out_bytes = mode.record_bytes() * (size_t)M;
     SCR(S_AOUT, out_bytes, d_out);
-    const size_t sb = rates && max_segments ? hvd::rate_segments_scratch_bytes((unsigned long long)max_bins)
-                      : rates               ? hvd::rates_scratch_bytes((unsigned long long)max_bins)
-                      : max_segments        ? hvd::segments_scratch_bytes((unsigned long long)max_bins)
-                                            : hvd::align_scratch_bytes((unsigned long long)max_bins);
+    const size_t sb = hvd::alignment_scratch_bytes(mode, (unsigned long long)max_bins);
     if (sb) SCR(S_ASCR, sb, d_scr);
     HIP_TRY(hipMemcpyAsync(d_pairs, pairs, 8 * (size_t)M, hipMemcpyHostToDevice, g.stream));
-    if (int rc = rates && max_segments
-                     ? hvd_dev_vpdq_align_rate_segments(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack, rates,
-                                                        n_rates, max_segments, min_band_votes, d_scr, sb, d_out)
-                 : rates      ? hvd_dev_vpdq_align_rates(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack, rates,
-                                                         n_rates, d_scr, sb, d_out)
-                 : max_segments ? hvd_dev_vpdq_align_segments(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack,
-                                                            max_segments, min_band_votes, d_scr, sb, d_out)
-                              : hvd_dev_vpdq_align_videos(d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, max_dist, slack,
-                                                          d_scr, sb, d_out))
+    if (int rc = align_on_device(mode, rates, n_rates, {d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, h.max_dist, h.slack, d_scr, sb, d_out}))
         return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(h.out, d_out, out_bytes, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
     return HVD_OK;
 }
@@ -1644,42 +1596,32 @@ static int align_from_host(const uint8_t* frames_q, const int64_t* offsets_q, in
 int hvd_vpdq_align_videos(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
                           const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                           const uint32_t* pairs, int64_t M, int max_dist, int slack, hvd_valign* out) {
-    return align_from_host(frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, 0,
-                           1, out);
+    return align_from_host(AlignMode::of(false, false), nullptr, 0,
+                           {frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, nullptr, 0, out});
 }
 
 int hvd_vpdq_align_segments(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
                             const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                             const uint32_t* pairs, int64_t M, int max_dist, int slack, int max_segments, int min_band_votes,
                             hvd_vsegments* out) {
-    if (int rc = check_segment_limits(max_segments, min_band_votes)) return rc;
-    return align_from_host(frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack,
-                           max_segments, min_band_votes, out);
+    return align_from_host(AlignMode::of(false, true, max_segments, min_band_votes), nullptr, 0,
+                           {frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, nullptr, 0, out});
 }
 
 int hvd_vpdq_align_rates(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
                          const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                          const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                          hvd_vrate* out) {
-    uint32_t nums = 0, dens = 0;
-    if (!hvd::pack_rate_list(rates, n_rates, &nums, &dens))
-        return fail(HVD_ERR_ARG, "rates: need 1..%d pairs (num, den) with 1 <= num, den <= 8, no common factor, none listed twice",
-                    HVD_ALIGN_MAX_RATES);
-    return align_from_host(frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, 0,
-                           1, out, rates, n_rates);
+    return align_from_host(AlignMode::of(true, false), rates, n_rates,
+                           {frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, nullptr, 0, out});
 }
 
 int hvd_vpdq_align_rate_segments(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
                                  const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                                  const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                                  int max_segments, int min_band_votes, hvd_vrsegments* out) {
-    uint32_t nums = 0, dens = 0;
-    if (!hvd::pack_rate_list(rates, n_rates, &nums, &dens))
-        return fail(HVD_ERR_ARG, "rates: need 1..%d pairs (num, den) with 1 <= num, den <= 8, no common factor, none listed twice",
-                    HVD_ALIGN_MAX_RATES);
-    if (int rc = check_segment_limits(max_segments, min_band_votes)) return rc;
-    return align_from_host(frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack,
-                           max_segments, min_band_votes, out, rates, n_rates);
+    return align_from_host(AlignMode::of(true, true, max_segments, min_band_votes), rates, n_rates,
+                           {frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, nullptr, 0, out});
 }
 
 /* ---- duplicate groups with a keeper: connected components of a pair list (k_group.hip) ---- */

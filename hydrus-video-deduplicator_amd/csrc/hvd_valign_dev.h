@@ -1,7 +1,9 @@
 // hvd_valign_dev.h -- what the time-alignment kernels share, one definition of each piece: k_valign.hip (one offset per pair,
-// DESIGN.md 4.8), k_valign_segments.hip (up to eight) and k_valign_rates.hip (one offset at the best of up to eight
-// listed rates) include it and add their records and their loops. Device code first; the last section is host
-// code: the slot count, the scratch sizing and the helper that enqueues the two launches.
+// DESIGN.md 4.8), k_valign_segments.hip (up to eight), k_valign_rates.hip (one offset at the best of up to eight
+// listed rates) and k_valign_rate_segments.hip (rate x segments) include it and add their kernel
+// and its loops; what they write into a record alike -- the hit counts of round one, a side's aligned count, first and last -- is
+// here too (k_valign_segments writes them out: with the helpers it was rescheduled and measurably moved). Device code first; the last section is host code: the slot count, the scratch sizing, the helper that enqueues the
+// two launches, and the four files' launchers, which hvd::launch_alignment (k_valign.hip) chooses among by the mode.
 //
 // The rule, integers only (include/hvd_mi355x.h has the full text):
 //   H = {(i, j) : hamming(A_i, B_j) <= max_dist},  delta(i, j) = p_b(j) - p_a(i),  votes[d] = |{(i, j) in H : delta = d}|,
@@ -146,6 +148,33 @@ __device__ __forceinline__ void count_bits(const uint32_t* flags, uint32_t n_bit
     *last = max(max(red[2], red[5]), max(red[8], red[11]));
 }
 
+// ---- what the kernels write into a record alike (lane 0 writes) -------------------------------------------------------------
+// after pass 1 of round one: the frames of b and of a with a hit at all -> rec->t_hits, rec->q_hits; returns q_hits (0: H is empty)
+template <class Rec>
+__device__ __forceinline__ uint32_t store_hit_counts(Rec* rec, const uint32_t* flags, uint32_t wa, const Side& A, const Side& B,
+                                                     uint32_t* red) {
+    uint32_t cnt, first, last;
+    count_bits(flags + wa, B.n, red, &cnt, &first, &last);
+    if (threadIdx.x == 0) rec->t_hits = cnt;
+    count_bits(flags, A.n, red, &cnt, &first, &last);
+    if (threadIdx.x == 0) rec->q_hits = cnt;
+    return cnt;
+}
+
+// after pass 2: the aligned frames of one side X (T_SIDE: video b, flags: its run of flag words) into a record or a segment
+// of one: their number, the first and the last position. -> the number
+template <bool T_SIDE, class Seg>
+__device__ __forceinline__ uint32_t store_aligned(Seg* seg, const uint32_t* flags, const Side& X, uint32_t* red) {
+    uint32_t cnt, first, last;
+    count_bits(flags, X.n, red, &cnt, &first, &last);
+    if (threadIdx.x == 0) {
+        (T_SIDE ? seg->t_aligned : seg->q_aligned) = cnt;
+        (T_SIDE ? seg->t_first : seg->q_first) = pos_of(X, min(first, X.n - 1u));
+        (T_SIDE ? seg->t_last : seg->q_last) = pos_of(X, min(last, X.n - 1u));
+    }
+    return cnt;
+}
+
 // ---- one pass over the Hamming matrix -----------------------------------------------------------------------------------
 // PASS 1: votes, and with hit_bits one bit per frame with a hit. PASS 2: the bits of the frames with a hit within slack of dstar.
 // Video a is staged, chunk by chunk; a lane keeps one frame of video b. flagA / flagB / takenA / takenB: where the runs of bit
@@ -264,15 +293,26 @@ inline size_t slot_scratch_bytes(unsigned long long max_bins, unsigned runs) {
 // LDS, one workgroup per pair up to 8192; then the pairs beyond: found again from the same geometry, by as many workgroups as
 // there are slots.
 template <class Launch>
-hipError_t launch_lds_then_scratch(unsigned long long M, void* d_scratch, size_t scratch_bytes, Launch launch) {
+hipError_t launch_lds_then_scratch(const hvd::AlignOperands& op, Launch launch) {
+    const unsigned long long M = (unsigned long long)op.M;
     if (M == 0) return hipSuccess;
     const unsigned grid = (unsigned)(M < 8192ull ? M : 8192ull);
     launch(std::false_type{}, grid, (uint32_t*)nullptr, 0u);
-    unsigned long long slot_words = d_scratch ? scratch_bytes / 4u / kSlots : 0ull;
+    unsigned long long slot_words = op.scratch ? op.scratch_bytes / 4u / kSlots : 0ull;
     if (slot_words > 2u * kMaxBins) slot_words = 2u * kMaxBins;  // (more than any pair needs)
     const unsigned big_grid = (unsigned)(M < kSlots ? M : kSlots);
-    launch(std::true_type{}, big_grid, (uint32_t*)d_scratch, (uint32_t)slot_words);
+    launch(std::true_type{}, big_grid, (uint32_t*)op.scratch, (uint32_t)slot_words);
     return hipGetLastError();
 }
 
 }  // namespace
+
+namespace hvd {
+
+// one per kernel file, each with its file's only kernel launch; launch_alignment (k_valign.hip) goes by mode.kind()
+hipError_t launch_valign(const AlignMode& mode, const AlignOperands& op, hipStream_t s);
+hipError_t launch_valign_segments(const AlignMode& mode, const AlignOperands& op, hipStream_t s);
+hipError_t launch_valign_rates(const AlignMode& mode, const AlignOperands& op, hipStream_t s);
+hipError_t launch_valign_rate_segments(const AlignMode& mode, const AlignOperands& op, hipStream_t s);
+
+}  // namespace hvd

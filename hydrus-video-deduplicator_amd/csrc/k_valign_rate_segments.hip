@@ -117,14 +117,8 @@ __global__ __launch_bounds__(256) void k_valign_rate_segments(
                 for (uint32_t k = tid; k < nbins; k += 256u) hist[k] = 0u;
                 scan_pair<1, true, true>(A, B, max_dist, stage, spos, hist, flagA, flagB, takenA, takenB, dmin, core, slack_r, 0,
                                          (s | r) == 0u, num, den);
-                if ((s | r) == 0u) {
-                    uint32_t cnt, first, last;
-                    count_bits(flags + wa, B.n, red, &cnt, &first, &last);
-                    if (tid == 0) rec->t_hits = cnt;
-                    count_bits(flags, A.n, red, &cnt, &first, &last);
-                    if (tid == 0) rec->q_hits = cnt;
-                    if (cnt == 0u) break;  // H is empty: the round is left without a winner
-                }
+                // H is empty: the round is left without a winner
+                if ((s | r) == 0u && store_hit_counts(rec, flags, wa, A, B, red) == 0u) break;
                 const Best best = best_offset<true>(hist, nbins, slack_r, dmin, wbest);
                 if (tid == 0) ub[r] = best.S;
                 if (win_r == R || best.S > win_S) {  // ties go to the earlier rate
@@ -143,29 +137,18 @@ __global__ __launch_bounds__(256) void k_valign_rate_segments(
             scan_pair<2, true, true>(A, B, max_dist, stage, spos, hist, flagA, flagB, takenA, takenB, 0, 0u, slack * max(num, den),
                                      win_d, true, num, den);
             hvd_vrsegment* seg = rec->seg + s;
-            uint32_t cnt, first, last;
-            count_bits(flags, A.n, red, &cnt, &first, &last);
-            q_covered += cnt;
+            q_covered += store_aligned<false>(seg, flags, A, red);
             if (tid == 0) {
                 seg->offset = win_d;
                 seg->band_votes = win_S;
-                seg->q_aligned = cnt;
-                seg->q_first = pos_of(A, min(first, A.n - 1u));
-                seg->q_last = pos_of(A, min(last, A.n - 1u));
                 seg->rate_num = num;
                 seg->rate_den = den;
                 seg->rate_index = win_r;
                 rec->q_covered = q_covered;
                 rec->n_segments = s + 1u;
             }
-            count_bits(flags + wa, B.n, red, &cnt, &first, &last);
-            t_covered += cnt;
-            if (tid == 0) {
-                seg->t_aligned = cnt;
-                seg->t_first = pos_of(B, min(first, B.n - 1u));
-                seg->t_last = pos_of(B, min(last, B.n - 1u));
-                rec->t_covered = t_covered;
-            }
+            t_covered += store_aligned<true>(seg, flags + wa, B, red);
+            if (tid == 0) rec->t_covered = t_covered;
             if (q_covered >= A.n || t_covered >= B.n) break;  // nothing is left of one side: no further pass
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
             for (uint32_t k = tid; k < wa + wb; k += 256u) flags[wa + wb + k] |= flags[k];  // taken |= aligned
@@ -177,17 +160,13 @@ __global__ __launch_bounds__(256) void k_valign_rate_segments(
 
 namespace hvd {
 
-size_t rate_segments_scratch_bytes(unsigned long long max_bins) { return slot_scratch_bytes(max_bins, 2u); }  // flag words and taken words
-
-hipError_t launch_valign_rate_segments(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
-                                       const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
-                                       const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, uint32_t nums,
-                                       uint32_t dens, uint32_t max_segments, uint32_t min_band_votes, void* d_scratch,
-                                       size_t scratch_bytes, hvd_vrsegments* d_out, hipStream_t s) {
-    return launch_lds_then_scratch(M, d_scratch, scratch_bytes, [&](auto big, unsigned grid, uint32_t* scratch, uint32_t slot_words) {
-        hipLaunchKernelGGL(k_valign_rate_segments<decltype(big)::value>, dim3(grid), dim3(256), 0, s, (const uint4*)d_hashes_q,
-                           d_offsets_q, VQ, d_pos_q, (const uint4*)d_hashes_t, d_offsets_t, VT, d_pos_t, (const uint2*)d_pairs,
-                           (uint32_t)M, max_dist, slack, nums, dens, max_segments, min_band_votes, scratch, slot_words, d_out);
+hipError_t launch_valign_rate_segments(const AlignMode& mode, const AlignOperands& op, hipStream_t s) {
+    return launch_lds_then_scratch(op, [&](auto big, unsigned grid, uint32_t* scratch, uint32_t slot_words) {
+        hipLaunchKernelGGL(k_valign_rate_segments<decltype(big)::value>, dim3(grid), dim3(256), 0, s, (const uint4*)op.hashes_q,
+                           (const long long*)op.offsets_q, (uint32_t)op.VQ, (const int32_t*)op.pos_q, (const uint4*)op.hashes_t,
+                           (const long long*)op.offsets_t, (uint32_t)op.VT, (const int32_t*)op.pos_t, (const uint2*)op.pairs,
+                           (uint32_t)op.M, (uint32_t)op.max_dist, (uint32_t)op.slack, mode.nums, mode.dens,
+                           (uint32_t)mode.max_segments, (uint32_t)mode.min_band_votes, scratch, slot_words, (hvd_vrsegments*)op.out);
     });
 }
 

@@ -99,13 +99,8 @@ __global__ __launch_bounds__(256) void k_valign_rates(const uint4* __restrict__ 
             scan_pair<1, false, true>(A, B, max_dist, stage, spos, hist, flagA, flagB, 0u, 0u, dmin, core, slack_r, 0, r == 0u, num,
                                       den);
             if (r == 0u) {
-                uint32_t cnt, first, last;
-                count_bits(flags + wa, B.n, red, &cnt, &first, &last);
-                if (tid == 0) rec->t_hits = cnt;
-                count_bits(flags, A.n, red, &cnt, &first, &last);
-                if (tid == 0) rec->q_hits = cnt;
-                hits = cnt;
-                if (cnt == 0u) break;  // H is empty
+                hits = store_hit_counts(rec, flags, wa, A, B, red);
+                if (hits == 0u) break;  // H is empty
             }
             const Best best = best_offset<true>(hist, nbins, slack_r, dmin, wbest);
             if (r == 0u || best.S > win_S) {  // ties go to the earlier rate
@@ -127,19 +122,8 @@ __global__ __launch_bounds__(256) void k_valign_rates(const uint4* __restrict__ 
         for (uint32_t k = tid; k < wa + wb; k += 256u) flags[k] = 0u;
         scan_pair<2, false, true>(A, B, max_dist, stage, spos, hist, flagA, flagB, 0u, 0u, 0, 0u, slack * max(num, den), win_d, true,
                                   num, den);
-        uint32_t cnt, first, last;
-        count_bits(flags, A.n, red, &cnt, &first, &last);
-        if (tid == 0) {
-            rec->q_aligned = cnt;
-            rec->q_first = pos_of(A, min(first, A.n - 1u));
-            rec->q_last = pos_of(A, min(last, A.n - 1u));
-        }
-        count_bits(flags + wa, B.n, red, &cnt, &first, &last);
-        if (tid == 0) {
-            rec->t_aligned = cnt;
-            rec->t_first = pos_of(B, min(first, B.n - 1u));
-            rec->t_last = pos_of(B, min(last, B.n - 1u));
-        }
+        store_aligned<false>(rec, flags, A, red);
+        store_aligned<true>(rec, flags + wa, B, red);
     }
 }
 
@@ -147,16 +131,13 @@ __global__ __launch_bounds__(256) void k_valign_rates(const uint4* __restrict__ 
 
 namespace hvd {
 
-size_t rates_scratch_bytes(unsigned long long max_bins) { return slot_scratch_bytes(max_bins, 1u); }  // the flag words
-
-hipError_t launch_valign_rates(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
-                               const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
-                               const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack, uint32_t nums,
-                               uint32_t dens, void* d_scratch, size_t scratch_bytes, hvd_vrate* d_out, hipStream_t s) {
-    return launch_lds_then_scratch(M, d_scratch, scratch_bytes, [&](auto big, unsigned grid, uint32_t* scratch, uint32_t slot_words) {
-        hipLaunchKernelGGL(k_valign_rates<decltype(big)::value>, dim3(grid), dim3(256), 0, s, (const uint4*)d_hashes_q, d_offsets_q,
-                           VQ, d_pos_q, (const uint4*)d_hashes_t, d_offsets_t, VT, d_pos_t, (const uint2*)d_pairs, (uint32_t)M,
-                           max_dist, slack, nums, dens, scratch, slot_words, d_out);
+hipError_t launch_valign_rates(const AlignMode& mode, const AlignOperands& op, hipStream_t s) {
+    return launch_lds_then_scratch(op, [&](auto big, unsigned grid, uint32_t* scratch, uint32_t slot_words) {
+        hipLaunchKernelGGL(k_valign_rates<decltype(big)::value>, dim3(grid), dim3(256), 0, s, (const uint4*)op.hashes_q,
+                           (const long long*)op.offsets_q, (uint32_t)op.VQ, (const int32_t*)op.pos_q, (const uint4*)op.hashes_t,
+                           (const long long*)op.offsets_t, (uint32_t)op.VT, (const int32_t*)op.pos_t, (const uint2*)op.pairs,
+                           (uint32_t)op.M, (uint32_t)op.max_dist, (uint32_t)op.slack, mode.nums, mode.dens, scratch, slot_words,
+                           (hvd_vrate*)op.out);
     });
 }
 

@@ -135,17 +135,13 @@ __global__ __launch_bounds__(256) void k_valign_segments(const uint4* __restrict
 
 namespace hvd {
 
-size_t segments_scratch_bytes(unsigned long long max_bins) { return slot_scratch_bytes(max_bins, 2u); }  // flag words and taken words
-
-hipError_t launch_valign_segments(const void* d_hashes_q, const long long* d_offsets_q, uint32_t VQ, const int32_t* d_pos_q,
-                                  const void* d_hashes_t, const long long* d_offsets_t, uint32_t VT, const int32_t* d_pos_t,
-                                  const uint32_t* d_pairs, unsigned long long M, uint32_t max_dist, uint32_t slack,
-                                  uint32_t max_segments, uint32_t min_band_votes, void* d_scratch, size_t scratch_bytes,
-                                  hvd_vsegments* d_out, hipStream_t s) {
-    return launch_lds_then_scratch(M, d_scratch, scratch_bytes, [&](auto big, unsigned grid, uint32_t* scratch, uint32_t slot_words) {
-        hipLaunchKernelGGL(k_valign_segments<decltype(big)::value>, dim3(grid), dim3(256), 0, s, (const uint4*)d_hashes_q, d_offsets_q,
-                           VQ, d_pos_q, (const uint4*)d_hashes_t, d_offsets_t, VT, d_pos_t, (const uint2*)d_pairs, (uint32_t)M,
-                           max_dist, slack, max_segments, min_band_votes, scratch, slot_words, d_out);
+hipError_t launch_valign_segments(const AlignMode& mode, const AlignOperands& op, hipStream_t s) {
+    return launch_lds_then_scratch(op, [&](auto big, unsigned grid, uint32_t* scratch, uint32_t slot_words) {
+        hipLaunchKernelGGL(k_valign_segments<decltype(big)::value>, dim3(grid), dim3(256), 0, s, (const uint4*)op.hashes_q,
+                           (const long long*)op.offsets_q, (uint32_t)op.VQ, (const int32_t*)op.pos_q, (const uint4*)op.hashes_t,
+                           (const long long*)op.offsets_t, (uint32_t)op.VT, (const int32_t*)op.pos_t, (const uint2*)op.pairs,
+                           (uint32_t)op.M, (uint32_t)op.max_dist, (uint32_t)op.slack, (uint32_t)mode.max_segments,
+                           (uint32_t)mode.min_band_votes, scratch, slot_words, (hvd_vsegments*)op.out);
     });
 }
 

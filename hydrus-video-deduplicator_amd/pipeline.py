@@ -25,7 +25,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import _lib, search, vpdq
-from ._lib import GROUP_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VRSEGMENTS_DTYPE, VSEGMENTS_DTYPE, DeviceBuffer
+from ._lib import GROUP_DTYPE, VMATCH_DTYPE, DeviceBuffer
 
 
 def hash_videos(videos, autocrop=False) -> list[vpdq.VpdqHash]:
@@ -435,28 +435,20 @@ class DeviceLibrary:
         int[M, 2]): one VALIGN_DTYPE record per pair, in their order. The hashes, the CSR and the positions stay where they
         are; the pair list goes up, the records come back. Positions: those of from_raw_hashes(positions=True), else the
         index inside the kept video."""
-        lib = _lib.ensure()
-        return self._align(records, slack, max_dist, VALIGN_DTYPE, lib.hvd_align_scratch_bytes, lib.hvd_dev_vpdq_align_videos, ())
+        return self._align(records, search.AlignMode(), slack, max_dist)
 
     def align_segments(self, records, slack: int = search.ALIGN_SLACK, max_dist: int | None = None,
                        max_segments: int = _lib.ALIGN_MAX_SEGMENTS, min_band_votes: int = 1) -> np.ndarray:
         """hvd_dev_vpdq_align_segments of the listed pairs of this library against itself: one VSEGMENTS_DTYPE record per
         pair, in their order (search.align_segments on what is in HBM; operands and positions as `align`)."""
-        lib = _lib.ensure()
-        return self._align(records, slack, max_dist, VSEGMENTS_DTYPE, lib.hvd_segments_scratch_bytes,
-                           lib.hvd_dev_vpdq_align_segments, (int(max_segments), int(min_band_votes)))
+        return self._align(records, search.AlignMode(None, max_segments, min_band_votes), slack, max_dist)
 
     def align_rates(self, records, rates=search.DEFAULT_RATES, slack: int = search.ALIGN_SLACK,
                     max_dist: int | None = None) -> np.ndarray:
         """hvd_dev_vpdq_align_rates of the listed pairs of this library against itself: one VRATE_DTYPE record per pair, in
         their order (search.align_rates on what is in HBM; operands and positions as `align`). A broken rate list gives
         INT32_MIN records, as the device entry does."""
-        lib = _lib.ensure()
-        rates = search.rate_array(rates)
-        # a pair's histogram is sized by its largest bins_r = num span_a + den span_b + 1 + 2 slack max(num, den)
-        widest = [lambda span, r=r: (int(r[0]) + int(r[1])) * span + 1 + 2 * int(slack) * int(max(r)) for r in rates]
-        return self._align(records, slack, max_dist, VRATE_DTYPE, lib.hvd_rates_scratch_bytes, lib.hvd_dev_vpdq_align_rates,
-                           (rates.ctypes.data, rates.shape[0]), widest)
+        return self._align(records, search.AlignMode(rates), slack, max_dist)
 
     def align_rate_segments(self, records, rates=search.DEFAULT_RATES, slack: int = search.ALIGN_SLACK,
                             max_dist: int | None = None, max_segments: int = _lib.ALIGN_MAX_SEGMENTS,
@@ -464,22 +456,18 @@ class DeviceLibrary:
         """hvd_dev_vpdq_align_rate_segments of the listed pairs of this library against itself: one VRSEGMENTS_DTYPE record
         per pair, in their order (search.align_rate_segments on what is in HBM; operands and positions as `align`). A broken
         rate list gives INT32_MIN records, as the device entry does."""
-        lib = _lib.ensure()
-        rates = search.rate_array(rates)
-        widest = [lambda span, r=r: (int(r[0]) + int(r[1])) * span + 1 + 2 * int(slack) * int(max(r)) for r in rates]  # (align_rates')
-        return self._align(records, slack, max_dist, VRSEGMENTS_DTYPE, lib.hvd_rate_segments_scratch_bytes,
-                           lib.hvd_dev_vpdq_align_rate_segments,
-                           (rates.ctypes.data, rates.shape[0], int(max_segments), int(min_band_votes)), widest)
+        return self._align(records, search.AlignMode(rates, max_segments, min_band_votes), slack, max_dist)
 
-    def _align(self, records, slack, max_dist, dtype, scratch_bytes, entry, extra: tuple, widest=()) -> np.ndarray:
-        """One device-resident alignment call over this library against itself: `entry` with the operands both alignments
-        share, `extra` between slack and the scratch, records of `dtype` back. widest: functions span -> bins, for an entry
-        whose histogram may be wider than span_a + span_b + 1 + 2 slack."""
+    def _align(self, records, mode: search.AlignMode, slack, max_dist) -> np.ndarray:
+        """One device-resident alignment call over this library against itself: the entries, the record dtype and the extra
+        arguments are those of the mode's row (search.ALIGN_ROWS)."""
         lib = _lib.ensure()
+        row = mode.row
+        rates = None if mode.rates is None else search.rate_array(mode.rates)
         pairs = search.pair_array(records)
         M = pairs.shape[0]
         max_dist = _default_max_dist(max_dist)
-        out = np.zeros(M, dtype=dtype)
+        out = np.zeros(M, dtype=row.dtype)
         out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
         if M == 0 or max_dist < 0:
             return out
@@ -489,19 +477,20 @@ class DeviceLibrary:
             limit = int(lengths.max()) if lengths.size else 0
         else:
             limit = self._position_limit
-        max_bins = 2 * max(limit, 1) - 1 + 2 * int(slack)
-        max_bins = min(max([max_bins] + [bins(max(limit, 1) - 1) for bins in widest]), _lib.ALIGN_MAX_BINS)
+        # a pair's histogram is sized by its largest bins_r = num span_a + den span_b + 1 + 2 slack max(num, den), slope one among them
+        max_bins = max((num + den) * (max(limit, 1) - 1) + 1 + 2 * int(slack) * max(num, den)
+                       for num, den in [(1, 1)] + ([] if rates is None else rates.tolist()))
         sb = C.c_size_t(0)
-        _lib.check(scratch_bytes(max_bins, C.byref(sb)))
+        _lib.check(getattr(lib, row.scratch_entry)(min(max_bins, _lib.ALIGN_MAX_BINS), C.byref(sb)))
         with _DeviceScope() as scope:
             d_pairs = scope.temp(DeviceBuffer.from_array(pairs))
-            d_out = scope.temp(DeviceBuffer(dtype.itemsize * M))
+            d_out = scope.temp(DeviceBuffer(row.dtype.itemsize * M))
             d_scr = scope.temp(DeviceBuffer(sb.value) if sb.value else None)
             d_pos = self.d_positions.ptr if self.d_positions is not None else None
-            _lib.check(entry(self.d_hashes.ptr, self.d_offsets.ptr, self.n_videos, d_pos, self.d_hashes.ptr, self.d_offsets.ptr,
-                             self.n_videos, d_pos, d_pairs.ptr, M, max_dist, int(slack), *extra,
-                             d_scr.ptr if d_scr else None, sb.value, d_out.ptr))
-            aligned = d_out.to_array(dtype, M)  # (the copy waits for the library stream)
+            _lib.check(getattr(lib, row.device_entry)(
+                self.d_hashes.ptr, self.d_offsets.ptr, self.n_videos, d_pos, self.d_hashes.ptr, self.d_offsets.ptr, self.n_videos,
+                d_pos, d_pairs.ptr, M, max_dist, int(slack), *mode.entry_args(rates), d_scr.ptr if d_scr else None, sb.value, d_out.ptr))
+            aligned = d_out.to_array(row.dtype, M)  # (the copy waits for the library stream)
             lib.hvd_dev_sync()  # nothing may still run on a buffer that is freed here
         return aligned
 
@@ -1147,18 +1136,18 @@ def find_keeper_groups_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: 
     return search.keeper_groups_from(keeper_of, groups), keeper_of, groups, library
 
 
-def _aligned_search_on_device(d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library, align, fold):
+def _aligned_search_on_device(mode, d_frames_ptr, raw_offsets, h, w, channels, threshold, min_aligned, slack, positions, keep_library):
     """The chain of the excerpt searches on frames in HBM, one device: hash -> quality filter + CSR, with the kept frames' raw
-    positions (`DeviceLibrary.from_raw_hashes(positions=True)`) -> video search -> align(library, records) -> fold(aligned,
-    lengths, similarity). -> (fold's result, search records, alignment records, library or None)."""
+    positions (`DeviceLibrary.from_raw_hashes(positions=True)`) -> video search -> the mode's alignment of its records -> the
+    mode's fold (search.fold_aligned_records). -> (fold's result, search records, alignment records, library or None)."""
     library = _hashed_library(
         raw_offsets, 0, 1, None, lambda mine: hash_frames_on_device(d_frames_ptr, int(mine[-1]), h, w, channels), 32,
         lambda *raw: DeviceLibrary.from_raw_hashes(*raw, positions=bool(positions)), None)
     try:
         recs = library.match_videos()
-        aligned = align(library, recs)
+        aligned = library._align(recs, mode, slack, None)
         lengths = library.lengths()
-        out = fold(aligned, lengths, search.similarity_of_records(recs, lengths))
+        out = search.fold_aligned_records(mode, aligned, lengths, search.similarity_of_records(recs, lengths), threshold, min_aligned)
     except BaseException:
         library.free()
         raise
@@ -1177,9 +1166,8 @@ def find_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, 
     positions=False aligns on the index inside the KEPT video instead: a frame the quality filter dropped then shifts
     everything after it (kept for comparison; the default is what a caller wants).
     -> (excerpts, search records, alignment records, library or None); Excerpt offsets / first / last are raw frame indices."""
-    return _aligned_search_on_device(
-        d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library, lambda library, recs: library.align(recs, slack=slack),
-        lambda aligned, lengths, sim: search.excerpts_from_records(aligned, lengths, sim, threshold, min_aligned))
+    return _aligned_search_on_device(search.AlignMode(), d_frames_ptr, raw_offsets, h, w, channels, threshold, min_aligned, slack,
+                                     positions, keep_library)
 
 
 def find_segmented_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
@@ -1190,10 +1178,8 @@ def find_segmented_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray
     multi-segment alignment (`DeviceLibrary.align_segments`, min_band_votes = min_aligned) and the keep rule of
     search.segmented_excerpts_from_records; nothing but records crosses PCIe.
     -> (segmented excerpts, search records, VSEGMENTS records, library or None); positions are raw frame indices."""
-    return _aligned_search_on_device(
-        d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library,
-        lambda library, recs: library.align_segments(recs, slack=slack, max_segments=max_segments, min_band_votes=int(min_aligned)),
-        lambda aligned, lengths, sim: search.segmented_excerpts_from_records(aligned, lengths, sim, threshold, min_aligned))
+    return _aligned_search_on_device(search.AlignMode(None, max_segments, int(min_aligned)), d_frames_ptr, raw_offsets, h, w,
+                                     channels, threshold, min_aligned, slack, positions, keep_library)
 
 
 def find_rate_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
@@ -1202,10 +1188,8 @@ def find_rate_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: 
     """search.find_rate_excerpts on frames in HBM, one device: the chain of `find_excerpts_on_device` with the rate-aware
     alignment (`DeviceLibrary.align_rates`) and the keep rule of search.rate_excerpts_from_records; nothing but records
     crosses PCIe. -> (rate excerpts, search records, VRATE records, library or None); positions are raw frame indices."""
-    return _aligned_search_on_device(
-        d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library,
-        lambda library, recs: library.align_rates(recs, rates=rates, slack=slack),
-        lambda aligned, lengths, sim: search.rate_excerpts_from_records(aligned, lengths, sim, threshold, min_aligned))
+    return _aligned_search_on_device(search.AlignMode(rates), d_frames_ptr, raw_offsets, h, w, channels, threshold, min_aligned,
+                                     slack, positions, keep_library)
 
 
 def find_rate_segmented_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
@@ -1216,11 +1200,8 @@ def find_rate_segmented_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.nd
     rate-aware multi-segment alignment (`DeviceLibrary.align_rate_segments`, min_band_votes = min_aligned) and the keep rule of
     search.rate_segmented_excerpts_from_records; nothing but records crosses PCIe.
     -> (rate-segmented excerpts, search records, VRSEGMENTS records, library or None); positions are raw frame indices."""
-    return _aligned_search_on_device(
-        d_frames_ptr, raw_offsets, h, w, channels, positions, keep_library,
-        lambda library, recs: library.align_rate_segments(recs, rates=rates, slack=slack, max_segments=max_segments,
-                                                          min_band_votes=int(min_aligned)),
-        lambda aligned, lengths, sim: search.rate_segmented_excerpts_from_records(aligned, lengths, sim, threshold, min_aligned))
+    return _aligned_search_on_device(search.AlignMode(rates, max_segments, int(min_aligned)), d_frames_ptr, raw_offsets, h, w,
+                                     channels, threshold, min_aligned, slack, positions, keep_library)
 
 
 def _rank0_of_every_context(entry, frames_of_rank, timings, n_results: int, *args, **kwargs):

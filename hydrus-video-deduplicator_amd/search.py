@@ -511,6 +511,52 @@ def _align_operands(frames, offsets, pairs, positions, max_dist, frames_t, offse
     return frames, offsets, positions, frames_t, offsets_t, positions_t, pair_array(pairs), max_dist
 
 
+class AlignMode(namedtuple("AlignMode", "rates max_segments min_band_votes")):
+    """Which of the four time alignments a call is, and what only some of them take. rates: None = slope one
+    only, else the list of (num, den) of align_rates; max_segments: None = one line per pair, else align_segments' limit;
+    min_band_votes: align_segments' floor (the excerpt searches also take None: their min_aligned). `row` is the mode's line
+    of the table below: everything else that differs between the four, at every level above the kernels."""
+    __slots__ = ()
+
+    def __new__(cls, rates=None, max_segments=None, min_band_votes=1):
+        return super().__new__(cls, rates, max_segments, min_band_votes)
+
+    @property
+    def row(self) -> "AlignRow":
+        return ALIGN_ROWS[self.rates is not None, self.max_segments is not None]
+
+    def entry_args(self, rates: np.ndarray | None) -> tuple:
+        """What the mode's C entries take between slack and the scratch / the records; rates: rate_array(self.rates), which
+        the caller keeps alive over the call."""
+        return (() if rates is None else (rates.ctypes.data, rates.shape[0])) + \
+            (() if self.max_segments is None else (int(self.max_segments), int(self.min_band_votes)))
+
+
+# One row per (rated, segmented): the record dtype, the host, device and scratch-size entries of the C ABI, the name of the
+# align_* function here and on a `matcher`, and the result tuples of the fold (ALIGN_ROWS, below them).
+AlignRow = namedtuple("AlignRow", "dtype host_entry device_entry scratch_entry method excerpt segment")
+
+
+def _align(mode: AlignMode, frames, offsets, pairs, positions, max_dist, slack, frames_t, offsets_t, positions_t) -> np.ndarray:
+    """The call behind align_videos, align_segments, align_rates and align_rate_segments."""
+    row = mode.row
+    frames, offsets, positions, frames_t, offsets_t, positions_t, pairs, max_dist = _align_operands(
+        frames, offsets, pairs, positions, max_dist, frames_t, offsets_t, positions_t)
+    rates = None if mode.rates is None else rate_array(mode.rates)
+    M = pairs.shape[0]
+    out = np.zeros(M, dtype=row.dtype)
+    out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
+    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
+        if rates is None:
+            return out
+        max_dist, M = 0, 0  # (a rate entry still judges the list, the limits and the libraries)
+    lib = _lib.ensure()
+    _lib.check(getattr(lib, row.host_entry)(
+        _ptr(frames), offsets.ctypes.data, offsets.size - 1, _ptr(positions), _ptr(frames_t), offsets_t.ctypes.data,
+        offsets_t.size - 1, _ptr(positions_t), _ptr(pairs), M, max_dist, int(slack), *mode.entry_args(rates), _ptr(out)))
+    return out
+
+
 def align_videos(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.ndarray | None = None,
                  max_dist: int | None = None, slack: int = ALIGN_SLACK, frames_t: np.ndarray | None = None,
                  offsets_t: np.ndarray | None = None, positions_t: np.ndarray | None = None) -> np.ndarray:
@@ -520,21 +566,77 @@ def align_videos(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.n
     too unless frames_t / offsets_t (/ positions_t) give another one. A record holds the pair's vPDQ counters, the best
     offset (p_b = p_a + offset), the frame hits within `slack` of it, and per side the number of frames with such a hit and
     the first and last position among them; max_dist defaults to the search's frame tolerance."""
-    frames, offsets, positions, frames_t, offsets_t, positions_t, pairs, max_dist = _align_operands(
-        frames, offsets, pairs, positions, max_dist, frames_t, offsets_t, positions_t)
-    M = pairs.shape[0]
-    out = np.zeros(M, dtype=VALIGN_DTYPE)
-    out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
-    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
-        return out
-    lib = _lib.ensure()
-    _lib.check(lib.hvd_vpdq_align_videos(_ptr(frames), offsets.ctypes.data, offsets.size - 1, _ptr(positions), _ptr(frames_t),
-                                         offsets_t.ctypes.data, offsets_t.size - 1, _ptr(positions_t), _ptr(pairs), M,
-                                         max_dist, int(slack), _ptr(out)))
-    return out
+    return _align(AlignMode(), frames, offsets, pairs, positions, max_dist, slack, frames_t, offsets_t, positions_t)
 
 
 Excerpt = namedtuple("Excerpt", "short long offset first last coverage similarity")
+Segment = namedtuple("Segment", "offset short_first short_last first last aligned")
+SegmentedExcerpt = namedtuple("SegmentedExcerpt", "short long coverage similarity segments")
+RateExcerpt = namedtuple("RateExcerpt", "short long rate offset first last coverage similarity")
+RateSegment = namedtuple("RateSegment", "rate offset short_first short_last first last aligned")
+RateSegmentedExcerpt = namedtuple("RateSegmentedExcerpt", "short long coverage similarity segments")
+
+ALIGN_ROWS = {
+    (False, False): AlignRow(VALIGN_DTYPE, "hvd_vpdq_align_videos", "hvd_dev_vpdq_align_videos", "hvd_align_scratch_bytes",
+                             "align_videos", Excerpt, None),
+    (False, True): AlignRow(VSEGMENTS_DTYPE, "hvd_vpdq_align_segments", "hvd_dev_vpdq_align_segments", "hvd_segments_scratch_bytes",
+                            "align_segments", SegmentedExcerpt, Segment),
+    (True, False): AlignRow(VRATE_DTYPE, "hvd_vpdq_align_rates", "hvd_dev_vpdq_align_rates", "hvd_rates_scratch_bytes",
+                            "align_rates", RateExcerpt, None),
+    (True, True): AlignRow(VRSEGMENTS_DTYPE, "hvd_vpdq_align_rate_segments", "hvd_dev_vpdq_align_rate_segments",
+                           "hvd_rate_segments_scratch_bytes", "align_rate_segments", RateSegmentedExcerpt, RateSegment),
+}
+
+
+def _line_in_long(num: int, den: int, d: int, a_short: bool) -> tuple:
+    """The line (num, den, d) of a record, p_b = (num / den) p_a + d / den, in long's timeline -> (rate, offset) with
+    p_long = rate * p_short + offset: as it stands when a is short, p_a = (den / num) p_b - d / num when b is."""
+    return (Fraction(num, den), Fraction(d, den)) if a_short else (Fraction(den, num), Fraction(-d, num))
+
+
+def fold_aligned_records(mode: AlignMode, aligned: np.ndarray, lengths: np.ndarray, similarity: np.ndarray, threshold: float = 50.0,
+                         min_aligned: int = 4) -> list:
+    """The keep rule behind excerpts_from_records, segmented_excerpts_from_records, rate_excerpts_from_records and
+    rate_segmented_excerpts_from_records, on records of mode.row.dtype (pure numpy; no device). A single-line record is read
+    as a record with one segment. short = the video with fewer frames (a on a tie); a segment counts iff at least min_aligned
+    frames of short are aligned in it; coverage = 100 * those frames over the segments that count / frames of short; kept iff
+    int(coverage) >= int(threshold) and at least one segment counts. A pair the entry could not align (its first line's offset
+    INT32_MIN) and a pair with an empty video are skipped. -> sorted list of mode.row.excerpt; the slope-one modes give plain
+    int offsets and no rate."""
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    row, rated, segmented = mode.row, mode.rates is not None, mode.max_segments is not None
+    lengths = np.asarray(lengths, dtype=np.int64)
+    out = []
+    for r, sim in zip(aligned, similarity):
+        a, b = int(r["a"]), int(r["b"])
+        a_short = lengths[a] <= lengths[b]
+        short, long = (a, b) if a_short else (b, a)
+        n_short = int(lengths[short])
+        lines = r["seg"][:int(r["n_segments"])] if segmented else (r,)
+        if n_short == 0 or int((r["seg"][0] if segmented else r)["offset"]) == -(1 << 31):
+            continue
+        segs = []
+        for s in lines:
+            on = int(s["q_aligned"] if a_short else s["t_aligned"])
+            if on < int(min_aligned):
+                continue
+            line = _line_in_long(int(s["rate_num"]) if rated else 1, int(s["rate_den"]) if rated else 1, int(s["offset"]), a_short)
+            in_a, in_b = (int(s["q_first"]), int(s["q_last"])), (int(s["t_first"]), int(s["t_last"]))
+            segs.append((line if rated else (int(line[1]),), *((in_a, in_b) if a_short else (in_b, in_a)), on))
+        if not segs:
+            continue
+        coverage = 100.0 * sum(on for *_, on in segs) / n_short
+        if int(coverage) < int(threshold):
+            continue
+        if segmented:
+            segs = sorted((row.segment(*line, *in_short, *in_long, on) for line, in_short, in_long, on in segs),
+                          key=lambda s: s.short_first)
+            out.append(row.excerpt(short, long, coverage, float(sim), tuple(segs)))
+        else:
+            ((line, _, in_long, _),) = segs
+            out.append(row.excerpt(short, long, *line, *in_long, coverage, float(sim)))
+    return sorted(out)
 
 
 def excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: np.ndarray, threshold: float = 50.0,
@@ -543,23 +645,7 @@ def excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: 
     a tie); coverage = 100 * aligned frames of short / frames of short; kept iff int(coverage) >= int(threshold) and at least
     min_aligned frames of short are aligned. -> sorted list of Excerpt; offset / first / last are in long's timeline
     (p_long = p_short + offset)."""
-    if int(threshold) < 1:
-        raise ValueError("threshold < 1 would select every pair of videos")
-    lengths = np.asarray(lengths, dtype=np.int64)
-    out = []
-    for r, sim in zip(aligned, similarity):
-        a, b = int(r["a"]), int(r["b"])
-        a_short = lengths[a] <= lengths[b]
-        n_short = int(lengths[a] if a_short else lengths[b])
-        on = int(r["q_aligned"] if a_short else r["t_aligned"])
-        if n_short == 0 or on < int(min_aligned) or int(r["offset"]) == -(1 << 31):
-            continue
-        coverage = 100.0 * on / n_short
-        if int(coverage) < int(threshold):
-            continue
-        out.append(Excerpt(a, b, int(r["offset"]), int(r["t_first"]), int(r["t_last"]), coverage, float(sim)) if a_short else
-                   Excerpt(b, a, -int(r["offset"]), int(r["q_first"]), int(r["q_last"]), coverage, float(sim)))
-    return sorted(out)
+    return fold_aligned_records(AlignMode(), aligned, lengths, similarity, threshold, min_aligned)
 
 
 def _positions_of(positions, blobs: list, lengths) -> np.ndarray | None:
@@ -572,18 +658,29 @@ def _positions_of(positions, blobs: list, lengths) -> np.ndarray | None:
         np.zeros(0, np.int32)
 
 
+def _excerpt_pairs(mode: AlignMode, blobs: list, threshold, min_aligned, slack, positions, matcher) -> list:
+    """The body behind excerpt_pairs, segmented_excerpt_pairs, rate_excerpt_pairs and rate_segmented_excerpt_pairs: the video
+    search, the mode's alignment of its records (a segmented one stops at min_band_votes, None = min_aligned) and their fold."""
+    more = {} if mode.rates is None else {"rates": mode.rates}  # what the mode's align_* takes beyond align_videos' keywords
+    if mode.max_segments is not None:
+        mode = mode._replace(min_band_votes=int(min_aligned if mode.min_band_votes is None else mode.min_band_votes))
+        more.update(max_segments=mode.max_segments, min_band_votes=mode.min_band_votes)
+    mv, al = (match_videos, globals()[mode.row.method]) if matcher is None else (matcher.match_videos, getattr(matcher, mode.row.method))
+    frames, offsets, lengths = pack_hashes(blobs)
+    pos = _positions_of(positions, blobs, lengths)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
+    recs = mv(frames, offsets, max_dist)
+    aligned = al(frames, offsets, np.stack([recs["a"], recs["b"]], axis=1), positions=pos, max_dist=max_dist, slack=slack,
+                 **more)
+    return fold_aligned_records(mode, aligned, lengths, similarity_of_records(recs, lengths), threshold, min_aligned)
+
+
 def excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK, positions=None,
                   matcher=None) -> list:
     """The search and the alignment of find_excerpts and their fold, on validated blobs (blobs[v]: the hash bytes of video v;
     positions: None, or one int sequence per video). matcher: object with match_videos / align_videos (default: the GPU
     entry points of this module). -> excerpts_from_records(...)."""
-    mv, al = (match_videos, align_videos) if matcher is None else (matcher.match_videos, matcher.align_videos)
-    frames, offsets, lengths = pack_hashes(blobs)
-    pos = _positions_of(positions, blobs, lengths)
-    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
-    recs = mv(frames, offsets, max_dist)
-    aligned = al(frames, offsets, np.stack([recs["a"], recs["b"]], axis=1), positions=pos, max_dist=max_dist, slack=slack)
-    return excerpts_from_records(aligned, lengths, similarity_of_records(recs, lengths), threshold, min_aligned)
+    return _excerpt_pairs(AlignMode(), blobs, threshold, min_aligned, slack, positions, matcher)
 
 
 def find_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
@@ -614,22 +711,8 @@ def align_segments(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np
     its best band holds fewer than `min_band_votes` hits. A record holds the pair's vPDQ counters, n_segments, the frames of
     a and of b that the segments cover, and the segments in the order they were found (the words of a VALIGN_DTYPE record from
     offset on; seg[0] IS the align_videos record of the pair)."""
-    frames, offsets, positions, frames_t, offsets_t, positions_t, pairs, max_dist = _align_operands(
-        frames, offsets, pairs, positions, max_dist, frames_t, offsets_t, positions_t)
-    M = pairs.shape[0]
-    out = np.zeros(M, dtype=VSEGMENTS_DTYPE)
-    out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
-    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
-        return out
-    lib = _lib.ensure()
-    _lib.check(lib.hvd_vpdq_align_segments(_ptr(frames), offsets.ctypes.data, offsets.size - 1, _ptr(positions), _ptr(frames_t),
-                                           offsets_t.ctypes.data, offsets_t.size - 1, _ptr(positions_t), _ptr(pairs), M,
-                                           max_dist, int(slack), int(max_segments), int(min_band_votes), _ptr(out)))
-    return out
-
-
-Segment = namedtuple("Segment", "offset short_first short_last first last aligned")
-SegmentedExcerpt = namedtuple("SegmentedExcerpt", "short long coverage similarity segments")
+    return _align(AlignMode(None, max_segments, min_band_votes), frames, offsets, pairs, positions, max_dist, slack, frames_t,
+                  offsets_t, positions_t)
 
 
 def segmented_excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: np.ndarray,
@@ -640,33 +723,7 @@ def segmented_excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, si
     int(threshold) and at least one segment counts. -> sorted list of SegmentedExcerpt(short, long, coverage, similarity,
     segments); segments: the ones that count, ordered by short_first, each Segment(offset, short_first, short_last, first,
     last, aligned) in long's timeline as Excerpt is (p_long = p_short + offset; first / last: positions in long)."""
-    if int(threshold) < 1:
-        raise ValueError("threshold < 1 would select every pair of videos")
-    lengths = np.asarray(lengths, dtype=np.int64)
-    out = []
-    for r, sim in zip(aligned, similarity):
-        a, b = int(r["a"]), int(r["b"])
-        a_short = lengths[a] <= lengths[b]
-        n_short = int(lengths[a] if a_short else lengths[b])
-        if n_short == 0:
-            continue
-        segs = []
-        for s in r["seg"][:int(r["n_segments"])]:
-            on = int(s["q_aligned"] if a_short else s["t_aligned"])
-            if on < int(min_aligned):
-                continue
-            segs.append(Segment(int(s["offset"]), int(s["q_first"]), int(s["q_last"]), int(s["t_first"]), int(s["t_last"]), on)
-                        if a_short else
-                        Segment(-int(s["offset"]), int(s["t_first"]), int(s["t_last"]), int(s["q_first"]), int(s["q_last"]), on))
-        if not segs:
-            continue
-        coverage = 100.0 * sum(s.aligned for s in segs) / n_short
-        if int(coverage) < int(threshold):
-            continue
-        segs = tuple(sorted(segs, key=lambda s: s.short_first))
-        out.append(SegmentedExcerpt(a, b, coverage, float(sim), segs) if a_short else
-                   SegmentedExcerpt(b, a, coverage, float(sim), segs))
-    return sorted(out)
+    return fold_aligned_records(AlignMode(None, ALIGN_MAX_SEGMENTS), aligned, lengths, similarity, threshold, min_aligned)
 
 
 def segmented_excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
@@ -675,14 +732,7 @@ def segmented_excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: i
     """The search and the segment alignment of find_segmented_excerpts and their fold, on validated blobs (as
     excerpt_pairs). matcher: object with match_videos / align_segments (default: the GPU entry points of this module).
     min_band_votes: None = min_aligned (see find_segmented_excerpts). -> segmented_excerpts_from_records(...)."""
-    mv, al = (match_videos, align_segments) if matcher is None else (matcher.match_videos, matcher.align_segments)
-    frames, offsets, lengths = pack_hashes(blobs)
-    pos = _positions_of(positions, blobs, lengths)
-    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
-    recs = mv(frames, offsets, max_dist)
-    aligned = al(frames, offsets, np.stack([recs["a"], recs["b"]], axis=1), positions=pos, max_dist=max_dist, slack=slack,
-                 max_segments=max_segments, min_band_votes=int(min_aligned if min_band_votes is None else min_band_votes))
-    return segmented_excerpts_from_records(aligned, lengths, similarity_of_records(recs, lengths), threshold, min_aligned)
+    return _excerpt_pairs(AlignMode(None, max_segments, min_band_votes), blobs, threshold, min_aligned, slack, positions, matcher)
 
 
 def find_segmented_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
@@ -730,22 +780,7 @@ def align_rates(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.nd
     rate_num, rate_den and rate_index. With rates = ((1, 1),) these ARE align_videos' records. The default list has 1x, the
     common speeds and their inverses except (1, 2): the limit is eight, list it in place of another if b may be the half-speed
     one."""
-    frames, offsets, positions, frames_t, offsets_t, positions_t, pairs, max_dist = _align_operands(
-        frames, offsets, pairs, positions, max_dist, frames_t, offsets_t, positions_t)
-    rates = rate_array(rates)
-    M = pairs.shape[0]
-    out = np.zeros(M, dtype=VRATE_DTYPE)
-    out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
-    lib = _lib.ensure()
-    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
-        max_dist, M = 0, 0  # (the entry still judges the list and the libraries)
-    _lib.check(lib.hvd_vpdq_align_rates(_ptr(frames), offsets.ctypes.data, offsets.size - 1, _ptr(positions), _ptr(frames_t),
-                                        offsets_t.ctypes.data, offsets_t.size - 1, _ptr(positions_t), _ptr(pairs), M,
-                                        max_dist, int(slack), rates.ctypes.data, rates.shape[0], _ptr(out)))
-    return out
-
-
-RateExcerpt = namedtuple("RateExcerpt", "short long rate offset first last coverage similarity")
+    return _align(AlignMode(rates), frames, offsets, pairs, positions, max_dist, slack, frames_t, offsets_t, positions_t)
 
 
 def rate_excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: np.ndarray, threshold: float = 50.0,
@@ -756,25 +791,7 @@ def rate_excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similar
     rate and offset are Fractions in long's timeline, p_long = rate * p_short + offset: a record (num, den, d) reads
     p_b = (num / den) p_a + d / den when a is short, and p_a = (den / num) p_b - d / num when b is. first / last: positions in
     long."""
-    if int(threshold) < 1:
-        raise ValueError("threshold < 1 would select every pair of videos")
-    lengths = np.asarray(lengths, dtype=np.int64)
-    out = []
-    for r, sim in zip(aligned, similarity):
-        a, b = int(r["a"]), int(r["b"])
-        a_short = lengths[a] <= lengths[b]
-        n_short = int(lengths[a] if a_short else lengths[b])
-        on = int(r["q_aligned"] if a_short else r["t_aligned"])
-        if n_short == 0 or on < int(min_aligned) or int(r["offset"]) == -(1 << 31):
-            continue
-        coverage = 100.0 * on / n_short
-        if int(coverage) < int(threshold):
-            continue
-        num, den, d = int(r["rate_num"]), int(r["rate_den"]), int(r["offset"])
-        out.append(RateExcerpt(a, b, Fraction(num, den), Fraction(d, den), int(r["t_first"]), int(r["t_last"]), coverage, float(sim))
-                   if a_short else
-                   RateExcerpt(b, a, Fraction(den, num), Fraction(-d, num), int(r["q_first"]), int(r["q_last"]), coverage, float(sim)))
-    return sorted(out)
+    return fold_aligned_records(AlignMode(DEFAULT_RATES), aligned, lengths, similarity, threshold, min_aligned)
 
 
 def rate_excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK, rates=DEFAULT_RATES,
@@ -782,14 +799,7 @@ def rate_excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 
     """The search and the rate alignment of find_rate_excerpts and their fold, on validated blobs (as excerpt_pairs).
     matcher: object with match_videos / align_rates (default: the GPU entry points of this module).
     -> rate_excerpts_from_records(...)."""
-    mv, al = (match_videos, align_rates) if matcher is None else (matcher.match_videos, matcher.align_rates)
-    frames, offsets, lengths = pack_hashes(blobs)
-    pos = _positions_of(positions, blobs, lengths)
-    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
-    recs = mv(frames, offsets, max_dist)
-    aligned = al(frames, offsets, np.stack([recs["a"], recs["b"]], axis=1), positions=pos, rates=rates, slack=slack,
-                 max_dist=max_dist)
-    return rate_excerpts_from_records(aligned, lengths, similarity_of_records(recs, lengths), threshold, min_aligned)
+    return _excerpt_pairs(AlignMode(rates), blobs, threshold, min_aligned, slack, positions, matcher)
 
 
 def find_rate_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
@@ -823,24 +833,8 @@ def align_rate_segments(frames: np.ndarray, offsets: np.ndarray, pairs, position
     The default list lacks (1, 2): a 2x reel is segmented cleanly when it is the `a` side of its pair (rate (2, 1)); as the `b`
     side the neighbouring rates of the list fragment it into short segments that still cover nearly all of it -- list (1, 2)
     in place of another rate if b may be the sped-up one."""
-    frames, offsets, positions, frames_t, offsets_t, positions_t, pairs, max_dist = _align_operands(
-        frames, offsets, pairs, positions, max_dist, frames_t, offsets_t, positions_t)
-    rates = rate_array(rates)
-    M = pairs.shape[0]
-    out = np.zeros(M, dtype=VRSEGMENTS_DTYPE)
-    out["a"], out["b"] = pairs[:, 0], pairs[:, 1]
-    lib = _lib.ensure()
-    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
-        max_dist, M = 0, 0  # (the entry still judges the list, the limits and the libraries)
-    _lib.check(lib.hvd_vpdq_align_rate_segments(_ptr(frames), offsets.ctypes.data, offsets.size - 1, _ptr(positions),
-                                                _ptr(frames_t), offsets_t.ctypes.data, offsets_t.size - 1, _ptr(positions_t),
-                                                _ptr(pairs), M, max_dist, int(slack), rates.ctypes.data, rates.shape[0],
-                                                int(max_segments), int(min_band_votes), _ptr(out)))
-    return out
-
-
-RateSegment = namedtuple("RateSegment", "rate offset short_first short_last first last aligned")
-RateSegmentedExcerpt = namedtuple("RateSegmentedExcerpt", "short long coverage similarity segments")
+    return _align(AlignMode(rates, max_segments, min_band_votes), frames, offsets, pairs, positions, max_dist, slack, frames_t,
+                  offsets_t, positions_t)
 
 
 def rate_segmented_excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: np.ndarray,
@@ -853,36 +847,7 @@ def rate_segmented_excerpts_from_records(aligned: np.ndarray, lengths: np.ndarra
     p_a = (den / num) p_b - d / num when b is. -> sorted list of RateSegmentedExcerpt(short, long, coverage, similarity,
     segments); segments: the ones that count, ordered by short_first, each RateSegment(rate, offset, short_first, short_last,
     first, last, aligned) with rate and offset Fractions in long's timeline, p_long = rate * p_short + offset."""
-    if int(threshold) < 1:
-        raise ValueError("threshold < 1 would select every pair of videos")
-    lengths = np.asarray(lengths, dtype=np.int64)
-    out = []
-    for r, sim in zip(aligned, similarity):
-        a, b = int(r["a"]), int(r["b"])
-        a_short = lengths[a] <= lengths[b]
-        n_short = int(lengths[a] if a_short else lengths[b])
-        if n_short == 0 or int(r["seg"][0]["offset"]) == -(1 << 31):
-            continue
-        segs = []
-        for s in r["seg"][:int(r["n_segments"])]:
-            on = int(s["q_aligned"] if a_short else s["t_aligned"])
-            if on < int(min_aligned):
-                continue
-            num, den, d = int(s["rate_num"]), int(s["rate_den"]), int(s["offset"])
-            segs.append(RateSegment(Fraction(num, den), Fraction(d, den), int(s["q_first"]), int(s["q_last"]), int(s["t_first"]),
-                                    int(s["t_last"]), on)
-                        if a_short else
-                        RateSegment(Fraction(den, num), Fraction(-d, num), int(s["t_first"]), int(s["t_last"]), int(s["q_first"]),
-                                    int(s["q_last"]), on))
-        if not segs:
-            continue
-        coverage = 100.0 * sum(s.aligned for s in segs) / n_short
-        if int(coverage) < int(threshold):
-            continue
-        segs = tuple(sorted(segs, key=lambda s: s.short_first))
-        out.append(RateSegmentedExcerpt(a, b, coverage, float(sim), segs) if a_short else
-                   RateSegmentedExcerpt(b, a, coverage, float(sim), segs))
-    return sorted(out)
+    return fold_aligned_records(AlignMode(DEFAULT_RATES, ALIGN_MAX_SEGMENTS), aligned, lengths, similarity, threshold, min_aligned)
 
 
 def rate_segmented_excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
@@ -891,14 +856,7 @@ def rate_segmented_excerpt_pairs(blobs: list, threshold: float = 50.0, min_align
     matcher: object with match_videos / align_rate_segments (default: the GPU entry points of this module). The alignment is
     asked to stop at min_band_votes = min_aligned (see find_rate_segmented_excerpts).
     -> rate_segmented_excerpts_from_records(...)."""
-    mv, al = (match_videos, align_rate_segments) if matcher is None else (matcher.match_videos, matcher.align_rate_segments)
-    frames, offsets, lengths = pack_hashes(blobs)
-    pos = _positions_of(positions, blobs, lengths)
-    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
-    recs = mv(frames, offsets, max_dist)
-    aligned = al(frames, offsets, np.stack([recs["a"], recs["b"]], axis=1), positions=pos, rates=rates, slack=slack,
-                 max_dist=max_dist, max_segments=max_segments, min_band_votes=int(min_aligned))
-    return rate_segmented_excerpts_from_records(aligned, lengths, similarity_of_records(recs, lengths), threshold, min_aligned)
+    return _excerpt_pairs(AlignMode(rates, max_segments, None), blobs, threshold, min_aligned, slack, positions, matcher)
 
 
 def find_rate_segmented_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
@@ -1216,7 +1174,7 @@ def without_common_frames(video_hashes, max_videos: int, max_share: int = 50, ma
     return CommonFrames(hashes, kept_pos, dropped, spread)
 
 
-# ------------------------------------------------ static scenes: one keyframe per run of frames (DESIGN 4.19) ------
+# ------------------------------------------------ static scenes: one keyframe per run of frames (DESIGN 4.21) ------
 
 MAX_RUN_LIMIT = 1 << 20
 

@@ -24,7 +24,7 @@ def test_grid_cap_and_slots_are_what_the_many_pairs_tests_assume(src):
     # both launches are grid-stride loops over the pair list
     assert len(re.findall(r"for \(uint32_t p = blockIdx\.x; p < (?:K\.)?M; p \+= gridDim\.x\)", text)) == 1
     # ... and the file's only kernel launch is the one it hands to the shared helper, at the grid the helper gives it
-    assert len(re.findall(r"\blaunch_lds_then_scratch\(M, d_scratch, scratch_bytes,", text)) == 1
+    assert len(re.findall(r"\blaunch_lds_then_scratch\(op,", text)) == 1
     assert re.findall(r"hipLaunchKernelGGL\((\w+)<decltype\(big\)::value>, dim3\((\w+)\), dim3\(256\)", text) == [(src[:-4], "grid")]
     assert text.count("hipLaunchKernelGGL") == 1 and '#include "hvd_valign_dev.h"' in text
     text = open(os.path.join(CSRC, "hvd_valign_dev.h")).read()

@@ -280,10 +280,13 @@ def test_the_new_file_has_the_shape_of_its_siblings():
     src = "k_valign_rate_segments.hip"
     text = open(os.path.join(CSRC, src)).read()
     assert len(re.findall(r"for \(uint32_t p = blockIdx\.x; p < (?:K\.)?M; p \+= gridDim\.x\)", text)) == 1
-    assert len(re.findall(r"\blaunch_lds_then_scratch\(M, d_scratch, scratch_bytes,", text)) == 1
+    assert len(re.findall(r"\blaunch_lds_then_scratch\(op,", text)) == 1
     assert re.findall(r"hipLaunchKernelGGL\((\w+)<decltype\(big\)::value>, dim3\((\w+)\), dim3\(256\)", text) == [(src[:-4], "grid")]
     assert text.count("hipLaunchKernelGGL") == 1 and '#include "hvd_valign_dev.h"' in text
-    assert "slot_scratch_bytes(max_bins, 2u)" in text and "asm" not in text
+    assert "asm" not in text
+    # the taken words: two pairs of runs of bit words in a slot, read off the mode (hvd::alignment_scratch_bytes in k_valign.hip)
+    assert "slot_scratch_bytes(max_bins, mode.runs())" in open(os.path.join(CSRC, "k_valign.hip")).read()
+    assert "unsigned runs() const { return segmented ? 2u : 1u; }" in open(os.path.join(CSRC, "hvd_kernels.h")).read()
     make = open(os.path.join(CSRC, "Makefile")).read()
     assert make.count("k_valign_rate_segments.o") == 3  # OBJS, the asan link line, the hvd_valign_dev.h dependency line
     assert re.search(r"^k_valign\.o .*k_valign_rate_segments\.o: hvd_valign_dev\.h$", make, re.M)
