@@ -713,6 +713,11 @@ int hvd_debug_set(const char* key, int value) {
         hvd::g_index_join_wgs = value;
         return HVD_OK;
     }
+    if (strcmp(key, "index_tile_split") == 0) {  // tests only: block groups per tile of the index build's k_index_scatter; 0 = from n and the compute units
+        if (value != 0 && value != 1 && value != 2 && value != 4) return fail(HVD_ERR_ARG, "index_tile_split: 0 (from n and the device) or 1 | 2 | 4");
+        hvd::g_index_tile_split = value;
+        return HVD_OK;
+    }
     if (strcmp(key, "hash_staging_bytes") == 0) {  // tests only: frames staged per batch by the host-buffer hashing entries; 0 = 1 GiB
         if (value != 0 && value < 4096) return fail(HVD_ERR_ARG, "hash_staging_bytes: 0 (the default, 1 GiB) or >= 4096");
         g_hash_staging_bytes = value;
@@ -880,6 +885,20 @@ int hvd_pdq_scratch_bytes(int64_t n, int h, int w, int channels, size_t* out_byt
     *out_bytes = hvd::HashScratch(n, h, w, channels, false).total;
     return HVD_OK;
 }
+
+#ifndef HVD_NO_BENCH_SYMBOLS
+int hvd_index_tile_split(int64_t n, int cus) {  // host arithmetic only
+    if (n < 0 || n > 0xFFFFFFFFll || cus <= 0) return fail(HVD_ERR_ARG, "hvd_index_tile_split: n in 0 .. 2^32 - 1, cus > 0");
+    return (int)hvd::index_tile_split((uint32_t)n, (uint32_t)cus);
+}
+
+int hvd_debug_index_tiles(const void* d_db, int64_t n, const void* d_select, void* d_tcnt_raw, void* d_tcnt, void* d_parts, void* d_rec) {
+    if (int rc = need_ready()) return rc;
+    if (!d_db || !d_select || !d_tcnt || !d_parts || !d_rec || n < 1 || n > 0x7FFFFFFFll) return fail(HVD_ERR_ARG, "hvd_debug_index_tiles: NULL buffer or n outside 1 .. 2^31 - 1");
+    HIP_TRY(hvd::index_tiles_debug(d_db, (uint32_t)n, (const uint32_t*)d_select, (uint32_t*)d_tcnt_raw, (uint32_t*)d_tcnt, (uint32_t*)d_parts, d_rec, g.stream));
+    return HVD_OK;
+}
+#endif
 
 }  // extern "C" (the helpers below have C++ linkage: hvd_hash_host.h)
 

@@ -125,9 +125,16 @@ hipError_t launch_index_join(const AllPairsArgs& a, uint32_t* d_select, uint32_t
 hipError_t launch_index_order(const uint2* rec, uint32_t n, const uint32_t* ptotal, const uint32_t* pbase, uint32_t* cnt, uint32_t* off,
                               uint32_t* hw, uint32_t* rows, const uint32_t* d_select, hipStream_t s);
 // the high-byte pass with a tile's runs laid out in LDS (k_index_scatter.hip): launched by launch_index_decide where
-// k_index_partition was, same grid and arguments, unless "index_stage" is 0
-hipError_t launch_index_scatter(const uint4* db, uint32_t n, uint32_t ntiles, const uint32_t* tcnt, const uint32_t* pbase, uint2* rec,
-                                const uint32_t* d_select, hipStream_t s);
+// k_index_partition was, same arguments, unless "index_stage" is 0; its grid is (ntiles, split), split = 1, 2 or 4
+hipError_t launch_index_scatter(const uint4* db, uint32_t n, uint32_t ntiles, uint32_t split, const uint32_t* tcnt, const uint32_t* pbase,
+                                uint2* rec, const uint32_t* d_select, hipStream_t s);
+// block groups per tile of k_index_scatter for n hashes on a device of `cus` compute units (host arithmetic only)
+uint32_t index_tile_split(uint32_t n, uint32_t cus);
+extern int g_index_tile_split;  // tests: 1 | 2 | 4 forces that split; 0 = index_tile_split
+// tests (hvd_debug_index_tiles): the build up to the partition records into the caller's buffers; d_parts = ptotal[4096],
+// pbase[4096], pfirst[4096 + 4], chunk_p; d_tcnt_raw = the tile counts before the scan over the tiles
+hipError_t index_tiles_debug(const void* d_db, uint32_t n, const uint32_t* d_select, uint32_t* d_tcnt_raw, uint32_t* d_tcnt, uint32_t* d_parts,
+                             void* d_rec, hipStream_t s);
 // the join's grid for n hashes on the current device (or what "index_join_wgs" sets): the same for every n <= 2^20
 hipError_t index_join_workgroups(uint32_t n, uint32_t* wgs);
 void index_release();

@@ -13,7 +13,8 @@
 //   k_index_scatter     (k_index_scatter.hip) the tiles again: record {row, key | sibling key << 16} -> its partition -- the
 //                       record carries the whole 32-bit word that holds block b. Block by block the tile's 4096 records
 //                       are ranked by a returning LDS atomic, laid out by high byte in LDS and copied out in that order,
-//                       so that neighbouring lanes write neighbouring records of a run
+//                       so that neighbouring lanes write neighbouring records of a run; with few tiles two workgroups
+//                       share a tile's 16 blocks (index_tile_split)
 //   k_index_partition   the same pass with every record stored straight from its lane to its run (a wave's store touches
 //                       ~64 cache lines): launched instead of k_index_scatter under hvd_debug_set "index_stage" 0, the
 //                       independent path of tests/test_gpu_index_scatter.py
@@ -76,17 +77,19 @@ constexpr uint32_t kTileThreads = 1024u;            // 16 waves per workgroup, k
 constexpr uint32_t kMinChunk = 4096u;               // a chunk: at most max(kMinChunk, 2 x the mean partition) entries ...
 constexpr uint32_t kMaxChunks = kParts + 2048u;     // ... so a pass never has more chunks than this (index_chunk)
 
-// tcnt[part][tile] = the tile's hashes whose key of block (part >> 8) has the high byte (part & 255)
+// tcnt[part][tile] = the tile's hashes whose key of block (part >> 8) has the high byte (part & 255). Which tile a workgroup
+// takes: xcd_consecutive (hvd_index_dev.h) -- a row of tcnt is written 4 bytes per tile, and the tiles whose counts share a
+// cache line are counted on one XCD.
 __global__ __launch_bounds__(kTileThreads) void k_index_tile_count(const uint4* __restrict__ db, uint32_t n, uint32_t ntiles,
                                                                    uint32_t* __restrict__ tcnt, const uint32_t* __restrict__ select) {
     __shared__ uint32_t bins[kParts];
     if (select[hvd::kSelIdxGate] == 0u) return;
-    const uint32_t tid = threadIdx.x;
+    const uint32_t tid = threadIdx.x, tile = xcd_consecutive(blockIdx.x, ntiles);
     for (uint32_t k = tid; k < kParts; k += kTileThreads) bins[k] = 0u;
     __syncthreads();
 #pragma unroll
     for (uint32_t j = 0; j < kTile / kTileThreads; ++j) {
-        const uint32_t i = blockIdx.x * kTile + j * kTileThreads + tid;
+        const uint32_t i = tile * kTile + j * kTileThreads + tid;
         if (i < n) {
             uint32_t w[8];
             load_words(db, i, w);
@@ -95,7 +98,7 @@ __global__ __launch_bounds__(kTileThreads) void k_index_tile_count(const uint4* 
         }
     }
     __syncthreads();
-    for (uint32_t k = tid; k < kParts; k += kTileThreads) tcnt[(size_t)k * ntiles + blockIdx.x] = bins[k];
+    for (uint32_t k = tid; k < kParts; k += kTileThreads) tcnt[(size_t)k * ntiles + tile] = bins[k];
 }
 
 // One wave per partition: tcnt[part][.] becomes its exclusive scan over the tiles, ptotal[part] the partition's size.
@@ -727,6 +730,7 @@ int g_allpairs_index = -1;
 int g_allpairs_index_fail = 0;
 int g_index_join_wgs = 0;
 int g_index_stage = 1;
+int g_index_tile_split = 0;
 
 // per-context scratch: per-key counts [16][65536], offsets [16][65537], words [16][n] x 4 B, rows [16][n] x 4 B -- in this
 // order: the join's scalar batch reads up to 15 words past a bucket's end, which behind the last block's words are rows --;
@@ -814,11 +818,14 @@ IndexRule index_rule(const AllPairsArgs& a, uint32_t r) {
     // 42 us, 43 us of launches (as many as before) and 21 us of fall-back launches: 106 us, rounded up.
     // With a lane's y in groups of kYS slots and every x batch read once per group (profiles/r24_kernel_stats_after.csv,
     // profiles/r24_index_join_time.jsonl): join 0.601 ms for 2.075e9 candidates = 0.29 ps each; the crowded DB 5.83 .. 5.85
-    // ms per call, less the same ~0.6 ms, over 25.15e6 pairs = 0.21 ns per pair, rounded up)
+    // ms per call, less the same ~0.6 ms, over 25.15e6 pairs = 0.21 ns per pair, rounded up.
+    // With the tiles dealt to the XCDs in consecutive ranges and two workgroups per tile in the scatter
+    // (profiles/r25_kernel_stats_after.csv): the tile count 12.8, the scatter 37.2 and the order pass 49.7 us, 0.100 ms =
+    // 0.10 ns per hash; the kernels whose length does not depend on n and the launches are what they were: fixed_ns stays)
     q.fs_mfma_fetch = 36.0f;
     q.fs_mfma_other = 40.0f;
     q.ps_cand = 0.29f;
-    q.ps_hash = 120.0f;
+    q.ps_hash = 100.0f;
     q.ps_crit = 220.0f;
     q.fixed_ns = 110000.0f;
     return q;
@@ -851,18 +858,61 @@ hipError_t index_reserve(int ctx_id, uint32_t n) {
     return hipSuccess;
 }
 
+static hipError_t device_cus(int* cus) {
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return e;
+    if (hipError_t e = hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev)) return e;
+    return *cus > 0 ? hipSuccess : hipErrorInvalidDevice;
+}
+
+// Block groups per tile of k_index_scatter: its grid is (tiles, G). A tile is 4096 hashes whatever n is, so a DB of 1 M
+// hashes has 245 of them for 256 compute units that each hold two of these workgroups: with one workgroup per tile some
+// compute units stand idle and the others have nobody to cover a workgroup's barrier waits. G = 2 below kTileWgsPerCu
+// workgroups per compute unit, G = 1 from there on (256 compute units: 4.2 M hashes), where the tiles alone fill the chip
+// several times over and the launch is what it was before the split. Measured (with the tiles dealt to the
+// XCDs by xcd_consecutive): the scatter 43 -> 37 us at 1 M, 83 -> 78 at 2 M, 198 -> 180 at 4 M; G = 4 46 us at 1 M, which
+// is why the rule never gives it ("index_tile_split" 4 still launches it). k_index_tile_count is not split: on (tiles, 2)
+// it took 15.4 us for 13.3, on (tiles, 4) 22.4. From n and the compute units alone: every rank of a pass on like devices
+// takes the same grid, and G never rises with n.
+constexpr uint32_t kTileWgsPerCu = 4u;
+uint32_t index_tile_split(uint32_t n, uint32_t cus) {
+    const unsigned long long tiles = ((unsigned long long)n + kTile - 1u) / kTile, want = (unsigned long long)kTileWgsPerCu * cus;
+    return tiles >= want ? 1u : 2u;
+}
+
+// The front of the build, up to the partition records: tile counts, the two scans, the high-byte pass. tcnt_raw (tests
+// only, or nullptr) receives the tile counts as k_index_tile_count left them, before k_index_scan_rows turns them into bases.
+static hipError_t launch_index_tiles(const uint4* db, uint32_t n, uint32_t* tcnt, uint32_t* tcnt_raw, uint32_t* ptotal, uint32_t* pbase,
+                                     uint32_t* pfirst, uint32_t* chunk_p, uint2* rec, const uint32_t* d_select, hipStream_t s) {
+    const uint32_t tiles = index_tiles(n), csz = index_chunk(n);
+    uint32_t split = (uint32_t)g_index_tile_split;
+    if (split == 0u) {
+        int cus = 0;
+        if (hipError_t e = device_cus(&cus)) return e;
+        split = index_tile_split(n, (uint32_t)cus);
+    }
+    hipLaunchKernelGGL(k_index_tile_count, dim3(tiles), dim3(kTileThreads), 0, s, db, n, tiles, tcnt, d_select);
+    if (tcnt_raw != nullptr) {
+        if (hipError_t e = hipMemcpyAsync(tcnt_raw, tcnt, 4u * (size_t)kParts * tiles, hipMemcpyDeviceToDevice, s)) return e;
+    }
+    hipLaunchKernelGGL(k_index_scan_rows, dim3(kParts / 4u), dim3(256), 0, s, tcnt, tiles, ptotal, d_select);
+    hipLaunchKernelGGL(k_index_scan_parts, dim3(1), dim3(1024), 0, s, ptotal, csz, pbase, pfirst, chunk_p, d_select);
+    if (g_index_stage != 0) return launch_index_scatter(db, n, tiles, split, tcnt, pbase, rec, d_select, s);
+    hipLaunchKernelGGL(k_index_partition, dim3(tiles), dim3(kTileThreads), 0, s, db, n, tiles, tcnt, pbase, rec, d_select);
+    return hipGetLastError();
+}
+
+hipError_t index_tiles_debug(const void* d_db, uint32_t n, const uint32_t* d_select, uint32_t* d_tcnt_raw, uint32_t* d_tcnt, uint32_t* d_parts,
+                             void* d_rec, hipStream_t s) {
+    return launch_index_tiles((const uint4*)d_db, n, d_tcnt, d_tcnt_raw, d_parts, d_parts + kParts, d_parts + 2u * kParts,
+                              d_parts + 3u * kParts + 4u, (uint2*)d_rec, d_select, s);
+}
+
 hipError_t launch_index_decide(const AllPairsArgs& a, uint32_t* d_select, const IndexRule& q, hipStream_t s) {
     const IndexPtrs p = index_ptrs(a.ctx_id, a.n);
-    const uint32_t tiles = index_tiles(a.n), csz = index_chunk(a.n);
-    const uint4* db = (const uint4*)a.d_db;
-    hipLaunchKernelGGL(k_index_tile_count, dim3(tiles), dim3(kTileThreads), 0, s, db, a.n, tiles, p.tcnt, d_select);
-    hipLaunchKernelGGL(k_index_scan_rows, dim3(kParts / 4u), dim3(256), 0, s, p.tcnt, tiles, p.ptotal, d_select);
-    hipLaunchKernelGGL(k_index_scan_parts, dim3(1), dim3(1024), 0, s, p.ptotal, csz, p.pbase, p.pfirst, p.chunk_p, d_select);
-    if (g_index_stage != 0) {
-        if (hipError_t e = launch_index_scatter(db, a.n, tiles, p.tcnt, p.pbase, p.rec, d_select, s)) return e;
-    } else {
-        hipLaunchKernelGGL(k_index_partition, dim3(tiles), dim3(kTileThreads), 0, s, db, a.n, tiles, p.tcnt, p.pbase, p.rec, d_select);
-    }
+    const uint32_t csz = index_chunk(a.n);
+    if (hipError_t e = launch_index_tiles((const uint4*)a.d_db, a.n, p.tcnt, nullptr, p.ptotal, p.pbase, p.pfirst, p.chunk_p, p.rec, d_select, s))
+        return e;
     if (hipError_t e = launch_index_order(p.rec, a.n, p.ptotal, p.pbase, p.cnt, p.off, p.hw, p.rows, d_select, s)) return e;
     hipLaunchKernelGGL(k_index_count, dim3(kMaxChunks), dim3(256), 0, s, p.rec, a.n, csz, p.ptotal, p.pbase, p.pfirst, p.chunk_p,
                        p.ccount, d_select);
@@ -886,10 +936,8 @@ hipError_t index_join_workgroups(uint32_t n, uint32_t* wgs) {
         *wgs = (uint32_t)g_index_join_wgs;
         return hipSuccess;
     }
-    int dev = 0, cus = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return e;
-    if (hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) return e;
-    if (cus <= 0) return hipErrorInvalidDevice;
+    int cus = 0;
+    if (hipError_t e = device_cus(&cus)) return e;
     const unsigned long long scale = n > (1u << 20) ? ((unsigned long long)n + (1u << 20) - 1u) >> 20 : 1u;
     *wgs = (uint32_t)min((unsigned long long)cus * 64u * scale, (unsigned long long)(kRuns / 4u));
     return hipSuccess;

@@ -30,6 +30,17 @@ int hvd_debug_parallel_copy(void* dst, const void* src, size_t n, int threads);
  * workgroups (1 .. 2^20) instead of as many as the device holds at once (0, the default), so that one wave walks many work
  * items, or crosses a block, on a DB small enough to check against the oracle; hvd_debug_get of the same key returns the
  * workgroups the next launch takes. Results do not depend on it.
+ * Tests only, same build rule: hvd_debug_set("index_tile_split", G) launches the high-byte pass of the pigeonhole index's
+ * build (k_index_scatter) on a grid of (tiles, G), G = 1 | 2 | 4 block groups per tile, instead of the G that n and the
+ * device's compute units give (0, the default: 1 or 2); process-wide like "index_stage". Results do not depend on
+ * it. Two entry points of the same build rule belong to it, which tests/test_gpu_index_tile_split.py and
+ * tests/test_index_tile_split_rule.py bind by hand -- they have no prototype here and no row in the ctypes table:
+ *   hvd_index_tile_split(int64_t n, int cus) -> the G of n hashes on a device of cus compute units (host arithmetic only);
+ *   hvd_debug_index_tiles(const void* d_db, int64_t n, const void* d_select, void* d_tcnt_raw, void* d_tcnt, void* d_parts,
+ *   void* d_rec) -> HVD_OK: the build up to the partition records, as a pass launches it, into the caller's device buffers --
+ *   d_select: 16 words with word 12 (the gate) set; d_tcnt_raw, d_tcnt: 4096 x tiles words, the tile counts and their scan
+ *   over the tiles; d_parts: ptotal[4096], pbase[4096], pfirst[4096 + 4], chunk_p[6144]; d_rec: 16 n records of 8 bytes.
+ *   Does not synchronise.
  * Fault injection, tests only: hvd_debug_set("vmatch_fail_rank", r + 1) makes rank r of the next video-level search fail
  * before the key exchange, so that the agreement step (every rank leaves the collective with the same error instead of
  * hanging) can be tested; 0 = off. Like the two entry points above it is absent from -DHVD_NO_BENCH_SYMBOLS builds (the
