@@ -57,20 +57,20 @@ def oracle_crops(oracle, frames, rects, fma=False):
 
 # ---- the copies ----
 
-def width_copy(seed, num, den, nf=4):
-    """The re-upload that keeps the centre num / den of the width of content(512, 512, seed), cropped to fill 512 x 512: the
-    scene sampled S = round(512 den / num) columns wide, its centre 512 columns."""
-    S = int(round(512 * den / num))
-    o = (S - 512) // 2
-    return np.ascontiguousarray(content(512, S, seed, nf)[:, :, o:o + 512])
+def width_copy(seed, num, den, nf=4, h=512, w=512):
+    """The re-upload that keeps the centre num / den of the width of content(h, w, seed), cropped to fill h x w: the scene
+    sampled S = round(w den / num) columns wide, its centre w columns."""
+    S = int(round(w * den / num))
+    o = (S - w) // 2
+    return np.ascontiguousarray(content(h, S, seed, nf)[:, :, o:o + w])
 
 
-def pillared(seed, noise, nf=4):
-    """The scene of `seed` as a vertical video set into a 512 x 512 frame at the w81/256 rectangle, between pillars of coloured
-    noise (noise: uint8[nf,512,512,3] uniform in [60, 200]: bright, so the black-bar rule of DESIGN 4.7 finds the full frame)."""
-    _, left, _, ww = rung_rect(512, 512, "w", 81, 256)
+def pillared(seed, noise, nf=4, h=512, w=512):
+    """The scene of `seed` as a vertical video set into an h x w frame at the w81/256 rectangle, between pillars of coloured
+    noise (noise: uint8[nf,h,w,3] uniform in [60, 200]: bright, so the black-bar rule of DESIGN 4.7 finds the full frame)."""
+    _, left, _, ww = rung_rect(h, w, "w", 81, 256)
     fr = noise.copy()
-    fr[:, :, left:left + ww] = content(512, ww, seed, nf)
+    fr[:, :, left:left + ww] = content(h, ww, seed, nf)
     return fr
 
 
@@ -78,11 +78,15 @@ KINDS = ("original", "w3/4", "w9/16", "pillared")
 NF = 4
 
 
-@functools.lru_cache(maxsize=1)
-def library_crops():
-    """16 videos x 4 frames of 512 x 512 x 3: for each seed 0..3 the original, its w3/4 and w9/16 copies and the pillared
-    vertical one (pillars from default_rng(12), drawn in that order). -> (frames uint8[64,512,512,3], offsets int64[17],
-    kinds: video -> KINDS index, seeds: video -> seed)."""
+def library_crops(h=512, w=512):
+    """16 videos x 4 frames of h x w x 3: for each seed 0..3 the original, its w3/4 and w9/16 copies and the pillared
+    vertical one (pillars from default_rng(12), drawn in that order). -> (frames uint8[64,h,w,3], offsets int64[17],
+    kinds: video -> KINDS index, seeds: video -> seed). Built once per geometry."""
+    return _library_crops_cached(int(h), int(w))  # (one cache key whether the geometry was given or defaulted)
+
+
+@functools.lru_cache(maxsize=2)
+def _library_crops_cached(h, w):
     rng = np.random.default_rng(12)
     kinds, seeds, pillars = [], [], {}
     for s in range(4):
@@ -90,15 +94,15 @@ def library_crops():
             kinds.append(k)
             seeds.append(s)
             if kind == "pillared":
-                pillars[s] = rng.integers(60, 201, (NF, 512, 512, 3), dtype=np.uint8)
+                pillars[s] = rng.integers(60, 201, (NF, h, w, 3), dtype=np.uint8)
 
     def video(v):
         s, kind = seeds[v], KINDS[kinds[v]]
         if kind == "original":
-            return content(512, 512, s, NF)
+            return content(h, w, s, NF)
         if kind == "pillared":
-            return pillared(s, pillars[s], NF)
-        return width_copy(s, *RUNGS[kind][1:], NF)
+            return pillared(s, pillars[s], NF, h, w)
+        return width_copy(s, *RUNGS[kind][1:], NF, h, w)
 
     with ThreadPoolExecutor(max_workers=8) as pool:  # (numpy's cos releases the GIL: the 16 videos are independent)
         vids = list(pool.map(video, range(16)))
@@ -118,17 +122,18 @@ def expected_duplicates():
     return sorted(out)
 
 
-@functools.lru_cache(maxsize=1)
-def _oracle_variants_cached(oracle):
-    frames, offsets, _, _ = library_crops()
-    names, rects = ladder(512, 512, "aspect")
+@functools.lru_cache(maxsize=2)
+def _oracle_variants_cached(oracle, h, w):
+    frames, offsets, _, _ = library_crops(h, w)
+    names, rects = ladder(h, w, "aspect")
     hashes, quality = oracle_crops(oracle, frames, rects)
     return names, rects, hashes, quality
 
 
-def oracle_variants(oracle):
-    """(names, rects, hashes uint8[64,7,32], quality int32[64,7]) of library_crops() under the "aspect" ladder, computed once."""
-    return _oracle_variants_cached(oracle)
+def oracle_variants(oracle, h=512, w=512):
+    """(names, rects, hashes uint8[64,7,32], quality int32[64,7]) of library_crops(h, w) under the "aspect" ladder, computed
+    once per geometry."""
+    return _oracle_variants_cached(oracle, int(h), int(w))
 
 
 def variant_dicts(hashes, quality, offsets, names):

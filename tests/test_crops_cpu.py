@@ -297,6 +297,31 @@ def test_search_with_a_narrower_list_and_bad_dicts(hvd, oracle, oracle_result):
     assert hvd.search.find_cropped_duplicates([], matcher=H.OracleMatcher(oracle)) == []
 
 
+def test_search_finds_the_planted_crops_at_360x640(hvd, oracle):
+    """The same library sampled at a video geometry, whose frames take the generic passes on the device (a side above 512):
+    every frame is kept, a copy lies within the frame tolerance of its source's crop and beyond it from the source's whole
+    frame, and the search under the oracle matcher returns exactly the planted pairs, each at similarity 100."""
+    h, w = 360, 640
+    frames, offsets, _, _ = H.library_crops(h, w)
+    names, rects, hashes, quality = H.oracle_variants(oracle, h, w)
+    assert frames.shape == (64, h, w, 3) and np.array_equal(rects, H.ladder(h, w, "aspect")[1])
+    assert (quality[:, 0] >= 31).all(), int(quality[:, 0].min())
+    whole, rect = [], []
+    for a, b, crop, wide in H.expected_duplicates():
+        narrow = b if wide == a else a
+        k = 1 + names.index(crop)
+        fw, fn = slice(4 * wide, 4 * wide + 4), slice(4 * narrow, 4 * narrow + 4)
+        whole += H.hamming(hashes[fw, 0], hashes[fn, 0]).tolist()
+        rect += H.hamming(hashes[fw, k], hashes[fn, 0]).tolist()
+    print(f"360 x 640: whole-frame distances {min(whole)}..{max(whole)}, same-rectangle distances {min(rect)}..{max(rect)}, "
+          f"lowest full-frame quality {int(quality[:, 0].min())}")
+    assert min(whole) > H.FRAME_TOLERANCE and max(rect) <= H.FRAME_TOLERANCE, (min(whole), max(rect))
+    dicts = H.variant_dicts(hashes, quality[:, 0], offsets, names)
+    got = hvd.search.find_cropped_duplicates(dicts, matcher=H.OracleMatcher(oracle))
+    assert [(d.a, d.b, d.crop, d.wide) for d in got] == H.expected_duplicates()
+    assert [d.similarity for d in got] == [100.0] * 16
+
+
 # ---- 7. code shape (budgets: DESIGN 4.12) ----
 
 @pytest.fixture(scope="module")
