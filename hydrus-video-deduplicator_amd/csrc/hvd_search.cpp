@@ -823,20 +823,6 @@ int vmatch_to_host(const VmArgs& v, int64_t expect, std::vector<hvd_vmatch>& res
     return HVD_OK;
 }
 
-// the device-resident searches after their argument checks: nothing to compare zeroes the count, otherwise build + emit;
-// the stream is drained either way
-int vmatch_on_device(bool empty, const VmArgs& v, void* d_out, int64_t cap, void* d_count) {
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    if (empty) {
-        HIP_TRY(hipMemsetAsync(d_count, 0, 8, g.stream));
-    } else {
-        if (int rc = vmatch_build(v)) return rc;
-        if (int rc = vmatch_emit((hvd_vmatch*)d_out, cap, (unsigned long long*)d_count)) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return HVD_OK;
-}
-
 int check_offsets(const int64_t* offsets, int64_t V, int64_t* nf) {
     if (V < 0 || !offsets) return fail(HVD_ERR_ARG, "bad offsets");
     if (offsets[0] != 0) return fail(HVD_ERR_ARG, "offsets[0] must be 0");
@@ -866,166 +852,313 @@ int upload_library(const uint8_t* frames, const int64_t* offsets, int64_t V, int
     return HVD_OK;
 }
 
+/* ---- the video search's operands: one description from the entry to the fold ---- */
+
+// One side of a search as a host entry is handed it. n: the frame count check_offsets finds.
+struct HostSide {
+    const uint8_t* frames;
+    const int64_t* offsets;
+    int64_t V;
+    const int32_t* ids = nullptr;      // per video, both sides or neither: videos with equal ids are never compared
+    const int32_t* weights = nullptr;  // per frame, the weighted search only
+    int64_t* out_totals = nullptr;     // int64[V], the weighted search only, nullable
+    int64_t n = 0;
+};
+
+// One side as it lies in HBM: what a device entry is handed, and what upload_side leaves of a HostSide.
+struct DevSide {
+    const void* d_img = nullptr;
+    int64_t n = 0;
+    const void* d_video = nullptr;
+    const void* d_excl = nullptr;    // per frame, both sides or neither
+    const void* d_weight = nullptr;  // per frame, the weighted search only
+};
+
+// What a call asks for besides its sides. A search without a target side is the symmetric one: target side == query side.
+struct VmCall {
+    int max_dist;
+    int dist_limit;           // the entry's largest max_dist: 127, or 256 where the popcount route stands behind it
+    bool weighted = false;    // the weighted fold: weights on every side, max_weight caps one (0 = no cap)
+    int max_weight = 0;
+    int rank = 0, world = 1;
+    bool args_first = false;  // a host entry that judges every argument before the library's state (the weighted ones), not after
+
+    static VmCall plain(int max_dist, int dist_limit = 127, int rank = 0, int world = 1) {
+        return {max_dist, dist_limit, false, 0, rank, world, false};
+    }
+    static VmCall with_weights(int max_dist, int max_weight, bool args_first) { return {max_dist, 127, true, max_weight, 0, 1, args_first}; }
+};
+
+// where the records go: out[cap] and their count, all in host memory or all in HBM
+struct VmOut {
+    void* out;
+    int64_t cap;
+    void* count;
+};
+
+// The one place a VmArgs is put together: the symmetric form names its side twice, the rectangle sets `rect`.
+VmArgs vm_args(const VmCall& c, const DevSide& q, const DevSide* t) {
+    const DevSide& s = t ? *t : q;
+    VmArgs v{};
+    v.d_img_q = q.d_img, v.nq = (uint32_t)q.n, v.d_img_t = s.d_img, v.nt = (uint32_t)s.n;
+    v.rect = t != nullptr;
+    v.d_vid_q = (const int32_t*)q.d_video, v.d_vid_t = (const int32_t*)s.d_video;
+    v.d_excl_q = (const int32_t*)q.d_excl, v.d_excl_t = (const int32_t*)s.d_excl;
+    v.max_dist = c.max_dist, v.rank = c.rank, v.world = c.world;
+    if (c.weighted) v.d_weight_q = (const int32_t*)q.d_weight, v.d_weight_t = (const int32_t*)s.d_weight, v.max_weight = (uint32_t)c.max_weight;
+    return v;
+}
+
+// the scalars every entry shares; o: where the records go (the spread entries have none)
+int check_call(const VmCall& c, const VmOut* o) {
+    if (c.max_dist < 0 || c.max_dist > c.dist_limit) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,%d]", c.max_dist, c.dist_limit);
+    if (c.max_weight < 0) return fail(HVD_ERR_ARG, "max_weight=%d must not be negative (0 = no cap)", c.max_weight);
+    if (c.world < 1 || c.rank < 0 || c.rank >= c.world) return fail(HVD_ERR_ARG, "bad rank/world %d/%d", c.rank, c.world);
+    if (o && (o->cap < 0 || !o->count || (o->cap > 0 && !o->out))) return fail(HVD_ERR_ARG, "bad output buffer");
+    return HVD_OK;
+}
+
+int check_paired(const void* q, const void* t, const char* what) {
+    if ((q == nullptr) != (t == nullptr)) return fail(HVD_ERR_ARG, "pass both %s or neither", what);
+    return HVD_OK;
+}
+
+// The sides of a device entry: sizes, the exclusion maps, and -- unless there is nothing to compare -- what every side needs.
+int check_dev_sides(const VmCall& c, const DevSide& q, const DevSide* t, bool* empty) {
+    for (const DevSide* s : {&q, t})
+        if (s && (s->n < 0 || s->n >= (1ll << 32) - 1)) return fail(HVD_ERR_ARG, "set size %lld out of range", (long long)s->n);
+    if (t)
+        if (int rc = check_paired(q.d_excl, t->d_excl, "exclusion maps")) return rc;
+    *empty = t ? q.n == 0 || t->n == 0 : q.n < 2;
+    for (const DevSide* s : {&q, t})
+        if (s && !*empty && (!s->d_img || !s->d_video || (c.weighted && !s->d_weight)))
+            return fail(HVD_ERR_ARG, "NULL image / video map%s", c.weighted ? " / weights" : "");
+    return HVD_OK;
+}
+
+// The weights of a host library, before the library asks whether a device is there: one per frame, each at least 1, and per
+// video a capped total that the uint32 counters of a record can hold. out_totals: int64[V] or NULL.
+int check_weights(const int32_t* weights, const int64_t* offsets, int64_t V, int64_t nf, int max_weight, int64_t* out_totals) {
+    if (nf > 0 && !weights) return fail(HVD_ERR_ARG, "weights is NULL");
+    for (int64_t v = 0; v < V; ++v) {
+        uint64_t total = 0;
+        for (int64_t f = offsets[v]; f < offsets[v + 1]; ++f) {
+            if (weights[f] < 1) return fail(HVD_ERR_ARG, "weight %d of frame %lld (video %lld): weights are at least 1", weights[f], (long long)f, (long long)v);
+            total += (uint64_t)(max_weight > 0 && weights[f] > max_weight ? max_weight : weights[f]);
+        }
+        if (total > 0xFFFFFFFFull)
+            return fail(HVD_ERR_ARG, "video %lld: capped weight total %llu exceeds 2^32 - 1 (the counters are uint32)", (long long)v, (unsigned long long)total);
+        if (out_totals) out_totals[v] = (int64_t)total;
+    }
+    return HVD_OK;
+}
+
+// The sides of a host entry: the CSRs (-> n), the frames, then -- weighted -- the weights, whose totals are written last. An
+// args-first entry wants the frames of every side that has any; the others only when there is something to compare.
+int check_host_sides(const VmCall& c, HostSide& q, HostSide* t, bool* empty) {
+    for (HostSide* s : {&q, t})
+        if (s)
+            if (int rc = check_offsets(s->offsets, s->V, &s->n)) return rc;
+    *empty = t ? q.n == 0 || t->n == 0 : q.n < 2;
+    for (const HostSide* s : {&q, t})
+        if (s && (c.args_first ? s->n > 0 : !*empty) && !s->frames) return fail(HVD_ERR_ARG, "frames is NULL");
+    for (const HostSide* s : {&q, t})
+        if (s && c.weighted)
+            if (int rc = check_weights(s->weights, s->offsets, s->V, s->n, c.max_weight, s->out_totals)) return rc;
+    return HVD_OK;
+}
+
+// One value per frame from one per video: the form the exclusion maps take on the device.
+std::vector<int32_t> frame_ids(const HostSide& s) {
+    std::vector<int32_t> ids(s.ids ? (size_t)s.n : 0);
+    for (int64_t v = 0; s.ids && v < s.V; ++v)
+        for (int64_t f = s.offsets[v]; f < s.offsets[v + 1]; ++f) ids[(size_t)f] = s.ids[v];
+    return ids;
+}
+
+// One host side into its scratch slots (the query side's, or the target side's): the library, then the weights and the
+// per-frame ids where the call has them. The two small copies are not waited for: the caller drains the stream after its last side.
+int upload_side(const VmCall& c, const HostSide& s, const std::vector<int32_t>& ids, bool target, DevSide* d) {
+    void* d_img = nullptr;
+    int32_t *d_vid = nullptr, *d_w = nullptr, *d_ids = nullptr;
+    if (int rc = upload_library(s.frames, s.offsets, s.V, s.n, target ? Ctx::S_DB2 : Ctx::S_DB, target ? Ctx::S_IMG2 : Ctx::S_IMG,
+                                target ? Ctx::S_VIDT : Ctx::S_VIDQ, &d_img, &d_vid))
+        return rc;
+    if (c.weighted) {
+        if (int rc = scratch(target ? Ctx::S_WT : Ctx::S_WQ, 4 * (size_t)s.n, (void**)&d_w)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_w, s.weights, 4 * (size_t)s.n, hipMemcpyHostToDevice, g.stream));
+    }
+    if (s.ids) {
+        if (int rc = scratch(target ? Ctx::S_GRP2 : Ctx::S_GRP, 4 * (size_t)s.n, (void**)&d_ids)) return rc;
+        HIP_TRY(hipMemcpyAsync(d_ids, ids.data(), 4 * (size_t)s.n, hipMemcpyHostToDevice, g.stream));
+    }
+    *d = DevSide{d_img, s.n, d_vid, d_ids, d_w};
+    return HVD_OK;
+}
+
+// both sides of a host call (t == nullptr: one) on the current context; the stream is drained after the id copies
+int upload_sides(const VmCall& c, const HostSide& q, const HostSide* t, const std::vector<int32_t>& ids_q,
+                 const std::vector<int32_t>& ids_t, DevSide* dq, DevSide* dt) {
+    if (int rc = upload_side(c, q, ids_q, false, dq)) return rc;
+    if (t)
+        if (int rc = upload_side(c, *t, ids_t, true, dt)) return rc;
+    if (q.ids) HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
+}
+
+// The four host searches: judge, upload, search, sort the records out. t == nullptr: the symmetric search.
+int vmatch_from_host(const VmCall& c, HostSide q, HostSide* t, const VmOut& o) {
+    int64_t* out_count = (int64_t*)o.count;
+    if (!c.args_first)
+        if (int rc = need_ready()) return rc;
+    if (int rc = check_call(c, &o)) return rc;
+    if (t)
+        if (int rc = check_paired(q.ids, t->ids, "id arrays")) return rc;
+    if (!c.args_first) *out_count = 0;
+    bool empty = false;
+    if (int rc = check_host_sides(c, q, t, &empty)) return rc;
+    if (c.args_first) {
+        if (int rc = need_ready()) return rc;
+        *out_count = 0;
+    }
+    if (empty) return HVD_OK;
+    std::vector<hvd_vmatch> res;
+    if (c.max_dist >= 128) {
+        // popcount route (a tolerance the reference never uses; the plain symmetric entry alone admits it): frame-level hits
+        // reduced on the host
+        std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+        std::vector<int32_t> vid((size_t)q.n);
+        for (int64_t v = 0; v < q.V; ++v)
+            for (int64_t f = q.offsets[v]; f < q.offsets[v + 1]; ++f) vid[(size_t)f] = (int32_t)v;
+        std::vector<hvd_pair> recs;
+        int64_t fcap = std::max<int64_t>(1 << 16, q.n), fcount = 0;
+        for (;;) {
+            if (int rc = allpairs_host_raw(q.frames, q.n, vid.data(), c.max_dist, recs, fcap, &fcount)) return rc;
+            if (fcount <= fcap) break;
+            fcap = fcount;
+        }
+        aggregate_video_hits(recs, vid.data(), vid.data(), res);
+    } else {
+        const std::vector<int32_t> ids_q = frame_ids(q), ids_t = t ? frame_ids(*t) : std::vector<int32_t>();
+        // one rank's share (rank r of W contexts; W = 1: the whole search on the current context). A failed upload returns at
+        // once when this context is alone, and travels as pre_rc to the agreement step when it is one of a group.
+        auto one = [&](int r, int W, std::vector<hvd_vmatch>& mine) -> int {
+            std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+            DevSide dq, dt;
+            const int up = upload_sides(c, q, t, ids_q, ids_t, &dq, &dt);
+            if (W == 1 && up) return up;
+            VmCall mine_of = c;
+            mine_of.rank = r, mine_of.world = W;
+            VmArgs v = vm_args(mine_of, dq, t ? &dt : nullptr);
+            v.pre_rc = up;
+            return vmatch_to_host(v, q.V, mine);
+        };
+        // The group: library replicated on every device, tile (rb, cb) -> context (rb + cb) % W, key sets exchanged inside
+        // vmatch_build (RCCL all-gather between the devices, host memory where the group has no RCCL); every rank ends up with
+        // the whole result, rank 0's is returned. From 4096 frames, in both sets together. Only the plain searches fan out: the
+        // weighted ones stay on the calling context, whatever the group (a weighted search over the group is not built).
+        const int W = !c.weighted && g_nctx > 1 && q.n + (t ? t->n : 0) >= 4096 ? g_nctx : 1;
+        if (W > 1) {
+            if (int rc = run_keep_rank0(res, [&](int r, std::vector<hvd_vmatch>& mine) { return one(r, W, mine); })) return rc;
+        } else if (int rc = one(0, 1, res)) {
+            return rc;
+        }
+    }
+    return copy_out(res, (int64_t)res.size(), vmatch_less, (hvd_vmatch*)o.out, o.cap, out_count, c.weighted ? "weighted video match" : "video match");
+}
+
+// The four device searches: nothing to compare zeroes the count, otherwise build + emit; the stream is drained either way.
+int vmatch_dev_entry(const VmCall& c, const DevSide& q, const DevSide* t, const VmOut& o) {
+    if (int rc = need_ready()) return rc;
+    if (int rc = check_call(c, &o)) return rc;
+    bool empty = false;
+    if (int rc = check_dev_sides(c, q, t, &empty)) return rc;
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    if (empty) {
+        HIP_TRY(hipMemsetAsync(o.count, 0, 8, g.stream));
+    } else {
+        if (int rc = vmatch_build(vm_args(c, q, t))) return rc;
+        if (int rc = vmatch_emit((hvd_vmatch*)o.out, o.cap, (unsigned long long*)o.count)) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
+}
+
+// The two device spread entries: the key stage of the search on this context alone, then the count per frame. No pair map is
+// built, the last search's stays. The rectangle takes either output alone and zeroes by itself where there is nothing to
+// compare (unless it accumulates); it launches nothing else on an empty key set. The stream is drained.
+int spread_dev_entry(int max_dist, const DevSide& q, const DevSide* t, bool accumulate, void* d_spread_q, void* d_spread_t) {
+    if (int rc = need_ready()) return rc;
+    if (t ? !d_spread_q && !d_spread_t : q.n > 0 && !d_spread_q) return fail(HVD_ERR_ARG, "NULL spread output");
+    const VmCall c = VmCall::plain(max_dist);
+    if (int rc = check_call(c, nullptr)) return rc;
+    bool empty = false;
+    if (int rc = check_dev_sides(c, q, t, &empty)) return rc;
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    VmKeys k;
+    if (!empty)
+        if (int rc = vmatch_keys(vm_args(c, q, t), &k)) return rc;
+    if (t)
+        HIP_TRY(hvd::launch_keys_to_spread_cross(k.d_src, k.n_src, (unsigned long long)q.n, (unsigned long long)t->n, accumulate,
+                                                 (int32_t*)d_spread_q, (int32_t*)d_spread_t, g.stream));
+    else if (!empty)
+        HIP_TRY(hvd::launch_keys_to_spread(k.d_src, k.n_src, (unsigned long long)q.n, (int32_t*)d_spread_q, g.stream));
+    else if (q.n > 0)
+        HIP_TRY(hipMemsetAsync(d_spread_q, 0, 4 * (size_t)q.n, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
+}
+
+// the two host spread entries: every side with frames needs its output; nothing to compare answers zeroes without a device call
+int spread_from_host(int max_dist, HostSide q, HostSide* t, int32_t* out_q, int32_t* out_t) {
+    if (int rc = need_ready()) return rc;
+    const VmCall c = VmCall::plain(max_dist);
+    if (int rc = check_call(c, nullptr)) return rc;
+    bool empty = false;
+    if (int rc = check_host_sides(c, q, t, &empty)) return rc;
+    const int64_t nt = t ? t->n : 0;
+    if ((q.n > 0 && !out_q) || (nt > 0 && !out_t)) return fail(HVD_ERR_ARG, "out_spread is NULL");
+    if (empty) {
+        if (q.n > 0) memset(out_q, 0, 4 * (size_t)q.n);
+        if (nt > 0) memset(out_t, 0, 4 * (size_t)nt);
+        return HVD_OK;
+    }
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    DevSide dq, dt;
+    int32_t* d_spread = nullptr;
+    if (int rc = upload_sides(c, q, t, {}, {}, &dq, &dt)) return rc;
+    SCR(S_SPREAD, 4 * (size_t)(q.n + nt), d_spread);
+    if (int rc = spread_dev_entry(max_dist, dq, t ? &dt : nullptr, false, d_spread, d_spread + q.n)) return rc;
+    HIP_TRY(hipMemcpyAsync(out_q, d_spread, 4 * (size_t)q.n, hipMemcpyDeviceToHost, g.stream));
+    if (t) HIP_TRY(hipMemcpyAsync(out_t, d_spread + q.n, 4 * (size_t)nt, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 int hvd_vpdq_match_videos(const uint8_t* frames, const int64_t* offsets, int64_t V, int max_dist, hvd_vmatch* out,
                           int64_t cap, int64_t* out_count) {
-    if (int rc = need_ready()) return rc;
-    if (!out_count || cap < 0 || (cap > 0 && !out)) return fail(HVD_ERR_ARG, "bad arguments");
-    if (max_dist < 0 || max_dist > 256) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,256]", max_dist);
-    *out_count = 0;
-    int64_t nf = 0;
-    if (int rc = check_offsets(offsets, V, &nf)) return rc;
-    if (nf < 2) return HVD_OK;
-    if (!frames) return fail(HVD_ERR_ARG, "frames is NULL");
-    std::vector<hvd_vmatch> res;
-    if (g_nctx > 1 && max_dist < 128 && nf >= 4096) {
-        // the group: library replicated on every device, tile (rb, cb) -> context (rb + cb) % W, key sets exchanged inside
-        // vmatch_build (RCCL all-gather between the devices, host memory where the group has no RCCL); every rank ends up
-        // with the whole result, rank 0's is returned
-        const int W = g_nctx;
-        if (int rc = run_keep_rank0(res, [&](int r, std::vector<hvd_vmatch>& mine) -> int {
-                std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-                void* d_img = nullptr;
-                int32_t* d_vid = nullptr;
-                const int up = upload_library(frames, offsets, V, nf, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_img, &d_vid);
-                VmArgs v{d_img, (uint32_t)nf, d_img, (uint32_t)nf, false, d_vid, d_vid, nullptr, nullptr, max_dist, r, W};
-                v.pre_rc = up;
-                return vmatch_to_host(v, V, mine);
-            }))
-            return rc;
-    } else {
-        std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-        if (max_dist >= 128) {
-            // popcount route (a tolerance the reference never uses): frame-level hits reduced on the host
-            std::vector<int32_t> vid((size_t)nf);
-            for (int64_t v = 0; v < V; ++v)
-                for (int64_t f = offsets[v]; f < offsets[v + 1]; ++f) vid[(size_t)f] = (int32_t)v;
-            std::vector<hvd_pair> recs;
-            int64_t fcap = std::max<int64_t>(1 << 16, nf), fcount = 0;
-            for (;;) {
-                if (int rc = allpairs_host_raw(frames, nf, vid.data(), max_dist, recs, fcap, &fcount)) return rc;
-                if (fcount <= fcap) break;
-                fcap = fcount;
-            }
-            aggregate_video_hits(recs, vid.data(), vid.data(), res);
-        } else {
-            void* d_img = nullptr;
-            int32_t* d_vid = nullptr;
-            if (int rc = upload_library(frames, offsets, V, nf, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_img, &d_vid)) return rc;
-            VmArgs v{d_img, (uint32_t)nf, d_img, (uint32_t)nf, false, d_vid, d_vid, nullptr, nullptr, max_dist, 0, 1};
-            if (int rc = vmatch_to_host(v, V, res)) return rc;
-        }
-    }
-    return copy_out(res, (int64_t)res.size(), vmatch_less, out, cap, out_count, "video match");
+    return vmatch_from_host(VmCall::plain(max_dist, 256), {frames, offsets, V}, nullptr, {out, cap, out_count});
 }
 
 int hvd_vpdq_frame_spread(const uint8_t* frames, const int64_t* offsets, int64_t V, int max_dist, int32_t* out_spread) {
-    if (int rc = need_ready()) return rc;
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    int64_t nf = 0;
-    if (int rc = check_offsets(offsets, V, &nf)) return rc;
-    if (nf == 0) return HVD_OK;
-    if (!out_spread) return fail(HVD_ERR_ARG, "out_spread is NULL");
-    if (nf < 2) {
-        out_spread[0] = 0;
-        return HVD_OK;
-    }
-    if (!frames) return fail(HVD_ERR_ARG, "frames is NULL");
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    void *d_img = nullptr, *d_spread = nullptr;
-    int32_t* d_vid = nullptr;
-    if (int rc = upload_library(frames, offsets, V, nf, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_img, &d_vid)) return rc;
-    SCR(S_SPREAD, 4 * (size_t)nf, d_spread);
-    if (int rc = hvd_dev_vpdq_frame_spread(d_img, nf, d_vid, max_dist, d_spread)) return rc;
-    HIP_TRY(hipMemcpyAsync(out_spread, d_spread, 4 * (size_t)nf, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return HVD_OK;
+    return spread_from_host(max_dist, {frames, offsets, V}, nullptr, out_spread, nullptr);
 }
 
 int hvd_vpdq_match_videos_cross(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* ids_q,
                                 const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* ids_t,
                                 int max_dist, hvd_vmatch* out, int64_t cap, int64_t* out_count) {
-    if (int rc = need_ready()) return rc;
-    if (!out_count || cap < 0 || (cap > 0 && !out)) return fail(HVD_ERR_ARG, "bad output buffer");
-    if ((ids_q == nullptr) != (ids_t == nullptr)) return fail(HVD_ERR_ARG, "pass both id arrays or neither");
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    *out_count = 0;
-    int64_t nq = 0, nt = 0;
-    if (int rc = check_offsets(offsets_q, VQ, &nq)) return rc;
-    if (int rc = check_offsets(offsets_t, VT, &nt)) return rc;
-    if (nq == 0 || nt == 0) return HVD_OK;
-    if (!frames_q || !frames_t) return fail(HVD_ERR_ARG, "frames is NULL");
-    std::vector<int32_t> gq, gt;
-    if (ids_q) {  // frames of videos with equal ids are not compared (a query that is also in the target set)
-        gq.resize((size_t)nq);
-        gt.resize((size_t)nt);
-        for (int64_t v = 0; v < VQ; ++v)
-            for (int64_t f = offsets_q[v]; f < offsets_q[v + 1]; ++f) gq[(size_t)f] = ids_q[v];
-        for (int64_t v = 0; v < VT; ++v)
-            for (int64_t f = offsets_t[v]; f < offsets_t[v + 1]; ++f) gt[(size_t)f] = ids_t[v];
-    }
-    // one rank's share (rank r of W contexts; W = 1: the whole rectangle on the current context)
-    auto one = [&](int r, int W, std::vector<hvd_vmatch>& res) -> int {
-        std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-        void *d_iq = nullptr, *d_it = nullptr;
-        int32_t *d_vq = nullptr, *d_vt = nullptr, *d_gq = nullptr, *d_gt = nullptr;
-        auto upload = [&]() -> int {
-            if (int rc = upload_library(frames_q, offsets_q, VQ, nq, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_iq, &d_vq)) return rc;
-            if (int rc = upload_library(frames_t, offsets_t, VT, nt, Ctx::S_DB2, Ctx::S_IMG2, Ctx::S_VIDT, &d_it, &d_vt)) return rc;
-            if (ids_q) {
-                SCR(S_GRP, 4 * (size_t)nq, d_gq);
-                SCR(S_GRP2, 4 * (size_t)nt, d_gt);
-                HIP_TRY(hipMemcpyAsync(d_gq, gq.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, g.stream));
-                HIP_TRY(hipMemcpyAsync(d_gt, gt.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, g.stream));
-                HIP_TRY(hipStreamSynchronize(g.stream));
-            }
-            return HVD_OK;
-        };
-        const int up = upload();
-        if (W == 1 && up) return up;
-        VmArgs v{d_iq, (uint32_t)nq, d_it, (uint32_t)nt, true, d_vq, d_vt, d_gq, d_gt, max_dist, r, W};
-        v.pre_rc = up;
-        return vmatch_to_host(v, VQ, res);
-    };
-    std::vector<hvd_vmatch> res;
-    if (g_nctx > 1 && nq + nt >= 4096) {
-        const int W = g_nctx;
-        if (int rc = run_keep_rank0(res, [&](int r, std::vector<hvd_vmatch>& mine) { return one(r, W, mine); })) return rc;
-    } else if (int rc = one(0, 1, res)) {
-        return rc;
-    }
-    return copy_out(res, (int64_t)res.size(), vmatch_less, out, cap, out_count, "video match");
+    HostSide t{frames_t, offsets_t, VT, ids_t};
+    return vmatch_from_host(VmCall::plain(max_dist), {frames_q, offsets_q, VQ, ids_q}, &t, {out, cap, out_count});
 }
 
 int hvd_vpdq_frame_spread_cross(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const uint8_t* frames_t,
                                 const int64_t* offsets_t, int64_t VT, int max_dist, int32_t* out_spread_q, int32_t* out_spread_t) {
-    if (int rc = need_ready()) return rc;
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    int64_t nq = 0, nt = 0;
-    if (int rc = check_offsets(offsets_q, VQ, &nq)) return rc;
-    if (int rc = check_offsets(offsets_t, VT, &nt)) return rc;
-    if ((nq > 0 && !out_spread_q) || (nt > 0 && !out_spread_t)) return fail(HVD_ERR_ARG, "out_spread is NULL");
-    if (nq == 0 || nt == 0) {
-        if (nq > 0) memset(out_spread_q, 0, 4 * (size_t)nq);
-        if (nt > 0) memset(out_spread_t, 0, 4 * (size_t)nt);
-        return HVD_OK;
-    }
-    if (!frames_q || !frames_t) return fail(HVD_ERR_ARG, "frames is NULL");
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    void *d_iq = nullptr, *d_it = nullptr, *d_sq = nullptr, *d_st = nullptr;
-    int32_t *d_vq = nullptr, *d_vt = nullptr;
-    if (int rc = upload_library(frames_q, offsets_q, VQ, nq, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_iq, &d_vq)) return rc;
-    if (int rc = upload_library(frames_t, offsets_t, VT, nt, Ctx::S_DB2, Ctx::S_IMG2, Ctx::S_VIDT, &d_it, &d_vt)) return rc;
-    SCR(S_SPREAD, 4 * (size_t)(nq + nt), d_sq);
-    d_st = (int32_t*)d_sq + nq;
-    if (int rc = hvd_dev_vpdq_frame_spread_cross(d_iq, nq, d_vq, d_it, nt, d_vt, max_dist, 0, d_sq, d_st)) return rc;
-    HIP_TRY(hipMemcpyAsync(out_spread_q, d_sq, 4 * (size_t)nq, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipMemcpyAsync(out_spread_t, d_st, 4 * (size_t)nt, hipMemcpyDeviceToHost, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return HVD_OK;
+    HostSide t{frames_t, offsets_t, VT};
+    return spread_from_host(max_dist, {frames_q, offsets_q, VQ}, &t, out_spread_q, out_spread_t);
 }
 
 /* ---- device-resident forms: hashes / images / maps already in HBM (BASELINE config 5) ---- */
@@ -1092,15 +1225,7 @@ int hvd_dev_compact_kept_dihedral(const void* d_hashes8, const void* d_quality, 
 
 int hvd_dev_vpdq_match_videos(const void* d_img, int64_t n, const void* d_video, int max_dist, int rank, int world,
                               void* d_out, int64_t cap, void* d_count) {
-    if (int rc = need_ready()) return rc;
-    if (n < 0 || n >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "n=%lld out of range", (long long)n);
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    if (world < 1 || rank < 0 || rank >= world) return fail(HVD_ERR_ARG, "bad rank/world %d/%d", rank, world);
-    if (cap < 0 || !d_count || (cap > 0 && !d_out)) return fail(HVD_ERR_ARG, "bad output buffer");
-    if (n >= 2 && (!d_img || !d_video)) return fail(HVD_ERR_ARG, "d_img / d_video is NULL");
-    return vmatch_on_device(n < 2, {d_img, (uint32_t)n, d_img, (uint32_t)n, false, (const int32_t*)d_video, (const int32_t*)d_video,
-                                    nullptr, nullptr, max_dist, rank, world},
-                            d_out, cap, d_count);
+    return vmatch_dev_entry(VmCall::plain(max_dist, 127, rank, world), {d_img, n, d_video}, nullptr, {d_out, cap, d_count});
 }
 
 int hvd_dev_vpdq_emit_again(void* d_out, int64_t cap, void* d_count) {
@@ -1114,64 +1239,20 @@ int hvd_dev_vpdq_emit_again(void* d_out, int64_t cap, void* d_count) {
 }
 
 int hvd_dev_vpdq_frame_spread(const void* d_img, int64_t n, const void* d_video, int max_dist, void* d_out_spread) {
-    if (int rc = need_ready()) return rc;
-    if (n < 0 || n >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "n=%lld out of range", (long long)n);
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    if (n > 0 && !d_out_spread) return fail(HVD_ERR_ARG, "d_out_spread is NULL");
-    if (n >= 2 && (!d_img || !d_video)) return fail(HVD_ERR_ARG, "d_img / d_video is NULL");
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    if (n < 2) {
-        if (n > 0) HIP_TRY(hipMemsetAsync(d_out_spread, 0, 4 * (size_t)n, g.stream));
-    } else {
-        // the key stage of the symmetric search on this context alone; no pair map is built, the last search's stays
-        VmKeys k;
-        if (int rc = vmatch_keys({d_img, (uint32_t)n, d_img, (uint32_t)n, false, (const int32_t*)d_video, (const int32_t*)d_video,
-                                  nullptr, nullptr, max_dist, 0, 1},
-                                 &k))
-            return rc;
-        HIP_TRY(hvd::launch_keys_to_spread(k.d_src, k.n_src, (unsigned long long)n, (int32_t*)d_out_spread, g.stream));
-    }
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return HVD_OK;
+    return spread_dev_entry(max_dist, {d_img, n, d_video}, nullptr, false, d_out_spread, nullptr);
 }
 
 int hvd_dev_vpdq_frame_spread_cross(const void* d_img_q, int64_t nq, const void* d_video_q, const void* d_img_t, int64_t nt,
                                     const void* d_video_t, int max_dist, int accumulate, void* d_spread_q, void* d_spread_t) {
-    if (int rc = need_ready()) return rc;
-    if (!d_spread_q && !d_spread_t) return fail(HVD_ERR_ARG, "d_spread_q and d_spread_t are both NULL");
-    if (nq < 0 || nt < 0 || nq >= (1ll << 32) - 1 || nt >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "set size out of range");
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    const bool empty = nq == 0 || nt == 0;
-    if (!empty && (!d_img_q || !d_img_t || !d_video_q || !d_video_t)) return fail(HVD_ERR_ARG, "NULL image / video map");
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    // the key stage of the rectangular search on this context alone; no pair map is built, the last search's stays
-    VmKeys k;
-    if (!empty)
-        if (int rc = vmatch_keys({d_img_q, (uint32_t)nq, d_img_t, (uint32_t)nt, true, (const int32_t*)d_video_q,
-                                  (const int32_t*)d_video_t, nullptr, nullptr, max_dist, 0, 1},
-                                 &k))
-            return rc;
-    // (nothing to compare: k is empty, the launcher zeroes the outputs unless it accumulates and launches nothing else)
-    HIP_TRY(hvd::launch_keys_to_spread_cross(k.d_src, k.n_src, (unsigned long long)nq, (unsigned long long)nt, accumulate != 0,
-                                             (int32_t*)d_spread_q, (int32_t*)d_spread_t, g.stream));
-    HIP_TRY(hipStreamSynchronize(g.stream));
-    return HVD_OK;
+    const DevSide t{d_img_t, nt, d_video_t};
+    return spread_dev_entry(max_dist, {d_img_q, nq, d_video_q}, &t, accumulate != 0, d_spread_q, d_spread_t);
 }
 
 int hvd_dev_vpdq_match_videos_cross(const void* d_img_q, int64_t nq, const void* d_video_q, const void* d_excl_q,
                                     const void* d_img_t, int64_t nt, const void* d_video_t, const void* d_excl_t,
                                     int max_dist, int rank, int world, void* d_out, int64_t cap, void* d_count) {
-    if (int rc = need_ready()) return rc;
-    if (nq < 0 || nt < 0 || nq >= (1ll << 32) - 1 || nt >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "set size out of range");
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    if (world < 1 || rank < 0 || rank >= world) return fail(HVD_ERR_ARG, "bad rank/world %d/%d", rank, world);
-    if (cap < 0 || !d_count || (cap > 0 && !d_out)) return fail(HVD_ERR_ARG, "bad output buffer");
-    if ((d_excl_q == nullptr) != (d_excl_t == nullptr)) return fail(HVD_ERR_ARG, "pass both exclusion maps or neither");
-    const bool empty = nq == 0 || nt == 0;
-    if (!empty && (!d_img_q || !d_img_t || !d_video_q || !d_video_t)) return fail(HVD_ERR_ARG, "NULL image / video map");
-    return vmatch_on_device(empty, {d_img_q, (uint32_t)nq, d_img_t, (uint32_t)nt, true, (const int32_t*)d_video_q, (const int32_t*)d_video_t,
-                                    (const int32_t*)d_excl_q, (const int32_t*)d_excl_t, max_dist, rank, world},
-                            d_out, cap, d_count);
+    const DevSide t{d_img_t, nt, d_video_t, d_excl_t};
+    return vmatch_dev_entry(VmCall::plain(max_dist, 127, rank, world), {d_img_q, nq, d_video_q, d_excl_q}, &t, {d_out, cap, d_count});
 }
 
 /* ---- duration-weighted video search (k_vmatch_weighted.hip) ---- */
@@ -1189,87 +1270,24 @@ int hvd_dev_video_weights(const void* d_weight, const void* d_offsets, int64_t V
 
 int hvd_dev_vpdq_match_videos_weighted(const void* d_img, int64_t n, const void* d_video, const void* d_weight, int max_weight,
                                        int max_dist, void* d_out, int64_t cap, void* d_count) {
-    if (int rc = need_ready()) return rc;
-    if (n < 0 || n >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "n=%lld out of range", (long long)n);
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    if (max_weight < 0) return fail(HVD_ERR_ARG, "max_weight=%d must not be negative (0 = no cap)", max_weight);
-    if (cap < 0 || !d_count || (cap > 0 && !d_out)) return fail(HVD_ERR_ARG, "bad output buffer");
-    if (n >= 2 && (!d_img || !d_video || !d_weight)) return fail(HVD_ERR_ARG, "d_img / d_video / d_weight is NULL");
-    VmArgs v{d_img, (uint32_t)n, d_img, (uint32_t)n, false, (const int32_t*)d_video, (const int32_t*)d_video, nullptr, nullptr,
-             max_dist, 0, 1};
-    v.d_weight_q = v.d_weight_t = (const int32_t*)d_weight;
-    v.max_weight = (uint32_t)max_weight;
-    return vmatch_on_device(n < 2, v, d_out, cap, d_count);
+    return vmatch_dev_entry(VmCall::with_weights(max_dist, max_weight, false), {d_img, n, d_video, nullptr, d_weight}, nullptr,
+                            {d_out, cap, d_count});
 }
 
 int hvd_dev_vpdq_match_videos_cross_weighted(const void* d_img_q, int64_t nq, const void* d_video_q, const void* d_excl_q,
                                              const void* d_weight_q, const void* d_img_t, int64_t nt, const void* d_video_t,
                                              const void* d_excl_t, const void* d_weight_t, int max_weight, int max_dist,
                                              void* d_out, int64_t cap, void* d_count) {
-    if (int rc = need_ready()) return rc;
-    if (nq < 0 || nt < 0 || nq >= (1ll << 32) - 1 || nt >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "set size out of range");
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    if (max_weight < 0) return fail(HVD_ERR_ARG, "max_weight=%d must not be negative (0 = no cap)", max_weight);
-    if (cap < 0 || !d_count || (cap > 0 && !d_out)) return fail(HVD_ERR_ARG, "bad output buffer");
-    if ((d_excl_q == nullptr) != (d_excl_t == nullptr)) return fail(HVD_ERR_ARG, "pass both exclusion maps or neither");
-    const bool empty = nq == 0 || nt == 0;
-    if (!empty && (!d_img_q || !d_img_t || !d_video_q || !d_video_t || !d_weight_q || !d_weight_t))
-        return fail(HVD_ERR_ARG, "NULL image / video map / weights");
-    VmArgs v{d_img_q, (uint32_t)nq, d_img_t, (uint32_t)nt, true, (const int32_t*)d_video_q, (const int32_t*)d_video_t,
-             (const int32_t*)d_excl_q, (const int32_t*)d_excl_t, max_dist, 0, 1};
-    v.d_weight_q = (const int32_t*)d_weight_q;
-    v.d_weight_t = (const int32_t*)d_weight_t;
-    v.max_weight = (uint32_t)max_weight;
-    return vmatch_on_device(empty, v, d_out, cap, d_count);
+    const DevSide t{d_img_t, nt, d_video_t, d_excl_t, d_weight_t};
+    return vmatch_dev_entry(VmCall::with_weights(max_dist, max_weight, false), {d_img_q, nq, d_video_q, d_excl_q, d_weight_q}, &t,
+                            {d_out, cap, d_count});
 }
 
-// The weights of a host library, before the library asks whether a device is there: one per frame, each at least 1, and per
-// video a capped total that the uint32 counters of a record can hold. out_totals: int64[V] or NULL.
-static int check_weights(const int32_t* weights, const int64_t* offsets, int64_t V, int64_t nf, int max_weight, int64_t* out_totals) {
-    if (nf > 0 && !weights) return fail(HVD_ERR_ARG, "weights is NULL");
-    for (int64_t v = 0; v < V; ++v) {
-        uint64_t total = 0;
-        for (int64_t f = offsets[v]; f < offsets[v + 1]; ++f) {
-            if (weights[f] < 1) return fail(HVD_ERR_ARG, "weight %d of frame %lld (video %lld): weights are at least 1", weights[f], (long long)f, (long long)v);
-            total += (uint64_t)(max_weight > 0 && weights[f] > max_weight ? max_weight : weights[f]);
-        }
-        if (total > 0xFFFFFFFFull)
-            return fail(HVD_ERR_ARG, "video %lld: capped weight total %llu exceeds 2^32 - 1 (the counters are uint32)", (long long)v, (unsigned long long)total);
-        if (out_totals) out_totals[v] = (int64_t)total;
-    }
-    return HVD_OK;
-}
-
-static int upload_weights(Ctx::Scr slot, const int32_t* weights, int64_t nf, int32_t** d_w) {
-    if (int rc = scratch(slot, 4 * (size_t)nf, (void**)d_w)) return rc;
-    HIP_TRY(hipMemcpyAsync(*d_w, weights, 4 * (size_t)nf, hipMemcpyHostToDevice, g.stream));
-    return HVD_OK;
-}
-
+// (the two host forms refuse every bad argument before the question whether a device is there: VmCall::args_first)
 int hvd_vpdq_match_videos_weighted(const uint8_t* frames, const int64_t* offsets, int64_t V, const int32_t* weights, int max_weight,
                                    int max_dist, hvd_vmatch* out, int64_t cap, int64_t* out_count, int64_t* out_totals) {
-    // every refusal comes before the question whether a device is there
-    if (!out_count || cap < 0 || (cap > 0 && !out)) return fail(HVD_ERR_ARG, "bad arguments");
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    if (max_weight < 0) return fail(HVD_ERR_ARG, "max_weight=%d must not be negative (0 = no cap)", max_weight);
-    int64_t nf = 0;
-    if (int rc = check_offsets(offsets, V, &nf)) return rc;
-    if (nf > 0 && !frames) return fail(HVD_ERR_ARG, "frames is NULL");
-    if (int rc = check_weights(weights, offsets, V, nf, max_weight, out_totals)) return rc;
-    if (int rc = need_ready()) return rc;
-    *out_count = 0;
-    if (nf < 2) return HVD_OK;
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    void* d_img = nullptr;
-    int32_t *d_vid = nullptr, *d_w = nullptr;
-    if (int rc = upload_library(frames, offsets, V, nf, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_img, &d_vid)) return rc;
-    if (int rc = upload_weights(Ctx::S_WQ, weights, nf, &d_w)) return rc;
-    VmArgs v{d_img, (uint32_t)nf, d_img, (uint32_t)nf, false, d_vid, d_vid, nullptr, nullptr, max_dist, 0, 1};
-    v.d_weight_q = v.d_weight_t = d_w;
-    v.max_weight = (uint32_t)max_weight;
-    std::vector<hvd_vmatch> res;
-    if (int rc = vmatch_to_host(v, V, res)) return rc;
-    return copy_out(res, (int64_t)res.size(), vmatch_less, out, cap, out_count, "weighted video match");
+    return vmatch_from_host(VmCall::with_weights(max_dist, max_weight, true), {frames, offsets, V, nullptr, weights, out_totals}, nullptr,
+                            {out, cap, out_count});
 }
 
 int hvd_vpdq_match_videos_cross_weighted(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* ids_q,
@@ -1277,47 +1295,9 @@ int hvd_vpdq_match_videos_cross_weighted(const uint8_t* frames_q, const int64_t*
                                          const int32_t* ids_t, const int32_t* weights_t, int max_weight, int max_dist,
                                          hvd_vmatch* out, int64_t cap, int64_t* out_count, int64_t* out_totals_q,
                                          int64_t* out_totals_t) {
-    if (!out_count || cap < 0 || (cap > 0 && !out)) return fail(HVD_ERR_ARG, "bad output buffer");
-    if ((ids_q == nullptr) != (ids_t == nullptr)) return fail(HVD_ERR_ARG, "pass both id arrays or neither");
-    if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
-    if (max_weight < 0) return fail(HVD_ERR_ARG, "max_weight=%d must not be negative (0 = no cap)", max_weight);
-    int64_t nq = 0, nt = 0;
-    if (int rc = check_offsets(offsets_q, VQ, &nq)) return rc;
-    if (int rc = check_offsets(offsets_t, VT, &nt)) return rc;
-    if ((nq > 0 && !frames_q) || (nt > 0 && !frames_t)) return fail(HVD_ERR_ARG, "frames is NULL");
-    if (int rc = check_weights(weights_q, offsets_q, VQ, nq, max_weight, out_totals_q)) return rc;
-    if (int rc = check_weights(weights_t, offsets_t, VT, nt, max_weight, out_totals_t)) return rc;
-    if (int rc = need_ready()) return rc;
-    *out_count = 0;
-    if (nq == 0 || nt == 0) return HVD_OK;
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    void *d_iq = nullptr, *d_it = nullptr;
-    int32_t *d_vq = nullptr, *d_vt = nullptr, *d_gq = nullptr, *d_gt = nullptr, *d_wq = nullptr, *d_wt = nullptr;
-    std::vector<int32_t> gq, gt;
-    if (int rc = upload_library(frames_q, offsets_q, VQ, nq, Ctx::S_DB, Ctx::S_IMG, Ctx::S_VIDQ, &d_iq, &d_vq)) return rc;
-    if (int rc = upload_library(frames_t, offsets_t, VT, nt, Ctx::S_DB2, Ctx::S_IMG2, Ctx::S_VIDT, &d_it, &d_vt)) return rc;
-    if (int rc = upload_weights(Ctx::S_WQ, weights_q, nq, &d_wq)) return rc;
-    if (int rc = upload_weights(Ctx::S_WT, weights_t, nt, &d_wt)) return rc;
-    if (ids_q) {  // frames of videos with equal ids are not compared, as in hvd_vpdq_match_videos_cross
-        gq.resize((size_t)nq);
-        gt.resize((size_t)nt);
-        for (int64_t v = 0; v < VQ; ++v)
-            for (int64_t f = offsets_q[v]; f < offsets_q[v + 1]; ++f) gq[(size_t)f] = ids_q[v];
-        for (int64_t v = 0; v < VT; ++v)
-            for (int64_t f = offsets_t[v]; f < offsets_t[v + 1]; ++f) gt[(size_t)f] = ids_t[v];
-        SCR(S_GRP, 4 * (size_t)nq, d_gq);
-        SCR(S_GRP2, 4 * (size_t)nt, d_gt);
-        HIP_TRY(hipMemcpyAsync(d_gq, gq.data(), 4 * (size_t)nq, hipMemcpyHostToDevice, g.stream));
-        HIP_TRY(hipMemcpyAsync(d_gt, gt.data(), 4 * (size_t)nt, hipMemcpyHostToDevice, g.stream));
-        HIP_TRY(hipStreamSynchronize(g.stream));
-    }
-    VmArgs v{d_iq, (uint32_t)nq, d_it, (uint32_t)nt, true, d_vq, d_vt, d_gq, d_gt, max_dist, 0, 1};
-    v.d_weight_q = d_wq;
-    v.d_weight_t = d_wt;
-    v.max_weight = (uint32_t)max_weight;
-    std::vector<hvd_vmatch> res;
-    if (int rc = vmatch_to_host(v, VQ, res)) return rc;
-    return copy_out(res, (int64_t)res.size(), vmatch_less, out, cap, out_count, "weighted video match");
+    HostSide t{frames_t, offsets_t, VT, ids_t, weights_t, out_totals_t};
+    return vmatch_from_host(VmCall::with_weights(max_dist, max_weight, true), {frames_q, offsets_q, VQ, ids_q, weights_q, out_totals_q}, &t,
+                            {out, cap, out_count});
 }
 
 /* ---- time alignment of listed video pairs (k_valign*.hip) ---- */

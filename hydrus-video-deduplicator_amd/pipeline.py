@@ -370,16 +370,14 @@ class DeviceLibrary:
         2^32 - 1, which the uint32 counters of that video's records cannot hold."""
         if self.d_weights is None:
             raise ValueError("no weights attached: call attach_weights first")
-        if int(max_weight) != max_weight or max_weight < 0:
-            raise ValueError("max_weight is an integer, at least 0 (0 = no cap)")
+        max_weight = search.check_max_weight(max_weight)
         lib = _lib.ensure()
         V = self.n_videos
         if V == 0:
             return np.zeros(0, dtype=np.int64)
         with _DeviceScope() as scope:
             d_totals = scope.temp(DeviceBuffer(8 * V))
-            _lib.check(lib.hvd_dev_video_weights(self.d_weights.ptr, self.d_offsets.ptr, V, self.n_frames, int(max_weight),
-                                                 d_totals.ptr))
+            _lib.check(lib.hvd_dev_video_weights(self.d_weights.ptr, self.d_offsets.ptr, V, self.n_frames, max_weight, d_totals.ptr))
             totals = d_totals.to_array(np.int64, V)
         over = np.flatnonzero(totals > search.WEIGHT_TOTAL_LIMIT)
         if over.size:
@@ -392,40 +390,50 @@ class DeviceLibrary:
         hvd_dev_vpdq_match_videos_weighted with the attached weights -- a matched frame adds
         min(weight, max_weight) (max_weight 0: its weight) to q_hits / t_hits instead of 1, `weight_totals(max_weight)` are
         the denominators; on this context alone (world must be 1)."""
-        lib = _lib.ensure()
-        max_dist = _default_max_dist(max_dist)
         if weighted:
             if world != 1 or rank != 0:
                 raise ValueError("the weighted search is not sharded over a device group: world must be 1")
             if self.d_weights is None:
                 raise ValueError("no weights attached: call attach_weights first")
-            if int(max_weight) != max_weight or max_weight < 0:
-                raise ValueError("max_weight is an integer, at least 0 (0 = no cap)")
+            max_weight = search.check_max_weight(max_weight)
         elif max_weight:
             raise ValueError("max_weight caps weights: pass weighted=True as well")
-        if max_dist < 0 or self.n_frames < 2:
+        return self._match(None, None, weighted, max_weight, max_dist, rank, world, cap)
+
+    def _match(self, queries: "DeviceLibrary | None", excl, weighted: bool, max_weight: int, max_dist, rank: int, world: int,
+               cap) -> np.ndarray:
+        """The device video search behind match_videos, match_queries and match_library. queries: the query side,
+        this library being the target side -- None: the symmetric search of this library; excl: the exclusion maps (query
+        side's, this side's) as DeviceBuffers, or None; weighted: the attached weights (symmetric only). Nothing to compare:
+        no call. Default cap: max(4096, videos of the query side). The images are built inside the launch, after the record
+        buffers, the query side's first."""
+        lib = _lib.ensure()
+        max_dist = _default_max_dist(max_dist)
+        q = self if queries is None else queries
+        if max_dist < 0 or (self.n_frames < 2 if queries is None else queries.n_frames == 0 or self.n_frames == 0):
             return np.zeros(0, dtype=VMATCH_DTYPE)
-        cap = max(4096, self.n_videos) if cap is None else int(cap)
-        if weighted:
-            return _search_records(lambda d_out, cap_, d_cnt: lib.hvd_dev_vpdq_match_videos_weighted(
-                self.image().ptr, self.n_frames, self.d_video.ptr, self.d_weights.ptr, int(max_weight), max_dist, d_out, cap_,
-                d_cnt), cap)
-        return _search_records(lambda d_out, cap_, d_cnt: lib.hvd_dev_vpdq_match_videos(
-            self.image().ptr, self.n_frames, self.d_video.ptr, max_dist, rank, world, d_out, cap_, d_cnt), cap)
+        excl_q, excl_t = (None, None) if excl is None else (excl[0].ptr, excl[1].ptr)
+
+        def launch(d_out, cap_, d_cnt):
+            if queries is not None:
+                return lib.hvd_dev_vpdq_match_videos_cross(q.image().ptr, q.n_frames, q.d_video.ptr, excl_q, self.image().ptr,
+                                                           self.n_frames, self.d_video.ptr, excl_t, max_dist, rank, world, d_out,
+                                                           cap_, d_cnt)
+            if weighted:
+                return lib.hvd_dev_vpdq_match_videos_weighted(q.image().ptr, q.n_frames, q.d_video.ptr, self.d_weights.ptr,
+                                                              max_weight, max_dist, d_out, cap_, d_cnt)
+            return lib.hvd_dev_vpdq_match_videos(q.image().ptr, q.n_frames, q.d_video.ptr, max_dist, rank, world, d_out, cap_, d_cnt)
+
+        return _search_records(launch, max(4096, q.n_videos) if cap is None else int(cap))
 
     def match_queries(self, queries: "DeviceQueries", max_dist: int | None = None, rank: int = 0, world: int = 1,
                       cap: int | None = None) -> np.ndarray:
         """hvd_dev_vpdq_match_videos_cross of a query set (from_raw_dihedral) against this library, a video never against
         its own variants (the library's frame -> video map is the target's exclusion map). VMATCH_DTYPE records (a = query
         video v*K + k, b = video) sorted by (a, b); the same record buffer, cap and emit-again retry as match_videos."""
-        lib = _lib.ensure()
-        max_dist = _default_max_dist(max_dist)
-        if max_dist < 0 or queries is None or queries.n_frames == 0 or self.n_frames == 0:
+        if queries is None:
             return np.zeros(0, dtype=VMATCH_DTYPE)
-        cap = max(4096, queries.n_videos) if cap is None else int(cap)
-        return _search_records(lambda d_out, cap_, d_cnt: lib.hvd_dev_vpdq_match_videos_cross(
-            queries.image().ptr, queries.n_frames, queries.d_video.ptr, queries.d_excl.ptr, self.image().ptr, self.n_frames,
-            self.d_video.ptr, self.d_video.ptr, max_dist, rank, world, d_out, cap_, d_cnt), cap)
+        return self._match(queries, (queries.d_excl, self.d_video), False, 0, max_dist, rank, world, cap)
 
     def positions(self) -> np.ndarray | None:
         return None if self.d_positions is None else self.d_positions.to_array(np.int32, self.n_frames)
@@ -498,15 +506,27 @@ class DeviceLibrary:
         """hvd_dev_vpdq_frame_spread: int32 per kept frame, the number of OTHER videos of this library the frame occurs in
         (DESIGN 4.13), as a DeviceBuffer that is the caller's to free. The compare and the key set of `match_videos`
         without its fold; the records of the last search stay valid for hvd_dev_vpdq_emit_again."""
-        lib = _lib.ensure()
-        max_dist = _default_max_dist(max_dist)
         with _DeviceScope() as scope:
             d_spread = scope.keep(DeviceBuffer(4 * max(self.n_frames, 1)))
-            if max_dist < 0 or self.n_frames < 2:
+            if not self._spread_into(None, max_dist, False, d_spread.ptr, None):
                 d_spread.zero()
-            else:
-                _lib.check(lib.hvd_dev_vpdq_frame_spread(self.image().ptr, self.n_frames, self.d_video.ptr, max_dist, d_spread.ptr))
         return d_spread
+
+    def _spread_into(self, other: "DeviceLibrary | None", max_dist, accumulate: bool, sq_ptr, st_ptr) -> bool:
+        """The device spread behind spread, spread_cross and ingest, into buffers of the caller's. other: the
+        query side, this library being the target side -- None: the spread inside this library, into sq_ptr. accumulate
+        (two sides): add to what the buffers hold. -> False: nothing to compare, nothing was called."""
+        lib = _lib.ensure()
+        max_dist = _default_max_dist(max_dist)
+        if max_dist < 0 or (self.n_frames < 2 if other is None else other.n_frames == 0 or self.n_frames == 0):
+            return False
+        if other is None:
+            _lib.check(lib.hvd_dev_vpdq_frame_spread(self.image().ptr, self.n_frames, self.d_video.ptr, max_dist, sq_ptr))
+        else:
+            _lib.check(lib.hvd_dev_vpdq_frame_spread_cross(other.image().ptr, other.n_frames, other.d_video.ptr, self.image().ptr,
+                                                           self.n_frames, self.d_video.ptr, max_dist, int(accumulate), sq_ptr,
+                                                           st_ptr))
+        return True
 
     def without_common_frames(self, max_videos: int, max_share: int = 50,
                               max_dist: int | None = None) -> tuple["DeviceLibrary", np.ndarray]:
@@ -599,32 +619,19 @@ class DeviceLibrary:
         -> (sq, st), DeviceBuffers that are the caller's to free. sq: int32 per frame of `other`, the number of this library's
         videos it occurs in; st: int32 per frame of this library, the number of `other`'s videos it occurs in. The records of
         the last search stay valid for hvd_dev_vpdq_emit_again."""
-        lib = _lib.ensure()
-        max_dist = _default_max_dist(max_dist)
         with _DeviceScope() as scope:
             d_sq = scope.keep(DeviceBuffer(4 * max(other.n_frames, 1)))
             d_st = scope.keep(DeviceBuffer(4 * max(self.n_frames, 1)))
-            if max_dist < 0 or other.n_frames == 0 or self.n_frames == 0:
+            if not self._spread_into(other, max_dist, False, d_sq.ptr, d_st.ptr):
                 d_sq.zero()
                 d_st.zero()
-            else:
-                _lib.check(lib.hvd_dev_vpdq_frame_spread_cross(other.image().ptr, other.n_frames, other.d_video.ptr,
-                                                               self.image().ptr, self.n_frames, self.d_video.ptr, max_dist, 0,
-                                                               d_sq.ptr, d_st.ptr))
         return d_sq, d_st
 
     def match_library(self, other: "DeviceLibrary", max_dist: int | None = None, cap: int | None = None) -> np.ndarray:
         """hvd_dev_vpdq_match_videos_cross of another resident library (query side) against this one (target side), no
         exclusion maps: VMATCH_DTYPE records (a = other's video, b = this library's video) sorted by (a, b); the same record
         buffer, cap and emit-again retry as match_queries."""
-        lib = _lib.ensure()
-        max_dist = _default_max_dist(max_dist)
-        if max_dist < 0 or other.n_frames == 0 or self.n_frames == 0:
-            return np.zeros(0, dtype=VMATCH_DTYPE)
-        cap = max(4096, other.n_videos) if cap is None else int(cap)
-        return _search_records(lambda d_out, cap_, d_cnt: lib.hvd_dev_vpdq_match_videos_cross(
-            other.image().ptr, other.n_frames, other.d_video.ptr, None, self.image().ptr, self.n_frames, self.d_video.ptr, None,
-            max_dist, 0, 1, d_out, cap_, d_cnt), cap)
+        return self._match(other, None, False, 0, max_dist, 0, 1, cap)
 
     def _check_extension(self, other: "DeviceLibrary") -> None:
         """ValueError unless `extended(other)` can be built; touches nothing on the device."""
@@ -712,10 +719,7 @@ class DeviceLibrary:
                 _lib.check(lib.hvd_memcpy_d2d(d_su.ptr, d_spread_t.ptr, 4 * nT))
             if nQ:
                 _lib.check(lib.hvd_memcpy_d2d(d_su.ptr + 4 * nT, d_spread_q.ptr, 4 * nQ))
-            if max_dist >= 0 and nT and nQ:
-                _lib.check(lib.hvd_dev_vpdq_frame_spread_cross(new.image().ptr, nQ, new.d_video.ptr, self.image().ptr, nT,
-                                                               self.d_video.ptr, max_dist, 1, d_su.ptr + 4 * nT, d_su.ptr))
-            else:
+            if not self._spread_into(new, max_dist, True, d_su.ptr + 4 * nT, d_su.ptr):
                 _lib.check(lib.hvd_dev_sync())  # the copies read buffers the scope frees
             old, fresh = self, new
             dropped = np.zeros(V, dtype=np.int64)

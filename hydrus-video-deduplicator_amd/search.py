@@ -73,13 +73,19 @@ def allpairs_hamming(db: np.ndarray, max_dist: int = DISTANCE_TOLERANCE, group: 
 WEIGHT_TOTAL_LIMIT = (1 << 32) - 1  # the counters of a VMATCH record are uint32: no video's capped weights may add up to more
 
 
+def check_max_weight(max_weight) -> int:
+    """The cap on a weight of the weighted search as an int, or ValueError: an integer, at least 0 (0 = no cap)."""
+    if int(max_weight) != max_weight or max_weight < 0:
+        raise ValueError("max_weight is an integer, at least 0 (0 = no cap)")
+    return int(max_weight)
+
+
 def check_weights(weights, lengths, max_weight: int = 0) -> np.ndarray:
     """The frame weights of the weighted search as the C-ABI takes them, or ValueError naming the video at fault.
     weights: one int sequence per video (the shape of RepeatedFrames.runs), or one flat array with a weight per frame;
     lengths: frames per video. Every weight is an integer in [1, 2^31 - 1]; max_weight >= 0 (0 = no cap); no video's capped
     total exceeds 2^32 - 1. -> the weights, flat, int32."""
-    if int(max_weight) != max_weight or max_weight < 0:
-        raise ValueError("max_weight is an integer, at least 0 (0 = no cap)")
+    max_weight = check_max_weight(max_weight)
     lengths = np.asarray(lengths, dtype=np.int64)
     if isinstance(weights, np.ndarray) and weights.dtype != object and weights.ndim == 1:
         flat = weights
@@ -120,6 +126,48 @@ def video_weights(weights, offsets, max_weight: int = 0) -> np.ndarray:
     return (before[offsets[1:]] - before[offsets[:-1]]).astype(np.int64)
 
 
+# One side of the video search as the C-ABI takes it: `_library`'s arrays, the number of videos, the ids (int32
+# per video) and the weights (`check_weights`: flat int32) where the call has them.
+_Side = namedtuple("_Side", "frames offsets V ids weights")
+
+
+def _side(frames, offsets, ids=None, weights=None, max_weight: int = 0) -> _Side:
+    frames, offsets, _ = _library(frames, offsets)
+    V = offsets.size - 1
+    if weights is not None:
+        weights = check_weights(weights, np.diff(offsets), max_weight)
+    if ids is not None:
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        if ids.shape != (V,):
+            raise ValueError("one id per video")
+    return _Side(frames, offsets, V, ids, weights)
+
+
+def _video_search(q: _Side, t: _Side | None, max_dist: int, cap: int | None, max_weight: int) -> np.ndarray:
+    """The host video search of checked sides (t None: the symmetric one). The entry is picked by "one side or two" x "weights
+    or none"; a side is handed over as frames, offsets, V[, ids -- two sides][, weights -- weighted]; the totals the weighted
+    entries can write are not asked for. Default cap: max(1024, videos of the query side)."""
+    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
+        return np.zeros(0, dtype=VMATCH_DTYPE)
+    two, weighted = t is not None, q.weights is not None
+    entry = getattr(_lib.ensure(), _VIDEO_SEARCHES[two, weighted])
+    args = []
+    for s in (q, t) if two else (q,):
+        args += (_ptr(s.frames), s.offsets.ctypes.data, s.V)
+        if two:
+            args.append(None if s.ids is None else s.ids.ctypes.data)
+        if weighted:
+            args.append(_ptr(s.weights))
+    args += (int(max_weight), int(max_dist)) if weighted else (int(max_dist),)
+    totals = (None,) * (1 + two) if weighted else ()
+    return _lib.records_with_retry(lambda out, cap_, cnt: entry(*args, out, cap_, cnt, *totals), VMATCH_DTYPE,
+                                   max(1024, q.V) if cap is None else int(cap))
+
+
+_VIDEO_SEARCHES = {(False, False): "hvd_vpdq_match_videos", (True, False): "hvd_vpdq_match_videos_cross",
+                   (False, True): "hvd_vpdq_match_videos_weighted", (True, True): "hvd_vpdq_match_videos_cross_weighted"}
+
+
 def match_videos(frames: np.ndarray, offsets: np.ndarray, max_dist: int = DISTANCE_TOLERANCE,
                  cap: int | None = None, weights=None, max_weight: int = 0) -> np.ndarray:
     """Every video pair a<b with at least one frame hit, with its vPDQ counters, as a
@@ -127,21 +175,7 @@ def match_videos(frames: np.ndarray, offsets: np.ndarray, max_dist: int = DISTAN
     weights (flat, one per frame, or one sequence per video; `check_weights`): the duration-weighted search of DESIGN 4.20
     (hvd_vpdq_match_videos_weighted) -- a matched frame adds min(weight, max_weight) (max_weight 0: its weight) to q_hits /
     t_hits instead of 1, and `video_weights` gives the denominators. None: the plain search."""
-    frames, offsets, _ = _library(frames, offsets)
-    V = offsets.size - 1
-    if weights is not None:
-        weights = check_weights(weights, np.diff(offsets), max_weight)
-    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
-        return np.zeros(0, dtype=VMATCH_DTYPE)
-    lib = _lib.ensure()
-    if weights is not None:
-        return _lib.records_with_retry(
-            lambda out, cap_, cnt: lib.hvd_vpdq_match_videos_weighted(_ptr(frames), offsets.ctypes.data, V, _ptr(weights),
-                                                                      int(max_weight), int(max_dist), out, cap_, cnt, None),
-            VMATCH_DTYPE, max(1024, V) if cap is None else int(cap))
-    return _lib.records_with_retry(
-        lambda out, cap_, cnt: lib.hvd_vpdq_match_videos(_ptr(frames), offsets.ctypes.data, V, int(max_dist), out, cap_, cnt),
-        VMATCH_DTYPE, max(1024, V) if cap is None else int(cap))
+    return _video_search(_side(frames, offsets, None, weights, max_weight), None, max_dist, cap, max_weight)
 
 
 def match_videos_cross(frames_q: np.ndarray, offsets_q: np.ndarray, frames_t: np.ndarray, offsets_t: np.ndarray,
@@ -153,37 +187,12 @@ def match_videos_cross(frames_q: np.ndarray, offsets_q: np.ndarray, frames_t: np
     ids_q/ids_t (int32 per video): equal ids are never compared (a query that is in the target set).
     weights_q / weights_t (both or neither; as `match_videos` takes weights): the duration-weighted form
     (hvd_vpdq_match_videos_cross_weighted) -- q_hits sums the query side's weights, t_hits the target side's."""
-    frames_q, offsets_q, _ = _library(frames_q, offsets_q)
-    frames_t, offsets_t, _ = _library(frames_t, offsets_t)
-    VQ, VT = offsets_q.size - 1, offsets_t.size - 1
     if (ids_q is None) != (ids_t is None):
         raise ValueError("pass both id arrays or neither")
     if (weights_q is None) != (weights_t is None):
         raise ValueError("pass both weight arrays or neither")
-    if weights_q is not None:
-        weights_q = check_weights(weights_q, np.diff(offsets_q), max_weight)
-        weights_t = check_weights(weights_t, np.diff(offsets_t), max_weight)
-    if ids_q is not None:
-        ids_q = np.ascontiguousarray(ids_q, dtype=np.int32)
-        ids_t = np.ascontiguousarray(ids_t, dtype=np.int32)
-        if ids_q.shape != (VQ,) or ids_t.shape != (VT,):
-            raise ValueError("one id per video")
-    if max_dist < 0:
-        return np.zeros(0, dtype=VMATCH_DTYPE)
-    lib = _lib.ensure()
-    if weights_q is not None:
-        return _lib.records_with_retry(
-            lambda out, cap_, cnt: lib.hvd_vpdq_match_videos_cross_weighted(
-                _ptr(frames_q), offsets_q.ctypes.data, VQ, ids_q.ctypes.data if ids_q is not None else None, _ptr(weights_q),
-                _ptr(frames_t), offsets_t.ctypes.data, VT, ids_t.ctypes.data if ids_t is not None else None, _ptr(weights_t),
-                int(max_weight), int(max_dist), out, cap_, cnt, None, None),
-            VMATCH_DTYPE, max(1024, VQ) if cap is None else int(cap))
-    return _lib.records_with_retry(
-        lambda out, cap_, cnt: lib.hvd_vpdq_match_videos_cross(
-            _ptr(frames_q), offsets_q.ctypes.data, VQ, ids_q.ctypes.data if ids_q is not None else None,
-            _ptr(frames_t), offsets_t.ctypes.data, VT, ids_t.ctypes.data if ids_t is not None else None, int(max_dist),
-            out, cap_, cnt),
-        VMATCH_DTYPE, max(1024, VQ) if cap is None else int(cap))
+    q = _side(frames_q, offsets_q, ids_q, weights_q, max_weight)
+    return _video_search(q, _side(frames_t, offsets_t, ids_t, weights_t, max_weight), max_dist, cap, max_weight)
 
 
 def similarity_of_records(records: np.ndarray, lengths: np.ndarray, policy: str | None = None) -> np.ndarray:
@@ -1086,13 +1095,12 @@ def frame_spread(frames: np.ndarray, offsets: np.ndarray, max_dist: int | None =
     """In how many OTHER videos does every frame occur? int32 per frame hash: the number of videos v != the frame's own that
     hold at least one frame within max_dist of it (hvd_vpdq_frame_spread: the compare and the key set of match_videos without
     its fold). frames: uint8[sum,32]; offsets: int64[V+1] (CSR); max_dist: default the tolerance of the video search."""
-    frames, offsets, _ = _library(frames, offsets)
+    q = _side(frames, offsets)
     max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
-    spread = np.zeros(frames.shape[0], dtype=np.int32)
-    if max_dist < 0 or frames.shape[0] < 2:  # comparator "lt" at tolerance 0: nothing can match
+    spread = np.zeros(q.frames.shape[0], dtype=np.int32)
+    if max_dist < 0 or spread.size < 2:  # comparator "lt" at tolerance 0: nothing can match
         return spread
-    _lib.check(_lib.ensure().hvd_vpdq_frame_spread(_ptr(frames), offsets.ctypes.data, offsets.size - 1, max_dist,
-                                                   spread.ctypes.data))
+    _lib.check(_lib.ensure().hvd_vpdq_frame_spread(_ptr(q.frames), q.offsets.ctypes.data, q.V, max_dist, spread.ctypes.data))
     return spread
 
 
@@ -1103,15 +1111,14 @@ def frame_spread_cross(frames_q: np.ndarray, offsets_q: np.ndarray, frames_t: np
     of T: the number of videos of Q likewise (hvd_vpdq_frame_spread_cross: the compare and the key set of match_videos_cross
     without its fold). Q's frames are never compared with Q's, nor T's with T's: with `frame_spread` of each side alone they
     add up to the spread of the union. Arguments as `match_videos_cross`; max_dist: default the video search's tolerance."""
-    frames_q, offsets_q, _ = _library(frames_q, offsets_q)
-    frames_t, offsets_t, _ = _library(frames_t, offsets_t)
+    q, t = _side(frames_q, offsets_q), _side(frames_t, offsets_t)
     max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
-    spread_q, spread_t = np.zeros(frames_q.shape[0], dtype=np.int32), np.zeros(frames_t.shape[0], dtype=np.int32)
-    if max_dist < 0 or frames_q.shape[0] == 0 or frames_t.shape[0] == 0:
+    spread_q, spread_t = np.zeros(q.frames.shape[0], dtype=np.int32), np.zeros(t.frames.shape[0], dtype=np.int32)
+    if max_dist < 0 or spread_q.size == 0 or spread_t.size == 0:
         return spread_q, spread_t
-    _lib.check(_lib.ensure().hvd_vpdq_frame_spread_cross(_ptr(frames_q), offsets_q.ctypes.data, offsets_q.size - 1, _ptr(frames_t),
-                                                         offsets_t.ctypes.data, offsets_t.size - 1, max_dist,
-                                                         spread_q.ctypes.data, spread_t.ctypes.data))
+    _lib.check(_lib.ensure().hvd_vpdq_frame_spread_cross(_ptr(q.frames), q.offsets.ctypes.data, q.V, _ptr(t.frames),
+                                                         t.offsets.ctypes.data, t.V, max_dist, spread_q.ctypes.data,
+                                                         spread_t.ctypes.data))
     return spread_q, spread_t
 
 
