@@ -29,6 +29,9 @@ VMATCH_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("q_hits", "<u4"), ("t_hits
 VALIGN_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("q_hits", "<u4"), ("t_hits", "<u4"), ("offset", "<i4"),
                          ("band_votes", "<u4"), ("q_aligned", "<u4"), ("t_aligned", "<u4"), ("q_first", "<i4"),
                          ("q_last", "<i4"), ("t_first", "<i4"), ("t_last", "<i4")])
+# one video's coverage by its partners of a pair list (hvd_vcover): the union of the contributed frame sets, the contributing
+# list entries, the largest single contribution, the video's length
+VCOVER_DTYPE = np.dtype([("covered", "<u4"), ("sources", "<u4"), ("best_single", "<u4"), ("frames", "<u4")])
 ALIGN_LDS_BINS = 4096  # HVD_ALIGN_LDS_BINS
 ALIGN_MAX_SEGMENTS = 8  # HVD_ALIGN_MAX_SEGMENTS
 # one segment of a pair (hvd_vsegment): the words of VALIGN_DTYPE from offset on, on the frame hits no earlier segment owns
@@ -90,6 +93,7 @@ SIGNATURES = {
     "hvd_vpdq_match_videos_cross": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _int, _vp, _i64,
                                            C.POINTER(_i64)]),
     "hvd_vpdq_align_videos": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp]),
+    "hvd_vpdq_cover_videos": (_int, [_vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _int, _vp, _vp]),
     "hvd_vpdq_align_segments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _int, _int, _vp]),
     "hvd_vpdq_align_rates": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _vp]),
     "hvd_vpdq_align_rate_segments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _int, _int,
@@ -156,6 +160,8 @@ SIGNATURES = {
     "hvd_align_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
     "hvd_dev_vpdq_align_videos": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _sz, _vp]),
     "hvd_segments_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
+    "hvd_cover_scratch_bytes": (_int, [_i64, _i64, C.POINTER(_sz)]),
+    "hvd_dev_vpdq_cover_videos": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _int, _int, _int, _vp, _sz, _vp, _vp]),
     "hvd_dev_vpdq_align_segments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _sz,
                                            _vp]),
     "hvd_rates_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),

@@ -250,6 +250,21 @@ struct AlignOperands {
 size_t alignment_scratch_bytes(const AlignMode& mode, unsigned long long max_bins);
 hipError_t launch_alignment(const AlignMode& mode, const AlignOperands& op, hipStream_t s);
 
+// Coverage of a video by several others (k_valign_cover.hip): the slope-one alignment with a second output, not a
+// fifth mode. align: one library on both sides (the q operands are read), out = M hvd_valign; its scratch holds the bitmap
+// over the n_frames frames of the library (cover_bitmap_bytes, 16-byte aligned), then the slots of the scratch launch
+// (alignment_scratch_bytes of the slope-one mode). cover: VQ hvd_vcover. Enqueued: the clear of the bitmap and of the cover
+// records, the two launches, the count.
+struct CoverOperands {
+    AlignOperands align;
+    int64_t n_frames;
+    int min_aligned;
+    void* cover;
+};
+size_t cover_bitmap_bytes(unsigned long long n_frames);
+size_t cover_scratch_bytes(unsigned long long n_frames, unsigned long long max_bins);
+hipError_t launch_valign_cover(const CoverOperands& op, hipStream_t s);
+
 // The rate list of the rate-aware alignments travels as two kernel arguments: entry r = (num, den) in bits 4r .. 4r + 3 of nums and
 // of dens, and it ends at the first entry whose two nibbles are 0. rate_list_length: its length R, or 0 for a broken list (a
 // value outside 1..8, a pair with a common factor, a rate listed twice, something behind the end, no entry) -- the one definition

@@ -1490,9 +1490,11 @@ static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V
 }
 
 // The host-buffer form of the alignments: validate, stage, run, copy the records back. h: the operands as host buffers (no
-// scratch). The list and the limits are judged first; a rated mode then judges the other arguments before the library's state,
-// so that a bad call is HVD_ERR_ARG with or without a device, the slope-one modes after it (mode.args_first).
-static int align_from_host(AlignMode mode, const int32_t* rates, int n_rates, const AlignOperands& h) {
+// scratch). Two steps that hvd_vpdq_cover_videos takes as well. align_check: the list and the limits are judged first; a rated
+// mode then judges the other arguments before the library's state, so that a bad call is HVD_ERR_ARG with or without a device,
+// the slope-one modes after it (mode.args_first). -> the frames of either library and the largest bins of any pair.
+static int align_check(AlignMode& mode, const int32_t* rates, int n_rates, const AlignOperands& h, int64_t* nq_out, int64_t* nt_out,
+                       int64_t* max_bins_out) {
     if (mode.rated && !hvd::pack_rate_list(rates, n_rates, &mode.nums, &mode.dens))
         return fail(HVD_ERR_ARG, "rates: need 1..%d pairs (num, den) with 1 <= num, den <= 8, no common factor, none listed twice",
                     HVD_ALIGN_MAX_RATES);
@@ -1534,12 +1536,26 @@ static int align_from_host(AlignMode mode, const int32_t* rates, int n_rates, co
     }
     if (mode.args_first)
         if (int rc = need_ready()) return rc;
-    if (M == 0) return HVD_OK;
-    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
-    const bool self = h.hashes_t == h.hashes_q && offsets_t == offsets_q && positions_t == positions_q && VT == VQ;
-    void *d_hq = nullptr, *d_ht = nullptr, *d_scr = nullptr, *d_pairs = nullptr, *d_out = nullptr;
+    *nq_out = nq;
+    *nt_out = nt;
+    *max_bins_out = max_bins;
+    return HVD_OK;
+}
+
+// the libraries of an alignment on the device: hashes, CSR offsets, positions or nullptr, per side
+struct AlignStaged {
+    void *d_hq = nullptr, *d_ht = nullptr;
     long long *d_oq = nullptr, *d_ot = nullptr;
     int32_t *d_pq = nullptr, *d_pt = nullptr;
+};
+
+// align_upload: the libraries of h (nq, nt frames) into the library's slots, one upload when both sides are one library. The
+// caller holds g.h_mu.
+static int align_upload(const AlignOperands& h, int64_t nq, int64_t nt, AlignStaged* st) {
+    const auto *offsets_q = (const int64_t*)h.offsets_q, *offsets_t = (const int64_t*)h.offsets_t;
+    const auto *positions_q = (const int32_t*)h.pos_q, *positions_t = (const int32_t*)h.pos_t;
+    const int64_t VQ = h.VQ, VT = h.VT;
+    const bool self = h.hashes_t == h.hashes_q && offsets_t == offsets_q && positions_t == positions_q && VT == VQ;
     auto upload = [&](const void* frames, const int64_t* offsets, int64_t V, int64_t n, const int32_t* pos, Ctx::Scr s_db,
                       Ctx::Scr s_off, Ctx::Scr s_pos, void** d_h, long long** d_o, int32_t** d_p) -> int {
         if (int rc = scratch(s_db, 32 * (size_t)n, d_h)) return rc;
@@ -1552,21 +1568,33 @@ static int align_from_host(AlignMode mode, const int32_t* rates, int n_rates, co
         }
         return HVD_OK;
     };
-    if (int rc = upload(h.hashes_q, offsets_q, VQ, nq, positions_q, Ctx::S_DB, Ctx::S_OFF, Ctx::S_POSQ, &d_hq, &d_oq, &d_pq)) return rc;
+    if (int rc = upload(h.hashes_q, offsets_q, VQ, nq, positions_q, Ctx::S_DB, Ctx::S_OFF, Ctx::S_POSQ, &st->d_hq, &st->d_oq, &st->d_pq)) return rc;
     if (self) {
-        d_ht = d_hq;
-        d_ot = d_oq;
-        d_pt = d_pq;
-    } else if (int rc = upload(h.hashes_t, offsets_t, VT, nt, positions_t, Ctx::S_DB2, Ctx::S_OFF2, Ctx::S_POST, &d_ht, &d_ot, &d_pt)) {
-        return rc;
+        st->d_ht = st->d_hq;
+        st->d_ot = st->d_oq;
+        st->d_pt = st->d_pq;
+        return HVD_OK;
     }
+    return upload(h.hashes_t, offsets_t, VT, nt, positions_t, Ctx::S_DB2, Ctx::S_OFF2, Ctx::S_POST, &st->d_ht, &st->d_ot, &st->d_pt);
+}
+
+static int align_from_host(AlignMode mode, const int32_t* rates, int n_rates, const AlignOperands& h) {
+    int64_t nq = 0, nt = 0, max_bins = 0;
+    if (int rc = align_check(mode, rates, n_rates, h, &nq, &nt, &max_bins)) return rc;
+    const int64_t M = h.M;
+    if (M == 0) return HVD_OK;
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    AlignStaged st;
+    if (int rc = align_upload(h, nq, nt, &st)) return rc;
+    void *d_scr = nullptr, *d_pairs = nullptr, *d_out = nullptr;
     SCR(S_APAIRS, 8 * (size_t)M, d_pairs);
     const size_t out_bytes = mode.record_bytes() * (size_t)M;
     SCR(S_AOUT, out_bytes, d_out);
     const size_t sb = hvd::alignment_scratch_bytes(mode, (unsigned long long)max_bins);
     if (sb) SCR(S_ASCR, sb, d_scr);
-    HIP_TRY(hipMemcpyAsync(d_pairs, pairs, 8 * (size_t)M, hipMemcpyHostToDevice, g.stream));
-    if (int rc = align_on_device(mode, rates, n_rates, {d_hq, d_oq, VQ, d_pq, d_ht, d_ot, VT, d_pt, d_pairs, M, h.max_dist, h.slack, d_scr, sb, d_out}))
+    HIP_TRY(hipMemcpyAsync(d_pairs, h.pairs, 8 * (size_t)M, hipMemcpyHostToDevice, g.stream));
+    if (int rc = align_on_device(mode, rates, n_rates, {st.d_hq, st.d_oq, h.VQ, st.d_pq, st.d_ht, st.d_ot, h.VT, st.d_pt, d_pairs, M, h.max_dist,
+                                                        h.slack, d_scr, sb, d_out}))
         return rc;
     HIP_TRY(hipMemcpyAsync(h.out, d_out, out_bytes, hipMemcpyDeviceToHost, g.stream));
     HIP_TRY(hipStreamSynchronize(g.stream));
@@ -1602,6 +1630,76 @@ int hvd_vpdq_align_rate_segments(const uint8_t* frames_q, const int64_t* offsets
                                  int max_segments, int min_band_votes, hvd_vrsegments* out) {
     return align_from_host(AlignMode::of(true, true, max_segments, min_band_votes), rates, n_rates,
                            {frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, nullptr, 0, out});
+}
+
+/* ---- coverage of a video by several others (k_valign_cover.hip): the slope-one alignment with a second output ---- */
+
+static int check_cover_floor(int min_aligned) {
+    if (min_aligned < 1) return fail(HVD_ERR_ARG, "min_aligned=%d: need >= 1", min_aligned);
+    return HVD_OK;
+}
+
+int hvd_cover_scratch_bytes(int64_t n_frames, int64_t max_bins, size_t* out_bytes) {
+    if (!out_bytes) return fail(HVD_ERR_ARG, "out_bytes is NULL");
+    if (max_bins < 0 || max_bins > (1ll << 20)) return fail(HVD_ERR_ARG, "max_bins=%lld: need 0..2^20", (long long)max_bins);
+    if (n_frames < 0 || n_frames >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "n_frames=%lld out of range", (long long)n_frames);
+    *out_bytes = hvd::cover_scratch_bytes((unsigned long long)n_frames, (unsigned long long)max_bins);
+    return HVD_OK;
+}
+
+int hvd_dev_vpdq_cover_videos(const void* d_hashes, const void* d_offsets, int64_t V, int64_t n_frames, const void* d_pos,
+                              const void* d_pairs, int64_t M, int max_dist, int slack, int min_aligned, void* d_scratch,
+                              size_t scratch_bytes, void* d_out_align, void* d_out_cover) {
+    if (int rc = need_ready()) return rc;
+    if (V < 0 || V >= (1ll << 31) || M < 0) return fail(HVD_ERR_ARG, "bad counts");
+    if (n_frames < 0 || n_frames >= (1ll << 32) - 1) return fail(HVD_ERR_ARG, "n_frames=%lld out of range", (long long)n_frames);
+    if (int rc = check_tolerances(max_dist, slack)) return rc;
+    if (int rc = check_cover_floor(min_aligned)) return rc;
+    if (V == 0 && M == 0) return HVD_OK;
+    if (!d_offsets || (M > 0 && (!d_pairs || !d_out_align)) || (V > 0 && !d_out_cover)) return fail(HVD_ERR_ARG, "NULL device pointer");
+    const size_t bitmap_bytes = hvd::cover_bitmap_bytes((unsigned long long)n_frames);
+    if (scratch_bytes < bitmap_bytes || (bitmap_bytes && !d_scratch))
+        return fail(HVD_ERR_ARG, "scratch of %zu bytes: the bitmap over %lld frames needs %zu (hvd_cover_scratch_bytes)", scratch_bytes,
+                    (long long)n_frames, bitmap_bytes);
+    if (((uintptr_t)d_hashes | (uintptr_t)d_scratch | (uintptr_t)d_out_cover) & 15u)
+        return fail(HVD_ERR_ARG, "hashes, scratch and cover records must be 16-byte aligned");
+    HIP_TRY(hvd::launch_valign_cover({{d_hashes, d_offsets, V, d_pos, d_hashes, d_offsets, V, d_pos, d_pairs, M, max_dist, slack, d_scratch,
+                                       scratch_bytes, d_out_align},
+                                      n_frames, min_aligned, d_out_cover},
+                                     g.stream));
+    return HVD_OK;
+}
+
+int hvd_vpdq_cover_videos(const uint8_t* frames, const int64_t* offsets, int64_t V, const int32_t* positions, const uint32_t* pairs,
+                          int64_t M, int max_dist, int slack, int min_aligned, hvd_valign* out_align, hvd_vcover* out_cover) {
+    // every refusal comes before the question whether a device is there (as the rate entries: args_first); the checks and the
+    // upload are the alignment's, on one library
+    if (int rc = check_cover_floor(min_aligned)) return rc;
+    if (V > 0 && !out_cover) return fail(HVD_ERR_ARG, "out_cover is NULL");
+    AlignMode mode = AlignMode::of(false, false);
+    mode.args_first = true;
+    const AlignOperands h = {frames, offsets, V, positions, frames, offsets, V, positions, pairs, M, max_dist, slack, nullptr, 0, out_align};
+    int64_t nf = 0, nt = 0, max_bins = 0;
+    if (int rc = align_check(mode, nullptr, 0, h, &nf, &nt, &max_bins)) return rc;
+    if (V == 0) return HVD_OK;
+    std::lock_guard<std::recursive_mutex> lk(g.h_mu);
+    AlignStaged st;
+    if (int rc = align_upload(h, nf, nt, &st)) return rc;
+    // the alignment records, then (16-byte aligned: a record is 48 bytes) the cover records, in one slot
+    void *d_scr = nullptr, *d_pairs = nullptr, *d_out = nullptr;
+    const size_t align_bytes = sizeof(hvd_valign) * (size_t)M, cover_bytes = sizeof(hvd_vcover) * (size_t)V;
+    SCR(S_APAIRS, 8 * (size_t)M, d_pairs);
+    SCR(S_AOUT, align_bytes + cover_bytes, d_out);
+    void* const d_cover = (char*)d_out + align_bytes;
+    const size_t sb = hvd::cover_scratch_bytes((unsigned long long)nf, (unsigned long long)max_bins);
+    if (sb) SCR(S_ASCR, sb, d_scr);
+    if (M > 0) HIP_TRY(hipMemcpyAsync(d_pairs, pairs, 8 * (size_t)M, hipMemcpyHostToDevice, g.stream));
+    if (int rc = hvd_dev_vpdq_cover_videos(st.d_hq, st.d_oq, V, nf, st.d_pq, d_pairs, M, max_dist, slack, min_aligned, d_scr, sb, d_out, d_cover))
+        return rc;
+    if (M > 0) HIP_TRY(hipMemcpyAsync(out_align, d_out, align_bytes, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipMemcpyAsync(out_cover, d_cover, cover_bytes, hipMemcpyDeviceToHost, g.stream));
+    HIP_TRY(hipStreamSynchronize(g.stream));
+    return HVD_OK;
 }
 
 /* ---- duplicate groups with a keeper: connected components of a pair list (k_group.hip) ---- */

@@ -502,6 +502,48 @@ class DeviceLibrary:
             lib.hvd_dev_sync()  # nothing may still run on a buffer that is freed here
         return aligned
 
+    def cover(self, records, slack: int = search.ALIGN_SLACK, max_dist: int | None = None,
+              min_aligned: int = 4) -> tuple[np.ndarray, np.ndarray]:
+        """hvd_dev_vpdq_cover_videos of the listed pairs of this library against itself (records: VMATCH records, or
+        int[M, 2]; search.cover_videos on what is in HBM): -> (one VALIGN_DTYPE record per pair, in their order -- `align`'s,
+        word for word; one VCOVER_DTYPE record per video: the union of its aligned frames over all its pairs). The union is
+        taken in a bitmap on the device; the pair list goes up, the records come back. Operands and positions as `align`."""
+        lib = _lib.ensure()
+        pairs = search.pair_array(records)
+        M, V = pairs.shape[0], self.n_videos
+        max_dist = _default_max_dist(max_dist)
+        aligned = np.zeros(M, dtype=_lib.VALIGN_DTYPE)
+        aligned["a"], aligned["b"] = pairs[:, 0], pairs[:, 1]
+        if V == 0:
+            return aligned, np.zeros(0, dtype=_lib.VCOVER_DTYPE)
+        if max_dist < 0:
+            cover = np.zeros(V, dtype=_lib.VCOVER_DTYPE)
+            cover["frames"] = self.lengths()
+            return aligned, cover
+        # the scratch serves the widest pair this library can hold, as `_align` sizes it, and the bitmap over its frames
+        if self.d_positions is None:
+            lengths = self.lengths()
+            limit = int(lengths.max()) if lengths.size else 0
+        else:
+            limit = self._position_limit
+        max_bins = 2 * (max(limit, 1) - 1) + 1 + 2 * int(slack)
+        sb = C.c_size_t(0)
+        _lib.check(lib.hvd_cover_scratch_bytes(self.n_frames, min(max_bins, _lib.ALIGN_MAX_BINS), C.byref(sb)))
+        with _DeviceScope() as scope:
+            d_pairs = scope.temp(DeviceBuffer.from_array(pairs) if M else None)
+            d_out = scope.temp(DeviceBuffer(_lib.VALIGN_DTYPE.itemsize * M) if M else None)
+            d_cover = scope.temp(DeviceBuffer(_lib.VCOVER_DTYPE.itemsize * V))
+            d_scr = scope.temp(DeviceBuffer(sb.value) if sb.value else None)
+            d_pos = self.d_positions.ptr if self.d_positions is not None else None
+            _lib.check(lib.hvd_dev_vpdq_cover_videos(
+                self.d_hashes.ptr, self.d_offsets.ptr, V, self.n_frames, d_pos, d_pairs.ptr if M else None, M, max_dist, int(slack),
+                int(min_aligned), d_scr.ptr if d_scr else None, sb.value, d_out.ptr if M else None, d_cover.ptr))
+            if M:
+                aligned = d_out.to_array(_lib.VALIGN_DTYPE, M)  # (the copy waits for the library stream)
+            cover = d_cover.to_array(_lib.VCOVER_DTYPE, V)
+            lib.hvd_dev_sync()  # nothing may still run on a buffer that is freed here
+        return aligned, cover
+
     def spread(self, max_dist: int | None = None) -> DeviceBuffer:
         """hvd_dev_vpdq_frame_spread: int32 per kept frame, the number of OTHER videos of this library the frame occurs in
         (DESIGN 4.13), as a DeviceBuffer that is the caller's to free. The compare and the key set of `match_videos`
@@ -1206,6 +1248,30 @@ def find_rate_segmented_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.nd
     -> (rate-segmented excerpts, search records, VRSEGMENTS records, library or None); positions are raw frame indices."""
     return _aligned_search_on_device(search.AlignMode(rates, max_segments, int(min_aligned)), d_frames_ptr, raw_offsets, h, w,
                                      channels, threshold, min_aligned, slack, positions, keep_library)
+
+
+def find_compilations_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                threshold: float = 50.0, min_aligned: int = 4, slack: int = search.ALIGN_SLACK,
+                                positions: bool = True, keep_library: bool = False):
+    """search.find_compilations on frames in HBM, one device: hash -> quality filter + CSR, with the kept frames' raw positions
+    -> video search -> alignment of its records with the union of every video's aligned frames (`DeviceLibrary.cover`) -> the
+    keep rule of search.compilations_from_records; nothing but records crosses PCIe. The arguments are
+    `find_excerpts_on_device`'s. -> (compilations, search records, alignment records, cover records, library or None);
+    first / last / offset of a source are raw frame indices."""
+    library = _hashed_library(
+        raw_offsets, 0, 1, None, lambda mine: hash_frames_on_device(d_frames_ptr, int(mine[-1]), h, w, channels), 32,
+        lambda *raw: DeviceLibrary.from_raw_hashes(*raw, positions=bool(positions)), None)
+    try:
+        recs = library.match_videos()
+        aligned, cover = library.cover(recs, slack, None, min_aligned)
+        out = search.compilations_from_records(aligned, cover, library.lengths(), threshold, min_aligned)
+    except BaseException:
+        library.free()
+        raise
+    if keep_library:
+        return out, recs, aligned, cover, library
+    library.free()
+    return out, recs, aligned, cover, None
 
 
 def _rank0_of_every_context(entry, frames_of_rank, timings, n_results: int, *args, **kwargs):

@@ -18,8 +18,8 @@ from fractions import Fraction
 import numpy as np
 
 from . import _lib, vpdq
-from ._lib import (ALIGN_MAX_RATES, ALIGN_MAX_SEGMENTS, GROUP_DTYPE, PAIR_DTYPE, VALIGN_DTYPE, VMATCH_DTYPE, VRATE_DTYPE, VRSEGMENTS_DTYPE,
-                   VSEGMENTS_DTYPE)
+from ._lib import (ALIGN_MAX_RATES, ALIGN_MAX_SEGMENTS, GROUP_DTYPE, PAIR_DTYPE, VALIGN_DTYPE, VCOVER_DTYPE, VMATCH_DTYPE, VRATE_DTYPE,
+                   VRSEGMENTS_DTYPE, VSEGMENTS_DTYPE)
 
 DISTANCE_TOLERANCE = 31  # per-frame Hamming tolerance (vpdqpy/vpdqpy.py:53, db/vptree.py:31)
 DEFAULT_VARIANT = 13  # all-pairs kernel the product uses (FP4-MFMA, 128-bit first stage, form chosen by a probe); DESIGN.md 4.1
@@ -889,6 +889,108 @@ def find_rate_segmented_excerpts(video_hashes, threshold: float = 50.0, min_alig
     fragments (the coverage nearly the same) when it is the second; list (1, 2) in place of another rate to change that."""
     return rate_segmented_excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, rates, positions,
                                         max_segments)
+
+
+# ------------------------------------------ compilations and multi-part uploads: coverage by several videos (DESIGN 4.23) ------
+
+def cover_videos(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.ndarray | None = None,
+                 max_dist: int | None = None, slack: int = ALIGN_SLACK, min_aligned: int = 4) -> tuple[np.ndarray, np.ndarray]:
+    """Time alignment of the listed pairs of ONE library and, per video, the union of its aligned frames over all its pairs
+    (hvd_vpdq_cover_videos). -> (VALIGN_DTYPE records in the order of `pairs`: align_videos' on the same operands, word for
+    word; VCOVER_DTYPE records, one per video). A pair contributes the aligned frames of its a side to video a iff a != b, the
+    pair could be aligned and at least `min_aligned` frames of a are aligned, and likewise for b; covered = the size of the
+    union of what was contributed to the video, sources = the list entries that contributed, best_single = the largest single
+    contribution, frames = the video's length. Pass each unordered pair once (as match_videos' records do): a pair listed
+    twice counts twice in `sources`. frames / offsets / positions / max_dist / slack: as align_videos."""
+    frames, offsets, positions = _library(frames, offsets, positions)
+    pairs = pair_array(pairs)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE) if max_dist is None else int(max_dist)
+    M, V = pairs.shape[0], offsets.size - 1
+    aligned = np.zeros(M, dtype=VALIGN_DTYPE)
+    aligned["a"], aligned["b"] = pairs[:, 0], pairs[:, 1]
+    cover = np.zeros(V, dtype=VCOVER_DTYPE)
+    if max_dist < 0:  # comparator "lt" at tolerance 0: nothing can match
+        cover["frames"] = np.diff(offsets)
+        return aligned, cover
+    lib = _lib.ensure()
+    _lib.check(lib.hvd_vpdq_cover_videos(_ptr(frames), offsets.ctypes.data, V, _ptr(positions), _ptr(pairs), M, max_dist, int(slack),
+                                         int(min_aligned), _ptr(aligned), _ptr(cover)))
+    return aligned, cover
+
+
+Compilation = namedtuple("Compilation", "video coverage covered sources")
+CompilationSource = namedtuple("CompilationSource", "other offset first last aligned")
+
+
+def compilation_sources(aligned: np.ndarray, V: int, min_aligned: int = 4) -> list:
+    """Per video, the contributions the alignment records hold for it, by the kernel's own rule (cover_videos): a list of V
+    lists of CompilationSource(other, offset, first, last, aligned), each sorted by `first`. The video's positions
+    first..last line up with `other` at p_other = p_video + offset; aligned = the frames of the video on that band."""
+    out = [[] for _ in range(int(V))]
+    for r in aligned:
+        a, b, d = int(r["a"]), int(r["b"]), int(r["offset"])
+        if a == b or d == -(1 << 31):
+            continue
+        if int(r["q_aligned"]) >= int(min_aligned):
+            out[a].append(CompilationSource(b, d, int(r["q_first"]), int(r["q_last"]), int(r["q_aligned"])))
+        if int(r["t_aligned"]) >= int(min_aligned):
+            out[b].append(CompilationSource(a, -d, int(r["t_first"]), int(r["t_last"]), int(r["t_aligned"])))
+    return [sorted(v, key=lambda s: (s.first, s.last, s.other)) for v in out]
+
+
+def compilations_from_records(aligned: np.ndarray, cover: np.ndarray, lengths: np.ndarray, threshold: float = 50.0,
+                              min_aligned: int = 4) -> list:
+    """The keep rule of find_compilations on the two outputs of cover_videos (pure numpy; no device). coverage = 100 * covered
+    / frames; video v is kept iff frames > 0, covered > best_single -- no single partner explains it, so a video with two full
+    copies is a duplicate, not a compilation -- and int(coverage) >= int(threshold). lengths: the frames of every video of the
+    library the cover was made on; the rule goes by the record's `frames`, and records of another library (a different
+    number of videos, or other lengths) are refused. -> sorted list of Compilation(video, coverage, covered, sources),
+    sources = tuple of CompilationSource ordered by `first` (compilation_sources: read off the alignment records with the same
+    min_aligned the cover was made with)."""
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every video")
+    lengths = np.asarray(lengths, dtype=np.int64)
+    V = lengths.size
+    if len(cover) != V or not np.array_equal(cover["frames"], lengths):
+        raise ValueError("cover must hold one record per video of the library with these lengths")
+    sources = compilation_sources(aligned, V, min_aligned)
+    out = []
+    for v, c in enumerate(cover):
+        n, covered = int(c["frames"]), int(c["covered"])
+        if n == 0 or covered <= int(c["best_single"]):
+            continue
+        coverage = 100.0 * covered / n
+        if int(coverage) >= int(threshold):
+            out.append(Compilation(v, coverage, covered, tuple(sources[v])))
+    return sorted(out)
+
+
+def compilation_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK, positions=None,
+                      matcher=None) -> list:
+    """The search and the cover of find_compilations and their fold, on validated blobs (as excerpt_pairs). matcher: object
+    with match_videos / cover_videos (default: the GPU entry points of this module). -> compilations_from_records(...)."""
+    mv, cv = (match_videos, cover_videos) if matcher is None else (matcher.match_videos, matcher.cover_videos)
+    frames, offsets, lengths = pack_hashes(blobs)
+    pos = _positions_of(positions, blobs, lengths)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
+    recs = mv(frames, offsets, max_dist)
+    aligned, cover = cv(frames, offsets, np.stack([recs["a"], recs["b"]], axis=1), positions=pos, max_dist=max_dist, slack=slack,
+                        min_aligned=int(min_aligned))
+    return compilations_from_records(aligned, cover, lengths, threshold, min_aligned)
+
+
+def find_compilations(video_hashes, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
+                      positions=None) -> list:
+    """Videos that are made up of SEVERAL other videos of the library: a "best of" compilation whose clips are all there, a
+    film next to its part1 / part2 / part3, a stream archive next to its per-segment uploads. find_excerpts reports every part
+    against the long video -- the parts may go; this search says whether the LONG video may go, that is, whether the parts
+    together hold it. Every pair of the video search (match_videos) is aligned in time, and the aligned frames of a video are
+    united over all its partners on the device (cover_videos); a video is kept iff the union covers at least `threshold`
+    percent of it and is larger than any single partner's share. The arguments are find_excerpts'. -> sorted list of
+    Compilation(video, coverage, covered, sources): covered frames of the video, sources = tuple of CompilationSource(other,
+    offset, first, last, aligned) ordered by first: the video's positions first..last line up with video `other` at
+    p_other = p_video + offset. A source used in two places of the video contributes its best band only."""
+    return compilation_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, positions)
 
 
 # ------------------------------------------------------------------ duplicate groups with a keeper (DESIGN 4.11) ------

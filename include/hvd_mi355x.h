@@ -40,7 +40,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross, then + hvd_rate_segments_scratch_bytes, hvd_dev_vpdq_align_rate_segments, hvd_vpdq_align_rate_segments, then + hvd_dev_frame_runs, hvd_vpdq_frame_runs, then + hvd_dev_video_weights, hvd_dev_vpdq_match_videos_weighted, hvd_dev_vpdq_match_videos_cross_weighted, hvd_vpdq_match_videos_weighted, hvd_vpdq_match_videos_cross_weighted; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross, then + hvd_rate_segments_scratch_bytes, hvd_dev_vpdq_align_rate_segments, hvd_vpdq_align_rate_segments, then + hvd_dev_frame_runs, hvd_vpdq_frame_runs, then + hvd_dev_video_weights, hvd_dev_vpdq_match_videos_weighted, hvd_dev_vpdq_match_videos_cross_weighted, hvd_vpdq_match_videos_weighted, hvd_vpdq_match_videos_cross_weighted, then + hvd_cover_scratch_bytes, hvd_dev_vpdq_cover_videos, hvd_vpdq_cover_videos; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -65,6 +65,12 @@ typedef struct hvd_valign {
     uint32_t band_votes, q_aligned, t_aligned;
     int32_t q_first, q_last, t_first, t_last;
 } hvd_valign;
+/* One video's coverage by its partners of a pair list (hvd_vpdq_cover_videos / hvd_dev_vpdq_cover_videos), four
+ * 32-bit words. covered: the size of the union of the frame sets contributed to the video; sources: the number of list entries
+ * that contributed; best_single: the largest single contribution; frames: the video's length as the kernel clamps it. */
+typedef struct hvd_vcover {
+    uint32_t covered, sources, best_single, frames;
+} hvd_vcover;
 /* Pairs of up to this many histogram bins (span of p_a + span of p_b + 1 + 2 slack) are aligned out of LDS alone. */
 #define HVD_ALIGN_LDS_BINS 4096
 
@@ -350,6 +356,26 @@ int hvd_vpdq_frame_spread_cross(const uint8_t* frames_q, const int64_t* offsets_
 int hvd_vpdq_align_videos(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
                           const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                           const uint32_t* pairs, int64_t M, int max_dist, int slack, hvd_valign* out);
+
+/* Coverage of a video by SEVERAL others: a compilation of clips that are all in the library, a film next to its parts, a stream
+ * archive next to its per-segment uploads. hvd_vpdq_align_videos judges one pair at a time; here the aligned
+ * frames of every pair a video takes part in are united. The rule, integers only. One library (frames / offsets / positions
+ * as above), pairs: uint32[M][2] = (a, b), both videos of that library; max_dist in [0, 127], slack in [0, 16], min_aligned >= 1.
+ * Per pair: out_align[p] is the hvd_valign record of hvd_vpdq_align_videos on the same operands, word for word. Let on_a / on_b
+ * be the pair's aligned frame sets -- frame indices inside the video, the sets whose sizes are q_aligned / t_aligned. The pair
+ * contributes on_a to video a iff a != b, the record's offset is not INT32_MIN and |on_a| >= min_aligned; independently it
+ * contributes on_b to video b iff a != b, the offset is not INT32_MIN and |on_b| >= min_aligned.
+ * Per video v: out_cover[v] (hvd_vcover) = covered: the size of the union of the frame sets contributed to v; sources: the
+ * number of list entries that contributed to v; best_single: the largest single contribution; frames: the length of v.
+ * Five consequences: (a) best_single <= covered <= min(frames, the sum of the contributions); (b) sources == 0 iff covered == 0;
+ * (c) listing a pair twice, or as (a, b) and as (b, a), changes sources and nothing else -- callers pass each unordered pair
+ * once, as the records of hvd_vpdq_match_videos do; (d) a video that no pair names has the record (0, 0, 0, frames); (e) the
+ * alignment records do not depend on min_aligned. covered > best_single says that no single partner explains the video.
+ * This host-buffer form checks what hvd_vpdq_align_videos checks, and min_aligned, before it asks whether a device is there
+ * (HVD_ERR_ARG with or without one); then it stages, runs and copies both outputs back. M == 0 is legal and gives the records
+ * of (d). out_align: M records (may be NULL when M == 0); out_cover: V records. positions may be NULL. */
+int hvd_vpdq_cover_videos(const uint8_t* frames, const int64_t* offsets, int64_t V, const int32_t* positions, const uint32_t* pairs,
+                          int64_t M, int max_dist, int slack, int min_aligned, hvd_valign* out_align, hvd_vcover* out_cover);
 
 /* Multi-segment time alignment of listed video pairs: a short video that is SEVERAL pieces of a longer one. The
  * notation and the operands of hvd_vpdq_align_videos apply (H, delta, votes, S, slack, the tie order). The rule, integers only,
@@ -808,6 +834,22 @@ int hvd_dev_vpdq_align_videos(const void* d_hashes_q, const void* d_offsets_q, i
                               const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                               const void* d_pairs, int64_t M, int max_dist, int slack, void* d_scratch, size_t scratch_bytes,
                               void* d_out);
+
+/* Device-resident coverage (the rule: hvd_vpdq_cover_videos above). One library: d_hashes (n_frames * 32 B, 16-byte aligned),
+ * d_offsets int64[V+1], d_pos int32 per frame or NULL; d_pairs: uint32[M][2]; d_out_align: M hvd_valign records; d_out_cover: V
+ * hvd_vcover records, 16-byte aligned. d_scratch (16-byte aligned) holds one bit per frame of the library -- bit offsets[v] + i
+ * is frame i of video v -- and behind it the scratch of hvd_dev_vpdq_align_videos: hvd_cover_scratch_bytes(n_frames, max_bins)
+ * = the bitmap, (n_frames + 31) / 32 words rounded up to 16 bytes, plus hvd_align_scratch_bytes(max_bins). The entry enqueues,
+ * on the library stream, the clear of the bitmap and of the V cover records, the two launches of the alignment and the count:
+ * no host synchronisation, nothing allocated, nothing on the device validated. A pair the entry cannot align (the conditions of
+ * hvd_valign) gets the INT32_MIN record and contributes nothing; frame ranges are clamped to [0, offsets[V]] and every word
+ * index of the bitmap is checked against its length, so broken operands give wrong records, never an access out of bounds.
+ * HVD_ERR_ARG: what hvd_dev_vpdq_align_videos rejects, min_aligned < 1, n_frames outside [0, 2^32 - 2], a scratch smaller
+ * than the bitmap needs. M == 0 is legal: every video gets (0, 0, 0, frames). */
+int hvd_cover_scratch_bytes(int64_t n_frames, int64_t max_bins, size_t* out_bytes);
+int hvd_dev_vpdq_cover_videos(const void* d_hashes, const void* d_offsets, int64_t V, int64_t n_frames, const void* d_pos,
+                              const void* d_pairs, int64_t M, int max_dist, int slack, int min_aligned, void* d_scratch,
+                              size_t scratch_bytes, void* d_out_align, void* d_out_cover);
 
 /* Device-resident multi-segment alignment (the rule: hvd_vpdq_align_segments above). The operands of
  * hvd_dev_vpdq_align_videos, plus max_segments in [1, HVD_ALIGN_MAX_SEGMENTS] and min_band_votes >= 1 (HVD_ERR_ARG otherwise);
