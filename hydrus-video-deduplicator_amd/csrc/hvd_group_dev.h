@@ -1,9 +1,16 @@
 // hvd_group_dev.h -- what the kernels over a list of 16-byte edge records share, one definition: k_group.hip (connected
 // components) and k_keeper.hip (keeper-first groups) judge a record by the same predicate, take the
-// same number of records, and aggregate their atomics on one destination per wave the same way.
+// same number of records, and aggregate their atomics on one destination per wave the same way. Device code first; the last
+// section is host code, what the two launchers share: the grid of the grid-stride kernels, the min flag, the
+// choice of the kernels' record kind, and the launches that close either grouping with its group records.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <type_traits>
+
+#include "hvd_kernels.h"
+#include "hvd_scan_dev.h"
 
 namespace {
 
@@ -66,6 +73,43 @@ __device__ __forceinline__ void max_key(unsigned long long* arr, uint32_t dst, u
     } else if (active) {
         atomicMax(arr + dst, key);
     }
+}
+
+// ---- host code: what the two launchers share ---------------------------------------------------------------------------
+constexpr unsigned kMaxGrid = 16384;  // grid-stride kernels
+
+inline unsigned grid_for(unsigned long long n) {
+    const unsigned long long b = (n + 255ull) / 256ull;
+    return (unsigned)(b < 1 ? 1 : b > kMaxGrid ? kMaxGrid : b);
+}
+
+// workgroups of the block-sum pattern over the V nodes (hvd_scan_dev.h); the scratch holds one block sum more
+inline unsigned scan_blocks(unsigned long long V) { return (unsigned)((V + kScanBlk - 1) / kScanBlk); }
+
+// the is_min argument of every kernel over the records: the policy counts for the VMATCH predicate alone
+inline int min_flag(const hvd::EdgeList& in) { return in.kind == HVD_EDGES_VMATCH && in.is_min ? 1 : 0; }
+
+// launch(kind) enqueues one kernel over the records, kind a std::integral_constant<int, KIND>: the kernel's template argument.
+// An empty list gets no launch.
+template <class Launch>
+void launch_over_records(const hvd::EdgeList& in, Launch launch) {
+    if (in.n_records <= 0) return;
+    if (in.kind == HVD_EDGES_VMATCH)
+        launch(std::integral_constant<int, 1>{});
+    else
+        launch(std::integral_constant<int, 0>{});
+}
+
+// The group records, the close of either grouping: the nodes whose size is >= 2 counted block by block, the block sums scanned
+// (*d_count = the number of groups), then emit(nb): the caller's emit kernel, on the grid of k_keep_count.
+template <class Emit>
+hipError_t launch_group_records(uint32_t V, const uint32_t* size, uint32_t* sums, unsigned long long* d_count, hipStream_t s,
+                                Emit emit) {
+    const unsigned nb = scan_blocks(V);
+    hipLaunchKernelGGL(k_keep_count, dim3(nb), dim3(256), 0, s, (const int32_t*)size, (unsigned long long)V, 2, sums);
+    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, sums, nb, d_count);
+    emit(nb);
+    return hipGetLastError();
 }
 
 }  // namespace

@@ -299,24 +299,38 @@ inline bool pack_rate_list(const int32_t* rates, int n_rates, uint32_t* nums, ui
     return true;
 }
 
-// Duplicate groups with a keeper: connected components of a list of 16-byte records (k_group.hip). d_scratch:
-// group_scratch_bytes(V), 8-byte aligned; d_record_count: nullptr, or the uint64 an all-pairs pass counted its records in (the
-// kernels then take min(*d_record_count, n_records)); d_count: one uint64, receives the number of groups.
+// The two groupings over a list of 16-byte edge records: connected components (k_group.hip) and
+// keeper-first groups (k_keeper.hip) take the same operands and fill the same outputs.
+// EdgeList: the records in HBM, named and typed as by the C entries (group_on_device judges the ranges, the launchers narrow).
+// d_record_count: nullptr, or the uint64 an all-pairs pass counted its records in (the kernels then take min(*d_record_count,
+// n_records)); d_lengths, T, is_min: the pair predicate of HVD_EDGES_VMATCH; d_score: uint32 per node or nullptr.
+struct EdgeList {
+    const void* records;
+    int64_t n_records;
+    const unsigned long long* d_record_count;
+    int kind;
+    const long long* d_lengths;
+    int T;
+    bool is_min;
+    int64_t V;
+    const uint32_t* d_score;
+};
+// GroupsOut: scratch: group_scratch_bytes(V) or keeper_scratch_bytes(V), 8-byte aligned; node: int32 per node, the labels or
+// keeper_of; groups: room for cap records; count: one uint64, receives the number of groups.
+struct GroupsOut {
+    void* scratch;
+    int32_t* node;
+    hvd_group* groups;
+    int64_t cap;
+    unsigned long long* count;
+};
 size_t group_scratch_bytes(unsigned long long V);
-hipError_t launch_group_edges(const void* d_records, unsigned long long n_records, const unsigned long long* d_record_count,
-                              int kind, const long long* d_lengths, uint32_t T, bool is_min, uint32_t V, const uint32_t* d_score,
-                              void* d_scratch, int32_t* d_label, hvd_group* d_groups, unsigned long long cap,
-                              unsigned long long* d_count, hipStream_t s);
-
-// Keeper-first duplicate groups over the same records (k_keeper.hip). d_scratch: keeper_scratch_bytes(V), 8-byte
-// aligned. The rounds are enqueued in batches of 32 with the undecided count read back in between, so the call synchronises
+hipError_t launch_group_edges(const EdgeList& edges, const GroupsOut& out, hipStream_t s);
+// The keeper-first rounds are enqueued in batches of 32 with the undecided count read back in between, so the call synchronises
 // the stream; *settled: no node was left undecided within V rounds (else nothing else was launched); *rounds (may be nullptr):
 // the rounds that ran.
 size_t keeper_scratch_bytes(unsigned long long V);
-hipError_t launch_keeper_groups(const void* d_records, unsigned long long n_records, const unsigned long long* d_record_count,
-                                int kind, const long long* d_lengths, uint32_t T, bool is_min, uint32_t V, const uint32_t* d_score,
-                                void* d_scratch, int32_t* d_keeper, hvd_group* d_groups, unsigned long long cap,
-                                unsigned long long* d_count, hipStream_t s, long long* rounds, bool* settled);
+hipError_t launch_keeper_groups(const EdgeList& edges, const GroupsOut& out, hipStream_t s, long long* rounds, bool* settled);
 
 // Synthetic 64x64 gray video frames generated in HBM (k_synth.hip; workload generator, not on the hashing path).
 hipError_t launch_synth_frames64(uint8_t* d_out, long long v0, uint32_t frames_per_video, unsigned long long n_frames,

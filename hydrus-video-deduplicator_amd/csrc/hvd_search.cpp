@@ -1715,59 +1715,58 @@ static int check_group_shape(int64_t n_records, int kind, const void* lengths, i
     return HVD_OK;
 }
 
-int hvd_group_scratch_bytes(int64_t V, size_t* out_bytes) {
+static int group_scratch_entry(bool keeper_first, int64_t V, size_t* out_bytes) {
     if (!out_bytes || V < 1 || V >= (1ll << 31)) return fail(HVD_ERR_ARG, "V=%lld out of range [1,2^31)", (long long)V);
-    *out_bytes = hvd::group_scratch_bytes((unsigned long long)V);
+    *out_bytes = keeper_first ? hvd::keeper_scratch_bytes((unsigned long long)V) : hvd::group_scratch_bytes((unsigned long long)V);
+    return HVD_OK;
+}
+
+int hvd_group_scratch_bytes(int64_t V, size_t* out_bytes) { return group_scratch_entry(false, V, out_bytes); }
+int hvd_keeper_scratch_bytes(int64_t V, size_t* out_bytes) { return group_scratch_entry(true, V, out_bytes); }
+
+// The device form of both groupings: the checks, then the launches of k_group.hip, or of k_keeper.hip
+// (keeper_first; out_rounds may be nullptr) with the answer to rounds that did not settle.
+static int group_on_device(bool keeper_first, const hvd::EdgeList& edges, const hvd::GroupsOut& out, int64_t* out_rounds) {
+    if (int rc = need_ready()) return rc;
+    if (int rc = check_group_shape(edges.n_records, edges.kind, edges.d_lengths, edges.T, edges.V)) return rc;
+    if (!out.scratch || !out.node || !out.count || (edges.n_records > 0 && !edges.records) || out.cap < 0 || (out.cap > 0 && !out.groups))
+        return fail(HVD_ERR_ARG, "NULL device pointer / bad cap");
+    if ((((uintptr_t)edges.records | (uintptr_t)out.groups) & 15u) ||
+        (((uintptr_t)out.scratch | (uintptr_t)out.count | (uintptr_t)edges.d_record_count) & 7u))
+        return fail(HVD_ERR_ARG, "records and groups must be 16-byte aligned, scratch and counts 8-byte aligned");
+    if (!keeper_first) {
+        HIP_TRY(hvd::launch_group_edges(edges, out, g.stream));
+        return HVD_OK;
+    }
+    bool settled = false;
+    long long rounds = 0;
+    HIP_TRY(hvd::launch_keeper_groups(edges, out, g.stream, out_rounds ? &rounds : nullptr, &settled));
+    if (!settled)
+        return fail(HVD_ERR_STATE, "nodes left undecided after %lld rounds: every round decides one at least", (long long)edges.V);
+    if (out_rounds) *out_rounds = (int64_t)rounds;
     return HVD_OK;
 }
 
 int hvd_dev_group_edges(const void* d_records, int64_t n_records, const void* d_record_count, int kind, const void* d_lengths,
                         int threshold, int policy_is_min, int64_t V, const void* d_score, void* d_scratch, void* d_out_label,
                         void* d_out_groups, int64_t cap, void* d_out_count) {
-    if (int rc = need_ready()) return rc;
-    if (int rc = check_group_shape(n_records, kind, d_lengths, threshold, V)) return rc;
-    if (!d_scratch || !d_out_label || !d_out_count || (n_records > 0 && !d_records) || cap < 0 || (cap > 0 && !d_out_groups))
-        return fail(HVD_ERR_ARG, "NULL device pointer / bad cap");
-    if ((((uintptr_t)d_records | (uintptr_t)d_out_groups) & 15u) || (((uintptr_t)d_scratch | (uintptr_t)d_out_count | (uintptr_t)d_record_count) & 7u))
-        return fail(HVD_ERR_ARG, "records and groups must be 16-byte aligned, scratch and counts 8-byte aligned");
-    HIP_TRY(hvd::launch_group_edges(d_records, (unsigned long long)n_records, (const unsigned long long*)d_record_count, kind,
-                                    (const long long*)d_lengths, (uint32_t)threshold, policy_is_min != 0, (uint32_t)V,
-                                    (const uint32_t*)d_score, d_scratch, (int32_t*)d_out_label, (hvd_group*)d_out_groups,
-                                    (unsigned long long)cap, (unsigned long long*)d_out_count, g.stream));
-    return HVD_OK;
+    return group_on_device(false, {d_records, n_records, (const unsigned long long*)d_record_count, kind, (const long long*)d_lengths,
+                                   threshold, policy_is_min != 0, V, (const uint32_t*)d_score},
+                           {d_scratch, (int32_t*)d_out_label, (hvd_group*)d_out_groups, cap, (unsigned long long*)d_out_count}, nullptr);
 }
 
 /* ---- keeper-first duplicate groups: every member matches its keeper directly (k_keeper.hip) ---- */
 
-int hvd_keeper_scratch_bytes(int64_t V, size_t* out_bytes) {
-    if (!out_bytes || V < 1 || V >= (1ll << 31)) return fail(HVD_ERR_ARG, "V=%lld out of range [1,2^31)", (long long)V);
-    *out_bytes = hvd::keeper_scratch_bytes((unsigned long long)V);
-    return HVD_OK;
-}
-
 int hvd_dev_keeper_groups(const void* d_records, int64_t n_records, const void* d_record_count, int kind, const void* d_lengths,
                           int threshold, int policy_is_min, int64_t V, const void* d_score, void* d_scratch, void* d_out_keeper,
                           void* d_out_groups, int64_t cap, void* d_out_count, int64_t* out_rounds) {
-    if (int rc = need_ready()) return rc;
-    if (int rc = check_group_shape(n_records, kind, d_lengths, threshold, V)) return rc;
-    if (!d_scratch || !d_out_keeper || !d_out_count || (n_records > 0 && !d_records) || cap < 0 || (cap > 0 && !d_out_groups))
-        return fail(HVD_ERR_ARG, "NULL device pointer / bad cap");
-    if ((((uintptr_t)d_records | (uintptr_t)d_out_groups) & 15u) || (((uintptr_t)d_scratch | (uintptr_t)d_out_count | (uintptr_t)d_record_count) & 7u))
-        return fail(HVD_ERR_ARG, "records and groups must be 16-byte aligned, scratch and counts 8-byte aligned");
-    bool settled = false;
-    long long rounds = 0;
-    HIP_TRY(hvd::launch_keeper_groups(d_records, (unsigned long long)n_records, (const unsigned long long*)d_record_count, kind,
-                                      (const long long*)d_lengths, (uint32_t)threshold, policy_is_min != 0, (uint32_t)V,
-                                      (const uint32_t*)d_score, d_scratch, (int32_t*)d_out_keeper, (hvd_group*)d_out_groups,
-                                      (unsigned long long)cap, (unsigned long long*)d_out_count, g.stream,
-                                      out_rounds ? &rounds : nullptr, &settled));
-    if (!settled) return fail(HVD_ERR_STATE, "nodes left undecided after %lld rounds: every round decides one at least", (long long)V);
-    if (out_rounds) *out_rounds = (int64_t)rounds;
-    return HVD_OK;
+    return group_on_device(true, {d_records, n_records, (const unsigned long long*)d_record_count, kind, (const long long*)d_lengths,
+                                  threshold, policy_is_min != 0, V, (const uint32_t*)d_score},
+                           {d_scratch, (int32_t*)d_out_keeper, (hvd_group*)d_out_groups, cap, (unsigned long long*)d_out_count}, out_rounds);
 }
 
 // The host-array form of both groupings: everything is judged, the operands go up, the device entry runs, the node array and
-// the group records come down. keeper_first: hvd_dev_keeper_groups (out_node = keeper_of), else hvd_dev_group_edges (labels).
+// the group records come down. keeper_first: out_node = keeper_of, else the labels.
 static int groups_from_host(bool keeper_first, const void* records, int64_t E, int kind, const int64_t* lengths, int threshold,
                             int policy_is_min, int64_t V, const uint32_t* score, int32_t* out_node, hvd_group* out_groups,
                             int64_t cap, int64_t* out_count, int64_t* out_rounds) {
@@ -1800,10 +1799,9 @@ static int groups_from_host(bool keeper_first, const void* records, int64_t E, i
         HIP_TRY(hipMemcpyAsync(d_score, score, 4 * (size_t)V, hipMemcpyHostToDevice, g.stream));
     }
     void* d_groups = cap > 0 ? d_out + 16 : nullptr;
-    if (int rc = keeper_first ? hvd_dev_keeper_groups(d_rec, E, nullptr, kind, d_len, threshold, policy_is_min, V, d_score, d_scr,
-                                                      d_node, d_groups, cap, d_out, out_rounds)
-                              : hvd_dev_group_edges(d_rec, E, nullptr, kind, d_len, threshold, policy_is_min, V, d_score, d_scr, d_node,
-                                                    d_groups, cap, d_out))
+    if (int rc = group_on_device(keeper_first, {d_rec, E, nullptr, kind, (const long long*)d_len, threshold, policy_is_min != 0, V,
+                                                (const uint32_t*)d_score},
+                                 {d_scr, (int32_t*)d_node, (hvd_group*)d_groups, cap, (unsigned long long*)d_out}, out_rounds))
         return rc;
     unsigned long long count = 0;
     HIP_TRY(hipMemcpyAsync(&count, d_out, 8, hipMemcpyDeviceToHost, g.stream));

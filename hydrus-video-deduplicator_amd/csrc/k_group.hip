@@ -20,12 +20,8 @@
 #include <stdint.h>
 
 #include "hvd_group_dev.h"
-#include "hvd_kernels.h"
-#include "hvd_scan_dev.h"
 
 namespace {
-
-constexpr unsigned kMaxGrid = 16384;  // grid-stride kernels
 
 __device__ __forceinline__ uint32_t ld(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st(uint32_t* p, uint32_t x) { __hip_atomic_store(p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -121,54 +117,37 @@ __global__ __launch_bounds__(256) void k_group_emit(uint32_t V, const uint32_t* 
     }
 }
 
-unsigned grid_for(unsigned long long n) {
-    const unsigned long long b = (n + 255ull) / 256ull;
-    return (unsigned)(b < 1 ? 1 : b > kMaxGrid ? kMaxGrid : b);
-}
-
 }  // namespace
 
 namespace hvd {
 
 // key 8 V | parent, size, edges 4 V each | block sums 4 (ceil(V / 1024) + 1), rounded up to 16
-size_t group_scratch_bytes(unsigned long long V) {
-    const unsigned long long nb = (V + kScanBlk - 1) / kScanBlk;
-    return (size_t)((20ull * V + 4ull * (nb + 1) + 15ull) & ~15ull);
-}
+size_t group_scratch_bytes(unsigned long long V) { return (size_t)((20ull * V + 4ull * (scan_blocks(V) + 1) + 15ull) & ~15ull); }
 
-hipError_t launch_group_edges(const void* d_records, unsigned long long n_records, const unsigned long long* d_record_count,
-                              int kind, const long long* d_lengths, uint32_t T, bool is_min, uint32_t V, const uint32_t* d_score,
-                              void* d_scratch, int32_t* d_label, hvd_group* d_groups, unsigned long long cap,
-                              unsigned long long* d_count, hipStream_t s) {
-    const unsigned nb = (unsigned)(((unsigned long long)V + kScanBlk - 1) / kScanBlk);
-    unsigned long long* key = (unsigned long long*)d_scratch;
+hipError_t launch_group_edges(const EdgeList& in, const GroupsOut& out, hipStream_t s) {
+    const uint32_t V = (uint32_t)in.V, T = (uint32_t)in.T;
+    const unsigned long long n_records = (unsigned long long)in.n_records;
+    const int is_min = min_flag(in);
+    unsigned long long* key = (unsigned long long*)out.scratch;
     uint32_t* parent = (uint32_t*)(key + V);
     uint32_t* size = parent + V;
     uint32_t* edges = size + V;
     uint32_t* sums = edges + V;
-    const uint4* recs = (const uint4*)d_records;
+    const uint4* recs = (const uint4*)in.records;
     hipLaunchKernelGGL(k_group_init, dim3(grid_for(V)), dim3(256), 0, s, V, parent, size, edges, key);
-    if (n_records > 0) {
-        if (kind == HVD_EDGES_VMATCH)
-            hipLaunchKernelGGL(k_group_hook<1>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records, d_record_count, V,
-                               d_lengths, T, is_min ? 1 : 0, parent);
-        else
-            hipLaunchKernelGGL(k_group_hook<0>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records, d_record_count, V,
-                               d_lengths, T, 0, parent);
-    }
-    hipLaunchKernelGGL(k_group_flatten, dim3(grid_for(V)), dim3(256), 0, s, V, parent, d_score, d_label, size, key);
-    if (n_records > 0) {
-        if (kind == HVD_EDGES_VMATCH)
-            hipLaunchKernelGGL(k_group_count<1>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records, d_record_count, V,
-                               d_lengths, T, is_min ? 1 : 0, d_label, edges);
-        else
-            hipLaunchKernelGGL(k_group_count<0>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records, d_record_count, V,
-                               d_lengths, T, 0, d_label, edges);
-    }
-    hipLaunchKernelGGL(k_keep_count, dim3(nb), dim3(256), 0, s, (const int32_t*)size, (unsigned long long)V, 2, sums);
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, sums, nb, d_count);
-    hipLaunchKernelGGL(k_group_emit, dim3(nb), dim3(256), 0, s, V, size, edges, key, sums, (uint4*)d_groups, cap);
-    return hipGetLastError();
+    launch_over_records(in, [&](auto kind) {
+        hipLaunchKernelGGL(k_group_hook<decltype(kind)::value>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records,
+                           in.d_record_count, V, in.d_lengths, T, is_min, parent);
+    });
+    hipLaunchKernelGGL(k_group_flatten, dim3(grid_for(V)), dim3(256), 0, s, V, parent, in.d_score, out.node, size, key);
+    launch_over_records(in, [&](auto kind) {
+        hipLaunchKernelGGL(k_group_count<decltype(kind)::value>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records,
+                           in.d_record_count, V, in.d_lengths, T, is_min, out.node, edges);
+    });
+    return launch_group_records(V, size, sums, out.count, s, [&](unsigned nb) {
+        hipLaunchKernelGGL(k_group_emit, dim3(nb), dim3(256), 0, s, V, size, edges, key, sums, (uint4*)out.groups,
+                           (unsigned long long)out.cap);
+    });
 }
 
 }  // namespace hvd

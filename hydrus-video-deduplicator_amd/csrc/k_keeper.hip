@@ -26,12 +26,9 @@
 #include <stdint.h>
 
 #include "hvd_group_dev.h"
-#include "hvd_kernels.h"
-#include "hvd_scan_dev.h"
 
 namespace {
 
-constexpr unsigned kMaxGrid = 16384;  // grid-stride kernels, as k_group.hip
 constexpr uint32_t kUndecided = 0, kKeeper = 1, kMember = 2;
 constexpr uint32_t kCtlRounds = 3, kCtlWords = 4;  // behind count[0..2]
 constexpr uint32_t kBatch = 32;                    // rounds enqueued between two read-backs of the undecided count
@@ -175,11 +172,6 @@ __global__ __launch_bounds__(256) void k_keeper_emit(uint32_t V, const uint32_t*
     }
 }
 
-unsigned grid_for(unsigned long long n) {
-    const unsigned long long b = (n + 255ull) / 256ull;
-    return (unsigned)(b < 1 ? 1 : b > kMaxGrid ? kMaxGrid : b);
-}
-
 }  // namespace
 
 namespace hvd {
@@ -187,40 +179,33 @@ namespace hvd {
 // best 8 V | state, member stamp, blocked stamp, size, edges 4 V each | block sums 4 (ceil(V / 1024) + 1) | 4 control words,
 // rounded up to 16
 size_t keeper_scratch_bytes(unsigned long long V) {
-    const unsigned long long nb = (V + kScanBlk - 1) / kScanBlk;
-    return (size_t)((28ull * V + 4ull * (nb + 1) + 4ull * kCtlWords + 15ull) & ~15ull);
+    return (size_t)((28ull * V + 4ull * (scan_blocks(V) + 1) + 4ull * kCtlWords + 15ull) & ~15ull);
 }
 
-hipError_t launch_keeper_groups(const void* d_records, unsigned long long n_records, const unsigned long long* d_record_count,
-                                int kind, const long long* d_lengths, uint32_t T, bool is_min, uint32_t V, const uint32_t* d_score,
-                                void* d_scratch, int32_t* d_keeper, hvd_group* d_groups, unsigned long long cap,
-                                unsigned long long* d_count, hipStream_t s, long long* rounds, bool* settled) {
-    const unsigned nb = (unsigned)(((unsigned long long)V + kScanBlk - 1) / kScanBlk);
-    unsigned long long* best = (unsigned long long*)d_scratch;
+hipError_t launch_keeper_groups(const EdgeList& in, const GroupsOut& out, hipStream_t s, long long* rounds, bool* settled) {
+    const uint32_t V = (uint32_t)in.V, T = (uint32_t)in.T;
+    const unsigned long long n_records = (unsigned long long)in.n_records;
+    const int is_min = min_flag(in);
+    unsigned long long* best = (unsigned long long*)out.scratch;
     uint32_t* state = (uint32_t*)(best + V);
     uint32_t* member_stamp = state + V;
     uint32_t* blocked_stamp = member_stamp + V;
     uint32_t* size = blocked_stamp + V;
     uint32_t* edges = size + V;
     uint32_t* sums = edges + V;
-    uint32_t* ctl = sums + nb + 1;
-    const uint4* recs = (const uint4*)d_records;
-    const bool vmatch = kind == HVD_EDGES_VMATCH;
-    const int min_flag = vmatch && is_min ? 1 : 0;
+    uint32_t* ctl = sums + scan_blocks(V) + 1;
+    const uint4* recs = (const uint4*)in.records;
     *settled = false;
     hipLaunchKernelGGL(k_keeper_init, dim3(grid_for(V)), dim3(256), 0, s, V, state, member_stamp, blocked_stamp, size, edges, best, ctl);
     uint32_t undecided = V, round = 0;
     while (undecided != 0 && round < V) {
         for (uint32_t k = 0; k < kBatch; ++k) {
             ++round;
-            if (n_records > 0) {
-                if (vmatch)
-                    hipLaunchKernelGGL(k_keeper_edges<1>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records, d_record_count,
-                                       V, d_lengths, T, min_flag, d_score, state, member_stamp, blocked_stamp, ctl, round);
-                else
-                    hipLaunchKernelGGL(k_keeper_edges<0>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records, d_record_count,
-                                       V, d_lengths, T, 0, d_score, state, member_stamp, blocked_stamp, ctl, round);
-            }
+            launch_over_records(in, [&](auto kind) {
+                hipLaunchKernelGGL(k_keeper_edges<decltype(kind)::value>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records,
+                                   in.d_record_count, V, in.d_lengths, T, is_min, in.d_score, state, member_stamp, blocked_stamp, ctl,
+                                   round);
+            });
             hipLaunchKernelGGL(k_keeper_nodes, dim3(grid_for(V)), dim3(256), 0, s, V, state, member_stamp, blocked_stamp, ctl, round);
         }
         if (hipError_t e = hipGetLastError()) return e;
@@ -235,27 +220,19 @@ hipError_t launch_keeper_groups(const void* d_records, unsigned long long n_reco
         if (hipError_t e = hipStreamSynchronize(s)) return e;
         *rounds = (long long)ran;
     }
-    if (n_records > 0) {
-        if (vmatch)
-            hipLaunchKernelGGL(k_keeper_assign<1>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records, d_record_count, V,
-                               d_lengths, T, min_flag, d_score, state, best);
-        else
-            hipLaunchKernelGGL(k_keeper_assign<0>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records, d_record_count, V,
-                               d_lengths, T, 0, d_score, state, best);
-    }
-    hipLaunchKernelGGL(k_keeper_label, dim3(grid_for(V)), dim3(256), 0, s, V, state, best, d_keeper, size);
-    if (n_records > 0) {
-        if (vmatch)
-            hipLaunchKernelGGL(k_keeper_count<1>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records, d_record_count, V,
-                               d_lengths, T, min_flag, d_keeper, edges);
-        else
-            hipLaunchKernelGGL(k_keeper_count<0>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records, d_record_count, V,
-                               d_lengths, T, 0, d_keeper, edges);
-    }
-    hipLaunchKernelGGL(k_keep_count, dim3(nb), dim3(256), 0, s, (const int32_t*)size, (unsigned long long)V, 2, sums);
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(1024), 0, s, sums, nb, d_count);
-    hipLaunchKernelGGL(k_keeper_emit, dim3(nb), dim3(256), 0, s, V, size, edges, sums, (uint4*)d_groups, cap);
-    return hipGetLastError();
+    launch_over_records(in, [&](auto kind) {
+        hipLaunchKernelGGL(k_keeper_assign<decltype(kind)::value>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records,
+                           in.d_record_count, V, in.d_lengths, T, is_min, in.d_score, state, best);
+    });
+    hipLaunchKernelGGL(k_keeper_label, dim3(grid_for(V)), dim3(256), 0, s, V, state, best, out.node, size);
+    launch_over_records(in, [&](auto kind) {
+        hipLaunchKernelGGL(k_keeper_count<decltype(kind)::value>, dim3(grid_for(n_records)), dim3(256), 0, s, recs, n_records,
+                           in.d_record_count, V, in.d_lengths, T, is_min, out.node, edges);
+    });
+    return launch_group_records(V, size, sums, out.count, s, [&](unsigned nb) {
+        hipLaunchKernelGGL(k_keeper_emit, dim3(nb), dim3(256), 0, s, V, size, edges, sums, (uint4*)out.groups,
+                           (unsigned long long)out.cap);
+    });
 }
 
 }  // namespace hvd

@@ -1059,28 +1059,40 @@ def dedupe_frames_without_repeats_on_device(d_frames_ptr: int, raw_offsets: np.n
     return pairs, recs, dropped, timings
 
 
+def _groups_on_device(grouping, d_records_ptr, n_records, d_record_count_ptr, kind, d_lengths_ptr, T, is_min, V, d_score_ptr,
+                      accept=None):
+    """The device entry of `grouping` (search.COMPONENTS or search.KEEPER_FIRST) over records that lie in HBM, behind
+    group_records_on_device and keeper_groups_on_device -> (node array, groups, rounds), or None when accept() refused; rounds
+    stays 0 where the entry reports none."""
+    lib = _lib.ensure()
+    sb = C.c_size_t(0)
+    _lib.check(getattr(lib, grouping.scratch_entry)(V, C.byref(sb)))
+    cap = max(1, min(V // 2, n_records))  # a group has two members and one record at least
+    rounds = C.c_int64(0)
+    with _DeviceScope() as scope:
+        d_scr, d_node = scope.temp(DeviceBuffer(sb.value)), scope.temp(DeviceBuffer(4 * V))
+        d_groups, d_cnt = scope.temp(DeviceBuffer(16 * cap)), scope.temp(DeviceBuffer(8))
+        _lib.check(getattr(lib, grouping.device_entry)(
+            d_records_ptr, n_records, d_record_count_ptr, kind, d_lengths_ptr, T, int(is_min), V, d_score_ptr, d_scr.ptr, d_node.ptr,
+            d_groups.ptr, cap, d_cnt.ptr, *((C.byref(rounds),) if grouping.rounds else ())))
+        out = None
+        if accept is None or accept():
+            count = int(d_cnt.to_array(np.uint64, 1)[0])  # (the copy waits for the library stream)
+            assert count <= cap
+            out = d_node.to_array(np.int32, V), d_groups.to_array(GROUP_DTYPE, count), rounds.value
+        _lib.check(lib.hvd_dev_sync())  # nothing may still run on a buffer that is freed here
+    return out
+
+
 def group_records_on_device(d_records_ptr: int, n_records: int, d_record_count_ptr, V: int, d_score_ptr=None,
                             accept=None) -> tuple[np.ndarray, np.ndarray] | None:
     """hvd_dev_group_edges (HVD_EDGES_ALL) over records that lie in HBM -> (labels, groups) as search.group_edges returns them;
     only those cross PCIe. d_record_count_ptr: None, or the uint64 an all-pairs entry counted its records in: the grouping is
     then enqueued behind that pass with no read-back in between and takes min(count, n_records) records. accept(): called after
     the launches and before anything is downloaded; returning False drops the result (-> None)."""
-    lib = _lib.ensure()
-    sb = C.c_size_t(0)
-    _lib.check(lib.hvd_group_scratch_bytes(V, C.byref(sb)))
-    cap = max(1, min(V // 2, n_records))  # a group has two members and one record at least
-    with _DeviceScope() as scope:
-        d_scr, d_label = scope.temp(DeviceBuffer(sb.value)), scope.temp(DeviceBuffer(4 * V))
-        d_groups, d_cnt = scope.temp(DeviceBuffer(16 * cap)), scope.temp(DeviceBuffer(8))
-        _lib.check(lib.hvd_dev_group_edges(d_records_ptr, n_records, d_record_count_ptr, _lib.EDGES_ALL, None, 0, 0, V, d_score_ptr,
-                                           d_scr.ptr, d_label.ptr, d_groups.ptr, cap, d_cnt.ptr))
-        out = None
-        if accept is None or accept():
-            count = int(d_cnt.to_array(np.uint64, 1)[0])  # (the copy waits for the library stream)
-            assert count <= cap
-            out = d_label.to_array(np.int32, V), d_groups.to_array(GROUP_DTYPE, count)
-        _lib.check(lib.hvd_dev_sync())  # nothing may still run on a buffer that is freed here
-    return out
+    out = _groups_on_device(search.COMPONENTS, d_records_ptr, n_records, d_record_count_ptr, _lib.EDGES_ALL, None, 0, False, V,
+                            d_score_ptr, accept)
+    return None if out is None else out[:2]
 
 
 def cluster_hashes_on_device(d_db_ptr: int, n: int, max_dist: int = search.DISTANCE_TOLERANCE, pair_cap: int | None = None,
@@ -1123,23 +1135,29 @@ def cluster_hashes_on_device(d_db_ptr: int, n: int, max_dist: int = search.DISTA
             cap = found
 
 
-def find_duplicate_groups_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
-                                    threshold: float = 50.0, policy: str | None = None, score=None, keep_library: bool = False):
-    """search.find_duplicate_groups on frames in HBM, one device: the chain of `dedupe_frames_on_device` (hash -> quality filter
-    + CSR -> video search), then search.group_records over its records with the library's kept lengths: the pair predicate and
-    the grouping run on the device. score: uint32 per video for the keeper; default the number of kept frames.
-    -> (duplicate groups, labels, group records, library or None)."""
+def _find_groups_on_device(grouping, d_frames_ptr, raw_offsets, h, w, channels, threshold, policy, score, keep_library):
+    """The chain behind find_duplicate_groups_on_device and find_keeper_groups_on_device: `dedupe_frames_on_device`, the kept
+    lengths, the grouping of its records, the fold -> (groups as the fold gives them, node array, group records, library or None)."""
     _, recs, library = dedupe_frames_on_device(d_frames_ptr, raw_offsets, h, w, channels, threshold, policy, keep_library=True)
     try:
         lengths = library.lengths()
-        labels, groups = search.group_records(recs, lengths, threshold, policy, lengths if score is None else score)
+        node, groups = search._grouped_records(grouping, recs, lengths, threshold, policy, lengths if score is None else score)
     except BaseException:
         library.free()
         raise
     if not keep_library:
         library.free()
         library = None
-    return search.groups_from_labels(labels, groups), labels, groups, library
+    return grouping.fold(node, groups), node, groups, library
+
+
+def find_duplicate_groups_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                    threshold: float = 50.0, policy: str | None = None, score=None, keep_library: bool = False):
+    """search.find_duplicate_groups on frames in HBM, one device: the chain of `dedupe_frames_on_device` (hash -> quality filter
+    + CSR -> video search), then search.group_records over its records with the library's kept lengths: the pair predicate and
+    the grouping run on the device. score: uint32 per video for the keeper; default the number of kept frames.
+    -> (duplicate groups, labels, group records, library or None)."""
+    return _find_groups_on_device(search.COMPONENTS, d_frames_ptr, raw_offsets, h, w, channels, threshold, policy, score, keep_library)
 
 
 def keeper_groups_on_device(d_records_ptr: int, n_records: int, d_record_count_ptr, V: int, d_score_ptr=None,
@@ -1147,21 +1165,8 @@ def keeper_groups_on_device(d_records_ptr: int, n_records: int, d_record_count_p
     """hvd_dev_keeper_groups over records that lie in HBM -> (keeper_of, groups, rounds): the first two as
     search.keeper_groups returns them, only those cross PCIe; rounds: how many rounds the keepers took. d_record_count_ptr as for
     `group_records_on_device`; the entry itself waits for the stream between its batches of rounds."""
-    lib = _lib.ensure()
-    sb = C.c_size_t(0)
-    _lib.check(lib.hvd_keeper_scratch_bytes(V, C.byref(sb)))
-    cap = max(1, min(V // 2, n_records))  # a group has two nodes and one record at least
-    rounds = C.c_int64(0)
-    with _DeviceScope() as scope:
-        d_scr, d_keeper = scope.temp(DeviceBuffer(sb.value)), scope.temp(DeviceBuffer(4 * V))
-        d_groups, d_cnt = scope.temp(DeviceBuffer(16 * cap)), scope.temp(DeviceBuffer(8))
-        _lib.check(lib.hvd_dev_keeper_groups(d_records_ptr, n_records, d_record_count_ptr, kind, d_lengths_ptr, T, int(is_min), V,
-                                             d_score_ptr, d_scr.ptr, d_keeper.ptr, d_groups.ptr, cap, d_cnt.ptr, C.byref(rounds)))
-        count = int(d_cnt.to_array(np.uint64, 1)[0])  # (the copy waits for the library stream)
-        assert count <= cap
-        out = d_keeper.to_array(np.int32, V), d_groups.to_array(GROUP_DTYPE, count), rounds.value
-        _lib.check(lib.hvd_dev_sync())  # nothing may still run on a buffer that is freed here
-    return out
+    return _groups_on_device(search.KEEPER_FIRST, d_records_ptr, n_records, d_record_count_ptr, kind, d_lengths_ptr, T, is_min, V,
+                             d_score_ptr)
 
 
 def find_keeper_groups_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
@@ -1169,17 +1174,7 @@ def find_keeper_groups_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: 
     """search.find_keeper_groups on frames in HBM, one device: the chain of `dedupe_frames_on_device`, then
     search.keeper_group_records over its records with the library's kept lengths. score: uint32 per video, the larger is kept;
     default the number of kept frames. -> (keeper groups, keeper_of, group records, library or None)."""
-    _, recs, library = dedupe_frames_on_device(d_frames_ptr, raw_offsets, h, w, channels, threshold, policy, keep_library=True)
-    try:
-        lengths = library.lengths()
-        keeper_of, groups = search.keeper_group_records(recs, lengths, threshold, policy, lengths if score is None else score)
-    except BaseException:
-        library.free()
-        raise
-    if not keep_library:
-        library.free()
-        library = None
-    return search.keeper_groups_from(keeper_of, groups), keeper_of, groups, library
+    return _find_groups_on_device(search.KEEPER_FIRST, d_frames_ptr, raw_offsets, h, w, channels, threshold, policy, score, keep_library)
 
 
 def _aligned_search_on_device(mode, d_frames_ptr, raw_offsets, h, w, channels, threshold, min_aligned, slack, positions, keep_library):

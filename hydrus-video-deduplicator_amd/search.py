@@ -1023,8 +1023,16 @@ def _score_array(score, V: int) -> np.ndarray | None:
     return np.ascontiguousarray(score, dtype=np.uint32)
 
 
-def _group(records: np.ndarray, kind: int, lengths, T: int, is_min: bool, V: int, score) -> tuple[np.ndarray, np.ndarray]:
-    """hvd_group_edges -> (labels int32[V], GROUP_DTYPE records sorted by root)."""
+# Which of the two groupings a call is -- COMPONENTS (4.11) or KEEPER_FIRST (4.14), below the two folds -- and all
+# that differs between them above the kernels: the host, device and scratch-size entries of the C ABI, whether those entries
+# take the trailing out_rounds, and the fold of (node array, group records) into result tuples.
+Grouping = namedtuple("Grouping", "host_entry device_entry scratch_entry rounds fold")
+
+
+def _grouped(grouping: Grouping, records: np.ndarray, kind: int, lengths, T: int, is_min: bool, V: int,
+             score) -> tuple[np.ndarray, np.ndarray]:
+    """The host entry of `grouping` -> (node array int32[V], GROUP_DTYPE records sorted by root): the labels of the components,
+    keeper_of of the keeper-first groups."""
     score = _score_array(score, V)
     if V == 0:
         if records.size:
@@ -1032,29 +1040,18 @@ def _group(records: np.ndarray, kind: int, lengths, T: int, is_min: bool, V: int
         return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=GROUP_DTYPE)
     E = records.shape[0]
     cap = min(V // 2, E)  # a group has two members and one record at least
-    labels = np.empty(V, dtype=np.int32)
+    node = np.empty(V, dtype=np.int32)
     groups = np.zeros(max(cap, 1), dtype=GROUP_DTYPE)
     cnt = C.c_int64(0)
     lib = _lib.ensure()
-    _lib.check(lib.hvd_group_edges(_ptr(records), E, kind, _ptr(lengths), T, int(is_min), V, _ptr(score), labels.ctypes.data,
-                                   groups.ctypes.data, cap, C.byref(cnt)))
-    return labels, groups[: cnt.value].copy()
+    _lib.check(getattr(lib, grouping.host_entry)(_ptr(records), E, kind, _ptr(lengths), T, int(is_min), V, _ptr(score), node.ctypes.data,
+                                                 groups.ctypes.data, cap, C.byref(cnt), *((None,) if grouping.rounds else ())))
+    return node, groups[: cnt.value].copy()
 
 
-def group_edges(edges, V: int, score=None) -> tuple[np.ndarray, np.ndarray]:
-    """Connected components of a pair list on the GPU (hvd_group_edges, HVD_EDGES_ALL): `edges` are the records of a search or
-    int[M, 2] rows (see `edge_records`) over nodes 0..V-1, either orientation, repeats allowed. -> (labels, groups): labels
-    int32[V], labels[v] = the smallest index in v's component; groups: one GROUP_DTYPE record (root, size, edges, keeper) per
-    component of two or more nodes, sorted by root. keeper: the member with the largest score (uint32 per node; default all 0),
-    ties to the smaller index."""
-    return _group(edge_records(edges), _lib.EDGES_ALL, None, 0, False, int(V), score)
-
-
-def group_records(records: np.ndarray, lengths: np.ndarray, threshold: float = 50.0, policy: str | None = None,
-                  score=None) -> tuple[np.ndarray, np.ndarray]:
-    """The groups of a video search: `group_edges` over the VMATCH records that pass the pair predicate of
-    `similar_video_pairs` (hvd_group_edges, HVD_EDGES_VMATCH: the same rows, chosen in integers on the device). lengths: frames
-    per video, one node each. -> (labels, groups)."""
+def _grouped_records(grouping: Grouping, records, lengths, threshold, policy, score) -> tuple[np.ndarray, np.ndarray]:
+    """The call behind group_records and keeper_group_records: policy and threshold judged, the VMATCH records and the lengths
+    as the entries read them."""
     policy = vpdq.MATCH_POLICY if policy is None else policy
     if policy not in ("min", "max", "query", "target"):
         raise ValueError(f"unknown match policy {policy!r}")
@@ -1064,9 +1061,32 @@ def group_records(records: np.ndarray, lengths: np.ndarray, threshold: float = 5
     records = np.ascontiguousarray(records, dtype=VMATCH_DTYPE).reshape(-1)
     lengths = np.ascontiguousarray(lengths, dtype=np.int64)
     V = lengths.shape[0]
-    if T > 100:  # no similarity is above 100: every video on its own
+    if T > 100:  # no similarity is above 100: every video on its own, its own keeper
         return np.arange(V, dtype=np.int32), np.zeros(0, dtype=GROUP_DTYPE)
-    return _group(records, _lib.EDGES_VMATCH, lengths, T, policy == "min", V, score)
+    return _grouped(grouping, records, _lib.EDGES_VMATCH, lengths, T, policy == "min", V, score)
+
+
+def _find_groups(grouping: Grouping, video_hashes, threshold, policy, score, weights, max_weight) -> list:
+    """The search behind find_duplicate_groups and find_keeper_groups."""
+    recs, lengths = _library_search(video_hashes, weights, max_weight)
+    return grouping.fold(*_grouped_records(grouping, recs, lengths, threshold, policy, lengths if score is None else score))
+
+
+def group_edges(edges, V: int, score=None) -> tuple[np.ndarray, np.ndarray]:
+    """Connected components of a pair list on the GPU (hvd_group_edges, HVD_EDGES_ALL): `edges` are the records of a search or
+    int[M, 2] rows (see `edge_records`) over nodes 0..V-1, either orientation, repeats allowed. -> (labels, groups): labels
+    int32[V], labels[v] = the smallest index in v's component; groups: one GROUP_DTYPE record (root, size, edges, keeper) per
+    component of two or more nodes, sorted by root. keeper: the member with the largest score (uint32 per node; default all 0),
+    ties to the smaller index."""
+    return _grouped(COMPONENTS, edge_records(edges), _lib.EDGES_ALL, None, 0, False, int(V), score)
+
+
+def group_records(records: np.ndarray, lengths: np.ndarray, threshold: float = 50.0, policy: str | None = None,
+                  score=None) -> tuple[np.ndarray, np.ndarray]:
+    """The groups of a video search: `group_edges` over the VMATCH records that pass the pair predicate of
+    `similar_video_pairs` (hvd_group_edges, HVD_EDGES_VMATCH: the same rows, chosen in integers on the device). lengths: frames
+    per video, one node each. -> (labels, groups)."""
+    return _grouped_records(COMPONENTS, records, lengths, threshold, policy, score)
 
 
 def groups_from_labels(labels: np.ndarray, groups: np.ndarray) -> list:
@@ -1092,32 +1112,12 @@ def find_duplicate_groups(video_hashes, threshold: float = 50.0, policy: str | N
     largest score, ties to the smaller index; default: the number of kept frames, so the longest copy is kept -- pass
     resolution, file size or bitrate to keep by those. weights / max_weight: as `find_potential_duplicates`; the capped weight
     totals then stand for the frame counts, in the predicate and as the default score."""
-    recs, lengths = _library_search(video_hashes, weights, max_weight)
-    labels, groups = group_records(recs, lengths, threshold, policy, lengths if score is None else score)
-    return groups_from_labels(labels, groups)
+    return _find_groups(COMPONENTS, video_hashes, threshold, policy, score, weights, max_weight)
 
 
 # ------------------------------------------------ keeper-first groups: every member matches its keeper (DESIGN 4.14) ------
 
 KeeperGroup = namedtuple("KeeperGroup", "keeper members edges complete")
-
-
-def _keeper(records: np.ndarray, kind: int, lengths, T: int, is_min: bool, V: int, score) -> tuple[np.ndarray, np.ndarray]:
-    """hvd_keeper_groups -> (keeper_of int32[V], GROUP_DTYPE records sorted by keeper)."""
-    score = _score_array(score, V)
-    if V == 0:
-        if records.size:
-            raise ValueError("records without a node")
-        return np.zeros(0, dtype=np.int32), np.zeros(0, dtype=GROUP_DTYPE)
-    E = records.shape[0]
-    cap = min(V // 2, E)  # a group has two nodes and one record at least
-    keeper_of = np.empty(V, dtype=np.int32)
-    groups = np.zeros(max(cap, 1), dtype=GROUP_DTYPE)
-    cnt = C.c_int64(0)
-    lib = _lib.ensure()
-    _lib.check(lib.hvd_keeper_groups(_ptr(records), E, kind, _ptr(lengths), T, int(is_min), V, _ptr(score), keeper_of.ctypes.data,
-                                     groups.ctypes.data, cap, C.byref(cnt), None))
-    return keeper_of, groups[: cnt.value].copy()
 
 
 def keeper_groups(edges, V: int, score=None) -> tuple[np.ndarray, np.ndarray]:
@@ -1126,25 +1126,14 @@ def keeper_groups(edges, V: int, score=None) -> tuple[np.ndarray, np.ndarray]:
     -> (keeper_of, groups): keeper_of int32[V], keeper_of[v] = the keeper v is a direct match of (v itself for a keeper);
     groups: one GROUP_DTYPE record (root = keeper, size, edges, keeper) per keeper with a member, sorted by keeper. Unlike the
     components of `group_edges`, every member pairs with its keeper and no two keepers pair."""
-    return _keeper(edge_records(edges), _lib.EDGES_ALL, None, 0, False, int(V), score)
+    return _grouped(KEEPER_FIRST, edge_records(edges), _lib.EDGES_ALL, None, 0, False, int(V), score)
 
 
 def keeper_group_records(records: np.ndarray, lengths: np.ndarray, threshold: float = 50.0, policy: str | None = None,
                          score=None) -> tuple[np.ndarray, np.ndarray]:
     """`keeper_groups` over the VMATCH records that pass the pair predicate of `similar_video_pairs` (hvd_keeper_groups,
     HVD_EDGES_VMATCH), as `group_records` is to `group_edges`. -> (keeper_of, groups)."""
-    policy = vpdq.MATCH_POLICY if policy is None else policy
-    if policy not in ("min", "max", "query", "target"):
-        raise ValueError(f"unknown match policy {policy!r}")
-    T = int(threshold)
-    if T < 1:
-        raise ValueError("threshold < 1 would select every pair of videos")
-    records = np.ascontiguousarray(records, dtype=VMATCH_DTYPE).reshape(-1)
-    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
-    V = lengths.shape[0]
-    if T > 100:  # no similarity is above 100: every video its own keeper
-        return np.arange(V, dtype=np.int32), np.zeros(0, dtype=GROUP_DTYPE)
-    return _keeper(records, _lib.EDGES_VMATCH, lengths, T, policy == "min", V, score)
+    return _grouped_records(KEEPER_FIRST, records, lengths, threshold, policy, score)
 
 
 def keeper_groups_from(keeper_of: np.ndarray, groups: np.ndarray) -> list:
@@ -1163,15 +1152,17 @@ def keeper_groups_from(keeper_of: np.ndarray, groups: np.ndarray) -> list:
     return out
 
 
+COMPONENTS = Grouping("hvd_group_edges", "hvd_dev_group_edges", "hvd_group_scratch_bytes", False, groups_from_labels)
+KEEPER_FIRST = Grouping("hvd_keeper_groups", "hvd_dev_keeper_groups", "hvd_keeper_scratch_bytes", True, keeper_groups_from)
+
+
 def find_keeper_groups(video_hashes, threshold: float = 50.0, policy: str | None = None, score=None, weights=None,
                        max_weight: int = 0) -> list:
     """find_potential_duplicates as groups that can be acted on: [KeeperGroup(keeper, members, edges, complete)] sorted by
     keeper, where every member is itself one of the keeper's pairs, and no pair is left among the videos that remain once every
     member is removed. score (uint32 per video): the larger is kept, ties to the smaller index; default: the number of kept
     frames, as in `find_duplicate_groups`. weights / max_weight: as there."""
-    recs, lengths = _library_search(video_hashes, weights, max_weight)
-    keeper_of, groups = keeper_group_records(recs, lengths, threshold, policy, lengths if score is None else score)
-    return keeper_groups_from(keeper_of, groups)
+    return _find_groups(KEEPER_FIRST, video_hashes, threshold, policy, score, weights, max_weight)
 
 
 def cluster_hashes(db: np.ndarray, max_dist: int = DISTANCE_TOLERANCE, score=None) -> tuple[np.ndarray, np.ndarray]:

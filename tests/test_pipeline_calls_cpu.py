@@ -2,7 +2,9 @@
 dedupe_transformed_frames_on_device, find_excerpts_on_device), without a GPU: the library handle is replaced by a recorder
 that answers every call with HVD_OK, and the calls it saw are held against lists recorded the same way on the commit
 before the entries were folded onto shared helpers. An extra hvd_dev_sync, hvd_dev_malloc or read-back in the layer
-above the C-ABI shows up here before it shows up in a benchmark."""
+above the C-ABI shows up here before it shows up in a benchmark. The four grouping cases (find_duplicate_groups_on_device,
+find_keeper_groups_on_device, group_records_on_device, keeper_groups_on_device) were recorded the same way on the parent of
+the commit that put the two groupings behind one helper each, not on that commit's code."""
 import ctypes as C
 
 import numpy as np
@@ -16,7 +18,8 @@ class Recorder:
     """Stands in for the loaded library: logs "name(arguments)" per call. Device addresses are (k + 1) << 48 for the k-th
     allocation and are logged as dk (+ offset), host pointers as "host", by-reference outputs as "&"."""
 
-    SCRATCH = ("hvd_pdq_scratch_bytes", "hvd_pdq_rects_scratch_bytes", "hvd_align_scratch_bytes")
+    SCRATCH = ("hvd_pdq_scratch_bytes", "hvd_pdq_rects_scratch_bytes", "hvd_align_scratch_bytes", "hvd_group_scratch_bytes",
+               "hvd_keeper_scratch_bytes")
 
     def __init__(self, signatures, failing=None):
         self.signatures, self.calls, self.allocated, self.failing = signatures, [], 0, failing
@@ -24,9 +27,9 @@ class Recorder:
     def show(self, value, ctype):
         if value is not None and not isinstance(value, (int, bytes, np.integer)):
             return "&"
+        if value is None:  # (also a typed pointer that is not given: out_rounds)
+            return "None"
         if ctype is C.c_void_p:
-            if value is None:
-                return "None"
             if value < 1 << 48:
                 return "host"
             k, off = (value >> 48) - 1, value & ((1 << 48) - 1)
@@ -107,6 +110,12 @@ CASES = {
     "mirror_rank1_of_2": lambda P, d: mirror(P, d, **group_exchange()),
     "excerpts": excerpts,
     "excerpts_kept_index": lambda P, d: excerpts(P, d, positions=False),
+    # the two groupings: the chains on RAW_OFFSETS, and the resident calls over a fake list of two records with
+    # V = 4 -- the frame buffer d0 stands for the records, places inside it for the count, the scores and the lengths
+    "duplicate_groups_kept": lambda P, d: P.find_duplicate_groups_on_device(d, RAW_OFFSETS, H, W, 1, keep_library=True),
+    "keeper_groups": lambda P, d: P.find_keeper_groups_on_device(d, RAW_OFFSETS, H, W, 1),
+    "group_resident": lambda P, d: P.group_records_on_device(d, 2, d + 32, 4, d + 64),
+    "keeper_resident": lambda P, d: P.keeper_groups_on_device(d, 2, None, 4, d + 64, kind=1, d_lengths_ptr=d + 96, T=50, is_min=True),
 }
 
 # Recorded with this recorder on the commit before the fold (the parent of the one that added this file), not on the code
@@ -497,6 +506,99 @@ EXPECTED = {
         hvd_dev_free(d6)
         hvd_dev_free(d7)
         hvd_dev_free(d10)
+    """,
+    # the grouping functions: recorded the same way on the parent of the commit that folded them (DESIGN 4.24)
+    "duplicate_groups_kept": """
+        hvd_dev_malloc(&, 288)
+        hvd_dev_malloc(&, 36)
+        hvd_pdq_scratch_bytes(9, 64, 64, 1, &)
+        hvd_dev_malloc(&, 4096)
+        hvd_dev_pdq_hash_frames(d0, 9, 64, 64, 1, d3, d1, d2)
+        hvd_dev_sync()
+        hvd_dev_free(d3)
+        hvd_dev_malloc(&, 32)
+        hvd_memcpy_h2d(d4, host, 32)
+        hvd_dev_malloc(&, 288)
+        hvd_dev_malloc(&, 32)
+        hvd_dev_malloc(&, 36)
+        hvd_dev_compact_kept(d1, d2, 9, d4, 3, 31, d5, d6, d7, &)
+        hvd_dev_free(d4)
+        hvd_dev_free(d1)
+        hvd_dev_free(d2)
+        hvd_get_context()
+        hvd_get_context()
+        hvd_dev_malloc(&, 65536)
+        hvd_dev_malloc(&, 8)
+        hvd_fp4_image_bytes(9, &)
+        hvd_dev_malloc(&, 0)
+        hvd_dev_expand_fp4(d5, 9, d10)
+        hvd_dev_vpdq_match_videos(d10, 9, d7, 31, 0, 1, d8, 4096, d9)
+        hvd_memcpy_d2h(host, d9, 8)
+        hvd_memcpy_d2h(host, d6, 32)
+        hvd_group_edges(None, 0, 1, host, 50, 1, 3, host, host, host, 0, &)
+    """,
+    "keeper_groups": """
+        hvd_dev_malloc(&, 288)
+        hvd_dev_malloc(&, 36)
+        hvd_pdq_scratch_bytes(9, 64, 64, 1, &)
+        hvd_dev_malloc(&, 4096)
+        hvd_dev_pdq_hash_frames(d0, 9, 64, 64, 1, d3, d1, d2)
+        hvd_dev_sync()
+        hvd_dev_free(d3)
+        hvd_dev_malloc(&, 32)
+        hvd_memcpy_h2d(d4, host, 32)
+        hvd_dev_malloc(&, 288)
+        hvd_dev_malloc(&, 32)
+        hvd_dev_malloc(&, 36)
+        hvd_dev_compact_kept(d1, d2, 9, d4, 3, 31, d5, d6, d7, &)
+        hvd_dev_free(d4)
+        hvd_dev_free(d1)
+        hvd_dev_free(d2)
+        hvd_get_context()
+        hvd_get_context()
+        hvd_dev_malloc(&, 65536)
+        hvd_dev_malloc(&, 8)
+        hvd_fp4_image_bytes(9, &)
+        hvd_dev_malloc(&, 0)
+        hvd_dev_expand_fp4(d5, 9, d10)
+        hvd_dev_vpdq_match_videos(d10, 9, d7, 31, 0, 1, d8, 4096, d9)
+        hvd_memcpy_d2h(host, d9, 8)
+        hvd_memcpy_d2h(host, d6, 32)
+        hvd_keeper_groups(None, 0, 1, host, 50, 1, 3, host, host, host, 0, &, None)
+        hvd_dev_free(d5)
+        hvd_dev_free(d6)
+        hvd_dev_free(d7)
+        hvd_dev_free(d10)
+    """,
+    "group_resident": """
+        hvd_group_scratch_bytes(4, &)
+        hvd_dev_malloc(&, 4096)
+        hvd_dev_malloc(&, 16)
+        hvd_dev_malloc(&, 32)
+        hvd_dev_malloc(&, 8)
+        hvd_dev_group_edges(d0, 2, d0+32, 0, None, 0, 0, 4, d0+64, d1, d2, d3, 2, d4)
+        hvd_memcpy_d2h(host, d4, 8)
+        hvd_memcpy_d2h(host, d2, 16)
+        hvd_dev_sync()
+        hvd_dev_free(d1)
+        hvd_dev_free(d2)
+        hvd_dev_free(d3)
+        hvd_dev_free(d4)
+    """,
+    "keeper_resident": """
+        hvd_keeper_scratch_bytes(4, &)
+        hvd_dev_malloc(&, 4096)
+        hvd_dev_malloc(&, 16)
+        hvd_dev_malloc(&, 32)
+        hvd_dev_malloc(&, 8)
+        hvd_dev_keeper_groups(d0, 2, None, 1, d0+96, 50, 1, 4, d0+64, d1, d2, d3, 2, d4, &)
+        hvd_memcpy_d2h(host, d4, 8)
+        hvd_memcpy_d2h(host, d2, 16)
+        hvd_dev_sync()
+        hvd_dev_free(d1)
+        hvd_dev_free(d2)
+        hvd_dev_free(d3)
+        hvd_dev_free(d4)
     """,
 }
 
