@@ -11,7 +11,7 @@ from .hashing import compute_phash, decode_phash_from_str, encode_phash_to_str, 
 from .search import (allpairs_hamming, calculate_distance, find_compilations, find_cropped_duplicates, find_duplicate_groups,  # noqa: F401
                      find_excerpts,
                      find_keeper_groups, find_new_duplicates, find_potential_duplicates,
-                     find_rate_excerpts, find_rate_segmented_excerpts, find_segmented_excerpts, find_transformed_duplicates,
+                     find_rate_excerpts, find_rate_segmented_excerpts, find_reversed_excerpts, find_segmented_excerpts, find_transformed_duplicates,
                      fix_vpdq_similarity,
                      match_videos, without_common_frames, without_repeated_frames)
 from .vpdq import VideoHasher, VpdqHash, matchHash, matchHashBytes  # noqa: F401

@@ -210,19 +210,30 @@ hipError_t launch_video_weights(const int32_t* d_weight, const long long* d_offs
 
 // Time alignment of listed video pairs: one offset per pair (k_valign.hip, 4.8), up to eight (k_valign_segments.hip,
 // 4.9), one line at the best of the listed rates (k_valign_rates.hip, 4.10), rate x segments (k_valign_rate_segments.hip, 4.18).
-// AlignMode says which of the four a call is and carries what only some of them take; everything that differs between them on
+// A fifth, rate x segments with negative numerators for clips played backwards (k_valign_signed.hip, 4.25), came later.
+// AlignMode says which of them a call is and carries what only some of them take; everything that differs between them on
 // the host is read off it.
 struct AlignMode {
     uint32_t nums, dens;               // rated: the packed list (pack_rate_list below); 0, 0: a broken list
     int max_segments, min_band_votes;  // segmented: as the caller gave them (check_segment_limits judges them)
     bool rated, segmented;
     bool args_first;  // the host entry judges its arguments before the library's state (the rate entries), not after
+    // signed_: rate x segments with negative numerators (k_valign_signed.hip; `signed` is a keyword). nums and
+    // dens then hold |num| and den, and bit r of revs says that entry r is negative (pack_signed_rate_list below).
+    bool signed_ = false;
+    uint32_t revs = 0u;
     static AlignMode of(bool rated, bool segmented, int max_segments = 0, int min_band_votes = 1) {
         return {0u, 0u, max_segments, min_band_votes, rated, segmented, rated};
     }
-    unsigned kind() const { return (rated ? 2u : 0u) + (segmented ? 1u : 0u); }
+    static AlignMode of_signed(int max_segments, int min_band_votes) {
+        AlignMode m = of(true, true, max_segments, min_band_votes);
+        m.signed_ = true;
+        return m;
+    }
+    unsigned kind() const { return signed_ ? 4u : (rated ? 2u : 0u) + (segmented ? 1u : 0u); }
     size_t record_bytes() const {
-        constexpr size_t bytes[4] = {sizeof(hvd_valign), sizeof(hvd_vsegments), sizeof(hvd_vrate), sizeof(hvd_vrsegments)};
+        constexpr size_t bytes[5] = {sizeof(hvd_valign), sizeof(hvd_vsegments), sizeof(hvd_vrate), sizeof(hvd_vrsegments),
+                                     sizeof(hvd_vssegments)};
         return bytes[kind()];
     }
     unsigned runs() const { return segmented ? 2u : 1u; }  // pairs of runs of bit words: the flag words, and the taken words
@@ -296,6 +307,45 @@ inline bool pack_rate_list(const int32_t* rates, int n_rates, uint32_t* nums, ui
     if (rate_list_length(nn, dd) != (uint32_t)n_rates) return false;
     *nums = nn;
     *dens = dd;
+    return true;
+}
+// The signed list of the alignment with negative rates travels as three words: nums and dens as above with |num|
+// in nums, and revs, bit r set when entry r is negative. signed_rate_list_length: its length R, or 0 for a broken list -- the
+// magnitudes judged as rate_list_length judges them, except that a pair may be listed once per sign; a bit of revs at or
+// behind the end breaks the list. The one definition of a sound signed list, for the host entry and for the kernel.
+constexpr uint32_t signed_rate_list_length(uint32_t nums, uint32_t dens, uint32_t revs) {
+    uint32_t R = 0;
+    while (R < (uint32_t)HVD_ALIGN_MAX_RATES && (((nums | dens) >> (4u * R)) & 15u)) ++R;
+    if (R < (uint32_t)HVD_ALIGN_MAX_RATES && ((nums | dens) >> (4u * R))) return 0u;
+    if (revs >> R) return 0u;
+    for (uint32_t r = 0; r < R; ++r) {
+        const uint32_t num = (nums >> (4u * r)) & 15u, den = (dens >> (4u * r)) & 15u;
+        if (num - 1u >= 8u || den - 1u >= 8u) return 0u;
+        for (uint32_t f = 2; f <= 7u; ++f)
+            if (num % f == 0u && den % f == 0u) return 0u;
+        for (uint32_t q = 0; q < r; ++q)
+            if (((nums >> (4u * q)) & 15u) == num && ((dens >> (4u * q)) & 15u) == den && (((revs >> q) ^ (revs >> r)) & 1u) == 0u)
+                return 0u;
+    }
+    return R;
+}
+// (num, den) x n_rates as the caller lists them, num of either sign -> the three words; false (and 0, 0, 0: a broken list)
+// unless the list is sound as a signed list
+inline bool pack_signed_rate_list(const int32_t* rates, int n_rates, uint32_t* nums, uint32_t* dens, uint32_t* revs) {
+    *nums = *dens = *revs = 0u;
+    if (!rates || n_rates < 1 || n_rates > HVD_ALIGN_MAX_RATES) return false;
+    uint32_t nn = 0, dd = 0, vv = 0;
+    for (int r = 0; r < n_rates; ++r) {
+        const int32_t num = rates[2 * r], den = rates[2 * r + 1];
+        if (num < -8 || num > 8 || num == 0 || den < 1 || den > 8) return false;
+        nn |= (uint32_t)(num < 0 ? -num : num) << (4 * r);
+        dd |= (uint32_t)den << (4 * r);
+        vv |= (num < 0 ? 1u : 0u) << r;
+    }
+    if (signed_rate_list_length(nn, dd, vv) != (uint32_t)n_rates) return false;
+    *nums = nn;
+    *dens = dd;
+    *revs = vv;
     return true;
 }
 

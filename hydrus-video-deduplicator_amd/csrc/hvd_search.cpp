@@ -1408,6 +1408,7 @@ int hvd_align_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratc
 int hvd_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of(false, true), max_bins, out_bytes); }
 int hvd_rates_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of(true, false), max_bins, out_bytes); }
 int hvd_rate_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of(true, true), max_bins, out_bytes); }
+int hvd_signed_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of_signed(0, 1), max_bins, out_bytes); }
 
 static int check_tolerances(int max_dist, int slack) {
     if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
@@ -1422,7 +1423,7 @@ static int check_segment_limits(int max_segments, int min_band_votes) {
     return HVD_OK;
 }
 
-// The four device entries: the checks in the order their errors are reported, then the mode's launches. rates / n_rates: the
+// The device entries: the checks in the order their errors are reported, then the mode's launches. rates / n_rates: the
 // list as the caller gave it (rated modes); a broken one travels as (0, 0), the kernel's INT32_MIN records.
 static int align_on_device(AlignMode mode, const int32_t* rates, int n_rates, const AlignOperands& op) {
     if (int rc = need_ready()) return rc;
@@ -1437,7 +1438,10 @@ static int align_on_device(AlignMode mode, const int32_t* rates, int n_rates, co
     const uintptr_t aligned16 = (uintptr_t)op.hashes_q | (uintptr_t)op.hashes_t | (uintptr_t)op.scratch | (mode.records16() ? (uintptr_t)op.out : 0u);
     if (aligned16 & 15u)
         return fail(HVD_ERR_ARG, "%s must be 16-byte aligned", mode.records16() ? "hashes, scratch and records" : "hashes and scratch");
-    if (mode.rated) hvd::pack_rate_list(rates, n_rates, &mode.nums, &mode.dens);
+    if (mode.signed_)
+        hvd::pack_signed_rate_list(rates, n_rates, &mode.nums, &mode.dens, &mode.revs);
+    else if (mode.rated)
+        hvd::pack_rate_list(rates, n_rates, &mode.nums, &mode.dens);
     HIP_TRY(hvd::launch_alignment(mode, op, g.stream));
     return HVD_OK;
 }
@@ -1478,6 +1482,15 @@ int hvd_dev_vpdq_align_rate_segments(const void* d_hashes_q, const void* d_offse
                             d_scratch, scratch_bytes, d_out});
 }
 
+int hvd_dev_vpdq_align_signed(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                              const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                              const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                              int max_segments, int min_band_votes, void* d_scratch, size_t scratch_bytes, void* d_out) {
+    return align_on_device(AlignMode::of_signed(max_segments, min_band_votes), rates, n_rates,
+                           {d_hashes_q, d_offsets_q, VQ, d_pos_q, d_hashes_t, d_offsets_t, VT, d_pos_t, d_pairs, M, max_dist, slack,
+                            d_scratch, scratch_bytes, d_out});
+}
+
 // positions of one library: non-negative, strictly increasing inside a video, below 2^20
 static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V, const char* side) {
     if (!pos) return HVD_OK;
@@ -1495,7 +1508,10 @@ static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V
 // the slope-one modes after it (mode.args_first). -> the frames of either library and the largest bins of any pair.
 static int align_check(AlignMode& mode, const int32_t* rates, int n_rates, const AlignOperands& h, int64_t* nq_out, int64_t* nt_out,
                        int64_t* max_bins_out) {
-    if (mode.rated && !hvd::pack_rate_list(rates, n_rates, &mode.nums, &mode.dens))
+    if (mode.signed_ && !hvd::pack_signed_rate_list(rates, n_rates, &mode.nums, &mode.dens, &mode.revs))
+        return fail(HVD_ERR_ARG, "rates: need 1..%d pairs (num, den) with 1 <= |num|, den <= 8, no common factor, none listed twice "
+                    "with one sign", HVD_ALIGN_MAX_RATES);
+    if (mode.rated && !mode.signed_ && !hvd::pack_rate_list(rates, n_rates, &mode.nums, &mode.dens))
         return fail(HVD_ERR_ARG, "rates: need 1..%d pairs (num, den) with 1 <= num, den <= 8, no common factor, none listed twice",
                     HVD_ALIGN_MAX_RATES);
     if (mode.segmented)
@@ -1526,9 +1542,10 @@ static int align_check(AlignMode& mode, const int32_t* rates, int n_rates, const
         const int64_t sa = span(positions_q, offsets_q, a), sb = span(positions_t, offsets_t, b);
         if (sa < 0 || sb < 0) continue;  // an empty video: the zero record
         int64_t bins = sa + sb + 1 + 2 * (int64_t)h.slack;
-        for (int r = 0; r < n_rates; ++r)  // the largest bins_r of the list
-            bins = std::max(bins, rates[2 * r] * sa + rates[2 * r + 1] * sb + 1 +
-                                      2 * (int64_t)h.slack * std::max(rates[2 * r], rates[2 * r + 1]));
+        for (int r = 0; r < n_rates; ++r) {  // the largest bins_r of the list (|num|: a signed list may hold negative ones)
+            const int64_t num = std::abs((int64_t)rates[2 * r]), den = rates[2 * r + 1];
+            bins = std::max(bins, num * sa + den * sb + 1 + 2 * (int64_t)h.slack * std::max(num, den));
+        }
         if (bins > (1ll << 20))
             return fail(HVD_ERR_ARG, "pair %lld = (%u, %u) spans %lld offsets with slack %d: more than the 2^20 histogram bins",
                         (long long)p, a, b, (long long)bins, h.slack);
@@ -1629,6 +1646,14 @@ int hvd_vpdq_align_rate_segments(const uint8_t* frames_q, const int64_t* offsets
                                  const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                                  int max_segments, int min_band_votes, hvd_vrsegments* out) {
     return align_from_host(AlignMode::of(true, true, max_segments, min_band_votes), rates, n_rates,
+                           {frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, nullptr, 0, out});
+}
+
+int hvd_vpdq_align_signed(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                          const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                          const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                          int max_segments, int min_band_votes, hvd_vssegments* out) {
+    return align_from_host(AlignMode::of_signed(max_segments, min_band_votes), rates, n_rates,
                            {frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, nullptr, 0, out});
 }
 

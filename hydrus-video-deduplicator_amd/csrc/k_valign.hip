@@ -90,8 +90,8 @@ namespace hvd {
 size_t alignment_scratch_bytes(const AlignMode& mode, unsigned long long max_bins) { return slot_scratch_bytes(max_bins, mode.runs()); }
 
 hipError_t launch_alignment(const AlignMode& mode, const AlignOperands& op, hipStream_t s) {
-    constexpr decltype(&launch_valign) launchers[4] = {launch_valign, launch_valign_segments, launch_valign_rates,
-                                                       launch_valign_rate_segments};
+    constexpr decltype(&launch_valign) launchers[5] = {launch_valign, launch_valign_segments, launch_valign_rates,
+                                                       launch_valign_rate_segments, launch_valign_signed};
     return launchers[mode.kind()](mode, op, s);
 }
 

@@ -466,6 +466,14 @@ class DeviceLibrary:
         rate list gives INT32_MIN records, as the device entry does."""
         return self._align(records, search.AlignMode(rates, max_segments, min_band_votes), slack, max_dist)
 
+    def align_signed(self, records, rates=search.REVERSED_RATES, slack: int = search.ALIGN_SLACK,
+                     max_dist: int | None = None, max_segments: int = _lib.ALIGN_MAX_SEGMENTS,
+                     min_band_votes: int = 1) -> np.ndarray:
+        """hvd_dev_vpdq_align_signed of the listed pairs of this library against itself: one VSSEGMENTS_DTYPE record per
+        pair, in their order (search.align_signed on what is in HBM; operands and positions as `align`). A list that is not
+        sound as a signed list gives INT32_MIN records, as the device entry does."""
+        return self._align(records, search.AlignMode(rates, max_segments, min_band_votes, True), slack, max_dist)
+
     def _align(self, records, mode: search.AlignMode, slack, max_dist) -> np.ndarray:
         """One device-resident alignment call over this library against itself: the entries, the record dtype and the extra
         arguments are those of the mode's row (search.ALIGN_ROWS)."""
@@ -485,8 +493,9 @@ class DeviceLibrary:
             limit = int(lengths.max()) if lengths.size else 0
         else:
             limit = self._position_limit
-        # a pair's histogram is sized by its largest bins_r = num span_a + den span_b + 1 + 2 slack max(num, den), slope one among them
-        max_bins = max((num + den) * (max(limit, 1) - 1) + 1 + 2 * int(slack) * max(num, den)
+        # a pair's histogram is sized by its largest bins_r = |num| span_a + den span_b + 1 + 2 slack max(|num|, den), slope one
+        # among them (a signed mode lists negative nums)
+        max_bins = max((abs(num) + den) * (max(limit, 1) - 1) + 1 + 2 * int(slack) * max(abs(num), den)
                        for num, den in [(1, 1)] + ([] if rates is None else rates.tolist()))
         sb = C.c_size_t(0)
         _lib.check(getattr(lib, row.scratch_entry)(min(max_bins, _lib.ALIGN_MAX_BINS), C.byref(sb)))
@@ -1242,6 +1251,18 @@ def find_rate_segmented_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.nd
     search.rate_segmented_excerpts_from_records; nothing but records crosses PCIe.
     -> (rate-segmented excerpts, search records, VRSEGMENTS records, library or None); positions are raw frame indices."""
     return _aligned_search_on_device(search.AlignMode(rates, max_segments, int(min_aligned)), d_frames_ptr, raw_offsets, h, w,
+                                     channels, threshold, min_aligned, slack, positions, keep_library)
+
+
+def find_reversed_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                     threshold: float = 50.0, min_aligned: int = 4, slack: int = search.ALIGN_SLACK,
+                                     rates=search.REVERSED_RATES, positions: bool = True,
+                                     max_segments: int = _lib.ALIGN_MAX_SEGMENTS, keep_library: bool = False):
+    """search.find_reversed_excerpts on frames in HBM, one device: the chain of `find_excerpts_on_device` with the alignment
+    with negative rates (`DeviceLibrary.align_signed`, min_band_votes = min_aligned) and the keep rule of
+    search.signed_excerpts_from_records; nothing but records crosses PCIe.
+    -> (rate-segmented excerpts, search records, VSSEGMENTS records, library or None); positions are raw frame indices."""
+    return _aligned_search_on_device(search.AlignMode(rates, max_segments, int(min_aligned), True), d_frames_ptr, raw_offsets, h, w,
                                      channels, threshold, min_aligned, slack, positions, keep_library)
 
 

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _lib, vpdq
 from ._lib import (ALIGN_MAX_RATES, ALIGN_MAX_SEGMENTS, GROUP_DTYPE, PAIR_DTYPE, VALIGN_DTYPE, VCOVER_DTYPE, VMATCH_DTYPE, VRATE_DTYPE,
-                   VRSEGMENTS_DTYPE, VSEGMENTS_DTYPE)
+                   VRSEGMENTS_DTYPE, VSEGMENTS_DTYPE, VSSEGMENTS_DTYPE)
 
 DISTANCE_TOLERANCE = 31  # per-frame Hamming tolerance (vpdqpy/vpdqpy.py:53, db/vptree.py:31)
 DEFAULT_VARIANT = 13  # all-pairs kernel the product uses (FP4-MFMA, 128-bit first stage, form chosen by a probe); DESIGN.md 4.1
@@ -520,19 +520,20 @@ def _align_operands(frames, offsets, pairs, positions, max_dist, frames_t, offse
     return frames, offsets, positions, frames_t, offsets_t, positions_t, pair_array(pairs), max_dist
 
 
-class AlignMode(namedtuple("AlignMode", "rates max_segments min_band_votes")):
-    """Which of the four time alignments a call is, and what only some of them take. rates: None = slope one
+class AlignMode(namedtuple("AlignMode", "rates max_segments min_band_votes signed")):
+    """Which of the time alignments a call is, and what only some of them take. rates: None = slope one
     only, else the list of (num, den) of align_rates; max_segments: None = one line per pair, else align_segments' limit;
-    min_band_votes: align_segments' floor (the excerpt searches also take None: their min_aligned). `row` is the mode's line
-    of the table below: everything else that differs between the four, at every level above the kernels."""
+    min_band_votes: align_segments' floor (the excerpt searches also take None: their min_aligned); signed: the rate x segments
+    alignment whose numerators may be negative (align_signed). `row` is the mode's line of the table below (SIGNED_ROW
+    for a signed mode): everything else that differs between them, at every level above the kernels."""
     __slots__ = ()
 
-    def __new__(cls, rates=None, max_segments=None, min_band_votes=1):
-        return super().__new__(cls, rates, max_segments, min_band_votes)
+    def __new__(cls, rates=None, max_segments=None, min_band_votes=1, signed=False):
+        return super().__new__(cls, rates, max_segments, min_band_votes, signed)
 
     @property
     def row(self) -> "AlignRow":
-        return ALIGN_ROWS[self.rates is not None, self.max_segments is not None]
+        return SIGNED_ROW if self.signed else ALIGN_ROWS[self.rates is not None, self.max_segments is not None]
 
     def entry_args(self, rates: np.ndarray | None) -> tuple:
         """What the mode's C entries take between slack and the scratch / the records; rates: rate_array(self.rates), which
@@ -595,6 +596,10 @@ ALIGN_ROWS = {
     (True, True): AlignRow(VRSEGMENTS_DTYPE, "hvd_vpdq_align_rate_segments", "hvd_dev_vpdq_align_rate_segments",
                            "hvd_rate_segments_scratch_bytes", "align_rate_segments", RateSegmentedExcerpt, RateSegment),
 }
+# the row of a signed mode (AlignMode.signed): rate x segments with negative numerators; a reversed piece is a RateSegment with
+# rate < 0
+SIGNED_ROW = AlignRow(VSSEGMENTS_DTYPE, "hvd_vpdq_align_signed", "hvd_dev_vpdq_align_signed", "hvd_signed_scratch_bytes",
+                      "align_signed", RateSegmentedExcerpt, RateSegment)
 
 
 def _line_in_long(num: int, den: int, d: int, a_short: bool) -> tuple:
@@ -889,6 +894,64 @@ def find_rate_segmented_excerpts(video_hashes, threshold: float = 50.0, min_alig
     fragments (the coverage nearly the same) when it is the second; list (1, 2) in place of another rate to change that."""
     return rate_segmented_excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, rates, positions,
                                         max_segments)
+
+
+# ------------------------------------------------ reversed clips and reels: alignment with negative rates (DESIGN 4.25) ---
+
+# (num, den) with num < 0: b runs backwards against a, p_b = (num / den) p_a + c. The default costs R + 1 = 3 passes over a
+# pair; nobody has measured which reversed speeds occur in real collections, so list (-5, 4), (-2, 1), ... as needed, eight
+# entries in all, and keep (1, 1) first: a pair that forward and backward tie on (one hit, a static scene) is then reported
+# forward.
+REVERSED_RATES = ((1, 1), (-1, 1))
+
+
+def align_signed(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.ndarray | None = None, rates=REVERSED_RATES,
+                 slack: int = ALIGN_SLACK, max_dist: int | None = None, frames_t: np.ndarray | None = None,
+                 offsets_t: np.ndarray | None = None, positions_t: np.ndarray | None = None,
+                 max_segments: int = ALIGN_MAX_SEGMENTS, min_band_votes: int = 1) -> np.ndarray:
+    """Time alignment with negative rates (hvd_vpdq_align_signed): one VSSEGMENTS_DTYPE record per pair, in the order of
+    `pairs`. The operands and the rule are align_rate_segments', except that a listed num may be negative, 1 <= |num| <= 8 in
+    lowest terms with den, and that a pair may be listed once per sign: (num, den) with num < 0 models a b that runs BACKWARDS
+    against a, p_b = (num / den) p_a + c with c = offset / rate_den. The slack of a rate is slack * max(|num|, den). rate_num
+    is stored signed. With every num > 0 the records are align_rate_segments' word for word. A pair on which a forward and a
+    backward rate tie goes to the one listed first."""
+    return _align(AlignMode(rates, max_segments, min_band_votes, True), frames, offsets, pairs, positions, max_dist, slack,
+                  frames_t, offsets_t, positions_t)
+
+
+def signed_excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: np.ndarray, threshold: float = 50.0,
+                                 min_aligned: int = 4) -> list:
+    """The keep rule of find_reversed_excerpts on VSSEGMENTS_DTYPE records (pure numpy; no device): the rule and the
+    orientation arithmetic of rate_segmented_excerpts_from_records. -> sorted list of RateSegmentedExcerpt; a reversed piece
+    is a RateSegment with rate < 0, p_long = rate * p_short + offset, so its short_first sits at `last` of long."""
+    return fold_aligned_records(AlignMode(REVERSED_RATES, ALIGN_MAX_SEGMENTS, 1, True), aligned, lengths, similarity, threshold,
+                                min_aligned)
+
+
+def signed_excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
+                         rates=REVERSED_RATES, positions=None, max_segments: int = ALIGN_MAX_SEGMENTS, matcher=None) -> list:
+    """The search and the alignment of find_reversed_excerpts and their fold, on validated blobs (as excerpt_pairs).
+    matcher: object with match_videos / align_signed (default: the GPU entry points of this module). The alignment is asked
+    to stop at min_band_votes = min_aligned. -> signed_excerpts_from_records(...)."""
+    return _excerpt_pairs(AlignMode(rates, max_segments, None, True), blobs, threshold, min_aligned, slack, positions, matcher)
+
+
+def find_reversed_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, slack: int = ALIGN_SLACK,
+                           rates=REVERSED_RATES, positions=None, max_segments: int = ALIGN_MAX_SEGMENTS) -> list:
+    """Clips played BACKWARDS -- a reversed GIF or webm, a "rewind" piece inside a reel, a reversed re-upload -- besides what
+    find_segmented_excerpts finds. Against a forward offset such a clip lines up two frames at a time, so the other excerpt
+    searches drop it. Every pair of the video search is aligned on up to `max_segments` lines, each at the best of the listed
+    rates, whose numerators may be negative (align_signed); the keep rule is find_rate_segmented_excerpts'. -> sorted list of
+    RateSegmentedExcerpt(short, long, coverage, similarity, segments); a RateSegment with rate < 0 is a reversed piece:
+    p_long = rate * p_short + offset, short's short_first..short_last run from `last` down to `first` of long. With an
+    all-positive list the result is find_rate_segmented_excerpts'.
+    The default list is ((1, 1), (-1, 1)): list (-5, 4), (-2, 1), ... as needed, eight entries in all, and keep (1, 1) first --
+    a static scene fits forward and backward alike, and the earlier entry takes the tie. A rate is listed from the side of
+    the pair's first video (the one earlier in video_hashes): a piece reversed at 2x is whole under (-2, 1) when the reel
+    comes first, and needs (-1, 2) when its source does. The same frames in shuffled order
+    stay unreported. A ping-pong loop (a clip forward, then the same frames backwards) is reported with one of its halves: a
+    frame of the source serves one segment only."""
+    return signed_excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, rates, positions, max_segments)
 
 
 # ------------------------------------------ compilations and multi-part uploads: coverage by several videos (DESIGN 4.23) ------

@@ -104,6 +104,18 @@ class Vpdq:
         return search.align_rate_segments(frames, offsets, [(0, 1)], rates=search.DEFAULT_RATES if rates is None else rates,
                                           slack=slack, max_segments=max_segments)[0]
 
+    @staticmethod
+    def align_signed(phash_a, phash_b, rates=None, slack: int = 1, max_segments: int = 8):
+        """Where the pieces of two video hashes line up in time when a piece may run BACKWARDS -- a reversed clip or a
+        "rewind" piece of a reel against its source: the one ``search.align_signed`` record of the pair (a = 0, b = 1; up to
+        max_segments lines, each at the best-fitting rate of `rates`, default ``search.REVERSED_RATES``; rate_num < 0: b runs
+        backwards against a). VpdqHash or bytes."""
+        from . import search
+
+        frames, offsets, _ = search.pack_hashes((phash_a, phash_b))
+        return search.align_signed(frames, offsets, [(0, 1)], rates=search.REVERSED_RATES if rates is None else rates,
+                                   slack=slack, max_segments=max_segments)[0]
+
     select_frames = staticmethod(select_frames)
 
     @staticmethod

@@ -40,7 +40,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross, then + hvd_rate_segments_scratch_bytes, hvd_dev_vpdq_align_rate_segments, hvd_vpdq_align_rate_segments, then + hvd_dev_frame_runs, hvd_vpdq_frame_runs, then + hvd_dev_video_weights, hvd_dev_vpdq_match_videos_weighted, hvd_dev_vpdq_match_videos_cross_weighted, hvd_vpdq_match_videos_weighted, hvd_vpdq_match_videos_cross_weighted, then + hvd_cover_scratch_bytes, hvd_dev_vpdq_cover_videos, hvd_vpdq_cover_videos; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross, then + hvd_rate_segments_scratch_bytes, hvd_dev_vpdq_align_rate_segments, hvd_vpdq_align_rate_segments, then + hvd_dev_frame_runs, hvd_vpdq_frame_runs, then + hvd_dev_video_weights, hvd_dev_vpdq_match_videos_weighted, hvd_dev_vpdq_match_videos_cross_weighted, hvd_vpdq_match_videos_weighted, hvd_vpdq_match_videos_cross_weighted, then + hvd_cover_scratch_bytes, hvd_dev_vpdq_cover_videos, hvd_vpdq_cover_videos, then + hvd_signed_scratch_bytes, hvd_dev_vpdq_align_signed, hvd_vpdq_align_signed; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -125,6 +125,23 @@ typedef struct hvd_vrsegments {
     uint32_t a, b, q_hits, t_hits, n_segments, q_covered, t_covered, reserved;
     hvd_vrsegment seg[HVD_ALIGN_MAX_SEGMENTS];
 } hvd_vrsegments;
+
+/* One video pair aligned on up to HVD_ALIGN_MAX_SEGMENTS lines, each at the best of up to HVD_ALIGN_MAX_RATES listed rates
+ * whose numerators may be NEGATIVE (hvd_vpdq_align_signed / hvd_dev_vpdq_align_signed): a clip played backwards,
+ * a "rewind" piece inside a reel. The layout is hvd_vrsegments' (416 bytes, 16-byte aligned; a segment is 48 bytes) with
+ * rate_num a signed word: rate_num < 0 says b runs backwards against a in that segment. offset is d* in the rate's scaled
+ * units (den p_b - num p_a), so c = offset / rate_den. The zero record and the INT32_MIN record are hvd_vrsegments'. */
+typedef struct hvd_vssegment {
+    int32_t offset;
+    uint32_t band_votes, q_aligned, t_aligned;
+    int32_t q_first, q_last, t_first, t_last;
+    int32_t rate_num;
+    uint32_t rate_den, rate_index, reserved;
+} hvd_vssegment;
+typedef struct hvd_vssegments {
+    uint32_t a, b, q_hits, t_hits, n_segments, q_covered, t_covered, reserved;
+    hvd_vssegment seg[HVD_ALIGN_MAX_SEGMENTS];
+} hvd_vssegments;
 
 /* One duplicate group (hvd_group_edges / hvd_dev_group_edges): a connected component of size >= 2 of the graph
  * whose edges are the records of a search. root: the smallest member, which is also the label of every member; size: members;
@@ -462,6 +479,32 @@ int hvd_vpdq_align_rate_segments(const uint8_t* frames_q, const int64_t* offsets
                                  const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                                  const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                                  int max_segments, int min_band_votes, hvd_vrsegments* out);
+
+/* Time alignment with negative rates: a clip played BACKWARDS, a reversed piece inside a reel. The rule is
+ * hvd_vpdq_align_rate_segments' rule, word for word, with signed numerators:
+ *   rates: int32[n_rates][2] = (num_r, den_r), 1 <= n_rates <= HVD_ALIGN_MAX_RATES, 1 <= |num| <= 8, 1 <= den <= 8,
+ *   gcd(|num|, den) = 1, the entries pairwise distinct AS SIGNED PAIRS: (1, 1) and (-1, 1) may both be listed.
+ *   (num, den) models p_b = (num / den) p_a + c; num < 0: b runs backwards against a.
+ *   per rate: delta_r = den p_b - num p_a;  slack_r = slack max(|num|, den);
+ *             bins_r = |num| span_a + den span_b + 1 + 2 slack_r;
+ *             the smallest delta is den p_b0 - num p_a1 for num > 0 and den p_b0 - num p_a0 for num < 0.
+ * The rounds, the taken sets on both sides, min_band_votes, the tie order (larger S, larger votes[d], smaller |d|, smaller d,
+ * the earlier rate), the 2^20-bin limit at ANY listed rate, the INT32_MIN record and the zero record are unchanged. A segment's
+ * offset is d*_w in the scaled units of its rate, c = offset / rate_den; rate_num is stored signed.
+ * Four consequences: (a) with every num > 0 the records are hvd_vpdq_align_rate_segments' records word for word, and with
+ * max_segments = 1 seg[0] is then hvd_vpdq_align_rates' record; (b) q_hits and t_hits do not depend on the list; (c) ties go
+ * forward by list order: with (1, 1) listed before (-1, 1), a pair the two tie on -- one hit, a static pair -- is reported
+ * forward (50 against 80 copies of one frame: rate (1, 1), offset 1, band_votes 150 at slack 1), and listing (-1, 1) first
+ * reports it as (-1, 1), offset 50, band_votes 150; (d) reflection: reversing a's frame order (index positions) and negating
+ * every num gives, for a pair without a tie on |d|, the same band_votes, q_aligned, t_aligned, t_first and t_last per
+ * segment, offset' = offset + num (n_a - 1) with num the original segment's, and q_first' = n_a - 1 - q_last.
+ * out: M hvd_vssegments records in the order of the pair list. This host-buffer form rejects with HVD_ERR_ARG, before it asks
+ * for a device, everything hvd_vpdq_align_rate_segments rejects and a list that is not sound as a signed list. The other
+ * alignment entries keep rejecting a negative num. */
+int hvd_vpdq_align_signed(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                          const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                          const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                          int max_segments, int min_band_votes, hvd_vssegments* out);
 
 /* Duplicate groups with a keeper: the connected components of a pair list. The rule, integers only, one answer per
  * input. V nodes, 1 <= V < 2^31. E records of 16 bytes, E < 2^32, words 0 and 1 the two node indices u, v (hvd_pair and
@@ -892,6 +935,18 @@ int hvd_dev_vpdq_align_rate_segments(const void* d_hashes_q, const void* d_offse
                                      const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                                      const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                                      int max_segments, int min_band_votes, void* d_scratch, size_t scratch_bytes, void* d_out);
+
+/* Device-resident alignment with negative rates (the rule: hvd_vpdq_align_signed above). The operands of
+ * hvd_dev_vpdq_align_rate_segments; rates may hold negative numerators; d_out: M hvd_vssegments records, 16-byte aligned. A
+ * pair's histogram is sized by its largest bins_r = |num| span_a + den span_b + 1 + 2 slack max(|num|, den) over the list:
+ * hvd_signed_scratch_bytes(max_bins) bytes serve every pair of up to max_bins bins (<= 2^20). Two launches are enqueued on the
+ * library stream: no host synchronisation, nothing allocated, nothing on the device validated. A list that is not sound as a
+ * signed list gives every pair the INT32_MIN record; broken operands give wrong records, never an access out of bounds. */
+int hvd_signed_scratch_bytes(int64_t max_bins, size_t* out_bytes);
+int hvd_dev_vpdq_align_signed(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                              const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                              const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                              int max_segments, int min_band_votes, void* d_scratch, size_t scratch_bytes, void* d_out);
 
 /* Device-resident grouping (the rule: hvd_group_edges above). d_records: n_records records of 16 bytes, 16-byte aligned;
  * d_record_count: NULL, or the uint64 the all-pairs entries bump -- the kernels then take min(*d_record_count, n_records)
