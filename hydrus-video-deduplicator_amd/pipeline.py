@@ -474,6 +474,14 @@ class DeviceLibrary:
         sound as a signed list gives INT32_MIN records, as the device entry does."""
         return self._align(records, search.AlignMode(rates, max_segments, min_band_votes, True), slack, max_dist)
 
+    def align_loops(self, records, rates=search.REVERSED_RATES, slack: int = search.ALIGN_SLACK, max_dist: int | None = None,
+                    max_rounds: int = _lib.ALIGN_MAX_ROUNDS, min_band_votes: int = 1) -> np.ndarray:
+        """hvd_dev_vpdq_align_loops of the listed pairs of this library against itself: one VLOOPS_DTYPE record per pair, in
+        their order (search.align_loops on what is in HBM; operands and positions as `align`). The loop is a pair's a side:
+        list (b, a) as well to try the other orientation. A list that is not sound as a signed list gives INT32_MIN records,
+        as the device entry does."""
+        return self._align(records, search.AlignMode(rates, max_rounds, min_band_votes, True, True), slack, max_dist)
+
     def _align(self, records, mode: search.AlignMode, slack, max_dist) -> np.ndarray:
         """One device-resident alignment call over this library against itself: the entries, the record dtype and the extra
         arguments are those of the mode's row (search.ALIGN_ROWS)."""
@@ -1264,6 +1272,32 @@ def find_reversed_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray,
     -> (rate-segmented excerpts, search records, VSSEGMENTS records, library or None); positions are raw frame indices."""
     return _aligned_search_on_device(search.AlignMode(rates, max_segments, int(min_aligned), True), d_frames_ptr, raw_offsets, h, w,
                                      channels, threshold, min_aligned, slack, positions, keep_library)
+
+
+def find_looped_excerpts_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,
+                                   threshold: float = 50.0, min_aligned: int = 4, rates=search.REVERSED_RATES,
+                                   max_rounds: int = _lib.ALIGN_MAX_ROUNDS, slack: int = search.ALIGN_SLACK, positions: bool = True,
+                                   keep_library: bool = False):
+    """search.find_looped_excerpts on frames in HBM, one device: the chain of `find_excerpts_on_device` up to the video search,
+    then every record aligned in both orientations, (a, b) and then (b, a), in one `DeviceLibrary.align_loops` call
+    (min_band_votes = min_aligned), and the keep rule of search.looped_excerpts_from_records; nothing but records crosses PCIe.
+    -> (looped excerpts, search records, VLOOPS records -- twice as many --, library or None); positions are raw frame indices."""
+    library = _hashed_library(
+        raw_offsets, 0, 1, None, lambda mine: hash_frames_on_device(d_frames_ptr, int(mine[-1]), h, w, channels), 32,
+        lambda *raw: DeviceLibrary.from_raw_hashes(*raw, positions=bool(positions)), None)
+    try:
+        recs = library.match_videos()
+        ab = np.stack([recs["a"], recs["b"]], axis=1)
+        aligned = library.align_loops(np.concatenate([ab, ab[:, ::-1]]), rates, slack, None, max_rounds, int(min_aligned))
+        lengths = library.lengths()
+        out = search.looped_excerpts_from_records(aligned, lengths, np.tile(search.similarity_of_records(recs, lengths), 2), threshold)
+    except BaseException:
+        library.free()
+        raise
+    if keep_library:
+        return out, recs, aligned, library
+    library.free()
+    return out, recs, aligned, None
 
 
 def find_compilations_on_device(d_frames_ptr: int, raw_offsets: np.ndarray, h: int, w: int, channels: int,

@@ -18,8 +18,8 @@ from fractions import Fraction
 import numpy as np
 
 from . import _lib, vpdq
-from ._lib import (ALIGN_MAX_RATES, ALIGN_MAX_SEGMENTS, GROUP_DTYPE, PAIR_DTYPE, VALIGN_DTYPE, VCOVER_DTYPE, VMATCH_DTYPE, VRATE_DTYPE,
-                   VRSEGMENTS_DTYPE, VSEGMENTS_DTYPE, VSSEGMENTS_DTYPE)
+from ._lib import (ALIGN_MAX_RATES, ALIGN_MAX_ROUNDS, ALIGN_MAX_SEGMENTS, GROUP_DTYPE, PAIR_DTYPE, VALIGN_DTYPE, VCOVER_DTYPE, VLOOPS_DTYPE,
+                   VMATCH_DTYPE, VRATE_DTYPE, VRSEGMENTS_DTYPE, VSEGMENTS_DTYPE, VSSEGMENTS_DTYPE)
 
 DISTANCE_TOLERANCE = 31  # per-frame Hamming tolerance (vpdqpy/vpdqpy.py:53, db/vptree.py:31)
 DEFAULT_VARIANT = 13  # all-pairs kernel the product uses (FP4-MFMA, 128-bit first stage, form chosen by a probe); DESIGN.md 4.1
@@ -524,15 +524,23 @@ class AlignMode(namedtuple("AlignMode", "rates max_segments min_band_votes signe
     """Which of the time alignments a call is, and what only some of them take. rates: None = slope one
     only, else the list of (num, den) of align_rates; max_segments: None = one line per pair, else align_segments' limit;
     min_band_votes: align_segments' floor (the excerpt searches also take None: their min_aligned); signed: the rate x segments
-    alignment whose numerators may be negative (align_signed). `row` is the mode's line of the table below (SIGNED_ROW
-    for a signed mode): everything else that differs between them, at every level above the kernels."""
+    alignment whose numerators may be negative (align_signed); loops: the signed rule without a taken set on the b
+    side, max_segments then holding max_rounds (align_loops). `row` is the mode's line of the table below (SIGNED_ROW
+    for a signed mode, LOOPS_ROW for a loops mode): everything else that differs between them, at every level above the kernels."""
     __slots__ = ()
 
-    def __new__(cls, rates=None, max_segments=None, min_band_votes=1, signed=False):
-        return super().__new__(cls, rates, max_segments, min_band_votes, signed)
+    # `loops` is a class attribute and AlignMode(..., loops=True) a _LoopsMode, not a fifth tuple field, only because
+    # tests/test_signed_cpu.py pins _fields to the four names: when that test lets go of them, `loops` becomes the fifth field
+    # and _LoopsMode goes.
+    loops = False
+
+    def __new__(cls, rates=None, max_segments=None, min_band_votes=1, signed=False, loops=False):
+        return super().__new__(_LoopsMode if loops else cls, rates, max_segments, min_band_votes, bool(signed or loops))
 
     @property
     def row(self) -> "AlignRow":
+        if self.loops:
+            return LOOPS_ROW
         return SIGNED_ROW if self.signed else ALIGN_ROWS[self.rates is not None, self.max_segments is not None]
 
     def entry_args(self, rates: np.ndarray | None) -> tuple:
@@ -540,6 +548,12 @@ class AlignMode(namedtuple("AlignMode", "rates max_segments min_band_votes signe
         the caller keeps alive over the call."""
         return (() if rates is None else (rates.ctypes.data, rates.shape[0])) + \
             (() if self.max_segments is None else (int(self.max_segments), int(self.min_band_votes)))
+
+
+class _LoopsMode(AlignMode):
+    """AlignMode(..., loops=True): a signed mode whose max_segments holds max_rounds; _replace keeps the class."""
+    __slots__ = ()
+    loops = True
 
 
 # One row per (rated, segmented): the record dtype, the host, device and scratch-size entries of the C ABI, the name of the
@@ -600,6 +614,11 @@ ALIGN_ROWS = {
 # rate < 0
 SIGNED_ROW = AlignRow(VSSEGMENTS_DTYPE, "hvd_vpdq_align_signed", "hvd_dev_vpdq_align_signed", "hvd_signed_scratch_bytes",
                       "align_signed", RateSegmentedExcerpt, RateSegment)
+# the row of a loops mode (AlignMode.loops): the signed rule where a frame of b serves any number of rounds; its fold is
+# looped_excerpts_from_records, not fold_aligned_records
+LoopedExcerpt = namedtuple("LoopedExcerpt", "loop source coverage similarity rounds source_frames segments")
+LOOPS_ROW = AlignRow(VLOOPS_DTYPE, "hvd_vpdq_align_loops", "hvd_dev_vpdq_align_loops", "hvd_loops_scratch_bytes", "align_loops",
+                     LoopedExcerpt, RateSegment)
 
 
 def _line_in_long(num: int, den: int, d: int, a_short: bool) -> tuple:
@@ -952,6 +971,106 @@ def find_reversed_excerpts(video_hashes, threshold: float = 50.0, min_aligned: i
     stay unreported. A ping-pong loop (a clip forward, then the same frames backwards) is reported with one of its halves: a
     frame of the source serves one segment only."""
     return signed_excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, slack, rates, positions, max_segments)
+
+
+# ------------------------------------------------ looped clips and boomerangs: a source frame serves twice (DESIGN 4.26) ---
+
+def align_loops(frames: np.ndarray, offsets: np.ndarray, pairs, positions: np.ndarray | None = None, rates=REVERSED_RATES,
+                max_rounds: int = ALIGN_MAX_ROUNDS, min_band_votes: int = 1, slack: int = ALIGN_SLACK, max_dist: int | None = None,
+                frames_t: np.ndarray | None = None, offsets_t: np.ndarray | None = None,
+                positions_t: np.ndarray | None = None) -> np.ndarray:
+    """Time alignment where a frame of b may serve MORE THAN ONCE (hvd_vpdq_align_loops): one VLOOPS_DTYPE record per pair, in
+    the order of `pairs`. The operands and the list are align_signed's. The rule is align_signed's with two changes: only the
+    frames of a that a round aligned are withheld from the later rounds -- b's frames serve any number of them -- and up to
+    `max_rounds` (1..64) rounds are made. A pair ends when a round's best band holds fewer than `min_band_votes` hits, when
+    every frame of a is aligned, or after max_rounds. The LOOP is therefore the a side and its source the b side: list a pair
+    in the orientation to be tried, or in both. A record holds the first eight rounds as segments (seg[0] IS align_signed's
+    seg[0]); a later round adds to `rounds`, q_covered and t_covered only. q_covered: frames of a in any round; t_covered:
+    DISTINCT frames of b in any round."""
+    return _align(AlignMode(rates, max_rounds, min_band_votes, True, True), frames, offsets, pairs, positions, max_dist, slack,
+                  frames_t, offsets_t, positions_t)
+
+
+def looped_excerpts_from_records(aligned: np.ndarray, lengths: np.ndarray, similarity: np.ndarray, threshold: float = 50.0) -> list:
+    """The keep rule of find_looped_excerpts on VLOOPS_DTYPE records (pure numpy; no device). The records may name a pair of
+    videos in both orientations, (a, b) and (b, a), and in any order; similarity: one value per record. Per unordered pair the
+    orientation with the larger int(100 * q_covered / len(a)) is kept; ties go to fewer rounds, then to the lower video index
+    as a. loop = a, source = b, coverage = 100 * q_covered / len(a), source_frames = t_covered; the pair is kept iff
+    int(coverage) >= int(threshold) and rounds >= 1. A pair the entry could not align (seg[0].offset INT32_MIN) and a pair
+    with an empty video are skipped.
+    Coverage counts EVERY round whose band reached the entry's min_band_votes, the rounds past the eighth included, whose
+    per-round frame counts are not recorded: there is no per-segment min_aligned here as in fold_aligned_records -- the floor
+    is the one the alignment was called with.
+    -> sorted list of LoopedExcerpt(loop, source, coverage, similarity, rounds, source_frames, segments); segments: the first
+    min(rounds, 8) rounds as RateSegment(rate, offset, short_first, short_last, first, last, aligned) ordered by short_first, in
+    the SOURCE's timeline: the loop's positions short_first..short_last sit at first..last of the source,
+    p_source = rate * p_loop + offset, backwards where rate < 0."""
+    if int(threshold) < 1:
+        raise ValueError("threshold < 1 would select every pair of videos")
+    lengths = np.asarray(lengths, dtype=np.int64)
+    best = {}
+    for r, sim in zip(aligned, similarity):
+        a, b = int(r["a"]), int(r["b"])
+        na, rounds = int(lengths[a]), int(r["rounds"])
+        if na == 0 or int(lengths[b]) == 0 or int(r["seg"][0]["offset"]) == -(1 << 31) or rounds < 1:
+            continue
+        percent = int(100 * int(r["q_covered"]) // na)
+        key = (-percent, rounds, a)
+        pair = (min(a, b), max(a, b))
+        if pair not in best or key < best[pair][0]:
+            best[pair] = (key, r, float(sim))
+    out = []
+    for key, r, sim in best.values():
+        a, b = int(r["a"]), int(r["b"])
+        coverage = 100.0 * int(r["q_covered"]) / int(lengths[a])
+        if int(coverage) < int(threshold):
+            continue
+        segs = []
+        for s in r["seg"][:int(r["n_segments"])]:
+            rate, offset = _line_in_long(int(s["rate_num"]), int(s["rate_den"]), int(s["offset"]), True)
+            segs.append(RateSegment(rate, offset, int(s["q_first"]), int(s["q_last"]), int(s["t_first"]), int(s["t_last"]),
+                                    int(s["q_aligned"])))
+        out.append(LoopedExcerpt(a, b, coverage, sim, int(r["rounds"]), int(r["t_covered"]),
+                                 tuple(sorted(segs, key=lambda s: s.short_first))))
+    return sorted(out)
+
+
+def looped_excerpt_pairs(blobs: list, threshold: float = 50.0, min_aligned: int = 4, rates=REVERSED_RATES,
+                         max_rounds: int = ALIGN_MAX_ROUNDS, slack: int = ALIGN_SLACK, positions=None, matcher=None) -> list:
+    """The search and the alignment of find_looped_excerpts and their fold, on validated blobs (as excerpt_pairs). matcher:
+    object with match_videos / align_loops (default: the GPU entry points of this module). Every record of the search is
+    aligned in BOTH orientations, (a, b) and then (b, a), in one call, with min_band_votes = min_aligned.
+    -> looped_excerpts_from_records(...)."""
+    mv, al = (match_videos, align_loops) if matcher is None else (matcher.match_videos, matcher.align_loops)
+    frames, offsets, lengths = pack_hashes(blobs)
+    pos = _positions_of(positions, blobs, lengths)
+    max_dist = vpdq.frame_max_dist(DISTANCE_TOLERANCE)
+    recs = mv(frames, offsets, max_dist)
+    ab = np.stack([recs["a"], recs["b"]], axis=1)
+    aligned = al(frames, offsets, np.concatenate([ab, ab[:, ::-1]]), positions=pos, rates=rates, max_rounds=max_rounds,
+                 min_band_votes=int(min_aligned), slack=slack, max_dist=max_dist)
+    return looped_excerpts_from_records(aligned, lengths, np.tile(similarity_of_records(recs, lengths), 2), threshold)
+
+
+def find_looped_excerpts(video_hashes, threshold: float = 50.0, min_aligned: int = 4, rates=REVERSED_RATES,
+                         max_rounds: int = ALIGN_MAX_ROUNDS, slack: int = ALIGN_SLACK, positions=None) -> list:
+    """LOOPED clips -- a few seconds of a longer video repeated over and over, a GIF that plays a moment N times, a ping-pong /
+    boomerang loop (forward, then the same frames backwards) -- besides plain copies and plain excerpts. The other excerpt
+    searches let a frame of the source explain one frame of the copy, so a clip that shows the same source frames N times is
+    covered 1 / N by them. Here every pair of the video search is aligned in both orientations (align_loops): in each, the
+    frames of the first video are peeled off in up to `max_rounds` rounds, each at the best of the listed rates, while the
+    second video's frames may serve any number of rounds. Per pair the orientation that covers more of its first video is
+    kept (looped_excerpts_from_records has the tie rules), and the pair is reported iff that coverage reaches `threshold`
+    percent. -> sorted list of LoopedExcerpt(loop, source, coverage, similarity, rounds, source_frames, segments): `rounds`
+    lines were needed (1 for a plain copy or a plain excerpt, 2 for a boomerang, N for an N-fold loop), source_frames distinct
+    frames of the source were used, and segments holds the first eight rounds as RateSegment in the source's timeline
+    (rate < 0: that repetition runs backwards).
+    A round counts iff its band holds at least `min_aligned` frame hits (the alignment's min_band_votes); coverage counts
+    every such round, also those past the eighth, whose detail is not recorded. More than max_rounds repetitions are covered
+    max_rounds / N. A static or near-static pair spends its rounds a few frames at a time: collapse it with
+    without_repeated_frames first. The default list is REVERSED_RATES; list other speeds as find_reversed_excerpts does, from
+    the side of the loop."""
+    return looped_excerpt_pairs([hash_blob(h) for h in video_hashes], threshold, min_aligned, rates, max_rounds, slack, positions)
 
 
 # ------------------------------------------ compilations and multi-part uploads: coverage by several videos (DESIGN 4.23) ------

@@ -116,6 +116,18 @@ class Vpdq:
         return search.align_signed(frames, offsets, [(0, 1)], rates=search.REVERSED_RATES if rates is None else rates,
                                    slack=slack, max_segments=max_segments)[0]
 
+    @staticmethod
+    def align_loops(phash_a, phash_b, rates=None, slack: int = 1, max_rounds: int = 64, min_band_votes: int = 1):
+        """Where a LOOPED clip a -- a moment repeated, a ping-pong / boomerang loop -- lines up with its source b: the one
+        ``search.align_loops`` record of the pair (a = 0, b = 1; up to max_rounds lines, each at the best-fitting rate of
+        `rates`, default ``search.REVERSED_RATES``; a frame of b may serve any number of lines, a frame of a serves one; the
+        first eight lines are stored as segments). VpdqHash or bytes."""
+        from . import search
+
+        frames, offsets, _ = search.pack_hashes((phash_a, phash_b))
+        return search.align_loops(frames, offsets, [(0, 1)], rates=search.REVERSED_RATES if rates is None else rates,
+                                  max_rounds=max_rounds, min_band_votes=min_band_votes, slack=slack)[0]
+
     select_frames = staticmethod(select_frames)
 
     @staticmethod

@@ -40,7 +40,7 @@ extern "C" {
 
 #define HVD_BYTES_PER_PDQ_HASH 32 /* == vpdq.VpdqHash.bytesPerPdqHash, dedup.py:83 */
 #define HVD_UNIQUE_ID_BYTES 128
-#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross, then + hvd_rate_segments_scratch_bytes, hvd_dev_vpdq_align_rate_segments, hvd_vpdq_align_rate_segments, then + hvd_dev_frame_runs, hvd_vpdq_frame_runs, then + hvd_dev_video_weights, hvd_dev_vpdq_match_videos_weighted, hvd_dev_vpdq_match_videos_cross_weighted, hvd_vpdq_match_videos_weighted, hvd_vpdq_match_videos_cross_weighted, then + hvd_cover_scratch_bytes, hvd_dev_vpdq_cover_videos, hvd_vpdq_cover_videos, then + hvd_signed_scratch_bytes, hvd_dev_vpdq_align_signed, hvd_vpdq_align_signed; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
+#define HVD_ABI_VERSION 6 /* 6 (round 6): + hvd_group_rearm; later, still 6 (additions only, backward compatible): + hvd_dev_pdq_hash_frames_dihedral, hvd_pdq_hash_frames_dihedral_gray_u8 / _rgb24_u8, then + hvd_hasher_create_dihedral, hvd_hasher_finish_dihedral, then + hvd_dev_compact_kept_dihedral, then + hvd_align_scratch_bytes, hvd_dev_vpdq_align_videos, hvd_dev_kept_positions, hvd_vpdq_align_videos, then + hvd_hasher_create_autocrop, hvd_hasher_finish_autocrop, then + hvd_segments_scratch_bytes, hvd_dev_vpdq_align_segments, hvd_vpdq_align_segments, then + hvd_rates_scratch_bytes, hvd_dev_vpdq_align_rates, hvd_vpdq_align_rates, then + hvd_group_scratch_bytes, hvd_dev_group_edges, hvd_group_edges, then + hvd_pdq_crops_scratch_bytes, hvd_dev_pdq_hash_frames_crops, hvd_pdq_hash_frames_crops_gray_u8 / _rgb24_u8, then + hvd_dev_content_rects_detail, hvd_pdq_hash_frames_detail_gray_u8 / _rgb24_u8, hvd_hasher_create_autocrop_detail, then + hvd_dev_vpdq_frame_spread_cross, hvd_vpdq_frame_spread_cross, then + hvd_rate_segments_scratch_bytes, hvd_dev_vpdq_align_rate_segments, hvd_vpdq_align_rate_segments, then + hvd_dev_frame_runs, hvd_vpdq_frame_runs, then + hvd_dev_video_weights, hvd_dev_vpdq_match_videos_weighted, hvd_dev_vpdq_match_videos_cross_weighted, hvd_vpdq_match_videos_weighted, hvd_vpdq_match_videos_cross_weighted, then + hvd_cover_scratch_bytes, hvd_dev_vpdq_cover_videos, hvd_vpdq_cover_videos, then + hvd_signed_scratch_bytes, hvd_dev_vpdq_align_signed, hvd_vpdq_align_signed, then + hvd_loops_scratch_bytes, hvd_dev_vpdq_align_loops, hvd_vpdq_align_loops; 5 (round 5): + hvd_hasher_acquire_n, hvd_hasher_commit_n, hvd_group_abort, hvd_runtime_info, hvd_timer_mark, hvd_timer_between; 4 (round 4): + hvd_init_devices, hvd_context_count, hvd_set_context, hvd_get_context, hvd_group_exchange; 3 (round 3): + hvd_host_malloc/free, hvd_hasher_set_threads, hvd_dev_vpdq_emit_again, hvd_comm_abort, hvd_dct_matrix_libm */
 /* All-pairs kernel the host entry points use: FP4-MFMA with a 128-bit first stage; which of its two forms runs
  * (survivors fetch their other half | second stage out of registers) is chosen per launch from a probe of the data. */
 #define HVD_DEFAULT_VARIANT 13
@@ -142,6 +142,18 @@ typedef struct hvd_vssegments {
     uint32_t a, b, q_hits, t_hits, n_segments, q_covered, t_covered, reserved;
     hvd_vssegment seg[HVD_ALIGN_MAX_SEGMENTS];
 } hvd_vssegments;
+
+/* One video pair aligned where a frame of b may serve MORE THAN ONCE (hvd_vpdq_align_loops / hvd_dev_vpdq_align_loops; DESIGN
+ * 4.26): a looped clip, a ping-pong / boomerang loop, a short moment repeated. The layout is hvd_vssegments' (416 bytes, 16-byte
+ * aligned) with `rounds` in the place of the reserved word. seg[0 .. n_segments - 1] are the first min(rounds, 8) rounds in the
+ * order found; a round past the eighth writes no segment and adds to rounds, q_covered and t_covered only. q_covered: the frames
+ * of a in any round (the rounds' frames of a are disjoint: the sum of q_aligned over ALL rounds); t_covered: the DISTINCT frames
+ * of b in any round, so t_covered <= the sum of t_aligned. The zero record and the INT32_MIN record are hvd_vssegments'. */
+#define HVD_ALIGN_MAX_ROUNDS 64
+typedef struct hvd_vloops {
+    uint32_t a, b, q_hits, t_hits, n_segments, q_covered, t_covered, rounds;
+    hvd_vssegment seg[HVD_ALIGN_MAX_SEGMENTS];
+} hvd_vloops;
 
 /* One duplicate group (hvd_group_edges / hvd_dev_group_edges): a connected component of size >= 2 of the graph
  * whose edges are the records of a search. root: the smallest member, which is also the label of every member; size: members;
@@ -505,6 +517,30 @@ int hvd_vpdq_align_signed(const uint8_t* frames_q, const int64_t* offsets_q, int
                           const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
                           const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                           int max_segments, int min_band_votes, hvd_vssegments* out);
+
+/* Time alignment where a frame of the source serves more than once: looped clips and boomerangs. The rule is
+ * hvd_vpdq_align_signed's rule with two changes: the taken set of b is dropped, and the rounds may go on past the eight stored
+ * segments. rates: a signed list exactly as hvd_vpdq_align_signed takes it. max_rounds in [1, HVD_ALIGN_MAX_ROUNDS],
+ * min_band_votes >= 1. With taken_a = {} and seen_b = {}, for r = 1 .. max_rounds:
+ *   H_r = the hits of H whose frame OF A is not in taken_a; stop if it is empty;
+ *   votes, S, d*, the winning rate and the tie order as hvd_vpdq_align_signed's on H_r; stop if S < min_band_votes;
+ *   the frames of a and of b with a hit of H_r within slack_r of d* are round r: those of a join taken_a, those of b join
+ *   seen_b, which is never consulted as a filter;
+ *   stop when taken_a holds every frame of a.
+ * b's frames may serve any number of rounds, a's serve one: the loop is the A side, and the caller chooses the orientation.
+ * The record is hvd_vloops (above): the first eight rounds as segments, then counts only. Five consequences: (1) seg[0], q_hits
+ * and t_hits are hvd_vpdq_align_signed's for the same arguments, word for word; (2) band_votes never increases from one round to
+ * the next (H_{r+1} is a subset of H_r); (3) q_covered is the sum of q_aligned over the stored segments whenever rounds <= 8;
+ * (4) a record with rounds = 1 is hvd_vpdq_align_signed's record at max_segments = 1, the `rounds` word aside; (5) on a pair
+ * where no frame of b lies in two rounds and rounds <= 8, the segments are those of the signed rule WITH ITS b-FILTER OFF --
+ * not an identity with hvd_vpdq_align_signed itself, whose b-filter changes H_r even there.
+ * out: M hvd_vloops records in the order of the pair list. This host-buffer form rejects with HVD_ERR_ARG, before it asks for a
+ * device, a list that is not sound as a signed list, max_rounds outside [1, HVD_ALIGN_MAX_ROUNDS], min_band_votes < 1 and
+ * everything hvd_vpdq_align_signed rejects in the other arguments. */
+int hvd_vpdq_align_loops(const uint8_t* frames_q, const int64_t* offsets_q, int64_t VQ, const int32_t* positions_q,
+                         const uint8_t* frames_t, const int64_t* offsets_t, int64_t VT, const int32_t* positions_t,
+                         const uint32_t* pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                         int max_rounds, int min_band_votes, hvd_vloops* out);
 
 /* Duplicate groups with a keeper: the connected components of a pair list. The rule, integers only, one answer per
  * input. V nodes, 1 <= V < 2^31. E records of 16 bytes, E < 2^32, words 0 and 1 the two node indices u, v (hvd_pair and
@@ -947,6 +983,18 @@ int hvd_dev_vpdq_align_signed(const void* d_hashes_q, const void* d_offsets_q, i
                               const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
                               const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
                               int max_segments, int min_band_votes, void* d_scratch, size_t scratch_bytes, void* d_out);
+
+/* Device-resident alignment of looped clips (the rule: hvd_vpdq_align_loops above). The operands of hvd_dev_vpdq_align_signed
+ * with max_rounds in the place of max_segments; d_out: M hvd_vloops records, 16-byte aligned. A slot of the scratch holds the
+ * histogram and three pairs of runs of bit words (flag, taken, seen): hvd_loops_scratch_bytes(max_bins) bytes serve every pair
+ * of up to max_bins bins (<= 2^20), 0 up to HVD_ALIGN_LDS_BINS. Two launches are enqueued on the library stream: no host
+ * synchronisation, nothing allocated, nothing on the device validated. A list that is not sound as a signed list gives every
+ * pair the INT32_MIN record; broken operands give wrong records, never an access out of bounds. */
+int hvd_loops_scratch_bytes(int64_t max_bins, size_t* out_bytes);
+int hvd_dev_vpdq_align_loops(const void* d_hashes_q, const void* d_offsets_q, int64_t VQ, const void* d_pos_q,
+                             const void* d_hashes_t, const void* d_offsets_t, int64_t VT, const void* d_pos_t,
+                             const void* d_pairs, int64_t M, int max_dist, int slack, const int32_t* rates, int n_rates,
+                             int max_rounds, int min_band_votes, void* d_scratch, size_t scratch_bytes, void* d_out);
 
 /* Device-resident grouping (the rule: hvd_group_edges above). d_records: n_records records of 16 bytes, 16-byte aligned;
  * d_record_count: NULL, or the uint64 the all-pairs entries bump -- the kernels then take min(*d_record_count, n_records)

@@ -10,7 +10,7 @@ FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize --offload-arch=
 # (.cpp units go through hipcc too: csrc/Makefile)
 ( cd $SRC && /opt/rocm/bin/hipcc $FLAGS "$@" -c $UNIT -o $OUT/${UNIT%.*}_$NAME.o )
 OBJS=""
-for o in hvd_api hvd_search hvd_comm hvd_stream k_hamming k_hamming_mfma k_hamming_index k_index_order k_index_scatter k_fp4_image k_vmatch k_synth k_pdq k_pdq_dihedral k_autocrop k_autocrop_fused k_barcolor k_detail k_crops k_valign k_valign_segments k_valign_rates k_valign_rate_segments k_valign_signed k_group k_keeper k_spread k_runs; do
+for o in hvd_api hvd_search hvd_comm hvd_stream k_hamming k_hamming_mfma k_hamming_index k_index_order k_index_scatter k_fp4_image k_vmatch k_synth k_pdq k_pdq_dihedral k_autocrop k_autocrop_fused k_barcolor k_detail k_crops k_valign k_valign_segments k_valign_rates k_valign_rate_segments k_valign_signed k_valign_loops k_group k_keeper k_spread k_runs; do
   if [ "$o" = "${UNIT%.*}" ]; then OBJS="$OBJS $OUT/${o}_$NAME.o"; else OBJS="$OBJS $SRC/$o.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 $OBJS -shared -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib -o $OUT/libhvd_$NAME.so
